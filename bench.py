@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — block-bloom probe throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the probe hot path over one batch of synthetic input: Q = 4096 three-term
 And(FieldToken, FieldToken, FieldToken) queries against the filters of one 10M-row / 1 000-block file set
@@ -11,9 +11,12 @@ table and compiled programs are resident in HBM before the timed region; the sur
 Step i probes arena replica i % R (R x streamed bytes >= 2 x the 256 MiB Infinity Cache), and consecutive steps go
 to bsg_probe_many together (one dispatch covers up to --group arenas).
 
-stdout carries ONE compact JSON line (< 4 KB, strict JSON): metric, value, roofline, cpu_baseline, clock, and the
-one-number summaries of BASELINE's other configs (build = configs[2], c4 = configs[3], or_reduce = configs[4]).
-Every leg's full object goes to bench_legs.json beside this script (and a digest of each to stderr).
+A plain run sets up, warms up, times the K steps and prints ONE compact JSON line (< 4 KB, strict JSON): metric, value,
+unit, ms_per_step, dtype, config, clock.  --dump-outputs DIR then also writes the survivors of the last timed step to
+DIR/survivors.npy.  --full adds everything else the bench measures and checks: the oracle checks, the timestamped and host-gather
+passes, roofline, cpu_baseline, and the one-number summaries of BASELINE's other configs in the line (build = configs[2],
+c4 = configs[3], or_reduce = configs[4]); every leg's full object goes to bench_legs.json beside this script (and a digest
+of each to stderr).
 
 N > 1 (torchrun, one process per GPU): the headline is BASELINE configs[3] (C4: 10 000 blocks in total, block b on rank
 b % N, 8-term Or batch, strong scaling); the weak-scaling C2 run moves to bench_legs.json["c2_weak"].  The C4 curve over
@@ -121,9 +124,10 @@ def cpu_baseline(words, desc, cb, ops, poff, n_blocks, budget_s, log, terms_per_
 
 def self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it (no RANK / WORLD_SIZE in the environment): this process
-    replaces itself with `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P
-    bench.py <the same arguments>` — one rank per GPU, the same command the driver's scaling tier uses; stdout (the one JSON
-    line rank 0 prints) stays this process' stdout."""
+    runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <the
+    same arguments>` as a child — one rank per GPU, the same command the driver's scaling tier uses — and exits with its status;
+    stdout (the one JSON line rank 0 prints) is inherited.  A child, not an exec: this process has initialised the GPU
+    (device_count), and replacing such a process' program is not safe on every driver."""
     if args.gpus <= 1 or "RANK" in os.environ or "WORLD_SIZE" in os.environ:
         return
     import socket
@@ -138,9 +142,11 @@ def self_launch(args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    print("[bench] --gpus %d without a launcher: re-executing as %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
+    print("[bench] --gpus %d without a launcher: re-executing as a child process: %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    import subprocess
+    rc = subprocess.call(cmd, env=env)
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 
@@ -191,7 +197,8 @@ def headline(h, legs):
     if o:
         line["or_reduce"] = pick(o, "kernel", "kernel_ms", "filters_this_rank", "achieved", "frac", "allreduce_ms", "allreduce_gbps_in_per_gpu",
                                  "n_ranks_seen_by_rccl", "allreduce_error")
-    line["legs"] = "bench_legs.json: " + ", ".join(sorted(legs))
+    if legs:
+        line["legs"] = "bench_legs.json: " + ", ".join(sorted(legs))
     text = json.dumps(sig(jsonable(line)), allow_nan=False, separators=(",", ":"))
     if len(text) >= LINE_LIMIT:          # never let an addition silently break the driver's parser again: shed the optional objects
         for k in ("legs", "or_reduce", "roofline_scaled", "c4", "build"):
@@ -302,7 +309,17 @@ def parse_args():
     ap.add_argument("--no-concurrent", action="store_true", help="skip the concurrent_queries leg (T host threads x bsg_query)")
     ap.add_argument("--no-big-filters", action="store_true", help="skip the leg with block filters beyond the LDS budget (~1 MB each)")
     ap.add_argument("--no-single", action="store_true", help="skip the one-arena-per-launch sampling pass")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: oracle checks, timestamped / host-gather / sampling passes, roofline, cpu_baseline, "
+                         "the other legs and bench_legs.json (a plain run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the survivors of the last step as DIR/survivors.npy (float32 0/1, queries x blocks)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs writes the one-GPU headline's survivors (--gpus 1)")
+    return args
 
 
 def main():
@@ -365,17 +382,20 @@ def main():
     block_ids = np.arange(B, dtype=np.int64) * world + rank
     plan = plan_blocks(generate_blocks(block_ids, rows, 0xB100F5EA4C4, workers), args.fpr)
     log("generated %d blocks (%d entries, %.0f MB) in %.1fs" % (B, len(plan.off) - 1, len(plan.blob) / 1e6, time.time() - t0))
-    words, build = LG.build_leg(ctx, plan, B, rows, log, calls=6 if rank == 0 else 1)   # C3 (BASELINE configs[2]) through the product build path
-    if rank == 0:
-        legs["build"] = build
-        if not args.no_decode:
-            legs["decode"] = LG.decode_leg(ctx, plan, words, B, log)
     or_reduce, or_state = None, None
-    if args.or_union > 0:
-        or_reduce, or_state = LG.or_reduce_leg(ctx, plan, B, args.fpr, args.or_union, world, log)
-        legs["or_reduce"] = or_reduce
-    if rank == 0 and world == 1 and args.ingest_blocks > 0:
-        legs["ingest"] = LG.ingest_leg(ctx, min(args.ingest_blocks, B), rows, 0xB100F5EA4C4, workers, plan, words, args.fpr, log)
+    if not args.full:
+        words = ctx.build(plan.blob, plan.off, plan.fstart, plan.desc, plan.n_words)
+    else:
+        words, build = LG.build_leg(ctx, plan, B, rows, log, calls=6 if rank == 0 else 1)   # C3 (BASELINE configs[2]) through the product build path
+        if rank == 0:
+            legs["build"] = build
+            if not args.no_decode:
+                legs["decode"] = LG.decode_leg(ctx, plan, words, B, log)
+        if args.or_union > 0:
+            or_reduce, or_state = LG.or_reduce_leg(ctx, plan, B, args.fpr, args.or_union, world, log)
+            legs["or_reduce"] = or_reduce
+        if rank == 0 and world == 1 and args.ingest_blocks > 0:
+            legs["ingest"] = LG.ingest_leg(ctx, min(args.ingest_blocks, B), rows, 0xB100F5EA4C4, workers, plan, words, args.fpr, log)
 
     exprs = synth.make_queries(NQ, args.workload, seed=1234)
     terms_per_query = 8 if args.workload == "c4" else 3
@@ -395,8 +415,10 @@ def main():
         % (B, ft_bytes / 1e6, R, NQ, len(terms)))
 
     # ---- correctness spot check against the oracle (outside the timed region) ----
+    # (the batch's first probe runs in a plain run too: the device and the library are then in the state the headline has
+    # always been timed from; measured on one box: the same median either way, and no slow outliers with it)
     got = ctx.probe_batch(arenas[0], bid, NQ, B)
-    if not args.no_check and rank == 0:
+    if args.full and not args.no_check and rank == 0:
         from oracle import oracle as O
         # a RANDOM sample of the batch, checked by the oracle's tree-walking evaluator (query_exec.go:89-159 restated over the
         # expression trees: no postfix, none of the product's lowering in between)
@@ -413,8 +435,8 @@ def main():
             % (nchk, 100.0 * sum(bin(int(x)).count("1") for x in got.ravel()) / (NQ * B)))
 
     # One step = one arena probed once.  Consecutive steps are handed to bsg_probe_many together (the library covers up to
-    # --group arenas with one dispatch).  The K steps twice: bare (the headline: what a caller who asks for no timestamps pays), then
-    # the same K steps with the dispatch's own start/stop timestamps on every launch (BSG_PROBE_TIMED: hipExtLaunchKernelGGL events on
+    # --group arenas with one dispatch).  The K steps run bare (the headline: what a caller who asks for no timestamps pays); --full
+    # repeats them with the dispatch's own start/stop timestamps on every launch (BSG_PROBE_TIMED: hipExtLaunchKernelGGL events on
     # the library's stream = what a rocprofv3 kernel trace reports) — the roofline's kernel durations come from these and from the
     # sampling pass below.  A profiled dispatch costs the host ~8 us more than a bare one.
     pr = Prober(ctx, bid, world, log, barrier)
@@ -430,82 +452,89 @@ def main():
     else:
         elapsed, _ = pr.measure(make, args.steps, args.warmup, per_call, timed=False)
         clock = dict(pr.last_closing)
-        _, tm = pr.measure(make, args.steps, min(args.warmup, 4), per_call, timed=True)
-    timed_region = kstats(tm)
+    if args.dump_outputs:
+        # the survivors a caller of the timed path receives for its last step: the timed region's last call (the same arenas
+        # behind one bsg_probe_many dispatch) again, with the survivors copied to host memory this time; bitsets -> 0/1 per block
+        last = (args.steps - 1) // per_call * per_call
+        ids = [a for i in range(last, args.steps) for a in make(args.warmup + i)]
+        surv = ctx.probe_many(ids, bid, 0, NQ, [B] * len(ids))[-1]
+        bits = np.unpackbits(np.ascontiguousarray(surv).view(np.uint8), axis=1, bitorder="little")[:, :B]
+        if bits.size * 4 > 64 << 20:           # the dump stays under 64 MB: a fixed sample of the queries beyond that
+            bits = bits[np.sort(np.random.default_rng(20261016).choice(NQ, size=(64 << 20) // (4 * B), replace=False))]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "survivors.npy"), bits.astype(np.float32))
+        log("survivors of the last timed step (%d queries x %d blocks) -> %s" % (NQ, B, os.path.join(args.dump_outputs, "survivors.npy")))
 
-    # the same steps with the host-side gather inside the timed region: survivors of every step DMA-ed into a shared,
-    # page-locked host segment (a ring: only the last calls' survivors are kept) ...
-    wps = NQ * ((B + 63) // 64)
-    ring_steps = min(max(args.steps, 1), 2 * per_call)
-    row_words = wps * ring_steps
-    sh = SharedHost(ctx, row_words * 8 + NQ * 4 * ring_steps, rank, world, "c2")
-    h_elapsed, _ = pr.measure(make, args.steps, min(args.warmup, 4), per_call, timed=False, out=Ring(sh.mine[:row_words]), words_per_step=wps)
-    if rank == 0 and not args.no_check and not np.array_equal(sh.part(0)[:wps].reshape(NQ, -1), got):
-        sys.exit("survivors delivered to the shared host segment differ from the direct probe")
-    page_locked = sh.registered
-    # ... and as survivor ROWS (bsg_probe_many_rows): a 4-byte header per query + block ids / words only where the row needs them,
-    # written by the device into the same page-locked segment — the north star's "host-side gather of surviving block IDs"
-    r_elapsed = rows_tags = None
-    if page_locked:
-        from bloomsearch_amd.gpu import rows_to_dense
-        hdr_ring = sh.mine[row_words:].view(np.uint32)[: NQ * ring_steps]
-        r_elapsed, _ = pr.measure(make, args.steps, min(args.warmup, 4), per_call, timed=False, out=Ring(sh.mine[:row_words]), words_per_step=wps,
-                                  hdr=Ring(hdr_ring), hdr_per_step=NQ)
-        if rank == 0:
-            h0 = sh.part(0)[row_words:].view(np.uint8)[:NQ] if C.ROWS_PACKED else sh.part(0)[row_words:].view(np.uint32)[:NQ]      # (packed: byte headers)
-            if not args.no_check and not np.array_equal(rows_to_dense(h0, sh.part(0)[:wps], B, packed=C.ROWS_PACKED), got):
-                sys.exit("survivor rows delivered to the shared host segment do not expand to the direct probe's bitsets")
-            rows_tags = [int(x) for x in np.bincount(h0 >> (6 if C.ROWS_PACKED else 30), minlength=4)]
-    sh.close()
+    if args.full:
+        if not args.events_in_headline:
+            _, tm = pr.measure(make, args.steps, min(args.warmup, 4), per_call, timed=True)
+        timed_region = kstats(tm)
 
-    # ---- kernel sampling beyond the timed region: the driver's --steps may cover a single dispatch, the number of record
-    # must not depend on it.  Same launch shape (G0 arenas per dispatch, rotating replicas), every dispatch timestamped.
-    samples, all_t = {}, tm
-    if args.samples > 0:
-        _, t_s = pr.measure(make, args.samples * G0, G0, G0)      # n dispatches of each kernel, one call (one group) each
-        samples, all_t = kstats(t_s), merge_timing(t_s, tm)
-    allk = kstats(all_t)
+        # the same steps with the host-side gather inside the timed region: survivors of every step DMA-ed into a shared,
+        # page-locked host segment (a ring: only the last calls' survivors are kept) ...
+        wps = NQ * ((B + 63) // 64)
+        ring_steps = min(max(args.steps, 1), 2 * per_call)
+        row_words = wps * ring_steps
+        sh = SharedHost(ctx, row_words * 8 + NQ * 4 * ring_steps, rank, world, "c2")
+        h_elapsed, _ = pr.measure(make, args.steps, min(args.warmup, 4), per_call, timed=False, out=Ring(sh.mine[:row_words]), words_per_step=wps)
+        if rank == 0 and not args.no_check and not np.array_equal(sh.part(0)[:wps].reshape(NQ, -1), got):
+            sys.exit("survivors delivered to the shared host segment differ from the direct probe")
+        page_locked = sh.registered
+        # ... and as survivor ROWS (bsg_probe_many_rows): a 4-byte header per query + block ids / words only where the row needs them,
+        # written by the device into the same page-locked segment — the north star's "host-side gather of surviving block IDs"
+        r_elapsed = rows_tags = None
+        if page_locked:
+            from bloomsearch_amd.gpu import rows_to_dense
+            hdr_ring = sh.mine[row_words:].view(np.uint32)[: NQ * ring_steps]
+            r_elapsed, _ = pr.measure(make, args.steps, min(args.warmup, 4), per_call, timed=False, out=Ring(sh.mine[:row_words]), words_per_step=wps,
+                                      hdr=Ring(hdr_ring), hdr_per_step=NQ)
+            if rank == 0:
+                h0 = sh.part(0)[row_words:].view(np.uint8)[:NQ] if C.ROWS_PACKED else sh.part(0)[row_words:].view(np.uint32)[:NQ]      # (packed: byte headers)
+                if not args.no_check and not np.array_equal(rows_to_dense(h0, sh.part(0)[:wps], B, packed=C.ROWS_PACKED), got):
+                    sys.exit("survivor rows delivered to the shared host segment do not expand to the direct probe's bitsets")
+                rows_tags = [int(x) for x in np.bincount(h0 >> (6 if C.ROWS_PACKED else 30), minlength=4)]
+        sh.close()
 
-    if not args.no_single and world == 1:
-        ctx.set_probe_group(1)
-        _, t1 = pr.measure(make, 64, 8, 64, nofuse=True)
-        ctx.set_probe_group(args.group)
-        single = kstats(t1)
-        legs["roofline_single_launch"] = dict(single.get(probe_kernel, {}), bound="hbm", kernel=probe_kernel, peak=HBM_PEAK_GBPS, unit="GB/s",
-                                              eval_kernel_ms=single.get("k_eval_programs", {}).get("kernel_ms"),
-                                              note="one 1 000-block arena (35 MB) per dispatch: ~half of such a launch is dispatch ramp + completion")
-    if rank == 0 and world == 1:
-        if not args.no_q1:
-            legs["q1"] = LG.q1_latency(ctx, arenas[0], B, None, log)
-        if not args.no_concurrent:
-            legs["concurrent_queries"] = LG.concurrent_queries_leg(ctx, arenas, B, exprs, got, log)
-    if args.scaled > 1 and world == 1:
-        for a in arenas[1:]:
-            ctx.arena_free(a)
-        arenas = arenas[:1]
-        legs["roofline_scaled"] = dict(LG.scaled_leg(ctx, pr, args, plan, words, B, NQ, ft_bytes, len(terms), terms_per_query, log),
-                                       bound="hbm", kernel=probe_kernel, peak=HBM_PEAK_GBPS, unit="GB/s",
-                                       note="C2' of SURVEY 8d: same filters replicated x%d at distinct addresses, one arena, one launch" % args.scaled)
+        # ---- kernel sampling beyond the timed region: the driver's --steps may cover a single dispatch, the number of record
+        # must not depend on it.  Same launch shape (G0 arenas per dispatch, rotating replicas), every dispatch timestamped.
+        samples, all_t = {}, tm
+        if args.samples > 0:
+            _, t_s = pr.measure(make, args.samples * G0, G0, G0)      # n dispatches of each kernel, one call (one group) each
+            samples, all_t = kstats(t_s), merge_timing(t_s, tm)
+        allk = kstats(all_t)
+
+        if not args.no_single and world == 1:
+            ctx.set_probe_group(1)
+            _, t1 = pr.measure(make, 64, 8, 64, nofuse=True)
+            ctx.set_probe_group(args.group)
+            single = kstats(t1)
+            legs["roofline_single_launch"] = dict(single.get(probe_kernel, {}), bound="hbm", kernel=probe_kernel, peak=HBM_PEAK_GBPS, unit="GB/s",
+                                                  eval_kernel_ms=single.get("k_eval_programs", {}).get("kernel_ms"),
+                                                  note="one 1 000-block arena (35 MB) per dispatch: ~half of such a launch is dispatch ramp + completion")
+        if rank == 0 and world == 1:
+            if not args.no_q1:
+                legs["q1"] = LG.q1_latency(ctx, arenas[0], B, None, log)
+            if not args.no_concurrent:
+                legs["concurrent_queries"] = LG.concurrent_queries_leg(ctx, arenas, B, exprs, got, log)
+        if args.scaled > 1 and world == 1:
+            for a in arenas[1:]:
+                ctx.arena_free(a)
+            arenas = arenas[:1]
+            legs["roofline_scaled"] = dict(LG.scaled_leg(ctx, pr, args, plan, words, B, NQ, ft_bytes, len(terms), terms_per_query, log),
+                                           bound="hbm", kernel=probe_kernel, peak=HBM_PEAK_GBPS, unit="GB/s",
+                                           note="C2' of SURVEY 8d: same filters replicated x%d at distinct addresses, one arena, one launch" % args.scaled)
     for a in arenas:
         ctx.arena_free(a)
     arenas = []
-    if rank == 0 and world == 1 and not args.no_big_filters:
+    if args.full and rank == 0 and world == 1 and not args.no_big_filters:
         legs["big_filters"] = LG.big_filter_leg(ctx, args, log)
     c4 = None
-    if args.c4_files > 0:
+    if args.c4_files > 0 and (args.full or world > 1):        # (at N > 1 the C4 leg is the headline)
         c4 = legs["c4"] = LG.c4_leg(ctx, args, rank, world, workers, log, barrier, headline=world > 1)
 
     probes_per_step = NQ * B * terms_per_query * world
     h = None
     if rank == 0:
-        # roofline of the dominant kernel of the timed region: algorithmic bytes per launch (streaming regime) =
-        # every referenced bitset of the launch's arenas once + the term table; over the mean of the dispatch's own
-        # start/stop timestamps, timed region and sampling pass together (same launch shape).
-        dom = dominant_kernel(tm, probe_kernel)
-        k = allk.get(dom) or {}
-        traffic, traffic_src = LG.traffic_from_profiles(dom, k, args, B)
-        copy_gbps = C.measured_copy_gbps(log)
-        delivered = probes_per_step * args.steps / min(h_elapsed, r_elapsed or h_elapsed)
         h = {"metric": "block-bloom probes/sec", "value": probes_per_step * args.steps / elapsed, "unit": "probes/s", "n_gpus": world,
              "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
              "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
@@ -515,41 +544,52 @@ def main():
                                        "8-term Or(FieldToken)" if args.workload == "c4" else "3-term And(FieldToken)", args.fpr, R, G0),
                         "blocks_per_gpu": B, "queries": NQ, "distinct_terms": int(len(terms)), "probes_per_step": probes_per_step,
                         "sharding": "round-robin blocks, no collective"},
-             "roofline": {"bound": "hbm", "kernel": dom, "achieved": k.get("achieved"), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                          "frac": k.get("frac"), "traffic": traffic, "traffic_source": traffic_src,
-                          "algorithmic_bytes_per_launch": k.get("algorithmic_bytes_per_launch"), "kernel_ms": k.get("kernel_ms"),
-                          "samples": k.get("samples"), "arenas_per_launch": k.get("arenas_per_launch"), "copy_gbps": copy_gbps,
-                          "frac_of_copy": (k.get("achieved") / copy_gbps) if (copy_gbps and k.get("achieved")) else None},
-             "clock": dict(clock, barrier="host flags in shared memory after each rank's device synchronize; closing barrier INSIDE value/ms_per_step"),
-             "value_survivors_delivered_to_host": delivered,
-             "survivors_note": "value: survivor bitsets stay in HBM; value_survivors_delivered_to_host: the same K steps with every query's "
-                               "survivor rows (bsg_probe_many_rows) written into page-locked host memory, PCIe-inclusive"}
-        legs["c2_probe"] = {"timed_region": timed_region, "sampling_pass": samples, "all": allk, "clock_note": C.CLOCK_NOTE,
-                            "valu_issue": LG.valu_issue_from_profiles(dom, k, B) if dom == "k_probe_terms_many" else None,
-                            "host_gather": {"ms_per_step": h_elapsed / args.steps * 1e3, "value": probes_per_step * args.steps / h_elapsed,
-                                            "survivor_bytes_per_step_per_gpu": wps * 8, "page_locked": page_locked,
-                                            "rows": None if r_elapsed is None else {
-                                                "api": "bsg_probe_many_rows" + (" (BSG_PROBE_ROWS_PACKED)" if C.ROWS_PACKED else ""), "ms_per_step": r_elapsed / args.steps * 1e3,
-                                                "value": probes_per_step * args.steps / r_elapsed, "rows_by_tag_none_all_list_dense": rows_tags}}}
+             "clock": dict(clock, barrier="host flags in shared memory after each rank's device synchronize; closing barrier INSIDE value/ms_per_step")}
+        copy_gbps = None
+        if args.full:
+            # roofline of the dominant kernel of the timed region: algorithmic bytes per launch (streaming regime) =
+            # every referenced bitset of the launch's arenas once + the term table; over the mean of the dispatch's own
+            # start/stop timestamps, timed region and sampling pass together (same launch shape).
+            dom = dominant_kernel(tm, probe_kernel)
+            k = allk.get(dom) or {}
+            traffic, traffic_src = LG.traffic_from_profiles(dom, k, args, B)
+            copy_gbps = C.measured_copy_gbps(log)
+            delivered = probes_per_step * args.steps / min(h_elapsed, r_elapsed or h_elapsed)
+            h.update({"roofline": {"bound": "hbm", "kernel": dom, "achieved": k.get("achieved"), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                   "frac": k.get("frac"), "traffic": traffic, "traffic_source": traffic_src,
+                                   "algorithmic_bytes_per_launch": k.get("algorithmic_bytes_per_launch"), "kernel_ms": k.get("kernel_ms"),
+                                   "samples": k.get("samples"), "arenas_per_launch": k.get("arenas_per_launch"), "copy_gbps": copy_gbps,
+                                   "frac_of_copy": (k.get("achieved") / copy_gbps) if (copy_gbps and k.get("achieved")) else None},
+                      "value_survivors_delivered_to_host": delivered,
+                      "survivors_note": "value: survivor bitsets stay in HBM; value_survivors_delivered_to_host: the same K steps with every query's "
+                                        "survivor rows (bsg_probe_many_rows) written into page-locked host memory, PCIe-inclusive"})
+            legs["c2_probe"] = {"timed_region": timed_region, "sampling_pass": samples, "all": allk, "clock_note": C.CLOCK_NOTE,
+                                "valu_issue": LG.valu_issue_from_profiles(dom, k, B) if dom == "k_probe_terms_many" else None,
+                                "host_gather": {"ms_per_step": h_elapsed / args.steps * 1e3, "value": probes_per_step * args.steps / h_elapsed,
+                                                "survivor_bytes_per_step_per_gpu": wps * 8, "page_locked": page_locked,
+                                                "rows": None if r_elapsed is None else {
+                                                    "api": "bsg_probe_many_rows" + (" (BSG_PROBE_ROWS_PACKED)" if C.ROWS_PACKED else ""), "ms_per_step": r_elapsed / args.steps * 1e3,
+                                                    "value": probes_per_step * args.steps / r_elapsed, "rows_by_tag_none_all_list_dense": rows_tags}}}
         if world > 1 and c4:
             # N > 1: the headline is BASELINE configs[3] — C4, STRONG scaling (10 000 blocks in total, block b on rank b % N, the 8-term
             # Or batch, exactly --steps timed steps); the weak-scaling C2 figures above move to the legs.
             ck = (c4.get("kernels") or {}).get(c4.get("dominant_kernel")) or {}
             legs["c2_weak"] = {key: h[key] for key in ("value", "value_survivors_delivered_to_host", "steps", "warmup", "ms_per_step", "clock",
-                                                       "scaling", "config", "roofline")}
-            h.update({"value": c4["value"], "value_survivors_delivered_to_host": (c4["host_gather"].get("rows") or c4["host_gather"])["value"],
-                      "steps": c4["steps"], "warmup": c4["warmup"], "ms_per_step": c4["ms_per_step"], "scaling": "strong",
+                                                       "scaling", "config", "roofline") if key in h}
+            h.update({"value": c4["value"], "steps": c4["steps"], "warmup": c4["warmup"], "ms_per_step": c4["ms_per_step"], "scaling": "strong",
                       "clock": dict(c4["clock"], barrier=h["clock"]["barrier"]),
                       "config": {"workload": c4["workload"] + "; survivors device-resident", "blocks_total": c4["blocks_total"], "queries": NQ,
                                  "probes_per_step": c4["probes_per_step"], "sharding": "block b -> rank b % N, no collective",
-                                 "curve": "strong scaling of BASELINE configs[3]: compare with c4.value of the N = 1 line"},
-                      "roofline": {"bound": "hbm", "kernel": c4.get("dominant_kernel"), "achieved": ck.get("achieved"), "peak": HBM_PEAK_GBPS,
-                                   "unit": "GB/s", "frac": ck.get("frac"), "traffic": None,
-                                   "algorithmic_bytes_per_launch": ck.get("algorithmic_bytes_per_launch"), "kernel_ms": ck.get("kernel_ms"),
-                                   "samples": ck.get("samples"), "arenas_per_launch": ck.get("arenas_per_launch"), "copy_gbps": copy_gbps,
-                                   "note": "rank 0's dispatches of the timed region; every rank's kernel time: bench_legs.json c4.per_rank"}})
+                                 "curve": "strong scaling of BASELINE configs[3]: compare with c4.value of the N = 1 line"}})
+            if args.full:
+                h.update({"value_survivors_delivered_to_host": (c4["host_gather"].get("rows") or c4["host_gather"])["value"],
+                          "roofline": {"bound": "hbm", "kernel": c4.get("dominant_kernel"), "achieved": ck.get("achieved"), "peak": HBM_PEAK_GBPS,
+                                       "unit": "GB/s", "frac": ck.get("frac"), "traffic": None,
+                                       "algorithmic_bytes_per_launch": ck.get("algorithmic_bytes_per_launch"), "kernel_ms": ck.get("kernel_ms"),
+                                       "samples": ck.get("samples"), "arenas_per_launch": ck.get("arenas_per_launch"), "copy_gbps": copy_gbps,
+                                       "note": "rank 0's dispatches of the timed region; every rank's kernel time: bench_legs.json c4.per_rank"}})
             h["clock"].pop("note", None)
-        if args.cpu_budget > 0 and world == 1:
+        if args.full and args.cpu_budget > 0 and world == 1:
             base, cpu_out, nq = cpu_baseline(words, plan.desc, cb, ops, poff, B, args.cpu_budget, log, terms_per_query)
             if not args.no_check and not np.array_equal(cpu_out, got[:nq]):
                 sys.exit("CPU baseline survivors differ from the GPU's")
@@ -562,9 +602,13 @@ def main():
 
     def emit():
         if rank == 0 and emitted.acquire(blocking=False):
-            write_legs(legs, log)
-            print(headline(h, legs), file=json_out, flush=True)
-    closing_legs(emit, legs, ctx, args, rank, world, local_rank, plan, words, block_ids, rows, terms, ops, poff, got, or_reduce, or_state, log)
+            if args.full:
+                write_legs(legs, log)
+            print(headline(h, legs if args.full else {}), file=json_out, flush=True)
+    if args.full:
+        closing_legs(emit, legs, ctx, args, rank, world, local_rank, plan, words, block_ids, rows, terms, ops, poff, got, or_reduce, or_state, log)
+    else:
+        emit()
     C.stop_pool()
     barrier.close()
     ctx.batch_free(bid)

@@ -1,5 +1,8 @@
 """bench.py as the driver calls it.
 
+A plain run (no --full) prints the headline only: no bench_legs.json, and with --dump-outputs DIR the survivors of the last
+timed step in DIR/survivors.npy.  Everything below that reads legs, roofline or cpu_baseline runs with --full.
+
 `python bench.py --gpus N ...` WITHOUT a launcher around it must start its own N ranks (torch.distributed.run, one rank per
 GPU) and print ONE compact JSON line (< 4 KB, strict JSON) whose headline at N > 1 is BASELINE configs[3] (C4, strong scaling); every leg's
 full object — the weak-scaling C2 run under `c2_weak` among them — goes to bench_legs.json.  On a one-GPU box the ranks share device 0 (BSG_BENCH_SHARE_GPU=1: a functional check of every N > 1 host
@@ -38,6 +41,11 @@ def run_bench(extra, env_extra=None, timeout=600):
     # the driver's parser gave up on round 5's 25 KB line: the headline is compact, strict JSON (no NaN / Infinity)
     assert len(lines[0]) < 4096, len(lines[0])
     out = json.loads(lines[0], parse_constant=fail_constant)
+    if "--full" not in extra:
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "clock"):
+            assert key in out, key
+        assert not os.path.exists(legs_path), "a plain run writes no bench_legs.json"
+        return out, None, p.stderr
     legs = json.load(open(legs_path), parse_constant=fail_constant)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
                 "config", "roofline", "clock", "value_survivors_delivered_to_host"):
@@ -50,7 +58,7 @@ def run_bench(extra, env_extra=None, timeout=600):
 
 @pytest.mark.gpu
 def test_bench_gpus_2_launches_its_own_ranks_and_reports_c4_strong_scaling():
-    out, legs, err = run_bench(["--gpus", "2", "--steps", "20", "--warmup", "5"] + SMALL, {"BSG_BENCH_SHARE_GPU": "1", "BSG_BENCH_RCCL_TIMEOUT": "60"})
+    out, legs, err = run_bench(["--full", "--gpus", "2", "--steps", "20", "--warmup", "5"] + SMALL, {"BSG_BENCH_SHARE_GPU": "1", "BSG_BENCH_RCCL_TIMEOUT": "60"})
     assert "re-executing as" in err
     assert out["n_gpus"] == 2 and out["steps"] == 20 and out["warmup"] == 5
     assert out["scaling"] == "strong" and out["config"]["workload"].startswith("C4")
@@ -77,7 +85,7 @@ def test_bench_gpus_2_launches_its_own_ranks_and_reports_c4_strong_scaling():
 
 @pytest.mark.gpu
 def test_bench_gpus_1_keeps_c2_as_the_headline():
-    out, legs, err = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"] + SMALL)
+    out, legs, err = run_bench(["--full", "--gpus", "1", "--steps", "20", "--warmup", "5"] + SMALL)
     assert "re-executing" not in err
     assert out["n_gpus"] == 1 and out["scaling"] == "weak" and out["config"]["workload"].startswith("C2")
     assert legs["c4"]["scaling"] == "strong" and legs["c4"]["n_gpus"] == 1 and "c2_weak" not in legs
@@ -91,9 +99,9 @@ def test_bench_gpus_1_keeps_c2_as_the_headline():
 
 @pytest.mark.gpu
 def test_bench_line_as_the_driver_runs_it_is_compact_and_carries_roofline_and_cpu_baseline():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` — the driver's exact command, every leg on: one line under 4 KB of strict
+    """`python bench.py --full --gpus 1 --steps 20 --warmup 5` — the driver's exact command with every leg on: one line under 4 KB of strict
     JSON with roofline.frac and cpu_baseline.value; cores = the CPUs the process may use, not the box's logical count."""
-    out, legs, _ = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"], timeout=1500)
+    out, legs, _ = run_bench(["--full", "--gpus", "1", "--steps", "20", "--warmup", "5"], timeout=1500)
     assert out["steps"] == 20 and out["warmup"] == 5
     assert 0 < out["roofline"]["frac"] <= 1 and out["roofline"]["kernel_ms"] > 0
     cb = out["cpu_baseline"]
@@ -103,3 +111,30 @@ def test_bench_line_as_the_driver_runs_it_is_compact_and_carries_roofline_and_cp
     assert (cb["cores"], cb["logical_cpus"]) == effective_cpus()
     for leg in ("build", "c4", "decode", "ingest", "or_reduce", "q1", "concurrent_queries", "roofline_scaled", "big_filters", "c2_probe"):
         assert leg in legs, leg
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_the_last_steps_survivors(tmp_path):
+    """A plain run: the headline of exactly --steps timed steps, and --dump-outputs writes the survivors of the last one as 0/1 per
+    (query, block), float32 — equal to the oracle's tree-walking evaluator over the same seeded blocks and queries."""
+    import numpy as np
+    out, _, err = run_bench(["--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(tmp_path)] + SMALL)
+    assert out["steps"] == 7 and out["warmup"] == 3 and out["n_gpus"] == 1 and out["dtype"] == "u64" and out["higher_is_better"] is True
+    assert out["metric"] == "block-bloom probes/sec" and out["unit"] == "probes/s" and out["config"]["workload"].startswith("C2")
+    assert out["value"] > 0 and abs(out["value"] - out["config"]["probes_per_step"] / (out["ms_per_step"] * 1e-3)) < 1e-4 * out["value"]
+    assert "roofline" not in out and "cpu_baseline" not in out and "c4" not in out and "build" not in out
+    assert "7 steps:" in err
+    got = np.load(tmp_path / "survivors.npy")
+    assert got.dtype == np.float32 and got.shape == (512, 128) and set(np.unique(got)) <= {0.0, 1.0}
+    sys.path.insert(0, ROOT)
+    from benchlib.common import generate_blocks
+    from bloomsearch_amd import synth
+    from bloomsearch_amd.arena import plan_blocks
+    from oracle import oracle as O
+    plan = plan_blocks(generate_blocks(np.arange(128), 1000, 0xB100F5EA4C4, 1), 0.001)
+    words = O.build_many(plan.blob, plan.off, plan.fstart, plan.desc.view(O.DESC_DTYPE), plan.n_words)
+    exprs = synth.make_queries(512, "c2", seed=1234)
+    sel = np.random.default_rng(7).choice(512, size=32, replace=False)
+    want = O.survivors_tree(words, plan.desc.view(O.DESC_DTYPE), [exprs[int(i)] for i in sel])
+    want_bits = np.unpackbits(np.ascontiguousarray(want).view(np.uint8), axis=1, bitorder="little")[:, :128]
+    assert np.array_equal(got[sel], want_bits.astype(np.float32))

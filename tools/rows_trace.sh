@@ -5,7 +5,7 @@ REPO=$(pwd)
 export TMPDIR=/tmp
 OUT=/tmp/rows_trace
 rm -rf $OUT
-(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $OUT -- python $REPO/bench.py --steps 20 --warmup 5 --no-big-filters > /tmp/rows_trace.json 2> /tmp/rows_trace.err) || { tail -5 /tmp/rows_trace.err; exit 1; }
+(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $OUT -- python $REPO/bench.py --full --steps 20 --warmup 5 --no-big-filters > /tmp/rows_trace.json 2> /tmp/rows_trace.err) || { tail -5 /tmp/rows_trace.err; exit 1; }
 python - <<'PY'
 import csv, glob, collections
 f = glob.glob('/tmp/rows_trace/**/*kernel_trace.csv', recursive=True)[0]

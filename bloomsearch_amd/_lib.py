@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(HERE, "csrc", "libbloomgpu.so")
 # status codes (bloomgpu.h)
 BSG_OK, BSG_E_INVALID, BSG_E_HIP, BSG_E_NOMEM, BSG_E_NOTFOUND, BSG_E_UNSUPPORTED, BSG_E_NODEVICE = 0, -1, -2, -3, -4, -5, -6
 KIND_FIELD, KIND_TOKEN, KIND_FIELD_TOKEN = 0, 1, 2
+KIND_FIELD_REGEX = 3          # row matcher only (bsg_match_rows_regex)
 OP_TERM, OP_AND, OP_OR, OP_TRUE, OP_FALSE = 0, 1, 2, 3, 4
 PROBE_ASYNC, PROBE_TIMED, PROBE_NOFUSE, PROBE_ROWS_PACKED = 1, 2, 4, 8
 INGEST_TRUSTED_JSON = 1
@@ -79,7 +80,7 @@ EXPORTS = [
     "bsg_ingest_rows", "bsg_ingest_fallback_rows", "bsg_ingest_add_entries", "bsg_ingest_finish", "bsg_ingest_build",
     "bsg_ingest_stats_read", "bsg_ingest_free", "bsg_ingest_build_sections",
     "bsg_sections_size", "bsg_build_sections", "bsg_last_encode_ms",
-    "bsg_match_rows", "bsg_last_match_ms", "bsg_pinned_alloc", "bsg_pinned_free", "bsg_host_register", "bsg_host_unregister",
+    "bsg_match_rows", "bsg_match_rows_regex", "bsg_last_match_ms", "bsg_pinned_alloc", "bsg_pinned_free", "bsg_host_register", "bsg_host_unregister",
 ]
 
 _lib = None
@@ -170,6 +171,7 @@ def load():
     L.bsg_build_sections.argtypes = [vp, vp, vp, u32, vp, vp, u32, u64, vp, u64, vp]
     L.bsg_last_encode_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.bsg_match_rows.argtypes = [vp, vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, vp, u32, C.POINTER(u32)]
+    L.bsg_match_rows_regex.argtypes = L.bsg_match_rows.argtypes
     L.bsg_last_match_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.bsg_pinned_alloc.argtypes = [vp, u64, C.POINTER(vp)]
     L.bsg_pinned_free.argtypes = [vp, vp]

@@ -13,6 +13,7 @@
 #include "direct.hip.h"
 #include "match.hip.h"
 #include "host/combiner_sync.hpp"
+#include "host/regex_dfa.hpp"  // FieldRegex patterns -> the DFA tables k_match_rows_regex steps
 #include "host/text.hpp"   // the host walker's Unicode tables: the device defers to the same data
 #include <hip/hip_ext.h>
 
@@ -703,6 +704,8 @@ int32_t bsg_open(const int32_t *device_ids, int32_t n_devices, bsg_ctx **out_ctx
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_build), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_build_sets), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget - bsg::kSetListBytes));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_union_partitions), hipFuncAttributeMaxDynamicSharedMemorySize, bsg::kPartLdsBytes));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_match_rows_regex), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    bsg::kMatchLdsBytes + bsg::kRxLdsCap));
 
         ctx->devs.push_back(std::move(d));
     }

@@ -53,6 +53,10 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // true: the final row test of the surviving blocks (matchRowBytes, query_exec.go:751) runs on the device too
     // (bsg_match_rows); rows it hands back, and expressions beyond its limits, go through the host matcher.
     bool device_match = false;
+    // true (with device_match): queries whose regex patterns all compile to the device's byte DFAs (regex_dfa.hpp) are
+    // matched bloom AND regex by ONE bsg_match_rows_regex call, and the rows it hands back by the host matcher with the same
+    // DFAs (RE2 semantics on both sides); other regex queries keep the std::regex path below.  Off by default.
+    bool device_regex = false;
 };
 
 struct DataBlock {
@@ -317,7 +321,9 @@ public:
         const int64_t probe_share = candidate_blocks ? std::max<int64_t>(1, probe_ns / (int64_t)candidate_blocks) : 0;
         RowMatcher matcher(row_expr);
         RegexRowMatcher regex_matcher(regex);
-        if (!regex_matcher.valid()) return fail(kErrInvalidQuery, "regex pattern does not compile");
+        RegexRowMatcher regex_dfa(cfg_.device_regex && cfg_.device_match ? regex : nullptr, true);
+        const bool regex_on_device = regex && cfg_.device_regex && cfg_.device_match && regex_dfa.valid();
+        if (!regex_on_device && !regex_matcher.valid()) return fail(kErrInvalidQuery, "regex pattern does not compile");
         // the scan list: every row of every block that survived both stages, in file / block order
         std::vector<const std::string *> scan;
         std::vector<size_t> scanned_stats;          // block_stats entries of the scanned blocks (for the scan's time share)
@@ -353,13 +359,18 @@ public:
             }
         }
         std::vector<uint8_t> hit(scan.size(), 0);
-        bool on_device = false;
-        if (cfg_.device_match && row_expr && !scan.empty()) {
+        bool on_device = false, regex_done = false;
+        if (regex_on_device && !scan.empty()) {
+            if (int32_t rc = match_rows_device_regex(row_expr, *regex, scan, matcher, regex_dfa, hit, regex_done)) return rc;
+            if (!regex_done && !regex_matcher.valid()) return fail(kErrInvalidQuery, "regex pattern does not compile");
+        }
+        on_device = regex_done;
+        if (!on_device && cfg_.device_match && row_expr && !scan.empty()) {
             if (int32_t rc = match_rows_device(row_expr, scan, matcher, hit, on_device)) return rc;
         }
         if (!on_device)
             for (size_t i = 0; i < scan.size(); ++i) hit[i] = matcher.match(*scan[i]);
-        if (regex) {
+        if (regex && !regex_done) {
             // the regex patterns only run on rows the bloom tree kept AND — when the device matcher is on — on rows whose
             // guard fields exist: the field guard the probe already used, evaluated per row by k_match_rows.  Only when every
             // regex node translated into the guard (regex_guard_is_exact): the reference prunes files and blocks with it, never rows
@@ -617,6 +628,63 @@ private:
 
     // matchRowBytes for the whole scan list in one bsg_match_rows call.  on_device stays false (and the host matcher
     // takes over) when the expression is beyond the device matcher's limits.
+    // compileRowMatcher's root And(bloom root, regex root) (row_matcher.go:353-368) as one bsg_match_rows_regex program; the regex
+    // side lowered by compileRegexExpression's rules (row_matcher.go:440-480).  on_device stays false when the library answers
+    // BSG_E_UNSUPPORTED (too many conditions, tables over its LDS cap): the caller takes the host path.
+    static void lower_regex(const RegexExpression &e, MatcherProgram &mp)
+    {
+        switch (e.type) {
+        case RegexType::Condition:
+            if (!e.has_condition) { mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0)); return; }
+            if (e.field.empty()) { mp.prog_ops.push_back(BSG_OP(BSG_OP_FALSE, 0)); return; }
+            mp.prog_ops.push_back(BSG_OP(BSG_OP_TERM, (uint32_t)mp.kinds.size()));
+            mp.kinds.push_back(BSG_KIND_FIELD_REGEX);
+            mp.fields.push_back(e.field);
+            mp.tokens.push_back(e.pattern);
+            return;
+        case RegexType::And:
+        case RegexType::Or:
+            if (e.children.empty()) { mp.prog_ops.push_back(BSG_OP(e.type == RegexType::And ? BSG_OP_TRUE : BSG_OP_FALSE, 0)); return; }
+            for (auto &c : e.children) lower_regex(c, mp);
+            mp.prog_ops.push_back(BSG_OP(e.type == RegexType::And ? BSG_OP_AND : BSG_OP_OR, (uint32_t)e.children.size()));
+            return;
+        default:
+            mp.prog_ops.push_back(BSG_OP(BSG_OP_FALSE, 0));
+        }
+    }
+    int32_t match_rows_device_regex(const BloomExpression *expr, const RegexExpression &regex, const std::vector<const std::string *> &scan,
+                                    RowMatcher &host_matcher, RegexRowMatcher &host_regex, std::vector<uint8_t> &hit, bool &on_device)
+    {
+        MatcherProgram mp(expr);
+        if (!expr) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
+        lower_regex(regex, mp);
+        mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 2));
+        std::vector<uint8_t> cbytes;
+        std::vector<uint32_t> coff{0};
+        for (size_t c = 0; c < mp.kinds.size(); ++c) {
+            cbytes.insert(cbytes.end(), mp.fields[c].begin(), mp.fields[c].end()); coff.push_back((uint32_t)cbytes.size());
+            cbytes.insert(cbytes.end(), mp.tokens[c].begin(), mp.tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
+        }
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> row_off{0};
+        for (const std::string *r : scan) { bytes.insert(bytes.end(), r->begin(), r->end()); row_off.push_back(bytes.size()); }
+        std::vector<uint64_t> bits((scan.size() + 63) / 64);
+        std::vector<uint32_t> fb(scan.size());
+        uint32_t n_fb = 0;
+        const int32_t rc = bsg_match_rows_regex(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
+                                                mp.kinds.data(), (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(),
+                                                bits.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
+        if (rc == BSG_E_UNSUPPORTED) return kEngineOk;
+        if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
+        for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
+        for (uint32_t i = 0; i < n_fb; ++i) {
+            const std::string &row = *scan[fb[i]];
+            hit[fb[i]] = host_matcher.match(row) && host_regex.match(row);
+        }
+        on_device = true;
+        return kEngineOk;
+    }
+
     int32_t match_rows_device(const BloomExpression *expr, const std::vector<const std::string *> &scan, RowMatcher &host_matcher,
                               std::vector<uint8_t> &hit, bool &on_device)
     {

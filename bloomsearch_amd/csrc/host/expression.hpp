@@ -20,6 +20,7 @@
 
 #include "bloomgpu.h"
 #include "json.hpp"
+#include "regex_dfa.hpp"
 #include "text.hpp"
 #include "walker.hpp"
 
@@ -214,9 +215,12 @@ inline bool and_bloom_queries(const BloomExpression *left, const BloomExpression
 // "regex pattern does not compile" where the reference accepts them: \\pL / \\p{..}, (?s) (?m) (?U) and inline flags other than
 // a leading (?i), named groups (?P<n>..), \\Q..\\E, \\z, \\C.  A Go host keeps its own regexp; this mirror exists for the parity
 // tests of the DEVICE path (the field guard and the bloom side of regex queries), which use patterns inside the subset.
+// dfa = true: the patterns are compiled to the device row matcher's byte DFAs (regex_dfa.hpp) instead — RE2 MatchString
+// semantics for its subset; valid() is false when a pattern is outside it.  The engine uses this form for the rows the device
+// hands back when DeviceRegex is on, so that device rows and host rows answer alike.
 class RegexRowMatcher {
 public:
-    explicit RegexRowMatcher(const RegexExpression *e)
+    explicit RegexRowMatcher(const RegexExpression *e, bool dfa = false) : dfa_(dfa)
     {
         if (!e) return;
         root_ = *e; has_root_ = true;
@@ -233,7 +237,9 @@ public:
                 if (sat_[i]) continue;
                 const std::string &f = conds_[i]->field;
                 const bool under = em.path == f || (em.path.size() > f.size() && em.path.compare(0, f.size(), f) == 0 && em.path[f.size()] == kDelimiter);   // the walker's delimiter (walker.hpp), not a literal
-                if (under && std::regex_search(em.text.begin(), em.text.end(), res_[i])) sat_[i] = 1;
+                if (!under) continue;
+                if (dfa_ ? bsh_rx::run(dfas_[i], (const uint8_t *)em.text.data(), em.text.size())
+                         : std::regex_search(em.text.begin(), em.text.end(), res_[i])) sat_[i] = 1;
             }
             return true;
         });
@@ -243,9 +249,10 @@ public:
 
 private:
     RegexExpression root_;
-    bool has_root_ = false, valid_ = true;
+    bool has_root_ = false, valid_ = true, dfa_ = false;
     std::vector<const RegexExpression *> conds_;
     std::vector<std::regex> res_;
+    std::vector<bsh_rx::Dfa> dfas_;
     std::vector<uint8_t> sat_;
     PathWalker walker_;
     void collect(const RegexExpression &e)
@@ -253,6 +260,12 @@ private:
         if (e.type == RegexType::Condition) {
             if (!e.has_condition || e.field.empty()) return;   // nil condition: true; empty field: constant false (row_matcher.go:446-451)
             conds_.push_back(&e);
+            if (dfa_) {
+                std::string err;
+                dfas_.emplace_back();
+                if (!bsh_rx::compile(e.pattern, dfas_.back(), err)) valid_ = false;
+                return;
+            }
             // the one RE2 idiom the mirror translates: a leading (?i) becomes the icase flag
             const bool icase = e.pattern.rfind("(?i)", 0) == 0;
             try { res_.emplace_back(icase ? e.pattern.substr(4) : e.pattern,

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "engine.hpp"
+#include "regex_dfa.hpp"
 
 using namespace bsh;
 
@@ -246,6 +247,16 @@ int32_t bsh_match_row_regex(const char *regex_json, uint64_t regex_len, const ui
     return m.match(std::string_view(reinterpret_cast<const char *>(row), row_len)) ? 1 : 0;
 }
 
+// MatchString of one pattern of the device regex subset (regex_dfa.hpp) on one text: 1 / 0 / BSG_E_UNSUPPORTED
+int32_t bsh_regex_match(const char *pattern, uint64_t plen, const uint8_t *text, uint64_t tlen)
+{
+    if ((plen && !pattern) || (tlen && !text)) return BSH_E_INVALID;
+    bsh_rx::Dfa d;
+    std::string err;
+    if (!bsh_rx::compile(std::string_view(pattern ? pattern : "", plen), d, err)) return BSG_E_UNSUPPORTED;
+    return bsh_rx::run(d, text, tlen) ? 1 : 0;
+}
+
 int32_t bsh_section_encode(const uint64_t *const words[3], const uint64_t m[3], const uint64_t k[3], uint8_t **out, uint64_t *out_len)
 {
     FilterView fv[3];
@@ -296,6 +307,7 @@ int32_t bse_open(const char *config_json, uint64_t len, bsg_ctx *ctx, bse_engine
         if (const JNode *n = dom.get("PartitionField")) { if (n->type == JType::String) cfg.partition_field = n->text; }
         if (const JNode *n = dom.get("DeviceIngest")) cfg.device_ingest = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatch")) cfg.device_match = n->type == JType::True;
+        if (const JNode *n = dom.get("DeviceRegex")) cfg.device_regex = n->type == JType::True;
     }
     std::string err;
     if (int32_t rc = BloomSearchEngine::validate(cfg, err)) return rc;

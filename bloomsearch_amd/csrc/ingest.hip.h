@@ -517,6 +517,16 @@ __device__ __forceinline__ uint32_t str_rune(Walker &w, uint32_t r)
     return 0xFFu;
 }
 
+// What the walker hands a text consumer besides its own hashing: the bytes of every primitive's candidate text as
+// leafTokenInput makes it (row_matcher.go) — a string's decoded bytes (escapes as what they decode to, a non-ASCII rune as
+// the UTF-8 of the ORIGINAL rune), a number's raw literal, true / false.  The ingest walker and the plain row matcher use
+// RxNone: every hook is empty and their code is what it was without the hooks.
+struct RxNone {
+    __device__ __forceinline__ void feed(uint32_t) {}
+    __device__ __forceinline__ void feed_run(uint64_t, uint32_t) {}
+    __device__ __forceinline__ void feed_rune(uint32_t) {}
+};
+
 struct ChunkCursor {
     const uint64_t *chunks;
     uint64_t ci;     // index of the chunk in Walker::cur
@@ -531,8 +541,8 @@ struct ChunkCursor {
 // S_KEY_OPEN when their byte sits in the same chunk and a has-dots flag for S_PREFIX (no change), the rare escape /
 // UTF-8 states behind one test (slower: 8.9 -> 11.1 ms per 3 M rows, the structurizer's layout got worse), S_STR / S_KEY
 // runs continuing into the next chunk within one trip (8.76 -> 9.05 ms).
-template <bool EMIT>
-__device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc)
+template <bool EMIT, class RX>
+__device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &rx)
 {
     lds_u8 *stack = w.path + kPathCap;
     if ((w.pos >> 3) != cc.ci) {                      // the step before ended on the chunk boundary
@@ -640,8 +650,9 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc)
             if (key) {
                 if (w.key_len >= kPathCap) return R_FAIL;
                 w.path[w.key_len++] = (uint8_t)b;
-            } else if (str_decoded_byte(w, b)) {
-                return R_CONTINUE;
+            } else {
+                rx.feed(b);
+                if (str_decoded_byte(w, b)) return R_CONTINUE;
             }
             break;
         }
@@ -672,8 +683,10 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc)
                 if (w.key_len + n > kPathCap) return R_FAIL;
                 for (uint32_t i = 0; i < n; ++i) w.path[w.key_len++] = (uint8_t)(bytes >> (8u * i));
             } else if (cp < 0x80u) {
+                rx.feed(cp);
                 if (str_decoded_byte(w, cp)) return R_CONTINUE;
             } else {
+                rx.feed_rune(cp);
                 const uint32_t r = str_rune(w, cp);
                 if (r != 0xFFu) return r;
             }
@@ -701,6 +714,7 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc)
             w.aux = (w.aux << 6) | (c & 0x3Fu);
             if (left > 1) { w.lit = ((left - 1) << 28) | (0xBFu << 16) | (0x80u << 8); break; }
             w.st = S_STR;
+            rx.feed_rune(w.aux);
             const uint32_t r = str_rune(w, w.aux);
             if (r != 0xFFu) return r;
             break;
@@ -721,6 +735,7 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc)
             uint32_t n = stops ? (uint32_t)(__builtin_ctzll(stops) >> 3) : 8u;
             if (n > avail) n = avail;
             if (n != 0u) {
+                rx.feed_run(v, n);
                 word_run(w, n == 8u ? v : (v & ((1ULL << (n * 8u)) - 1ULL)), n);
                 w.pos += n;
             }
@@ -728,7 +743,7 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc)
                 const uint32_t b = c_at(v, n);
                 ++w.pos;
                 if (b == '"') { w.st = S_AFTER; if (word_end(w)) return R_CONTINUE; }
-                else if (b == ' ') { if (word_end(w)) return R_CONTINUE; }   // raw white space other than 0x20 fails here
+                else if (b == ' ') { rx.feed(b); if (word_end(w)) return R_CONTINUE; }   // raw white space other than 0x20 fails here
                 else if (b == '\\') w.st = S_STR_ESC;
                 else if (b >= 0xC2u && b <= 0xF4u) {                // UTF-8 lead byte (decode_rune, text.hpp)
                     uint32_t left, lo = 0x80u, hi = 0xBFu;
@@ -744,7 +759,7 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc)
         }
         case S_NUM: {                                               // the token is the RAW literal (tokenizer.go:124-125)
             const uint32_t nx = num_next(w.aux, c);
-            if (nx != 0xFFu) { w.aux = nx; word_byte(w, c); ++w.pos; break; }
+            if (nx != 0xFFu) { w.aux = nx; rx.feed(c); word_byte(w, c); ++w.pos; break; }
             if (!num_accepting(w.aux)) return R_FAIL;
             w.st = S_AFTER;                                         // c is not part of the number: S_AFTER looks at it
             if (word_end(w)) return R_CONTINUE;
@@ -757,7 +772,7 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc)
             if (c != want) return R_FAIL;
             ++w.pos;
             ++w.aux;
-            if (w.lit != 2u) word_byte(w, c);                       // null: field existence only (tokenizer.go:130-131)
+            if (w.lit != 2u) { rx.feed(c); word_byte(w, c); }       // null: field existence only (tokenizer.go:130-131)
             if (w.aux == (w.lit == 1u ? 5u : 4u)) {
                 w.st = S_AFTER;
                 if (word_end(w)) return R_CONTINUE;
@@ -848,7 +863,9 @@ __device__ __forceinline__ void walker_reset(Walker &w, ChunkCursor &cc, uint64_
 }
 
 template <bool EMIT>
-__device__ __forceinline__ uint32_t advance(Walker &w, ChunkCursor &cc) { return walker_step<EMIT>(w, cc); }
+__device__ __forceinline__ uint32_t advance(Walker &w, ChunkCursor &cc) { RxNone rx; return walker_step<EMIT>(w, cc, rx); }
+template <bool EMIT, class RX>
+__device__ __forceinline__ uint32_t advance(Walker &w, ChunkCursor &cc, RX &rx) { return walker_step<EMIT>(w, cc, rx); }
 
 // One wave walks a contiguous run of rows_per_wave rows, 64 at a time (lane = row); the four waves of a workgroup take
 // neighbouring runs, so a workgroup stays inside one block (or two) and its dedup cache stays warm: a workgroup that

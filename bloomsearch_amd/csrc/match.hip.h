@@ -8,7 +8,17 @@
 // (ingest.hip.h, FpKey): an emission whose hashes equal a condition's but whose fingerprint differs is a murmur3 state
 // collision — the row is handed to the host matcher, which compares bytes as matchRowBytes does.
 // Rows outside the device walker's envelope are reported back and decided by the host matcher too.
+//
+// FieldRegex conditions (kind 3, k_match_rows_regex = the same body with REGEX = true): each pattern is a byte DFA compiled
+// on the host (host/regex_dfa.hpp) whose tables sit in LDS behind the plain matcher's.  At a leaf request the converged part
+// of the loop decides which regex conditions see the leaf (its path equals the field or starts with field + ".",
+// row_matcher.go hasStringPrefix) by a byte compare of the lane's path buffer; the lane keeps those conditions' DFA states
+// in registers (at most kRxActive per leaf, more make the row a fallback row) and the walker feeds them the leaf's
+// candidate text (leafTokenInput) one byte at a time, one LDS lookup each.  A condition leaves the active set once it
+// accepts (its flag is set) or its DFA is dead; the states still active when the leaf closes are checked for
+// accept-at-end.  null is never a candidate text.
 #pragma once
+#include <type_traits>
 #include "ingest.hip.h"
 
 namespace bsg {
@@ -36,7 +46,64 @@ struct MatchArgs {
 
 constexpr uint32_t kMatchLdsBytes = kMatchMaxConds * kMatchCondWords * 8 + kMatchMaxOps * 4 + kIngestThreads * kLaneLds;
 
-__global__ __launch_bounds__(kIngestThreads) void k_match_rows(const MatchArgs a)
+// ---- FieldRegex conditions ----
+constexpr uint32_t kRxMaxConds = 16;       // regex conditions per call
+constexpr uint32_t kRxActive = 4;          // regex conditions one leaf may feed at once (registers per lane)
+constexpr uint32_t kRxLdsCap = 80u * 1024u - kMatchLdsBytes;   // table bytes: the regex kernel keeps 2 workgroups per CU
+// LDS table blob, built by the host (match_api.inc build_rx_blob):
+//   header [n_rx][4] u32: { region offset | (n_classes - 1) << 16 | slot << 24,  start entry | condition index << 16,
+//                           field offset | field length << 16,  0 }
+//   per pattern (4-byte aligned region): class map [256] u8, then transitions [n_states * n_classes] u16 whose entries are
+//   target state | kRxAccept / kRxDead / kRxAcceptAtEnd of the target; then the field strings.
+constexpr uint32_t kRxAccept = 0x8000u, kRxDead = 0x4000u, kRxAcceptAtEnd = 0x2000u, kRxStateMask = 0x1FFFu;
+struct RxArgs {
+    const uint32_t *blob;       // the table blob as words
+    uint32_t n_words, n_rx;
+};
+typedef __attribute__((address_space(3))) uint16_t lds_u16;
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+
+// one lane's active regex conditions (hd = header word 0 of the condition, ~0u = free slot; st = its DFA entry)
+struct RxLane {
+    const lds_u8 *tab;
+    uint32_t hd[kRxActive], st[kRxActive];
+    uint32_t sat;                                   // bit j: regex slot j matched a candidate text of this row
+    __device__ __forceinline__ void feed(uint32_t b)
+    {
+#pragma unroll
+        for (uint32_t k = 0; k < kRxActive; ++k)
+            if (hd[k] != ~0u) {
+                const uint32_t off = hd[k] & 0xFFFFu, ncls = ((hd[k] >> 16) & 0xFFu) + 1u;
+                const uint32_t v = ((const lds_u16 *)(tab + off + 256u))[(st[k] & kRxStateMask) * ncls + tab[off + b]];
+                st[k] = v;
+                if (v & (kRxAccept | kRxDead)) {
+                    if (v & kRxAccept) sat |= 1u << (hd[k] >> 24);
+                    hd[k] = ~0u;
+                }
+            }
+    }
+    __device__ __forceinline__ void feed_run(uint64_t v, uint32_t n)
+    {
+        for (uint32_t i = 0; i < n; ++i) feed(c_at(v, i));
+    }
+    __device__ __forceinline__ void feed_rune(uint32_t r)
+    {
+        uint32_t n = 1;
+        const uint32_t bytes = rune_utf8(r, n);
+        for (uint32_t i = 0; i < n; ++i) feed((bytes >> (8u * i)) & 0xFFu);
+    }
+    __device__ __forceinline__ void close()
+    {
+#pragma unroll
+        for (uint32_t k = 0; k < kRxActive; ++k) {
+            if (hd[k] != ~0u && (st[k] & kRxAcceptAtEnd)) sat |= 1u << (hd[k] >> 24);
+            hd[k] = ~0u;
+        }
+    }
+};
+
+template <bool REGEX>
+__device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs &x)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     lds_u64i *conds = (lds_u64i *)lds_raw;
@@ -49,6 +116,8 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows(const MatchArgs a
         e[10] = a.cond_kind[c];
     }
     for (uint32_t i = threadIdx.x; i < a.n_ops; i += kIngestThreads) prog[i] = a.prog[i];
+    if constexpr (REGEX)
+        for (uint32_t i = threadIdx.x; i < x.n_words; i += kIngestThreads) ((lds_u32 *)(lds_raw + kMatchLdsBytes))[i] = x.blob[i];
     __syncthreads();
     const uint32_t r = blockIdx.x * kIngestThreads + threadIdx.x;
     const bool live = r < a.n_rows;
@@ -64,9 +133,17 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows(const MatchArgs a
     uint32_t res = live ? R_CONTINUE : R_DONE;
     uint64_t sat = 0, leaf_mask = 0;
     bool collided = false;       // equal hashes, different fingerprint: only the host's byte compare can decide this row
+    typename std::conditional<REGEX, RxLane, RxNone>::type rx;
+    bool rx_over = false;        // more regex conditions on one leaf than a lane holds: the host decides this row
+    if constexpr (REGEX) {
+        rx.tab = (const lds_u8 *)lds_raw + kMatchLdsBytes;
+        rx.sat = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kRxActive; ++k) rx.hd[k] = ~0u;
+    }
     while (__ballot(res == R_CONTINUE || w.req != Q_NONE) != 0ull) {
         while (__ballot(res == R_CONTINUE && w.req == Q_NONE) != 0ull)
-            if (res == R_CONTINUE && w.req == Q_NONE) res = advance<true>(w, cc);
+            if (res == R_CONTINUE && w.req == Q_NONE) res = advance<true>(w, cc, rx);
         const uint32_t q = w.req;
         w.req = Q_NONE;
         HashStream s;
@@ -78,10 +155,36 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows(const MatchArgs a
         uint64_t h[4] = {0, 0, 0, 0}, fp = 0;
         if (q != Q_NONE) fp = hs_finish(s, h, w.key);
         if (q == Q_LEAF) leaf_mask = 0;
+        if constexpr (REGEX) {
+            if (q == Q_LEAF) rx.close();                                 // the previous leaf's text ended before this request
+            const bool text = q == Q_LEAF && !(w.st == S_LIT && w.lit == 2u);   // null is never a candidate text
+            const lds_u32 *hdr = (const lds_u32 *)rx.tab;
+            // only a leaf request opens DFAs: the (more frequent) word and field rounds skip the header loop as a whole wave
+            for (uint32_t j = 0; j < x.n_rx && __ballot(text) != 0ull; ++j) {   // uniform loop: header words are LDS broadcasts
+                const uint32_t h0 = hdr[4 * j], h1 = hdr[4 * j + 1], h2 = hdr[4 * j + 2], flen = h2 >> 16;
+                const lds_u8 *fld = rx.tab + (h2 & 0xFFFFu);
+                bool under = text && !((rx.sat >> j) & 1u) && flen != 0u && flen <= kPathCap &&
+                             (plen == flen || (plen > flen && w.path[flen] == '.'));
+                for (uint32_t i = 0; i < flen && __ballot(under) != 0ull; ++i)   // ends once no lane's path can still match
+                    if (under) under = w.path[i] == fld[i];
+                if (under) {
+                    const uint32_t sv = h1 & 0xFFFFu;
+                    if (sv & kRxAccept) rx.sat |= 1u << j;               // the pattern matches every text (an empty match)
+                    else if (!(sv & kRxDead)) {
+                        bool placed = false;
+#pragma unroll
+                        for (uint32_t k = 0; k < kRxActive; ++k)
+                            if (!placed && rx.hd[k] == ~0u) { rx.hd[k] = h0; rx.st[k] = sv; placed = true; }
+                        rx_over |= !placed;
+                    }
+                }
+            }
+        }
         const bool is_path = q == Q_FIELD || q == Q_LEAF, is_word = q == Q_WORD;
         for (uint32_t c = 0; c < a.n_conds; ++c) {                       // uniform loop: the conditions come from LDS broadcasts
             const lds_u64i *e = conds + c * kMatchCondWords;
             const uint32_t kind = (uint32_t)e[10];                       // 0 Field, 1 Token, 2 FieldToken
+            if (REGEX && kind == 3u) continue;                           // FieldRegex: the DFAs above
             const uint64_t bit = 1ULL << c;
             if (kind != 1u) {                                            // conditions with a field: compare paths
                 const bool heq = is_path && e[0] == h[0] && e[1] == h[1] && e[2] == h[2] && e[3] == h[3];
@@ -97,6 +200,13 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows(const MatchArgs a
                 if (eq && (kind == 1u || (leaf_mask & bit))) sat |= bit; // Token anywhere; FieldToken only under its own path
             }
         }
+    }
+    if constexpr (REGEX) {
+        rx.close();
+        const lds_u32 *hdr = (const lds_u32 *)rx.tab;
+        for (uint32_t j = 0; j < x.n_rx; ++j)
+            if ((rx.sat >> j) & 1u) sat |= 1ULL << (hdr[4 * j + 1] >> 16);
+        if (rx_over && res == R_DONE) res = R_FAIL;
     }
     // evalMatcherNode over the flags: one bit of stack per lane and level
     uint64_t stk = 0;
@@ -119,5 +229,9 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows(const MatchArgs a
         a.fallback_rows[slot] = a.row_base + r;
     }
 }
+
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows(const MatchArgs a) { match_rows_body<false>(a, RxArgs{}); }
+// Field / Token / FieldToken and FieldRegex conditions; dynamic LDS kMatchLdsBytes + the table blob (<= kRxLdsCap)
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_regex(const MatchArgs a, const RxArgs x) { match_rows_body<true>(a, x); }
 
 }  // namespace bsg

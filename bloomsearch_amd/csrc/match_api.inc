@@ -2,10 +2,61 @@
 
 namespace {
 
+// The LDS table blob of a call's FieldRegex conditions (layout: match.hip.h).  BSG_E_UNSUPPORTED, before anything is
+// launched, for a pattern outside the compiler's subset, more than kRxMaxConds of them, or tables over kRxLdsCap.
+int32_t build_rx_blob(const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                      std::vector<uint32_t> &blob, uint32_t &n_rx)
+{
+    std::vector<uint32_t> rx;
+    for (uint32_t c = 0; c < n_conds; ++c)
+        if (cond_kinds[c] == BSG_KIND_FIELD_REGEX) rx.push_back(c);
+    n_rx = (uint32_t)rx.size();
+    blob.clear();
+    if (rx.empty()) return BSG_OK;
+    if (n_rx > bsg::kRxMaxConds)
+        return fail(BSG_E_UNSUPPORTED, "%u regex conditions (the device matcher holds %u)", n_rx, bsg::kRxMaxConds);
+    std::vector<uint8_t> bytes((size_t)n_rx * 16, 0);
+    auto put32 = [&](size_t at, uint32_t v) { memcpy(bytes.data() + at, &v, 4); };
+    bool over = false;
+    for (uint32_t j = 0; j < n_rx; ++j) {
+        const uint32_t c = rx[j];
+        const std::string_view pat((const char *)cond_bytes + cond_off[2 * c + 1], cond_off[2 * c + 2] - cond_off[2 * c + 1]);
+        bsh_rx::Dfa d;
+        std::string err;
+        if (!bsh_rx::compile(pat, d, err))
+            return fail(BSG_E_UNSUPPORTED, "regex condition %u (pattern \"%.*s\"): %s", c, (int)std::min<size_t>(pat.size(), 200), pat.data(), err.c_str());
+        bytes.resize((bytes.size() + 3) & ~(size_t)3);
+        const size_t off = bytes.size();
+        if (off + 256 + d.trans.size() * 2 > bsg::kRxLdsCap) { over = true; break; }
+        bytes.insert(bytes.end(), d.cls, d.cls + 256);
+        const size_t t0 = bytes.size();
+        bytes.resize(t0 + d.trans.size() * 2);
+        memcpy(bytes.data() + t0, d.trans.data(), d.trans.size() * 2);
+        put32((size_t)j * 16, (uint32_t)off | ((d.n_classes - 1) << 16) | (j << 24));
+        put32((size_t)j * 16 + 4, (uint32_t)d.start | (c << 16));
+    }
+    for (uint32_t j = 0; j < n_rx && !over; ++j) {
+        const uint32_t c = rx[j];
+        uint32_t flen = cond_off[2 * c + 1] - cond_off[2 * c];
+        // a path the device keeps is at most kPathCap bytes: a longer field is never at or above a leaf of a row it decides
+        if (flen > bsg::kPathCap) flen = bsg::kPathCap + 1;
+        const size_t off = bytes.size();
+        if (flen <= bsg::kPathCap) bytes.insert(bytes.end(), cond_bytes + cond_off[2 * c], cond_bytes + cond_off[2 * c] + flen);
+        put32((size_t)j * 16 + 8, (uint32_t)std::min<size_t>(off, 0xFFFF) | (flen << 16));
+    }
+    if (over || bytes.size() > bsg::kRxLdsCap)
+        return fail(BSG_E_UNSUPPORTED, "regex tables need more than %u bytes of LDS", bsg::kRxLdsCap);
+    bytes.resize((bytes.size() + 3) & ~(size_t)3);
+    blob.resize(bytes.size() / 4);
+    memcpy(blob.data(), bytes.data(), bytes.size());
+    return BSG_OK;
+}
+
 // rows [r0, r1) (r0 a multiple of 64: whole words of out_bits) on one device; fb receives the GLOBAL indices of the rows handed back
 int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64_t *row_off, uint32_t r0, uint32_t r1,
                       const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds, uint32_t cond_len,
-                      const std::vector<uint32_t> &prog, uint64_t *out_bits, std::vector<uint32_t> &fb, float *ms)
+                      const std::vector<uint32_t> &prog, const std::vector<uint32_t> &rx_blob, uint32_t n_rx,
+                      uint64_t *out_bits, std::vector<uint32_t> &fb, float *ms)
 {
     const uint32_t n_rows = r1 - r0;
     const uint64_t byte0 = row_off[r0], n_bytes = row_off[r1] - byte0;
@@ -25,10 +76,10 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
     const size_t n_words = ((size_t)n_rows + 63) / 64;
     uint8_t *d_rows = nullptr, *d_cbytes = nullptr;
     uint64_t *d_off = nullptr, *d_ch = nullptr, *d_cfp = nullptr, *d_bits = nullptr;
-    uint32_t *d_prog = nullptr, *d_fb = nullptr, *d_nfb = nullptr, *d_coff = nullptr, *d_ckind = nullptr;
+    uint32_t *d_prog = nullptr, *d_fb = nullptr, *d_nfb = nullptr, *d_coff = nullptr, *d_ckind = nullptr, *d_rx = nullptr;
     auto cleanup = [&]() {
         for (void *p : {(void *)d_rows, (void *)d_off, (void *)d_ch, (void *)d_cfp, (void *)d_bits, (void *)d_prog, (void *)d_fb, (void *)d_nfb,
-                        (void *)d_cbytes, (void *)d_coff, (void *)d_ckind})
+                        (void *)d_cbytes, (void *)d_coff, (void *)d_ckind, (void *)d_rx})
             if (p) d.pool.free(p);
     };
     hipError_t e = d.pool.alloc((void **)&d_rows, n_bytes + 64);
@@ -42,6 +93,7 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
     if (e == hipSuccess) e = d.pool.alloc((void **)&d_bits, n_words * 8);
     if (e == hipSuccess) e = d.pool.alloc((void **)&d_fb, (size_t)n_rows * 4);
     if (e == hipSuccess) e = d.pool.alloc((void **)&d_nfb, 4);
+    if (e == hipSuccess && n_rx) e = d.pool.alloc((void **)&d_rx, rx_blob.size() * 4);
     lap("device buffers allocated");
     if (e == hipSuccess) e = hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_off, local_off.data(), ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream);
@@ -59,6 +111,7 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
     }
     if (e == hipSuccess && !prog.empty()) e = hipMemcpyAsync(d_prog, prog.data(), prog.size() * 4, hipMemcpyHostToDevice, d.stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_nfb, 0, 4, d.stream);
+    if (e == hipSuccess && n_rx) e = hipMemcpyAsync(d_rx, rx_blob.data(), rx_blob.size() * 4, hipMemcpyHostToDevice, d.stream);
     // The rows travel in chunks on the copy stream while the chunk before is being matched (a surviving block is <= 10 MiB and
     // goes in one piece; a scan of many blocks in one call is 64, 128, then 256 MiB pieces as in bsg_ingest_rows: the walk of
     // 2.5 GB takes 12 ms, their copy 50 ms — one after the other they would add up).  Chunks are whole 256-row workgroups.
@@ -115,8 +168,15 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
         if (e == hipSuccess) e = hipEventCreate(&evs[(size_t)c * 3 + 2]);
         if (e == hipSuccess && n_chunks > 1) e = hipStreamWaitEvent(d.stream, evs[(size_t)c * 3], 0);
         if (e != hipSuccess) break;
-        hipExtLaunchKernelGGL(bsg::k_match_rows, dim3((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads), dim3(bsg::kIngestThreads),
-                              bsg::kMatchLdsBytes, d.stream, evs[(size_t)c * 3 + 1], evs[(size_t)c * 3 + 2], 0, a);
+        const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads);
+        if (n_rx) {
+            const bsg::RxArgs x{d_rx, (uint32_t)rx_blob.size(), n_rx};
+            hipExtLaunchKernelGGL(bsg::k_match_rows_regex, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes + (uint32_t)rx_blob.size() * 4,
+                                  d.stream, evs[(size_t)c * 3 + 1], evs[(size_t)c * 3 + 2], 0, a, x);
+        } else {
+            hipExtLaunchKernelGGL(bsg::k_match_rows, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes, d.stream, evs[(size_t)c * 3 + 1],
+                                  evs[(size_t)c * 3 + 2], 0, a);
+        }
         e = hipGetLastError();
         // K(c) is running: now the next chunk's bytes (from pageable memory this call only returns once they are staged)
         if (e == hipSuccess && c + 1 < n_chunks) e = copy_chunk(c + 1);
@@ -143,23 +203,19 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
     return BSG_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int32_t bsg_match_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
-                       const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
-                       const uint32_t *prog_ops, uint32_t n_ops,
-                       uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+// bsg_match_rows (max_kind 2) and bsg_match_rows_regex (max_kind 3)
+int32_t match_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                        const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                        const uint32_t *prog_ops, uint32_t n_ops,
+                        uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback, uint32_t max_kind)
 {
-    BSG_ENTER(ctx);
     if (!ctx) return fail(BSG_E_INVALID, "ctx is null");
     if (!out_n_fallback || (n_rows && (!row_off || !out_bits))) return fail(BSG_E_INVALID, "null argument");
     if (n_conds && (!cond_off || !cond_kinds)) return fail(BSG_E_INVALID, "conditions are null");
     if (n_ops && !prog_ops) return fail(BSG_E_INVALID, "prog_ops is null");
     if (n_conds > bsg::kMatchMaxConds) return fail(BSG_E_UNSUPPORTED, "%u conditions (the device matcher holds %u)", n_conds, bsg::kMatchMaxConds);
     for (uint32_t c = 0; c < n_conds; ++c)
-        if (cond_kinds[c] > 2) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, cond_kinds[c]);
+        if (cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, cond_kinds[c]);
     for (uint32_t e = 0; e < 2 * n_conds; ++e)
         if (cond_off[e + 1] < cond_off[e]) return fail(BSG_E_INVALID, "cond_off not monotone at %u", e);
     const uint32_t cond_len = n_conds ? cond_off[2 * n_conds] : 0;
@@ -174,6 +230,9 @@ int32_t bsg_match_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_of
     if (int32_t rc = lower_program(prog_ops, n_ops, n_conds, ident, prog, depth)) return rc;
     if (depth > 64 || prog.size() > bsg::kMatchMaxOps)
         return fail(BSG_E_UNSUPPORTED, "expression too large for the device matcher (depth %u, %zu ops)", depth, prog.size());
+    std::vector<uint32_t> rx_blob;
+    uint32_t n_rx = 0;
+    if (int32_t rc = build_rx_blob(cond_bytes, cond_off, cond_kinds, n_conds, rx_blob, n_rx)) return rc;
     *out_n_fallback = 0;
     if (n_rows == 0) return BSG_OK;
     // Surviving blocks are independent (query_exec.go:729-764): a large scan is cut into one contiguous run of rows per
@@ -194,7 +253,7 @@ int32_t bsg_match_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_of
     const uint32_t first = n_parts == 1 ? pick_device(ctx) : 0;
     if (int32_t rc = run_parts(n_parts, [&](uint32_t i) -> int32_t {
             return match_rows_on(ctx, *ctx->devs[(first + i) % nd], rows, row_off, cuts[i], cuts[i + 1], cond_bytes, cond_off, cond_kinds, n_conds,
-                                 cond_len, prog, out_bits, fbs[i], &ms[i]);
+                                 cond_len, prog, rx_blob, n_rx, out_bits, fbs[i], &ms[i]);
         })) return rc;
     std::vector<uint32_t> fb;
     for (auto &v : fbs) fb.insert(fb.end(), v.begin(), v.end());
@@ -208,6 +267,30 @@ int32_t bsg_match_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_of
     if (fb.size() > fallback_cap && out_fallback_rows)
         return fail(BSG_E_INVALID, "%zu rows need the host matcher, caller's list holds %u", fb.size(), fallback_cap);
     return BSG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t bsg_match_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                       const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                       const uint32_t *prog_ops, uint32_t n_ops,
+                       uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    return match_rows_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, n_ops, out_bits, out_fallback_rows,
+                           fallback_cap, out_n_fallback, BSG_KIND_FIELD_TOKEN);
+}
+
+int32_t bsg_match_rows_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                             const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                             const uint32_t *prog_ops, uint32_t n_ops,
+                             uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    return match_rows_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, n_ops, out_bits, out_fallback_rows,
+                           fallback_cap, out_n_fallback, BSG_KIND_FIELD_REGEX);
 }
 
 int32_t bsg_pinned_alloc(bsg_ctx *ctx, uint64_t n_bytes, void **out_ptr)

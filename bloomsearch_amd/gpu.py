@@ -573,6 +573,13 @@ class Context:
     def match_rows(self, rows, matcher):
         """rows: list[bytes] or (u8 blob, u64 offsets); matcher: query.CompiledMatcher.
         -> (bool array [n_rows], sorted u32 array of rows the host matcher must decide)."""
+        return self._match_rows(self.L.bsg_match_rows, rows, matcher)
+
+    def match_rows_regex(self, rows, matcher):
+        """bsg_match_rows_regex: as match_rows, and the matcher (query.CompiledRowQuery) may hold FieldRegex conditions."""
+        return self._match_rows(self.L.bsg_match_rows_regex, rows, matcher)
+
+    def _match_rows(self, fn, rows, matcher):
         if isinstance(rows, tuple):
             blob = np.ascontiguousarray(rows[0], dtype=np.uint8)
             off = np.ascontiguousarray(rows[1], dtype=np.uint64)
@@ -589,8 +596,8 @@ class Context:
         bits = np.zeros((n + 63) // 64, dtype=np.uint64)
         fb = np.zeros(max(n, 1), dtype=np.uint32)
         nfb = C.c_uint32()
-        self._check(self.L.bsg_match_rows(self.h, _lib._ptr(blob), _lib._ptr(off), n, _lib._ptr(cblob), _lib._ptr(coff), _lib._ptr(kinds), len(kinds),
-                                          _lib._ptr(ops), len(ops), _lib._ptr(bits), _lib._ptr(fb), len(fb), C.byref(nfb)))
+        self._check(fn(self.h, _lib._ptr(blob), _lib._ptr(off), n, _lib._ptr(cblob), _lib._ptr(coff), _lib._ptr(kinds), len(kinds),
+                       _lib._ptr(ops), len(ops), _lib._ptr(bits), _lib._ptr(fb), len(fb), C.byref(nfb)))
         match = np.unpackbits(bits.view(np.uint8), bitorder="little")[:n].astype(bool)
         return match, fb[: nfb.value].copy()
 

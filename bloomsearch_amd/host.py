@@ -15,6 +15,7 @@ HOST_EXPORTS = [
     "bsh_free", "bsh_tokenize", "bsh_entry_sets_new", "bsh_entry_sets_free", "bsh_entry_sets_index_row",
     "bsh_entry_sets_union_into", "bsh_entry_sets_counts", "bsh_entry_sets_export_sizes", "bsh_entry_sets_export",
     "bsh_batch_new", "bsh_batch_free", "bsh_batch_add_query", "bsh_batch_sizes", "bsh_batch_export", "bsh_match_row", "bsh_prune_query", "bsh_match_row_regex",
+    "bsh_regex_match",
     "bsh_section_encode", "bsh_section_parse", "bsh_crc32c",
     "bse_open", "bse_close", "bse_last_error", "bse_stop", "bse_ingest_rows", "bse_flush", "bse_merge", "bse_query",
     "bse_describe", "bse_corrupt_section_byte", "bse_section_bytes",
@@ -53,6 +54,7 @@ def lib():
     L.bsh_match_row.argtypes = [C.c_char_p, u64, C.c_char_p, u64]
     L.bsh_prune_query.argtypes = [C.c_char_p, u64, C.c_char_p, u64, pp, pu64]
     L.bsh_match_row_regex.argtypes = [C.c_char_p, u64, C.c_char_p, u64]
+    L.bsh_regex_match.argtypes = [C.c_char_p, u64, C.c_char_p, u64]
     L.bsh_section_encode.argtypes = [C.POINTER(vp), pu64, pu64, pp, pu64]
     L.bsh_section_parse.argtypes = [C.c_char_p, u64, pu64, pu64, C.POINTER(vp)]
     L.bsh_crc32c.argtypes = [C.c_char_p, u64]; L.bsh_crc32c.restype = u32
@@ -295,3 +297,11 @@ class Engine:
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self.L.bse_section_bytes(self.h, file_index, block_index, C.byref(p), C.byref(n)))
         return _take(self.L, p, n)
+
+
+def regex_match(pattern: str | bytes, text: str | bytes) -> int:
+    """Go regexp MatchString for the device regex subset on the DFA tables: 1 / 0, or _lib.BSG_E_UNSUPPORTED."""
+    L = lib()
+    p = pattern.encode("utf-8", "surrogatepass") if isinstance(pattern, str) else pattern
+    t = text.encode("utf-8", "surrogatepass") if isinstance(text, str) else text
+    return int(L.bsh_regex_match(p, len(p), t, len(t)))

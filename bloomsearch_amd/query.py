@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import KIND_FIELD, KIND_FIELD_TOKEN, KIND_TOKEN, OP_AND, OP_FALSE, OP_OR, OP_TERM, OP_TRUE, op
+from ._lib import KIND_FIELD, KIND_FIELD_REGEX, KIND_FIELD_TOKEN, KIND_TOKEN, OP_AND, OP_FALSE, OP_OR, OP_TERM, OP_TRUE, op
 
 BLOOM_FIELD, BLOOM_TOKEN, BLOOM_FIELD_TOKEN = "FIELD", "TOKEN", "FIELD_TOKEN"
 EXPR_CONDITION, EXPR_AND, EXPR_OR = "CONDITION", "AND", "OR"
@@ -222,6 +222,49 @@ class CompiledMatcher:
             kids = e.get("Children") or []
             for c in kids:
                 self._emit(c)
+            self.prog_ops.append(op(OP_AND if et == EXPR_AND else OP_OR, len(kids)))
+        else:
+            self.prog_ops.append(op(OP_FALSE))
+
+
+class CompiledRowQuery(CompiledMatcher):
+    """The whole compileRowMatcher root And(bloom root, regex root) (row_matcher.go:353-368) for bsg_match_rows_regex: the
+    bloom side lowered as CompiledMatcher does, the regex side by compileRegexExpression's rules (row_matcher.go:440-480) —
+    a nil expression or condition is TRUE, an empty field FALSE, an empty Or FALSE, an empty And TRUE.  A FieldRegex
+    condition keeps its field in `fields` and its pattern in `tokens` (entry 2i + 1)."""
+
+    def __init__(self, bloom_expression, regex_expression):
+        super().__init__(None)
+        if bloom_expression is None:
+            self.prog_ops.append(op(OP_TRUE))
+        else:
+            self._emit(bloom_expression)
+        self._emit_regex(regex_expression)
+        self.prog_ops.append(op(OP_AND, 2))
+
+    def _emit_regex(self, e) -> None:
+        if e is None:
+            self.prog_ops.append(op(OP_TRUE))
+            return
+        et = e.get("ExpressionType")
+        if et == EXPR_CONDITION:
+            cond = e.get("Condition")
+            if cond is None:
+                self.prog_ops.append(op(OP_TRUE))
+            elif cond.get("Field", "") == "":
+                self.prog_ops.append(op(OP_FALSE))
+            else:
+                self.prog_ops.append(op(OP_TERM, len(self.kinds)))
+                self.kinds.append(KIND_FIELD_REGEX)
+                self.fields.append(cond["Field"].encode("utf-8", "surrogatepass"))
+                self.tokens.append(cond.get("Pattern", "").encode("utf-8", "surrogatepass"))
+        elif et in (EXPR_AND, EXPR_OR):
+            kids = e.get("Children") or []
+            if not kids:
+                self.prog_ops.append(op(OP_TRUE if et == EXPR_AND else OP_FALSE))
+                return
+            for c in kids:
+                self._emit_regex(c)
             self.prog_ops.append(op(OP_AND if et == EXPR_AND else OP_OR, len(kids)))
         else:
             self.prog_ops.append(op(OP_FALSE))

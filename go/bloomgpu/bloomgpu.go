@@ -34,6 +34,8 @@ const (
 	KindField      uint32 = C.BSG_KIND_FIELD
 	KindToken      uint32 = C.BSG_KIND_TOKEN
 	KindFieldToken uint32 = C.BSG_KIND_FIELD_TOKEN
+	// KindFieldRegex is a FieldRegex condition of the row matcher (MatchRowsRegex only): Field = the field, Token = the pattern.
+	KindFieldRegex uint32 = C.BSG_KIND_FIELD_REGEX
 )
 
 // Program opcodes: op = opcode<<28 | arg, postfix order (see bloomgpu.h).
@@ -153,6 +155,13 @@ type Error struct {
 }
 
 func (e *Error) Error() string { return fmt.Sprintf("bloomgpu: %s (%d)", e.Message, e.Code) }
+
+// IsUnsupported reports whether err is BSG_E_UNSUPPORTED: the call is outside what the device serves (for MatchRowsRegex, a
+// pattern outside its RE2 subset among others) and was refused before anything ran — the caller takes its host path.
+func IsUnsupported(err error) bool {
+	e, ok := err.(*Error)
+	return ok && e.Code == int(C.BSG_E_UNSUPPORTED)
+}
 
 func (g *Context) err(rc C.int32_t) error {
 	if rc == C.BSG_OK {
@@ -869,6 +878,17 @@ func (in *Ingest) Free() error { return in.g.err(C.bsg_ingest_free(in.g.c, in.id
 // in hostRows must be decided by matchRowBytes (outside the device walker's envelope, or a hash collision with a
 // condition string that only a byte compare can settle).
 func (g *Context) MatchRows(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32) (bits []uint64, hostRows []uint32, err error) {
+	return g.matchRows(false, rows, rowOff, conds, progOps)
+}
+
+// MatchRowsRegex is MatchRows through bsg_match_rows_regex: conds may also hold KindFieldRegex conditions (Token = the pattern,
+// pattern.String() of the compiled regexp), so a whole compileRowMatcher root And(bloomRoot, regexRoot) is one call.  A pattern
+// outside the device's RE2 subset, more than 16 of them or tables over its LDS budget: IsUnsupported(err).
+func (g *Context) MatchRowsRegex(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32) (bits []uint64, hostRows []uint32, err error) {
+	return g.matchRows(true, rows, rowOff, conds, progOps)
+}
+
+func (g *Context) matchRows(regex bool, rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32) (bits []uint64, hostRows []uint32, err error) {
 	n := len(rowOff) - 1
 	if n <= 0 {
 		return nil, nil, nil
@@ -886,7 +906,13 @@ func (g *Context) MatchRows(rows []byte, rowOff []uint64, conds []MatchCond, pro
 		kinds[i] = c.Kind
 	}
 	var nfb C.uint32_t
-	rc := C.bsg_match_rows(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
-		u32p(progOps), C.uint32_t(len(progOps)), u64p(bits), u32p(hostRows), C.uint32_t(n), &nfb)
+	var rc C.int32_t
+	if regex {
+		rc = C.bsg_match_rows_regex(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+			u32p(progOps), C.uint32_t(len(progOps)), u64p(bits), u32p(hostRows), C.uint32_t(n), &nfb)
+	} else {
+		rc = C.bsg_match_rows(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+			u32p(progOps), C.uint32_t(len(progOps)), u64p(bits), u32p(hostRows), C.uint32_t(n), &nfb)
+	}
 	return bits, hostRows[:nfb], g.err(rc)
 }

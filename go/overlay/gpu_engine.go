@@ -39,6 +39,11 @@ type gpuEngine struct {
 	scopeMu   sync.Mutex
 	idle, all []*bloomgpu.Context // error scopes: one per goroutine-confined caller at a time (bsg_scope_open)
 
+	// regex matchers the device refused (BSG_E_UNSUPPORTED: a pattern outside its RE2 subset, too many conditions), keyed by
+	// their (field, pattern) list: later blocks and queries with the same conditions go straight to the stock matcher
+	regexMu      sync.Mutex
+	regexRefused map[string]bool
+
 }
 
 // gpuFileArena is a query's lease on one file's block filters decoded on the device.  Blocks are in ascending RowDataOffset
@@ -468,10 +473,24 @@ type gpuRowVerdicts struct {
 }
 
 // matchBlock runs the block's rows through bsg_match_rows for matchers made of Field / Token / FieldToken conditions under the
-// default tokenizer; anything else (regex conditions, a custom tokenizer, constant matchers) keeps the stock per-row matcher.
+// default tokenizer, and through bsg_match_rows_regex when the matcher has FieldRegex conditions too (the whole root
+// And(bloomRoot, regexRoot) in one call; a matcher the device refuses is remembered and keeps the stock matcher); anything else
+// (a custom tokenizer, constant matchers) keeps the stock per-row matcher.
 func (e *gpuEngine) matchBlock(rowData []byte, m *compiledRowMatcher) *gpuRowVerdicts {
-	if e == nil || m.matchesAll || m.neverMatches || !m.fastTokens || len(m.regexConds) > 0 || len(m.conditions) == 0 || len(m.conditions) > 64 {
+	if e == nil || m.matchesAll || m.neverMatches || !m.fastTokens || len(m.conditions) == 0 || len(m.conditions) > 64 || len(m.regexConds) > 16 {
 		return nil
+	}
+	regexKey := ""
+	for _, i := range m.regexConds {
+		regexKey += m.conditions[i].field + "\x00" + m.conditions[i].pattern.String() + "\x00"
+	}
+	if len(m.regexConds) > 0 {
+		e.regexMu.Lock()
+		refused := e.regexRefused[regexKey]
+		e.regexMu.Unlock()
+		if refused {
+			return nil
+		}
 	}
 	conds := make([]bloomgpu.MatchCond, len(m.conditions))
 	for i, c := range m.conditions {
@@ -482,6 +501,8 @@ func (e *gpuEngine) matchBlock(rowData []byte, m *compiledRowMatcher) *gpuRowVer
 			conds[i] = bloomgpu.MatchCond{Kind: bloomgpu.KindToken, Token: c.token}
 		case rowCondFieldToken:
 			conds[i] = bloomgpu.MatchCond{Kind: bloomgpu.KindFieldToken, Field: c.field, Token: c.token}
+		case rowCondRegex: // at or beneath c.field (fieldWithDelim), the pattern as the caller's regexp compiled it
+			conds[i] = bloomgpu.MatchCond{Kind: bloomgpu.KindFieldRegex, Field: c.field, Token: c.pattern.String()}
 		default:
 			return nil
 		}
@@ -528,7 +549,23 @@ func (e *gpuEngine) matchBlock(rowData []byte, m *compiledRowMatcher) *gpuRowVer
 	}
 	s := e.scope()
 	defer e.release(s)
-	bits, hostRows, err := s.MatchRows(blob, rowOff, conds, ops)
+	var bits []uint64
+	var hostRows []uint32
+	var err error
+	if len(m.regexConds) > 0 {
+		bits, hostRows, err = s.MatchRowsRegex(blob, rowOff, conds, ops)
+		if bloomgpu.IsUnsupported(err) {
+			e.regexMu.Lock()
+			if e.regexRefused == nil || len(e.regexRefused) >= 4096 {
+				e.regexRefused = make(map[string]bool)
+			}
+			e.regexRefused[regexKey] = true
+			e.regexMu.Unlock()
+			return nil
+		}
+	} else {
+		bits, hostRows, err = s.MatchRows(blob, rowOff, conds, ops)
+	}
 	if err != nil {
 		e.logger.Warn("bloomgpu: row match failed; matching this block on the host", "error", err)
 		return nil

@@ -51,6 +51,7 @@ extern "C" {
 #define BSG_KIND_FIELD        0u
 #define BSG_KIND_TOKEN        1u
 #define BSG_KIND_FIELD_TOKEN  2u
+#define BSG_KIND_FIELD_REGEX  3u   /* row matcher only (bsg_match_rows_regex): entry 2i = field, 2i + 1 = pattern */
 
 /* ---- query program opcodes: op = (opcode << 28) | arg, postfix order ----
  * TERM i : push TestString(term i) against the block's filter of term i's kind;
@@ -541,7 +542,24 @@ BSG_API int32_t bsg_match_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t
                                const uint32_t *prog_ops, uint32_t n_ops,
                                uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                uint32_t *out_n_fallback);
-/* Device time of the most recent k_match_rows dispatch (the slowest device's). */
+/* The same call (same arguments, sharding, chunked upload and fallback rows) with FieldRegex conditions as well:
+ * cond_kinds[i] == BSG_KIND_FIELD_REGEX, entry 2i = the field, entry 2i + 1 = the pattern, so one program holds a whole
+ * compileRowMatcher root And(bloom root, regex root) (row_matcher.go:353-368).  A regex condition holds when its pattern
+ * matches (Go regexp MatchString) the candidate text of any leaf whose path equals the field or starts with field + ".":
+ * a string's decoded text, a number's raw literal, true / false — never null; an empty field never holds.
+ * Patterns are compiled per call to byte DFAs for a stated subset of RE2 syntax (bloomsearch_amd/csrc/host/regex_dfa.hpp:
+ * literals, escapes, ., classes, Perl / ASCII POSIX classes, ^ $ \A \z, groups, alternation, counted and lazy
+ * repetition, flags i s U with (?i) over ASCII only); bsh_regex_match (bloomsearch_host.h) runs the same tables on the host.
+ * BSG_E_UNSUPPORTED before anything is launched (message in bsg_last_error naming the construct): a pattern outside the
+ * subset or whose DFA exceeds 1 024 states, more than 16 regex conditions, or tables over 44 544 bytes of LDS.  Callers
+ * validate patterns with their own engine first; the device never decides that a pattern is invalid.  Rows whose leaf
+ * falls under more than 4 regex conditions are fallback rows too. */
+BSG_API int32_t bsg_match_rows_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                     const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                     const uint32_t *prog_ops, uint32_t n_ops,
+                                     uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                     uint32_t *out_n_fallback);
+/* Device time of the most recent k_match_rows / k_match_rows_regex dispatch (the slowest device's). */
 BSG_API int32_t bsg_last_match_ms(bsg_ctx *ctx, float *match_ms);
 
 #ifdef __cplusplus

@@ -70,6 +70,12 @@ BSG_API int32_t bsh_prune_query(const char *bloom_json, uint64_t bloom_len, cons
 /* The regex half of the final row test (row_matcher.go:548-573; std::regex ECMAScript stands in for RE2): 1 / 0 / < 0. */
 BSG_API int32_t bsh_match_row_regex(const char *regex_json, uint64_t regex_len, const uint8_t *row, uint64_t row_len);
 
+/* Go regexp MatchString of `pattern` on `text` for the subset the device row matcher compiles (bsg_match_rows_regex; the
+ * subset is listed in bloomsearch_amd/csrc/host/regex_dfa.hpp), run on the same DFA tables.  The text is read as Go reads a
+ * string: an invalid byte is U+FFFD.  1 match, 0 no match, BSG_E_UNSUPPORTED for a pattern outside the subset (syntax
+ * errors included), BSH_E_INVALID for null pointers. */
+BSG_API int32_t bsh_regex_match(const char *pattern, uint64_t plen, const uint8_t *text, uint64_t tlen);
+
 /* filter section codec; filters[c].m == 0 => absent */
 BSG_API int32_t bsh_section_encode(const uint64_t *const words[3], const uint64_t m[3], const uint64_t k[3],
                                    uint8_t **out, uint64_t *out_len);
@@ -80,12 +86,16 @@ BSG_API uint32_t bsh_crc32c(const uint8_t *data, uint64_t len);
 /* ---- engine mirror ---- */
 typedef struct bse_engine bse_engine;
 /* config_json: {"MaxRowGroupRows":..,"MaxRowGroupBytes":..,"MaxBufferedRows":..,"MaxBufferedBytes":..,
- *               "BloomFalsePositiveRate":..,"PartitionField":"..","DeviceIngest":true|false,"DeviceMatch":true|false}; missing keys take the
+ *               "BloomFalsePositiveRate":..,"PartitionField":"..","DeviceIngest":true|false,"DeviceMatch":true|false,
+ *               "DeviceRegex":true|false}; missing keys take the
  *               reference defaults.  DeviceIngest (default false): rows are walked / tokenized / deduplicated /
  *               counted on the GPU at flush and merge time (bloomgpu.h bsg_ingest_*) instead of by indexRow on the
  *               host at ingest time; the files it writes are byte-identical either way.  DeviceMatch (default false): the
  *               final row test of the surviving blocks runs on the GPU (bsg_match_rows) instead of in the host matcher;
- *               the delivered row set is the same. */
+ *               the delivered row set is the same.  DeviceRegex (default false, needs DeviceMatch):
+ *               a query whose regex patterns all lie in the device's RE2 subset is matched bloom AND regex by one
+ *               bsg_match_rows_regex call, the rows it hands back by the host matcher on the same DFAs; other regex queries
+ *               keep the std::regex path. */
 BSG_API int32_t bse_open(const char *config_json, uint64_t len, bsg_ctx *ctx, bse_engine **out);
 BSG_API void bse_close(bse_engine *e);
 BSG_API const char *bse_last_error(bse_engine *e);

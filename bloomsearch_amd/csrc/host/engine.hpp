@@ -57,6 +57,10 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // matched bloom AND regex by ONE bsg_match_rows_regex call, and the rows it hands back by the host matcher with the same
     // DFAs (RE2 semantics on both sides); other regex queries keep the std::regex path below.  Off by default.
     bool device_regex = false;
+    // Tokenizer (engine.go:83, "for both indexing and verification"), restricted to the separator family
+    // strings.FieldsFunc(lower ? strings.ToLower(v) : v, isSep) (text.hpp Tokenizer): indexRow, the host matcher and the
+    // device calls (bsg_ingest_rows_tok / bsg_match_rows_tok) all use it.  Default: BasicWhitespaceLowerTokenizer.
+    Tokenizer tokenizer;
 };
 
 struct DataBlock {
@@ -146,6 +150,7 @@ public:
         bool should_flush = false;
         for (size_t i = 0; i < rows.size(); ++i) {
             PartitionBuffer &pb = buffers_[pids[i]];
+            pb.entries.tok = cfg_.tokenizer;
             if (!cfg_.device_ingest) pb.entries.index_row(rows[i]);   // HOT: walk + tokenize + dedup (ingest.go:450)
             pb.rows.emplace_back(rows[i]);
             pb.bytes += rows[i].size() + 4;
@@ -214,7 +219,7 @@ public:
         BloomEntrySets file_entries;
         for (auto &kv : by_partition) {
             DataBlock cur;
-            auto start_block = [&]() { cur = DataBlock{}; cur.partition_id = kv.first; cur.fpr = cfg_.bloom_false_positive_rate; block_sets.push_back(std::make_unique<BloomEntrySets>()); };
+            auto start_block = [&]() { cur = DataBlock{}; cur.partition_id = kv.first; cur.fpr = cfg_.bloom_false_positive_rate; block_sets.push_back(std::make_unique<BloomEntrySets>(cfg_.tokenizer)); };
             auto finish_block = [&]() {
                 if (!cfg_.device_ingest) {
                     cur.counts = block_sets.back()->counts();
@@ -319,7 +324,7 @@ public:
         size_t candidate_blocks = 0;
         for (size_t f = 0; f < files_.size(); ++f) if (file_ok[f]) candidate_blocks += files_[f].blocks.size();
         const int64_t probe_share = candidate_blocks ? std::max<int64_t>(1, probe_ns / (int64_t)candidate_blocks) : 0;
-        RowMatcher matcher(row_expr);
+        RowMatcher matcher(row_expr, cfg_.tokenizer);
         RegexRowMatcher regex_matcher(regex);
         RegexRowMatcher regex_dfa(cfg_.device_regex && cfg_.device_match ? regex : nullptr, true);
         const bool regex_on_device = regex && cfg_.device_regex && cfg_.device_match && regex_dfa.valid();
@@ -377,7 +382,7 @@ public:
             std::vector<uint8_t> cand(scan.size(), 1);
             bool guard_on_device = false;
             if (cfg_.device_match && has_guard && regex_guard_is_exact(*regex) && !scan.empty()) {
-                RowMatcher guard_host(&guard);
+                RowMatcher guard_host(&guard, cfg_.tokenizer);
                 if (int32_t rc = match_rows_device(&guard, scan, guard_host, cand, guard_on_device)) return rc;
                 if (!guard_on_device) std::fill(cand.begin(), cand.end(), 1);
             }
@@ -394,6 +399,15 @@ public:
     }
 
 private:
+    bsg_tokenizer c_tokenizer() const
+    {
+        bsg_tokenizer t{};
+        t.sep_ascii[0] = cfg_.tokenizer.sep[0];
+        t.sep_ascii[1] = cfg_.tokenizer.sep[1];
+        t.flags = cfg_.tokenizer.flags;
+        return t;
+    }
+
     struct PartitionBuffer {
         BloomEntrySets entries;
         std::vector<std::string> rows;
@@ -540,8 +554,9 @@ private:
             first.push_back((uint32_t)set_of_row.size());
         }
         uint64_t ing = 0;
-        if (bsg_ingest_rows(ctx_, bytes.data(), row_off.data(), (uint32_t)set_of_row.size(), first.data(), (uint32_t)nb,
-                            parent.data(), 1, nullptr, BSG_INGEST_TRUSTED_JSON /* ingest_rows validated every row */, &ing))
+        const bsg_tokenizer tok = c_tokenizer();
+        if (bsg_ingest_rows_tok(ctx_, bytes.data(), row_off.data(), (uint32_t)set_of_row.size(), first.data(), (uint32_t)nb,
+                                parent.data(), 1, nullptr, BSG_INGEST_TRUSTED_JSON /* ingest_rows validated every row */, &tok, &ing))
             return fail(kErrGpu, bsg_last_error(ctx_));
         struct Free { bsg_ctx *c; uint64_t id; ~Free() { bsg_ingest_free(c, id); } } guard{ctx_, ing};
         uint32_t n_fb = 0;
@@ -552,7 +567,7 @@ private:
             std::map<uint32_t, BloomEntrySets> per_set;
             for (uint32_t r : fb) {
                 const uint32_t b = set_of_row[r];
-                per_set[b].index_row(file.blocks[b].rows[r - first[b]]);
+                per_set.try_emplace(b, cfg_.tokenizer).first->second.index_row(file.blocks[b].rows[r - first[b]]);
             }
             std::vector<uint8_t> eb;
             std::vector<uint32_t> eo{0}, es, ek;
@@ -615,7 +630,7 @@ private:
         BloomEntrySets file_entries;
         std::vector<const BloomEntrySets *> sets;
         for (auto &blk : file.blocks) {
-            block_sets.push_back(std::make_unique<BloomEntrySets>());
+            block_sets.push_back(std::make_unique<BloomEntrySets>(cfg_.tokenizer));
             for (const std::string &r : blk.rows) block_sets.back()->index_row(r);
             blk.counts = block_sets.back()->counts();
             block_sets.back()->union_into(file_entries);
@@ -671,9 +686,10 @@ private:
         std::vector<uint64_t> bits((scan.size() + 63) / 64);
         std::vector<uint32_t> fb(scan.size());
         uint32_t n_fb = 0;
-        const int32_t rc = bsg_match_rows_regex(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
-                                                mp.kinds.data(), (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(),
-                                                bits.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
+        const bsg_tokenizer tok = c_tokenizer();
+        const int32_t rc = bsg_match_rows_tok(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
+                                              mp.kinds.data(), (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok,
+                                              bits.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
         if (rc == BSG_E_UNSUPPORTED) return kEngineOk;
         if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
         for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
@@ -703,9 +719,10 @@ private:
         std::vector<uint64_t> bits((scan.size() + 63) / 64);
         std::vector<uint32_t> fb(scan.size());
         uint32_t n_fb = 0;
-        const int32_t rc = bsg_match_rows(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(),
-                                          (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), bits.data(), fb.data(),
-                                          (uint32_t)fb.size(), &n_fb);
+        const bsg_tokenizer tok = c_tokenizer();
+        const int32_t rc = bsg_match_rows_tok(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(),
+                                              (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok, bits.data(), fb.data(),
+                                              (uint32_t)fb.size(), &n_fb);
         if (rc == BSG_E_UNSUPPORTED) return kEngineOk;      // expression too deep / long: host matcher
         if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
         for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;

@@ -19,8 +19,12 @@ struct BloomEntryCounts { uint64_t fields = 0, tokens = 0, field_tokens = 0; }; 
 class BloomEntrySets {
 public:
     std::unordered_set<std::string> fields, tokens, field_tokens;
+    Tokenizer tok;   // the engine's tokenizer (default: BasicWhitespaceLowerTokenizer)
 
-    // indexRow (ingest.go:55-89) with the BasicWhitespaceLowerTokenizer fast path.
+    BloomEntrySets() = default;
+    explicit BloomEntrySets(const Tokenizer &t) : tok(t) {}
+
+    // indexRow (ingest.go:55-89) with the BasicWhitespaceLowerTokenizer fast path, or tok's words.
     // Returns false when the row is not valid JSON (nothing is rolled back: entries seen
     // before the error stay, as they would for the reference's lenient parser).
     bool index_row(std::string_view row)
@@ -29,11 +33,9 @@ public:
             path_scratch_.assign(e.path);
             fields.insert(path_scratch_);
             if (!e.is_leaf || !e.has_text) return true;  // null: field existence only (tokenizer.go:130-131)
-            for_each_word(e.text, [&](std::string_view word) {
-                token_buf_.clear();
-                append_folded_word(token_buf_, word);
-                tokens.insert(token_buf_);
-                add_field_token(e.path, token_buf_);
+            for_each_token(e.text, tok, token_buf_, [&](std::string_view token) {
+                tokens.insert(std::string(token));
+                add_field_token(e.path, token);
                 return true;
             });
             return true;

@@ -379,7 +379,8 @@ private:
 
 class RowMatcher {
 public:
-    explicit RowMatcher(const BloomExpression *expression)
+    explicit RowMatcher(const BloomExpression *expression, const Tokenizer &tok = Tokenizer())
+        : tok_(tok)
     {
         if (expression) { root_ = *expression; has_root_ = true; collect(root_); }
     }
@@ -394,14 +395,12 @@ public:
             for (size_t i = 0; i < conds_.size(); ++i)
                 if (!sat_[i] && conds_[i]->type == CondType::Field && e.path == conds_[i]->field) sat_[i] = 1;
             if (!e.is_leaf || !e.has_text || !wants_tokens_) return true;
-            for_each_word(e.text, [&](std::string_view word) {
-                fold_.clear();
-                append_folded_word(fold_, word);
+            for_each_token(e.text, tok_, fold_, [&](std::string_view word) {
                 for (size_t i = 0; i < conds_.size(); ++i) {
                     if (sat_[i]) continue;
                     const BloomCondition &c = *conds_[i];
-                    if (c.type == CondType::Token) { if (fold_ == c.token) sat_[i] = 1; }               // targets never normalised
-                    else if (c.type == CondType::FieldToken) { if (e.path == c.field && fold_ == c.token) sat_[i] = 1; }
+                    if (c.type == CondType::Token) { if (word == c.token) sat_[i] = 1; }                // targets never normalised
+                    else if (c.type == CondType::FieldToken) { if (e.path == c.field && word == c.token) sat_[i] = 1; }
                 }
                 return true;
             });
@@ -417,6 +416,7 @@ private:
     std::vector<const BloomCondition *> conds_;  // pre-order, matching eval()'s traversal
     std::vector<uint8_t> sat_;
     PathWalker walker_;
+    Tokenizer tok_;
     std::string fold_;
 
     void collect(const BloomExpression &e)

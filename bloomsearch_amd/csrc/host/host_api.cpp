@@ -63,6 +63,37 @@ bool parse_expression_json(const char *json, uint64_t len, BloomExpression &expr
     return expression_from_json(dom, expr);
 }
 
+// a C spec -> the host mirror's Tokenizer (NULL = the default); false for an invalid spec (bloomgpu.h bsg_tokenizer)
+bool tokenizer_from(const bsg_tokenizer *in, Tokenizer &out)
+{
+    out = Tokenizer();
+    if (!in) return true;
+    if ((in->sep_ascii[0] & 1u) || in->reserved || (in->flags & ~(BSG_TOK_UNICODE_SPACE | BSG_TOK_LOWER))) return false;
+    out.sep[0] = in->sep_ascii[0];
+    out.sep[1] = in->sep_ascii[1];
+    out.flags = in->flags;
+    return true;
+}
+
+// "Tokenizer": {"Separators": "...", "UnicodeSpace": bool, "Lower": bool}; a missing key is Go's zero value ("", false).
+// false: not an object, a separator that is NUL or not ASCII.
+bool tokenizer_from_json(const JNode &n, Tokenizer &out)
+{
+    if (n.type != JType::Object) return false;
+    out.sep[0] = out.sep[1] = 0;
+    out.flags = 0;
+    if (const JNode *s = n.get("Separators")) {
+        if (s->type != JType::String) return false;
+        for (unsigned char c : s->text) {
+            if (c == 0 || c >= 0x80) return false;
+            out.sep[c >> 6] |= 1ull << (c & 63);
+        }
+    }
+    if (const JNode *u = n.get("UnicodeSpace")) { if (u->type == JType::True) out.flags |= Tokenizer::kUnicodeSpace; }
+    if (const JNode *l = n.get("Lower")) { if (l->type == JType::True) out.flags |= Tokenizer::kLower; }
+    return true;
+}
+
 uint64_t num_or(const JNode &cfg, const char *key, uint64_t dflt)
 {
     const JNode *n = cfg.get(key);
@@ -89,6 +120,20 @@ int32_t bsh_tokenize(const uint8_t *text, uint64_t len, char **out, uint64_t *ou
     return give(joined, out, out_len);
 }
 
+int32_t bsh_tokenize_with(const uint8_t *text, uint64_t len, const bsg_tokenizer *tok, uint8_t **out, uint64_t *out_len)
+{
+    Tokenizer t;
+    if (!out || !tokenizer_from(tok, t)) return BSH_E_INVALID;
+    std::string packed, buf;
+    for_each_token(std::string_view(reinterpret_cast<const char *>(text), len), t, buf, [&](std::string_view w) {
+        const uint32_t n = (uint32_t)w.size();
+        for (int i = 0; i < 4; ++i) packed.push_back((char)(n >> (8 * i)));
+        packed.append(w);
+        return true;
+    });
+    return give(packed, reinterpret_cast<char **>(out), out_len);
+}
+
 bsh_entry_sets *bsh_entry_sets_new(void) { return new bsh_entry_sets(); }
 void bsh_entry_sets_free(bsh_entry_sets *s) { delete s; }
 
@@ -96,6 +141,16 @@ int32_t bsh_entry_sets_index_row(bsh_entry_sets *s, const uint8_t *row, uint64_t
 {
     if (!s) return BSH_E_INVALID;
     return s->sets.index_row(std::string_view(reinterpret_cast<const char *>(row), len)) ? 0 : BSH_E_INVALID;
+}
+
+int32_t bsh_entry_sets_index_row_with(bsh_entry_sets *s, const uint8_t *row, uint64_t len, const bsg_tokenizer *tok)
+{
+    Tokenizer t;
+    if (!s || !tokenizer_from(tok, t)) return BSH_E_INVALID;
+    s->sets.tok = t;
+    const bool ok = s->sets.index_row(std::string_view(reinterpret_cast<const char *>(row), len));
+    s->sets.tok = Tokenizer();
+    return ok ? 0 : BSH_E_INVALID;
 }
 
 int32_t bsh_entry_sets_union_into(const bsh_entry_sets *src, bsh_entry_sets *dst)
@@ -182,6 +237,16 @@ int32_t bsh_match_row(const char *expr_json, uint64_t expr_len, const uint8_t *r
     bool nil = true;
     if (!parse_expression_json(expr_json, expr_len, e, nil)) return BSH_E_INVALID;
     RowMatcher m(nil ? nullptr : &e);
+    return m.match(std::string_view(reinterpret_cast<const char *>(row), row_len)) ? 1 : 0;
+}
+
+int32_t bsh_match_row_with(const char *expr_json, uint64_t expr_len, const uint8_t *row, uint64_t row_len, const bsg_tokenizer *tok)
+{
+    BloomExpression e;
+    bool nil = true;
+    Tokenizer t;
+    if (!tokenizer_from(tok, t) || !parse_expression_json(expr_json, expr_len, e, nil)) return BSH_E_INVALID;
+    RowMatcher m(nil ? nullptr : &e, t);
     return m.match(std::string_view(reinterpret_cast<const char *>(row), row_len)) ? 1 : 0;
 }
 
@@ -292,7 +357,7 @@ uint32_t bsh_crc32c(const uint8_t *data, uint64_t len) { return crc32c(data, len
 // ---- engine ----
 int32_t bse_open(const char *config_json, uint64_t len, bsg_ctx *ctx, bse_engine **out)
 {
-    if (!out || !ctx) return BSH_E_INVALID;
+    if (!out) return BSH_E_INVALID;
     *out = nullptr;
     EngineConfig cfg;
     std::string_view sv(config_json ? config_json : "", config_json ? len : 0);
@@ -308,9 +373,13 @@ int32_t bse_open(const char *config_json, uint64_t len, bsg_ctx *ctx, bse_engine
         if (const JNode *n = dom.get("DeviceIngest")) cfg.device_ingest = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatch")) cfg.device_match = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceRegex")) cfg.device_regex = n->type == JType::True;
+        if (const JNode *n = dom.get("Tokenizer")) {
+            if (n->type != JType::Null && !tokenizer_from_json(*n, cfg.tokenizer)) return BSE_E_INVALID_CONFIG;
+        }
     }
     std::string err;
     if (int32_t rc = BloomSearchEngine::validate(cfg, err)) return rc;
+    if (!ctx) return BSH_E_INVALID;     // (after the config: a config is checked without a device)
     auto *e = new bse_engine();
     e->eng = std::make_unique<BloomSearchEngine>(cfg, ctx);
     *out = e;

@@ -2,7 +2,8 @@
 // whitespace+lowercase tokenizer, byte-for-byte as Go's standard library behaves
 // for the reference's BasicWhitespaceLowerTokenizer = strings.Fields(strings.ToLower(v))
 // (tokenizer.go:141-143) and its zero-alloc twin forEachWord + appendFoldedWord
-// (row_matcher.go:142-202).
+// (row_matcher.go:142-202); and the separator family it belongs to,
+// strings.FieldsFunc(lower ? strings.ToLower(v) : v, isSep) (Tokenizer, for_each_token).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -150,6 +151,58 @@ inline void append_folded_word(std::string &dst, std::string_view word)
         i += w;
         append_rune(dst, to_lower(r));
     }
+}
+
+// A tokenizer of the separator family (bloomgpu.h bsg_tokenizer): tokens = FieldsFunc(lower ? ToLower(text) : text, isSep),
+// isSep(r) = bit r of sep for ASCII r, unicode.IsSpace(r) for r >= 0x80 under kUnicodeSpace.  The default members are
+// BasicWhitespaceLowerTokenizer's.
+struct Tokenizer {
+    static constexpr uint32_t kUnicodeSpace = 1, kLower = 2;      // BSG_TOK_UNICODE_SPACE, BSG_TOK_LOWER
+    static constexpr uint64_t kWhiteSpace = (1ull << 9) | (1ull << 10) | (1ull << 11) | (1ull << 12) | (1ull << 13) | (1ull << 32);
+    uint64_t sep[2] = {kWhiteSpace, 0};
+    uint32_t flags = kUnicodeSpace | kLower;
+
+    bool is_default() const { return sep[0] == kWhiteSpace && sep[1] == 0 && flags == (kUnicodeSpace | kLower); }
+    bool lower() const { return (flags & kLower) != 0; }
+    // the rune AFTER lowering
+    bool is_sep(uint32_t r) const { return r < 0x80 ? ((sep[r >> 6] >> (r & 63)) & 1) != 0 : ((flags & kUnicodeSpace) != 0 && is_space(r)); }
+    bool operator==(const Tokenizer &o) const { return sep[0] == o.sep[0] && sep[1] == o.sep[1] && flags == o.flags; }
+};
+
+// fn(token) for each token of `text` under t, the token's bytes as they are after lowering (buf is scratch).  The default
+// tokenizer takes the forEachWord + appendFoldedWord path above.  strings.ToLower turns an invalid byte into U+FFFD;
+// without lowering FieldsFunc keeps the raw byte inside its word (it decodes it as U+FFFD, which is no separator).
+template <class F>
+inline void for_each_token(std::string_view text, const Tokenizer &t, std::string &buf, F &&fn)
+{
+    if (t.is_default()) {
+        for_each_word(text, [&](std::string_view word) {
+            buf.clear();
+            append_folded_word(buf, word);
+            return fn(std::string_view(buf));
+        });
+        return;
+    }
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(text.data());
+    const size_t n = text.size();
+    buf.clear();
+    for (size_t i = 0; i < n;) {
+        size_t w;
+        uint32_t r = decode_rune(p + i, n - i, w);
+        if (t.lower()) r = to_lower(r);
+        if (t.is_sep(r)) {
+            if (!buf.empty()) {
+                if (!fn(std::string_view(buf))) return;
+                buf.clear();
+            }
+        } else if (t.lower()) {
+            append_rune(buf, r);
+        } else {
+            buf.append(text.data() + i, w);
+        }
+        i += w;
+    }
+    if (!buf.empty()) fn(std::string_view(buf));
 }
 
 }  // namespace bsh

@@ -400,21 +400,83 @@ __device__ __forceinline__ void leaf_start(Walker &w)
     if (!w.quiet) { w.req = Q_LEAF; w.req_len = w.path_len; }
 }
 
-__device__ __forceinline__ void word_byte(Walker &w, uint32_t c)
+// unicode.IsSpace below 0x80: \t \n \v \f \r and space (forEachWord, row_matcher.go:142-181)
+__device__ __forceinline__ bool ascii_space(uint32_t b) { return b == ' ' || (b - 9u) <= 4u; }
+// unicode.IsSpace above 0x7F (text.hpp is_space)
+__device__ __forceinline__ bool rune_space(uint32_t r)
+{
+    return r == 0x85u || r == 0xA0u || r == 0x1680u || (r - 0x2000u) <= 0xAu || r == 0x2028u || r == 0x2029u || r == 0x202Fu ||
+           r == 0x205Fu || r == 0x3000u;
+}
+
+// ---------------- tokenizer policies ----------------
+// Where a word ends and whether a rune is folded (bloomgpu.h bsg_tokenizer: tokens = FieldsFunc(lower ? ToLower(text) : text,
+// isSep)).  TokDefault is BasicWhitespaceLowerTokenizer and compiles to the walker as it was before the policies existed.
+// TokSpec is one spec of the separator family, passed by value in the kernel arguments (uniform: it lives in SGPRs); the host
+// (ingest_api.inc tok_spec) derives its bitmaps from the caller's spec:
+struct TokSpec {
+    uint64_t raw[2];      // bit c: the TEXT's ASCII byte c ends a word, i.e. isSep(lower ? fold(c) : c)
+    uint64_t run[2];      // raw without '"', '\\', DEL and controls: the separators the S_STR run scan stops on
+    uint64_t low[2];      // bit c: an ASCII rune c AFTER lowering ends a word (a non-ASCII rune may lower to one: U+212A -> k)
+    uint32_t flags;       // BSG_TOK_UNICODE_SPACE (1): runes >= 0x80 with unicode.IsSpace end a word; BSG_TOK_LOWER (2)
+    uint32_t pad;
+};
+constexpr uint32_t kTokUnicodeSpace = 1u, kTokLower = 2u;
+
+__device__ __forceinline__ bool bit128(const uint64_t m[2], uint32_t c) { return ((m[(c >> 6) & 1u] >> (c & 63u)) & 1u) != 0u; }
+
+struct TokDefault {
+    static constexpr bool kSpec = false;
+    __device__ __forceinline__ bool lower() const { return true; }
+    __device__ __forceinline__ bool sep_byte(uint32_t b) const { return ascii_space(b); }
+    __device__ __forceinline__ bool run_sep(uint32_t b) const { return b == ' '; }          // a byte the S_STR run scan stopped on
+};
+
+// The run scan's separators: one bitmap test per byte lane (the spec's 128-bit map, two 64-bit words), whatever the spec holds —
+// its cost does not grow with the number of separators.  Measured on MI355X, 1 M synth rows (tools/tokenizer_lab.py,
+// profiles/tokenizer_lab.txt): the default spec plus byte 0x01 (same words, so the difference is this scan) walks in 3.64 ms
+// against k_ingest_rows' 3.25 ms (1.12x); the 18-separator punctuation spec 3.88 ms for 10 % more words (1.08x per word).
+// Per-separator swar_eq and a coarse SWAR punctuation filter were not tried: the bitmap already meets the 1.25x bar.
+struct TokSpecP {
+    static constexpr bool kSpec = true;
+    TokSpec t;
+    __device__ __forceinline__ bool lower() const { return (t.flags & kTokLower) != 0u; }
+    __device__ __forceinline__ bool sep_byte(uint32_t b) const { return bit128(t.raw, b); }      // an ASCII byte of the text
+    __device__ __forceinline__ bool run_sep(uint32_t b) const { return b < 0x80u && bit128(t.run, b); }
+    __device__ __forceinline__ bool sep_rune(uint32_t r) const                                      // a rune after lowering
+    {
+        return r < 0x80u ? bit128(t.low, r) : ((t.flags & kTokUnicodeSpace) != 0u && rune_space(r));
+    }
+    // 0x80 in the byte lanes of v that hold a run separator (exact in every lane; bytes >= 0x80 are stops anyway)
+    __device__ __forceinline__ uint64_t run_stops(uint64_t v) const
+    {
+        uint64_t m = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 8; ++i) {
+            const uint32_t c = (uint32_t)(v >> (8u * i)) & 0xFFu;
+            m |= (uint64_t)bit128(t.run, c) << (8u * i + 7u);
+        }
+        return m;
+    }
+};
+
+template <class TOK>
+__device__ __forceinline__ void word_byte(Walker &w, uint32_t c, const TOK &tk)
 {
     if (w.quiet) return;
     if (!w.in_token) { hs_init(w.tok, w.key); w.ft = w.ps; w.in_token = true; }
-    if (c - 'A' < 26u) c += 32;                    // ASCII fold (appendFoldedWord fast path, row_matcher.go:187-202)
+    if (tk.lower() && c - 'A' < 26u) c += 32;      // ASCII fold (appendFoldedWord fast path, row_matcher.go:187-202)
     hs_absorb(w.tok, c, w.key);
     if (w.ft_on) hs_absorb(w.ft, c, w.key);
 }
 
 // n (1..8) word bytes, little-endian in v, upper bytes zero
-__device__ __forceinline__ void word_run(Walker &w, uint64_t v, uint32_t n)
+template <class TOK>
+__device__ __forceinline__ void word_run(Walker &w, uint64_t v, uint32_t n, const TOK &tk)
 {
     if (w.quiet) return;
     if (!w.in_token) { hs_init(w.tok, w.key); w.ft = w.ps; w.in_token = true; }
-    v = swar_lower(v);                             // ASCII fold (appendFoldedWord fast path, row_matcher.go:187-202)
+    if (tk.lower()) v = swar_lower(v);             // ASCII fold (appendFoldedWord fast path, row_matcher.go:187-202)
     hs_absorb_n(w.tok, v, n, w.key);
     if (w.ft_on) hs_absorb_n(w.ft, v, n, w.key);
 }
@@ -470,22 +532,13 @@ __device__ __forceinline__ uint32_t hex_value(uint32_t c)
     const uint32_t l = c | 0x20u;
     return (l - 'a' <= 5u) ? l - 'a' + 10u : 0xFFu;
 }
-// unicode.IsSpace below 0x80: \t \n \v \f \r and space (forEachWord, row_matcher.go:142-181)
-__device__ __forceinline__ bool ascii_space(uint32_t b) { return b == ' ' || (b - 9u) <= 4u; }
-
-// a decoded (escaped) byte of a string value: white space ends the word, anything else belongs to it
-__device__ __forceinline__ bool str_decoded_byte(Walker &w, uint32_t b)
+// a decoded (escaped) byte of a string value: a separator (white space by default) ends the word, anything else belongs to it
+template <class TOK>
+__device__ __forceinline__ bool str_decoded_byte(Walker &w, uint32_t b, const TOK &tk)
 {
-    if (ascii_space(b)) return word_end(w);
-    word_byte(w, b);
+    if (tk.sep_byte(b)) return word_end(w);
+    word_byte(w, b, tk);
     return false;
-}
-
-// unicode.IsSpace above 0x7F (text.hpp is_space)
-__device__ __forceinline__ bool rune_space(uint32_t r)
-{
-    return r == 0x85u || r == 0xA0u || r == 0x1680u || (r - 0x2000u) <= 0xAu || r == 0x2028u || r == 0x2029u || r == 0x202Fu ||
-           r == 0x205Fu || r == 0x3000u;
 }
 // UTF-8 encoding of a rune >= 0x80 (not a surrogate, <= 0x10FFFF) as little-endian bytes in a u32; n = its length
 __device__ __forceinline__ uint32_t rune_utf8(uint32_t r, uint32_t &n)
@@ -499,13 +552,25 @@ __device__ __forceinline__ uint32_t rune_utf8(uint32_t r, uint32_t &n)
 // as the UTF-8 bytes of unicode.ToLower(rune) — the simple one-rune mapping, looked up in the table the host walker
 // folds with (the lower-case form may be shorter or longer than the original, or plain ASCII: U+212A -> 'k').
 // Returns R_CONTINUE + request, or 0xFF = keep going.
-__device__ __forceinline__ uint32_t str_rune(Walker &w, uint32_t r)
+// TokSpec: the rune is lowered first (LOWER only) and the LOWERED rune is tested (an ASCII result against the spec's map, a
+// non-ASCII one against unicode.IsSpace under UNICODE_SPACE); without LOWER no table is read, so no code point goes to the host.
+template <class TOK>
+__device__ __forceinline__ uint32_t str_rune(Walker &w, uint32_t r, const TOK &tk)
 {
-    if (rune_space(r)) return word_end(w) ? R_CONTINUE : 0xFFu;
-    // (the validation pass looks the rune up too: a code point these tables do not know sends the row to the host, whose
-    // own unicode.ToLower decides — a newer Unicode may have made it a cased letter)
-    const uint32_t lo = r < 0x20000u ? w.lower[r] : 0u;
-    if (lo == 0xFFFFFFFFu) return R_FAIL;
+    uint32_t lo = 0u;
+    if constexpr (TOK::kSpec) {
+        if (tk.lower()) {
+            lo = r < 0x20000u ? w.lower[r] : 0u;
+            if (lo == 0xFFFFFFFFu) return R_FAIL;
+        }
+        if (tk.sep_rune(lo != 0u ? lo : r)) return word_end(w) ? R_CONTINUE : 0xFFu;
+    } else {
+        if (rune_space(r)) return word_end(w) ? R_CONTINUE : 0xFFu;
+        // (the validation pass looks the rune up too: a code point these tables do not know sends the row to the host, whose
+        // own unicode.ToLower decides — a newer Unicode may have made it a cased letter)
+        lo = r < 0x20000u ? w.lower[r] : 0u;
+        if (lo == 0xFFFFFFFFu) return R_FAIL;
+    }
     if (!w.quiet) {
         if (lo != 0u) r = lo;
         uint32_t n = 1, bytes = r;
@@ -541,8 +606,8 @@ struct ChunkCursor {
 // S_KEY_OPEN when their byte sits in the same chunk and a has-dots flag for S_PREFIX (no change), the rare escape /
 // UTF-8 states behind one test (slower: 8.9 -> 11.1 ms per 3 M rows, the structurizer's layout got worse), S_STR / S_KEY
 // runs continuing into the next chunk within one trip (8.76 -> 9.05 ms).
-template <bool EMIT, class RX>
-__device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &rx)
+template <bool EMIT, class RX, class TOK>
+__device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &rx, const TOK &tk)
 {
     lds_u8 *stack = w.path + kPathCap;
     if ((w.pos >> 3) != cc.ci) {                      // the step before ended on the chunk boundary
@@ -652,7 +717,7 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &
                 w.path[w.key_len++] = (uint8_t)b;
             } else {
                 rx.feed(b);
-                if (str_decoded_byte(w, b)) return R_CONTINUE;
+                if (str_decoded_byte(w, b, tk)) return R_CONTINUE;
             }
             break;
         }
@@ -684,10 +749,10 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &
                 for (uint32_t i = 0; i < n; ++i) w.path[w.key_len++] = (uint8_t)(bytes >> (8u * i));
             } else if (cp < 0x80u) {
                 rx.feed(cp);
-                if (str_decoded_byte(w, cp)) return R_CONTINUE;
+                if (str_decoded_byte(w, cp, tk)) return R_CONTINUE;
             } else {
                 rx.feed_rune(cp);
-                const uint32_t r = str_rune(w, cp);
+                const uint32_t r = str_rune(w, cp, tk);
                 if (r != 0xFFu) return r;
             }
             break;
@@ -715,7 +780,7 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &
             if (left > 1) { w.lit = ((left - 1) << 28) | (0xBFu << 16) | (0x80u << 8); break; }
             w.st = S_STR;
             rx.feed_rune(w.aux);
-            const uint32_t r = str_rune(w, w.aux);
+            const uint32_t r = str_rune(w, w.aux, tk);
             if (r != 0xFFu) return r;
             break;
         }
@@ -731,19 +796,21 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &
             uint32_t avail = 8u - k;
             if (w.end - w.pos < avail) avail = (uint32_t)(w.end - w.pos);
             const uint64_t v = w.cur >> (k * 8u);
-            const uint64_t stops = swar_str_stops(v);
+            uint64_t stops;
+            if constexpr (TOK::kSpec) stops = swar_key_stops(v) | (v & kHighs) | tk.run_stops(v);   // quote, backslash, DEL, controls, non-ASCII, separators
+            else stops = swar_str_stops(v);
             uint32_t n = stops ? (uint32_t)(__builtin_ctzll(stops) >> 3) : 8u;
             if (n > avail) n = avail;
             if (n != 0u) {
                 rx.feed_run(v, n);
-                word_run(w, n == 8u ? v : (v & ((1ULL << (n * 8u)) - 1ULL)), n);
+                word_run(w, n == 8u ? v : (v & ((1ULL << (n * 8u)) - 1ULL)), n, tk);
                 w.pos += n;
             }
             if (n < avail) {                                        // stopped on a byte inside the chunk
                 const uint32_t b = c_at(v, n);
                 ++w.pos;
                 if (b == '"') { w.st = S_AFTER; if (word_end(w)) return R_CONTINUE; }
-                else if (b == ' ') { rx.feed(b); if (word_end(w)) return R_CONTINUE; }   // raw white space other than 0x20 fails here
+                else if (tk.run_sep(b)) { rx.feed(b); if (word_end(w)) return R_CONTINUE; }   // raw white space other than 0x20 fails here
                 else if (b == '\\') w.st = S_STR_ESC;
                 else if (b >= 0xC2u && b <= 0xF4u) {                // UTF-8 lead byte (decode_rune, text.hpp)
                     uint32_t left, lo = 0x80u, hi = 0xBFu;
@@ -759,7 +826,12 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &
         }
         case S_NUM: {                                               // the token is the RAW literal (tokenizer.go:124-125)
             const uint32_t nx = num_next(w.aux, c);
-            if (nx != 0xFFu) { w.aux = nx; rx.feed(c); word_byte(w, c); ++w.pos; break; }
+            if (nx != 0xFFu) {
+                w.aux = nx; rx.feed(c); ++w.pos;
+                if (TOK::kSpec && tk.sep_byte(c)) { if (word_end(w)) return R_CONTINUE; }   // "-1.5e-3" with '.' '-': 1, 5e, 3
+                else word_byte(w, c, tk);
+                break;
+            }
             if (!num_accepting(w.aux)) return R_FAIL;
             w.st = S_AFTER;                                         // c is not part of the number: S_AFTER looks at it
             if (word_end(w)) return R_CONTINUE;
@@ -772,7 +844,17 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &
             if (c != want) return R_FAIL;
             ++w.pos;
             ++w.aux;
-            if (w.lit != 2u) { rx.feed(c); word_byte(w, c); }       // null: field existence only (tokenizer.go:130-131)
+            if constexpr (TOK::kSpec) {
+                bool ended = false;                                 // a separator inside true / false splits it
+                if (w.lit != 2u) { rx.feed(c); if (tk.sep_byte(c)) ended = word_end(w); else word_byte(w, c, tk); }
+                if (w.aux == (w.lit == 1u ? 5u : 4u)) {
+                    w.st = S_AFTER;
+                    ended |= word_end(w);                           // (never both: a separator has already closed the word)
+                }
+                if (ended) return R_CONTINUE;
+                break;
+            }
+            if (w.lit != 2u) { rx.feed(c); word_byte(w, c, tk); }   // null: field existence only (tokenizer.go:130-131)
             if (w.aux == (w.lit == 1u ? 5u : 4u)) {
                 w.st = S_AFTER;
                 if (word_end(w)) return R_CONTINUE;
@@ -862,16 +944,17 @@ __device__ __forceinline__ void walker_reset(Walker &w, ChunkCursor &cc, uint64_
     cc.nxt = live ? cc.chunks[cc.ci + 1] : 0;
 }
 
-template <bool EMIT>
-__device__ __forceinline__ uint32_t advance(Walker &w, ChunkCursor &cc) { RxNone rx; return walker_step<EMIT>(w, cc, rx); }
-template <bool EMIT, class RX>
-__device__ __forceinline__ uint32_t advance(Walker &w, ChunkCursor &cc, RX &rx) { return walker_step<EMIT>(w, cc, rx); }
+template <bool EMIT, class TOK>
+__device__ __forceinline__ uint32_t advance(Walker &w, ChunkCursor &cc, const TOK &tk) { RxNone rx; return walker_step<EMIT>(w, cc, rx, tk); }
+template <bool EMIT, class RX, class TOK>
+__device__ __forceinline__ uint32_t advance(Walker &w, ChunkCursor &cc, RX &rx, const TOK &tk) { return walker_step<EMIT>(w, cc, rx, tk); }
 
 // One wave walks a contiguous run of rows_per_wave rows, 64 at a time (lane = row); the four waves of a workgroup take
 // neighbouring runs, so a workgroup stays inside one block (or two) and its dedup cache stays warm: a workgroup that
 // sees each lane's row only once sends ~15 of a row's 32 emission rounds to the table (every entry is new to IT), one
 // that has walked a few rows per lane only the 2-3 rounds whose entries are new to the block (timestamps, ids).
-__global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows(const IngestArgs a)
+template <class TOK>
+__device__ __forceinline__ void ingest_rows_body(const IngestArgs &a, const TOK &tk)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     lds_u64i *cache = (lds_u64i *)lds_raw;
@@ -913,7 +996,7 @@ __global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows(
         walker_reset(w, cc, row_begin, row_end, live);
         res = live ? R_CONTINUE : R_DONE;
         while (__ballot(res == R_CONTINUE) != 0ull)
-            if (res == R_CONTINUE) res = advance<false>(w, cc);
+            if (res == R_CONTINUE) res = advance<false>(w, cc, tk);
         if (res == R_FAIL) {
             const uint32_t slot = __hip_atomic_fetch_add(a.n_fallback, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             a.fallback_rows[slot] = r;
@@ -933,7 +1016,7 @@ __global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows(
         w.iters = 0;
 #endif
         while (__ballot(res == R_CONTINUE && w.req == Q_NONE) != 0ull)
-            if (res == R_CONTINUE && w.req == Q_NONE) res = advance<true>(w, cc);
+            if (res == R_CONTINUE && w.req == Q_NONE) res = advance<true>(w, cc, tk);
         BSG_PROF_T(ta1);
         BSG_PROF_ADD(2, ta0, ta1);
         BSG_PROF_ADD(5, 0, 1);
@@ -990,6 +1073,10 @@ __global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows(
     }
     BSG_PROF_FLUSH();
 }
+
+__global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows(const IngestArgs a) { ingest_rows_body(a, TokDefault{}); }
+// the same walk under a separator-family tokenizer spec (bsg_ingest_rows_tok)
+__global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows_tok(const IngestArgs a, const TokSpec t) { ingest_rows_body(a, TokSpecP{t}); }
 
 // ---------------- host-walked entries (fallback rows) ----------------
 __global__ __launch_bounds__(256) void k_ingest_add(const uint8_t *bytes, const uint32_t *off, const uint32_t *table_of_entry,

@@ -44,6 +44,7 @@ struct Ingest {
     std::shared_ptr<IngestPart> merged;       // the parents, unioned across parts on the first part's device (several parts only)
     std::vector<uint32_t> fallback;           // caller's row indices, ascending
     std::vector<uint32_t> counts, status;     // caller's numbering: sets, then parents
+    bsg_tokenizer tok{};                      // the spec the rows were tokenized with (bsg_ingest_rows_tok; default otherwise)
     bool finished = false;
     float ms_merge = 0.f, ms_build = 0.f, ms_encode = 0.f;
     uint32_t n_tables() const { return (n_sets + n_parents) * 3; }
@@ -96,6 +97,39 @@ int32_t ensure_lower_table(Device &d)
         return fail(BSG_E_HIP, "lower-case table: %s", hipGetErrorString(e));
     }
     d.d_lower = t;
+    return BSG_OK;
+}
+
+// BasicWhitespaceLowerTokenizer as a spec: tab, LF, VT, FF, CR, space; UNICODE_SPACE | LOWER
+bsg_tokenizer default_tokenizer()
+{
+    bsg_tokenizer t{};
+    t.sep_ascii[0] = (1ull << 9) | (1ull << 10) | (1ull << 11) | (1ull << 12) | (1ull << 13) | (1ull << 32);
+    t.flags = BSG_TOK_UNICODE_SPACE | BSG_TOK_LOWER;
+    return t;
+}
+
+// Checks a caller's spec and derives the kernels' bitmaps (ingest.hip.h TokSpec).  *is_default: the spec is the default
+// tokenizer's (NULL included), which the existing kernels serve.
+int32_t tok_spec(const bsg_tokenizer *in, bsg_tokenizer &rec, bsg::TokSpec &out, bool &is_default)
+{
+    rec = in ? *in : default_tokenizer();
+    if (rec.sep_ascii[0] & 1u) return fail(BSG_E_INVALID, "tokenizer: NUL cannot be a separator");
+    if (rec.reserved) return fail(BSG_E_INVALID, "tokenizer: reserved must be 0");
+    if (rec.flags & ~(BSG_TOK_UNICODE_SPACE | BSG_TOK_LOWER)) return fail(BSG_E_INVALID, "tokenizer: unknown flags 0x%x", rec.flags);
+    const bsg_tokenizer d = default_tokenizer();
+    is_default = rec.sep_ascii[0] == d.sep_ascii[0] && rec.sep_ascii[1] == d.sep_ascii[1] && rec.flags == d.flags;
+    const bool lower = rec.flags & BSG_TOK_LOWER;
+    auto bit = [&](uint32_t c) { return (rec.sep_ascii[c >> 6] >> (c & 63u)) & 1u; };
+    out = bsg::TokSpec{};
+    out.flags = rec.flags;
+    for (uint32_t c = 1; c < 128; ++c) {
+        const uint32_t folded = (lower && c - 'A' < 26u) ? c + 32 : c;
+        const uint64_t b = bit(folded);
+        out.low[c >> 6] |= (uint64_t)bit(c) << (c & 63u);
+        out.raw[c >> 6] |= b << (c & 63u);
+        if (c >= 0x20u && c != 0x7Fu && c != '"' && c != '\\') out.run[c >> 6] |= b << (c & 63u);
+    }
     return BSG_OK;
 }
 
@@ -238,7 +272,7 @@ int32_t get_ingest(bsg_ctx *ctx, uint64_t id, std::shared_ptr<Ingest> &out)
 // One part: rows [0, n_rows) of `rows` (row_off relative to `rows`), n_sets sets, on device d.
 int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
                          const uint32_t *set_first_row, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents,
-                         const uint32_t *slots_hint, uint32_t flags)
+                         const uint32_t *slots_hint, uint32_t flags, const bsg::TokSpec *tok)
 {
     const uint64_t n_bytes = row_off[n_rows];
     static const bool trace = getenv("BSG_LAB_TRACE") != nullptr;   // lab only: phase times of this call on stderr
@@ -379,8 +413,12 @@ int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *
                 const uint64_t waves = std::min<uint64_t>((n + 63) / 64, max_waves);
                 b.rows_per_wave = (uint32_t)(((n + waves - 1) / waves + 63) / 64 * 64);
                 const uint64_t used = (n + b.rows_per_wave - 1) / b.rows_per_wave, wpw = bsg::kIngestThreads / 64;
-                hipExtLaunchKernelGGL(bsg::k_ingest_rows, dim3((uint32_t)((used + wpw - 1) / wpw)),
-                                      dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b);
+                if (tok)
+                    hipExtLaunchKernelGGL(bsg::k_ingest_rows_tok, dim3((uint32_t)((used + wpw - 1) / wpw)),
+                                          dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, *tok);
+                else
+                    hipExtLaunchKernelGGL(bsg::k_ingest_rows, dim3((uint32_t)((used + wpw - 1) / wpw)),
+                                          dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b);
                 if (first_attempt) {
                     first_attempt = false;
                     if (c + 1 < n_chunks) if (int32_t rc2 = copy_chunk(c + 1)) return rc2;
@@ -700,16 +738,17 @@ int32_t merge_parents(bsg_ctx *ctx, Ingest &I)
     return BSG_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int32_t bsg_ingest_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
-                        const uint32_t *set_first_row, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents,
-                        const uint32_t *slots_hint, uint32_t flags, uint64_t *out_ingest_id)
+// bsg_ingest_rows (tok_in NULL) and bsg_ingest_rows_tok
+int32_t ingest_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                         const uint32_t *set_first_row, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents,
+                         const uint32_t *slots_hint, uint32_t flags, const bsg_tokenizer *tok_in, uint64_t *out_ingest_id)
 {
-    BSG_ENTER(ctx);
     if (!ctx) return fail(BSG_E_INVALID, "ctx is null");
+    bsg_tokenizer rec{};
+    bsg::TokSpec spec{};
+    bool is_default = true;
+    if (int32_t rc = tok_spec(tok_in, rec, spec, is_default)) return rc;
+    const bsg::TokSpec *tok = is_default ? nullptr : &spec;
     if (!out_ingest_id || !row_off || !set_first_row || n_sets == 0) return fail(BSG_E_INVALID, "null argument or no sets");
     if (set_first_row[0] != 0 || set_first_row[n_sets] != n_rows) return fail(BSG_E_INVALID, "set_first_row must span [0, n_rows]");
     for (uint32_t s = 0; s < n_sets; ++s)
@@ -724,6 +763,7 @@ int32_t bsg_ingest_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_o
 
     auto I = std::make_shared<Ingest>();
     I->n_rows = n_rows; I->n_sets = n_sets; I->n_parents = n_parents;
+    I->tok = rec;
     I->parent_of_set.assign(n_sets, 0xFFFFFFFFu);
     if (parent_of_set) I->parent_of_set.assign(parent_of_set, parent_of_set + n_sets);
     // parts: contiguous runs of sets, about equal in row bytes, one per device
@@ -746,7 +786,7 @@ int32_t bsg_ingest_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_o
         G.set0 = s0; G.row0 = r0;
         Device &d = *ctx->devs[(first + i) % nd];
         if (np == 1)
-            return ingest_rows_part(ctx, d, G, rows, row_off, n_rows, set_first_row, n_sets, parent_of_set, n_parents, slots_hint, flags);
+            return ingest_rows_part(ctx, d, G, rows, row_off, n_rows, set_first_row, n_sets, parent_of_set, n_parents, slots_hint, flags, tok);
         // the part's rows and sets, renumbered from zero (offsets relative to the part's first byte)
         const uint64_t byte0 = row_off[r0];
         std::vector<uint64_t> off((size_t)(r1 - r0) + 1);
@@ -754,7 +794,7 @@ int32_t bsg_ingest_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_o
         std::vector<uint32_t> sfr((size_t)(s1 - s0) + 1);
         for (uint32_t s = s0; s <= s1; ++s) sfr[s - s0] = set_first_row[s] - r0;
         return ingest_rows_part(ctx, d, G, rows ? rows + byte0 : nullptr, off.data(), r1 - r0, sfr.data(), s1 - s0, parent_of_set ? parent_of_set + s0 : nullptr,
-                                n_parents, slots_hint ? slots_hint + (size_t)s0 * 3 : nullptr, flags);
+                                n_parents, slots_hint ? slots_hint + (size_t)s0 * 3 : nullptr, flags, tok);
     });
     if (rc) { free_ingest(*I); return rc; }
     for (auto &p : I->parts)
@@ -765,6 +805,33 @@ int32_t bsg_ingest_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_o
     ctx->ingests[id] = I;
     *out_ingest_id = id;
     return BSG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t bsg_tokenizer_default(bsg_tokenizer *out)
+{
+    if (!out) return fail(BSG_E_INVALID, "null argument");
+    *out = default_tokenizer();
+    return BSG_OK;
+}
+
+int32_t bsg_ingest_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                        const uint32_t *set_first_row, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents,
+                        const uint32_t *slots_hint, uint32_t flags, uint64_t *out_ingest_id)
+{
+    BSG_ENTER(ctx);
+    return ingest_rows_call(ctx, rows, row_off, n_rows, set_first_row, n_sets, parent_of_set, n_parents, slots_hint, flags, nullptr, out_ingest_id);
+}
+
+int32_t bsg_ingest_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                            const uint32_t *set_first_row, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents,
+                            const uint32_t *slots_hint, uint32_t flags, const bsg_tokenizer *tok, uint64_t *out_ingest_id)
+{
+    BSG_ENTER(ctx);
+    return ingest_rows_call(ctx, rows, row_off, n_rows, set_first_row, n_sets, parent_of_set, n_parents, slots_hint, flags, tok, out_ingest_id);
 }
 
 int32_t bsg_ingest_fallback_rows(bsg_ctx *ctx, uint64_t ingest_id, uint32_t *rows_out, uint32_t cap, uint32_t *n_out)

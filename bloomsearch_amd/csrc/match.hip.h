@@ -102,8 +102,8 @@ struct RxLane {
     }
 };
 
-template <bool REGEX>
-__device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs &x)
+template <bool REGEX, class TOK>
+__device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs &x, const TOK &tk)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     lds_u64i *conds = (lds_u64i *)lds_raw;
@@ -143,7 +143,7 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
     }
     while (__ballot(res == R_CONTINUE || w.req != Q_NONE) != 0ull) {
         while (__ballot(res == R_CONTINUE && w.req == Q_NONE) != 0ull)
-            if (res == R_CONTINUE && w.req == Q_NONE) res = advance<true>(w, cc, rx);
+            if (res == R_CONTINUE && w.req == Q_NONE) res = advance<true>(w, cc, rx, tk);
         const uint32_t q = w.req;
         w.req = Q_NONE;
         HashStream s;
@@ -230,8 +230,14 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
     }
 }
 
-__global__ __launch_bounds__(kIngestThreads) void k_match_rows(const MatchArgs a) { match_rows_body<false>(a, RxArgs{}); }
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows(const MatchArgs a) { match_rows_body<false>(a, RxArgs{}, TokDefault{}); }
 // Field / Token / FieldToken and FieldRegex conditions; dynamic LDS kMatchLdsBytes + the table blob (<= kRxLdsCap)
-__global__ __launch_bounds__(kIngestThreads) void k_match_rows_regex(const MatchArgs a, const RxArgs x) { match_rows_body<true>(a, x); }
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_regex(const MatchArgs a, const RxArgs x) { match_rows_body<true>(a, x, TokDefault{}); }
+// the same two under a separator-family tokenizer spec (bsg_match_rows_tok; regex conditions read the leaf text, not its words)
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_tok(const MatchArgs a, const TokSpec t) { match_rows_body<false>(a, RxArgs{}, TokSpecP{t}); }
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_regex_tok(const MatchArgs a, const RxArgs x, const TokSpec t)
+{
+    match_rows_body<true>(a, x, TokSpecP{t});
+}
 
 }  // namespace bsg

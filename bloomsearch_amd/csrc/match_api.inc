@@ -55,7 +55,7 @@ int32_t build_rx_blob(const uint8_t *cond_bytes, const uint32_t *cond_off, const
 // rows [r0, r1) (r0 a multiple of 64: whole words of out_bits) on one device; fb receives the GLOBAL indices of the rows handed back
 int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64_t *row_off, uint32_t r0, uint32_t r1,
                       const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds, uint32_t cond_len,
-                      const std::vector<uint32_t> &prog, const std::vector<uint32_t> &rx_blob, uint32_t n_rx,
+                      const std::vector<uint32_t> &prog, const std::vector<uint32_t> &rx_blob, uint32_t n_rx, const bsg::TokSpec *tok,
                       uint64_t *out_bits, std::vector<uint32_t> &fb, float *ms)
 {
     const uint32_t n_rows = r1 - r0;
@@ -169,10 +169,17 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
         if (e == hipSuccess && n_chunks > 1) e = hipStreamWaitEvent(d.stream, evs[(size_t)c * 3], 0);
         if (e != hipSuccess) break;
         const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads);
-        if (n_rx) {
+        if (n_rx && tok) {
+            const bsg::RxArgs x{d_rx, (uint32_t)rx_blob.size(), n_rx};
+            hipExtLaunchKernelGGL(bsg::k_match_rows_regex_tok, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes + (uint32_t)rx_blob.size() * 4,
+                                  d.stream, evs[(size_t)c * 3 + 1], evs[(size_t)c * 3 + 2], 0, a, x, *tok);
+        } else if (n_rx) {
             const bsg::RxArgs x{d_rx, (uint32_t)rx_blob.size(), n_rx};
             hipExtLaunchKernelGGL(bsg::k_match_rows_regex, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes + (uint32_t)rx_blob.size() * 4,
                                   d.stream, evs[(size_t)c * 3 + 1], evs[(size_t)c * 3 + 2], 0, a, x);
+        } else if (tok) {
+            hipExtLaunchKernelGGL(bsg::k_match_rows_tok, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes, d.stream, evs[(size_t)c * 3 + 1],
+                                  evs[(size_t)c * 3 + 2], 0, a, *tok);
         } else {
             hipExtLaunchKernelGGL(bsg::k_match_rows, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes, d.stream, evs[(size_t)c * 3 + 1],
                                   evs[(size_t)c * 3 + 2], 0, a);
@@ -203,13 +210,19 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
     return BSG_OK;
 }
 
-// bsg_match_rows (max_kind 2) and bsg_match_rows_regex (max_kind 3)
+// bsg_match_rows (max_kind 2), bsg_match_rows_regex (max_kind 3) and bsg_match_rows_tok (max_kind 3, a spec; NULL = default)
 int32_t match_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
                         const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
                         const uint32_t *prog_ops, uint32_t n_ops,
-                        uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback, uint32_t max_kind)
+                        uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback, uint32_t max_kind,
+                        const bsg_tokenizer *tok_in = nullptr)
 {
     if (!ctx) return fail(BSG_E_INVALID, "ctx is null");
+    bsg_tokenizer rec{};
+    bsg::TokSpec spec{};
+    bool is_default = true;
+    if (int32_t rc = tok_spec(tok_in, rec, spec, is_default)) return rc;
+    const bsg::TokSpec *tok = is_default ? nullptr : &spec;
     if (!out_n_fallback || (n_rows && (!row_off || !out_bits))) return fail(BSG_E_INVALID, "null argument");
     if (n_conds && (!cond_off || !cond_kinds)) return fail(BSG_E_INVALID, "conditions are null");
     if (n_ops && !prog_ops) return fail(BSG_E_INVALID, "prog_ops is null");
@@ -253,7 +266,7 @@ int32_t match_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_o
     const uint32_t first = n_parts == 1 ? pick_device(ctx) : 0;
     if (int32_t rc = run_parts(n_parts, [&](uint32_t i) -> int32_t {
             return match_rows_on(ctx, *ctx->devs[(first + i) % nd], rows, row_off, cuts[i], cuts[i + 1], cond_bytes, cond_off, cond_kinds, n_conds,
-                                 cond_len, prog, rx_blob, n_rx, out_bits, fbs[i], &ms[i]);
+                                 cond_len, prog, rx_blob, n_rx, tok, out_bits, fbs[i], &ms[i]);
         })) return rc;
     std::vector<uint32_t> fb;
     for (auto &v : fbs) fb.insert(fb.end(), v.begin(), v.end());
@@ -291,6 +304,16 @@ int32_t bsg_match_rows_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *
     BSG_ENTER(ctx);
     return match_rows_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, n_ops, out_bits, out_fallback_rows,
                            fallback_cap, out_n_fallback, BSG_KIND_FIELD_REGEX);
+}
+
+int32_t bsg_match_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                           const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                           const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
+                           uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    return match_rows_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, n_ops, out_bits, out_fallback_rows,
+                           fallback_cap, out_n_fallback, BSG_KIND_FIELD_REGEX, tok);
 }
 
 int32_t bsg_pinned_alloc(bsg_ctx *ctx, uint64_t n_bytes, void **out_ptr)

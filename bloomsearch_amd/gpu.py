@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import DESC_DTYPE, TERM_DTYPE, BloomGpuError, IngestStats, Timing
+from .tokenizer import c_spec
 
 
 def pack_entries(entries):
@@ -463,8 +464,10 @@ class Context:
         self._check(self.L.bsg_or_words_dev(self.h, C.c_void_p(d_dst_ptr), C.c_void_p(d_src_ptr), n_words, n_src))
 
     # ---- device ingest (rows -> distinct entries -> counts -> bitsets) ----
-    def ingest_rows(self, rows, set_first_row, parent_of_set=None, n_parents: int = 0, slots_hint=None, flags: int = 0) -> int:
-        """rows: list[bytes] (or (u8 blob, u64 offsets[n+1])); returns the ingest id."""
+    def ingest_rows(self, rows, set_first_row, parent_of_set=None, n_parents: int = 0, slots_hint=None, flags: int = 0,
+                    tokenizer=None) -> int:
+        """rows: list[bytes] (or (u8 blob, u64 offsets[n+1])); returns the ingest id.  tokenizer: None = bsg_ingest_rows
+        (the default tokenizer); a tokenizer.Tokenizer = bsg_ingest_rows_tok under that spec."""
         if isinstance(rows, tuple):
             blob, off = rows
             blob = np.ascontiguousarray(blob, dtype=np.uint8)
@@ -478,6 +481,10 @@ class Context:
         pos = None if parent_of_set is None else np.ascontiguousarray(parent_of_set, dtype=np.uint32)
         hint = None if slots_hint is None else np.ascontiguousarray(slots_hint, dtype=np.uint32)
         out = C.c_uint64()
+        if tokenizer is not None:
+            self._check(self.L.bsg_ingest_rows_tok(self.h, _lib._ptr(blob), _lib._ptr(off), len(off) - 1, _lib._ptr(sfr), len(sfr) - 1,
+                                                   _lib._ptr(pos), n_parents, _lib._ptr(hint), flags, c_spec(tokenizer), C.byref(out)))
+            return int(out.value)
         self._check(self.L.bsg_ingest_rows(self.h, _lib._ptr(blob), _lib._ptr(off), len(off) - 1, _lib._ptr(sfr), len(sfr) - 1,
                                            _lib._ptr(pos), n_parents, _lib._ptr(hint), flags, C.byref(out)))
         return int(out.value)
@@ -570,16 +577,17 @@ class Context:
         self._check(self.L.bsg_host_unregister(self.h, C.c_void_p(arr.ctypes.data)))
 
     # ---- final row test on the device ----
-    def match_rows(self, rows, matcher):
+    def match_rows(self, rows, matcher, tokenizer=None):
         """rows: list[bytes] or (u8 blob, u64 offsets); matcher: query.CompiledMatcher.
-        -> (bool array [n_rows], sorted u32 array of rows the host matcher must decide)."""
-        return self._match_rows(self.L.bsg_match_rows, rows, matcher)
+        -> (bool array [n_rows], sorted u32 array of rows the host matcher must decide).
+        tokenizer: None = bsg_match_rows; a tokenizer.Tokenizer = bsg_match_rows_tok under that spec."""
+        return self._match_rows(self.L.bsg_match_rows, rows, matcher, tokenizer)
 
-    def match_rows_regex(self, rows, matcher):
+    def match_rows_regex(self, rows, matcher, tokenizer=None):
         """bsg_match_rows_regex: as match_rows, and the matcher (query.CompiledRowQuery) may hold FieldRegex conditions."""
-        return self._match_rows(self.L.bsg_match_rows_regex, rows, matcher)
+        return self._match_rows(self.L.bsg_match_rows_regex, rows, matcher, tokenizer)
 
-    def _match_rows(self, fn, rows, matcher):
+    def _match_rows(self, fn, rows, matcher, tokenizer=None):
         if isinstance(rows, tuple):
             blob = np.ascontiguousarray(rows[0], dtype=np.uint8)
             off = np.ascontiguousarray(rows[1], dtype=np.uint64)
@@ -596,8 +604,13 @@ class Context:
         bits = np.zeros((n + 63) // 64, dtype=np.uint64)
         fb = np.zeros(max(n, 1), dtype=np.uint32)
         nfb = C.c_uint32()
-        self._check(fn(self.h, _lib._ptr(blob), _lib._ptr(off), n, _lib._ptr(cblob), _lib._ptr(coff), _lib._ptr(kinds), len(kinds),
-                       _lib._ptr(ops), len(ops), _lib._ptr(bits), _lib._ptr(fb), len(fb), C.byref(nfb)))
+        if tokenizer is not None:
+            self._check(self.L.bsg_match_rows_tok(self.h, _lib._ptr(blob), _lib._ptr(off), n, _lib._ptr(cblob), _lib._ptr(coff), _lib._ptr(kinds),
+                                                  len(kinds), _lib._ptr(ops), len(ops), c_spec(tokenizer), _lib._ptr(bits), _lib._ptr(fb), len(fb),
+                                                  C.byref(nfb)))
+        else:
+            self._check(fn(self.h, _lib._ptr(blob), _lib._ptr(off), n, _lib._ptr(cblob), _lib._ptr(coff), _lib._ptr(kinds), len(kinds),
+                           _lib._ptr(ops), len(ops), _lib._ptr(bits), _lib._ptr(fb), len(fb), C.byref(nfb)))
         match = np.unpackbits(bits.view(np.uint8), bitorder="little")[:n].astype(bool)
         return match, fb[: nfb.value].copy()
 

@@ -10,11 +10,13 @@ import numpy as np
 
 from . import _lib
 from ._lib import TERM_DTYPE
+from .tokenizer import c_spec
 
 HOST_EXPORTS = [
-    "bsh_free", "bsh_tokenize", "bsh_entry_sets_new", "bsh_entry_sets_free", "bsh_entry_sets_index_row",
+    "bsh_free", "bsh_tokenize", "bsh_tokenize_with", "bsh_entry_sets_new", "bsh_entry_sets_free", "bsh_entry_sets_index_row",
+    "bsh_entry_sets_index_row_with",
     "bsh_entry_sets_union_into", "bsh_entry_sets_counts", "bsh_entry_sets_export_sizes", "bsh_entry_sets_export",
-    "bsh_batch_new", "bsh_batch_free", "bsh_batch_add_query", "bsh_batch_sizes", "bsh_batch_export", "bsh_match_row", "bsh_prune_query", "bsh_match_row_regex",
+    "bsh_batch_new", "bsh_batch_free", "bsh_batch_add_query", "bsh_batch_sizes", "bsh_batch_export", "bsh_match_row", "bsh_match_row_with", "bsh_prune_query", "bsh_match_row_regex",
     "bsh_regex_match",
     "bsh_section_encode", "bsh_section_parse", "bsh_crc32c",
     "bse_open", "bse_close", "bse_last_error", "bse_stop", "bse_ingest_rows", "bse_flush", "bse_merge", "bse_query",
@@ -42,6 +44,8 @@ def lib():
     L.bsh_entry_sets_new.restype = vp
     L.bsh_entry_sets_free.argtypes = [vp]; L.bsh_entry_sets_free.restype = None
     L.bsh_entry_sets_index_row.argtypes = [vp, C.c_char_p, u64]
+    L.bsh_tokenize_with.argtypes = [C.c_char_p, u64, C.POINTER(_lib.Tokenizer), pp, pu64]
+    L.bsh_entry_sets_index_row_with.argtypes = [vp, C.c_char_p, u64, C.POINTER(_lib.Tokenizer)]
     L.bsh_entry_sets_union_into.argtypes = [vp, vp]
     L.bsh_entry_sets_counts.argtypes = [vp, pu64]; L.bsh_entry_sets_counts.restype = None
     L.bsh_entry_sets_export_sizes.argtypes = [vp, u32, pu64, pu64]
@@ -52,6 +56,7 @@ def lib():
     L.bsh_batch_sizes.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), pu64]; L.bsh_batch_sizes.restype = None
     L.bsh_batch_export.argtypes = [vp, vp, vp, vp, vp, vp]
     L.bsh_match_row.argtypes = [C.c_char_p, u64, C.c_char_p, u64]
+    L.bsh_match_row_with.argtypes = [C.c_char_p, u64, C.c_char_p, u64, C.POINTER(_lib.Tokenizer)]
     L.bsh_prune_query.argtypes = [C.c_char_p, u64, C.c_char_p, u64, pp, pu64]
     L.bsh_match_row_regex.argtypes = [C.c_char_p, u64, C.c_char_p, u64]
     L.bsh_regex_match.argtypes = [C.c_char_p, u64, C.c_char_p, u64]
@@ -83,10 +88,24 @@ def _take(L, p, n):
     return data
 
 
-def tokenize(text: bytes | str) -> list[str]:
+def tokenize(text: bytes | str, tokenizer=None, as_bytes: bool = False) -> list:
+    """The tokens of `text`.  tokenizer: None = BasicWhitespaceLowerTokenizer through bsh_tokenize; a
+    tokenizer.Tokenizer (or its C form) goes through bsh_tokenize_with.  as_bytes: the tokens' exact bytes (a token of a
+    spec without lowering may keep an invalid UTF-8 byte) instead of str."""
     L = lib()
     b = text.encode("utf-8", "surrogatepass") if isinstance(text, str) else text
     p, n = C.c_void_p(), C.c_uint64()
+    if tokenizer is not None or as_bytes:
+        rc = L.bsh_tokenize_with(b, len(b), c_spec(tokenizer), C.byref(p), C.byref(n))
+        if rc:
+            raise HostError(rc, "invalid tokenizer spec")
+        raw = _take(L, p, n)
+        out, i = [], 0
+        while i < len(raw):
+            ln = int.from_bytes(raw[i: i + 4], "little")
+            out.append(raw[i + 4: i + 4 + ln])
+            i += 4 + ln
+        return out if as_bytes else [t.decode("utf-8", "replace") for t in out]
     rc = L.bsh_tokenize(b, len(b), C.byref(p), C.byref(n))
     if rc:
         raise HostError(rc)
@@ -106,10 +125,14 @@ class EntrySets:
             self.L.bsh_entry_sets_free(self.h)
             self.h = None
 
-    def index_row(self, row: bytes):
-        rc = self.L.bsh_entry_sets_index_row(self.h, row, len(row))
+    def index_row(self, row: bytes, tokenizer=None):
+        """indexRow; tokenizer: None = the default, or a tokenizer.Tokenizer of the separator family."""
+        if tokenizer is None:
+            rc = self.L.bsh_entry_sets_index_row(self.h, row, len(row))
+        else:
+            rc = self.L.bsh_entry_sets_index_row_with(self.h, row, len(row), c_spec(tokenizer))
         if rc:
-            raise HostError(rc, "row is not valid JSON")
+            raise HostError(rc, "row is not valid JSON (or the tokenizer spec is invalid)")
 
     def union_into(self, dst: "EntrySets"):
         self.L.bsh_entry_sets_union_into(self.h, dst.h)
@@ -172,10 +195,14 @@ class HostBatch:
         return strings, kinds[: nt.value], ops[: no.value], poff
 
 
-def match_row(expression, row: bytes) -> bool:
+def match_row(expression, row: bytes, tokenizer=None) -> bool:
+    """The host RowMatcher; tokenizer: None = the default (bsh_match_row), a tokenizer.Tokenizer = bsh_match_row_with."""
     L = lib()
     s = json.dumps(expression).encode()
-    rc = L.bsh_match_row(s, len(s), row, len(row))
+    if tokenizer is None:
+        rc = L.bsh_match_row(s, len(s), row, len(row))
+    else:
+        rc = L.bsh_match_row_with(s, len(s), row, len(row), c_spec(tokenizer))
     if rc < 0:
         raise HostError(rc)
     return bool(rc)
@@ -244,6 +271,8 @@ class Engine:
     def __init__(self, ctx, **config):
         self.L = lib()
         self.ctx = ctx
+        if hasattr(config.get("Tokenizer"), "to_json"):
+            config["Tokenizer"] = config["Tokenizer"].to_json()
         cfg = json.dumps(config).encode()
         h = C.c_void_p()
         rc = self.L.bse_open(cfg, len(cfg), ctx.h, C.byref(h))

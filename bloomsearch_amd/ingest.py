@@ -39,9 +39,9 @@ def plan_desc(counts: np.ndarray, fpr: float):
     return desc, max(cursor, 2)
 
 
-def host_walk_entries(rows, row_ids, set_of_row):
+def host_walk_entries(rows, row_ids, set_of_row, tokenizer=None):
     """The host walker (walker.hpp through bsh_entry_sets_*) over the fallback rows ->
-    (entries, set_of_entry, kind_of_entry)."""
+    (entries, set_of_entry, kind_of_entry).  tokenizer: the spec the device walked with (None = the default)."""
     by_set: dict = {}
     for r in row_ids:
         by_set.setdefault(int(set_of_row[r]), []).append(rows[int(r)])
@@ -50,7 +50,7 @@ def host_walk_entries(rows, row_ids, set_of_row):
         es = host.EntrySets()
         for row in rs:
             try:
-                es.index_row(row)
+                es.index_row(row, tokenizer)
             except host.HostError:
                 pass  # malformed row: what the walker saw before the error stays (entry_sets.hpp)
         for kind in range(3):
@@ -65,17 +65,18 @@ def host_walk_entries(rows, row_ids, set_of_row):
 
 
 def device_ingest(ctx: Context, row_sets, fpr: float, parent_of_set=None, n_parents: int = 0, slots_hint=None,
-                  keep: bool = False, flags: int = 0) -> IngestResult:
-    """row_sets: list (one per set) of lists of row bytes."""
+                  keep: bool = False, flags: int = 0, tokenizer=None) -> IngestResult:
+    """row_sets: list (one per set) of lists of row bytes.  tokenizer: None = the default tokenizer (bsg_ingest_rows); a
+    tokenizer.Tokenizer of the separator family = bsg_ingest_rows_tok, its fallback rows walked by the host with the same spec."""
     rows = [r for rs in row_sets for r in rs]
     first = np.zeros(len(row_sets) + 1, dtype=np.uint32)
     first[1:] = np.cumsum([len(rs) for rs in row_sets])
-    ing = ctx.ingest_rows(rows, first, parent_of_set, n_parents, slots_hint, flags)
+    ing = ctx.ingest_rows(rows, first, parent_of_set, n_parents, slots_hint, flags, tokenizer=tokenizer)
     try:
         fb = ctx.ingest_fallback_rows(ing)
         if len(fb):
             set_of_row = np.repeat(np.arange(len(row_sets)), np.diff(first.astype(np.int64)))
-            entries, sets, kinds = host_walk_entries(rows, fb, set_of_row)
+            entries, sets, kinds = host_walk_entries(rows, fb, set_of_row, tokenizer)
             if entries:
                 ctx.ingest_add_entries(ing, entries, sets, kinds)
         n_total = len(row_sets) + n_parents

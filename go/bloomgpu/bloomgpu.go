@@ -26,6 +26,9 @@ import "C"
 import (
 	"errors"
 	"fmt"
+	"strings"
+	"unicode"
+	"unicode/utf8"
 	"unsafe"
 )
 
@@ -785,6 +788,83 @@ func (g *Context) PinnedFree(b []byte) error {
 	return g.err(C.bsg_pinned_free(g.c, unsafe.Pointer(unsafe.SliceData(b[:1]))))
 }
 
+// Tokenizer is a tokenizer of the separator family (bsg_tokenizer): tokens = strings.FieldsFunc(v lowered when Lower, isSep),
+// isSep(r) = r is an ASCII rune in Separators, or (UnicodeSpace) r >= 0x80 with unicode.IsSpace.  Separators are tested after
+// lowering.  {" \t\n\v\f\r", true, true} is BasicWhitespaceLowerTokenizer.
+type Tokenizer struct {
+	Separators   string
+	UnicodeSpace bool
+	Lower        bool
+}
+
+// Validate refuses a separator that is NUL or not ASCII (the device tests ASCII separators only).
+func (t Tokenizer) Validate() error {
+	for i := 0; i < len(t.Separators); i++ {
+		if c := t.Separators[i]; c == 0 || c >= utf8.RuneSelf {
+			return fmt.Errorf("bloomgpu: tokenizer separator %q is NUL or not ASCII", t.Separators)
+		}
+	}
+	return nil
+}
+
+// Func is the tokenizer as the function the engine's Tokenizer field holds: host fallback rows and queries use the very
+// definition the device implements.  Call Validate first: a separator byte that is not ASCII is skipped here.
+func (t Tokenizer) Func() func(string) []string {
+	var set [2]uint64
+	for i := 0; i < len(t.Separators); i++ {
+		if c := t.Separators[i]; c < utf8.RuneSelf { // Validate refuses the others; Func skips them
+			set[c>>6] |= 1 << (c & 63)
+		}
+	}
+	unicodeSpace := t.UnicodeSpace
+	isSep := func(r rune) bool {
+		if r < utf8.RuneSelf {
+			return set[r>>6]>>(uint(r)&63)&1 != 0
+		}
+		return unicodeSpace && unicode.IsSpace(r)
+	}
+	lower := t.Lower
+	return func(v string) []string {
+		if lower {
+			v = strings.ToLower(v)
+		}
+		return strings.FieldsFunc(v, isSep)
+	}
+}
+
+func (t Tokenizer) c() C.bsg_tokenizer {
+	var ct C.bsg_tokenizer
+	for i := 0; i < len(t.Separators); i++ {
+		if c := t.Separators[i]; c < utf8.RuneSelf { // callers Validate first
+			ct.sep_ascii[c>>6] |= C.uint64_t(1) << (c & 63)
+		}
+	}
+	if t.UnicodeSpace {
+		ct.flags |= C.BSG_TOK_UNICODE_SPACE
+	}
+	if t.Lower {
+		ct.flags |= C.BSG_TOK_LOWER
+	}
+	return ct
+}
+
+// IngestRowsTok is IngestRows under a separator-family tokenizer (bsg_ingest_rows_tok); the caller's host walker must tokenize
+// the fallback rows with tok.Func().
+func (g *Context) IngestRowsTok(rows []byte, rowOff []uint64, setFirstRow, parentOfSet []uint32, nParents int, flags uint32, tok Tokenizer) (*Ingest, error) {
+	if err := tok.Validate(); err != nil {
+		return nil, err
+	}
+	var id C.uint64_t
+	nSets := len(setFirstRow) - 1
+	ct := tok.c()
+	rc := C.bsg_ingest_rows_tok(g.c, u8p(rows), u64p(rowOff), C.uint32_t(len(rowOff)-1), u32p(setFirstRow), C.uint32_t(nSets),
+		u32p(parentOfSet), C.uint32_t(nParents), nil, C.uint32_t(flags), &ct, &id)
+	if err := g.err(rc); err != nil {
+		return nil, err
+	}
+	return &Ingest{g, id, nSets, nParents}, nil
+}
+
 // Ingest is a device ingest in progress (bsg_ingest_*): rows -> distinct bloom entries -> exact counts -> bitsets.
 type Ingest struct {
 	g        *Context
@@ -878,17 +958,26 @@ func (in *Ingest) Free() error { return in.g.err(C.bsg_ingest_free(in.g.c, in.id
 // in hostRows must be decided by matchRowBytes (outside the device walker's envelope, or a hash collision with a
 // condition string that only a byte compare can settle).
 func (g *Context) MatchRows(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32) (bits []uint64, hostRows []uint32, err error) {
-	return g.matchRows(false, rows, rowOff, conds, progOps)
+	return g.matchRows(false, rows, rowOff, conds, progOps, nil)
 }
 
 // MatchRowsRegex is MatchRows through bsg_match_rows_regex: conds may also hold KindFieldRegex conditions (Token = the pattern,
 // pattern.String() of the compiled regexp), so a whole compileRowMatcher root And(bloomRoot, regexRoot) is one call.  A pattern
 // outside the device's RE2 subset, more than 16 of them or tables over its LDS budget: IsUnsupported(err).
 func (g *Context) MatchRowsRegex(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32) (bits []uint64, hostRows []uint32, err error) {
-	return g.matchRows(true, rows, rowOff, conds, progOps)
+	return g.matchRows(true, rows, rowOff, conds, progOps, nil)
 }
 
-func (g *Context) matchRows(regex bool, rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32) (bits []uint64, hostRows []uint32, err error) {
+// MatchRowsTok is MatchRowsRegex (conds may hold KindFieldRegex conditions too) under a separator-family tokenizer
+// (bsg_match_rows_tok): Token and FieldToken conditions compare tok's words; the host matcher must use tok.Func().
+func (g *Context) MatchRowsTok(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, tok Tokenizer) (bits []uint64, hostRows []uint32, err error) {
+	if err := tok.Validate(); err != nil {
+		return nil, nil, err
+	}
+	return g.matchRows(true, rows, rowOff, conds, progOps, &tok)
+}
+
+func (g *Context) matchRows(regex bool, rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, tok *Tokenizer) (bits []uint64, hostRows []uint32, err error) {
 	n := len(rowOff) - 1
 	if n <= 0 {
 		return nil, nil, nil
@@ -907,7 +996,11 @@ func (g *Context) matchRows(regex bool, rows []byte, rowOff []uint64, conds []Ma
 	}
 	var nfb C.uint32_t
 	var rc C.int32_t
-	if regex {
+	if tok != nil {
+		ct := tok.c()
+		rc = C.bsg_match_rows_tok(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+			u32p(progOps), C.uint32_t(len(progOps)), &ct, u64p(bits), u32p(hostRows), C.uint32_t(n), &nfb)
+	} else if regex {
 		rc = C.bsg_match_rows_regex(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
 			u32p(progOps), C.uint32_t(len(progOps)), u64p(bits), u32p(hostRows), C.uint32_t(n), &nfb)
 	} else {

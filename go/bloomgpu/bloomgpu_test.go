@@ -1,6 +1,9 @@
 package bloomgpu
 
-import "testing"
+import (
+	"fmt"
+	"testing"
+)
 
 // The public MurmurHash3_x64_128 vector for "hello" (seed 0) through bsg_hash_entries: h0, h1 of bloom/v3's
 // baseHashes are exactly that digest.  Needs a gfx950 device; skipped otherwise.
@@ -54,5 +57,68 @@ func TestScopesOwnTheirErrors(t *testing.T) {
 	got := <-done
 	if got[0] == got[1] || errA == nil || errB == nil {
 		t.Fatalf("scopes share an error slot: %q / %q", got[0], got[1])
+	}
+}
+
+// Tokenizer.Func is strings.FieldsFunc(lowered, isSep); Validate refuses NUL and non-ASCII separators.  Host only.
+func TestTokenizerFunc(t *testing.T) {
+	punct := Tokenizer{Separators: " \t\n\v\f\r,;:=/.-\"[]()", UnicodeSpace: true, Lower: true}
+	cases := []struct {
+		tok  Tokenizer
+		in   string
+		want []string
+	}{
+		{punct, "user=Alice GET /api/v1/users", []string{"user", "alice", "get", "api", "v1", "users"}},
+		{punct, "-1.5E-3", []string{"1", "5e", "3"}},
+		{Tokenizer{Separators: " \t\n\v\f\r,;:=/.-\"[]()", UnicodeSpace: true}, "-1.5E-3", []string{"1", "5E", "3"}},
+		{Tokenizer{Separators: "k", Lower: true}, "xKy", []string{"x", "y"}},
+		{Tokenizer{Separators: " "}, "a\u00a0b c", []string{"a\u00a0b", "c"}},
+		{Tokenizer{Separators: " \t\n\v\f\r", UnicodeSpace: true, Lower: true}, "Hello  World\u3000X", []string{"hello", "world", "x"}},
+	}
+	for _, c := range cases {
+		got := c.tok.Func()(c.in)
+		if fmt.Sprint(got) != fmt.Sprint(c.want) {
+			t.Errorf("%+v(%q) = %q, want %q", c.tok, c.in, got, c.want)
+		}
+	}
+	if got := (Tokenizer{Separators: "é,"}).Func()("a,b"); fmt.Sprint(got) != "[a b]" { // an unvalidated spec must not panic
+		t.Errorf("Func with a non-ASCII separator: %q", got)
+	}
+	for _, bad := range []string{"\x00", "é", "a\u3000"} {
+		if (Tokenizer{Separators: bad}).Validate() == nil {
+			t.Errorf("Validate(%q) accepted", bad)
+		}
+	}
+}
+
+// IngestRowsTok / MatchRowsTok: Token("alice") finds {"msg":"user=alice"} under the punctuation tokenizer only.  Needs a gfx950
+// device; skipped otherwise.
+func TestMatchRowsTokPunctuation(t *testing.T) {
+	g, err := Open([]int32{0})
+	if err != nil {
+		t.Skip(err)
+	}
+	defer g.Close()
+	row := []byte(`{"msg":"user=alice"}`)
+	off := []uint64{0, uint64(len(row))}
+	conds := []MatchCond{{Kind: KindToken, Token: "alice"}}
+	prog := []uint32{0}
+	punct := Tokenizer{Separators: " \t\n\v\f\r,;:=/.-\"[]()", UnicodeSpace: true, Lower: true}
+	bits, host, err := g.MatchRowsTok(row, off, conds, prog, punct)
+	if err != nil || len(host) != 0 || bits[0]&1 != 1 {
+		t.Fatalf("punctuation: bits %v host %v err %v", bits, host, err)
+	}
+	bits, _, err = g.MatchRows(row, off, conds, prog)
+	if err != nil || bits[0]&1 != 0 {
+		t.Fatalf("default: bits %v err %v", bits, err)
+	}
+	in, err := g.IngestRowsTok(row, off, []uint32{0, 1}, nil, 0, 0, punct)
+	if err != nil {
+		t.Fatal(err)
+	}
+	defer in.Free()
+	counts, _, err := in.Finish()
+	if err != nil || counts[0] != 1 || counts[1] != 2 || counts[2] != 2 {
+		t.Fatalf("counts %v err %v", counts, err)
 	}
 }

@@ -31,9 +31,27 @@ import (
 	"bloomsearch_amd/go/bloomgpu"
 )
 
+// GPUTokenizer is the type of BloomSearchEngineConfig.GPUTokenizer: a tokenizer of the separator family the device serves
+// (bloomgpu.Tokenizer, include/bloomgpu.h bsg_tokenizer).
+type GPUTokenizer = bloomgpu.Tokenizer
+
+// gpuTokenizerFunc is the engine's Tokenizer for a config with GPUTokenizer set: its Func(), so indexing, the stock matcher and
+// the host fallback rows use the very definition the device implements.  An error (ErrInvalidConfig for the caller): a
+// separator that is NUL or not ASCII, or a non-default Tokenizer set as well (two tokenizers, one of them would be ignored).
+func gpuTokenizerFunc(config BloomSearchEngineConfig) (ValueTokenizerFunc, error) {
+	if config.Tokenizer != nil && !isBasicWhitespaceLowerTokenizer(config.Tokenizer) {
+		return nil, errors.New("GPUTokenizer and a non-default Tokenizer are both set")
+	}
+	if err := config.GPUTokenizer.Validate(); err != nil {
+		return nil, err
+	}
+	return config.GPUTokenizer.Func(), nil
+}
+
 type gpuEngine struct {
 	g      *bloomgpu.Context
 	ingest bool
+	tok    *bloomgpu.Tokenizer // config.GPUTokenizer (nil: the default tokenizer); the engine's Tokenizer is tok.Func()
 	logger *slog.Logger
 
 	scopeMu   sync.Mutex
@@ -92,15 +110,20 @@ func openGPUEngine(config BloomSearchEngineConfig, logger *slog.Logger) (*gpuEng
 	if err != nil {
 		return nil, err
 	}
-	if ingest && !isBasicWhitespaceLowerTokenizer(config.Tokenizer) {
-		logger.Warn("GPUIngest needs the default tokenizer; rows stay on the host walker")
+	var tok *bloomgpu.Tokenizer
+	if config.GPUTokenizer != nil {
+		t := *config.GPUTokenizer
+		tok = &t
+	}
+	if ingest && tok == nil && !isBasicWhitespaceLowerTokenizer(config.Tokenizer) {
+		logger.Warn("GPUIngest needs the default tokenizer or a GPUTokenizer; rows stay on the host walker")
 		ingest = false
 	}
 	if err := g.SetArenaBudget(arenaBudgetFromEnv()); err != nil {
 		g.Close()
 		return nil, err
 	}
-	return &gpuEngine{g: g, ingest: ingest, logger: logger}, nil
+	return &gpuEngine{g: g, ingest: ingest, tok: tok, logger: logger}, nil
 }
 
 func (e *gpuEngine) close() {
@@ -189,7 +212,7 @@ func (e *gpuEngine) flushFilters(buffers map[string]*partitionBuffer, tokenizer 
 		for i, pb := range order {
 			rows[i] = pb.gpuRows
 		}
-		filters, counts, err := buildFiltersFromRowsGPU(s, rows, fpr)
+		filters, counts, err := buildFiltersFromRowsTokGPU(s, rows, fpr, e.tok, tokenizer)
 		if err == nil {
 			n := len(order)
 			f.filters, f.counts, f.fileLevel = filters[:n], counts, &filters[n]
@@ -474,10 +497,12 @@ type gpuRowVerdicts struct {
 
 // matchBlock runs the block's rows through bsg_match_rows for matchers made of Field / Token / FieldToken conditions under the
 // default tokenizer, and through bsg_match_rows_regex when the matcher has FieldRegex conditions too (the whole root
-// And(bloomRoot, regexRoot) in one call; a matcher the device refuses is remembered and keeps the stock matcher); anything else
-// (a custom tokenizer, constant matchers) keeps the stock per-row matcher.
+// And(bloomRoot, regexRoot) in one call; a matcher the device refuses is remembered and keeps the stock matcher).  Under a
+// GPUTokenizer (the matcher's tokenizer is then e.tok.Func()) both go through bsg_match_rows_tok.  Anything else (another
+// custom tokenizer, constant matchers) keeps the stock per-row matcher.
 func (e *gpuEngine) matchBlock(rowData []byte, m *compiledRowMatcher) *gpuRowVerdicts {
-	if e == nil || m.matchesAll || m.neverMatches || !m.fastTokens || len(m.conditions) == 0 || len(m.conditions) > 64 || len(m.regexConds) > 16 {
+	if e == nil || m.matchesAll || m.neverMatches || !(m.fastTokens || e.tok != nil) || len(m.conditions) == 0 || len(m.conditions) > 64 ||
+		len(m.regexConds) > 16 {
 		return nil
 	}
 	regexKey := ""
@@ -552,9 +577,13 @@ func (e *gpuEngine) matchBlock(rowData []byte, m *compiledRowMatcher) *gpuRowVer
 	var bits []uint64
 	var hostRows []uint32
 	var err error
-	if len(m.regexConds) > 0 {
-		bits, hostRows, err = s.MatchRowsRegex(blob, rowOff, conds, ops)
-		if bloomgpu.IsUnsupported(err) {
+	if len(m.regexConds) > 0 || e.tok != nil {
+		if e.tok != nil {
+			bits, hostRows, err = s.MatchRowsTok(blob, rowOff, conds, ops, *e.tok)
+		} else {
+			bits, hostRows, err = s.MatchRowsRegex(blob, rowOff, conds, ops)
+		}
+		if bloomgpu.IsUnsupported(err) && len(m.regexConds) > 0 {
 			e.regexMu.Lock()
 			if e.regexRefused == nil || len(e.regexRefused) >= 4096 {
 				e.regexRefused = make(map[string]bool)

@@ -14,6 +14,17 @@ import (
 
 type gpuEngine struct{}
 
+// GPUTokenizer is the shape of bloomgpu.Tokenizer; without the library it cannot be served.
+type GPUTokenizer struct {
+	Separators   string
+	UnicodeSpace bool
+	Lower        bool
+}
+
+func gpuTokenizerFunc(config BloomSearchEngineConfig) (ValueTokenizerFunc, error) {
+	return nil, errors.New("GPUTokenizer is set but the engine was built without -tags bloomgpu")
+}
+
 func openGPUEngine(config BloomSearchEngineConfig, _ *slog.Logger) (*gpuEngine, error) {
 	if len(config.GPUDevices) > 0 {
 		return nil, errors.New("GPUDevices is set but the engine was built without -tags bloomgpu")

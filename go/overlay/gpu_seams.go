@@ -7,7 +7,8 @@
 //
 // Seams (reference file:line):
 //   buildFiltersGPU ........... entries.buildFilters per partition + file level, flush.go:204,253; merge.go:771,516
-//   buildFiltersFromRowsGPU ... indexRow per row + buildFilters (ingest.go:450, merge.go:746) for the default tokenizer
+//   buildFiltersFromRowsGPU ... indexRow per row + buildFilters (ingest.go:450, merge.go:746) for the default tokenizer;
+//                               buildFiltersFromRowsTokGPU for a GPUTokenizer
 //   loadArena / loadArenaSections ... cursor.filtersFor + parseFilterSection per block, file_format.go:392-448,575
 //   probeBlocks ............... evaluateBlockFilters' per-block loop, query_exec.go:572-615 (one bsg_query call)
 //   gpu_engine.go ............. the engine methods engine_gpu.patch hooks into handleFlush / merge / evaluateBlockFilters / processDataBlock
@@ -75,10 +76,17 @@ func buildFiltersGPU(g *bloomgpu.Context, sets []*bloomEntrySets, fpr float64) (
 
 // buildFiltersFromRowsGPU is the device-ingest variant of the flush / merge build: the marshaled rows of every
 // partition buffer go to the device as they are, which walks, tokenizes, deduplicates and counts them —
-// bloomEntrySets.indexRow never runs on the host for rows inside the device walker's envelope.  Only valid for the
+// bloomEntrySets.indexRow never runs on the host for rows inside the device walker's envelope.  This form is for the
 // default tokenizer (isBasicWhitespaceLowerTokenizer, row_matcher.go:37-40).  rows[b] = marshaled rows of partition
 // buffer b.  Returns per-buffer filters + counts, then the file-level ones (last element).
 func buildFiltersFromRowsGPU(g *bloomgpu.Context, rows [][][]byte, fpr float64) ([]BloomFilters, []BloomEntryCounts, error) {
+	return buildFiltersFromRowsTokGPU(g, rows, fpr, nil, BasicWhitespaceLowerTokenizer)
+}
+
+// buildFiltersFromRowsTokGPU is buildFiltersFromRowsGPU under a tokenizer spec: tok == nil is the default tokenizer
+// (bsg_ingest_rows), otherwise the device walks with tok (bsg_ingest_rows_tok).  tokenizer is the engine's Tokenizer —
+// tok.Func() when tok is set — and indexes the rows the device hands back.
+func buildFiltersFromRowsTokGPU(g *bloomgpu.Context, rows [][][]byte, fpr float64, tok *bloomgpu.Tokenizer, tokenizer ValueTokenizerFunc) ([]BloomFilters, []BloomEntryCounts, error) {
 	var blob []byte
 	rowOff := []uint64{0}
 	first := []uint32{0}
@@ -90,7 +98,13 @@ func buildFiltersFromRowsGPU(g *bloomgpu.Context, rows [][][]byte, fpr float64) 
 		}
 		first = append(first, uint32(len(rowOff)-1))
 	}
-	ing, err := g.IngestRows(blob, rowOff, first, parent, 1, bloomgpu.IngestTrustedJSON /* json.Marshal output */)
+	var ing *bloomgpu.Ingest
+	var err error
+	if tok != nil {
+		ing, err = g.IngestRowsTok(blob, rowOff, first, parent, 1, bloomgpu.IngestTrustedJSON /* json.Marshal output */, *tok)
+	} else {
+		ing, err = g.IngestRows(blob, rowOff, first, parent, 1, bloomgpu.IngestTrustedJSON)
+	}
 	if err != nil {
 		return nil, nil, err
 	}
@@ -108,7 +122,7 @@ func buildFiltersFromRowsGPU(g *bloomgpu.Context, rows [][][]byte, fpr float64) 
 			if perSet[b] == nil {
 				perSet[b] = newBloomEntrySets()
 			}
-			perSet[b].indexRow(rows[b][r-first[b]], BasicWhitespaceLowerTokenizer)
+			perSet[b].indexRow(rows[b][r-first[b]], tokenizer)
 		}
 		var eb []byte
 		eo, es, ek := []uint32{0}, []uint32{}, []uint32{}

@@ -445,13 +445,31 @@ BSG_API int32_t bsg_pinned_free(bsg_ctx *ctx, void *ptr);
 BSG_API int32_t bsg_host_register(bsg_ctx *ctx, void *ptr, uint64_t n_bytes);
 BSG_API int32_t bsg_host_unregister(bsg_ctx *ctx, void *ptr);
 
+/* ---- tokenizers of the separator family ----
+ * tokens(text) = strings.FieldsFunc(lower ? strings.ToLower(text) : text, isSep), where isSep(r) holds for an ASCII r whose bit
+ * is set in sep_ascii and, under BSG_TOK_UNICODE_SPACE, for r >= 0x80 with unicode.IsSpace(r).  The text is leafTokenInput's
+ * (a string's decoded text, a number's raw literal, true / false); keys and paths are never tokenized.  Separators are tested
+ * AFTER lowering (U+212A KELVIN SIGN lowers to 'k', U+0130 to 'i'; under BSG_TOK_LOWER an upper-case ASCII separator never
+ * occurs).  BasicWhitespaceLowerTokenizer = strings.Fields(strings.ToLower(v)) is the member bsg_tokenizer_default returns:
+ * tab, LF, VT, FF, CR and space, UNICODE_SPACE | LOWER.  A NULL spec means that default.  BSG_E_INVALID: bit 0 (NUL), a
+ * non-zero `reserved`, unknown flags.  Separators are ASCII only. */
+#define BSG_TOK_UNICODE_SPACE 1u   /* runes >= 0x80 with unicode.IsSpace end a word too */
+#define BSG_TOK_LOWER         2u   /* the text is lower-cased first (unicode.ToLower per rune, as strings.ToLower) */
+typedef struct bsg_tokenizer {
+    uint64_t sep_ascii[2];  /* bit (c & 63) of sep_ascii[c >> 6]: ASCII byte c (1..127) ends a word */
+    uint32_t flags;         /* BSG_TOK_* */
+    uint32_t reserved;      /* 0 */
+} bsg_tokenizer;
+BSG_API int32_t bsg_tokenizer_default(bsg_tokenizer *out);
+
 /* ---- device ingest: rows -> distinct bloom entries -> exact counts -> bitsets ----
  * Replaces, on the flush / merge worker, the reference's per-row host loop
  *   bloomEntrySets.indexRow (ingest.go:55-89: pathWalker.walk row_matcher.go:51-135, leafTokenInput
  *   tokenizer.go:120-133, BasicWhitespaceLowerTokenizer tokenizer.go:141-143, addFieldToken ingest.go:95-102),
  *   unionInto (ingest.go:105-115), counts (ingest.go:117-123) and buildFilters' AddString loop (ingest.go:127-145)
- * for the DEFAULT tokenizer (the reference's own fast-path check, row_matcher.go:37-40; custom tokenizers
- * keep the host path).  A "set" is one partition buffer's bloomEntrySets; set s owns rows
+ * for the DEFAULT tokenizer (the reference's own fast-path check, row_matcher.go:37-40) and, through bsg_ingest_rows_tok, for
+ * every tokenizer of the separator family (bsg_tokenizer below); tokenizers outside that family stay on the host.
+ * A "set" is one partition buffer's bloomEntrySets; set s owns rows
  * [set_first_row[s], set_first_row[s+1]).  A "parent" is a file-level union (flush.go:221,253);
  * parent_of_set[s] names it or is 0xFFFFFFFF.  Tables are indexed t = set * 3 + kind with parents
  * numbered after the sets (set index n_sets + p).
@@ -487,6 +505,14 @@ typedef struct bsg_ingest_stats {
 BSG_API int32_t bsg_ingest_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
                                 const uint32_t *set_first_row, uint32_t n_sets, const uint32_t *parent_of_set,
                                 uint32_t n_parents, const uint32_t *slots_hint, uint32_t flags, uint64_t *out_ingest_id);
+/* bsg_ingest_rows under a tokenizer of the separator family (tok: NULL = the default): the same arguments, chunked upload,
+ * multi-device sharding and fallback rows.  A spec equal to the default runs exactly bsg_ingest_rows' kernel.  The spec is
+ * recorded on the ingest; bsg_ingest_add_entries does not use it (the caller's host walker tokenizes its fallback rows with
+ * the same spec). */
+BSG_API int32_t bsg_ingest_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                    const uint32_t *set_first_row, uint32_t n_sets, const uint32_t *parent_of_set,
+                                    uint32_t n_parents, const uint32_t *slots_hint, uint32_t flags, const bsg_tokenizer *tok,
+                                    uint64_t *out_ingest_id);
 /* bsg_ingest_rows uploads the rows in chunks: the first of about this many bytes (default 64 MiB, 0 restores it), each
  * later one twice the one before up to four times this; the copy of chunk i+1 overlaps the walk of chunk i. */
 BSG_API int32_t bsg_set_ingest_chunk(bsg_ctx *ctx, uint64_t bytes);
@@ -559,6 +585,15 @@ BSG_API int32_t bsg_match_rows_regex(bsg_ctx *ctx, const uint8_t *rows, const ui
                                      const uint32_t *prog_ops, uint32_t n_ops,
                                      uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                      uint32_t *out_n_fallback);
+/* bsg_match_rows / bsg_match_rows_regex for an engine whose tokenizer is of the separator family (tok: NULL = the default):
+ * Token and FieldToken conditions compare the words of that tokenizer; FieldRegex conditions (allowed here) read the leaf
+ * text and ignore it.  The condition kinds choose the kernel, a spec equal to the default runs the default kernels.  Same
+ * arguments, limits, sharding, chunked upload and fallback rows as bsg_match_rows_regex. */
+BSG_API int32_t bsg_match_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                   const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                   const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
+                                   uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                   uint32_t *out_n_fallback);
 /* Device time of the most recent k_match_rows / k_match_rows_regex dispatch (the slowest device's). */
 BSG_API int32_t bsg_last_match_ms(bsg_ctx *ctx, float *match_ms);
 

@@ -8,6 +8,7 @@
  *
  * Mirrors (reference file:line):
  *   bsh_tokenize ............. BasicWhitespaceLowerTokenizer, tokenizer.go:141-143
+ *   bsh_tokenize_with ........ strings.FieldsFunc(lower ? strings.ToLower(v) : v, isSep) (the separator family)
  *   bsh_entry_sets_* ......... bloomEntrySets.indexRow/unionInto/counts, ingest.go:24-123
  *   bsh_batch_* .............. Field/Token/FieldToken/And/Or trees (JSON of the exported structs,
  *                              query.go:478-610) lowered to bloomgpu.h terms + programs
@@ -40,12 +41,18 @@ BSG_API void bsh_free(void *p);
 
 /* tokens of `text`, joined by '\n' (a token never contains white space) */
 BSG_API int32_t bsh_tokenize(const uint8_t *text, uint64_t len, char **out, uint64_t *out_len);
+/* tokens of `text` under a tokenizer of the separator family (bloomgpu.h bsg_tokenizer; NULL = the default), packed as
+ * (u32 little-endian length, bytes) per token: such a token may hold any byte but a separator.  BSH_E_INVALID for an
+ * invalid spec. */
+BSG_API int32_t bsh_tokenize_with(const uint8_t *text, uint64_t len, const bsg_tokenizer *tok, uint8_t **out, uint64_t *out_len);
 
 typedef struct bsh_entry_sets bsh_entry_sets;
 BSG_API bsh_entry_sets *bsh_entry_sets_new(void);
 BSG_API void bsh_entry_sets_free(bsh_entry_sets *s);
 /* indexRow on one marshaled-JSON row; BSH_E_INVALID if it is not valid JSON */
 BSG_API int32_t bsh_entry_sets_index_row(bsh_entry_sets *s, const uint8_t *row, uint64_t len);
+/* indexRow with the words of a separator-family tokenizer (NULL = the default); BSH_E_INVALID for an invalid spec too */
+BSG_API int32_t bsh_entry_sets_index_row_with(bsh_entry_sets *s, const uint8_t *row, uint64_t len, const bsg_tokenizer *tok);
 BSG_API int32_t bsh_entry_sets_union_into(const bsh_entry_sets *src, bsh_entry_sets *dst);
 BSG_API void bsh_entry_sets_counts(const bsh_entry_sets *s, uint64_t counts[3]);
 /* packed export of one kind (0 field, 1 token, 2 field::token): sizes, then fill */
@@ -63,6 +70,9 @@ BSG_API int32_t bsh_batch_export(const bsh_batch *b, uint8_t *term_bytes, uint32
 
 /* final exact test of one row against one expression: 1 match, 0 no match, negative error */
 BSG_API int32_t bsh_match_row(const char *expr_json, uint64_t expr_len, const uint8_t *row, uint64_t row_len);
+/* the same under a separator-family tokenizer (bloomgpu.h bsg_tokenizer; NULL = the default): the host matcher the rows
+ * bsg_match_rows_tok hands back are decided by.  BSH_E_INVALID for an invalid spec. */
+BSG_API int32_t bsh_match_row_with(const char *expr_json, uint64_t expr_len, const uint8_t *row, uint64_t row_len, const bsg_tokenizer *tok);
 /* pruneBloomQuery = AndBloomQueries(bloom, RegexFieldGuardBloomQuery(regex)) (query_exec.go:220, query.go:651-718) as JSON in the
  * reference's struct shape; "null" when both sides are nil.  regex_json: {"ExpressionType": "CONDITION"|"AND"|"OR",
  * "Condition": {"Field", "Pattern"}, "Children": [...]}. */
@@ -87,7 +97,8 @@ BSG_API uint32_t bsh_crc32c(const uint8_t *data, uint64_t len);
 typedef struct bse_engine bse_engine;
 /* config_json: {"MaxRowGroupRows":..,"MaxRowGroupBytes":..,"MaxBufferedRows":..,"MaxBufferedBytes":..,
  *               "BloomFalsePositiveRate":..,"PartitionField":"..","DeviceIngest":true|false,"DeviceMatch":true|false,
- *               "DeviceRegex":true|false}; missing keys take the
+ *               "DeviceRegex":true|false,"Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false}};
+ *               missing keys take the
  *               reference defaults.  DeviceIngest (default false): rows are walked / tokenized / deduplicated /
  *               counted on the GPU at flush and merge time (bloomgpu.h bsg_ingest_*) instead of by indexRow on the
  *               host at ingest time; the files it writes are byte-identical either way.  DeviceMatch (default false): the
@@ -95,7 +106,11 @@ typedef struct bse_engine bse_engine;
  *               the delivered row set is the same.  DeviceRegex (default false, needs DeviceMatch):
  *               a query whose regex patterns all lie in the device's RE2 subset is matched bloom AND regex by one
  *               bsg_match_rows_regex call, the rows it hands back by the host matcher on the same DFAs; other regex queries
- *               keep the std::regex path. */
+ *               keep the std::regex path.  Tokenizer (default: BasicWhitespaceLowerTokenizer): the engine's tokenizer
+ *               of the separator family (bloomgpu.h bsg_tokenizer), used by indexing, the host matcher and the device calls;
+ *               a missing member is Go's zero value ("" / false); BSE_E_INVALID_CONFIG for a NUL or non-ASCII separator.
+ *               The config is checked before ctx: an invalid one gives BSE_E_INVALID_CONFIG even with a NULL ctx, a valid one
+ *               with a NULL ctx BSH_E_INVALID. */
 BSG_API int32_t bse_open(const char *config_json, uint64_t len, bsg_ctx *ctx, bse_engine **out);
 BSG_API void bse_close(bse_engine *e);
 BSG_API const char *bse_last_error(bse_engine *e);

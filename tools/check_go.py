@@ -11,7 +11,9 @@ these ~1 900 lines of Go have never met a compiler; this lowers the chance that 
  3. every identifier the overlay uses that it does not declare itself is declared somewhere in the reference's non-test sources,
     in the cgo binding, or is a Go builtin / standard-library name from a short list (catches a misremembered newBloomEntrySets);
  4. go/overlay/engine_gpu.patch applies cleanly to the reference (patch --dry-run), and the names its hooks call exist in
-    BOTH gpu_engine.go and gpu_engine_stub.go with the same parameter counts.
+    BOTH gpu_engine.go and gpu_engine_stub.go with the same parameter counts (the gpuEngine / gpuFlushFilters / gpuRowVerdicts
+    methods and the top-level hooks openGPUEngine and gpuTokenizerFunc), and the types its config fields name that the
+    reference does not declare (GPUTokenizer) are declared in both files.
 Checks 3 and 4 need the reference checkout (default /root/reference; skipped with a note when absent).
 Exit status 0 = clean; every finding is printed.
 """
@@ -329,12 +331,16 @@ def check_reference_names(overlay_files, binding_files, reference, problems):
                 problems.append("reference: no %s declaration of %s (the overlay relies on it)" % (kind, name))
 
 
+TOP_HOOKS = ("openGPUEngine", "gpuTokenizerFunc")   # top-level functions engine_gpu.patch calls
+PATCH_TYPES = ("GPUTokenizer",)                      # overlay types engine_gpu.patch's config fields name
+
+
 def hook_signatures(path: str):
-    """{name: parameter count} of the gpuEngine / gpuFlushFilters / gpuRowVerdicts methods and openGPUEngine in a file."""
+    """{name: parameter count} of the gpuEngine / gpuFlushFilters / gpuRowVerdicts methods and the TOP_HOOKS in a file."""
     src = strip_go(open(path).read())
     out = {}
     for m in re.finditer(r"^func\s+(?:\(\s*\w*\s*\*?(gpuEngine|gpuFlushFilters|gpuRowVerdicts)\s*\)\s*)?(\w+)\s*\(", src, flags=re.M):
-        if m.group(1) is None and m.group(2) != "openGPUEngine":
+        if m.group(1) is None and m.group(2) not in TOP_HOOKS:
             continue
         close = matching_paren(src, m.end() - 1)
         params = split_args(src[m.end():close])
@@ -383,11 +389,19 @@ def check_patch(reference, problems, notes):
                     problems.append("engine_gpu.patch calls %s, which gpu_engine.go does not declare" % key)
                 elif real[key] != n:
                     problems.append("engine_gpu.patch calls %s with %d arguments; it takes %d" % (key, n, real[key]))
-        m = re.search(r"openGPUEngine\s*\(", added)
-        if not m or len(split_args(added[m.end():matching_paren(added, m.end() - 1)])) != real.get(".openGPUEngine"):
-            problems.append("engine_gpu.patch's openGPUEngine call does not match its declaration")
+        for hook in TOP_HOOKS:
+            m = re.search(hook + r"\s*\(", added)
+            if not m or len(split_args(added[m.end():matching_paren(added, m.end() - 1)])) != real.get("." + hook):
+                problems.append("engine_gpu.patch's %s call does not match its declaration" % hook)
+            n_calls += 1
+        for typ in PATCH_TYPES:
+            if not re.search(r"\b" + typ + r"\b", added):
+                problems.append("engine_gpu.patch no longer names %s: drop it from PATCH_TYPES" % typ)
+            for f in ("gpu_engine.go", "gpu_engine_stub.go"):
+                if not re.search(r"^type\s+" + typ + r"\b", strip_go(open(os.path.join(ROOT, "go", "overlay", f)).read()), flags=re.M):
+                    problems.append("%s is named by engine_gpu.patch but not declared in %s" % (typ, f))
         notes.append("engine_gpu.patch applies to %s (%d hunks, %d hook calls checked against gpu_engine.go and the stub)"
-                     % (reference, open(patch).read().count("\n@@"), n_calls + 1))
+                     % (reference, open(patch).read().count("\n@@"), n_calls))
     finally:
         shutil.rmtree(work, ignore_errors=True)
 

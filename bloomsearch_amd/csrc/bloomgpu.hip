@@ -14,6 +14,7 @@
 #include "match.hip.h"
 #include "host/combiner_sync.hpp"
 #include "host/regex_dfa.hpp"  // FieldRegex patterns -> the DFA tables k_match_rows_regex steps
+#include "host/row_chunks.hpp" // the chunk plan and byte ranges RowUpload copies by
 #include "host/text.hpp"   // the host walker's Unicode tables: the device defers to the same data
 #include <hip/hip_ext.h>
 
@@ -78,8 +79,8 @@ bsg_ctx *root_of(bsg_ctx *c);
     do {                                                                                   \
         hipError_t e_ = (expr);                                                            \
         if (e_ != hipSuccess)                                                              \
-            return fail(BSG_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                               \
+            return fail(e_ == hipErrorOutOfMemory ? BSG_E_NOMEM : BSG_E_HIP, "%s failed: %s (%s:%d)", #expr, \
+                        hipGetErrorString(e_), __FILE__, __LINE__);                        \
     } while (0)
 
 constexpr uint32_t kLdsBudget = 144 * 1024;   // dynamic LDS a workgroup may request (of 160 KiB per CU; opt-in above 64 KiB)
@@ -226,6 +227,120 @@ struct Device {
     std::atomic<uint64_t> calls{0};   // construct / match parts this device has served (bsg_device_calls)
     float last_or_ms = 0.f;    // this device's last k_or_reduce_blocks (the context keeps the slowest device's: bsg_last_or_ms)
     bool or_pending = false;   // kb0/kb1 hold an un-read k_or_reduce_blocks dispatch
+};
+
+hipError_t ensure_copy_stream(Device &d)      // the copy stream and its cross-stream events are made on first use
+{
+    if (d.copy_stream) return hipSuccess;
+    hipError_t e = hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking);
+    for (int s = 0; s < 2 && e == hipSuccess; ++s) {
+        e = hipEventCreateWithFlags(&d.ev_eval[s], hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&d.ev_copy[s], hipEventDisableTiming);
+    }
+    return e;
+}
+
+// DevPool blocks owned by a scope (or by an object such as an ingest part) on a device whose lock the owner holds.  THE rule
+// for handing device memory back: a scope left on a failure path drains d.stream (and d.copy_stream if it exists) before its
+// first block goes back to the pool — an early return may leave a copy or a dispatch in flight that still touches the blocks,
+// or a copy from the caller's page-locked rows, and the pool hands a block to the next call at once.  On the success path the
+// caller has synchronised already and says so with done(): nothing is added there.
+struct Scratch {
+    Device &d;
+    std::vector<void *> blocks;
+    bool idle = false;
+    explicit Scratch(Device &dev) : d(dev) {}
+    Scratch(Scratch &&o) : d(o.d), blocks(std::move(o.blocks)), idle(o.idle) { o.blocks.clear(); }
+    ~Scratch() { clear(); }
+    template <class T>
+    hipError_t alloc(T **out, size_t n_bytes)
+    {
+        void *p = nullptr;
+        const hipError_t e = d.pool.alloc(&p, n_bytes);
+        if (e == hipSuccess) { blocks.push_back(p); *out = static_cast<T *>(p); }
+        return e;
+    }
+    void done() { idle = true; }           // the caller has synchronised: nothing in flight touches the blocks
+    void clear()
+    {
+        if (blocks.empty()) return;
+        if (!idle) {
+            (void)hipStreamSynchronize(d.stream);
+            if (d.copy_stream) (void)hipStreamSynchronize(d.copy_stream);
+        }
+        for (void *p : blocks) d.pool.free(p);
+        blocks.clear();
+    }
+};
+
+struct EventList {                         // events of one call, destroyed with it
+    std::vector<hipEvent_t> v;
+    EventList() = default;
+    EventList(const EventList &) = delete;
+    ~EventList() { for (hipEvent_t e : v) (void)hipEventDestroy(e); }
+    hipError_t add(uint32_t n, unsigned flags = hipEventDefault)
+    {
+        for (; n; --n) {
+            hipEvent_t e = nullptr;
+            if (hipError_t x = hipEventCreateWithFlags(&e, flags); x != hipSuccess) return x;
+            v.push_back(e);
+        }
+        return hipSuccess;
+    }
+};
+
+// The rows of one ingest / match call on their way to the device.  They travel in chunks (host/row_chunks.hpp) while the compute
+// stream works on the chunk before.  Order per chunk, which the overlap depends on: the caller launches K(c) (asynchronous),
+// THEN calls copy(c + 1) — from pageable memory that call only returns when the bytes are staged, and K(c) runs meanwhile —
+// then looks at what K(c) wrote.  This launches nothing; K(c) must be preceded by wait_landed(c) on the compute stream.
+struct RowUpload {
+    Device &d;
+    const uint8_t *src;                    // host bytes; off[] counts from here
+    uint8_t *dst;
+    const uint64_t *off;
+    const uint64_t n_bytes;
+    const std::vector<uint32_t> cuts;      // chunk c = rows [cuts[c], cuts[c + 1])
+    EventList landed;                      // per chunk: its bytes are on the device
+    hipStream_t cs = nullptr;              // where the bytes travel
+    uint64_t copied_to = 0;                // chunks are copied in order: chunk c starts where chunk c - 1 ended
+    RowUpload(Device &dev, const uint8_t *rows, uint8_t *d_rows, const uint64_t *row_off, uint32_t n_rows, uint64_t first_chunk_bytes)
+        : d(dev), src(rows), dst(d_rows), off(row_off), n_bytes(row_off[n_rows]), cuts(bsh::plan_row_chunks(row_off, n_rows, first_chunk_bytes)) {}
+    uint32_t n_chunks() const { return (uint32_t)cuts.size() - 1; }
+    // on the copy stream (made here if need be), behind everything enqueued on d.stream so far — the zeroed tail and the small
+    // uploads precede the first row bytes; or in order on d.stream itself
+    hipError_t start(bool on_copy_stream)
+    {
+        cs = d.stream;
+        if (!on_copy_stream) return hipSuccess;
+        hipError_t e = ensure_copy_stream(d);
+        if (e == hipSuccess) e = hipEventRecord(d.ev_eval[0], d.stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(d.copy_stream, d.ev_eval[0], 0);
+        cs = d.copy_stream;
+        return e;
+    }
+    hipError_t copy(uint32_t c)            // once per chunk, in order
+    {
+        const auto [b0, b1] = bsh::chunk_copy_range(off, cuts, c, n_bytes, copied_to);
+        copied_to = b1;
+        hipError_t e = landed.add(1, hipEventDisableTiming);
+        if (e == hipSuccess && b1 > b0) e = hipMemcpyAsync(dst + b0, src + b0, b1 - b0, hipMemcpyHostToDevice, cs);
+        if (e == hipSuccess) e = hipEventRecord(landed.v[c], cs);
+        return e;
+    }
+    hipError_t wait_landed(uint32_t c) { return cs == d.stream ? hipSuccess : hipStreamWaitEvent(d.stream, landed.v[c], 0); }
+};
+
+// BSG_LAB_TRACE (lab only): phase times of one call on stderr (tools/ingest_e2e.py, tools/match_trace.py read them)
+struct LabTrace {
+    const char *tag;
+    int dev;
+    std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+    void lap(const char *what) const
+    {
+        static const bool on = getenv("BSG_LAB_TRACE") != nullptr;
+        if (on) fprintf(stderr, "[%s dev %d] %-28s +%.3f ms\n", tag, dev, what,
+                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+    }
 };
 
 struct ArenaShard {
@@ -907,17 +1022,14 @@ int32_t bsg_hash_entries(bsg_ctx *ctx, const uint8_t *bytes, const uint32_t *off
 }
 
 // One bitset beyond LDS from binned locations (bin_build.hip.h): a.t / a.d / a.n_slots / a.n_locs_cap / a.out / a.overflow
-// come filled in; the scratch this takes from the pool is appended to `scratch` (freed by the caller after the stream has
-// drained).  first / last: timestamps of the first and the last dispatch, nullptr for none.
-static int32_t enqueue_binned_build(Device &d, bsg::BinArgs a, bool dense, std::vector<void *> &scratch, hipEvent_t first, hipEvent_t last)
+// come filled in; the scratch this takes from the pool joins the caller's `scratch`.  first / last: timestamps of the first
+// and the last dispatch, nullptr for none.
+static int32_t enqueue_binned_build(Device &d, bsg::BinArgs a, bool dense, Scratch &scratch, hipEvent_t first, hipEvent_t last)
 {
     a.n_windows = (uint32_t)((a.d.m + bsg::kBinWindowBits - 1) / bsg::kBinWindowBits);
-    HIP_TRY(d.pool.alloc((void **)&a.prefix, ((size_t)a.n_windows + 1) * 4));
-    scratch.push_back(a.prefix);
-    HIP_TRY(d.pool.alloc((void **)&a.cursor, (size_t)a.n_windows * 4));
-    scratch.push_back(a.cursor);
-    HIP_TRY(d.pool.alloc((void **)&a.locs, std::max<size_t>(a.n_locs_cap, 1) * 4));
-    scratch.push_back(a.locs);
+    HIP_TRY(scratch.alloc(&a.prefix, ((size_t)a.n_windows + 1) * 4));
+    HIP_TRY(scratch.alloc(&a.cursor, (size_t)a.n_windows * 4));
+    HIP_TRY(scratch.alloc(&a.locs, std::max<size_t>(a.n_locs_cap, 1) * 4));
     HIP_TRY(hipMemsetAsync(a.prefix, 0, ((size_t)a.n_windows + 1) * 4, d.stream));
     const uint32_t tiles = (uint32_t)((a.n_slots + bsg::kBinTile - 1) / bsg::kBinTile);
     if (dense) hipExtLaunchKernelGGL((bsg::k_bin_pass<false, true>), dim3(tiles), dim3(bsg::kBinThreads), 0, d.stream, first, nullptr, 0, a);
@@ -989,8 +1101,7 @@ static int32_t build_on_device(bsg_ctx *ctx, Device &d, BuildPart &P, const uint
     HIP_TRY(d.stage_words.reserve(n_words));
     HIP_TRY(hipMemsetAsync(d.stage_words.p, 0, n_words * 8, d.stream));
     bool launched = false;
-    std::vector<void *> scratch;
-    struct ScratchGuard { Device &d; std::vector<void *> &v; ~ScratchGuard() { if (!v.empty()) (void)hipStreamSynchronize(d.stream); for (void *p : v) d.pool.free(p); } } sguard{d, scratch};
+    Scratch scratch(d);
     uint32_t *d_over = nullptr;
     if (!items.empty() || !binned.empty()) {
         HIP_TRY(d.stage_desc.reserve(nf));
@@ -1028,8 +1139,7 @@ static int32_t build_on_device(bsg_ctx *ctx, Device &d, BuildPart &P, const uint
             HIP_TRY(hipGetLastError());
         }
         if (!binned.empty()) {
-            HIP_TRY(d.pool.alloc((void **)&d_over, 64));
-            scratch.push_back(d_over);
+            HIP_TRY(scratch.alloc(&d_over, 64));
             HIP_TRY(hipMemsetAsync(d_over, 0, 64, d.stream));
         }
         for (size_t bi = 0; bi < binned.size(); ++bi) {
@@ -1059,6 +1169,7 @@ static int32_t build_on_device(bsg_ctx *ctx, Device &d, BuildPart &P, const uint
         HIP_TRY(hipMemcpyAsync(out_words + P.w_lo, d.stage_words.p, (P.w_hi - P.w_lo) * 8, hipMemcpyDeviceToHost, d.stream));
         HIP_TRY(hipStreamSynchronize(d.stream));
     }
+    scratch.done();      // either branch above has synchronised the stream
     P.ms = 0.f;
     if (launched) HIP_TRY(hipEventElapsedTime(&P.ms, d.kb0, d.kb1));
     return BSG_OK;

@@ -46,35 +46,25 @@ int32_t encode_sections_device(Device &d, const uint64_t *d_words, const bsg_fil
         HIP_TRY(hipMemcpyAsync(d.d_crc, &crc_consts(), sizeof(bsg::CrcConsts), hipMemcpyHostToDevice, d.stream));
     }
     HIP_TRY(d.stage_region.reserve(total + 64));
+    Scratch scratch(d);
     bsg::EncodeInfo *d_info = nullptr;
-    HIP_TRY(d.pool.alloc(reinterpret_cast<void **>(&d_info), info.size() * sizeof(bsg::EncodeInfo)));
-    int32_t rc = BSG_OK;
-    hipError_t e = hipMemcpyAsync(d_info, info.data(), info.size() * sizeof(bsg::EncodeInfo), hipMemcpyHostToDevice, d.stream);
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventCreate(&e2);
-    if (e == hipSuccess) e = hipEventCreate(&e3);
-    if (e == hipSuccess) {
-        hipExtLaunchKernelGGL(bsg::k_encode_payload, dim3(n_blocks), dim3(256), 0, d.stream, e0, e1, 0, d_words,
-                              (const bsg::EncodeInfo *)d_info, d.stage_region.p);
-        hipExtLaunchKernelGGL(bsg::k_crc_sections, dim3(n_blocks), dim3(bsg::kDecodeThreads), 0, d.stream, e2, e3, 0,
-                              d.stage_region.p, (const bsg::EncodeInfo *)d_info, (const bsg::CrcConsts *)d.d_crc);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_region, d.stage_region.p, total, hipMemcpyDeviceToHost, d.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
-    if (e == hipSuccess) {
-        float a = 0.f, b = 0.f;
-        (void)hipEventElapsedTime(&a, e0, e1);
-        (void)hipEventElapsedTime(&b, e2, e3);
-        if (ms) *ms = a + b;
-    } else {
-        rc = fail(BSG_E_HIP, "encode sections: %s", hipGetErrorString(e));
-    }
-    for (hipEvent_t ev : {e0, e1, e2, e3}) if (ev) (void)hipEventDestroy(ev);
-    d.pool.free(d_info);
-    return rc;
+    HIP_TRY(scratch.alloc(&d_info, info.size() * sizeof(bsg::EncodeInfo)));
+    HIP_TRY(hipMemcpyAsync(d_info, info.data(), info.size() * sizeof(bsg::EncodeInfo), hipMemcpyHostToDevice, d.stream));
+    EventList ev;                          // start / stop of the two dispatches
+    HIP_TRY(ev.add(4));
+    hipExtLaunchKernelGGL(bsg::k_encode_payload, dim3(n_blocks), dim3(256), 0, d.stream, ev.v[0], ev.v[1], 0, d_words,
+                          (const bsg::EncodeInfo *)d_info, d.stage_region.p);
+    hipExtLaunchKernelGGL(bsg::k_crc_sections, dim3(n_blocks), dim3(bsg::kDecodeThreads), 0, d.stream, ev.v[2], ev.v[3], 0,
+                          d.stage_region.p, (const bsg::EncodeInfo *)d_info, (const bsg::CrcConsts *)d.d_crc);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_region, d.stage_region.p, total, hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    scratch.done();
+    float t_payload = 0.f, t_crc = 0.f;
+    (void)hipEventElapsedTime(&t_payload, ev.v[0], ev.v[1]);
+    (void)hipEventElapsedTime(&t_crc, ev.v[2], ev.v[3]);
+    if (ms) *ms = t_payload + t_crc;
+    return BSG_OK;
 }
 
 }  // namespace

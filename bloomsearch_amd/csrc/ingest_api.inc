@@ -15,20 +15,17 @@ using bsg::IngestTable;
 constexpr uint64_t kSlotBytes = 40;   // four base hashes + the keyed fingerprint (kept in a parallel array behind the slots)
 
 struct IngestPart {
-    Device *dev = nullptr;
+    Device *dev;
+    Scratch mem;                              // every device block the part keeps: slot storage (initial chunk + grown tables + parents) and the d_ arrays
+    explicit IngestPart(Device &d) : dev(&d), mem(d) {}
     uint32_t set0 = 0, row0 = 0;              // first set / first row of this part in the caller's numbering
     uint32_t n_rows = 0, n_sets = 0, n_parents = 0;
     std::vector<uint32_t> parent_of_set;
     std::vector<IngestTable> tables;          // host mirror of d_tables [(n_sets + n_parents) * 3]
-    std::vector<void *> allocs;               // slot storage (initial chunk + grown tables + parents)
-    void *placeholder = nullptr;              // 64 zeroed slots: what an empty parent's table points at
-    uint64_t slot_bytes = 0;                  // HBM held by slot storage (allocs)
+    uint64_t slot_bytes = 0;                  // HBM held by slot storage
     IngestTable *d_tables = nullptr;
     uint32_t *d_counts = nullptr, *d_status = nullptr;
-    uint8_t *d_rows = nullptr;
-    uint64_t *d_row_off = nullptr;
-    uint32_t *d_set_first = nullptr;
-    uint32_t *d_fb = nullptr, *d_nfb = nullptr;
+    uint32_t *d_set_first = nullptr, *d_nfb = nullptr;
     std::vector<uint32_t> fallback;           // part-local row indices
     std::vector<uint32_t> counts, status;     // last read back
     bool finished = false;
@@ -51,17 +48,12 @@ struct Ingest {
     uint32_t part_of_set(uint32_t s) const { return (uint32_t)(std::upper_bound(set_cut.begin(), set_cut.end(), s) - set_cut.begin()) - 1; }
 };
 
-void free_part(IngestPart &g)
+void free_part(IngestPart &g)                 // caller holds the device lock
 {
-    if (!g.dev) return;
     (void)hipSetDevice(g.dev->id);
-    for (void *p : g.allocs) g.dev->pool.free(p);
-    g.allocs.clear();
-    for (void *p : {(void *)g.d_tables, (void *)g.d_counts, (void *)g.d_status, (void *)g.d_rows, (void *)g.d_row_off,
-                    (void *)g.d_set_first, (void *)g.d_fb, (void *)g.d_nfb})
-        if (p) g.dev->pool.free(p);
-    g.d_tables = nullptr; g.d_counts = g.d_status = nullptr; g.d_rows = nullptr; g.d_row_off = nullptr;
-    g.d_set_first = nullptr; g.d_fb = g.d_nfb = nullptr;
+    g.mem.clear();
+    g.d_tables = nullptr; g.d_counts = g.d_status = nullptr;
+    g.d_set_first = g.d_nfb = nullptr;
 }
 
 void free_ingest(Ingest &g)
@@ -152,12 +144,6 @@ IngestTable make_table(void *base, uint64_t first_slot, uint64_t total_slots, ui
     return IngestTable{(uint64_t *)base + first_slot * 4, (uint64_t *)base + total_slots * 4 + first_slot, (uint32_t)(cap - 1), shift_for(cap)};
 }
 
-struct IngestEvents {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~IngestEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-};
-
 int32_t push_tables(IngestPart &g)
 {
     HIP_TRY(hipMemcpyAsync(g.d_tables, g.tables.data(), g.tables.size() * sizeof(IngestTable), hipMemcpyHostToDevice, g.dev->stream));
@@ -187,8 +173,7 @@ int32_t grow_overflowed(IngestPart &g, uint32_t first, uint32_t last, uint32_t *
         const uint64_t cap = ((uint64_t)g.tables[t].mask + 1) * 4;
         if (cap > (1ull << 31)) return fail(BSG_E_NOMEM, "distinct-entry table %u would exceed 2^31 slots", t);
         void *p = nullptr;
-        HIP_TRY(g.dev->pool.alloc(&p, cap * kSlotBytes));
-        g.allocs.push_back(p);
+        HIP_TRY(g.mem.alloc(&p, cap * kSlotBytes));
         g.slot_bytes += cap * kSlotBytes;
         HIP_TRY(hipMemsetAsync(p, 0, cap * kSlotBytes, g.dev->stream));
         fresh[t] = make_table(p, 0, cap, cap);
@@ -196,36 +181,22 @@ int32_t grow_overflowed(IngestPart &g, uint32_t first, uint32_t last, uint32_t *
     }
     if (items.empty()) return BSG_OK;
     // old tables stay where d_tables points; the fresh ones go to a temporary descriptor array
+    Scratch scratch(*g.dev);
     IngestTable *d_fresh = nullptr;
     bsg::UnionItem *d_items = nullptr;
-    HIP_TRY(g.dev->pool.alloc((void **)&d_fresh, fresh.size() * sizeof(IngestTable)));
-    if (hipError_t e0 = g.dev->pool.alloc((void **)&d_items, items.size() * sizeof(bsg::UnionItem)); e0 != hipSuccess) {
-        g.dev->pool.free(d_fresh);
-        return fail(BSG_E_HIP, "grow: %s", hipGetErrorString(e0));
+    HIP_TRY(scratch.alloc(&d_fresh, fresh.size() * sizeof(IngestTable)));
+    HIP_TRY(scratch.alloc(&d_items, items.size() * sizeof(bsg::UnionItem)));
+    HIP_TRY(hipMemcpyAsync(d_fresh, fresh.data(), fresh.size() * sizeof(IngestTable), hipMemcpyHostToDevice, g.dev->stream));
+    HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::UnionItem), hipMemcpyHostToDevice, g.dev->stream));
+    for (auto &it : items) {   // counts restart from zero: the rehash re-counts what it moves
+        HIP_TRY(hipMemsetAsync(g.d_counts + it.dst, 0, 4, g.dev->stream));
+        HIP_TRY(hipMemsetAsync(g.d_status + it.dst, 0, 4, g.dev->stream));
     }
-    int32_t rc = BSG_OK;
-    do {
-        hipError_t e;
-        if ((e = hipMemcpyAsync(d_fresh, fresh.data(), fresh.size() * sizeof(IngestTable), hipMemcpyHostToDevice, g.dev->stream)) != hipSuccess ||
-            (e = hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::UnionItem), hipMemcpyHostToDevice, g.dev->stream)) != hipSuccess) {
-            rc = fail(BSG_E_HIP, "grow: %s", hipGetErrorString(e));
-            break;
-        }
-        for (auto &it : items) {   // counts restart from zero: the rehash re-counts what it moves
-            if ((e = hipMemsetAsync(g.d_counts + it.dst, 0, 4, g.dev->stream)) != hipSuccess ||
-                (e = hipMemsetAsync(g.d_status + it.dst, 0, 4, g.dev->stream)) != hipSuccess) { rc = fail(BSG_E_HIP, "grow: %s", hipGetErrorString(e)); break; }
-        }
-        if (rc) break;
-        hipLaunchKernelGGL(bsg::k_ingest_union, dim3(64, (uint32_t)items.size()), dim3(256), 0, g.dev->stream,
-                           g.d_tables, d_fresh, d_items, g.d_counts, g.d_status);
-        if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(g.dev->stream)) != hipSuccess) {
-            rc = fail(BSG_E_HIP, "grow: %s", hipGetErrorString(e));
-            break;
-        }
-    } while (false);
-    g.dev->pool.free(d_fresh);
-    g.dev->pool.free(d_items);
-    if (rc) return rc;
+    hipLaunchKernelGGL(bsg::k_ingest_union, dim3(64, (uint32_t)items.size()), dim3(256), 0, g.dev->stream,
+                       g.d_tables, d_fresh, d_items, g.d_counts, g.d_status);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g.dev->stream));
+    scratch.done();
     g.tables = fresh;
     if (int32_t rc2 = push_tables(g)) return rc2;
     *grown = (uint32_t)items.size();
@@ -237,14 +208,14 @@ int32_t grow_overflowed(IngestPart &g, uint32_t first, uint32_t last, uint32_t *
 template <class Launch>
 int32_t run_until_fits(IngestPart &g, uint32_t first, uint32_t last, float *ms, Launch &&launch)
 {
-    IngestEvents ev;
-    HIP_TRY(ev.init());
+    EventList ev;                          // start / stop of the dispatch
+    HIP_TRY(ev.add(2));
     for (int attempt = 0; attempt < 12; ++attempt) {
-        if (int32_t rc = launch(ev.a, ev.b)) return rc;
+        if (int32_t rc = launch(ev.v[0], ev.v[1])) return rc;
         HIP_TRY(hipGetLastError());
         if (int32_t rc = read_state(g)) return rc;
         float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, ev.a, ev.b));
+        HIP_TRY(hipEventElapsedTime(&t, ev.v[0], ev.v[1]));
         *ms += t;
         uint32_t grown = 0;
         if (int32_t rc = grow_overflowed(g, first, last, &grown)) return rc;
@@ -275,21 +246,17 @@ int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *
                          const uint32_t *slots_hint, uint32_t flags, const bsg::TokSpec *tok)
 {
     const uint64_t n_bytes = row_off[n_rows];
-    static const bool trace = getenv("BSG_LAB_TRACE") != nullptr;   // lab only: phase times of this call on stderr
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (trace) fprintf(stderr, "[bsg_ingest_rows dev %d] %-28s +%.3f ms\n", d.id, what,
-                           std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-    };
+    const LabTrace trace{"bsg_ingest_rows", d.id};
     IngestPart *g = &G;
-    g->dev = &d;
     g->n_rows = n_rows; g->n_sets = n_sets; g->n_parents = n_parents;
     g->parent_of_set.assign(n_sets, 0xFFFFFFFFu);
     if (parent_of_set) g->parent_of_set.assign(parent_of_set, parent_of_set + n_sets);
     d.calls.fetch_add(1, std::memory_order_relaxed);
     std::lock_guard<std::mutex> lk(d.mu);
     if (int32_t rc = use_device(d)) return rc;
-    struct Guard { IngestPart *g; ~Guard() { if (g) free_part(*g); } } guard{g};
+    // What only this call needs on the device (the row bytes) is `scratch`; what the part keeps is g->mem, declared idle at the
+    // successful end only: a failed call's parts are emptied by ingest_rows_call (free_ingest), drained first like any Scratch.
+    Scratch scratch(d);
 
     // initial capacities: fields are few; tokens / field::tokens get 4 slots per row unless the caller knows better
     const uint32_t nt = g->n_tables();
@@ -309,8 +276,7 @@ int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *
     }
     // 32-byte hash slots, then one 8-byte fingerprint per slot (kSlotBytes = 40 in all)
     void *chunk = nullptr;
-    HIP_TRY(d.pool.alloc(&chunk, std::max<uint64_t>(total_slots, 1) * kSlotBytes));
-    g->allocs.push_back(chunk);
+    HIP_TRY(g->mem.alloc(&chunk, std::max<uint64_t>(total_slots, 1) * kSlotBytes));
     g->slot_bytes += std::max<uint64_t>(total_slots, 1) * kSlotBytes;
     HIP_TRY(hipMemsetAsync(chunk, 0, total_slots * kSlotBytes, d.stream));
     for (uint32_t t = 0; t < n_sets * 3; ++t) g->tables[t] = make_table(chunk, first_slot[t], total_slots, (uint64_t)g->tables[t].mask + 1);
@@ -318,93 +284,53 @@ int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *
     // parent table is a 64-slot placeholder nothing inserts into
     if (n_parents) {
         void *ph = nullptr;
-        HIP_TRY(d.pool.alloc(&ph, 64 * kSlotBytes));
-        g->allocs.push_back(ph);
+        HIP_TRY(g->mem.alloc(&ph, 64 * kSlotBytes));
         HIP_TRY(hipMemsetAsync(ph, 0, 64 * kSlotBytes, d.stream));
         for (uint32_t t = n_sets * 3; t < nt; ++t) g->tables[t] = make_table(ph, 0, 64, 64);
-        g->placeholder = ph;
     }
-    HIP_TRY(d.pool.alloc((void **)&g->d_tables, std::max<size_t>(nt, 1) * sizeof(IngestTable)));
-    HIP_TRY(d.pool.alloc((void **)&g->d_counts, std::max<size_t>(nt, 1) * 4));
-    HIP_TRY(d.pool.alloc((void **)&g->d_status, std::max<size_t>(nt, 1) * 4));
+    HIP_TRY(g->mem.alloc(&g->d_tables, std::max<size_t>(nt, 1) * sizeof(IngestTable)));
+    HIP_TRY(g->mem.alloc(&g->d_counts, std::max<size_t>(nt, 1) * 4));
+    HIP_TRY(g->mem.alloc(&g->d_status, std::max<size_t>(nt, 1) * 4));
     HIP_TRY(hipMemsetAsync(g->d_counts, 0, std::max<size_t>(nt, 1) * 4, d.stream));
     HIP_TRY(hipMemsetAsync(g->d_status, 0, std::max<size_t>(nt, 1) * 4, d.stream));
     if (nt) if (int32_t rc = push_tables(*g)) return rc;
-    HIP_TRY(d.pool.alloc((void **)&g->d_rows, n_bytes + 64));
-    HIP_TRY(d.pool.alloc((void **)&g->d_row_off, ((size_t)n_rows + 1) * 8));
-    HIP_TRY(d.pool.alloc((void **)&g->d_set_first, ((size_t)n_sets + 1) * 4));
-    HIP_TRY(d.pool.alloc((void **)&g->d_fb, std::max<size_t>(n_rows, 1) * 4));
-    HIP_TRY(d.pool.alloc((void **)&g->d_nfb, 128));
-    lap("device buffers allocated");
-    HIP_TRY(hipMemsetAsync(g->d_rows + n_bytes, 0, 64, d.stream));
-    HIP_TRY(hipMemcpyAsync(g->d_row_off, row_off, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream));
+    uint8_t *d_rows = nullptr;
+    uint64_t *d_row_off = nullptr; uint32_t *d_fb = nullptr;
+    HIP_TRY(scratch.alloc(&d_rows, n_bytes + 64));
+    HIP_TRY(scratch.alloc(&d_row_off, ((size_t)n_rows + 1) * 8));
+    HIP_TRY(g->mem.alloc(&g->d_set_first, ((size_t)n_sets + 1) * 4));
+    HIP_TRY(scratch.alloc(&d_fb, std::max<size_t>(n_rows, 1) * 4));
+    HIP_TRY(g->mem.alloc(&g->d_nfb, 128));
+    trace.lap("device buffers allocated");
+    HIP_TRY(hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream));
+    HIP_TRY(hipMemcpyAsync(d_row_off, row_off, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipMemcpyAsync(g->d_set_first, set_first_row, ((size_t)n_sets + 1) * 4, hipMemcpyHostToDevice, d.stream));
 
     g->stats.n_rows = n_rows;
     g->stats.row_bytes = n_bytes;
     if (n_rows) {
         bsg::IngestArgs a{};
-        a.rows = g->d_rows; a.row_off = g->d_row_off; a.set_first_row = g->d_set_first;
-        a.counts = g->d_counts; a.status = g->d_status; a.fallback_rows = g->d_fb; a.n_fallback = g->d_nfb;
+        a.rows = d_rows; a.row_off = d_row_off; a.set_first_row = g->d_set_first;
+        a.counts = g->d_counts; a.status = g->d_status; a.fallback_rows = d_fb; a.n_fallback = g->d_nfb;
         a.n_rows = n_rows; a.n_sets = n_sets; a.validate = (flags & BSG_INGEST_TRUSTED_JSON) ? 0u : 1u;
         a.key = ctx->fp_key;
         if (int32_t rc = ensure_lower_table(d)) return rc;
         a.lower = d.d_lower;
         HIP_TRY(hipMemsetAsync(G.d_nfb, 0, 128, d.stream));
-        // The rows travel in chunks of ~kIngestChunkBytes on the copy stream while the compute stream walks the chunk
-        // before: 2.5 GB of rows (BASELINE configs[2]) take ~50 ms over PCIe, their walk ~30 ms — one after the other
-        // they would add up.  Order per chunk: launch K(c) (asynchronous), THEN enqueue copy(c + 1) — from pageable
-        // memory that call only returns when the bytes are staged, and K(c) runs meanwhile — then look at K(c)'s tables.
-        if (!d.copy_stream) {
-            HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking));
-            for (int s2 = 0; s2 < 2; ++s2) {
-                HIP_TRY(hipEventCreateWithFlags(&d.ev_eval[s2], hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&d.ev_copy[s2], hipEventDisableTiming));
-            }
-        }
-        // The first chunk is small (the walk starts as soon as it has landed), every later one twice as large up to 4x:
-        // a launch must be big enough that each of the ~3 workgroups a CU holds walks several rows per lane (warm dedup
-        // cache, see k_ingest_rows), and the last chunk's walk is all that is left once the copy is over.
-        std::vector<uint32_t> cuts{0};                  // chunk c = rows [cuts[c], cuts[c + 1])
-        uint64_t chunk_bytes = ctx->ingest_chunk_bytes;
-        for (uint32_t r = 0; r < n_rows;) {
-            const uint64_t lim = row_off[r] + chunk_bytes;
-            if (chunk_bytes < 4 * ctx->ingest_chunk_bytes) chunk_bytes *= 2;
-            uint32_t e = (uint32_t)(std::upper_bound(row_off + r + 1, row_off + n_rows + 1, lim) - row_off) - 1;
-            e = std::max(e, r + 1);
-            // whole 256-row workgroups per chunk (the last one takes what is left)
-            if (e < n_rows) e = std::min<uint32_t>(n_rows, (e + 255u) / 256u * 256u);
-            cuts.push_back(e);
-            r = e;
-        }
-        const uint32_t n_chunks = (uint32_t)cuts.size() - 1;
-        std::vector<hipEvent_t> landed(n_chunks, nullptr);
-        struct EvGuard { std::vector<hipEvent_t> &v; ~EvGuard() { for (auto e : v) if (e) (void)hipEventDestroy(e); } } evguard{landed};
-        uint64_t copied_to = 0;            // chunks are copied in order: chunk c starts where chunk c - 1 ended
-        auto copy_chunk = [&](uint32_t c) -> int32_t {
-            // The walker reads whole aligned 8-byte words, at most the word that holds a row's last byte: a chunk's range ends 16..23
-            // bytes past its last row (rounded to 8) so that K(c) never touches a byte that has not landed — and the NEXT chunk
-            // starts exactly there, so no copy ever rewrites a byte a running kernel may be reading (ranges are disjoint).
-            const uint64_t b0 = c == 0 ? (row_off[cuts[c]] & ~7ull) : copied_to, b1 = std::max(b0, std::min<uint64_t>(n_bytes, (row_off[cuts[c + 1]] + 23) & ~7ull));
-            copied_to = b1;
-            HIP_TRY(hipEventCreateWithFlags(&landed[c], hipEventDisableTiming));
-            if (b1 > b0) HIP_TRY(hipMemcpyAsync(g->d_rows + b0, rows + b0, b1 - b0, hipMemcpyHostToDevice, d.copy_stream));
-            HIP_TRY(hipEventRecord(landed[c], d.copy_stream));
-            return BSG_OK;
-        };
-        // the memsets / small copies above must precede the first row bytes
-        HIP_TRY(hipEventRecord(d.ev_eval[0], d.stream));
-        HIP_TRY(hipStreamWaitEvent(d.copy_stream, d.ev_eval[0], 0));
-        if (int32_t rc = copy_chunk(0)) return rc;
-        lap("first chunk enqueued");
+        // The rows travel in chunks on the copy stream while the compute stream walks the chunk before (RowUpload)
+        RowUpload up(d, rows, d_rows, row_off, n_rows, ctx->ingest_chunk_bytes);
+        const uint32_t n_chunks = up.n_chunks();
+        HIP_TRY(up.start(true));
+        HIP_TRY(up.copy(0));
+        trace.lap("first chunk enqueued");
         for (uint32_t c = 0; c < n_chunks; ++c) {
             bool first_attempt = true;
-            const uint32_t rf = cuts[c], re = cuts[c + 1];
+            const uint32_t rf = up.cuts[c], re = up.cuts[c + 1];
             uint32_t nfb_before = 0;
             if (c) HIP_TRY(hipMemcpy(&nfb_before, g->d_nfb, 4, hipMemcpyDeviceToHost));   // K(c-1) has been synchronised
             int32_t rc = run_until_fits(G, 0, n_sets * 3, &g->stats.ms_walk, [&](hipEvent_t e0, hipEvent_t e1) -> int32_t {
                 if (!first_attempt) HIP_TRY(hipMemcpyAsync(G.d_nfb, &nfb_before, 4, hipMemcpyHostToDevice, d.stream));   // a re-run lists its rows again
-                else HIP_TRY(hipStreamWaitEvent(d.stream, landed[c], 0));
+                else HIP_TRY(up.wait_landed(c));
                 bsg::IngestArgs b = a;
                 b.tables = G.d_tables;
                 b.row_first = rf; b.row_end = re;
@@ -421,14 +347,14 @@ int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *
                                           dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b);
                 if (first_attempt) {
                     first_attempt = false;
-                    if (c + 1 < n_chunks) if (int32_t rc2 = copy_chunk(c + 1)) return rc2;
+                    if (c + 1 < n_chunks) HIP_TRY(up.copy(c + 1));   // K(c) is running: now the next chunk's bytes
                 }
                 return BSG_OK;
             });
             if (rc) return rc;
         }
         HIP_TRY(hipStreamSynchronize(d.copy_stream));
-        lap("all chunks walked");
+        trace.lap("all chunks walked");
         uint32_t nfb = 0;
         HIP_TRY(hipMemcpy(&nfb, g->d_nfb, 4, hipMemcpyDeviceToHost));
 #ifdef BSG_INGEST_PROF
@@ -443,17 +369,15 @@ int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *
         }
 #endif
         g->fallback.resize(nfb);
-        if (nfb) HIP_TRY(hipMemcpy(g->fallback.data(), g->d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
+        if (nfb) HIP_TRY(hipMemcpy(g->fallback.data(), d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
         std::sort(g->fallback.begin(), g->fallback.end());
     } else {
         if (int32_t rc = read_state(*g)) return rc;
     }
     g->stats.n_fallback_rows = (uint32_t)g->fallback.size();
-    // the row bytes are no longer needed on the device
-    d.pool.free(g->d_rows); g->d_rows = nullptr;
-    d.pool.free(g->d_row_off); g->d_row_off = nullptr;
-    d.pool.free(g->d_fb); g->d_fb = nullptr;
-    guard.g = nullptr;
+    // both streams have been synchronised: the row bytes leave the device with `scratch`, the part keeps the rest
+    scratch.done();
+    g->mem.done();
     return BSG_OK;
 }
 
@@ -472,26 +396,24 @@ int32_t union_global_tables(IngestPart &G, const std::vector<uint64_t> &sum, con
         total += cap;
     }
     void *chunk = nullptr;
-    HIP_TRY(d.pool.alloc(&chunk, total * kSlotBytes));
-    G.allocs.push_back(chunk);
+    HIP_TRY(G.mem.alloc(&chunk, total * kSlotBytes));
     G.slot_bytes += total * kSlotBytes;
     HIP_TRY(hipMemsetAsync(chunk, 0, total * kSlotBytes, d.stream));
     for (size_t i = 0; i < sum.size(); ++i)
         G.tables[(size_t)G.n_sets * 3 + i] = make_table(chunk, first[i], total, (uint64_t)G.tables[(size_t)G.n_sets * 3 + i].mask + 1);
     if (int32_t rc = push_tables(G)) return rc;
     if (items.empty()) return BSG_OK;
+    Scratch scratch(d);
     bsg::UnionItem *d_items = nullptr;
-    HIP_TRY(d.pool.alloc((void **)&d_items, items.size() * sizeof(bsg::UnionItem)));
-    hipError_t e = hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::UnionItem), hipMemcpyHostToDevice, d.stream);
-    int32_t rc = e == hipSuccess ? BSG_OK : fail(BSG_E_HIP, "finish: %s", hipGetErrorString(e));
-    if (!rc)
-        rc = run_until_fits(G, G.n_sets * 3, G.n_tables(), &G.stats.ms_union, [&](hipEvent_t e0, hipEvent_t e1) -> int32_t {
+    HIP_TRY(scratch.alloc(&d_items, items.size() * sizeof(bsg::UnionItem)));
+    HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::UnionItem), hipMemcpyHostToDevice, d.stream));
+    if (int32_t rc = run_until_fits(G, G.n_sets * 3, G.n_tables(), &G.stats.ms_union, [&](hipEvent_t e0, hipEvent_t e1) -> int32_t {
             hipExtLaunchKernelGGL(bsg::k_ingest_union, dim3(64, (uint32_t)items.size()), dim3(256), 0, d.stream, e0, e1, 0,
                                   G.d_tables, G.d_tables, d_items, G.d_counts, G.d_status);
             return BSG_OK;
-        });
-    d.pool.free(d_items);
-    return rc;
+        })) return rc;
+    scratch.done();                        // run_until_fits returns synchronised
+    return BSG_OK;
 }
 
 // The file-level union partition by partition in LDS (k_union_partitions): dense parents of exactly the distinct entries,
@@ -513,8 +435,7 @@ int32_t union_partitioned(IngestPart &G, const std::vector<uint64_t> &sum, const
     if (total == 0) return push_tables(G);                 // every parent is empty: the placeholders stay
     if (total > (1ull << 31)) { *fell_back = true; return BSG_OK; }
     void *chunk = nullptr;
-    HIP_TRY(d.pool.alloc(&chunk, total * kSlotBytes));
-    G.allocs.push_back(chunk);
+    HIP_TRY(G.mem.alloc(&chunk, total * kSlotBytes));
     G.slot_bytes += total * kSlotBytes;
     uint32_t max_log2P = 0;
     for (uint32_t t = 0; t < P3; ++t) {
@@ -534,15 +455,12 @@ int32_t union_partitioned(IngestPart &G, const std::vector<uint64_t> &sum, const
     }
     uint32_t *d_kids = nullptr;
     bsg::PartParent *d_parents = nullptr;
-    HIP_TRY(d.pool.alloc((void **)&d_kids, std::max<size_t>(child_list.size(), 1) * 4));
-    if (hipError_t e0 = d.pool.alloc((void **)&d_parents, parents.size() * sizeof(bsg::PartParent)); e0 != hipSuccess) {
-        d.pool.free(d_kids);
-        return fail(BSG_E_HIP, "finish: %s", hipGetErrorString(e0));
-    }
-    struct Free { Device &d; void *a, *b; ~Free() { d.pool.free(a); d.pool.free(b); } } fr{d, d_kids, d_parents};
+    Scratch scratch(d);
+    HIP_TRY(scratch.alloc(&d_kids, std::max<size_t>(child_list.size(), 1) * 4));
+    HIP_TRY(scratch.alloc(&d_parents, parents.size() * sizeof(bsg::PartParent)));
     if (!child_list.empty()) HIP_TRY(hipMemcpyAsync(d_kids, child_list.data(), child_list.size() * 4, hipMemcpyHostToDevice, d.stream));
-    IngestEvents ev;
-    HIP_TRY(ev.init());
+    EventList ev;                          // start / stop of the dispatch
+    HIP_TRY(ev.add(2));
     // `todo`: the parents this attempt launches — all of them first, then only those whose partitioning was too coarse (their
     // records are the first todo.size() entries of d_parents; the kernel reaches counts / status / output through pp.table, so
     // the finished parents keep their counts and their dense lists while the others are repeated 4 x finer)
@@ -556,12 +474,12 @@ int32_t union_partitioned(IngestPart &G, const std::vector<uint64_t> &sum, const
         HIP_TRY(hipMemcpyAsync(d_parents, launch.data(), launch.size() * sizeof(bsg::PartParent), hipMemcpyHostToDevice, d.stream));
         if (todo.size() == P3) HIP_TRY(hipMemsetAsync(G.d_counts + G.n_sets * 3, 0, (size_t)P3 * 4, d.stream));
         else for (uint32_t t : todo) HIP_TRY(hipMemsetAsync(G.d_counts + G.n_sets * 3 + t, 0, 4, d.stream));
-        hipExtLaunchKernelGGL(bsg::k_union_partitions, dim3(1u << max_log2P, (uint32_t)todo.size()), dim3(bsg::kPartThreads), bsg::kPartLdsBytes, d.stream, ev.a, ev.b, 0,
+        hipExtLaunchKernelGGL(bsg::k_union_partitions, dim3(1u << max_log2P, (uint32_t)todo.size()), dim3(bsg::kPartThreads), bsg::kPartLdsBytes, d.stream, ev.v[0], ev.v[1], 0,
                               (const IngestTable *)G.d_tables, (const uint32_t *)d_kids, (const bsg::PartParent *)d_parents, G.d_counts, G.d_status);
         HIP_TRY(hipGetLastError());
         if (int32_t rc = read_state(G)) return rc;
         float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+        HIP_TRY(hipEventElapsedTime(&ms, ev.v[0], ev.v[1]));
         G.stats.ms_union += ms;
         bool again = false;
         std::vector<uint32_t> next;
@@ -577,6 +495,7 @@ int32_t union_partitioned(IngestPart &G, const std::vector<uint64_t> &sum, const
                 const uint32_t n = G.counts[G.n_sets * 3 + t];
                 if (n) G.tables[G.n_sets * 3 + t] = IngestTable{parents[t].out_slots, parents[t].out_fps, n - 1, 0};      // a dense list
             }
+            scratch.done();                // read_state has synchronised; push_tables touches neither list
             return push_tables(G);
         }
         // only the overflowed parents' status is cleared: exotic flags of the others (and theirs) must survive
@@ -587,6 +506,7 @@ int32_t union_partitioned(IngestPart &G, const std::vector<uint64_t> &sum, const
     // not splittable (an adversarial key distribution): clear what this path left behind and let the global tables do it
     HIP_TRY(hipMemsetAsync(G.d_counts + G.n_sets * 3, 0, (size_t)P3 * 4, d.stream));
     HIP_TRY(hipMemsetAsync(G.d_status + G.n_sets * 3, 0, (size_t)P3 * 4, d.stream));
+    scratch.done();                        // the last attempt's read_state has synchronised; the memsets touch neither list
     *fell_back = true;
     return BSG_OK;
 }
@@ -637,9 +557,9 @@ int32_t merge_parents(bsg_ctx *ctx, Ingest &I)
         Device &d = *G.dev;
         std::lock_guard<std::mutex> lk(d.mu);
         if (int32_t rc2 = use_device(d)) return rc2;
+        Scratch scratch(d);
         uint32_t *d_counter = nullptr;
-        HIP_TRY(d.pool.alloc((void **)&d_counter, (size_t)P3 * 4));
-        struct FreeCounter { Device &d; void *p; ~FreeCounter() { d.pool.free(p); } } fc{d, d_counter};
+        HIP_TRY(scratch.alloc(&d_counter, (size_t)P3 * 4));
         HIP_TRY(hipMemsetAsync(d_counter, 0, (size_t)P3 * 4, d.stream));
         for (uint32_t t = 0; t < P3; ++t) {
             const uint32_t n = G.counts[G.n_sets * 3 + t];
@@ -654,17 +574,16 @@ int32_t merge_parents(bsg_ctx *ctx, Ingest &I)
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipStreamSynchronize(d.stream));
+        scratch.done();
         return BSG_OK;
     });
     if (rc) { drop_dense(); return rc; }
-    auto M = std::make_shared<IngestPart>();
-    M->dev = &H;
+    auto M = std::make_shared<IngestPart>(H);
     M->n_sets = 0; M->n_parents = I.n_parents;
-    std::vector<void *> copies;
     {
         std::lock_guard<std::mutex> lk(H.mu);
-        struct Guard { IngestPart *g; std::vector<void *> &c; Device &H; ~Guard() { for (void *p : c) H.pool.free(p); if (g) free_part(*g); } } guard{M.get(), copies, H};
         if ((rc = use_device(H))) { drop_dense(); return rc; }
+        Scratch copies(H);                 // the other parts' dense lists on this device, and the union's two argument arrays
         // capacity: 2 x the sum of the partial counts bounds the union
         M->tables.assign(P3, IngestTable{nullptr, nullptr, 0, 0});
         uint64_t total = 0;
@@ -678,12 +597,12 @@ int32_t merge_parents(bsg_ctx *ctx, Ingest &I)
             total += cap;
         }
         void *chunk = nullptr;
-        hipError_t e = H.pool.alloc(&chunk, total * kSlotBytes);
-        if (e == hipSuccess) { M->allocs.push_back(chunk); M->slot_bytes += total * kSlotBytes; e = hipMemsetAsync(chunk, 0, total * kSlotBytes, H.stream); }
+        hipError_t e = M->mem.alloc(&chunk, total * kSlotBytes);
+        if (e == hipSuccess) { M->slot_bytes += total * kSlotBytes; e = hipMemsetAsync(chunk, 0, total * kSlotBytes, H.stream); }
         for (uint32_t t = 0; t < P3 && e == hipSuccess; ++t) M->tables[t] = make_table(chunk, first[t], total, (uint64_t)M->tables[t].mask + 1);
-        if (e == hipSuccess) e = H.pool.alloc((void **)&M->d_tables, (size_t)P3 * sizeof(IngestTable));
-        if (e == hipSuccess) e = H.pool.alloc((void **)&M->d_counts, (size_t)P3 * 4);
-        if (e == hipSuccess) e = H.pool.alloc((void **)&M->d_status, (size_t)P3 * 4);
+        if (e == hipSuccess) e = M->mem.alloc(&M->d_tables, (size_t)P3 * sizeof(IngestTable));
+        if (e == hipSuccess) e = M->mem.alloc(&M->d_counts, (size_t)P3 * 4);
+        if (e == hipSuccess) e = M->mem.alloc(&M->d_status, (size_t)P3 * 4);
         if (e == hipSuccess) e = hipMemsetAsync(M->d_counts, 0, (size_t)P3 * 4, H.stream);
         if (e == hipSuccess) e = hipMemsetAsync(M->d_status, 0, (size_t)P3 * 4, H.stream);
         // sources: part 0's partial tables in place, every other part's dense copy
@@ -696,9 +615,8 @@ int32_t merge_parents(bsg_ctx *ctx, Ingest &I)
                 const Dense &x = dense[(size_t)q * P3 + t];
                 if (!x.n) continue;
                 void *cp = nullptr;
-                e = H.pool.alloc(&cp, (uint64_t)x.n * kSlotBytes);
+                e = copies.alloc(&cp, (uint64_t)x.n * kSlotBytes);
                 if (e != hipSuccess) break;
-                copies.push_back(cp);
                 e = peer_copy(ctx, dev_index(ctx, &H), cp, dev_index(ctx, x.dev), x.buf, (uint64_t)x.n * kSlotBytes, H.stream);
                 src[(size_t)q * P3 + t] = IngestTable{(uint64_t *)cp, (uint64_t *)cp + (uint64_t)x.n * 4, x.n - 1, 0};
                 items.push_back({q * P3 + t, t});
@@ -706,10 +624,8 @@ int32_t merge_parents(bsg_ctx *ctx, Ingest &I)
         }
         IngestTable *d_src = nullptr;
         bsg::UnionItem *d_items = nullptr;
-        if (e == hipSuccess) e = H.pool.alloc((void **)&d_src, src.size() * sizeof(IngestTable));
-        if (e == hipSuccess) copies.push_back(d_src);
-        if (e == hipSuccess) e = H.pool.alloc((void **)&d_items, std::max<size_t>(items.size(), 1) * sizeof(bsg::UnionItem));
-        if (e == hipSuccess) copies.push_back(d_items);
+        if (e == hipSuccess) e = copies.alloc(&d_src, src.size() * sizeof(IngestTable));
+        if (e == hipSuccess) e = copies.alloc(&d_items, std::max<size_t>(items.size(), 1) * sizeof(bsg::UnionItem));
         if (e == hipSuccess) e = hipMemcpyAsync(d_src, src.data(), src.size() * sizeof(IngestTable), hipMemcpyHostToDevice, H.stream);
         if (e == hipSuccess && !items.empty()) e = hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::UnionItem), hipMemcpyHostToDevice, H.stream);
         if (e != hipSuccess) { rc = fail(e == hipErrorOutOfMemory ? BSG_E_NOMEM : BSG_E_HIP, "parent merge: %s", hipGetErrorString(e)); }
@@ -728,9 +644,11 @@ int32_t merge_parents(bsg_ctx *ctx, Ingest &I)
             for (uint32_t t = 0; t < P3; ++t)
                 for (uint32_t q = 0; q < np; ++q) M->status[t] = std::max(M->status[t], I.parts[q]->status[I.parts[q]->n_sets * 3 + t]);
             M->finished = true;
-            guard.g = nullptr;
+            copies.done();                 // run_until_fits / read_state return synchronised
+            M->mem.done();
+        } else {
+            free_part(*M);                 // (under H's lock)
         }
-        (void)hipStreamSynchronize(H.stream);
     }
     drop_dense();
     if (rc) return rc;
@@ -777,14 +695,13 @@ int32_t ingest_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_
         I->set_cut = {0, n_sets};
     }
     const uint32_t np = (uint32_t)I->set_cut.size() - 1;
-    I->parts.resize(np);
-    for (auto &p : I->parts) p = std::make_shared<IngestPart>();
     const uint32_t first = np == 1 ? pick_device(ctx) : 0;
+    for (uint32_t i = 0; i < np; ++i) I->parts.push_back(std::make_shared<IngestPart>(*ctx->devs[(first + i) % nd]));
     const int32_t rc = run_parts(np, [&](uint32_t i) -> int32_t {
         IngestPart &G = *I->parts[i];
         const uint32_t s0 = I->set_cut[i], s1 = I->set_cut[i + 1], r0 = set_first_row[s0], r1 = set_first_row[s1];
         G.set0 = s0; G.row0 = r0;
-        Device &d = *ctx->devs[(first + i) % nd];
+        Device &d = *G.dev;
         if (np == 1)
             return ingest_rows_part(ctx, d, G, rows, row_off, n_rows, set_first_row, n_sets, parent_of_set, n_parents, slots_hint, flags, tok);
         // the part's rows and sets, renumbered from zero (offsets relative to the part's first byte)
@@ -1086,31 +1003,26 @@ int32_t build_part(bsg_ctx *ctx, PartBuild &B, const bsg_filter_desc *desc_in, u
     if (!items.empty() || !binned.empty()) {
         HIP_TRY(d.stage_desc.reserve(nt));
         HIP_TRY(hipMemcpyAsync(d.stage_desc.p, dd.data(), dd.size() * sizeof(DevDesc), hipMemcpyHostToDevice, d.stream));
+        Scratch scratch(d);
         bsg::SetBuildItem *d_items = nullptr;
-        HIP_TRY(d.pool.alloc((void **)&d_items, std::max<size_t>(items.size(), 1) * sizeof(bsg::SetBuildItem)));
-        std::vector<void *> scratch{d_items};
-        // (an early return may leave a dispatch in flight that still reads these: drain the stream before they go back to the pool)
-        struct ScratchGuard { Device &d; std::vector<void *> &v; ~ScratchGuard() { (void)hipStreamSynchronize(d.stream); for (void *p : v) d.pool.free(p); } } sguard{d, scratch};
-        IngestEvents ev;
-        hipError_t e;
-        if ((e = ev.init()) != hipSuccess ||
-            (!items.empty() && (e = hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::SetBuildItem), hipMemcpyHostToDevice, d.stream)) != hipSuccess))
-            return fail(BSG_E_HIP, "ingest build: %s", hipGetErrorString(e));
-        // ev.a = start of the first dispatch, ev.b = end of the last one
+        HIP_TRY(scratch.alloc(&d_items, std::max<size_t>(items.size(), 1) * sizeof(bsg::SetBuildItem)));
+        EventList ev;
+        HIP_TRY(ev.add(2));
+        if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::SetBuildItem), hipMemcpyHostToDevice, d.stream));
+        // ev.v[0] = start of the first dispatch, ev.v[1] = end of the last one
         bool started = false;
-        auto start_ev = [&]() { hipEvent_t s = started ? nullptr : ev.a; started = true; return s; };
+        auto start_ev = [&]() { hipEvent_t s = started ? nullptr : ev.v[0]; started = true; return s; };
         if (!items.empty()) {
             // items name the part's own table indices; the descriptor array holds tables [t0, t1) only: its base moves back by t0
             bsg::SetBuildArgs a{G.d_tables, d_items, d.stage_desc.p - B.t0, d.stage_words.p};
             const size_t lds = std::max<uint64_t>(max_staged, 2) * 8;
             hipExtLaunchKernelGGL(bsg::k_build_sets, dim3((uint32_t)items.size()), dim3(bsg::kBuildSetsThreads), (uint32_t)lds, d.stream,
-                                  start_ev(), binned.empty() ? ev.b : nullptr, 0, a);
-            if ((e = hipGetLastError()) != hipSuccess) return fail(BSG_E_HIP, "k_build_sets: %s", hipGetErrorString(e));
+                                  start_ev(), binned.empty() ? ev.v[1] : nullptr, 0, a);
+            HIP_TRY(hipGetLastError());
         }
         uint32_t *d_over = nullptr;
         if (!binned.empty()) {
-            HIP_TRY(d.pool.alloc((void **)&d_over, 64));
-            scratch.push_back(d_over);
+            HIP_TRY(scratch.alloc(&d_over, 64));
             HIP_TRY(hipMemsetAsync(d_over, 0, 64, d.stream));
         }
         for (size_t bi = 0; bi < binned.size(); ++bi) {
@@ -1122,10 +1034,11 @@ int32_t build_part(bsg_ctx *ctx, PartBuild &B, const bsg_filter_desc *desc_in, u
             a.n_locs_cap = (uint32_t)((uint64_t)G.counts[t] * local[i].k);
             a.overflow = d_over;
             a.out = d.stage_words.p;
-            if (int32_t rc = enqueue_binned_build(d, a, false, scratch, start_ev(), bi + 1 == binned.size() ? ev.b : nullptr)) return rc;
+            if (int32_t rc = enqueue_binned_build(d, a, false, scratch, start_ev(), bi + 1 == binned.size() ? ev.v[1] : nullptr)) return rc;
         }
-        if ((e = hipStreamSynchronize(d.stream)) != hipSuccess) return fail(BSG_E_HIP, "ingest build: %s", hipGetErrorString(e));
-        (void)hipEventElapsedTime(&B.ms_build, ev.a, ev.b);
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        scratch.done();
+        (void)hipEventElapsedTime(&B.ms_build, ev.v[0], ev.v[1]);
         if (d_over) {
             uint32_t over = 0;
             HIP_TRY(hipMemcpy(&over, d_over, 4, hipMemcpyDeviceToHost));

@@ -60,153 +60,94 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
 {
     const uint32_t n_rows = r1 - r0;
     const uint64_t byte0 = row_off[r0], n_bytes = row_off[r1] - byte0;
-    static const bool trace = getenv("BSG_LAB_TRACE") != nullptr;   // lab only: phase times of this call on stderr
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (trace) fprintf(stderr, "[bsg_match_rows dev %d] %-28s +%.3f ms\n", d.id, what,
-                           std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-    };
+    const LabTrace trace{"bsg_match_rows", d.id};
     std::vector<uint64_t> local_off((size_t)n_rows + 1);                  // the run's offsets, relative to its first byte
     for (uint32_t r = 0; r <= n_rows; ++r) local_off[r] = row_off[r0 + r] - byte0;
     d.calls.fetch_add(1, std::memory_order_relaxed);
     std::lock_guard<std::mutex> lk(d.mu);
     if (int32_t rc = use_device(d)) return rc;
     if (int32_t rc = ensure_lower_table(d)) return rc;
-    lap("offsets rebased, lock taken");
+    trace.lap("offsets rebased, lock taken");
     const size_t n_words = ((size_t)n_rows + 63) / 64;
+    Scratch scratch(d);                                                   // every early return below leaves through it: drained, then freed
     uint8_t *d_rows = nullptr, *d_cbytes = nullptr;
     uint64_t *d_off = nullptr, *d_ch = nullptr, *d_cfp = nullptr, *d_bits = nullptr;
     uint32_t *d_prog = nullptr, *d_fb = nullptr, *d_nfb = nullptr, *d_coff = nullptr, *d_ckind = nullptr, *d_rx = nullptr;
-    auto cleanup = [&]() {
-        for (void *p : {(void *)d_rows, (void *)d_off, (void *)d_ch, (void *)d_cfp, (void *)d_bits, (void *)d_prog, (void *)d_fb, (void *)d_nfb,
-                        (void *)d_cbytes, (void *)d_coff, (void *)d_ckind, (void *)d_rx})
-            if (p) d.pool.free(p);
-    };
-    hipError_t e = d.pool.alloc((void **)&d_rows, n_bytes + 64);
-    if (e == hipSuccess) e = d.pool.alloc((void **)&d_off, ((size_t)n_rows + 1) * 8);
-    if (e == hipSuccess) e = d.pool.alloc((void **)&d_ch, std::max<size_t>(n_conds, 1) * 2 * 32);
-    if (e == hipSuccess) e = d.pool.alloc((void **)&d_cfp, std::max<size_t>(n_conds, 1) * 2 * 8);
-    if (e == hipSuccess) e = d.pool.alloc((void **)&d_cbytes, (size_t)cond_len + 64);
-    if (e == hipSuccess) e = d.pool.alloc((void **)&d_coff, ((size_t)2 * n_conds + 1) * 4);
-    if (e == hipSuccess) e = d.pool.alloc((void **)&d_ckind, std::max<size_t>(n_conds, 1) * 4);
-    if (e == hipSuccess) e = d.pool.alloc((void **)&d_prog, std::max<size_t>(prog.size(), 1) * 4);
-    if (e == hipSuccess) e = d.pool.alloc((void **)&d_bits, n_words * 8);
-    if (e == hipSuccess) e = d.pool.alloc((void **)&d_fb, (size_t)n_rows * 4);
-    if (e == hipSuccess) e = d.pool.alloc((void **)&d_nfb, 4);
-    if (e == hipSuccess && n_rx) e = d.pool.alloc((void **)&d_rx, rx_blob.size() * 4);
-    lap("device buffers allocated");
-    if (e == hipSuccess) e = hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, local_off.data(), ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream);
-    if (e == hipSuccess && n_conds) {
+    HIP_TRY(scratch.alloc(&d_rows, n_bytes + 64));
+    HIP_TRY(scratch.alloc(&d_off, ((size_t)n_rows + 1) * 8));
+    HIP_TRY(scratch.alloc(&d_ch, std::max<size_t>(n_conds, 1) * 2 * 32));
+    HIP_TRY(scratch.alloc(&d_cfp, std::max<size_t>(n_conds, 1) * 2 * 8));
+    HIP_TRY(scratch.alloc(&d_cbytes, (size_t)cond_len + 64));
+    HIP_TRY(scratch.alloc(&d_coff, ((size_t)2 * n_conds + 1) * 4));
+    HIP_TRY(scratch.alloc(&d_ckind, std::max<size_t>(n_conds, 1) * 4));
+    HIP_TRY(scratch.alloc(&d_prog, std::max<size_t>(prog.size(), 1) * 4));
+    HIP_TRY(scratch.alloc(&d_bits, n_words * 8));
+    HIP_TRY(scratch.alloc(&d_fb, (size_t)n_rows * 4));
+    HIP_TRY(scratch.alloc(&d_nfb, 4));
+    if (n_rx) HIP_TRY(scratch.alloc(&d_rx, rx_blob.size() * 4));
+    trace.lap("device buffers allocated");
+    HIP_TRY(hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream));
+    HIP_TRY(hipMemcpyAsync(d_off, local_off.data(), ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream));
+    if (n_conds) {
         // the condition strings are hashed AND fingerprinted (under the context's secret key) on the device
-        if (cond_len) e = hipMemcpyAsync(d_cbytes, cond_bytes, cond_len, hipMemcpyHostToDevice, d.stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_cbytes + cond_len, 0, 64, d.stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_coff, cond_off, ((size_t)2 * n_conds + 1) * 4, hipMemcpyHostToDevice, d.stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_ckind, cond_kinds, (size_t)n_conds * 4, hipMemcpyHostToDevice, d.stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(bsg::k_hash_fp_entries, dim3((2 * n_conds + 255) / 256), dim3(256), 0, d.stream, (const uint8_t *)d_cbytes,
-                               (const uint32_t *)d_coff, 2 * n_conds, d_ch, d_cfp, ctx->fp_key);
-            e = hipGetLastError();
-        }
+        if (cond_len) HIP_TRY(hipMemcpyAsync(d_cbytes, cond_bytes, cond_len, hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemsetAsync(d_cbytes + cond_len, 0, 64, d.stream));
+        HIP_TRY(hipMemcpyAsync(d_coff, cond_off, ((size_t)2 * n_conds + 1) * 4, hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemcpyAsync(d_ckind, cond_kinds, (size_t)n_conds * 4, hipMemcpyHostToDevice, d.stream));
+        hipLaunchKernelGGL(bsg::k_hash_fp_entries, dim3((2 * n_conds + 255) / 256), dim3(256), 0, d.stream, (const uint8_t *)d_cbytes,
+                           (const uint32_t *)d_coff, 2 * n_conds, d_ch, d_cfp, ctx->fp_key);
+        HIP_TRY(hipGetLastError());
     }
-    if (e == hipSuccess && !prog.empty()) e = hipMemcpyAsync(d_prog, prog.data(), prog.size() * 4, hipMemcpyHostToDevice, d.stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_nfb, 0, 4, d.stream);
-    if (e == hipSuccess && n_rx) e = hipMemcpyAsync(d_rx, rx_blob.data(), rx_blob.size() * 4, hipMemcpyHostToDevice, d.stream);
-    // The rows travel in chunks on the copy stream while the chunk before is being matched (a surviving block is <= 10 MiB and
-    // goes in one piece; a scan of many blocks in one call is 64, 128, then 256 MiB pieces as in bsg_ingest_rows: the walk of
-    // 2.5 GB takes 12 ms, their copy 50 ms — one after the other they would add up).  Chunks are whole 256-row workgroups.
-    std::vector<uint32_t> cuts{0};
-    {
-        uint64_t chunk_bytes = ctx->ingest_chunk_bytes;
-        for (uint32_t r = 0; r < n_rows;) {
-            const uint64_t lim = local_off[r] + chunk_bytes;
-            if (chunk_bytes < 4 * ctx->ingest_chunk_bytes) chunk_bytes *= 2;
-            uint32_t c1 = (uint32_t)(std::upper_bound(local_off.begin() + r + 1, local_off.end(), lim) - local_off.begin()) - 1;
-            c1 = std::max(c1, r + 1);
-            if (c1 < n_rows) c1 = std::min<uint32_t>(n_rows, (c1 + 255u) / 256u * 256u);
-            cuts.push_back(c1);
-            r = c1;
-        }
-    }
-    const uint32_t n_chunks = (uint32_t)cuts.size() - 1;
-    std::vector<hipEvent_t> evs((size_t)n_chunks * 3, nullptr);          // per chunk: bytes landed, kernel start, kernel stop
-    struct EvGuard { std::vector<hipEvent_t> &v; ~EvGuard() { for (auto x : v) if (x) (void)hipEventDestroy(x); } } evguard{evs};
-    if (e == hipSuccess && n_chunks > 1 && !d.copy_stream) {
-        e = hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking);
-        for (int s2 = 0; s2 < 2 && e == hipSuccess; ++s2) {
-            e = hipEventCreateWithFlags(&d.ev_eval[s2], hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&d.ev_copy[s2], hipEventDisableTiming);
-        }
-    }
-    hipStream_t cs = n_chunks > 1 ? d.copy_stream : d.stream;            // one chunk: everything in order on the one stream
-    uint64_t copied_to = 0;                // chunks are copied in order: chunk c starts where chunk c - 1 ended
-    auto copy_chunk = [&](uint32_t c) -> hipError_t {
-        // The walker reads whole aligned 8-byte words, at most the word that holds a row's last byte: a chunk's range ends 16..23
-        // bytes past its last row so that K(c) never touches a byte that has not landed — and the next chunk starts exactly there,
-        // so no copy rewrites a byte a running kernel may be reading (disjoint ranges).
-        const uint64_t b0 = c == 0 ? (local_off[cuts[c]] & ~7ull) : copied_to, b1 = std::max(b0, std::min<uint64_t>(n_bytes, (local_off[cuts[c + 1]] + 23) & ~7ull));
-        copied_to = b1;
-        hipError_t x = hipEventCreateWithFlags(&evs[(size_t)c * 3], hipEventDisableTiming);
-        if (x == hipSuccess && b1 > b0) x = hipMemcpyAsync(d_rows + b0, rows + byte0 + b0, b1 - b0, hipMemcpyHostToDevice, cs);
-        if (x == hipSuccess) x = hipEventRecord(evs[(size_t)c * 3], cs);
-        return x;
-    };
-    if (e == hipSuccess && n_chunks > 1) {                               // the zeroed tail and the offsets precede the first row bytes
-        e = hipEventRecord(d.ev_eval[0], d.stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(cs, d.ev_eval[0], 0);
-    }
-    lap("small uploads enqueued");
-    if (e == hipSuccess && n_chunks) e = copy_chunk(0);
-    uint32_t nfb = 0;
-    for (uint32_t c = 0; c < n_chunks && e == hipSuccess; ++c) {
+    if (!prog.empty()) HIP_TRY(hipMemcpyAsync(d_prog, prog.data(), prog.size() * 4, hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipMemsetAsync(d_nfb, 0, 4, d.stream));
+    if (n_rx) HIP_TRY(hipMemcpyAsync(d_rx, rx_blob.data(), rx_blob.size() * 4, hipMemcpyHostToDevice, d.stream));
+    // The rows travel in chunks while the chunk before is being matched (RowUpload).  A surviving block is <= 10 MiB and goes in
+    // one piece, in order on the one stream; a scan of many blocks in one call goes in pieces on the copy stream.
+    RowUpload up(d, rows + byte0, d_rows, local_off.data(), n_rows, ctx->ingest_chunk_bytes);
+    const uint32_t n_chunks = up.n_chunks();
+    HIP_TRY(up.start(n_chunks > 1));
+    trace.lap("small uploads enqueued");
+    HIP_TRY(up.copy(0));
+    EventList kev;                                                       // per chunk: kernel start, kernel stop
+    for (uint32_t c = 0; c < n_chunks; ++c) {
+        const uint32_t rf = up.cuts[c], re = up.cuts[c + 1];
         bsg::MatchArgs a{};
-        a.rows = d_rows; a.row_off = d_off + cuts[c]; a.cond_h = d_ch; a.cond_fp = d_cfp; a.cond_kind = d_ckind; a.prog = d_prog; a.lower = d.d_lower;
+        a.rows = d_rows; a.row_off = d_off + rf; a.cond_h = d_ch; a.cond_fp = d_cfp; a.cond_kind = d_ckind; a.prog = d_prog; a.lower = d.d_lower;
         a.key = ctx->fp_key;
-        a.out_bits = d_bits + cuts[c] / 64; a.fallback_rows = d_fb; a.n_fallback = d_nfb;
-        a.n_rows = cuts[c + 1] - cuts[c]; a.row_base = cuts[c]; a.n_conds = n_conds; a.n_ops = (uint32_t)prog.size();
-        e = hipEventCreate(&evs[(size_t)c * 3 + 1]);
-        if (e == hipSuccess) e = hipEventCreate(&evs[(size_t)c * 3 + 2]);
-        if (e == hipSuccess && n_chunks > 1) e = hipStreamWaitEvent(d.stream, evs[(size_t)c * 3], 0);
-        if (e != hipSuccess) break;
+        a.out_bits = d_bits + rf / 64; a.fallback_rows = d_fb; a.n_fallback = d_nfb;
+        a.n_rows = re - rf; a.row_base = rf; a.n_conds = n_conds; a.n_ops = (uint32_t)prog.size();
+        HIP_TRY(kev.add(2));
+        HIP_TRY(up.wait_landed(c));
+        const hipEvent_t k0 = kev.v[(size_t)c * 2], k1 = kev.v[(size_t)c * 2 + 1];
         const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads);
         if (n_rx && tok) {
             const bsg::RxArgs x{d_rx, (uint32_t)rx_blob.size(), n_rx};
             hipExtLaunchKernelGGL(bsg::k_match_rows_regex_tok, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes + (uint32_t)rx_blob.size() * 4,
-                                  d.stream, evs[(size_t)c * 3 + 1], evs[(size_t)c * 3 + 2], 0, a, x, *tok);
+                                  d.stream, k0, k1, 0, a, x, *tok);
         } else if (n_rx) {
             const bsg::RxArgs x{d_rx, (uint32_t)rx_blob.size(), n_rx};
             hipExtLaunchKernelGGL(bsg::k_match_rows_regex, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes + (uint32_t)rx_blob.size() * 4,
-                                  d.stream, evs[(size_t)c * 3 + 1], evs[(size_t)c * 3 + 2], 0, a, x);
+                                  d.stream, k0, k1, 0, a, x);
         } else if (tok) {
-            hipExtLaunchKernelGGL(bsg::k_match_rows_tok, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes, d.stream, evs[(size_t)c * 3 + 1],
-                                  evs[(size_t)c * 3 + 2], 0, a, *tok);
+            hipExtLaunchKernelGGL(bsg::k_match_rows_tok, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes, d.stream, k0, k1, 0, a, *tok);
         } else {
-            hipExtLaunchKernelGGL(bsg::k_match_rows, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes, d.stream, evs[(size_t)c * 3 + 1],
-                                  evs[(size_t)c * 3 + 2], 0, a);
+            hipExtLaunchKernelGGL(bsg::k_match_rows, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes, d.stream, k0, k1, 0, a);
         }
-        e = hipGetLastError();
-        // K(c) is running: now the next chunk's bytes (from pageable memory this call only returns once they are staged)
-        if (e == hipSuccess && c + 1 < n_chunks) e = copy_chunk(c + 1);
+        HIP_TRY(hipGetLastError());
+        if (c + 1 < n_chunks) HIP_TRY(up.copy(c + 1));                   // K(c) is running: now the next chunk's bytes
     }
-    lap("all chunks enqueued");
-    if (e == hipSuccess) e = hipMemcpyAsync(out_bits + r0 / 64, d_bits, n_words * 8, hipMemcpyDeviceToHost, d.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&nfb, d_nfb, 4, hipMemcpyDeviceToHost, d.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
-    lap("matched, bits back");
-    if (e == hipSuccess) {
-        *ms = 0.f;
-        for (uint32_t c = 0; c < n_chunks; ++c) { float t = 0.f; (void)hipEventElapsedTime(&t, evs[(size_t)c * 3 + 1], evs[(size_t)c * 3 + 2]); *ms += t; }
-        fb.resize(nfb);
-        if (nfb) {
-            e = hipMemcpy(fb.data(), d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost);
-            for (uint32_t &r : fb) r += r0;
-        }
-    } else {
-        (void)hipStreamSynchronize(d.stream);                            // nothing in flight may still read what goes back to the pool
-        if (n_chunks > 1 && d.copy_stream) (void)hipStreamSynchronize(d.copy_stream);
-    }
-    cleanup();
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? BSG_E_NOMEM : BSG_E_HIP, "bsg_match_rows: %s", hipGetErrorString(e));
+    trace.lap("all chunks enqueued");
+    uint32_t nfb = 0;
+    HIP_TRY(hipMemcpyAsync(out_bits + r0 / 64, d_bits, n_words * 8, hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipMemcpyAsync(&nfb, d_nfb, 4, hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    trace.lap("matched, bits back");
+    *ms = 0.f;
+    for (uint32_t c = 0; c < n_chunks; ++c) { float t = 0.f; (void)hipEventElapsedTime(&t, kev.v[(size_t)c * 2], kev.v[(size_t)c * 2 + 1]); *ms += t; }
+    fb.resize(nfb);
+    if (nfb) HIP_TRY(hipMemcpy(fb.data(), d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
+    for (uint32_t &r : fb) r += r0;
+    scratch.done();                        // every kernel has finished, and each waited for its chunk's copy
     return BSG_OK;
 }
 

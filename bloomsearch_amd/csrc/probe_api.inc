@@ -844,13 +844,7 @@ int32_t probe_arenas(bsg_ctx *ctx, const std::vector<std::shared_ptr<Arena>> &ar
         // latency path (a single interactive query): one group, a small synchronous result — the copy rides the compute
         // stream, no cross-stream events
         const bool inline_copy = want_copy && groups.size() == 1 && !(flags & BSG_PROBE_ASYNC) && groups[0].out_words * 8 <= (1u << 20);
-        if (want_copy && !inline_copy && !d.copy_stream) {
-            HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking));
-            for (int s2 = 0; s2 < 2; ++s2) {
-                HIP_TRY(hipEventCreateWithFlags(&d.ev_eval[s2], hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&d.ev_copy[s2], hipEventDisableTiming));
-            }
-        }
+        if (want_copy && !inline_copy) HIP_TRY(ensure_copy_stream(d));
         // one interactive query (a small synchronous batch with a few terms against one group): one dispatch, and the
         // survivors are written straight into page-locked host memory — one launch and one wait instead of three enqueues
         uint32_t real_terms = 0;

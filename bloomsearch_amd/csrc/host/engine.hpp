@@ -20,6 +20,7 @@
 #include <memory>
 #include <string>
 #include <string_view>
+#include <tuple>
 #include <vector>
 
 #include "bloomgpu.h"
@@ -274,52 +275,9 @@ public:
         BloomExpression guard, prune_storage;
         const bool has_guard = regex_field_guard(regex, guard);
         const BloomExpression *expr = and_bloom_queries(row_expr, has_guard ? &guard : nullptr, prune_storage) ? &prune_storage : nullptr;
-        std::vector<uint8_t> file_ok(files_.size(), 1);
-        std::vector<std::vector<uint8_t>> block_ok(files_.size());
-        for (size_t f = 0; f < files_.size(); ++f) block_ok[f].assign(files_[f].blocks.size(), 1);
-        if (expr && !files_.empty()) {
-            QueryBatch qb;
-            qb.add_query(expr);
-            std::vector<bsg_term> terms;
-            if (int32_t rc = hash_terms(qb, terms)) return rc;
-            uint64_t batch = 0;
-            if (bsg_batch_create(ctx_, terms.data(), (uint32_t)terms.size(), qb.prog_ops.data(), qb.prog_off.data(), 1, &batch))
-                return fail(kErrGpu, bsg_last_error(ctx_));
-            struct FreeBatch { bsg_ctx *c; uint64_t id; ~FreeBatch() { bsg_batch_free(c, id); } } guard{ctx_, batch};
-            // file stage (query_exec.go:399-406): one probe over the file-level filters, one "block" per file
-            if (int32_t rc = ensure_files_arena()) return rc;
-            std::vector<uint64_t> fs((files_.size() + 63) / 64);
-            if (bsg_probe_batch(ctx_, files_arena_, batch, 0, fs.data())) return fail(kErrGpu, bsg_last_error(ctx_));
-            // block stage: only the files that passed, each through its arena — resident in the library's cache, or decoded now
-            // and published there — all in one pipelined call; the leases end when the survivors are on the host
-            std::vector<uint64_t> ids;
-            std::vector<size_t> which;
-            std::vector<FileLease> leases;
-            struct ReleaseAll { bsg_ctx *c; std::vector<FileLease> &v; ~ReleaseAll() { for (auto &l : v) bsg_file_arena_release(c, l.lease); } } release{ctx_, leases};
-            size_t words = 0;
-            for (size_t f = 0; f < files_.size(); ++f) {
-                file_ok[f] = (fs[f >> 6] >> (f & 63)) & 1;   // a corrupt file-level section decodes to nil filters: cannot disqualify
-                if (!file_ok[f] || files_[f].blocks.empty()) continue;
-                leases.emplace_back();
-                if (int32_t rc = lease_file_arena(files_[f], leases.back())) { leases.pop_back(); return rc; }
-                ids.push_back(leases.back().arena);
-                which.push_back(f);
-                words += (files_[f].blocks.size() + 63) / 64;
-            }
-            std::vector<uint64_t> bs(std::max<size_t>(words, 1));
-            if (!ids.empty() && bsg_probe_many(ctx_, ids.data(), (uint32_t)ids.size(), batch, 0, bs.data()))
-                return fail(kErrGpu, bsg_last_error(ctx_));
-            size_t o = 0;
-            for (size_t i = 0; i < which.size(); ++i) {
-                const size_t f = which[i];
-                for (size_t b = 0; b < files_[f].blocks.size(); ++b) {
-                    const uint32_t r = leases[i].rows[b];                      // block b's row in the arena
-                    block_ok[f][b] = (bs[o + (r >> 6)] >> (r & 63)) & 1;
-                    if (leases[i].status[b] != 0) block_ok[f][b] = 2;   // unreadable filters: neither pruned nor scanned (query_exec.go:580-590)
-                }
-                o += (files_[f].blocks.size() + 63) / 64;
-            }
-        }
+        std::vector<Survivors> sv;
+        if (int32_t rc = probe_stage({expr}, sv)) return rc;
+        const std::vector<uint8_t> &file_ok = sv[0].file_ok;
         const int64_t probe_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_begin).count();
         size_t candidate_blocks = 0;
         for (size_t f = 0; f < files_.size(); ++f) if (file_ok[f]) candidate_blocks += files_[f].blocks.size();
@@ -331,38 +289,11 @@ public:
         if (!regex_on_device && !regex_matcher.valid()) return fail(kErrInvalidQuery, "regex pattern does not compile");
         // the scan list: every row of every block that survived both stages, in file / block order
         std::vector<const std::string *> scan;
-        std::vector<size_t> scanned_stats;          // block_stats entries of the scanned blocks (for the scan's time share)
+        std::vector<ScanBlock> scanned;             // the scanned blocks and their block_stats entries (for the scan's time share)
         const auto t_scan = std::chrono::steady_clock::now();
-        for (size_t f = 0; f < files_.size(); ++f) {
-            out.files_considered++;
-            if (!file_ok[f]) { out.files_bloom_skipped++; continue; }   // file stage prune: no BlockStats for its blocks
-            for (size_t b = 0; b < files_[f].blocks.size(); ++b) {
-                const DataBlock &blk = files_[f].blocks[b];
-                BlockStats st;
-                st.file_id = files_[f].file_id; st.block_offset = blk.block_offset;
-                st.total_rows = (int64_t)blk.rows.size();
-                st.total_bytes = (int64_t)(blk.row_bytes + blk.filter_section.size());
-                st.duration_ns = probe_share;
-                if (block_ok[f][b] == 2) {        // recordUnreadBlocks (query_exec.go:625-639): totals only, error surfaced
-                    out.errors.push_back("failed to read data block bloom filters: file " + std::to_string(files_[f].file_id) +
-                                         " block offset " + std::to_string(blk.block_offset) + ": invalid hash");
-                    out.block_stats.push_back(st);
-                    continue;
-                }
-                if (!block_ok[f][b]) {                                    // query_exec.go:607-614
-                    st.bloom_filter_skipped = true;
-                    out.block_stats.push_back(st);
-                    continue;
-                }
-                for (const std::string &row : blk.rows) {
-                    st.rows_processed++;
-                    st.bytes_processed += (int64_t)row.size() + 4;
-                    scan.push_back(&row);
-                }
-                scanned_stats.push_back(out.block_stats.size());
-                out.block_stats.push_back(st);
-            }
-        }
+        block_stage_stats(sv[0], probe_share, out, scanned);
+        for (const ScanBlock &sb : scanned)
+            for (const std::string &row : files_[sb.f].blocks[sb.b].rows) scan.push_back(&row);
         std::vector<uint8_t> hit(scan.size(), 0);
         bool on_device = false, regex_done = false;
         if (regex_on_device && !scan.empty()) {
@@ -391,9 +322,76 @@ public:
         }
         for (size_t i = 0; i < scan.size(); ++i)
             if (hit[i]) out.rows.push_back(*scan[i]);
-        if (!scanned_stats.empty()) {
-            const int64_t scan_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_scan).count();
-            for (size_t i : scanned_stats) out.block_stats[i].duration_ns += std::max<int64_t>(1, scan_ns / (int64_t)scanned_stats.size());
+        add_scan_time(t_scan, scanned, out);
+        return kEngineOk;
+    }
+
+    // A batch of queries in one pass: element i of `results` is what query(exprs[i], ..., regexes[i]) returns (duration_ns aside).
+    // One QueryBatch holds every bloom-only query: one file-stage probe, one bsg_probe_many over the leased arenas; the scan list
+    // is the rows of every block at least one query survived on, one set per block with its query mask, and - under DeviceMatch -
+    // one bsg_match_rows_many call per group of <= 64 queries / <= 64 distinct conditions decides them (the rows it hands back: the
+    // host matcher, per query whose mask bit is set).  Without DeviceMatch the host matcher runs per (query, surviving block).
+    // A query with a regex tree is answered by query() and placed at its position.
+    int32_t query_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
+                       std::vector<QueryResult> &results)
+    {
+        results.assign(exprs.size(), QueryResult{});
+        std::vector<size_t> live;                   // the batch: queries without a regex tree
+        for (size_t i = 0; i < exprs.size(); ++i) {
+            if (i < regexes.size() && regexes[i]) { if (int32_t rc = query(exprs[i], results[i], regexes[i])) return rc; }
+            else live.push_back(i);
+        }
+        if (live.empty()) return kEngineOk;
+        const auto t_begin = std::chrono::steady_clock::now();
+        std::vector<const BloomExpression *> batch;
+        for (size_t i : live) batch.push_back(exprs[i]);
+        std::vector<Survivors> sv;
+        if (int32_t rc = probe_stage(batch, sv)) return rc;
+        const int64_t probe_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_begin).count();
+        const auto t_scan = std::chrono::steady_clock::now();
+        const size_t Q = live.size();
+        std::vector<std::vector<ScanBlock>> scanned(Q);
+        // per block (in file / block order): which queries scan it
+        std::vector<std::vector<std::vector<uint8_t>>> wants(files_.size());
+        for (size_t f = 0; f < files_.size(); ++f) wants[f].assign(files_[f].blocks.size(), std::vector<uint8_t>());
+        for (size_t k = 0; k < Q; ++k) {
+            size_t candidate_blocks = 0;
+            for (size_t f = 0; f < files_.size(); ++f) if (sv[k].file_ok[f]) candidate_blocks += files_[f].blocks.size();
+            const int64_t probe_share = candidate_blocks ? std::max<int64_t>(1, probe_ns / (int64_t)candidate_blocks) : 0;
+            block_stage_stats(sv[k], probe_share, results[live[k]], scanned[k]);
+            for (const ScanBlock &sb : scanned[k]) {
+                if (wants[sb.f][sb.b].empty()) wants[sb.f][sb.b].assign(Q, 0);
+                wants[sb.f][sb.b][k] = 1;
+            }
+        }
+        std::vector<const std::string *> scan;
+        std::vector<uint32_t> set_first{0};
+        std::vector<const std::vector<uint8_t> *> set_wants;
+        for (size_t f = 0; f < files_.size(); ++f)
+            for (size_t b = 0; b < files_[f].blocks.size(); ++b) {
+                if (wants[f][b].empty()) continue;
+                for (const std::string &row : files_[f].blocks[b].rows) scan.push_back(&row);
+                set_first.push_back((uint32_t)scan.size());
+                set_wants.push_back(&wants[f][b]);
+            }
+        // hit[k][row]: only read where query k scans the row's set
+        std::vector<std::vector<uint8_t>> hit(Q, std::vector<uint8_t>(scan.size(), 0));
+        std::vector<RowMatcher> matchers;
+        matchers.reserve(Q);
+        for (size_t k = 0; k < Q; ++k) matchers.emplace_back(batch[k], cfg_.tokenizer);
+        std::vector<uint8_t> on_device(Q, 0);
+        if (cfg_.device_match && !scan.empty())
+            if (int32_t rc = match_rows_device_many(batch, scan, set_first, set_wants, matchers, hit, on_device)) return rc;
+        for (size_t k = 0; k < Q; ++k) {
+            QueryResult &out = results[live[k]];
+            for (size_t s = 0; s + 1 < set_first.size(); ++s) {
+                if (!(*set_wants[s])[k]) continue;
+                for (uint32_t i = set_first[s]; i < set_first[s + 1]; ++i) {
+                    if (!on_device[k]) hit[k][i] = matchers[k].match(*scan[i]);
+                    if (hit[k][i]) out.rows.push_back(*scan[i]);
+                }
+            }
+            add_scan_time(t_scan, scanned[k], out);
         }
         return kEngineOk;
     }
@@ -427,6 +425,119 @@ private:
     std::vector<int32_t> file_status_;   // parseFilterSection outcome per file (0 ok)
 
     int32_t fail(int32_t code, std::string msg) { err_ = std::move(msg); return code; }
+
+    // what the two probe stages leave of the files and blocks for one query: block_ok 0 pruned, 1 scanned, 2 unreadable filters
+    struct Survivors {
+        std::vector<uint8_t> file_ok;
+        std::vector<std::vector<uint8_t>> block_ok;
+    };
+    struct ScanBlock { size_t f, b, stat; };        // a scanned block and its entry in block_stats
+
+    // File stage and block stage for a batch of pruning expressions in ONE QueryBatch (a nil expression probes nothing: every
+    // file and block stays).
+    int32_t probe_stage(const std::vector<const BloomExpression *> &exprs, std::vector<Survivors> &sv)
+    {
+        sv.assign(exprs.size(), Survivors{});
+        for (Survivors &s : sv) {
+            s.file_ok.assign(files_.size(), 1);
+            s.block_ok.resize(files_.size());
+            for (size_t f = 0; f < files_.size(); ++f) s.block_ok[f].assign(files_[f].blocks.size(), 1);
+        }
+        QueryBatch qb;
+        std::vector<size_t> probed;                 // batch query k = exprs[probed[k]]
+        for (size_t i = 0; i < exprs.size(); ++i)
+            if (exprs[i]) { qb.add_query(exprs[i]); probed.push_back(i); }
+        if (probed.empty() || files_.empty()) return kEngineOk;
+        const size_t Q = probed.size();
+        std::vector<bsg_term> terms;
+        if (int32_t rc = hash_terms(qb, terms)) return rc;
+        uint64_t batch = 0;
+        if (bsg_batch_create(ctx_, terms.data(), (uint32_t)terms.size(), qb.prog_ops.data(), qb.prog_off.data(), (uint32_t)Q, &batch))
+            return fail(kErrGpu, bsg_last_error(ctx_));
+        struct FreeBatch { bsg_ctx *c; uint64_t id; ~FreeBatch() { bsg_batch_free(c, id); } } guard{ctx_, batch};
+        // file stage (query_exec.go:399-406): one probe over the file-level filters, one "block" per file
+        if (int32_t rc = ensure_files_arena()) return rc;
+        const size_t fw = (files_.size() + 63) / 64;
+        std::vector<uint64_t> fs(Q * fw);
+        if (bsg_probe_batch(ctx_, files_arena_, batch, 0, fs.data())) return fail(kErrGpu, bsg_last_error(ctx_));
+        // block stage: only the files that passed (for any query), each through its arena - resident in the library's cache, or
+        // decoded now and published there - all in one pipelined call; the leases end when the survivors are on the host
+        std::vector<uint64_t> ids;
+        std::vector<size_t> which;
+        std::vector<FileLease> leases;
+        struct ReleaseAll { bsg_ctx *c; std::vector<FileLease> &v; ~ReleaseAll() { for (auto &l : v) bsg_file_arena_release(c, l.lease); } } release{ctx_, leases};
+        size_t words = 0;
+        for (size_t f = 0; f < files_.size(); ++f) {
+            bool any = false;
+            for (size_t k = 0; k < Q; ++k) {
+                // a corrupt file-level section decodes to nil filters: cannot disqualify
+                any |= (sv[probed[k]].file_ok[f] = (fs[k * fw + (f >> 6)] >> (f & 63)) & 1) != 0;
+            }
+            if (!any || files_[f].blocks.empty()) continue;
+            leases.emplace_back();
+            if (int32_t rc = lease_file_arena(files_[f], leases.back())) { leases.pop_back(); return rc; }
+            ids.push_back(leases.back().arena);
+            which.push_back(f);
+            words += Q * ((files_[f].blocks.size() + 63) / 64);
+        }
+        std::vector<uint64_t> bs(std::max<size_t>(words, 1));
+        if (!ids.empty() && bsg_probe_many(ctx_, ids.data(), (uint32_t)ids.size(), batch, 0, bs.data()))
+            return fail(kErrGpu, bsg_last_error(ctx_));
+        size_t o = 0;
+        for (size_t i = 0; i < which.size(); ++i) {
+            const size_t f = which[i], bw = (files_[f].blocks.size() + 63) / 64;
+            for (size_t k = 0; k < Q; ++k)
+                for (size_t b = 0; b < files_[f].blocks.size(); ++b) {
+                    const uint32_t r = leases[i].rows[b];                      // block b's row in the arena
+                    uint8_t &ok = sv[probed[k]].block_ok[f][b];
+                    ok = (bs[o + k * bw + (r >> 6)] >> (r & 63)) & 1;
+                    if (leases[i].status[b] != 0) ok = 2;   // unreadable filters: neither pruned nor scanned (query_exec.go:580-590)
+                }
+            o += Q * bw;
+        }
+        return kEngineOk;
+    }
+
+    // One query's FilesConsidered / FilesBloomSkipped / BlockStats / Errors from what the probe stages left, and its scanned blocks.
+    void block_stage_stats(const Survivors &sv, int64_t probe_share, QueryResult &out, std::vector<ScanBlock> &scanned)
+    {
+        for (size_t f = 0; f < files_.size(); ++f) {
+            out.files_considered++;
+            if (!sv.file_ok[f]) { out.files_bloom_skipped++; continue; }   // file stage prune: no BlockStats for its blocks
+            for (size_t b = 0; b < files_[f].blocks.size(); ++b) {
+                const DataBlock &blk = files_[f].blocks[b];
+                BlockStats st;
+                st.file_id = files_[f].file_id; st.block_offset = blk.block_offset;
+                st.total_rows = (int64_t)blk.rows.size();
+                st.total_bytes = (int64_t)(blk.row_bytes + blk.filter_section.size());
+                st.duration_ns = probe_share;
+                if (sv.block_ok[f][b] == 2) {        // recordUnreadBlocks (query_exec.go:625-639): totals only, error surfaced
+                    out.errors.push_back("failed to read data block bloom filters: file " + std::to_string(files_[f].file_id) +
+                                         " block offset " + std::to_string(blk.block_offset) + ": invalid hash");
+                    out.block_stats.push_back(st);
+                    continue;
+                }
+                if (!sv.block_ok[f][b]) {                                    // query_exec.go:607-614
+                    st.bloom_filter_skipped = true;
+                    out.block_stats.push_back(st);
+                    continue;
+                }
+                for (const std::string &row : blk.rows) {
+                    st.rows_processed++;
+                    st.bytes_processed += (int64_t)row.size() + 4;
+                }
+                scanned.push_back(ScanBlock{f, b, out.block_stats.size()});
+                out.block_stats.push_back(st);
+            }
+        }
+    }
+
+    void add_scan_time(std::chrono::steady_clock::time_point t_scan, const std::vector<ScanBlock> &scanned, QueryResult &out)
+    {
+        if (scanned.empty()) return;
+        const int64_t scan_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_scan).count();
+        for (const ScanBlock &sb : scanned) out.block_stats[sb.stat].duration_ns += std::max<int64_t>(1, scan_ns / (int64_t)scanned.size());
+    }
 
     void drop_files_arena()
     {
@@ -698,6 +809,76 @@ private:
             hit[fb[i]] = host_matcher.match(row) && host_regex.match(row);
         }
         on_device = true;
+        return kEngineOk;
+    }
+
+    // The scan list under DeviceMatch for a batch: queries are packed, in order, into groups of <= 64 queries over <= 64 distinct
+    // conditions (deduplicated across the group's queries by (kind, field, token)); one bsg_match_rows_many call per group with
+    // the sets' masks restricted to the group.  on_device[k] stays 0 (the host matcher decides query k) for a query with more
+    // than 64 conditions of its own or a group the library answers BSG_E_UNSUPPORTED for.
+    int32_t match_rows_device_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const std::string *> &scan,
+                                   const std::vector<uint32_t> &set_first, const std::vector<const std::vector<uint8_t> *> &set_wants,
+                                   std::vector<RowMatcher> &host_matchers, std::vector<std::vector<uint8_t>> &hit, std::vector<uint8_t> &on_device)
+    {
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> row_off{0};
+        for (const std::string *r : scan) { bytes.insert(bytes.end(), r->begin(), r->end()); row_off.push_back(bytes.size()); }
+        const bsg_tokenizer tok = c_tokenizer();
+        const size_t n_words = (scan.size() + 63) / 64, n_sets = set_wants.size();
+        size_t k = 0;
+        while (k < exprs.size()) {
+            // the group's table and programs
+            std::map<std::tuple<uint32_t, std::string, std::string>, uint32_t> index;
+            std::vector<uint32_t> kinds, prog_ops, prog_off{0};
+            std::vector<std::string> fields, tokens;
+            std::vector<size_t> members;
+            for (; k < exprs.size() && members.size() < 64; ++k) {
+                MatcherProgram mp(exprs[k]);
+                size_t fresh = 0;
+                for (size_t c = 0; c < mp.kinds.size(); ++c) fresh += index.count(std::make_tuple(mp.kinds[c], mp.fields[c], mp.tokens[c])) == 0;
+                if (mp.kinds.size() > 64) { if (members.empty()) { ++k; } break; }     // alone beyond the table: the host matcher's
+                if (index.size() + fresh > 64) break;                                    // (an upper bound: opens the next group)
+                for (uint32_t op : mp.prog_ops) {
+                    if ((op >> 28) == BSG_OP_TERM) {
+                        const uint32_t c = op & 0x0FFFFFFFu;
+                        auto it = index.emplace(std::make_tuple(mp.kinds[c], mp.fields[c], mp.tokens[c]), (uint32_t)kinds.size());
+                        if (it.second) { kinds.push_back(mp.kinds[c]); fields.push_back(mp.fields[c]); tokens.push_back(mp.tokens[c]); }
+                        op = BSG_OP(BSG_OP_TERM, it.first->second);
+                    }
+                    prog_ops.push_back(op);
+                }
+                prog_off.push_back((uint32_t)prog_ops.size());
+                members.push_back(k);
+            }
+            if (members.empty()) continue;
+            std::vector<uint8_t> cbytes;
+            std::vector<uint32_t> coff{0};
+            for (size_t c = 0; c < kinds.size(); ++c) {
+                cbytes.insert(cbytes.end(), fields[c].begin(), fields[c].end()); coff.push_back((uint32_t)cbytes.size());
+                cbytes.insert(cbytes.end(), tokens[c].begin(), tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
+            }
+            std::vector<uint64_t> masks(n_sets, 0);
+            for (size_t s = 0; s < n_sets; ++s)
+                for (size_t j = 0; j < members.size(); ++j) masks[s] |= (uint64_t)((*set_wants[s])[members[j]] != 0) << j;
+            std::vector<uint64_t> bits(members.size() * n_words);
+            std::vector<uint32_t> fb(scan.size());
+            uint32_t n_fb = 0;
+            const int32_t rc = bsg_match_rows_many(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
+                                                   (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(),
+                                                   masks.data(), (uint32_t)n_sets, &tok, bits.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
+            if (rc == BSG_E_UNSUPPORTED) continue;              // programs too deep / long: the host matcher
+            if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
+            for (size_t j = 0; j < members.size(); ++j) {
+                std::vector<uint8_t> &h = hit[members[j]];
+                for (size_t i = 0; i < scan.size(); ++i) h[i] = (bits[j * n_words + (i >> 6)] >> (i & 63)) & 1;
+                on_device[members[j]] = 1;
+            }
+            for (uint32_t i = 0; i < n_fb; ++i) {               // rows outside the walker's envelope or colliding: per live query
+                const size_t s = (size_t)(std::upper_bound(set_first.begin() + 1, set_first.end(), fb[i]) - (set_first.begin() + 1));
+                for (size_t j = 0; j < members.size(); ++j)
+                    if ((masks[s] >> j) & 1) hit[members[j]][fb[i]] = host_matchers[members[j]].match(*scan[fb[i]]);
+            }
+        }
         return kEngineOk;
     }
 

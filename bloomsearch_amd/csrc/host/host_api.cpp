@@ -408,40 +408,43 @@ int32_t bse_ingest_rows(bse_engine *e, const uint8_t *ndjson, uint64_t len)
 int32_t bse_flush(bse_engine *e) { return e ? e->eng->flush() : BSH_E_INVALID; }
 int32_t bse_merge(bse_engine *e) { return e ? e->eng->merge() : BSH_E_INVALID; }
 
-int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, char **out_json, uint64_t *out_len)
-{
-    if (!e || !out_json) return BSH_E_INVALID;
+namespace {
+
+// one element of bse_query / bse_query_many: {"Bloom":{"Expression":..}|null,"Regex":{"Expression":..}|null} or null
+struct ParsedQuery {
     BloomExpression expr;
     RegexExpression regex;
     bool nil = true, has_regex = false;
-    std::string_view sv(query_json ? query_json : "", query_json ? len : 0);
-    if (!sv.empty()) {
-        JNode dom;
-        if (!parse_dom(sv, dom)) return BSE_E_INVALID_QUERY;
-        if (dom.type == JType::Object) {
-            const JNode *bloom = dom.get("Bloom");
-            if (bloom && bloom->type == JType::Object) {
-                const JNode *ex = bloom->get("Expression");
-                if (ex && ex->type == JType::Object) {
-                    if (!expression_from_json(*ex, expr)) return BSE_E_INVALID_QUERY;
-                    nil = false;
-                }
+};
+
+int32_t query_from_dom(const JNode &dom, ParsedQuery &q)
+{
+    if (dom.type == JType::Object) {
+        const JNode *bloom = dom.get("Bloom");
+        if (bloom && bloom->type == JType::Object) {
+            const JNode *ex = bloom->get("Expression");
+            if (ex && ex->type == JType::Object) {
+                if (!expression_from_json(*ex, q.expr)) return BSE_E_INVALID_QUERY;
+                q.nil = false;
             }
-            const JNode *rx = dom.get("Regex");
-            if (rx && rx->type == JType::Object) {
-                const JNode *ex = rx->get("Expression");
-                if (ex && ex->type == JType::Object) {
-                    if (!regex_expression_from_json(*ex, regex)) return BSE_E_INVALID_QUERY;
-                    has_regex = true;
-                }
-            }
-        } else if (dom.type != JType::Null) {
-            return BSE_E_INVALID_QUERY;
         }
+        const JNode *rx = dom.get("Regex");
+        if (rx && rx->type == JType::Object) {
+            const JNode *ex = rx->get("Expression");
+            if (ex && ex->type == JType::Object) {
+                if (!regex_expression_from_json(*ex, q.regex)) return BSE_E_INVALID_QUERY;
+                q.has_regex = true;
+            }
+        }
+    } else if (dom.type != JType::Null) {
+        return BSE_E_INVALID_QUERY;
     }
-    QueryResult res;
-    if (int32_t rc = e->eng->query(nil ? nullptr : &expr, res, has_regex ? &regex : nullptr)) return rc;
-    std::string out = "{\"rows\":[";
+    return 0;
+}
+
+void result_to_json(const QueryResult &res, std::string &out)
+{
+    out += "{\"rows\":[";
     for (size_t i = 0; i < res.rows.size(); ++i) { if (i) out.push_back(','); out += res.rows[i]; }
     out += "],\"stats\":{\"BlockStats\":[";
     for (size_t i = 0; i < res.block_stats.size(); ++i) {
@@ -456,6 +459,43 @@ int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, char **ou
     out += "],\"Errors\":[";
     for (size_t i = 0; i < res.errors.size(); ++i) { if (i) out.push_back(','); json_escape(out, res.errors[i]); }
     out += "],\"FilesConsidered\":" + std::to_string(res.files_considered) + ",\"FilesBloomSkipped\":" + std::to_string(res.files_bloom_skipped) + "}}";
+}
+
+}  // namespace
+
+int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, char **out_json, uint64_t *out_len)
+{
+    if (!e || !out_json) return BSH_E_INVALID;
+    ParsedQuery q;
+    std::string_view sv(query_json ? query_json : "", query_json ? len : 0);
+    if (!sv.empty()) {
+        JNode dom;
+        if (!parse_dom(sv, dom)) return BSE_E_INVALID_QUERY;
+        if (int32_t rc = query_from_dom(dom, q)) return rc;
+    }
+    QueryResult res;
+    if (int32_t rc = e->eng->query(q.nil ? nullptr : &q.expr, res, q.has_regex ? &q.regex : nullptr)) return rc;
+    std::string out;
+    result_to_json(res, out);
+    return give(out, out_json, out_len);
+}
+
+int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, char **out_json, uint64_t *out_len)
+{
+    if (!e || !out_json || !queries_json) return BSH_E_INVALID;
+    JNode dom;
+    if (!parse_dom(std::string_view(queries_json, len), dom) || dom.type != JType::Array) return BSE_E_INVALID_QUERY;
+    std::vector<ParsedQuery> qs(dom.items.size());
+    for (size_t i = 0; i < qs.size(); ++i)
+        if (int32_t rc = query_from_dom(dom.items[i], qs[i])) return rc;
+    std::vector<const BloomExpression *> exprs;
+    std::vector<const RegexExpression *> regexes;
+    for (const ParsedQuery &q : qs) { exprs.push_back(q.nil ? nullptr : &q.expr); regexes.push_back(q.has_regex ? &q.regex : nullptr); }
+    std::vector<QueryResult> res;
+    if (int32_t rc = e->eng->query_many(exprs, regexes, res)) return rc;
+    std::string out = "[";
+    for (size_t i = 0; i < res.size(); ++i) { if (i) out.push_back(','); result_to_json(res[i], out); }
+    out.push_back(']');
     return give(out, out_json, out_len);
 }
 

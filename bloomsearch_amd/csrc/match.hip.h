@@ -17,6 +17,18 @@
 // candidate text (leafTokenInput) one byte at a time, one LDS lookup each.  A condition leaves the active set once it
 // accepts (its flag is set) or its DFA is dead; the states still active when the leaf closes are checked for
 // accept-at-end.  null is never a candidate text.
+//
+// A batch of queries in one walk (k_match_rows_many / k_match_rows_many_tok = the same body with MANY = true): the table holds
+// the DISTINCT conditions of up to kMatchManyMaxQueries queries, the walk collects the same 64-bit `sat` mask per row, and the
+// epilogue evaluates one lowered program per query over it (programs concatenated in LDS behind a prog_off table, at most
+// kMatchManyMaxOps ops in all, each of depth <= 64).  Query q's verdicts form bit-plane q of out_bits, laid out as the single
+// call's result.  Rows come grouped in sets (one surviving block each) with a u64 query mask per set: a lane looks its set up
+// once (binary search in global memory), a verdict is ANDed with its mask bit, a row with mask 0 is never walked (so never a
+// fallback row) and a wave of such rows skips the walk altogether.  A row with a non-zero mask that leaves the walker's envelope
+// or collides with ANY table condition is a fallback row: all its plane bits are 0.  No FieldRegex conditions here: the regex
+// instance runs at 2 workgroups per CU with 80 KiB of LDS and would need its own sizing.
+// LDS of the MANY instance: conditions 5 632 + programs 8 192 + prog_off 260 + lanes 29 696 = 43 780 bytes, three workgroups
+// per CU as k_match_rows.
 #pragma once
 #include <type_traits>
 #include "ingest.hip.h"
@@ -45,6 +57,21 @@ struct MatchArgs {
 };
 
 constexpr uint32_t kMatchLdsBytes = kMatchMaxConds * kMatchCondWords * 8 + kMatchMaxOps * 4 + kIngestThreads * kLaneLds;
+
+// ---- a batch of queries over one condition table (k_match_rows_many) ----
+constexpr uint32_t kMatchManyMaxQueries = 64;   // one mask bit per query and set
+constexpr uint32_t kMatchManyMaxOps = 2048;     // lowered ops of all programs together: 8 KiB of LDS
+constexpr uint32_t kMatchManyProgBytes = kMatchManyMaxOps * 4 + (kMatchManyMaxQueries + 1) * 4;   // programs, then prog_off
+constexpr uint32_t kMatchManyLdsBytes = kMatchMaxConds * kMatchCondWords * 8 + kMatchManyProgBytes + kIngestThreads * kLaneLds;
+static_assert(3u * kMatchManyLdsBytes <= 160u * 1024u, "k_match_rows_many keeps three workgroups per CU");
+// MatchArgs::prog holds the concatenated lowered programs (n_ops = their total), out_bits plane 0
+struct MatchManyArgs {
+    const uint32_t *prog_off;        // [n_queries + 1] into MatchArgs::prog
+    const uint32_t *set_first_row;   // [n_sets + 1], in the rows MatchArgs::row_base counts; first 0, last = their number
+    const uint64_t *set_mask;        // [n_sets]: bit q = evaluate query q on this set's rows
+    uint64_t plane_words;            // words between two planes of out_bits
+    uint32_t n_queries, n_sets;      // n_sets == 0: every query on every row
+};
 
 // ---- FieldRegex conditions ----
 constexpr uint32_t kRxMaxConds = 16;       // regex conditions per call
@@ -102,9 +129,11 @@ struct RxLane {
     }
 };
 
-template <bool REGEX, class TOK>
-__device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs &x, const TOK &tk)
+template <bool REGEX, class TOK, bool MANY = false>
+__device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs &x, const TOK &tk, const MatchManyArgs &m = MatchManyArgs{})
 {
+    static_assert(!(REGEX && MANY), "the batched matcher takes no FieldRegex conditions");
+    constexpr uint32_t kProgBytes = MANY ? kMatchManyProgBytes : kMatchMaxOps * 4;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     lds_u64i *conds = (lds_u64i *)lds_raw;
     typedef __attribute__((address_space(3))) uint32_t lds_u32i;
@@ -116,6 +145,8 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
         e[10] = a.cond_kind[c];
     }
     for (uint32_t i = threadIdx.x; i < a.n_ops; i += kIngestThreads) prog[i] = a.prog[i];
+    if constexpr (MANY)
+        for (uint32_t i = threadIdx.x; i <= m.n_queries; i += kIngestThreads) prog[kMatchManyMaxOps + i] = m.prog_off[i];
     if constexpr (REGEX)
         for (uint32_t i = threadIdx.x; i < x.n_words; i += kIngestThreads) ((lds_u32 *)(lds_raw + kMatchLdsBytes))[i] = x.blob[i];
     __syncthreads();
@@ -124,13 +155,27 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
     Walker w;
     ChunkCursor cc;
     cc.chunks = reinterpret_cast<const uint64_t *>(a.rows);
-    w.path = (lds_u8 *)lds_raw + kMatchMaxConds * kMatchCondWords * 8 + kMatchMaxOps * 4 + threadIdx.x * kLaneLds;
+    w.path = (lds_u8 *)lds_raw + kMatchMaxConds * kMatchCondWords * 8 + kProgBytes + threadIdx.x * kLaneLds;
     w.lower = a.lower;
     w.key = a.key;
     w.ft_on = false;
     hs_init(w.ps, w.key); hs_init(w.tok, w.key); hs_init(w.ft, w.key);
-    walker_reset(w, cc, live ? a.row_off[r] : 0, live ? a.row_off[r + 1] : 0, live);
-    uint32_t res = live ? R_CONTINUE : R_DONE;
+    uint64_t qmask = ~0ull;      // MANY: the queries evaluated on this lane's row
+    if constexpr (MANY) {
+        if (live && m.n_sets) {
+            // the row's set: the first s whose rows end behind it (set_first_row[n_sets] = the number of rows > g)
+            const uint32_t g = a.row_base + r;
+            uint32_t lo = 0, hi = m.n_sets - 1u;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (m.set_first_row[mid + 1] <= g) lo = mid + 1u; else hi = mid;
+            }
+            qmask = m.set_mask[lo];
+        }
+    }
+    const bool walk = MANY ? (live && qmask != 0ull) : live;
+    walker_reset(w, cc, walk ? a.row_off[r] : 0, walk ? a.row_off[r + 1] : 0, walk);
+    uint32_t res = walk ? R_CONTINUE : R_DONE;
     uint64_t sat = 0, leaf_mask = 0;
     bool collided = false;       // equal hashes, different fingerprint: only the host's byte compare can decide this row
     typename std::conditional<REGEX, RxLane, RxNone>::type rx;
@@ -208,6 +253,36 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
             if ((rx.sat >> j) & 1u) sat |= 1ULL << (hdr[4 * j + 1] >> 16);
         if (rx_over && res == R_DONE) res = R_FAIL;
     }
+    if constexpr (MANY) {
+        // one program per query over the same flags: the loop and the program words (LDS broadcasts) are wave-uniform, each
+        // lane evaluates over its own sat, the 64 verdicts fold into one word of plane q
+        if (collided && res == R_DONE) res = R_FAIL;
+        const bool decided = live && res == R_DONE;
+        const bool store = (threadIdx.x & 63u) == 0u && (r & ~63u) < a.n_rows;
+        const lds_u32i *poff = prog + kMatchManyMaxOps;
+        for (uint32_t q = 0; q < m.n_queries; ++q) {
+            const uint32_t j0 = poff[q], j1 = poff[q + 1];
+            uint64_t stk = 0;
+            for (uint32_t j = j0; j < j1; ++j) {
+                const uint32_t op = prog[j], opc = op >> 28;
+                if (opc == 0u) stk = (stk << 1) | ((sat >> (op & 63u)) & 1ULL);
+                else if (opc == 3u) stk = (stk << 1) | 1ULL;
+                else if (opc == 4u) stk = stk << 1;
+                else {
+                    const uint64_t x = stk & 1ULL, y = (stk >> 1) & 1ULL;
+                    stk = ((stk >> 2) << 1) | (opc == 1u ? (x & y) : (x | y));
+                }
+            }
+            const bool verdict = (j0 == j1 ? true : (stk & 1ULL) != 0) && ((qmask >> q) & 1ULL) != 0;   // nil expression matches
+            const uint64_t word = __ballot(decided && verdict);
+            if (store) a.out_bits[(uint64_t)q * m.plane_words + (r >> 6)] = word;
+        }
+        if (res == R_FAIL) {
+            const uint32_t slot = __hip_atomic_fetch_add(a.n_fallback, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            a.fallback_rows[slot] = a.row_base + r;
+        }
+        return;
+    }
     // evalMatcherNode over the flags: one bit of stack per lane and level
     uint64_t stk = 0;
     for (uint32_t j = 0; j < a.n_ops; ++j) {
@@ -238,6 +313,15 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_tok(const MatchAr
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_regex_tok(const MatchArgs a, const RxArgs x, const TokSpec t)
 {
     match_rows_body<true>(a, x, TokSpecP{t});
+}
+// a batch of queries over one table of Field / Token / FieldToken conditions; dynamic LDS kMatchManyLdsBytes
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many(const MatchArgs a, const MatchManyArgs m)
+{
+    match_rows_body<false, TokDefault, true>(a, RxArgs{}, TokDefault{}, m);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_tok(const MatchArgs a, const MatchManyArgs m, const TokSpec t)
+{
+    match_rows_body<false, TokSpecP, true>(a, RxArgs{}, TokSpecP{t}, m);
 }
 
 }  // namespace bsg

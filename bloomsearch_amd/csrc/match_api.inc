@@ -52,27 +52,51 @@ int32_t build_rx_blob(const uint8_t *cond_bytes, const uint32_t *cond_off, const
     return BSG_OK;
 }
 
+// bsg_match_rows_many: what a part needs beyond the single call's arguments.  `prog` then holds the lowered programs of all
+// queries behind each other and out_bits n_queries planes of call_words words.
+struct ManyPlan {
+    std::vector<uint32_t> prog_off;        // [n_queries + 1] into prog
+    const uint32_t *set_first_row;         // the call's set table (n_sets == 0: every query on every row)
+    const uint64_t *set_mask;
+    uint32_t n_sets, n_queries;
+    size_t call_words;
+};
+
 // rows [r0, r1) (r0 a multiple of 64: whole words of out_bits) on one device; fb receives the GLOBAL indices of the rows handed back
+// many: the batched call (k_match_rows_many*), NULL = one expression
 int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64_t *row_off, uint32_t r0, uint32_t r1,
                       const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds, uint32_t cond_len,
                       const std::vector<uint32_t> &prog, const std::vector<uint32_t> &rx_blob, uint32_t n_rx, const bsg::TokSpec *tok,
-                      uint64_t *out_bits, std::vector<uint32_t> &fb, float *ms)
+                      uint64_t *out_bits, std::vector<uint32_t> &fb, float *ms, const ManyPlan *many = nullptr)
 {
     const uint32_t n_rows = r1 - r0;
     const uint64_t byte0 = row_off[r0], n_bytes = row_off[r1] - byte0;
-    const LabTrace trace{"bsg_match_rows", d.id};
+    const LabTrace trace{many ? "bsg_match_rows_many" : "bsg_match_rows", d.id};
     std::vector<uint64_t> local_off((size_t)n_rows + 1);                  // the run's offsets, relative to its first byte
     for (uint32_t r = 0; r <= n_rows; ++r) local_off[r] = row_off[r0 + r] - byte0;
+    // the sets this run's rows lie in, their first rows clamped to the run and counted from r0
+    std::vector<uint32_t> set_first;
+    uint32_t s0 = 0, n_sets = 0;
+    if (many && many->n_sets) {
+        const uint32_t *sf = many->set_first_row;
+        s0 = (uint32_t)(std::upper_bound(sf + 1, sf + many->n_sets + 1, r0) - (sf + 1));       // the first set that ends behind r0
+        const uint32_t s1 = (uint32_t)(std::lower_bound(sf, sf + many->n_sets, r1) - sf);      // the first set that begins at or behind r1
+        n_sets = s1 - s0;
+        set_first.resize((size_t)n_sets + 1);
+        for (uint32_t i = 0; i <= n_sets; ++i) set_first[i] = std::min(std::max(sf[s0 + i], r0), r1) - r0;
+    }
     d.calls.fetch_add(1, std::memory_order_relaxed);
     std::lock_guard<std::mutex> lk(d.mu);
     if (int32_t rc = use_device(d)) return rc;
     if (int32_t rc = ensure_lower_table(d)) return rc;
     trace.lap("offsets rebased, lock taken");
-    const size_t n_words = ((size_t)n_rows + 63) / 64;
+    const size_t n_words = ((size_t)n_rows + 63) / 64, n_planes = many ? many->n_queries : 1;
     Scratch scratch(d);                                                   // every early return below leaves through it: drained, then freed
     uint8_t *d_rows = nullptr, *d_cbytes = nullptr;
     uint64_t *d_off = nullptr, *d_ch = nullptr, *d_cfp = nullptr, *d_bits = nullptr;
     uint32_t *d_prog = nullptr, *d_fb = nullptr, *d_nfb = nullptr, *d_coff = nullptr, *d_ckind = nullptr, *d_rx = nullptr;
+    uint32_t *d_poff = nullptr, *d_sfirst = nullptr;
+    uint64_t *d_smask = nullptr;
     HIP_TRY(scratch.alloc(&d_rows, n_bytes + 64));
     HIP_TRY(scratch.alloc(&d_off, ((size_t)n_rows + 1) * 8));
     HIP_TRY(scratch.alloc(&d_ch, std::max<size_t>(n_conds, 1) * 2 * 32));
@@ -81,10 +105,15 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
     HIP_TRY(scratch.alloc(&d_coff, ((size_t)2 * n_conds + 1) * 4));
     HIP_TRY(scratch.alloc(&d_ckind, std::max<size_t>(n_conds, 1) * 4));
     HIP_TRY(scratch.alloc(&d_prog, std::max<size_t>(prog.size(), 1) * 4));
-    HIP_TRY(scratch.alloc(&d_bits, n_words * 8));
+    HIP_TRY(scratch.alloc(&d_bits, n_words * n_planes * 8));
     HIP_TRY(scratch.alloc(&d_fb, (size_t)n_rows * 4));
     HIP_TRY(scratch.alloc(&d_nfb, 4));
     if (n_rx) HIP_TRY(scratch.alloc(&d_rx, rx_blob.size() * 4));
+    if (many) HIP_TRY(scratch.alloc(&d_poff, many->prog_off.size() * 4));
+    if (n_sets) {
+        HIP_TRY(scratch.alloc(&d_sfirst, ((size_t)n_sets + 1) * 4));
+        HIP_TRY(scratch.alloc(&d_smask, (size_t)n_sets * 8));
+    }
     trace.lap("device buffers allocated");
     HIP_TRY(hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream));
     HIP_TRY(hipMemcpyAsync(d_off, local_off.data(), ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream));
@@ -101,6 +130,11 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
     if (!prog.empty()) HIP_TRY(hipMemcpyAsync(d_prog, prog.data(), prog.size() * 4, hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipMemsetAsync(d_nfb, 0, 4, d.stream));
     if (n_rx) HIP_TRY(hipMemcpyAsync(d_rx, rx_blob.data(), rx_blob.size() * 4, hipMemcpyHostToDevice, d.stream));
+    if (many) HIP_TRY(hipMemcpyAsync(d_poff, many->prog_off.data(), many->prog_off.size() * 4, hipMemcpyHostToDevice, d.stream));
+    if (n_sets) {
+        HIP_TRY(hipMemcpyAsync(d_sfirst, set_first.data(), ((size_t)n_sets + 1) * 4, hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemcpyAsync(d_smask, many->set_mask + s0, (size_t)n_sets * 8, hipMemcpyHostToDevice, d.stream));
+    }
     // The rows travel in chunks while the chunk before is being matched (RowUpload).  A surviving block is <= 10 MiB and goes in
     // one piece, in order on the one stream; a scan of many blocks in one call goes in pieces on the copy stream.
     RowUpload up(d, rows + byte0, d_rows, local_off.data(), n_rows, ctx->ingest_chunk_bytes);
@@ -120,7 +154,13 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
         HIP_TRY(up.wait_landed(c));
         const hipEvent_t k0 = kev.v[(size_t)c * 2], k1 = kev.v[(size_t)c * 2 + 1];
         const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads);
-        if (n_rx && tok) {
+        if (many) {
+            const bsg::MatchManyArgs m{d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets};
+            if (tok)
+                hipExtLaunchKernelGGL(bsg::k_match_rows_many_tok, grid, dim3(bsg::kIngestThreads), bsg::kMatchManyLdsBytes, d.stream, k0, k1, 0, a, m, *tok);
+            else
+                hipExtLaunchKernelGGL(bsg::k_match_rows_many, grid, dim3(bsg::kIngestThreads), bsg::kMatchManyLdsBytes, d.stream, k0, k1, 0, a, m);
+        } else if (n_rx && tok) {
             const bsg::RxArgs x{d_rx, (uint32_t)rx_blob.size(), n_rx};
             hipExtLaunchKernelGGL(bsg::k_match_rows_regex_tok, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes + (uint32_t)rx_blob.size() * 4,
                                   d.stream, k0, k1, 0, a, x, *tok);
@@ -138,7 +178,10 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
     }
     trace.lap("all chunks enqueued");
     uint32_t nfb = 0;
-    HIP_TRY(hipMemcpyAsync(out_bits + r0 / 64, d_bits, n_words * 8, hipMemcpyDeviceToHost, d.stream));
+    if (!many || many->call_words == n_words)
+        HIP_TRY(hipMemcpyAsync(out_bits + r0 / 64, d_bits, n_words * n_planes * 8, hipMemcpyDeviceToHost, d.stream));
+    else                                                                 // this run's words of every plane
+        HIP_TRY(hipMemcpy2DAsync(out_bits + r0 / 64, many->call_words * 8, d_bits, n_words * 8, n_words * 8, n_planes, hipMemcpyDeviceToHost, d.stream));
     HIP_TRY(hipMemcpyAsync(&nfb, d_nfb, 4, hipMemcpyDeviceToHost, d.stream));
     HIP_TRY(hipStreamSynchronize(d.stream));
     trace.lap("matched, bits back");
@@ -151,46 +194,33 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
     return BSG_OK;
 }
 
-// bsg_match_rows (max_kind 2), bsg_match_rows_regex (max_kind 3) and bsg_match_rows_tok (max_kind 3, a spec; NULL = default)
-int32_t match_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
-                        const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
-                        const uint32_t *prog_ops, uint32_t n_ops,
-                        uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback, uint32_t max_kind,
-                        const bsg_tokenizer *tok_in = nullptr)
+// What every row-matcher call checks of its rows and conditions (the kinds themselves are the caller's); cond_len / n_bytes out.
+int32_t check_match_inputs(const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows, const uint8_t *cond_bytes, const uint32_t *cond_off,
+                           const uint32_t *cond_kinds, uint32_t n_conds, const uint64_t *out_bits, const uint32_t *out_n_fallback,
+                           uint32_t &cond_len, uint64_t &n_bytes)
 {
-    if (!ctx) return fail(BSG_E_INVALID, "ctx is null");
-    bsg_tokenizer rec{};
-    bsg::TokSpec spec{};
-    bool is_default = true;
-    if (int32_t rc = tok_spec(tok_in, rec, spec, is_default)) return rc;
-    const bsg::TokSpec *tok = is_default ? nullptr : &spec;
     if (!out_n_fallback || (n_rows && (!row_off || !out_bits))) return fail(BSG_E_INVALID, "null argument");
     if (n_conds && (!cond_off || !cond_kinds)) return fail(BSG_E_INVALID, "conditions are null");
-    if (n_ops && !prog_ops) return fail(BSG_E_INVALID, "prog_ops is null");
     if (n_conds > bsg::kMatchMaxConds) return fail(BSG_E_UNSUPPORTED, "%u conditions (the device matcher holds %u)", n_conds, bsg::kMatchMaxConds);
-    for (uint32_t c = 0; c < n_conds; ++c)
-        if (cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, cond_kinds[c]);
     for (uint32_t e = 0; e < 2 * n_conds; ++e)
         if (cond_off[e + 1] < cond_off[e]) return fail(BSG_E_INVALID, "cond_off not monotone at %u", e);
-    const uint32_t cond_len = n_conds ? cond_off[2 * n_conds] : 0;
+    cond_len = n_conds ? cond_off[2 * n_conds] : 0;
     if (cond_len && !cond_bytes) return fail(BSG_E_INVALID, "cond_bytes is null");
     for (uint32_t r = 0; r < n_rows; ++r)
         if (row_off[r + 1] < row_off[r]) return fail(BSG_E_INVALID, "row_off not monotone at %u", r);
-    const uint64_t n_bytes = n_rows ? row_off[n_rows] - row_off[0] : 0;
+    n_bytes = n_rows ? row_off[n_rows] - row_off[0] : 0;
     if (n_bytes && !rows) return fail(BSG_E_INVALID, "rows is null");
-    std::vector<uint32_t> ident(n_conds), prog;
-    for (uint32_t c = 0; c < n_conds; ++c) ident[c] = c;
-    uint32_t depth = 1;
-    if (int32_t rc = lower_program(prog_ops, n_ops, n_conds, ident, prog, depth)) return rc;
-    if (depth > 64 || prog.size() > bsg::kMatchMaxOps)
-        return fail(BSG_E_UNSUPPORTED, "expression too large for the device matcher (depth %u, %zu ops)", depth, prog.size());
-    std::vector<uint32_t> rx_blob;
-    uint32_t n_rx = 0;
-    if (int32_t rc = build_rx_blob(cond_bytes, cond_off, cond_kinds, n_conds, rx_blob, n_rx)) return rc;
-    *out_n_fallback = 0;
-    if (n_rows == 0) return BSG_OK;
-    // Surviving blocks are independent (query_exec.go:729-764): a large scan is cut into one contiguous run of rows per
-    // device (on 64-row boundaries: whole words of out_bits, about equal bytes); a small one takes one device.
+    return BSG_OK;
+}
+
+// The validated, lowered call on the context's devices.
+// Surviving blocks are independent (query_exec.go:729-764): a large scan is cut into one contiguous run of rows per
+// device (on 64-row boundaries: whole words of out_bits, about equal bytes); a small one takes one device.
+int32_t match_rows_run(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows, uint64_t n_bytes,
+                       const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds, uint32_t cond_len,
+                       const std::vector<uint32_t> &prog, const std::vector<uint32_t> &rx_blob, uint32_t n_rx, const bsg::TokSpec *tok,
+                       uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback, const ManyPlan *many = nullptr)
+{
     const uint32_t nd = (uint32_t)ctx->devs.size();
     uint32_t want = (nd > 1 && n_bytes >= ctx->shard_min_row_bytes) ? nd : 1;
     std::vector<uint32_t> cuts{0};
@@ -207,7 +237,7 @@ int32_t match_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_o
     const uint32_t first = n_parts == 1 ? pick_device(ctx) : 0;
     if (int32_t rc = run_parts(n_parts, [&](uint32_t i) -> int32_t {
             return match_rows_on(ctx, *ctx->devs[(first + i) % nd], rows, row_off, cuts[i], cuts[i + 1], cond_bytes, cond_off, cond_kinds, n_conds,
-                                 cond_len, prog, rx_blob, n_rx, tok, out_bits, fbs[i], &ms[i]);
+                                 cond_len, prog, rx_blob, n_rx, tok, out_bits, fbs[i], &ms[i], many);
         })) return rc;
     std::vector<uint32_t> fb;
     for (auto &v : fbs) fb.insert(fb.end(), v.begin(), v.end());
@@ -221,6 +251,97 @@ int32_t match_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_o
     if (fb.size() > fallback_cap && out_fallback_rows)
         return fail(BSG_E_INVALID, "%zu rows need the host matcher, caller's list holds %u", fb.size(), fallback_cap);
     return BSG_OK;
+}
+
+// bsg_match_rows (max_kind 2), bsg_match_rows_regex (max_kind 3) and bsg_match_rows_tok (max_kind 3, a spec; NULL = default)
+int32_t match_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                        const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                        const uint32_t *prog_ops, uint32_t n_ops,
+                        uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback, uint32_t max_kind,
+                        const bsg_tokenizer *tok_in = nullptr)
+{
+    if (!ctx) return fail(BSG_E_INVALID, "ctx is null");
+    bsg_tokenizer rec{};
+    bsg::TokSpec spec{};
+    bool is_default = true;
+    if (int32_t rc = tok_spec(tok_in, rec, spec, is_default)) return rc;
+    const bsg::TokSpec *tok = is_default ? nullptr : &spec;
+    if (n_ops && !prog_ops) return fail(BSG_E_INVALID, "prog_ops is null");
+    uint32_t cond_len = 0;
+    uint64_t n_bytes = 0;
+    if (int32_t rc = check_match_inputs(rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_n_fallback, cond_len, n_bytes))
+        return rc;
+    for (uint32_t c = 0; c < n_conds; ++c)
+        if (cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, cond_kinds[c]);
+    std::vector<uint32_t> ident(n_conds), prog;
+    for (uint32_t c = 0; c < n_conds; ++c) ident[c] = c;
+    uint32_t depth = 1;
+    if (int32_t rc = lower_program(prog_ops, n_ops, n_conds, ident, prog, depth)) return rc;
+    if (depth > 64 || prog.size() > bsg::kMatchMaxOps)
+        return fail(BSG_E_UNSUPPORTED, "expression too large for the device matcher (depth %u, %zu ops)", depth, prog.size());
+    std::vector<uint32_t> rx_blob;
+    uint32_t n_rx = 0;
+    if (int32_t rc = build_rx_blob(cond_bytes, cond_off, cond_kinds, n_conds, rx_blob, n_rx)) return rc;
+    *out_n_fallback = 0;
+    if (n_rows == 0) return BSG_OK;
+    return match_rows_run(ctx, rows, row_off, n_rows, n_bytes, cond_bytes, cond_off, cond_kinds, n_conds, cond_len, prog, rx_blob, n_rx, tok, out_bits,
+                          out_fallback_rows, fallback_cap, out_n_fallback);
+}
+
+// bsg_match_rows_many: n_queries programs over one table of distinct conditions, one upload and one walk of the rows
+int32_t match_rows_many_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                             const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                             const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                             const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets, const bsg_tokenizer *tok_in,
+                             uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    if (!ctx) return fail(BSG_E_INVALID, "ctx is null");
+    bsg_tokenizer rec{};
+    bsg::TokSpec spec{};
+    bool is_default = true;
+    if (int32_t rc = tok_spec(tok_in, rec, spec, is_default)) return rc;
+    const bsg::TokSpec *tok = is_default ? nullptr : &spec;
+    if (n_queries > bsg::kMatchManyMaxQueries)
+        return fail(BSG_E_UNSUPPORTED, "%u queries (one batched match call holds %u)", n_queries, bsg::kMatchManyMaxQueries);
+    if (n_queries && !prog_off) return fail(BSG_E_INVALID, "prog_off is null");
+    for (uint32_t q = 0; q < n_queries; ++q)
+        if (prog_off[q + 1] < prog_off[q]) return fail(BSG_E_INVALID, "prog_off not monotone at %u", q);
+    if (n_queries && prog_off[n_queries] > prog_off[0] && !prog_ops) return fail(BSG_E_INVALID, "prog_ops is null");
+    uint32_t cond_len = 0;
+    uint64_t n_bytes = 0;
+    if (int32_t rc = check_match_inputs(rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_n_fallback, cond_len, n_bytes))
+        return rc;
+    for (uint32_t c = 0; c < n_conds; ++c) {
+        if (cond_kinds[c] == BSG_KIND_FIELD_REGEX)
+            return fail(BSG_E_UNSUPPORTED, "condition %u: FieldRegex conditions are not matched by the batched call (use bsg_match_rows_regex)", c);
+        if (cond_kinds[c] > BSG_KIND_FIELD_TOKEN) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, cond_kinds[c]);
+    }
+    if (n_sets) {
+        if (!set_first_row || !query_mask_of_set) return fail(BSG_E_INVALID, "set table is null");
+        if (set_first_row[0] != 0 || set_first_row[n_sets] != n_rows)
+            return fail(BSG_E_INVALID, "set_first_row spans rows [%u, %u), the call has %u", set_first_row[0], set_first_row[n_sets], n_rows);
+        for (uint32_t s = 0; s < n_sets; ++s) {
+            if (set_first_row[s + 1] < set_first_row[s]) return fail(BSG_E_INVALID, "set_first_row not monotone at %u", s);
+            if (n_queries < 64 && (query_mask_of_set[s] >> n_queries) != 0)
+                return fail(BSG_E_INVALID, "set %u: mask 0x%llx has bits at or above query %u", s, (unsigned long long)query_mask_of_set[s], n_queries);
+        }
+    }
+    ManyPlan plan{{0}, set_first_row, query_mask_of_set, n_sets, n_queries, ((size_t)n_rows + 63) / 64};
+    std::vector<uint32_t> ident(n_conds), prog, one;
+    for (uint32_t c = 0; c < n_conds; ++c) ident[c] = c;
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        uint32_t depth = 1;
+        if (int32_t rc = lower_program(prog_ops + prog_off[q], prog_off[q + 1] - prog_off[q], n_conds, ident, one, depth)) return rc;
+        if (depth > 64) return fail(BSG_E_UNSUPPORTED, "query %u: expression too deep for the device matcher (depth %u)", q, depth);
+        prog.insert(prog.end(), one.begin(), one.end());
+        if (prog.size() > bsg::kMatchManyMaxOps)
+            return fail(BSG_E_UNSUPPORTED, "the batch's programs hold more than %u lowered ops (at query %u)", bsg::kMatchManyMaxOps, q);
+        plan.prog_off.push_back((uint32_t)prog.size());
+    }
+    if (n_queries == 0 || n_rows == 0) return BSG_OK;
+    *out_n_fallback = 0;
+    return match_rows_run(ctx, rows, row_off, n_rows, n_bytes, cond_bytes, cond_off, cond_kinds, n_conds, cond_len, prog, {}, 0, tok, out_bits,
+                          out_fallback_rows, fallback_cap, out_n_fallback, &plan);
 }
 
 }  // namespace
@@ -255,6 +376,17 @@ int32_t bsg_match_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *ro
     BSG_ENTER(ctx);
     return match_rows_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, n_ops, out_bits, out_fallback_rows,
                            fallback_cap, out_n_fallback, BSG_KIND_FIELD_REGEX, tok);
+}
+
+int32_t bsg_match_rows_many(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                            const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                            const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                            const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets, const bsg_tokenizer *tok,
+                            uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    return match_rows_many_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, prog_off, n_queries, set_first_row,
+                                query_mask_of_set, n_sets, tok, out_bits, out_fallback_rows, fallback_cap, out_n_fallback);
 }
 
 int32_t bsg_pinned_alloc(bsg_ctx *ctx, uint64_t n_bytes, void **out_ptr)

@@ -614,6 +614,40 @@ class Context:
         match = np.unpackbits(bits.view(np.uint8), bitorder="little")[:n].astype(bool)
         return match, fb[: nfb.value].copy()
 
+    def match_rows_many(self, rows, batch, set_first_row=None, masks=None, tokenizer=None):
+        """bsg_match_rows_many: rows as match_rows; batch: query.CompiledMatcherBatch (or anything with its kinds / fields / tokens /
+        prog_ops / prog_off).  set_first_row [n_sets + 1] and masks [n_sets] (u64, bit q = evaluate query q on the set): both
+        None = every query on every row.  -> (bool planes [n_queries, n_rows], sorted u32 array of rows the host matcher must decide)."""
+        if isinstance(rows, tuple):
+            blob = np.ascontiguousarray(rows[0], dtype=np.uint8)
+            off = np.ascontiguousarray(rows[1], dtype=np.uint64)
+        else:
+            off = np.zeros(len(rows) + 1, dtype=np.uint64)
+            if rows:
+                off[1:] = np.cumsum([len(r) for r in rows], dtype=np.uint64)
+            blob = np.frombuffer(b"".join(rows), dtype=np.uint8)
+        n = len(off) - 1
+        cblob, coff = pack_entries([s for pair in zip(batch.fields, batch.tokens) for s in pair])
+        kinds = np.asarray(batch.kinds, dtype=np.uint32)
+        ops = np.asarray(batch.prog_ops, dtype=np.uint32)
+        poff = np.asarray(batch.prog_off, dtype=np.uint32)
+        nq, n_words = len(poff) - 1, (n + 63) // 64
+        if (set_first_row is None) != (masks is None):
+            raise ValueError("set_first_row and masks go together")
+        sfr = None if set_first_row is None else np.ascontiguousarray(set_first_row, dtype=np.uint32)
+        msk = None if masks is None else np.ascontiguousarray(masks, dtype=np.uint64)
+        if sfr is not None and len(sfr) != len(msk) + 1:
+            raise ValueError("set_first_row holds one more entry than masks")
+        bits = np.zeros((nq, n_words), dtype=np.uint64)
+        fb = np.zeros(max(n, 1), dtype=np.uint32)
+        nfb = C.c_uint32()
+        self._check(self.L.bsg_match_rows_many(self.h, _lib._ptr(blob), _lib._ptr(off), n, _lib._ptr(cblob), _lib._ptr(coff), _lib._ptr(kinds),
+                                               len(kinds), _lib._ptr(ops), poff.ctypes.data, nq, _lib._ptr(sfr), _lib._ptr(msk),
+                                               0 if msk is None else len(msk), None if tokenizer is None else c_spec(tokenizer),
+                                               _lib._ptr(bits), _lib._ptr(fb), len(fb), C.byref(nfb)))
+        planes = np.unpackbits(bits.view(np.uint8).reshape(nq, n_words * 8), axis=1, bitorder="little")[:, :n].astype(bool)
+        return planes, fb[: nfb.value].copy()
+
     def last_match_ms(self) -> float:
         v = C.c_float()
         self._check(self.L.bsg_last_match_ms(self.h, C.byref(v)))

@@ -19,7 +19,7 @@ HOST_EXPORTS = [
     "bsh_batch_new", "bsh_batch_free", "bsh_batch_add_query", "bsh_batch_sizes", "bsh_batch_export", "bsh_match_row", "bsh_match_row_with", "bsh_prune_query", "bsh_match_row_regex",
     "bsh_regex_match",
     "bsh_section_encode", "bsh_section_parse", "bsh_crc32c",
-    "bse_open", "bse_close", "bse_last_error", "bse_stop", "bse_ingest_rows", "bse_flush", "bse_merge", "bse_query",
+    "bse_open", "bse_close", "bse_last_error", "bse_stop", "bse_ingest_rows", "bse_flush", "bse_merge", "bse_query", "bse_query_many",
     "bse_describe", "bse_corrupt_section_byte", "bse_section_bytes",
 ]
 
@@ -71,6 +71,7 @@ def lib():
     L.bse_flush.argtypes = [vp]
     L.bse_merge.argtypes = [vp]
     L.bse_query.argtypes = [vp, C.c_char_p, u64, pp, pu64]
+    L.bse_query_many.argtypes = [vp, C.c_char_p, u64, pp, pu64]
     L.bse_describe.argtypes = [vp, pp, pu64]
     L.bse_corrupt_section_byte.argtypes = [vp, u32, i32, u64]
     L.bse_section_bytes.argtypes = [vp, u32, i32, pp, pu64]
@@ -312,6 +313,16 @@ class Engine:
                         "Regex": {"Expression": regex_expression} if regex_expression is not None else None}).encode()
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self.L.bse_query(self.h, q, len(q), C.byref(p), C.byref(n)))
+        return json.loads(_take(self.L, p, n))
+
+    def query_many(self, bloom_expressions, regex_expressions=None):
+        """bse_query_many: one pass for a batch of queries -> list of query()'s results, element i for bloom_expressions[i]
+        (and regex_expressions[i], where given)."""
+        rx = list(regex_expressions) if regex_expressions is not None else [None] * len(bloom_expressions)
+        q = json.dumps([{"Bloom": {"Expression": b} if b is not None else None,
+                         "Regex": {"Expression": r} if r is not None else None} for b, r in zip(bloom_expressions, rx)]).encode()
+        p, n = C.c_void_p(), C.c_uint64()
+        self._check(self.L.bse_query_many(self.h, q, len(q), C.byref(p), C.byref(n)))
         return json.loads(_take(self.L, p, n))
 
     def describe(self):

@@ -227,6 +227,61 @@ class CompiledMatcher:
             self.prog_ops.append(op(OP_FALSE))
 
 
+MATCH_MANY_MAX_QUERIES, MATCH_MANY_MAX_CONDS, MATCH_MANY_MAX_OPS = 64, 64, 2048      # bloomgpu.h bsg_match_rows_many
+
+
+def lowered_ops(prog_ops) -> int:
+    """Length of the binary program the library lowers a public postfix program to: an n-ary And / Or becomes n - 1 binary
+    ops, an empty one a constant."""
+    n = 0
+    for o in prog_ops:
+        opc, arg = o >> 28, o & 0x0FFFFFFF
+        n += (arg - 1 if arg else 1) if opc in (OP_AND, OP_OR) else 1
+    return n
+
+
+class CompiledMatcherBatch:
+    """A batch of expressions for one bsg_match_rows_many call: ONE table of distinct conditions — deduplicated across the
+    queries by (kind, field, token) — and one postfix program per query over the table's indices (query q's is
+    CompiledMatcher(expr_q)'s with its condition indices remapped).  Raises ValueError beyond the call's limits."""
+
+    def __init__(self, expressions):
+        expressions = list(expressions)
+        if len(expressions) > MATCH_MANY_MAX_QUERIES:
+            raise ValueError(f"{len(expressions)} queries: one batched match call holds {MATCH_MANY_MAX_QUERIES}")
+        self.kinds: list[int] = []
+        self.fields: list[bytes] = []
+        self.tokens: list[bytes] = []
+        self.prog_ops: list[int] = []
+        self.prog_off: list[int] = [0]
+        self.index_maps: list[list[int]] = []          # per query: CompiledMatcher condition index -> table index
+        index: dict = {}
+        lowered = 0
+        for e in expressions:
+            m = CompiledMatcher(e)
+            remap = []
+            for key in zip(m.kinds, m.fields, m.tokens):
+                i = index.get(key)
+                if i is None:
+                    i = index[key] = len(self.kinds)
+                    self.kinds.append(key[0])
+                    self.fields.append(key[1])
+                    self.tokens.append(key[2])
+                remap.append(i)
+            if len(self.kinds) > MATCH_MANY_MAX_CONDS:
+                raise ValueError(f"more than {MATCH_MANY_MAX_CONDS} distinct conditions in one batched match call")
+            self.index_maps.append(remap)
+            self.prog_ops.extend(op(OP_TERM, remap[o & 0x0FFFFFFF]) if (o >> 28) == OP_TERM else o for o in m.prog_ops)
+            self.prog_off.append(len(self.prog_ops))
+            lowered += lowered_ops(m.prog_ops)
+            if lowered > MATCH_MANY_MAX_OPS:
+                raise ValueError(f"the batch's programs lower to more than {MATCH_MANY_MAX_OPS} ops")
+
+    @property
+    def n_queries(self) -> int:
+        return len(self.prog_off) - 1
+
+
 class CompiledRowQuery(CompiledMatcher):
     """The whole compileRowMatcher root And(bloom root, regex root) (row_matcher.go:353-368) for bsg_match_rows_regex: the
     bloom side lowered as CompiledMatcher does, the regex side by compileRegexExpression's rules (row_matcher.go:440-480) —

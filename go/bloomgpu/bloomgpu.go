@@ -1009,3 +1009,54 @@ func (g *Context) matchRows(regex bool, rows []byte, rowOff []uint64, conds []Ma
 	}
 	return bits, hostRows[:nfb], g.err(rc)
 }
+
+// MatchRowsMany is the final row test of a batch of queries in one upload and one walk of the rows (bsg_match_rows_many): conds is ONE
+// table of distinct Field / Token / FieldToken conditions (no KindFieldRegex here: IsUnsupported), progOps / progOff[nQueries+1]
+// the queries' postfix programs over its indices, laid out as for BatchCreate (an empty program = nil expression = matches).
+// setFirstRow[nSets+1] and masks[nSets] group the rows in sets (one surviving block each) with bit q of a set's mask = "query q is
+// evaluated on these rows"; both nil = every query on every row.  tok: nil = the default tokenizer.
+// planes[q] has the layout MatchRows returns for query q alone; rows in hostRows (all their plane bits 0) must be decided by
+// matchRowBytes for every query whose mask bit is set on their set.  Limits: 64 queries, 64 conditions, 2048 lowered ops.
+func (g *Context) MatchRowsMany(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
+	setFirstRow []uint32, masks []uint64, tok *Tokenizer) (planes [][]uint64, hostRows []uint32, err error) {
+	n, nq := len(rowOff)-1, len(progOff)-1
+	if n <= 0 || nq <= 0 {
+		return nil, nil, nil
+	}
+	if (setFirstRow == nil) != (masks == nil) || (masks != nil && len(setFirstRow) != len(masks)+1) {
+		return nil, nil, fmt.Errorf("bloomgpu: setFirstRow holds one more entry than masks, or both are nil")
+	}
+	var ct *C.bsg_tokenizer
+	if tok != nil {
+		if err := tok.Validate(); err != nil {
+			return nil, nil, err
+		}
+		c := tok.c()
+		ct = &c
+	}
+	words := (n + 63) / 64
+	bits := make([]uint64, nq*words)
+	hostRows = make([]uint32, n)
+	var cbytes []byte
+	coff := make([]uint32, 1, 2*len(conds)+1)
+	kinds := make([]uint32, len(conds))
+	for i, c := range conds {
+		cbytes = append(cbytes, c.Field...)
+		coff = append(coff, uint32(len(cbytes)))
+		cbytes = append(cbytes, c.Token...)
+		coff = append(coff, uint32(len(cbytes)))
+		kinds[i] = c.Kind
+	}
+	var nfb C.uint32_t
+	rc := C.bsg_match_rows_many(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+		u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u64p(masks), C.uint32_t(len(masks)), ct,
+		u64p(bits), u32p(hostRows), C.uint32_t(n), &nfb)
+	if err := g.err(rc); err != nil {
+		return nil, nil, err
+	}
+	planes = make([][]uint64, nq)
+	for q := range planes {
+		planes[q] = bits[q*words : (q+1)*words]
+	}
+	return planes, hostRows[:nfb], nil
+}

@@ -594,7 +594,31 @@ BSG_API int32_t bsg_match_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint
                                    const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
                                    uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                    uint32_t *out_n_fallback);
-/* Device time of the most recent k_match_rows / k_match_rows_regex dispatch (the slowest device's). */
+/* A batch of queries matched in ONE upload and ONE walk of the rows (k_match_rows_many): n_queries <= 64 expressions over ONE
+ * table of distinct Field / Token / FieldToken conditions (packed as for bsg_match_rows), prog_ops / prog_off[n_queries + 1]
+ * the public postfix programs over condition indices laid out as for bsg_batch_create (an empty program = nil expression =
+ * every row matches).  out_bits holds n_queries bit-planes of ceil(n_rows / 64) words: plane q = what bsg_match_rows(_tok)
+ * returns for expression q alone.
+ * Rows may come grouped in sets (one surviving block each): set s = rows [set_first_row[s], set_first_row[s + 1]),
+ * set_first_row[0] == 0, set_first_row[n_sets] == n_rows, and bit q of query_mask_of_set[s] says that query q survived the probe on
+ * that block and is evaluated there; every other plane bit of the set's rows is 0.  NULL, NULL, 0 = every query on every row.
+ * A row whose set has mask 0 is never walked.  tok: NULL = the default tokenizer, as bsg_match_rows_tok.
+ * Fallback rows (listed once, ascending; all their plane bits are 0): a row with a non-zero mask that leaves the device walker's
+ * envelope, or in which an emission has the base hashes of ANY table condition but not its fingerprint.  A row with mask 0 is
+ * never a fallback row.  The host matcher decides them per query whose mask bit is set.
+ * Limits (BSG_E_UNSUPPORTED before anything is launched): 64 queries, 64 conditions, 2 048 lowered ops over all programs
+ * (an n-ary AND / OR lowers to n - 1 binary ops), depth 64 per program, and no BSG_KIND_FIELD_REGEX condition: the regex kernels
+ * are sized differently (bsg_match_rows_regex).  BSG_E_INVALID: null arguments, offsets that are not monotone, a set table that
+ * does not span [0, n_rows), mask bits at or above n_queries.  n_queries == 0 or n_rows == 0: BSG_OK, nothing written.
+ * Sharding over the context's devices, chunked upload and bsg_last_match_ms as bsg_match_rows. */
+BSG_API int32_t bsg_match_rows_many(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                    const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                    const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                    const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets,
+                                    const bsg_tokenizer *tok,
+                                    uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                    uint32_t *out_n_fallback);
+/* Device time of the most recent k_match_rows / k_match_rows_regex / k_match_rows_many dispatch (the slowest device's). */
 BSG_API int32_t bsg_last_match_ms(bsg_ctx *ctx, float *match_ms);
 
 #ifdef __cplusplus

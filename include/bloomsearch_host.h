@@ -123,6 +123,13 @@ BSG_API int32_t bse_merge(bse_engine *e);
  * {"rows":[...],"stats":{"BlockStats":[{"FileID","BlockOffset","RowsProcessed","BytesProcessed","TotalRows",
  *  "TotalBytes","BloomFilterSkipped"}],"Errors":[..],"FilesConsidered","FilesBloomSkipped"}} */
 BSG_API int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, char **out_json, uint64_t *out_len);
+/* A batch of queries in one pass.  queries_json: a JSON array of bse_query's query objects; out_json: a JSON array of bse_query's
+ * result objects, element i equal to what bse_query returns for query i alone (rows in the same order, the same BlockStats,
+ * Errors, FilesConsidered, FilesBloomSkipped; Duration is exempt).  All bloom-only queries share one query batch: one file-stage
+ * probe, one bsg_probe_many over the leased arenas, then the rows of every block at least one query survived on are scanned once
+ * - under DeviceMatch by one bsg_match_rows_many call per group of <= 64 queries / <= 64 distinct conditions, each block a set
+ * with the mask of the queries that survived on it.  A query with a Regex tree is answered as by bse_query.  "[]" gives "[]". */
+BSG_API int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, char **out_json, uint64_t *out_len);
 /* {"files":[{"FileID","BloomEntryCounts":{..},"section_bytes","blocks":[{"PartitionID","Rows","BloomEntryCounts":{..},
  *  "BloomFalsePositiveRate","BloomFilterSize","filters":[{"m","k"}|null x3]}]}]} */
 BSG_API int32_t bse_describe(bse_engine *e, char **out_json, uint64_t *out_len);

@@ -13,6 +13,7 @@
 #include "direct.hip.h"
 #include "match.hip.h"
 #include "host/combiner_sync.hpp"
+#include "host/probe_plan.hpp" // survivor offsets, launch groups, rows layout and the host merge of a probe call
 #include "host/regex_dfa.hpp"  // FieldRegex patterns -> the DFA tables k_match_rows_regex steps
 #include "host/row_chunks.hpp" // the chunk plan and byte ranges RowUpload copies by
 #include "host/text.hpp"   // the host walker's Unicode tables: the device defers to the same data

@@ -175,7 +175,7 @@ int32_t enqueue_hot(bsg_ctx *ctx, Hot &h, uint32_t di, std::vector<Dispatch> &al
     for (size_t pos = 0; pos < h.arenas.size(); ++pos) {
         const ArenaShard &s = h.arenas[pos]->shards[di];
         if (s.n_blocks == 0) continue;
-        group_add(g, B, s, (uint32_t)pos);
+        group_add(g, B.n_queries, B.Wt, s, (uint32_t)pos);
         at[pos] = (int64_t)(gp * B.n_queries);
         G_of[pos] = (s.n_blocks + 63) / 64;
         gp += G_of[pos];
@@ -361,7 +361,7 @@ int32_t finish_dispatches(bsg_ctx *ctx, std::vector<Dispatch> &all, int32_t rc_i
                 const uint64_t *src = P.result.first + row.second;
                 uint64_t *dst = r.out + r.out_off[row.first.j];
                 if (nd == 1) memcpy(dst, src, (size_t)r.n_queries * G * 8);
-                else interleave_shard(src, r.n_queries, s.n_blocks, P.di, nd, dst, ((uint64_t)A.n_blocks + 63) / 64);      // (the caller zeroed its rows)
+                else bsh::interleave_shard(src, r.n_queries, s.n_blocks, P.di, nd, dst, ((uint64_t)A.n_blocks + 63) / 64);      // (the caller zeroed its rows)
             }
     }
     ctx->cmb.ns_scatter.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_s).count(), std::memory_order_relaxed);

@@ -1,0 +1,202 @@
+// probe_plan.hpp — the arithmetic of a probe call, free of any device type: where the survivors of every arena go, how one device's
+// shards are cut into launch groups, the tail-split cut, the layout of survivor rows, and the host merge of the per-device bitsets.
+// probe_arenas / query_solo (probe_api.inc) plan and merge by these functions; tests/probe_plan_check.cpp runs the same code on the
+// CPU (tests/test_probe_plan.py).  Everything here works on block counts and sizes only; a list of block counts is taken as a
+// callable i -> blocks (the library reads them out of its arenas in place, the test out of a vector).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace bsh {
+
+// bytes of survivors / verdict words one dispatch group may need (a single arena beyond it still forms a group)
+constexpr uint64_t kGroupScratchBudget = 256ull << 20;
+
+inline uint32_t words64(uint64_t n_blocks) { return (uint32_t)((n_blocks + 63) / 64); }
+
+// [n_arenas + 1] word offsets: arena i's survivors ([n_queries][ceil(blocks / 64)]) start at out + offsets[i]
+template <class BlocksOf>
+inline std::vector<uint64_t> survivor_offsets(uint32_t n_arenas, uint32_t n_queries, BlocksOf &&blocks)
+{
+    std::vector<uint64_t> off(n_arenas + 1, 0);
+    for (uint32_t i = 0; i < n_arenas; ++i) off[i + 1] = off[i] + (uint64_t)n_queries * words64(blocks(i));
+    return off;
+}
+
+// A launch group as numbers: the shards (on one device) of some arenas of the caller's list, probed by ONE dispatch.
+struct GroupPlan {
+    std::vector<uint32_t> index;     // position of each shard's arena in the caller's list
+    uint64_t v_words = 0;            // verdict scratch the group needs (u64)
+    uint64_t out_words = 0;          // survivors the group produces (u64)
+    uint32_t max_blocks = 0, max_G = 0, total_G = 0;
+    void add(uint32_t pos, uint32_t n_blocks, uint32_t n_queries, uint32_t Wt)
+    {
+        const uint32_t G = words64(n_blocks);
+        index.push_back(pos);
+        v_words += (uint64_t)G * std::max(Wt, 1u) * 64;
+        out_words += (uint64_t)n_queries * G;
+        max_blocks = std::max(max_blocks, n_blocks);
+        max_G = std::max(max_G, G);
+        total_G += G;
+    }
+};
+
+// The groups of one device from its local block counts per arena (empty shards join no group).  A group closes when it holds
+// `limit` shards, and also on BYTES: its survivors (n_queries x 64-block groups x 8) and verdict words live in scratch that never
+// shrinks, and one huge group is one copy behind one dispatch — nothing for the copy stream to overlap.  A single shard beyond the
+// budget still forms a group.  G: GroupPlan, or what the caller derives from it.
+template <class G = GroupPlan, class BlocksOf>
+inline std::vector<G> plan_groups(uint32_t n_arenas, BlocksOf &&local_blocks, uint32_t n_queries, uint32_t Wt, uint32_t limit,
+                                  uint64_t budget = kGroupScratchBudget)
+{
+    std::vector<G> groups;
+    for (uint32_t i = 0; i < n_arenas; ++i) {
+        const uint32_t n_blocks = local_blocks(i);
+        if (n_blocks == 0) continue;
+        const uint64_t G_add = words64(n_blocks);
+        const bool full = !groups.empty() && !groups.back().index.empty() &&
+                          ((groups.back().out_words + (uint64_t)n_queries * G_add) * 8 > budget ||
+                           (groups.back().v_words + G_add * std::max(Wt, 1u) * 64) * 8 > budget);
+        if (groups.empty() || groups.back().index.size() >= limit || full) groups.emplace_back();
+        groups.back().add(i, n_blocks, n_queries, Wt);
+    }
+    return groups;
+}
+
+// [n_groups + 1] where each group's survivors go (u64 offset).  out_off != nullptr (one device, or survivors left on the device):
+// a group's arenas are consecutive in the caller's list unless empty arenas sit between them (those produce no words), so the
+// group's words are contiguous at out_off[first arena of the group]; the last entry stays 0.  out_off == nullptr (several devices,
+// host output): a running sum inside the device's own part buffer, the last entry its size.
+template <class G>
+inline std::vector<uint64_t> group_offsets(const std::vector<G> &groups, const uint64_t *out_off)
+{
+    std::vector<uint64_t> goff(groups.size() + 1, 0);
+    uint64_t total = 0;
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        goff[gi] = out_off ? out_off[groups[gi].index[0]] : total;
+        total += groups[gi].out_words;
+    }
+    if (!out_off) goff[groups.size()] = total;
+    return goff;
+}
+
+// Tail split (lab key 19, percent): a run of ONE group of n_shards shards is cut into two dispatches' worth, the first n0 shards
+// and the rest.  Returns n0 (1 <= n0 <= n_shards - 1), or 0 where the run is not cut: fewer than 8 shards, or more than one
+// launch's kernel arguments hold.
+inline size_t tail_split_cut(size_t n_shards, uint32_t pct, size_t max_group_arenas)
+{
+    if (pct == 0 || n_shards < 8 || n_shards > max_group_arenas) return 0;
+    return std::min(n_shards - 1, std::max<size_t>(1, n_shards * pct / 100));
+}
+
+// bsg_probe_many_rows on a context of nd devices: device d writes the rows of ITS shards (local block numbers: local l of device d is
+// global block l * nd + d) into a slice of its own of the caller's page-locked buffers —
+//   headers: out_hdr + d * n_arenas * n_queries, [arena][query]
+//   rows   : out_rows + row_base[d], arena i's [n_queries][G(i, d)] slots back to back, G(i, d) = ceil(local blocks of (i, d) / 64)
+// (nd == 1: exactly the single-device layout).  bsg_survivor_rows_list merges a (arena, query)'s nd rows into global block order.
+struct RowsLayout {
+    uint32_t nd = 1, n_arenas = 0, n_queries = 0;
+    std::vector<uint64_t> row_base;                 // [nd + 1] first row word of device d's slice
+    std::vector<std::vector<uint64_t>> arena_off;   // [nd][n_arenas] arena i's rows inside device d's slice
+};
+
+// local_blocks(d, i): the blocks of arena i on device d
+template <class BlocksOf>
+inline RowsLayout rows_layout(uint32_t nd, uint32_t n_arenas, uint32_t n_queries, BlocksOf &&local_blocks)
+{
+    RowsLayout L;
+    L.nd = nd; L.n_arenas = n_arenas; L.n_queries = n_queries;
+    L.row_base.assign(nd + 1, 0);
+    L.arena_off.assign(nd, std::vector<uint64_t>(n_arenas, 0));
+    for (uint32_t d = 0; d < nd; ++d) {
+        uint64_t o = 0;
+        for (uint32_t i = 0; i < n_arenas; ++i) {
+            L.arena_off[d][i] = o;
+            o += (uint64_t)n_queries * words64(local_blocks(d, i));
+        }
+        L.row_base[d + 1] = L.row_base[d] + o;
+    }
+    return L;
+}
+
+// survivors of device di's shard (local block lb == global block lb * nd + di) -> the caller's global bitset (ORed into it).
+// An output word holds, from device di, the local bits lo..hi at the positions p0, p0 + nd, ...: one bit-field extract and
+// one parallel deposit (BMI2 pdep) per (word, device) instead of a loop over the set bits — a 10 000-block, 4 096-query
+// result has 17 M of them.  Hosts without BMI2 take the loop.
+inline void interleave_shard_loop(const uint64_t *part, uint32_t Q, uint32_t n_local, uint32_t di, uint32_t nd, uint64_t *dst, uint64_t Gglobal)
+{
+    const uint32_t G = (n_local + 63) / 64;
+    for (uint32_t q = 0; q < Q; ++q) {
+        const uint64_t *row = part + (size_t)q * G;
+        uint64_t *o = dst + (size_t)q * Gglobal;
+        for (uint32_t g = 0; g < G; ++g) {
+            uint64_t w = row[g];
+            while (w) {
+                const uint32_t bit = (uint32_t)__builtin_ctzll(w);
+                w &= w - 1;
+                const uint64_t b = ((uint64_t)g * 64 + bit) * nd + di;
+                o[b >> 6] |= 1ULL << (b & 63);
+            }
+        }
+    }
+}
+
+__attribute__((target("bmi2"))) inline void interleave_shard_pdep(const uint64_t *part, uint32_t Q, uint32_t n_local, uint32_t di, uint32_t nd,
+                                                                   uint64_t *dst, uint64_t Gglobal)
+{
+    const uint32_t G = (n_local + 63) / 64;
+    // deposit masks by first position p0 < nd: bits p0, p0 + nd, ... below 64
+    std::vector<uint64_t> masks(nd, 0);
+    for (uint32_t p0 = 0; p0 < nd; ++p0)
+        for (uint32_t p = p0; p < 64; p += nd) masks[p0] |= 1ULL << p;
+    const uint64_t n_global = (uint64_t)(n_local - 1) * nd + di + 1;      // one past this shard's last global block
+    const uint64_t n_words = (n_global + 63) / 64;
+    // per output word: first local bit and first position (the same for every query)
+    std::vector<uint32_t> lo_of(n_words), p0_of(n_words);
+    for (uint64_t ow = 0; ow < n_words; ++ow) {
+        const uint64_t first = ow * 64;                                   // lo = ceil((first - di) / nd), clamped at 0
+        const uint64_t lo = first > di ? (first - di + nd - 1) / nd : 0;
+        lo_of[ow] = (uint32_t)lo;
+        p0_of[ow] = (uint32_t)(lo * nd + di - first);
+    }
+    for (uint32_t q = 0; q < Q; ++q) {
+        const uint64_t *row = part + (size_t)q * G;
+        uint64_t *o = dst + (size_t)q * Gglobal;
+        for (uint64_t ow = 0; ow < n_words; ++ow) {
+            const uint32_t lo = lo_of[ow], p0 = p0_of[ow];
+            if (lo >= n_local || p0 >= 64) continue;
+            const uint32_t wi = lo >> 6, sh = lo & 63u;
+            uint64_t src = row[wi] >> sh;
+            if (sh && wi + 1 < G) src |= row[wi + 1] << (64 - sh);       // (bits past n_local are zero in the survivors)
+            o[ow] |= __builtin_ia32_pdep_di(src, masks[p0]);
+        }
+    }
+}
+
+inline void interleave_shard(const uint64_t *part, uint32_t Q, uint32_t n_local, uint32_t di, uint32_t nd, uint64_t *dst, uint64_t Gglobal)
+{
+    if (n_local == 0) return;
+    static const bool has_bmi2 = __builtin_cpu_supports("bmi2");
+    if (has_bmi2 && nd <= 64) interleave_shard_pdep(part, Q, n_local, di, nd, dst, Gglobal);
+    else interleave_shard_loop(part, Q, n_local, di, nd, dst, Gglobal);
+}
+
+// One device's survivors into the caller's (zeroed) layout: `part` holds the device's non-empty shards back to back in list order,
+// shard i as [n_queries][ceil(local_blocks[i] / 64)]; arena i's global bitsets ([n_queries][ceil(global_blocks[i] / 64)]) start at
+// dst + out_off[i].
+template <class LocalBlocksOf, class GlobalBlocksOf>
+inline void merge_device_part(const uint64_t *part, uint32_t n_arenas, LocalBlocksOf &&local_blocks, GlobalBlocksOf &&global_blocks, uint32_t n_queries,
+                              uint32_t di, uint32_t nd, uint64_t *dst, const uint64_t *out_off)
+{
+    uint64_t o = 0;
+    for (uint32_t i = 0; i < n_arenas; ++i) {
+        const uint32_t n_local = local_blocks(i);
+        if (n_local == 0) continue;
+        interleave_shard(part + o, n_queries, n_local, di, nd, dst + out_off[i], words64(global_blocks(i)));
+        o += (uint64_t)n_queries * words64(n_local);
+    }
+}
+
+}  // namespace bsh

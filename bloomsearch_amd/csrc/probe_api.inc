@@ -302,19 +302,14 @@ int32_t take_events(bsg_ctx *ctx, Device &d, EventTriple &ev)
     return BSG_OK;
 }
 
-constexpr uint64_t kGroupScratchBudget = 256ull << 20;     // bytes of survivors / verdict words one dispatch group may need (a single arena beyond it still forms a group)
-
-// A launch group: the shards (on one device) of up to kMaxGroupArenas arenas, probed by ONE dispatch.
-struct Group {
+// A launch group: the shards (on one device) of up to kMaxGroupArenas arenas, probed by ONE dispatch — the plan's figures
+// (host/probe_plan.hpp: index, v_words, out_words, max_blocks, max_G, total_G) and the shards they stand for.
+struct Group : bsh::GroupPlan {
     std::vector<const ArenaShard *> shards;
-    std::vector<uint32_t> index;     // position of each shard's arena in the caller's list
-    uint64_t v_words = 0;            // verdict scratch the group needs (u64)
-    uint64_t out_words = 0;          // survivors the group produces (u64)
-    uint32_t max_blocks = 0, max_G = 0, total_G = 0;
 };
 
 // the group's arena records from position i0 on (at most `cap` of them); g_prefix counts from the group's first arena
-void fill_refs(const Group &g, const Batch &, bsg::ArenaRef *refs, size_t i0 = 0, size_t cap = ~size_t(0))
+void fill_refs(const Group &g, bsg::ArenaRef *refs, size_t i0 = 0, size_t cap = ~size_t(0))
 {
     uint32_t gp = 0;
     for (size_t i = 0; i < g.shards.size() && i < i0 + cap; ++i) {
@@ -324,31 +319,37 @@ void fill_refs(const Group &g, const Batch &, bsg::ArenaRef *refs, size_t i0 = 0
     }
 }
 
-void group_add(Group &g, const Batch &B, const ArenaShard &s, uint32_t idx)
+void group_add(Group &g, uint32_t n_queries, uint32_t Wt, const ArenaShard &s, uint32_t idx)
 {
-    const uint32_t G = (s.n_blocks + 63) / 64;
+    g.add(idx, s.n_blocks, n_queries, Wt);
     g.shards.push_back(&s);
-    g.index.push_back(idx);
-    g.v_words += (uint64_t)G * std::max(B.Wt, 1u) * 64;
-    g.out_words += (uint64_t)B.n_queries * G;
-    g.max_blocks = std::max(g.max_blocks, s.n_blocks);
-    g.max_G = std::max(g.max_G, G);
-    g.total_G += G;
 }
+
+// block counts as the plan takes them (i -> blocks): of the arenas, and of their shards on device di
+struct ArenaBlocks {
+    const std::vector<std::shared_ptr<Arena>> &arenas;
+    uint32_t operator()(uint32_t i) const { return arenas[i]->n_blocks; }
+};
+
+struct ShardBlocks {
+    const std::vector<std::shared_ptr<Arena>> &arenas;
+    uint32_t di;
+    uint32_t operator()(uint32_t i) const { return arenas[i]->shards[di].n_blocks; }
+};
 
 // The arena records of a group for k_probe_terms(_many) / k_eval_programs: in the kernel arguments up to kMaxGroupArenas, else
 // uploaded into the scratch slot's device table in front of the dispatch (same stream: ordered before it, and after the
 // previous user of the slot).  *ext = nullptr or the device table.
-int32_t group_table(Device &d, const Group &g, const Batch &B, uint32_t slot, bsg::ArenaTable<bsg::kMaxGroupArenas> &t, const bsg::ArenaRef **ext)
+int32_t group_table(Device &d, const Group &g, bsg::ArenaTable<bsg::kMaxGroupArenas> &t, const bsg::ArenaRef **ext)
 {
     *ext = nullptr;
     const size_t n = g.shards.size();
-    if (n <= bsg::kMaxGroupArenas) { fill_refs(g, B, t.ar); return BSG_OK; }
+    if (n <= bsg::kMaxGroupArenas) { fill_refs(g, t.ar); return BSG_OK; }
     // A table in device memory is a pure function of its records, and hosts probe the same candidate files again and again: the
     // device keeps the last few tables it wrote (round 5), so a group that was probed before costs no k_write_arena_table dispatches
     // — two serial ~5 us dispatches in front of the stream for the 200 shards a rank holds of 20 steps x 10 files at N = 8.
     std::vector<bsg::ArenaRef> refs(n);
-    fill_refs(g, B, refs.data());
+    fill_refs(g, refs.data());
     uint64_t h = 0x9E3779B97F4A7C15ull ^ n;
     for (const auto &r : refs) { h = (h ^ (uint64_t)(uintptr_t)r.words) * 0x100000001B3ull; h = (h ^ (uint64_t)(uintptr_t)r.desc) * 0x100000001B3ull; h = (h ^ r.n_blocks) * 0x100000001B3ull; }
     for (auto &c : d.table_cache)
@@ -372,7 +373,6 @@ int32_t group_table(Device &d, const Group &g, const Batch &B, uint32_t slot, bs
     }
     e->hash = h; e->refs = std::move(refs); e->last_use = ++d.table_tick;
     *ext = e->buf.p;
-    (void)slot;
     return BSG_OK;
 }
 
@@ -443,7 +443,7 @@ int32_t enqueue_terms(bsg_ctx *ctx, Device &d, const Group &g, const BatchDev &b
     // fault that tools/fuzz_probe.py reached after 2 100 seeds: an all-constant batch against 129+ arenas behind a larger batch)
     bsg::ArenaTable<bsg::kMaxGroupArenas> t;
     const bsg::ArenaRef *ext = nullptr;
-    if (int32_t rc = group_table(d, g, B, slot, t, &ext)) return rc;
+    if (int32_t rc = group_table(d, g, t, &ext)) return rc;
     d.ext_of_slot[slot] = ext;
     if (B.n_kinds == 0) return BSG_OK;
     const dim3 grid(g.max_blocks, B.n_kinds, a.n_arenas), wg(bsg::kProbeThreads);
@@ -466,10 +466,67 @@ int32_t ring_doorbell(Device &d, uint64_t *flag, uint64_t seq)
     return BSG_OK;
 }
 
+// A doorbell'd result on its way to the host: a page-locked buffer from the device's idle list, which k_probe_direct / k_query_direct
+// write the survivors into, and the doorbell word behind the survivors.  The object lives OUTSIDE the scope of the device lock that
+// take() is called under, because its destructor takes that lock: the buffer goes back to the device whatever way the call ends,
+// behind a drain of the device's stream unless the call knows the kernels that write it to be over (drained).
+struct DirectResult {
+    Device *dev = nullptr;
+    uint32_t di = 0;                 // the device's position in the context
+    uint64_t *buf = nullptr;
+    size_t cap = 0, bytes = 0;       // of the buffer; of the survivors in it
+    uint64_t *flag = nullptr;
+    uint64_t seq = 0;
+    uint64_t *dst = nullptr;         // where the caller wants the survivors, if it copies them as they are
+    bool drained = false;
+    DirectResult() = default;
+    DirectResult(DirectResult &&o) noexcept
+        : dev(o.dev), di(o.di), buf(o.buf), cap(o.cap), bytes(o.bytes), flag(o.flag), seq(o.seq), dst(o.dst), drained(o.drained) { o.buf = nullptr; }
+    DirectResult &operator=(DirectResult &&) = delete;
+    ~DirectResult()
+    {
+        if (!buf) return;
+        std::lock_guard<std::mutex> lk(dev->mu);
+        if (!drained) (void)hipStreamSynchronize(dev->stream);
+        dev->direct_bufs.emplace_back(buf, cap);
+    }
+    // under d.mu: a buffer for n_bytes of survivors, the device's workgroup counter, the bell armed with the device's next number
+    int32_t take(Device &d, uint32_t device_index, size_t n_bytes)
+    {
+        dev = &d; di = device_index; bytes = n_bytes;
+        const size_t need = n_bytes + 64;                  // the doorbell word sits behind the survivors
+        for (size_t i = 0; i < d.direct_bufs.size(); ++i)
+            if (d.direct_bufs[i].second >= need) { buf = d.direct_bufs[i].first; cap = d.direct_bufs[i].second; d.direct_bufs.erase(d.direct_bufs.begin() + i); break; }
+        if (!buf) {
+            uint64_t *p = nullptr;
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(64 * 1024, need), hipHostMallocDefault));
+            buf = p; cap = std::max<size_t>(64 * 1024, need);
+        }
+        if (!d.d_direct_count) {
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_direct_count), 64));
+            HIP_TRY(hipMemsetAsync(d.d_direct_count, 0, 64, d.stream));
+        }
+        flag = buf + (n_bytes + 7) / 8; seq = ++d.direct_seq;
+        *reinterpret_cast<volatile uint64_t *>(flag) = 0;
+        return BSG_OK;
+    }
+    // polls the bell for at most `limit`; false: it stayed silent (the caller asks the runtime)
+    bool wait(std::chrono::microseconds limit) const
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq)
+            if (std::chrono::steady_clock::now() - t0 > limit) return false;
+        return true;
+    }
+};
+
 // One dispatch for a small batch: bit tests + programs of every 64-block group (direct.hip.h); survivors to `out`.
-int32_t enqueue_direct(Device &d, const Group &g, const BatchDev &bd, const Batch &B, uint64_t *out, uint64_t *flag, uint64_t seq, EventTriple *ev, uint32_t ring_wgs)
+// res: the doorbell'd buffer `out` belongs to (nullptr: survivors left on the device, no bell).
+int32_t enqueue_direct(Device &d, const Group &g, const BatchDev &bd, const Batch &B, uint64_t *out, const DirectResult *res, EventTriple *ev, uint32_t ring_wgs)
 {
     bsg::DirectArgs a{};
+    uint64_t *flag = res ? res->flag : nullptr;
+    const uint64_t seq = d.direct_seq;                     // (== res->seq: taken under the same hold of the device lock)
     // (the kernel's own doorbell costs every workgroup a system-scope fence: beyond ring_wgs workgroups a dispatch behind it rings)
     const bool ring = flag && (uint64_t)g.max_G * g.shards.size() > ring_wgs;
     if (!ring) { a.done_count = d.d_direct_count; a.flag = flag; a.seq = seq; }
@@ -478,7 +535,7 @@ int32_t enqueue_direct(Device &d, const Group &g, const BatchDev &bd, const Batc
     for (uint32_t y = 0; y < B.n_kinds; ++y) { a.kind[y] = B.kind[y]; a.term_begin[y] = B.term_begin[y]; a.term_count[y] = B.term_count[y]; }
     a.n_arenas = (uint32_t)g.shards.size();
     bsg::ArenaTable<bsg::kMaxGroupArenas> t;
-    fill_refs(g, B, t.ar);
+    fill_refs(g, t.ar);
     hipExtLaunchKernelGGL(bsg::k_probe_direct, dim3(g.max_G, 1, a.n_arenas), dim3(bsg::kEvalThreads), bsg::direct_lds_bytes(a.Wt, B.max_depth),
                           d.stream, ev ? ev->k1s : nullptr, ev ? ev->k1e : nullptr, 0, a, t);
     HIP_TRY(hipGetLastError());
@@ -503,7 +560,7 @@ int32_t enqueue_eval(Device &d, const Group &g, const BatchDev &bd, const Batch 
     const uint32_t tile = eval_tile_for(g);
     bsg::ArenaTable<bsg::kMaxGroupArenas> t;
     const bsg::ArenaRef *ext = nullptr;
-    if (g.shards.size() <= bsg::kMaxGroupArenas) fill_refs(g, B, t.ar);
+    if (g.shards.size() <= bsg::kMaxGroupArenas) fill_refs(g, t.ar);
     else ext = d.ext_of_slot[slot];         // written (or found in the device's table cache) by this group's probe dispatch (enqueue_terms), same slot, same stream
     // batches with the identity word list transpose a whole tile's words at once (eval_role_all) when that fits 64 KB of LDS
     static const bool lab_serial = getenv("BSG_LAB_EVAL_SERIAL") != nullptr;   // lab only: the per-group walk for every batch
@@ -558,7 +615,7 @@ int32_t enqueue_fold(bsg_ctx *ctx, Device &d, const Group &g, const BatchDev &bd
     f.n_kinds = B.n_kinds;
     lds = std::max(lds, bsg::fold_eval_lds_bytes(f.tile_groups, B.max_cw, B.max_depth));
     bsg::ArenaTable<bsg::kMaxGroupArenas> t;
-    fill_refs(g, B, t.ar);
+    fill_refs(g, t.ar);
     hipExtLaunchKernelGGL(bsg::k_probe_eval, dim3(g.max_blocks, B.n_kinds, f.p.n_arenas), dim3(bsg::kProbeThreads), lds, d.stream,
                           ev ? ev->k1s : nullptr, ev ? ev->k1e : nullptr, 0, f, t);
     HIP_TRY(hipGetLastError());
@@ -583,75 +640,13 @@ int32_t enqueue_fused(bsg_ctx *ctx, Device &d, const Group &g, uint32_t slot, co
     const uint64_t grid = (uint64_t)f.n_probe + (uint64_t)(pg.max_G + f.eval_tile - 1) / f.eval_tile * f.eval_pairs * f.e.n_arenas;
     if (grid > 0x7FFFFFFFull) return fail(BSG_E_UNSUPPORTED, "fused launch of %llu workgroups", (unsigned long long)grid);
     bsg::ArenaTable<bsg::kMaxFusedArenas> tp, te;              // (the caller keeps fused groups within kMaxFusedArenas)
-    fill_refs(g, B, tp.ar);
-    fill_refs(pg, B, te.ar);
+    fill_refs(g, tp.ar);
+    fill_refs(pg, te.ar);
     hipExtLaunchKernelGGL(bsg::k_probe_fused, dim3((uint32_t)grid), dim3(bsg::kProbeThreads), lds, d.stream, ev ? ev->k1s : nullptr,
                           ev ? ev->k1e : nullptr, 0, f, tp, te);
     HIP_TRY(hipGetLastError());
     if (ev) { ev->has_k1 = true; ev->fused = true; }
     return BSG_OK;
-}
-
-// survivors of device di's shard (local block lb == global block lb * nd + di) -> the caller's global bitset.
-// An output word holds, from device di, the local bits lo..hi at the positions p0, p0 + nd, ...: one bit-field extract and
-// one parallel deposit (BMI2 pdep) per (word, device) instead of a loop over the set bits — a 10 000-block, 4 096-query
-// result has 17 M of them.  Hosts without BMI2 take the loop.
-static void interleave_shard_loop(const uint64_t *part, uint32_t Q, uint32_t n_local, uint32_t di, uint32_t nd, uint64_t *dst, uint64_t Gglobal)
-{
-    const uint32_t G = (n_local + 63) / 64;
-    for (uint32_t q = 0; q < Q; ++q) {
-        const uint64_t *row = part + (size_t)q * G;
-        uint64_t *o = dst + (size_t)q * Gglobal;
-        for (uint32_t g = 0; g < G; ++g) {
-            uint64_t w = row[g];
-            while (w) {
-                const uint32_t bit = (uint32_t)__builtin_ctzll(w);
-                w &= w - 1;
-                const uint64_t b = ((uint64_t)g * 64 + bit) * nd + di;
-                o[b >> 6] |= 1ULL << (b & 63);
-            }
-        }
-    }
-}
-
-__attribute__((target("bmi2"))) static void interleave_shard_pdep(const uint64_t *part, uint32_t Q, uint32_t n_local, uint32_t di, uint32_t nd,
-                                                                   uint64_t *dst, uint64_t Gglobal)
-{
-    const uint32_t G = (n_local + 63) / 64;
-    // deposit masks by first position p0 < nd: bits p0, p0 + nd, ... below 64
-    std::vector<uint64_t> masks(nd, 0);
-    for (uint32_t p0 = 0; p0 < nd; ++p0)
-        for (uint32_t p = p0; p < 64; p += nd) masks[p0] |= 1ULL << p;
-    const uint64_t n_global = (uint64_t)(n_local - 1) * nd + di + 1;      // one past this shard's last global block
-    const uint64_t n_words = (n_global + 63) / 64;
-    // per output word: first local bit and first position (the same for every query)
-    std::vector<uint32_t> lo_of(n_words), p0_of(n_words);
-    for (uint64_t ow = 0; ow < n_words; ++ow) {
-        const uint64_t first = ow * 64;                                   // lo = ceil((first - di) / nd), clamped at 0
-        const uint64_t lo = first > di ? (first - di + nd - 1) / nd : 0;
-        lo_of[ow] = (uint32_t)lo;
-        p0_of[ow] = (uint32_t)(lo * nd + di - first);
-    }
-    for (uint32_t q = 0; q < Q; ++q) {
-        const uint64_t *row = part + (size_t)q * G;
-        uint64_t *o = dst + (size_t)q * Gglobal;
-        for (uint64_t ow = 0; ow < n_words; ++ow) {
-            const uint32_t lo = lo_of[ow], p0 = p0_of[ow];
-            if (lo >= n_local || p0 >= 64) continue;
-            const uint32_t wi = lo >> 6, sh = lo & 63u;
-            uint64_t src = row[wi] >> sh;
-            if (sh && wi + 1 < G) src |= row[wi + 1] << (64 - sh);       // (bits past n_local are zero in the survivors)
-            o[ow] |= __builtin_ia32_pdep_di(src, masks[p0]);
-        }
-    }
-}
-
-void interleave_shard(const uint64_t *part, uint32_t Q, uint32_t n_local, uint32_t di, uint32_t nd, uint64_t *dst, uint64_t Gglobal)
-{
-    if (n_local == 0) return;
-    static const bool has_bmi2 = __builtin_cpu_supports("bmi2");
-    if (has_bmi2 && nd <= 64) interleave_shard_pdep(part, Q, n_local, di, nd, dst, Gglobal);
-    else interleave_shard_loop(part, Q, n_local, di, nd, dst, Gglobal);
 }
 
 // Probes batch B against every arena of the list.  Per device the launches are software-pipelined on one in-order stream
@@ -671,16 +666,13 @@ int32_t probe_composite(bsg_ctx *ctx, const std::vector<std::shared_ptr<Arena>> 
                         uint64_t *out_survivors, uint64_t *out_dev)
 {
     const uint32_t n_arenas = (uint32_t)arenas.size();
-    // a composite batch: every run of queries probes on its own; its rows are scattered into the caller's layout
-    // (arena i: [n_queries][G_i], the runs' rows [q0, q0 + nq) of it) on the host
     if (out_dev) return fail(BSG_E_UNSUPPORTED, "a batch beyond one launch's limits cannot leave its survivors at a device pointer");
     if (!out_survivors) {
         for (auto &sub : B.subs) if (int32_t rc = probe_arenas(ctx, arenas, *sub, flags, nullptr, nullptr)) return rc;
         return BSG_OK;
     }
     if (flags & BSG_PROBE_ASYNC) return fail(BSG_E_UNSUPPORTED, "a batch beyond one launch's limits needs a synchronous probe");
-    std::vector<uint64_t> G(n_arenas), aoff(n_arenas + 1, 0);
-    for (uint32_t i = 0; i < n_arenas; ++i) { G[i] = ((uint64_t)arenas[i]->n_blocks + 63) / 64; aoff[i + 1] = aoff[i] + (uint64_t)B.n_queries * G[i]; }
+    const std::vector<uint64_t> aoff = bsh::survivor_offsets(n_arenas, B.n_queries, ArenaBlocks{arenas});
     std::vector<uint64_t> tmp;
     for (size_t si = 0; si < B.subs.size(); ++si) {
         const Batch &S = *B.subs[si];
@@ -688,45 +680,26 @@ int32_t probe_composite(bsg_ctx *ctx, const std::vector<std::shared_ptr<Arena>> 
         if (int32_t rc = probe_arenas(ctx, arenas, S, flags, tmp.data(), nullptr)) return rc;
         uint64_t o = 0;
         for (uint32_t i = 0; i < n_arenas; ++i) {
-            memcpy(out_survivors + aoff[i] + (uint64_t)B.sub_q0[si] * G[i], tmp.data() + o, (uint64_t)S.n_queries * G[i] * 8);
-            o += (uint64_t)S.n_queries * G[i];
+            const uint64_t G = bsh::words64(arenas[i]->n_blocks);
+            memcpy(out_survivors + aoff[i] + (uint64_t)B.sub_q0[si] * G, tmp.data() + o, (uint64_t)S.n_queries * G * 8);
+            o += (uint64_t)S.n_queries * G;
         }
     }
     return BSG_OK;
 }
 
-// bsg_probe_many_rows on a context of nd devices: device d writes the rows of ITS shards (local block numbers: local l of device d is
-// global block l * nd + d) into a slice of its own of the caller's page-locked buffers —
-//   headers: out_hdr + d * n_arenas * n_queries, [arena][query]
-//   rows   : out_rows + row_base[d], arena i's [n_queries][G(i, d)] slots back to back, G(i, d) = ceil(local blocks of (i, d) / 64)
-// (nd == 1: exactly the single-device layout).  bsg_survivor_rows_list merges a (arena, query)'s nd rows into global block order.
-struct RowsLayout {
-    uint32_t nd = 1, n_arenas = 0, n_queries = 0;
-    std::vector<uint64_t> row_base;                 // [nd + 1] first row word of device d's slice
-    std::vector<std::vector<uint64_t>> arena_off;   // [nd][n_arenas] arena i's rows inside device d's slice
-};
+// The layout of survivor rows (host/probe_plan.hpp) for these arenas on a context of nd devices.
+using bsh::RowsLayout;
 
 RowsLayout rows_layout(const std::vector<std::shared_ptr<Arena>> &arenas, uint32_t nd, uint32_t n_queries)
 {
-    RowsLayout L;
-    L.nd = nd; L.n_arenas = (uint32_t)arenas.size(); L.n_queries = n_queries;
-    L.row_base.assign(nd + 1, 0);
-    L.arena_off.assign(nd, std::vector<uint64_t>(arenas.size(), 0));
-    for (uint32_t d = 0; d < nd; ++d) {
-        uint64_t o = 0;
-        for (size_t i = 0; i < arenas.size(); ++i) {
-            L.arena_off[d][i] = o;
-            o += (uint64_t)n_queries * ((arenas[i]->shards[d].n_blocks + 63) / 64);
-        }
-        L.row_base[d + 1] = L.row_base[d] + o;
-    }
-    return L;
+    return bsh::rows_layout(nd, (uint32_t)arenas.size(), n_queries, [&arenas](uint32_t d, uint32_t i) { return arenas[i]->shards[d].n_blocks; });
 }
 
 // the device pointers behind the caller's page-locked row slots and headers (per device); every check first, then the headers of
 // shards without blocks (no launch ever touches them) are set to NONE
 int32_t rows_targets(bsg_ctx *ctx, const std::vector<std::shared_ptr<Arena>> &arenas, const Batch &B, uint64_t *out_survivors, uint64_t *out_dev,
-                     uint32_t *rows_hdr, const RowsLayout &L, std::vector<uint64_t *> &d_rows, std::vector<uint32_t *> &d_hdr, bool packed)
+                     uint32_t *rows_hdr, std::vector<uint64_t *> &d_rows, std::vector<uint32_t *> &d_hdr, bool packed)
 {
     const uint32_t nd = (uint32_t)ctx->devs.size();
     if (!B.subs.empty() || !out_survivors || out_dev)
@@ -751,267 +724,275 @@ int32_t rows_targets(bsg_ctx *ctx, const std::vector<std::shared_ptr<Arena>> &ar
     return BSG_OK;
 }
 
-// rows_hdr != nullptr (bsg_probe_many_rows): out_survivors and rows_hdr are PAGE-LOCKED host memory that
-// k_survivor_rows writes itself — a header per (arena, query) and, only where needed, block ids or words in the row's dense slot.
-int32_t probe_arenas(bsg_ctx *ctx, const std::vector<std::shared_ptr<Arena>> &arenas, const Batch &B, uint32_t flags,
-                     uint64_t *out_survivors, uint64_t *out_dev, uint32_t *rows_hdr)
-{
-    const uint32_t nd = (uint32_t)ctx->devs.size();
-    const uint32_t n_arenas = (uint32_t)arenas.size();
-    if (B.n_queries == 0 || n_arenas == 0) return BSG_OK;
+// One probe_arenas call: its arguments, what is decided once for all devices, and what the devices leave for the wait and the merge.
+struct ProbeCall {
+    bsg_ctx *ctx;
+    const std::vector<std::shared_ptr<Arena>> &arenas;
+    const Batch &B;
+    uint32_t flags;
+    uint64_t *out_survivors, *out_dev;
+    uint32_t *rows_hdr;            // != nullptr (bsg_probe_many_rows): out_survivors and rows_hdr are page-locked, written by the device
+    uint32_t nd, n_arenas;
+    bool timed, fuse, packed;
+    uint32_t fuse_max_arenas, limit;
+    std::vector<uint64_t> out_off;                 // arena i's survivors start at out_survivors + out_off[i]
+    RowsLayout RL;
     std::vector<uint64_t *> d_rows;
     std::vector<uint32_t *> d_hdr;
-    RowsLayout RL;
-    if (rows_hdr) {
-        if (flags & BSG_PROBE_ROWS_PACKED)
-            for (auto &a : arenas)
-                for (auto &sh : a->shards)
-                    if ((sh.n_blocks + 63) / 64 > bsg::kRowsStageG)
-                        return fail(BSG_E_UNSUPPORTED, "BSG_PROBE_ROWS_PACKED takes arenas of at most %u blocks per device (one of these holds %u)",
-                                    bsg::kRowsStageG * 64, sh.n_blocks);
-        RL = rows_layout(arenas, nd, B.n_queries);
-        if (int32_t rc = rows_targets(ctx, arenas, B, out_survivors, out_dev, rows_hdr, RL, d_rows, d_hdr, (flags & BSG_PROBE_ROWS_PACKED) != 0)) return rc;
-    } else if (flags & BSG_PROBE_ROWS_PACKED) {
-        return fail(BSG_E_INVALID, "BSG_PROBE_ROWS_PACKED is a flag of bsg_probe_many_rows");
+    std::vector<std::vector<uint64_t>> parts;      // several devices, host output: every device's shard bitsets land in a buffer of its own
+    std::vector<DirectResult> direct;              // k_probe_direct results waiting in page-locked buffers for the stream to drain
+};
+
+// the ways a group's survivors leave out[slot] once its evaluation is enqueued
+enum class SurvivorsOut { kStay, kRows, kInlineCopy, kCopyStream };
+
+// One device's part of a probe_arenas call, under the device's lock: its groups, where their survivors go and how, and the two
+// points of bookkeeping around every evaluation.
+struct DeviceRun {
+    ProbeCall &c;
+    Device &d;
+    const BatchDev &bd;
+    uint32_t di;
+    std::vector<Group> groups;
+    std::vector<uint64_t> goff;          // where each group's survivors go (u64 offset from host_base / out_dev)
+    uint64_t *host_base = nullptr;
+    SurvivorsOut way = SurvivorsOut::kStay;
+    std::vector<EventTriple> evs;        // per group; tflag: the group is timed
+    std::vector<uint8_t> tflag;
+
+    EventTriple *ev(size_t gi) { return tflag[gi] ? &evs[gi] : nullptr; }
+    bool fusable(size_t gi) const        // groups gi - 1 and gi in one k_probe_fused launch
+    {
+        return c.fuse && groups[gi].shards.size() <= c.fuse_max_arenas && groups[gi - 1].shards.size() <= c.fuse_max_arenas;
     }
-    if (!B.subs.empty()) return probe_composite(ctx, arenas, B, flags, out_survivors, out_dev);
-    const bool timed = flags & BSG_PROBE_TIMED;
-    // Fusing pays while a dispatch is short enough for its ramp + completion to matter (a few arenas); behind a large
-    // group the evaluation workgroups only take LDS and issue slots from the streaming (measured at 20-32 arenas of
-    // 35 MB per dispatch: fused 5.9 us per arena, k_probe_terms + k_eval_programs 5.2 + 1.0 us with the evaluation
-    // costing no HBM time of its own).
-    const bool fuse = !(flags & BSG_PROBE_NOFUSE) && !B.many_terms && B.n_kinds > 0 && 2 * bsg::eval_lds_bytes(B.max_cw, B.max_depth) <= 64 * 1024;
-    const uint32_t fuse_max_arenas = std::min(ctx->fuse_max_arenas, bsg::kMaxFusedArenas);
-    const uint32_t limit = std::max(1u, std::min(ctx->group_limit, bsg::kMaxExtGroupArenas));
-    std::vector<uint64_t> out_off(n_arenas + 1, 0);   // arena i's survivors start at out_survivors + out_off[i]
-    for (uint32_t i = 0; i < n_arenas; ++i)
-        out_off[i + 1] = out_off[i] + (uint64_t)B.n_queries * (((uint64_t)arenas[i]->n_blocks + 63) / 64);
-    // multi-device: every device's shard bitsets land in a host buffer of its own and are interleaved afterwards
-    std::vector<std::vector<uint64_t>> parts(nd > 1 && out_survivors && !rows_hdr ? nd : 0);
-    std::vector<std::vector<uint64_t>> part_off(parts.size());
-    struct DirectPending { uint64_t *buf; size_t cap; uint64_t *dst; size_t bytes; Device *dev; uint64_t *flag; uint64_t seq; };
-    std::vector<DirectPending> direct_pending;     // k_probe_direct results waiting in page-locked buffers for the stream to drain
-    struct DirectGuard {                           // the buffers go back to their device whatever way this call ends
-        std::vector<DirectPending> &v;
-        bool drained = false;                      // the kernels that write them are known to be over
-        ~DirectGuard()
-        {
-            for (auto &p : v) {
-                std::lock_guard<std::mutex> lk(p.dev->mu);
-                if (!drained) (void)hipStreamSynchronize(p.dev->stream);
-                p.dev->direct_bufs.emplace_back(p.buf, p.cap);
-            }
-        }
-    } direct_guard{direct_pending};
-    for (uint32_t di = 0; di < nd; ++di) {
-        Device &d = *ctx->devs[di];
-        const BatchDev &bd = B.dev[di];
-        std::lock_guard<std::mutex> lk(d.mu);
-        if (int32_t rc = use_device(d)) return rc;
-        // groups of this device
-        std::vector<Group> groups;
-        // (measured, round 5: a run of 129 .. 256 arenas as TWO kernel-argument groups instead of one group behind two
-        // k_write_arena_table dispatches loses — 200 shards of 125 blocks: probe 2 x 74.4 vs 139.4 us, evaluation 2 x 11.3 vs 18.3 us,
-        // 10.11 vs 9.62 us per step — the second ramp costs more than the two table writes: profiles/r05_step.txt)
-        for (uint32_t i = 0; i < n_arenas; ++i) {
-            const ArenaShard &s = arenas[i]->shards[di];
-            if (s.n_blocks == 0) continue;
-            // a group also closes on BYTES: its survivors (n_queries x 64-block groups x 8) and verdict words live in scratch that never
-            // shrinks, and one huge group is one copy behind one dispatch — nothing for the copy stream to overlap (ADVICE round 4)
-            const uint64_t G_add = (s.n_blocks + 63) / 64;
-            const bool full = !groups.empty() && !groups.back().shards.empty() &&
-                              ((groups.back().out_words + (uint64_t)B.n_queries * G_add) * 8 > kGroupScratchBudget ||
-                               (groups.back().v_words + G_add * std::max(B.Wt, 1u) * 64) * 8 > kGroupScratchBudget);
-            if (groups.empty() || groups.back().shards.size() >= limit || full) groups.push_back(Group{});
-            group_add(groups.back(), B, s, i);
-        }
-        if (groups.empty()) continue;
-        uint64_t *host_base = out_survivors;
-        std::vector<uint64_t> goff(groups.size() + 1, 0);   // where each group's survivors go (u64 offset)
-        if (!parts.empty()) {
-            uint64_t total = 0;
-            for (size_t gi = 0; gi < groups.size(); ++gi) { goff[gi] = total; total += groups[gi].out_words; }
-            goff[groups.size()] = total;
-            parts[di].resize(total);
-            part_off[di] = goff;
-            host_base = parts[di].data();
-        } else {
-            // single device: a group's arenas are consecutive in the caller's list unless empty arenas sit between
-            // them (those produce no words), so the group's words are contiguous at out_off[first arena of the group]
-            for (size_t gi = 0; gi < groups.size(); ++gi) goff[gi] = out_off[groups[gi].index[0]];
-        }
-        const bool want_copy = (out_survivors != nullptr || out_dev != nullptr) && !rows_hdr;
-        // latency path (a single interactive query): one group, a small synchronous result — the copy rides the compute
-        // stream, no cross-stream events
-        const bool inline_copy = want_copy && groups.size() == 1 && !(flags & BSG_PROBE_ASYNC) && groups[0].out_words * 8 <= (1u << 20);
-        if (want_copy && !inline_copy) HIP_TRY(ensure_copy_stream(d));
-        // one interactive query (a small synchronous batch with a few terms against one group): one dispatch, and the
-        // survivors are written straight into page-locked host memory — one launch and one wait instead of three enqueues
-        uint32_t real_terms = 0;
-        for (uint32_t y = 0; y < B.n_kinds; ++y) real_terms += B.term_count[y];
-        const bool direct = inline_copy && !(flags & BSG_PROBE_NOFUSE) && B.n_chunks == 1 && B.identity_cw && !B.many_terms &&
-                            groups[0].shards.size() <= bsg::kMaxGroupArenas && real_terms <= ctx->direct_max_terms && bsg::direct_lds_bytes(std::max(B.Wt, 1u), B.max_depth) <= 64 * 1024;
-        if (direct) {
-            EventTriple ev0;
-            const bool t0 = timed;
-            if (t0) if (int32_t rc = take_events(ctx, d, ev0)) return rc;
-            const uint64_t bytes = groups[0].out_words * 8;
-            uint64_t *target = out_dev ? out_dev + goff[0] : nullptr;
-            uint64_t *flag = nullptr;
-            if (!out_dev) {
-                DirectPending p{};
-                const size_t need = bytes + 64;                  // the doorbell word sits behind the survivors
-                for (size_t i = 0; i < d.direct_bufs.size(); ++i)
-                    if (d.direct_bufs[i].second >= need) { p.buf = d.direct_bufs[i].first; p.cap = d.direct_bufs[i].second; d.direct_bufs.erase(d.direct_bufs.begin() + i); break; }
-                if (!p.buf) {
-                    p.cap = std::max<size_t>(64 * 1024, need);
-                    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&p.buf), p.cap, hipHostMallocDefault));
-                }
-                if (!d.d_direct_count) {
-                    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_direct_count), 64));
-                    HIP_TRY(hipMemsetAsync(d.d_direct_count, 0, 64, d.stream));
-                }
-                p.dst = host_base + goff[0]; p.bytes = bytes; p.dev = &d;
-                p.flag = p.buf + (bytes + 7) / 8; p.seq = ++d.direct_seq;
-                *reinterpret_cast<volatile uint64_t *>(p.flag) = 0;
-                flag = p.flag;
-                direct_pending.push_back(p);
-                target = p.buf;
-            }
-            if (int32_t rc = enqueue_direct(d, groups[0], bd, B, target, flag, d.direct_seq, t0 ? &ev0 : nullptr, ctx->solo_ring_wgs)) return rc;
-            if (t0) d.pending.push_back(ev0);
-            continue;
-        }
-        std::vector<EventTriple> evs(groups.size());
-        std::vector<uint8_t> tflag(groups.size(), 0);
-        auto after_eval = [&](size_t gi, uint32_t slot) -> int32_t {   // bookkeeping once K2(gi) is enqueued
-            if (tflag[gi]) d.pending.push_back(evs[gi]);
-            if (rows_hdr) {
-                // the group's rows, tagged and compacted, straight into the caller's page-locked buffers (same stream: ordered
-                // behind the evaluation and ahead of the next use of out[slot])
-                const Group &g = groups[gi];
-                // (packed rows: byte headers — the device's slice starts at BYTE di * n_arenas * n_queries of the header buffer)
-                uint32_t *hdr_base = (flags & BSG_PROBE_ROWS_PACKED)
-                                         ? reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(d_hdr[di]) + (size_t)di * n_arenas * B.n_queries)
-                                         : d_hdr[di] + (size_t)di * n_arenas * B.n_queries;
-                bsg::RowsArgs ra{d.out[slot].p, d_rows[di] + RL.row_base[di], hdr_base, B.n_queries};
-                for (size_t i0 = 0; i0 < g.shards.size(); i0 += bsg::kMaxRowsArenas) {      // (two tables ride in the kernel arguments: runs of 64 arenas)
-                    const size_t n = std::min<size_t>(bsg::kMaxRowsArenas, g.shards.size() - i0);
-                    bsg::ArenaTable<bsg::kMaxRowsArenas> t;
-                    bsg::RowsTable<bsg::kMaxRowsArenas> dst;
-                    fill_refs(g, B, t.ar, i0, n);
-                    for (size_t i = 0; i < n; ++i) dst.d[i] = bsg::RowsDst{RL.arena_off[di][g.index[i0 + i]], (uint64_t)g.index[i0 + i] * B.n_queries};
-                    if (flags & BSG_PROBE_ROWS_PACKED)
-                        hipLaunchKernelGGL(bsg::k_survivor_rows_packed, dim3((B.n_queries + 255) / 256, (uint32_t)n), dim3(256), 0, d.stream, ra, t, dst);
-                    else
-                        hipLaunchKernelGGL(bsg::k_survivor_rows, dim3((B.n_queries + 255) / 256, (uint32_t)n), dim3(256), 0, d.stream, ra, t, dst);
-                    HIP_TRY(hipGetLastError());
-                }
-                return BSG_OK;
-            }
-            if (!want_copy) return BSG_OK;
-            const uint64_t bytes = groups[gi].out_words * 8;
-            if (inline_copy) {
-                HIP_TRY(hipMemcpyAsync(out_dev ? (void *)(out_dev + goff[gi]) : (void *)(host_base + goff[gi]), d.out[slot].p, bytes,
-                                       out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, d.stream));
-                return BSG_OK;
-            }
-            HIP_TRY(hipEventRecord(d.ev_eval[slot], d.stream));
-            HIP_TRY(hipStreamWaitEvent(d.copy_stream, d.ev_eval[slot], 0));
-            if (out_dev) HIP_TRY(hipMemcpyAsync(out_dev + goff[gi], d.out[slot].p, bytes, hipMemcpyDeviceToDevice, d.copy_stream));
-            else HIP_TRY(hipMemcpyAsync(host_base + goff[gi], d.out[slot].p, bytes, hipMemcpyDeviceToHost, d.copy_stream));
-            HIP_TRY(hipEventRecord(d.ev_copy[slot], d.copy_stream));
-            d.copy_busy[slot] = true;
-            return BSG_OK;
-        };
-        auto before_eval = [&](uint32_t slot) -> int32_t {           // out[slot] is about to be overwritten
-            if (d.copy_busy[slot]) { HIP_TRY(hipStreamWaitEvent(d.stream, d.ev_copy[slot], 0)); d.copy_busy[slot] = false; }
-            return BSG_OK;
-        };
-        bool fold = fold_applies(ctx, B, flags);
-        for (const Group &g : groups) fold = fold && g.shards.size() <= bsg::kMaxGroupArenas;     // (k_probe_eval keeps its records in the kernel arguments)
-        // A short run — ONE group, survivors left on the device — ends in a serial tail: the whole group's program evaluation behind
-        // its stream (11 of 132 us at 20 arenas of C2).  tail_split (bsg_set_lab key 19, percent) cuts the group in two dispatches'
-        // worth: the first part's evaluation runs on a second stream while the second part streams, and only the second part's
-        // evaluation is left behind the stream.
-        bool split = false;
-        if (ctx->tail_split_pct && groups.size() == 1 && !want_copy && !rows_hdr && !fold && groups[0].shards.size() >= 8 &&
-            groups[0].shards.size() <= bsg::kMaxGroupArenas) {
-            const Group whole = groups[0];
-            const size_t n0 = std::min(whole.shards.size() - 1, std::max<size_t>(1, whole.shards.size() * ctx->tail_split_pct / 100));
+    int32_t plan();
+    bool direct_applies() const;
+    int32_t direct();
+    int32_t pipeline();
+    int32_t before_eval(uint32_t slot);
+    int32_t after_eval(size_t gi, uint32_t slot);
+    int32_t rows_out(size_t gi, uint32_t slot);
+    int32_t inline_copy_out(size_t gi, uint32_t slot);
+    int32_t copy_stream_out(size_t gi, uint32_t slot);
+};
+
+// The groups of this device (host/probe_plan.hpp), their output offsets and the way out of their survivors.
+// (measured, round 5: a run of 129 .. 256 arenas as TWO kernel-argument groups instead of one group behind two
+// k_write_arena_table dispatches loses — 200 shards of 125 blocks: probe 2 x 74.4 vs 139.4 us, evaluation 2 x 11.3 vs 18.3 us,
+// 10.11 vs 9.62 us per step — the second ramp costs more than the two table writes: profiles/r05_step.txt)
+int32_t DeviceRun::plan()
+{
+    groups = bsh::plan_groups<Group>(c.n_arenas, ShardBlocks{c.arenas, di}, c.B.n_queries, c.B.Wt, c.limit);
+    for (Group &g : groups) {
+        g.shards.reserve(g.index.size());
+        for (uint32_t i : g.index) g.shards.push_back(&c.arenas[i]->shards[di]);
+    }
+    if (groups.empty()) return BSG_OK;
+    if (!c.parts.empty()) {
+        goff = bsh::group_offsets(groups, nullptr);
+        c.parts[di].resize(goff.back());
+        host_base = c.parts[di].data();
+    } else {
+        goff = bsh::group_offsets(groups, c.out_off.data());
+        host_base = c.out_survivors;
+    }
+    // latency path (a single interactive query): one group, a small synchronous result — the copy rides the compute
+    // stream, no cross-stream events
+    if (c.rows_hdr) way = SurvivorsOut::kRows;
+    else if (!c.out_survivors && !c.out_dev) way = SurvivorsOut::kStay;
+    else if (groups.size() == 1 && !(c.flags & BSG_PROBE_ASYNC) && groups[0].out_words * 8 <= (1u << 20)) way = SurvivorsOut::kInlineCopy;
+    else way = SurvivorsOut::kCopyStream;
+    if (way == SurvivorsOut::kCopyStream) HIP_TRY(ensure_copy_stream(d));
+    return BSG_OK;
+}
+
+// one interactive query (a small synchronous batch with a few terms against one group): one dispatch, and the
+// survivors are written straight into page-locked host memory — one launch and one wait instead of three enqueues
+bool DeviceRun::direct_applies() const
+{
+    const Batch &B = c.B;
+    uint32_t real_terms = 0;
+    for (uint32_t y = 0; y < B.n_kinds; ++y) real_terms += B.term_count[y];
+    return way == SurvivorsOut::kInlineCopy && !(c.flags & BSG_PROBE_NOFUSE) && B.n_chunks == 1 && B.identity_cw && !B.many_terms &&
+           groups[0].shards.size() <= bsg::kMaxGroupArenas && real_terms <= c.ctx->direct_max_terms &&
+           bsg::direct_lds_bytes(std::max(B.Wt, 1u), B.max_depth) <= 64 * 1024;
+}
+
+int32_t DeviceRun::direct()
+{
+    EventTriple ev0;
+    if (c.timed) if (int32_t rc = take_events(c.ctx, d, ev0)) return rc;
+    uint64_t *target = c.out_dev ? c.out_dev + goff[0] : nullptr;
+    const DirectResult *res = nullptr;
+    if (!c.out_dev) {
+        c.direct.emplace_back();
+        if (int32_t rc = c.direct.back().take(d, di, groups[0].out_words * 8)) return rc;
+        c.direct.back().dst = host_base + goff[0];
+        res = &c.direct.back();
+        target = res->buf;
+    }
+    if (int32_t rc = enqueue_direct(d, groups[0], bd, c.B, target, res, c.timed ? &ev0 : nullptr, c.ctx->solo_ring_wgs)) return rc;
+    if (c.timed) d.pending.push_back(ev0);
+    return BSG_OK;
+}
+
+// out[slot] is about to be overwritten
+int32_t DeviceRun::before_eval(uint32_t slot)
+{
+    if (d.copy_busy[slot]) { HIP_TRY(hipStreamWaitEvent(d.stream, d.ev_copy[slot], 0)); d.copy_busy[slot] = false; }
+    return BSG_OK;
+}
+
+// K2 of group gi is enqueued: its timing triple is complete, its survivors leave
+int32_t DeviceRun::after_eval(size_t gi, uint32_t slot)
+{
+    if (tflag[gi]) d.pending.push_back(evs[gi]);
+    switch (way) {
+    case SurvivorsOut::kRows: return rows_out(gi, slot);
+    case SurvivorsOut::kInlineCopy: return inline_copy_out(gi, slot);
+    case SurvivorsOut::kCopyStream: return copy_stream_out(gi, slot);
+    case SurvivorsOut::kStay: break;
+    }
+    return BSG_OK;
+}
+
+// the group's rows, tagged and compacted, straight into the caller's page-locked buffers (same stream: ordered
+// behind the evaluation and ahead of the next use of out[slot])
+int32_t DeviceRun::rows_out(size_t gi, uint32_t slot)
+{
+    const Group &g = groups[gi];
+    const uint32_t Q = c.B.n_queries;
+    // (packed rows: byte headers — the device's slice starts at BYTE di * n_arenas * n_queries of the header buffer)
+    uint32_t *hdr_base = c.packed ? reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(c.d_hdr[di]) + (size_t)di * c.n_arenas * Q)
+                                  : c.d_hdr[di] + (size_t)di * c.n_arenas * Q;
+    bsg::RowsArgs ra{d.out[slot].p, c.d_rows[di] + c.RL.row_base[di], hdr_base, Q};
+    for (size_t i0 = 0; i0 < g.shards.size(); i0 += bsg::kMaxRowsArenas) {      // (two tables ride in the kernel arguments: runs of 64 arenas)
+        const size_t n = std::min<size_t>(bsg::kMaxRowsArenas, g.shards.size() - i0);
+        bsg::ArenaTable<bsg::kMaxRowsArenas> t;
+        bsg::RowsTable<bsg::kMaxRowsArenas> dst;
+        fill_refs(g, t.ar, i0, n);
+        for (size_t i = 0; i < n; ++i) dst.d[i] = bsg::RowsDst{c.RL.arena_off[di][g.index[i0 + i]], (uint64_t)g.index[i0 + i] * Q};
+        if (c.packed) hipLaunchKernelGGL(bsg::k_survivor_rows_packed, dim3((Q + 255) / 256, (uint32_t)n), dim3(256), 0, d.stream, ra, t, dst);
+        else hipLaunchKernelGGL(bsg::k_survivor_rows, dim3((Q + 255) / 256, (uint32_t)n), dim3(256), 0, d.stream, ra, t, dst);
+        HIP_TRY(hipGetLastError());
+    }
+    return BSG_OK;
+}
+
+int32_t DeviceRun::inline_copy_out(size_t gi, uint32_t slot)
+{
+    HIP_TRY(hipMemcpyAsync(c.out_dev ? (void *)(c.out_dev + goff[gi]) : (void *)(host_base + goff[gi]), d.out[slot].p, groups[gi].out_words * 8,
+                           c.out_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, d.stream));
+    return BSG_OK;
+}
+
+int32_t DeviceRun::copy_stream_out(size_t gi, uint32_t slot)
+{
+    const uint64_t bytes = groups[gi].out_words * 8;
+    HIP_TRY(hipEventRecord(d.ev_eval[slot], d.stream));
+    HIP_TRY(hipStreamWaitEvent(d.copy_stream, d.ev_eval[slot], 0));
+    if (c.out_dev) HIP_TRY(hipMemcpyAsync(c.out_dev + goff[gi], d.out[slot].p, bytes, hipMemcpyDeviceToDevice, d.copy_stream));
+    else HIP_TRY(hipMemcpyAsync(host_base + goff[gi], d.out[slot].p, bytes, hipMemcpyDeviceToHost, d.copy_stream));
+    HIP_TRY(hipEventRecord(d.ev_copy[slot], d.copy_stream));
+    d.copy_busy[slot] = true;
+    return BSG_OK;
+}
+
+// The software pipeline over the groups; per group one of four arms: folded (one dispatch per group), fused with the evaluation of
+// the group before, or the two kernels — the evaluation of the group before on the device's stream, or (tail split) on a second one.
+int32_t DeviceRun::pipeline()
+{
+    bsg_ctx *ctx = c.ctx;
+    const Batch &B = c.B;
+    bool fold = fold_applies(ctx, B, c.flags);
+    for (const Group &g : groups) fold = fold && g.shards.size() <= bsg::kMaxGroupArenas;     // (k_probe_eval keeps its records in the kernel arguments)
+    // A short run — ONE group, survivors left on the device — ends in a serial tail: the whole group's program evaluation behind
+    // its stream (11 of 132 us at 20 arenas of C2).  tail_split (bsg_set_lab key 19, percent) cuts the group in two dispatches'
+    // worth: the first part's evaluation runs on a second stream while the second part streams, and only the second part's
+    // evaluation is left behind the stream.  Two groups that fuse are left to the fused launch.
+    const bool tail_mode = ctx->tail_split_pct && way == SurvivorsOut::kStay && !fold;
+    if (tail_mode && groups.size() == 1)
+        if (const size_t n0 = bsh::tail_split_cut(groups[0].shards.size(), ctx->tail_split_pct, bsg::kMaxGroupArenas)) {
+            const Group whole = std::move(groups[0]);
             groups.assign(2, Group{});
-            for (size_t i = 0; i < whole.shards.size(); ++i) group_add(groups[i < n0 ? 0 : 1], B, *whole.shards[i], whole.index[i]);
+            for (size_t i = 0; i < whole.shards.size(); ++i) group_add(groups[i < n0 ? 0 : 1], B.n_queries, B.Wt, *whole.shards[i], whole.index[i]);
             goff.assign(3, 0);
-            evs.resize(2); tflag.assign(2, 0);
         }
-        if (ctx->tail_split_pct && groups.size() == 2 && !want_copy && !rows_hdr && !fold &&
-            !(fuse && groups[0].shards.size() <= fuse_max_arenas && groups[1].shards.size() <= fuse_max_arenas)) {
-            if (!d.aux_stream) {
-                HIP_TRY(hipStreamCreateWithFlags(&d.aux_stream, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&d.ev_aux[0], hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&d.ev_aux[1], hipEventDisableTiming));
-            }
-            split = true;
-        }
-        for (size_t gi = 0; gi < groups.size(); ++gi) {
-            const uint32_t slot = (uint32_t)(gi & 1);
-            tflag[gi] = timed && (ctx->timed_stride <= 1 || (ctx->timed_counter++ % ctx->timed_stride) == ctx->timed_stride / 2);
-            if (tflag[gi]) if (int32_t rc = take_events(ctx, d, evs[gi])) return rc;
-            EventTriple *ev = tflag[gi] ? &evs[gi] : nullptr;
-            if (fold) {
-                // one dispatch per group: the survivors of group gi are complete when its kernel is
-                if (int32_t rc = before_eval(slot)) return rc;
-                if (int32_t rc = enqueue_fold(ctx, d, groups[gi], bd, B, slot, ev)) return rc;
-                if (int32_t rc = after_eval(gi, slot)) return rc;
-                continue;
-            }
-            if (gi > 0 && fuse && groups[gi].shards.size() <= fuse_max_arenas && groups[gi - 1].shards.size() <= fuse_max_arenas) {
-                // a fused launch's own timestamps cover the streaming of group gi AND the evaluation of group gi-1
-                if (int32_t rc = before_eval(slot ^ 1)) return rc;
-                if (int32_t rc = enqueue_fused(ctx, d, groups[gi], slot, groups[gi - 1], slot ^ 1, bd, B, ev)) return rc;
-                if (int32_t rc = after_eval(gi - 1, slot ^ 1)) return rc;
-            } else {
-                if (gi > 0) {
-                    if (int32_t rc = before_eval(slot ^ 1)) return rc;
-                    if (split) {
-                        // the evaluation of the first part: on the second stream, behind the first part's probe, beside the second part's
-                        HIP_TRY(hipEventRecord(d.ev_aux[0], d.stream));
-                        HIP_TRY(hipStreamWaitEvent(d.aux_stream, d.ev_aux[0], 0));
-                        if (int32_t rc = enqueue_eval(d, groups[gi - 1], bd, B, slot ^ 1, tflag[gi - 1] ? &evs[gi - 1] : nullptr, nullptr, d.aux_stream)) return rc;
-                        HIP_TRY(hipEventRecord(d.ev_aux[1], d.aux_stream));
-                    } else if (int32_t rc = enqueue_eval(d, groups[gi - 1], bd, B, slot ^ 1, tflag[gi - 1] ? &evs[gi - 1] : nullptr)) return rc;
-                    if (int32_t rc = after_eval(gi - 1, slot ^ 1)) return rc;
-                }
-                if (int32_t rc = enqueue_terms(ctx, d, groups[gi], bd, B, slot, ev)) return rc;
-                if (split && gi > 0) HIP_TRY(hipStreamWaitEvent(d.stream, d.ev_aux[1], 0));      // the stream's end is the call's end: it joins the second stream
-            }
-        }
-        if (!fold) {
-            const size_t gl = groups.size() - 1;
-            const uint32_t slot = (uint32_t)(gl & 1);
+    const bool split = tail_mode && groups.size() == 2 && !fusable(1);
+    if (split && !d.aux_stream) {
+        HIP_TRY(hipStreamCreateWithFlags(&d.aux_stream, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&d.ev_aux[0], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&d.ev_aux[1], hipEventDisableTiming));
+    }
+    evs.resize(groups.size());
+    tflag.assign(groups.size(), 0);
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const uint32_t slot = (uint32_t)(gi & 1);
+        tflag[gi] = c.timed && (ctx->timed_stride <= 1 || (ctx->timed_counter++ % ctx->timed_stride) == ctx->timed_stride / 2);
+        if (tflag[gi]) if (int32_t rc = take_events(ctx, d, evs[gi])) return rc;
+        if (fold) {
+            // one dispatch per group: the survivors of group gi are complete when its kernel is
             if (int32_t rc = before_eval(slot)) return rc;
-            if (int32_t rc = enqueue_eval(d, groups[gl], bd, B, slot, tflag[gl] ? &evs[gl] : nullptr)) return rc;
-            if (int32_t rc = after_eval(gl, slot)) return rc;
+            if (int32_t rc = enqueue_fold(ctx, d, groups[gi], bd, B, slot, ev(gi))) return rc;
+            if (int32_t rc = after_eval(gi, slot)) return rc;
+        } else if (gi > 0 && fusable(gi)) {
+            // a fused launch's own timestamps cover the streaming of group gi AND the evaluation of group gi-1
+            if (int32_t rc = before_eval(slot ^ 1)) return rc;
+            if (int32_t rc = enqueue_fused(ctx, d, groups[gi], slot, groups[gi - 1], slot ^ 1, bd, B, ev(gi))) return rc;
+            if (int32_t rc = after_eval(gi - 1, slot ^ 1)) return rc;
+        } else if (gi > 0 && split) {
+            // the evaluation of the first part: on the second stream, behind the first part's probe, beside the second part's
+            if (int32_t rc = before_eval(slot ^ 1)) return rc;
+            HIP_TRY(hipEventRecord(d.ev_aux[0], d.stream));
+            HIP_TRY(hipStreamWaitEvent(d.aux_stream, d.ev_aux[0], 0));
+            if (int32_t rc = enqueue_eval(d, groups[gi - 1], bd, B, slot ^ 1, ev(gi - 1), nullptr, d.aux_stream)) return rc;
+            HIP_TRY(hipEventRecord(d.ev_aux[1], d.aux_stream));
+            if (int32_t rc = after_eval(gi - 1, slot ^ 1)) return rc;
+            if (int32_t rc = enqueue_terms(ctx, d, groups[gi], bd, B, slot, ev(gi))) return rc;
+            HIP_TRY(hipStreamWaitEvent(d.stream, d.ev_aux[1], 0));      // the stream's end is the call's end: it joins the second stream
+        } else {
+            if (gi > 0) {
+                if (int32_t rc = before_eval(slot ^ 1)) return rc;
+                if (int32_t rc = enqueue_eval(d, groups[gi - 1], bd, B, slot ^ 1, ev(gi - 1))) return rc;
+                if (int32_t rc = after_eval(gi - 1, slot ^ 1)) return rc;
+            }
+            if (int32_t rc = enqueue_terms(ctx, d, groups[gi], bd, B, slot, ev(gi))) return rc;
         }
     }
-    if (flags & BSG_PROBE_ASYNC) return BSG_OK;
-    // k_probe_direct rings a doorbell in page-locked memory when its last workgroup is done: reading our own memory is
-    // cheaper than asking the runtime.  Completion is tracked PER DEVICE: eligibility for the one-dispatch path is decided
-    // per device (one group, a small result), so on a context over several devices some shards may have gone direct and
-    // others through the streaming kernels + an asynchronous copy — a device is only excused from the stream wait when
-    // every doorbell it owes has rung (a bell that stays silent for a millisecond falls back to the wait as well).
-    std::vector<uint8_t> rang(nd, 0);
-    for (auto &p : direct_pending) {
-        uint32_t di = 0;
-        while (di < nd && ctx->devs[di].get() != p.dev) ++di;
-        const auto t0 = std::chrono::steady_clock::now();
-        bool ok = true;
-        while (__atomic_load_n(p.flag, __ATOMIC_ACQUIRE) != p.seq) {
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(1000)) { ok = false; break; }
-        }
-        if (di < nd) rang[di] = ok ? std::max<uint8_t>(rang[di], 1) : 2;     // 2: a bell of this device stayed silent
+    if (!fold) {
+        const size_t gl = groups.size() - 1;
+        const uint32_t slot = (uint32_t)(gl & 1);
+        if (int32_t rc = before_eval(slot)) return rc;
+        if (int32_t rc = enqueue_eval(d, groups[gl], bd, B, slot, ev(gl))) return rc;
+        if (int32_t rc = after_eval(gl, slot)) return rc;
     }
-    for (uint32_t di = 0; di < nd; ++di) {
+    return BSG_OK;
+}
+
+// everything device di owes the call, enqueued under its lock
+int32_t enqueue_device(ProbeCall &c, uint32_t di)
+{
+    Device &d = *c.ctx->devs[di];
+    std::lock_guard<std::mutex> lk(d.mu);
+    if (int32_t rc = use_device(d)) return rc;
+    DeviceRun r{c, d, c.B.dev[di], di};
+    if (int32_t rc = r.plan()) return rc;
+    if (r.groups.empty()) return BSG_OK;
+    return r.direct_applies() ? r.direct() : r.pipeline();
+}
+
+// k_probe_direct rings a doorbell in page-locked memory when its last workgroup is done: reading our own memory is
+// cheaper than asking the runtime.  Completion is tracked PER DEVICE: eligibility for the one-dispatch path is decided
+// per device (one group, a small result), so on a context over several devices some shards may have gone direct and
+// others through the streaming kernels + an asynchronous copy — a device is only excused from the stream wait when
+// every doorbell it owes has rung (a bell that stays silent for a millisecond falls back to the wait as well).
+int32_t wait_devices(ProbeCall &c)
+{
+    bsg_ctx *ctx = c.ctx;
+    std::vector<uint8_t> rang(c.nd, 0);
+    for (const DirectResult &p : c.direct)
+        rang[p.di] = p.wait(std::chrono::microseconds(1000)) ? std::max<uint8_t>(rang[p.di], 1) : 2;     // 2: a bell of this device stayed silent
+    for (uint32_t di = 0; di < c.nd; ++di) {
         if (rang[di] == 1) continue;                                          // every result of this device is in host memory
         Device &d = *ctx->devs[di];
         std::lock_guard<std::mutex> lk(d.mu);
@@ -1025,21 +1006,51 @@ int32_t probe_arenas(bsg_ctx *ctx, const std::vector<std::shared_ptr<Arena>> &ar
         if (d.copy_stream) HIP_TRY(hipStreamSynchronize(d.copy_stream));
         d.copy_busy[0] = d.copy_busy[1] = false;
     }
-    for (auto &p : direct_pending) memcpy(p.dst, p.buf, p.bytes);
-    direct_guard.drained = true;                   // the doorbell rang, or the stream was waited for
-    if (!parts.empty()) {
-        memset(out_survivors, 0, out_off[n_arenas] * 8);
-        for (uint32_t di = 0; di < nd; ++di) {
-            uint64_t o = 0;
-            for (uint32_t i = 0; i < n_arenas; ++i) {
-                const ArenaShard &s = arenas[i]->shards[di];
-                if (s.n_blocks == 0) continue;
-                const uint32_t G = (s.n_blocks + 63) / 64;
-                interleave_shard(parts[di].data() + o, B.n_queries, s.n_blocks, di, nd, out_survivors + out_off[i],
-                                 ((uint64_t)arenas[i]->n_blocks + 63) / 64);
-                o += (uint64_t)B.n_queries * G;
-            }
-        }
+    return BSG_OK;
+}
+
+int32_t probe_arenas(bsg_ctx *ctx, const std::vector<std::shared_ptr<Arena>> &arenas, const Batch &B, uint32_t flags,
+                     uint64_t *out_survivors, uint64_t *out_dev, uint32_t *rows_hdr)
+{
+    const uint32_t nd = (uint32_t)ctx->devs.size();
+    const uint32_t n_arenas = (uint32_t)arenas.size();
+    if (B.n_queries == 0 || n_arenas == 0) return BSG_OK;
+    ProbeCall c{ctx, arenas, B, flags, out_survivors, out_dev, rows_hdr, nd, n_arenas};
+    c.packed = (flags & BSG_PROBE_ROWS_PACKED) != 0;
+    if (rows_hdr) {
+        if (c.packed)
+            for (auto &a : arenas)
+                for (auto &sh : a->shards)
+                    if ((sh.n_blocks + 63) / 64 > bsg::kRowsStageG)
+                        return fail(BSG_E_UNSUPPORTED, "BSG_PROBE_ROWS_PACKED takes arenas of at most %u blocks per device (one of these holds %u)",
+                                    bsg::kRowsStageG * 64, sh.n_blocks);
+        c.RL = rows_layout(arenas, nd, B.n_queries);
+        if (int32_t rc = rows_targets(ctx, arenas, B, out_survivors, out_dev, rows_hdr, c.d_rows, c.d_hdr, c.packed)) return rc;
+    } else if (c.packed) {
+        return fail(BSG_E_INVALID, "BSG_PROBE_ROWS_PACKED is a flag of bsg_probe_many_rows");
+    }
+    if (!B.subs.empty()) return probe_composite(ctx, arenas, B, flags, out_survivors, out_dev);
+    c.timed = flags & BSG_PROBE_TIMED;
+    // Fusing pays while a dispatch is short enough for its ramp + completion to matter (a few arenas); behind a large
+    // group the evaluation workgroups only take LDS and issue slots from the streaming (measured at 20-32 arenas of
+    // 35 MB per dispatch: fused 5.9 us per arena, k_probe_terms + k_eval_programs 5.2 + 1.0 us with the evaluation
+    // costing no HBM time of its own).
+    c.fuse = !(flags & BSG_PROBE_NOFUSE) && !B.many_terms && B.n_kinds > 0 && 2 * bsg::eval_lds_bytes(B.max_cw, B.max_depth) <= 64 * 1024;
+    c.fuse_max_arenas = std::min(ctx->fuse_max_arenas, bsg::kMaxFusedArenas);
+    c.limit = std::max(1u, std::min(ctx->group_limit, bsg::kMaxExtGroupArenas));
+    c.out_off = bsh::survivor_offsets(n_arenas, B.n_queries, ArenaBlocks{arenas});
+    c.parts.resize(nd > 1 && out_survivors && !rows_hdr ? nd : 0);
+    for (uint32_t di = 0; di < nd; ++di) if (int32_t rc = enqueue_device(c, di)) return rc;      // every device before any wait
+    if (flags & BSG_PROBE_ASYNC) return BSG_OK;
+    if (int32_t rc = wait_devices(c)) return rc;
+    for (DirectResult &p : c.direct) {
+        memcpy(p.dst, p.buf, p.bytes);
+        p.drained = true;                          // the doorbell rang, or the stream was waited for
+    }
+    if (!c.parts.empty()) {
+        memset(out_survivors, 0, c.out_off[n_arenas] * 8);
+        for (uint32_t di = 0; di < nd; ++di)
+            bsh::merge_device_part(c.parts[di].data(), n_arenas, ShardBlocks{arenas, di}, ArenaBlocks{arenas}, B.n_queries, di, nd, out_survivors, c.out_off.data());
     }
     return BSG_OK;
 }
@@ -1399,7 +1410,6 @@ int32_t query_solo(bsg_ctx *ctx, const std::vector<std::shared_ptr<Arena>> &aren
         if (n > bsg::kQueryMaxArenas) fast = false;
     }
     bsg::QueryKernArgs q{};
-    Batch B;                                            // host-only stand-in: geometry for fill_refs, nothing on a device
     const uint32_t max_depth = cq->max_depth;
     if (fast) {
         q.a.n_kinds = cq->n_kinds;
@@ -1408,7 +1418,6 @@ int32_t query_solo(bsg_ctx *ctx, const std::vector<std::shared_ptr<Arena>> &aren
         memcpy(q.prog, cq->prog, sizeof q.prog);
         q.len = cq->len; q.stride = n_queries;
         q.a.Tp = bsg::kQueryMaxTerms; q.a.Wt = 1; q.a.n_queries = n_queries; q.a.Lmax = cq->len; q.a.max_depth = max_depth;
-        B.n_queries = n_queries; B.Wt = 1;
     }
     if (!fast) {                                        // a larger batch: the batch object after all (hashes still from the host)
         uint64_t bid = 0;
@@ -1422,37 +1431,17 @@ int32_t query_solo(bsg_ctx *ctx, const std::vector<std::shared_ptr<Arena>> &aren
         return rc;
     }
     // ---- one k_query_direct per device that holds blocks; survivors land in page-locked memory, a doorbell says when ----
-    std::vector<uint64_t> out_off(n_arenas + 1, 0);
-    for (uint32_t i = 0; i < n_arenas; ++i) out_off[i + 1] = out_off[i] + (uint64_t)n_queries * (((uint64_t)arenas[i]->n_blocks + 63) / 64);
-    struct Pending { uint64_t *buf; size_t cap; size_t words; Device *dev; uint64_t *flag; uint64_t seq; uint32_t di; };
-    std::vector<Pending> pend;
-    struct Guard {
-        std::vector<Pending> &v; bool drained = false;
-        ~Guard() { for (auto &p : v) { std::lock_guard<std::mutex> lk(p.dev->mu); if (!drained) (void)hipStreamSynchronize(p.dev->stream); p.dev->direct_bufs.emplace_back(p.buf, p.cap); } }
-    } guard{pend};
+    std::vector<DirectResult> pend;
     for (uint32_t di = 0; di < nd; ++di) {
         Device &d = *ctx->devs[di];
         Group g;
-        for (uint32_t i = 0; i < n_arenas; ++i) if (arenas[i]->shards[di].n_blocks) group_add(g, B, arenas[i]->shards[di], i);
+        for (uint32_t i = 0; i < n_arenas; ++i) if (arenas[i]->shards[di].n_blocks) group_add(g, n_queries, 1, arenas[i]->shards[di], i);
         if (g.shards.empty()) continue;
         std::lock_guard<std::mutex> lk(d.mu);
         if (int32_t rc = use_device(d)) return rc;
-        Pending p{};
-        const size_t bytes = g.out_words * 8, need = bytes + 64;
-        for (size_t i = 0; i < d.direct_bufs.size(); ++i)
-            if (d.direct_bufs[i].second >= need) { p.buf = d.direct_bufs[i].first; p.cap = d.direct_bufs[i].second; d.direct_bufs.erase(d.direct_bufs.begin() + i); break; }
-        if (!p.buf) {
-            p.cap = std::max<size_t>(64 * 1024, need);
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&p.buf), p.cap, hipHostMallocDefault));
-        }
-        p.words = g.out_words; p.dev = &d; p.di = di;
-        p.flag = p.buf + g.out_words; p.seq = ++d.direct_seq;
-        *reinterpret_cast<volatile uint64_t *>(p.flag) = 0;
-        pend.push_back(p);
-        if (!d.d_direct_count) {
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_direct_count), 64));
-            HIP_TRY(hipMemsetAsync(d.d_direct_count, 0, 64, d.stream));
-        }
+        pend.emplace_back();
+        DirectResult &p = pend.back();
+        if (int32_t rc = p.take(d, di, g.out_words * 8)) return rc;
         bsg::QueryKernArgs k = q;
         k.a.n_arenas = (uint32_t)g.shards.size();
         // the kernel's own doorbell costs every workgroup a system-scope fence, and those serialise: beyond a few dozen workgroups
@@ -1460,38 +1449,27 @@ int32_t query_solo(bsg_ctx *ctx, const std::vector<std::shared_ptr<Arena>> &aren
         const bool ring = (uint64_t)g.max_G * k.a.n_arenas > ctx->solo_ring_wgs;
         k.a.out = p.buf;
         if (!ring) { k.a.done_count = d.d_direct_count; k.a.flag = p.flag; k.a.seq = p.seq; }
-        fill_refs(g, B, k.t.ar);
+        fill_refs(g, k.t.ar);
         hipLaunchKernelGGL(bsg::k_query_direct, dim3(g.max_G, 1, k.a.n_arenas), dim3(bsg::kEvalThreads), bsg::direct_lds_bytes(1, max_depth), d.stream, k);
         HIP_TRY(hipGetLastError());
         if (ring) if (int32_t rc = ring_doorbell(d, p.flag, p.seq)) return rc;
     }
-    for (auto &p : pend) {
-        const auto t0 = std::chrono::steady_clock::now();
-        bool ok = true;
-        while (__atomic_load_n(p.flag, __ATOMIC_ACQUIRE) != p.seq)
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(1000)) { ok = false; break; }
-        if (!ok) {                                      // the bell did not ring within a millisecond: ask the runtime
+    for (DirectResult &p : pend)
+        if (!p.wait(std::chrono::microseconds(1000))) {     // the bell did not ring within a millisecond: ask the runtime, on this buffer's device only
             std::lock_guard<std::mutex> lk(p.dev->mu);
             if (int32_t rc = use_device(*p.dev)) return rc;
             HIP_TRY(hipStreamSynchronize(p.dev->stream));
         }
-    }
-    guard.drained = true;
+    for (DirectResult &p : pend) p.drained = true;
     if (nd == 1) {
         // one device: a group's arenas are the caller's non-empty arenas in order, their words back to back — as out_survivors wants them
-        if (!pend.empty()) memcpy(out_survivors, pend[0].buf, pend[0].words * 8);
+        if (!pend.empty()) memcpy(out_survivors, pend[0].buf, pend[0].bytes);
         return BSG_OK;
     }
+    const std::vector<uint64_t> out_off = bsh::survivor_offsets(n_arenas, n_queries, ArenaBlocks{arenas});
     memset(out_survivors, 0, out_off[n_arenas] * 8);
-    for (auto &p : pend) {
-        uint64_t o = 0;
-        for (uint32_t i = 0; i < n_arenas; ++i) {
-            const ArenaShard &s = arenas[i]->shards[p.di];
-            if (s.n_blocks == 0) continue;
-            interleave_shard(p.buf + o, n_queries, s.n_blocks, p.di, nd, out_survivors + out_off[i], ((uint64_t)arenas[i]->n_blocks + 63) / 64);
-            o += (uint64_t)n_queries * ((s.n_blocks + 63) / 64);
-        }
-    }
+    for (const DirectResult &p : pend)
+        bsh::merge_device_part(p.buf, n_arenas, ShardBlocks{arenas, p.di}, ArenaBlocks{arenas}, n_queries, p.di, nd, out_survivors, out_off.data());
     return BSG_OK;
 }
 

@@ -15,6 +15,7 @@
 #include "host/combiner_sync.hpp"
 #include "host/probe_plan.hpp" // survivor offsets, launch groups, rows layout and the host merge of a probe call
 #include "host/regex_dfa.hpp"  // FieldRegex patterns -> the DFA tables k_match_rows_regex steps
+#include "host/regex_groups.hpp"  // the regex table blob, user masks and limits shared with the engine mirror
 #include "host/row_chunks.hpp" // the chunk plan and byte ranges RowUpload copies by
 #include "host/text.hpp"   // the host walker's Unicode tables: the device defers to the same data
 #include <hip/hip_ext.h>
@@ -822,6 +823,10 @@ int32_t bsg_open(const int32_t *device_ids, int32_t n_devices, bsg_ctx **out_ctx
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_union_partitions), hipFuncAttributeMaxDynamicSharedMemorySize, bsg::kPartLdsBytes));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_match_rows_regex), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     bsg::kMatchLdsBytes + bsg::kRxLdsCap));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_match_rows_many_regex), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    bsg::kMatchManyLdsBytes + bsg::kRxManyLdsCap));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_match_rows_many_regex_tok), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    bsg::kMatchManyLdsBytes + bsg::kRxManyLdsCap));
 
         ctx->devs.push_back(std::move(d));
     }

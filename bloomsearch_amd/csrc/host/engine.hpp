@@ -26,6 +26,7 @@
 #include "bloomgpu.h"
 #include "entry_sets.hpp"
 #include "expression.hpp"
+#include "regex_groups.hpp"
 #include "section_codec.hpp"
 
 namespace bsh {
@@ -331,22 +332,44 @@ public:
     // is the rows of every block at least one query survived on, one set per block with its query mask, and - under DeviceMatch -
     // one bsg_match_rows_many call per group of <= 64 queries / <= 64 distinct conditions decides them (the rows it hands back: the
     // host matcher, per query whose mask bit is set).  Without DeviceMatch the host matcher runs per (query, surviving block).
-    // A query with a regex tree is answered by query() and placed at its position.
+    // A query with a regex tree stays in the batch under DeviceMatch + DeviceRegex when all its patterns compile in the device
+    // subset (the test query() makes): it is probed with query()'s pruning expression And(bloom, field guard) and matched as the
+    // program And(bloom root | TRUE, regex root) by bsg_match_rows_many_regex.  Every other regex query is answered by query() and
+    // placed at its position, and so is a batched one whose group the device did not decide.
     int32_t query_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
                        std::vector<QueryResult> &results)
     {
         results.assign(exprs.size(), QueryResult{});
-        std::vector<size_t> live;                   // the batch: queries without a regex tree
+        std::vector<size_t> live;                   // the batch: queries without a regex tree, and regex queries the device matches
+        std::vector<const RegexExpression *> live_regex;
+        std::vector<std::unique_ptr<RegexRowMatcher>> regex_dfas;   // per batched query: the DFA-backed matcher of the rows handed back
         for (size_t i = 0; i < exprs.size(); ++i) {
-            if (i < regexes.size() && regexes[i]) { if (int32_t rc = query(exprs[i], results[i], regexes[i])) return rc; }
-            else live.push_back(i);
+            const RegexExpression *rx = i < regexes.size() ? regexes[i] : nullptr;
+            std::unique_ptr<RegexRowMatcher> dfa;
+            if (rx && cfg_.device_match && cfg_.device_regex) {
+                dfa = std::make_unique<RegexRowMatcher>(rx, true);
+                if (!dfa->valid()) dfa.reset();
+            }
+            if (rx && !dfa) { if (int32_t rc = query(exprs[i], results[i], rx)) return rc; continue; }
+            live.push_back(i);
+            live_regex.push_back(rx);
+            regex_dfas.push_back(std::move(dfa));
         }
         if (live.empty()) return kEngineOk;
         const auto t_begin = std::chrono::steady_clock::now();
-        std::vector<const BloomExpression *> batch;
-        for (size_t i : live) batch.push_back(exprs[i]);
+        std::vector<const BloomExpression *> batch, prune;
+        std::vector<std::unique_ptr<BloomExpression>> prune_storage;
+        for (size_t k = 0; k < live.size(); ++k) {
+            batch.push_back(exprs[live[k]]);
+            // pruneBloomQuery = AndBloomQueries(bloom, RegexFieldGuardBloomQuery(regex)), as query(); a plain query keeps its pointer
+            if (!live_regex[k]) { prune.push_back(batch[k]); continue; }
+            BloomExpression guard;
+            const bool has_guard = regex_field_guard(live_regex[k], guard);
+            prune_storage.push_back(std::make_unique<BloomExpression>());
+            prune.push_back(and_bloom_queries(batch[k], has_guard ? &guard : nullptr, *prune_storage.back()) ? prune_storage.back().get() : nullptr);
+        }
         std::vector<Survivors> sv;
-        if (int32_t rc = probe_stage(batch, sv)) return rc;
+        if (int32_t rc = probe_stage(prune, sv)) return rc;
         const int64_t probe_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_begin).count();
         const auto t_scan = std::chrono::steady_clock::now();
         const size_t Q = live.size();
@@ -381,9 +404,15 @@ public:
         for (size_t k = 0; k < Q; ++k) matchers.emplace_back(batch[k], cfg_.tokenizer);
         std::vector<uint8_t> on_device(Q, 0);
         if (cfg_.device_match && !scan.empty())
-            if (int32_t rc = match_rows_device_many(batch, scan, set_first, set_wants, matchers, hit, on_device)) return rc;
+            if (int32_t rc = match_rows_device_many(batch, live_regex, scan, set_first, set_wants, matchers, regex_dfas, hit, on_device)) return rc;
         for (size_t k = 0; k < Q; ++k) {
             QueryResult &out = results[live[k]];
+            // not decided in a group (alone beyond a limit, or the library refused the group): per query, as before.  query() probes
+            // again and rewrites the stats block_stage_stats left here: known, and rare enough not to carry the survivors over
+            if (live_regex[k] && !on_device[k] && !scanned[k].empty()) {
+                if (int32_t rc = query(exprs[live[k]], out, live_regex[k])) return rc;
+                continue;
+            }
             for (size_t s = 0; s + 1 < set_first.size(); ++s) {
                 if (!(*set_wants[s])[k]) continue;
                 for (uint32_t i = set_first[s]; i < set_first[s + 1]; ++i) {
@@ -813,18 +842,34 @@ private:
     }
 
     // The scan list under DeviceMatch for a batch: queries are packed, in order, into groups of <= 64 queries over <= 64 distinct
-    // conditions (deduplicated across the group's queries by (kind, field, token)); one bsg_match_rows_many call per group with
-    // the sets' masks restricted to the group.  on_device[k] stays 0 (the host matcher decides query k) for a query with more
-    // than 64 conditions of its own or a group the library answers BSG_E_UNSUPPORTED for.
-    int32_t match_rows_device_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const std::string *> &scan,
-                                   const std::vector<uint32_t> &set_first, const std::vector<const std::vector<uint8_t> *> &set_wants,
-                                   std::vector<RowMatcher> &host_matchers, std::vector<std::vector<uint8_t>> &hit, std::vector<uint8_t> &on_device)
+    // conditions (deduplicated across the group's queries by (kind, field, token or pattern)); one call per group with the sets'
+    // masks restricted to the group: bsg_match_rows_many_regex for a group with a regex condition, bsg_match_rows_many otherwise.
+    // A regex query's program is And(bloom root | TRUE, regex root).  A group also closes when the next query would bring it over 16
+    // regex conditions, over the batched kernel's table bytes (by regex_groups.hpp's estimate) or would let one leaf lie under
+    // more regex conditions than a lane holds (co_active_bound).  on_device[k] stays 0 (the caller decides query k by itself) for
+    // a query beyond one of these limits alone or a group the library answers BSG_E_UNSUPPORTED for.
+    int32_t match_rows_device_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
+                                   const std::vector<const std::string *> &scan, const std::vector<uint32_t> &set_first,
+                                   const std::vector<const std::vector<uint8_t> *> &set_wants, std::vector<RowMatcher> &host_matchers,
+                                   std::vector<std::unique_ptr<RegexRowMatcher>> &host_regex, std::vector<std::vector<uint8_t>> &hit,
+                                   std::vector<uint8_t> &on_device)
     {
         std::vector<uint8_t> bytes;
         std::vector<uint64_t> row_off{0};
         for (const std::string *r : scan) { bytes.insert(bytes.end(), r->begin(), r->end()); row_off.push_back(bytes.size()); }
         const bsg_tokenizer tok = c_tokenizer();
         const size_t n_words = (scan.size() + 63) / 64, n_sets = set_wants.size();
+        std::map<std::string, std::pair<uint32_t, uint32_t>> dfa_size;      // pattern -> (states, classes); (0, 0): outside the subset
+        auto rx_bytes = [&](const std::string &field, const std::string &pattern) -> uint32_t {
+            auto it = dfa_size.find(pattern);
+            if (it == dfa_size.end()) {
+                bsh_rx::Dfa d;
+                std::string err;
+                const bool ok = bsh_rx::compile(pattern, d, err);
+                it = dfa_size.emplace(pattern, ok ? std::make_pair(d.n_states, d.n_classes) : std::make_pair(0u, 0u)).first;
+            }
+            return bsh_rxg::rx_table_bytes(it->second.first, it->second.second, (uint32_t)field.size(), true);
+        };
         size_t k = 0;
         while (k < exprs.size()) {
             // the group's table and programs
@@ -832,12 +877,33 @@ private:
             std::vector<uint32_t> kinds, prog_ops, prog_off{0};
             std::vector<std::string> fields, tokens;
             std::vector<size_t> members;
+            uint32_t n_rx = 0, rx_table = 0;                                 // the group's regex conditions and their table bytes
             for (; k < exprs.size() && members.size() < 64; ++k) {
                 MatcherProgram mp(exprs[k]);
-                size_t fresh = 0;
-                for (size_t c = 0; c < mp.kinds.size(); ++c) fresh += index.count(std::make_tuple(mp.kinds[c], mp.fields[c], mp.tokens[c])) == 0;
-                if (mp.kinds.size() > 64) { if (members.empty()) { ++k; } break; }     // alone beyond the table: the host matcher's
-                if (index.size() + fresh > 64) break;                                    // (an upper bound: opens the next group)
+                if (regexes[k]) {
+                    if (!exprs[k]) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
+                    lower_regex(*regexes[k], mp);
+                    mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 2));
+                }
+                // what the query adds: distinct conditions, regex conditions, table bytes, and the fields that may meet on a leaf
+                std::map<std::tuple<uint32_t, std::string, std::string>, uint32_t> added;
+                uint32_t fresh_rx = 0, fresh_bytes = 0;
+                for (size_t c = 0; c < mp.kinds.size(); ++c) {
+                    const auto key = std::make_tuple(mp.kinds[c], mp.fields[c], mp.tokens[c]);
+                    if (index.count(key) || !added.emplace(key, 0).second) continue;
+                    if (mp.kinds[c] == BSG_KIND_FIELD_REGEX) { ++fresh_rx; fresh_bytes += rx_bytes(mp.fields[c], mp.tokens[c]); }
+                }
+                std::vector<std::string_view> rx_fields;
+                for (size_t c = 0; c < kinds.size(); ++c) if (kinds[c] == BSG_KIND_FIELD_REGEX) rx_fields.push_back(fields[c]);
+                for (const auto &kv : added) if (std::get<0>(kv.first) == BSG_KIND_FIELD_REGEX) rx_fields.push_back(std::get<1>(kv.first));
+                const bool fits = mp.kinds.size() <= 64 && index.size() + added.size() <= 64 && n_rx + fresh_rx <= bsh_rxg::kMaxRegexConds &&
+                                  bsh_rxg::align4(rx_table + fresh_bytes) <= bsh_rxg::kManyLdsCap &&
+                                  bsh_rxg::co_active_bound(rx_fields) <= bsh_rxg::kManySlots;
+                if (!fits) {
+                    // alone beyond the call: the caller's (the host matcher; per query for a regex query).  Else it opens the next group
+                    if (members.empty()) ++k;
+                    break;
+                }
                 for (uint32_t op : mp.prog_ops) {
                     if ((op >> 28) == BSG_OP_TERM) {
                         const uint32_t c = op & 0x0FFFFFFFu;
@@ -849,6 +915,8 @@ private:
                 }
                 prog_off.push_back((uint32_t)prog_ops.size());
                 members.push_back(k);
+                n_rx += fresh_rx;
+                rx_table += fresh_bytes;
             }
             if (members.empty()) continue;
             std::vector<uint8_t> cbytes;
@@ -863,20 +931,23 @@ private:
             std::vector<uint64_t> bits(members.size() * n_words);
             std::vector<uint32_t> fb(scan.size());
             uint32_t n_fb = 0;
-            const int32_t rc = bsg_match_rows_many(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
-                                                   (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(),
-                                                   masks.data(), (uint32_t)n_sets, &tok, bits.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
-            if (rc == BSG_E_UNSUPPORTED) continue;              // programs too deep / long: the host matcher
+            const int32_t rc = (n_rx ? bsg_match_rows_many_regex : bsg_match_rows_many)(
+                ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(), (uint32_t)kinds.size(),
+                prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(), masks.data(), (uint32_t)n_sets, &tok, bits.data(),
+                fb.data(), (uint32_t)fb.size(), &n_fb);
+            if (rc == BSG_E_UNSUPPORTED) continue;              // programs too deep / long, tables too large: the caller decides
             if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
             for (size_t j = 0; j < members.size(); ++j) {
                 std::vector<uint8_t> &h = hit[members[j]];
                 for (size_t i = 0; i < scan.size(); ++i) h[i] = (bits[j * n_words + (i >> 6)] >> (i & 63)) & 1;
                 on_device[members[j]] = 1;
             }
-            for (uint32_t i = 0; i < n_fb; ++i) {               // rows outside the walker's envelope or colliding: per live query
+            for (uint32_t i = 0; i < n_fb; ++i) {               // rows outside the walker's envelope, colliding or over the slots: per live query
                 const size_t s = (size_t)(std::upper_bound(set_first.begin() + 1, set_first.end(), fb[i]) - (set_first.begin() + 1));
+                const std::string &row = *scan[fb[i]];
                 for (size_t j = 0; j < members.size(); ++j)
-                    if ((masks[s] >> j) & 1) hit[members[j]][fb[i]] = host_matchers[members[j]].match(*scan[fb[i]]);
+                    if ((masks[s] >> j) & 1)
+                        hit[members[j]][fb[i]] = host_matchers[members[j]].match(row) && (!host_regex[members[j]] || host_regex[members[j]]->match(row));
             }
         }
         return kEngineOk;

@@ -25,10 +25,16 @@
 // call's result.  Rows come grouped in sets (one surviving block each) with a u64 query mask per set: a lane looks its set up
 // once (binary search in global memory), a verdict is ANDed with its mask bit, a row with mask 0 is never walked (so never a
 // fallback row) and a wave of such rows skips the walk altogether.  A row with a non-zero mask that leaves the walker's envelope
-// or collides with ANY table condition is a fallback row: all its plane bits are 0.  No FieldRegex conditions here: the regex
-// instance runs at 2 workgroups per CU with 80 KiB of LDS and would need its own sizing.
+// or collides with ANY table condition is a fallback row: all its plane bits are 0.
 // LDS of the MANY instance: conditions 5 632 + programs 8 192 + prog_off 260 + lanes 29 696 = 43 780 bytes, three workgroups
 // per CU as k_match_rows.
+//
+// Both together (k_match_rows_many_regex / k_match_rows_many_regex_tok = REGEX and MANY): the table also holds the DISTINCT
+// FieldRegex conditions of the batch, their blob sits behind the MANY instance's 43 780 bytes (at most kRxManyLdsCap = 38 140
+// bytes of it: 80 KiB in all, 2 workgroups per CU as k_match_rows_regex) and carries, behind its header, one u64 per regex slot:
+// the queries whose program references the condition.  A leaf opens a condition's DFA only on a row whose set mask selects one
+// of those queries, so a lane's kRxManyActive slots hold what the row's own queries need, and a row is handed back for too many
+// regex conditions on one leaf only when the queries live on its set put them there.
 #pragma once
 #include <type_traits>
 #include "ingest.hip.h"
@@ -77,11 +83,20 @@ struct MatchManyArgs {
 constexpr uint32_t kRxMaxConds = 16;       // regex conditions per call
 constexpr uint32_t kRxActive = 4;          // regex conditions one leaf may feed at once (registers per lane)
 constexpr uint32_t kRxLdsCap = 80u * 1024u - kMatchLdsBytes;   // table bytes: the regex kernel keeps 2 workgroups per CU
-// LDS table blob, built by the host (match_api.inc build_rx_blob):
+#ifndef BSG_RX_MANY_SLOTS                   // a lab build may try another slot count (tools/regex_many_lab.py); the library ships 4
+#define BSG_RX_MANY_SLOTS 4
+#endif
+constexpr uint32_t kRxManyActive = BSG_RX_MANY_SLOTS;          // the same per leaf in the batched regex kernels (4 against 8: DESIGN.md section 9)
+constexpr uint32_t kRxManyLdsCap = 80u * 1024u - kMatchManyLdsBytes;   // their table bytes, user masks included
+static_assert(kRxManyLdsCap == 38140u && 2u * (kMatchManyLdsBytes + kRxManyLdsCap) <= 160u * 1024u,
+              "k_match_rows_many_regex keeps two workgroups per CU");
+// LDS table blob, built by the host (host/regex_groups.hpp build_blob):
 //   header [n_rx][4] u32: { region offset | (n_classes - 1) << 16 | slot << 24,  start entry | condition index << 16,
 //                           field offset | field length << 16,  0 }
 //   per pattern (4-byte aligned region): class map [256] u8, then transitions [n_states * n_classes] u16 whose entries are
 //   target state | kRxAccept / kRxDead / kRxAcceptAtEnd of the target; then the field strings.
+//   The batched call's blob holds, between the header and the first region, users [n_rx] u64: bit q = query q's program
+//   references the condition (host/regex_groups.hpp user_masks).
 constexpr uint32_t kRxAccept = 0x8000u, kRxDead = 0x4000u, kRxAcceptAtEnd = 0x2000u, kRxStateMask = 0x1FFFu;
 struct RxArgs {
     const uint32_t *blob;       // the table blob as words
@@ -91,14 +106,15 @@ typedef __attribute__((address_space(3))) uint16_t lds_u16;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 
 // one lane's active regex conditions (hd = header word 0 of the condition, ~0u = free slot; st = its DFA entry)
-struct RxLane {
+template <uint32_t SLOTS>
+struct RxLaneT {
     const lds_u8 *tab;
-    uint32_t hd[kRxActive], st[kRxActive];
+    uint32_t hd[SLOTS], st[SLOTS];
     uint32_t sat;                                   // bit j: regex slot j matched a candidate text of this row
     __device__ __forceinline__ void feed(uint32_t b)
     {
 #pragma unroll
-        for (uint32_t k = 0; k < kRxActive; ++k)
+        for (uint32_t k = 0; k < SLOTS; ++k)
             if (hd[k] != ~0u) {
                 const uint32_t off = hd[k] & 0xFFFFu, ncls = ((hd[k] >> 16) & 0xFFu) + 1u;
                 const uint32_t v = ((const lds_u16 *)(tab + off + 256u))[(st[k] & kRxStateMask) * ncls + tab[off + b]];
@@ -122,18 +138,20 @@ struct RxLane {
     __device__ __forceinline__ void close()
     {
 #pragma unroll
-        for (uint32_t k = 0; k < kRxActive; ++k) {
+        for (uint32_t k = 0; k < SLOTS; ++k) {
             if (hd[k] != ~0u && (st[k] & kRxAcceptAtEnd)) sat |= 1u << (hd[k] >> 24);
             hd[k] = ~0u;
         }
     }
 };
 
-template <bool REGEX, class TOK, bool MANY = false>
+typedef RxLaneT<kRxActive> RxLane;
+
+template <bool REGEX, class TOK, bool MANY = false, uint32_t SLOTS = kRxActive>
 __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs &x, const TOK &tk, const MatchManyArgs &m = MatchManyArgs{})
 {
-    static_assert(!(REGEX && MANY), "the batched matcher takes no FieldRegex conditions");
     constexpr uint32_t kProgBytes = MANY ? kMatchManyProgBytes : kMatchMaxOps * 4;
+    constexpr uint32_t kRxBase = MANY ? kMatchManyLdsBytes : kMatchLdsBytes;   // the regex blob sits behind the instance's own LDS
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     lds_u64i *conds = (lds_u64i *)lds_raw;
     typedef __attribute__((address_space(3))) uint32_t lds_u32i;
@@ -148,7 +166,7 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
     if constexpr (MANY)
         for (uint32_t i = threadIdx.x; i <= m.n_queries; i += kIngestThreads) prog[kMatchManyMaxOps + i] = m.prog_off[i];
     if constexpr (REGEX)
-        for (uint32_t i = threadIdx.x; i < x.n_words; i += kIngestThreads) ((lds_u32 *)(lds_raw + kMatchLdsBytes))[i] = x.blob[i];
+        for (uint32_t i = threadIdx.x; i < x.n_words; i += kIngestThreads) ((lds_u32 *)(lds_raw + kRxBase))[i] = x.blob[i];
     __syncthreads();
     const uint32_t r = blockIdx.x * kIngestThreads + threadIdx.x;
     const bool live = r < a.n_rows;
@@ -178,13 +196,13 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
     uint32_t res = walk ? R_CONTINUE : R_DONE;
     uint64_t sat = 0, leaf_mask = 0;
     bool collided = false;       // equal hashes, different fingerprint: only the host's byte compare can decide this row
-    typename std::conditional<REGEX, RxLane, RxNone>::type rx;
+    typename std::conditional<REGEX, RxLaneT<SLOTS>, RxNone>::type rx;
     bool rx_over = false;        // more regex conditions on one leaf than a lane holds: the host decides this row
     if constexpr (REGEX) {
-        rx.tab = (const lds_u8 *)lds_raw + kMatchLdsBytes;
+        rx.tab = (const lds_u8 *)lds_raw + kRxBase;
         rx.sat = 0;
 #pragma unroll
-        for (uint32_t k = 0; k < kRxActive; ++k) rx.hd[k] = ~0u;
+        for (uint32_t k = 0; k < SLOTS; ++k) rx.hd[k] = ~0u;
     }
     while (__ballot(res == R_CONTINUE || w.req != Q_NONE) != 0ull) {
         while (__ballot(res == R_CONTINUE && w.req == Q_NONE) != 0ull)
@@ -210,6 +228,10 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
                 const lds_u8 *fld = rx.tab + (h2 & 0xFFFFu);
                 bool under = text && !((rx.sat >> j) & 1u) && flen != 0u && flen <= kPathCap &&
                              (plen == flen || (plen > flen && w.path[flen] == '.'));
+                if constexpr (MANY) {                                    // only for a row whose set evaluates a query that uses the condition
+                    const uint64_t users = (uint64_t)hdr[4 * x.n_rx + 2 * j] | ((uint64_t)hdr[4 * x.n_rx + 2 * j + 1] << 32);
+                    under = under && (qmask & users) != 0ull;
+                }
                 for (uint32_t i = 0; i < flen && __ballot(under) != 0ull; ++i)   // ends once no lane's path can still match
                     if (under) under = w.path[i] == fld[i];
                 if (under) {
@@ -218,7 +240,7 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
                     else if (!(sv & kRxDead)) {
                         bool placed = false;
 #pragma unroll
-                        for (uint32_t k = 0; k < kRxActive; ++k)
+                        for (uint32_t k = 0; k < SLOTS; ++k)
                             if (!placed && rx.hd[k] == ~0u) { rx.hd[k] = h0; rx.st[k] = sv; placed = true; }
                         rx_over |= !placed;
                     }
@@ -322,6 +344,15 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many(const MatchA
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_tok(const MatchArgs a, const MatchManyArgs m, const TokSpec t)
 {
     match_rows_body<false, TokSpecP, true>(a, RxArgs{}, TokSpecP{t}, m);
+}
+// a batch of queries with FieldRegex conditions in the table; dynamic LDS kMatchManyLdsBytes + the table blob (<= kRxManyLdsCap)
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex(const MatchArgs a, const RxArgs x, const MatchManyArgs m)
+{
+    match_rows_body<true, TokDefault, true, kRxManyActive>(a, x, TokDefault{}, m);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_tok(const MatchArgs a, const RxArgs x, const MatchManyArgs m, const TokSpec t)
+{
+    match_rows_body<true, TokSpecP, true, kRxManyActive>(a, x, TokSpecP{t}, m);
 }
 
 }  // namespace bsg

@@ -2,54 +2,30 @@
 
 namespace {
 
-// The LDS table blob of a call's FieldRegex conditions (layout: match.hip.h).  BSG_E_UNSUPPORTED, before anything is
-// launched, for a pattern outside the compiler's subset, more than kRxMaxConds of them, or tables over kRxLdsCap.
+static_assert(bsh_rxg::kMaxRegexConds == bsg::kRxMaxConds && bsh_rxg::kSingleLdsCap == bsg::kRxLdsCap && bsh_rxg::kManyLdsCap == bsg::kRxManyLdsCap &&
+                  bsh_rxg::kSingleSlots == bsg::kRxActive && (bsh_rxg::kManySlots == bsg::kRxManyActive || BSG_RX_MANY_SLOTS != 4) &&
+                  bsh_rxg::kPathCap == bsg::kPathCap,
+              "host/regex_groups.hpp states the kernels' limits");
+
+// The LDS table blob of a call's FieldRegex conditions (layout: match.hip.h; built by host/regex_groups.hpp).  BSG_E_UNSUPPORTED,
+// before anything is launched, for a pattern outside the compiler's subset, more than kRxMaxConds of them, or tables over `cap`
+// (kRxLdsCap; kRxManyLdsCap for the batched call, whose blob also holds the conditions' user masks: users [n_conds], else NULL).
 int32_t build_rx_blob(const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
-                      std::vector<uint32_t> &blob, uint32_t &n_rx)
+                      std::vector<uint32_t> &blob, uint32_t &n_rx, uint32_t cap = bsg::kRxLdsCap, const uint64_t *users = nullptr)
 {
-    std::vector<uint32_t> rx;
-    for (uint32_t c = 0; c < n_conds; ++c)
-        if (cond_kinds[c] == BSG_KIND_FIELD_REGEX) rx.push_back(c);
-    n_rx = (uint32_t)rx.size();
-    blob.clear();
-    if (rx.empty()) return BSG_OK;
-    if (n_rx > bsg::kRxMaxConds)
+    const bsh_rxg::BlobResult r = bsh_rxg::build_blob(cond_bytes, cond_off, cond_kinds, n_conds, BSG_KIND_FIELD_REGEX, cap, users, blob);
+    n_rx = r.n_rx;
+    switch (r.status) {
+    case bsh_rxg::BlobStatus::Ok: return BSG_OK;
+    case bsh_rxg::BlobStatus::TooMany:
         return fail(BSG_E_UNSUPPORTED, "%u regex conditions (the device matcher holds %u)", n_rx, bsg::kRxMaxConds);
-    std::vector<uint8_t> bytes((size_t)n_rx * 16, 0);
-    auto put32 = [&](size_t at, uint32_t v) { memcpy(bytes.data() + at, &v, 4); };
-    bool over = false;
-    for (uint32_t j = 0; j < n_rx; ++j) {
-        const uint32_t c = rx[j];
+    case bsh_rxg::BlobStatus::Pattern: {
+        const uint32_t c = r.cond;
         const std::string_view pat((const char *)cond_bytes + cond_off[2 * c + 1], cond_off[2 * c + 2] - cond_off[2 * c + 1]);
-        bsh_rx::Dfa d;
-        std::string err;
-        if (!bsh_rx::compile(pat, d, err))
-            return fail(BSG_E_UNSUPPORTED, "regex condition %u (pattern \"%.*s\"): %s", c, (int)std::min<size_t>(pat.size(), 200), pat.data(), err.c_str());
-        bytes.resize((bytes.size() + 3) & ~(size_t)3);
-        const size_t off = bytes.size();
-        if (off + 256 + d.trans.size() * 2 > bsg::kRxLdsCap) { over = true; break; }
-        bytes.insert(bytes.end(), d.cls, d.cls + 256);
-        const size_t t0 = bytes.size();
-        bytes.resize(t0 + d.trans.size() * 2);
-        memcpy(bytes.data() + t0, d.trans.data(), d.trans.size() * 2);
-        put32((size_t)j * 16, (uint32_t)off | ((d.n_classes - 1) << 16) | (j << 24));
-        put32((size_t)j * 16 + 4, (uint32_t)d.start | (c << 16));
+        return fail(BSG_E_UNSUPPORTED, "regex condition %u (pattern \"%.*s\"): %s", c, (int)std::min<size_t>(pat.size(), 200), pat.data(), r.err.c_str());
     }
-    for (uint32_t j = 0; j < n_rx && !over; ++j) {
-        const uint32_t c = rx[j];
-        uint32_t flen = cond_off[2 * c + 1] - cond_off[2 * c];
-        // a path the device keeps is at most kPathCap bytes: a longer field is never at or above a leaf of a row it decides
-        if (flen > bsg::kPathCap) flen = bsg::kPathCap + 1;
-        const size_t off = bytes.size();
-        if (flen <= bsg::kPathCap) bytes.insert(bytes.end(), cond_bytes + cond_off[2 * c], cond_bytes + cond_off[2 * c] + flen);
-        put32((size_t)j * 16 + 8, (uint32_t)std::min<size_t>(off, 0xFFFF) | (flen << 16));
+    default: return fail(BSG_E_UNSUPPORTED, "regex tables need more than %u bytes of LDS", cap);
     }
-    if (over || bytes.size() > bsg::kRxLdsCap)
-        return fail(BSG_E_UNSUPPORTED, "regex tables need more than %u bytes of LDS", bsg::kRxLdsCap);
-    bytes.resize((bytes.size() + 3) & ~(size_t)3);
-    blob.resize(bytes.size() / 4);
-    memcpy(blob.data(), bytes.data(), bytes.size());
-    return BSG_OK;
 }
 
 // bsg_match_rows_many: what a part needs beyond the single call's arguments.  `prog` then holds the lowered programs of all
@@ -63,7 +39,7 @@ struct ManyPlan {
 };
 
 // rows [r0, r1) (r0 a multiple of 64: whole words of out_bits) on one device; fb receives the GLOBAL indices of the rows handed back
-// many: the batched call (k_match_rows_many*), NULL = one expression
+// many: the batched call (k_match_rows_many*; with regex conditions k_match_rows_many_regex*), NULL = one expression
 int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64_t *row_off, uint32_t r0, uint32_t r1,
                       const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds, uint32_t cond_len,
                       const std::vector<uint32_t> &prog, const std::vector<uint32_t> &rx_blob, uint32_t n_rx, const bsg::TokSpec *tok,
@@ -71,7 +47,7 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
 {
     const uint32_t n_rows = r1 - r0;
     const uint64_t byte0 = row_off[r0], n_bytes = row_off[r1] - byte0;
-    const LabTrace trace{many ? "bsg_match_rows_many" : "bsg_match_rows", d.id};
+    const LabTrace trace{many ? (n_rx ? "bsg_match_rows_many_regex" : "bsg_match_rows_many") : "bsg_match_rows", d.id};
     std::vector<uint64_t> local_off((size_t)n_rows + 1);                  // the run's offsets, relative to its first byte
     for (uint32_t r = 0; r <= n_rows; ++r) local_off[r] = row_off[r0 + r] - byte0;
     // the sets this run's rows lie in, their first rows clamped to the run and counted from r0
@@ -156,7 +132,13 @@ int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64
         const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads);
         if (many) {
             const bsg::MatchManyArgs m{d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets};
-            if (tok)
+            const bsg::RxArgs x{d_rx, (uint32_t)rx_blob.size(), n_rx};
+            const uint32_t rx_lds = bsg::kMatchManyLdsBytes + (uint32_t)rx_blob.size() * 4;
+            if (n_rx && tok)
+                hipExtLaunchKernelGGL(bsg::k_match_rows_many_regex_tok, grid, dim3(bsg::kIngestThreads), rx_lds, d.stream, k0, k1, 0, a, x, m, *tok);
+            else if (n_rx)
+                hipExtLaunchKernelGGL(bsg::k_match_rows_many_regex, grid, dim3(bsg::kIngestThreads), rx_lds, d.stream, k0, k1, 0, a, x, m);
+            else if (tok)
                 hipExtLaunchKernelGGL(bsg::k_match_rows_many_tok, grid, dim3(bsg::kIngestThreads), bsg::kMatchManyLdsBytes, d.stream, k0, k1, 0, a, m, *tok);
             else
                 hipExtLaunchKernelGGL(bsg::k_match_rows_many, grid, dim3(bsg::kIngestThreads), bsg::kMatchManyLdsBytes, d.stream, k0, k1, 0, a, m);
@@ -288,12 +270,14 @@ int32_t match_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_o
                           out_fallback_rows, fallback_cap, out_n_fallback);
 }
 
-// bsg_match_rows_many: n_queries programs over one table of distinct conditions, one upload and one walk of the rows
+// bsg_match_rows_many (max_kind 2) and bsg_match_rows_many_regex (max_kind 3): n_queries programs over one table of distinct
+// conditions, one upload and one walk of the rows
 int32_t match_rows_many_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
                              const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
                              const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
                              const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets, const bsg_tokenizer *tok_in,
-                             uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+                             uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback,
+                             uint32_t max_kind)
 {
     if (!ctx) return fail(BSG_E_INVALID, "ctx is null");
     bsg_tokenizer rec{};
@@ -312,9 +296,9 @@ int32_t match_rows_many_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *
     if (int32_t rc = check_match_inputs(rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_n_fallback, cond_len, n_bytes))
         return rc;
     for (uint32_t c = 0; c < n_conds; ++c) {
-        if (cond_kinds[c] == BSG_KIND_FIELD_REGEX)
+        if (cond_kinds[c] == BSG_KIND_FIELD_REGEX && max_kind < BSG_KIND_FIELD_REGEX)
             return fail(BSG_E_UNSUPPORTED, "condition %u: FieldRegex conditions are not matched by the batched call (use bsg_match_rows_regex)", c);
-        if (cond_kinds[c] > BSG_KIND_FIELD_TOKEN) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, cond_kinds[c]);
+        if (cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, cond_kinds[c]);
     }
     if (n_sets) {
         if (!set_first_row || !query_mask_of_set) return fail(BSG_E_INVALID, "set table is null");
@@ -338,9 +322,16 @@ int32_t match_rows_many_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *
             return fail(BSG_E_UNSUPPORTED, "the batch's programs hold more than %u lowered ops (at query %u)", bsg::kMatchManyMaxOps, q);
         plan.prog_off.push_back((uint32_t)prog.size());
     }
+    // the regex conditions' tables, each with the queries that use it (a table without any: exactly bsg_match_rows_many's kernels)
+    std::vector<uint32_t> rx_blob;
+    uint32_t n_rx = 0;
+    if (max_kind >= BSG_KIND_FIELD_REGEX && n_queries) {
+        const std::vector<uint64_t> users = bsh_rxg::user_masks(prog_ops, prog_off, n_queries, n_conds);
+        if (int32_t rc = build_rx_blob(cond_bytes, cond_off, cond_kinds, n_conds, rx_blob, n_rx, bsg::kRxManyLdsCap, users.data())) return rc;
+    }
     if (n_queries == 0 || n_rows == 0) return BSG_OK;
     *out_n_fallback = 0;
-    return match_rows_run(ctx, rows, row_off, n_rows, n_bytes, cond_bytes, cond_off, cond_kinds, n_conds, cond_len, prog, {}, 0, tok, out_bits,
+    return match_rows_run(ctx, rows, row_off, n_rows, n_bytes, cond_bytes, cond_off, cond_kinds, n_conds, cond_len, prog, rx_blob, n_rx, tok, out_bits,
                           out_fallback_rows, fallback_cap, out_n_fallback, &plan);
 }
 
@@ -386,7 +377,18 @@ int32_t bsg_match_rows_many(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *r
 {
     BSG_ENTER(ctx);
     return match_rows_many_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, prog_off, n_queries, set_first_row,
-                                query_mask_of_set, n_sets, tok, out_bits, out_fallback_rows, fallback_cap, out_n_fallback);
+                                query_mask_of_set, n_sets, tok, out_bits, out_fallback_rows, fallback_cap, out_n_fallback, BSG_KIND_FIELD_TOKEN);
+}
+
+int32_t bsg_match_rows_many_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                  const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                  const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                  const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets, const bsg_tokenizer *tok,
+                                  uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    return match_rows_many_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, prog_off, n_queries, set_first_row,
+                                query_mask_of_set, n_sets, tok, out_bits, out_fallback_rows, fallback_cap, out_n_fallback, BSG_KIND_FIELD_REGEX);
 }
 
 int32_t bsg_pinned_alloc(bsg_ctx *ctx, uint64_t n_bytes, void **out_ptr)

@@ -618,6 +618,13 @@ class Context:
         """bsg_match_rows_many: rows as match_rows; batch: query.CompiledMatcherBatch (or anything with its kinds / fields / tokens /
         prog_ops / prog_off).  set_first_row [n_sets + 1] and masks [n_sets] (u64, bit q = evaluate query q on the set): both
         None = every query on every row.  -> (bool planes [n_queries, n_rows], sorted u32 array of rows the host matcher must decide)."""
+        return self._match_rows_many(self.L.bsg_match_rows_many, rows, batch, set_first_row, masks, tokenizer)
+
+    def match_rows_many_regex(self, rows, batch, set_first_row=None, masks=None, tokenizer=None):
+        """bsg_match_rows_many_regex: as match_rows_many, and the batch (query.CompiledRowQueryBatch) may hold FieldRegex conditions."""
+        return self._match_rows_many(self.L.bsg_match_rows_many_regex, rows, batch, set_first_row, masks, tokenizer)
+
+    def _match_rows_many(self, fn, rows, batch, set_first_row, masks, tokenizer):
         if isinstance(rows, tuple):
             blob = np.ascontiguousarray(rows[0], dtype=np.uint8)
             off = np.ascontiguousarray(rows[1], dtype=np.uint64)
@@ -641,10 +648,10 @@ class Context:
         bits = np.zeros((nq, n_words), dtype=np.uint64)
         fb = np.zeros(max(n, 1), dtype=np.uint32)
         nfb = C.c_uint32()
-        self._check(self.L.bsg_match_rows_many(self.h, _lib._ptr(blob), _lib._ptr(off), n, _lib._ptr(cblob), _lib._ptr(coff), _lib._ptr(kinds),
-                                               len(kinds), _lib._ptr(ops), poff.ctypes.data, nq, _lib._ptr(sfr), _lib._ptr(msk),
-                                               0 if msk is None else len(msk), None if tokenizer is None else c_spec(tokenizer),
-                                               _lib._ptr(bits), _lib._ptr(fb), len(fb), C.byref(nfb)))
+        self._check(fn(self.h, _lib._ptr(blob), _lib._ptr(off), n, _lib._ptr(cblob), _lib._ptr(coff), _lib._ptr(kinds),
+                       len(kinds), _lib._ptr(ops), poff.ctypes.data, nq, _lib._ptr(sfr), _lib._ptr(msk),
+                       0 if msk is None else len(msk), None if tokenizer is None else c_spec(tokenizer),
+                       _lib._ptr(bits), _lib._ptr(fb), len(fb), C.byref(nfb)))
         planes = np.unpackbits(bits.view(np.uint8).reshape(nq, n_words * 8), axis=1, bitorder="little")[:, :n].astype(bool)
         return planes, fb[: nfb.value].copy()
 

@@ -228,6 +228,7 @@ class CompiledMatcher:
 
 
 MATCH_MANY_MAX_QUERIES, MATCH_MANY_MAX_CONDS, MATCH_MANY_MAX_OPS = 64, 64, 2048      # bloomgpu.h bsg_match_rows_many
+MATCH_MANY_MAX_REGEX_CONDS = 16                                                      # bloomgpu.h bsg_match_rows_many_regex
 
 
 def lowered_ops(prog_ops) -> int:
@@ -258,7 +259,7 @@ class CompiledMatcherBatch:
         index: dict = {}
         lowered = 0
         for e in expressions:
-            m = CompiledMatcher(e)
+            m = self._compile(e)
             remap = []
             for key in zip(m.kinds, m.fields, m.tokens):
                 i = index.get(key)
@@ -270,12 +271,18 @@ class CompiledMatcherBatch:
                 remap.append(i)
             if len(self.kinds) > MATCH_MANY_MAX_CONDS:
                 raise ValueError(f"more than {MATCH_MANY_MAX_CONDS} distinct conditions in one batched match call")
+            if self.kinds.count(KIND_FIELD_REGEX) > MATCH_MANY_MAX_REGEX_CONDS:
+                raise ValueError(f"more than {MATCH_MANY_MAX_REGEX_CONDS} distinct regex conditions in one batched match call")
             self.index_maps.append(remap)
             self.prog_ops.extend(op(OP_TERM, remap[o & 0x0FFFFFFF]) if (o >> 28) == OP_TERM else o for o in m.prog_ops)
             self.prog_off.append(len(self.prog_ops))
             lowered += lowered_ops(m.prog_ops)
             if lowered > MATCH_MANY_MAX_OPS:
                 raise ValueError(f"the batch's programs lower to more than {MATCH_MANY_MAX_OPS} ops")
+
+    @staticmethod
+    def _compile(expression):
+        return CompiledMatcher(expression)
 
     @property
     def n_queries(self) -> int:
@@ -323,3 +330,14 @@ class CompiledRowQuery(CompiledMatcher):
             self.prog_ops.append(op(OP_AND if et == EXPR_AND else OP_OR, len(kids)))
         else:
             self.prog_ops.append(op(OP_FALSE))
+
+
+class CompiledRowQueryBatch(CompiledMatcherBatch):
+    """A batch of (bloom expression, regex expression) pairs for one bsg_match_rows_many_regex call: query q's program is
+    CompiledRowQuery(bloom_q, regex_q)'s with its condition indices remapped into ONE table of distinct conditions,
+    deduplicated by (kind, field, token or pattern) as CompiledMatcherBatch does.  Raises ValueError beyond 64 queries, 64
+    conditions, 2 048 lowered ops or 16 regex conditions."""
+
+    @staticmethod
+    def _compile(pair):
+        return CompiledRowQuery(*pair)

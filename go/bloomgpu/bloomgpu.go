@@ -1019,6 +1019,21 @@ func (g *Context) matchRows(regex bool, rows []byte, rowOff []uint64, conds []Ma
 // matchRowBytes for every query whose mask bit is set on their set.  Limits: 64 queries, 64 conditions, 2048 lowered ops.
 func (g *Context) MatchRowsMany(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
 	setFirstRow []uint32, masks []uint64, tok *Tokenizer) (planes [][]uint64, hostRows []uint32, err error) {
+	return g.matchRowsMany(false, rows, rowOff, conds, progOps, progOff, setFirstRow, masks, tok)
+}
+
+// MatchRowsManyRegex is MatchRowsMany through bsg_match_rows_many_regex: the table may also hold up to 16 distinct KindFieldRegex
+// conditions (Token = the pattern), so every query's program is a whole compileRowMatcher root And(bloomRoot, regexRoot).  A regex
+// condition is opened on a leaf only for rows whose set evaluates a query that references it.  A pattern outside the device's RE2
+// subset, more than 16 of them or tables over 38140 bytes of LDS: IsUnsupported(err).  hostRows also lists rows in which one leaf lies
+// under more than 4 regex conditions of the queries live on the row's set.
+func (g *Context) MatchRowsManyRegex(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
+	setFirstRow []uint32, masks []uint64, tok *Tokenizer) (planes [][]uint64, hostRows []uint32, err error) {
+	return g.matchRowsMany(true, rows, rowOff, conds, progOps, progOff, setFirstRow, masks, tok)
+}
+
+func (g *Context) matchRowsMany(regex bool, rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
+	setFirstRow []uint32, masks []uint64, tok *Tokenizer) (planes [][]uint64, hostRows []uint32, err error) {
 	n, nq := len(rowOff)-1, len(progOff)-1
 	if n <= 0 || nq <= 0 {
 		return nil, nil, nil
@@ -1048,9 +1063,16 @@ func (g *Context) MatchRowsMany(rows []byte, rowOff []uint64, conds []MatchCond,
 		kinds[i] = c.Kind
 	}
 	var nfb C.uint32_t
-	rc := C.bsg_match_rows_many(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
-		u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u64p(masks), C.uint32_t(len(masks)), ct,
-		u64p(bits), u32p(hostRows), C.uint32_t(n), &nfb)
+	var rc C.int32_t
+	if regex {
+		rc = C.bsg_match_rows_many_regex(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+			u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u64p(masks), C.uint32_t(len(masks)), ct,
+			u64p(bits), u32p(hostRows), C.uint32_t(n), &nfb)
+	} else {
+		rc = C.bsg_match_rows_many(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+			u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u64p(masks), C.uint32_t(len(masks)), ct,
+			u64p(bits), u32p(hostRows), C.uint32_t(n), &nfb)
+	}
 	if err := g.err(rc); err != nil {
 		return nil, nil, err
 	}

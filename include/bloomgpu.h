@@ -618,7 +618,30 @@ BSG_API int32_t bsg_match_rows_many(bsg_ctx *ctx, const uint8_t *rows, const uin
                                     const bsg_tokenizer *tok,
                                     uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                     uint32_t *out_n_fallback);
-/* Device time of the most recent k_match_rows / k_match_rows_regex / k_match_rows_many dispatch (the slowest device's). */
+/* bsg_match_rows_many with FieldRegex conditions in the table (k_match_rows_many_regex): the same nineteen arguments, set / mask
+ * semantics, plane layout, sharding over the context's devices, chunked upload and bsg_last_match_ms.  What differs:
+ * - cond_kinds[i] may be BSG_KIND_FIELD_REGEX (entry 2i = the field, 2i + 1 = the pattern) with the meaning bsg_match_rows_regex
+ *   documents: the pattern matches the candidate text of any leaf at or under the field, never null, an empty field never holds;
+ *   under a tokenizer spec the regex still reads the leaf text, not its words.  Plane q = what bsg_match_rows_tok returns for
+ *   program q alone over the same table.
+ * - A table without any regex condition runs exactly bsg_match_rows_many's kernels and returns exactly its result.
+ * - Limits (BSG_E_UNSUPPORTED before anything is launched, the message names the condition index and the construct): those of
+ *   bsg_match_rows_many; more than 16 distinct regex conditions; a pattern outside the compiler's subset or over 1 024 states; DFA
+ *   tables over 38 140 bytes of LDS (80 KiB minus the batched matcher's 43 780: 6 404 bytes less than bsg_match_rows_regex takes),
+ *   of which every regex condition spends 16 header bytes, 8 bytes for the mask of the queries that use it, its class map and
+ *   transitions (256 + 2 * states * classes, padded to 4) and its field string.
+ * - Fallback rows: those of bsg_match_rows_many, and a row in which one leaf would feed more than 4 regex conditions at once,
+ *   counting only conditions referenced by a query whose mask bit is set on the row's set (a regex condition is opened on a leaf
+ *   only for rows that evaluate a query using it).  Listed once, ascending, all plane bits 0. */
+BSG_API int32_t bsg_match_rows_many_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                          const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                          const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                          const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets,
+                                          const bsg_tokenizer *tok,
+                                          uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                          uint32_t *out_n_fallback);
+/* Device time of the most recent k_match_rows / k_match_rows_regex / k_match_rows_many / k_match_rows_many_regex dispatch (the
+ * slowest device's). */
 BSG_API int32_t bsg_last_match_ms(bsg_ctx *ctx, float *match_ms);
 
 #ifdef __cplusplus

@@ -128,7 +128,10 @@ BSG_API int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, c
  * Errors, FilesConsidered, FilesBloomSkipped; Duration is exempt).  All bloom-only queries share one query batch: one file-stage
  * probe, one bsg_probe_many over the leased arenas, then the rows of every block at least one query survived on are scanned once
  * - under DeviceMatch by one bsg_match_rows_many call per group of <= 64 queries / <= 64 distinct conditions, each block a set
- * with the mask of the queries that survived on it.  A query with a Regex tree is answered as by bse_query.  "[]" gives "[]". */
+ * with the mask of the queries that survived on it.  Under DeviceMatch + DeviceRegex a query with a Regex tree whose patterns
+ * all lie in the device's RE2 subset joins the batch (probed with its pruning expression, matched by bsg_match_rows_many_regex in
+ * groups of <= 16 regex conditions whose tables fit the batched kernel and of which no more than 4 can meet on one leaf); every
+ * other query with a Regex tree is answered as by bse_query.  "[]" gives "[]". */
 BSG_API int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, char **out_json, uint64_t *out_len);
 /* {"files":[{"FileID","BloomEntryCounts":{..},"section_bytes","blocks":[{"PartitionID","Rows","BloomEntryCounts":{..},
  *  "BloomFalsePositiveRate","BloomFilterSize","filters":[{"m","k"}|null x3]}]}]} */

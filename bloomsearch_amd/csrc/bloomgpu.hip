@@ -12,6 +12,7 @@
 #include "bin_build.hip.h"
 #include "direct.hip.h"
 #include "match.hip.h"
+#include "host/build_plan.hpp"  // shard layout and stats, the parts of a build call, the route a filter is built by
 #include "host/combiner_sync.hpp"
 #include "host/probe_plan.hpp" // survivor offsets, launch groups, rows layout and the host merge of a probe call
 #include "host/regex_dfa.hpp"  // FieldRegex patterns -> the DFA tables k_match_rows_regex steps
@@ -91,6 +92,11 @@ constexpr uint64_t kAlignWords = 16;          // filters start on 128-byte bound
 constexpr uint32_t kBuildSliceEntries = 8192; // entries per workgroup for non-staged builds
 constexpr uint64_t kBinScratchBytes = 16ull << 30;   // locations (4 bytes each) one binned build may park in HBM
 constexpr uint64_t kMaxHashCount = 1024;      // k above this is rejected (EstimateParameters: 30 at p = 1e-9, 100 at 1e-30)
+static_assert(bsh::kLdsBudget == kLdsBudget && bsh::kLdsCapWords == kLdsCapWords && bsh::kAlignWords == kAlignWords && kLdsBudget % 8 == 0 &&
+              bsh::kSetListBytes == bsg::kSetListBytes,
+              "host/build_plan.hpp lays shards out and routes builds by the library's constants");
+using bsh::balanced_cuts;
+using bsh::section_len;
 
 uint64_t barrett_magic(uint64_t m)
 {
@@ -100,6 +106,7 @@ uint64_t barrett_magic(uint64_t m)
     if ((m & (m - 1)) == 0) q += 1;
     return q;
 }
+DevDesc dev_desc(const bsg_filter_desc &f) { return DevDesc{f.word_off, f.m, barrett_magic(f.m), f.k, 0}; }
 
 template <typename T>
 struct DevBuf {
@@ -345,16 +352,11 @@ struct LabTrace {
     }
 };
 
-struct ArenaShard {
+struct ArenaShard : bsh::ShardStats {    // (max_staged_words, sum_words, fixed_m / fixed_k, geometry_uniform per kind)
     uint64_t *d_words = nullptr;
     DevDesc *d_desc = nullptr;
     uint32_t n_blocks = 0;          // local blocks
     uint64_t n_words = 0;
-    uint64_t max_staged_words[3] = {0, 0, 0};
-    uint64_t sum_words[3] = {0, 0, 0};  // present filters, for stream-byte accounting
-    uint64_t fixed_m[3] = {0, 0, 0};    // common m if all present filters share geometry, else 0
-    uint32_t fixed_k[3] = {0, 0, 0};
-    bool geometry_uniform[3] = {true, true, true};
 };
 
 struct Arena {
@@ -486,7 +488,6 @@ void arena_cache_destroy(bsg_ctx *ctx);
 int32_t ensure_lower_table(Device &d);   // ingest_api.inc: the unicode.ToLower table the walkers fold with
 
 struct SectionsOut { uint8_t *region; uint64_t cap; uint64_t *sec_off; };   // encode_api.inc
-uint64_t section_len(const bsg_filter_desc *d3);
 int32_t encode_sections_device(Device &d, const uint64_t *d_words, const bsg_filter_desc *desc, uint32_t n_blocks,
                                uint8_t *out_region, uint64_t region_cap, uint64_t *out_sec_off, float *ms);
 
@@ -563,24 +564,6 @@ int32_t run_parts(uint32_t n, F &&part)
     // g_err around a nested call, and the scope's slot (which a later part may have overwritten) all name the same failure
     for (uint32_t i = 0; i < n; ++i) if (rc[i]) return fail(rc[i], "%s", msg[i].empty() ? "a device part failed" : msg[i].c_str());
     return BSG_OK;
-}
-
-// cuts [0, n) items with the given costs into at most `parts` contiguous runs of about equal cost; returns the run
-// boundaries (size runs + 1).  `unit`: boundaries fall on multiples of it (3 = whole blocks of filters).
-std::vector<uint32_t> balanced_cuts(const std::vector<uint64_t> &cost, uint32_t parts, uint32_t unit = 1)
-{
-    const uint32_t n = (uint32_t)cost.size();
-    std::vector<uint32_t> cuts{0};
-    uint64_t total = 0;
-    for (uint64_t c : cost) total += c;
-    uint64_t acc = 0;
-    uint32_t made = 1;
-    for (uint32_t i = 0; i < n && made < parts; ++i) {
-        acc += cost[i];
-        if ((i + 1) % unit == 0 && i + 1 < n && acc * parts >= total * made) { cuts.push_back(i + 1); ++made; }
-    }
-    cuts.push_back(n);
-    return cuts;
 }
 
 void free_arena(bsg_ctx *ctx, Arena &a)
@@ -1048,55 +1031,137 @@ static int32_t enqueue_binned_build(Device &d, bsg::BinArgs a, bool dense, Scrat
     if (e != hipSuccess) return fail(BSG_E_HIP, "binned build: %s", hipGetErrorString(e));
     return BSG_OK;
 }
-// Binning pays from a few million locations on (three more launches, scratch from the pool); a bitset just beyond LDS with
-// a few ten thousand entries stays L2-resident under its atomics (1 000 such filters in one call: one k_build launch
-// instead of 5 000 small ones).
-static bool binned_build_fits(const bsg_ctx *root, uint64_t m, uint64_t n_entries, uint64_t k)
-{
-    const uint64_t n_locs = n_entries * k;
-    return m < (1ull << 31) && n_locs >= std::max<uint64_t>(root->bin_min_locs, 1) && n_locs < (1ull << 32) - 4096 &&
-           n_locs * 4 <= root->bin_scratch_bytes;
-}
+}  // extern "C"
 
-// One part of a build: filters [f0, f1) — whose entries [fstart[f0], fstart[f1]) are contiguous — on one device.  The
-// part's filters occupy words [w_lo, w_hi) of the caller's arena (disjoint from every other part's); sections: the part's
-// blocks f0 / 3 .. f1 / 3 are serialised at region + region_off (their offsets, relative to the part, into sec_off_local).
-struct BuildPart {
-    uint32_t f0 = 0, f1 = 0;
-    uint64_t w_lo = 0, w_hi = 0;
-    uint64_t region_off = 0, region_len = 0;
+namespace {
+
+// ---- what the two build routes share: entries (build_common below) and the tables of an ingest (ingest_api.inc) ----
+
+// One part of a build on one device: descriptors [i0, i1) of the call, whose filters occupy words [w_lo, w_hi) of the caller's
+// arena (disjoint from every other part's); sections: the part's blocks i0 / 3 .. i1 / 3 are serialised at region + region_off
+// (their offsets, relative to the part, into sec_off_local).
+struct BuildPart : bsh::PartSpan {
     std::vector<uint64_t> sec_off_local;
     float ms = 0.f, encode_ms = 0.f;
 };
 
-static int32_t build_on_device(bsg_ctx *ctx, Device &d, BuildPart &P, const uint8_t *bytes, const uint32_t *offsets, const uint64_t *h,
+// A part's device descriptors and the work its filters make: items of the route's build kernel (staged in LDS, or slices that
+// set bits with global atomics) and the filters that are binned.
+template <class Item>
+struct PartWork {
+    std::vector<DevDesc> dd;
+    std::vector<Item> items;
+    std::vector<uint32_t> binned;                  // bitsets beyond LDS: assembled window by window (bin_build.hip.h)
+    uint64_t max_staged = 0;
+    size_t lds_bytes() const { return std::max<uint64_t>(max_staged, 2) * 8; }
+};
+
+// local: the part's descriptors, word offsets into the part's own buffer.  lds_head_bytes: static LDS of the route's kernel
+// beside a staged bitset; n_entries(i): what filter i holds; emit(items, i, staged): filter i's item(s).
+template <class Item, class Count, class Emit>
+PartWork<Item> classify_part(const bsg_ctx *root, const std::vector<bsg_filter_desc> &local, uint32_t lds_head_bytes, Count &&n_entries, Emit &&emit)
+{
+    PartWork<Item> W;
+    W.dd.resize(local.size());
+    for (uint32_t i = 0; i < local.size(); ++i) {
+        W.dd[i] = dev_desc(local[i]);
+        if (local[i].m == 0) continue;
+        switch (bsh::build_route(local[i].m, n_entries(i), local[i].k, lds_head_bytes, root->bin_min_locs, root->bin_scratch_bytes)) {
+        case bsh::BuildRoute::Staged:
+            emit(W.items, i, true);
+            W.max_staged = std::max(W.max_staged, bsh::filter_words(local[i].m));
+            break;
+        case bsh::BuildRoute::Binned: W.binned.push_back(i); break;
+        case bsh::BuildRoute::Sliced: emit(W.items, i, false); break;
+        }
+    }
+    return W;
+}
+
+// A part's device time runs from the start of its first dispatch to the end of its last: first() hands the start event to
+// whichever dispatch comes first, last(true) the stop event to the one the caller knows to be the last.
+struct DispatchSpan {
+    hipEvent_t start = nullptr, stop = nullptr;
+    bool started = false;
+    hipEvent_t first() { hipEvent_t s = started ? nullptr : start; started = true; return s; }
+    hipEvent_t last(bool is_last) const { return is_last ? stop : nullptr; }
+};
+
+// The binned filters of a part, one after the other behind its staged launch.  fill(i, args): the route's source of filter i
+// (args.t, n_slots, n_locs_cap; the entries route hashes the filter's entries first).  d_over, where given: receives the overflow
+// word the filters share, for a caller that reads it back.
+template <class Fill>
+int32_t enqueue_binned_filters(Device &d, const std::vector<DevDesc> &dd, const std::vector<uint32_t> &binned, bool dense, Scratch &scratch,
+                                      DispatchSpan &span, uint32_t **d_over, Fill &&fill)
+{
+    if (binned.empty()) return BSG_OK;
+    uint32_t *over = nullptr;
+    HIP_TRY(scratch.alloc(&over, 64));
+    HIP_TRY(hipMemsetAsync(over, 0, 64, d.stream));
+    if (d_over) *d_over = over;
+    for (size_t bi = 0; bi < binned.size(); ++bi) {
+        bsg::BinArgs a{};
+        a.d = dd[binned[bi]];
+        a.overflow = over;
+        a.out = d.stage_words.p;
+        if (int32_t rc = fill(binned[bi], a)) return rc;
+        if (int32_t rc = enqueue_binned_build(d, a, dense, scratch, span.first(), span.last(bi + 1 == binned.size()))) return rc;
+    }
+    return BSG_OK;
+}
+
+// Where a part's words go from d.stage_words: with sections they never leave the device (encodeFilterSection runs there too),
+// without, [w_lo, w_hi) of the caller's arena is copied back.  Returns with the stream synchronised.
+int32_t deliver_part(Device &d, BuildPart &P, const std::vector<bsg_filter_desc> &local, uint64_t *out_words, const SectionsOut *sections)
+{
+    if (sections) {
+        P.sec_off_local.assign(local.size() / 3 + 1, 0);
+        return encode_sections_device(d, d.stage_words.p, local.data(), (uint32_t)(local.size() / 3), sections->region + P.region_off, P.region_len,
+                                      P.sec_off_local.data(), &P.encode_ms);
+    }
+    HIP_TRY(hipMemcpyAsync(out_words + P.w_lo, d.stage_words.p, (P.w_hi - P.w_lo) * 8, hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    return BSG_OK;
+}
+
+// a call's sections, all parts', must fit the region the caller gave
+int32_t check_region(uint64_t region_bytes, const SectionsOut *sections)
+{
+    if (sections && !bsh::region_fits(region_bytes, sections->cap))
+        return fail(BSG_E_INVALID, "section region needs %llu bytes, caller gave %llu", (unsigned long long)region_bytes, (unsigned long long)sections->cap);
+    return BSG_OK;
+}
+
+// The parts ran side by side: the call's device times are the slowest part's; every part's section offsets join the caller's.
+template <class Part>
+void fold_parts(const std::vector<Part> &parts, const SectionsOut *sections, float &ms, float &encode_ms)
+{
+    ms = encode_ms = 0.f;
+    for (const BuildPart &P : parts) {
+        ms = std::max(ms, P.ms);
+        encode_ms = std::max(encode_ms, P.encode_ms);
+        if (sections) bsh::scatter_sec_off(sections->sec_off, P, P.sec_off_local);
+    }
+}
+
+// ---- the entries route: filter f's entries are [fstart[f], fstart[f + 1]), contiguous over a part ----
+int32_t build_on_device(bsg_ctx *ctx, Device &d, BuildPart &P, const uint8_t *bytes, const uint32_t *offsets, const uint64_t *h,
                                const uint32_t *fstart, const bsg_filter_desc *desc, uint64_t *out_words, const SectionsOut *sections)
 {
-    const uint32_t f0 = P.f0, f1 = P.f1, nf = f1 - f0;
+    const uint32_t f0 = P.i0, f1 = P.i1, nf = f1 - f0;
     const uint32_t e0 = fstart[f0], e1 = fstart[f1], ne_all = e1 - e0;
     const uint32_t b0 = (!h && ne_all) ? offsets[e0] : 0, n_bytes = (!h && ne_all) ? offsets[e1] - b0 : 0;
     const uint64_t n_words = std::max<uint64_t>(P.w_hi - P.w_lo, 2);
-    std::vector<DevDesc> dd(nf);
-    std::vector<bsg_filter_desc> local(nf);          // the part's descriptors with word offsets relative to the part
-    std::vector<bsg::BuildItem> items;
-    std::vector<uint32_t> binned;                  // bitsets beyond LDS: assembled window by window (bin_build.hip.h)
-    uint64_t max_staged = 0;
-    for (uint32_t f = f0; f < f1; ++f) {
-        local[f - f0] = desc[f];
-        if (desc[f].m) local[f - f0].word_off = desc[f].word_off - P.w_lo;
-        dd[f - f0] = DevDesc{local[f - f0].word_off, desc[f].m, barrett_magic(desc[f].m), desc[f].k, 0};
-        if (desc[f].m == 0) continue;
-        const uint64_t nw = (desc[f].m + 63) / 64;
-        if (nw <= kLdsCapWords) {
-            items.push_back({f, fstart[f], fstart[f + 1], 1u});
-            max_staged = std::max(max_staged, nw);
-        } else if (binned_build_fits(ctx, desc[f].m, fstart[f + 1] - fstart[f], desc[f].k)) {
-            binned.push_back(f);
-        } else {
+    std::vector<bsg_filter_desc> local(desc + f0, desc + f1);          // the part's descriptors with word offsets relative to the part
+    for (bsg_filter_desc &f : local) if (f.m) f.word_off -= P.w_lo;
+    PartWork<bsg::BuildItem> W = classify_part<bsg::BuildItem>(ctx, local, 0, [&](uint32_t i) { return fstart[f0 + i + 1] - fstart[f0 + i]; },
+        [&](std::vector<bsg::BuildItem> &items, uint32_t i, bool staged) {
+            const uint32_t f = f0 + i;
+            if (staged) { items.push_back({f, fstart[f], fstart[f + 1], 1u}); return; }
             for (uint32_t e = fstart[f]; e < fstart[f + 1]; e += kBuildSliceEntries)
                 items.push_back({f, e, std::min(fstart[f + 1], e + kBuildSliceEntries), 0u});
-        }
-    }
+        });
+    std::vector<bsg::BuildItem> &items = W.items;
     // Longest first: workgroups are handed out in item order, so the few-entry items (a block's field filter: nine entries) fill the
     // tail of the launch instead of taking slots between the long ones.
     if (items.size() > 1)
@@ -1106,13 +1171,12 @@ static int32_t build_on_device(bsg_ctx *ctx, Device &d, BuildPart &P, const uint
     if (int32_t rc = use_device(d)) return rc;
     HIP_TRY(d.stage_words.reserve(n_words));
     HIP_TRY(hipMemsetAsync(d.stage_words.p, 0, n_words * 8, d.stream));
-    bool launched = false;
+    DispatchSpan span;
     Scratch scratch(d);
-    uint32_t *d_over = nullptr;
-    if (!items.empty() || !binned.empty()) {
+    if (!items.empty() || !W.binned.empty()) {
         HIP_TRY(d.stage_desc.reserve(nf));
         HIP_TRY(d.stage_items.reserve(std::max<size_t>(items.size(), 1)));
-        HIP_TRY(hipMemcpyAsync(d.stage_desc.p, dd.data(), dd.size() * sizeof(DevDesc), hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemcpyAsync(d.stage_desc.p, W.dd.data(), W.dd.size() * sizeof(DevDesc), hipMemcpyHostToDevice, d.stream));
         if (!items.empty())
             HIP_TRY(hipMemcpyAsync(d.stage_items.p, items.data(), items.size() * sizeof(bsg::BuildItem), hipMemcpyHostToDevice, d.stream));
         // Items keep the caller's ABSOLUTE entry and filter indices; the device arrays hold the part's run only, so their
@@ -1130,58 +1194,42 @@ static int32_t build_on_device(bsg_ctx *ctx, Device &d, BuildPart &P, const uint
                 HIP_TRY(hipMemcpyAsync(d.stage_off.p, offsets + e0, ((size_t)ne_all + 1) * 4, hipMemcpyHostToDevice, d.stream));
             a.bytes = d.stage_a.p - b0;
             a.off = d.stage_off.p - e0;
-            if (!binned.empty()) HIP_TRY(d.stage_h.reserve((size_t)std::max(ne_all, 1u) * 4));   // the binned filters' entries are hashed once, up front
+            if (!W.binned.empty()) HIP_TRY(d.stage_h.reserve((size_t)std::max(ne_all, 1u) * 4));   // the binned filters' entries are hashed once, up front
         }
         a.items = d.stage_items.p;
         a.desc = d.stage_desc.p - f0;
         a.out = d.stage_words.p;
-        const size_t lds = std::max<uint64_t>(max_staged, 2) * 8;
         if (!d.kb0) { HIP_TRY(hipEventCreate(&d.kb0)); HIP_TRY(hipEventCreate(&d.kb1)); }
-        // d.kb0 = start of the first dispatch, d.kb1 = end of the last one
-        auto first_ev = [&]() { hipEvent_t s = launched ? nullptr : d.kb0; launched = true; return s; };
+        span.start = d.kb0; span.stop = d.kb1;
         if (!items.empty()) {
-            hipExtLaunchKernelGGL(bsg::k_build, dim3((uint32_t)items.size()), dim3(bsg::kBuildThreads), (uint32_t)lds, d.stream,
-                                  first_ev(), binned.empty() ? d.kb1 : nullptr, 0, a);
+            hipExtLaunchKernelGGL(bsg::k_build, dim3((uint32_t)items.size()), dim3(bsg::kBuildThreads), (uint32_t)W.lds_bytes(), d.stream,
+                                  span.first(), span.last(W.binned.empty()), 0, a);
             HIP_TRY(hipGetLastError());
         }
-        if (!binned.empty()) {
-            HIP_TRY(scratch.alloc(&d_over, 64));
-            HIP_TRY(hipMemsetAsync(d_over, 0, 64, d.stream));
-        }
-        for (size_t bi = 0; bi < binned.size(); ++bi) {
-            const uint32_t f = binned[bi];
-            const uint32_t fe0 = fstart[f], ne = fstart[f + 1] - fstart[f];
-            uint64_t *hslot = d.stage_h.p + (size_t)(fe0 - e0) * 4;     // this filter's hashes inside the part's staging
-            if (!h) {
-                hipExtLaunchKernelGGL(bsg::k_hash_entries, dim3((ne + 255) / 256), dim3(256), 0, d.stream, first_ev(), nullptr, 0,
-                                      (const uint8_t *)d.stage_a.p - b0, (const uint32_t *)d.stage_off.p + (fe0 - e0), ne, hslot);
-                HIP_TRY(hipGetLastError());
-            }
-            bsg::BinArgs b{};
-            b.t = bsg::IngestTable{hslot, nullptr, 0, 0};      // (a dense list of hashes: never inserted into)
-            b.d = dd[f - f0];
-            b.n_slots = ne;
-            b.n_locs_cap = (uint32_t)((uint64_t)ne * desc[f].k);
-            b.overflow = d_over;
-            b.out = d.stage_words.p;
-            if (int32_t rc = enqueue_binned_build(d, b, true, scratch, first_ev(), bi + 1 == binned.size() ? d.kb1 : nullptr)) return rc;
-        }
+        // The overflow word is never read back here: n_locs_cap is the filter's exact entries x k, so the binning passes cannot
+        // run over it.  (The tables route sizes it from counts taken earlier and does read it: ingest_api.inc, build_part.)
+        if (int32_t rc = enqueue_binned_filters(d, W.dd, W.binned, true, scratch, span, nullptr, [&](uint32_t i, bsg::BinArgs &b) -> int32_t {
+                const uint32_t f = f0 + i, fe0 = fstart[f], ne = fstart[f + 1] - fstart[f];
+                uint64_t *hslot = d.stage_h.p + (size_t)(fe0 - e0) * 4;     // this filter's hashes inside the part's staging
+                if (!h) {
+                    hipExtLaunchKernelGGL(bsg::k_hash_entries, dim3((ne + 255) / 256), dim3(256), 0, d.stream, span.first(), nullptr, 0,
+                                          (const uint8_t *)d.stage_a.p - b0, (const uint32_t *)d.stage_off.p + (fe0 - e0), ne, hslot);
+                    HIP_TRY(hipGetLastError());
+                }
+                b.t = bsg::IngestTable{hslot, nullptr, 0, 0};      // (a dense list of hashes: never inserted into)
+                b.n_slots = ne;
+                b.n_locs_cap = (uint32_t)((uint64_t)ne * desc[f].k);
+                return BSG_OK;
+            })) return rc;
     }
-    if (sections) {      // the words never leave the device: encodeFilterSection runs there too
-        P.sec_off_local.assign((size_t)nf / 3 + 1, 0);
-        if (int32_t rc = encode_sections_device(d, d.stage_words.p, local.data(), nf / 3, sections->region + P.region_off, P.region_len,
-                                                P.sec_off_local.data(), &P.encode_ms)) return rc;
-    } else {
-        HIP_TRY(hipMemcpyAsync(out_words + P.w_lo, d.stage_words.p, (P.w_hi - P.w_lo) * 8, hipMemcpyDeviceToHost, d.stream));
-        HIP_TRY(hipStreamSynchronize(d.stream));
-    }
-    scratch.done();      // either branch above has synchronised the stream
+    if (int32_t rc = deliver_part(d, P, local, out_words, sections)) return rc;
+    scratch.done();      // deliver_part has synchronised the stream on either way out
     P.ms = 0.f;
-    if (launched) HIP_TRY(hipEventElapsedTime(&P.ms, d.kb0, d.kb1));
+    if (span.started) HIP_TRY(hipEventElapsedTime(&P.ms, d.kb0, d.kb1));
     return BSG_OK;
 }
 
-static int32_t build_common(bsg_ctx *ctx, const uint8_t *bytes, const uint32_t *offsets, const uint64_t *h,
+int32_t build_common(bsg_ctx *ctx, const uint8_t *bytes, const uint32_t *offsets, const uint64_t *h,
                             uint32_t n_entries, const uint32_t *fstart, const bsg_filter_desc *desc,
                             uint32_t n_filters, uint64_t *out_words, uint64_t n_words, const SectionsOut *sections = nullptr)
 {
@@ -1205,14 +1253,7 @@ static int32_t build_common(bsg_ctx *ctx, const uint8_t *bytes, const uint32_t *
     const uint32_t nd = (uint32_t)ctx->devs.size();
     const uint32_t unit = sections ? 3u : 1u;
     uint32_t want_parts = (nd > 1 && n_entries >= ctx->shard_min_entries) ? std::min<uint32_t>(nd, n_filters / unit) : 1;
-    if (want_parts > 1) {
-        uint64_t prev_end = 0;
-        for (uint32_t f = 0; f < n_filters && want_parts > 1; ++f) {
-            if (desc[f].m == 0) continue;
-            if (desc[f].word_off < prev_end) want_parts = 1;
-            prev_end = desc[f].word_off + (desc[f].m + 63) / 64;
-        }
-    }
+    if (want_parts > 1 && !bsh::offsets_ascend(desc, n_filters)) want_parts = 1;
     std::vector<uint32_t> cuts{0, n_filters};
     if (want_parts > 1) {
         std::vector<uint64_t> cost(n_filters);
@@ -1221,47 +1262,24 @@ static int32_t build_common(bsg_ctx *ctx, const uint8_t *bytes, const uint32_t *
     }
     const uint32_t n_parts = (uint32_t)cuts.size() - 1;
     std::vector<BuildPart> parts(n_parts);
-    uint64_t region_cursor = 0;
-    for (uint32_t i = 0; i < n_parts; ++i) {
-        BuildPart &P = parts[i];
-        P.f0 = cuts[i]; P.f1 = cuts[i + 1];
-        uint64_t lo = ~0ull, hi = 0;
-        for (uint32_t f = P.f0; f < P.f1; ++f) {
-            if (desc[f].m == 0) continue;
-            lo = std::min(lo, desc[f].word_off);
-            hi = std::max(hi, desc[f].word_off + (desc[f].m + 63) / 64);
-        }
-        if (lo == ~0ull) lo = hi = 0;
-        if (n_parts == 1) { lo = 0; hi = n_words; }          // the single-device call keeps its round-1 contract: the whole arena comes back, zero-filled
-        P.w_lo = lo; P.w_hi = hi;
-        if (sections) {
-            P.region_off = region_cursor;
-            for (uint32_t b = P.f0 / 3; b < P.f1 / 3; ++b) P.region_len += section_len(desc + (size_t)b * 3);
-            region_cursor += P.region_len;
-        }
-    }
-    if (sections && region_cursor > sections->cap)
-        return fail(BSG_E_INVALID, "section region needs %llu bytes, caller gave %llu", (unsigned long long)region_cursor, (unsigned long long)sections->cap);
-    if (!sections && n_parts > 1) {                            // words no part owns (gaps, absent filters) are zero, as the single-device call leaves them
-        uint64_t at = 0;
-        for (const BuildPart &P : parts) { if (P.w_lo > at) memset(out_words + at, 0, (P.w_lo - at) * 8); at = std::max(at, P.w_hi); }
-        if (n_words > at) memset(out_words + at, 0, (n_words - at) * 8);
-    }
+    for (uint32_t i = 0; i < n_parts; ++i) { parts[i].i0 = cuts[i]; parts[i].i1 = cuts[i + 1]; }
+    if (int32_t rc = check_region(bsh::plan_parts(desc, parts, n_words, sections != nullptr), sections)) return rc;
+    if (!sections && n_parts > 1) bsh::zero_unowned(out_words, n_words, parts);
     const uint32_t first = n_parts == 1 ? pick_device(ctx) : 0;
     if (int32_t rc = run_parts(n_parts, [&](uint32_t i) -> int32_t {
             return build_on_device(ctx, *ctx->devs[(first + i) % nd], parts[i], bytes, offsets, h, fstart, desc, out_words, sections);
         })) return rc;
     float ms = 0.f, ems = 0.f;
-    for (const BuildPart &P : parts) { ms = std::max(ms, P.ms); ems = std::max(ems, P.encode_ms); }
-    if (sections) {
-        for (const BuildPart &P : parts)
-            for (uint32_t b = P.f0 / 3; b <= P.f1 / 3; ++b) sections->sec_off[b] = P.region_off + P.sec_off_local[b - P.f0 / 3];
-    }
+    fold_parts(parts, sections, ms, ems);
     std::lock_guard<std::shared_mutex> lk(ctx->mu);
     ctx->last_build_ms = ms;
     if (sections) ctx->last_encode_ms = ems;
     return BSG_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int32_t bsg_build(bsg_ctx *ctx, const uint8_t *bytes, const uint32_t *offsets, uint32_t n_entries,
                   const uint32_t *filter_entry_start, const bsg_filter_desc *desc, uint32_t n_filters,
@@ -1298,28 +1316,14 @@ int32_t bsg_arena_load(bsg_ctx *ctx, const uint64_t *words, uint64_t n_words, co
     for (uint32_t di = 0; di < nd && e == hipSuccess; ++di) {
         ArenaShard &s = arena->shards[di];
         Device &d = *ctx->devs[di];
-        s.n_blocks = n_blocks > di ? (n_blocks - di + nd - 1) / nd : 0;
         // re-lay the shard's filters on 128-byte boundaries
+        const bsh::ShardLayout L = bsh::layout_shard(desc, n_blocks, di, nd);
+        static_cast<bsh::ShardStats &>(s) = L.stats;
+        s.n_blocks = L.n_blocks;
+        s.n_words = L.n_words;
         std::vector<DevDesc> &dd = descs[di];
-        dd.resize((size_t)s.n_blocks * 3);
-        uint64_t cursor = 0;
-        for (uint32_t lb = 0; lb < s.n_blocks; ++lb) {
-            const uint32_t b = lb * nd + di;
-            for (uint32_t c = 0; c < 3; ++c) {
-                const bsg_filter_desc &f = desc[(size_t)b * 3 + c];
-                DevDesc &o = dd[(size_t)lb * 3 + c];
-                o = DevDesc{0, f.m, barrett_magic(f.m), f.k, 0};
-                if (f.m == 0) continue;
-                const uint64_t nw = (f.m + 63) / 64;
-                o.word_off = cursor;
-                cursor += (nw + kAlignWords - 1) / kAlignWords * kAlignWords;
-                s.sum_words[c] += nw;
-                if (nw <= kLdsCapWords) s.max_staged_words[c] = std::max(s.max_staged_words[c], nw);
-                if (s.fixed_m[c] == 0 && s.geometry_uniform[c]) { s.fixed_m[c] = f.m; s.fixed_k[c] = f.k; }
-                else if (s.fixed_m[c] != f.m || s.fixed_k[c] != f.k) s.geometry_uniform[c] = false;
-            }
-        }
-        s.n_words = cursor + kAlignWords;
+        dd.resize(L.filters.size());
+        std::transform(L.filters.begin(), L.filters.end(), dd.begin(), dev_desc);
         // one repacked host image -> one H2D copy (the caller's pointers are not retained)
         std::vector<uint64_t> &image = images[di];
         image.assign(s.n_words, 0);

@@ -2,15 +2,6 @@
 
 namespace {
 
-// Section sizes are a function of the geometry alone: 1 + sum over present filters (4 + 24 + 8 * ceil(m/64)) + 4.
-uint64_t section_len(const bsg_filter_desc *d3)
-{
-    uint64_t len = 1 + 4;
-    for (int c = 0; c < 3; ++c)
-        if (d3[c].m) len += 4 + 24 + 8 * ((d3[c].m + 63) / 64);
-    return len;
-}
-
 // d_words: device word arena the descriptors' word_off point into.  Caller holds d.mu and has set the device.
 int32_t encode_sections_device(Device &d, const uint64_t *d_words, const bsg_filter_desc *desc, uint32_t n_blocks,
                                uint8_t *out_region, uint64_t region_cap, uint64_t *out_sec_off, float *ms)

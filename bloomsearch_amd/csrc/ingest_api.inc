@@ -862,13 +862,6 @@ struct ArenaPlan {
     uint64_t *out_id = nullptr;
 };
 
-uint64_t block_span_words(const bsg_filter_desc *d3)
-{
-    uint64_t w = 0;
-    for (uint32_t c = 0; c < 3; ++c) if (d3[c].m) w += ((d3[c].m + 63) / 64 + kAlignWords - 1) / kAlignWords * kAlignWords;
-    return w;
-}
-
 int32_t plan_arena(bsg_ctx *ctx, const bsg_filter_desc *desc, uint32_t n_blocks, ArenaPlan &plan)
 {
     const uint32_t nd = (uint32_t)ctx->devs.size();
@@ -879,30 +872,14 @@ int32_t plan_arena(bsg_ctx *ctx, const bsg_filter_desc *desc, uint32_t n_blocks,
     hipError_t e = hipSuccess;
     for (uint32_t di = 0; di < nd && e == hipSuccess; ++di) {
         ArenaShard &s = plan.arena->shards[di];
-        const uint32_t n_local = n_blocks > di ? (n_blocks - di + nd - 1) / nd : 0;
-        s.n_blocks = n_local;
-        std::vector<DevDesc> dd((size_t)n_local * 3);
-        uint64_t cursor = 0;
-        for (uint32_t lb = 0; lb < n_local; ++lb) {
-            const uint32_t b = lb * nd + di;
-            plan.dst_off[b] = cursor;
-            uint64_t at = cursor;
-            for (uint32_t c = 0; c < 3; ++c) {
-                const bsg_filter_desc &f = desc[(size_t)b * 3 + c];
-                DevDesc &o = dd[(size_t)lb * 3 + c];
-                o = DevDesc{0, f.m, barrett_magic(f.m), f.k, 0};
-                if (f.m == 0) continue;
-                const uint64_t nw = (f.m + 63) / 64;
-                o.word_off = at;
-                at += (nw + kAlignWords - 1) / kAlignWords * kAlignWords;
-                s.sum_words[c] += nw;
-                if (nw <= kLdsCapWords) s.max_staged_words[c] = std::max(s.max_staged_words[c], nw);
-                if (s.fixed_m[c] == 0 && s.geometry_uniform[c]) { s.fixed_m[c] = f.m; s.fixed_k[c] = f.k; }
-                else if (s.fixed_m[c] != f.m || s.fixed_k[c] != f.k) s.geometry_uniform[c] = false;
-            }
-            cursor = at;
-        }
-        s.n_words = cursor + kAlignWords;
+        const bsh::ShardLayout L = bsh::layout_shard(desc, n_blocks, di, nd);
+        static_cast<bsh::ShardStats &>(s) = L.stats;
+        s.n_blocks = L.n_blocks;
+        s.n_words = L.n_words;
+        for (uint32_t lb = 0; lb < L.n_blocks; ++lb) plan.dst_off[lb * nd + di] = L.block_off[lb];
+        std::vector<DevDesc> dd(L.filters.size());
+        std::transform(L.filters.begin(), L.filters.end(), dd.begin(), dev_desc);
+        const uint64_t cursor = L.n_words - kAlignWords;
         e = hipSetDevice(ctx->devs[di]->id);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s.d_words), s.n_words * 8);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s.d_desc), std::max<size_t>(dd.size(), 1) * sizeof(DevDesc));
@@ -929,7 +906,7 @@ int32_t fill_arena(bsg_ctx *ctx, Device &d, const uint64_t *d_words, const bsg_f
         uint64_t lo = ~0ull;
         for (uint32_t c = 0; c < 3; ++c) if (d3[c].m) lo = std::min(lo, d3[c].word_off);
         if (lo == ~0ull) continue;
-        const uint64_t words = block_span_words(d3);
+        const uint64_t words = bsh::block_span_words(d3);
         const uint32_t di = b % nd;
         if (!spans.empty() && spans.back().di == di && spans.back().src + spans.back().words == lo && spans.back().dst + spans.back().words == plan.dst_off[b])
             spans.back().words += words;                              // (one device: neighbouring blocks merge into one copy)
@@ -945,14 +922,11 @@ int32_t fill_arena(bsg_ctx *ctx, Device &d, const uint64_t *d_words, const bsg_f
     return BSG_OK;
 }
 
-// What one part contributes to a build: tables [t0, t1) of part G are the caller's tables [g0, g0 + t1 - t0).
-struct PartBuild {
+// What one part contributes to a build: tables [t0, t1) of part G are the caller's tables [i0, i1).
+struct PartBuild : BuildPart {
     IngestPart *G = nullptr;
-    uint32_t t0 = 0, t1 = 0, g0 = 0;
-    uint64_t w_lo = 0, w_hi = 0;              // words route: the part's filters occupy [w_lo, w_hi) of the caller's arena
-    uint64_t region_off = 0, region_len = 0;  // sections route
-    std::vector<uint64_t> sec_off_local;
-    float ms_build = 0.f, ms_encode = 0.f;
+    uint32_t t0 = 0, t1 = 0;
+    PartBuild(IngestPart *g, uint32_t t1_, uint32_t i0_) : G(g), t1(t1_) { i0 = i0_; i1 = i0_ + t1_; }
 };
 
 int32_t build_part(bsg_ctx *ctx, PartBuild &B, const bsg_filter_desc *desc_in, uint64_t *out_words, const SectionsOut *sections,
@@ -963,94 +937,70 @@ int32_t build_part(bsg_ctx *ctx, PartBuild &B, const bsg_filter_desc *desc_in, u
     if (nt == 0) return BSG_OK;
     // the part's descriptors: word offsets relative to the part (words route) or a layout of its own (sections route: every
     // filter on a 128-byte boundary, so a run of blocks becomes a resident arena with plain copies)
-    std::vector<bsg_filter_desc> local(desc_in + B.g0, desc_in + B.g0 + nt);
+    std::vector<bsg_filter_desc> local(desc_in + B.i0, desc_in + B.i1);
     uint64_t n_words = 2;
     if (sections) {
         uint64_t cursor = 0;
-        for (uint32_t i = 0; i < nt; ++i) {
-            local[i].word_off = cursor;
-            if (local[i].m) cursor += ((local[i].m + 63) / 64 + kAlignWords - 1) / kAlignWords * kAlignWords;
-        }
+        for (bsg_filter_desc &f : local) { f.word_off = cursor; cursor += bsh::aligned_words(f.m); }
         n_words = std::max<uint64_t>(cursor, 2);
     } else {
-        for (uint32_t i = 0; i < nt; ++i) if (local[i].m) local[i].word_off -= B.w_lo;
+        for (bsg_filter_desc &f : local) if (f.m) f.word_off -= B.w_lo;
         n_words = std::max<uint64_t>(B.w_hi - B.w_lo, 2);
     }
-    std::vector<DevDesc> dd(nt);
-    std::vector<bsg::SetBuildItem> items;
-    std::vector<uint32_t> binned;                 // filters too large for LDS: assembled window by window (bin_build.hip.h)
-    uint64_t max_staged = 0;
-    for (uint32_t i = 0; i < nt; ++i) {
-        const uint32_t t = B.t0 + i;
-        dd[i] = DevDesc{local[i].word_off, local[i].m, barrett_magic(local[i].m), local[i].k, 0};
-        if (local[i].m == 0) continue;
-        const uint64_t nw = (local[i].m + 63) / 64, cap = (uint64_t)G.tables[t].mask + 1;
-        if (nw * 8 + bsg::kSetListBytes <= kLdsBudget) {          // the bitset beside the kernel's compaction list
-            items.push_back({t, 1u, 0, cap});
-            max_staged = std::max(max_staged, nw);
-        } else if (binned_build_fits(ctx, local[i].m, G.counts[t], local[i].k)) {
-            binned.push_back(i);
-        } else {
-            const uint64_t slice = (uint64_t)kBuildSliceEntries * 4;
+    // a staged bitset sits beside k_build_sets' compaction list in LDS; a sliced table is cut by slots, four per entry of a slice
+    PartWork<bsg::SetBuildItem> W = classify_part<bsg::SetBuildItem>(ctx, local, bsg::kSetListBytes, [&](uint32_t i) { return G.counts[B.t0 + i]; },
+        [&](std::vector<bsg::SetBuildItem> &items, uint32_t i, bool staged) {
+            const uint32_t t = B.t0 + i;
+            const uint64_t cap = (uint64_t)G.tables[t].mask + 1, slice = (uint64_t)kBuildSliceEntries * 4;
+            if (staged) { items.push_back({t, 1u, 0, cap}); return; }
             for (uint64_t s = 0; s < cap; s += slice) items.push_back({t, 0u, s, std::min(cap, s + slice)});
-        }
-    }
+        });
+    const std::vector<bsg::SetBuildItem> &items = W.items;
     Device &d = *G.dev;
     std::lock_guard<std::mutex> lk(d.mu);
     if (int32_t rc = use_device(d)) return rc;
     HIP_TRY(d.stage_words.reserve(n_words));
     HIP_TRY(hipMemsetAsync(d.stage_words.p, 0, n_words * 8, d.stream));
-    if (!items.empty() || !binned.empty()) {
+    if (!items.empty() || !W.binned.empty()) {
         HIP_TRY(d.stage_desc.reserve(nt));
-        HIP_TRY(hipMemcpyAsync(d.stage_desc.p, dd.data(), dd.size() * sizeof(DevDesc), hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemcpyAsync(d.stage_desc.p, W.dd.data(), W.dd.size() * sizeof(DevDesc), hipMemcpyHostToDevice, d.stream));
         Scratch scratch(d);
         bsg::SetBuildItem *d_items = nullptr;
         HIP_TRY(scratch.alloc(&d_items, std::max<size_t>(items.size(), 1) * sizeof(bsg::SetBuildItem)));
         EventList ev;
         HIP_TRY(ev.add(2));
         if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::SetBuildItem), hipMemcpyHostToDevice, d.stream));
-        // ev.v[0] = start of the first dispatch, ev.v[1] = end of the last one
-        bool started = false;
-        auto start_ev = [&]() { hipEvent_t s = started ? nullptr : ev.v[0]; started = true; return s; };
+        DispatchSpan span{ev.v[0], ev.v[1]};
         if (!items.empty()) {
             // items name the part's own table indices; the descriptor array holds tables [t0, t1) only: its base moves back by t0
             bsg::SetBuildArgs a{G.d_tables, d_items, d.stage_desc.p - B.t0, d.stage_words.p};
-            const size_t lds = std::max<uint64_t>(max_staged, 2) * 8;
-            hipExtLaunchKernelGGL(bsg::k_build_sets, dim3((uint32_t)items.size()), dim3(bsg::kBuildSetsThreads), (uint32_t)lds, d.stream,
-                                  start_ev(), binned.empty() ? ev.v[1] : nullptr, 0, a);
+            hipExtLaunchKernelGGL(bsg::k_build_sets, dim3((uint32_t)items.size()), dim3(bsg::kBuildSetsThreads), (uint32_t)W.lds_bytes(), d.stream,
+                                  span.first(), span.last(W.binned.empty()), 0, a);
             HIP_TRY(hipGetLastError());
         }
         uint32_t *d_over = nullptr;
-        if (!binned.empty()) {
-            HIP_TRY(scratch.alloc(&d_over, 64));
-            HIP_TRY(hipMemsetAsync(d_over, 0, 64, d.stream));
-        }
-        for (size_t bi = 0; bi < binned.size(); ++bi) {
-            const uint32_t i = binned[bi], t = B.t0 + i;
-            bsg::BinArgs a{};
-            a.t = G.tables[t];
-            a.d = dd[i];
-            a.n_slots = (uint64_t)G.tables[t].mask + 1;
-            a.n_locs_cap = (uint32_t)((uint64_t)G.counts[t] * local[i].k);
-            a.overflow = d_over;
-            a.out = d.stage_words.p;
-            if (int32_t rc = enqueue_binned_build(d, a, false, scratch, start_ev(), bi + 1 == binned.size() ? ev.v[1] : nullptr)) return rc;
-        }
+        if (int32_t rc = enqueue_binned_filters(d, W.dd, W.binned, false, scratch, span, &d_over, [&](uint32_t i, bsg::BinArgs &a) -> int32_t {
+                const uint32_t t = B.t0 + i;
+                a.t = G.tables[t];
+                a.n_slots = (uint64_t)G.tables[t].mask + 1;
+                a.n_locs_cap = (uint32_t)((uint64_t)G.counts[t] * local[i].k);
+                return BSG_OK;
+            })) return rc;
         HIP_TRY(hipStreamSynchronize(d.stream));
         scratch.done();
-        (void)hipEventElapsedTime(&B.ms_build, ev.v[0], ev.v[1]);
+        (void)hipEventElapsedTime(&B.ms, ev.v[0], ev.v[1]);
+        // n_locs_cap comes from the counts bsg_ingest_finish read, and entries may have joined the tables since: the binning passes
+        // flag what did not fit, and the call fails on it.  (The entries route counts exactly and has nothing to read.)
         if (d_over) {
             uint32_t over = 0;
             HIP_TRY(hipMemcpy(&over, d_over, 4, hipMemcpyDeviceToHost));
             if (over) return fail(BSG_E_INVALID, "a set holds more entries than bsg_ingest_finish counted");
         }
     }
+    if (int32_t rc = deliver_part(d, B, local, out_words, sections)) return rc;
     if (sections) {
-        B.sec_off_local.assign((size_t)nt / 3 + 1, 0);
-        if (int32_t rc = encode_sections_device(d, d.stage_words.p, local.data(), nt / 3, sections->region + B.region_off, B.region_len,
-                                                B.sec_off_local.data(), &B.ms_encode)) return rc;
-        // the caller's tables [g0, g0 + nt) are blocks g0 / 3 ...: sets first, parents after
-        const uint32_t blk0 = B.g0 / 3, blk1 = blk0 + nt / 3;
+        // the caller's tables [i0, i1) are blocks i0 / 3 ...: sets first, parents after
+        const uint32_t blk0 = B.i0 / 3, blk1 = blk0 + nt / 3;
         if (sets_plan && blk0 < n_sets_global) {
             const uint32_t e1 = std::min(blk1, n_sets_global);
             if (int32_t rc = fill_arena(ctx, d, d.stage_words.p, local.data(), blk0, e1, *sets_plan)) return rc;
@@ -1059,10 +1009,7 @@ int32_t build_part(bsg_ctx *ctx, PartBuild &B, const bsg_filter_desc *desc_in, u
             const uint32_t s0 = std::max(blk0, n_sets_global);
             if (int32_t rc = fill_arena(ctx, d, d.stage_words.p, local.data() + (size_t)(s0 - blk0) * 3, s0 - n_sets_global, blk1 - n_sets_global, *parents_plan)) return rc;
         }
-        return BSG_OK;
     }
-    HIP_TRY(hipMemcpyAsync(out_words + B.w_lo, d.stage_words.p, (B.w_hi - B.w_lo) * 8, hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(hipStreamSynchronize(d.stream));
     return BSG_OK;
 }
 
@@ -1083,61 +1030,17 @@ int32_t ingest_build_common(bsg_ctx *ctx, uint64_t ingest_id, const bsg_filter_d
     // ---- who builds what: every part its sets; the parents by the merged part (several parts) or by the only part ----
     std::vector<PartBuild> jobs;
     if (I.parts.size() == 1) {
-        PartBuild B;
-        B.G = I.parts[0].get(); B.t0 = 0; B.t1 = I.parts[0]->n_tables(); B.g0 = 0;       // sets and parents in one go
-        jobs.push_back(std::move(B));
+        jobs.emplace_back(I.parts[0].get(), I.parts[0]->n_tables(), 0u);       // sets and parents in one go
     } else {
-        for (auto &p : I.parts) {
-            PartBuild B;
-            B.G = p.get(); B.t0 = 0; B.t1 = p->n_sets * 3; B.g0 = p->set0 * 3;
-            jobs.push_back(std::move(B));
-        }
-        if (I.merged) {
-            PartBuild B;
-            B.G = I.merged.get(); B.t0 = 0; B.t1 = I.n_parents * 3; B.g0 = I.n_sets * 3;
-            jobs.push_back(std::move(B));
-        }
+        for (auto &p : I.parts) jobs.emplace_back(p.get(), p->n_sets * 3, p->set0 * 3);
+        if (I.merged) jobs.emplace_back(I.merged.get(), I.n_parents * 3, I.n_sets * 3);
     }
     // words route: a job owns the words [first filter, end of last filter) of the caller's arena: the layout must ascend
-    // with the table index, or the jobs' copies back would overlap — then every job copies back the whole arena in turn
-    bool disjoint = true;
-    if (!sections) {
-        uint64_t prev_end = 0;
-        for (uint32_t t = 0; t < nt && disjoint; ++t) {
-            if (desc[t].m == 0) continue;
-            if (desc[t].word_off < prev_end) disjoint = false;
-            prev_end = desc[t].word_off + (desc[t].m + 63) / 64;
-        }
-        if (!disjoint && jobs.size() > 1)
-            return fail(BSG_E_UNSUPPORTED, "an ingest cut over %zu devices needs filter word offsets that ascend with the table index", jobs.size());
-    }
-    uint64_t region_cursor = 0;
-    for (PartBuild &B : jobs) {
-        const uint32_t n = B.t1 - B.t0;
-        if (sections) {
-            B.region_off = region_cursor;
-            for (uint32_t b = B.g0 / 3; b < (B.g0 + n) / 3; ++b) B.region_len += section_len(desc + (size_t)b * 3);
-            region_cursor += B.region_len;
-        } else if (jobs.size() == 1) {
-            B.w_lo = 0; B.w_hi = n_words;        // the whole arena comes back, zero-filled between the filters (round-1 contract)
-        } else {
-            uint64_t lo = ~0ull, hi = 0;
-            for (uint32_t t = B.g0; t < B.g0 + n; ++t) {
-                if (desc[t].m == 0) continue;
-                lo = std::min(lo, desc[t].word_off);
-                hi = std::max(hi, desc[t].word_off + (desc[t].m + 63) / 64);
-            }
-            if (lo == ~0ull) lo = hi = 0;
-            B.w_lo = lo; B.w_hi = hi;
-        }
-    }
-    if (sections && region_cursor > sections->cap)
-        return fail(BSG_E_INVALID, "section region needs %llu bytes, caller gave %llu", (unsigned long long)region_cursor, (unsigned long long)sections->cap);
-    if (!sections && jobs.size() > 1) {
-        uint64_t at = 0;
-        for (const PartBuild &B : jobs) { if (B.w_lo > at) memset(out_words + at, 0, (B.w_lo - at) * 8); at = std::max(at, B.w_hi); }
-        if (n_words > at) memset(out_words + at, 0, (n_words - at) * 8);
-    }
+    // with the table index, or the jobs' copies back would overlap
+    if (!sections && jobs.size() > 1 && !bsh::offsets_ascend(desc, nt))
+        return fail(BSG_E_UNSUPPORTED, "an ingest cut over %zu devices needs filter word offsets that ascend with the table index", jobs.size());
+    if (int32_t rc = check_region(bsh::plan_parts(desc, jobs, n_words, sections != nullptr), sections)) return rc;
+    if (!sections && jobs.size() > 1) bsh::zero_unowned(out_words, n_words, jobs);
     ArenaPlan sets_plan, parents_plan;
     if (sections && out_sets_arena) { *out_sets_arena = 0; if (int32_t rc = plan_arena(ctx, desc, I.n_sets, sets_plan)) return rc; }
     if (sections && out_parents_arena) {
@@ -1155,12 +1058,7 @@ int32_t ingest_build_common(bsg_ctx *ctx, uint64_t ingest_id, const bsg_filter_d
         if (parents_plan.arena) free_arena(ctx, *parents_plan.arena);
         return rc;
     }
-    I.ms_build = I.ms_encode = 0.f;
-    for (const PartBuild &B : jobs) { I.ms_build = std::max(I.ms_build, B.ms_build); I.ms_encode = std::max(I.ms_encode, B.ms_encode); }
-    if (sections) {
-        for (const PartBuild &B : jobs)
-            for (uint32_t b = 0; b <= (B.t1 - B.t0) / 3; ++b) sections->sec_off[B.g0 / 3 + b] = B.region_off + B.sec_off_local[b];
-    }
+    fold_parts(jobs, sections, I.ms_build, I.ms_encode);
     {
         std::lock_guard<std::shared_mutex> lk(ctx->mu);
         if (sections) ctx->last_encode_ms = I.ms_encode;

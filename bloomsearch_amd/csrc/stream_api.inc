@@ -216,7 +216,7 @@ int32_t stream_begin(bsg_ctx *ctx, const uint64_t *sec_begin, const uint64_t *se
     // every device's slot table is laid out (and rejected, if the metadata is bad) before anything is allocated
     for (uint32_t di = 0; di < nd; ++di) {
         StreamDev &s = st->dev[di];
-        const uint32_t n_local = n_blocks > di ? (n_blocks - di + nd - 1) / nd : 0;
+        const uint32_t n_local = bsh::shard_blocks(n_blocks, di, nd);
         s.shard.n_blocks = n_local;
         // this device's sections in file order
         std::vector<uint32_t> idx;
@@ -308,15 +308,7 @@ int32_t stream_finish(bsg_ctx *ctx, ArenaStream &st, int32_t *out_status, uint64
             if (!s.decoded[i] && s.slots[i].len != 0) out_status[s.global_block[i]] = kSectionUnread;
         ArenaShard &sh = s.shard;
         for (uint32_t lb = 0; lb < n_local; ++lb)
-            for (uint32_t c = 0; c < 3; ++c) {
-                const DevDesc &f = dd[(size_t)lb * 3 + c];
-                if (f.m == 0) continue;
-                const uint64_t nw = (f.m + 63) / 64;
-                sh.sum_words[c] += nw;
-                if (nw <= kLdsCapWords) sh.max_staged_words[c] = std::max(sh.max_staged_words[c], nw);
-                if (sh.fixed_m[c] == 0 && sh.geometry_uniform[c]) { sh.fixed_m[c] = f.m; sh.fixed_k[c] = f.k; }
-                else if (sh.fixed_m[c] != f.m || sh.fixed_k[c] != f.k) sh.geometry_uniform[c] = false;
-            }
+            for (uint32_t c = 0; c < 3; ++c) sh.add_filter(c, dd[(size_t)lb * 3 + c].m, dd[(size_t)lb * 3 + c].k);
         float ms = 0.f;
         for (auto &t : s.timers) { float x = 0.f; if (hipEventElapsedTime(&x, t.first, t.second) == hipSuccess) ms += x; }
         { std::lock_guard<std::shared_mutex> lk2(ctx->mu); ctx->last_decode_ms = di == 0 ? ms : std::max(ctx->last_decode_ms, ms); }

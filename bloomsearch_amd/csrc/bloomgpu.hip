@@ -18,6 +18,7 @@
 #include "host/regex_dfa.hpp"  // FieldRegex patterns -> the DFA tables k_match_rows_regex steps
 #include "host/regex_groups.hpp"  // the regex table blob, user masks and limits shared with the engine mirror
 #include "host/row_chunks.hpp" // the chunk plan and byte ranges RowUpload copies by
+#include "host/wide_plan.hpp"  // bsg_match_rows_wide: pair words, condition masks, part cuts and evaluation items
 #include "host/text.hpp"   // the host walker's Unicode tables: the device defers to the same data
 #include <hip/hip_ext.h>
 
@@ -810,6 +811,10 @@ int32_t bsg_open(const int32_t *device_ids, int32_t n_devices, bsg_ctx **out_ctx
                                     bsg::kMatchManyLdsBytes + bsg::kRxManyLdsCap));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_match_rows_many_regex_tok), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     bsg::kMatchManyLdsBytes + bsg::kRxManyLdsCap));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_match_rows_store_regex), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    bsg::kMatchWideLdsBytes + bsg::kRxWideLdsCap));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_match_rows_store_regex_tok), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    bsg::kMatchWideLdsBytes + bsg::kRxWideLdsCap));
 
         ctx->devs.push_back(std::move(d));
     }

@@ -28,6 +28,7 @@
 #include "expression.hpp"
 #include "regex_groups.hpp"
 #include "section_codec.hpp"
+#include "wide_plan.hpp"
 
 namespace bsh {
 
@@ -59,6 +60,11 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // matched bloom AND regex by ONE bsg_match_rows_regex call, and the rows it hands back by the host matcher with the same
     // DFAs (RE2 semantics on both sides); other regex queries keep the std::regex path below.  Off by default.
     bool device_regex = false;
+    // true (with device_match): query_many packs its queries into groups bounded by the condition table alone (64 distinct
+    // conditions, 16 regex conditions, the table bytes, co_active_bound) - not by 64 members - and decides each group by ONE
+    // bsg_match_rows_wide call, every set's query list read straight from the probe's survivors.  Off by default: routing is then
+    // exactly the batched calls'.
+    bool device_match_wide = false;
     // Tokenizer (engine.go:83, "for both indexing and verification"), restricted to the separator family
     // strings.FieldsFunc(lower ? strings.ToLower(v) : v, isSep) (text.hpp Tokenizer): indexRow, the host matcher and the
     // device calls (bsg_ingest_rows_tok / bsg_match_rows_tok) all use it.  Default: BasicWhitespaceLowerTokenizer.
@@ -848,6 +854,8 @@ private:
     // regex conditions, over the batched kernel's table bytes (by regex_groups.hpp's estimate) or would let one leaf lie under
     // more regex conditions than a lane holds (co_active_bound).  on_device[k] stays 0 (the caller decides query k by itself) for
     // a query beyond one of these limits alone or a group the library answers BSG_E_UNSUPPORTED for.
+    // Under DeviceMatchWide a group has no member limit (and the storing walker's larger table cap): one bsg_match_rows_wide call per
+    // group, each set's CSR query list read from set_wants; its result holds a bit row per (set, listed query) only.
     int32_t match_rows_device_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
                                    const std::vector<const std::string *> &scan, const std::vector<uint32_t> &set_first,
                                    const std::vector<const std::vector<uint8_t> *> &set_wants, std::vector<RowMatcher> &host_matchers,
@@ -859,6 +867,10 @@ private:
         for (const std::string *r : scan) { bytes.insert(bytes.end(), r->begin(), r->end()); row_off.push_back(bytes.size()); }
         const bsg_tokenizer tok = c_tokenizer();
         const size_t n_words = (scan.size() + 63) / 64, n_sets = set_wants.size();
+        // DeviceMatchWide: a group is bounded by its table, not by its members; the storing walker's LDS leaves the tables more room
+        const bool wide = cfg_.device_match_wide;
+        const size_t max_members = wide ? bsh_wide::kMaxQueries : 64;
+        const uint32_t table_cap = wide ? bsh_wide::kWideLdsCap : bsh_rxg::kManyLdsCap;
         std::map<std::string, std::pair<uint32_t, uint32_t>> dfa_size;      // pattern -> (states, classes); (0, 0): outside the subset
         auto rx_bytes = [&](const std::string &field, const std::string &pattern) -> uint32_t {
             auto it = dfa_size.find(pattern);
@@ -868,7 +880,7 @@ private:
                 const bool ok = bsh_rx::compile(pattern, d, err);
                 it = dfa_size.emplace(pattern, ok ? std::make_pair(d.n_states, d.n_classes) : std::make_pair(0u, 0u)).first;
             }
-            return bsh_rxg::rx_table_bytes(it->second.first, it->second.second, (uint32_t)field.size(), true);
+            return bsh_rxg::rx_table_bytes(it->second.first, it->second.second, (uint32_t)field.size(), !wide);   // the wide blob holds no user masks
         };
         size_t k = 0;
         while (k < exprs.size()) {
@@ -878,7 +890,7 @@ private:
             std::vector<std::string> fields, tokens;
             std::vector<size_t> members;
             uint32_t n_rx = 0, rx_table = 0;                                 // the group's regex conditions and their table bytes
-            for (; k < exprs.size() && members.size() < 64; ++k) {
+            for (; k < exprs.size() && members.size() < max_members; ++k) {
                 MatcherProgram mp(exprs[k]);
                 if (regexes[k]) {
                     if (!exprs[k]) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
@@ -897,7 +909,7 @@ private:
                 for (size_t c = 0; c < kinds.size(); ++c) if (kinds[c] == BSG_KIND_FIELD_REGEX) rx_fields.push_back(fields[c]);
                 for (const auto &kv : added) if (std::get<0>(kv.first) == BSG_KIND_FIELD_REGEX) rx_fields.push_back(std::get<1>(kv.first));
                 const bool fits = mp.kinds.size() <= 64 && index.size() + added.size() <= 64 && n_rx + fresh_rx <= bsh_rxg::kMaxRegexConds &&
-                                  bsh_rxg::align4(rx_table + fresh_bytes) <= bsh_rxg::kManyLdsCap &&
+                                  bsh_rxg::align4(rx_table + fresh_bytes) <= table_cap &&
                                   bsh_rxg::co_active_bound(rx_fields) <= bsh_rxg::kManySlots;
                 if (!fits) {
                     // alone beyond the call: the caller's (the host matcher; per query for a regex query).  Else it opens the next group
@@ -924,6 +936,44 @@ private:
             for (size_t c = 0; c < kinds.size(); ++c) {
                 cbytes.insert(cbytes.end(), fields[c].begin(), fields[c].end()); coff.push_back((uint32_t)cbytes.size());
                 cbytes.insert(cbytes.end(), tokens[c].begin(), tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
+            }
+            if (wide) {
+                // each set's list: the group's members that survived the probe on it, straight from set_wants
+                std::vector<uint32_t> sq_off{0}, sq;
+                for (size_t s = 0; s < n_sets; ++s) {
+                    for (size_t j = 0; j < members.size(); ++j)
+                        if ((*set_wants[s])[members[j]]) sq.push_back((uint32_t)j);
+                    sq_off.push_back((uint32_t)sq.size());
+                }
+                std::vector<uint64_t> pair_word_off(sq.size() + 1);
+                uint64_t total = 0;
+                if (bsg_match_wide_size(set_first.data(), sq_off.data(), (uint32_t)n_sets, (uint32_t)scan.size(), (uint32_t)members.size(),
+                                        pair_word_off.data(), &total))
+                    return fail(kErrGpu, bsg_last_error(ctx_));
+                std::vector<uint64_t> words(total + 1);
+                std::vector<uint32_t> fb(scan.size());
+                uint32_t n_fb = 0;
+                const int32_t rc = bsg_match_rows_wide(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
+                                                       (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(),
+                                                       sq_off.data(), sq.data(), (uint32_t)n_sets, &tok, words.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
+                if (rc == BSG_E_UNSUPPORTED) continue;
+                if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
+                for (size_t s = 0; s < n_sets; ++s)
+                    for (uint32_t p = sq_off[s]; p < sq_off[s + 1]; ++p) {
+                        std::vector<uint8_t> &h = hit[members[sq[p]]];
+                        const uint64_t *w = words.data() + pair_word_off[p];
+                        for (uint32_t i = set_first[s]; i < set_first[s + 1]; ++i) h[i] = (w[(i - set_first[s]) >> 6] >> ((i - set_first[s]) & 63)) & 1;
+                    }
+                for (size_t j = 0; j < members.size(); ++j) on_device[members[j]] = 1;
+                for (uint32_t i = 0; i < n_fb; ++i) {           // per query listed on the row's set
+                    const size_t s = (size_t)(std::upper_bound(set_first.begin() + 1, set_first.end(), fb[i]) - (set_first.begin() + 1));
+                    const std::string &row = *scan[fb[i]];
+                    for (uint32_t p = sq_off[s]; p < sq_off[s + 1]; ++p) {
+                        const size_t m = members[sq[p]];
+                        hit[m][fb[i]] = host_matchers[m].match(row) && (!host_regex[m] || host_regex[m]->match(row));
+                    }
+                }
+                continue;
             }
             std::vector<uint64_t> masks(n_sets, 0);
             for (size_t s = 0; s < n_sets; ++s)

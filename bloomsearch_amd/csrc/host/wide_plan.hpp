@@ -1,0 +1,160 @@
+// wide_plan.hpp — the arithmetic of bsg_match_rows_wide (match_api.inc), free of any device type: where a (set, query) pair's bit row
+// lies in the result (pair_words), which conditions a set's queries reference (query_cond_masks / set_cond_masks: the mask the
+// storing walker opens a regex condition's DFA by), where a call's rows are cut between devices (part_cuts: at set-relative multiples
+// of 64 rows, so no two devices write one word), a part's sets (part_sets) and the work items of k_eval_row_programs (eval_items: a
+// wave owns 64 consecutive rows of ONE set and a range of its pairs).  tests/wide_plan_check.cpp runs the same code on the CPU
+// (tests/test_match_wide_plan.py).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace bsh_wide {
+
+constexpr uint32_t kMaxQueries = 1u << 20;     // bloomgpu.h bsg_match_rows_wide: queries of one call
+constexpr uint32_t kMaxOps = 1u << 22;         // lowered ops of all programs together (16 MiB of device scratch)
+constexpr uint32_t kMaxPairs = 1u << 24;       // (set, query) pairs of one call
+constexpr uint32_t kMaxItems = 1u << 30;       // work items of one device's evaluation launch
+constexpr uint32_t kItemPairs = 64;            // pairs one wave evaluates over its 64 rows
+constexpr uint32_t kWideLdsCap = 46592;        // match.hip.h kRxWideLdsCap: regex table bytes of the storing walker
+
+inline uint32_t tiles_of(uint32_t n_rows) { return n_rows / 64u + (n_rows % 64u ? 1u : 0u); }
+
+enum class SizeStatus { Ok, Null, SetSpan, SetOrder, PairOrder };
+
+// Pair p of set s owns tiles_of(rows of s) consecutive words, pairs in order: pair_word_off [n_pairs + 1] (may be NULL) and the
+// total.  set_first_row == NULL && set_query_off == NULL && n_sets == 0: one implicit set of all rows with every query.
+inline SizeStatus pair_words(const uint32_t *set_first_row, const uint32_t *set_query_off, uint32_t n_sets, uint32_t n_rows, uint32_t n_queries,
+                             uint64_t *pair_word_off, uint64_t *total_words, uint32_t *bad_set = nullptr)
+{
+    uint64_t at = 0;
+    if (n_sets == 0) {
+        if (set_first_row || set_query_off) return SizeStatus::Null;
+        for (uint32_t q = 0; q < n_queries; ++q) {
+            if (pair_word_off) pair_word_off[q] = at;
+            at += tiles_of(n_rows);
+        }
+        if (pair_word_off) pair_word_off[n_queries] = at;
+        if (total_words) *total_words = at;
+        return SizeStatus::Ok;
+    }
+    if (!set_first_row || !set_query_off) return SizeStatus::Null;
+    if (set_first_row[0] != 0 || set_first_row[n_sets] != n_rows) return SizeStatus::SetSpan;
+    for (uint32_t s = 0; s < n_sets; ++s) {
+        if (bad_set) *bad_set = s;
+        if (set_first_row[s + 1] < set_first_row[s]) return SizeStatus::SetOrder;
+        if (set_query_off[s + 1] < set_query_off[s] || (s == 0 && set_query_off[0] != 0)) return SizeStatus::PairOrder;
+    }
+    for (uint32_t s = 0; s < n_sets; ++s) {
+        const uint32_t t = tiles_of(set_first_row[s + 1] - set_first_row[s]);
+        for (uint32_t p = set_query_off[s]; p < set_query_off[s + 1]; ++p) {
+            if (pair_word_off) pair_word_off[p] = at;
+            at += t;
+        }
+    }
+    if (pair_word_off) pair_word_off[set_query_off[n_sets]] = at;
+    if (total_words) *total_words = at;
+    return SizeStatus::Ok;
+}
+
+// bit c of masks[q]: program q references condition c (public postfix ops: opcode 0 = TERM, the low 28 bits its condition)
+inline std::vector<uint64_t> query_cond_masks(const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries, uint32_t n_conds)
+{
+    std::vector<uint64_t> masks(n_queries, 0);
+    for (uint32_t q = 0; q < n_queries; ++q)
+        for (uint32_t j = prog_off[q]; j < prog_off[q + 1]; ++j) {
+            const uint32_t arg = prog_ops[j] & 0x0FFFFFFFu;
+            if ((prog_ops[j] >> 28) == 0u && arg < n_conds && arg < 64u) masks[q] |= 1ull << arg;
+        }
+    return masks;
+}
+
+// per set: the OR of its listed queries' masks.  A set with pairs and mask 0 (only constant programs) is still walked: what says
+// "not walked" is an empty list, not an empty mask.
+inline std::vector<uint64_t> set_cond_masks(const std::vector<uint64_t> &query_masks, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                            uint32_t n_sets)
+{
+    std::vector<uint64_t> masks(n_sets, 0);
+    for (uint32_t s = 0; s < n_sets; ++s)
+        for (uint32_t p = set_query_off[s]; p < set_query_off[s + 1]; ++p) masks[s] |= query_masks[set_queries[p]];
+    return masks;
+}
+
+// Cut points of a call's rows for `want` devices of about equal bytes: each cut lies at a set-relative multiple of 64 rows (a
+// whole number of the set's 64-row tiles before it), so every (pair, tile) word is written by one device.  [0, ..., n_rows].
+inline std::vector<uint32_t> part_cuts(const uint64_t *row_off, uint32_t n_rows, const uint32_t *set_first_row, uint32_t n_sets, uint32_t want)
+{
+    std::vector<uint32_t> cuts{0};
+    const uint64_t n_bytes = row_off[n_rows] - row_off[0];
+    for (uint32_t i = 1; i < want; ++i) {
+        const uint64_t target = row_off[0] + n_bytes * i / want;
+        uint32_t r = (uint32_t)(std::lower_bound(row_off, row_off + n_rows, target) - row_off);
+        if (r >= n_rows) continue;
+        // the set r lies in: the last one that begins at or before it
+        const uint32_t s = (uint32_t)(std::upper_bound(set_first_row, set_first_row + n_sets + 1, r) - set_first_row) - 1u;
+        r = set_first_row[s] + (r - set_first_row[s]) / 64u * 64u;
+        if (r > cuts.back() && r < n_rows) cuts.push_back(r);
+    }
+    cuts.push_back(n_rows);
+    return cuts;
+}
+
+// What rows [r0, r1) of a call hold of its sets: per local set the rows (counted from r0), its pairs (indices into the call's
+// set_queries) and the set's tile its first row begins (r0 is a set-relative multiple of 64).
+struct PartSets {
+    uint32_t s0 = 0;                       // the call's set of local set 0
+    std::vector<uint32_t> first_row;       // [n + 1], counted from r0
+    std::vector<uint32_t> pair_off;        // [n + 1] into the call's set_queries
+    std::vector<uint32_t> tile0;           // [n]: local tile 0 is this tile of the call's set
+    uint32_t n() const { return (uint32_t)tile0.size(); }
+};
+
+inline PartSets part_sets(const uint32_t *set_first_row, const uint32_t *set_query_off, uint32_t n_sets, uint32_t r0, uint32_t r1)
+{
+    PartSets ps;
+    const uint32_t *sf = set_first_row;
+    ps.s0 = (uint32_t)(std::upper_bound(sf + 1, sf + n_sets + 1, r0) - (sf + 1));            // the first set that ends behind r0
+    const uint32_t s1 = (uint32_t)(std::lower_bound(sf, sf + n_sets, r1) - sf);              // the first set that begins at or behind r1
+    for (uint32_t s = ps.s0; s < s1; ++s) {
+        const uint32_t lo = std::max(sf[s], r0);
+        ps.first_row.push_back(lo - r0);
+        ps.pair_off.push_back(set_query_off[s]);
+        ps.tile0.push_back((lo - sf[s]) / 64u);
+    }
+    ps.first_row.push_back(r1 - r0);
+    ps.pair_off.push_back(set_query_off[s1]);
+    return ps;
+}
+
+// One wave of k_eval_row_programs: rows [row0, row0 + n_rows) of the part (n_rows <= 64, one tile of one set), pairs [pair0, pair1)
+// of the part's pair list, and where pair0's word goes in the part's result; the next pair's word lies `stride` words on (the
+// part's tiles of the set).
+struct EvalItem {
+    uint64_t out0;
+    uint32_t row0, n_rows, pair0, pair1, stride, pad;
+};
+static_assert(sizeof(EvalItem) == 32, "k_eval_row_programs reads an item as four u64");
+
+// The part's result: local pair lp of local set ls owns tiles_of(local rows) words, pairs in order (for a part that holds its sets
+// whole, the call's layout from its first pair on).  pair_off_local counts from the part's first pair.  false: over kMaxItems.
+inline bool eval_items(const PartSets &ps, std::vector<EvalItem> &items, uint64_t &part_words)
+{
+    items.clear();
+    uint64_t at = 0;
+    for (uint32_t ls = 0; ls < ps.n(); ++ls) {
+        const uint32_t rows = ps.first_row[ls + 1] - ps.first_row[ls], tiles = tiles_of(rows);
+        const uint32_t p0 = ps.pair_off[ls] - ps.pair_off[0], p1 = ps.pair_off[ls + 1] - ps.pair_off[0];
+        if (p0 == p1 || tiles == 0) continue;
+        if ((uint64_t)tiles * ((p1 - p0 + kItemPairs - 1) / kItemPairs) + items.size() > kMaxItems) return false;
+        for (uint32_t pa = p0; pa < p1; pa += kItemPairs)
+            for (uint32_t t = 0; t < tiles; ++t)
+                items.push_back(EvalItem{at + (uint64_t)(pa - p0) * tiles + t, ps.first_row[ls] + t * 64u, std::min(64u, rows - t * 64u), pa,
+                                         std::min(p1, pa + kItemPairs), tiles, 0u});
+        at += (uint64_t)tiles * (p1 - p0);
+    }
+    part_words = at;
+    return true;
+}
+
+}  // namespace bsh_wide

@@ -35,6 +35,17 @@
 // the queries whose program references the condition.  A leaf opens a condition's DFA only on a row whose set mask selects one
 // of those queries, so a lane's kRxManyActive slots hold what the row's own queries need, and a row is handed back for too many
 // regex conditions on one leaf only when the queries live on its set put them there.
+//
+// Any number of queries (bsg_match_rows_wide): the work is split as the probe side splits it.  k_match_rows_store / _tok / _regex /
+// _regex_tok = the same body with WIDE = true: the walk collects `sat` over the table's <= 64 distinct conditions and STORES it per row
+// with a state byte (not walked / decided / fallback) instead of evaluating anything; it holds no program in LDS (conditions 5 632 +
+// lanes 29 696 = 35 328 bytes, three workgroups per CU; with regex tables of at most kRxWideLdsCap = 46 592 bytes 80 KiB, two).  Rows come
+// in sets with a CSR list of the queries evaluated on each: a set with an empty list is never walked, and a leaf opens a regex
+// condition's DFA only when the set's condition mask (the OR of the conditions its queries' programs reference) selects it.
+// k_eval_row_programs then evaluates the programs over the stored words: a wave owns 64 consecutive rows of ONE set (tiles are
+// set-relative) and a range of the set's pairs, loads each lane's sat and state once, reads a pair's query and program on the scalar
+// path (constant address space: uniform addresses) and writes __ballot(decided && verdict) as the pair's word of the tile.  No LDS,
+// no limit on the number of queries.
 #pragma once
 #include <type_traits>
 #include "ingest.hip.h"
@@ -102,6 +113,36 @@ struct RxArgs {
     const uint32_t *blob;       // the table blob as words
     uint32_t n_words, n_rx;
 };
+// ---- any number of queries: the walk stores, k_eval_row_programs evaluates (bsg_match_rows_wide) ----
+constexpr uint32_t kMatchWideLdsBytes = kMatchMaxConds * kMatchCondWords * 8 + kIngestThreads * kLaneLds;   // no programs in LDS
+static_assert(3u * kMatchWideLdsBytes <= 160u * 1024u, "k_match_rows_store keeps three workgroups per CU");
+constexpr uint32_t kRxWideLdsCap = 80u * 1024u - kMatchWideLdsBytes;   // regex table bytes of the storing walker (no user masks in its blob)
+static_assert(kRxWideLdsCap == 46592u && kRxWideLdsCap <= 0x10000u && 2u * (kMatchWideLdsBytes + kRxWideLdsCap) <= 160u * 1024u,
+              "k_match_rows_store_regex keeps two workgroups per CU, and the blob's 16-bit offsets reach all of it");
+constexpr uint8_t kRowNotWalked = 0, kRowDecided = 1, kRowFallback = 2;
+struct MatchWideArgs {
+    const uint32_t *set_first_row;   // [n_sets + 1], in the rows MatchArgs::row_base counts; n_sets >= 1 (the host makes the implicit set)
+    const uint64_t *set_cond_mask;   // [n_sets]: bit c = a program of a query listed on the set references condition c
+    const uint32_t *set_pair_off;    // [n_sets + 1]: the set's pairs; an empty range = the set's rows are not walked
+    uint64_t *sat;                   // [n_rows] of the launch: the row's satisfaction flags
+    uint8_t *state;                  // [n_rows] of the launch: kRowNotWalked / kRowDecided / kRowFallback
+    uint32_t n_sets;
+};
+// one wave of k_eval_row_programs (host/wide_plan.hpp RowEvalItem, read as four u64 on the scalar path)
+struct RowEvalItem {
+    uint64_t out0;
+    uint32_t row0, n_rows, pair0, pair1, stride, pad;
+};
+struct RowEvalArgs {
+    const RowEvalItem *items;
+    const uint32_t *pairs;           // the part's pairs: the query of each
+    const uint32_t *prog_off;        // [n_queries + 1] into prog
+    const uint32_t *prog;            // the lowered programs
+    const uint64_t *sat;
+    const uint8_t *state;
+    uint64_t *out;                   // the part's result words
+    uint32_t n_items;
+};
 typedef __attribute__((address_space(3))) uint16_t lds_u16;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 
@@ -147,11 +188,13 @@ struct RxLaneT {
 
 typedef RxLaneT<kRxActive> RxLane;
 
-template <bool REGEX, class TOK, bool MANY = false, uint32_t SLOTS = kRxActive>
-__device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs &x, const TOK &tk, const MatchManyArgs &m = MatchManyArgs{})
+template <bool REGEX, class TOK, bool MANY = false, uint32_t SLOTS = kRxActive, bool WIDE = false>
+__device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs &x, const TOK &tk, const MatchManyArgs &m = MatchManyArgs{},
+                                                const MatchWideArgs &wd = MatchWideArgs{})
 {
-    constexpr uint32_t kProgBytes = MANY ? kMatchManyProgBytes : kMatchMaxOps * 4;
-    constexpr uint32_t kRxBase = MANY ? kMatchManyLdsBytes : kMatchLdsBytes;   // the regex blob sits behind the instance's own LDS
+    static_assert(!(MANY && WIDE), "the storing walker evaluates no program");
+    constexpr uint32_t kProgBytes = WIDE ? 0u : MANY ? kMatchManyProgBytes : kMatchMaxOps * 4;
+    constexpr uint32_t kRxBase = WIDE ? kMatchWideLdsBytes : MANY ? kMatchManyLdsBytes : kMatchLdsBytes;   // the regex blob sits behind the instance's own LDS
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     lds_u64i *conds = (lds_u64i *)lds_raw;
     typedef __attribute__((address_space(3))) uint32_t lds_u32i;
@@ -162,7 +205,8 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
         e[8] = a.cond_fp[2 * c]; e[9] = a.cond_fp[2 * c + 1];
         e[10] = a.cond_kind[c];
     }
-    for (uint32_t i = threadIdx.x; i < a.n_ops; i += kIngestThreads) prog[i] = a.prog[i];
+    if constexpr (!WIDE)
+        for (uint32_t i = threadIdx.x; i < a.n_ops; i += kIngestThreads) prog[i] = a.prog[i];
     if constexpr (MANY)
         for (uint32_t i = threadIdx.x; i <= m.n_queries; i += kIngestThreads) prog[kMatchManyMaxOps + i] = m.prog_off[i];
     if constexpr (REGEX)
@@ -191,7 +235,21 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
             qmask = m.set_mask[lo];
         }
     }
-    const bool walk = MANY ? (live && qmask != 0ull) : live;
+    uint64_t cmask = 0;          // WIDE: the conditions the row's set evaluates; listed: the set has a pair at all
+    bool listed = false;
+    if constexpr (WIDE) {
+        if (live) {
+            const uint32_t g = a.row_base + r;
+            uint32_t lo = 0, hi = wd.n_sets - 1u;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (wd.set_first_row[mid + 1] <= g) lo = mid + 1u; else hi = mid;
+            }
+            cmask = wd.set_cond_mask[lo];
+            listed = wd.set_pair_off[lo + 1] != wd.set_pair_off[lo];
+        }
+    }
+    const bool walk = WIDE ? listed : MANY ? (live && qmask != 0ull) : live;
     walker_reset(w, cc, walk ? a.row_off[r] : 0, walk ? a.row_off[r + 1] : 0, walk);
     uint32_t res = walk ? R_CONTINUE : R_DONE;
     uint64_t sat = 0, leaf_mask = 0;
@@ -232,6 +290,7 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
                     const uint64_t users = (uint64_t)hdr[4 * x.n_rx + 2 * j] | ((uint64_t)hdr[4 * x.n_rx + 2 * j + 1] << 32);
                     under = under && (qmask & users) != 0ull;
                 }
+                if constexpr (WIDE) under = under && ((cmask >> (h1 >> 16)) & 1ull) != 0ull;   // ... whose set lists a query that uses it
                 for (uint32_t i = 0; i < flen && __ballot(under) != 0ull; ++i)   // ends once no lane's path can still match
                     if (under) under = w.path[i] == fld[i];
                 if (under) {
@@ -274,6 +333,19 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
         for (uint32_t j = 0; j < x.n_rx; ++j)
             if ((rx.sat >> j) & 1u) sat |= 1ULL << (hdr[4 * j + 1] >> 16);
         if (rx_over && res == R_DONE) res = R_FAIL;
+    }
+    if constexpr (WIDE) {
+        // nothing is evaluated here: the flags and what became of the row go to device memory for k_eval_row_programs
+        if (collided && res == R_DONE) res = R_FAIL;
+        if (live) {
+            wd.sat[r] = sat;
+            wd.state[r] = !walk ? kRowNotWalked : res == R_DONE ? kRowDecided : kRowFallback;
+        }
+        if (res == R_FAIL) {
+            const uint32_t slot = __hip_atomic_fetch_add(a.n_fallback, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            a.fallback_rows[slot] = a.row_base + r;
+        }
+        return;
     }
     if constexpr (MANY) {
         // one program per query over the same flags: the loop and the program words (LDS broadcasts) are wave-uniform, each
@@ -353,6 +425,63 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex(const 
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_tok(const MatchArgs a, const RxArgs x, const MatchManyArgs m, const TokSpec t)
 {
     match_rows_body<true, TokSpecP, true, kRxManyActive>(a, x, TokSpecP{t}, m);
+}
+
+// the storing walker (bsg_match_rows_wide): plain / regex x default / spec tokenizer; dynamic LDS kMatchWideLdsBytes (+ the table
+// blob, <= kRxWideLdsCap)
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store(const MatchArgs a, const MatchWideArgs wd)
+{
+    match_rows_body<false, TokDefault, false, kRxActive, true>(a, RxArgs{}, TokDefault{}, MatchManyArgs{}, wd);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_tok(const MatchArgs a, const MatchWideArgs wd, const TokSpec t)
+{
+    match_rows_body<false, TokSpecP, false, kRxActive, true>(a, RxArgs{}, TokSpecP{t}, MatchManyArgs{}, wd);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex(const MatchArgs a, const RxArgs x, const MatchWideArgs wd)
+{
+    match_rows_body<true, TokDefault, false, kRxActive, true>(a, x, TokDefault{}, MatchManyArgs{}, wd);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_tok(const MatchArgs a, const RxArgs x, const MatchWideArgs wd, const TokSpec t)
+{
+    match_rows_body<true, TokSpecP, false, kRxActive, true>(a, x, TokSpecP{t}, MatchManyArgs{}, wd);
+}
+
+// The programs of the listed (set, query) pairs over the stored flags.  Wave w of the grid owns item w: one 64-row tile of one set
+// and up to kItemPairs of the set's pairs.  Everything but sat / state / the ballot is wave-uniform and read through the constant
+// address space (items, pairs, prog_off and prog are written by the host before the launch, never by a kernel): scalar loads, the
+// loop bounds in SGPRs, no LDS.  Lane 0 stores the pair's word of the tile with a vector store.
+constexpr uint32_t kRowEvalThreads = 256;
+__global__ __launch_bounds__(kRowEvalThreads) void k_eval_row_programs(const RowEvalArgs e)
+{
+    typedef const __attribute__((address_space(4))) uint64_t c64;
+    typedef const __attribute__((address_space(4))) uint32_t c32;
+    const uint32_t it = blockIdx.x * (kRowEvalThreads / 64u) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (it >= e.n_items) return;
+    c64 *iw = (c64 *)(uintptr_t)(e.items + it);
+    const uint64_t out0 = iw[0], w1 = iw[1], w2 = iw[2], w3 = iw[3];
+    const uint32_t row0 = (uint32_t)w1, n_rows = (uint32_t)(w1 >> 32), pair0 = (uint32_t)w2, pair1 = (uint32_t)(w2 >> 32), stride = (uint32_t)w3;
+    c32 *pairs = (c32 *)(uintptr_t)e.pairs, *poff = (c32 *)(uintptr_t)e.prog_off, *prog = (c32 *)(uintptr_t)e.prog;
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool live = lane < n_rows;
+    const uint64_t sat = live ? e.sat[row0 + lane] : 0ull;
+    const bool decided = live && e.state[row0 + lane] == kRowDecided;
+    for (uint32_t p = pair0; p < pair1; ++p) {
+        const uint32_t q = pairs[p], j0 = poff[q], j1 = poff[q + 1];
+        uint64_t stk = 0;
+        for (uint32_t j = j0; j < j1; ++j) {
+            const uint32_t op = prog[j], opc = op >> 28;
+            if (opc == 0u) stk = (stk << 1) | ((sat >> (op & 63u)) & 1ULL);
+            else if (opc == 3u) stk = (stk << 1) | 1ULL;
+            else if (opc == 4u) stk = stk << 1;
+            else {
+                const uint64_t x = stk & 1ULL, y = (stk >> 1) & 1ULL;
+                stk = ((stk >> 2) << 1) | (opc == 1u ? (x & y) : (x | y));
+            }
+        }
+        const bool verdict = j0 == j1 ? true : (stk & 1ULL) != 0;        // nil expression matches every row
+        const uint64_t word = __ballot(decided && verdict);
+        if (lane == 0u) e.out[out0 + (uint64_t)(p - pair0) * stride] = word;
+    }
 }
 
 }  // namespace bsg

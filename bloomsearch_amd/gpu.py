@@ -97,6 +97,12 @@ def estimate_parameters(n: int, p: float):
     return int(m.value), int(k.value)
 
 
+def wide_pair_bits(words, pair_word_off, pair: int, n_set_rows: int) -> np.ndarray:
+    """The bool row of pair `pair` of a Context.match_rows_wide result, over the n_set_rows rows of its set."""
+    w = np.ascontiguousarray(words[int(pair_word_off[pair]): int(pair_word_off[pair + 1])])
+    return np.unpackbits(w.view(np.uint8), bitorder="little")[:n_set_rows].astype(bool)
+
+
 class Context:
     """bsg_ctx: one or more gfx950 devices, per-device streams."""
 
@@ -654,6 +660,61 @@ class Context:
                        _lib._ptr(bits), _lib._ptr(fb), len(fb), C.byref(nfb)))
         planes = np.unpackbits(bits.view(np.uint8).reshape(nq, n_words * 8), axis=1, bitorder="little")[:, :n].astype(bool)
         return planes, fb[: nfb.value].copy()
+
+    def match_rows_wide(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None):
+        """bsg_match_rows_wide: rows as match_rows; batch: query.CompiledWideBatch (or anything with kinds / fields / tokens / prog_ops /
+        prog_off), any number of queries.  set_first_row [n_sets + 1], set_query_off [n_sets + 1] and set_queries (CSR: the queries
+        evaluated on each set, strictly ascending): all None = one implicit set of all rows with every query.
+        -> (u64 words, u64 pair_word_off [n_pairs + 1], sorted u32 array of rows the host matcher must decide): pair p's bit row is
+        words[pair_word_off[p]: pair_word_off[p + 1]] (wide_pair_bits unpacks it)."""
+        if isinstance(rows, tuple):
+            blob = np.ascontiguousarray(rows[0], dtype=np.uint8)
+            off = np.ascontiguousarray(rows[1], dtype=np.uint64)
+        else:
+            off = np.zeros(len(rows) + 1, dtype=np.uint64)
+            if rows:
+                off[1:] = np.cumsum([len(r) for r in rows], dtype=np.uint64)
+            blob = np.frombuffer(b"".join(rows), dtype=np.uint8)
+        n = len(off) - 1
+        cblob, coff = pack_entries([s for pair in zip(batch.fields, batch.tokens) for s in pair])
+        kinds = np.asarray(batch.kinds, dtype=np.uint32)
+        ops = np.asarray(batch.prog_ops, dtype=np.uint32)
+        poff = np.asarray(batch.prog_off, dtype=np.uint32)
+        nq = len(poff) - 1
+        given = [a is not None for a in (set_first_row, set_query_off, set_queries)]
+        if any(given) and not all(given):
+            raise ValueError("set_first_row, set_query_off and set_queries go together")
+        sfr = sqo = sq = None
+        if all(given):
+            sfr = np.ascontiguousarray(set_first_row, dtype=np.uint32)
+            sqo = np.ascontiguousarray(set_query_off, dtype=np.uint32)
+            sq = np.ascontiguousarray(set_queries, dtype=np.uint32)
+            if len(sfr) != len(sqo) or len(sfr) < 2:
+                raise ValueError("set_first_row and set_query_off hold one entry per set and one more")
+        n_sets = 0 if sfr is None else len(sfr) - 1
+        pair_word_off, total = self.match_wide_size(sfr, sqo, n, nq)
+        if sq is not None and len(sq) != len(pair_word_off) - 1:
+            raise ValueError("set_queries holds set_query_off[n_sets] entries")
+        words = np.zeros(total, dtype=np.uint64)
+        fb = np.zeros(max(n, 1), dtype=np.uint32)
+        nfb = C.c_uint32()
+        self._check(self.L.bsg_match_rows_wide(self.h, _lib._ptr(blob), _lib._ptr(off), n, _lib._ptr(cblob), _lib._ptr(coff), _lib._ptr(kinds),
+                                               len(kinds), _lib._ptr(ops), poff.ctypes.data, nq, _lib._ptr(sfr), _lib._ptr(sqo),
+                                               None if sq is None else sq.ctypes.data, n_sets,
+                                               None if tokenizer is None else c_spec(tokenizer), words.ctypes.data, _lib._ptr(fb), len(fb),
+                                               C.byref(nfb)))
+        return words, pair_word_off, fb[: nfb.value].copy()
+
+    def match_wide_size(self, set_first_row, set_query_off, n_rows: int, n_queries: int):
+        """bsg_match_wide_size (host arithmetic) -> (u64 pair_word_off [n_pairs + 1], total words); None, None = the implicit set."""
+        sfr = None if set_first_row is None else np.ascontiguousarray(set_first_row, dtype=np.uint32)
+        sqo = None if set_query_off is None else np.ascontiguousarray(set_query_off, dtype=np.uint32)
+        n_sets = 0 if sfr is None else len(sfr) - 1
+        n_pairs = n_queries if sqo is None or len(sqo) == 0 else int(sqo[-1])
+        pwo = np.zeros(n_pairs + 1, dtype=np.uint64)
+        total = C.c_uint64()
+        self._check(self.L.bsg_match_wide_size(_lib._ptr(sfr), _lib._ptr(sqo), n_sets, n_rows, n_queries, pwo.ctypes.data, C.byref(total)))
+        return pwo, int(total.value)
 
     def last_match_ms(self) -> float:
         v = C.c_float()

@@ -246,10 +246,12 @@ class CompiledMatcherBatch:
     queries by (kind, field, token) — and one postfix program per query over the table's indices (query q's is
     CompiledMatcher(expr_q)'s with its condition indices remapped).  Raises ValueError beyond the call's limits."""
 
+    MAX_QUERIES, MAX_OPS = MATCH_MANY_MAX_QUERIES, MATCH_MANY_MAX_OPS
+
     def __init__(self, expressions):
         expressions = list(expressions)
-        if len(expressions) > MATCH_MANY_MAX_QUERIES:
-            raise ValueError(f"{len(expressions)} queries: one batched match call holds {MATCH_MANY_MAX_QUERIES}")
+        if len(expressions) > self.MAX_QUERIES:
+            raise ValueError(f"{len(expressions)} queries: one batched match call holds {self.MAX_QUERIES}")
         self.kinds: list[int] = []
         self.fields: list[bytes] = []
         self.tokens: list[bytes] = []
@@ -277,8 +279,8 @@ class CompiledMatcherBatch:
             self.prog_ops.extend(op(OP_TERM, remap[o & 0x0FFFFFFF]) if (o >> 28) == OP_TERM else o for o in m.prog_ops)
             self.prog_off.append(len(self.prog_ops))
             lowered += lowered_ops(m.prog_ops)
-            if lowered > MATCH_MANY_MAX_OPS:
-                raise ValueError(f"the batch's programs lower to more than {MATCH_MANY_MAX_OPS} ops")
+            if lowered > self.MAX_OPS:
+                raise ValueError(f"the batch's programs lower to more than {self.MAX_OPS} ops")
 
     @staticmethod
     def _compile(expression):
@@ -341,3 +343,19 @@ class CompiledRowQueryBatch(CompiledMatcherBatch):
     @staticmethod
     def _compile(pair):
         return CompiledRowQuery(*pair)
+
+
+MATCH_WIDE_MAX_QUERIES, MATCH_WIDE_MAX_OPS, MATCH_WIDE_MAX_PAIRS = 1 << 20, 1 << 22, 1 << 24      # bloomgpu.h bsg_match_rows_wide
+
+
+class CompiledWideBatch(CompiledRowQueryBatch):
+    """Any number of queries for one bsg_match_rows_wide call: the table and the programs exactly as CompiledRowQueryBatch builds
+    them — ONE table of at most 64 distinct conditions (16 of them regex), query q's program CompiledRowQuery's (for a
+    (bloom, regex) pair) or CompiledMatcher's (for a plain expression, or None) with its indices remapped — without the 64-query and
+    2 048-op limits of the batched calls.  Raises ValueError beyond 2^20 queries, 2^22 lowered ops, 64 conditions, 16 regex conditions."""
+
+    MAX_QUERIES, MAX_OPS = MATCH_WIDE_MAX_QUERIES, MATCH_WIDE_MAX_OPS
+
+    @staticmethod
+    def _compile(item):
+        return CompiledRowQuery(*item) if isinstance(item, tuple) else CompiledMatcher(item)

@@ -1032,6 +1032,71 @@ func (g *Context) MatchRowsManyRegex(rows []byte, rowOff []uint64, conds []Match
 	return g.matchRowsMany(true, rows, rowOff, conds, progOps, progOff, setFirstRow, masks, tok)
 }
 
+// MatchRowsWide matches ANY number of queries over one table of at most 64 distinct conditions (up to 16 of them KindFieldRegex) in
+// one upload and one walk of the rows (bsg_match_rows_wide): the walk stores every row's condition word on the device and a second
+// kernel evaluates the programs over them.  The masks of MatchRowsMany become a CSR list: setQueries[setQueryOff[s]:setQueryOff[s+1]]
+// are the queries evaluated on set s, strictly ascending; a pair p is an index into setQueries.  All three nil = one set of all rows
+// with every query (the plane layout of MatchRowsMany).  words[pairWordOff[p]:pairWordOff[p+1]] is pair p's bit row over the rows of
+// its set (bit i&63 of word i>>6 = row setFirstRow[s]+i); rows in hostRows (all their pair bits 0) must be decided by matchRowBytes
+// for every query listed on their set.  In matchBlock this is the call for a batch of more than 64 queries: one call per group of
+// <= 64 distinct conditions instead of one MatchRowsMany per 64 queries.  Limits: 64 conditions, 16 regex conditions, tables over
+// 46592 bytes of LDS, 1<<20 queries, 1<<22 lowered ops, 1<<24 pairs: IsUnsupported(err).
+func (g *Context) MatchRowsWide(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
+	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (words []uint64, pairWordOff []uint64, hostRows []uint32, err error) {
+	n, nq := len(rowOff)-1, len(progOff)-1
+	if n <= 0 || nq <= 0 {
+		return nil, nil, nil, nil
+	}
+	if (setFirstRow == nil) != (setQueryOff == nil) || (setFirstRow == nil && setQueries != nil) || len(setFirstRow) != len(setQueryOff) {
+		return nil, nil, nil, fmt.Errorf("bloomgpu: setFirstRow and setQueryOff hold one entry per set and one more, or all three tables are nil")
+	}
+	nSets, nPairs := 0, nq
+	if setFirstRow != nil {
+		nSets = len(setFirstRow) - 1
+		nPairs = int(setQueryOff[nSets])
+		if nSets < 1 || len(setQueries) != nPairs {
+			return nil, nil, nil, fmt.Errorf("bloomgpu: setQueries holds setQueryOff[nSets] entries")
+		}
+	}
+	var ct *C.bsg_tokenizer
+	if tok != nil {
+		if err := tok.Validate(); err != nil {
+			return nil, nil, nil, err
+		}
+		c := tok.c()
+		ct = &c
+	}
+	pairWordOff = make([]uint64, nPairs+1)
+	var total C.uint64_t
+	if err := g.err(C.bsg_match_wide_size(u32p(setFirstRow), u32p(setQueryOff), C.uint32_t(nSets), C.uint32_t(n), C.uint32_t(nq),
+		u64p(pairWordOff), &total)); err != nil {
+		return nil, nil, nil, err
+	}
+	if nPairs == 0 {
+		return nil, pairWordOff, nil, nil
+	}
+	words = make([]uint64, int(total)+1)
+	hostRows = make([]uint32, n)
+	var cbytes []byte
+	coff := make([]uint32, 1, 2*len(conds)+1)
+	kinds := make([]uint32, len(conds))
+	for i, c := range conds {
+		cbytes = append(cbytes, c.Field...)
+		coff = append(coff, uint32(len(cbytes)))
+		cbytes = append(cbytes, c.Token...)
+		coff = append(coff, uint32(len(cbytes)))
+		kinds[i] = c.Kind
+	}
+	var nfb C.uint32_t
+	rc := C.bsg_match_rows_wide(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+		u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u32p(setQueryOff), u32p(setQueries), C.uint32_t(nSets), ct,
+		u64p(words), u32p(hostRows), C.uint32_t(n), &nfb)
+	if err := g.err(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	return words[:total], pairWordOff, hostRows[:nfb], nil
+}
+
 func (g *Context) matchRowsMany(regex bool, rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
 	setFirstRow []uint32, masks []uint64, tok *Tokenizer) (planes [][]uint64, hostRows []uint32, err error) {
 	n, nq := len(rowOff)-1, len(progOff)-1

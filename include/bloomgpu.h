@@ -640,8 +640,45 @@ BSG_API int32_t bsg_match_rows_many_regex(bsg_ctx *ctx, const uint8_t *rows, con
                                           const bsg_tokenizer *tok,
                                           uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                           uint32_t *out_n_fallback);
+/* ANY number of queries over one condition table in ONE upload and ONE walk of the rows.  The work is split as the probe side
+ * splits it: the walk (k_match_rows_store*) writes every row's 64-bit condition word to device memory, k_eval_row_programs
+ * evaluates the programs over those words.  The condition table (FieldRegex conditions allowed), prog_ops / prog_off[n_queries + 1]
+ * and tok are exactly bsg_match_rows_many_regex's; an empty program is the nil expression: every row matches.
+ * Sets: set s = rows [set_first_row[s], set_first_row[s + 1]), set_first_row[0] == 0, set_first_row[n_sets] == n_rows.  The u64 mask
+ * of the batched call becomes a CSR list: set_queries[set_query_off[s] .. set_query_off[s + 1]) are the queries evaluated on set s,
+ * strictly ascending, each < n_queries; set_query_off[0] == 0.  A PAIR p is an index into set_queries.  NULL, NULL, NULL, 0 = one
+ * implicit set of all rows with every query: the result then has the plane layout of bsg_match_rows_many.
+ * out_bits (bsg_match_wide_size says how many words): pair p of set s owns ceil(rows of s / 64) consecutive words from
+ * pair_word_off[p] on, pairs in order; bit i & 63 of word i >> 6 is set <=> row set_first_row[s] + i matches the program of
+ * set_queries[p] (= what bsg_match_rows_tok returns for that program alone over the same table); bits past the set's last row are
+ * 0.  The result is sparse: nothing is stored for a (set, query) the caller did not list.
+ * Fallback rows (listed once, ascending, all their pair bits 0), only among rows of a set with at least one pair: a row that leaves
+ * the device walker's envelope; a row in which an emission has the base hashes of ANY table condition but not its fingerprint; a
+ * row in which one leaf would feed more than 4 regex conditions at once, counting only conditions referenced by the program of a
+ * query in the set's list.  Rows of a set with no pair are never walked and never fallback rows.
+ * Limits (BSG_E_UNSUPPORTED before anything is launched): 64 distinct conditions; 16 regex conditions; the regex subset and 1 024
+ * states of bsg_match_rows_regex; program depth 64; DFA tables over 46 592 bytes of LDS (80 KiB minus the storing walker's 35 328:
+ * it keeps no program in LDS; per regex condition 16 header bytes, its class map and transitions (256 + 2 * states * classes,
+ * padded to 4) and its field string); 1 048 576 (2^20) queries; 4 194 304 (2^22) lowered ops over all programs (an n-ary AND / OR
+ * lowers to n - 1 binary ops); 16 777 216 (2^24) pairs; 2^30 (64-row tile, 64-pair range) items on one device.  Beyond that only
+ * device memory bounds a call (BSG_E_NOMEM): 9 bytes per row, 4 per lowered op, query and pair, 8 per result word.
+ * BSG_E_INVALID: null arguments, offsets that are not monotone, a set table that does not span [0, n_rows), a query list that is not
+ * strictly ascending or names a query >= n_queries.  n_rows == 0 or zero pairs: BSG_OK, nothing written.
+ * Sharding over the context's devices (parts are cut at set-relative multiples of 64 rows: no two devices write one word), chunked
+ * upload and bsg_last_match_ms (the walk plus the evaluation of the slowest device) as bsg_match_rows_many. */
+BSG_API int32_t bsg_match_rows_wide(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                    const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                    const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                    const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                    uint32_t n_sets, const bsg_tokenizer *tok,
+                                    uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                    uint32_t *out_n_fallback);
+/* The layout of bsg_match_rows_wide's result, host arithmetic without a context: out_pair_word_off[n_pairs + 1] (may be NULL) and
+ * the total number of words.  NULL, NULL, 0 = the implicit set (n_pairs = n_queries).  BSG_E_INVALID as the call itself. */
+BSG_API int32_t bsg_match_wide_size(const uint32_t *set_first_row, const uint32_t *set_query_off, uint32_t n_sets, uint32_t n_rows,
+                                    uint32_t n_queries, uint64_t *out_pair_word_off, uint64_t *out_total_words);
 /* Device time of the most recent k_match_rows / k_match_rows_regex / k_match_rows_many / k_match_rows_many_regex dispatch (the
- * slowest device's). */
+ * slowest device's); after bsg_match_rows_wide, its walk plus its evaluation. */
 BSG_API int32_t bsg_last_match_ms(bsg_ctx *ctx, float *match_ms);
 
 #ifdef __cplusplus

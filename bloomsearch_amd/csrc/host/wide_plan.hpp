@@ -1,9 +1,10 @@
-// wide_plan.hpp — the arithmetic of bsg_match_rows_wide (match_api.inc), free of any device type: where a (set, query) pair's bit row
-// lies in the result (pair_words), which conditions a set's queries reference (query_cond_masks / set_cond_masks: the mask the
-// storing walker opens a regex condition's DFA by), where a call's rows are cut between devices (part_cuts: at set-relative multiples
-// of 64 rows, so no two devices write one word), a part's sets (part_sets) and the work items of k_eval_row_programs (eval_items: a
-// wave owns 64 consecutive rows of ONE set and a range of its pairs).  tests/wide_plan_check.cpp runs the same code on the CPU
-// (tests/test_match_wide_plan.py).
+// wide_plan.hpp — the arithmetic of the row-matcher calls (match_api.inc), free of any device type.  For every call: where its rows are
+// cut between devices (part_cuts: at set-relative multiples of 64 rows, so no two devices write one word; the single and batched calls
+// pass one implicit set {0, n_rows} and get multiples of 64 rows) and the sets a part's rows lie in (part_set_range).  For
+// bsg_match_rows_wide: where a (set, query) pair's bit row lies in the result (pair_words), which conditions a set's queries reference
+// (query_cond_masks / set_cond_masks: the mask the storing walker opens a regex condition's DFA by), a part's pairs and tiles
+// (part_sets) and the work items of k_eval_row_programs (eval_items: a wave owns 64 consecutive rows of ONE set and a range of its
+// pairs).  tests/wide_plan_check.cpp runs the same code on the CPU (tests/test_match_wide_plan.py).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -83,6 +84,7 @@ inline std::vector<uint64_t> set_cond_masks(const std::vector<uint64_t> &query_m
 
 // Cut points of a call's rows for `want` devices of about equal bytes: each cut lies at a set-relative multiple of 64 rows (a
 // whole number of the set's 64-row tiles before it), so every (pair, tile) word is written by one device.  [0, ..., n_rows].
+// A target inside the last row counts as a row of the last set: the cut is that set's last tile boundary.
 inline std::vector<uint32_t> part_cuts(const uint64_t *row_off, uint32_t n_rows, const uint32_t *set_first_row, uint32_t n_sets, uint32_t want)
 {
     std::vector<uint32_t> cuts{0};
@@ -90,9 +92,8 @@ inline std::vector<uint32_t> part_cuts(const uint64_t *row_off, uint32_t n_rows,
     for (uint32_t i = 1; i < want; ++i) {
         const uint64_t target = row_off[0] + n_bytes * i / want;
         uint32_t r = (uint32_t)(std::lower_bound(row_off, row_off + n_rows, target) - row_off);
-        if (r >= n_rows) continue;
         // the set r lies in: the last one that begins at or before it
-        const uint32_t s = (uint32_t)(std::upper_bound(set_first_row, set_first_row + n_sets + 1, r) - set_first_row) - 1u;
+        const uint32_t s = (uint32_t)(std::upper_bound(set_first_row, set_first_row + n_sets, r) - set_first_row) - 1u;
         r = set_first_row[s] + (r - set_first_row[s]) / 64u * 64u;
         if (r > cuts.back() && r < n_rows) cuts.push_back(r);
     }
@@ -100,30 +101,41 @@ inline std::vector<uint32_t> part_cuts(const uint64_t *row_off, uint32_t n_rows,
     return cuts;
 }
 
-// What rows [r0, r1) of a call hold of its sets: per local set the rows (counted from r0), its pairs (indices into the call's
-// set_queries) and the set's tile its first row begins (r0 is a set-relative multiple of 64).
-struct PartSets {
+// The sets rows [r0, r1) of a call lie in, s0 on, their first rows clamped to the part and counted from r0 (what a walker's set
+// search reads; the batched call needs no more).
+struct SetRange {
     uint32_t s0 = 0;                       // the call's set of local set 0
     std::vector<uint32_t> first_row;       // [n + 1], counted from r0
+    uint32_t n() const { return (uint32_t)first_row.size() - 1u; }
+};
+
+inline SetRange part_set_range(const uint32_t *set_first_row, uint32_t n_sets, uint32_t r0, uint32_t r1)
+{
+    SetRange sr;
+    const uint32_t *sf = set_first_row;
+    sr.s0 = (uint32_t)(std::upper_bound(sf + 1, sf + n_sets + 1, r0) - (sf + 1));            // the first set that ends behind r0
+    const uint32_t s1 = (uint32_t)(std::lower_bound(sf, sf + n_sets, r1) - sf);              // the first set that begins at or behind r1
+    for (uint32_t s = sr.s0; s < s1; ++s) sr.first_row.push_back(std::max(sf[s], r0) - r0);
+    sr.first_row.push_back(r1 - r0);
+    return sr;
+}
+
+// ... and, for the wide call, per local set its pairs (indices into the call's set_queries) and the set's tile its first row begins
+// (r0 is a set-relative multiple of 64).
+struct PartSets : SetRange {
     std::vector<uint32_t> pair_off;        // [n + 1] into the call's set_queries
     std::vector<uint32_t> tile0;           // [n]: local tile 0 is this tile of the call's set
-    uint32_t n() const { return (uint32_t)tile0.size(); }
 };
 
 inline PartSets part_sets(const uint32_t *set_first_row, const uint32_t *set_query_off, uint32_t n_sets, uint32_t r0, uint32_t r1)
 {
     PartSets ps;
-    const uint32_t *sf = set_first_row;
-    ps.s0 = (uint32_t)(std::upper_bound(sf + 1, sf + n_sets + 1, r0) - (sf + 1));            // the first set that ends behind r0
-    const uint32_t s1 = (uint32_t)(std::lower_bound(sf, sf + n_sets, r1) - sf);              // the first set that begins at or behind r1
-    for (uint32_t s = ps.s0; s < s1; ++s) {
-        const uint32_t lo = std::max(sf[s], r0);
-        ps.first_row.push_back(lo - r0);
-        ps.pair_off.push_back(set_query_off[s]);
-        ps.tile0.push_back((lo - sf[s]) / 64u);
+    static_cast<SetRange &>(ps) = part_set_range(set_first_row, n_sets, r0, r1);
+    for (uint32_t ls = 0; ls < ps.n(); ++ls) {
+        ps.pair_off.push_back(set_query_off[ps.s0 + ls]);
+        ps.tile0.push_back((ps.first_row[ls] + r0 - set_first_row[ps.s0 + ls]) / 64u);
     }
-    ps.first_row.push_back(r1 - r0);
-    ps.pair_off.push_back(set_query_off[s1]);
+    ps.pair_off.push_back(set_query_off[ps.s0 + ps.n()]);
     return ps;
 }
 

@@ -1,4 +1,9 @@
-// match_api.inc — C-ABI of the device row matcher (included by bloomgpu.hip).  Kernel: match.hip.h.
+// match_api.inc — C-ABI of the device row matcher (included by bloomgpu.hip).  Kernels: match.hip.h; host arithmetic: host/wide_plan.hpp.
+// Every family (bsg_match_rows / _regex / _tok, bsg_match_rows_many / _many_regex, bsg_match_rows_wide) takes ONE path:
+//   entry point -> MatchCall (the caller's arguments) -> begin_match_call (tokenizer, program and input checks) -> the family's own
+//   checks (kinds, sets) -> lower_programs -> build_rx_blob -> match_fan_out (device cuts, parts, fallback fold) -> match_part per
+//   device (buffers, condition hashing, chunked upload, one walker launch per chunk through launch_walker, results back).
+// What a family adds to a part is its PartMode (PlanePart: bit planes; WidePart: stored flags, k_eval_row_programs, pair words).
 
 namespace {
 
@@ -28,153 +33,43 @@ int32_t build_rx_blob(const uint8_t *cond_bytes, const uint32_t *cond_off, const
     }
 }
 
-// bsg_match_rows_many: what a part needs beyond the single call's arguments.  `prog` then holds the lowered programs of all
-// queries behind each other and out_bits n_queries planes of call_words words.
-struct ManyPlan {
-    std::vector<uint32_t> prog_off;        // [n_queries + 1] into prog
-    const uint32_t *set_first_row;         // the call's set table (n_sets == 0: every query on every row)
-    const uint64_t *set_mask;
-    uint32_t n_sets, n_queries;
-    size_t call_words;
+static_assert(bsh_wide::kWideLdsCap == bsg::kRxWideLdsCap && sizeof(bsh_wide::EvalItem) == sizeof(bsg::RowEvalItem) &&
+                  offsetof(bsh_wide::EvalItem, stride) == offsetof(bsg::RowEvalItem, stride),
+              "host/wide_plan.hpp states the kernels' limits and item layout");
+
+// One row-matcher call.  The entry points fill the caller's arguments; validation and lowering fill the rest.
+struct MatchCall {
+    const uint8_t *rows;
+    const uint64_t *row_off;
+    uint32_t n_rows;
+    const uint8_t *cond_bytes;             // the condition table: strings 2c (field) and 2c + 1 (token) of condition c
+    const uint32_t *cond_off, *cond_kinds;
+    uint32_t n_conds;
+    uint64_t *out_bits;
+    uint32_t *out_fallback_rows;
+    uint32_t fallback_cap;
+    uint32_t *out_n_fallback;
+    uint64_t n_bytes = 0;                  // check_match_inputs
+    uint32_t cond_len = 0;
+    std::vector<uint32_t> prog;            // lower_programs: the lowered programs behind each other
+    std::vector<uint32_t> prog_off{0};     // [n_queries + 1] into prog
+    std::vector<uint32_t> rx_blob;         // build_rx_blob
+    uint32_t n_rx = 0;
+    bsg::TokSpec spec{};                   // tok_spec
+    bool default_tok = true;
+    const bsg::TokSpec *tok() const { return default_tok ? nullptr : &spec; }
 };
 
-// rows [r0, r1) (r0 a multiple of 64: whole words of out_bits) on one device; fb receives the GLOBAL indices of the rows handed back
-// many: the batched call (k_match_rows_many*; with regex conditions k_match_rows_many_regex*), NULL = one expression
-int32_t match_rows_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64_t *row_off, uint32_t r0, uint32_t r1,
-                      const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds, uint32_t cond_len,
-                      const std::vector<uint32_t> &prog, const std::vector<uint32_t> &rx_blob, uint32_t n_rx, const bsg::TokSpec *tok,
-                      uint64_t *out_bits, std::vector<uint32_t> &fb, float *ms, const ManyPlan *many = nullptr)
-{
-    const uint32_t n_rows = r1 - r0;
-    const uint64_t byte0 = row_off[r0], n_bytes = row_off[r1] - byte0;
-    const LabTrace trace{many ? (n_rx ? "bsg_match_rows_many_regex" : "bsg_match_rows_many") : "bsg_match_rows", d.id};
-    std::vector<uint64_t> local_off((size_t)n_rows + 1);                  // the run's offsets, relative to its first byte
-    for (uint32_t r = 0; r <= n_rows; ++r) local_off[r] = row_off[r0 + r] - byte0;
-    // the sets this run's rows lie in, their first rows clamped to the run and counted from r0
-    std::vector<uint32_t> set_first;
-    uint32_t s0 = 0, n_sets = 0;
-    if (many && many->n_sets) {
-        const uint32_t *sf = many->set_first_row;
-        s0 = (uint32_t)(std::upper_bound(sf + 1, sf + many->n_sets + 1, r0) - (sf + 1));       // the first set that ends behind r0
-        const uint32_t s1 = (uint32_t)(std::lower_bound(sf, sf + many->n_sets, r1) - sf);      // the first set that begins at or behind r1
-        n_sets = s1 - s0;
-        set_first.resize((size_t)n_sets + 1);
-        for (uint32_t i = 0; i <= n_sets; ++i) set_first[i] = std::min(std::max(sf[s0 + i], r0), r1) - r0;
-    }
-    d.calls.fetch_add(1, std::memory_order_relaxed);
-    std::lock_guard<std::mutex> lk(d.mu);
-    if (int32_t rc = use_device(d)) return rc;
-    if (int32_t rc = ensure_lower_table(d)) return rc;
-    trace.lap("offsets rebased, lock taken");
-    const size_t n_words = ((size_t)n_rows + 63) / 64, n_planes = many ? many->n_queries : 1;
-    Scratch scratch(d);                                                   // every early return below leaves through it: drained, then freed
-    uint8_t *d_rows = nullptr, *d_cbytes = nullptr;
-    uint64_t *d_off = nullptr, *d_ch = nullptr, *d_cfp = nullptr, *d_bits = nullptr;
-    uint32_t *d_prog = nullptr, *d_fb = nullptr, *d_nfb = nullptr, *d_coff = nullptr, *d_ckind = nullptr, *d_rx = nullptr;
-    uint32_t *d_poff = nullptr, *d_sfirst = nullptr;
-    uint64_t *d_smask = nullptr;
-    HIP_TRY(scratch.alloc(&d_rows, n_bytes + 64));
-    HIP_TRY(scratch.alloc(&d_off, ((size_t)n_rows + 1) * 8));
-    HIP_TRY(scratch.alloc(&d_ch, std::max<size_t>(n_conds, 1) * 2 * 32));
-    HIP_TRY(scratch.alloc(&d_cfp, std::max<size_t>(n_conds, 1) * 2 * 8));
-    HIP_TRY(scratch.alloc(&d_cbytes, (size_t)cond_len + 64));
-    HIP_TRY(scratch.alloc(&d_coff, ((size_t)2 * n_conds + 1) * 4));
-    HIP_TRY(scratch.alloc(&d_ckind, std::max<size_t>(n_conds, 1) * 4));
-    HIP_TRY(scratch.alloc(&d_prog, std::max<size_t>(prog.size(), 1) * 4));
-    HIP_TRY(scratch.alloc(&d_bits, n_words * n_planes * 8));
-    HIP_TRY(scratch.alloc(&d_fb, (size_t)n_rows * 4));
-    HIP_TRY(scratch.alloc(&d_nfb, 4));
-    if (n_rx) HIP_TRY(scratch.alloc(&d_rx, rx_blob.size() * 4));
-    if (many) HIP_TRY(scratch.alloc(&d_poff, many->prog_off.size() * 4));
-    if (n_sets) {
-        HIP_TRY(scratch.alloc(&d_sfirst, ((size_t)n_sets + 1) * 4));
-        HIP_TRY(scratch.alloc(&d_smask, (size_t)n_sets * 8));
-    }
-    trace.lap("device buffers allocated");
-    HIP_TRY(hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream));
-    HIP_TRY(hipMemcpyAsync(d_off, local_off.data(), ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream));
-    if (n_conds) {
-        // the condition strings are hashed AND fingerprinted (under the context's secret key) on the device
-        if (cond_len) HIP_TRY(hipMemcpyAsync(d_cbytes, cond_bytes, cond_len, hipMemcpyHostToDevice, d.stream));
-        HIP_TRY(hipMemsetAsync(d_cbytes + cond_len, 0, 64, d.stream));
-        HIP_TRY(hipMemcpyAsync(d_coff, cond_off, ((size_t)2 * n_conds + 1) * 4, hipMemcpyHostToDevice, d.stream));
-        HIP_TRY(hipMemcpyAsync(d_ckind, cond_kinds, (size_t)n_conds * 4, hipMemcpyHostToDevice, d.stream));
-        hipLaunchKernelGGL(bsg::k_hash_fp_entries, dim3((2 * n_conds + 255) / 256), dim3(256), 0, d.stream, (const uint8_t *)d_cbytes,
-                           (const uint32_t *)d_coff, 2 * n_conds, d_ch, d_cfp, ctx->fp_key);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!prog.empty()) HIP_TRY(hipMemcpyAsync(d_prog, prog.data(), prog.size() * 4, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemsetAsync(d_nfb, 0, 4, d.stream));
-    if (n_rx) HIP_TRY(hipMemcpyAsync(d_rx, rx_blob.data(), rx_blob.size() * 4, hipMemcpyHostToDevice, d.stream));
-    if (many) HIP_TRY(hipMemcpyAsync(d_poff, many->prog_off.data(), many->prog_off.size() * 4, hipMemcpyHostToDevice, d.stream));
-    if (n_sets) {
-        HIP_TRY(hipMemcpyAsync(d_sfirst, set_first.data(), ((size_t)n_sets + 1) * 4, hipMemcpyHostToDevice, d.stream));
-        HIP_TRY(hipMemcpyAsync(d_smask, many->set_mask + s0, (size_t)n_sets * 8, hipMemcpyHostToDevice, d.stream));
-    }
-    // The rows travel in chunks while the chunk before is being matched (RowUpload).  A surviving block is <= 10 MiB and goes in
-    // one piece, in order on the one stream; a scan of many blocks in one call goes in pieces on the copy stream.
-    RowUpload up(d, rows + byte0, d_rows, local_off.data(), n_rows, ctx->ingest_chunk_bytes);
-    const uint32_t n_chunks = up.n_chunks();
-    HIP_TRY(up.start(n_chunks > 1));
-    trace.lap("small uploads enqueued");
-    HIP_TRY(up.copy(0));
-    EventList kev;                                                       // per chunk: kernel start, kernel stop
-    for (uint32_t c = 0; c < n_chunks; ++c) {
-        const uint32_t rf = up.cuts[c], re = up.cuts[c + 1];
-        bsg::MatchArgs a{};
-        a.rows = d_rows; a.row_off = d_off + rf; a.cond_h = d_ch; a.cond_fp = d_cfp; a.cond_kind = d_ckind; a.prog = d_prog; a.lower = d.d_lower;
-        a.key = ctx->fp_key;
-        a.out_bits = d_bits + rf / 64; a.fallback_rows = d_fb; a.n_fallback = d_nfb;
-        a.n_rows = re - rf; a.row_base = rf; a.n_conds = n_conds; a.n_ops = (uint32_t)prog.size();
-        HIP_TRY(kev.add(2));
-        HIP_TRY(up.wait_landed(c));
-        const hipEvent_t k0 = kev.v[(size_t)c * 2], k1 = kev.v[(size_t)c * 2 + 1];
-        const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads);
-        if (many) {
-            const bsg::MatchManyArgs m{d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets};
-            const bsg::RxArgs x{d_rx, (uint32_t)rx_blob.size(), n_rx};
-            const uint32_t rx_lds = bsg::kMatchManyLdsBytes + (uint32_t)rx_blob.size() * 4;
-            if (n_rx && tok)
-                hipExtLaunchKernelGGL(bsg::k_match_rows_many_regex_tok, grid, dim3(bsg::kIngestThreads), rx_lds, d.stream, k0, k1, 0, a, x, m, *tok);
-            else if (n_rx)
-                hipExtLaunchKernelGGL(bsg::k_match_rows_many_regex, grid, dim3(bsg::kIngestThreads), rx_lds, d.stream, k0, k1, 0, a, x, m);
-            else if (tok)
-                hipExtLaunchKernelGGL(bsg::k_match_rows_many_tok, grid, dim3(bsg::kIngestThreads), bsg::kMatchManyLdsBytes, d.stream, k0, k1, 0, a, m, *tok);
-            else
-                hipExtLaunchKernelGGL(bsg::k_match_rows_many, grid, dim3(bsg::kIngestThreads), bsg::kMatchManyLdsBytes, d.stream, k0, k1, 0, a, m);
-        } else if (n_rx && tok) {
-            const bsg::RxArgs x{d_rx, (uint32_t)rx_blob.size(), n_rx};
-            hipExtLaunchKernelGGL(bsg::k_match_rows_regex_tok, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes + (uint32_t)rx_blob.size() * 4,
-                                  d.stream, k0, k1, 0, a, x, *tok);
-        } else if (n_rx) {
-            const bsg::RxArgs x{d_rx, (uint32_t)rx_blob.size(), n_rx};
-            hipExtLaunchKernelGGL(bsg::k_match_rows_regex, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes + (uint32_t)rx_blob.size() * 4,
-                                  d.stream, k0, k1, 0, a, x);
-        } else if (tok) {
-            hipExtLaunchKernelGGL(bsg::k_match_rows_tok, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes, d.stream, k0, k1, 0, a, *tok);
-        } else {
-            hipExtLaunchKernelGGL(bsg::k_match_rows, grid, dim3(bsg::kIngestThreads), bsg::kMatchLdsBytes, d.stream, k0, k1, 0, a);
-        }
-        HIP_TRY(hipGetLastError());
-        if (c + 1 < n_chunks) HIP_TRY(up.copy(c + 1));                   // K(c) is running: now the next chunk's bytes
-    }
-    trace.lap("all chunks enqueued");
-    uint32_t nfb = 0;
-    if (!many || many->call_words == n_words)
-        HIP_TRY(hipMemcpyAsync(out_bits + r0 / 64, d_bits, n_words * n_planes * 8, hipMemcpyDeviceToHost, d.stream));
-    else                                                                 // this run's words of every plane
-        HIP_TRY(hipMemcpy2DAsync(out_bits + r0 / 64, many->call_words * 8, d_bits, n_words * 8, n_words * 8, n_planes, hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(hipMemcpyAsync(&nfb, d_nfb, 4, hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    trace.lap("matched, bits back");
-    *ms = 0.f;
-    for (uint32_t c = 0; c < n_chunks; ++c) { float t = 0.f; (void)hipEventElapsedTime(&t, kev.v[(size_t)c * 2], kev.v[(size_t)c * 2 + 1]); *ms += t; }
-    fb.resize(nfb);
-    if (nfb) HIP_TRY(hipMemcpy(fb.data(), d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
-    for (uint32_t &r : fb) r += r0;
-    scratch.done();                        // every kernel has finished, and each waited for its chunk's copy
-    return BSG_OK;
-}
+// What differs between the families in the shared checks: limits and the words their messages name the call by.
+struct Family {
+    uint32_t max_queries;
+    const char *call;                      // "%u queries (one <call> match call holds %u)"
+    uint32_t max_ops;
+    const char *programs_of;               // "the <programs_of> programs hold more than ..."; NULL: the single call's one message
+};
+constexpr Family kSingleFamily{1, "single", bsg::kMatchMaxOps, nullptr};
+constexpr Family kManyFamily{bsg::kMatchManyMaxQueries, "batched", bsg::kMatchManyMaxOps, "batch's"};
+constexpr Family kWideFamily{bsh_wide::kMaxQueries, "wide", bsh_wide::kMaxOps, "call's"};
 
 // What every row-matcher call checks of its rows and conditions (the kinds themselves are the caller's); cond_len / n_bytes out.
 int32_t check_match_inputs(const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows, const uint8_t *cond_bytes, const uint32_t *cond_off,
@@ -195,110 +90,404 @@ int32_t check_match_inputs(const uint8_t *rows, const uint64_t *row_off, uint32_
     return BSG_OK;
 }
 
+// The head of every call: the tokenizer spec, the query limit, the program table and check_match_inputs.
+int32_t begin_match_call(MatchCall &mc, const Family &f, const bsg_tokenizer *tok_in, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries)
+{
+    bsg_tokenizer rec{};
+    if (int32_t rc = tok_spec(tok_in, rec, mc.spec, mc.default_tok)) return rc;
+    if (n_queries > f.max_queries) return fail(BSG_E_UNSUPPORTED, "%u queries (one %s match call holds %u)", n_queries, f.call, f.max_queries);
+    if (n_queries && !prog_off) return fail(BSG_E_INVALID, "prog_off is null");
+    for (uint32_t q = 0; q < n_queries; ++q)
+        if (prog_off[q + 1] < prog_off[q]) return fail(BSG_E_INVALID, "prog_off not monotone at %u", q);
+    if (n_queries && prog_off[n_queries] > prog_off[0] && !prog_ops) return fail(BSG_E_INVALID, "prog_ops is null");
+    return check_match_inputs(mc.rows, mc.row_off, mc.n_rows, mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.out_bits, mc.out_n_fallback,
+                              mc.cond_len, mc.n_bytes);
+}
+
+// Every query's program lowered over the identity term positions into mc.prog / mc.prog_off: depth <= 64 per query, f.max_ops in all.
+int32_t lower_programs(MatchCall &mc, const Family &f, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries)
+{
+    std::vector<uint32_t> ident(mc.n_conds), one;
+    for (uint32_t c = 0; c < mc.n_conds; ++c) ident[c] = c;
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        uint32_t depth = 1;
+        if (int32_t rc = lower_program(prog_ops + prog_off[q], prog_off[q + 1] - prog_off[q], mc.n_conds, ident, one, depth)) return rc;
+        if (!f.programs_of) {
+            if (depth > 64 || one.size() > f.max_ops)
+                return fail(BSG_E_UNSUPPORTED, "expression too large for the device matcher (depth %u, %zu ops)", depth, one.size());
+        } else if (depth > 64) {
+            return fail(BSG_E_UNSUPPORTED, "query %u: expression too deep for the device matcher (depth %u)", q, depth);
+        }
+        mc.prog.insert(mc.prog.end(), one.begin(), one.end());
+        if (mc.prog.size() > f.max_ops)
+            return fail(BSG_E_UNSUPPORTED, "the %s programs hold more than %u lowered ops (at query %u)", f.programs_of, f.max_ops, q);
+        mc.prog_off.push_back((uint32_t)mc.prog.size());
+    }
+    return BSG_OK;
+}
+
+// ---- the twelve walkers: (single / many / wide) x (regex) x (tokenizer spec) ----
+// E: the mode's own argument struct (none, MatchManyArgs, MatchWideArgs).  Dynamic LDS: the mode's base plus the regex blob's bytes
+// (a call without regex conditions has no blob).
+template <class... E>
+struct Walkers {
+    void (*plain)(bsg::MatchArgs, E...);
+    void (*tok)(bsg::MatchArgs, E..., bsg::TokSpec);
+    void (*regex)(bsg::MatchArgs, bsg::RxArgs, E...);
+    void (*regex_tok)(bsg::MatchArgs, bsg::RxArgs, E..., bsg::TokSpec);
+    uint32_t lds;
+};
+constexpr Walkers<> kSingleWalkers{bsg::k_match_rows, bsg::k_match_rows_tok, bsg::k_match_rows_regex, bsg::k_match_rows_regex_tok, bsg::kMatchLdsBytes};
+constexpr Walkers<bsg::MatchManyArgs> kManyWalkers{bsg::k_match_rows_many, bsg::k_match_rows_many_tok, bsg::k_match_rows_many_regex,
+                                                   bsg::k_match_rows_many_regex_tok, bsg::kMatchManyLdsBytes};
+constexpr Walkers<bsg::MatchWideArgs> kWideWalkers{bsg::k_match_rows_store, bsg::k_match_rows_store_tok, bsg::k_match_rows_store_regex,
+                                                   bsg::k_match_rows_store_regex_tok, bsg::kMatchWideLdsBytes};
+
+// one chunk's walk: a.n_rows rows, one per lane, between the events k0 and k1
+template <class... E>
+void launch_walker(const Walkers<E...> &w, hipStream_t stream, hipEvent_t k0, hipEvent_t k1, const bsg::MatchArgs &a, const bsg::RxArgs &x,
+                   const bsg::TokSpec *tok, const E &...e)
+{
+    const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads), block(bsg::kIngestThreads);
+    const uint32_t lds = w.lds + x.n_words * 4;
+    if (x.n_rx && tok) hipExtLaunchKernelGGL(w.regex_tok, grid, block, lds, stream, k0, k1, 0, a, x, e..., *tok);
+    else if (x.n_rx) hipExtLaunchKernelGGL(w.regex, grid, block, lds, stream, k0, k1, 0, a, x, e...);
+    else if (tok) hipExtLaunchKernelGGL(w.tok, grid, block, lds, stream, k0, k1, 0, a, e..., *tok);
+    else hipExtLaunchKernelGGL(w.plain, grid, block, lds, stream, k0, k1, 0, a, e...);
+}
+
+// ---- one part: rows [r0, r1) of a call on one device ----
+// What match_part hands a mode's hooks: the device (its lock held), the part's scratch and what is on the device already.
+struct PartDev {
+    Device &d;
+    Scratch &scratch;
+    uint32_t r0, n_rows;
+    uint32_t *d_prog = nullptr, *d_poff = nullptr;     // the call's lowered programs and (mode.prog_off()) their offsets
+    bsg::RxArgs rx{};                                  // the regex blob
+};
+
+// bsg_match_rows_many: what a part needs beyond the call.  mc.prog then holds the lowered programs of all queries behind each other
+// and out_bits n_queries planes of call_words words.
+struct ManyPlan {
+    const uint32_t *set_first_row;         // the call's set table (n_sets == 0: every query on every row)
+    const uint64_t *set_mask;
+    uint32_t n_sets, n_queries;
+    size_t call_words;
+};
+
+// The single and the batched calls: the walker evaluates, one plane of bits per query.  r0 is a multiple of 64: whole words.
+struct PlanePart {
+    static constexpr const char *kPlanned = "offsets rebased, lock taken", *kBack = "matched, bits back";
+    const MatchCall &mc;
+    const ManyPlan *many;                              // NULL = one expression
+    bsh_wide::SetRange sets;                           // the part's sets, their first rows counted from r0
+    uint32_t n_sets = 0;
+    size_t n_words = 0, n_planes = 1;
+    uint64_t *d_bits = nullptr, *d_smask = nullptr;
+    uint32_t *d_sfirst = nullptr;
+
+    const char *tag() const { return many ? (mc.n_rx ? "bsg_match_rows_many_regex" : "bsg_match_rows_many") : "bsg_match_rows"; }
+    bool prog_off() const { return many != nullptr; }
+    int32_t plan(uint32_t r0, uint32_t r1)
+    {
+        n_words = ((size_t)(r1 - r0) + 63) / 64;
+        if (many) n_planes = many->n_queries;
+        if (many && many->n_sets) {
+            sets = bsh_wide::part_set_range(many->set_first_row, many->n_sets, r0, r1);
+            n_sets = sets.n();
+        }
+        return BSG_OK;
+    }
+    int32_t alloc(PartDev &p)
+    {
+        HIP_TRY(p.scratch.alloc(&d_bits, n_words * n_planes * 8));
+        if (n_sets) {
+            HIP_TRY(p.scratch.alloc(&d_sfirst, ((size_t)n_sets + 1) * 4));
+            HIP_TRY(p.scratch.alloc(&d_smask, (size_t)n_sets * 8));
+        }
+        return BSG_OK;
+    }
+    int32_t upload(PartDev &p)
+    {
+        if (n_sets) {
+            HIP_TRY(hipMemcpyAsync(d_sfirst, sets.first_row.data(), ((size_t)n_sets + 1) * 4, hipMemcpyHostToDevice, p.d.stream));
+            HIP_TRY(hipMemcpyAsync(d_smask, many->set_mask + sets.s0, (size_t)n_sets * 8, hipMemcpyHostToDevice, p.d.stream));
+        }
+        return BSG_OK;
+    }
+    void launch(PartDev &p, bsg::MatchArgs &a, uint32_t rf, hipEvent_t k0, hipEvent_t k1)
+    {
+        a.prog = p.d_prog; a.n_ops = (uint32_t)mc.prog.size(); a.out_bits = d_bits + rf / 64;
+        if (many) launch_walker(kManyWalkers, p.d.stream, k0, k1, a, p.rx, mc.tok(), bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
+        else launch_walker(kSingleWalkers, p.d.stream, k0, k1, a, p.rx, mc.tok());
+    }
+    int32_t results(PartDev &p, EventList &)           // this part's words of every plane
+    {
+        if (!many || many->call_words == n_words)
+            HIP_TRY(hipMemcpyAsync(mc.out_bits + p.r0 / 64, d_bits, n_words * n_planes * 8, hipMemcpyDeviceToHost, p.d.stream));
+        else
+            HIP_TRY(hipMemcpy2DAsync(mc.out_bits + p.r0 / 64, many->call_words * 8, d_bits, n_words * 8, n_words * 8, n_planes, hipMemcpyDeviceToHost, p.d.stream));
+        return BSG_OK;
+    }
+    void landed() {}
+};
+
+// bsg_match_rows_wide: what a part needs beyond the call (sets always materialised: the implicit set is one set with every query)
+struct WidePlan {
+    const uint32_t *set_first_row, *set_query_off, *set_queries;
+    uint32_t n_sets, n_queries;
+    std::vector<uint64_t> set_cond_mask;       // [n_sets]
+    std::vector<uint64_t> set_word0;           // [n_sets + 1]: the first result word of the set's first pair
+};
+
+// The wide call: the storing walk chunk by chunk, then one evaluation launch over the part's items (r0 a set-relative multiple of 64).
+// direct: the part is the whole call and its words go straight to out_bits; else they are scattered on the host into the call's
+// layout (a set cut by a part boundary has some of its tiles here and some on the next device).
+struct WidePart {
+    static constexpr const char *kPlanned = "part planned, lock taken", *kBack = "matched, words back";
+    const MatchCall &mc;
+    const WidePlan &wp;
+    const bool direct;
+    bsh_wide::PartSets ps;
+    uint32_t n_sets = 0, pair0 = 0, n_pairs = 0;
+    std::vector<uint32_t> pair_off_local;
+    std::vector<bsh_wide::EvalItem> items;
+    uint64_t part_words = 0;
+    std::vector<uint64_t> staged;
+    uint8_t *d_state = nullptr;
+    uint64_t *d_sat = nullptr, *d_out = nullptr, *d_smask = nullptr;
+    uint32_t *d_sfirst = nullptr, *d_spair = nullptr, *d_pairs = nullptr;
+    bsg::RowEvalItem *d_items = nullptr;
+
+    const char *tag() const { return "bsg_match_rows_wide"; }
+    bool prog_off() const { return true; }
+    int32_t plan(uint32_t r0, uint32_t r1)
+    {
+        ps = bsh_wide::part_sets(wp.set_first_row, wp.set_query_off, wp.n_sets, r0, r1);
+        n_sets = ps.n(); pair0 = ps.pair_off[0]; n_pairs = ps.pair_off[n_sets] - pair0;
+        pair_off_local = ps.pair_off;
+        for (uint32_t &v : pair_off_local) v -= pair0;
+        if (!bsh_wide::eval_items(ps, items, part_words))
+            return fail(BSG_E_UNSUPPORTED, "more than %u (tile, pair range) items on one device", bsh_wide::kMaxItems);
+        return BSG_OK;
+    }
+    int32_t alloc(PartDev &p)
+    {
+        HIP_TRY(p.scratch.alloc(&d_sat, (size_t)p.n_rows * 8));
+        HIP_TRY(p.scratch.alloc(&d_state, (size_t)p.n_rows));
+        HIP_TRY(p.scratch.alloc(&d_out, std::max<uint64_t>(part_words, 1) * 8));
+        HIP_TRY(p.scratch.alloc(&d_sfirst, ((size_t)n_sets + 1) * 4));
+        HIP_TRY(p.scratch.alloc(&d_spair, ((size_t)n_sets + 1) * 4));
+        HIP_TRY(p.scratch.alloc(&d_smask, (size_t)n_sets * 8));
+        HIP_TRY(p.scratch.alloc(&d_pairs, std::max<size_t>(n_pairs, 1) * 4));
+        HIP_TRY(p.scratch.alloc(&d_items, std::max<size_t>(items.size(), 1) * sizeof(bsg::RowEvalItem)));
+        return BSG_OK;
+    }
+    int32_t upload(PartDev &p)
+    {
+        HIP_TRY(hipMemcpyAsync(d_sfirst, ps.first_row.data(), ((size_t)n_sets + 1) * 4, hipMemcpyHostToDevice, p.d.stream));
+        HIP_TRY(hipMemcpyAsync(d_spair, pair_off_local.data(), ((size_t)n_sets + 1) * 4, hipMemcpyHostToDevice, p.d.stream));
+        HIP_TRY(hipMemcpyAsync(d_smask, wp.set_cond_mask.data() + ps.s0, (size_t)n_sets * 8, hipMemcpyHostToDevice, p.d.stream));
+        if (n_pairs) HIP_TRY(hipMemcpyAsync(d_pairs, wp.set_queries + pair0, (size_t)n_pairs * 4, hipMemcpyHostToDevice, p.d.stream));
+        if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::RowEvalItem), hipMemcpyHostToDevice, p.d.stream));
+        return BSG_OK;
+    }
+    void launch(PartDev &p, bsg::MatchArgs &a, uint32_t rf, hipEvent_t k0, hipEvent_t k1)
+    {
+        launch_walker(kWideWalkers, p.d.stream, k0, k1, a, p.rx, mc.tok(), bsg::MatchWideArgs{d_sfirst, d_smask, d_spair, d_sat + rf, d_state + rf, n_sets});
+    }
+    int32_t results(PartDev &p, EventList &kev)        // the evaluation between two more events, then the part's words
+    {
+        if (!items.empty()) {
+            const size_t k = kev.v.size();
+            HIP_TRY(kev.add(2));
+            const bsg::RowEvalArgs e{d_items, d_pairs, p.d_poff, p.d_prog, d_sat, d_state, d_out, (uint32_t)items.size()};
+            const uint32_t per_block = bsg::kRowEvalThreads / 64;
+            hipExtLaunchKernelGGL(bsg::k_eval_row_programs, dim3(((uint32_t)items.size() + per_block - 1) / per_block), dim3(bsg::kRowEvalThreads), 0,
+                                  p.d.stream, kev.v[k], kev.v[k + 1], 0, e);
+            HIP_TRY(hipGetLastError());
+        }
+        if (part_words) {
+            uint64_t *dst = mc.out_bits + wp.set_word0[ps.s0];
+            if (!direct) { staged.resize(part_words); dst = staged.data(); }
+            HIP_TRY(hipMemcpyAsync(dst, d_out, part_words * 8, hipMemcpyDeviceToHost, p.d.stream));
+        }
+        return BSG_OK;
+    }
+    void landed()                                      // the part's layout -> the call's: per pair, the part's tiles of the set
+    {
+        if (direct) return;
+        uint64_t at = 0;
+        for (uint32_t ls = 0; ls < n_sets; ++ls) {
+            const uint32_t s = ps.s0 + ls, tiles = bsh_wide::tiles_of(ps.first_row[ls + 1] - ps.first_row[ls]);
+            const uint32_t set_tiles = bsh_wide::tiles_of(wp.set_first_row[s + 1] - wp.set_first_row[s]);
+            for (uint32_t p = ps.pair_off[ls]; p < ps.pair_off[ls + 1] && tiles; ++p, at += tiles)
+                memcpy(mc.out_bits + wp.set_word0[s] + (uint64_t)(p - wp.set_query_off[s]) * set_tiles + ps.tile0[ls], staged.data() + at, (size_t)tiles * 8);
+        }
+    }
+};
+
+// Rows [r0, r1) on one device, for every family: the rows' offsets rebased, the device's lock, scratch for rows / offsets / the
+// condition table / programs / blob / fallback list, the conditions hashed and fingerprinted on the device, the rows uploaded in
+// chunks (RowUpload) with one walker launch per chunk, the mode's results and the fallback rows back (GLOBAL indices), the
+// kernels' time in *ms.  mode: PlanePart or WidePart.
+template <class Mode>
+int32_t match_part(bsg_ctx *ctx, Device &d, const MatchCall &mc, uint32_t r0, uint32_t r1, Mode &mode, std::vector<uint32_t> &fb, float *ms)
+{
+    const uint32_t n_rows = r1 - r0, n_conds = mc.n_conds;
+    const uint64_t byte0 = mc.row_off[r0], n_bytes = mc.row_off[r1] - byte0;
+    const LabTrace trace{mode.tag(), d.id};
+    std::vector<uint64_t> local_off((size_t)n_rows + 1);                  // the run's offsets, relative to its first byte
+    for (uint32_t r = 0; r <= n_rows; ++r) local_off[r] = mc.row_off[r0 + r] - byte0;
+    if (int32_t rc = mode.plan(r0, r1)) return rc;
+    d.calls.fetch_add(1, std::memory_order_relaxed);
+    std::lock_guard<std::mutex> lk(d.mu);
+    if (int32_t rc = use_device(d)) return rc;
+    if (int32_t rc = ensure_lower_table(d)) return rc;
+    trace.lap(Mode::kPlanned);
+    Scratch scratch(d);                                                   // every early return below leaves through it: drained, then freed
+    PartDev p{d, scratch, r0, n_rows};
+    uint8_t *d_rows = nullptr, *d_cbytes = nullptr;
+    uint64_t *d_off = nullptr, *d_ch = nullptr, *d_cfp = nullptr;
+    uint32_t *d_fb = nullptr, *d_nfb = nullptr, *d_coff = nullptr, *d_ckind = nullptr, *d_rx = nullptr;
+    HIP_TRY(scratch.alloc(&d_rows, n_bytes + 64));
+    HIP_TRY(scratch.alloc(&d_off, ((size_t)n_rows + 1) * 8));
+    HIP_TRY(scratch.alloc(&d_ch, std::max<size_t>(n_conds, 1) * 2 * 32));
+    HIP_TRY(scratch.alloc(&d_cfp, std::max<size_t>(n_conds, 1) * 2 * 8));
+    HIP_TRY(scratch.alloc(&d_cbytes, (size_t)mc.cond_len + 64));
+    HIP_TRY(scratch.alloc(&d_coff, ((size_t)2 * n_conds + 1) * 4));
+    HIP_TRY(scratch.alloc(&d_ckind, std::max<size_t>(n_conds, 1) * 4));
+    HIP_TRY(scratch.alloc(&p.d_prog, std::max<size_t>(mc.prog.size(), 1) * 4));
+    if (mode.prog_off()) HIP_TRY(scratch.alloc(&p.d_poff, mc.prog_off.size() * 4));
+    HIP_TRY(scratch.alloc(&d_fb, (size_t)n_rows * 4));
+    HIP_TRY(scratch.alloc(&d_nfb, 4));
+    if (mc.n_rx) HIP_TRY(scratch.alloc(&d_rx, mc.rx_blob.size() * 4));
+    if (int32_t rc = mode.alloc(p)) return rc;
+    trace.lap("device buffers allocated");
+    HIP_TRY(hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream));
+    HIP_TRY(hipMemcpyAsync(d_off, local_off.data(), ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream));
+    if (n_conds) {
+        // the condition strings are hashed AND fingerprinted (under the context's secret key) on the device
+        if (mc.cond_len) HIP_TRY(hipMemcpyAsync(d_cbytes, mc.cond_bytes, mc.cond_len, hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemsetAsync(d_cbytes + mc.cond_len, 0, 64, d.stream));
+        HIP_TRY(hipMemcpyAsync(d_coff, mc.cond_off, ((size_t)2 * n_conds + 1) * 4, hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemcpyAsync(d_ckind, mc.cond_kinds, (size_t)n_conds * 4, hipMemcpyHostToDevice, d.stream));
+        hipLaunchKernelGGL(bsg::k_hash_fp_entries, dim3((2 * n_conds + 255) / 256), dim3(256), 0, d.stream, (const uint8_t *)d_cbytes,
+                           (const uint32_t *)d_coff, 2 * n_conds, d_ch, d_cfp, ctx->fp_key);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!mc.prog.empty()) HIP_TRY(hipMemcpyAsync(p.d_prog, mc.prog.data(), mc.prog.size() * 4, hipMemcpyHostToDevice, d.stream));
+    if (p.d_poff) HIP_TRY(hipMemcpyAsync(p.d_poff, mc.prog_off.data(), mc.prog_off.size() * 4, hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipMemsetAsync(d_nfb, 0, 4, d.stream));
+    if (mc.n_rx) HIP_TRY(hipMemcpyAsync(d_rx, mc.rx_blob.data(), mc.rx_blob.size() * 4, hipMemcpyHostToDevice, d.stream));
+    p.rx = bsg::RxArgs{d_rx, (uint32_t)mc.rx_blob.size(), mc.n_rx};
+    if (int32_t rc = mode.upload(p)) return rc;
+    // The rows travel in chunks while the chunk before is being matched (RowUpload).  A surviving block is <= 10 MiB and goes in
+    // one piece, in order on the one stream; a scan of many blocks in one call goes in pieces on the copy stream.
+    RowUpload up(d, mc.rows + byte0, d_rows, local_off.data(), n_rows, ctx->ingest_chunk_bytes);
+    const uint32_t n_chunks = up.n_chunks();
+    HIP_TRY(up.start(n_chunks > 1));
+    trace.lap("small uploads enqueued");
+    HIP_TRY(up.copy(0));
+    EventList kev;                                                       // per launch: kernel start, kernel stop
+    for (uint32_t c = 0; c < n_chunks; ++c) {
+        const uint32_t rf = up.cuts[c], re = up.cuts[c + 1];
+        bsg::MatchArgs a{};
+        a.rows = d_rows; a.row_off = d_off + rf; a.cond_h = d_ch; a.cond_fp = d_cfp; a.cond_kind = d_ckind; a.lower = d.d_lower;
+        a.key = ctx->fp_key;
+        a.fallback_rows = d_fb; a.n_fallback = d_nfb;
+        a.n_rows = re - rf; a.row_base = rf; a.n_conds = n_conds;
+        HIP_TRY(kev.add(2));
+        HIP_TRY(up.wait_landed(c));
+        mode.launch(p, a, rf, kev.v[(size_t)c * 2], kev.v[(size_t)c * 2 + 1]);
+        HIP_TRY(hipGetLastError());
+        if (c + 1 < n_chunks) HIP_TRY(up.copy(c + 1));                   // K(c) is running: now the next chunk's bytes
+    }
+    trace.lap("all chunks enqueued");
+    uint32_t nfb = 0;
+    if (int32_t rc = mode.results(p, kev)) return rc;
+    HIP_TRY(hipMemcpyAsync(&nfb, d_nfb, 4, hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    trace.lap(Mode::kBack);
+    *ms = 0.f;
+    for (size_t k = 0; k + 1 < kev.v.size(); k += 2) { float t = 0.f; (void)hipEventElapsedTime(&t, kev.v[k], kev.v[k + 1]); *ms += t; }
+    fb.resize(nfb);
+    if (nfb) HIP_TRY(hipMemcpy(fb.data(), d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
+    for (uint32_t &r : fb) r += r0;
+    scratch.done();                        // every kernel has finished, and each waited for its chunk's copy
+    mode.landed();
+    return BSG_OK;
+}
+
 // The validated, lowered call on the context's devices.
 // Surviving blocks are independent (query_exec.go:729-764): a large scan is cut into one contiguous run of rows per
-// device (on 64-row boundaries: whole words of out_bits, about equal bytes); a small one takes one device.
-int32_t match_rows_run(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows, uint64_t n_bytes,
-                       const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds, uint32_t cond_len,
-                       const std::vector<uint32_t> &prog, const std::vector<uint32_t> &rx_blob, uint32_t n_rx, const bsg::TokSpec *tok,
-                       uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback, const ManyPlan *many = nullptr)
+// device (bsh_wide::part_cuts over the call's sets: whole words of every result row, about equal bytes); a small one takes one
+// device.  part(i, n_parts, device, r0, r1, fb, ms) runs one of them; their fallback rows are merged, sorted and handed out.
+template <class F>
+int32_t match_fan_out(bsg_ctx *ctx, const MatchCall &mc, const uint32_t *set_first_row, uint32_t n_sets, F &&part)
 {
     const uint32_t nd = (uint32_t)ctx->devs.size();
-    uint32_t want = (nd > 1 && n_bytes >= ctx->shard_min_row_bytes) ? nd : 1;
-    std::vector<uint32_t> cuts{0};
-    for (uint32_t i = 1; i < want; ++i) {
-        const uint64_t target = row_off[0] + n_bytes * i / want;
-        uint32_t r = (uint32_t)(std::lower_bound(row_off, row_off + n_rows, target) - row_off);
-        r = r / 64 * 64;
-        if (r > cuts.back() && r < n_rows) cuts.push_back(r);
-    }
-    cuts.push_back(n_rows);
+    const uint32_t want = (nd > 1 && mc.n_bytes >= ctx->shard_min_row_bytes) ? nd : 1;
+    const std::vector<uint32_t> cuts = bsh_wide::part_cuts(mc.row_off, mc.n_rows, set_first_row, n_sets, want);
     const uint32_t n_parts = (uint32_t)cuts.size() - 1;
     std::vector<std::vector<uint32_t>> fbs(n_parts);
     std::vector<float> ms(n_parts, 0.f);
     const uint32_t first = n_parts == 1 ? pick_device(ctx) : 0;
     if (int32_t rc = run_parts(n_parts, [&](uint32_t i) -> int32_t {
-            return match_rows_on(ctx, *ctx->devs[(first + i) % nd], rows, row_off, cuts[i], cuts[i + 1], cond_bytes, cond_off, cond_kinds, n_conds,
-                                 cond_len, prog, rx_blob, n_rx, tok, out_bits, fbs[i], &ms[i], many);
+            return part(n_parts, *ctx->devs[(first + i) % nd], cuts[i], cuts[i + 1], fbs[i], &ms[i]);
         })) return rc;
     std::vector<uint32_t> fb;
     for (auto &v : fbs) fb.insert(fb.end(), v.begin(), v.end());
     std::sort(fb.begin(), fb.end());
-    *out_n_fallback = (uint32_t)fb.size();
-    if (!fb.empty() && out_fallback_rows) memcpy(out_fallback_rows, fb.data(), (size_t)std::min<uint32_t>((uint32_t)fb.size(), fallback_cap) * 4);
+    *mc.out_n_fallback = (uint32_t)fb.size();
+    if (!fb.empty() && mc.out_fallback_rows)
+        memcpy(mc.out_fallback_rows, fb.data(), (size_t)std::min<uint32_t>((uint32_t)fb.size(), mc.fallback_cap) * 4);
     {
         std::lock_guard<std::shared_mutex> lk(ctx->mu);
         ctx->last_match_ms = *std::max_element(ms.begin(), ms.end());
     }
-    if (fb.size() > fallback_cap && out_fallback_rows)
-        return fail(BSG_E_INVALID, "%zu rows need the host matcher, caller's list holds %u", fb.size(), fallback_cap);
+    if (fb.size() > mc.fallback_cap && mc.out_fallback_rows)
+        return fail(BSG_E_INVALID, "%zu rows need the host matcher, caller's list holds %u", fb.size(), mc.fallback_cap);
     return BSG_OK;
 }
 
-// bsg_match_rows (max_kind 2), bsg_match_rows_regex (max_kind 3) and bsg_match_rows_tok (max_kind 3, a spec; NULL = default)
-int32_t match_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
-                        const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
-                        const uint32_t *prog_ops, uint32_t n_ops,
-                        uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback, uint32_t max_kind,
-                        const bsg_tokenizer *tok_in = nullptr)
+// the single and the batched calls' parts: planes over the implicit set {0, n_rows} (cuts at multiples of 64 rows)
+int32_t match_planes_run(bsg_ctx *ctx, const MatchCall &mc, const ManyPlan *many)
 {
-    if (!ctx) return fail(BSG_E_INVALID, "ctx is null");
-    bsg_tokenizer rec{};
-    bsg::TokSpec spec{};
-    bool is_default = true;
-    if (int32_t rc = tok_spec(tok_in, rec, spec, is_default)) return rc;
-    const bsg::TokSpec *tok = is_default ? nullptr : &spec;
-    if (n_ops && !prog_ops) return fail(BSG_E_INVALID, "prog_ops is null");
-    uint32_t cond_len = 0;
-    uint64_t n_bytes = 0;
-    if (int32_t rc = check_match_inputs(rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_n_fallback, cond_len, n_bytes))
-        return rc;
-    for (uint32_t c = 0; c < n_conds; ++c)
-        if (cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, cond_kinds[c]);
-    std::vector<uint32_t> ident(n_conds), prog;
-    for (uint32_t c = 0; c < n_conds; ++c) ident[c] = c;
-    uint32_t depth = 1;
-    if (int32_t rc = lower_program(prog_ops, n_ops, n_conds, ident, prog, depth)) return rc;
-    if (depth > 64 || prog.size() > bsg::kMatchMaxOps)
-        return fail(BSG_E_UNSUPPORTED, "expression too large for the device matcher (depth %u, %zu ops)", depth, prog.size());
-    std::vector<uint32_t> rx_blob;
-    uint32_t n_rx = 0;
-    if (int32_t rc = build_rx_blob(cond_bytes, cond_off, cond_kinds, n_conds, rx_blob, n_rx)) return rc;
-    *out_n_fallback = 0;
-    if (n_rows == 0) return BSG_OK;
-    return match_rows_run(ctx, rows, row_off, n_rows, n_bytes, cond_bytes, cond_off, cond_kinds, n_conds, cond_len, prog, rx_blob, n_rx, tok, out_bits,
-                          out_fallback_rows, fallback_cap, out_n_fallback);
+    const uint32_t all_rows[2] = {0, mc.n_rows};
+    return match_fan_out(ctx, mc, all_rows, 1, [&](uint32_t, Device &d, uint32_t r0, uint32_t r1, std::vector<uint32_t> &fb, float *ms) -> int32_t {
+        PlanePart mode{mc, many};
+        return match_part(ctx, d, mc, r0, r1, mode, fb, ms);
+    });
+}
+
+// bsg_match_rows (max_kind 2), bsg_match_rows_regex (max_kind 3) and bsg_match_rows_tok (max_kind 3, a spec; NULL = default): the
+// one-query case of the shared checks
+int32_t match_rows_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, uint32_t n_ops, uint32_t max_kind, const bsg_tokenizer *tok_in)
+{
+    const uint32_t prog_off[2] = {0, n_ops};
+    if (int32_t rc = begin_match_call(mc, kSingleFamily, tok_in, prog_ops, prog_off, 1)) return rc;
+    for (uint32_t c = 0; c < mc.n_conds; ++c)
+        if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
+    if (int32_t rc = lower_programs(mc, kSingleFamily, prog_ops, prog_off, 1)) return rc;
+    if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx)) return rc;
+    *mc.out_n_fallback = 0;
+    if (mc.n_rows == 0) return BSG_OK;
+    return match_planes_run(ctx, mc, nullptr);
 }
 
 // bsg_match_rows_many (max_kind 2) and bsg_match_rows_many_regex (max_kind 3): n_queries programs over one table of distinct
 // conditions, one upload and one walk of the rows
-int32_t match_rows_many_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
-                             const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
-                             const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+int32_t match_rows_many_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
                              const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets, const bsg_tokenizer *tok_in,
-                             uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback,
                              uint32_t max_kind)
 {
-    if (!ctx) return fail(BSG_E_INVALID, "ctx is null");
-    bsg_tokenizer rec{};
-    bsg::TokSpec spec{};
-    bool is_default = true;
-    if (int32_t rc = tok_spec(tok_in, rec, spec, is_default)) return rc;
-    const bsg::TokSpec *tok = is_default ? nullptr : &spec;
-    if (n_queries > bsg::kMatchManyMaxQueries)
-        return fail(BSG_E_UNSUPPORTED, "%u queries (one batched match call holds %u)", n_queries, bsg::kMatchManyMaxQueries);
-    if (n_queries && !prog_off) return fail(BSG_E_INVALID, "prog_off is null");
-    for (uint32_t q = 0; q < n_queries; ++q)
-        if (prog_off[q + 1] < prog_off[q]) return fail(BSG_E_INVALID, "prog_off not monotone at %u", q);
-    if (n_queries && prog_off[n_queries] > prog_off[0] && !prog_ops) return fail(BSG_E_INVALID, "prog_ops is null");
-    uint32_t cond_len = 0;
-    uint64_t n_bytes = 0;
-    if (int32_t rc = check_match_inputs(rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_n_fallback, cond_len, n_bytes))
-        return rc;
-    for (uint32_t c = 0; c < n_conds; ++c) {
-        if (cond_kinds[c] == BSG_KIND_FIELD_REGEX && max_kind < BSG_KIND_FIELD_REGEX)
+    if (int32_t rc = begin_match_call(mc, kManyFamily, tok_in, prog_ops, prog_off, n_queries)) return rc;
+    const uint32_t n_rows = mc.n_rows;
+    for (uint32_t c = 0; c < mc.n_conds; ++c) {
+        if (mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX && max_kind < BSG_KIND_FIELD_REGEX)
             return fail(BSG_E_UNSUPPORTED, "condition %u: FieldRegex conditions are not matched by the batched call (use bsg_match_rows_regex)", c);
-        if (cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, cond_kinds[c]);
+        if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
     }
     if (n_sets) {
         if (!set_first_row || !query_mask_of_set) return fail(BSG_E_INVALID, "set table is null");
@@ -310,186 +499,19 @@ int32_t match_rows_many_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *
                 return fail(BSG_E_INVALID, "set %u: mask 0x%llx has bits at or above query %u", s, (unsigned long long)query_mask_of_set[s], n_queries);
         }
     }
-    ManyPlan plan{{0}, set_first_row, query_mask_of_set, n_sets, n_queries, ((size_t)n_rows + 63) / 64};
-    std::vector<uint32_t> ident(n_conds), prog, one;
-    for (uint32_t c = 0; c < n_conds; ++c) ident[c] = c;
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        uint32_t depth = 1;
-        if (int32_t rc = lower_program(prog_ops + prog_off[q], prog_off[q + 1] - prog_off[q], n_conds, ident, one, depth)) return rc;
-        if (depth > 64) return fail(BSG_E_UNSUPPORTED, "query %u: expression too deep for the device matcher (depth %u)", q, depth);
-        prog.insert(prog.end(), one.begin(), one.end());
-        if (prog.size() > bsg::kMatchManyMaxOps)
-            return fail(BSG_E_UNSUPPORTED, "the batch's programs hold more than %u lowered ops (at query %u)", bsg::kMatchManyMaxOps, q);
-        plan.prog_off.push_back((uint32_t)prog.size());
-    }
+    const ManyPlan plan{set_first_row, query_mask_of_set, n_sets, n_queries, ((size_t)n_rows + 63) / 64};
+    if (int32_t rc = lower_programs(mc, kManyFamily, prog_ops, prog_off, n_queries)) return rc;
     // the regex conditions' tables, each with the queries that use it (a table without any: exactly bsg_match_rows_many's kernels)
-    std::vector<uint32_t> rx_blob;
-    uint32_t n_rx = 0;
     if (max_kind >= BSG_KIND_FIELD_REGEX && n_queries) {
-        const std::vector<uint64_t> users = bsh_rxg::user_masks(prog_ops, prog_off, n_queries, n_conds);
-        if (int32_t rc = build_rx_blob(cond_bytes, cond_off, cond_kinds, n_conds, rx_blob, n_rx, bsg::kRxManyLdsCap, users.data())) return rc;
+        const std::vector<uint64_t> users = bsh_rxg::user_masks(prog_ops, prog_off, n_queries, mc.n_conds);
+        if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, bsg::kRxManyLdsCap, users.data())) return rc;
     }
     if (n_queries == 0 || n_rows == 0) return BSG_OK;
-    *out_n_fallback = 0;
-    return match_rows_run(ctx, rows, row_off, n_rows, n_bytes, cond_bytes, cond_off, cond_kinds, n_conds, cond_len, prog, rx_blob, n_rx, tok, out_bits,
-                          out_fallback_rows, fallback_cap, out_n_fallback, &plan);
+    *mc.out_n_fallback = 0;
+    return match_planes_run(ctx, mc, &plan);
 }
 
 // ---- bsg_match_rows_wide: any number of queries over one condition table (k_match_rows_store*, then k_eval_row_programs) ----
-static_assert(bsh_wide::kWideLdsCap == bsg::kRxWideLdsCap && sizeof(bsh_wide::EvalItem) == sizeof(bsg::RowEvalItem) &&
-                  offsetof(bsh_wide::EvalItem, stride) == offsetof(bsg::RowEvalItem, stride),
-              "host/wide_plan.hpp states the kernels' limits and item layout");
-
-// what a part needs of the validated call (sets always materialised: the implicit set is one set with every query)
-struct WidePlan {
-    const uint32_t *set_first_row, *set_query_off, *set_queries;
-    uint32_t n_sets, n_queries;
-    std::vector<uint32_t> prog_off;            // [n_queries + 1] into the lowered programs
-    std::vector<uint64_t> set_cond_mask;       // [n_sets]
-    std::vector<uint64_t> set_word0;           // [n_sets + 1]: the first result word of the set's first pair
-};
-
-// rows [r0, r1) (r0 a set-relative multiple of 64) on one device: the storing walk chunk by chunk, then one evaluation launch over
-// the part's items.  direct: the part is the whole call and its words go straight to out_bits; else they are scattered on the host
-// into the call's layout (a set cut by a part boundary has some of its tiles here and some on the next device).
-int32_t match_rows_wide_on(bsg_ctx *ctx, Device &d, const uint8_t *rows, const uint64_t *row_off, uint32_t r0, uint32_t r1,
-                           const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds, uint32_t cond_len,
-                           const std::vector<uint32_t> &prog, const std::vector<uint32_t> &rx_blob, uint32_t n_rx, const bsg::TokSpec *tok,
-                           const WidePlan &wp, bool direct, uint64_t *out_bits, std::vector<uint32_t> &fb, float *ms)
-{
-    const uint32_t n_rows = r1 - r0;
-    const uint64_t byte0 = row_off[r0], n_bytes = row_off[r1] - byte0;
-    const LabTrace trace{"bsg_match_rows_wide", d.id};
-    std::vector<uint64_t> local_off((size_t)n_rows + 1);
-    for (uint32_t r = 0; r <= n_rows; ++r) local_off[r] = row_off[r0 + r] - byte0;
-    const bsh_wide::PartSets ps = bsh_wide::part_sets(wp.set_first_row, wp.set_query_off, wp.n_sets, r0, r1);
-    const uint32_t n_sets = ps.n(), pair0 = ps.pair_off[0], n_pairs = ps.pair_off[n_sets] - pair0;
-    std::vector<uint32_t> pair_off_local(ps.pair_off);
-    for (uint32_t &v : pair_off_local) v -= pair0;
-    std::vector<bsh_wide::EvalItem> items;
-    uint64_t part_words = 0;
-    if (!bsh_wide::eval_items(ps, items, part_words))
-        return fail(BSG_E_UNSUPPORTED, "more than %u (tile, pair range) items on one device", bsh_wide::kMaxItems);
-    d.calls.fetch_add(1, std::memory_order_relaxed);
-    std::lock_guard<std::mutex> lk(d.mu);
-    if (int32_t rc = use_device(d)) return rc;
-    if (int32_t rc = ensure_lower_table(d)) return rc;
-    trace.lap("part planned, lock taken");
-    Scratch scratch(d);
-    uint8_t *d_rows = nullptr, *d_cbytes = nullptr, *d_state = nullptr;
-    uint64_t *d_off = nullptr, *d_ch = nullptr, *d_cfp = nullptr, *d_sat = nullptr, *d_out = nullptr, *d_smask = nullptr;
-    uint32_t *d_prog = nullptr, *d_fb = nullptr, *d_nfb = nullptr, *d_coff = nullptr, *d_ckind = nullptr, *d_rx = nullptr;
-    uint32_t *d_poff = nullptr, *d_sfirst = nullptr, *d_spair = nullptr, *d_pairs = nullptr;
-    bsg::RowEvalItem *d_items = nullptr;
-    HIP_TRY(scratch.alloc(&d_rows, n_bytes + 64));
-    HIP_TRY(scratch.alloc(&d_off, ((size_t)n_rows + 1) * 8));
-    HIP_TRY(scratch.alloc(&d_ch, std::max<size_t>(n_conds, 1) * 2 * 32));
-    HIP_TRY(scratch.alloc(&d_cfp, std::max<size_t>(n_conds, 1) * 2 * 8));
-    HIP_TRY(scratch.alloc(&d_cbytes, (size_t)cond_len + 64));
-    HIP_TRY(scratch.alloc(&d_coff, ((size_t)2 * n_conds + 1) * 4));
-    HIP_TRY(scratch.alloc(&d_ckind, std::max<size_t>(n_conds, 1) * 4));
-    HIP_TRY(scratch.alloc(&d_prog, std::max<size_t>(prog.size(), 1) * 4));
-    HIP_TRY(scratch.alloc(&d_poff, wp.prog_off.size() * 4));
-    HIP_TRY(scratch.alloc(&d_sat, (size_t)n_rows * 8));
-    HIP_TRY(scratch.alloc(&d_state, (size_t)n_rows));
-    HIP_TRY(scratch.alloc(&d_out, std::max<uint64_t>(part_words, 1) * 8));
-    HIP_TRY(scratch.alloc(&d_fb, (size_t)n_rows * 4));
-    HIP_TRY(scratch.alloc(&d_nfb, 4));
-    HIP_TRY(scratch.alloc(&d_sfirst, ((size_t)n_sets + 1) * 4));
-    HIP_TRY(scratch.alloc(&d_spair, ((size_t)n_sets + 1) * 4));
-    HIP_TRY(scratch.alloc(&d_smask, (size_t)n_sets * 8));
-    HIP_TRY(scratch.alloc(&d_pairs, std::max<size_t>(n_pairs, 1) * 4));
-    HIP_TRY(scratch.alloc(&d_items, std::max<size_t>(items.size(), 1) * sizeof(bsg::RowEvalItem)));
-    if (n_rx) HIP_TRY(scratch.alloc(&d_rx, rx_blob.size() * 4));
-    trace.lap("device buffers allocated");
-    HIP_TRY(hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream));
-    HIP_TRY(hipMemcpyAsync(d_off, local_off.data(), ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream));
-    if (n_conds) {
-        if (cond_len) HIP_TRY(hipMemcpyAsync(d_cbytes, cond_bytes, cond_len, hipMemcpyHostToDevice, d.stream));
-        HIP_TRY(hipMemsetAsync(d_cbytes + cond_len, 0, 64, d.stream));
-        HIP_TRY(hipMemcpyAsync(d_coff, cond_off, ((size_t)2 * n_conds + 1) * 4, hipMemcpyHostToDevice, d.stream));
-        HIP_TRY(hipMemcpyAsync(d_ckind, cond_kinds, (size_t)n_conds * 4, hipMemcpyHostToDevice, d.stream));
-        hipLaunchKernelGGL(bsg::k_hash_fp_entries, dim3((2 * n_conds + 255) / 256), dim3(256), 0, d.stream, (const uint8_t *)d_cbytes,
-                           (const uint32_t *)d_coff, 2 * n_conds, d_ch, d_cfp, ctx->fp_key);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!prog.empty()) HIP_TRY(hipMemcpyAsync(d_prog, prog.data(), prog.size() * 4, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(d_poff, wp.prog_off.data(), wp.prog_off.size() * 4, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemsetAsync(d_nfb, 0, 4, d.stream));
-    if (n_rx) HIP_TRY(hipMemcpyAsync(d_rx, rx_blob.data(), rx_blob.size() * 4, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(d_sfirst, ps.first_row.data(), ((size_t)n_sets + 1) * 4, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(d_spair, pair_off_local.data(), ((size_t)n_sets + 1) * 4, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(d_smask, wp.set_cond_mask.data() + ps.s0, (size_t)n_sets * 8, hipMemcpyHostToDevice, d.stream));
-    if (n_pairs) HIP_TRY(hipMemcpyAsync(d_pairs, wp.set_queries + pair0, (size_t)n_pairs * 4, hipMemcpyHostToDevice, d.stream));
-    if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::RowEvalItem), hipMemcpyHostToDevice, d.stream));
-    RowUpload up(d, rows + byte0, d_rows, local_off.data(), n_rows, ctx->ingest_chunk_bytes);
-    const uint32_t n_chunks = up.n_chunks();
-    HIP_TRY(up.start(n_chunks > 1));
-    trace.lap("small uploads enqueued");
-    HIP_TRY(up.copy(0));
-    EventList kev;                                                       // per chunk: walk start, walk stop; then the evaluation's two
-    const bsg::RxArgs x{d_rx, (uint32_t)rx_blob.size(), n_rx};
-    const uint32_t lds = bsg::kMatchWideLdsBytes + (uint32_t)rx_blob.size() * 4;
-    for (uint32_t c = 0; c < n_chunks; ++c) {
-        const uint32_t rf = up.cuts[c], re = up.cuts[c + 1];
-        bsg::MatchArgs a{};
-        a.rows = d_rows; a.row_off = d_off + rf; a.cond_h = d_ch; a.cond_fp = d_cfp; a.cond_kind = d_ckind; a.lower = d.d_lower;
-        a.key = ctx->fp_key;
-        a.fallback_rows = d_fb; a.n_fallback = d_nfb;
-        a.n_rows = re - rf; a.row_base = rf; a.n_conds = n_conds;
-        const bsg::MatchWideArgs wd{d_sfirst, d_smask, d_spair, d_sat + rf, d_state + rf, n_sets};
-        HIP_TRY(kev.add(2));
-        HIP_TRY(up.wait_landed(c));
-        const hipEvent_t k0 = kev.v[(size_t)c * 2], k1 = kev.v[(size_t)c * 2 + 1];
-        const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads);
-        if (n_rx && tok) hipExtLaunchKernelGGL(bsg::k_match_rows_store_regex_tok, grid, dim3(bsg::kIngestThreads), lds, d.stream, k0, k1, 0, a, x, wd, *tok);
-        else if (n_rx) hipExtLaunchKernelGGL(bsg::k_match_rows_store_regex, grid, dim3(bsg::kIngestThreads), lds, d.stream, k0, k1, 0, a, x, wd);
-        else if (tok) hipExtLaunchKernelGGL(bsg::k_match_rows_store_tok, grid, dim3(bsg::kIngestThreads), lds, d.stream, k0, k1, 0, a, wd, *tok);
-        else hipExtLaunchKernelGGL(bsg::k_match_rows_store, grid, dim3(bsg::kIngestThreads), lds, d.stream, k0, k1, 0, a, wd);
-        HIP_TRY(hipGetLastError());
-        if (c + 1 < n_chunks) HIP_TRY(up.copy(c + 1));
-    }
-    trace.lap("all chunks enqueued");
-    HIP_TRY(kev.add(2));
-    if (!items.empty()) {
-        const bsg::RowEvalArgs e{d_items, d_pairs, d_poff, d_prog, d_sat, d_state, d_out, (uint32_t)items.size()};
-        const uint32_t per_block = bsg::kRowEvalThreads / 64;
-        hipExtLaunchKernelGGL(bsg::k_eval_row_programs, dim3(((uint32_t)items.size() + per_block - 1) / per_block), dim3(bsg::kRowEvalThreads), 0, d.stream,
-                              kev.v[(size_t)n_chunks * 2], kev.v[(size_t)n_chunks * 2 + 1], 0, e);
-        HIP_TRY(hipGetLastError());
-    }
-    uint32_t nfb = 0;
-    std::vector<uint64_t> staged;
-    if (part_words) {
-        uint64_t *dst = out_bits + wp.set_word0[ps.s0];
-        if (!direct) { staged.resize(part_words); dst = staged.data(); }
-        HIP_TRY(hipMemcpyAsync(dst, d_out, part_words * 8, hipMemcpyDeviceToHost, d.stream));
-    }
-    HIP_TRY(hipMemcpyAsync(&nfb, d_nfb, 4, hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    trace.lap("matched, words back");
-    *ms = 0.f;
-    for (uint32_t c = 0; c < n_chunks + (items.empty() ? 0u : 1u); ++c) {
-        float t = 0.f;
-        (void)hipEventElapsedTime(&t, kev.v[(size_t)c * 2], kev.v[(size_t)c * 2 + 1]);
-        *ms += t;
-    }
-    fb.resize(nfb);
-    if (nfb) HIP_TRY(hipMemcpy(fb.data(), d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
-    for (uint32_t &r : fb) r += r0;
-    scratch.done();
-    if (!direct) {                                                       // the part's layout -> the call's: per pair, the part's tiles of the set
-        uint64_t at = 0;
-        for (uint32_t ls = 0; ls < n_sets; ++ls) {
-            const uint32_t s = ps.s0 + ls, tiles = bsh_wide::tiles_of(ps.first_row[ls + 1] - ps.first_row[ls]);
-            const uint32_t set_tiles = bsh_wide::tiles_of(wp.set_first_row[s + 1] - wp.set_first_row[s]);
-            for (uint32_t p = ps.pair_off[ls]; p < ps.pair_off[ls + 1] && tiles; ++p, at += tiles)
-                memcpy(out_bits + wp.set_word0[s] + (uint64_t)(p - wp.set_query_off[s]) * set_tiles + ps.tile0[ls], staged.data() + at, (size_t)tiles * 8);
-        }
-    }
-    return BSG_OK;
-}
-
 int32_t wide_size_status(bsh_wide::SizeStatus st, uint32_t bad_set, const uint32_t *set_first_row, uint32_t n_sets, uint32_t n_rows)
 {
     switch (st) {
@@ -502,33 +524,16 @@ int32_t wide_size_status(bsh_wide::SizeStatus st, uint32_t bad_set, const uint32
     }
 }
 
-int32_t match_rows_wide_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
-                             const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
-                             const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
                              const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
-                             const bsg_tokenizer *tok_in, uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
-                             uint32_t *out_n_fallback)
+                             const bsg_tokenizer *tok_in)
 {
-    if (!ctx) return fail(BSG_E_INVALID, "ctx is null");
-    bsg_tokenizer rec{};
-    bsg::TokSpec spec{};
-    bool is_default = true;
-    if (int32_t rc = tok_spec(tok_in, rec, spec, is_default)) return rc;
-    const bsg::TokSpec *tok = is_default ? nullptr : &spec;
-    if (n_queries > bsh_wide::kMaxQueries)
-        return fail(BSG_E_UNSUPPORTED, "%u queries (one wide match call holds %u)", n_queries, bsh_wide::kMaxQueries);
-    if (n_queries && !prog_off) return fail(BSG_E_INVALID, "prog_off is null");
-    for (uint32_t q = 0; q < n_queries; ++q)
-        if (prog_off[q + 1] < prog_off[q]) return fail(BSG_E_INVALID, "prog_off not monotone at %u", q);
-    if (n_queries && prog_off[n_queries] > prog_off[0] && !prog_ops) return fail(BSG_E_INVALID, "prog_ops is null");
-    uint32_t cond_len = 0;
-    uint64_t n_bytes = 0;
-    if (int32_t rc = check_match_inputs(rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_n_fallback, cond_len, n_bytes))
-        return rc;
-    for (uint32_t c = 0; c < n_conds; ++c)
-        if (cond_kinds[c] > BSG_KIND_FIELD_REGEX) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, cond_kinds[c]);
+    if (int32_t rc = begin_match_call(mc, kWideFamily, tok_in, prog_ops, prog_off, n_queries)) return rc;
+    const uint32_t n_rows = mc.n_rows;
+    for (uint32_t c = 0; c < mc.n_conds; ++c)
+        if (mc.cond_kinds[c] > BSG_KIND_FIELD_REGEX) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
     // the sets: the caller's, or one implicit set of all rows with every query
-    WidePlan wp{set_first_row, set_query_off, set_queries, n_sets, n_queries, {0}, {}, {}};
+    WidePlan wp{set_first_row, set_query_off, set_queries, n_sets, n_queries, {}, {}};
     std::vector<uint32_t> implicit_first, implicit_off, implicit_queries;
     if (n_sets == 0) {
         if (set_first_row || set_query_off || set_queries) return fail(BSG_E_INVALID, "a set table without its number of sets");
@@ -551,51 +556,21 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *
                     return fail(BSG_E_INVALID, "set %u: its query list is not strictly ascending at pair %u", s, p);
             }
     }
-    std::vector<uint32_t> ident(n_conds), prog, one;
-    for (uint32_t c = 0; c < n_conds; ++c) ident[c] = c;
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        uint32_t depth = 1;
-        if (int32_t rc = lower_program(prog_ops + prog_off[q], prog_off[q + 1] - prog_off[q], n_conds, ident, one, depth)) return rc;
-        if (depth > 64) return fail(BSG_E_UNSUPPORTED, "query %u: expression too deep for the device matcher (depth %u)", q, depth);
-        prog.insert(prog.end(), one.begin(), one.end());
-        if (prog.size() > bsh_wide::kMaxOps)
-            return fail(BSG_E_UNSUPPORTED, "the call's programs hold more than %u lowered ops (at query %u)", bsh_wide::kMaxOps, q);
-        wp.prog_off.push_back((uint32_t)prog.size());
-    }
-    std::vector<uint32_t> rx_blob;
-    uint32_t n_rx = 0;
-    if (int32_t rc = build_rx_blob(cond_bytes, cond_off, cond_kinds, n_conds, rx_blob, n_rx, bsg::kRxWideLdsCap)) return rc;
+    if (int32_t rc = lower_programs(mc, kWideFamily, prog_ops, prog_off, n_queries)) return rc;
+    if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, bsg::kRxWideLdsCap)) return rc;
     const uint32_t n_pairs = wp.set_query_off[wp.n_sets];
     if (n_rows == 0 || n_pairs == 0) return BSG_OK;
-    wp.set_cond_mask = bsh_wide::set_cond_masks(bsh_wide::query_cond_masks(prog_ops, prog_off, n_queries, n_conds), wp.set_query_off, wp.set_queries, wp.n_sets);
+    wp.set_cond_mask = bsh_wide::set_cond_masks(bsh_wide::query_cond_masks(prog_ops, prog_off, n_queries, mc.n_conds), wp.set_query_off, wp.set_queries, wp.n_sets);
     wp.set_word0.assign((size_t)wp.n_sets + 1, 0);
     for (uint32_t s = 0; s < wp.n_sets; ++s)
         wp.set_word0[s + 1] = wp.set_word0[s] + (uint64_t)bsh_wide::tiles_of(wp.set_first_row[s + 1] - wp.set_first_row[s]) *
                                                     (wp.set_query_off[s + 1] - wp.set_query_off[s]);
-    *out_n_fallback = 0;
-    const uint32_t nd = (uint32_t)ctx->devs.size();
-    const uint32_t want = (nd > 1 && n_bytes >= ctx->shard_min_row_bytes) ? nd : 1;
-    const std::vector<uint32_t> cuts = bsh_wide::part_cuts(row_off, n_rows, wp.set_first_row, wp.n_sets, want);
-    const uint32_t n_parts = (uint32_t)cuts.size() - 1;
-    std::vector<std::vector<uint32_t>> fbs(n_parts);
-    std::vector<float> ms(n_parts, 0.f);
-    const uint32_t first = n_parts == 1 ? pick_device(ctx) : 0;
-    if (int32_t rc = run_parts(n_parts, [&](uint32_t i) -> int32_t {
-            return match_rows_wide_on(ctx, *ctx->devs[(first + i) % nd], rows, row_off, cuts[i], cuts[i + 1], cond_bytes, cond_off, cond_kinds, n_conds,
-                                      cond_len, prog, rx_blob, n_rx, tok, wp, n_parts == 1, out_bits, fbs[i], &ms[i]);
-        })) return rc;
-    std::vector<uint32_t> fb;
-    for (auto &v : fbs) fb.insert(fb.end(), v.begin(), v.end());
-    std::sort(fb.begin(), fb.end());
-    *out_n_fallback = (uint32_t)fb.size();
-    if (!fb.empty() && out_fallback_rows) memcpy(out_fallback_rows, fb.data(), (size_t)std::min<uint32_t>((uint32_t)fb.size(), fallback_cap) * 4);
-    {
-        std::lock_guard<std::shared_mutex> lk(ctx->mu);
-        ctx->last_match_ms = *std::max_element(ms.begin(), ms.end());
-    }
-    if (fb.size() > fallback_cap && out_fallback_rows)
-        return fail(BSG_E_INVALID, "%zu rows need the host matcher, caller's list holds %u", fb.size(), fallback_cap);
-    return BSG_OK;
+    *mc.out_n_fallback = 0;
+    return match_fan_out(ctx, mc, wp.set_first_row, wp.n_sets,
+                         [&](uint32_t n_parts, Device &d, uint32_t r0, uint32_t r1, std::vector<uint32_t> &fb, float *ms) -> int32_t {
+                             WidePart mode{mc, wp, n_parts == 1};
+                             return match_part(ctx, d, mc, r0, r1, mode, fb, ms);
+                         });
 }
 
 }  // namespace
@@ -610,8 +585,8 @@ int32_t bsg_match_rows_wide(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *r
                             uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
 {
     BSG_ENTER(ctx);
-    return match_rows_wide_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, prog_off, n_queries, set_first_row,
-                                set_query_off, set_queries, n_sets, tok, out_bits, out_fallback_rows, fallback_cap, out_n_fallback);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
 }
 
 int32_t bsg_match_wide_size(const uint32_t *set_first_row, const uint32_t *set_query_off, uint32_t n_sets, uint32_t n_rows, uint32_t n_queries,
@@ -629,8 +604,8 @@ int32_t bsg_match_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_of
                        uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
 {
     BSG_ENTER(ctx);
-    return match_rows_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, n_ops, out_bits, out_fallback_rows,
-                           fallback_cap, out_n_fallback, BSG_KIND_FIELD_TOKEN);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_TOKEN, nullptr);
 }
 
 int32_t bsg_match_rows_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -639,8 +614,8 @@ int32_t bsg_match_rows_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *
                              uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
 {
     BSG_ENTER(ctx);
-    return match_rows_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, n_ops, out_bits, out_fallback_rows,
-                           fallback_cap, out_n_fallback, BSG_KIND_FIELD_REGEX);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_REGEX, nullptr);
 }
 
 int32_t bsg_match_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -649,8 +624,8 @@ int32_t bsg_match_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *ro
                            uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
 {
     BSG_ENTER(ctx);
-    return match_rows_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, n_ops, out_bits, out_fallback_rows,
-                           fallback_cap, out_n_fallback, BSG_KIND_FIELD_REGEX, tok);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_REGEX, tok);
 }
 
 int32_t bsg_match_rows_many(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -660,8 +635,8 @@ int32_t bsg_match_rows_many(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *r
                             uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
 {
     BSG_ENTER(ctx);
-    return match_rows_many_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, prog_off, n_queries, set_first_row,
-                                query_mask_of_set, n_sets, tok, out_bits, out_fallback_rows, fallback_cap, out_n_fallback, BSG_KIND_FIELD_TOKEN);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_TOKEN);
 }
 
 int32_t bsg_match_rows_many_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -671,8 +646,8 @@ int32_t bsg_match_rows_many_regex(bsg_ctx *ctx, const uint8_t *rows, const uint6
                                   uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
 {
     BSG_ENTER(ctx);
-    return match_rows_many_call(ctx, rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, prog_ops, prog_off, n_queries, set_first_row,
-                                query_mask_of_set, n_sets, tok, out_bits, out_fallback_rows, fallback_cap, out_n_fallback, BSG_KIND_FIELD_REGEX);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_REGEX);
 }
 
 int32_t bsg_pinned_alloc(bsg_ctx *ctx, uint64_t n_bytes, void **out_ptr)

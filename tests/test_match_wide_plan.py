@@ -1,7 +1,8 @@
-"""The arithmetic of bsg_match_rows_wide on the host (no GPU): tests/wide_plan_check.cpp, built with plain g++ against
+"""The arithmetic of the row-matcher calls on the host (no GPU): tests/wide_plan_check.cpp, built with plain g++ against
 bloomsearch_amd/csrc/host/wide_plan.hpp, compared with restatements written here from the call's contract (include/bloomgpu.h):
 where a pair's words lie, which conditions a set's queries reference, where a call is cut between devices, a part's sets and the
-evaluation kernel's work items.  What the callers rely on is asserted by itself too: every (pair, tile) word of a part is written
+evaluation kernel's work items; and, for the single and batched calls that share the cuts and the set range, against restatements of
+the loops those calls had of their own.  What the callers rely on is asserted by itself too: every (pair, tile) word of a part is written
 by exactly one item, cuts lie at set-relative multiples of 64 rows, and the parts' words scatter to the call's layout without
 overlap."""
 import os
@@ -152,9 +153,7 @@ def want_parts(row_off, first, sqo, want):
     for i in range(1, want):
         target = row_off[0] + total * i // want
         r = int(np.searchsorted(np.asarray(row_off[:n_rows], dtype=np.uint64), target, side="left"))
-        if r >= n_rows:
-            continue
-        s = max(k for k in range(len(first)) if first[k] <= r)
+        s = max(k for k in range(len(first) - 1) if first[k] <= r)                     # a target inside the last row: the last set's last tile boundary
         r = first[s] + (r - first[s]) // 64 * 64
         if cuts[-1] < r < n_rows:
             cuts.append(r)
@@ -220,6 +219,86 @@ def test_parts_and_items(driver, tmp_path):
     assert ans.done() and cut_inside_a_set >= 3
 
 
+def old_plane_cuts(row_off, want):
+    """the cut loop match_rows_run had for the single and batched calls: byte targets, moved down to a multiple of 64 rows"""
+    n_rows = len(row_off) - 1
+    n_bytes = row_off[-1] - row_off[0]
+    cuts = [0]
+    for i in range(1, want):
+        target = row_off[0] + n_bytes * i // want
+        r = 0                                                                          # std::lower_bound(row_off, row_off + n_rows, target)
+        while r < n_rows and row_off[r] < target:
+            r += 1
+        r = r // 64 * 64
+        if cuts[-1] < r < n_rows:
+            cuts.append(r)
+    return cuts + [n_rows]
+
+
+def plane_cut_shapes():
+    rng = np.random.default_rng(21)
+    shapes = []
+    for n_rows in (1, 63, 64, 65, 129, 4097):
+        uniform = [3] + [3 + 100 * (r + 1) for r in range(n_rows)]
+        lens = rng.integers(1, 40, size=n_rows)
+        lens[rng.integers(0, n_rows, size=max(1, n_rows // 50))] = 50000                # a few rows hold most of the bytes
+        skewed = [0] + [int(x) for x in np.cumsum(lens)]
+        last = [0] + [int(x) for x in np.cumsum([10] * (n_rows - 1) + [10 ** 6])]      # every target falls into the last row
+        head = [0] + [int(x) for x in np.cumsum([10 ** 6] + [10] * (n_rows - 1))]      # ... into the first
+        for row_off in (uniform, skewed, last, head):
+            for want in (1, 2, 3, 8):
+                shapes.append((row_off, want))
+    # two targets in one 64-row block: rows 70 and 100 hold the thirds of the bytes, both move down to row 64
+    lens = [1] * 129
+    lens[70] = lens[100] = 10 ** 5
+    shapes.append(([0] + [int(x) for x in np.cumsum(lens)], 3))
+    return shapes
+
+
+def test_the_plane_calls_cuts_are_the_cuts_of_one_implicit_set(driver, tmp_path):
+    shapes = plane_cut_shapes()
+    ans = run_driver(driver, tmp_path, [[4, len(ro) - 1] + ro + [w] for ro, w in shapes])
+    seen = set()
+    for row_off, want in shapes:
+        cuts = ans.take(ans.take())
+        assert cuts == old_plane_cuts(row_off, want), (len(row_off) - 1, want)
+        assert all(c % 64 == 0 for c in cuts[:-1]) and cuts == sorted(set(cuts))
+        seen.add(len(cuts) - 1)
+    assert ans.done() and {1, 2, 3, 8} <= seen
+    assert old_plane_cuts(shapes[-1][0], 3) == [0, 64, 129]                            # the second target's cut is dropped, not repeated
+    last_129 = [0] + [int(x) for x in np.cumsum([10] * 128 + [10 ** 6])]
+    assert old_plane_cuts(last_129, 2) == [0, 128, 129]                                # a target inside the last row still cuts
+
+
+def old_set_clamp(first, r0, r1):
+    """the clamp loop match_rows_on had: the sets rows [r0, r1) lie in, their first rows clamped to the run and counted from r0"""
+    n_sets = len(first) - 1
+    s0 = 0                                                                             # std::upper_bound(sf + 1, sf + n_sets + 1, r0) - (sf + 1)
+    while s0 < n_sets and first[s0 + 1] <= r0:
+        s0 += 1
+    s1 = 0                                                                             # std::lower_bound(sf, sf + n_sets, r1) - sf
+    while s1 < n_sets and first[s1] < r1:
+        s1 += 1
+    return s0, [min(max(first[s0 + i], r0), r1) - r0 for i in range(s1 - s0 + 1)]
+
+
+def test_a_parts_set_range_is_the_batched_calls_clamp(driver, tmp_path):
+    sizes = [0, 0, 64, 1, 0, 0, 130, 63, 0, 65, 0]                                     # empty sets at both ends and in the middle
+    first = [0] + [int(x) for x in np.cumsum(sizes)]
+    n_rows = first[-1]
+    ranges = [(0, n_rows), (0, 64), (64, 65), (64, 128), (65, 195), (128, 192), (100, 101), (0, 1), (n_rows - 1, n_rows), (195, 258), (258, n_rows),
+              (192, n_rows), (63, 66), (1, 64)]                                         # inside a set, on set boundaries, across empty sets
+    ranges += [(r0, r1) for r0 in range(0, n_rows, 37) for r1 in range(r0 + 1, n_rows + 1, 41)]
+    shapes = [(first, r0, r1) for r0, r1 in ranges] + [([0, 5], 0, 5), ([0, 5], 2, 3), ([0, 0, 5, 5], 0, 5)]
+    ans = run_driver(driver, tmp_path, [[5, len(f) - 1] + f + [r0, r1] for f, r0, r1 in shapes])
+    for f, r0, r1 in shapes:
+        s0, n = ans.take(), ans.take()
+        first_row = ans.take(n + 1)
+        assert (s0, first_row) == old_set_clamp(f, r0, r1), (r0, r1)
+        assert first_row[0] == 0 and first_row[-1] == r1 - r0 and first_row == sorted(first_row)
+    assert ans.done()
+
+
 def test_the_driver_is_clean_under_the_sanitizers(tmp_path):
     """the same driver as a stand-alone program under AddressSanitizer and UBSan, over every kind of case"""
     exe = tmp_path / "wide_plan_check_san"
@@ -229,6 +308,7 @@ def test_the_driver_is_clean_under_the_sanitizers(tmp_path):
     first, off = [0, 0, 1, 64, 128, 193, 323], [0, 3, 3, 4, 74, 75, 145]
     row_off = list(range(0, 324 * 50, 50))
     cases = [[0], [1, 6, 323, 80, 1, 1, 1] + first + off, [1, 0, 65, 3, 0, 0, 1], [1, 6, 322, 80, 1, 1, 1] + first + off,
-             [2, 3, 2, 0, 2, 3, 0, 2, 1, 2, 0, 1, 2, 0, 1], [3, 323] + row_off + [6] + first + off + [3]]
+             [2, 3, 2, 0, 2, 3, 0, 2, 1, 2, 0, 1, 2, 0, 1], [3, 323] + row_off + [6] + first + off + [3],
+             [4, 323] + row_off + [3], [5, 6] + first + [64, 200]]
     ans = run_driver(exe, tmp_path, cases)
     assert ans.take(7)[5] == 46592

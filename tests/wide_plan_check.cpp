@@ -1,4 +1,4 @@
-// wide_plan_check.cpp — drives bloomsearch_amd/csrc/host/wide_plan.hpp (the arithmetic of bsg_match_rows_wide) on the CPU for
+// wide_plan_check.cpp — drives bloomsearch_amd/csrc/host/wide_plan.hpp (the arithmetic of the row-matcher calls) on the CPU for
 // tests/test_match_wide_plan.py.  Input: a file of little-endian u64 words, [n_cases] then each case beginning with its kind;
 // output: a file of u64 answers.  Plain C++: builds with g++ alone (and under -fsanitize=address,undefined as it stands).
 #include <cstdio>
@@ -101,6 +101,21 @@ int main(int argc, char **argv)
                     for (uint64_t v : {it.out0, (uint64_t)it.row0, (uint64_t)it.n_rows, (uint64_t)it.pair0, (uint64_t)it.pair1, (uint64_t)it.stride})
                         out.push_back(v);
             }
+        } else if (kind == 4) {          // the single and batched calls' cuts (one implicit set of all rows): n_rows, row_off, want
+            const uint32_t n_rows = (uint32_t)in.take();
+            const std::vector<uint64_t> row_off = in.take64((size_t)n_rows + 1);
+            const uint32_t want = (uint32_t)in.take(), all_rows[2] = {0, n_rows};
+            const std::vector<uint32_t> cuts = bsh_wide::part_cuts(row_off.data(), n_rows, all_rows, 1, want);
+            out.push_back(cuts.size());
+            out.insert(out.end(), cuts.begin(), cuts.end());
+        } else if (kind == 5) {          // a part's set range: n_sets, set_first_row, r0, r1
+            const uint32_t n_sets = (uint32_t)in.take();
+            const std::vector<uint32_t> first = in.take32((size_t)n_sets + 1);
+            const uint32_t r0 = (uint32_t)in.take(), r1 = (uint32_t)in.take();
+            const bsh_wide::SetRange sr = bsh_wide::part_set_range(first.data(), n_sets, r0, r1);
+            out.push_back(sr.s0);
+            out.push_back(sr.n());
+            out.insert(out.end(), sr.first_row.begin(), sr.first_row.end());
         } else {
             fprintf(stderr, "unknown case kind %llu\n", (unsigned long long)kind);
             return 2;

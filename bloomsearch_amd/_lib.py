@@ -85,7 +85,7 @@ EXPORTS = [
     "bsg_batch_create", "bsg_batch_free", "bsg_probe_batch", "bsg_probe_many", "bsg_probe", "bsg_query", "bsg_query_stats_read", "bsg_survivor_list", "bsg_probe_many_rows", "bsg_survivor_row_list", "bsg_survivor_rows_size", "bsg_survivor_rows_list", "bsg_survivor_rows_list_packed", "bsg_timing_read", "bsg_last_kernel_ms",
     "bsg_or_reduce", "bsg_or_words_dev", "bsg_or_reduce_dev", "bsg_last_or_ms",
     "bsg_comm_unique_id", "bsg_comm_init", "bsg_comm_destroy", "bsg_comm_info", "bsg_or_allreduce", "bsg_or_allreduce_dev",
-    "bsg_tokenizer_default", "bsg_ingest_rows", "bsg_ingest_rows_tok", "bsg_ingest_fallback_rows", "bsg_ingest_add_entries", "bsg_ingest_finish", "bsg_ingest_build",
+    "bsg_tokenizer_default", "bsg_ingest_rows", "bsg_ingest_rows_tok", "bsg_ingest_open", "bsg_ingest_add_sets", "bsg_ingest_append_rows", "bsg_ingest_fallback_rows", "bsg_ingest_add_entries", "bsg_ingest_finish", "bsg_ingest_build",
     "bsg_ingest_stats_read", "bsg_ingest_free", "bsg_ingest_build_sections",
     "bsg_sections_size", "bsg_build_sections", "bsg_last_encode_ms",
     "bsg_match_rows", "bsg_match_rows_regex", "bsg_match_rows_tok", "bsg_match_rows_many", "bsg_match_rows_many_regex", "bsg_match_rows_wide", "bsg_match_wide_size", "bsg_last_match_ms", "bsg_pinned_alloc", "bsg_pinned_free", "bsg_host_register", "bsg_host_unregister",
@@ -169,6 +169,9 @@ def load():
     L.bsg_or_allreduce_dev.argtypes = [vp, vp, u64]
     L.bsg_ingest_rows.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, vp, u32, C.POINTER(u64)]
     L.bsg_ingest_rows_tok.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, vp, u32, C.POINTER(Tokenizer), C.POINTER(u64)]
+    L.bsg_ingest_open.argtypes = [vp, u32, vp, u32, vp, u32, C.POINTER(Tokenizer), C.POINTER(u64)]
+    L.bsg_ingest_add_sets.argtypes = [vp, u64, u32, vp, vp, C.POINTER(u32)]
+    L.bsg_ingest_append_rows.argtypes = [vp, u64, vp, vp, u32, vp, vp, u32, C.POINTER(u32)]
     L.bsg_tokenizer_default.argtypes = [C.POINTER(Tokenizer)]
     L.bsg_ingest_fallback_rows.argtypes = [vp, u64, vp, u32, C.POINTER(u32)]
     L.bsg_ingest_add_entries.argtypes = [vp, u64, vp, vp, u32, vp, vp]

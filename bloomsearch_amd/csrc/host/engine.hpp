@@ -53,6 +53,11 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // build all run on the device at flush / merge time (bsg_ingest_*), the host walker only finishing the rows
     // the device walker hands back.  false: indexRow on the host at ingest time, as the reference does.
     bool device_ingest = false;
+    // true (with device_ingest; alone it is an invalid config): every validated ingest_rows batch is handed to an open streaming
+    // ingest when it arrives (bsg_ingest_open / bsg_ingest_add_sets / bsg_ingest_append_rows: one set per partition buffer, the
+    // file as their only parent) and the rows it hands back are finished by the host walker at once; flush only finishes, sizes
+    // and builds.  Merge keeps the one-shot path.  Off by default.
+    bool device_ingest_stream = false;
     // true: the final row test of the surviving blocks (matchRowBytes, query_exec.go:751) runs on the device too
     // (bsg_match_rows); rows it hands back, and expressions beyond its limits, go through the host matcher.
     bool device_match = false;
@@ -111,16 +116,21 @@ struct QueryResult {
 class BloomSearchEngine {
 public:
     BloomSearchEngine(const EngineConfig &cfg, bsg_ctx *ctx) : cfg_(cfg), ctx_(ctx) {}
-    ~BloomSearchEngine() { drop_arenas(); }
+    ~BloomSearchEngine() { drop_stream(); drop_arenas(); }
 
     static int32_t validate(const EngineConfig &c, std::string &err)
     {
         if (c.max_row_group_rows == 0 || c.max_row_group_bytes == 0) { err = "MaxRowGroupRows / MaxRowGroupBytes must be positive"; return kErrInvalidConfig; }
         if (!(c.bloom_false_positive_rate > 0.0 && c.bloom_false_positive_rate < 1.0)) { err = "BloomFalsePositiveRate must be in (0, 1)"; return kErrInvalidConfig; }
+        if (c.device_ingest_stream && !c.device_ingest) { err = "DeviceIngestStream needs DeviceIngest"; return kErrInvalidConfig; }
         return kEngineOk;
     }
 
     const std::string &last_error() const { return err_; }
+    // DeviceIngestStream at work (bse_describe "IngestStream"): batches and rows handed to a streaming ingest at ingest time, the
+    // rows among them the host walker finished at once, and the flushes built from a stream (not from the kept row bytes)
+    struct StreamStats { uint64_t batches = 0, rows = 0, host_rows = 0, flushes = 0; };
+    const StreamStats &stream_stats() const { return stream_stats_; }
     const std::vector<DataFile> &files() const { return files_; }
 
     void stop() { stopped_ = true; }
@@ -154,6 +164,11 @@ public:
             if (!validate_object_row(rows[i], cfg_.partition_field, pids[i], has_pid, scratch))
                 return fail(kErrInvalidRow, "row " + std::to_string(i) + " is not a JSON object");
             if (!has_pid) pids[i].clear();
+        }
+        // the batch goes to the device now.  A failure is the caller's to see, like the one-shot path's at flush: the batch is not
+        // buffered, the stream is dropped, and the rows buffered so far are built from their kept bytes (build_sections_device).
+        if (cfg_.device_ingest_stream && !stream_broken_) {
+            if (int32_t rc = stream_append(rows, pids)) { drop_stream(); stream_broken_ = true; return rc; }
         }
         bool should_flush = false;
         for (size_t i = 0; i < rows.size(); ++i) {
@@ -191,7 +206,10 @@ public:
             file.blocks.push_back(std::move(blk));
         }
         std::vector<std::vector<uint8_t>> sections;
-        if (cfg_.device_ingest) {
+        if (cfg_.device_ingest_stream && stream_ && !stream_broken_) {
+            if (int32_t rc = build_sections_stream(file, sections)) return rc;
+            stream_stats_.flushes += 1;
+        } else if (cfg_.device_ingest) {
             if (int32_t rc = build_sections_device(file, sections)) return rc;
         } else {
             for (auto &kv : buffers_) sets.push_back(&kv.second.entries);
@@ -209,6 +227,8 @@ public:
         files_.push_back(std::move(file));
         buffers_.clear();
         buffered_rows_ = buffered_bytes_ = 0;
+        drop_stream();               // the next batch opens the next one
+        stream_broken_ = false;
         drop_files_arena();          // one more file-level "block"; the other files' block arenas stay where they are
         return kEngineOk;
     }
@@ -450,6 +470,12 @@ private:
     EngineConfig cfg_;
     bsg_ctx *ctx_;
     std::map<std::string, PartitionBuffer> buffers_;
+    // DeviceIngestStream: the open streaming ingest of the rows in buffers_ (0 = none yet: opened by the first batch) and the set
+    // every partition buffer got in it, numbered by first arrival (the blocks of a file are ordered by partition id)
+    uint64_t stream_ = 0;
+    std::map<std::string, uint32_t> stream_set_;
+    bool stream_broken_ = false;         // an append failed (and ingest_rows said so): this flush builds from the kept rows
+    StreamStats stream_stats_;
     uint64_t buffered_rows_ = 0, buffered_bytes_ = 0;
     std::vector<DataFile> files_;
     uint64_t next_file_id_ = 1;
@@ -681,6 +707,113 @@ private:
         for (size_t s = 0; s + 1 < sec_off.size(); ++s) sections[s].assign(region.begin() + sec_off[s], region.begin() + sec_off[s + 1]);
     }
 
+    // the host walker's entry sets of the rows the device handed back -> bsg_ingest_add_entries (set index -> its entries)
+    int32_t add_host_entries(uint64_t ing, const std::map<uint32_t, BloomEntrySets> &per_set)
+    {
+        std::vector<uint8_t> eb;
+        std::vector<uint32_t> eo{0}, es, ek;
+        for (auto &kv : per_set)
+            for (uint32_t c = 0; c < 3; ++c) {
+                const size_t before = eo.size() - 1;
+                pack_entries(kv.second.set_of(c), eb, eo);
+                es.insert(es.end(), eo.size() - 1 - before, kv.first);
+                ek.insert(ek.end(), eo.size() - 1 - before, c);
+            }
+        if (bsg_ingest_add_entries(ctx_, ing, eb.data(), eo.data(), (uint32_t)es.size(), es.data(), ek.data()))
+            return fail(kErrGpu, bsg_last_error(ctx_));
+        return kEngineOk;
+    }
+
+    void drop_stream()
+    {
+        if (stream_) bsg_ingest_free(ctx_, stream_);
+        stream_ = 0;
+        stream_set_.clear();
+    }
+
+    // DeviceIngestStream, ingest time (ingest.go:444-450 with indexRow on the device): one validated batch -> the open stream.
+    // A partition id met for the first time gets the next set (bsg_ingest_add_sets, parent 0 = the file); the rows the device
+    // walker hands back are walked here and now, while the batch is at hand.
+    int32_t stream_append(const std::vector<std::string_view> &rows, const std::vector<std::string> &pids)
+    {
+        const bsg_tokenizer tok = c_tokenizer();
+        if (!stream_ && bsg_ingest_open(ctx_, 0, nullptr, 1, nullptr, BSG_INGEST_TRUSTED_JSON /* ingest_rows validated every row */, &tok, &stream_))
+            return fail(kErrGpu, bsg_last_error(ctx_));
+        std::vector<uint32_t> set_of_row(rows.size());
+        uint32_t n_new = 0;
+        for (size_t i = 0; i < rows.size(); ++i) {
+            auto it = stream_set_.find(pids[i]);
+            if (it == stream_set_.end()) { it = stream_set_.emplace(pids[i], (uint32_t)stream_set_.size()).first; ++n_new; }
+            set_of_row[i] = it->second;
+        }
+        if (n_new) {
+            const std::vector<uint32_t> parent(n_new, 0);
+            uint32_t first = 0;
+            if (bsg_ingest_add_sets(ctx_, stream_, n_new, parent.data(), nullptr, &first)) return fail(kErrGpu, bsg_last_error(ctx_));
+        }
+        std::vector<uint8_t> bytes;                 // this batch only: the rows of a batch are not contiguous in the caller's buffer
+        std::vector<uint64_t> row_off{0};
+        for (std::string_view r : rows) { bytes.insert(bytes.end(), r.begin(), r.end()); row_off.push_back(bytes.size()); }
+        std::vector<uint32_t> fb(rows.size());
+        uint32_t n_fb = 0;
+        if (bsg_ingest_append_rows(ctx_, stream_, bytes.data(), row_off.data(), (uint32_t)rows.size(), set_of_row.data(), fb.data(),
+                                   (uint32_t)fb.size(), &n_fb))
+            return fail(kErrGpu, bsg_last_error(ctx_));
+        if (n_fb) {
+            std::map<uint32_t, BloomEntrySets> per_set;
+            for (uint32_t i = 0; i < n_fb; ++i) per_set.try_emplace(set_of_row[fb[i]], cfg_.tokenizer).first->second.index_row(rows[fb[i]]);
+            if (int32_t rc = add_host_entries(stream_, per_set)) return rc;
+        }
+        stream_stats_.batches += 1;
+        stream_stats_.rows += rows.size();
+        stream_stats_.host_rows += n_fb;
+        return kEngineOk;
+    }
+
+    // DeviceIngestStream, flush time: what is left of build_sections_device once every batch has been walked — finish, size,
+    // bsg_ingest_build_sections.  The stream numbers its sets by first arrival, the file orders its blocks by partition id: the
+    // sections and counts are permuted into block order, and no resident arena is asked for (its block i would be set i); the
+    // file's arena is decoded from the stored sections by the first query, as without DeviceIngest.
+    int32_t build_sections_stream(DataFile &file, std::vector<std::vector<uint8_t>> &sections)
+    {
+        const size_t nb = file.blocks.size();
+        std::vector<uint32_t> set_of_block(nb);
+        for (size_t b = 0; b < nb; ++b) {
+            auto it = stream_set_.find(file.blocks[b].partition_id);
+            if (it == stream_set_.end() || stream_set_.size() != nb)    // every buffered row was appended: anything else is a bug here
+                return fail(kErrGpu, "the streaming ingest does not hold the partitions of this flush");
+            set_of_block[b] = it->second;
+        }
+        std::vector<uint64_t> counts((nb + 1) * 3);
+        std::vector<uint32_t> status(nb + 1);
+        if (bsg_ingest_finish(ctx_, stream_, counts.data(), status.data())) return fail(kErrGpu, bsg_last_error(ctx_));
+        for (uint32_t st : status)
+            if (st != 0) return build_sections_host_rows(file, sections);   // a set the device tables cannot represent (2^-62/entry)
+        std::vector<bsg_filter_desc> desc((nb + 1) * 3);
+        for (size_t i = 0; i < desc.size(); ++i) {
+            uint64_t m = 0, k = 0;
+            if (bsg_estimate_parameters(std::max<uint64_t>(counts[i], 1), cfg_.bloom_false_positive_rate, &m, &k))
+                return fail(kErrGpu, bsg_last_error(ctx_));
+            desc[i] = bsg_filter_desc{0, m, (uint32_t)k, 0};    // (word_off: the sections route lays the words out itself)
+        }
+        uint64_t total = 0;
+        if (bsg_sections_size(desc.data(), (uint32_t)nb + 1, &total)) return fail(kErrGpu, bsg_last_error(ctx_));
+        std::vector<uint8_t> region(total);
+        std::vector<uint64_t> sec_off(nb + 2);
+        if (bsg_ingest_build_sections(ctx_, stream_, desc.data(), region.data(), region.size(), sec_off.data(), nullptr, nullptr))
+            return fail(kErrGpu, bsg_last_error(ctx_));
+        std::vector<std::vector<uint8_t>> by_set;
+        split_sections(region, sec_off, by_set);
+        sections.resize(nb + 1);
+        for (size_t b = 0; b <= nb; ++b) {
+            const size_t s = b < nb ? set_of_block[b] : nb;
+            sections[b] = std::move(by_set[s]);
+            BloomEntryCounts &bc = b < nb ? file.blocks[b].counts : file.counts;
+            bc = BloomEntryCounts{counts[s * 3], counts[s * 3 + 1], counts[s * 3 + 2]};
+        }
+        return kEngineOk;
+    }
+
     // Device ingest of one file's blocks (flush.go:179-254 / merge.go:706-804 with a1-a5 on the GPU): rows ->
     // bsg_ingest_rows, the rows it hands back -> host walker -> bsg_ingest_add_entries, exact counts ->
     // EstimateParameters on the host -> bsg_ingest_build -> encodeFilterSection.  Fills the blocks' and the
@@ -715,17 +848,7 @@ private:
                 const uint32_t b = set_of_row[r];
                 per_set.try_emplace(b, cfg_.tokenizer).first->second.index_row(file.blocks[b].rows[r - first[b]]);
             }
-            std::vector<uint8_t> eb;
-            std::vector<uint32_t> eo{0}, es, ek;
-            for (auto &kv : per_set)
-                for (uint32_t c = 0; c < 3; ++c) {
-                    const size_t before = eo.size() - 1;
-                    pack_entries(kv.second.set_of(c), eb, eo);
-                    es.insert(es.end(), eo.size() - 1 - before, kv.first);
-                    ek.insert(ek.end(), eo.size() - 1 - before, c);
-                }
-            if (bsg_ingest_add_entries(ctx_, ing, eb.data(), eo.data(), (uint32_t)es.size(), es.data(), ek.data()))
-                return fail(kErrGpu, bsg_last_error(ctx_));
+            if (int32_t rc = add_host_entries(ing, per_set)) return rc;
         }
         std::vector<uint64_t> counts((nb + 1) * 3);
         std::vector<uint32_t> status(nb + 1);

@@ -371,6 +371,7 @@ int32_t bse_open(const char *config_json, uint64_t len, bsg_ctx *ctx, bse_engine
         if (const JNode *n = dom.get("BloomFalsePositiveRate")) { if (n->type == JType::Number) cfg.bloom_false_positive_rate = strtod(n->text.c_str(), nullptr); }
         if (const JNode *n = dom.get("PartitionField")) { if (n->type == JType::String) cfg.partition_field = n->text; }
         if (const JNode *n = dom.get("DeviceIngest")) cfg.device_ingest = n->type == JType::True;
+        if (const JNode *n = dom.get("DeviceIngestStream")) cfg.device_ingest_stream = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatch")) cfg.device_match = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceRegex")) cfg.device_regex = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchWide")) cfg.device_match_wide = n->type == JType::True;
@@ -534,7 +535,9 @@ int32_t bse_describe(bse_engine *e, char **out_json, uint64_t *out_len)
         }
         out += "]}";
     }
-    out += "]}";
+    const BloomSearchEngine::StreamStats &ss = e->eng->stream_stats();
+    out += "],\"IngestStream\":{\"Batches\":" + std::to_string(ss.batches) + ",\"Rows\":" + std::to_string(ss.rows) +
+           ",\"HostRows\":" + std::to_string(ss.host_rows) + ",\"Flushes\":" + std::to_string(ss.flushes) + "}}";
     return give(out, out_json, out_len);
 }
 

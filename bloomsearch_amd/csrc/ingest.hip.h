@@ -953,8 +953,28 @@ __device__ __forceinline__ uint32_t advance(Walker &w, ChunkCursor &cc, RX &rx, 
 // neighbouring runs, so a workgroup stays inside one block (or two) and its dedup cache stays warm: a workgroup that
 // sees each lane's row only once sends ~15 of a row's 32 emission rounds to the table (every entry is new to IT), one
 // that has walked a few rows per lane only the 2-3 rounds whose entries are new to the block (timestamps, ids).
-template <class TOK>
-__device__ __forceinline__ void ingest_rows_body(const IngestArgs &a, const TOK &tk)
+//
+// ROWS says which row a lane of a tile walks and which set it belongs to (a policy like TOK: each kernel is compiled for one).
+// RowsGrouped is bsg_ingest_rows' layout: position i of the launch IS row i, the rows of a set are contiguous and the set is
+// found by binary search over set_first_row.  RowsBySet is a batch of a streaming ingest (bsg_ingest_append_rows), whose rows
+// arrive in any order of sets: the host groups every upload chunk by set over INDICES only (host/row_groups.hpp, a stable
+// counting sort; no row byte moves) and uploads, per position, the row to walk and its set.  A wave still walks a contiguous run of
+// positions, so its 64 lanes and the workgroup's neighbouring runs stay inside one set (or two) exactly as above: the dedup
+// cache is indexed by the entry hash alone (cache_set; only the tag carries the table), and a tile that mixed many sets would
+// evict one set's hot entries with another's.  Both arrays are read once per tile, one coalesced 256-byte load each; what is
+// no longer coalesced is the tile's row_off reads (two 8-byte gathers per row, against the ~250 row bytes that follow).
+struct RowsGrouped {
+    static constexpr bool kBySet = false;
+};
+struct RowsBySet {
+    static constexpr bool kBySet = true;
+    const uint32_t *row_order;      // [n_rows]: positions [row_first, row_end) of a launch hold a permutation of the rows [row_first, row_end),
+                                    // stably grouped by set; the value is the row's index in the batch (what the fallback list receives)
+    const uint32_t *set_of_order;   // [n_rows]: set_of_row[row_order[i]], permuted on the host with it so that this load is coalesced too
+};
+
+template <class TOK, class ROWS>
+__device__ __forceinline__ void ingest_rows_body(const IngestArgs &a, const TOK &tk, const ROWS &rows)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     lds_u64i *cache = (lds_u64i *)lds_raw;
@@ -977,13 +997,20 @@ __device__ __forceinline__ void ingest_rows_body(const IngestArgs &a, const TOK 
 #endif
     BSG_PROF_DECL;
     for (uint64_t tile = run_begin; tile < run_end; tile += 64) {
-    const uint32_t r = (uint32_t)tile + lane;
+    uint32_t r = (uint32_t)tile + lane;
     const bool live = r < run_end;
-    // the set this row belongs to: last s with set_first_row[s] <= r
-    uint32_t lo = 0, hi = a.n_sets;
-    while (live && hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a.set_first_row[mid] <= r) lo = mid; else hi = mid;
+    uint32_t lo = 0;
+    if constexpr (ROWS::kBySet) {
+        // position r of the launch: the row to walk and its set, one coalesced load each
+        lo = live ? rows.set_of_order[r] : 0u;
+        r = live ? rows.row_order[r] : 0u;
+    } else {
+        // the set this row belongs to: last s with set_first_row[s] <= r
+        uint32_t hi = a.n_sets;
+        while (live && hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (a.set_first_row[mid] <= r) lo = mid; else hi = mid;
+        }
     }
     const uint32_t t0 = lo * 3;
     const uint64_t row_begin = live ? a.row_off[r] : 0, row_end = live ? a.row_off[r + 1] : 0;
@@ -1074,9 +1101,15 @@ __device__ __forceinline__ void ingest_rows_body(const IngestArgs &a, const TOK 
     BSG_PROF_FLUSH();
 }
 
-__global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows(const IngestArgs a) { ingest_rows_body(a, TokDefault{}); }
+__global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows(const IngestArgs a) { ingest_rows_body(a, TokDefault{}, RowsGrouped{}); }
 // the same walk under a separator-family tokenizer spec (bsg_ingest_rows_tok)
-__global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows_tok(const IngestArgs a, const TokSpec t) { ingest_rows_body(a, TokSpecP{t}); }
+__global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows_tok(const IngestArgs a, const TokSpec t) { ingest_rows_body(a, TokSpecP{t}, RowsGrouped{}); }
+// ... and over a batch whose rows belong to arbitrary sets in arrival order (bsg_ingest_append_rows): a.set_first_row is unused
+__global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows_sets(const IngestArgs a, const RowsBySet rows) { ingest_rows_body(a, TokDefault{}, rows); }
+__global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows_sets_tok(const IngestArgs a, const RowsBySet rows, const TokSpec t)
+{
+    ingest_rows_body(a, TokSpecP{t}, rows);
+}
 
 // ---------------- host-walked entries (fallback rows) ----------------
 __global__ __launch_bounds__(256) void k_ingest_add(const uint8_t *bytes, const uint32_t *off, const uint32_t *table_of_entry,

@@ -26,6 +26,7 @@ struct IngestPart {
     IngestTable *d_tables = nullptr;
     uint32_t *d_counts = nullptr, *d_status = nullptr;
     uint32_t *d_set_first = nullptr, *d_nfb = nullptr;
+    uint32_t table_cap = 0;                   // (streaming) descriptors / counters d_tables, d_counts, d_status have room for
     std::vector<uint32_t> fallback;           // part-local row indices
     std::vector<uint32_t> counts, status;     // last read back
     bool finished = false;
@@ -42,6 +43,10 @@ struct Ingest {
     std::vector<uint32_t> fallback;           // caller's row indices, ascending
     std::vector<uint32_t> counts, status;     // caller's numbering: sets, then parents
     bsg_tokenizer tok{};                      // the spec the rows were tokenized with (bsg_ingest_rows_tok; default otherwise)
+    bool streaming = false;                   // made by bsg_ingest_open: one part, rows arrive through bsg_ingest_append_rows
+    uint32_t flags = 0;                       // (streaming) BSG_INGEST_* of bsg_ingest_open, applied to every append
+    bsg::TokSpec spec{};                      // (streaming) the kernels' form of tok; tok_default: the default tokenizer's kernels serve
+    bool tok_default = true;
     bool finished = false;
     float ms_merge = 0.f, ms_build = 0.f, ms_encode = 0.f;
     uint32_t n_tables() const { return (n_sets + n_parents) * 3; }
@@ -240,6 +245,51 @@ int32_t get_ingest(bsg_ctx *ctx, uint64_t id, std::shared_ptr<Ingest> &out)
     return BSG_OK;
 }
 
+// The chunk loop of a row walk (bsg_ingest_rows' parts and bsg_ingest_append_rows): chunk c + 1 travels on the copy stream while
+// the compute stream walks chunk c, and a chunk is walked again after a table it overflowed has grown.  a: the launch arguments
+// but for the tables and the row range; tables [0, n_set_tables) are inserted into.  stage(c), right before chunk c's bytes are
+// enqueued, sends along what must have landed with them (on up.cs: the chunk's landed event covers it); launch(b, grid, e0, e1)
+// enqueues the walker over b on d.stream.  Caller holds the device lock; G.d_nfb has been zeroed on d.stream.
+template <class Stage, class Launch>
+int32_t walk_chunks(Device &d, IngestPart &G, RowUpload &up, const bsg::IngestArgs &a, uint32_t n_set_tables, const LabTrace &trace,
+                    Stage &&stage, Launch &&launch)
+{
+    const uint32_t n_chunks = up.n_chunks();
+    HIP_TRY(up.start(true));
+    HIP_TRY(stage(0));
+    HIP_TRY(up.copy(0));
+    trace.lap("first chunk enqueued");
+    for (uint32_t c = 0; c < n_chunks; ++c) {
+        bool first_attempt = true;
+        const uint32_t rf = up.cuts[c], re = up.cuts[c + 1];
+        uint32_t nfb_before = 0;
+        if (c) HIP_TRY(hipMemcpy(&nfb_before, G.d_nfb, 4, hipMemcpyDeviceToHost));   // K(c-1) has been synchronised
+        int32_t rc = run_until_fits(G, 0, n_set_tables, &G.stats.ms_walk, [&](hipEvent_t e0, hipEvent_t e1) -> int32_t {
+            if (!first_attempt) HIP_TRY(hipMemcpyAsync(G.d_nfb, &nfb_before, 4, hipMemcpyHostToDevice, d.stream));   // a re-run lists its rows again
+            else HIP_TRY(up.wait_landed(c));
+            bsg::IngestArgs b = a;
+            b.tables = G.d_tables;
+            b.row_first = rf; b.row_end = re;
+            // as many waves as the device holds at once (BSG_INGEST_WPE per SIMD), each with a contiguous run of rows
+            const uint64_t n = re - rf, max_waves = (uint64_t)d.n_cus * 4 * BSG_INGEST_WPE;
+            const uint64_t waves = std::min<uint64_t>((n + 63) / 64, max_waves);
+            b.rows_per_wave = (uint32_t)(((n + waves - 1) / waves + 63) / 64 * 64);
+            const uint64_t used = (n + b.rows_per_wave - 1) / b.rows_per_wave, wpw = bsg::kIngestThreads / 64;
+            launch(b, (uint32_t)((used + wpw - 1) / wpw), e0, e1);
+            if (first_attempt) {
+                first_attempt = false;
+                if (c + 1 < n_chunks) {                          // K(c) is running: now the next chunk's bytes
+                    HIP_TRY(stage(c + 1));
+                    HIP_TRY(up.copy(c + 1));
+                }
+            }
+            return BSG_OK;
+        });
+        if (rc) return rc;
+    }
+    return BSG_OK;
+}
+
 // One part: rows [0, n_rows) of `rows` (row_off relative to `rows`), n_sets sets, on device d.
 int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
                          const uint32_t *set_first_row, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents,
@@ -319,40 +369,13 @@ int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *
         HIP_TRY(hipMemsetAsync(G.d_nfb, 0, 128, d.stream));
         // The rows travel in chunks on the copy stream while the compute stream walks the chunk before (RowUpload)
         RowUpload up(d, rows, d_rows, row_off, n_rows, ctx->ingest_chunk_bytes);
-        const uint32_t n_chunks = up.n_chunks();
-        HIP_TRY(up.start(true));
-        HIP_TRY(up.copy(0));
-        trace.lap("first chunk enqueued");
-        for (uint32_t c = 0; c < n_chunks; ++c) {
-            bool first_attempt = true;
-            const uint32_t rf = up.cuts[c], re = up.cuts[c + 1];
-            uint32_t nfb_before = 0;
-            if (c) HIP_TRY(hipMemcpy(&nfb_before, g->d_nfb, 4, hipMemcpyDeviceToHost));   // K(c-1) has been synchronised
-            int32_t rc = run_until_fits(G, 0, n_sets * 3, &g->stats.ms_walk, [&](hipEvent_t e0, hipEvent_t e1) -> int32_t {
-                if (!first_attempt) HIP_TRY(hipMemcpyAsync(G.d_nfb, &nfb_before, 4, hipMemcpyHostToDevice, d.stream));   // a re-run lists its rows again
-                else HIP_TRY(up.wait_landed(c));
-                bsg::IngestArgs b = a;
-                b.tables = G.d_tables;
-                b.row_first = rf; b.row_end = re;
-                // as many waves as the device holds at once (BSG_INGEST_WPE per SIMD), each with a contiguous run of rows
-                const uint64_t n = re - rf, max_waves = (uint64_t)d.n_cus * 4 * BSG_INGEST_WPE;
-                const uint64_t waves = std::min<uint64_t>((n + 63) / 64, max_waves);
-                b.rows_per_wave = (uint32_t)(((n + waves - 1) / waves + 63) / 64 * 64);
-                const uint64_t used = (n + b.rows_per_wave - 1) / b.rows_per_wave, wpw = bsg::kIngestThreads / 64;
-                if (tok)
-                    hipExtLaunchKernelGGL(bsg::k_ingest_rows_tok, dim3((uint32_t)((used + wpw - 1) / wpw)),
-                                          dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, *tok);
-                else
-                    hipExtLaunchKernelGGL(bsg::k_ingest_rows, dim3((uint32_t)((used + wpw - 1) / wpw)),
-                                          dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b);
-                if (first_attempt) {
-                    first_attempt = false;
-                    if (c + 1 < n_chunks) HIP_TRY(up.copy(c + 1));   // K(c) is running: now the next chunk's bytes
-                }
-                return BSG_OK;
-            });
-            if (rc) return rc;
-        }
+        if (int32_t rc = walk_chunks(d, G, up, a, n_sets * 3, trace, [](uint32_t) { return hipSuccess; },
+                [&](const bsg::IngestArgs &b, uint32_t grid, hipEvent_t e0, hipEvent_t e1) {
+                    if (tok)
+                        hipExtLaunchKernelGGL(bsg::k_ingest_rows_tok, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, *tok);
+                    else
+                        hipExtLaunchKernelGGL(bsg::k_ingest_rows, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b);
+                })) return rc;
         HIP_TRY(hipStreamSynchronize(d.copy_stream));
         trace.lap("all chunks walked");
         uint32_t nfb = 0;
@@ -724,6 +747,199 @@ int32_t ingest_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_
     return BSG_OK;
 }
 
+
+// ---- streaming ingest: bsg_ingest_open, bsg_ingest_add_sets, bsg_ingest_append_rows ----
+// One part on one device.  Its tables are laid out like every part's — the sets' three tables each, then the parents' — so
+// finish, build and free see nothing new.  The parents are placeholders until finish_part gives them storage and nothing is
+// inserted into them before: their counters and flags are zero, so adding sets only moves their DESCRIPTORS behind the new
+// sets' (the caller's numbering "sets, then parents" holds at every moment; a parent's table index is (n_sets + p) * 3 + kind
+// with the n_sets of the time).
+
+constexpr uint32_t kStreamFieldSlots = 256, kStreamTokenSlots = 1024;   // no row count is known when a set is made
+
+// n_more empty sets behind the existing ones.  Caller holds the device lock and has made the device current.
+int32_t stream_add_sets(IngestPart &G, uint32_t n_more, const uint32_t *parent_of_new_set, const uint32_t *slots_hint)
+{
+    Device &d = *G.dev;
+    const uint32_t old_sets = G.n_sets, new_sets = old_sets + n_more, nt = (new_sets + G.n_parents) * 3;
+    std::vector<IngestTable> tables(nt, IngestTable{nullptr, nullptr, 0, 0});
+    std::copy(G.tables.begin(), G.tables.begin() + (size_t)old_sets * 3, tables.begin());
+    std::copy(G.tables.begin() + (size_t)old_sets * 3, G.tables.end(), tables.begin() + (size_t)new_sets * 3);   // the parents' placeholders
+    if (n_more) {
+        uint64_t total_slots = 0;
+        std::vector<uint64_t> first_slot((size_t)n_more * 3), cap((size_t)n_more * 3);
+        for (size_t i = 0; i < cap.size(); ++i) {
+            uint64_t want = i % 3 == 0 ? kStreamFieldSlots : kStreamTokenSlots;
+            if (slots_hint && slots_hint[i]) want = slots_hint[i];
+            cap[i] = pow2_at_least(want);
+            first_slot[i] = total_slots;
+            total_slots += cap[i];
+        }
+        void *chunk = nullptr;
+        HIP_TRY(G.mem.alloc(&chunk, total_slots * kSlotBytes));
+        G.slot_bytes += total_slots * kSlotBytes;
+        HIP_TRY(hipMemsetAsync(chunk, 0, total_slots * kSlotBytes, d.stream));
+        for (size_t i = 0; i < cap.size(); ++i) tables[(size_t)old_sets * 3 + i] = make_table(chunk, first_slot[i], total_slots, cap[i]);
+    }
+    if (nt > G.table_cap || !G.d_tables) {
+        // room for twice as many: partitions keep showing up.  The sets' counters travel; everything behind them is zero.
+        const uint32_t room = std::max<uint32_t>(96, nt > 0x7FFFFFFFu ? nt : nt * 2);
+        IngestTable *nd_tables = nullptr;
+        uint32_t *nd_counts = nullptr, *nd_status = nullptr;
+        HIP_TRY(G.mem.alloc(&nd_tables, (size_t)room * sizeof(IngestTable)));
+        HIP_TRY(G.mem.alloc(&nd_counts, (size_t)room * 4));
+        HIP_TRY(G.mem.alloc(&nd_status, (size_t)room * 4));
+        HIP_TRY(hipMemsetAsync(nd_counts, 0, (size_t)room * 4, d.stream));
+        HIP_TRY(hipMemsetAsync(nd_status, 0, (size_t)room * 4, d.stream));
+        if (old_sets) {
+            HIP_TRY(hipMemcpyAsync(nd_counts, G.d_counts, (size_t)old_sets * 3 * 4, hipMemcpyDeviceToDevice, d.stream));
+            HIP_TRY(hipMemcpyAsync(nd_status, G.d_status, (size_t)old_sets * 3 * 4, hipMemcpyDeviceToDevice, d.stream));
+        }
+        G.d_tables = nd_tables; G.d_counts = nd_counts; G.d_status = nd_status;   // (the blocks before stay with G.mem until the ingest is freed)
+        G.table_cap = room;
+    }
+    G.tables.swap(tables);
+    G.n_sets = new_sets;
+    for (uint32_t i = 0; i < n_more; ++i) G.parent_of_set.push_back(parent_of_new_set ? parent_of_new_set[i] : 0xFFFFFFFFu);
+    if (nt) if (int32_t rc = push_tables(G)) return rc;
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    return BSG_OK;
+}
+
+int32_t check_parents(const uint32_t *parent_of_set, uint32_t n_sets, uint32_t n_parents)
+{
+    if (n_sets && n_parents && !parent_of_set) return fail(BSG_E_INVALID, "parent_of_set is null");
+    for (uint32_t s = 0; s < n_sets && parent_of_set; ++s)
+        if (parent_of_set[s] != 0xFFFFFFFFu && parent_of_set[s] >= n_parents) return fail(BSG_E_INVALID, "parent_of_set[%u] out of range", s);
+    return BSG_OK;
+}
+
+int32_t ingest_open_call(bsg_ctx *ctx, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents, const uint32_t *slots_hint,
+                         uint32_t flags, const bsg_tokenizer *tok_in, uint64_t *out_ingest_id)
+{
+    auto I = std::make_shared<Ingest>();
+    if (int32_t rc = tok_spec(tok_in, I->tok, I->spec, I->tok_default)) return rc;
+    if (!out_ingest_id) return fail(BSG_E_INVALID, "null argument");
+    if (flags & ~BSG_INGEST_TRUSTED_JSON) return fail(BSG_E_INVALID, "unknown flags 0x%x", flags);
+    if ((uint64_t)n_sets + n_parents > 0xFFFFFFFFu / 3) return fail(BSG_E_INVALID, "too many sets and parents");
+    if (int32_t rc = check_parents(parent_of_set, n_sets, n_parents)) return rc;
+    I->streaming = true;
+    I->flags = flags;
+    I->n_parents = n_parents;
+    Device &d = *ctx->devs[pick_device(ctx)];
+    auto P = std::make_shared<IngestPart>(d);
+    I->parts.push_back(P);
+    IngestPart &G = *P;
+    G.n_parents = n_parents;
+    int32_t rc = BSG_OK;
+    {
+        std::lock_guard<std::mutex> lk(d.mu);
+        rc = [&]() -> int32_t {
+            if (int32_t rc2 = use_device(d)) return rc2;
+            // a parent table is a 64-slot placeholder nothing inserts into until the finish step sizes it from its children
+            if (n_parents) {
+                void *ph = nullptr;
+                HIP_TRY(G.mem.alloc(&ph, 64 * kSlotBytes));
+                HIP_TRY(hipMemsetAsync(ph, 0, 64 * kSlotBytes, d.stream));
+                G.tables.assign((size_t)n_parents * 3, make_table(ph, 0, 64, 64));
+            }
+            HIP_TRY(G.mem.alloc(&G.d_nfb, 128));
+            if (int32_t rc2 = stream_add_sets(G, n_sets, parent_of_set, slots_hint)) return rc2;
+            G.mem.done();                  // stream_add_sets returns synchronised
+            return BSG_OK;
+        }();
+    }
+    if (rc) { free_ingest(*I); return rc; }
+    I->n_sets = n_sets;
+    I->parent_of_set = G.parent_of_set;
+    I->set_cut = {0, n_sets};
+    std::lock_guard<std::shared_mutex> lk2(ctx->mu);
+    const uint64_t id = ctx->next_id++;
+    ctx->ingests[id] = I;
+    *out_ingest_id = id;
+    return BSG_OK;
+}
+
+// a streaming ingest that still takes sets and rows
+int32_t get_open_stream(bsg_ctx *ctx, uint64_t id, std::shared_ptr<Ingest> &g, const char *call)
+{
+    if (int32_t rc = get_ingest(ctx, id, g)) return rc;
+    if (!g->streaming) return fail(BSG_E_INVALID, "%s: ingest %llu was made by bsg_ingest_rows, not by bsg_ingest_open", call, (unsigned long long)id);
+    if (g->finished) return fail(BSG_E_INVALID, "%s: ingest already finished", call);
+    return BSG_OK;
+}
+
+// One batch of a streaming ingest: rows in any order of sets, walked chunk by chunk in the order row_groups.hpp gives them.
+int32_t append_rows_stream(bsg_ctx *ctx, Ingest &I, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows, const uint32_t *set_of_row,
+                           uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *n_fallback)
+{
+    IngestPart &G = *I.parts[0];
+    Device &d = *G.dev;
+    const uint64_t n_bytes = row_off[n_rows];
+    const LabTrace trace{"bsg_ingest_append_rows", d.id};
+    d.calls.fetch_add(1, std::memory_order_relaxed);
+    std::lock_guard<std::mutex> lk(d.mu);
+    if (int32_t rc = use_device(d)) return rc;
+    Scratch scratch(d);                    // the row bytes, their offsets, the walking order and the fallback list: this call's only
+    uint8_t *d_rows = nullptr;
+    uint64_t *d_row_off = nullptr;
+    uint32_t *d_fb = nullptr, *d_order = nullptr, *d_set_of_order = nullptr;
+    HIP_TRY(scratch.alloc(&d_rows, n_bytes + 64));
+    HIP_TRY(scratch.alloc(&d_row_off, ((size_t)n_rows + 1) * 8));
+    HIP_TRY(scratch.alloc(&d_fb, (size_t)n_rows * 4));
+    HIP_TRY(scratch.alloc(&d_order, (size_t)n_rows * 4));
+    HIP_TRY(scratch.alloc(&d_set_of_order, (size_t)n_rows * 4));
+    trace.lap("device buffers allocated");
+    HIP_TRY(hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream));
+    HIP_TRY(hipMemcpyAsync(d_row_off, row_off, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipMemsetAsync(G.d_nfb, 0, 128, d.stream));
+    bsg::IngestArgs a{};
+    a.rows = d_rows; a.row_off = d_row_off;
+    a.counts = G.d_counts; a.status = G.d_status; a.fallback_rows = d_fb; a.n_fallback = G.d_nfb;
+    a.n_rows = n_rows; a.n_sets = G.n_sets; a.validate = (I.flags & BSG_INGEST_TRUSTED_JSON) ? 0u : 1u;
+    a.key = ctx->fp_key;
+    if (int32_t rc = ensure_lower_table(d)) return rc;
+    a.lower = d.d_lower;
+    const bsg::RowsBySet by_set{d_order, d_set_of_order};
+    std::vector<uint32_t> order(n_rows), set_of_order(n_rows), group_scratch;
+    RowUpload up(d, rows, d_rows, row_off, n_rows, ctx->ingest_chunk_bytes);
+    if (int32_t rc = walk_chunks(d, G, up, a, G.n_sets * 3, trace,
+            [&](uint32_t c) -> hipError_t {   // the chunk's walking order lands with its bytes
+                const uint32_t rf = up.cuts[c], re = up.cuts[c + 1];
+                bsh::group_rows_by_set(set_of_row, rf, re, G.n_sets, order.data(), set_of_order.data(), group_scratch);
+                hipError_t e = hipMemcpyAsync(d_order + rf, order.data() + rf, (size_t)(re - rf) * 4, hipMemcpyHostToDevice, up.cs);
+                if (e == hipSuccess) e = hipMemcpyAsync(d_set_of_order + rf, set_of_order.data() + rf, (size_t)(re - rf) * 4, hipMemcpyHostToDevice, up.cs);
+                return e;
+            },
+            [&](const bsg::IngestArgs &b, uint32_t grid, hipEvent_t e0, hipEvent_t e1) {
+                if (!I.tok_default)
+                    hipExtLaunchKernelGGL(bsg::k_ingest_rows_sets_tok, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, by_set, I.spec);
+                else
+                    hipExtLaunchKernelGGL(bsg::k_ingest_rows_sets, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, by_set);
+            })) return rc;
+    HIP_TRY(hipStreamSynchronize(d.copy_stream));
+    trace.lap("all chunks walked");
+    uint32_t nfb = 0;
+    HIP_TRY(hipMemcpy(&nfb, G.d_nfb, 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> fb(nfb);
+    if (nfb) HIP_TRY(hipMemcpy(fb.data(), d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
+    scratch.done();                        // both streams have been synchronised: the row bytes leave the device here
+    std::sort(fb.begin(), fb.end());
+    *n_fallback = nfb;
+    // a call that could not deliver its list is appended again (or walked on the host): its rows are counted by the call that does
+    const bool count_only = !out_fallback_rows && fallback_cap == 0;
+    if (!count_only && nfb > fallback_cap)
+        return fail(BSG_E_INVALID, "bsg_ingest_append_rows: %u rows are handed back, out_fallback_rows has room for %u", nfb, fallback_cap);
+    if (count_only && nfb) return BSG_OK;
+    G.n_rows += n_rows;
+    I.n_rows += n_rows;
+    G.stats.n_rows += n_rows;
+    G.stats.row_bytes += n_bytes;
+    G.stats.n_fallback_rows += nfb;
+    if (nfb) memcpy(out_fallback_rows, fb.data(), (size_t)nfb * 4);
+    return BSG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -751,12 +967,62 @@ int32_t bsg_ingest_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *r
     return ingest_rows_call(ctx, rows, row_off, n_rows, set_first_row, n_sets, parent_of_set, n_parents, slots_hint, flags, tok, out_ingest_id);
 }
 
+int32_t bsg_ingest_open(bsg_ctx *ctx, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents, const uint32_t *slots_hint,
+                        uint32_t flags, const bsg_tokenizer *tok, uint64_t *out_ingest_id)
+{
+    BSG_ENTER(ctx);
+    return ingest_open_call(ctx, n_sets, parent_of_set, n_parents, slots_hint, flags, tok, out_ingest_id);
+}
+
+int32_t bsg_ingest_add_sets(bsg_ctx *ctx, uint64_t ingest_id, uint32_t n_more, const uint32_t *parent_of_new_set,
+                            const uint32_t *slots_hint_new, uint32_t *out_first_new_set)
+{
+    BSG_ENTER(ctx);
+    if (!out_first_new_set) return fail(BSG_E_INVALID, "null argument");
+    std::shared_ptr<Ingest> g;
+    if (int32_t rc = get_open_stream(ctx, ingest_id, g, "bsg_ingest_add_sets")) return rc;
+    Ingest &I = *g;
+    if ((uint64_t)I.n_sets + n_more + I.n_parents > 0xFFFFFFFFu / 3) return fail(BSG_E_INVALID, "too many sets and parents");
+    if (int32_t rc = check_parents(parent_of_new_set, n_more, I.n_parents)) return rc;
+    *out_first_new_set = I.n_sets;
+    if (n_more == 0) return BSG_OK;
+    IngestPart &G = *I.parts[0];
+    {
+        std::lock_guard<std::mutex> lk(G.dev->mu);
+        if (int32_t rc = use_device(*G.dev)) return rc;
+        if (int32_t rc = stream_add_sets(G, n_more, parent_of_new_set, slots_hint_new)) return rc;
+    }
+    I.n_sets = G.n_sets;
+    I.parent_of_set = G.parent_of_set;
+    I.set_cut = {0, I.n_sets};
+    return BSG_OK;
+}
+
+int32_t bsg_ingest_append_rows(bsg_ctx *ctx, uint64_t ingest_id, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                               const uint32_t *set_of_row, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    if (!out_n_fallback) return fail(BSG_E_INVALID, "null argument");
+    std::shared_ptr<Ingest> g;
+    if (int32_t rc = get_open_stream(ctx, ingest_id, g, "bsg_ingest_append_rows")) return rc;
+    *out_n_fallback = 0;
+    if (n_rows == 0) return BSG_OK;
+    if (!row_off || !set_of_row || (!out_fallback_rows && fallback_cap)) return fail(BSG_E_INVALID, "null argument");
+    for (uint32_t r = 0; r < n_rows; ++r)
+        if (row_off[r + 1] < row_off[r]) return fail(BSG_E_INVALID, "row_off not monotone at %u", r);
+    if (row_off[n_rows] && !rows) return fail(BSG_E_INVALID, "rows is null");
+    if (const uint32_t bad = bsh::first_bad_set(set_of_row, n_rows, g->n_sets); bad < n_rows)
+        return fail(BSG_E_INVALID, "set_of_row[%u] = %u, the ingest has %u sets", bad, set_of_row[bad], g->n_sets);
+    return append_rows_stream(ctx, *g, rows, row_off, n_rows, set_of_row, out_fallback_rows, fallback_cap, out_n_fallback);
+}
+
 int32_t bsg_ingest_fallback_rows(bsg_ctx *ctx, uint64_t ingest_id, uint32_t *rows_out, uint32_t cap, uint32_t *n_out)
 {
     BSG_ENTER(ctx);
     if (!ctx || !n_out) return fail(BSG_E_INVALID, "null argument");
     std::shared_ptr<Ingest> g;
     if (int32_t rc = get_ingest(ctx, ingest_id, g)) return rc;
+    if (g->streaming) return fail(BSG_E_INVALID, "a streaming ingest hands its rows back batch by batch: bsg_ingest_append_rows returns them");
     *n_out = (uint32_t)g->fallback.size();
     if (rows_out) memcpy(rows_out, g->fallback.data(), (size_t)std::min<uint32_t>(cap, *n_out) * 4);
     return BSG_OK;
@@ -1105,7 +1371,7 @@ int32_t bsg_ingest_stats_read(bsg_ctx *ctx, uint64_t ingest_id, bsg_ingest_stats
         bytes += p->slot_bytes;
     }
     if (g->merged) bytes += g->merged->slot_bytes;
-    st.n_fallback_rows = (uint32_t)g->fallback.size();
+    st.n_fallback_rows = g->streaming ? g->parts[0]->stats.n_fallback_rows : (uint32_t)g->fallback.size();   // (a stream: summed over the appends)
     st.ms_union += g->ms_merge;
     st.ms_build = g->ms_build;
     st.ms_encode = g->ms_encode;

@@ -495,6 +495,44 @@ class Context:
                                            _lib._ptr(pos), n_parents, _lib._ptr(hint), flags, C.byref(out)))
         return int(out.value)
 
+    # streaming ingest: open without rows, append batches whose rows belong to arbitrary sets, then finish / build as above
+    def ingest_open(self, n_sets: int, parent_of_set=None, n_parents: int = 0, slots_hint=None, flags: int = 0, tokenizer=None) -> int:
+        pos = None if parent_of_set is None else np.ascontiguousarray(parent_of_set, dtype=np.uint32)
+        hint = None if slots_hint is None else np.ascontiguousarray(slots_hint, dtype=np.uint32)
+        out = C.c_uint64()
+        self._check(self.L.bsg_ingest_open(self.h, n_sets, _lib._ptr(pos), n_parents, _lib._ptr(hint), flags,
+                                           None if tokenizer is None else c_spec(tokenizer), C.byref(out)))
+        return int(out.value)
+
+    def ingest_add_sets(self, ingest_id: int, parent_of_new_set, slots_hint=None) -> int:
+        """len(parent_of_new_set) more sets; returns the index of the first."""
+        pos = np.ascontiguousarray(parent_of_new_set, dtype=np.uint32)
+        hint = None if slots_hint is None else np.ascontiguousarray(slots_hint, dtype=np.uint32)
+        first = C.c_uint32()
+        self._check(self.L.bsg_ingest_add_sets(self.h, ingest_id, len(pos), _lib._ptr(pos), _lib._ptr(hint), C.byref(first)))
+        return int(first.value)
+
+    def ingest_append_rows(self, ingest_id: int, rows, set_of_row) -> np.ndarray:
+        """rows: list[bytes] (or (u8 blob, u64 offsets[n+1])), row r to set set_of_row[r]; returns the batch-local indices
+        (ascending) of the rows the host walker must finish."""
+        if isinstance(rows, tuple):
+            blob, off = rows
+            blob = np.ascontiguousarray(blob, dtype=np.uint8)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+        else:
+            off = np.zeros(len(rows) + 1, dtype=np.uint64)
+            if rows:
+                off[1:] = np.cumsum([len(r) for r in rows], dtype=np.uint64)
+            blob = np.frombuffer(b"".join(rows), dtype=np.uint8)
+        sor = np.ascontiguousarray(set_of_row, dtype=np.uint32)
+        n_rows = len(off) - 1
+        assert len(sor) == n_rows
+        fb = np.zeros(n_rows, dtype=np.uint32)
+        n = C.c_uint32()
+        self._check(self.L.bsg_ingest_append_rows(self.h, ingest_id, _lib._ptr(blob), _lib._ptr(off), n_rows, _lib._ptr(sor),
+                                                  _lib._ptr(fb), n_rows, C.byref(n)))
+        return fb[: n.value].copy()
+
     def ingest_fallback_rows(self, ingest_id: int) -> np.ndarray:
         n = C.c_uint32()
         self._check(self.L.bsg_ingest_fallback_rows(self.h, ingest_id, None, 0, C.byref(n)))

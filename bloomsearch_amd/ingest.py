@@ -88,3 +88,59 @@ def device_ingest(ctx: Context, row_sets, fpr: float, parent_of_set=None, n_pare
     finally:
         if not keep:
             ctx.ingest_free(ing)
+
+
+class IngestStream:
+    """A streaming device ingest (bsg_ingest_open / bsg_ingest_add_sets / bsg_ingest_append_rows): batches of rows that belong
+    to arbitrary sets are handed to the device as they arrive; finish / build see what bsg_ingest_rows would have left.  Lives
+    on one device of the context.  Use as a context manager or call close()."""
+
+    def __init__(self, ctx: Context, ingest_id: int, n_sets: int, n_parents: int, tokenizer=None):
+        self.ctx, self.id, self.n_sets, self.n_parents, self.tokenizer = ctx, ingest_id, n_sets, n_parents, tokenizer
+
+    @classmethod
+    def open(cls, ctx: Context, n_sets: int = 0, parent_of_set=None, n_parents: int = 0, slots_hint=None, flags: int = 0,
+             tokenizer=None) -> "IngestStream":
+        return cls(ctx, ctx.ingest_open(n_sets, parent_of_set, n_parents, slots_hint, flags, tokenizer), n_sets, n_parents, tokenizer)
+
+    def add_sets(self, parent_of_new_set, slots_hint=None) -> int:
+        first = self.ctx.ingest_add_sets(self.id, parent_of_new_set, slots_hint)
+        self.n_sets += len(parent_of_new_set)
+        return first
+
+    def append(self, rows, set_of_row, finish_fallback: bool = True) -> np.ndarray:
+        """rows: list of row bytes (or, with finish_fallback=False, a (u8 blob, u64 offsets) pair), row r to set set_of_row[r].
+        Returns the batch-local indices of the rows the device handed
+        back; with finish_fallback they have been walked by the host walker and added already."""
+        if finish_fallback and isinstance(rows, tuple):
+            raise TypeError("IngestStream.append: a (blob, offsets) batch has no row list for the host walker; pass finish_fallback=False")
+        fb = self.ctx.ingest_append_rows(self.id, rows, set_of_row)
+        if finish_fallback and len(fb):
+            entries, sets, kinds = host_walk_entries(rows, fb, set_of_row, self.tokenizer)
+            if entries:
+                self.ctx.ingest_add_entries(self.id, entries, sets, kinds)
+        return fb
+
+    def finish(self):
+        """-> (counts u64 [n_sets + n_parents, 3], status u32 [n_sets + n_parents]): sets, then parents"""
+        return self.ctx.ingest_finish(self.id, self.n_sets + self.n_parents)
+
+    def build(self, desc, n_words: int) -> np.ndarray:
+        return self.ctx.ingest_build(self.id, desc, n_words)
+
+    def build_sections(self, desc, arenas: bool = False):
+        return self.ctx.ingest_build_sections(self.id, desc, arenas)
+
+    def stats(self):
+        return self.ctx.ingest_stats(self.id)
+
+    def close(self):
+        if self.id:
+            self.ctx.ingest_free(self.id)
+            self.id = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

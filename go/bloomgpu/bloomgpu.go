@@ -887,6 +887,57 @@ func (g *Context) IngestRows(rows []byte, rowOff []uint64, setFirstRow, parentOf
 	return &Ingest{g, id, nSets, nParents}, nil
 }
 
+// IngestOpen creates a streaming ingest without rows (bsg_ingest_open): len(parentOfSet) empty sets (may be none) and nParents
+// parents; batches follow through IngestAppendRows, sets that show up later through IngestAddSets.  flags (IngestTrustedJSON
+// or 0) and tok (nil = the default tokenizer) apply to every batch.  A streaming ingest lives on one device of the context.
+// Finish / Build / BuildSections / Free are the one-shot ingest's.
+func (g *Context) IngestOpen(parentOfSet []uint32, nParents int, flags uint32, tok *Tokenizer) (*Ingest, error) {
+	var id C.uint64_t
+	var ctp *C.bsg_tokenizer
+	if tok != nil {
+		if err := tok.Validate(); err != nil {
+			return nil, err
+		}
+		ct := tok.c()
+		ctp = &ct
+	}
+	rc := C.bsg_ingest_open(g.c, C.uint32_t(len(parentOfSet)), u32p(parentOfSet), C.uint32_t(nParents), nil, C.uint32_t(flags), ctp, &id)
+	if err := g.err(rc); err != nil {
+		return nil, err
+	}
+	return &Ingest{g, id, len(parentOfSet), nParents}, nil
+}
+
+// IngestAddSets adds len(parentOfNewSet) sets behind the existing ones and returns the index of the first
+// (bsg_ingest_add_sets).  The numbering of every later call stays "sets, then parents".
+func (in *Ingest) IngestAddSets(parentOfNewSet []uint32) (firstNewSet uint32, err error) {
+	var first C.uint32_t
+	rc := C.bsg_ingest_add_sets(in.g.c, in.id, C.uint32_t(len(parentOfNewSet)), u32p(parentOfNewSet), nil, &first)
+	if err := in.g.err(rc); err != nil {
+		return 0, err
+	}
+	in.nSets += len(parentOfNewSet)
+	return uint32(first), nil
+}
+
+// IngestAppendRows hands one batch to the device (bsg_ingest_append_rows): row r goes to set setOfRow[r], in any order of
+// sets.  hostRows are the batch-local indices (ascending) of the rows the host walker must finish — the caller still holds
+// the batch — and hand back through AddEntries before Finish.
+func (in *Ingest) IngestAppendRows(rows []byte, rowOff []uint64, setOfRow []uint32) (hostRows []uint32, err error) {
+	nRows := len(setOfRow)
+	if nRows == 0 {
+		return nil, nil
+	}
+	hostRows = make([]uint32, nRows)
+	var n C.uint32_t
+	rc := C.bsg_ingest_append_rows(in.g.c, in.id, u8p(rows), u64p(rowOff), C.uint32_t(nRows), u32p(setOfRow), u32p(hostRows),
+		C.uint32_t(nRows), &n)
+	if err := in.g.err(rc); err != nil {
+		return nil, err
+	}
+	return hostRows[:n], nil
+}
+
 // FallbackRows lists the rows the host walker must finish (bsg_ingest_fallback_rows).
 func (in *Ingest) FallbackRows() ([]uint32, error) {
 	var n C.uint32_t

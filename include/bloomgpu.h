@@ -477,6 +477,7 @@ BSG_API int32_t bsg_tokenizer_default(bsg_tokenizer *out);
  * Call order:  bsg_ingest_rows -> [bsg_ingest_fallback_rows -> host walker -> bsg_ingest_add_entries]
  *              -> bsg_ingest_finish (exact distinct counts; the caller sizes (m, k) with its own
  *              EstimateParameters) -> bsg_ingest_build -> bsg_ingest_free.
+ * (Rows that arrive batch by batch: bsg_ingest_open / bsg_ingest_append_rows below.)
  * The device walker finishes rows of valid UTF-8 (see ingest.hip.h for the few exceptions); every other
  * row is reported by bsg_ingest_fallback_rows and MUST be walked by the host and added back with
  * bsg_ingest_add_entries before bsg_ingest_finish, or its entries are missing. */
@@ -487,7 +488,7 @@ typedef struct bsg_ingest_stats {
     uint32_t reserved;
     uint64_t row_bytes;
     uint64_t table_bytes;      /* HBM held by the distinct-entry tables */
-    float ms_walk;             /* k_ingest_rows dispatch time (sum over re-runs after a table grew) */
+    float ms_walk;             /* k_ingest_rows dispatch time (sum over re-runs after a table grew; a stream: over its appends) */
     float ms_union;            /* k_ingest_union into the parents */
     float ms_build;            /* k_build_sets (+ k_bin_* for bitsets beyond LDS): first dispatch start to last dispatch end */
     float ms_encode;           /* k_encode_payload + k_crc_sections (bsg_ingest_build_sections) */
@@ -516,6 +517,48 @@ BSG_API int32_t bsg_ingest_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uin
 /* bsg_ingest_rows uploads the rows in chunks: the first of about this many bytes (default 64 MiB, 0 restores it), each
  * later one twice the one before up to four times this; the copy of chunk i+1 overlaps the walk of chunk i. */
 BSG_API int32_t bsg_set_ingest_chunk(bsg_ctx *ctx, uint64_t bytes);
+/* ---- streaming device ingest: open an ingest without rows, append batches as they arrive, build at flush ----
+ * bsg_ingest_rows takes every row of a flush at once, grouped by set.  A caller whose rows arrive in batches over seconds
+ * (IngestRows, ingest.go:444-450) opens an ingest, hands each batch to the device when it arrives — the row bytes leave the
+ * device again when the call returns, only the distinct-entry tables stay — and finds the union and the build left at flush time.
+ * Call order:  bsg_ingest_open -> { [bsg_ingest_add_sets] -> bsg_ingest_append_rows -> [host walker -> bsg_ingest_add_entries] }*
+ *              -> bsg_ingest_finish -> bsg_ingest_build | bsg_ingest_build_sections -> bsg_ingest_free,
+ * the last four exactly as after bsg_ingest_rows (resident arenas included: block i = set i).
+ * A streaming ingest lives on ONE device, chosen the way a small bsg_ingest_rows call chooses one; cutting a stream over the
+ * devices of a context is not supported.
+ *
+ * bsg_ingest_open: n_sets (may be 0) empty sets and n_parents parents; parent_of_set[n_sets] as in bsg_ingest_rows (NULL with
+ * n_parents == 0).  Tables are allocated, nothing is walked.  slots_hint: optional initial capacities [n_sets * 3] (0 = default:
+ * 256 slots for fields, 1 024 for tokens and field::tokens — no row count is known; tables grow on demand).  flags
+ * (BSG_INGEST_TRUSTED_JSON or 0) and tok (NULL = the default tokenizer) are recorded and apply to every append. */
+BSG_API int32_t bsg_ingest_open(bsg_ctx *ctx, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents,
+                                const uint32_t *slots_hint, uint32_t flags, const bsg_tokenizer *tok, uint64_t *out_ingest_id);
+/* n_more sets numbered after the existing ones (partitions show up while batches arrive); *out_first_new_set = the first new
+ * index.  parent_of_new_set[n_more], slots_hint_new[n_more * 3] (may be NULL) as in bsg_ingest_open.  The numbering of every
+ * later call (add_entries, finish, build*) stays "sets, then parents": parent p is set index n_sets + p with the n_sets of that
+ * moment.  Nothing is rehashed: parents get their storage in bsg_ingest_finish. */
+BSG_API int32_t bsg_ingest_add_sets(bsg_ctx *ctx, uint64_t ingest_id, uint32_t n_more, const uint32_t *parent_of_new_set,
+                                    const uint32_t *slots_hint_new, uint32_t *out_first_new_set);
+/* One batch: row r (rows / row_off as in bsg_ingest_rows) goes to set set_of_row[r]; the rows come in any order of sets.  The
+ * upload is chunked like bsg_ingest_rows' (bsg_set_ingest_chunk).  Rows the device walker hands back are returned HERE:
+ * out_fallback_rows receives their batch-local indices, ascending, *out_n_fallback their number; the caller still holds
+ * exactly these rows, walks them on the host and adds their entries with bsg_ingest_add_entries before bsg_ingest_finish.
+ * out_fallback_rows == NULL with fallback_cap == 0 only asks for the number.  More rows handed back than fallback_cap:
+ * BSG_E_INVALID with the number in *out_n_fallback and no index written; the batch HAS been walked — every row not handed back
+ * is in the tables, and (as under BSG_INGEST_TRUSTED_JSON above) the call has inserted nothing the host walker would not insert
+ * again — so appending the same batch again with enough room, or walking all of it on the host, gives the same sets.
+ * A call that did not deliver its list (this one, or a count-only call that found rows to hand back) leaves n_rows, row_bytes
+ * and n_fallback_rows of the stats as they were — the call that delivers the list counts the batch; ms_walk and table_grows
+ * count every walk.  The calls on ONE streaming ingest (add_sets, append_rows, add_entries, finish) must be serialised by the
+ * caller: the set count and numbering are not guarded against a concurrent add_sets.  Different ingests may run side by side.
+ * bsg_ingest_fallback_rows on a streaming ingest is BSG_E_INVALID.  bsg_ingest_stats_read sums n_rows, row_bytes,
+ * n_fallback_rows, ms_walk and table_grows over the appends.
+ * Before anything is launched: BSG_E_NOTFOUND unknown id; BSG_E_INVALID an ingest made by bsg_ingest_rows(_tok), an ingest
+ * already finished, a set_of_row value >= the current number of sets, a parent index >= n_parents (open, add_sets), row_off
+ * not monotone, null arguments.  n_rows == 0: BSG_OK, nothing is launched. */
+BSG_API int32_t bsg_ingest_append_rows(bsg_ctx *ctx, uint64_t ingest_id, const uint8_t *rows, const uint64_t *row_off,
+                                       uint32_t n_rows, const uint32_t *set_of_row, uint32_t *out_fallback_rows,
+                                       uint32_t fallback_cap, uint32_t *out_n_fallback);
 /* Row indices (ascending) the host walker must finish; rows_out may be NULL to query the count. */
 BSG_API int32_t bsg_ingest_fallback_rows(bsg_ctx *ctx, uint64_t ingest_id, uint32_t *rows_out, uint32_t cap,
                                          uint32_t *n_out);

@@ -96,12 +96,17 @@ BSG_API uint32_t bsh_crc32c(const uint8_t *data, uint64_t len);
 /* ---- engine mirror ---- */
 typedef struct bse_engine bse_engine;
 /* config_json: {"MaxRowGroupRows":..,"MaxRowGroupBytes":..,"MaxBufferedRows":..,"MaxBufferedBytes":..,
- *               "BloomFalsePositiveRate":..,"PartitionField":"..","DeviceIngest":true|false,"DeviceMatch":true|false,
+ *               "BloomFalsePositiveRate":..,"PartitionField":"..","DeviceIngest":true|false,"DeviceIngestStream":true|false,
+ *               "DeviceMatch":true|false,
  *               "DeviceRegex":true|false,"DeviceMatchWide":true|false,"Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false}};
  *               missing keys take the
  *               reference defaults.  DeviceIngest (default false): rows are walked / tokenized / deduplicated /
  *               counted on the GPU at flush and merge time (bloomgpu.h bsg_ingest_*) instead of by indexRow on the
- *               host at ingest time; the files it writes are byte-identical either way.  DeviceMatch (default false): the
+ *               host at ingest time; the files it writes are byte-identical either way.  DeviceIngestStream (default false,
+ *               needs DeviceIngest: BSE_E_INVALID_CONFIG without it): every bse_ingest_rows batch is handed to an open
+ *               streaming ingest when it arrives (bsg_ingest_open / _add_sets / _append_rows) and its fallback rows are
+ *               finished at once, so a flush only finishes, sizes and builds; merge keeps the one-shot path; same bytes.
+ *               DeviceMatch (default false): the
  *               final row test of the surviving blocks runs on the GPU (bsg_match_rows) instead of in the host matcher;
  *               the delivered row set is the same.  DeviceMatchWide (default false, needs DeviceMatch): bse_query_many packs
  *               its queries into groups bounded by 64 distinct conditions (16 regex), not by 64 members, and decides each
@@ -136,7 +141,11 @@ BSG_API int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, c
  * other query with a Regex tree is answered as by bse_query.  "[]" gives "[]". */
 BSG_API int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, char **out_json, uint64_t *out_len);
 /* {"files":[{"FileID","BloomEntryCounts":{..},"section_bytes","blocks":[{"PartitionID","Rows","BloomEntryCounts":{..},
- *  "BloomFalsePositiveRate","BloomFilterSize","filters":[{"m","k"}|null x3]}]}]} */
+ *  "BloomFalsePositiveRate","BloomFilterSize","filters":[{"m","k"}|null x3]}]}],
+ *  "IngestStream":{"Batches","Rows","HostRows","Flushes"}} — the last: DeviceIngestStream at work since bse_open: bse_ingest_rows
+ *  batches and rows handed to a streaming ingest when they arrived, the rows among them the host walker finished at once, and the
+ *  flushes built from a stream.  A batch whose append fails is answered with the error and is not buffered; the rows buffered
+ *  before it are flushed through the one-shot path. */
 BSG_API int32_t bse_describe(bse_engine *e, char **out_json, uint64_t *out_len);
 /* fault injection (the reference's tests wrap its stores to corrupt reads): XOR one byte of a stored section */
 BSG_API int32_t bse_corrupt_section_byte(bse_engine *e, uint32_t file_index, int32_t block_index, uint64_t byte_index);

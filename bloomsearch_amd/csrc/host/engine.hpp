@@ -70,6 +70,10 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // bsg_match_rows_wide call, every set's query list read straight from the probe's survivors.  Off by default: routing is then
     // exactly the batched calls'.
     bool device_match_wide = false;
+    // true (with device_match): the grouping of device_match_wide, each group decided by ONE bsg_match_rows_wide_rows call: every
+    // pair's matching rows come back as a list (or NONE / ALL / its words) and are consumed as such, no bit row is scanned.  Off by
+    // default like device_match_wide.
+    bool device_match_wide_rows = false;
     // Tokenizer (engine.go:83, "for both indexing and verification"), restricted to the separator family
     // strings.FieldsFunc(lower ? strings.ToLower(v) : v, isSep) (text.hpp Tokenizer): indexRow, the host matcher and the
     // device calls (bsg_ingest_rows_tok / bsg_match_rows_tok) all use it.  Default: BasicWhitespaceLowerTokenizer.
@@ -991,7 +995,7 @@ private:
         const bsg_tokenizer tok = c_tokenizer();
         const size_t n_words = (scan.size() + 63) / 64, n_sets = set_wants.size();
         // DeviceMatchWide: a group is bounded by its table, not by its members; the storing walker's LDS leaves the tables more room
-        const bool wide = cfg_.device_match_wide;
+        const bool wide_rows = cfg_.device_match_wide_rows, wide = cfg_.device_match_wide || wide_rows;
         const size_t max_members = wide ? bsh_wide::kMaxQueries : 64;
         const uint32_t table_cap = wide ? bsh_wide::kWideLdsCap : bsh_rxg::kManyLdsCap;
         std::map<std::string, std::pair<uint32_t, uint32_t>> dfa_size;      // pattern -> (states, classes); (0, 0): outside the subset
@@ -1073,9 +1077,34 @@ private:
                 if (bsg_match_wide_size(set_first.data(), sq_off.data(), (uint32_t)n_sets, (uint32_t)scan.size(), (uint32_t)members.size(),
                                         pair_word_off.data(), &total))
                     return fail(kErrGpu, bsg_last_error(ctx_));
-                std::vector<uint64_t> words(total + 1);
                 std::vector<uint32_t> fb(scan.size());
                 uint32_t n_fb = 0;
+                if (wide_rows) {
+                    // the lists themselves: 2 u32 per word is the payload's bound, so the call cannot fail on space
+                    std::vector<uint32_t> hdr(sq.size() + 1), payload(2 * total + 1), ids;
+                    std::vector<uint64_t> pair_off(sq.size() + 1);
+                    uint64_t payload_len = 0;
+                    const int32_t rc = bsg_match_rows_wide_rows(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
+                                                                kinds.data(), (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(),
+                                                                (uint32_t)members.size(), set_first.data(), sq_off.data(), sq.data(), (uint32_t)n_sets, &tok,
+                                                                hdr.data(), pair_off.data(), payload.data(), 2 * total, &payload_len, fb.data(),
+                                                                (uint32_t)fb.size(), &n_fb);
+                    if (rc == BSG_E_UNSUPPORTED) continue;
+                    if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
+                    for (size_t s = 0; s < n_sets; ++s) {
+                        const uint32_t set_rows = set_first[s + 1] - set_first[s];
+                        ids.resize(set_rows);
+                        for (uint32_t p = sq_off[s]; p < sq_off[s + 1]; ++p) {
+                            uint32_t n = 0;
+                            if (bsg_match_pair_rows_list(hdr[p], payload.data() + pair_off[p], set_rows, ids.data(), set_rows, &n))
+                                return fail(kErrGpu, bsg_last_error(ctx_));
+                            uint8_t *h = hit[members[sq[p]]].data() + set_first[s];
+                            std::fill(h, h + set_rows, (uint8_t)0);
+                            for (uint32_t k = 0; k < n; ++k) h[ids[k]] = 1;
+                        }
+                    }
+                } else {
+                std::vector<uint64_t> words(total + 1);
                 const int32_t rc = bsg_match_rows_wide(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
                                                        (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(),
                                                        sq_off.data(), sq.data(), (uint32_t)n_sets, &tok, words.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
@@ -1087,6 +1116,7 @@ private:
                         const uint64_t *w = words.data() + pair_word_off[p];
                         for (uint32_t i = set_first[s]; i < set_first[s + 1]; ++i) h[i] = (w[(i - set_first[s]) >> 6] >> ((i - set_first[s]) & 63)) & 1;
                     }
+                }
                 for (size_t j = 0; j < members.size(); ++j) on_device[members[j]] = 1;
                 for (uint32_t i = 0; i < n_fb; ++i) {           // per query listed on the row's set
                     const size_t s = (size_t)(std::upper_bound(set_first.begin() + 1, set_first.end(), fb[i]) - (set_first.begin() + 1));

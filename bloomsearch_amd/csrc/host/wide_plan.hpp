@@ -4,7 +4,10 @@
 // bsg_match_rows_wide: where a (set, query) pair's bit row lies in the result (pair_words), which conditions a set's queries reference
 // (query_cond_masks / set_cond_masks: the mask the storing walker opens a regex condition's DFA by), a part's pairs and tiles
 // (part_sets) and the work items of k_eval_row_programs (eval_items: a wave owns 64 consecutive rows of ONE set and a range of its
-// pairs).  tests/wide_plan_check.cpp runs the same code on the CPU (tests/test_match_wide_plan.py).
+// pairs).  tests/wide_plan_check.cpp runs the same code on the CPU (tests/test_match_wide_plan.py).  For bsg_match_rows_wide_rows: a
+// pair's tag and header (pair_tag / pair_header), a header's payload size, offsets from headers, bsg_match_pair_rows_list's
+// expansion, the stitch of a multi-device call (stitch_headers / stitch_payloads) and the set table of the device's list passes
+// (pair_sets); tests/wide_rows_check.cpp runs those (tests/test_match_wide_rows_plan.py).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -167,6 +170,214 @@ inline bool eval_items(const PartSets &ps, std::vector<EvalItem> &items, uint64_
     }
     part_words = at;
     return true;
+}
+
+// ---- bsg_match_rows_wide_rows: a pair's matches as a tagged row list ----
+// Header = tag << 30 | n.  c of the pair's R rows match, T = tiles_of(R): NONE c == 0; ALL c == R > 0; LIST 0 < c < R and c < 2T, n = c
+// and c ascending set-relative row indices; DENSE otherwise, the pair's T words as 2T u32 (low half first).  The tag is a function
+// of (c, R) alone, and no payload is longer than the pair's bit row.  match.hip.h states the same rule for the device.
+constexpr uint32_t kPairNone = 0, kPairAll = 1, kPairList = 2, kPairDense = 3;
+constexpr uint32_t kPairScanWidth = 256;       // pairs one workgroup of the device's offset scan covers (BSG_MATCH_PAIR_SCAN_WIDTH)
+
+inline uint32_t pair_tag(uint64_t c, uint32_t R)
+{
+    if (c == 0) return kPairNone;
+    if (c == R) return kPairAll;
+    return c < 2ull * tiles_of(R) ? kPairList : kPairDense;
+}
+inline uint32_t pair_header(uint64_t c, uint32_t R)
+{
+    const uint32_t tag = pair_tag(c, R);
+    return tag << 30 | (tag == kPairList ? (uint32_t)c : 0u);
+}
+// u32 of payload behind a header of a pair over R rows
+inline uint64_t pair_payload_size(uint32_t hdr, uint32_t R)
+{
+    const uint32_t tag = hdr >> 30;
+    return tag == kPairList ? (hdr & 0x3FFFFFFFu) : tag == kPairDense ? 2ull * tiles_of(R) : 0ull;
+}
+// Where each pair's payload begins, from the headers: pair p of set s (pair_off[s] <= p < pair_off[s + 1], rows first_row[s] to
+// first_row[s + 1]) has header hdr[p - pair_off[0]] — the call's tables (pair_off[0] == 0) or a part's (PartSets).  off
+// [n_pairs + 1] may be NULL; -> the total.
+inline uint64_t pair_payload_offsets(const uint32_t *hdr, const uint32_t *first_row, const uint32_t *pair_off, uint32_t n_sets, uint64_t *off)
+{
+    uint64_t at = 0;
+    for (uint32_t s = 0; s < n_sets; ++s)
+        for (uint32_t p = pair_off[s]; p < pair_off[s + 1]; ++p) {
+            if (off) off[p - pair_off[0]] = at;
+            at += pair_payload_size(hdr[p - pair_off[0]], first_row[s + 1] - first_row[s]);
+        }
+    if (off) off[pair_off[n_sets] - pair_off[0]] = at;
+    return at;
+}
+
+inline uint64_t dense_word(const uint32_t *payload, uint32_t t) { return payload[2 * t] | (uint64_t)payload[2 * t + 1] << 32; }
+
+enum class ListStatus { Ok, Null, Header };
+
+// bsg_match_pair_rows_list: any tag expanded to the ascending set-relative indices; *out_n the full count, at most cap written.
+// Header: a count or an index that the set's rows cannot hold, indices that do not ascend, DENSE bits past the last row.
+inline ListStatus pair_rows_list(uint32_t hdr, const uint32_t *payload, uint32_t set_rows, uint32_t *out_rows, uint32_t cap, uint32_t *out_n)
+{
+    if (!out_n || (cap && !out_rows)) return ListStatus::Null;
+    const uint32_t tag = hdr >> 30, n = hdr & 0x3FFFFFFFu, T = tiles_of(set_rows);
+    *out_n = 0;
+    if (tag == kPairNone || tag == kPairAll) {
+        if (n || (tag == kPairAll && set_rows == 0)) return ListStatus::Header;
+        if (tag == kPairAll) {
+            *out_n = set_rows;
+            for (uint32_t i = 0; i < std::min(cap, set_rows); ++i) out_rows[i] = i;
+        }
+        return ListStatus::Ok;
+    }
+    if (tag == kPairList ? (n == 0 || n >= set_rows || n >= 2ull * T) : n != 0) return ListStatus::Header;
+    if (!payload) return ListStatus::Null;
+    if (tag == kPairList) {
+        for (uint32_t i = 0; i < n; ++i)
+            if (payload[i] >= set_rows || (i && payload[i] <= payload[i - 1])) return ListStatus::Header;
+        *out_n = n;
+        std::copy(payload, payload + std::min(cap, n), out_rows);
+        return ListStatus::Ok;
+    }
+    uint32_t k = 0;
+    for (uint32_t t = 0; t < T; ++t) {
+        uint64_t w = dense_word(payload, t);
+        if (t + 1 == T && set_rows % 64u && (w >> (set_rows % 64u))) return ListStatus::Header;
+        for (; w; w &= w - 1, ++k)
+            if (k < cap) out_rows[k] = t * 64u + (uint32_t)__builtin_ctzll(w);
+    }
+    *out_n = k;
+    return ListStatus::Ok;
+}
+
+// One device's share of a pair: the part's header over its `rows` rows of the set, which begin at the set's tile `tile0`, and its
+// payload (LIST indices are set-relative already: the write pass adds tile0; DENSE words are the part's own tiles).
+struct PairPiece {
+    uint32_t hdr, rows, tile0;
+    const uint32_t *payload;
+};
+
+inline uint64_t piece_count(const PairPiece &pc)
+{
+    const uint32_t tag = pc.hdr >> 30;
+    if (tag == kPairNone) return 0;
+    if (tag == kPairAll) return pc.rows;
+    if (tag == kPairList) return pc.hdr & 0x3FFFFFFFu;
+    uint64_t c = 0;
+    for (uint32_t t = 0; t < tiles_of(pc.rows); ++t) c += (uint64_t)__builtin_popcountll(dense_word(pc.payload, t));
+    return c;
+}
+
+// The stitch of a multi-device call: a pair's pieces in row order (a set cut at set-relative multiples of 64 rows has one per
+// device) -> the header over the whole set's R rows by the rule above.
+inline uint32_t stitch_header(const PairPiece *pieces, uint32_t n, uint32_t R)
+{
+    uint64_t c = 0;
+    for (uint32_t i = 0; i < n; ++i) c += piece_count(pieces[i]);
+    return pair_header(c, R);
+}
+// ... and its canonical payload behind that header (pair_payload_size(hdr, R) u32 at out): LIST = the pieces' indices one after
+// the other (ascending, as the pieces are), DENSE = the pieces scattered back into the set's words.
+inline void stitch_payload(const PairPiece *pieces, uint32_t n, uint32_t R, uint32_t hdr, uint32_t *out)
+{
+    const uint32_t tag = hdr >> 30;
+    if (tag == kPairList) {
+        for (uint32_t i = 0; i < n; ++i) {
+            const PairPiece &pc = pieces[i];
+            const uint32_t ptag = pc.hdr >> 30;
+            if (ptag == kPairAll) {
+                for (uint32_t r = 0; r < pc.rows; ++r) *out++ = pc.tile0 * 64u + r;
+            } else if (ptag == kPairList) {
+                out = std::copy(pc.payload, pc.payload + (pc.hdr & 0x3FFFFFFFu), out);
+            } else if (ptag == kPairDense) {
+                for (uint32_t t = 0; t < tiles_of(pc.rows); ++t)
+                    for (uint64_t w = dense_word(pc.payload, t); w; w &= w - 1) *out++ = (pc.tile0 + t) * 64u + (uint32_t)__builtin_ctzll(w);
+            }
+        }
+    } else if (tag == kPairDense) {
+        std::fill(out, out + 2ull * tiles_of(R), 0u);
+        for (uint32_t i = 0; i < n; ++i) {
+            const PairPiece &pc = pieces[i];
+            const uint32_t ptag = pc.hdr >> 30;
+            if (ptag == kPairAll) {
+                for (uint32_t r = pc.tile0 * 64u; r < pc.tile0 * 64u + pc.rows; ++r) out[r / 32u] |= 1u << (r % 32u);
+            } else if (ptag == kPairList) {
+                for (uint32_t k = 0; k < (pc.hdr & 0x3FFFFFFFu); ++k) out[pc.payload[k] / 32u] |= 1u << (pc.payload[k] % 32u);
+            } else if (ptag == kPairDense) {
+                std::copy(pc.payload, pc.payload + 2ull * tiles_of(pc.rows), out + 2ull * pc.tile0);
+            }
+        }
+    }
+}
+
+// One part's result as the stitch reads it: its sets, its headers (from its first pair on), its payload and where each pair's begins.
+struct PartRows {
+    const PartSets *ps;
+    const uint32_t *hdr, *payload;
+    std::vector<uint64_t> off;             // pair_payload_offsets over ps
+};
+
+// The pieces of pair p of set s among the call's parts (in row order), at most parts.size().  A set without rows lies in no part.
+inline uint32_t pair_pieces(const std::vector<PartRows> &parts, uint32_t s, uint32_t p, PairPiece *pieces)
+{
+    uint32_t n = 0;
+    for (const PartRows &pr : parts) {
+        const PartSets &ps = *pr.ps;
+        if (s < ps.s0 || s >= ps.s0 + ps.n()) continue;
+        const uint32_t ls = s - ps.s0, lp = p - ps.pair_off[0];
+        pieces[n++] = PairPiece{pr.hdr[lp], ps.first_row[ls + 1] - ps.first_row[ls], ps.tile0[ls], pr.payload + pr.off[lp]};
+    }
+    return n;
+}
+
+// The call's headers from its parts' (out_hdr [n_pairs]) and the payload's length ...
+inline uint64_t stitch_headers(const std::vector<PartRows> &parts, const uint32_t *set_first_row, const uint32_t *set_query_off, uint32_t n_sets,
+                               uint32_t *out_hdr)
+{
+    std::vector<PairPiece> pieces(parts.size());
+    uint64_t at = 0;
+    for (uint32_t s = 0; s < n_sets; ++s) {
+        const uint32_t R = set_first_row[s + 1] - set_first_row[s];
+        for (uint32_t p = set_query_off[s]; p < set_query_off[s + 1]; ++p) {
+            out_hdr[p] = stitch_header(pieces.data(), pair_pieces(parts, s, p, pieces.data()), R);
+            at += pair_payload_size(out_hdr[p], R);
+        }
+    }
+    return at;
+}
+// ... and, once the caller's buffer is known to hold it, the payload behind them.
+inline void stitch_payloads(const std::vector<PartRows> &parts, const uint32_t *set_first_row, const uint32_t *set_query_off, uint32_t n_sets,
+                            const uint32_t *hdr, uint32_t *out_payload)
+{
+    std::vector<PairPiece> pieces(parts.size());
+    for (uint32_t s = 0; s < n_sets; ++s) {
+        const uint32_t R = set_first_row[s + 1] - set_first_row[s];
+        for (uint32_t p = set_query_off[s]; p < set_query_off[s + 1]; ++p) {
+            const uint64_t size = pair_payload_size(hdr[p], R);
+            if (size) stitch_payload(pieces.data(), pair_pieces(parts, s, p, pieces.data()), R, hdr[p], out_payload);
+            out_payload += size;
+        }
+    }
+}
+
+// What the device's passes read per local set of a part (match.hip.h PairSetDesc): the first of its pairs (counted from the part's
+// first), where that pair's words begin in the part's result, the part's rows of the set and the set's tile they begin at.  One
+// more entry closes the table: pair0 = the part's pairs.
+struct PairSet {
+    uint64_t word0;
+    uint32_t pair0, rows, tile0, pad;
+};
+inline std::vector<PairSet> pair_sets(const PartSets &ps)
+{
+    std::vector<PairSet> v;
+    uint64_t at = 0;
+    for (uint32_t ls = 0; ls < ps.n(); ++ls) {
+        const uint32_t rows = ps.first_row[ls + 1] - ps.first_row[ls];
+        v.push_back(PairSet{at, ps.pair_off[ls] - ps.pair_off[0], rows, ps.tile0[ls], 0u});
+        at += (uint64_t)tiles_of(rows) * (ps.pair_off[ls + 1] - ps.pair_off[ls]);
+    }
+    v.push_back(PairSet{at, ps.pair_off[ps.n()] - ps.pair_off[0], 0u, 0u, 0u});
+    return v;
 }
 
 }  // namespace bsh_wide

@@ -46,6 +46,11 @@
 // set-relative) and a range of the set's pairs, loads each lane's sat and state once, reads a pair's query and program on the scalar
 // path (constant address space: uniform addresses) and writes __ballot(decided && verdict) as the pair's word of the tile.  No LDS,
 // no limit on the number of queries.
+//
+// The same pairs as tagged row lists (bsg_match_rows_wide_rows): k_pair_sizes, k_pair_scan_sums / _blocks / _apply and k_pair_write
+// run behind k_eval_row_programs over the words it left on the device: a header per pair (NONE / ALL / LIST / DENSE by the count of
+// its matching rows), an exclusive scan of the payload sizes over any number of pairs, then the LIST indices or the DENSE words
+// written back to back.  Headers and payload travel to the host, the words do not.
 #pragma once
 #include <type_traits>
 #include "ingest.hip.h"
@@ -481,6 +486,152 @@ __global__ __launch_bounds__(kRowEvalThreads) void k_eval_row_programs(const Row
         const bool verdict = j0 == j1 ? true : (stk & 1ULL) != 0;        // nil expression matches every row
         const uint64_t word = __ballot(decided && verdict);
         if (lane == 0u) e.out[out0 + (uint64_t)(p - pair0) * stride] = word;
+    }
+}
+
+// ---- the part's words as tagged row lists (bsg_match_rows_wide_rows) ----
+// Three passes over what k_eval_row_programs left in RowEvalArgs::out, a wave per pair of the part in the first and the last:
+//   k_pair_sizes   the pair's header over the part's rows of its set and its payload's u32 (host/wide_plan.hpp pair_header)
+//   k_pair_scan_*  the exclusive u64 prefix of the sizes over the part's pairs: block sums, their scan (one workgroup that walks
+//                  them kPairScanWidth at a time with a carry: any number of blocks), then each block's own scan behind its base
+//   k_pair_write   LIST: set-relative row indices, ascending; DENSE: the words copied as u32
+// Device memory: the payload scratch is sized at its bound, 2 u32 per result word (what RowEvalArgs::out takes once more), plus 20
+// bytes per pair (header, size, offset), 8 per kPairScanWidth pairs and 24 per set of the part.  Only the headers and the payload's
+// first `total` u32 travel back.
+constexpr uint32_t kPairNone = 0, kPairAll = 1, kPairList = 2, kPairDense = 3;
+constexpr uint32_t kPairThreads = 256;         // four waves, a pair each
+constexpr uint32_t kPairScanWidth = 256;       // pairs per workgroup of the scan, one per thread
+struct PairSetDesc {                           // host/wide_plan.hpp PairSet
+    uint64_t word0;                            // where the set's first pair's words begin in `words`
+    uint32_t pair0, rows, tile0, pad;          // its first pair, the part's rows of it, the set's tile they begin at
+};
+struct PairRowsArgs {
+    const PairSetDesc *sets;                   // [n_sets + 1], the last one closes the table (pair0 = n_pairs)
+    const uint64_t *words;                     // the part's result words
+    uint32_t *hdr;                             // [n_pairs]
+    uint64_t *size;                            // [n_pairs] u32 of payload
+    uint64_t *off;                             // [n_pairs + 1] their exclusive prefix, then the total
+    uint64_t *block_sum;                       // [ceil(n_pairs / kPairScanWidth)]
+    uint32_t *payload;
+    uint32_t n_pairs, n_sets;
+};
+
+// the local set of pair lp: the last one whose pair0 is <= lp (sets without pairs share their pair0 with the next one)
+__device__ __forceinline__ uint32_t pair_set_of(const PairSetDesc *sets, uint32_t n_sets, uint32_t lp)
+{
+    uint32_t lo = 0, hi = n_sets;              // sets[lo].pair0 <= lp < sets[hi].pair0
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (sets[mid].pair0 <= lp) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+template <class T>
+__device__ __forceinline__ T wave_inclusive_sum(T v, uint32_t lane)
+{
+#pragma unroll
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const T up = __shfl_up(v, o, 64);
+        if (lane >= o) v += up;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(kPairThreads) void k_pair_sizes(const PairRowsArgs a)
+{
+    const uint32_t lp = blockIdx.x * (kPairThreads / 64u) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (lp >= a.n_pairs) return;
+    const PairSetDesc sd = a.sets[pair_set_of(a.sets, a.n_sets, lp)];
+    const uint32_t T = (sd.rows + 63u) / 64u;
+    const uint64_t *w = a.words + sd.word0 + (uint64_t)(lp - sd.pair0) * T;
+    uint32_t c = 0;
+    for (uint32_t t = lane; t < T; t += 64u) c += (uint32_t)__popcll(w[t]);
+#pragma unroll
+    for (uint32_t o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, (int)o, 64);
+    if (lane == 0u) {
+        const uint32_t tag = c == 0u ? kPairNone : c == sd.rows ? kPairAll : c < 2u * T ? kPairList : kPairDense;
+        a.hdr[lp] = tag << 30 | (tag == kPairList ? c : 0u);
+        a.size[lp] = tag == kPairList ? (uint64_t)c : tag == kPairDense ? 2ull * T : 0ull;
+    }
+}
+
+// the inclusive prefix of one value per thread over the workgroup's kPairScanWidth threads; *total = their sum
+__device__ __forceinline__ uint64_t block_inclusive_sum(uint64_t v, uint64_t *wave_total, uint64_t *total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t incl = wave_inclusive_sum(v, lane);
+    if (lane == 63u) wave_total[wave] = incl;
+    __syncthreads();
+    uint64_t sum = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kPairScanWidth / 64u; ++k) {
+        if (k < wave) incl += wave_total[k];
+        sum += wave_total[k];
+    }
+    __syncthreads();                           // wave_total may be written again
+    *total = sum;
+    return incl;
+}
+
+__global__ __launch_bounds__(kPairScanWidth) void k_pair_scan_sums(const PairRowsArgs a)
+{
+    __shared__ uint64_t wave_total[kPairScanWidth / 64u];
+    const uint32_t i = blockIdx.x * kPairScanWidth + threadIdx.x;
+    uint64_t total;
+    (void)block_inclusive_sum(i < a.n_pairs ? a.size[i] : 0ull, wave_total, &total);
+    if (threadIdx.x == 0u) a.block_sum[blockIdx.x] = total;
+}
+
+// ONE workgroup: block_sum [n_blocks] becomes its own exclusive prefix, off[n_pairs] the total
+__global__ __launch_bounds__(kPairScanWidth) void k_pair_scan_blocks(const PairRowsArgs a, const uint32_t n_blocks)
+{
+    __shared__ uint64_t wave_total[kPairScanWidth / 64u];
+    uint64_t carry = 0;
+    for (uint32_t b0 = 0; b0 < n_blocks; b0 += kPairScanWidth) {
+        const uint32_t b = b0 + threadIdx.x;
+        const uint64_t v = b < n_blocks ? a.block_sum[b] : 0ull;
+        uint64_t total;
+        const uint64_t incl = block_inclusive_sum(v, wave_total, &total);
+        if (b < n_blocks) a.block_sum[b] = carry + incl - v;
+        carry += total;
+    }
+    if (threadIdx.x == 0u) a.off[a.n_pairs] = carry;
+}
+
+__global__ __launch_bounds__(kPairScanWidth) void k_pair_scan_apply(const PairRowsArgs a)
+{
+    __shared__ uint64_t wave_total[kPairScanWidth / 64u];
+    const uint32_t i = blockIdx.x * kPairScanWidth + threadIdx.x;
+    const uint64_t v = i < a.n_pairs ? a.size[i] : 0ull;
+    uint64_t total;
+    const uint64_t incl = block_inclusive_sum(v, wave_total, &total);
+    if (i < a.n_pairs) a.off[i] = a.block_sum[blockIdx.x] + incl - v;
+}
+
+__global__ __launch_bounds__(kPairThreads) void k_pair_write(const PairRowsArgs a)
+{
+    const uint32_t lp = blockIdx.x * (kPairThreads / 64u) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (lp >= a.n_pairs) return;
+    const uint32_t tag = a.hdr[lp] >> 30;
+    if (tag != kPairList && tag != kPairDense) return;
+    const PairSetDesc sd = a.sets[pair_set_of(a.sets, a.n_sets, lp)];
+    const uint32_t T = (sd.rows + 63u) / 64u;
+    const uint64_t *w = a.words + sd.word0 + (uint64_t)(lp - sd.pair0) * T;
+    uint32_t *out = a.payload + a.off[lp];     // size[lp] u32: c of a LIST (the bits of w), 2T of a DENSE pair
+    if (tag == kPairDense) {
+        const uint32_t *w32 = reinterpret_cast<const uint32_t *>(w);
+        for (uint32_t i = lane; i < 2u * T; i += 64u) out[i] = w32[i];
+        return;
+    }
+    uint32_t base = 0;                         // the bits of the rounds before
+    for (uint32_t t0 = 0; t0 < T; t0 += 64u) {
+        const uint32_t t = t0 + lane;
+        uint64_t x = t < T ? w[t] : 0ull;
+        const uint32_t cnt = (uint32_t)__popcll(x), incl = wave_inclusive_sum(cnt, lane);
+        uint32_t at = base + incl - cnt;
+        for (; x; x &= x - 1) out[at++] = (sd.tile0 + t) * 64u + (uint32_t)__builtin_ctzll(x);
+        base += (uint32_t)__shfl((int)incl, 63, 64);
     }
 }
 

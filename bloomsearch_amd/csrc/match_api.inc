@@ -3,7 +3,9 @@
 //   entry point -> MatchCall (the caller's arguments) -> begin_match_call (tokenizer, program and input checks) -> the family's own
 //   checks (kinds, sets) -> lower_programs -> build_rx_blob -> match_fan_out (device cuts, parts, fallback fold) -> match_part per
 //   device (buffers, condition hashing, chunked upload, one walker launch per chunk through launch_walker, results back).
-// What a family adds to a part is its PartMode (PlanePart: bit planes; WidePart: stored flags, k_eval_row_programs, pair words).
+// What a family adds to a part is its PartMode (PlanePart: bit planes; WidePart: stored flags, k_eval_row_programs, pair words —
+// or, for bsg_match_rows_wide_rows, the same part with the rows policy: three more passes turn the words into tagged row lists on
+// the device, headers and payload come back instead, and match_fan_out's finish step stitches the parts into the call's result).
 
 namespace {
 
@@ -36,6 +38,12 @@ int32_t build_rx_blob(const uint8_t *cond_bytes, const uint32_t *cond_off, const
 static_assert(bsh_wide::kWideLdsCap == bsg::kRxWideLdsCap && sizeof(bsh_wide::EvalItem) == sizeof(bsg::RowEvalItem) &&
                   offsetof(bsh_wide::EvalItem, stride) == offsetof(bsg::RowEvalItem, stride),
               "host/wide_plan.hpp states the kernels' limits and item layout");
+static_assert(sizeof(bsh_wide::PairSet) == sizeof(bsg::PairSetDesc) && offsetof(bsh_wide::PairSet, tile0) == offsetof(bsg::PairSetDesc, tile0) &&
+                  bsh_wide::kPairScanWidth == bsg::kPairScanWidth && BSG_MATCH_PAIR_SCAN_WIDTH == bsg::kPairScanWidth &&
+                  bsh_wide::kPairNone == bsg::kPairNone && bsh_wide::kPairAll == bsg::kPairAll && bsh_wide::kPairList == bsg::kPairList &&
+                  bsh_wide::kPairDense == bsg::kPairDense && BSG_ROW_NONE == bsg::kPairNone && BSG_ROW_ALL == bsg::kPairAll &&
+                  BSG_ROW_LIST == bsg::kPairList && BSG_ROW_DENSE == bsg::kPairDense,
+              "host/wide_plan.hpp and bloomgpu.h state the list passes' set table, scan width and tags");
 
 // One row-matcher call.  The entry points fill the caller's arguments; validation and lowering fill the rest.
 struct MatchCall {
@@ -232,12 +240,20 @@ struct PlanePart {
     void landed() {}
 };
 
+// bsg_match_rows_wide_rows: where the call's tagged row lists go
+struct WideRowsOut {
+    uint32_t *hdr;                             // [n_pairs]
+    uint64_t *off;                             // [n_pairs + 1] or NULL
+    uint32_t *payload;
+    uint64_t cap, *len;
+};
 // bsg_match_rows_wide: what a part needs beyond the call (sets always materialised: the implicit set is one set with every query)
 struct WidePlan {
     const uint32_t *set_first_row, *set_query_off, *set_queries;
     uint32_t n_sets, n_queries;
     std::vector<uint64_t> set_cond_mask;       // [n_sets]
     std::vector<uint64_t> set_word0;           // [n_sets + 1]: the first result word of the set's first pair
+    const WideRowsOut *rows = nullptr;         // the rows policy: lists instead of words
 };
 
 // The wide call: the storing walk chunk by chunk, then one evaluation launch over the part's items (r0 a set-relative multiple of 64).
@@ -258,8 +274,16 @@ struct WidePart {
     uint64_t *d_sat = nullptr, *d_out = nullptr, *d_smask = nullptr;
     uint32_t *d_sfirst = nullptr, *d_spair = nullptr, *d_pairs = nullptr;
     bsg::RowEvalItem *d_items = nullptr;
+    // the rows policy: the words stay on the device, k_pair_sizes / k_pair_scan_* / k_pair_write make the lists, headers and
+    // payload_len u32 of payload come back (direct: into the caller's buffers, when the payload fits; else staged for the stitch)
+    std::vector<bsh_wide::PairSet> psets;
+    std::vector<uint32_t> staged_hdr, staged_payload;
+    uint64_t payload_len = 0;
+    bsg::PairSetDesc *d_psets = nullptr;
+    uint32_t *d_phdr = nullptr, *d_payload = nullptr;
+    uint64_t *d_psize = nullptr, *d_poffs = nullptr, *d_bsum = nullptr;
 
-    const char *tag() const { return "bsg_match_rows_wide"; }
+    const char *tag() const { return wp.rows ? "bsg_match_rows_wide_rows" : "bsg_match_rows_wide"; }
     bool prog_off() const { return true; }
     int32_t plan(uint32_t r0, uint32_t r1)
     {
@@ -269,6 +293,7 @@ struct WidePart {
         for (uint32_t &v : pair_off_local) v -= pair0;
         if (!bsh_wide::eval_items(ps, items, part_words))
             return fail(BSG_E_UNSUPPORTED, "more than %u (tile, pair range) items on one device", bsh_wide::kMaxItems);
+        if (wp.rows) psets = bsh_wide::pair_sets(ps);
         return BSG_OK;
     }
     int32_t alloc(PartDev &p)
@@ -281,8 +306,17 @@ struct WidePart {
         HIP_TRY(p.scratch.alloc(&d_smask, (size_t)n_sets * 8));
         HIP_TRY(p.scratch.alloc(&d_pairs, std::max<size_t>(n_pairs, 1) * 4));
         HIP_TRY(p.scratch.alloc(&d_items, std::max<size_t>(items.size(), 1) * sizeof(bsg::RowEvalItem)));
+        if (wp.rows && n_pairs) {
+            HIP_TRY(p.scratch.alloc(&d_psets, psets.size() * sizeof(bsg::PairSetDesc)));
+            HIP_TRY(p.scratch.alloc(&d_phdr, (size_t)n_pairs * 4));
+            HIP_TRY(p.scratch.alloc(&d_psize, (size_t)n_pairs * 8));
+            HIP_TRY(p.scratch.alloc(&d_poffs, ((size_t)n_pairs + 1) * 8));
+            HIP_TRY(p.scratch.alloc(&d_bsum, (size_t)scan_blocks() * 8));
+            HIP_TRY(p.scratch.alloc(&d_payload, std::max<uint64_t>(part_words, 1) * 8));      // the bound: 2 u32 per word
+        }
         return BSG_OK;
     }
+    uint32_t scan_blocks() const { return (n_pairs + bsg::kPairScanWidth - 1) / bsg::kPairScanWidth; }
     int32_t upload(PartDev &p)
     {
         HIP_TRY(hipMemcpyAsync(d_sfirst, ps.first_row.data(), ((size_t)n_sets + 1) * 4, hipMemcpyHostToDevice, p.d.stream));
@@ -290,6 +324,7 @@ struct WidePart {
         HIP_TRY(hipMemcpyAsync(d_smask, wp.set_cond_mask.data() + ps.s0, (size_t)n_sets * 8, hipMemcpyHostToDevice, p.d.stream));
         if (n_pairs) HIP_TRY(hipMemcpyAsync(d_pairs, wp.set_queries + pair0, (size_t)n_pairs * 4, hipMemcpyHostToDevice, p.d.stream));
         if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::RowEvalItem), hipMemcpyHostToDevice, p.d.stream));
+        if (d_psets) HIP_TRY(hipMemcpyAsync(d_psets, psets.data(), psets.size() * sizeof(bsg::PairSetDesc), hipMemcpyHostToDevice, p.d.stream));
         return BSG_OK;
     }
     void launch(PartDev &p, bsg::MatchArgs &a, uint32_t rf, hipEvent_t k0, hipEvent_t k1)
@@ -307,6 +342,7 @@ struct WidePart {
                                   p.d.stream, kev.v[k], kev.v[k + 1], 0, e);
             HIP_TRY(hipGetLastError());
         }
+        if (wp.rows) return rows_results(p, kev);
         if (part_words) {
             uint64_t *dst = mc.out_bits + wp.set_word0[ps.s0];
             if (!direct) { staged.resize(part_words); dst = staged.data(); }
@@ -314,9 +350,37 @@ struct WidePart {
         }
         return BSG_OK;
     }
+    // The list passes between two more events (the first kernel's start, the last one's stop), then the headers, the payload's
+    // length (the stream is waited for: it sizes the copy) and that much payload.
+    int32_t rows_results(PartDev &p, EventList &kev)
+    {
+        if (!n_pairs) return BSG_OK;
+        const size_t k = kev.v.size();
+        HIP_TRY(kev.add(2));
+        const bsg::PairRowsArgs a{d_psets, d_out, d_phdr, d_psize, d_poffs, d_bsum, d_payload, n_pairs, n_sets};
+        const dim3 waves((n_pairs + bsg::kPairThreads / 64 - 1) / (bsg::kPairThreads / 64)), scan(scan_blocks());
+        hipExtLaunchKernelGGL(bsg::k_pair_sizes, waves, dim3(bsg::kPairThreads), 0, p.d.stream, kev.v[k], nullptr, 0, a);
+        hipLaunchKernelGGL(bsg::k_pair_scan_sums, scan, dim3(bsg::kPairScanWidth), 0, p.d.stream, a);
+        hipLaunchKernelGGL(bsg::k_pair_scan_blocks, dim3(1), dim3(bsg::kPairScanWidth), 0, p.d.stream, a, scan_blocks());
+        hipLaunchKernelGGL(bsg::k_pair_scan_apply, scan, dim3(bsg::kPairScanWidth), 0, p.d.stream, a);
+        hipExtLaunchKernelGGL(bsg::k_pair_write, waves, dim3(bsg::kPairThreads), 0, p.d.stream, nullptr, kev.v[k + 1], 0, a);
+        HIP_TRY(hipGetLastError());
+        uint32_t *hdr = wp.rows->hdr + pair0;
+        if (!direct) { staged_hdr.resize(n_pairs); hdr = staged_hdr.data(); }
+        HIP_TRY(hipMemcpyAsync(hdr, d_phdr, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, p.d.stream));
+        HIP_TRY(hipMemcpyAsync(&payload_len, d_poffs + n_pairs, 8, hipMemcpyDeviceToHost, p.d.stream));
+        HIP_TRY(hipStreamSynchronize(p.d.stream));
+        if (payload_len > 2 * part_words) return fail(BSG_E_HIP, "the list passes report %llu u32 of payload for %llu words",
+                                                      (unsigned long long)payload_len, (unsigned long long)part_words);
+        uint32_t *dst = wp.rows->payload;              // direct: every pair before the part's first has no rows, so no payload
+        if (!direct) { staged_payload.resize(payload_len); dst = staged_payload.data(); }
+        else if (payload_len > wp.rows->cap) return BSG_OK;                // the finish step reports it; no payload is written
+        if (payload_len) HIP_TRY(hipMemcpyAsync(dst, d_payload, payload_len * 4, hipMemcpyDeviceToHost, p.d.stream));
+        return BSG_OK;
+    }
     void landed()                                      // the part's layout -> the call's: per pair, the part's tiles of the set
     {
-        if (direct) return;
+        if (direct || wp.rows) return;
         uint64_t at = 0;
         for (uint32_t ls = 0; ls < n_sets; ++ls) {
             const uint32_t s = ps.s0 + ls, tiles = bsh_wide::tiles_of(ps.first_row[ls + 1] - ps.first_row[ls]);
@@ -423,8 +487,9 @@ int32_t match_part(bsg_ctx *ctx, Device &d, const MatchCall &mc, uint32_t r0, ui
 // Surviving blocks are independent (query_exec.go:729-764): a large scan is cut into one contiguous run of rows per
 // device (bsh_wide::part_cuts over the call's sets: whole words of every result row, about equal bytes); a small one takes one
 // device.  part(i, n_parts, device, r0, r1, fb, ms) runs one of them; their fallback rows are merged, sorted and handed out.
-template <class F>
-int32_t match_fan_out(bsg_ctx *ctx, const MatchCall &mc, const uint32_t *set_first_row, uint32_t n_sets, F &&part)
+// finish() runs once every part has succeeded (bsg_match_rows_wide_rows: the stitch); the fallback list is handed out whatever it says.
+template <class F, class G>
+int32_t match_fan_out(bsg_ctx *ctx, const MatchCall &mc, const uint32_t *set_first_row, uint32_t n_sets, F &&part, G &&finish)
 {
     const uint32_t nd = (uint32_t)ctx->devs.size();
     const uint32_t want = (nd > 1 && mc.n_bytes >= ctx->shard_min_row_bytes) ? nd : 1;
@@ -436,6 +501,7 @@ int32_t match_fan_out(bsg_ctx *ctx, const MatchCall &mc, const uint32_t *set_fir
     if (int32_t rc = run_parts(n_parts, [&](uint32_t i) -> int32_t {
             return part(n_parts, *ctx->devs[(first + i) % nd], cuts[i], cuts[i + 1], fbs[i], &ms[i]);
         })) return rc;
+    const int32_t finished = finish();
     std::vector<uint32_t> fb;
     for (auto &v : fbs) fb.insert(fb.end(), v.begin(), v.end());
     std::sort(fb.begin(), fb.end());
@@ -448,7 +514,12 @@ int32_t match_fan_out(bsg_ctx *ctx, const MatchCall &mc, const uint32_t *set_fir
     }
     if (fb.size() > mc.fallback_cap && mc.out_fallback_rows)
         return fail(BSG_E_INVALID, "%zu rows need the host matcher, caller's list holds %u", fb.size(), mc.fallback_cap);
-    return BSG_OK;
+    return finished;
+}
+template <class F>
+int32_t match_fan_out(bsg_ctx *ctx, const MatchCall &mc, const uint32_t *set_first_row, uint32_t n_sets, F &&part)
+{
+    return match_fan_out(ctx, mc, set_first_row, n_sets, part, [] { return (int32_t)BSG_OK; });
 }
 
 // the single and the batched calls' parts: planes over the implicit set {0, n_rows} (cuts at multiples of 64 rows)
@@ -526,14 +597,15 @@ int32_t wide_size_status(bsh_wide::SizeStatus st, uint32_t bad_set, const uint32
 
 int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
                              const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
-                             const bsg_tokenizer *tok_in)
+                             const bsg_tokenizer *tok_in, const WideRowsOut *rows = nullptr)
 {
+    if (rows && (!rows->len || (rows->cap && !rows->payload))) return fail(BSG_E_INVALID, "null argument");
     if (int32_t rc = begin_match_call(mc, kWideFamily, tok_in, prog_ops, prog_off, n_queries)) return rc;
     const uint32_t n_rows = mc.n_rows;
     for (uint32_t c = 0; c < mc.n_conds; ++c)
         if (mc.cond_kinds[c] > BSG_KIND_FIELD_REGEX) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
     // the sets: the caller's, or one implicit set of all rows with every query
-    WidePlan wp{set_first_row, set_query_off, set_queries, n_sets, n_queries, {}, {}};
+    WidePlan wp{set_first_row, set_query_off, set_queries, n_sets, n_queries, {}, {}, rows};
     std::vector<uint32_t> implicit_first, implicit_off, implicit_queries;
     if (n_sets == 0) {
         if (set_first_row || set_query_off || set_queries) return fail(BSG_E_INVALID, "a set table without its number of sets");
@@ -559,6 +631,12 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
     if (int32_t rc = lower_programs(mc, kWideFamily, prog_ops, prog_off, n_queries)) return rc;
     if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, bsg::kRxWideLdsCap)) return rc;
     const uint32_t n_pairs = wp.set_query_off[wp.n_sets];
+    if (rows) {                                // every pair NONE until a part says otherwise (a set without rows lies in no part)
+        if (n_pairs && !rows->hdr) return fail(BSG_E_INVALID, "null argument");
+        if (n_pairs) memset(rows->hdr, 0, (size_t)n_pairs * 4);
+        if (rows->off) memset(rows->off, 0, ((size_t)n_pairs + 1) * 8);
+        *rows->len = 0;
+    }
     if (n_rows == 0 || n_pairs == 0) return BSG_OK;
     wp.set_cond_mask = bsh_wide::set_cond_masks(bsh_wide::query_cond_masks(prog_ops, prog_off, n_queries, mc.n_conds), wp.set_query_off, wp.set_queries, wp.n_sets);
     wp.set_word0.assign((size_t)wp.n_sets + 1, 0);
@@ -566,11 +644,47 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
         wp.set_word0[s + 1] = wp.set_word0[s] + (uint64_t)bsh_wide::tiles_of(wp.set_first_row[s + 1] - wp.set_first_row[s]) *
                                                     (wp.set_query_off[s + 1] - wp.set_query_off[s]);
     *mc.out_n_fallback = 0;
-    return match_fan_out(ctx, mc, wp.set_first_row, wp.n_sets,
-                         [&](uint32_t n_parts, Device &d, uint32_t r0, uint32_t r1, std::vector<uint32_t> &fb, float *ms) -> int32_t {
-                             WidePart mode{mc, wp, n_parts == 1};
-                             return match_part(ctx, d, mc, r0, r1, mode, fb, ms);
-                         });
+    if (!rows)
+        return match_fan_out(ctx, mc, wp.set_first_row, wp.n_sets,
+                             [&](uint32_t n_parts, Device &d, uint32_t r0, uint32_t r1, std::vector<uint32_t> &fb, float *ms) -> int32_t {
+                                 WidePart mode{mc, wp, n_parts == 1};
+                                 return match_part(ctx, d, mc, r0, r1, mode, fb, ms);
+                             });
+    // the rows policy: the parts outlive their devices' work, the finish step makes the call's result of them
+    std::mutex kept_mu;
+    std::vector<std::unique_ptr<WidePart>> kept;
+    return match_fan_out(
+        ctx, mc, wp.set_first_row, wp.n_sets,
+        [&](uint32_t n_parts, Device &d, uint32_t r0, uint32_t r1, std::vector<uint32_t> &fb, float *ms) -> int32_t {
+            WidePart *mode = new WidePart{mc, wp, n_parts == 1};
+            {
+                std::lock_guard<std::mutex> lk(kept_mu);
+                kept.emplace_back(mode);
+            }
+            return match_part(ctx, d, mc, r0, r1, *mode, fb, ms);
+        },
+        [&]() -> int32_t {
+            uint64_t len = 0;
+            std::vector<bsh_wide::PartRows> parts;
+            if (kept.size() == 1) {                    // direct: the headers are the call's already, and the payload if it fits
+                len = kept[0]->payload_len;
+            } else {
+                std::sort(kept.begin(), kept.end(), [](const auto &a, const auto &b) { return a->ps.s0 != b->ps.s0 ? a->ps.s0 < b->ps.s0 : a->ps.tile0[0] < b->ps.tile0[0]; });
+                for (const auto &k : kept) {
+                    if (!k->n_pairs) continue;
+                    parts.push_back(bsh_wide::PartRows{&k->ps, k->staged_hdr.data(), k->staged_payload.data(), std::vector<uint64_t>((size_t)k->n_pairs + 1)});
+                    bsh_wide::pair_payload_offsets(parts.back().hdr, k->ps.first_row.data(), k->ps.pair_off.data(), k->n_sets, parts.back().off.data());
+                }
+                len = bsh_wide::stitch_headers(parts, wp.set_first_row, wp.set_query_off, wp.n_sets, rows->hdr);
+            }
+            *rows->len = len;
+            if (rows->off) bsh_wide::pair_payload_offsets(rows->hdr, wp.set_first_row, wp.set_query_off, wp.n_sets, rows->off);
+            if (len > rows->cap)
+                return fail(BSG_E_INVALID, "the matches take %llu u32 of payload, caller's buffer holds %llu", (unsigned long long)len,
+                            (unsigned long long)rows->cap);
+            if (kept.size() != 1) bsh_wide::stitch_payloads(parts, wp.set_first_row, wp.set_query_off, wp.n_sets, rows->hdr, rows->payload);
+            return BSG_OK;
+        });
 }
 
 }  // namespace
@@ -587,6 +701,32 @@ int32_t bsg_match_rows_wide(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *r
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
     return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
+}
+
+int32_t bsg_match_rows_wide_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                 const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                 const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                 const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
+                                 const bsg_tokenizer *tok,
+                                 uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap, uint64_t *out_payload_len,
+                                 uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    // (the shared checks ask for a result pointer with the rows: this call's is out_payload_len, the headers are asked for once the
+    // pairs are counted; nothing is written through out_bits)
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
+                 fallback_cap, out_n_fallback};
+    const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
+}
+
+int32_t bsg_match_pair_rows_list(uint32_t hdr, const uint32_t *payload, uint32_t set_rows, uint32_t *out_rows, uint32_t cap, uint32_t *out_n)
+{
+    switch (bsh_wide::pair_rows_list(hdr, payload, set_rows, out_rows, cap, out_n)) {
+    case bsh_wide::ListStatus::Ok: return BSG_OK;
+    case bsh_wide::ListStatus::Null: return fail(BSG_E_INVALID, "null argument");
+    default: return fail(BSG_E_INVALID, "header 0x%08x and its payload are no pair of a set of %u rows", hdr, set_rows);
+    }
 }
 
 int32_t bsg_match_wide_size(const uint32_t *set_first_row, const uint32_t *set_query_off, uint32_t n_sets, uint32_t n_rows, uint32_t n_queries,

@@ -103,6 +103,19 @@ def wide_pair_bits(words, pair_word_off, pair: int, n_set_rows: int) -> np.ndarr
     return np.unpackbits(w.view(np.uint8), bitorder="little")[:n_set_rows].astype(bool)
 
 
+def pair_rows_list(hdr: int, payload, set_rows: int, cap=None) -> np.ndarray:
+    """bsg_match_pair_rows_list (host arithmetic, no GPU needed): one pair of Context.match_rows_wide_rows, whatever its tag, as the
+    ascending set-relative indices of its matching rows (at most cap of them; default: all)."""
+    L = _lib.load()
+    pl = np.ascontiguousarray(payload, dtype=np.uint32)
+    out = np.zeros(max(set_rows if cap is None else cap, 1), dtype=np.uint32)
+    n = C.c_uint32()
+    rc = L.bsg_match_pair_rows_list(int(hdr), pl.ctypes.data if len(pl) else None, set_rows, out.ctypes.data, set_rows if cap is None else cap, C.byref(n))
+    if rc:
+        raise BloomGpuError(rc, L.bsg_last_error(None).decode())
+    return out[: min(n.value, set_rows if cap is None else cap)].copy()
+
+
 class Context:
     """bsg_ctx: one or more gfx950 devices, per-device streams."""
 
@@ -699,12 +712,9 @@ class Context:
         planes = np.unpackbits(bits.view(np.uint8).reshape(nq, n_words * 8), axis=1, bitorder="little")[:, :n].astype(bool)
         return planes, fb[: nfb.value].copy()
 
-    def match_rows_wide(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None):
-        """bsg_match_rows_wide: rows as match_rows; batch: query.CompiledWideBatch (or anything with kinds / fields / tokens / prog_ops /
-        prog_off), any number of queries.  set_first_row [n_sets + 1], set_query_off [n_sets + 1] and set_queries (CSR: the queries
-        evaluated on each set, strictly ascending): all None = one implicit set of all rows with every query.
-        -> (u64 words, u64 pair_word_off [n_pairs + 1], sorted u32 array of rows the host matcher must decide): pair p's bit row is
-        words[pair_word_off[p]: pair_word_off[p + 1]] (wide_pair_bits unpacks it)."""
+    def _wide_args(self, rows, batch, set_first_row, set_query_off, set_queries, tokenizer):
+        """What bsg_match_rows_wide and bsg_match_rows_wide_rows take up to and including tok -> (the arguments, the arrays they point
+        into, n_rows, pair_word_off, total words)."""
         if isinstance(rows, tuple):
             blob = np.ascontiguousarray(rows[0], dtype=np.uint8)
             off = np.ascontiguousarray(rows[1], dtype=np.uint64)
@@ -733,15 +743,40 @@ class Context:
         pair_word_off, total = self.match_wide_size(sfr, sqo, n, nq)
         if sq is not None and len(sq) != len(pair_word_off) - 1:
             raise ValueError("set_queries holds set_query_off[n_sets] entries")
+        spec = None if tokenizer is None else c_spec(tokenizer)
+        args = (self.h, _lib._ptr(blob), _lib._ptr(off), n, _lib._ptr(cblob), _lib._ptr(coff), _lib._ptr(kinds), len(kinds), _lib._ptr(ops),
+                poff.ctypes.data, nq, _lib._ptr(sfr), _lib._ptr(sqo), None if sq is None else sq.ctypes.data, n_sets, spec)
+        return args, (blob, off, cblob, coff, kinds, ops, poff, sfr, sqo, sq, spec), n, pair_word_off, total
+
+    def match_rows_wide(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None):
+        """bsg_match_rows_wide: rows as match_rows; batch: query.CompiledWideBatch (or anything with kinds / fields / tokens / prog_ops /
+        prog_off), any number of queries.  set_first_row [n_sets + 1], set_query_off [n_sets + 1] and set_queries (CSR: the queries
+        evaluated on each set, strictly ascending): all None = one implicit set of all rows with every query.
+        -> (u64 words, u64 pair_word_off [n_pairs + 1], sorted u32 array of rows the host matcher must decide): pair p's bit row is
+        words[pair_word_off[p]: pair_word_off[p + 1]] (wide_pair_bits unpacks it)."""
+        args, _keep, n, pair_word_off, total = self._wide_args(rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
         words = np.zeros(total, dtype=np.uint64)
         fb = np.zeros(max(n, 1), dtype=np.uint32)
         nfb = C.c_uint32()
-        self._check(self.L.bsg_match_rows_wide(self.h, _lib._ptr(blob), _lib._ptr(off), n, _lib._ptr(cblob), _lib._ptr(coff), _lib._ptr(kinds),
-                                               len(kinds), _lib._ptr(ops), poff.ctypes.data, nq, _lib._ptr(sfr), _lib._ptr(sqo),
-                                               None if sq is None else sq.ctypes.data, n_sets,
-                                               None if tokenizer is None else c_spec(tokenizer), words.ctypes.data, _lib._ptr(fb), len(fb),
-                                               C.byref(nfb)))
+        self._check(self.L.bsg_match_rows_wide(*args, words.ctypes.data, _lib._ptr(fb), len(fb), C.byref(nfb)))
         return words, pair_word_off, fb[: nfb.value].copy()
+
+    def match_rows_wide_rows(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None, payload_cap=None):
+        """bsg_match_rows_wide_rows: the arguments of match_rows_wide; payload_cap (u32 of payload the buffer holds) defaults to the
+        bound, 2 per result word.  -> (u32 headers [n_pairs], u64 pair_off [n_pairs + 1], u32 payload [its length], sorted u32 array of
+        rows the host matcher must decide): pair p is pair_rows_list(hdr[p], payload[pair_off[p]: pair_off[p + 1]], rows of its set)."""
+        args, _keep, n, pair_word_off, total = self._wide_args(rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
+        n_pairs = len(pair_word_off) - 1
+        cap = 2 * total if payload_cap is None else int(payload_cap)
+        hdr = np.zeros(n_pairs, dtype=np.uint32)
+        pair_off = np.zeros(n_pairs + 1, dtype=np.uint64)
+        payload = np.zeros(max(cap, 1), dtype=np.uint32)
+        length = C.c_uint64()
+        fb = np.zeros(max(n, 1), dtype=np.uint32)
+        nfb = C.c_uint32()
+        self._check(self.L.bsg_match_rows_wide_rows(*args, _lib._ptr(hdr), pair_off.ctypes.data, payload.ctypes.data, cap, C.byref(length),
+                                                    _lib._ptr(fb), len(fb), C.byref(nfb)))
+        return hdr, pair_off, payload[: length.value].copy(), fb[: nfb.value].copy()
 
     def match_wide_size(self, set_first_row, set_query_off, n_rows: int, n_queries: int):
         """bsg_match_wide_size (host arithmetic) -> (u64 pair_word_off [n_pairs + 1], total words); None, None = the implicit set."""

@@ -1148,6 +1148,89 @@ func (g *Context) MatchRowsWide(rows []byte, rowOff []uint64, conds []MatchCond,
 	return words[:total], pairWordOff, hostRows[:nfb], nil
 }
 
+// Tags of a pair's header in MatchRowsWideRows' result (hdr >> 30); a RowList header's low 30 bits count its rows.
+const (
+	RowNone  = 0
+	RowAll   = 1
+	RowList  = 2
+	RowDense = 3
+)
+
+// MatchRowsWideRows is MatchRowsWide with every pair's matches delivered as a tagged row list (bsg_match_rows_wide_rows): what
+// matchBlock goes on with is the rows to materialise, not a bitmap to search.  Arguments as MatchRowsWide.  hdr[p] = tag<<30 | n and
+// payload[pairOff[p]:pairOff[p+1]] of pair p of set s (R rows, T = ceil(R/64)): RowNone / RowAll no payload; RowList n ascending
+// set-relative row indices (row setFirstRow[s]+i); RowDense 2T uint32, the words MatchRowsWide returns, low half first.
+// MatchPairRowsList expands any of them.  Rows in hostRows count in no pair and must be decided by matchRowBytes for every query
+// listed on their set.  The payload buffer is sized at its bound (2 uint32 per word of the bit rows), so the call cannot fail on space.
+func (g *Context) MatchRowsWideRows(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
+	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (hdr []uint32, pairOff []uint64, payload []uint32, hostRows []uint32, err error) {
+	n, nq := len(rowOff)-1, len(progOff)-1
+	if n <= 0 || nq <= 0 {
+		return nil, nil, nil, nil, nil
+	}
+	if (setFirstRow == nil) != (setQueryOff == nil) || (setFirstRow == nil && setQueries != nil) || len(setFirstRow) != len(setQueryOff) {
+		return nil, nil, nil, nil, fmt.Errorf("bloomgpu: setFirstRow and setQueryOff hold one entry per set and one more, or all three tables are nil")
+	}
+	nSets, nPairs := 0, nq
+	if setFirstRow != nil {
+		nSets = len(setFirstRow) - 1
+		nPairs = int(setQueryOff[nSets])
+		if nSets < 1 || len(setQueries) != nPairs {
+			return nil, nil, nil, nil, fmt.Errorf("bloomgpu: setQueries holds setQueryOff[nSets] entries")
+		}
+	}
+	var ct *C.bsg_tokenizer
+	if tok != nil {
+		if err := tok.Validate(); err != nil {
+			return nil, nil, nil, nil, err
+		}
+		c := tok.c()
+		ct = &c
+	}
+	var total C.uint64_t
+	if err := g.err(C.bsg_match_wide_size(u32p(setFirstRow), u32p(setQueryOff), C.uint32_t(nSets), C.uint32_t(n), C.uint32_t(nq),
+		nil, &total)); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	pairOff = make([]uint64, nPairs+1)
+	if nPairs == 0 {
+		return nil, pairOff, nil, nil, nil
+	}
+	hdr = make([]uint32, nPairs)
+	payload = make([]uint32, 2*int(total)+1)
+	hostRows = make([]uint32, n)
+	var cbytes []byte
+	coff := make([]uint32, 1, 2*len(conds)+1)
+	kinds := make([]uint32, len(conds))
+	for i, c := range conds {
+		cbytes = append(cbytes, c.Field...)
+		coff = append(coff, uint32(len(cbytes)))
+		cbytes = append(cbytes, c.Token...)
+		coff = append(coff, uint32(len(cbytes)))
+		kinds[i] = c.Kind
+	}
+	var nfb C.uint32_t
+	var plen C.uint64_t
+	rc := C.bsg_match_rows_wide_rows(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+		u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u32p(setQueryOff), u32p(setQueries), C.uint32_t(nSets), ct,
+		u32p(hdr), u64p(pairOff), u32p(payload), C.uint64_t(2*total), &plen, u32p(hostRows), C.uint32_t(n), &nfb)
+	if err := g.err(rc); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	return hdr, pairOff, payload[:plen], hostRows[:nfb], nil
+}
+
+// MatchPairRowsList expands one pair of MatchRowsWideRows, whatever its tag, to the ascending set-relative indices of its matching
+// rows (bsg_match_pair_rows_list, host arithmetic): payload = payload[pairOff[p]:pairOff[p+1]], setRows the rows of the pair's set.
+func (g *Context) MatchPairRowsList(hdr uint32, payload []uint32, setRows int) ([]uint32, error) {
+	out := make([]uint32, setRows+1)
+	var cnt C.uint32_t
+	if err := g.err(C.bsg_match_pair_rows_list(C.uint32_t(hdr), u32p(payload), C.uint32_t(setRows), u32p(out), C.uint32_t(setRows), &cnt)); err != nil {
+		return nil, err
+	}
+	return out[:cnt], nil
+}
+
 func (g *Context) matchRowsMany(regex bool, rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
 	setFirstRow []uint32, masks []uint64, tok *Tokenizer) (planes [][]uint64, hostRows []uint32, err error) {
 	n, nq := len(rowOff)-1, len(progOff)-1

@@ -720,8 +720,46 @@ BSG_API int32_t bsg_match_rows_wide(bsg_ctx *ctx, const uint8_t *rows, const uin
  * the total number of words.  NULL, NULL, 0 = the implicit set (n_pairs = n_queries).  BSG_E_INVALID as the call itself. */
 BSG_API int32_t bsg_match_wide_size(const uint32_t *set_first_row, const uint32_t *set_query_off, uint32_t n_sets, uint32_t n_rows,
                                     uint32_t n_queries, uint64_t *out_pair_word_off, uint64_t *out_total_words);
+/* bsg_match_rows_wide with each pair's matches delivered as a tagged row list: what the host goes on with is the rows to
+ * materialise (matchRowBytes is followed at once by materializeRow, query_exec.go:751-755), not a bitmap to search, and a
+ * search's answer is a handful of rows per query while the bit rows cost rows / 8 bytes per pair whatever they hold.  Every argument
+ * up to and including tok, the limits, validation, sharding, chunked upload and the fallback-row rules are bsg_match_rows_wide's.
+ * Pair p of set s (R rows, T = ceil(R / 64)), c of whose rows match (a fallback row never counts), gets the header
+ * out_pair_hdr[p] = tag << 30 | n and, from out_payload[out_pair_off[p]] on (offsets in u32):
+ *   BSG_ROW_NONE   c == 0 (every pair of a set with R == 0)   n = 0, no payload
+ *   BSG_ROW_ALL    c == R, R > 0                              n = 0, no payload
+ *   BSG_ROW_LIST   0 < c < R and c < 2 * T                    n = c, c ascending set-relative row indices i: row set_first_row[s] + i
+ *   BSG_ROW_DENSE  otherwise                                  n = 0, 2 * T u32: word t of the pair's bit row is
+ *                                                             payload[2 * t] | (uint64_t)payload[2 * t + 1] << 32, exactly the
+ *                                                             words bsg_match_rows_wide returns (no alignment is promised)
+ * The tag is a function of (c, R) alone and the result is the same for any number of devices and any chunk size: a set cut
+ * between devices is stitched on the host into the canonical form.  Payloads lie back to back in pair order; out_pair_off
+ * [n_pairs + 1] may be NULL (the host computes it from the headers: a LIST takes n, a DENSE pair 2 * T, the others nothing).  No
+ * result is longer than the bit rows: payload_cap = 2 * bsg_match_wide_size's total words can never be too small.
+ * *out_payload_len = the payload's u32.  payload_cap too small: every header, out_pair_off and *out_payload_len (the length
+ * needed) are written, no payload is, and the call returns BSG_E_INVALID (the message names both numbers).  n_rows == 0 or zero
+ * pairs: BSG_OK, every header NONE, *out_payload_len = 0.  out_payload may be NULL when payload_cap is 0.
+ * On the device three passes follow the evaluation (k_pair_sizes, the k_pair_scan_* offset scan over BSG_MATCH_PAIR_SCAN_WIDTH
+ * pairs per workgroup, k_pair_write); only the headers (4 bytes per pair) and the payload cross PCIe.  Device memory beyond
+ * bsg_match_rows_wide's: the payload scratch is sized at its bound, 8 more bytes per result word, and 20 bytes per pair.
+ * bsg_last_match_ms: the walk, the evaluation and the list passes. */
+#define BSG_MATCH_PAIR_SCAN_WIDTH 256u
+BSG_API int32_t bsg_match_rows_wide_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                         const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                         const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                         const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                         uint32_t n_sets, const bsg_tokenizer *tok,
+                                         uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap,
+                                         uint64_t *out_payload_len, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                         uint32_t *out_n_fallback);
+/* One pair of bsg_match_rows_wide_rows, whatever its tag, as its ascending set-relative row indices (host arithmetic without a
+ * context): payload = out_payload + out_pair_off[p] (not read for NONE / ALL), set_rows = the rows of the pair's set.  *out_n is the
+ * full count; at most cap indices are written.  BSG_E_INVALID: a header and payload that are no pair of such a set (a count the
+ * tag's rule excludes, indices that do not ascend below set_rows, DENSE bits past the last row). */
+BSG_API int32_t bsg_match_pair_rows_list(uint32_t hdr, const uint32_t *payload, uint32_t set_rows, uint32_t *out_rows, uint32_t cap,
+                                         uint32_t *out_n);
 /* Device time of the most recent k_match_rows / k_match_rows_regex / k_match_rows_many / k_match_rows_many_regex dispatch (the
- * slowest device's); after bsg_match_rows_wide, its walk plus its evaluation. */
+ * slowest device's); after bsg_match_rows_wide, its walk plus its evaluation; after bsg_match_rows_wide_rows, its list passes too. */
 BSG_API int32_t bsg_last_match_ms(bsg_ctx *ctx, float *match_ms);
 
 #ifdef __cplusplus

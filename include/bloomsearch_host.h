@@ -98,7 +98,7 @@ typedef struct bse_engine bse_engine;
 /* config_json: {"MaxRowGroupRows":..,"MaxRowGroupBytes":..,"MaxBufferedRows":..,"MaxBufferedBytes":..,
  *               "BloomFalsePositiveRate":..,"PartitionField":"..","DeviceIngest":true|false,"DeviceIngestStream":true|false,
  *               "DeviceMatch":true|false,
- *               "DeviceRegex":true|false,"DeviceMatchWide":true|false,"Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false}};
+ *               "DeviceRegex":true|false,"DeviceMatchWide":true|false,"DeviceMatchWideRows":true|false,"Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false}};
  *               missing keys take the
  *               reference defaults.  DeviceIngest (default false): rows are walked / tokenized / deduplicated /
  *               counted on the GPU at flush and merge time (bloomgpu.h bsg_ingest_*) instead of by indexRow on the
@@ -110,7 +110,9 @@ typedef struct bse_engine bse_engine;
  *               final row test of the surviving blocks runs on the GPU (bsg_match_rows) instead of in the host matcher;
  *               the delivered row set is the same.  DeviceMatchWide (default false, needs DeviceMatch): bse_query_many packs
  *               its queries into groups bounded by 64 distinct conditions (16 regex), not by 64 members, and decides each
- *               group by one bsg_match_rows_wide call; same answers.  DeviceRegex (default false, needs DeviceMatch):
+ *               group by one bsg_match_rows_wide call; same answers.  DeviceMatchWideRows (default false, needs DeviceMatch):
+ *               the same groups, each decided by one bsg_match_rows_wide_rows call whose row lists are consumed as they
+ *               come, no bit row is scanned; same answers.  DeviceRegex (default false, needs DeviceMatch):
  *               a query whose regex patterns all lie in the device's RE2 subset is matched bloom AND regex by one
  *               bsg_match_rows_regex call, the rows it hands back by the host matcher on the same DFAs; other regex queries
  *               keep the std::regex path.  Tokenizer (default: BasicWhitespaceLowerTokenizer): the engine's tokenizer

@@ -21,6 +21,8 @@ KIND_FIELD_REGEX = 3          # row matcher only (bsg_match_rows_regex)
 OP_TERM, OP_AND, OP_OR, OP_TRUE, OP_FALSE = 0, 1, 2, 3, 4
 PROBE_ASYNC, PROBE_TIMED, PROBE_NOFUSE, PROBE_ROWS_PACKED = 1, 2, 4, 8
 INGEST_TRUSTED_JSON = 1
+ROUTE_NONE, ROUTE_STREAM, ROUTE_GATHER = 0, 1, 2      # bsg_lab_last_probe_route (bloomgpu_lab.h)
+GATHER_COST_DEFAULT = 108                             # bsg_set_gather_cost's default (bloomgpu_lab.h)
 
 TERM_DTYPE = np.dtype([("h", "<u8", (4,)), ("kind", "<u4"), ("reserved", "<u4")])
 DESC_DTYPE = np.dtype([("word_off", "<u8"), ("m", "<u8"), ("k", "<u4"), ("reserved", "<u4")])
@@ -72,7 +74,7 @@ def op(opcode: int, arg: int = 0) -> int:
 
 
 # every symbol include/bloomgpu_lab.h declares: lab switches, not part of the drop-in contract
-LAB_EXPORTS = ["bsg_set_lab", "bsg_set_spin_wait", "bsg_set_fuse_limit", "bsg_set_gather_cost", "bsg_lab_query_cpu", "bsg_set_timed_stride"]
+LAB_EXPORTS = ["bsg_set_lab", "bsg_set_spin_wait", "bsg_set_fuse_limit", "bsg_set_gather_cost", "bsg_lab_query_cpu", "bsg_set_timed_stride", "bsg_lab_last_probe_route"]
 
 # every symbol include/bloomgpu.h declares (tests assert the .so exports all of them)
 EXPORTS = [
@@ -114,6 +116,7 @@ def load():
     L.bsg_probe_many_dev.argtypes = [vp, vp, u32, u64, u32, vp]
     L.bsg_set_probe_group.argtypes = [vp, u32]
     L.bsg_set_gather_cost.argtypes = [vp, u32]
+    L.bsg_lab_last_probe_route.argtypes = [vp, C.POINTER(u32)]
     L.bsg_set_fuse_limit.argtypes = [vp, u32]
     L.bsg_set_spin_wait.argtypes = [vp, u32]
     L.bsg_set_ingest_chunk.argtypes = [vp, u64]

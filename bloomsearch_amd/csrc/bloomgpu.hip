@@ -440,7 +440,9 @@ struct bsg_ctx {
     uint64_t timed_counter = 0;
     uint32_t group_limit = 1024;   // arenas one probe dispatch may cover (bsg_set_probe_group; beyond kMaxGroupArenas the records travel in device memory)
     uint32_t solo_ring_wgs = 32;  // a lone bsg_query of more workgroups than this gets its doorbell from a dispatch behind the kernel (bsg_set_lab key 22)
-    uint32_t gather_cost = 256;  // a filter is gathered instead of staged when terms * k * gather_cost < its bytes
+    uint32_t gather_cost = 108;   // bytes a gathered word load is taken to cost: a launch / a filter is gathered when terms * k * gather_cost < its bytes (bsg_set_gather_cost; the value: profiles/probe_gather_lab.txt)
+    uint32_t gather_kernel = 1;  // 0 (bsg_set_lab key 26): a launch never takes k_probe_gather, only the per-block gathered path inside k_probe_terms
+    std::atomic<uint32_t> last_probe_route{0};   // route of the last k_probe_terms(_many) / k_probe_gather dispatch (bsg_lab_last_probe_route)
     bsg::FpKey fp_key{};         // secret key of the entries' fingerprints (drawn at bsg_open; never leaves the process)
     std::vector<uint8_t> peer;   // [i * nd + j]: 1 = device i reaches device j's memory directly (xGMI peer access enabled, or the same device)
     std::atomic<uint64_t> peer_warned{0};   // pairs (bit i * 8 + j, contexts of <= 8 devices) whose staged copies were announced

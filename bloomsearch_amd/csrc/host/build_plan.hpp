@@ -49,12 +49,16 @@ struct ShardStats {
     uint64_t fixed_m[3] = {0, 0, 0};    // common m if all present filters share geometry, else 0
     uint32_t fixed_k[3] = {0, 0, 0};
     bool geometry_uniform[3] = {true, true, true};
+    uint32_t max_k[3] = {0, 0, 0};      // largest k of the present filters: the gather / stream decision of a probe launch (probe_plan.hpp)
+    uint64_t sum_unstaged_words[3] = {0, 0, 0};   // the part of sum_words in filters beyond the LDS budget (never streamed: gathered per block)
     void add_filter(uint32_t c, uint64_t m, uint32_t k)
     {
         if (m == 0) return;
         const uint64_t nw = filter_words(m);
         sum_words[c] += nw;
+        max_k[c] = std::max(max_k[c], k);
         if (nw <= kLdsCapWords) max_staged_words[c] = std::max(max_staged_words[c], nw);
+        else sum_unstaged_words[c] += nw;
         if (fixed_m[c] == 0 && geometry_uniform[c]) { fixed_m[c] = m; fixed_k[c] = k; }
         else if (fixed_m[c] != m || fixed_k[c] != k) geometry_uniform[c] = false;
     }

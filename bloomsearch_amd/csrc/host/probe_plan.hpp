@@ -5,6 +5,7 @@
 // callable i -> blocks (the library reads them out of its arenas in place, the test out of a vector).
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -80,6 +81,54 @@ inline std::vector<uint64_t> group_offsets(const std::vector<G> &groups, const u
     }
     if (!out_off) goff[groups.size()] = total;
     return goff;
+}
+
+// Gather or stream (the few-term probe of a launch group).  A filter kind of the group is cheaper to GATHER — terms x k word loads per
+// block, each costing `gather_cost` bytes of memory traffic — than to stream when
+//     terms x k x gather_cost x n_blocks  <  sum_words x 8          (strictly: equality streams)
+// with sum_words the u64 words of that kind's filters over the group's blocks and k the largest k among them.  The whole launch takes
+// the gather kernel only when EVERY referenced kind satisfies it and the batch is a few-term batch (the many-term kernels compact
+// their survivors in LDS: there is no gathered form of them).  A kind whose filters are all nil (sum_words 0) never satisfies it, nor
+// does a group without blocks; cost 0 gathers whatever has bytes.
+// Filters beyond the LDS budget (unstaged_words) are never streamed: k_probe_terms gathers them per block already, the rule's bytes
+// are not what the launch would otherwise move, and measured (profiles/probe_gather_lab.txt, big_filters geometry) the gather kernel
+// is a draw up to 29 terms and 1-3 us behind from 48 — a launch that holds one keeps the streaming kernels unless the cost is 0.
+// (unstaged_words counts by the library's fixed staging cap, bsh::kLdsCapWords.  A launch's own cap is a little lower — the LDS
+// budget minus its verdict words and wave queues — so a filter between the two is gathered per block by k_probe_terms and still
+// counts as staged here: the byte rule then decides for it as for any other filter.)
+// The left side is formed in 128 bits and saturates: terms, k and cost are 32-bit and n_blocks is 64-bit, so the plain product can
+// pass 2^64 (and, for arguments no launch has, 2^128).
+struct GatherKind {
+    uint64_t sum_words;        // u64 words of this kind's filters over every block of the group
+    uint64_t unstaged_words;   // ... of which in filters beyond the LDS budget
+    uint32_t terms;            // distinct terms of the kind in the batch
+    uint32_t max_k;            // largest k of the kind's filters in the group
+};
+inline bool launch_gathers(const GatherKind *kinds, uint32_t n_kinds, uint64_t n_blocks, bool many_terms, uint32_t gather_cost)
+{
+    if (many_terms || n_kinds == 0 || n_blocks == 0) return false;
+    for (uint32_t y = 0; y < n_kinds; ++y) {
+        if (kinds[y].unstaged_words != 0 && gather_cost != 0) return false;
+        constexpr unsigned __int128 kCap = (unsigned __int128)1 << 80;       // far above any byte count (sum_words x 8 < 2^67): saturating there decides the same
+        unsigned __int128 probes = (unsigned __int128)kinds[y].terms * kinds[y].max_k;                       // < 2^64
+        probes = probes > kCap / n_blocks ? kCap : probes * n_blocks;
+        if (!(probes * gather_cost < (unsigned __int128)kinds[y].sum_words * 8)) return false;               // <= 2^112: no overflow
+    }
+    return true;
+}
+
+// Bytes a gathered launch moves for one kind, as the counters show them (an L2 miss fills a 128-byte line, FETCH_SIZE of
+// profiles/probe_gather_lab.txt): a filter of L lines tested at t = terms x k uniformly spread bits has L (1 - exp(-t / L)) of its
+// lines touched in expectation — C2: 275 lines, 290 tests, 179 lines, against 180-188 requests per block measured.  L is the
+// kind's mean over the group's blocks; never more than the filters themselves.  bsg_timing.stream_bytes of a gathered launch.
+inline uint64_t gathered_bytes(const GatherKind &k, uint64_t n_blocks)
+{
+    if (n_blocks == 0 || k.sum_words == 0) return 0;
+    const double lines = (double)k.sum_words * 8.0 / 128.0 / (double)n_blocks;
+    const double tests = (double)k.terms * (double)k.max_k;
+    const double touched = lines * (1.0 - std::exp(-tests / lines)) * 128.0 * (double)n_blocks;
+    const double all = (double)k.sum_words * 8.0;
+    return (uint64_t)(touched < all ? touched : all);
 }
 
 // Tail split (lab key 19, percent): a run of ONE group of n_shards shards is cut into two dispatches' worth, the first n0 shards

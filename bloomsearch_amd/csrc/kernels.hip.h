@@ -927,6 +927,132 @@ __global__ __launch_bounds__(kProbeThreads) void k_probe_terms_many_ext(const Pr
     probe_role<kProbeThreads, false>(a, ar, blockIdx.x, blockIdx.y, lds64);
 }
 
+// ---------------------------------------------------------------------------
+// K1g  probe_gather: the few-term probe for launches whose filters are all cheaper to GATHER than to stream (the host decides for the
+// whole launch: bsh::launch_gathers, host/probe_plan.hpp).  One WAVE per (block, referenced kind): a 512-thread workgroup covers 8
+// consecutive blocks of one arena; no LDS, no barrier, no atomics.  Each lane owns one term of a 64-term word: its four hashes, then
+// the k locations in batches of kGatherBatch — the reductions and the 4-byte loads of a batch are issued back to back before the
+// first word is looked at — read straight from the arena.  The verdict word is the ballot, stored by lane 0 at the address
+// probe_role computes: a workgroup's 8 words are 64 contiguous bytes.
+// The block index is made wave-uniform (readfirstlane), so the descriptor still arrives by scalar loads (load_desc_uniform: a
+// wave-uniform address is all a scalar load needs) and d.m / d.k, the modulo mode and the loop trips live in SGPRs.
+// grid = (ceil(max_blocks / 8), referenced kinds, arenas of the group)
+// ---------------------------------------------------------------------------
+// Measured on MI355X at the headline's launch shape (C2: 29 terms, k = 10, 35 KB filters, 20 arenas of 1 000 blocks per dispatch;
+// tools/probe_gather_lab.py, profiles/probe_gather_lab.txt), against k_probe_terms' 97-98 us streamed and 88-93 us on its per-block
+// gathered path:
+//   one phase, batches of 4                 78.1 us (76.0 .. 80.4)
+//   + non-temporal loads                    92.0 us: a 128-byte line is wanted again by later locations — plain loads
+//   all 10 locations in one batch           92.4 us
+//   + the fp64 modulo                       79.5 us: a draw, the kernel waits on memory — Barrett, as the other few-term kernels
+//   two phases, first phase = batch of 4    70.2 / 70.5 us (69.0 .. 75.9 / 69.2 .. 72.0): 8 us ahead, twice the spread — the default
+//   ... first phase of 2 / 3 / 5            67.9 / 71.4 / 77.4 us: 2 is inside the spread of 4, which stays (kTailBatch's value)
+// An L2 miss fills a 128-byte line (FETCH_SIZE: 180-188 requests per block = the 179 lines 290 bit tests touch, not the 225 sectors):
+// the kernel moves ~0.67 of the streamed bytes at the streaming kernel's own 6.8 TB/s.
+#ifndef BSG_GATHER_BATCH
+#define BSG_GATHER_BATCH 4        // locations whose loads are in flight together per lane, and the length of the first phase (lab: -DBSG_GATHER_BATCH)
+#endif
+#ifndef BSG_GATHER_NT
+#define BSG_GATHER_NT 0           // lab: 1 = non-temporal loads of the filter words
+#endif
+#ifndef BSG_GATHER_EARLY
+#define BSG_GATHER_EARLY 1        // two phases: after the first batch only the lanes still alive load (a term absent from the block dies after ~2
+                                  // locations), and a wave without one stops; lab: 0 = every location of every term
+#endif
+#ifndef BSG_GATHER_FP64
+#define BSG_GATHER_FP64 0         // lab: 1 = the fp64 modulo for 64 <= m <= 2^19
+#endif
+constexpr uint32_t kGatherBatch = BSG_GATHER_BATCH;
+constexpr uint32_t kGatherBlocks = kProbeThreads / kWave;      // blocks per workgroup: one per wave
+
+// one 4-byte word of the filter at `base` (wave-uniform) + a per-lane word index
+template <int MODE>
+__device__ __forceinline__ uint32_t gather_load(const uint64_t *base, uint64_t loc)
+{
+    const uint32_t *p;
+    // below 2^31 bits the byte offset fits 32 bits: the saddr + voffset form, no 64-bit address arithmetic per lane
+    if (MODE != kModBarrett64) p = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(base) + (((uint32_t)loc >> 5) << 2));
+    else                       p = reinterpret_cast<const uint32_t *>(base) + (loc >> 5);
+#if BSG_GATHER_NT
+    return __builtin_nontemporal_load(p);
+#else
+    return *p;
+#endif
+}
+
+template <int MODE>
+__device__ __forceinline__ void gather_block(const ProbeArgs &a, const ProbeDesc &d, const uint64_t *src, uint32_t t0, uint32_t n_real,
+                                             uint32_t n_tw, uint64_t *vout, uint32_t lane)
+{
+    const uint32_t k = d.k;
+    for (uint32_t w = 0; w < n_tw; ++w) {
+        const uint32_t idx = w * 64 + lane;
+        const bool real = idx < n_real;
+        const uint64_t *th = a.th + (t0 + idx);                       // (the padded tail of the last word holds hashes too: Tp is a multiple of 64)
+        const uint64_t h0 = th[0], h1 = th[a.Tp], h2 = th[2ull * a.Tp], h3 = th[3ull * a.Tp];
+        uint32_t alive = 1u;
+        for (uint32_t i0 = 0; i0 < k; i0 += kGatherBatch) {
+#if BSG_GATHER_EARLY
+            if (i0 != 0 && __ballot(alive != 0u && real) == 0) break;
+#endif
+            uint32_t wd[kGatherBatch], sh[kGatherBatch];
+#pragma unroll
+            for (uint32_t v = 0; v < kGatherBatch; ++v) {
+                const uint32_t iv = i0 + v;                           // wave-uniform
+                wd[v] = ~0u; sh[v] = 0u;
+#if BSG_GATHER_EARLY
+                if (iv < k && real && (i0 == 0 || alive != 0u)) {
+#else
+                if (iv < k && real) {                                 // (the padded lanes of a term word load nothing)
+#endif
+                    const uint64_t loc = locate_c<MODE>(d, location(h0, h1, h2, h3, iv));      // always < d.m: the word lies inside the filter
+                    sh[v] = (uint32_t)loc;
+                    wd[v] = gather_load<MODE>(src, loc);
+                }
+            }
+#pragma unroll
+            for (uint32_t v = 0; v < kGatherBatch; ++v) alive &= __builtin_amdgcn_ubfe(wd[v], sh[v], 1u);   // v_bfe_u32: offset from bits [4:0]
+        }
+        const uint64_t verdict = __ballot(alive != 0u || !real);
+        if (lane == 0) vout[(uint64_t)w * 64] = verdict;
+    }
+}
+
+__device__ __forceinline__ void gather_role(const ProbeArgs &a, const ArenaRef &ar, uint32_t y)
+{
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const uint32_t b = blockIdx.x * kGatherBlocks + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);   // wave-uniform, in an SGPR
+    if (b >= ar.n_blocks) return;   // arenas of a group may differ in size; the last workgroup of an arena may be partial
+    ProbeDesc d;
+    static_cast<DevDesc &>(d) = load_desc_uniform(ar.desc + ((uint64_t)b * 3 + a.kind[y]));
+    const uint32_t t0 = a.term_begin[y];
+    const uint32_t n_real = a.term_count[y];
+    const uint32_t n_tw = (n_real + 63) >> 6;
+    uint64_t *vout = a.V + (ar.v_off(a.Wt) + ((uint64_t)(b >> 6) * a.Wt + (t0 >> 6)) * 64 + (b & 63));
+    if (d.m == 0) {  // nil filter: cannot disqualify (query_exec.go:137-151)
+        if (lane == 0) for (uint32_t w = 0; w < n_tw; ++w) vout[(uint64_t)w * 64] = ~0ULL;
+        return;
+    }
+    const uint64_t *src = ar.words + d.word_off;
+    d.f = ModF64{};
+#if BSG_GATHER_FP64
+    if (modf64_ok(d.m)) { d.f = make_modf64(d.m, d.magic); gather_block<kModFp64>(a, d, src, t0, n_real, n_tw, vout, lane); return; }
+#endif
+    if (d.m < (1ull << 31)) gather_block<kModBarrett32>(a, d, src, t0, n_real, n_tw, vout, lane);
+    else                    gather_block<kModBarrett64>(a, d, src, t0, n_real, n_tw, vout, lane);
+}
+
+__global__ __launch_bounds__(kProbeThreads) void k_probe_gather(const ProbeArgs a, const ArenaTable<kMaxGroupArenas> t)
+{
+    gather_role(a, t.ar[blockIdx.z], blockIdx.y);
+}
+// the same kernel for groups whose arena records lie in device memory (separate for the reason given at kMaxExtGroupArenas)
+__global__ __launch_bounds__(kProbeThreads) void k_probe_gather_ext(const ProbeArgs a, const ArenaRef *__restrict__ ext)
+{
+    const ArenaRef ar = load_arena_ref(ext, blockIdx.z);
+    gather_role(a, ar, blockIdx.y);
+}
+
 // (Measured and dropped, twice now: the same kernel with 1 024 threads per block — 16 waves sharing one block's image, 32
 // waves per CU instead of 24 — runs the 4 054-term batch in 28.6 us per 1 000 blocks against 19.0 us: each wave then owns
 // half as many term words, and its fixed per-round costs and queue traffic stay.)

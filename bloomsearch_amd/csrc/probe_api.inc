@@ -446,8 +446,41 @@ int32_t enqueue_terms(bsg_ctx *ctx, Device &d, const Group &g, const BatchDev &b
     if (int32_t rc = group_table(d, g, t, &ext)) return rc;
     d.ext_of_slot[slot] = ext;
     if (B.n_kinds == 0) return BSG_OK;
-    const dim3 grid(g.max_blocks, B.n_kinds, a.n_arenas), wg(bsg::kProbeThreads);
+    const dim3 wg(bsg::kProbeThreads);
     hipEvent_t e0 = ev ? ev->k1s : nullptr, e1 = ev ? ev->k1e : nullptr;
+    // Gather or stream, for the whole launch (bsh::launch_gathers): where every referenced kind's terms x k word loads cost less than
+    // its filters' bytes, one wave per block reads the words it tests straight from the arena (k_probe_gather: no LDS, same verdict
+    // words, same event slots); anything else keeps the streaming kernels and their per-block fallback.
+    bsh::GatherKind gk[3];
+    uint64_t group_blocks = 0;
+    for (const ArenaShard *s : g.shards) group_blocks += s->n_blocks;
+    for (uint32_t y = 0; y < B.n_kinds; ++y) {
+        gk[y] = bsh::GatherKind{0, 0, B.term_count[y], 0};
+        for (const ArenaShard *s : g.shards) {
+            gk[y].sum_words += s->sum_words[B.kind[y]];
+            gk[y].unstaged_words += s->sum_unstaged_words[B.kind[y]];
+            gk[y].max_k = std::max(gk[y].max_k, s->max_k[B.kind[y]]);
+        }
+    }
+    if (ctx->gather_kernel && bsh::launch_gathers(gk, B.n_kinds, group_blocks, B.many_terms, ctx->gather_cost)) {
+        const dim3 ggrid((g.max_blocks + bsg::kGatherBlocks - 1) / bsg::kGatherBlocks, B.n_kinds, a.n_arenas);
+        if (ext) hipExtLaunchKernelGGL(bsg::k_probe_gather_ext, ggrid, wg, 0, d.stream, e0, e1, 0, a, ext);
+        else     hipExtLaunchKernelGGL(bsg::k_probe_gather, ggrid, wg, 0, d.stream, e0, e1, 0, a, t);
+        HIP_TRY(hipGetLastError());
+        ctx->last_probe_route.store(BSG_LAB_ROUTE_GATHER, std::memory_order_relaxed);
+        if (ev) {
+            // bsg_timing's stream_bytes for a gathered launch: not the bitsets (it does not stream them) but the 128-byte lines its bit
+            // tests are expected to touch (bsh::gathered_bytes: what FETCH_SIZE shows) — a roofline fraction formed from it stays one
+            for (uint32_t y = 0; y < B.n_kinds; ++y) {
+                ev->bytes -= gk[y].sum_words * 8;
+                ev->bytes += bsh::gathered_bytes(gk[y], group_blocks);
+            }
+            ev->has_k1 = true;
+        }
+        return BSG_OK;
+    }
+    const dim3 grid(g.max_blocks, B.n_kinds, a.n_arenas);
+    ctx->last_probe_route.store(BSG_LAB_ROUTE_STREAM, std::memory_order_relaxed);
     if (ext && B.many_terms) hipExtLaunchKernelGGL(bsg::k_probe_terms_many_ext, grid, wg, lds, d.stream, e0, e1, 0, a, ext);
     else if (ext)            hipExtLaunchKernelGGL(bsg::k_probe_terms_ext, grid, wg, lds, d.stream, e0, e1, 0, a, ext);
     else if (B.many_terms)   hipExtLaunchKernelGGL(bsg::k_probe_terms_many, grid, wg, lds, d.stream, e0, e1, 0, a, t);
@@ -1099,7 +1132,7 @@ extern "C" int32_t bsg_set_lab(bsg_ctx *ctx, uint32_t key, uint64_t value)
     // 15 (tests) = (linger microseconds << 16) | calls: a collector waits that long, or until that many calls are queued, before it collects;
     // 16 = queries asked of one arena in a cycle from which the arena is streamed once for all of them (default 8, 0 = never); 17 = microseconds a
     // queued caller polls before it sleeps (default 60); 19 = percent of a single-group device-resident run whose evaluation moves to a second
-    // stream beside the rest's probe (0 = off)
+    // stream beside the rest's probe (0 = off); 26 = 0: few-term launches never take k_probe_gather (default 1)
     if (key == 12) { ctx->cmb.mode = (uint32_t)std::min<uint64_t>(value, 2); return BSG_OK; }
     if (key == 13) { ctx->cmb.sync.max_inflight = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(value, 1), 8); return BSG_OK; }
     if (key == 15) { ctx->cmb.linger_us = (uint32_t)std::min<uint64_t>(value >> 16, 1000000); ctx->cmb.linger_calls = (uint32_t)(value & 0xFFFF); return BSG_OK; }
@@ -1110,6 +1143,7 @@ extern "C" int32_t bsg_set_lab(bsg_ctx *ctx, uint32_t key, uint64_t value)
     if (key == 24) { ctx->cmb.part_bytes = std::max<uint64_t>(value, 8); return BSG_OK; }
     if (key == 22) { ctx->solo_ring_wgs = (uint32_t)std::min<uint64_t>(value, 1u << 30); return BSG_OK; }
     if (key == 21) { ctx->cmb.inline_jobs = value ? 1u : 0u; return BSG_OK; }
+    if (key == 26) { ctx->gather_kernel = value ? 1u : 0u; return BSG_OK; }     // 0: launches never take k_probe_gather (tools/probe_gather_lab.py: the per-block gathered path of k_probe_terms on its own)
     if (key == 17) { ctx->cmb.sync.spin_us = (uint32_t)std::min<uint64_t>(value, 1000000); return BSG_OK; }
     return fail(BSG_E_INVALID, "unknown lab key %u", key);
 }
@@ -1139,6 +1173,14 @@ extern "C" int32_t bsg_set_gather_cost(bsg_ctx *ctx, uint32_t bytes_per_probe)
 {
     BSG_ENTER(ctx);
     ctx->gather_cost = bytes_per_probe;
+    return BSG_OK;
+}
+
+extern "C" int32_t bsg_lab_last_probe_route(bsg_ctx *ctx, uint32_t *out_route)
+{
+    BSG_ENTER(ctx);
+    if (!out_route) return fail(BSG_E_INVALID, "null argument");
+    *out_route = ctx->last_probe_route.load(std::memory_order_relaxed);
     return BSG_OK;
 }
 

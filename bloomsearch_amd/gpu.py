@@ -363,6 +363,12 @@ class Context:
     def set_gather_cost(self, bytes_per_probe: int):
         self._check(self.L.bsg_set_gather_cost(self.h, bytes_per_probe))
 
+    def last_probe_route(self) -> int:
+        """_lib.ROUTE_STREAM / ROUTE_GATHER: the kernel family of the last k_probe_terms(_many) / k_probe_gather dispatch (ROUTE_NONE: none yet)."""
+        r = C.c_uint32()
+        self._check(self.L.bsg_lab_last_probe_route(self.h, C.byref(r)))
+        return int(r.value)
+
     def scope(self):
         """An error scope: an alias of this context with its own last-error slot (bsg_scope_open)."""
         h = C.c_void_p()

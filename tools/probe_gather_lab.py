@@ -1,0 +1,174 @@
+"""Lab: a few-term probe launch GATHERED (k_probe_gather: one wave per block reads the words it tests) against STREAMED (k_probe_terms:
+every bitset through LDS) and against the per-block gathered path inside k_probe_terms, at the headline's launch shape: the bench's C2
+arena (1 000 blocks x 10 000 rows, fpr 0.001) and batch, 20 arenas per dispatch over 16 rotating replicas, BSG_PROBE_TIMED.
+
+    python tools/probe_gather_lab.py c2 [launches [routes]] kernel time per launch from the dispatch timestamps, the three routes interleaved
+    python tools/probe_gather_lab.py sweep [launches]     distinct terms per kind {3 .. 128}: gather vs stream, product and big_filters geometry
+    python tools/probe_gather_lab.py pmc ROUTE [launches] launches of ONE route and nothing else (under rocprofv3 --pmc FETCH_SIZE)
+
+ROUTE: stream (bsg_set_gather_cost(1 << 20)), block (cost 0, bsg_set_lab key 26 = 0: k_probe_terms' per-block gathered path), gather (cost 0).
+BSG_LAB_LIB=path loads another build of the library (the -DBSG_GATHER_* variants of csrc/kernels.hip.h).
+The numbers on record and the stop rule they are read by: profiles/probe_gather_lab.txt.
+"""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+from bloomsearch_amd import _lib, query as Q, synth
+if os.environ.get("BSG_LAB_LIB"):
+    _lib.LIB_PATH = os.path.abspath(os.environ["BSG_LAB_LIB"])
+from bloomsearch_amd.arena import plan_blocks
+from bloomsearch_amd.gpu import Context, estimate_parameters
+from benchlib import common as bench
+
+ROUTES = {"stream": (1 << 20, 1, _lib.ROUTE_STREAM), "block": (0, 0, _lib.ROUTE_STREAM), "gather": (0, 1, _lib.ROUTE_GATHER)}
+PER_CALL, R = 20, 16
+PRESENT = [("level", v) for v in synth.LEVELS] + [("service", v) for v in synth.SERVICES] + [("nested.region", "region-%d" % i) for i in range(synth.N_REGIONS)] + \
+          [("nested.az", "az-%d" % i) for i in range(synth.N_AZS)] + [(f, w) for f in ("tags", "message") for w in synth.WORDS]
+
+
+def set_route(ctx, name):
+    cost, kernel, _ = ROUTES[name]
+    ctx.set_gather_cost(cost)
+    ctx.set_lab(26, kernel)
+
+
+def batch_of(ctx, exprs):
+    cb = Q.compile_queries(exprs)
+    ops, poff, kinds = cb.arrays()
+    terms = np.zeros(len(cb.term_strings), dtype=_lib.TERM_DTYPE)
+    terms["h"] = ctx.hash_strings(cb.term_strings)
+    terms["kind"] = kinds
+    return ctx.batch_create(terms, ops, poff), len(exprs), len(terms)
+
+
+def c2_arenas(ctx):
+    """the bench's arena, R replicas.  BSG_LAB_CACHE=dir keeps the built words between runs of this script (generation is most of a run)."""
+    B, rows = 1000, 10000
+    cache = os.environ.get("BSG_LAB_CACHE")
+    files = [os.path.join(cache, "c2_%s.npy" % n) for n in ("words", "desc")] if cache else []
+    if cache and all(os.path.exists(f) for f in files):
+        words, desc = np.load(files[0]), np.load(files[1])
+    else:
+        plan = plan_blocks(bench.generate_blocks(np.arange(B, dtype=np.int64), rows, 0xB100F5EA4C4, 16), 0.001)
+        words, desc = ctx.build(plan.blob, plan.off, plan.fstart, plan.desc, plan.n_words), plan.desc
+        if cache:
+            os.makedirs(cache, exist_ok=True)
+            np.save(files[0], words)
+            np.save(files[1], desc)
+    return [ctx.arena_load(words, desc) for _ in range(R)], B
+
+
+def big_arenas(ctx):
+    """benchlib.legs.big_filter_leg's geometry: 64 blocks x one 1.04 MB token filter, 4 replicas."""
+    n_blocks, per_block = 64, 580_000
+    m, k = estimate_parameters(per_block, 0.001)
+    stride = ((m + 63) // 64 + 15) // 16 * 16
+    toks = np.random.default_rng(20260927).integers(1, 1 << 62, size=n_blocks * per_block, dtype=np.uint64)
+    off = (np.arange(n_blocks * per_block + 1, dtype=np.uint64) * 8).astype(np.uint32)
+    desc = np.zeros(n_blocks * 3, dtype=_lib.DESC_DTYPE)
+    fstart = [0]
+    for b in range(n_blocks):
+        fstart.append(b * per_block)
+        desc[b * 3 + 1] = (b * stride, m, k, 0)
+        fstart += [(b + 1) * per_block, (b + 1) * per_block]
+    words = ctx.build(toks.view(np.uint8), off, np.asarray(fstart, dtype=np.uint32), desc, n_blocks * stride)
+    return [ctx.arena_load(words, desc) for _ in range(4)], n_blocks
+
+
+def time_routes(ctx, arenas, bid, per_call, routes, launches, warm=3):
+    """-> {route: [kernel us per launch]}: the routes take turns launch by launch, each launch on the next replicas in rotation."""
+    flags = _lib.PROBE_TIMED | _lib.PROBE_ASYNC | _lib.PROBE_NOFUSE
+    out = {r: [] for r in routes}
+    step = 0
+    for i in range(warm + launches):
+        for r in routes:
+            set_route(ctx, r)
+            ids = np.ascontiguousarray([arenas[(step + j) % len(arenas)] for j in range(per_call)], dtype=np.uint64)
+            step += per_call
+            ctx.probe_many(ids, bid, flags)
+            ctx.sync()
+            tm = ctx.timing_read(reset=True)
+            assert ctx.last_probe_route() == ROUTES[r][2], (r, ctx.last_probe_route())
+            if i >= warm:
+                out[r].append(tm.ms_terms_kernel / max(tm.n_probes, 1) * 1e3)
+    return out
+
+
+def fmt(v):
+    return "median %7.1f us  (min %7.1f, max %7.1f, spread %5.1f, n = %d)" % (float(np.median(v)), min(v), max(v), max(v) - min(v), len(v))
+
+
+def same_results(ctx, arenas, bid, nq, n_blocks, routes):
+    ref = None
+    for r in routes:
+        set_route(ctx, r)
+        got = ctx.probe_many(arenas[:2], bid, _lib.PROBE_NOFUSE, nq, [n_blocks] * 2)
+        if ref is None:
+            ref = got
+        assert all(np.array_equal(a, b) for a, b in zip(got, ref)), "route %s differs" % r
+
+
+def main():
+    mode = sys.argv[1] if len(sys.argv) > 1 else "c2"
+    print("library %s" % _lib.LIB_PATH, flush=True)
+    bench.start_pool(16)         # the synthetic generator's workers: forked before the HIP runtime exists here
+    ctx = Context((0,))
+    ctx.set_lab(3, 0)            # no one-dispatch path: every launch goes through k_probe_terms / k_probe_gather
+    ctx.set_timed_stride(1)
+    if mode == "c2":
+        launches = int(sys.argv[2]) if len(sys.argv) > 2 else 24
+        arenas, B = c2_arenas(ctx)
+        bid, nq, nt = batch_of(ctx, synth.make_queries(4096, "c2", seed=1234))
+        routes = sys.argv[3].split(",") if len(sys.argv) > 3 else ["stream", "block", "gather"]
+        same_results(ctx, arenas, bid, nq, B, routes)
+        print("C2: %d queries, %d distinct terms, %d arenas of %d blocks per dispatch, %d replicas; survivors identical on all routes" % (nq, nt, PER_CALL, B, R))
+        for r, v in time_routes(ctx, arenas, bid, PER_CALL, routes, launches).items():
+            print("  %-7s %s" % (r, fmt(v)), flush=True)
+    elif mode == "pmc":
+        route, launches = sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 8
+        arenas, B = c2_arenas(ctx)
+        bid, nq, nt = batch_of(ctx, synth.make_queries(4096, "c2", seed=1234))
+        set_route(ctx, route)
+        for i in range(launches):
+            ctx.probe_many(np.ascontiguousarray([arenas[(i * PER_CALL + j) % R] for j in range(PER_CALL)], dtype=np.uint64), bid, _lib.PROBE_ASYNC | _lib.PROBE_NOFUSE)
+            ctx.sync()
+        print("pmc: %d launches of %d arenas on route %s" % (launches, PER_CALL, route))
+    elif mode == "sweep":
+        launches = int(sys.argv[2]) if len(sys.argv) > 2 else 12
+        for name, (arenas, B), per_call, field in (("product geometry: 1 000-block arenas, 20 per launch", c2_arenas(ctx), PER_CALL, "nested.region"),
+                                                   ("big_filters geometry: 64 blocks x 1.04 MB, 8 arenas per launch", big_arenas(ctx), 8, None)):
+            print(name, flush=True)
+            mixes = [(T, None) for T in (3, 8, 16, 29, 32, 36, 48, 64, 77, 128)]
+            if field and os.environ.get("BSG_LAB_SWEEP") == "near":       # only the rows around the crossover, C2's mix and every term present
+                mixes = [(T, None) for T in (29, 32, 36)] + [(T, T) for T in (29, 32, 36)]
+            elif field:
+                mixes += [(T, T) for T in (29, 32, 36)]                   # ... and every term present in every block: the dearest batch for the two-phase kernel
+            elif os.environ.get("BSG_LAB_SWEEP") == "near":
+                mixes = []
+            for T, forced in mixes:
+                if field:
+                    # C2's mix where the generator allows it: three terms in four occur in every block (the synthetic rows hold 46 such
+                    # field::token values), the rest in none; an absent term dies after the first batch of locations, a present one pays all k
+                    n_present = forced if forced is not None else min(len(PRESENT), (3 * T + 3) // 4)
+                    bid, nq, nt = batch_of(ctx, [Q.FieldToken(f, v) for f, v in PRESENT[:n_present]] + [Q.FieldToken(field, "region-%d" % (100 + i)) for i in range(T - n_present)])
+                else:
+                    bid, nq, nt = batch_of(ctx, [Q.Token("tok-%d" % i) for i in range(T)])
+                assert nt == T
+                same_results(ctx, arenas, bid, nq, B, ["stream", "gather"])
+                t = time_routes(ctx, arenas, bid, per_call, ["stream", "gather"], launches)
+                s, g = float(np.median(t["stream"])), float(np.median(t["gather"]))
+                print("  terms %3d (%2d in every block)   stream %8.1f us (%.1f .. %.1f)   gather %8.1f us (%.1f .. %.1f)   gather / stream %.2f"
+                      % (T, n_present if field else 0, s, min(t["stream"]), max(t["stream"]), g, min(t["gather"]), max(t["gather"]), g / s), flush=True)
+                ctx.batch_free(bid)
+            for a in arenas:
+                ctx.arena_free(a)
+    else:
+        sys.exit(__doc__)
+    bench.stop_pool()
+
+
+if __name__ == "__main__":
+    main()

@@ -12,6 +12,7 @@
 #include "bin_build.hip.h"
 #include "direct.hip.h"
 #include "match.hip.h"
+#include "match_lookup.hip.h"
 #include "host/build_plan.hpp"  // shard layout and stats, the parts of a build call, the route a filter is built by
 #include "host/combiner_sync.hpp"
 #include "host/probe_plan.hpp" // survivor offsets, launch groups, rows layout and the host merge of a probe call
@@ -20,6 +21,7 @@
 #include "host/row_chunks.hpp" // the chunk plan and byte ranges RowUpload copies by
 #include "host/row_groups.hpp" // the order a streaming ingest walks a chunk's rows in: stably grouped by set
 #include "host/wide_plan.hpp"  // bsg_match_rows_wide: pair words, condition masks, part cuts and evaluation items
+#include "host/lookup_plan.hpp"  // bsg_match_rows_lookup: string ids, role records, slot placement, flag words
 #include "host/text.hpp"   // the host walker's Unicode tables: the device defers to the same data
 #include <hip/hip_ext.h>
 

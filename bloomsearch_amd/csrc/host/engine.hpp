@@ -29,6 +29,7 @@
 #include "regex_groups.hpp"
 #include "section_codec.hpp"
 #include "wide_plan.hpp"
+#include "lookup_plan.hpp"
 
 namespace bsh {
 
@@ -74,6 +75,11 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // pair's matching rows come back as a list (or NONE / ALL / its words) and are consumed as such, no bit row is scanned.  Off by
     // default like device_match_wide.
     bool device_match_wide_rows = false;
+    // true (with device_match): query_many's groups WITHOUT a regex condition hold up to 1 024 distinct conditions and are each decided
+    // by ONE bsg_match_rows_lookup call (device_match_lookup_rows: bsg_match_rows_lookup_rows, the lists consumed as under
+    // device_match_wide_rows); a query with a regex condition keeps the 64-condition groups of the wide call.  Off by default.
+    bool device_match_lookup = false;
+    bool device_match_lookup_rows = false;
     // Tokenizer (engine.go:83, "for both indexing and verification"), restricted to the separator family
     // strings.FieldsFunc(lower ? strings.ToLower(v) : v, isSep) (text.hpp Tokenizer): indexRow, the host matcher and the
     // device calls (bsg_ingest_rows_tok / bsg_match_rows_tok) all use it.  Default: BasicWhitespaceLowerTokenizer.
@@ -981,6 +987,7 @@ private:
     // regex conditions, over the batched kernel's table bytes (by regex_groups.hpp's estimate) or would let one leaf lie under
     // more regex conditions than a lane holds (co_active_bound).  on_device[k] stays 0 (the caller decides query k by itself) for
     // a query beyond one of these limits alone or a group the library answers BSG_E_UNSUPPORTED for.
+    // Under DeviceMatchLookup(Rows) a group without a regex condition is bounded by 1 024 conditions and decided by bsg_match_rows_lookup(_rows).
     // Under DeviceMatchWide a group has no member limit (and the storing walker's larger table cap): one bsg_match_rows_wide call per
     // group, each set's CSR query list read from set_wants; its result holds a bit row per (set, listed query) only.
     int32_t match_rows_device_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
@@ -995,7 +1002,9 @@ private:
         const bsg_tokenizer tok = c_tokenizer();
         const size_t n_words = (scan.size() + 63) / 64, n_sets = set_wants.size();
         // DeviceMatchWide: a group is bounded by its table, not by its members; the storing walker's LDS leaves the tables more room
-        const bool wide_rows = cfg_.device_match_wide_rows, wide = cfg_.device_match_wide || wide_rows;
+        // DeviceMatchLookup: the wide call's groups; one without a regex condition may hold 1 024 conditions and takes the lookup call
+        const bool lookup_rows = cfg_.device_match_lookup_rows, lookup = cfg_.device_match_lookup || lookup_rows;
+        const bool wide_rows = cfg_.device_match_wide_rows || lookup_rows, wide = cfg_.device_match_wide || wide_rows || lookup;
         const size_t max_members = wide ? bsh_wide::kMaxQueries : 64;
         const uint32_t table_cap = wide ? bsh_wide::kWideLdsCap : bsh_rxg::kManyLdsCap;
         std::map<std::string, std::pair<uint32_t, uint32_t>> dfa_size;      // pattern -> (states, classes); (0, 0): outside the subset
@@ -1035,7 +1044,8 @@ private:
                 std::vector<std::string_view> rx_fields;
                 for (size_t c = 0; c < kinds.size(); ++c) if (kinds[c] == BSG_KIND_FIELD_REGEX) rx_fields.push_back(fields[c]);
                 for (const auto &kv : added) if (std::get<0>(kv.first) == BSG_KIND_FIELD_REGEX) rx_fields.push_back(std::get<1>(kv.first));
-                const bool fits = mp.kinds.size() <= 64 && index.size() + added.size() <= 64 && n_rx + fresh_rx <= bsh_rxg::kMaxRegexConds &&
+                const size_t cond_cap = lookup && n_rx + fresh_rx == 0 ? bsh_lookup::kMaxConds : 64;
+                const bool fits = mp.kinds.size() <= cond_cap && index.size() + added.size() <= cond_cap && n_rx + fresh_rx <= bsh_rxg::kMaxRegexConds &&
                                   bsh_rxg::align4(rx_table + fresh_bytes) <= table_cap &&
                                   bsh_rxg::co_active_bound(rx_fields) <= bsh_rxg::kManySlots;
                 if (!fits) {
@@ -1065,6 +1075,7 @@ private:
                 cbytes.insert(cbytes.end(), tokens[c].begin(), tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
             }
             if (wide) {
+                const bool by_lookup = lookup && n_rx == 0;
                 // each set's list: the group's members that survived the probe on it, straight from set_wants
                 std::vector<uint32_t> sq_off{0}, sq;
                 for (size_t s = 0; s < n_sets; ++s) {
@@ -1084,7 +1095,7 @@ private:
                     std::vector<uint32_t> hdr(sq.size() + 1), payload(2 * total + 1), ids;
                     std::vector<uint64_t> pair_off(sq.size() + 1);
                     uint64_t payload_len = 0;
-                    const int32_t rc = bsg_match_rows_wide_rows(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
+                    const int32_t rc = (by_lookup ? bsg_match_rows_lookup_rows : bsg_match_rows_wide_rows)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
                                                                 kinds.data(), (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(),
                                                                 (uint32_t)members.size(), set_first.data(), sq_off.data(), sq.data(), (uint32_t)n_sets, &tok,
                                                                 hdr.data(), pair_off.data(), payload.data(), 2 * total, &payload_len, fb.data(),
@@ -1105,7 +1116,7 @@ private:
                     }
                 } else {
                 std::vector<uint64_t> words(total + 1);
-                const int32_t rc = bsg_match_rows_wide(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
+                const int32_t rc = (by_lookup ? bsg_match_rows_lookup : bsg_match_rows_wide)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
                                                        (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(),
                                                        sq_off.data(), sq.data(), (uint32_t)n_sets, &tok, words.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
                 if (rc == BSG_E_UNSUPPORTED) continue;

@@ -376,6 +376,8 @@ int32_t bse_open(const char *config_json, uint64_t len, bsg_ctx *ctx, bse_engine
         if (const JNode *n = dom.get("DeviceRegex")) cfg.device_regex = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchWide")) cfg.device_match_wide = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchWideRows")) cfg.device_match_wide_rows = n->type == JType::True;
+        if (const JNode *n = dom.get("DeviceMatchLookup")) cfg.device_match_lookup = n->type == JType::True;
+        if (const JNode *n = dom.get("DeviceMatchLookupRows")) cfg.device_match_lookup_rows = n->type == JType::True;
         if (const JNode *n = dom.get("Tokenizer")) {
             if (n->type != JType::Null && !tokenizer_from_json(*n, cfg.tokenizer)) return BSE_E_INVALID_CONFIG;
         }

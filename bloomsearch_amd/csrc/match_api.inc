@@ -1,11 +1,14 @@
 // match_api.inc — C-ABI of the device row matcher (included by bloomgpu.hip).  Kernels: match.hip.h; host arithmetic: host/wide_plan.hpp.
-// Every family (bsg_match_rows / _regex / _tok, bsg_match_rows_many / _many_regex, bsg_match_rows_wide) takes ONE path:
+// Every family (bsg_match_rows / _regex / _tok, bsg_match_rows_many / _many_regex, bsg_match_rows_wide, bsg_match_rows_lookup) takes ONE path:
 //   entry point -> MatchCall (the caller's arguments) -> begin_match_call (tokenizer, program and input checks) -> the family's own
 //   checks (kinds, sets) -> lower_programs -> build_rx_blob -> match_fan_out (device cuts, parts, fallback fold) -> match_part per
 //   device (buffers, condition hashing, chunked upload, one walker launch per chunk through launch_walker, results back).
 // What a family adds to a part is its PartMode (PlanePart: bit planes; WidePart: stored flags, k_eval_row_programs, pair words —
 // or, for bsg_match_rows_wide_rows, the same part with the rows policy: three more passes turn the words into tagged row lists on
 // the device, headers and payload come back instead, and match_fan_out's finish step stitches the parts into the call's result).
+// bsg_match_rows_lookup(_rows) is the wide call with another Family and a LookupPlan beside its WidePlan: WidePart then sizes the
+// flags at W words per row, places the lookup tables (host/lookup_plan.hpp) from the hashes the device made, and launches
+// match_lookup.hip.h's walker and evaluator in place of match.hip.h's.
 
 namespace {
 
@@ -45,6 +48,10 @@ static_assert(sizeof(bsh_wide::PairSet) == sizeof(bsg::PairSetDesc) && offsetof(
                   BSG_ROW_LIST == bsg::kPairList && BSG_ROW_DENSE == bsg::kPairDense,
               "host/wide_plan.hpp and bloomgpu.h state the list passes' set table, scan width and tags");
 
+static_assert(bsh_lookup::kMaxConds == BSG_MATCH_LOOKUP_MAX_CONDS && bsg::lookup_lds_bytes(bsh_lookup::kMaxStringSlots, bsh_lookup::kMaxPairSlots) ==
+                                                                      bsg::kMatchLookupLdsBytes,
+              "host/lookup_plan.hpp and bloomgpu.h state the lookup walker's limits");
+
 // One row-matcher call.  The entry points fill the caller's arguments; validation and lowering fill the rest.
 struct MatchCall {
     const uint8_t *rows;
@@ -74,19 +81,21 @@ struct Family {
     const char *call;                      // "%u queries (one <call> match call holds %u)"
     uint32_t max_ops;
     const char *programs_of;               // "the <programs_of> programs hold more than ..."; NULL: the single call's one message
+    uint32_t max_conds = bsg::kMatchMaxConds;
 };
 constexpr Family kSingleFamily{1, "single", bsg::kMatchMaxOps, nullptr};
 constexpr Family kManyFamily{bsg::kMatchManyMaxQueries, "batched", bsg::kMatchManyMaxOps, "batch's"};
 constexpr Family kWideFamily{bsh_wide::kMaxQueries, "wide", bsh_wide::kMaxOps, "call's"};
+constexpr Family kLookupFamily{bsh_wide::kMaxQueries, "lookup", bsh_wide::kMaxOps, "call's", bsh_lookup::kMaxConds};
 
 // What every row-matcher call checks of its rows and conditions (the kinds themselves are the caller's); cond_len / n_bytes out.
 int32_t check_match_inputs(const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows, const uint8_t *cond_bytes, const uint32_t *cond_off,
                            const uint32_t *cond_kinds, uint32_t n_conds, const uint64_t *out_bits, const uint32_t *out_n_fallback,
-                           uint32_t &cond_len, uint64_t &n_bytes)
+                           uint32_t &cond_len, uint64_t &n_bytes, uint32_t max_conds = bsg::kMatchMaxConds)
 {
     if (!out_n_fallback || (n_rows && (!row_off || !out_bits))) return fail(BSG_E_INVALID, "null argument");
     if (n_conds && (!cond_off || !cond_kinds)) return fail(BSG_E_INVALID, "conditions are null");
-    if (n_conds > bsg::kMatchMaxConds) return fail(BSG_E_UNSUPPORTED, "%u conditions (the device matcher holds %u)", n_conds, bsg::kMatchMaxConds);
+    if (n_conds > max_conds) return fail(BSG_E_UNSUPPORTED, "%u conditions (the device matcher holds %u)", n_conds, max_conds);
     for (uint32_t e = 0; e < 2 * n_conds; ++e)
         if (cond_off[e + 1] < cond_off[e]) return fail(BSG_E_INVALID, "cond_off not monotone at %u", e);
     cond_len = n_conds ? cond_off[2 * n_conds] : 0;
@@ -109,14 +118,16 @@ int32_t begin_match_call(MatchCall &mc, const Family &f, const bsg_tokenizer *to
         if (prog_off[q + 1] < prog_off[q]) return fail(BSG_E_INVALID, "prog_off not monotone at %u", q);
     if (n_queries && prog_off[n_queries] > prog_off[0] && !prog_ops) return fail(BSG_E_INVALID, "prog_ops is null");
     return check_match_inputs(mc.rows, mc.row_off, mc.n_rows, mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.out_bits, mc.out_n_fallback,
-                              mc.cond_len, mc.n_bytes);
+                              mc.cond_len, mc.n_bytes, f.max_conds);
 }
 
-// Every query's program lowered over the identity term positions into mc.prog / mc.prog_off: depth <= 64 per query, f.max_ops in all.
-int32_t lower_programs(MatchCall &mc, const Family &f, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries)
+// Every query's program lowered over the identity term positions (the lookup call: over term_pos, where a repeated condition is its
+// first occurrence) into mc.prog / mc.prog_off: depth <= 64 per query, f.max_ops in all.
+int32_t lower_programs(MatchCall &mc, const Family &f, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                       const std::vector<uint32_t> *term_pos = nullptr)
 {
     std::vector<uint32_t> ident(mc.n_conds), one;
-    for (uint32_t c = 0; c < mc.n_conds; ++c) ident[c] = c;
+    for (uint32_t c = 0; c < mc.n_conds; ++c) ident[c] = term_pos ? (*term_pos)[c] : c;
     for (uint32_t q = 0; q < n_queries; ++q) {
         uint32_t depth = 1;
         if (int32_t rc = lower_program(prog_ops + prog_off[q], prog_off[q + 1] - prog_off[q], mc.n_conds, ident, one, depth)) return rc;
@@ -172,6 +183,7 @@ struct PartDev {
     uint32_t r0, n_rows;
     uint32_t *d_prog = nullptr, *d_poff = nullptr;     // the call's lowered programs and (mode.prog_off()) their offsets
     bsg::RxArgs rx{};                                  // the regex blob
+    const uint64_t *d_ch = nullptr;                    // [2 * n_conds][4]: the condition strings' base hashes (k_hash_fp_entries, enqueued)
 };
 
 // bsg_match_rows_many: what a part needs beyond the call.  mc.prog then holds the lowered programs of all queries behind each other
@@ -254,6 +266,7 @@ struct WidePlan {
     std::vector<uint64_t> set_cond_mask;       // [n_sets]
     std::vector<uint64_t> set_word0;           // [n_sets + 1]: the first result word of the set's first pair
     const WideRowsOut *rows = nullptr;         // the rows policy: lists instead of words
+    const bsh_lookup::Plan *lookup = nullptr;  // bsg_match_rows_lookup(_rows): the table's strings, roles and pairs
 };
 
 // The wide call: the storing walk chunk by chunk, then one evaluation launch over the part's items (r0 a set-relative multiple of 64).
@@ -282,8 +295,18 @@ struct WidePart {
     bsg::PairSetDesc *d_psets = nullptr;
     uint32_t *d_phdr = nullptr, *d_payload = nullptr;
     uint64_t *d_psize = nullptr, *d_poffs = nullptr, *d_bsum = nullptr;
+    // the lookup family: W flag words per row (word-major over the part's rows), the tables placed from the device's hashes
+    uint32_t flag_words = 1;
+    std::vector<uint64_t> cond_h, str_h0, pair_tab;
+    std::vector<uint32_t> str_tab;
+    uint32_t *d_lk_str = nullptr;
+    uint64_t *d_lk_pair = nullptr, *d_lk_rec = nullptr;
 
-    const char *tag() const { return wp.rows ? "bsg_match_rows_wide_rows" : "bsg_match_rows_wide"; }
+    const char *tag() const
+    {
+        if (wp.lookup) return wp.rows ? "bsg_match_rows_lookup_rows" : "bsg_match_rows_lookup";
+        return wp.rows ? "bsg_match_rows_wide_rows" : "bsg_match_rows_wide";
+    }
     bool prog_off() const { return true; }
     int32_t plan(uint32_t r0, uint32_t r1)
     {
@@ -298,7 +321,13 @@ struct WidePart {
     }
     int32_t alloc(PartDev &p)
     {
-        HIP_TRY(p.scratch.alloc(&d_sat, (size_t)p.n_rows * 8));
+        if (wp.lookup) {
+            flag_words = bsh_lookup::flag_words(mc.n_conds);
+            HIP_TRY(p.scratch.alloc(&d_lk_str, (size_t)bsh_lookup::table_slots(wp.lookup->n_strings()) * 4));
+            HIP_TRY(p.scratch.alloc(&d_lk_pair, (size_t)bsh_lookup::table_slots((uint32_t)wp.lookup->pairs.size()) * 8));
+            HIP_TRY(p.scratch.alloc(&d_lk_rec, std::max<size_t>(wp.lookup->n_strings(), 1) * 8));
+        }
+        HIP_TRY(p.scratch.alloc(&d_sat, (size_t)p.n_rows * 8 * flag_words));
         HIP_TRY(p.scratch.alloc(&d_state, (size_t)p.n_rows));
         HIP_TRY(p.scratch.alloc(&d_out, std::max<uint64_t>(part_words, 1) * 8));
         HIP_TRY(p.scratch.alloc(&d_sfirst, ((size_t)n_sets + 1) * 4));
@@ -325,10 +354,41 @@ struct WidePart {
         if (n_pairs) HIP_TRY(hipMemcpyAsync(d_pairs, wp.set_queries + pair0, (size_t)n_pairs * 4, hipMemcpyHostToDevice, p.d.stream));
         if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::RowEvalItem), hipMemcpyHostToDevice, p.d.stream));
         if (d_psets) HIP_TRY(hipMemcpyAsync(d_psets, psets.data(), psets.size() * sizeof(bsg::PairSetDesc), hipMemcpyHostToDevice, p.d.stream));
+        if (wp.lookup) return upload_lookup(p);
+        return BSG_OK;
+    }
+    // The lookup tables: word 0 of every role string's base hash comes back from the device (the strings are hashed there, under the
+    // context's key, like every family's), the host places the slots, tables and role records go up; the flags start at zero.
+    int32_t upload_lookup(PartDev &p)
+    {
+        const bsh_lookup::Plan &pl = *wp.lookup;
+        const uint32_t n = pl.n_strings();
+        if (n) {
+            cond_h.resize((size_t)mc.n_conds * 2 * 4);
+            HIP_TRY(hipMemcpyAsync(cond_h.data(), p.d_ch, cond_h.size() * 8, hipMemcpyDeviceToHost, p.d.stream));
+            HIP_TRY(hipStreamSynchronize(p.d.stream));
+        }
+        str_h0.resize(n);
+        for (uint32_t id = 0; id < n; ++id) str_h0[id] = cond_h[(size_t)bsh_lookup::rec_entry(pl.rec[id]) * 4];
+        str_tab = bsh_lookup::place_strings(str_h0.data(), n);
+        pair_tab = bsh_lookup::place_pairs(pl.pairs);
+        HIP_TRY(hipMemcpyAsync(d_lk_str, str_tab.data(), str_tab.size() * 4, hipMemcpyHostToDevice, p.d.stream));
+        HIP_TRY(hipMemcpyAsync(d_lk_pair, pair_tab.data(), pair_tab.size() * 8, hipMemcpyHostToDevice, p.d.stream));
+        if (n) HIP_TRY(hipMemcpyAsync(d_lk_rec, pl.rec.data(), (size_t)n * 8, hipMemcpyHostToDevice, p.d.stream));
+        HIP_TRY(hipMemsetAsync(d_sat, 0, (size_t)p.n_rows * 8 * flag_words, p.d.stream));
         return BSG_OK;
     }
     void launch(PartDev &p, bsg::MatchArgs &a, uint32_t rf, hipEvent_t k0, hipEvent_t k1)
     {
+        if (wp.lookup) {
+            const bsg::MatchLookupArgs lk{d_sfirst, d_spair, d_lk_str, d_lk_pair, d_lk_rec, d_sat + rf, d_state + rf, n_sets, (uint32_t)str_tab.size(),
+                                          (uint32_t)pair_tab.size(), p.n_rows, bsh_lookup::pair_shift((uint32_t)pair_tab.size())};
+            const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads), block(bsg::kIngestThreads);
+            const uint32_t lds = bsg::lookup_lds_bytes(lk.n_str_slots, lk.n_pair_slots);
+            if (mc.tok()) hipExtLaunchKernelGGL(bsg::k_match_rows_lookup_tok, grid, block, lds, p.d.stream, k0, k1, 0, a, lk, *mc.tok());
+            else hipExtLaunchKernelGGL(bsg::k_match_rows_lookup, grid, block, lds, p.d.stream, k0, k1, 0, a, lk);
+            return;
+        }
         launch_walker(kWideWalkers, p.d.stream, k0, k1, a, p.rx, mc.tok(), bsg::MatchWideArgs{d_sfirst, d_smask, d_spair, d_sat + rf, d_state + rf, n_sets});
     }
     int32_t results(PartDev &p, EventList &kev)        // the evaluation between two more events, then the part's words
@@ -338,8 +398,9 @@ struct WidePart {
             HIP_TRY(kev.add(2));
             const bsg::RowEvalArgs e{d_items, d_pairs, p.d_poff, p.d_prog, d_sat, d_state, d_out, (uint32_t)items.size()};
             const uint32_t per_block = bsg::kRowEvalThreads / 64;
-            hipExtLaunchKernelGGL(bsg::k_eval_row_programs, dim3(((uint32_t)items.size() + per_block - 1) / per_block), dim3(bsg::kRowEvalThreads), 0,
-                                  p.d.stream, kev.v[k], kev.v[k + 1], 0, e);
+            const dim3 grid(((uint32_t)items.size() + per_block - 1) / per_block), block(bsg::kRowEvalThreads);
+            if (wp.lookup) hipExtLaunchKernelGGL(bsg::k_eval_row_programs_w, grid, block, 0, p.d.stream, kev.v[k], kev.v[k + 1], 0, bsg::RowEvalWArgs{e, p.n_rows});
+            else hipExtLaunchKernelGGL(bsg::k_eval_row_programs, grid, block, 0, p.d.stream, kev.v[k], kev.v[k + 1], 0, e);
             HIP_TRY(hipGetLastError());
         }
         if (wp.rows) return rows_results(p, kev);
@@ -445,6 +506,7 @@ int32_t match_part(bsg_ctx *ctx, Device &d, const MatchCall &mc, uint32_t r0, ui
     HIP_TRY(hipMemsetAsync(d_nfb, 0, 4, d.stream));
     if (mc.n_rx) HIP_TRY(hipMemcpyAsync(d_rx, mc.rx_blob.data(), mc.rx_blob.size() * 4, hipMemcpyHostToDevice, d.stream));
     p.rx = bsg::RxArgs{d_rx, (uint32_t)mc.rx_blob.size(), mc.n_rx};
+    p.d_ch = d_ch;
     if (int32_t rc = mode.upload(p)) return rc;
     // The rows travel in chunks while the chunk before is being matched (RowUpload).  A surviving block is <= 10 MiB and goes in
     // one piece, in order on the one stream; a scan of many blocks in one call goes in pieces on the copy stream.
@@ -597,15 +659,28 @@ int32_t wide_size_status(bsh_wide::SizeStatus st, uint32_t bad_set, const uint32
 
 int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
                              const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
-                             const bsg_tokenizer *tok_in, const WideRowsOut *rows = nullptr)
+                             const bsg_tokenizer *tok_in, const WideRowsOut *rows = nullptr, bool lookup = false)
 {
+    const Family &fam = lookup ? kLookupFamily : kWideFamily;
     if (rows && (!rows->len || (rows->cap && !rows->payload))) return fail(BSG_E_INVALID, "null argument");
-    if (int32_t rc = begin_match_call(mc, kWideFamily, tok_in, prog_ops, prog_off, n_queries)) return rc;
+    if (int32_t rc = begin_match_call(mc, fam, tok_in, prog_ops, prog_off, n_queries)) return rc;
     const uint32_t n_rows = mc.n_rows;
-    for (uint32_t c = 0; c < mc.n_conds; ++c)
+    for (uint32_t c = 0; c < mc.n_conds; ++c) {
         if (mc.cond_kinds[c] > BSG_KIND_FIELD_REGEX) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
+    }
+    // the lookup call: the table's distinct role strings, their role records and the FieldToken pairs
+    bsh_lookup::Plan lookup_plan;
+    if (lookup) {
+        uint32_t bad = 0;
+        switch (bsh_lookup::build_strings(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, lookup_plan, &bad)) {
+        case bsh_lookup::Status::Ok: break;
+        case bsh_lookup::Status::Kind:          // kinds above FieldRegex were refused as unknown
+            return fail(BSG_E_UNSUPPORTED, "condition %u: FieldRegex conditions are not matched by the lookup call (use bsg_match_rows_wide)", bad);
+        default: return fail(BSG_E_UNSUPPORTED, "%u conditions (the device matcher holds %u)", mc.n_conds, fam.max_conds);
+        }
+    }
     // the sets: the caller's, or one implicit set of all rows with every query
-    WidePlan wp{set_first_row, set_query_off, set_queries, n_sets, n_queries, {}, {}, rows};
+    WidePlan wp{set_first_row, set_query_off, set_queries, n_sets, n_queries, {}, {}, rows, lookup ? &lookup_plan : nullptr};
     std::vector<uint32_t> implicit_first, implicit_off, implicit_queries;
     if (n_sets == 0) {
         if (set_first_row || set_query_off || set_queries) return fail(BSG_E_INVALID, "a set table without its number of sets");
@@ -619,7 +694,7 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
         const bsh_wide::SizeStatus st = bsh_wide::pair_words(set_first_row, set_query_off, n_sets, n_rows, n_queries, nullptr, nullptr, &bad);
         if (int32_t rc = wide_size_status(st, bad, set_first_row, n_sets, n_rows)) return rc;
         if (set_query_off[n_sets] > bsh_wide::kMaxPairs)
-            return fail(BSG_E_UNSUPPORTED, "%u (set, query) pairs (one wide match call holds %u)", set_query_off[n_sets], bsh_wide::kMaxPairs);
+            return fail(BSG_E_UNSUPPORTED, "%u (set, query) pairs (one %s match call holds %u)", set_query_off[n_sets], fam.call, bsh_wide::kMaxPairs);
         if (set_query_off[n_sets] && !set_queries) return fail(BSG_E_INVALID, "set_queries is null");
         for (uint32_t s = 0; s < n_sets; ++s)
             for (uint32_t p = set_query_off[s]; p < set_query_off[s + 1]; ++p) {
@@ -628,8 +703,9 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
                     return fail(BSG_E_INVALID, "set %u: its query list is not strictly ascending at pair %u", s, p);
             }
     }
-    if (int32_t rc = lower_programs(mc, kWideFamily, prog_ops, prog_off, n_queries)) return rc;
-    if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, bsg::kRxWideLdsCap)) return rc;
+    if (int32_t rc = lower_programs(mc, fam, prog_ops, prog_off, n_queries, lookup ? &lookup_plan.canon : nullptr)) return rc;
+    if (!lookup)
+        if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, bsg::kRxWideLdsCap)) return rc;
     const uint32_t n_pairs = wp.set_query_off[wp.n_sets];
     if (rows) {                                // every pair NONE until a part says otherwise (a set without rows lies in no part)
         if (n_pairs && !rows->hdr) return fail(BSG_E_INVALID, "null argument");
@@ -638,7 +714,9 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
         *rows->len = 0;
     }
     if (n_rows == 0 || n_pairs == 0) return BSG_OK;
-    wp.set_cond_mask = bsh_wide::set_cond_masks(bsh_wide::query_cond_masks(prog_ops, prog_off, n_queries, mc.n_conds), wp.set_query_off, wp.set_queries, wp.n_sets);
+    // (the masks open regex conditions' DFAs: the lookup walker has none and reads no mask)
+    if (lookup) wp.set_cond_mask.assign(wp.n_sets, 0);
+    else wp.set_cond_mask = bsh_wide::set_cond_masks(bsh_wide::query_cond_masks(prog_ops, prog_off, n_queries, mc.n_conds), wp.set_query_off, wp.set_queries, wp.n_sets);
     wp.set_word0.assign((size_t)wp.n_sets + 1, 0);
     for (uint32_t s = 0; s < wp.n_sets; ++s)
         wp.set_word0[s + 1] = wp.set_word0[s] + (uint64_t)bsh_wide::tiles_of(wp.set_first_row[s + 1] - wp.set_first_row[s]) *
@@ -718,6 +796,33 @@ int32_t bsg_match_rows_wide_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64
                  fallback_cap, out_n_fallback};
     const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
     return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
+}
+
+int32_t bsg_match_rows_lookup(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                              const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                              const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                              const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
+                              const bsg_tokenizer *tok,
+                              uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, nullptr, true);
+}
+
+int32_t bsg_match_rows_lookup_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                   const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                   const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                   const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
+                                   const bsg_tokenizer *tok,
+                                   uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap, uint64_t *out_payload_len,
+                                   uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
+                 fallback_cap, out_n_fallback};
+    const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out, true);
 }
 
 int32_t bsg_match_pair_rows_list(uint32_t hdr, const uint32_t *payload, uint32_t set_rows, uint32_t *out_rows, uint32_t cap, uint32_t *out_n)

@@ -760,17 +760,25 @@ class Context:
         evaluated on each set, strictly ascending): all None = one implicit set of all rows with every query.
         -> (u64 words, u64 pair_word_off [n_pairs + 1], sorted u32 array of rows the host matcher must decide): pair p's bit row is
         words[pair_word_off[p]: pair_word_off[p + 1]] (wide_pair_bits unpacks it)."""
+        return self._wide_bits(self.L.bsg_match_rows_wide, rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
+
+    def _wide_bits(self, call, rows, batch, set_first_row, set_query_off, set_queries, tokenizer):
+        """bsg_match_rows_wide or bsg_match_rows_lookup (one argument list, one result)"""
         args, _keep, n, pair_word_off, total = self._wide_args(rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
         words = np.zeros(total, dtype=np.uint64)
         fb = np.zeros(max(n, 1), dtype=np.uint32)
         nfb = C.c_uint32()
-        self._check(self.L.bsg_match_rows_wide(*args, words.ctypes.data, _lib._ptr(fb), len(fb), C.byref(nfb)))
+        self._check(call(*args, words.ctypes.data, _lib._ptr(fb), len(fb), C.byref(nfb)))
         return words, pair_word_off, fb[: nfb.value].copy()
 
     def match_rows_wide_rows(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None, payload_cap=None):
         """bsg_match_rows_wide_rows: the arguments of match_rows_wide; payload_cap (u32 of payload the buffer holds) defaults to the
         bound, 2 per result word.  -> (u32 headers [n_pairs], u64 pair_off [n_pairs + 1], u32 payload [its length], sorted u32 array of
         rows the host matcher must decide): pair p is pair_rows_list(hdr[p], payload[pair_off[p]: pair_off[p + 1]], rows of its set)."""
+        return self._wide_rows(self.L.bsg_match_rows_wide_rows, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap)
+
+    def _wide_rows(self, call, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap):
+        """bsg_match_rows_wide_rows or bsg_match_rows_lookup_rows (one argument list, one result)"""
         args, _keep, n, pair_word_off, total = self._wide_args(rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
         n_pairs = len(pair_word_off) - 1
         cap = 2 * total if payload_cap is None else int(payload_cap)
@@ -780,9 +788,17 @@ class Context:
         length = C.c_uint64()
         fb = np.zeros(max(n, 1), dtype=np.uint32)
         nfb = C.c_uint32()
-        self._check(self.L.bsg_match_rows_wide_rows(*args, _lib._ptr(hdr), pair_off.ctypes.data, payload.ctypes.data, cap, C.byref(length),
-                                                    _lib._ptr(fb), len(fb), C.byref(nfb)))
+        self._check(call(*args, _lib._ptr(hdr), pair_off.ctypes.data, payload.ctypes.data, cap, C.byref(length), _lib._ptr(fb), len(fb), C.byref(nfb)))
         return hdr, pair_off, payload[: length.value].copy(), fb[: nfb.value].copy()
+
+    def match_rows_lookup(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None):
+        """bsg_match_rows_lookup: match_rows_wide's arguments and result over a table of up to 1 024 Field / Token / FieldToken
+        conditions (batch: query.CompiledLookupBatch, or anything with kinds / fields / tokens / prog_ops / prog_off)."""
+        return self._wide_bits(self.L.bsg_match_rows_lookup, rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
+
+    def match_rows_lookup_rows(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None, payload_cap=None):
+        """bsg_match_rows_lookup_rows: match_rows_wide_rows' arguments and result over such a table."""
+        return self._wide_rows(self.L.bsg_match_rows_lookup_rows, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap)
 
     def match_wide_size(self, set_first_row, set_query_off, n_rows: int, n_queries: int):
         """bsg_match_wide_size (host arithmetic) -> (u64 pair_word_off [n_pairs + 1], total words); None, None = the implicit set."""

@@ -246,7 +246,7 @@ class CompiledMatcherBatch:
     queries by (kind, field, token) — and one postfix program per query over the table's indices (query q's is
     CompiledMatcher(expr_q)'s with its condition indices remapped).  Raises ValueError beyond the call's limits."""
 
-    MAX_QUERIES, MAX_OPS = MATCH_MANY_MAX_QUERIES, MATCH_MANY_MAX_OPS
+    MAX_QUERIES, MAX_OPS, MAX_CONDS = MATCH_MANY_MAX_QUERIES, MATCH_MANY_MAX_OPS, MATCH_MANY_MAX_CONDS
 
     def __init__(self, expressions):
         expressions = list(expressions)
@@ -271,8 +271,8 @@ class CompiledMatcherBatch:
                     self.fields.append(key[1])
                     self.tokens.append(key[2])
                 remap.append(i)
-            if len(self.kinds) > MATCH_MANY_MAX_CONDS:
-                raise ValueError(f"more than {MATCH_MANY_MAX_CONDS} distinct conditions in one batched match call")
+            if len(self.kinds) > self.MAX_CONDS:
+                raise ValueError(f"more than {self.MAX_CONDS} distinct conditions in one batched match call")
             if self.kinds.count(KIND_FIELD_REGEX) > MATCH_MANY_MAX_REGEX_CONDS:
                 raise ValueError(f"more than {MATCH_MANY_MAX_REGEX_CONDS} distinct regex conditions in one batched match call")
             self.index_maps.append(remap)
@@ -359,3 +359,21 @@ class CompiledWideBatch(CompiledRowQueryBatch):
     @staticmethod
     def _compile(item):
         return CompiledRowQuery(*item) if isinstance(item, tuple) else CompiledMatcher(item)
+
+
+MATCH_LOOKUP_MAX_CONDS = 1024                                                        # bloomgpu.h BSG_MATCH_LOOKUP_MAX_CONDS
+
+
+class CompiledLookupBatch(CompiledWideBatch):
+    """Any number of queries for one bsg_match_rows_lookup call: CompiledWideBatch's table and programs over at most 1 024 distinct
+    Field / Token / FieldToken conditions.  Raises ValueError beyond 2^20 queries, 2^22 lowered ops or 1 024 distinct conditions, and
+    on a FieldRegex condition (batches with one keep CompiledWideBatch)."""
+
+    MAX_CONDS = MATCH_LOOKUP_MAX_CONDS
+
+    @staticmethod
+    def _compile(item):
+        m = CompiledWideBatch._compile(item)
+        if KIND_FIELD_REGEX in m.kinds:
+            raise ValueError("a FieldRegex condition: the lookup match call holds Field, Token and FieldToken conditions only")
+        return m

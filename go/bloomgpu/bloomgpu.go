@@ -1094,6 +1094,25 @@ func (g *Context) MatchRowsManyRegex(rows []byte, rowOff []uint64, conds []Match
 // 46592 bytes of LDS, 1<<20 queries, 1<<22 lowered ops, 1<<24 pairs: IsUnsupported(err).
 func (g *Context) MatchRowsWide(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
 	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (words []uint64, pairWordOff []uint64, hostRows []uint32, err error) {
+	return g.matchRowsWide(false, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
+}
+
+// MatchLookupMaxConds is the number of distinct conditions one MatchRowsLookup / MatchRowsLookupRows call holds
+// (BSG_MATCH_LOOKUP_MAX_CONDS).
+const MatchLookupMaxConds = 1024
+
+// MatchRowsLookup is MatchRowsWide over a table of up to MatchLookupMaxConds distinct KindField / KindToken / KindFieldToken
+// conditions (bsg_match_rows_lookup): every emission is resolved by a hash lookup, the flags are ceil(len(conds)/64) words per row.
+// Arguments and result exactly as MatchRowsWide.  In matchBlock this is the call for a batch of standing searches with about as many
+// distinct tokens as queries: one call where MatchRowsWide needs one per 64 conditions.  A KindFieldRegex condition, more than
+// MatchLookupMaxConds conditions, and MatchRowsWide's other limits: IsUnsupported(err); batches with regex conditions keep MatchRowsWide.
+func (g *Context) MatchRowsLookup(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
+	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (words []uint64, pairWordOff []uint64, hostRows []uint32, err error) {
+	return g.matchRowsWide(true, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
+}
+
+func (g *Context) matchRowsWide(lookup bool, rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
+	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (words []uint64, pairWordOff []uint64, hostRows []uint32, err error) {
 	n, nq := len(rowOff)-1, len(progOff)-1
 	if n <= 0 || nq <= 0 {
 		return nil, nil, nil, nil
@@ -1139,9 +1158,16 @@ func (g *Context) MatchRowsWide(rows []byte, rowOff []uint64, conds []MatchCond,
 		kinds[i] = c.Kind
 	}
 	var nfb C.uint32_t
-	rc := C.bsg_match_rows_wide(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
-		u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u32p(setQueryOff), u32p(setQueries), C.uint32_t(nSets), ct,
-		u64p(words), u32p(hostRows), C.uint32_t(n), &nfb)
+	var rc C.int32_t
+	if lookup {
+		rc = C.bsg_match_rows_lookup(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+			u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u32p(setQueryOff), u32p(setQueries), C.uint32_t(nSets), ct,
+			u64p(words), u32p(hostRows), C.uint32_t(n), &nfb)
+	} else {
+		rc = C.bsg_match_rows_wide(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+			u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u32p(setQueryOff), u32p(setQueries), C.uint32_t(nSets), ct,
+			u64p(words), u32p(hostRows), C.uint32_t(n), &nfb)
+	}
 	if err := g.err(rc); err != nil {
 		return nil, nil, nil, err
 	}
@@ -1163,6 +1189,18 @@ const (
 // MatchPairRowsList expands any of them.  Rows in hostRows count in no pair and must be decided by matchRowBytes for every query
 // listed on their set.  The payload buffer is sized at its bound (2 uint32 per word of the bit rows), so the call cannot fail on space.
 func (g *Context) MatchRowsWideRows(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
+	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (hdr []uint32, pairOff []uint64, payload []uint32, hostRows []uint32, err error) {
+	return g.matchRowsWideRows(false, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
+}
+
+// MatchRowsLookupRows is MatchRowsWideRows over a table of up to MatchLookupMaxConds conditions (bsg_match_rows_lookup_rows): the
+// table and the limits of MatchRowsLookup, the result of MatchRowsWideRows.
+func (g *Context) MatchRowsLookupRows(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
+	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (hdr []uint32, pairOff []uint64, payload []uint32, hostRows []uint32, err error) {
+	return g.matchRowsWideRows(true, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
+}
+
+func (g *Context) matchRowsWideRows(lookup bool, rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
 	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (hdr []uint32, pairOff []uint64, payload []uint32, hostRows []uint32, err error) {
 	n, nq := len(rowOff)-1, len(progOff)-1
 	if n <= 0 || nq <= 0 {
@@ -1211,9 +1249,16 @@ func (g *Context) MatchRowsWideRows(rows []byte, rowOff []uint64, conds []MatchC
 	}
 	var nfb C.uint32_t
 	var plen C.uint64_t
-	rc := C.bsg_match_rows_wide_rows(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
-		u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u32p(setQueryOff), u32p(setQueries), C.uint32_t(nSets), ct,
-		u32p(hdr), u64p(pairOff), u32p(payload), C.uint64_t(2*total), &plen, u32p(hostRows), C.uint32_t(n), &nfb)
+	var rc C.int32_t
+	if lookup {
+		rc = C.bsg_match_rows_lookup_rows(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+			u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u32p(setQueryOff), u32p(setQueries), C.uint32_t(nSets), ct,
+			u32p(hdr), u64p(pairOff), u32p(payload), C.uint64_t(2*total), &plen, u32p(hostRows), C.uint32_t(n), &nfb)
+	} else {
+		rc = C.bsg_match_rows_wide_rows(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+			u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u32p(setQueryOff), u32p(setQueries), C.uint32_t(nSets), ct,
+			u32p(hdr), u64p(pairOff), u32p(payload), C.uint64_t(2*total), &plen, u32p(hostRows), C.uint32_t(n), &nfb)
+	}
 	if err := g.err(rc); err != nil {
 		return nil, nil, nil, nil, err
 	}

@@ -760,6 +760,36 @@ BSG_API int32_t bsg_match_rows_wide_rows(bsg_ctx *ctx, const uint8_t *rows, cons
  * tag's rule excludes, indices that do not ascend below set_rows, DENSE bits past the last row). */
 BSG_API int32_t bsg_match_pair_rows_list(uint32_t hdr, const uint32_t *payload, uint32_t set_rows, uint32_t *out_rows, uint32_t cap,
                                          uint32_t *out_n);
+/* bsg_match_rows_wide / bsg_match_rows_wide_rows over a table of up to BSG_MATCH_LOOKUP_MAX_CONDS distinct conditions: a batch of
+ * standing searches has about as many distinct tokens as queries, and cut into tables of 64 conditions it uploads and walks the same
+ * rows once per table.  The arguments and the results are exactly those of the two wide calls: sets, pairs and the implicit set, tok,
+ * sharding at set-relative multiples of 64 rows, chunked upload, the fallback-row rules, the canonical tagged lists,
+ * bsg_match_wide_size and bsg_match_pair_rows_list.  For a table both hold, the results are equal word for word, header for header,
+ * fallback row for fallback row.
+ * What differs: the walker (k_match_rows_lookup*) resolves every emission by a hash lookup instead of comparing it with every
+ * condition, and keeps ceil(n_conds / 64) flag words per row, which k_eval_row_programs_w evaluates the programs over.
+ * Condition kinds: Field, Token and FieldToken only.  A BSG_KIND_FIELD_REGEX condition is BSG_E_UNSUPPORTED (the message names the
+ * condition): batches with regex conditions keep bsg_match_rows_wide.  A condition repeated in the table is decided once.
+ * Limits (BSG_E_UNSUPPORTED before anything is launched): 1 024 conditions; program depth 64; the query, op, pair and item limits of
+ * bsg_match_rows_wide.  Device memory: 8 * ceil(n_conds / 64) + 1 bytes per row for the flags and the state byte, 4 per lowered op,
+ * query and pair, 8 per result word, at most 48 KiB of tables.
+ * bsg_last_match_ms as after the wide call of the same shape. */
+#define BSG_MATCH_LOOKUP_MAX_CONDS 1024u
+BSG_API int32_t bsg_match_rows_lookup(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                      const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                      const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                      const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                      uint32_t n_sets, const bsg_tokenizer *tok,
+                                      uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                      uint32_t *out_n_fallback);
+BSG_API int32_t bsg_match_rows_lookup_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                           const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                           const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                           const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                           uint32_t n_sets, const bsg_tokenizer *tok,
+                                           uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap,
+                                           uint64_t *out_payload_len, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                           uint32_t *out_n_fallback);
 /* Device time of the most recent k_match_rows / k_match_rows_regex / k_match_rows_many / k_match_rows_many_regex dispatch (the
  * slowest device's); after bsg_match_rows_wide, its walk plus its evaluation; after bsg_match_rows_wide_rows, its list passes too. */
 BSG_API int32_t bsg_last_match_ms(bsg_ctx *ctx, float *match_ms);

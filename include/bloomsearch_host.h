@@ -98,7 +98,8 @@ typedef struct bse_engine bse_engine;
 /* config_json: {"MaxRowGroupRows":..,"MaxRowGroupBytes":..,"MaxBufferedRows":..,"MaxBufferedBytes":..,
  *               "BloomFalsePositiveRate":..,"PartitionField":"..","DeviceIngest":true|false,"DeviceIngestStream":true|false,
  *               "DeviceMatch":true|false,
- *               "DeviceRegex":true|false,"DeviceMatchWide":true|false,"DeviceMatchWideRows":true|false,"Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false}};
+ *               "DeviceRegex":true|false,"DeviceMatchWide":true|false,"DeviceMatchWideRows":true|false,
+ *               "DeviceMatchLookup":true|false,"DeviceMatchLookupRows":true|false,"Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false}};
  *               missing keys take the
  *               reference defaults.  DeviceIngest (default false): rows are walked / tokenized / deduplicated /
  *               counted on the GPU at flush and merge time (bloomgpu.h bsg_ingest_*) instead of by indexRow on the
@@ -112,7 +113,11 @@ typedef struct bse_engine bse_engine;
  *               its queries into groups bounded by 64 distinct conditions (16 regex), not by 64 members, and decides each
  *               group by one bsg_match_rows_wide call; same answers.  DeviceMatchWideRows (default false, needs DeviceMatch):
  *               the same groups, each decided by one bsg_match_rows_wide_rows call whose row lists are consumed as they
- *               come, no bit row is scanned; same answers.  DeviceRegex (default false, needs DeviceMatch):
+ *               come, no bit row is scanned; same answers.  DeviceMatchLookup / DeviceMatchLookupRows (default false, need
+ *               DeviceMatch): the groups of DeviceMatchWide / DeviceMatchWideRows, but a group without a regex condition
+ *               holds up to 1 024 distinct conditions and is decided by one bsg_match_rows_lookup / _lookup_rows call (the
+ *               table arithmetic: csrc/host/lookup_plan.hpp, beside wide_plan.hpp); queries with a regex condition keep
+ *               their 64-condition groups and the wide call; same answers.  DeviceRegex (default false, needs DeviceMatch):
  *               a query whose regex patterns all lie in the device's RE2 subset is matched bloom AND regex by one
  *               bsg_match_rows_regex call, the rows it hands back by the host matcher on the same DFAs; other regex queries
  *               keep the std::regex path.  Tokenizer (default: BasicWhitespaceLowerTokenizer): the engine's tokenizer

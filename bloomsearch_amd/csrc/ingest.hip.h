@@ -949,6 +949,26 @@ __device__ __forceinline__ uint32_t advance(Walker &w, ChunkCursor &cc, const TO
 template <bool EMIT, class RX, class TOK>
 __device__ __forceinline__ uint32_t advance(Walker &w, ChunkCursor &cc, RX &rx, const TOK &tk) { return walker_step<EMIT>(w, cc, rx, tk); }
 
+// ---- what the ingest walkers and every row matcher (match.hip.h, match_lookup.hip.h) share around their emission rounds ----
+// A lane's walker bound to its LDS strip, the lower table, the context's key and whether it keeps the path::word stream.
+__device__ __forceinline__ void walker_bind(Walker &w, ChunkCursor &cc, const uint8_t *rows, lds_u8 *strip, const uint32_t *lower, const FpKey &key,
+                                            bool ft_on)
+{
+    cc.chunks = reinterpret_cast<const uint64_t *>(rows);
+    w.path = strip;
+    w.lower = lower;
+    w.key = key;
+    w.ft_on = ft_on;
+    hs_init(w.ps, w.key); hs_init(w.tok, w.key); hs_init(w.ft, w.key);
+}
+// a row the device walker gives up on: the host decides it (A: IngestArgs or MatchArgs)
+template <class A>
+__device__ __forceinline__ void report_fallback(const A &a, uint32_t row)
+{
+    const uint32_t slot = __hip_atomic_fetch_add(a.n_fallback, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    a.fallback_rows[slot] = row;
+}
+
 // One wave walks a contiguous run of rows_per_wave rows, 64 at a time (lane = row); the four waves of a workgroup take
 // neighbouring runs, so a workgroup stays inside one block (or two) and its dedup cache stays warm: a workgroup that
 // sees each lane's row only once sends ~15 of a row's 32 emission rounds to the table (every entry is new to IT), one
@@ -986,15 +1006,12 @@ __device__ __forceinline__ void ingest_rows_body(const IngestArgs &a, const TOK 
     const uint32_t run_end = (uint32_t)(run_begin + a.rows_per_wave < a.row_end ? run_begin + a.rows_per_wave : a.row_end);
     Walker w;
     ChunkCursor cc;
-    cc.chunks = reinterpret_cast<const uint64_t *>(a.rows);
-    w.path = (lds_u8 *)lds_raw + kCacheWords * 8 + threadIdx.x * kLaneLds;
-    w.lower = a.lower;
-    w.key = a.key;
 #ifdef BSG_LAB_NOFT      // lab only: what the field::token stream costs inside the parse (the sets come out wrong)
-    w.ft_on = false;
+    constexpr bool kFtOn = false;
 #else
-    w.ft_on = true;
+    constexpr bool kFtOn = true;
 #endif
+    walker_bind(w, cc, a.rows, (lds_u8 *)lds_raw + kCacheWords * 8 + threadIdx.x * kLaneLds, a.lower, a.key, kFtOn);
     BSG_PROF_DECL;
     for (uint64_t tile = run_begin; tile < run_end; tile += 64) {
     uint32_t r = (uint32_t)tile + lane;
@@ -1014,7 +1031,7 @@ __device__ __forceinline__ void ingest_rows_body(const IngestArgs &a, const TOK 
     }
     const uint32_t t0 = lo * 3;
     const uint64_t row_begin = live ? a.row_off[r] : 0, row_end = live ? a.row_off[r + 1] : 0;
-    hs_init(w.ps, w.key); hs_init(w.tok, w.key); hs_init(w.ft, w.key);
+    hs_init(w.ps, w.key); hs_init(w.tok, w.key); hs_init(w.ft, w.key);     // every tile: the streams begin afresh
 
     // pass 1: validate.  A row the device walker cannot finish contributes NOTHING here; it goes to the host walker whole.
     BSG_PROF_T(p0);
@@ -1024,10 +1041,7 @@ __device__ __forceinline__ void ingest_rows_body(const IngestArgs &a, const TOK 
         res = live ? R_CONTINUE : R_DONE;
         while (__ballot(res == R_CONTINUE) != 0ull)
             if (res == R_CONTINUE) res = advance<false>(w, cc, tk);
-        if (res == R_FAIL) {
-            const uint32_t slot = __hip_atomic_fetch_add(a.n_fallback, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            a.fallback_rows[slot] = r;
-        }
+        if (res == R_FAIL) report_fallback(a, r);
     }
 
     // pass 2: emit.  Rounds of  (A) every lane parses on until it has a request,  (B) all requests are hashed and
@@ -1093,10 +1107,7 @@ __device__ __forceinline__ void ingest_rows_body(const IngestArgs &a, const TOK 
     // without the validation pass a row is flagged when the emitting walk gives up on it: what it inserted before that
     // is a subset of what the host walker inserts for it PROVIDED the row is valid JSON (the caller's promise).
     // (After a validation pass the emitting walk cannot fail — both run the same automaton — but a row is never dropped.)
-    if (res == R_FAIL) {
-        const uint32_t slot = __hip_atomic_fetch_add(a.n_fallback, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a.fallback_rows[slot] = r;
-    }
+    if (res == R_FAIL) report_fallback(a, r);
     }
     BSG_PROF_FLUSH();
 }

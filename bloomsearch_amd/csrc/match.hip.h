@@ -54,6 +54,7 @@
 #pragma once
 #include <type_traits>
 #include "ingest.hip.h"
+#include "host/row_program.hpp"
 
 namespace bsg {
 
@@ -193,6 +194,17 @@ struct RxLaneT {
 
 typedef RxLaneT<kRxActive> RxLane;
 
+// the set of row g: the first s whose rows end behind it (set_first_row[n_sets] = the number of rows > g)
+__device__ __forceinline__ uint32_t row_set_of(const uint32_t *set_first_row, uint32_t n_sets, uint32_t g)
+{
+    uint32_t lo = 0, hi = n_sets - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (set_first_row[mid + 1] <= g) lo = mid + 1u; else hi = mid;
+    }
+    return lo;
+}
+
 template <bool REGEX, class TOK, bool MANY = false, uint32_t SLOTS = kRxActive, bool WIDE = false>
 __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs &x, const TOK &tk, const MatchManyArgs &m = MatchManyArgs{},
                                                 const MatchWideArgs &wd = MatchWideArgs{})
@@ -221,35 +233,16 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
     const bool live = r < a.n_rows;
     Walker w;
     ChunkCursor cc;
-    cc.chunks = reinterpret_cast<const uint64_t *>(a.rows);
-    w.path = (lds_u8 *)lds_raw + kMatchMaxConds * kMatchCondWords * 8 + kProgBytes + threadIdx.x * kLaneLds;
-    w.lower = a.lower;
-    w.key = a.key;
-    w.ft_on = false;
-    hs_init(w.ps, w.key); hs_init(w.tok, w.key); hs_init(w.ft, w.key);
+    walker_bind(w, cc, a.rows, (lds_u8 *)lds_raw + kMatchMaxConds * kMatchCondWords * 8 + kProgBytes + threadIdx.x * kLaneLds, a.lower, a.key, false);
     uint64_t qmask = ~0ull;      // MANY: the queries evaluated on this lane's row
     if constexpr (MANY) {
-        if (live && m.n_sets) {
-            // the row's set: the first s whose rows end behind it (set_first_row[n_sets] = the number of rows > g)
-            const uint32_t g = a.row_base + r;
-            uint32_t lo = 0, hi = m.n_sets - 1u;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (m.set_first_row[mid + 1] <= g) lo = mid + 1u; else hi = mid;
-            }
-            qmask = m.set_mask[lo];
-        }
+        if (live && m.n_sets) qmask = m.set_mask[row_set_of(m.set_first_row, m.n_sets, a.row_base + r)];
     }
     uint64_t cmask = 0;          // WIDE: the conditions the row's set evaluates; listed: the set has a pair at all
     bool listed = false;
     if constexpr (WIDE) {
         if (live) {
-            const uint32_t g = a.row_base + r;
-            uint32_t lo = 0, hi = wd.n_sets - 1u;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (wd.set_first_row[mid + 1] <= g) lo = mid + 1u; else hi = mid;
-            }
+            const uint32_t lo = row_set_of(wd.set_first_row, wd.n_sets, a.row_base + r);
             cmask = wd.set_cond_mask[lo];
             listed = wd.set_pair_off[lo + 1] != wd.set_pair_off[lo];
         }
@@ -346,10 +339,7 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
             wd.sat[r] = sat;
             wd.state[r] = !walk ? kRowNotWalked : res == R_DONE ? kRowDecided : kRowFallback;
         }
-        if (res == R_FAIL) {
-            const uint32_t slot = __hip_atomic_fetch_add(a.n_fallback, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            a.fallback_rows[slot] = a.row_base + r;
-        }
+        if (res == R_FAIL) report_fallback(a, a.row_base + r);
         return;
     }
     if constexpr (MANY) {
@@ -376,13 +366,13 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
             const uint64_t word = __ballot(decided && verdict);
             if (store) a.out_bits[(uint64_t)q * m.plane_words + (r >> 6)] = word;
         }
-        if (res == R_FAIL) {
-            const uint32_t slot = __hip_atomic_fetch_add(a.n_fallback, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            a.fallback_rows[slot] = a.row_base + r;
-        }
+        if (res == R_FAIL) report_fallback(a, a.row_base + r);
         return;
     }
-    // evalMatcherNode over the flags: one bit of stack per lane and level
+    // evalMatcherNode over the flags: one bit of stack per lane and level.  This loop and the one per query above are
+    // bsh_prog::eval_program (host/row_program.hpp) written out: called as a function from here, the same evaluator re-schedules the
+    // WALK of the eight kernels that end in it (k_match_rows 1.78 ms against 1.77 ms, profiles/walker_refactor.txt).  A change to the
+    // opcode contract goes to the header, its CPU check and these two loops.
     uint64_t stk = 0;
     for (uint32_t j = 0; j < a.n_ops; ++j) {
         const uint32_t op = prog[j], opc = op >> 28;
@@ -398,10 +388,7 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
     if (collided && res == R_DONE) res = R_FAIL;
     const uint64_t word = __ballot(live && res == R_DONE && verdict);
     if ((threadIdx.x & 63u) == 0u && (r & ~63u) < a.n_rows) a.out_bits[r >> 6] = word;
-    if (res == R_FAIL) {
-        const uint32_t slot = __hip_atomic_fetch_add(a.n_fallback, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a.fallback_rows[slot] = a.row_base + r;
-    }
+    if (res == R_FAIL) report_fallback(a, a.row_base + r);
 }
 
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows(const MatchArgs a) { match_rows_body<false>(a, RxArgs{}, TokDefault{}); }
@@ -456,7 +443,10 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_tok(c
 // address space (items, pairs, prog_off and prog are written by the host before the launch, never by a kernel): scalar loads, the
 // loop bounds in SGPRs, no LDS.  Lane 0 stores the pair's word of the tile with a vector store.
 constexpr uint32_t kRowEvalThreads = 256;
-__global__ __launch_bounds__(kRowEvalThreads) void k_eval_row_programs(const RowEvalArgs e)
+// make_term(row, live) gives the lane's TERM reader: how it reads flag c of its row.  The reader is ONE object for all of the item's
+// pairs and goes to eval_program as an lvalue: what it keeps (k_eval_row_programs_w: the last word loaded) lasts from pair to pair.
+template <class MAKE>
+__device__ __forceinline__ void eval_row_programs_body(const RowEvalArgs &e, MAKE &&make_term)
 {
     typedef const __attribute__((address_space(4))) uint64_t c64;
     typedef const __attribute__((address_space(4))) uint32_t c32;
@@ -468,25 +458,21 @@ __global__ __launch_bounds__(kRowEvalThreads) void k_eval_row_programs(const Row
     c32 *pairs = (c32 *)(uintptr_t)e.pairs, *poff = (c32 *)(uintptr_t)e.prog_off, *prog = (c32 *)(uintptr_t)e.prog;
     const uint32_t lane = threadIdx.x & 63u;
     const bool live = lane < n_rows;
-    const uint64_t sat = live ? e.sat[row0 + lane] : 0ull;
+    auto term = make_term(row0 + lane, live);
     const bool decided = live && e.state[row0 + lane] == kRowDecided;
     for (uint32_t p = pair0; p < pair1; ++p) {
-        const uint32_t q = pairs[p], j0 = poff[q], j1 = poff[q + 1];
-        uint64_t stk = 0;
-        for (uint32_t j = j0; j < j1; ++j) {
-            const uint32_t op = prog[j], opc = op >> 28;
-            if (opc == 0u) stk = (stk << 1) | ((sat >> (op & 63u)) & 1ULL);
-            else if (opc == 3u) stk = (stk << 1) | 1ULL;
-            else if (opc == 4u) stk = stk << 1;
-            else {
-                const uint64_t x = stk & 1ULL, y = (stk >> 1) & 1ULL;
-                stk = ((stk >> 2) << 1) | (opc == 1u ? (x & y) : (x | y));
-            }
-        }
-        const bool verdict = j0 == j1 ? true : (stk & 1ULL) != 0;        // nil expression matches every row
+        const uint32_t q = pairs[p];
+        const bool verdict = bsh_prog::eval_program(prog, poff[q], poff[q + 1], term);   // every lane: the program words stay wave-uniform
         const uint64_t word = __ballot(decided && verdict);
         if (lane == 0u) e.out[out0 + (uint64_t)(p - pair0) * stride] = word;
     }
+}
+// the row's one flag word, loaded once
+__global__ __launch_bounds__(kRowEvalThreads) void k_eval_row_programs(const RowEvalArgs e)
+{
+    eval_row_programs_body(e, [&](uint32_t row, bool live) {
+        return [sat = live ? e.sat[row] : 0ull](uint32_t c) { return (sat >> (c & 63u)) & 1ULL; };
+    });
 }
 
 // ---- the part's words as tagged row lists (bsg_match_rows_wide_rows) ----

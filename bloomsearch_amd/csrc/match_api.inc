@@ -10,6 +10,8 @@
 // flags at W words per row, places the lookup tables (host/lookup_plan.hpp) from the hashes the device made, and launches
 // match_lookup.hip.h's walker and evaluator in place of match.hip.h's.
 
+#include <cassert>
+
 namespace {
 
 static_assert(bsh_rxg::kMaxRegexConds == bsg::kRxMaxConds && bsh_rxg::kSingleLdsCap == bsg::kRxLdsCap && bsh_rxg::kManyLdsCap == bsg::kRxManyLdsCap &&
@@ -145,30 +147,31 @@ int32_t lower_programs(MatchCall &mc, const Family &f, const uint32_t *prog_ops,
     return BSG_OK;
 }
 
-// ---- the twelve walkers: (single / many / wide) x (regex) x (tokenizer spec) ----
-// E: the mode's own argument struct (none, MatchManyArgs, MatchWideArgs).  Dynamic LDS: the mode's base plus the regex blob's bytes
-// (a call without regex conditions has no blob).
+// ---- the fourteen walkers: (single / many / wide) x (regex) x (tokenizer spec), lookup x (tokenizer spec) ----
+// E: the mode's own argument struct (none, MatchManyArgs, MatchWideArgs, MatchLookupArgs).  Dynamic LDS: the mode's base (the lookup
+// walkers': what the launch's tables take) plus the regex blob's bytes (a call without regex conditions has no blob).
 template <class... E>
 struct Walkers {
     void (*plain)(bsg::MatchArgs, E...);
     void (*tok)(bsg::MatchArgs, E..., bsg::TokSpec);
     void (*regex)(bsg::MatchArgs, bsg::RxArgs, E...);
     void (*regex_tok)(bsg::MatchArgs, bsg::RxArgs, E..., bsg::TokSpec);
-    uint32_t lds;
 };
-constexpr Walkers<> kSingleWalkers{bsg::k_match_rows, bsg::k_match_rows_tok, bsg::k_match_rows_regex, bsg::k_match_rows_regex_tok, bsg::kMatchLdsBytes};
+constexpr Walkers<> kSingleWalkers{bsg::k_match_rows, bsg::k_match_rows_tok, bsg::k_match_rows_regex, bsg::k_match_rows_regex_tok};
 constexpr Walkers<bsg::MatchManyArgs> kManyWalkers{bsg::k_match_rows_many, bsg::k_match_rows_many_tok, bsg::k_match_rows_many_regex,
-                                                   bsg::k_match_rows_many_regex_tok, bsg::kMatchManyLdsBytes};
+                                                   bsg::k_match_rows_many_regex_tok};
 constexpr Walkers<bsg::MatchWideArgs> kWideWalkers{bsg::k_match_rows_store, bsg::k_match_rows_store_tok, bsg::k_match_rows_store_regex,
-                                                   bsg::k_match_rows_store_regex_tok, bsg::kMatchWideLdsBytes};
+                                                   bsg::k_match_rows_store_regex_tok};
+constexpr Walkers<bsg::MatchLookupArgs> kLookupWalkers{bsg::k_match_rows_lookup, bsg::k_match_rows_lookup_tok, nullptr, nullptr};   // regex: refused by the call
 
 // one chunk's walk: a.n_rows rows, one per lane, between the events k0 and k1
 template <class... E>
-void launch_walker(const Walkers<E...> &w, hipStream_t stream, hipEvent_t k0, hipEvent_t k1, const bsg::MatchArgs &a, const bsg::RxArgs &x,
+void launch_walker(const Walkers<E...> &w, uint32_t lds_base, hipStream_t stream, hipEvent_t k0, hipEvent_t k1, const bsg::MatchArgs &a, const bsg::RxArgs &x,
                    const bsg::TokSpec *tok, const E &...e)
 {
     const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads), block(bsg::kIngestThreads);
-    const uint32_t lds = w.lds + x.n_words * 4;
+    const uint32_t lds = lds_base + x.n_words * 4;
+    assert(!x.n_rx || (w.regex && w.regex_tok));   // a family without regex walkers (lookup) refuses FieldRegex conditions before it gets here
     if (x.n_rx && tok) hipExtLaunchKernelGGL(w.regex_tok, grid, block, lds, stream, k0, k1, 0, a, x, e..., *tok);
     else if (x.n_rx) hipExtLaunchKernelGGL(w.regex, grid, block, lds, stream, k0, k1, 0, a, x, e...);
     else if (tok) hipExtLaunchKernelGGL(w.tok, grid, block, lds, stream, k0, k1, 0, a, e..., *tok);
@@ -238,8 +241,8 @@ struct PlanePart {
     void launch(PartDev &p, bsg::MatchArgs &a, uint32_t rf, hipEvent_t k0, hipEvent_t k1)
     {
         a.prog = p.d_prog; a.n_ops = (uint32_t)mc.prog.size(); a.out_bits = d_bits + rf / 64;
-        if (many) launch_walker(kManyWalkers, p.d.stream, k0, k1, a, p.rx, mc.tok(), bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
-        else launch_walker(kSingleWalkers, p.d.stream, k0, k1, a, p.rx, mc.tok());
+        if (many) launch_walker(kManyWalkers, bsg::kMatchManyLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok(), bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
+        else launch_walker(kSingleWalkers, bsg::kMatchLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok());
     }
     int32_t results(PartDev &p, EventList &)           // this part's words of every plane
     {
@@ -383,13 +386,10 @@ struct WidePart {
         if (wp.lookup) {
             const bsg::MatchLookupArgs lk{d_sfirst, d_spair, d_lk_str, d_lk_pair, d_lk_rec, d_sat + rf, d_state + rf, n_sets, (uint32_t)str_tab.size(),
                                           (uint32_t)pair_tab.size(), p.n_rows, bsh_lookup::pair_shift((uint32_t)pair_tab.size())};
-            const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads), block(bsg::kIngestThreads);
-            const uint32_t lds = bsg::lookup_lds_bytes(lk.n_str_slots, lk.n_pair_slots);
-            if (mc.tok()) hipExtLaunchKernelGGL(bsg::k_match_rows_lookup_tok, grid, block, lds, p.d.stream, k0, k1, 0, a, lk, *mc.tok());
-            else hipExtLaunchKernelGGL(bsg::k_match_rows_lookup, grid, block, lds, p.d.stream, k0, k1, 0, a, lk);
+            launch_walker(kLookupWalkers, bsg::lookup_lds_bytes(lk.n_str_slots, lk.n_pair_slots), p.d.stream, k0, k1, a, p.rx, mc.tok(), lk);
             return;
         }
-        launch_walker(kWideWalkers, p.d.stream, k0, k1, a, p.rx, mc.tok(), bsg::MatchWideArgs{d_sfirst, d_smask, d_spair, d_sat + rf, d_state + rf, n_sets});
+        launch_walker(kWideWalkers, bsg::kMatchWideLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok(), bsg::MatchWideArgs{d_sfirst, d_smask, d_spair, d_sat + rf, d_state + rf, n_sets});
     }
     int32_t results(PartDev &p, EventList &kev)        // the evaluation between two more events, then the part's words
     {

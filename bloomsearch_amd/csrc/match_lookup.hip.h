@@ -67,20 +67,10 @@ __device__ __forceinline__ void match_rows_lookup_body(const MatchArgs &a, const
     const bool live = r < a.n_rows;
     Walker w;
     ChunkCursor cc;
-    cc.chunks = reinterpret_cast<const uint64_t *>(a.rows);
-    w.path = (lds_u8 *)lds_raw + lk.n_str_slots * 4u + lk.n_pair_slots * 8u + threadIdx.x * kLaneLds;
-    w.lower = a.lower;
-    w.key = a.key;
-    w.ft_on = false;
-    hs_init(w.ps, w.key); hs_init(w.tok, w.key); hs_init(w.ft, w.key);
+    walker_bind(w, cc, a.rows, (lds_u8 *)lds_raw + lk.n_str_slots * 4u + lk.n_pair_slots * 8u + threadIdx.x * kLaneLds, a.lower, a.key, false);
     bool listed = false;         // the row's set has a pair at all
     if (live) {
-        const uint32_t g = a.row_base + r;
-        uint32_t lo = 0, hi = lk.n_sets - 1u;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (lk.set_first_row[mid + 1] <= g) lo = mid + 1u; else hi = mid;
-        }
+        const uint32_t lo = row_set_of(lk.set_first_row, lk.n_sets, a.row_base + r);
         listed = lk.set_pair_off[lo + 1] != lk.set_pair_off[lo];
     }
     const bool walk = listed;
@@ -143,10 +133,7 @@ __device__ __forceinline__ void match_rows_lookup_body(const MatchArgs &a, const
     }
     if (collided && res == R_DONE) res = R_FAIL;
     if (live) lk.state[r] = !walk ? kRowNotWalked : res == R_DONE ? kRowDecided : kRowFallback;
-    if (res == R_FAIL) {
-        const uint32_t slot = __hip_atomic_fetch_add(a.n_fallback, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a.fallback_rows[slot] = a.row_base + r;
-    }
+    if (res == R_FAIL) report_fallback(a, a.row_base + r);
 }
 
 // dynamic LDS: lookup_lds_bytes(n_str_slots, n_pair_slots) <= kMatchLookupLdsBytes
@@ -164,47 +151,25 @@ struct RowEvalWArgs {
     RowEvalArgs e;
     uint32_t part_rows;
 };
+// TERM c reads bit c & 63 of word c >> 6 of the lane's row; the last word loaded is kept (the word index is wave-uniform)
+struct SatWords {
+    const uint64_t *my_sat;
+    uint32_t part_rows;
+    bool live;
+    uint32_t cur = ~0u;
+    uint64_t sat = 0;
+    __device__ __forceinline__ uint64_t operator()(uint32_t c)
+    {
+        if ((c >> 6) != cur) {
+            cur = c >> 6;
+            sat = live ? my_sat[(uint64_t)cur * part_rows] : 0ull;
+        }
+        return (sat >> (c & 63u)) & 1ULL;
+    }
+};
 __global__ __launch_bounds__(kRowEvalThreads) void k_eval_row_programs_w(const RowEvalWArgs a)
 {
-    typedef const __attribute__((address_space(4))) uint64_t c64;
-    typedef const __attribute__((address_space(4))) uint32_t c32;
-    const RowEvalArgs &e = a.e;
-    const uint32_t it = blockIdx.x * (kRowEvalThreads / 64u) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (it >= e.n_items) return;
-    c64 *iw = (c64 *)(uintptr_t)(e.items + it);
-    const uint64_t out0 = iw[0], w1 = iw[1], w2 = iw[2], w3 = iw[3];
-    const uint32_t row0 = (uint32_t)w1, n_rows = (uint32_t)(w1 >> 32), pair0 = (uint32_t)w2, pair1 = (uint32_t)(w2 >> 32), stride = (uint32_t)w3;
-    c32 *pairs = (c32 *)(uintptr_t)e.pairs, *poff = (c32 *)(uintptr_t)e.prog_off, *prog = (c32 *)(uintptr_t)e.prog;
-    const uint32_t lane = threadIdx.x & 63u;
-    const bool live = lane < n_rows;
-    const bool decided = live && e.state[row0 + lane] == kRowDecided;
-    const uint64_t *my_sat = e.sat + row0 + lane;
-    uint32_t cur = ~0u;                                                  // the word in `sat` (wave-uniform)
-    uint64_t sat = 0;
-    for (uint32_t p = pair0; p < pair1; ++p) {
-        const uint32_t q = pairs[p], j0 = poff[q], j1 = poff[q + 1];
-        uint64_t stk = 0;
-        for (uint32_t j = j0; j < j1; ++j) {
-            const uint32_t op = prog[j], opc = op >> 28;
-            if (opc == 0u) {
-                const uint32_t c = op & 0x0FFFFFFFu, wi = c >> 6;
-                if (wi != cur) {
-                    cur = wi;
-                    sat = live ? my_sat[(uint64_t)wi * a.part_rows] : 0ull;
-                }
-                stk = (stk << 1) | ((sat >> (c & 63u)) & 1ULL);
-            }
-            else if (opc == 3u) stk = (stk << 1) | 1ULL;
-            else if (opc == 4u) stk = stk << 1;
-            else {
-                const uint64_t x = stk & 1ULL, y = (stk >> 1) & 1ULL;
-                stk = ((stk >> 2) << 1) | (opc == 1u ? (x & y) : (x | y));
-            }
-        }
-        const bool verdict = j0 == j1 ? true : (stk & 1ULL) != 0;        // nil expression matches every row
-        const uint64_t word = __ballot(decided && verdict);
-        if (lane == 0u) e.out[out0 + (uint64_t)(p - pair0) * stride] = word;
-    }
+    eval_row_programs_body(a.e, [&](uint32_t row, bool live) { return SatWords{a.e.sat + row, a.part_rows, live}; });
 }
 
 }  // namespace bsg

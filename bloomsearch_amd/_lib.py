@@ -90,7 +90,7 @@ EXPORTS = [
     "bsg_tokenizer_default", "bsg_ingest_rows", "bsg_ingest_rows_tok", "bsg_ingest_open", "bsg_ingest_add_sets", "bsg_ingest_append_rows", "bsg_ingest_fallback_rows", "bsg_ingest_add_entries", "bsg_ingest_finish", "bsg_ingest_build",
     "bsg_ingest_stats_read", "bsg_ingest_free", "bsg_ingest_build_sections",
     "bsg_sections_size", "bsg_build_sections", "bsg_last_encode_ms",
-    "bsg_match_rows", "bsg_match_rows_regex", "bsg_match_rows_tok", "bsg_match_rows_many", "bsg_match_rows_many_regex", "bsg_match_rows_wide", "bsg_match_wide_size", "bsg_match_rows_wide_rows", "bsg_match_pair_rows_list", "bsg_match_rows_lookup", "bsg_match_rows_lookup_rows", "bsg_last_match_ms", "bsg_pinned_alloc", "bsg_pinned_free", "bsg_host_register", "bsg_host_unregister",
+    "bsg_match_rows", "bsg_match_rows_regex", "bsg_match_rows_tok", "bsg_match_rows_many", "bsg_match_rows_many_regex", "bsg_match_rows_wide", "bsg_match_wide_size", "bsg_match_rows_wide_rows", "bsg_match_pair_rows_list", "bsg_match_rows_lookup", "bsg_match_rows_lookup_rows", "bsg_match_rows_lookup_regex", "bsg_match_rows_lookup_regex_rows", "bsg_last_match_ms", "bsg_pinned_alloc", "bsg_pinned_free", "bsg_host_register", "bsg_host_unregister",
 ]
 
 _lib = None
@@ -197,6 +197,8 @@ def load():
                                            C.POINTER(u64), vp, u32, C.POINTER(u32)]
     L.bsg_match_rows_lookup.argtypes = L.bsg_match_rows_wide.argtypes
     L.bsg_match_rows_lookup_rows.argtypes = L.bsg_match_rows_wide_rows.argtypes
+    L.bsg_match_rows_lookup_regex.argtypes = L.bsg_match_rows_wide.argtypes
+    L.bsg_match_rows_lookup_regex_rows.argtypes = L.bsg_match_rows_wide_rows.argtypes
     L.bsg_match_pair_rows_list.argtypes = [u32, vp, u32, vp, u32, C.POINTER(u32)]
     L.bsg_last_match_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.bsg_pinned_alloc.argtypes = [vp, u64, C.POINTER(vp)]

@@ -80,6 +80,10 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // device_match_wide_rows); a query with a regex condition keeps the 64-condition groups of the wide call.  Off by default.
     bool device_match_lookup = false;
     bool device_match_lookup_rows = false;
+    // with either of the two (and device_regex): a group that holds regex conditions keeps the 1 024-condition bound and is decided by
+    // ONE bsg_match_rows_lookup_regex(_rows) call; it closes at 16 regex conditions, at more than 4 of them on one leaf, and where
+    // their tables pass what the group's strings and pairs (by their upper bounds) leave of the walker's LDS
+    bool device_match_lookup_regex = false;
     // Tokenizer (engine.go:83, "for both indexing and verification"), restricted to the separator family
     // strings.FieldsFunc(lower ? strings.ToLower(v) : v, isSep) (text.hpp Tokenizer): indexRow, the host matcher and the
     // device calls (bsg_ingest_rows_tok / bsg_match_rows_tok) all use it.  Default: BasicWhitespaceLowerTokenizer.
@@ -987,7 +991,9 @@ private:
     // regex conditions, over the batched kernel's table bytes (by regex_groups.hpp's estimate) or would let one leaf lie under
     // more regex conditions than a lane holds (co_active_bound).  on_device[k] stays 0 (the caller decides query k by itself) for
     // a query beyond one of these limits alone or a group the library answers BSG_E_UNSUPPORTED for.
-    // Under DeviceMatchLookup(Rows) a group without a regex condition is bounded by 1 024 conditions and decided by bsg_match_rows_lookup(_rows).
+    // Under DeviceMatchLookup(Rows) a group without a regex condition is bounded by 1 024 conditions and decided by bsg_match_rows_lookup(_rows);
+    // with DeviceMatchLookupRegex one WITH regex conditions is too, decided by bsg_match_rows_lookup_regex(_rows), its regex tables
+    // bounded by bsh_lookup::rx_lds_cap_of over the group's table (strings <= 2 x its other conditions, pairs <= its FieldToken ones).
     // Under DeviceMatchWide a group has no member limit (and the storing walker's larger table cap): one bsg_match_rows_wide call per
     // group, each set's CSR query list read from set_wants; its result holds a bit row per (set, listed query) only.
     int32_t match_rows_device_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
@@ -1005,6 +1011,7 @@ private:
         // DeviceMatchLookup: the wide call's groups; one without a regex condition may hold 1 024 conditions and takes the lookup call
         const bool lookup_rows = cfg_.device_match_lookup_rows, lookup = cfg_.device_match_lookup || lookup_rows;
         const bool wide_rows = cfg_.device_match_wide_rows || lookup_rows, wide = cfg_.device_match_wide || wide_rows || lookup;
+        const bool lookup_regex = lookup && cfg_.device_match_lookup_regex;
         const size_t max_members = wide ? bsh_wide::kMaxQueries : 64;
         const uint32_t table_cap = wide ? bsh_wide::kWideLdsCap : bsh_rxg::kManyLdsCap;
         std::map<std::string, std::pair<uint32_t, uint32_t>> dfa_size;      // pattern -> (states, classes); (0, 0): outside the subset
@@ -1026,6 +1033,7 @@ private:
             std::vector<std::string> fields, tokens;
             std::vector<size_t> members;
             uint32_t n_rx = 0, rx_table = 0;                                 // the group's regex conditions and their table bytes
+            uint32_t n_plain = 0, n_ft = 0;                                  // its other conditions, and the FieldToken ones among them
             for (; k < exprs.size() && members.size() < max_members; ++k) {
                 MatcherProgram mp(exprs[k]);
                 if (regexes[k]) {
@@ -1035,18 +1043,22 @@ private:
                 }
                 // what the query adds: distinct conditions, regex conditions, table bytes, and the fields that may meet on a leaf
                 std::map<std::tuple<uint32_t, std::string, std::string>, uint32_t> added;
-                uint32_t fresh_rx = 0, fresh_bytes = 0;
+                uint32_t fresh_rx = 0, fresh_bytes = 0, fresh_plain = 0, fresh_ft = 0;
                 for (size_t c = 0; c < mp.kinds.size(); ++c) {
                     const auto key = std::make_tuple(mp.kinds[c], mp.fields[c], mp.tokens[c]);
                     if (index.count(key) || !added.emplace(key, 0).second) continue;
                     if (mp.kinds[c] == BSG_KIND_FIELD_REGEX) { ++fresh_rx; fresh_bytes += rx_bytes(mp.fields[c], mp.tokens[c]); }
+                    else { ++fresh_plain; fresh_ft += mp.kinds[c] == BSG_KIND_FIELD_TOKEN ? 1u : 0u; }
                 }
                 std::vector<std::string_view> rx_fields;
                 for (size_t c = 0; c < kinds.size(); ++c) if (kinds[c] == BSG_KIND_FIELD_REGEX) rx_fields.push_back(fields[c]);
                 for (const auto &kv : added) if (std::get<0>(kv.first) == BSG_KIND_FIELD_REGEX) rx_fields.push_back(std::get<1>(kv.first));
-                const size_t cond_cap = lookup && n_rx + fresh_rx == 0 ? bsh_lookup::kMaxConds : 64;
+                const bool rx_group = n_rx + fresh_rx != 0;
+                const size_t cond_cap = lookup && (!rx_group || lookup_regex) ? bsh_lookup::kMaxConds : 64;
+                // the lookup regex call's cap depends on the table: what this group's strings and pairs can take at most
+                const uint32_t group_cap = lookup_regex && rx_group ? bsh_lookup::rx_lds_cap_of(2u * (n_plain + fresh_plain), n_ft + fresh_ft) : table_cap;
                 const bool fits = mp.kinds.size() <= cond_cap && index.size() + added.size() <= cond_cap && n_rx + fresh_rx <= bsh_rxg::kMaxRegexConds &&
-                                  bsh_rxg::align4(rx_table + fresh_bytes) <= table_cap &&
+                                  bsh_rxg::align4(rx_table + fresh_bytes) <= group_cap &&
                                   bsh_rxg::co_active_bound(rx_fields) <= bsh_rxg::kManySlots;
                 if (!fits) {
                     // alone beyond the call: the caller's (the host matcher; per query for a regex query).  Else it opens the next group
@@ -1066,6 +1078,8 @@ private:
                 members.push_back(k);
                 n_rx += fresh_rx;
                 rx_table += fresh_bytes;
+                n_plain += fresh_plain;
+                n_ft += fresh_ft;
             }
             if (members.empty()) continue;
             std::vector<uint8_t> cbytes;
@@ -1075,7 +1089,7 @@ private:
                 cbytes.insert(cbytes.end(), tokens[c].begin(), tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
             }
             if (wide) {
-                const bool by_lookup = lookup && n_rx == 0;
+                const bool by_lookup = lookup && n_rx == 0, by_lookup_regex = lookup_regex && n_rx != 0;
                 // each set's list: the group's members that survived the probe on it, straight from set_wants
                 std::vector<uint32_t> sq_off{0}, sq;
                 for (size_t s = 0; s < n_sets; ++s) {
@@ -1095,7 +1109,7 @@ private:
                     std::vector<uint32_t> hdr(sq.size() + 1), payload(2 * total + 1), ids;
                     std::vector<uint64_t> pair_off(sq.size() + 1);
                     uint64_t payload_len = 0;
-                    const int32_t rc = (by_lookup ? bsg_match_rows_lookup_rows : bsg_match_rows_wide_rows)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
+                    const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex_rows : by_lookup ? bsg_match_rows_lookup_rows : bsg_match_rows_wide_rows)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
                                                                 kinds.data(), (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(),
                                                                 (uint32_t)members.size(), set_first.data(), sq_off.data(), sq.data(), (uint32_t)n_sets, &tok,
                                                                 hdr.data(), pair_off.data(), payload.data(), 2 * total, &payload_len, fb.data(),
@@ -1116,7 +1130,7 @@ private:
                     }
                 } else {
                 std::vector<uint64_t> words(total + 1);
-                const int32_t rc = (by_lookup ? bsg_match_rows_lookup : bsg_match_rows_wide)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
+                const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex : by_lookup ? bsg_match_rows_lookup : bsg_match_rows_wide)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
                                                        (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(),
                                                        sq_off.data(), sq.data(), (uint32_t)n_sets, &tok, words.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
                 if (rc == BSG_E_UNSUPPORTED) continue;

@@ -378,6 +378,7 @@ int32_t bse_open(const char *config_json, uint64_t len, bsg_ctx *ctx, bse_engine
         if (const JNode *n = dom.get("DeviceMatchWideRows")) cfg.device_match_wide_rows = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchLookup")) cfg.device_match_lookup = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchLookupRows")) cfg.device_match_lookup_rows = n->type == JType::True;
+        if (const JNode *n = dom.get("DeviceMatchLookupRegex")) cfg.device_match_lookup_regex = n->type == JType::True;
         if (const JNode *n = dom.get("Tokenizer")) {
             if (n->type != JType::Null && !tokenizer_from_json(*n, cfg.tokenizer)) return BSE_E_INVALID_CONFIG;
         }

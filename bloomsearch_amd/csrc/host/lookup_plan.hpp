@@ -10,6 +10,11 @@
 //                   20-bit tag and a 12-bit id, the full record is read only on a tag hit
 //   place_pairs     the pair table: the same probing keyed on (field id, token id); a slot holds the whole key and the condition
 //   flag_words / flag_index   W u64 of satisfaction flags per row, stored word-major over the part's rows
+// bsg_match_rows_lookup_regex(_rows) adds FieldRegex conditions to such a table (build_strings with regex = true): a regex condition
+// takes no role string and no pair, a repeated one (the same field bytes and pattern bytes) shares its first occurrence's bit, the
+// first occurrences are the table's regex SLOTS (Plan::rx_conds, the order of the blob host/regex_groups.hpp builds of them), and
+//   set_rx_masks    per set of rows one u32: bit j = a program of a query listed on the set references regex slot j
+//   lookup_lds_bytes / rx_lds_cap   what the walker's tables and lanes take in LDS, and what that leaves of 80 KiB for the blob
 // The slot, tag and probe functions are constexpr: the kernels call the same ones.  tests/lookup_plan_check.cpp runs all of it on the
 // CPU (tests/test_match_lookup_plan.py).
 #pragma once
@@ -27,7 +32,8 @@ constexpr uint32_t kNoCond = 0xFFFFu, kNoString = 0xFFFFFFFFu;
 constexpr uint32_t kIdBits = 12, kIdMask = (1u << kIdBits) - 1u;
 constexpr uint32_t kSlotEmpty = 0xFFFFFFFFu;   // id 0xFFF is no string's (ids < kMaxStrings)
 constexpr uint64_t kPairEmpty = ~0ull;         // condition 0xFFFFFFFF is no condition's
-constexpr uint32_t kKindField = 0, kKindToken = 1, kKindFieldToken = 2;
+constexpr uint32_t kKindField = 0, kKindToken = 1, kKindFieldToken = 2, kKindFieldRegex = 3;
+constexpr uint32_t kMaxRegexConds = 16;        // host/regex_groups.hpp kMaxRegexConds: one bit of a set's u32 mask each
 constexpr uint32_t kRoleFtField = 1u, kRoleFtToken = 2u;
 static_assert(kMaxStrings <= kIdMask, "a slot's id field holds every string id and the empty mark");
 
@@ -55,20 +61,29 @@ struct Plan {
     std::vector<uint32_t> string_of;       // [2 * n_conds]: the id of entry e where the condition's kind gives it a role, else kNoString
     std::vector<uint32_t> canon;           // [n_conds]: the first condition with this kind and these role strings
     std::vector<Pair> pairs;               // the distinct FieldToken conditions
+    std::vector<uint32_t> rx_conds;        // the distinct FieldRegex conditions, ascending: regex slot j is condition rx_conds[j]
+    // the regex slot of condition c (of its first occurrence), or kNoCond where c is no regex condition
+    uint32_t rx_slot(uint32_t c) const
+    {
+        for (uint32_t j = 0; j < rx_conds.size(); ++j)
+            if (rx_conds[j] == canon[c]) return j;
+        return kNoCond;
+    }
     uint32_t n_strings() const { return (uint32_t)rec.size(); }
 };
 
 enum class Status { Ok, TooMany, Kind };
 
 // Condition c's strings are entries 2c (field) and 2c + 1 (token) of cond_bytes / cond_off.  Kind: *bad = the first condition that is
-// no Field / Token / FieldToken (the call names it in its refusal).
+// no Field / Token / FieldToken (the call names it in its refusal).  regex: FieldRegex conditions (entry 2c + 1 = the pattern) are
+// part of the table too; how many distinct ones a call holds is the blob's limit (regex_groups.hpp), not checked here.
 inline Status build_strings(const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds, Plan &pl,
-                            uint32_t *bad = nullptr)
+                            uint32_t *bad = nullptr, bool regex = false)
 {
     pl = Plan{};
     if (n_conds > kMaxConds) return Status::TooMany;
     for (uint32_t c = 0; c < n_conds; ++c)
-        if (cond_kinds[c] > kKindFieldToken) {
+        if (cond_kinds[c] > (regex ? kKindFieldRegex : kKindFieldToken)) {
             if (bad) *bad = c;
             return Status::Kind;
         }
@@ -76,6 +91,7 @@ inline Status build_strings(const uint8_t *cond_bytes, const uint32_t *cond_off,
     pl.canon.resize(n_conds);
     std::unordered_map<std::string, uint32_t> ids;
     std::unordered_map<uint32_t, uint32_t> pair_cond;      // fid << 16 | tid -> condition
+    std::unordered_map<std::string, uint32_t> rx_cond;     // field length, field bytes, pattern bytes -> condition
     std::vector<uint32_t> entry, fc, tc, flags;
     auto id_of = [&](uint32_t e) -> uint32_t {
         const std::string s(cond_bytes ? (const char *)cond_bytes + cond_off[e] : "", cond_off[e + 1] - cond_off[e]);
@@ -85,6 +101,15 @@ inline Status build_strings(const uint8_t *cond_bytes, const uint32_t *cond_off,
     };
     for (uint32_t c = 0; c < n_conds; ++c) {
         const uint32_t kind = cond_kinds[c];
+        if (kind == kKindFieldRegex) {                     // no role string, no pair: the walker's DFAs decide it
+            const uint32_t flen = cond_off[2 * c + 1] - cond_off[2 * c];
+            std::string key((const char *)&flen, 4);
+            key.append(cond_bytes ? (const char *)cond_bytes + cond_off[2 * c] : "", cond_off[2 * c + 2] - cond_off[2 * c]);
+            auto it = rx_cond.emplace(std::move(key), c);
+            if (it.second) pl.rx_conds.push_back(c);
+            pl.canon[c] = it.first->second;
+            continue;
+        }
         const uint32_t f = kind != kKindToken ? id_of(2 * c) : kNoString, t = kind != kKindField ? id_of(2 * c + 1) : kNoString;
         if (kind == kKindField) {
             if (fc[f] == kNoCond) fc[f] = c;
@@ -179,6 +204,39 @@ inline uint32_t find_pair(const uint64_t *tab, uint32_t slots, uint32_t fid, uin
         if ((uint32_t)(tab[i] >> 32) == key) return (uint32_t)tab[i];
     return kNoCond;
 }
+
+// ---- the regex conditions of a set ----
+// One u32 per set: bit j = a program of a query listed on the set references regex slot j (public postfix ops: opcode 0 = TERM, the
+// low 28 bits its condition; a repeated condition counts as its first occurrence).  A leaf opens a slot's DFA only on a row whose
+// set's mask selects it: bsh_wide::set_cond_masks over slots instead of conditions (a u64 there holds 64 conditions, no 1 024).
+inline std::vector<uint32_t> set_rx_masks(const Plan &pl, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                          const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets)
+{
+    std::vector<uint32_t> slot(pl.canon.size(), kNoCond), query(n_queries, 0u), sets(n_sets, 0u);
+    for (uint32_t j = 0; j < pl.rx_conds.size() && j < 32u; ++j) slot[pl.rx_conds[j]] = j;
+    for (uint32_t q = 0; q < n_queries; ++q)
+        for (uint32_t i = prog_off[q]; i < prog_off[q + 1]; ++i) {
+            const uint32_t arg = prog_ops[i] & 0x0FFFFFFFu;
+            if ((prog_ops[i] >> 28) == 0u && arg < pl.canon.size() && slot[pl.canon[arg]] != kNoCond) query[q] |= 1u << slot[pl.canon[arg]];
+        }
+    for (uint32_t s = 0; s < n_sets; ++s)
+        for (uint32_t p = set_query_off[s]; p < set_query_off[s + 1]; ++p)
+            if (set_queries[p] < n_queries) sets[s] |= query[set_queries[p]];
+    return sets;
+}
+
+// ---- LDS ----
+// The walker's workgroup: the two tables, then 256 lanes of 116 bytes (ingest.hip.h kIngestThreads * kLaneLds: match_lookup.hip.h
+// asserts the product).  The regex walker copies its table blob behind them and keeps two workgroups per CU (160 KiB of LDS), so the
+// blob's cap is what the tables of THIS call leave of 80 KiB: 52 200 bytes over an empty plain table, 19 456 over one at its limit.
+constexpr uint32_t kLaneBytes = 256u * 116u;
+constexpr uint32_t kWorkgroupLds = 80u * 1024u;
+constexpr uint32_t lookup_lds_bytes(uint32_t n_str_slots, uint32_t n_pair_slots) { return n_str_slots * 4u + n_pair_slots * 8u + kLaneBytes; }
+constexpr uint32_t rx_lds_cap(uint32_t n_str_slots, uint32_t n_pair_slots) { return kWorkgroupLds - lookup_lds_bytes(n_str_slots, n_pair_slots); }
+// ... of a table of n_strings role strings and n_pairs FieldToken pairs (upper bounds give a lower bound of the cap)
+constexpr uint32_t rx_lds_cap_of(uint32_t n_strings, uint32_t n_pairs) { return rx_lds_cap(table_slots(n_strings), table_slots(n_pairs)); }
+static_assert(rx_lds_cap_of(0, 0) == 52200u && rx_lds_cap(kMaxStringSlots, kMaxPairSlots) == 19456u && rx_lds_cap_of(0, 0) < 0x10000u,
+              "the regex blob's cap over the empty and the full table; its 16-bit offsets reach every cap");
 
 // ---- the flags ----
 // W words per row, word-major over the part's rows: the evaluator's 64 lanes load one word of 64 consecutive rows in one piece.  A

@@ -1,6 +1,6 @@
 // regex_groups.hpp — the arithmetic of FieldRegex conditions in a batch of queries, free of any device type: which regex
 // conditions can meet on one leaf (co_active_bound), what a pattern's DFA costs in the kernel's LDS table blob (rx_table_bytes),
-// which queries use a condition (user_masks), and the blob itself (build_blob: layout in match.hip.h).  bsg_match_rows_regex /
+// which queries use a condition (user_masks), and the blob itself (build_blob / build_blob_of: layout in match.hip.h).  bsg_match_rows_regex /
 // bsg_match_rows_tok / bsg_match_rows_many_regex (match_api.inc) build their tables by these functions and the engine mirror
 // (engine.hpp match_rows_device_many) closes its groups by them; tests/regex_groups_check.cpp runs the same code on the CPU
 // (tests/test_regex_groups.py).
@@ -82,13 +82,11 @@ struct BlobResult {
 
 // The LDS table blob of a table's FieldRegex conditions (kind 3), as words.  users: NULL = the single call's blob; else
 // [n_conds] user masks, stored as n_rx u64 behind the header (the batched blob).  Nothing is refused silently: status says why.
-inline BlobResult build_blob(const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds, uint32_t regex_kind,
-                             uint32_t cap, const uint64_t *users, std::vector<uint32_t> &blob)
+// rx: the table's regex conditions, ascending; slot j of the blob is condition rx[j].
+inline BlobResult build_blob_of(const uint8_t *cond_bytes, const uint32_t *cond_off, const std::vector<uint32_t> &rx, uint32_t cap, const uint64_t *users,
+                                std::vector<uint32_t> &blob)
 {
     BlobResult res;
-    std::vector<uint32_t> rx;
-    for (uint32_t c = 0; c < n_conds; ++c)
-        if (cond_kinds[c] == regex_kind) rx.push_back(c);
     const uint32_t n_rx = res.n_rx = (uint32_t)rx.size();
     blob.clear();
     if (rx.empty()) return res;
@@ -128,6 +126,15 @@ inline BlobResult build_blob(const uint8_t *cond_bytes, const uint32_t *cond_off
     blob.resize(bytes.size() / 4);
     memcpy(blob.data(), bytes.data(), bytes.size());
     return res;
+}
+// ... of every condition of kind regex_kind (the lookup call passes build_blob_of its DISTINCT regex conditions instead)
+inline BlobResult build_blob(const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds, uint32_t regex_kind,
+                             uint32_t cap, const uint64_t *users, std::vector<uint32_t> &blob)
+{
+    std::vector<uint32_t> rx;
+    for (uint32_t c = 0; c < n_conds; ++c)
+        if (cond_kinds[c] == regex_kind) rx.push_back(c);
+    return build_blob_of(cond_bytes, cond_off, rx, cap, users, blob);
 }
 
 }  // namespace bsh_rxg

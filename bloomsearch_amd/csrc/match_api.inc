@@ -1,5 +1,5 @@
 // match_api.inc — C-ABI of the device row matcher (included by bloomgpu.hip).  Kernels: match.hip.h; host arithmetic: host/wide_plan.hpp.
-// Every family (bsg_match_rows / _regex / _tok, bsg_match_rows_many / _many_regex, bsg_match_rows_wide, bsg_match_rows_lookup) takes ONE path:
+// Every family (bsg_match_rows / _regex / _tok, bsg_match_rows_many / _many_regex, bsg_match_rows_wide, bsg_match_rows_lookup / _lookup_regex) takes ONE path:
 //   entry point -> MatchCall (the caller's arguments) -> begin_match_call (tokenizer, program and input checks) -> the family's own
 //   checks (kinds, sets) -> lower_programs -> build_rx_blob -> match_fan_out (device cuts, parts, fallback fold) -> match_part per
 //   device (buffers, condition hashing, chunked upload, one walker launch per chunk through launch_walker, results back).
@@ -8,7 +8,9 @@
 // the device, headers and payload come back instead, and match_fan_out's finish step stitches the parts into the call's result).
 // bsg_match_rows_lookup(_rows) is the wide call with another Family and a LookupPlan beside its WidePlan: WidePart then sizes the
 // flags at W words per row, places the lookup tables (host/lookup_plan.hpp) from the hashes the device made, and launches
-// match_lookup.hip.h's walker and evaluator in place of match.hip.h's.
+// match_lookup.hip.h's walker and evaluator in place of match.hip.h's.  bsg_match_rows_lookup_regex(_rows) is that call with FieldRegex
+// conditions allowed in the table: the blob is built over the DISTINCT regex conditions under the cap THIS table's LDS leaves, a u32 of
+// regex slots per set goes where the wide call's condition mask goes, and the regex instances of the lookup walker are launched.
 
 #include <cassert>
 
@@ -22,10 +24,13 @@ static_assert(bsh_rxg::kMaxRegexConds == bsg::kRxMaxConds && bsh_rxg::kSingleLds
 // The LDS table blob of a call's FieldRegex conditions (layout: match.hip.h; built by host/regex_groups.hpp).  BSG_E_UNSUPPORTED,
 // before anything is launched, for a pattern outside the compiler's subset, more than kRxMaxConds of them, or tables over `cap`
 // (kRxLdsCap; kRxManyLdsCap for the batched call, whose blob also holds the conditions' user masks: users [n_conds], else NULL).
+// distinct: the regex conditions the blob is built of (the lookup call: each repeated condition once); NULL = every one of the table.
 int32_t build_rx_blob(const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
-                      std::vector<uint32_t> &blob, uint32_t &n_rx, uint32_t cap = bsg::kRxLdsCap, const uint64_t *users = nullptr)
+                      std::vector<uint32_t> &blob, uint32_t &n_rx, uint32_t cap = bsg::kRxLdsCap, const uint64_t *users = nullptr,
+                      const std::vector<uint32_t> *distinct = nullptr)
 {
-    const bsh_rxg::BlobResult r = bsh_rxg::build_blob(cond_bytes, cond_off, cond_kinds, n_conds, BSG_KIND_FIELD_REGEX, cap, users, blob);
+    const bsh_rxg::BlobResult r = distinct ? bsh_rxg::build_blob_of(cond_bytes, cond_off, *distinct, cap, users, blob)
+                                           : bsh_rxg::build_blob(cond_bytes, cond_off, cond_kinds, n_conds, BSG_KIND_FIELD_REGEX, cap, users, blob);
     n_rx = r.n_rx;
     switch (r.status) {
     case bsh_rxg::BlobStatus::Ok: return BSG_OK;
@@ -89,6 +94,9 @@ constexpr Family kSingleFamily{1, "single", bsg::kMatchMaxOps, nullptr};
 constexpr Family kManyFamily{bsg::kMatchManyMaxQueries, "batched", bsg::kMatchManyMaxOps, "batch's"};
 constexpr Family kWideFamily{bsh_wide::kMaxQueries, "wide", bsh_wide::kMaxOps, "call's"};
 constexpr Family kLookupFamily{bsh_wide::kMaxQueries, "lookup", bsh_wide::kMaxOps, "call's", bsh_lookup::kMaxConds};
+constexpr Family kLookupRegexFamily{bsh_wide::kMaxQueries, "lookup regex", bsh_wide::kMaxOps, "call's", bsh_lookup::kMaxConds};
+// which call match_rows_wide_call serves
+enum class WideKind { Wide, Lookup, LookupRegex };
 
 // What every row-matcher call checks of its rows and conditions (the kinds themselves are the caller's); cond_len / n_bytes out.
 int32_t check_match_inputs(const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows, const uint8_t *cond_bytes, const uint32_t *cond_off,
@@ -147,7 +155,7 @@ int32_t lower_programs(MatchCall &mc, const Family &f, const uint32_t *prog_ops,
     return BSG_OK;
 }
 
-// ---- the fourteen walkers: (single / many / wide) x (regex) x (tokenizer spec), lookup x (tokenizer spec) ----
+// ---- the sixteen walkers: (single / many / wide / lookup) x (regex) x (tokenizer spec) ----
 // E: the mode's own argument struct (none, MatchManyArgs, MatchWideArgs, MatchLookupArgs).  Dynamic LDS: the mode's base (the lookup
 // walkers': what the launch's tables take) plus the regex blob's bytes (a call without regex conditions has no blob).
 template <class... E>
@@ -162,7 +170,8 @@ constexpr Walkers<bsg::MatchManyArgs> kManyWalkers{bsg::k_match_rows_many, bsg::
                                                    bsg::k_match_rows_many_regex_tok};
 constexpr Walkers<bsg::MatchWideArgs> kWideWalkers{bsg::k_match_rows_store, bsg::k_match_rows_store_tok, bsg::k_match_rows_store_regex,
                                                    bsg::k_match_rows_store_regex_tok};
-constexpr Walkers<bsg::MatchLookupArgs> kLookupWalkers{bsg::k_match_rows_lookup, bsg::k_match_rows_lookup_tok, nullptr, nullptr};   // regex: refused by the call
+constexpr Walkers<bsg::MatchLookupArgs> kLookupWalkers{bsg::k_match_rows_lookup, bsg::k_match_rows_lookup_tok, bsg::k_match_rows_lookup_regex,
+                                                       bsg::k_match_rows_lookup_regex_tok};   // regex: bsg_match_rows_lookup_regex(_rows) only
 
 // one chunk's walk: a.n_rows rows, one per lane, between the events k0 and k1
 template <class... E>
@@ -171,7 +180,7 @@ void launch_walker(const Walkers<E...> &w, uint32_t lds_base, hipStream_t stream
 {
     const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads), block(bsg::kIngestThreads);
     const uint32_t lds = lds_base + x.n_words * 4;
-    assert(!x.n_rx || (w.regex && w.regex_tok));   // a family without regex walkers (lookup) refuses FieldRegex conditions before it gets here
+    assert(!x.n_rx || (w.regex && w.regex_tok));   // every family has its regex walkers; a call that takes none refuses FieldRegex conditions before it gets here
     if (x.n_rx && tok) hipExtLaunchKernelGGL(w.regex_tok, grid, block, lds, stream, k0, k1, 0, a, x, e..., *tok);
     else if (x.n_rx) hipExtLaunchKernelGGL(w.regex, grid, block, lds, stream, k0, k1, 0, a, x, e...);
     else if (tok) hipExtLaunchKernelGGL(w.tok, grid, block, lds, stream, k0, k1, 0, a, e..., *tok);
@@ -267,9 +276,11 @@ struct WidePlan {
     const uint32_t *set_first_row, *set_query_off, *set_queries;
     uint32_t n_sets, n_queries;
     std::vector<uint64_t> set_cond_mask;       // [n_sets]
+    std::vector<uint32_t> set_rx_mask;         // [n_sets] bsg_match_rows_lookup_regex(_rows): the regex slots the set's queries use
     std::vector<uint64_t> set_word0;           // [n_sets + 1]: the first result word of the set's first pair
     const WideRowsOut *rows = nullptr;         // the rows policy: lists instead of words
-    const bsh_lookup::Plan *lookup = nullptr;  // bsg_match_rows_lookup(_rows): the table's strings, roles and pairs
+    const bsh_lookup::Plan *lookup = nullptr;  // bsg_match_rows_lookup(_rows) / _lookup_regex(_rows): the table's strings, roles and pairs
+    bool lookup_regex = false;                 // ... the second of the two (the names in traces)
 };
 
 // The wide call: the storing walk chunk by chunk, then one evaluation launch over the part's items (r0 a set-relative multiple of 64).
@@ -302,11 +313,12 @@ struct WidePart {
     uint32_t flag_words = 1;
     std::vector<uint64_t> cond_h, str_h0, pair_tab;
     std::vector<uint32_t> str_tab;
-    uint32_t *d_lk_str = nullptr;
+    uint32_t *d_lk_str = nullptr, *d_lk_rxmask = nullptr;
     uint64_t *d_lk_pair = nullptr, *d_lk_rec = nullptr;
 
     const char *tag() const
     {
+        if (wp.lookup_regex) return wp.rows ? "bsg_match_rows_lookup_regex_rows" : "bsg_match_rows_lookup_regex";
         if (wp.lookup) return wp.rows ? "bsg_match_rows_lookup_rows" : "bsg_match_rows_lookup";
         return wp.rows ? "bsg_match_rows_wide_rows" : "bsg_match_rows_wide";
     }
@@ -335,7 +347,8 @@ struct WidePart {
         HIP_TRY(p.scratch.alloc(&d_out, std::max<uint64_t>(part_words, 1) * 8));
         HIP_TRY(p.scratch.alloc(&d_sfirst, ((size_t)n_sets + 1) * 4));
         HIP_TRY(p.scratch.alloc(&d_spair, ((size_t)n_sets + 1) * 4));
-        HIP_TRY(p.scratch.alloc(&d_smask, (size_t)n_sets * 8));
+        if (mc.n_rx && wp.lookup) HIP_TRY(p.scratch.alloc(&d_lk_rxmask, (size_t)n_sets * 4));     // the lookup walker reads no condition mask
+        else HIP_TRY(p.scratch.alloc(&d_smask, (size_t)n_sets * 8));
         HIP_TRY(p.scratch.alloc(&d_pairs, std::max<size_t>(n_pairs, 1) * 4));
         HIP_TRY(p.scratch.alloc(&d_items, std::max<size_t>(items.size(), 1) * sizeof(bsg::RowEvalItem)));
         if (wp.rows && n_pairs) {
@@ -353,7 +366,8 @@ struct WidePart {
     {
         HIP_TRY(hipMemcpyAsync(d_sfirst, ps.first_row.data(), ((size_t)n_sets + 1) * 4, hipMemcpyHostToDevice, p.d.stream));
         HIP_TRY(hipMemcpyAsync(d_spair, pair_off_local.data(), ((size_t)n_sets + 1) * 4, hipMemcpyHostToDevice, p.d.stream));
-        HIP_TRY(hipMemcpyAsync(d_smask, wp.set_cond_mask.data() + ps.s0, (size_t)n_sets * 8, hipMemcpyHostToDevice, p.d.stream));
+        if (d_lk_rxmask) HIP_TRY(hipMemcpyAsync(d_lk_rxmask, wp.set_rx_mask.data() + ps.s0, (size_t)n_sets * 4, hipMemcpyHostToDevice, p.d.stream));
+        else HIP_TRY(hipMemcpyAsync(d_smask, wp.set_cond_mask.data() + ps.s0, (size_t)n_sets * 8, hipMemcpyHostToDevice, p.d.stream));
         if (n_pairs) HIP_TRY(hipMemcpyAsync(d_pairs, wp.set_queries + pair0, (size_t)n_pairs * 4, hipMemcpyHostToDevice, p.d.stream));
         if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::RowEvalItem), hipMemcpyHostToDevice, p.d.stream));
         if (d_psets) HIP_TRY(hipMemcpyAsync(d_psets, psets.data(), psets.size() * sizeof(bsg::PairSetDesc), hipMemcpyHostToDevice, p.d.stream));
@@ -385,7 +399,8 @@ struct WidePart {
     {
         if (wp.lookup) {
             const bsg::MatchLookupArgs lk{d_sfirst, d_spair, d_lk_str, d_lk_pair, d_lk_rec, d_sat + rf, d_state + rf, n_sets, (uint32_t)str_tab.size(),
-                                          (uint32_t)pair_tab.size(), p.n_rows, bsh_lookup::pair_shift((uint32_t)pair_tab.size())};
+                                          (uint32_t)pair_tab.size(), p.n_rows, bsh_lookup::pair_shift((uint32_t)pair_tab.size()), d_lk_rxmask};
+            assert(bsg::lookup_lds_bytes(lk.n_str_slots, lk.n_pair_slots) + p.rx.n_words * 4 <= bsh_lookup::kWorkgroupLds);   // the call built the blob under this table's cap
             launch_walker(kLookupWalkers, bsg::lookup_lds_bytes(lk.n_str_slots, lk.n_pair_slots), p.d.stream, k0, k1, a, p.rx, mc.tok(), lk);
             return;
         }
@@ -659,9 +674,10 @@ int32_t wide_size_status(bsh_wide::SizeStatus st, uint32_t bad_set, const uint32
 
 int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
                              const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
-                             const bsg_tokenizer *tok_in, const WideRowsOut *rows = nullptr, bool lookup = false)
+                             const bsg_tokenizer *tok_in, const WideRowsOut *rows = nullptr, WideKind which = WideKind::Wide)
 {
-    const Family &fam = lookup ? kLookupFamily : kWideFamily;
+    const bool lookup = which != WideKind::Wide, lookup_regex = which == WideKind::LookupRegex;
+    const Family &fam = lookup_regex ? kLookupRegexFamily : lookup ? kLookupFamily : kWideFamily;
     if (rows && (!rows->len || (rows->cap && !rows->payload))) return fail(BSG_E_INVALID, "null argument");
     if (int32_t rc = begin_match_call(mc, fam, tok_in, prog_ops, prog_off, n_queries)) return rc;
     const uint32_t n_rows = mc.n_rows;
@@ -672,7 +688,7 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
     bsh_lookup::Plan lookup_plan;
     if (lookup) {
         uint32_t bad = 0;
-        switch (bsh_lookup::build_strings(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, lookup_plan, &bad)) {
+        switch (bsh_lookup::build_strings(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, lookup_plan, &bad, lookup_regex)) {
         case bsh_lookup::Status::Ok: break;
         case bsh_lookup::Status::Kind:          // kinds above FieldRegex were refused as unknown
             return fail(BSG_E_UNSUPPORTED, "condition %u: FieldRegex conditions are not matched by the lookup call (use bsg_match_rows_wide)", bad);
@@ -680,7 +696,7 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
         }
     }
     // the sets: the caller's, or one implicit set of all rows with every query
-    WidePlan wp{set_first_row, set_query_off, set_queries, n_sets, n_queries, {}, {}, rows, lookup ? &lookup_plan : nullptr};
+    WidePlan wp{set_first_row, set_query_off, set_queries, n_sets, n_queries, {}, {}, {}, rows, lookup ? &lookup_plan : nullptr, lookup_regex};
     std::vector<uint32_t> implicit_first, implicit_off, implicit_queries;
     if (n_sets == 0) {
         if (set_first_row || set_query_off || set_queries) return fail(BSG_E_INVALID, "a set table without its number of sets");
@@ -704,8 +720,13 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
             }
     }
     if (int32_t rc = lower_programs(mc, fam, prog_ops, prog_off, n_queries, lookup ? &lookup_plan.canon : nullptr)) return rc;
-    if (!lookup)
+    if (!lookup) {
         if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, bsg::kRxWideLdsCap)) return rc;
+    } else if (lookup_regex) {
+        // the DISTINCT regex conditions, under what this table's strings, pairs and lanes leave of a workgroup's 80 KiB
+        const uint32_t cap = bsh_lookup::rx_lds_cap_of(lookup_plan.n_strings(), (uint32_t)lookup_plan.pairs.size());
+        if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, cap, nullptr, &lookup_plan.rx_conds)) return rc;
+    }
     const uint32_t n_pairs = wp.set_query_off[wp.n_sets];
     if (rows) {                                // every pair NONE until a part says otherwise (a set without rows lies in no part)
         if (n_pairs && !rows->hdr) return fail(BSG_E_INVALID, "null argument");
@@ -714,8 +735,9 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
         *rows->len = 0;
     }
     if (n_rows == 0 || n_pairs == 0) return BSG_OK;
-    // (the masks open regex conditions' DFAs: the lookup walker has none and reads no mask)
+    // (the masks open regex conditions' DFAs: the lookup walker reads a u32 of regex slots per set instead, and none without regex conditions)
     if (lookup) wp.set_cond_mask.assign(wp.n_sets, 0);
+    if (mc.n_rx && lookup) wp.set_rx_mask = bsh_lookup::set_rx_masks(lookup_plan, prog_ops, prog_off, n_queries, wp.set_query_off, wp.set_queries, wp.n_sets);
     else wp.set_cond_mask = bsh_wide::set_cond_masks(bsh_wide::query_cond_masks(prog_ops, prog_off, n_queries, mc.n_conds), wp.set_query_off, wp.set_queries, wp.n_sets);
     wp.set_word0.assign((size_t)wp.n_sets + 1, 0);
     for (uint32_t s = 0; s < wp.n_sets; ++s)
@@ -807,7 +829,7 @@ int32_t bsg_match_rows_lookup(bsg_ctx *ctx, const uint8_t *rows, const uint64_t 
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, nullptr, true);
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, nullptr, WideKind::Lookup);
 }
 
 int32_t bsg_match_rows_lookup_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -822,7 +844,34 @@ int32_t bsg_match_rows_lookup_rows(bsg_ctx *ctx, const uint8_t *rows, const uint
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
                  fallback_cap, out_n_fallback};
     const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out, true);
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out, WideKind::Lookup);
+}
+
+int32_t bsg_match_rows_lookup_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                    const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                    const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                    const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
+                                    const bsg_tokenizer *tok,
+                                    uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, nullptr, WideKind::LookupRegex);
+}
+
+int32_t bsg_match_rows_lookup_regex_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                         const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                         const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                         const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
+                                         const bsg_tokenizer *tok,
+                                         uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap, uint64_t *out_payload_len,
+                                         uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
+                 fallback_cap, out_n_fallback};
+    const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out, WideKind::LookupRegex);
 }
 
 int32_t bsg_match_pair_rows_list(uint32_t hdr, const uint32_t *payload, uint32_t set_rows, uint32_t *out_rows, uint32_t cap, uint32_t *out_n)

@@ -763,7 +763,7 @@ class Context:
         return self._wide_bits(self.L.bsg_match_rows_wide, rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
 
     def _wide_bits(self, call, rows, batch, set_first_row, set_query_off, set_queries, tokenizer):
-        """bsg_match_rows_wide or bsg_match_rows_lookup (one argument list, one result)"""
+        """bsg_match_rows_wide, bsg_match_rows_lookup or bsg_match_rows_lookup_regex (one argument list, one result)"""
         args, _keep, n, pair_word_off, total = self._wide_args(rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
         words = np.zeros(total, dtype=np.uint64)
         fb = np.zeros(max(n, 1), dtype=np.uint32)
@@ -778,7 +778,7 @@ class Context:
         return self._wide_rows(self.L.bsg_match_rows_wide_rows, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap)
 
     def _wide_rows(self, call, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap):
-        """bsg_match_rows_wide_rows or bsg_match_rows_lookup_rows (one argument list, one result)"""
+        """bsg_match_rows_wide_rows, bsg_match_rows_lookup_rows or bsg_match_rows_lookup_regex_rows (one argument list, one result)"""
         args, _keep, n, pair_word_off, total = self._wide_args(rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
         n_pairs = len(pair_word_off) - 1
         cap = 2 * total if payload_cap is None else int(payload_cap)
@@ -799,6 +799,15 @@ class Context:
     def match_rows_lookup_rows(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None, payload_cap=None):
         """bsg_match_rows_lookup_rows: match_rows_wide_rows' arguments and result over such a table."""
         return self._wide_rows(self.L.bsg_match_rows_lookup_rows, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap)
+
+    def match_rows_lookup_regex(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None):
+        """bsg_match_rows_lookup_regex: match_rows_lookup with FieldRegex conditions allowed in the table, at most 16 distinct ones
+        (batch: query.CompiledLookupRegexBatch, or anything with kinds / fields / tokens / prog_ops / prog_off)."""
+        return self._wide_bits(self.L.bsg_match_rows_lookup_regex, rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
+
+    def match_rows_lookup_regex_rows(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None, payload_cap=None):
+        """bsg_match_rows_lookup_regex_rows: match_rows_wide_rows' arguments and result over such a table."""
+        return self._wide_rows(self.L.bsg_match_rows_lookup_regex_rows, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap)
 
     def match_wide_size(self, set_first_row, set_query_off, n_rows: int, n_queries: int):
         """bsg_match_wide_size (host arithmetic) -> (u64 pair_word_off [n_pairs + 1], total words); None, None = the implicit set."""

@@ -367,7 +367,7 @@ MATCH_LOOKUP_MAX_CONDS = 1024                                                   
 class CompiledLookupBatch(CompiledWideBatch):
     """Any number of queries for one bsg_match_rows_lookup call: CompiledWideBatch's table and programs over at most 1 024 distinct
     Field / Token / FieldToken conditions.  Raises ValueError beyond 2^20 queries, 2^22 lowered ops or 1 024 distinct conditions, and
-    on a FieldRegex condition (batches with one keep CompiledWideBatch)."""
+    on a FieldRegex condition (batches with one take CompiledLookupRegexBatch or CompiledWideBatch)."""
 
     MAX_CONDS = MATCH_LOOKUP_MAX_CONDS
 
@@ -377,3 +377,11 @@ class CompiledLookupBatch(CompiledWideBatch):
         if KIND_FIELD_REGEX in m.kinds:
             raise ValueError("a FieldRegex condition: the lookup match call holds Field, Token and FieldToken conditions only")
         return m
+
+
+class CompiledLookupRegexBatch(CompiledWideBatch):
+    """Any number of queries for one bsg_match_rows_lookup_regex call: CompiledWideBatch's items ((bloom, regex) pairs included), table
+    and programs over at most 1 024 distinct conditions, at most 16 of them FieldRegex.  Raises ValueError beyond 2^20 queries, 2^22
+    lowered ops, 1 024 distinct conditions or 16 distinct regex conditions (the message says which)."""
+
+    MAX_CONDS = MATCH_LOOKUP_MAX_CONDS

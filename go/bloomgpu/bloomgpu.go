@@ -1094,7 +1094,7 @@ func (g *Context) MatchRowsManyRegex(rows []byte, rowOff []uint64, conds []Match
 // 46592 bytes of LDS, 1<<20 queries, 1<<22 lowered ops, 1<<24 pairs: IsUnsupported(err).
 func (g *Context) MatchRowsWide(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
 	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (words []uint64, pairWordOff []uint64, hostRows []uint32, err error) {
-	return g.matchRowsWide(false, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
+	return g.matchRowsWide(wideCall, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
 }
 
 // MatchLookupMaxConds is the number of distinct conditions one MatchRowsLookup / MatchRowsLookupRows call holds
@@ -1105,13 +1105,35 @@ const MatchLookupMaxConds = 1024
 // conditions (bsg_match_rows_lookup): every emission is resolved by a hash lookup, the flags are ceil(len(conds)/64) words per row.
 // Arguments and result exactly as MatchRowsWide.  In matchBlock this is the call for a batch of standing searches with about as many
 // distinct tokens as queries: one call where MatchRowsWide needs one per 64 conditions.  A KindFieldRegex condition, more than
-// MatchLookupMaxConds conditions, and MatchRowsWide's other limits: IsUnsupported(err); batches with regex conditions keep MatchRowsWide.
+// MatchLookupMaxConds conditions, and MatchRowsWide's other limits: IsUnsupported(err); batches with regex conditions take
+// MatchRowsLookupRegex or MatchRowsWide.
 func (g *Context) MatchRowsLookup(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
 	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (words []uint64, pairWordOff []uint64, hostRows []uint32, err error) {
-	return g.matchRowsWide(true, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
+	return g.matchRowsWide(lookupCall, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
 }
 
-func (g *Context) matchRowsWide(lookup bool, rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
+// which of the calls with MatchRowsWide's arguments matchRowsWide / matchRowsWideRows make
+const (
+	wideCall = iota
+	lookupCall
+	lookupRegexCall
+)
+
+// MatchLookupMaxRegexConds is the number of distinct KindFieldRegex conditions one MatchRowsLookupRegex / MatchRowsLookupRegexRows call holds.
+const MatchLookupMaxRegexConds = 16
+
+// MatchRowsLookupRegex is MatchRowsLookup with KindFieldRegex conditions allowed in the table (bsg_match_rows_lookup_regex): up to
+// MatchLookupMaxConds distinct conditions, MatchLookupMaxRegexConds of them regex, matched as by MatchRowsWide.  A batch of standing
+// token searches with a handful of regex searches among them stays ONE call and one walk of the rows.  A table without a regex
+// condition gives MatchRowsLookup's result byte for byte.  Beyond MatchRowsLookup's limits, IsUnsupported(err) for a 17th distinct
+// regex condition, a pattern outside the DFA compiler's subset, and regex tables over the LDS the table's strings and pairs leave
+// (52 200 bytes over a table of regex conditions only, 19 456 over a full one).
+func (g *Context) MatchRowsLookupRegex(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
+	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (words []uint64, pairWordOff []uint64, hostRows []uint32, err error) {
+	return g.matchRowsWide(lookupRegexCall, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
+}
+
+func (g *Context) matchRowsWide(which int, rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
 	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (words []uint64, pairWordOff []uint64, hostRows []uint32, err error) {
 	n, nq := len(rowOff)-1, len(progOff)-1
 	if n <= 0 || nq <= 0 {
@@ -1159,7 +1181,11 @@ func (g *Context) matchRowsWide(lookup bool, rows []byte, rowOff []uint64, conds
 	}
 	var nfb C.uint32_t
 	var rc C.int32_t
-	if lookup {
+	if which == lookupRegexCall {
+		rc = C.bsg_match_rows_lookup_regex(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+			u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u32p(setQueryOff), u32p(setQueries), C.uint32_t(nSets), ct,
+			u64p(words), u32p(hostRows), C.uint32_t(n), &nfb)
+	} else if which == lookupCall {
 		rc = C.bsg_match_rows_lookup(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
 			u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u32p(setQueryOff), u32p(setQueries), C.uint32_t(nSets), ct,
 			u64p(words), u32p(hostRows), C.uint32_t(n), &nfb)
@@ -1190,17 +1216,24 @@ const (
 // listed on their set.  The payload buffer is sized at its bound (2 uint32 per word of the bit rows), so the call cannot fail on space.
 func (g *Context) MatchRowsWideRows(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
 	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (hdr []uint32, pairOff []uint64, payload []uint32, hostRows []uint32, err error) {
-	return g.matchRowsWideRows(false, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
+	return g.matchRowsWideRows(wideCall, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
 }
 
 // MatchRowsLookupRows is MatchRowsWideRows over a table of up to MatchLookupMaxConds conditions (bsg_match_rows_lookup_rows): the
 // table and the limits of MatchRowsLookup, the result of MatchRowsWideRows.
 func (g *Context) MatchRowsLookupRows(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
 	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (hdr []uint32, pairOff []uint64, payload []uint32, hostRows []uint32, err error) {
-	return g.matchRowsWideRows(true, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
+	return g.matchRowsWideRows(lookupCall, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
 }
 
-func (g *Context) matchRowsWideRows(lookup bool, rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
+// MatchRowsLookupRegexRows is MatchRowsLookupRows with KindFieldRegex conditions allowed in the table
+// (bsg_match_rows_lookup_regex_rows): the table and the limits of MatchRowsLookupRegex, the result of MatchRowsWideRows.
+func (g *Context) MatchRowsLookupRegexRows(rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
+	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (hdr []uint32, pairOff []uint64, payload []uint32, hostRows []uint32, err error) {
+	return g.matchRowsWideRows(lookupRegexCall, rows, rowOff, conds, progOps, progOff, setFirstRow, setQueryOff, setQueries, tok)
+}
+
+func (g *Context) matchRowsWideRows(which int, rows []byte, rowOff []uint64, conds []MatchCond, progOps []uint32, progOff []uint32,
 	setFirstRow []uint32, setQueryOff []uint32, setQueries []uint32, tok *Tokenizer) (hdr []uint32, pairOff []uint64, payload []uint32, hostRows []uint32, err error) {
 	n, nq := len(rowOff)-1, len(progOff)-1
 	if n <= 0 || nq <= 0 {
@@ -1250,7 +1283,11 @@ func (g *Context) matchRowsWideRows(lookup bool, rows []byte, rowOff []uint64, c
 	var nfb C.uint32_t
 	var plen C.uint64_t
 	var rc C.int32_t
-	if lookup {
+	if which == lookupRegexCall {
+		rc = C.bsg_match_rows_lookup_regex_rows(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
+			u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u32p(setQueryOff), u32p(setQueries), C.uint32_t(nSets), ct,
+			u32p(hdr), u64p(pairOff), u32p(payload), C.uint64_t(2*total), &plen, u32p(hostRows), C.uint32_t(n), &nfb)
+	} else if which == lookupCall {
 		rc = C.bsg_match_rows_lookup_rows(g.c, u8p(rows), u64p(rowOff), C.uint32_t(n), u8p(cbytes), u32p(coff), u32p(kinds), C.uint32_t(len(conds)),
 			u32p(progOps), u32p(progOff), C.uint32_t(nq), u32p(setFirstRow), u32p(setQueryOff), u32p(setQueries), C.uint32_t(nSets), ct,
 			u32p(hdr), u64p(pairOff), u32p(payload), C.uint64_t(2*total), &plen, u32p(hostRows), C.uint32_t(n), &nfb)

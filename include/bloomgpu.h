@@ -769,7 +769,8 @@ BSG_API int32_t bsg_match_pair_rows_list(uint32_t hdr, const uint32_t *payload, 
  * What differs: the walker (k_match_rows_lookup*) resolves every emission by a hash lookup instead of comparing it with every
  * condition, and keeps ceil(n_conds / 64) flag words per row, which k_eval_row_programs_w evaluates the programs over.
  * Condition kinds: Field, Token and FieldToken only.  A BSG_KIND_FIELD_REGEX condition is BSG_E_UNSUPPORTED (the message names the
- * condition): batches with regex conditions keep bsg_match_rows_wide.  A condition repeated in the table is decided once.
+ * condition): batches with regex conditions take bsg_match_rows_lookup_regex or bsg_match_rows_wide.  A condition repeated in the
+ * table is decided once.
  * Limits (BSG_E_UNSUPPORTED before anything is launched): 1 024 conditions; program depth 64; the query, op, pair and item limits of
  * bsg_match_rows_wide.  Device memory: 8 * ceil(n_conds / 64) + 1 bytes per row for the flags and the state byte, 4 per lowered op,
  * query and pair, 8 per result word, at most 48 KiB of tables.
@@ -790,6 +791,33 @@ BSG_API int32_t bsg_match_rows_lookup_rows(bsg_ctx *ctx, const uint8_t *rows, co
                                            uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap,
                                            uint64_t *out_payload_len, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                            uint32_t *out_n_fallback);
+/* bsg_match_rows_lookup / bsg_match_rows_lookup_rows with BSG_KIND_FIELD_REGEX conditions allowed in the table, as
+ * bsg_match_rows_many_regex is to bsg_match_rows_many: the same arguments, the same results.  A table without a regex condition runs
+ * the same kernels as the two calls above and returns the same bytes.
+ * The regex conditions are matched as by bsg_match_rows_wide (patterns in the DFA compiler's subset, the leaf's candidate text, a
+ * condition on field f sees the leaves at f or under f + "."): a leaf opens a condition's DFA only on rows of a set that lists a
+ * query whose program references it, and a row on which more than 4 such conditions lie on one leaf is a fallback row.  A regex
+ * condition repeated in the table (the same field and pattern bytes) is one condition.
+ * Limits (BSG_E_UNSUPPORTED before anything is launched), beyond those of bsg_match_rows_lookup: 16 distinct regex conditions; a
+ * pattern outside the subset (the message names the condition and the pattern); regex tables of more than
+ * 81 920 - (4 * string slots + 8 * pair slots + 29 696) bytes, where the slots are the least powers of two >= 2 * the table's
+ * distinct role strings / FieldToken pairs (at least 2): 52 200 bytes over a table of regex conditions only, 19 456 over one with
+ * 2 048 strings and 1 024 pairs.  The message names the cap of the table given. */
+BSG_API int32_t bsg_match_rows_lookup_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                            const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                            const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                            const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                            uint32_t n_sets, const bsg_tokenizer *tok,
+                                            uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                            uint32_t *out_n_fallback);
+BSG_API int32_t bsg_match_rows_lookup_regex_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                                 const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                                 const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                                 const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                                 uint32_t n_sets, const bsg_tokenizer *tok,
+                                                 uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap,
+                                                 uint64_t *out_payload_len, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                                 uint32_t *out_n_fallback);
 /* Device time of the most recent k_match_rows / k_match_rows_regex / k_match_rows_many / k_match_rows_many_regex dispatch (the
  * slowest device's); after bsg_match_rows_wide, its walk plus its evaluation; after bsg_match_rows_wide_rows, its list passes too. */
 BSG_API int32_t bsg_last_match_ms(bsg_ctx *ctx, float *match_ms);

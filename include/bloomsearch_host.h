@@ -99,7 +99,8 @@ typedef struct bse_engine bse_engine;
  *               "BloomFalsePositiveRate":..,"PartitionField":"..","DeviceIngest":true|false,"DeviceIngestStream":true|false,
  *               "DeviceMatch":true|false,
  *               "DeviceRegex":true|false,"DeviceMatchWide":true|false,"DeviceMatchWideRows":true|false,
- *               "DeviceMatchLookup":true|false,"DeviceMatchLookupRows":true|false,"Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false}};
+ *               "DeviceMatchLookup":true|false,"DeviceMatchLookupRows":true|false,"DeviceMatchLookupRegex":true|false,
+ *               "Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false}};
  *               missing keys take the
  *               reference defaults.  DeviceIngest (default false): rows are walked / tokenized / deduplicated /
  *               counted on the GPU at flush and merge time (bloomgpu.h bsg_ingest_*) instead of by indexRow on the
@@ -117,7 +118,12 @@ typedef struct bse_engine bse_engine;
  *               DeviceMatch): the groups of DeviceMatchWide / DeviceMatchWideRows, but a group without a regex condition
  *               holds up to 1 024 distinct conditions and is decided by one bsg_match_rows_lookup / _lookup_rows call (the
  *               table arithmetic: csrc/host/lookup_plan.hpp, beside wide_plan.hpp); queries with a regex condition keep
- *               their 64-condition groups and the wide call; same answers.  DeviceRegex (default false, needs DeviceMatch):
+ *               their 64-condition groups and the wide call; same answers.  DeviceMatchLookupRegex (default false, acts with
+ *               DeviceMatchLookup or DeviceMatchLookupRows, and DeviceRegex): a group WITH regex conditions keeps the 1 024
+ *               conditions too and is decided by one bsg_match_rows_lookup_regex / _lookup_regex_rows call; it closes at 16
+ *               regex conditions, at more than 4 of them over one leaf, and where their tables pass what the group's strings
+ *               (<= 2 x its other conditions) and pairs (<= its FieldToken conditions) leave of the walker's LDS
+ *               (lookup_plan.hpp rx_lds_cap_of); same answers.  DeviceRegex (default false, needs DeviceMatch):
  *               a query whose regex patterns all lie in the device's RE2 subset is matched bloom AND regex by one
  *               bsg_match_rows_regex call, the rows it hands back by the host matcher on the same DFAs; other regex queries
  *               keep the std::regex path.  Tokenizer (default: BasicWhitespaceLowerTokenizer): the engine's tokenizer

@@ -21,7 +21,7 @@ KIND_FIELD_REGEX = 3          # row matcher only (bsg_match_rows_regex)
 OP_TERM, OP_AND, OP_OR, OP_TRUE, OP_FALSE = 0, 1, 2, 3, 4
 PROBE_ASYNC, PROBE_TIMED, PROBE_NOFUSE, PROBE_ROWS_PACKED = 1, 2, 4, 8
 INGEST_TRUSTED_JSON = 1
-ROUTE_NONE, ROUTE_STREAM, ROUTE_GATHER = 0, 1, 2      # bsg_lab_last_probe_route (bloomgpu_lab.h)
+ROUTE_NONE, ROUTE_STREAM, ROUTE_GATHER, ROUTE_GATHER_CHUNKED = 0, 1, 2, 3      # bsg_lab_last_probe_route (bloomgpu_lab.h)
 GATHER_COST_DEFAULT = 108                             # bsg_set_gather_cost's default (bloomgpu_lab.h)
 
 TERM_DTYPE = np.dtype([("h", "<u8", (4,)), ("kind", "<u4"), ("reserved", "<u4")])

@@ -444,7 +444,7 @@ struct bsg_ctx {
     uint32_t solo_ring_wgs = 32;  // a lone bsg_query of more workgroups than this gets its doorbell from a dispatch behind the kernel (bsg_set_lab key 22)
     uint32_t gather_cost = 108;   // bytes a gathered word load is taken to cost: a launch / a filter is gathered when terms * k * gather_cost < its bytes (bsg_set_gather_cost; the value: profiles/probe_gather_lab.txt)
     uint32_t gather_kernel = 1;  // 0 (bsg_set_lab key 26): a launch never takes k_probe_gather, only the per-block gathered path inside k_probe_terms
-    std::atomic<uint32_t> last_probe_route{0};   // route of the last k_probe_terms(_many) / k_probe_gather dispatch (bsg_lab_last_probe_route)
+    std::atomic<uint32_t> last_probe_route{0};   // route of the last k_probe_terms(_many) / k_probe_gather dispatch, or of the last chunked gather (bsg_lab_last_probe_route)
     bsg::FpKey fp_key{};         // secret key of the entries' fingerprints (drawn at bsg_open; never leaves the process)
     std::vector<uint8_t> peer;   // [i * nd + j]: 1 = device i reaches device j's memory directly (xGMI peer access enabled, or the same device)
     std::atomic<uint64_t> peer_warned{0};   // pairs (bit i * 8 + j, contexts of <= 8 devices) whose staged copies were announced
@@ -464,6 +464,7 @@ struct bsg_ctx {
     // before the other tiles complete them, which costs what the second dispatch's ramp would (bsg_set_lab key 11 turns it on)
     uint32_t fold_helpers = 0;
     uint32_t tail_split_pct = 0;   // bsg_set_lab key 19
+    uint64_t pipeline_key = 0;     // bsg_set_lab key 27 (bsh::pipeline_chunks)
     Combiner cmb;                // concurrent bsg_query calls merged into shared dispatches (combine_api.inc)
     // write side / matcher over several devices: a call large enough is cut into one part per device (contiguous runs of
     // filters / sets / rows), each part on a thread of its own; smaller calls take ONE device, chosen round-robin among

@@ -140,6 +140,53 @@ inline size_t tail_split_cut(size_t n_shards, uint32_t pct, size_t max_group_are
     return std::min(n_shards - 1, std::max<size_t>(1, n_shards * pct / 100));
 }
 
+// Chunked gather (k_gather_fused): a group that gathers is probed in a few CHUNKS of consecutive arenas on one stream —
+//   k_probe_gather(chunk 0) | k_gather_fused(gather chunk i, evaluate chunk i - 1) ... | k_eval_programs(last chunk)
+// so that only the last chunk's program evaluation is left behind the probe.  Every further dispatch costs a boundary of a few
+// microseconds, so a run is chunked only where the evaluation it hides is longer than that: kPipelineMinArenas arenas AND
+// kPipelineMinBlocks blocks (the evaluation's time goes with the 64-block groups, the boundary's does not: many tiny arenas are
+// no reason to chunk).  Measured on MI355X with C2's 1 000-block arenas (profiles/probe_pipeline_lab.txt): three equal chunks with
+// the evaluation workgroups SPREAD through k_gather_fused's grid take 700 us against 741-745 at 200 arenas and 534 against 560-568 at
+// 150; at 50-100 arenas the result depends on what the calls alternate with (a draw against the plain route run by itself), at
+// 30 and 20 every chunking loses 3-25 %; with the evaluation workgroups in FRONT of the grid no chunking gains at any size.  So the
+// rule starts where a group's records lie in device memory anyway.
+// One chunk — the two plain dispatches — whenever the launch does not gather, the batch is not a few-term batch with the identity
+// word list, the run has more than one group, or fold / fuse / tail split is selected.
+// key (bsg_set_lab key 27): 0 = the rule above; 1 = never; low 16 bits n >= 2 = n chunks (at most one per arena) whatever the
+// thresholds say, as equal as possible; bits 16-23 = percent of an equal share the LAST chunk gets (0 = 100: equal) — it is the only
+// one whose evaluation stays exposed; bits 24-25 = where k_gather_fused's evaluation workgroups go (0 = kPipelineSpread, 1 = in front,
+// 2 = spread among the gather workgroups: not the planner's business).
+constexpr uint32_t kPipelineMinArenas = 129;
+constexpr uint64_t kPipelineMinBlocks = 128000;
+constexpr uint32_t kPipelineChunks = 3;
+constexpr uint32_t kPipelineLastPct = 100;
+constexpr bool kPipelineSpread = true;
+struct PipelineCase {
+    bool gathers;          // bsh::launch_gathers of the whole group
+    bool identity_few;     // few-term batch with the identity word list
+    uint32_t n_groups;     // groups of the run on this device
+    bool other_route;      // fold, fuse or tail split selected
+};
+inline std::vector<uint32_t> pipeline_chunks(uint32_t n_arenas, uint64_t n_blocks, const PipelineCase &pc, uint64_t key)
+{
+    std::vector<uint32_t> one(n_arenas ? 1 : 0, n_arenas);
+    if (n_arenas < 2 || key == 1 || !pc.gathers || !pc.identity_few || pc.n_groups != 1 || pc.other_route) return one;
+    uint32_t n = (uint32_t)(key & 0xFFFFu), last_pct = (uint32_t)std::min<uint64_t>((key >> 16) & 0xFFu, 100);
+    if (n < 2) {
+        if (n_arenas < kPipelineMinArenas || n_blocks < kPipelineMinBlocks) return one;
+        n = kPipelineChunks; last_pct = kPipelineLastPct;
+    }
+    if (last_pct == 0) last_pct = 100;
+    n = std::min(n, n_arenas);
+    // the last chunk: last_pct of an equal share, at least one arena; the others share the rest as equally as possible
+    const uint32_t last = std::max<uint32_t>(1, (uint32_t)((uint64_t)n_arenas * last_pct / (100ull * n)));
+    const uint32_t rest = n_arenas - last, m = n - 1;
+    std::vector<uint32_t> sizes(n);
+    for (uint32_t i = 0; i < m; ++i) sizes[i] = rest / m + (i < rest % m ? 1u : 0u);
+    sizes[m] = last;
+    return sizes;
+}
+
 // bsg_probe_many_rows on a context of nd devices: device d writes the rows of ITS shards (local block numbers: local l of device d is
 // global block l * nd + d) into a slice of its own of the caller's page-locked buffers —
 //   headers: out_hdr + d * n_arenas * n_queries, [arena][query]

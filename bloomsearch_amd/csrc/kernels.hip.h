@@ -1018,10 +1018,11 @@ __device__ __forceinline__ void gather_block(const ProbeArgs &a, const ProbeDesc
     }
 }
 
-__device__ __forceinline__ void gather_role(const ProbeArgs &a, const ArenaRef &ar, uint32_t y)
+// bx: the workgroup's position among the arena's ceil(max_blocks / kGatherBlocks) workgroups
+__device__ __forceinline__ void gather_role(const ProbeArgs &a, const ArenaRef &ar, uint32_t bx, uint32_t y)
 {
     const uint32_t lane = threadIdx.x & (kWave - 1);
-    const uint32_t b = blockIdx.x * kGatherBlocks + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);   // wave-uniform, in an SGPR
+    const uint32_t b = bx * kGatherBlocks + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);   // wave-uniform, in an SGPR
     if (b >= ar.n_blocks) return;   // arenas of a group may differ in size; the last workgroup of an arena may be partial
     ProbeDesc d;
     static_cast<DevDesc &>(d) = load_desc_uniform(ar.desc + ((uint64_t)b * 3 + a.kind[y]));
@@ -1044,13 +1045,13 @@ __device__ __forceinline__ void gather_role(const ProbeArgs &a, const ArenaRef &
 
 __global__ __launch_bounds__(kProbeThreads) void k_probe_gather(const ProbeArgs a, const ArenaTable<kMaxGroupArenas> t)
 {
-    gather_role(a, t.ar[blockIdx.z], blockIdx.y);
+    gather_role(a, t.ar[blockIdx.z], blockIdx.x, blockIdx.y);
 }
 // the same kernel for groups whose arena records lie in device memory (separate for the reason given at kMaxExtGroupArenas)
 __global__ __launch_bounds__(kProbeThreads) void k_probe_gather_ext(const ProbeArgs a, const ArenaRef *__restrict__ ext)
 {
     const ArenaRef ar = load_arena_ref(ext, blockIdx.z);
-    gather_role(a, ar, blockIdx.y);
+    gather_role(a, ar, blockIdx.x, blockIdx.y);
 }
 
 // (Measured and dropped, twice now: the same kernel with 1 024 threads per block — 16 waves sharing one block's image, 32
@@ -1304,9 +1305,9 @@ __host__ __device__ inline uint32_t eval_grid_blocks(uint32_t nx, uint32_t n_chu
 {
     return (n_chunks * n_arenas + 7u) / 8u * 8u * nx;
 }
-__device__ __forceinline__ bool eval_block_of(const EvalArgs &a, uint32_t nx, uint32_t n_chunks, uint32_t &combo, uint32_t &tx)
+__device__ __forceinline__ bool eval_block_of(const EvalArgs &a, uint32_t L, uint32_t nx, uint32_t n_chunks, uint32_t &combo, uint32_t &tx)
 {
-    const uint32_t L = blockIdx.x, span = 8u * nx;
+    const uint32_t span = 8u * nx;
     const uint32_t r = L % span;
     combo = L / span * 8u + (r & 7u);
     tx = r >> 3;
@@ -1327,7 +1328,7 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_programs(const EvalArgs a
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
     uint32_t combo, tx;
-    if (!eval_block_of(a, nx, n_chunks, combo, tx)) return;
+    if (!eval_block_of(a, blockIdx.x, nx, n_chunks, combo, tx)) return;
     eval_block(a, t.ar[combo / n_chunks], tile, tx, combo % n_chunks, lds64);
 }
 __global__ __launch_bounds__(kEvalThreads) void k_eval_programs_ext(const EvalArgs a, const ArenaRef *__restrict__ ext, const uint32_t tile, const uint32_t nx,
@@ -1335,7 +1336,7 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_programs_ext(const EvalAr
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
     uint32_t combo, tx;
-    if (!eval_block_of(a, nx, n_chunks, combo, tx)) return;
+    if (!eval_block_of(a, blockIdx.x, nx, n_chunks, combo, tx)) return;
     const ArenaRef ar = load_arena_ref(ext, combo / n_chunks);
     eval_block(a, ar, tile, tx, combo % n_chunks, lds64);
 }
@@ -1380,6 +1381,59 @@ __global__ __launch_bounds__(kProbeThreads) void k_probe_fused(const FusedArgs f
         const uint32_t c = pair * 2 + half;
         const uint32_t n_chunks = (f.e.n_queries + kEvalThreads - 1) / kEvalThreads;
         eval_role(f.e, ar, g0, min(f.eval_tile, ar.G() - g0), c, htid, lds64 + (uint64_t)half * (f.eval_lds_half / 8), c < n_chunks);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// K1g + K2 in one dispatch for a group that is probed in CHUNKS of arenas (bsh::pipeline_chunks): some workgroups evaluate the
+// programs of arenas [e0, e0 + e.n_arenas) from the verdict words an EARLIER dispatch on the same stream left in V, the others
+// run gather_role over arenas [a0, a0 + p.n_arenas) of the same group.  Every arena has its own v_off / out_off (ArenaRef), so the
+// chunks share the slot's V and out without overlap, and nothing is signalled between the roles: the stream's order is the only
+// one, and an evaluation workgroup never reads a verdict word that its own dispatch writes.  The gather role holds no LDS, no
+// barrier and no atomics, so the evaluator's dependent chain (program words, verdict words, transposes, LDS stack) can run on CUs
+// that keep their gather waves.
+// The grid is taken in OCTETS of 8 consecutive workgroups (one per XCD), each all evaluation or all gather: evaluation workgroup
+// L = 8 x (its octet's number among the evaluation octets) + blockIdx.x % 8 is k_eval_programs' workgroup L exactly — same
+// XCD-aware numbering, same body (eval_block: 256 threads; the upper half of the 512-thread workgroup leaves at once), so a
+// survivor row is still completed inside one XCD's L2.  spread = 0: the evaluation octets at the FRONT of the grid, as in
+// k_probe_fused; 1: spread evenly among the gather octets (octet o evaluates iff floor((o + 1) E / T) > floor(o E / T)), so that
+// at any time most resident waves gather.  The records of both roles come from the group's device-memory table.
+// ---------------------------------------------------------------------------
+struct GatherFusedArgs {
+    ProbeArgs p;             // p.n_arenas / p.max_blocks: of the arenas this dispatch gathers
+    EvalArgs e;              // e.n_arenas / e.max_G: of the arenas this dispatch evaluates
+    uint32_t a0, e0;         // first arena (position in the group's table) of the gather / the evaluation role
+    uint32_t n_eval;         // evaluation workgroups = eval_grid_blocks(eval_nx, n_chunks, e.n_arenas): a multiple of 8
+    uint32_t n_octets;       // the grid / 8 = n_eval / 8 + ceil(gather workgroups / 8)
+    uint32_t spread;
+    uint32_t n_chunks;       // 256-query chunks of the batch
+    uint32_t eval_nx;        // ceil(e.max_G / eval_tile)
+    uint32_t eval_tile;      // block groups per evaluation workgroup (1, 2 or kEvalGroupTile)
+    uint32_t n_kinds;
+    uint32_t gather_nx;      // ceil(p.max_blocks / kGatherBlocks)
+};
+
+__global__ __launch_bounds__(kProbeThreads) void k_gather_fused(const GatherFusedArgs f, const ArenaRef *__restrict__ ext)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
+    const uint32_t o = blockIdx.x >> 3, E = f.n_eval >> 3;
+    // evaluation octets in front of octet o, and in front of octet o + 1
+    const uint32_t c0 = f.spread ? (uint32_t)((uint64_t)o * E / f.n_octets) : min(o, E);
+    const uint32_t c1 = f.spread ? (uint32_t)((uint64_t)(o + 1) * E / f.n_octets) : min(o + 1, E);
+    if (c1 == c0) {
+        const uint32_t j = (o - c0) * 8u + (blockIdx.x & 7u);
+        const uint32_t per_arena = f.gather_nx * f.n_kinds;
+        const uint32_t ai = j / per_arena, r = j - ai * per_arena;
+        if (ai >= f.p.n_arenas) return;                       // (the last gather octet may be partial)
+        const uint32_t y = r / f.gather_nx;
+        const ArenaRef ar = load_arena_ref(ext, f.a0 + ai);
+        gather_role(f.p, ar, r - y * f.gather_nx, y);
+    } else {
+        if (threadIdx.x >= kEvalThreads) return;
+        uint32_t combo, tx;
+        if (!eval_block_of(f.e, c0 * 8u + (blockIdx.x & 7u), f.eval_nx, f.n_chunks, combo, tx)) return;
+        const ArenaRef ar = load_arena_ref(ext, f.e0 + combo / f.n_chunks);
+        eval_block(f.e, ar, f.eval_tile, tx, combo % f.n_chunks, lds64);
     }
 }
 

@@ -339,12 +339,13 @@ struct ShardBlocks {
 
 // The arena records of a group for k_probe_terms(_many) / k_eval_programs: in the kernel arguments up to kMaxGroupArenas, else
 // uploaded into the scratch slot's device table in front of the dispatch (same stream: ordered before it, and after the
-// previous user of the slot).  *ext = nullptr or the device table.
-int32_t group_table(Device &d, const Group &g, bsg::ArenaTable<bsg::kMaxGroupArenas> &t, const bsg::ArenaRef **ext)
+// previous user of the slot).  *ext = nullptr or the device table.  force_ext: the device table whatever the group's size (a group
+// probed in chunks, DeviceRun::pipeline_chunked: both roles of k_gather_fused index the group's records by arena).
+int32_t group_table(Device &d, const Group &g, bsg::ArenaTable<bsg::kMaxGroupArenas> &t, const bsg::ArenaRef **ext, bool force_ext = false)
 {
     *ext = nullptr;
     const size_t n = g.shards.size();
-    if (n <= bsg::kMaxGroupArenas) { fill_refs(g, t.ar); return BSG_OK; }
+    if (n <= bsg::kMaxGroupArenas && !force_ext) { fill_refs(g, t.ar); return BSG_OK; }
     // A table in device memory is a pure function of its records, and hosts probe the same candidate files again and again: the
     // device keeps the last few tables it wrote (round 5), so a group that was probed before costs no k_write_arena_table dispatches
     // — two serial ~5 us dispatches in front of the stream for the 200 shards a rank holds of 20 steps x 10 files at N = 8.
@@ -433,6 +434,42 @@ uint32_t eval_tile_for(const Group &g)
     return g.max_G <= 2 ? 2u : bsg::kEvalGroupTile;          // (many small shards — a file's 125 blocks on one of 8 GPUs — take tiles of 2 groups)
 }
 
+// What bsh::launch_gathers / bsh::gathered_bytes take of a group (or of a chunk of one): per referenced kind the filters' words, the
+// part beyond the LDS budget, the batch's terms and the largest k; -> the blocks of the group.
+uint64_t gather_kinds(const Group &g, const Batch &B, bsh::GatherKind *gk)
+{
+    uint64_t group_blocks = 0;
+    for (const ArenaShard *s : g.shards) group_blocks += s->n_blocks;
+    for (uint32_t y = 0; y < B.n_kinds; ++y) {
+        gk[y] = bsh::GatherKind{0, 0, B.term_count[y], 0};
+        for (const ArenaShard *s : g.shards) {
+            gk[y].sum_words += s->sum_words[B.kind[y]];
+            gk[y].unstaged_words += s->sum_unstaged_words[B.kind[y]];
+            gk[y].max_k = std::max(gk[y].max_k, s->max_k[B.kind[y]]);
+        }
+    }
+    return group_blocks;
+}
+
+bool group_gathers(const bsg_ctx *ctx, const Group &g, const Batch &B)
+{
+    bsh::GatherKind gk[3];
+    const uint64_t group_blocks = gather_kinds(g, B, gk);
+    return B.n_kinds > 0 && ctx->gather_kernel && bsh::launch_gathers(gk, B.n_kinds, group_blocks, B.many_terms, ctx->gather_cost);
+}
+
+// bsg_timing's stream_bytes for a gathered launch (ev->bytes holds the bitsets' bytes, make_probe_args): not the bitsets (it does not
+// stream them) but the 128-byte lines its bit tests are expected to touch (bsh::gathered_bytes: what FETCH_SIZE shows) — a roofline
+// fraction formed from it stays one
+void gathered_timing(EventTriple &ev, const Batch &B, const bsh::GatherKind *gk, uint64_t group_blocks)
+{
+    for (uint32_t y = 0; y < B.n_kinds; ++y) {
+        ev.bytes -= gk[y].sum_words * 8;
+        ev.bytes += bsh::gathered_bytes(gk[y], group_blocks);
+    }
+    ev.has_k1 = true;
+}
+
 int32_t enqueue_terms(bsg_ctx *ctx, Device &d, const Group &g, const BatchDev &bd, const Batch &B, uint32_t slot, EventTriple *ev)
 {
     bsg::ProbeArgs a;
@@ -452,31 +489,14 @@ int32_t enqueue_terms(bsg_ctx *ctx, Device &d, const Group &g, const BatchDev &b
     // its filters' bytes, one wave per block reads the words it tests straight from the arena (k_probe_gather: no LDS, same verdict
     // words, same event slots); anything else keeps the streaming kernels and their per-block fallback.
     bsh::GatherKind gk[3];
-    uint64_t group_blocks = 0;
-    for (const ArenaShard *s : g.shards) group_blocks += s->n_blocks;
-    for (uint32_t y = 0; y < B.n_kinds; ++y) {
-        gk[y] = bsh::GatherKind{0, 0, B.term_count[y], 0};
-        for (const ArenaShard *s : g.shards) {
-            gk[y].sum_words += s->sum_words[B.kind[y]];
-            gk[y].unstaged_words += s->sum_unstaged_words[B.kind[y]];
-            gk[y].max_k = std::max(gk[y].max_k, s->max_k[B.kind[y]]);
-        }
-    }
+    const uint64_t group_blocks = gather_kinds(g, B, gk);
     if (ctx->gather_kernel && bsh::launch_gathers(gk, B.n_kinds, group_blocks, B.many_terms, ctx->gather_cost)) {
         const dim3 ggrid((g.max_blocks + bsg::kGatherBlocks - 1) / bsg::kGatherBlocks, B.n_kinds, a.n_arenas);
         if (ext) hipExtLaunchKernelGGL(bsg::k_probe_gather_ext, ggrid, wg, 0, d.stream, e0, e1, 0, a, ext);
         else     hipExtLaunchKernelGGL(bsg::k_probe_gather, ggrid, wg, 0, d.stream, e0, e1, 0, a, t);
         HIP_TRY(hipGetLastError());
         ctx->last_probe_route.store(BSG_LAB_ROUTE_GATHER, std::memory_order_relaxed);
-        if (ev) {
-            // bsg_timing's stream_bytes for a gathered launch: not the bitsets (it does not stream them) but the 128-byte lines its bit
-            // tests are expected to touch (bsh::gathered_bytes: what FETCH_SIZE shows) — a roofline fraction formed from it stays one
-            for (uint32_t y = 0; y < B.n_kinds; ++y) {
-                ev->bytes -= gk[y].sum_words * 8;
-                ev->bytes += bsh::gathered_bytes(gk[y], group_blocks);
-            }
-            ev->has_k1 = true;
-        }
+        if (ev) gathered_timing(*ev, B, gk, group_blocks);
         return BSG_OK;
     }
     const dim3 grid(g.max_blocks, B.n_kinds, a.n_arenas);
@@ -581,10 +601,23 @@ int32_t enqueue_direct(Device &d, const Group &g, const BatchDev &bd, const Batc
     return BSG_OK;
 }
 
+// LDS of an evaluation workgroup (eval_block); sets the bit of a.identity_cw that selects eval_role_all:
+// batches with the identity word list transpose a whole tile's words at once (eval_role_all) when that fits 64 KB of LDS
+uint32_t eval_lds_for(const Batch &B, bsg::EvalArgs &a)
+{
+    static const bool lab_serial = getenv("BSG_LAB_EVAL_SERIAL") != nullptr;   // lab only: the per-group walk for every batch
+    if (B.identity_cw && !lab_serial && bsg::eval_lds_bytes(B.max_cw * bsg::kEvalGroupTile, B.max_depth * bsg::kEvalGroupTile) <= 64 * 1024) {
+        a.identity_cw |= 2u;
+        return bsg::eval_lds_bytes(B.max_cw * bsg::kEvalGroupTile, B.max_depth * bsg::kEvalGroupTile);
+    }
+    return bsg::eval_lds_bytes(B.max_cw, B.max_depth);
+}
+
 // K2: programs over V[slot] -> out[slot].
 // out_override: the survivors go there (device-visible memory in the group's layout) instead of out[slot].
+// ext_at: g is a CHUNK of the group in the slot (pipeline_chunked) and its records start there, inside the group's device table.
 int32_t enqueue_eval(Device &d, const Group &g, const BatchDev &bd, const Batch &B, uint32_t slot, EventTriple *ev, uint64_t *out_override = nullptr,
-                     hipStream_t on = nullptr)
+                     hipStream_t on = nullptr, const bsg::ArenaRef *ext_at = nullptr)
 {
     bsg::EvalArgs a;
     if (int32_t rc = make_eval_args(d, g, bd, B, slot, a)) return rc;
@@ -593,15 +626,10 @@ int32_t enqueue_eval(Device &d, const Group &g, const BatchDev &bd, const Batch 
     const uint32_t tile = eval_tile_for(g);
     bsg::ArenaTable<bsg::kMaxGroupArenas> t;
     const bsg::ArenaRef *ext = nullptr;
-    if (g.shards.size() <= bsg::kMaxGroupArenas) fill_refs(g, t.ar);
+    if (ext_at) ext = ext_at;
+    else if (g.shards.size() <= bsg::kMaxGroupArenas) fill_refs(g, t.ar);
     else ext = d.ext_of_slot[slot];         // written (or found in the device's table cache) by this group's probe dispatch (enqueue_terms), same slot, same stream
-    // batches with the identity word list transpose a whole tile's words at once (eval_role_all) when that fits 64 KB of LDS
-    static const bool lab_serial = getenv("BSG_LAB_EVAL_SERIAL") != nullptr;   // lab only: the per-group walk for every batch
-    uint32_t lds = bsg::eval_lds_bytes(B.max_cw, B.max_depth);
-    if (B.identity_cw && !lab_serial && bsg::eval_lds_bytes(B.max_cw * bsg::kEvalGroupTile, B.max_depth * bsg::kEvalGroupTile) <= 64 * 1024) {
-        a.identity_cw |= 2u;
-        lds = bsg::eval_lds_bytes(B.max_cw * bsg::kEvalGroupTile, B.max_depth * bsg::kEvalGroupTile);
-    }
+    const uint32_t lds = eval_lds_for(B, a);
     const uint32_t nx = (g.max_G + tile - 1) / tile;
     const uint64_t n_wg = (uint64_t)(B.n_chunks * (uint64_t)a.n_arenas + 7) / 8 * 8 * nx;
     if (n_wg > 0x7FFFFFFFull) return fail(BSG_E_UNSUPPORTED, "evaluation launch of %llu workgroups", (unsigned long long)n_wg);
@@ -679,6 +707,40 @@ int32_t enqueue_fused(bsg_ctx *ctx, Device &d, const Group &g, uint32_t slot, co
                           ev ? ev->k1e : nullptr, 0, f, tp, te);
     HIP_TRY(hipGetLastError());
     if (ev) { ev->has_k1 = true; ev->fused = true; }
+    return BSG_OK;
+}
+
+// One launch of a group probed in chunks: the gather of chunk `gc` (its records from ext + a0) + the evaluation of the chunk before
+// it, `ec` (from ext + e0), both in the group's scratch slot.  See k_gather_fused.  tile: eval_tile_for the whole group.
+int32_t enqueue_gather_fused(bsg_ctx *ctx, Device &d, const Group &gc, uint32_t a0, const Group &ec, uint32_t e0, const bsg::ArenaRef *ext,
+                             uint32_t tile, bool spread, const BatchDev &bd, const Batch &B, uint32_t slot, EventTriple *ev)
+{
+    bsg::GatherFusedArgs f{};
+    uint32_t lds = 0;
+    if (int32_t rc = make_probe_args(ctx, d, gc, bd, B, slot, ev, f.p, lds)) return rc;
+    if (int32_t rc = make_eval_args(d, ec, bd, B, slot, f.e)) return rc;
+    lds = eval_lds_for(B, f.e);
+    f.a0 = a0; f.e0 = e0;
+    f.spread = spread ? 1u : 0u;
+    f.n_kinds = B.n_kinds;
+    f.n_chunks = B.n_chunks;
+    f.gather_nx = (gc.max_blocks + bsg::kGatherBlocks - 1) / bsg::kGatherBlocks;
+    f.eval_tile = tile;
+    f.eval_nx = (ec.max_G + tile - 1) / tile;
+    const uint64_t n_eval = (uint64_t)(B.n_chunks * (uint64_t)f.e.n_arenas + 7) / 8 * 8 * f.eval_nx;
+    const uint64_t octets = n_eval / 8 + ((uint64_t)f.gather_nx * B.n_kinds * f.p.n_arenas + 7) / 8;
+    if (octets * 8 > 0x7FFFFFFFull) return fail(BSG_E_UNSUPPORTED, "chunked gather launch of %llu workgroups", (unsigned long long)(octets * 8));
+    f.n_eval = (uint32_t)n_eval;
+    f.n_octets = (uint32_t)octets;
+    hipExtLaunchKernelGGL(bsg::k_gather_fused, dim3((uint32_t)(octets * 8)), dim3(bsg::kProbeThreads), lds, d.stream, ev ? ev->k1s : nullptr,
+                          ev ? ev->k1e : nullptr, 0, f, ext);
+    HIP_TRY(hipGetLastError());
+    if (ev) {
+        bsh::GatherKind gk[3];
+        const uint64_t blocks = gather_kinds(gc, B, gk);
+        gathered_timing(*ev, B, gk, blocks);
+        ev->fused = true;
+    }
     return BSG_OK;
 }
 
@@ -802,6 +864,7 @@ struct DeviceRun {
     bool direct_applies() const;
     int32_t direct();
     int32_t pipeline();
+    int32_t pipeline_chunked(const std::vector<uint32_t> &sizes);
     int32_t before_eval(uint32_t slot);
     int32_t after_eval(size_t gi, uint32_t slot);
     int32_t rows_out(size_t gi, uint32_t slot);
@@ -931,6 +994,63 @@ int32_t DeviceRun::copy_stream_out(size_t gi, uint32_t slot)
     return BSG_OK;
 }
 
+// ONE group probed in chunks of consecutive arenas (bsh::pipeline_chunks), all in scratch slot 0:
+//   k_probe_gather_ext(chunk 0) | k_gather_fused(gather chunk i, evaluate chunk i - 1) ... | k_eval_programs_ext(last chunk)
+// The group's records lie in its device-memory table whatever its size, and every arena keeps the v_off / out_off it has in the
+// whole group: the chunks fill the slot's V and out side by side, and the survivors leave once, behind the last evaluation.
+// Timing: one triple per chunk — chunk 0's gather a terms kernel, every k_gather_fused a fused dispatch that counts the arenas it
+// gathers, the last evaluation the eval kernel of the last triple: every arena is counted once.
+int32_t DeviceRun::pipeline_chunked(const std::vector<uint32_t> &sizes)
+{
+    bsg_ctx *ctx = c.ctx;
+    const Batch &B = c.B;
+    const Group &g = groups[0];
+    const size_t nc = sizes.size();
+    std::vector<Group> chunks(nc);
+    std::vector<uint32_t> first(nc + 1, 0);
+    for (size_t ci = 0, i = 0; ci < nc; ++ci) {
+        first[ci + 1] = first[ci] + sizes[ci];
+        for (; i < first[ci + 1]; ++i) group_add(chunks[ci], B.n_queries, B.Wt, *g.shards[i], g.index[i]);
+    }
+    evs.resize(1);
+    tflag.assign(1, 0);                            // (after_eval pushes no triple of its own: the chunks' triples go below)
+    const bool timed = c.timed && (ctx->timed_stride <= 1 || (ctx->timed_counter++ % ctx->timed_stride) == ctx->timed_stride / 2);
+    std::vector<EventTriple> cev(timed ? nc : 0);
+    for (EventTriple &e : cev) if (int32_t rc = take_events(ctx, d, e)) return rc;
+    auto cv = [&](size_t ci) { return timed ? &cev[ci] : nullptr; };
+    // the whole group's scratch and records first: the chunks' own requests below then find both in place
+    HIP_TRY(d.V[0].reserve(std::max<uint64_t>(g.v_words, 1)));
+    HIP_TRY(d.out[0].reserve(std::max<uint64_t>(g.out_words, 1)));
+    bsg::ArenaTable<bsg::kMaxGroupArenas> t;
+    const bsg::ArenaRef *ext = nullptr;
+    if (int32_t rc = group_table(d, g, t, &ext, true)) return rc;
+    d.ext_of_slot[0] = ext;
+    const uint32_t tile = eval_tile_for(g);
+    const uint32_t place = (uint32_t)(ctx->pipeline_key >> 24) & 3u;      // 0: the default, 1: evaluation octets in front, 2: spread
+    const bool spread = place ? place == 2u : bsh::kPipelineSpread;
+    {
+        bsg::ProbeArgs a;
+        uint32_t lds = 0;
+        if (int32_t rc = make_probe_args(ctx, d, chunks[0], bd, B, 0, cv(0), a, lds)) return rc;
+        const dim3 ggrid((chunks[0].max_blocks + bsg::kGatherBlocks - 1) / bsg::kGatherBlocks, B.n_kinds, a.n_arenas);
+        hipExtLaunchKernelGGL(bsg::k_probe_gather_ext, ggrid, dim3(bsg::kProbeThreads), 0, d.stream, timed ? cev[0].k1s : nullptr,
+                              timed ? cev[0].k1e : nullptr, 0, a, ext);
+        HIP_TRY(hipGetLastError());
+        if (timed) {
+            bsh::GatherKind gk[3];
+            const uint64_t blocks = gather_kinds(chunks[0], B, gk);
+            gathered_timing(cev[0], B, gk, blocks);
+        }
+    }
+    if (int32_t rc = before_eval(0)) return rc;
+    for (size_t ci = 1; ci < nc; ++ci)
+        if (int32_t rc = enqueue_gather_fused(ctx, d, chunks[ci], first[ci], chunks[ci - 1], first[ci - 1], ext, tile, spread, bd, B, 0, cv(ci))) return rc;
+    if (int32_t rc = enqueue_eval(d, chunks[nc - 1], bd, B, 0, cv(nc - 1), nullptr, nullptr, ext + first[nc - 1])) return rc;
+    ctx->last_probe_route.store(BSG_LAB_ROUTE_GATHER_CHUNKED, std::memory_order_relaxed);
+    for (EventTriple &e : cev) d.pending.push_back(e);
+    return after_eval(0, 0);
+}
+
 // The software pipeline over the groups; per group one of four arms: folded (one dispatch per group), fused with the evaluation of
 // the group before, or the two kernels — the evaluation of the group before on the device's stream, or (tail split) on a second one.
 int32_t DeviceRun::pipeline()
@@ -943,6 +1063,20 @@ int32_t DeviceRun::pipeline()
     // its stream (11 of 132 us at 20 arenas of C2).  tail_split (bsg_set_lab key 19, percent) cuts the group in two dispatches'
     // worth: the first part's evaluation runs on a second stream while the second part streams, and only the second part's
     // evaluation is left behind the stream.  Two groups that fuse are left to the fused launch.
+    // a single group that gathers may run in chunks, its evaluation under its own gather (bsh::pipeline_chunks decides: first by
+    // everything that costs nothing to know, and only a run it would chunk is asked whether its launch gathers)
+    if (groups.size() == 1 && ctx->pipeline_key != 1 && groups[0].shards.size() >= 2) {
+        const Group &g = groups[0];
+        uint64_t g_blocks = 0;
+        for (const ArenaShard *s : g.shards) g_blocks += s->n_blocks;
+        bsh::PipelineCase pc{true, !B.many_terms && B.identity_cw && B.n_kinds > 0, (uint32_t)groups.size(),
+                             ctx->fold_helpers > 0 || ctx->tail_split_pct > 0 || (c.flags & BSG_PROBE_NOFUSE) != 0};
+        if (bsh::pipeline_chunks((uint32_t)g.shards.size(), g_blocks, pc, ctx->pipeline_key).size() > 1) {
+            pc.gathers = group_gathers(ctx, g, B);
+            const std::vector<uint32_t> sizes = bsh::pipeline_chunks((uint32_t)g.shards.size(), g_blocks, pc, ctx->pipeline_key);
+            if (sizes.size() > 1) return pipeline_chunked(sizes);
+        }
+    }
     const bool tail_mode = ctx->tail_split_pct && way == SurvivorsOut::kStay && !fold;
     if (tail_mode && groups.size() == 1)
         if (const size_t n0 = bsh::tail_split_cut(groups[0].shards.size(), ctx->tail_split_pct, bsg::kMaxGroupArenas)) {
@@ -1132,7 +1266,8 @@ extern "C" int32_t bsg_set_lab(bsg_ctx *ctx, uint32_t key, uint64_t value)
     // 15 (tests) = (linger microseconds << 16) | calls: a collector waits that long, or until that many calls are queued, before it collects;
     // 16 = queries asked of one arena in a cycle from which the arena is streamed once for all of them (default 8, 0 = never); 17 = microseconds a
     // queued caller polls before it sleeps (default 60); 19 = percent of a single-group device-resident run whose evaluation moves to a second
-    // stream beside the rest's probe (0 = off); 26 = 0: few-term launches never take k_probe_gather (default 1)
+    // stream beside the rest's probe (0 = off); 26 = 0: few-term launches never take k_probe_gather (default 1); 27 = chunks a single gathered group is probed in, its evaluation
+    // under its own gather (k_gather_fused; 0 = bsh::pipeline_chunks decides, 1 = never, n >= 2 = n chunks, + (percent of an equal share for the last chunk) << 16, + (1 = evaluation workgroups in front, 2 = spread) << 24)
     if (key == 12) { ctx->cmb.mode = (uint32_t)std::min<uint64_t>(value, 2); return BSG_OK; }
     if (key == 13) { ctx->cmb.sync.max_inflight = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(value, 1), 8); return BSG_OK; }
     if (key == 15) { ctx->cmb.linger_us = (uint32_t)std::min<uint64_t>(value >> 16, 1000000); ctx->cmb.linger_calls = (uint32_t)(value & 0xFFFF); return BSG_OK; }
@@ -1144,6 +1279,7 @@ extern "C" int32_t bsg_set_lab(bsg_ctx *ctx, uint32_t key, uint64_t value)
     if (key == 22) { ctx->solo_ring_wgs = (uint32_t)std::min<uint64_t>(value, 1u << 30); return BSG_OK; }
     if (key == 21) { ctx->cmb.inline_jobs = value ? 1u : 0u; return BSG_OK; }
     if (key == 26) { ctx->gather_kernel = value ? 1u : 0u; return BSG_OK; }     // 0: launches never take k_probe_gather (tools/probe_gather_lab.py: the per-block gathered path of k_probe_terms on its own)
+    if (key == 27) { ctx->pipeline_key = value & 0xFFFFFFFFull; return BSG_OK; }     // 0: bsh::pipeline_chunks decides, 1: never, n (+ last-chunk percent << 16, + placement << 24): n chunks
     if (key == 17) { ctx->cmb.sync.spin_us = (uint32_t)std::min<uint64_t>(value, 1000000); return BSG_OK; }
     return fail(BSG_E_INVALID, "unknown lab key %u", key);
 }

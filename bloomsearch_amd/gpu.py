@@ -364,7 +364,8 @@ class Context:
         self._check(self.L.bsg_set_gather_cost(self.h, bytes_per_probe))
 
     def last_probe_route(self) -> int:
-        """_lib.ROUTE_STREAM / ROUTE_GATHER: the kernel family of the last k_probe_terms(_many) / k_probe_gather dispatch (ROUTE_NONE: none yet)."""
+        """_lib.ROUTE_STREAM / ROUTE_GATHER: the kernel family of the last k_probe_terms(_many) / k_probe_gather dispatch (ROUTE_NONE: none yet);
+        ROUTE_GATHER_CHUNKED: the last group ran in chunks through k_gather_fused (set_lab key 27)."""
         r = C.c_uint32()
         self._check(self.L.bsg_lab_last_probe_route(self.h, C.byref(r)))
         return int(r.value)

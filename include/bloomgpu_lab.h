@@ -24,7 +24,12 @@ extern "C" {
  * preparation only, nothing probed; 13: cycles in flight (2; one more while cycles average > 32 calls); 15: (microseconds << 16) |
  * calls a collector waits for company (tests); 16: 3-term queries asked of one arena in a cycle from which it is streamed once for all of
  * them (8, for 35 KB of filters per block: scaled by the arena's bytes per block and the calls' distinct terms); 17: microseconds a queued caller polls while the context is quiet (60); 20: account the callers' processor time
- * (bsg_lab_query_cpu); 21: 0 = a cycle's job table is always uploaded (default 1: a table of <= ~4 KB rides in the kernel arguments); 22: workgroups of a lone call's dispatch beyond which its doorbell is a dispatch behind it (32); 24: bytes of survivor rows beyond which a cycle is served in parts (64 MB); 25: microseconds a collector polls its dispatch's doorbell before it sleeps on an event behind the dispatch (0 = adaptive, the default: 4 x the running mean of the polled waits within [50 us, 1 ms]); key 19: percent of a single-group device-resident run whose evaluation moves to a second stream (0 = off); key 26: 0 = few-term launches never take k_probe_gather, only the per-block gathered path inside k_probe_terms (default 1: bsg_set_gather_cost decides))) */
+ * (bsg_lab_query_cpu); 21: 0 = a cycle's job table is always uploaded (default 1: a table of <= ~4 KB rides in the kernel arguments); 22: workgroups of a lone call's dispatch beyond which its doorbell is a dispatch behind it (32); 24: bytes of survivor rows beyond which a cycle is served in parts (64 MB); 25: microseconds a collector polls its dispatch's doorbell before it sleeps on an event behind the dispatch (0 = adaptive, the default: 4 x the running mean of the polled waits within [50 us, 1 ms]); key 19: percent of a single-group device-resident run whose evaluation moves to a second stream (0 = off); key 26: 0 = few-term launches never take k_probe_gather, only the per-block gathered path inside k_probe_terms (default 1: bsg_set_gather_cost decides);
+ * key 27: chunks of consecutive arenas a single-group few-term launch that gathers is probed in — k_probe_gather on chunk 0, then one
+ * k_gather_fused per further chunk (gather chunk i + program evaluation of chunk i-1 in one dispatch), then k_eval_programs on the last
+ * chunk: 0 = bsh::pipeline_chunks decides (default), 1 = never, n >= 2 (low 16 bits) = n chunks as equal as possible, at most one
+ * per arena, whatever the thresholds say; bits 16-23 = percent of an equal share the last chunk gets (0 = equal); bits 24-25 = k_gather_fused's evaluation workgroups
+ * 1 = at the front of its grid, 2 = spread among the gather workgroups (0 = the default))) */
 BSG_API int32_t bsg_set_lab(bsg_ctx *ctx, uint32_t key, uint64_t value);
 /* Synchronous probes poll their stream for up to this long before they block (default 0: block at once).  A single
  * query's kernels finish in ~10 us; being woken from a blocking wait costs more than that. */
@@ -41,11 +46,12 @@ BSG_API int32_t bsg_set_fuse_limit(bsg_ctx *ctx, uint32_t max_arenas);
  * to each block's filter inside k_probe_terms (the per-block gathered path: filters beyond the LDS budget, mixed launches). */
 BSG_API int32_t bsg_set_gather_cost(bsg_ctx *ctx, uint32_t bytes_per_probe);
 /* Which kernel family the context's last probe dispatch through k_probe_terms(_many) / k_probe_gather took (the fused, folded and
- * one-dispatch paths do not report): tests assert the route instead of inferring it.  bsg_set_lab key 26 = 0 keeps every launch
+ * one-dispatch paths do not report; a group probed in chunks reports GATHER_CHUNKED): tests assert the route instead of inferring it.  bsg_set_lab key 26 = 0 keeps every launch
  * off k_probe_gather (the per-block gathered path of k_probe_terms measured on its own, tools/probe_gather_lab.py). */
 #define BSG_LAB_ROUTE_NONE   0u
 #define BSG_LAB_ROUTE_STREAM 1u
 #define BSG_LAB_ROUTE_GATHER 2u
+#define BSG_LAB_ROUTE_GATHER_CHUNKED 3u   /* the group ran in chunks: k_probe_gather + k_gather_fused ... + k_eval_programs (key 27) */
 BSG_API int32_t bsg_lab_last_probe_route(bsg_ctx *ctx, uint32_t *out_route);
 
 /* Lab (bsg_set_lab key 20 = 1 turns the accounting on): the CALLERS' own processor time, summed — out[0] profiled calls, out[1] ns

@@ -61,6 +61,11 @@ class Tokenizer(C.Structure):
 
 
 TOK_UNICODE_SPACE, TOK_LOWER = 1, 2
+TOK_NGRAM_SHIFT, TOK_NGRAM_MASK = 8, 0x700       # flags bits 8-10: the n-gram width (0, 2, 3, 4)
+
+
+def TOK_NGRAM(n: int) -> int:
+    return (n << TOK_NGRAM_SHIFT) & TOK_NGRAM_MASK
 
 
 class BloomGpuError(RuntimeError):

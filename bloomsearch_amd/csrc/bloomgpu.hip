@@ -817,6 +817,10 @@ int32_t bsg_open(const int32_t *device_ids, int32_t n_devices, bsg_ctx **out_ctx
                                     bsg::kMatchManyLdsBytes + bsg::kRxManyLdsCap));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_match_rows_many_regex_tok), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     bsg::kMatchManyLdsBytes + bsg::kRxManyLdsCap));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_match_rows_many_regex_gram), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    bsg::kMatchManyLdsBytes + bsg::kRxManyLdsCap));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_match_rows_store_regex_gram), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    bsg::kMatchWideLdsBytes + bsg::kRxWideLdsCap));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_match_rows_store_regex), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     bsg::kMatchWideLdsBytes + bsg::kRxWideLdsCap));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_match_rows_store_regex_tok), hipFuncAttributeMaxDynamicSharedMemorySize,

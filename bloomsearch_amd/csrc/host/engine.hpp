@@ -471,7 +471,7 @@ private:
         bsg_tokenizer t{};
         t.sep_ascii[0] = cfg_.tokenizer.sep[0];
         t.sep_ascii[1] = cfg_.tokenizer.sep[1];
-        t.flags = cfg_.tokenizer.flags;
+        t.flags = cfg_.tokenizer.flags | BSG_TOK_NGRAM(cfg_.tokenizer.ngram);
         return t;
     }
 

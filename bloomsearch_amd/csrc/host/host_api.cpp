@@ -68,20 +68,28 @@ bool tokenizer_from(const bsg_tokenizer *in, Tokenizer &out)
 {
     out = Tokenizer();
     if (!in) return true;
-    if ((in->sep_ascii[0] & 1u) || in->reserved || (in->flags & ~(BSG_TOK_UNICODE_SPACE | BSG_TOK_LOWER))) return false;
+    if ((in->sep_ascii[0] & 1u) || in->reserved || (in->flags & ~(BSG_TOK_UNICODE_SPACE | BSG_TOK_LOWER | BSG_TOK_NGRAM_MASK))) return false;
+    const uint32_t ngram = (in->flags & BSG_TOK_NGRAM_MASK) >> BSG_TOK_NGRAM_SHIFT;
+    if (!Tokenizer::valid_ngram(ngram)) return false;
     out.sep[0] = in->sep_ascii[0];
     out.sep[1] = in->sep_ascii[1];
-    out.flags = in->flags;
+    out.flags = in->flags & (BSG_TOK_UNICODE_SPACE | BSG_TOK_LOWER);
+    out.ngram = ngram;
     return true;
 }
 
-// "Tokenizer": {"Separators": "...", "UnicodeSpace": bool, "Lower": bool}; a missing key is Go's zero value ("", false).
-// false: not an object, a separator that is NUL or not ASCII.
+// "Tokenizer": {"Separators": "...", "UnicodeSpace": bool, "Lower": bool, "Ngram": int}; a missing key is Go's zero value ("", false, 0).
+// false: not an object, a separator that is NUL or not ASCII, an "Ngram" that is not the integer 0, 2, 3 or 4.
 bool tokenizer_from_json(const JNode &n, Tokenizer &out)
 {
     if (n.type != JType::Object) return false;
     out.sep[0] = out.sep[1] = 0;
     out.flags = 0;
+    out.ngram = 0;
+    if (const JNode *g = n.get("Ngram")) {
+        if (g->type != JType::Number || g->text.size() != 1 || g->text[0] < '0' || g->text[0] > '9' || !Tokenizer::valid_ngram(g->text[0] - '0')) return false;
+        out.ngram = g->text[0] - '0';
+    }
     if (const JNode *s = n.get("Separators")) {
         if (s->type != JType::String) return false;
         for (unsigned char c : s->text) {

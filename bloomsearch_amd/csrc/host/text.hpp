@@ -161,21 +161,47 @@ struct Tokenizer {
     static constexpr uint64_t kWhiteSpace = (1ull << 9) | (1ull << 10) | (1ull << 11) | (1ull << 12) | (1ull << 13) | (1ull << 32);
     uint64_t sep[2] = {kWhiteSpace, 0};
     uint32_t flags = kUnicodeSpace | kLower;
+    uint32_t ngram = 0;                                           // BSG_TOK_NGRAM: 0, or 2..4 = a word's windows of that many runes
 
-    bool is_default() const { return sep[0] == kWhiteSpace && sep[1] == 0 && flags == (kUnicodeSpace | kLower); }
+    static bool valid_ngram(uint64_t n) { return n == 0 || (n >= 2 && n <= 4); }
+    bool is_default() const { return sep[0] == kWhiteSpace && sep[1] == 0 && flags == (kUnicodeSpace | kLower) && ngram == 0; }
     bool lower() const { return (flags & kLower) != 0; }
     // the rune AFTER lowering
     bool is_sep(uint32_t r) const { return r < 0x80 ? ((sep[r >> 6] >> (r & 63)) & 1) != 0 : ((flags & kUnicodeSpace) != 0 && is_space(r)); }
-    bool operator==(const Tokenizer &o) const { return sep[0] == o.sep[0] && sep[1] == o.sep[1] && flags == o.flags; }
+    bool operator==(const Tokenizer &o) const { return sep[0] == o.sep[0] && sep[1] == o.sep[1] && flags == o.flags && ngram == o.ngram; }
 };
 
-// fn(token) for each token of `text` under t, the token's bytes as they are after lowering (buf is scratch).  The default
-// tokenizer takes the forEachWord + appendFoldedWord path above.  strings.ToLower turns an invalid byte into U+FFFD;
-// without lowering FieldsFunc keeps the raw byte inside its word (it decodes it as U+FFFD, which is no separator).
+// grams(w, n) of bloomgpu.h: fn(w) if w has at most n runes, else fn(window) for every n consecutive runes of w.  Runes as Go's
+// `range` decodes them: an invalid byte is one rune of width 1.  false: fn asked to stop.
 template <class F>
-inline void for_each_token(std::string_view text, const Tokenizer &t, std::string &buf, F &&fn)
+inline bool for_each_gram(std::string_view w, uint32_t n, F &&fn)
 {
-    if (t.is_default()) {
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(w.data());
+    size_t start[5];                       // byte offsets of the last n + 1 rune starts, as a ring
+    size_t runes = 0;
+    for (size_t i = 0; i < w.size();) {
+        start[runes % (n + 1)] = i;
+        ++runes;
+        size_t width;
+        (void)decode_rune(p + i, w.size() - i, width);
+        i += width;
+        if (runes >= n) {
+            const size_t from = start[(runes - n) % (n + 1)];
+            if (!fn(w.substr(from, i - from))) return false;
+        }
+    }
+    if (runes < n && runes > 0) return fn(w);
+    return true;
+}
+
+// fn(word) for each word of `text` under t's separators and flags (the width aside), the word's bytes as they are after lowering
+// (buf is scratch).  The default tokenizer takes the forEachWord + appendFoldedWord path above.  strings.ToLower turns an
+// invalid byte into U+FFFD; without lowering FieldsFunc keeps the raw byte inside its word (it decodes it as U+FFFD, which is
+// no separator).
+template <class F>
+inline void for_each_spec_word(std::string_view text, const Tokenizer &t, std::string &buf, F &&fn)
+{
+    if (t.sep[0] == Tokenizer::kWhiteSpace && t.sep[1] == 0 && t.flags == (Tokenizer::kUnicodeSpace | Tokenizer::kLower)) {
         for_each_word(text, [&](std::string_view word) {
             buf.clear();
             append_folded_word(buf, word);
@@ -203,6 +229,15 @@ inline void for_each_token(std::string_view text, const Tokenizer &t, std::strin
         i += w;
     }
     if (!buf.empty()) fn(std::string_view(buf));
+}
+
+// ... and with an n-gram width, each of those words cut into its windows (for_each_gram).  The one site the host walker,
+// EntrySets, RowMatcher, bsh_tokenize_with and the fallback rows tokenize through.
+template <class F>
+inline void for_each_token(std::string_view text, const Tokenizer &t, std::string &buf, F &&fn)
+{
+    if (t.ngram == 0) { for_each_spec_word(text, t, buf, fn); return; }
+    for_each_spec_word(text, t, buf, [&](std::string_view word) { return for_each_gram(word, t.ngram, fn); });
 }
 
 }  // namespace bsh

@@ -387,6 +387,11 @@ struct Walker {
     uint32_t iters;          // lab: trips of the walker_step loop
 #endif
     HashStream ps, tok, ft;  // path + "::" prefix state; current word; current path::word
+    // n-gram walkers only (TokGramP): the current word's last <= n runes as their bytes, oldest first, little-endian over g_lo then
+    // g_hi (n <= 4 runes of <= 4 bytes: 16 bytes), zero above them.  g_meta: runes held (bits 0-2), bytes held (3-7), the runes'
+    // lengths as nibbles, oldest lowest (8-23).  Valid while in_token; no other walker touches them.
+    uint64_t g_lo, g_hi;
+    uint32_t g_meta;
 };
 
 __device__ __forceinline__ bool is_plain(uint32_t c) { return c >= 0x20u && c < 0x7Fu && c != '\\'; }
@@ -419,14 +424,14 @@ struct TokSpec {
     uint64_t run[2];      // raw without '"', '\\', DEL and controls: the separators the S_STR run scan stops on
     uint64_t low[2];      // bit c: an ASCII rune c AFTER lowering ends a word (a non-ASCII rune may lower to one: U+212A -> k)
     uint32_t flags;       // BSG_TOK_UNICODE_SPACE (1): runes >= 0x80 with unicode.IsSpace end a word; BSG_TOK_LOWER (2)
-    uint32_t pad;
+    uint32_t ngram;       // 0: the words themselves; 2..4: every window of that many runes of a word (TokGramP), a shorter word whole
 };
 constexpr uint32_t kTokUnicodeSpace = 1u, kTokLower = 2u;
 
 __device__ __forceinline__ bool bit128(const uint64_t m[2], uint32_t c) { return ((m[(c >> 6) & 1u] >> (c & 63u)) & 1u) != 0u; }
 
 struct TokDefault {
-    static constexpr bool kSpec = false;
+    static constexpr bool kSpec = false, kGram = false;
     __device__ __forceinline__ bool lower() const { return true; }
     __device__ __forceinline__ bool sep_byte(uint32_t b) const { return ascii_space(b); }
     __device__ __forceinline__ bool run_sep(uint32_t b) const { return b == ' '; }          // a byte the S_STR run scan stopped on
@@ -438,7 +443,7 @@ struct TokDefault {
 // against k_ingest_rows' 3.25 ms (1.12x); the 18-separator punctuation spec 3.88 ms for 10 % more words (1.08x per word).
 // Per-separator swar_eq and a coarse SWAR punctuation filter were not tried: the bitmap already meets the 1.25x bar.
 struct TokSpecP {
-    static constexpr bool kSpec = true;
+    static constexpr bool kSpec = true, kGram = false;
     TokSpec t;
     __device__ __forceinline__ bool lower() const { return (t.flags & kTokLower) != 0u; }
     __device__ __forceinline__ bool sep_byte(uint32_t b) const { return bit128(t.raw, b); }      // an ASCII byte of the text
@@ -460,10 +465,83 @@ struct TokSpecP {
     }
 };
 
+// A spec with an n-gram width (bloomgpu.h BSG_TOK_NGRAM): the words are TokSpecP's, and a word of more than n runes is replaced
+// by its windows of n consecutive runes (after lowering); a word of at most n runes stays one token.  Every branch the width
+// adds to the walker is `if constexpr (TOK::kGram)`: the other two policies compile to what they were.
+struct TokGramP : TokSpecP {
+    static constexpr bool kGram = true;
+    __device__ __forceinline__ explicit TokGramP(const TokSpec &s) : TokSpecP{s} {}
+    __device__ __forceinline__ uint32_t width() const { return t.ngram; }
+};
+
+// w.tok = the ring's bytes, w.ft = path + "::" + the ring's bytes: what the emission round finishes for a Q_WORD request.  The
+// ring holds 1..16 bytes: hs_absorb_n takes them as its low word and, past 8 bytes, the rest of the high one.  The rounds call
+// this (word_request) in their converged part, once for the wave, when they take the request: a lane that raised Q_WORD returned
+// to the round at once, so the ring still is the window.  Between requests an n-gram walker keeps the ring and w.ps only;
+// w.tok and w.ft are not live across the parse (built inside the divergent walker_step at each of its fifteen raise sites
+// instead, k_ingest_rows_gram spilled 66 VGPRs against its _tok sibling's 24).
+__device__ __forceinline__ void gram_window(Walker &w)
+{
+    const uint32_t tot = (w.g_meta >> 3) & 31u, head = tot < 8u ? tot : 8u;
+    hs_init(w.tok, w.key);
+    hs_absorb_n(w.tok, w.g_lo, head, w.key);
+    if (tot > 8u) hs_absorb_n(w.tok, w.g_hi, tot - 8u, w.key);
+    if (w.ft_on) {
+        w.ft = w.ps;
+        hs_absorb_n(w.ft, w.g_lo, head, w.key);
+        if (tot > 8u) hs_absorb_n(w.ft, w.g_hi, tot - 8u, w.key);
+    }
+}
+
+// One rune of the current word (len 1..4 bytes, little-endian in `bytes`, already lowered) joins the ring; a ring that holds n
+// runes drops its oldest first.  With n runes in the ring the window is a token: the lane raises Q_WORD (the caller returns to
+// the emission round before it takes another byte).  Shift counts: dropping a rune shifts the 128 bits right by 8..32 (its
+// complement 32..56); a rune that straddles the two words starts at byte 5..7, so its upper part shifts right by 8..24.  No
+// count is 64, and none is 0 where its complement is used.
+template <class TOK>
+__device__ __forceinline__ void gram_push(Walker &w, uint32_t bytes, uint32_t len, const TOK &tk)
+{
+    const uint32_t n = tk.width();
+    if (!w.in_token) { w.g_lo = w.g_hi = 0; w.g_meta = 0; w.in_token = true; }
+    uint32_t cnt = w.g_meta & 7u, tot = (w.g_meta >> 3) & 31u, lens = w.g_meta >> 8;
+    if (cnt == n) {
+        const uint32_t l0 = lens & 15u, sh = l0 * 8u;
+        w.g_lo = (w.g_lo >> sh) | (w.g_hi << (64u - sh));
+        w.g_hi >>= sh;
+        lens >>= 4;
+        --cnt;
+        tot -= l0;
+    }
+    const uint64_t v = bytes;
+    if (tot < 8u) {
+        w.g_lo |= v << (tot * 8u);
+        if (tot + len > 8u) w.g_hi |= v >> ((8u - tot) * 8u);
+    } else {
+        w.g_hi |= v << ((tot - 8u) * 8u);
+    }
+    lens |= len << (4u * cnt);
+    ++cnt;
+    tot += len;                                    // <= 3 runes before + this one: <= 16
+    w.g_meta = cnt | (tot << 3) | (lens << 8);
+    if (cnt == n) w.req = Q_WORD;
+}
+
+// a round's first step for a Q_WORD request: the words' walkers have w.tok / w.ft ready, an n-gram walker builds them from its ring
+template <class TOK>
+__device__ __forceinline__ void word_request(Walker &w)
+{
+    if constexpr (TOK::kGram) gram_window(w);
+}
+
 template <class TOK>
 __device__ __forceinline__ void word_byte(Walker &w, uint32_t c, const TOK &tk)
 {
     if (w.quiet) return;
+    if constexpr (TOK::kGram) {
+        if (tk.lower() && c - 'A' < 26u) c += 32;
+        gram_push(w, c, 1u, tk);
+        return;
+    }
     if (!w.in_token) { hs_init(w.tok, w.key); w.ft = w.ps; w.in_token = true; }
     if (tk.lower() && c - 'A' < 26u) c += 32;      // ASCII fold (appendFoldedWord fast path, row_matcher.go:187-202)
     hs_absorb(w.tok, c, w.key);
@@ -483,10 +561,16 @@ __device__ __forceinline__ void word_run(Walker &w, uint64_t v, uint32_t n, cons
 
 __device__ __forceinline__ uint32_t c_at(uint64_t v, uint32_t i) { return (uint32_t)(v >> (i * 8u)) & 0xFFu; }
 
-__device__ __forceinline__ bool word_end(Walker &w)
+// TokGramP: a word that ended with n runes in the ring has had its last window emitted by gram_push; a shorter one is its own
+// token.  So a step raises at most one request: gram_push with the ring full, or this with the ring short.
+template <class TOK>
+__device__ __forceinline__ bool word_end(Walker &w, const TOK &tk)
 {
     if (w.quiet || !w.in_token) return false;
     w.in_token = false;
+    if constexpr (TOK::kGram) {
+        if ((w.g_meta & 7u) >= tk.width()) return false;
+    }
     w.req = Q_WORD;
     return true;
 }
@@ -536,8 +620,9 @@ __device__ __forceinline__ uint32_t hex_value(uint32_t c)
 template <class TOK>
 __device__ __forceinline__ bool str_decoded_byte(Walker &w, uint32_t b, const TOK &tk)
 {
-    if (tk.sep_byte(b)) return word_end(w);
+    if (tk.sep_byte(b)) return word_end(w, tk);
     word_byte(w, b, tk);
+    if constexpr (TOK::kGram) return w.req != Q_NONE;       // the byte closed a window
     return false;
 }
 // UTF-8 encoding of a rune >= 0x80 (not a surrogate, <= 0x10FFFF) as little-endian bytes in a u32; n = its length
@@ -563,9 +648,9 @@ __device__ __forceinline__ uint32_t str_rune(Walker &w, uint32_t r, const TOK &t
             lo = r < 0x20000u ? w.lower[r] : 0u;
             if (lo == 0xFFFFFFFFu) return R_FAIL;
         }
-        if (tk.sep_rune(lo != 0u ? lo : r)) return word_end(w) ? R_CONTINUE : 0xFFu;
+        if (tk.sep_rune(lo != 0u ? lo : r)) return word_end(w, tk) ? R_CONTINUE : 0xFFu;
     } else {
-        if (rune_space(r)) return word_end(w) ? R_CONTINUE : 0xFFu;
+        if (rune_space(r)) return word_end(w, tk) ? R_CONTINUE : 0xFFu;
         // (the validation pass looks the rune up too: a code point these tables do not know sends the row to the host, whose
         // own unicode.ToLower decides — a newer Unicode may have made it a cased letter)
         lo = r < 0x20000u ? w.lower[r] : 0u;
@@ -575,9 +660,14 @@ __device__ __forceinline__ uint32_t str_rune(Walker &w, uint32_t r, const TOK &t
         if (lo != 0u) r = lo;
         uint32_t n = 1, bytes = r;
         if (r >= 0x80u) bytes = rune_utf8(r, n);
-        if (!w.in_token) { hs_init(w.tok, w.key); w.ft = w.ps; w.in_token = true; }
-        hs_absorb_n(w.tok, bytes, n, w.key);
-        if (w.ft_on) hs_absorb_n(w.ft, bytes, n, w.key);
+        if constexpr (TOK::kGram) {
+            gram_push(w, bytes, n, tk);
+            if (w.req != Q_NONE) return R_CONTINUE;
+        } else {
+            if (!w.in_token) { hs_init(w.tok, w.key); w.ft = w.ps; w.in_token = true; }
+            hs_absorb_n(w.tok, bytes, n, w.key);
+            if (w.ft_on) hs_absorb_n(w.ft, bytes, n, w.key);
+        }
     }
     return 0xFFu;
 }
@@ -632,7 +722,7 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &
         if (w.pos >= w.end) {
             if (w.st == S_NUM && num_accepting(w.aux)) {          // a number ends with the row
                 w.st = S_AFTER;
-                if (word_end(w)) return R_CONTINUE;
+                if (word_end(w, tk)) return R_CONTINUE;
             }
             return (w.st == S_AFTER && w.depth == 0) ? R_DONE : R_FAIL;
         }
@@ -801,6 +891,17 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &
             else stops = swar_str_stops(v);
             uint32_t n = stops ? (uint32_t)(__builtin_ctzll(stops) >> 3) : 8u;
             if (n > avail) n = avail;
+            if constexpr (TOK::kGram) {
+                // one rune per step: a window may close on it, and its request is served before the next byte is taken (a leaf
+                // that emits nothing, and the validation pass, keep the 8-byte scan)
+                if (n != 0u && !w.quiet) {
+                    rx.feed(c);
+                    word_byte(w, c, tk);
+                    ++w.pos;
+                    if (w.req != Q_NONE) return R_CONTINUE;
+                    break;
+                }
+            }
             if (n != 0u) {
                 rx.feed_run(v, n);
                 word_run(w, n == 8u ? v : (v & ((1ULL << (n * 8u)) - 1ULL)), n, tk);
@@ -809,8 +910,8 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &
             if (n < avail) {                                        // stopped on a byte inside the chunk
                 const uint32_t b = c_at(v, n);
                 ++w.pos;
-                if (b == '"') { w.st = S_AFTER; if (word_end(w)) return R_CONTINUE; }
-                else if (tk.run_sep(b)) { rx.feed(b); if (word_end(w)) return R_CONTINUE; }   // raw white space other than 0x20 fails here
+                if (b == '"') { w.st = S_AFTER; if (word_end(w, tk)) return R_CONTINUE; }
+                else if (tk.run_sep(b)) { rx.feed(b); if (word_end(w, tk)) return R_CONTINUE; }   // raw white space other than 0x20 fails here
                 else if (b == '\\') w.st = S_STR_ESC;
                 else if (b >= 0xC2u && b <= 0xF4u) {                // UTF-8 lead byte (decode_rune, text.hpp)
                     uint32_t left, lo = 0x80u, hi = 0xBFu;
@@ -828,13 +929,14 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &
             const uint32_t nx = num_next(w.aux, c);
             if (nx != 0xFFu) {
                 w.aux = nx; rx.feed(c); ++w.pos;
-                if (TOK::kSpec && tk.sep_byte(c)) { if (word_end(w)) return R_CONTINUE; }   // "-1.5e-3" with '.' '-': 1, 5e, 3
+                if (TOK::kSpec && tk.sep_byte(c)) { if (word_end(w, tk)) return R_CONTINUE; }   // "-1.5e-3" with '.' '-': 1, 5e, 3
                 else word_byte(w, c, tk);
+                if constexpr (TOK::kGram) { if (w.req != Q_NONE) return R_CONTINUE; }
                 break;
             }
             if (!num_accepting(w.aux)) return R_FAIL;
             w.st = S_AFTER;                                         // c is not part of the number: S_AFTER looks at it
-            if (word_end(w)) return R_CONTINUE;
+            if (word_end(w, tk)) return R_CONTINUE;
             break;
         }
         case S_LIT: {
@@ -846,18 +948,19 @@ __device__ __forceinline__ uint32_t walker_step(Walker &w, ChunkCursor &cc, RX &
             ++w.aux;
             if constexpr (TOK::kSpec) {
                 bool ended = false;                                 // a separator inside true / false splits it
-                if (w.lit != 2u) { rx.feed(c); if (tk.sep_byte(c)) ended = word_end(w); else word_byte(w, c, tk); }
+                if (w.lit != 2u) { rx.feed(c); if (tk.sep_byte(c)) ended = word_end(w, tk); else word_byte(w, c, tk); }
                 if (w.aux == (w.lit == 1u ? 5u : 4u)) {
                     w.st = S_AFTER;
-                    ended |= word_end(w);                           // (never both: a separator has already closed the word)
+                    ended |= word_end(w, tk);                           // (never both: a separator has already closed the word)
                 }
+                if constexpr (TOK::kGram) ended |= w.req != Q_NONE;   // the byte closed a window
                 if (ended) return R_CONTINUE;
                 break;
             }
             if (w.lit != 2u) { rx.feed(c); word_byte(w, c, tk); }   // null: field existence only (tokenizer.go:130-131)
             if (w.aux == (w.lit == 1u ? 5u : 4u)) {
                 w.st = S_AFTER;
-                if (word_end(w)) return R_CONTINUE;
+                if (word_end(w, tk)) return R_CONTINUE;
             }
             break;
         }
@@ -1077,7 +1180,7 @@ __device__ __forceinline__ void ingest_rows_body(const IngestArgs &a, const TOK 
         const uint32_t plen = (q == Q_FIELD || q == Q_LEAF) ? w.req_len : 0u;
         for (uint32_t i = 0; __ballot(i < plen) != 0ull; ++i)
             if (i < plen) hs_absorb(s, w.path[i], w.key);
-        if (q == Q_WORD) s = w.tok;
+        if (q == Q_WORD) { word_request<TOK>(w); s = w.tok; }
         uint64_t ha[4], hb[4], fa = 0, fb = 0;
         if (q != Q_NONE) fa = hs_finish(s, ha, w.key);
         if (q == Q_LEAF) {                          // the leaf's words continue from path + "::" (makeFieldTokenKey, tokenizer.go:509-511)
@@ -1115,11 +1218,17 @@ __device__ __forceinline__ void ingest_rows_body(const IngestArgs &a, const TOK 
 __global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows(const IngestArgs a) { ingest_rows_body(a, TokDefault{}, RowsGrouped{}); }
 // the same walk under a separator-family tokenizer spec (bsg_ingest_rows_tok)
 __global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows_tok(const IngestArgs a, const TokSpec t) { ingest_rows_body(a, TokSpecP{t}, RowsGrouped{}); }
+// ... and under a spec with an n-gram width
+__global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows_gram(const IngestArgs a, const TokSpec t) { ingest_rows_body(a, TokGramP(t), RowsGrouped{}); }
 // ... and over a batch whose rows belong to arbitrary sets in arrival order (bsg_ingest_append_rows): a.set_first_row is unused
 __global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows_sets(const IngestArgs a, const RowsBySet rows) { ingest_rows_body(a, TokDefault{}, rows); }
 __global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows_sets_tok(const IngestArgs a, const RowsBySet rows, const TokSpec t)
 {
     ingest_rows_body(a, TokSpecP{t}, rows);
+}
+__global__ __launch_bounds__(kIngestThreads, BSG_INGEST_WPE) void k_ingest_rows_sets_gram(const IngestArgs a, const RowsBySet rows, const TokSpec t)
+{
+    ingest_rows_body(a, TokGramP(t), rows);
 }
 
 // ---------------- host-walked entries (fallback rows) ----------------

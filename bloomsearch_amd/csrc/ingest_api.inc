@@ -113,13 +113,16 @@ int32_t tok_spec(const bsg_tokenizer *in, bsg_tokenizer &rec, bsg::TokSpec &out,
     rec = in ? *in : default_tokenizer();
     if (rec.sep_ascii[0] & 1u) return fail(BSG_E_INVALID, "tokenizer: NUL cannot be a separator");
     if (rec.reserved) return fail(BSG_E_INVALID, "tokenizer: reserved must be 0");
-    if (rec.flags & ~(BSG_TOK_UNICODE_SPACE | BSG_TOK_LOWER)) return fail(BSG_E_INVALID, "tokenizer: unknown flags 0x%x", rec.flags);
+    if (rec.flags & ~(BSG_TOK_UNICODE_SPACE | BSG_TOK_LOWER | BSG_TOK_NGRAM_MASK)) return fail(BSG_E_INVALID, "tokenizer: unknown flags 0x%x", rec.flags);
+    const uint32_t ngram = (rec.flags & BSG_TOK_NGRAM_MASK) >> BSG_TOK_NGRAM_SHIFT;
+    if (ngram == 1u || ngram > 4u) return fail(BSG_E_INVALID, "tokenizer: n-gram width %u (0, 2, 3 or 4)", ngram);
     const bsg_tokenizer d = default_tokenizer();
-    is_default = rec.sep_ascii[0] == d.sep_ascii[0] && rec.sep_ascii[1] == d.sep_ascii[1] && rec.flags == d.flags;
+    is_default = rec.sep_ascii[0] == d.sep_ascii[0] && rec.sep_ascii[1] == d.sep_ascii[1] && rec.flags == d.flags;   // (a width is not the default)
     const bool lower = rec.flags & BSG_TOK_LOWER;
     auto bit = [&](uint32_t c) { return (rec.sep_ascii[c >> 6] >> (c & 63u)) & 1u; };
     out = bsg::TokSpec{};
-    out.flags = rec.flags;
+    out.flags = rec.flags & (BSG_TOK_UNICODE_SPACE | BSG_TOK_LOWER);
+    out.ngram = ngram;                        // non-zero: the _gram walkers (TokGramP)
     for (uint32_t c = 1; c < 128; ++c) {
         const uint32_t folded = (lower && c - 'A' < 26u) ? c + 32 : c;
         const uint64_t b = bit(folded);
@@ -371,7 +374,9 @@ int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *
         RowUpload up(d, rows, d_rows, row_off, n_rows, ctx->ingest_chunk_bytes);
         if (int32_t rc = walk_chunks(d, G, up, a, n_sets * 3, trace, [](uint32_t) { return hipSuccess; },
                 [&](const bsg::IngestArgs &b, uint32_t grid, hipEvent_t e0, hipEvent_t e1) {
-                    if (tok)
+                    if (tok && tok->ngram)
+                        hipExtLaunchKernelGGL(bsg::k_ingest_rows_gram, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, *tok);
+                    else if (tok)
                         hipExtLaunchKernelGGL(bsg::k_ingest_rows_tok, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, *tok);
                     else
                         hipExtLaunchKernelGGL(bsg::k_ingest_rows, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b);
@@ -912,7 +917,9 @@ int32_t append_rows_stream(bsg_ctx *ctx, Ingest &I, const uint8_t *rows, const u
                 return e;
             },
             [&](const bsg::IngestArgs &b, uint32_t grid, hipEvent_t e0, hipEvent_t e1) {
-                if (!I.tok_default)
+                if (!I.tok_default && I.spec.ngram)
+                    hipExtLaunchKernelGGL(bsg::k_ingest_rows_sets_gram, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, by_set, I.spec);
+                else if (!I.tok_default)
                     hipExtLaunchKernelGGL(bsg::k_ingest_rows_sets_tok, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, by_set, I.spec);
                 else
                     hipExtLaunchKernelGGL(bsg::k_ingest_rows_sets, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, by_set);

@@ -270,7 +270,7 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
         const uint32_t plen = (q == Q_FIELD || q == Q_LEAF) ? w.req_len : 0u;
         for (uint32_t i = 0; __ballot(i < plen) != 0ull; ++i)
             if (i < plen) hs_absorb(s, w.path[i], w.key);
-        if (q == Q_WORD) s = w.tok;
+        if (q == Q_WORD) { word_request<TOK>(w); s = w.tok; }
         uint64_t h[4] = {0, 0, 0, 0}, fp = 0;
         if (q != Q_NONE) fp = hs_finish(s, h, w.key);
         if (q == Q_LEAF) leaf_mask = 0;
@@ -400,6 +400,12 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_regex_tok(const M
 {
     match_rows_body<true>(a, x, TokSpecP{t});
 }
+// ... and under a spec with an n-gram width (TokGramP): Token and FieldToken conditions compare a row's n-rune windows
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_gram(const MatchArgs a, const TokSpec t) { match_rows_body<false>(a, RxArgs{}, TokGramP(t)); }
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_regex_gram(const MatchArgs a, const RxArgs x, const TokSpec t)
+{
+    match_rows_body<true>(a, x, TokGramP(t));
+}
 // a batch of queries over one table of Field / Token / FieldToken conditions; dynamic LDS kMatchManyLdsBytes
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many(const MatchArgs a, const MatchManyArgs m)
 {
@@ -408,6 +414,10 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many(const MatchA
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_tok(const MatchArgs a, const MatchManyArgs m, const TokSpec t)
 {
     match_rows_body<false, TokSpecP, true>(a, RxArgs{}, TokSpecP{t}, m);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_gram(const MatchArgs a, const MatchManyArgs m, const TokSpec t)
+{
+    match_rows_body<false, TokGramP, true>(a, RxArgs{}, TokGramP(t), m);
 }
 // a batch of queries with FieldRegex conditions in the table; dynamic LDS kMatchManyLdsBytes + the table blob (<= kRxManyLdsCap)
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex(const MatchArgs a, const RxArgs x, const MatchManyArgs m)
@@ -418,8 +428,12 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_tok(co
 {
     match_rows_body<true, TokSpecP, true, kRxManyActive>(a, x, TokSpecP{t}, m);
 }
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_gram(const MatchArgs a, const RxArgs x, const MatchManyArgs m, const TokSpec t)
+{
+    match_rows_body<true, TokGramP, true, kRxManyActive>(a, x, TokGramP(t), m);
+}
 
-// the storing walker (bsg_match_rows_wide): plain / regex x default / spec tokenizer; dynamic LDS kMatchWideLdsBytes (+ the table
+// the storing walker (bsg_match_rows_wide): plain / regex x default / spec / n-gram tokenizer; dynamic LDS kMatchWideLdsBytes (+ the table
 // blob, <= kRxWideLdsCap)
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_store(const MatchArgs a, const MatchWideArgs wd)
 {
@@ -436,6 +450,14 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex(const
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_tok(const MatchArgs a, const RxArgs x, const MatchWideArgs wd, const TokSpec t)
 {
     match_rows_body<true, TokSpecP, false, kRxActive, true>(a, x, TokSpecP{t}, MatchManyArgs{}, wd);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_gram(const MatchArgs a, const MatchWideArgs wd, const TokSpec t)
+{
+    match_rows_body<false, TokGramP, false, kRxActive, true>(a, RxArgs{}, TokGramP(t), MatchManyArgs{}, wd);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_gram(const MatchArgs a, const RxArgs x, const MatchWideArgs wd, const TokSpec t)
+{
+    match_rows_body<true, TokGramP, false, kRxActive, true>(a, x, TokGramP(t), MatchManyArgs{}, wd);
 }
 
 // The programs of the listed (set, query) pairs over the stored flags.  Wave w of the grid owns item w: one 64-row tile of one set

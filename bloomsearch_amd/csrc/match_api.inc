@@ -155,7 +155,7 @@ int32_t lower_programs(MatchCall &mc, const Family &f, const uint32_t *prog_ops,
     return BSG_OK;
 }
 
-// ---- the sixteen walkers: (single / many / wide / lookup) x (regex) x (tokenizer spec) ----
+// ---- the twenty-four walkers: (single / many / wide / lookup) x (regex) x (default tokenizer / spec / spec with an n-gram width) ----
 // E: the mode's own argument struct (none, MatchManyArgs, MatchWideArgs, MatchLookupArgs).  Dynamic LDS: the mode's base (the lookup
 // walkers': what the launch's tables take) plus the regex blob's bytes (a call without regex conditions has no blob).
 template <class... E>
@@ -164,14 +164,18 @@ struct Walkers {
     void (*tok)(bsg::MatchArgs, E..., bsg::TokSpec);
     void (*regex)(bsg::MatchArgs, bsg::RxArgs, E...);
     void (*regex_tok)(bsg::MatchArgs, bsg::RxArgs, E..., bsg::TokSpec);
+    void (*gram)(bsg::MatchArgs, E..., bsg::TokSpec);
+    void (*regex_gram)(bsg::MatchArgs, bsg::RxArgs, E..., bsg::TokSpec);
 };
-constexpr Walkers<> kSingleWalkers{bsg::k_match_rows, bsg::k_match_rows_tok, bsg::k_match_rows_regex, bsg::k_match_rows_regex_tok};
+constexpr Walkers<> kSingleWalkers{bsg::k_match_rows, bsg::k_match_rows_tok, bsg::k_match_rows_regex, bsg::k_match_rows_regex_tok,
+                                 bsg::k_match_rows_gram, bsg::k_match_rows_regex_gram};
 constexpr Walkers<bsg::MatchManyArgs> kManyWalkers{bsg::k_match_rows_many, bsg::k_match_rows_many_tok, bsg::k_match_rows_many_regex,
-                                                   bsg::k_match_rows_many_regex_tok};
+                                                   bsg::k_match_rows_many_regex_tok, bsg::k_match_rows_many_gram, bsg::k_match_rows_many_regex_gram};
 constexpr Walkers<bsg::MatchWideArgs> kWideWalkers{bsg::k_match_rows_store, bsg::k_match_rows_store_tok, bsg::k_match_rows_store_regex,
-                                                   bsg::k_match_rows_store_regex_tok};
+                                                   bsg::k_match_rows_store_regex_tok, bsg::k_match_rows_store_gram, bsg::k_match_rows_store_regex_gram};
 constexpr Walkers<bsg::MatchLookupArgs> kLookupWalkers{bsg::k_match_rows_lookup, bsg::k_match_rows_lookup_tok, bsg::k_match_rows_lookup_regex,
-                                                       bsg::k_match_rows_lookup_regex_tok};   // regex: bsg_match_rows_lookup_regex(_rows) only
+                                                       bsg::k_match_rows_lookup_regex_tok, bsg::k_match_rows_lookup_gram,
+                                                       bsg::k_match_rows_lookup_regex_gram};   // regex: bsg_match_rows_lookup_regex(_rows) only
 
 // one chunk's walk: a.n_rows rows, one per lane, between the events k0 and k1
 template <class... E>
@@ -181,7 +185,10 @@ void launch_walker(const Walkers<E...> &w, uint32_t lds_base, hipStream_t stream
     const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads), block(bsg::kIngestThreads);
     const uint32_t lds = lds_base + x.n_words * 4;
     assert(!x.n_rx || (w.regex && w.regex_tok));   // every family has its regex walkers; a call that takes none refuses FieldRegex conditions before it gets here
-    if (x.n_rx && tok) hipExtLaunchKernelGGL(w.regex_tok, grid, block, lds, stream, k0, k1, 0, a, x, e..., *tok);
+    const bool gram = tok && tok->ngram != 0u;     // a spec with an n-gram width: its own walkers
+    if (x.n_rx && gram) hipExtLaunchKernelGGL(w.regex_gram, grid, block, lds, stream, k0, k1, 0, a, x, e..., *tok);
+    else if (gram) hipExtLaunchKernelGGL(w.gram, grid, block, lds, stream, k0, k1, 0, a, e..., *tok);
+    else if (x.n_rx && tok) hipExtLaunchKernelGGL(w.regex_tok, grid, block, lds, stream, k0, k1, 0, a, x, e..., *tok);
     else if (x.n_rx) hipExtLaunchKernelGGL(w.regex, grid, block, lds, stream, k0, k1, 0, a, x, e...);
     else if (tok) hipExtLaunchKernelGGL(w.tok, grid, block, lds, stream, k0, k1, 0, a, e..., *tok);
     else hipExtLaunchKernelGGL(w.plain, grid, block, lds, stream, k0, k1, 0, a, e...);

@@ -118,7 +118,7 @@ __device__ __forceinline__ void match_rows_lookup_body(const MatchArgs &a, const
         const uint32_t plen = (q == Q_FIELD || q == Q_LEAF) ? w.req_len : 0u;
         for (uint32_t i = 0; __ballot(i < plen) != 0ull; ++i)
             if (i < plen) hs_absorb(s, w.path[i], w.key);
-        if (q == Q_WORD) s = w.tok;
+        if (q == Q_WORD) { word_request<TOK>(w); s = w.tok; }
         uint64_t h[4] = {0, 0, 0, 0}, fp = 0;
         if (q != Q_NONE) fp = hs_finish(s, h, w.key);
         if (q == Q_LEAF) leaf_fid = bsh_lookup::kNoString;
@@ -216,6 +216,15 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_lookup_regex(cons
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_lookup_regex_tok(const MatchArgs a, const RxArgs x, const MatchLookupArgs lk, const TokSpec t)
 {
     match_rows_lookup_body<true>(a, x, lk, TokSpecP{t});
+}
+// the same two under a spec with an n-gram width (TokGramP)
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_lookup_gram(const MatchArgs a, const MatchLookupArgs lk, const TokSpec t)
+{
+    match_rows_lookup_body<false>(a, RxArgs{}, lk, TokGramP(t));
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_lookup_regex_gram(const MatchArgs a, const RxArgs x, const MatchLookupArgs lk, const TokSpec t)
+{
+    match_rows_lookup_body<true>(a, x, lk, TokGramP(t));
 }
 
 // k_eval_row_programs over W flag words per row (word-major over the part's part_rows rows).  Items, pairs, programs: RowEvalArgs.

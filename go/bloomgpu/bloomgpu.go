@@ -791,14 +791,24 @@ func (g *Context) PinnedFree(b []byte) error {
 // Tokenizer is a tokenizer of the separator family (bsg_tokenizer): tokens = strings.FieldsFunc(v lowered when Lower, isSep),
 // isSep(r) = r is an ASCII rune in Separators, or (UnicodeSpace) r >= 0x80 with unicode.IsSpace.  Separators are tested after
 // lowering.  {" \t\n\v\f\r", true, true} is BasicWhitespaceLowerTokenizer.
+//
+// Ngram is 0 (the words themselves) or 2, 3, 4: every word of more than Ngram runes is replaced by its windows of Ngram
+// consecutive runes, a word of at most Ngram runes stays one token (bloomgpu.h, BSG_TOK_NGRAM).  Windows never cross a separator.
+// Query tokens are compared literally: a substring query ANDs the full windows of its needle and never uses a needle word
+// shorter than Ngram as a token.
 type Tokenizer struct {
 	Separators   string
 	UnicodeSpace bool
 	Lower        bool
+	Ngram        int
 }
 
-// Validate refuses a separator that is NUL or not ASCII (the device tests ASCII separators only).
+// Validate refuses a separator that is NUL or not ASCII (the device tests ASCII separators only) and an n-gram width other
+// than 0, 2, 3 or 4.
 func (t Tokenizer) Validate() error {
+	if t.Ngram != 0 && (t.Ngram < 2 || t.Ngram > 4) {
+		return fmt.Errorf("bloomgpu: tokenizer n-gram width %d (0, 2, 3 or 4)", t.Ngram)
+	}
 	for i := 0; i < len(t.Separators); i++ {
 		if c := t.Separators[i]; c == 0 || c >= utf8.RuneSelf {
 			return fmt.Errorf("bloomgpu: tokenizer separator %q is NUL or not ASCII", t.Separators)
@@ -824,12 +834,44 @@ func (t Tokenizer) Func() func(string) []string {
 		return unicodeSpace && unicode.IsSpace(r)
 	}
 	lower := t.Lower
-	return func(v string) []string {
+	words := func(v string) []string {
 		if lower {
 			v = strings.ToLower(v)
 		}
 		return strings.FieldsFunc(v, isSep)
 	}
+	n := t.Ngram
+	if n < 2 || n > 4 { // Validate refuses the others; Func serves the words
+		return words
+	}
+	return func(v string) []string {
+		var out []string
+		for _, w := range words(v) {
+			out = appendGrams(out, w, n)
+		}
+		return out
+	}
+}
+
+// appendGrams appends grams(w, n): w itself when it has at most n runes, otherwise every window of n consecutive runes.  Runes
+// are what range decodes: an invalid byte is one rune of width 1.
+func appendGrams(out []string, w string, n int) []string {
+	var start [5]int // byte offsets of the last n + 1 rune starts, as a ring
+	runes := 0
+	for i := range w {
+		if runes >= n {
+			out = append(out, w[start[(runes-n)%(n+1)]:i])
+		}
+		start[runes%(n+1)] = i
+		runes++
+	}
+	if runes >= n {
+		return append(out, w[start[(runes-n)%(n+1)]:])
+	}
+	if runes > 0 {
+		out = append(out, w)
+	}
+	return out
 }
 
 func (t Tokenizer) c() C.bsg_tokenizer {
@@ -845,6 +887,7 @@ func (t Tokenizer) c() C.bsg_tokenizer {
 	if t.Lower {
 		ct.flags |= C.BSG_TOK_LOWER
 	}
+	ct.flags |= (C.uint32_t(t.Ngram) << C.BSG_TOK_NGRAM_SHIFT) & C.BSG_TOK_NGRAM_MASK // callers Validate first
 	return ct
 }
 

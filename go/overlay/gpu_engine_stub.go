@@ -19,6 +19,7 @@ type GPUTokenizer struct {
 	Separators   string
 	UnicodeSpace bool
 	Lower        bool
+	Ngram        int
 }
 
 func gpuTokenizerFunc(config BloomSearchEngineConfig) (ValueTokenizerFunc, error) {

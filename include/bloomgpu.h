@@ -454,12 +454,28 @@ BSG_API int32_t bsg_host_unregister(bsg_ctx *ctx, void *ptr);
  * AFTER lowering (U+212A KELVIN SIGN lowers to 'k', U+0130 to 'i'; under BSG_TOK_LOWER an upper-case ASCII separator never
  * occurs).  BasicWhitespaceLowerTokenizer = strings.Fields(strings.ToLower(v)) is the member bsg_tokenizer_default returns:
  * tab, LF, VT, FF, CR and space, UNICODE_SPACE | LOWER.  A NULL spec means that default.  BSG_E_INVALID: bit 0 (NUL), a
- * non-zero `reserved`, unknown flags.  Separators are ASCII only. */
+ * non-zero `reserved`, unknown flags, an n-gram width of 1 or above 4.  Separators are ASCII only.
+ *
+ * N-gram tokens.  flags bits 8-10 hold a width n: 0 (the words themselves, every spec without the field) or 2, 3, 4.  For n > 0
+ *   tokens(text) = concat over w in FieldsFunc(lower ? ToLower(text) : text, isSep) of grams(w, n)
+ * where, with o_0 < ... < o_L = len(w) the byte offsets of w's runes as Go's `range` decodes them (an invalid byte is one rune
+ * of width 1: its byte without LOWER, EF BF BD under LOWER), grams(w, n) = [w] if L <= n (a short word stays searchable as
+ * itself) and w[o_i : o_(i+n)] for i = 0 .. L - n otherwise.  Windows never cross a separator; an empty separator set gives the
+ * n-grams of the whole leaf text, spaces included.  A window is at most 16 bytes.  Every call that takes a bsg_tokenizer accepts
+ * the width (bsg_ingest_rows_tok, bsg_ingest_open and its appends, bsg_match_rows_tok, _many, _many_regex, _wide, _wide_rows,
+ * _lookup, _lookup_rows, _lookup_regex, _lookup_regex_rows).
+ * Condition tokens are still compared LITERALLY with the row's tokens: the matcher does not cut a condition's token into windows.
+ * A substring query is built by the caller: AND the full n-rune windows of the needle (lowered as the spec lowers).  A needle
+ * word shorter than n must never become a Token term: in a row it is part of a longer word, whose set holds that word's
+ * windows and not the needle. */
 #define BSG_TOK_UNICODE_SPACE 1u   /* runes >= 0x80 with unicode.IsSpace end a word too */
 #define BSG_TOK_LOWER         2u   /* the text is lower-cased first (unicode.ToLower per rune, as strings.ToLower) */
+#define BSG_TOK_NGRAM_SHIFT   8u   /* flags bits 8-10: the n-gram width, 0 (none), 2, 3 or 4 */
+#define BSG_TOK_NGRAM_MASK    0x700u
+#define BSG_TOK_NGRAM(n)      (((uint32_t)(n) << BSG_TOK_NGRAM_SHIFT) & BSG_TOK_NGRAM_MASK)
 typedef struct bsg_tokenizer {
     uint64_t sep_ascii[2];  /* bit (c & 63) of sep_ascii[c >> 6]: ASCII byte c (1..127) ends a word */
-    uint32_t flags;         /* BSG_TOK_* */
+    uint32_t flags;         /* BSG_TOK_* | BSG_TOK_NGRAM(n) */
     uint32_t reserved;      /* 0 */
 } bsg_tokenizer;
 BSG_API int32_t bsg_tokenizer_default(bsg_tokenizer *out);
@@ -470,7 +486,8 @@ BSG_API int32_t bsg_tokenizer_default(bsg_tokenizer *out);
  *   tokenizer.go:120-133, BasicWhitespaceLowerTokenizer tokenizer.go:141-143, addFieldToken ingest.go:95-102),
  *   unionInto (ingest.go:105-115), counts (ingest.go:117-123) and buildFilters' AddString loop (ingest.go:127-145)
  * for the DEFAULT tokenizer (the reference's own fast-path check, row_matcher.go:37-40) and, through bsg_ingest_rows_tok, for
- * every tokenizer of the separator family (bsg_tokenizer below); tokenizers outside that family stay on the host.
+ * every tokenizer of the separator family, with or without an n-gram width (bsg_tokenizer above); tokenizers outside that
+ * family stay on the host.
  * A "set" is one partition buffer's bloomEntrySets; set s owns rows
  * [set_first_row[s], set_first_row[s+1]).  A "parent" is a file-level union (flush.go:221,253);
  * parent_of_set[s] names it or is 0xFFFFFFFF.  Tables are indexed t = set * 3 + kind with parents

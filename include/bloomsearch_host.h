@@ -42,8 +42,8 @@ BSG_API void bsh_free(void *p);
 /* tokens of `text`, joined by '\n' (a token never contains white space) */
 BSG_API int32_t bsh_tokenize(const uint8_t *text, uint64_t len, char **out, uint64_t *out_len);
 /* tokens of `text` under a tokenizer of the separator family (bloomgpu.h bsg_tokenizer; NULL = the default), packed as
- * (u32 little-endian length, bytes) per token: such a token may hold any byte but a separator.  BSH_E_INVALID for an
- * invalid spec. */
+ * (u32 little-endian length, bytes) per token: such a token may hold any byte but a separator.  A spec with an n-gram width
+ * (BSG_TOK_NGRAM) gives each word's windows in order.  BSH_E_INVALID for an invalid spec (a width of 1 or above 4 included). */
 BSG_API int32_t bsh_tokenize_with(const uint8_t *text, uint64_t len, const bsg_tokenizer *tok, uint8_t **out, uint64_t *out_len);
 
 typedef struct bsh_entry_sets bsh_entry_sets;
@@ -100,7 +100,7 @@ typedef struct bse_engine bse_engine;
  *               "DeviceMatch":true|false,
  *               "DeviceRegex":true|false,"DeviceMatchWide":true|false,"DeviceMatchWideRows":true|false,
  *               "DeviceMatchLookup":true|false,"DeviceMatchLookupRows":true|false,"DeviceMatchLookupRegex":true|false,
- *               "Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false}};
+ *               "Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false,"Ngram":0|2|3|4}};
  *               missing keys take the
  *               reference defaults.  DeviceIngest (default false): rows are walked / tokenized / deduplicated /
  *               counted on the GPU at flush and merge time (bloomgpu.h bsg_ingest_*) instead of by indexRow on the

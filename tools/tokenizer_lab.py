@@ -2,7 +2,11 @@
 (bsg_ingest_stats ms_walk, k_ingest_rows[_tok] dispatch time, best of R) and match ms (bsg_last_match_ms for
 FieldToken(level, error) AND Token(cache), best of R) for the default calls, the default-plus-0x01 spec (the same words as the
 default, so its cost over the default is the TokSpec scan's) and the punctuation spec; tokens emitted per row for each (from the
-host mirror's tokenizer on the leaf texts of a sample of the rows), and walk time per emitted token.
+host mirror's tokenizer on the leaf texts of a sample of the rows), and walk time per emitted token.  Then the same for the
+default spec with an n-gram width of 3 and of 4 (k_ingest_rows_gram / k_match_rows_gram): a window per rune instead of a token per
+word, so also the distinct entries the walk left (summed over the sets) and how often a table had to grow (bsg_ingest_stats
+table_grows: the walk is repeated after each).  Their match query is the substring form of the words' one: the AND of the windows
+of "error" under level and of "cache" anywhere.
 
     python tools/tokenizer_lab.py [n_rows] [repeats]
 """
@@ -31,7 +35,9 @@ print("rows %d, %.1f MB of row bytes" % (n_rows, int(off[-1]) / 1e6))
 
 SPECS = [("default (bsg_ingest_rows / bsg_match_rows)", None),
          ("default + 0x01 (TokSpec kernels, same words)", Tokenizer(WHITE_SPACE + "\x01", unicode_space=True, lower=True)),
-         ("punctuation \" \\t\\n\\v\\f\\r,;:=/.-\\\"[]()\" lowered", Tokenizer(" \t\n\v\f\r,;:=/.-\"[]()", unicode_space=True, lower=True))]
+         ("punctuation \" \\t\\n\\v\\f\\r,;:=/.-\\\"[]()\" lowered", Tokenizer(" \t\n\v\f\r,;:=/.-\"[]()", unicode_space=True, lower=True)),
+         ("default, trigrams (k_ingest_rows_gram, n = 3)", Tokenizer(WHITE_SPACE, unicode_space=True, lower=True, ngram=3)),
+         ("default, 4-grams (k_ingest_rows_gram, n = 4)", Tokenizer(WHITE_SPACE, unicode_space=True, lower=True, ngram=4))]
 
 
 def leaf_texts(v):
@@ -63,15 +69,30 @@ first[-1] = n_rows
 first = np.unique(first)
 sample = rows[:: max(1, n_rows // 20000)]
 base_walk = base_tok = None
-matcher = Q.CompiledMatcher(Q.And(Q.FieldToken("level", "error"), Q.Token("cache")))
+
+
+def matcher_for(spec):
+    """the words' query; under a width n its substring form (bloomgpu.h: AND the full n-rune windows of every needle word)"""
+    n = spec.ngram if spec is not None else 0
+    if not n:
+        return Q.CompiledMatcher(Q.And(Q.FieldToken("level", "error"), Q.Token("cache")))
+    grams = lambda w: [w[i:i + n] for i in range(len(w) - n + 1)]
+    return Q.CompiledMatcher(Q.And(*[Q.FieldToken("level", g) for g in grams("error")], *[Q.Token(g) for g in grams("cache")]))
+
+
 with Context((0,)) as ctx:
     for name, spec in SPECS:
         walk = 1e9
         for _ in range(reps + 1):                     # the first call warms the tables' pool
             ing = ctx.ingest_rows((blob, off), first, tokenizer=spec, flags=1)
-            walk = min(walk, ctx.ingest_stats(ing).ms_walk)
+            st = ctx.ingest_stats(ing)
+            walk = min(walk, st.ms_walk)
+            grows = st.table_grows                    # (the same every time: the tables start from the same sizes)
+            counts, status = ctx.ingest_finish(ing, len(first) - 1)
+            distinct = [int(x) for x in np.asarray(counts, dtype=np.int64).sum(axis=0)]
             ctx.ingest_free(ing)
         match = 1e9
+        matcher = matcher_for(spec)
         ctx.match_rows((blob, off), matcher, tokenizer=spec)
         for _ in range(reps):
             hits, fb = ctx.match_rows((blob, off), matcher, tokenizer=spec)
@@ -81,4 +102,5 @@ with Context((0,)) as ctx:
         if base_walk is None:
             base_walk, base_tok = walk, ns_tok
         print("%-48s walk %7.3f ms (%.2fx)  match %6.3f ms  %5.2f tokens/row  %.3f ns walk per token (%.2fx)  %d hits %d fallback"
-              % (name, walk, walk / base_walk, match, tpr, ns_tok, ns_tok / base_tok, int(hits.sum()), len(fb)))
+              "  table_grows %d  distinct fields/tokens/field::tokens %d/%d/%d (summed over %d sets)"
+              % (name, walk, walk / base_walk, match, tpr, ns_tok, ns_tok / base_tok, int(hits.sum()), len(fb), grows, *distinct, len(first) - 1))

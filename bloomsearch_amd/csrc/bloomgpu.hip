@@ -132,7 +132,17 @@ struct DevBuf {
 
 // start/stop timestamps of the two dispatches themselves (hipExtLaunchKernel), i.e. the same
 // begin/end a rocprofv3 kernel trace reports — not events bracketing the launches.
-struct EventTriple { hipEvent_t k1s, k1e, k2s, k2e; uint64_t bytes; uint32_t n_arenas; bool has_k1, has_k2, fused, folded; };
+struct EventTriple {
+    hipEvent_t k1s, k1e, k2s, k2e; uint64_t bytes; uint32_t n_arenas; bool has_k1, has_k2, fused, folded;
+    // a gathered launch (gathered_timing, probe_api.inc): `ran` — device counters of the triple's own (kGatherRanBytes, allocated at its first
+    // gathered launch), zeroed before the launch — receives the bit tests the kernel executed; drain_timing replaces the part of `bytes` that assumed
+    // every location of every term (gk_model = the sum of bsh::gathered_bytes over gk[0 .. n_gk)) by bsh::gathered_bytes_tests of them
+    uint64_t *ran = nullptr;
+    bool counted = false;
+    uint32_t n_gk = 0;
+    uint64_t gk_blocks = 0, gk_model = 0;
+    bsh::GatherKind gk[3] = {};
+};
 
 // Short-lived device buffers of the ingest / match / encode calls come from a per-device cache instead of
 // hipMalloc / hipFree (a flush of 1 000 rows made ~16 of each: 0.8 ms of fixed cost, 2/3 of the call).  Blocks are kept
@@ -444,6 +454,7 @@ struct bsg_ctx {
     uint32_t solo_ring_wgs = 32;  // a lone bsg_query of more workgroups than this gets its doorbell from a dispatch behind the kernel (bsg_set_lab key 22)
     uint32_t gather_cost = 108;   // bytes a gathered word load is taken to cost: a launch / a filter is gathered when terms * k * gather_cost < its bytes (bsg_set_gather_cost; the value: profiles/probe_gather_lab.txt)
     uint32_t gather_kernel = 1;  // 0 (bsg_set_lab key 26): a launch never takes k_probe_gather, only the per-block gathered path inside k_probe_terms
+    uint32_t gather_wgs_per_cu = 0;  // workgroups of the gather kernels per CU (bsg_set_lab key 28): 0 = bsh::kGatherWorkgroupsPerCu, above 4 = no cap
     std::atomic<uint32_t> last_probe_route{0};   // route of the last k_probe_terms(_many) / k_probe_gather dispatch, or of the last chunked gather (bsg_lab_last_probe_route)
     bsg::FpKey fp_key{};         // secret key of the entries' fingerprints (drawn at bsg_open; never leaves the process)
     std::vector<uint8_t> peer;   // [i * nd + j]: 1 = device i reaches device j's memory directly (xGMI peer access enabled, or the same device)
@@ -601,6 +612,16 @@ int32_t drain_timing(bsg_ctx *ctx, Device &d)
         float a = 0, b = 0;
         if (t.has_k1) HIP_TRY(hipEventElapsedTime(&a, t.k1s, t.k1e));
         if (t.has_k2) HIP_TRY(hipEventElapsedTime(&b, t.k2s, t.k2e));
+        if (t.has_k1 && t.counted && t.ran) {
+            std::vector<uint64_t> ran(bsg::kGatherRanBytes / sizeof(uint64_t));
+            HIP_TRY(hipMemcpy(ran.data(), t.ran, bsg::kGatherRanBytes, hipMemcpyDeviceToHost));
+            t.bytes -= t.gk_model;
+            for (uint32_t y = 0; y < t.n_gk; ++y) {
+                uint64_t tests = 0;
+                for (uint32_t i = 0; i < bsg::kGatherRanSlots; ++i) tests += ran[(size_t)(y * bsg::kGatherRanSlots + i) * bsg::kGatherRanStride];
+                t.bytes += bsh::gathered_bytes_tests(t.gk[y], t.gk_blocks, tests);
+            }
+        }
         std::lock_guard<std::shared_mutex> lk(ctx->mu);
         if (t.has_k1 && t.folded) {
             ctx->timing.n_folded += 1;
@@ -808,6 +829,10 @@ int32_t bsg_open(const int32_t *device_ids, int32_t n_devices, bsg_ctx **out_ctx
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_probe_terms_many_ext), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_probe_fused), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_probe_eval), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
+        // (the gather kernels use none of it: a launch's pad caps their workgroups per CU, bsh::gather_lds_pad)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_probe_gather), hipFuncAttributeMaxDynamicSharedMemorySize, bsh::gather_lds_pad(1)));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_probe_gather_ext), hipFuncAttributeMaxDynamicSharedMemorySize, bsh::gather_lds_pad(1)));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_gather_fused), hipFuncAttributeMaxDynamicSharedMemorySize, bsh::gather_lds_pad(1)));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_build), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_build_sets), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget - bsg::kSetListBytes));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bsg::k_union_partitions), hipFuncAttributeMaxDynamicSharedMemorySize, bsg::kPartLdsBytes));
@@ -906,6 +931,7 @@ int32_t bsg_close(bsg_ctx *ctx)
             for (auto &t : *v) {
                 (void)hipEventDestroy(t.k1s); (void)hipEventDestroy(t.k1e);
                 (void)hipEventDestroy(t.k2s); (void)hipEventDestroy(t.k2e);
+                if (t.ran) (void)hipFree(t.ran);
             }
         d.V[0].release(); d.V[1].release(); d.out[0].release(); d.out[1].release(); d.stage_a.release(); d.stage_off.release(); d.stage_h.release();
         d.stage_fstart.release(); d.stage_desc.release(); d.stage_items.release(); d.stage_words.release(); d.stage_region.release();

@@ -118,17 +118,48 @@ inline bool launch_gathers(const GatherKind *kinds, uint32_t n_kinds, uint64_t n
 }
 
 // Bytes a gathered launch moves for one kind, as the counters show them (an L2 miss fills a 128-byte line, FETCH_SIZE of
-// profiles/probe_gather_lab.txt): a filter of L lines tested at t = terms x k uniformly spread bits has L (1 - exp(-t / L)) of its
-// lines touched in expectation — C2: 275 lines, 290 tests, 179 lines, against 180-188 requests per block measured.  L is the
-// kind's mean over the group's blocks; never more than the filters themselves.  bsg_timing.stream_bytes of a gathered launch.
+// profiles/probe_gather_lab.txt): a filter of L lines tested at t uniformly spread bits has L (1 - exp(-t / L)) of its lines touched
+// in expectation.  L is the kind's mean over the group's blocks; never more than the filters themselves.
+// gathered_bytes: t = terms x k, every location of every term — all the host can know before the launch (C2: 275 lines, 290 tests,
+// 179 lines).  The gather kernels stop a term at the first phase that finds a clear bit, so they execute fewer tests wherever a term
+// is absent from a block (C2: 204.8 tests, 144.5 lines against 159-161 requests per block by the counters); a timestamped launch
+// counts the tests it executed on the device, and bsg_timing.stream_bytes is gathered_bytes_tests of that count
+// (`tests`: the executed bit tests of the kind summed over the group's blocks).
+inline uint64_t gathered_bytes_per_block_tests(const GatherKind &k, uint64_t n_blocks, double tests);
 inline uint64_t gathered_bytes(const GatherKind &k, uint64_t n_blocks)
+{
+    return gathered_bytes_per_block_tests(k, n_blocks, (double)k.terms * (double)k.max_k);
+}
+inline uint64_t gathered_bytes_tests(const GatherKind &k, uint64_t n_blocks, uint64_t tests)
+{
+    return n_blocks == 0 ? 0 : gathered_bytes_per_block_tests(k, n_blocks, (double)tests / (double)n_blocks);
+}
+inline uint64_t gathered_bytes_per_block_tests(const GatherKind &k, uint64_t n_blocks, double tests)
 {
     if (n_blocks == 0 || k.sum_words == 0) return 0;
     const double lines = (double)k.sum_words * 8.0 / 128.0 / (double)n_blocks;
-    const double tests = (double)k.terms * (double)k.max_k;
     const double touched = lines * (1.0 - std::exp(-tests / lines)) * 128.0 * (double)n_blocks;
     const double all = (double)k.sum_words * 8.0;
     return (uint64_t)(touched < all ? touched : all);
+}
+
+// Workgroups of the gather kernels per CU.  The kernels hold no LDS and 8 waves a workgroup, so 4 workgroups share a CU (8 waves per
+// SIMD) unless the launch asks for dynamic LDS it never touches: a pad of floor(160 KiB / n) keeps n workgroups there and no more
+// (4 / 3 / 2 / 1 workgroups = 8 / 6 / 4 / 2 waves per SIMD).  The pad is rounded DOWN to the LDS allocation unit, so that what the
+// hardware rounds up is the pad itself and n workgroups still fit; one workgroup per CU takes the largest request the library
+// makes anywhere (kLdsBudget's 144 KiB: two of them do not fit).  Pads above 64 KiB are opt-in per kernel (bsg_open sets the
+// attribute for gather_lds_pad(1)).  0, and anything above 4, is "no cap": no pad.
+// kGatherWorkgroupsPerCu is the planner's rule (bsg_set_lab key 28 = 0); measured: profiles/probe_gather_lines_lab.txt.
+constexpr uint32_t kCuLdsBytes = 160u * 1024u;
+constexpr uint32_t kLdsAllocUnit = 1280u;               // gfx950 allocates LDS in units of 320 dwords
+constexpr uint32_t kLdsOptInBytes = 64u * 1024u;        // more dynamic LDS than this needs hipFuncAttributeMaxDynamicSharedMemorySize
+constexpr uint32_t kGatherPadMax = 144u * 1024u;
+constexpr uint32_t kGatherMaxWorkgroupsPerCu = 4;
+constexpr uint32_t kGatherWorkgroupsPerCu = 0;
+inline uint32_t gather_lds_pad(uint32_t workgroups_per_cu)
+{
+    if (workgroups_per_cu == 0 || workgroups_per_cu > kGatherMaxWorkgroupsPerCu) return 0;
+    return std::min(kCuLdsBytes / workgroups_per_cu / kLdsAllocUnit * kLdsAllocUnit, kGatherPadMax);
 }
 
 // Tail split (lab key 19, percent): a run of ONE group of n_shards shards is cut into two dispatches' worth, the first n0 shards

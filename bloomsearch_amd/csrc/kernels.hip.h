@@ -931,39 +931,52 @@ __global__ __launch_bounds__(kProbeThreads) void k_probe_terms_many_ext(const Pr
 // K1g  probe_gather: the few-term probe for launches whose filters are all cheaper to GATHER than to stream (the host decides for the
 // whole launch: bsh::launch_gathers, host/probe_plan.hpp).  One WAVE per (block, referenced kind): a 512-thread workgroup covers 8
 // consecutive blocks of one arena; no LDS, no barrier, no atomics.  Each lane owns one term of a 64-term word: its four hashes, then
-// the k locations in batches of kGatherBatch — the reductions and the 4-byte loads of a batch are issued back to back before the
+// the k locations in phases (below) — the reductions and the 4-byte loads of a phase are issued back to back before the
 // first word is looked at — read straight from the arena.  The verdict word is the ballot, stored by lane 0 at the address
 // probe_role computes: a workgroup's 8 words are 64 contiguous bytes.
 // The block index is made wave-uniform (readfirstlane), so the descriptor still arrives by scalar loads (load_desc_uniform: a
 // wave-uniform address is all a scalar load needs) and d.m / d.k, the modulo mode and the loop trips live in SGPRs.
 // grid = (ceil(max_blocks / 8), referenced kinds, arenas of the group)
 // ---------------------------------------------------------------------------
-// Measured on MI355X at the headline's launch shape (C2: 29 terms, k = 10, 35 KB filters, 20 arenas of 1 000 blocks per dispatch;
-// tools/probe_gather_lab.py, profiles/probe_gather_lab.txt), against k_probe_terms' 97-98 us streamed and 88-93 us on its per-block
-// gathered path:
-//   one phase, batches of 4                 78.1 us (76.0 .. 80.4)
-//   + non-temporal loads                    92.0 us: a 128-byte line is wanted again by later locations — plain loads
-//   all 10 locations in one batch           92.4 us
-//   + the fp64 modulo                       79.5 us: a draw, the kernel waits on memory — Barrett, as the other few-term kernels
-//   two phases, first phase = batch of 4    70.2 / 70.5 us (69.0 .. 75.9 / 69.2 .. 72.0): 8 us ahead, twice the spread — the default
-//   ... first phase of 2 / 3 / 5            67.9 / 71.4 / 77.4 us: 2 is inside the spread of 4, which stays (kTailBatch's value)
-// An L2 miss fills a 128-byte line (FETCH_SIZE: 180-188 requests per block = the 179 lines 290 bit tests touch, not the 225 sectors):
-// the kernel moves ~0.67 of the streamed bytes at the streaming kernel's own 6.8 TB/s.
-#ifndef BSG_GATHER_BATCH
-#define BSG_GATHER_BATCH 4        // locations whose loads are in flight together per lane, and the length of the first phase (lab: -DBSG_GATHER_BATCH)
+// PHASES.  A lane takes its term's k locations in phases whose lengths are a compile-time list (GatherSchedule; the last length
+// repeats until k, and every phase is clipped at k).  Within a phase all of a lane's reductions and loads are issued back to back,
+// then the bit tests; a phase after the first runs only for the lanes whose bits were all set so far (a term absent from the block
+// dies after ~2 locations), and the wave leaves when it has none.  So the list sets both how many locations of an absent term are
+// read for nothing (the first lengths) and how many dependent round trips a present term takes (the count).
+// OCCUPANCY.  The kernels use no LDS, so dynamic LDS asked for at launch caps the workgroups per CU (bsh::gather_lds_pad,
+// bsg_set_lab key 28): 4 / 3 / 2 / 1 workgroups are 8 / 6 / 4 / 2 waves per SIMD.
+// Measured on MI355X at the headline's launch shapes (C2: 29 terms of which 17 are present, k = 10, 35 KB filters = 275 lines of 128 B,
+// 20 and 200 arenas of 1 000 blocks per call; tools/probe_gather_lab.py, profiles/probe_gather_lines_lab.txt; the kernel's first
+// record, against the streamed k_probe_terms: profiles/probe_gather_lab.txt).  The kernel runs at the memory system's rate on the
+// 128-byte lines it REQUESTS (6.8 TB/s), so what counts is how many it asks for, per block:
+//   schedule    tests executed   lines touched (exact, CPU)   requests (FETCH_SIZE)   gather time, 20 / 200 arenas
+//   {4,4,2} as one loop (before)  221.3        152.2                188.1 / 189.4            68.8 / 649 us
+//   {4,4,4}                       221.3        152.2                179.7                    65.0 / 629
+//   {4,6}                         222.8        152.8                                         64.2 / 629
+//   {2,8}                         218.1        150.5                                         61.1 / 597
+//   {2,2,6}                       204.8        144.4                166.8                    59.8 / 565
+//   {1,3,6}  the default          204.8        144.5                160.6 / 158.5            59.0 / 557
+// Short first phases save the absent terms' wasted tests AND most of the re-requests of lines a block's earlier loads had fetched;
+// the count of dependent round trips does not matter ({4,6} = {4,4,4}).  Capping the workgroups per CU at 3 is inside the spread
+// of 4, at 2 it gains 1-3 us at 20 arenas and loses 9-14 at 200, at 1 it loses 4-29 %: the kernel needs its 8 waves per SIMD, so the
+// planner's rule is no pad.  Earlier: non-temporal loads +18 % (a line is wanted again by later locations), all k locations in one
+// phase +18 %, the fp64 modulo a draw (the kernel waits on memory: Barrett, as the other few-term kernels).
+#ifndef BSG_GATHER_SCHEDULE
+#define BSG_GATHER_SCHEDULE 1, 3, 6   // phase lengths (lab: -DBSG_GATHER_SCHEDULE=4,4,4 ...)
 #endif
 #ifndef BSG_GATHER_NT
 #define BSG_GATHER_NT 0           // lab: 1 = non-temporal loads of the filter words
 #endif
-#ifndef BSG_GATHER_EARLY
-#define BSG_GATHER_EARLY 1        // two phases: after the first batch only the lanes still alive load (a term absent from the block dies after ~2
-                                  // locations), and a wave without one stops; lab: 0 = every location of every term
-#endif
 #ifndef BSG_GATHER_FP64
 #define BSG_GATHER_FP64 0         // lab: 1 = the fp64 modulo for 64 <= m <= 2^19
 #endif
-constexpr uint32_t kGatherBatch = BSG_GATHER_BATCH;
+template <uint32_t... L> struct GatherPhases {};
+typedef GatherPhases<BSG_GATHER_SCHEDULE> GatherSchedule;
 constexpr uint32_t kGatherBlocks = kProbeThreads / kWave;      // blocks per workgroup: one per wave
+// a timestamped launch's counters of executed bit tests: [kind][block % 128], each in a 128-byte line of its own — atomics on one
+// line queue at ~4 ns each (64 counters in 4 lines made a 59 us launch 77 us long; a line per counter leaves it where it was)
+constexpr uint32_t kGatherRanKinds = 3, kGatherRanSlots = 128, kGatherRanStride = 16;
+constexpr size_t kGatherRanBytes = sizeof(uint64_t) * kGatherRanKinds * kGatherRanSlots * kGatherRanStride;
 
 // one 4-byte word of the filter at `base` (wave-uniform) + a per-lane word index
 template <int MODE>
@@ -980,46 +993,72 @@ __device__ __forceinline__ uint32_t gather_load(const uint64_t *base, uint64_t l
 #endif
 }
 
+// One phase of N locations from i0 on (wave-uniform), clipped at k: the lanes that are `on` load, the others keep their verdict.
+// -> the lane's bits of this phase were all set.
+template <int MODE, uint32_t N>
+__device__ __forceinline__ uint32_t gather_phase(const ProbeDesc &d, const uint64_t *src, uint64_t h0, uint64_t h1, uint64_t h2, uint64_t h3,
+                                                 uint32_t i0, uint32_t k, bool on)
+{
+    uint32_t wd[N], sh[N];
+#pragma unroll
+    for (uint32_t v = 0; v < N; ++v) {
+        const uint32_t iv = i0 + v;                                   // wave-uniform
+        wd[v] = ~0u; sh[v] = 0u;
+        if (iv < k && on) {
+            const uint64_t loc = locate_c<MODE>(d, location(h0, h1, h2, h3, iv));      // always < d.m: the word lies inside the filter
+            sh[v] = (uint32_t)loc;
+            wd[v] = gather_load<MODE>(src, loc);
+        }
+    }
+    uint32_t set = 1u;
+#pragma unroll
+    for (uint32_t v = 0; v < N; ++v) set &= __builtin_amdgcn_ubfe(wd[v], sh[v], 1u);   // v_bfe_u32: offset from bits [4:0]
+    return set;
+}
+
+// The phases of one term word in the schedule's order; -> the lane's term passed all k bit tests.  `real`: the lane holds a term
+// (the padded lanes of a term word load nothing).  n_ran: the bit tests the lane executed are added to it.
+template <int MODE, uint32_t L0, uint32_t... L>
+__device__ __forceinline__ uint32_t gather_phases(GatherPhases<L0, L...>, const ProbeDesc &d, const uint64_t *src, uint64_t h0, uint64_t h1,
+                                                  uint64_t h2, uint64_t h3, uint32_t i0, uint32_t k, bool real, uint32_t alive, uint32_t &n_ran)
+{
+    if (i0 >= k) return alive;
+    if (i0 != 0 && __ballot(alive != 0u && real) == 0) return alive;
+    if (real && alive != 0u) n_ran += min(L0, k - i0);
+    alive &= gather_phase<MODE, L0>(d, src, h0, h1, h2, h3, i0, k, real && alive != 0u);
+    if constexpr (sizeof...(L) != 0) return gather_phases<MODE>(GatherPhases<L...>{}, d, src, h0, h1, h2, h3, i0 + L0, k, real, alive, n_ran);
+    for (i0 += L0; i0 < k && __ballot(alive != 0u && real) != 0; i0 += L0) {     // beyond the list: the last length again
+        if (real && alive != 0u) n_ran += min(L0, k - i0);
+        alive &= gather_phase<MODE, L0>(d, src, h0, h1, h2, h3, i0, k, real && alive != 0u);
+    }
+    return alive;
+}
+
 template <int MODE>
 __device__ __forceinline__ void gather_block(const ProbeArgs &a, const ProbeDesc &d, const uint64_t *src, uint32_t t0, uint32_t n_real,
-                                             uint32_t n_tw, uint64_t *vout, uint32_t lane)
+                                             uint32_t n_tw, uint64_t *vout, uint32_t lane, uint64_t *ran)
 {
     const uint32_t k = d.k;
+    uint32_t n_ran = 0;
     for (uint32_t w = 0; w < n_tw; ++w) {
         const uint32_t idx = w * 64 + lane;
         const bool real = idx < n_real;
         const uint64_t *th = a.th + (t0 + idx);                       // (the padded tail of the last word holds hashes too: Tp is a multiple of 64)
         const uint64_t h0 = th[0], h1 = th[a.Tp], h2 = th[2ull * a.Tp], h3 = th[3ull * a.Tp];
-        uint32_t alive = 1u;
-        for (uint32_t i0 = 0; i0 < k; i0 += kGatherBatch) {
-#if BSG_GATHER_EARLY
-            if (i0 != 0 && __ballot(alive != 0u && real) == 0) break;
-#endif
-            uint32_t wd[kGatherBatch], sh[kGatherBatch];
-#pragma unroll
-            for (uint32_t v = 0; v < kGatherBatch; ++v) {
-                const uint32_t iv = i0 + v;                           // wave-uniform
-                wd[v] = ~0u; sh[v] = 0u;
-#if BSG_GATHER_EARLY
-                if (iv < k && real && (i0 == 0 || alive != 0u)) {
-#else
-                if (iv < k && real) {                                 // (the padded lanes of a term word load nothing)
-#endif
-                    const uint64_t loc = locate_c<MODE>(d, location(h0, h1, h2, h3, iv));      // always < d.m: the word lies inside the filter
-                    sh[v] = (uint32_t)loc;
-                    wd[v] = gather_load<MODE>(src, loc);
-                }
-            }
-#pragma unroll
-            for (uint32_t v = 0; v < kGatherBatch; ++v) alive &= __builtin_amdgcn_ubfe(wd[v], sh[v], 1u);   // v_bfe_u32: offset from bits [4:0]
-        }
+        const uint32_t alive = gather_phases<MODE>(GatherSchedule{}, d, src, h0, h1, h2, h3, 0u, k, real, 1u, n_ran);
         const uint64_t verdict = __ballot(alive != 0u || !real);
         if (lane == 0) vout[(uint64_t)w * 64] = verdict;
+    }
+    if (ran != nullptr) {   // a timestamped launch (wave-uniform): the wave's executed bit tests into its counter, for bsg_timing's bytes
+        for (uint32_t o = kWave / 2; o != 0; o >>= 1) n_ran += __shfl_xor(n_ran, o);
+        if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(ran), (unsigned long long)n_ran);
     }
 }
 
 // bx: the workgroup's position among the arena's ceil(max_blocks / kGatherBlocks) workgroups
-__device__ __forceinline__ void gather_role(const ProbeArgs &a, const ArenaRef &ar, uint32_t bx, uint32_t y)
+// ran: nullptr, or (timestamped launches) kGatherRanKinds x kGatherRanSlots zeroed counters: the executed bit tests of kind y are
+// summed into ran[y][block % kGatherRanSlots] (that many lines, so the waves' atomics do not queue on one)
+__device__ __forceinline__ void gather_role(const ProbeArgs &a, const ArenaRef &ar, uint32_t bx, uint32_t y, uint64_t *ran)
 {
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t b = bx * kGatherBlocks + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);   // wave-uniform, in an SGPR
@@ -1035,23 +1074,24 @@ __device__ __forceinline__ void gather_role(const ProbeArgs &a, const ArenaRef &
         return;
     }
     const uint64_t *src = ar.words + d.word_off;
+    if (ran != nullptr) ran += ((y < kGatherRanKinds ? y : 0u) * kGatherRanSlots + (b & (kGatherRanSlots - 1))) * kGatherRanStride;
     d.f = ModF64{};
 #if BSG_GATHER_FP64
-    if (modf64_ok(d.m)) { d.f = make_modf64(d.m, d.magic); gather_block<kModFp64>(a, d, src, t0, n_real, n_tw, vout, lane); return; }
+    if (modf64_ok(d.m)) { d.f = make_modf64(d.m, d.magic); gather_block<kModFp64>(a, d, src, t0, n_real, n_tw, vout, lane, ran); return; }
 #endif
-    if (d.m < (1ull << 31)) gather_block<kModBarrett32>(a, d, src, t0, n_real, n_tw, vout, lane);
-    else                    gather_block<kModBarrett64>(a, d, src, t0, n_real, n_tw, vout, lane);
+    if (d.m < (1ull << 31)) gather_block<kModBarrett32>(a, d, src, t0, n_real, n_tw, vout, lane, ran);
+    else                    gather_block<kModBarrett64>(a, d, src, t0, n_real, n_tw, vout, lane, ran);
 }
 
-__global__ __launch_bounds__(kProbeThreads) void k_probe_gather(const ProbeArgs a, const ArenaTable<kMaxGroupArenas> t)
+__global__ __launch_bounds__(kProbeThreads) void k_probe_gather(const ProbeArgs a, const ArenaTable<kMaxGroupArenas> t, uint64_t *ran)
 {
-    gather_role(a, t.ar[blockIdx.z], blockIdx.x, blockIdx.y);
+    gather_role(a, t.ar[blockIdx.z], blockIdx.x, blockIdx.y, ran);
 }
 // the same kernel for groups whose arena records lie in device memory (separate for the reason given at kMaxExtGroupArenas)
-__global__ __launch_bounds__(kProbeThreads) void k_probe_gather_ext(const ProbeArgs a, const ArenaRef *__restrict__ ext)
+__global__ __launch_bounds__(kProbeThreads) void k_probe_gather_ext(const ProbeArgs a, const ArenaRef *__restrict__ ext, uint64_t *ran)
 {
     const ArenaRef ar = load_arena_ref(ext, blockIdx.z);
-    gather_role(a, ar, blockIdx.x, blockIdx.y);
+    gather_role(a, ar, blockIdx.x, blockIdx.y, ran);
 }
 
 // (Measured and dropped, twice now: the same kernel with 1 024 threads per block — 16 waves sharing one block's image, 32
@@ -1413,7 +1453,7 @@ struct GatherFusedArgs {
     uint32_t gather_nx;      // ceil(p.max_blocks / kGatherBlocks)
 };
 
-__global__ __launch_bounds__(kProbeThreads) void k_gather_fused(const GatherFusedArgs f, const ArenaRef *__restrict__ ext)
+__global__ __launch_bounds__(kProbeThreads) void k_gather_fused(const GatherFusedArgs f, const ArenaRef *__restrict__ ext, uint64_t *ran)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t lds64[];
     const uint32_t o = blockIdx.x >> 3, E = f.n_eval >> 3;
@@ -1427,7 +1467,7 @@ __global__ __launch_bounds__(kProbeThreads) void k_gather_fused(const GatherFuse
         if (ai >= f.p.n_arenas) return;                       // (the last gather octet may be partial)
         const uint32_t y = r / f.gather_nx;
         const ArenaRef ar = load_arena_ref(ext, f.a0 + ai);
-        gather_role(f.p, ar, r - y * f.gather_nx, y);
+        gather_role(f.p, ar, r - y * f.gather_nx, y, ran);
     } else {
         if (threadIdx.x >= kEvalThreads) return;
         uint32_t combo, tx;

@@ -295,8 +295,10 @@ int32_t take_events(bsg_ctx *ctx, Device &d, EventTriple &ev)
     else {
         HIP_TRY(hipEventCreate(&ev.k1s)); HIP_TRY(hipEventCreate(&ev.k1e));
         HIP_TRY(hipEventCreate(&ev.k2s)); HIP_TRY(hipEventCreate(&ev.k2e));
+        ev.ran = nullptr;
     }
     ev.bytes = 0;
+    ev.counted = false;
     ev.has_k1 = ev.has_k2 = ev.fused = ev.folded = false;
     ev.n_arenas = 0;
     return BSG_OK;
@@ -451,6 +453,13 @@ uint64_t gather_kinds(const Group &g, const Batch &B, bsh::GatherKind *gk)
     return group_blocks;
 }
 
+// dynamic LDS the gather kernels are launched with although they use none: it caps their workgroups per CU (bsh::gather_lds_pad;
+// bsg_set_lab key 28, 0 = the planner's rule)
+uint32_t gather_pad(const bsg_ctx *ctx)
+{
+    return bsh::gather_lds_pad(ctx->gather_wgs_per_cu ? ctx->gather_wgs_per_cu : bsh::kGatherWorkgroupsPerCu);
+}
+
 bool group_gathers(const bsg_ctx *ctx, const Group &g, const Batch &B)
 {
     bsh::GatherKind gk[3];
@@ -459,15 +468,34 @@ bool group_gathers(const bsg_ctx *ctx, const Group &g, const Batch &B)
 }
 
 // bsg_timing's stream_bytes for a gathered launch (ev->bytes holds the bitsets' bytes, make_probe_args): not the bitsets (it does not
-// stream them) but the 128-byte lines its bit tests are expected to touch (bsh::gathered_bytes: what FETCH_SIZE shows) — a roofline
-// fraction formed from it stays one
+// stream them) but the 128-byte lines its bit tests are expected to touch (what FETCH_SIZE shows) — a roofline fraction formed from
+// it stays one.  Here: bsh::gathered_bytes, every location of every term; the kernel skips the later locations of a term absent from
+// a block, so it counts the tests it executes into the triple's counters (gather_counters, before the launch) and drain_timing
+// puts bsh::gathered_bytes_tests of them in its place.
 void gathered_timing(EventTriple &ev, const Batch &B, const bsh::GatherKind *gk, uint64_t group_blocks)
 {
+    ev.n_gk = B.n_kinds;
+    ev.gk_blocks = group_blocks;
+    ev.gk_model = 0;
     for (uint32_t y = 0; y < B.n_kinds; ++y) {
+        ev.gk[y] = gk[y];
         ev.bytes -= gk[y].sum_words * 8;
-        ev.bytes += bsh::gathered_bytes(gk[y], group_blocks);
+        ev.gk_model += bsh::gathered_bytes(gk[y], group_blocks);
     }
+    ev.bytes += ev.gk_model;
+    ev.counted = ev.ran != nullptr;
     ev.has_k1 = true;
+}
+
+// the counters a timestamped gathered launch sums its executed bit tests into, zeroed on the stream ahead of it (nullptr: not timestamped)
+int32_t gather_counters(Device &d, EventTriple *ev, uint64_t **ran)
+{
+    *ran = nullptr;
+    if (!ev) return BSG_OK;
+    if (!ev->ran) HIP_TRY(hipMalloc(&ev->ran, bsg::kGatherRanBytes));
+    HIP_TRY(hipMemsetAsync(ev->ran, 0, bsg::kGatherRanBytes, d.stream));
+    *ran = ev->ran;
+    return BSG_OK;
 }
 
 int32_t enqueue_terms(bsg_ctx *ctx, Device &d, const Group &g, const BatchDev &bd, const Batch &B, uint32_t slot, EventTriple *ev)
@@ -492,8 +520,11 @@ int32_t enqueue_terms(bsg_ctx *ctx, Device &d, const Group &g, const BatchDev &b
     const uint64_t group_blocks = gather_kinds(g, B, gk);
     if (ctx->gather_kernel && bsh::launch_gathers(gk, B.n_kinds, group_blocks, B.many_terms, ctx->gather_cost)) {
         const dim3 ggrid((g.max_blocks + bsg::kGatherBlocks - 1) / bsg::kGatherBlocks, B.n_kinds, a.n_arenas);
-        if (ext) hipExtLaunchKernelGGL(bsg::k_probe_gather_ext, ggrid, wg, 0, d.stream, e0, e1, 0, a, ext);
-        else     hipExtLaunchKernelGGL(bsg::k_probe_gather, ggrid, wg, 0, d.stream, e0, e1, 0, a, t);
+        const uint32_t pad = gather_pad(ctx);
+        uint64_t *ran = nullptr;
+        if (int32_t rc = gather_counters(d, ev, &ran)) return rc;
+        if (ext) hipExtLaunchKernelGGL(bsg::k_probe_gather_ext, ggrid, wg, pad, d.stream, e0, e1, 0, a, ext, ran);
+        else     hipExtLaunchKernelGGL(bsg::k_probe_gather, ggrid, wg, pad, d.stream, e0, e1, 0, a, t, ran);
         HIP_TRY(hipGetLastError());
         ctx->last_probe_route.store(BSG_LAB_ROUTE_GATHER, std::memory_order_relaxed);
         if (ev) gathered_timing(*ev, B, gk, group_blocks);
@@ -719,7 +750,7 @@ int32_t enqueue_gather_fused(bsg_ctx *ctx, Device &d, const Group &gc, uint32_t 
     uint32_t lds = 0;
     if (int32_t rc = make_probe_args(ctx, d, gc, bd, B, slot, ev, f.p, lds)) return rc;
     if (int32_t rc = make_eval_args(d, ec, bd, B, slot, f.e)) return rc;
-    lds = eval_lds_for(B, f.e);
+    lds = std::max(eval_lds_for(B, f.e), gather_pad(ctx));     // (the pad is per workgroup, so it caps the evaluation workgroups of this dispatch too)
     f.a0 = a0; f.e0 = e0;
     f.spread = spread ? 1u : 0u;
     f.n_kinds = B.n_kinds;
@@ -732,8 +763,10 @@ int32_t enqueue_gather_fused(bsg_ctx *ctx, Device &d, const Group &gc, uint32_t 
     if (octets * 8 > 0x7FFFFFFFull) return fail(BSG_E_UNSUPPORTED, "chunked gather launch of %llu workgroups", (unsigned long long)(octets * 8));
     f.n_eval = (uint32_t)n_eval;
     f.n_octets = (uint32_t)octets;
+    uint64_t *ran = nullptr;
+    if (int32_t rc = gather_counters(d, ev, &ran)) return rc;
     hipExtLaunchKernelGGL(bsg::k_gather_fused, dim3((uint32_t)(octets * 8)), dim3(bsg::kProbeThreads), lds, d.stream, ev ? ev->k1s : nullptr,
-                          ev ? ev->k1e : nullptr, 0, f, ext);
+                          ev ? ev->k1e : nullptr, 0, f, ext, ran);
     HIP_TRY(hipGetLastError());
     if (ev) {
         bsh::GatherKind gk[3];
@@ -1033,8 +1066,10 @@ int32_t DeviceRun::pipeline_chunked(const std::vector<uint32_t> &sizes)
         uint32_t lds = 0;
         if (int32_t rc = make_probe_args(ctx, d, chunks[0], bd, B, 0, cv(0), a, lds)) return rc;
         const dim3 ggrid((chunks[0].max_blocks + bsg::kGatherBlocks - 1) / bsg::kGatherBlocks, B.n_kinds, a.n_arenas);
-        hipExtLaunchKernelGGL(bsg::k_probe_gather_ext, ggrid, dim3(bsg::kProbeThreads), 0, d.stream, timed ? cev[0].k1s : nullptr,
-                              timed ? cev[0].k1e : nullptr, 0, a, ext);
+        uint64_t *ran = nullptr;
+        if (int32_t rc = gather_counters(d, cv(0), &ran)) return rc;
+        hipExtLaunchKernelGGL(bsg::k_probe_gather_ext, ggrid, dim3(bsg::kProbeThreads), gather_pad(ctx), d.stream, timed ? cev[0].k1s : nullptr,
+                              timed ? cev[0].k1e : nullptr, 0, a, ext, ran);
         HIP_TRY(hipGetLastError());
         if (timed) {
             bsh::GatherKind gk[3];
@@ -1267,7 +1302,8 @@ extern "C" int32_t bsg_set_lab(bsg_ctx *ctx, uint32_t key, uint64_t value)
     // 16 = queries asked of one arena in a cycle from which the arena is streamed once for all of them (default 8, 0 = never); 17 = microseconds a
     // queued caller polls before it sleeps (default 60); 19 = percent of a single-group device-resident run whose evaluation moves to a second
     // stream beside the rest's probe (0 = off); 26 = 0: few-term launches never take k_probe_gather (default 1); 27 = chunks a single gathered group is probed in, its evaluation
-    // under its own gather (k_gather_fused; 0 = bsh::pipeline_chunks decides, 1 = never, n >= 2 = n chunks, + (percent of an equal share for the last chunk) << 16, + (1 = evaluation workgroups in front, 2 = spread) << 24)
+    // under its own gather (k_gather_fused; 0 = bsh::pipeline_chunks decides, 1 = never, n >= 2 = n chunks, + (percent of an equal share for the last chunk) << 16, + (1 = evaluation workgroups in front, 2 = spread) << 24);
+    // 28 = workgroups of the gather kernels per CU (0 = bsh::kGatherWorkgroupsPerCu, above 4 = no cap)
     if (key == 12) { ctx->cmb.mode = (uint32_t)std::min<uint64_t>(value, 2); return BSG_OK; }
     if (key == 13) { ctx->cmb.sync.max_inflight = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(value, 1), 8); return BSG_OK; }
     if (key == 15) { ctx->cmb.linger_us = (uint32_t)std::min<uint64_t>(value >> 16, 1000000); ctx->cmb.linger_calls = (uint32_t)(value & 0xFFFF); return BSG_OK; }
@@ -1279,6 +1315,7 @@ extern "C" int32_t bsg_set_lab(bsg_ctx *ctx, uint32_t key, uint64_t value)
     if (key == 22) { ctx->solo_ring_wgs = (uint32_t)std::min<uint64_t>(value, 1u << 30); return BSG_OK; }
     if (key == 21) { ctx->cmb.inline_jobs = value ? 1u : 0u; return BSG_OK; }
     if (key == 26) { ctx->gather_kernel = value ? 1u : 0u; return BSG_OK; }     // 0: launches never take k_probe_gather (tools/probe_gather_lab.py: the per-block gathered path of k_probe_terms on its own)
+    if (key == 28) { ctx->gather_wgs_per_cu = (uint32_t)std::min<uint64_t>(value, 255); return BSG_OK; }     // workgroups of the gather kernels per CU, by an LDS pad (bsh::gather_lds_pad): 0 = the planner's rule, 1-4, above 4 = no cap
     if (key == 27) { ctx->pipeline_key = value & 0xFFFFFFFFull; return BSG_OK; }     // 0: bsh::pipeline_chunks decides, 1: never, n (+ last-chunk percent << 16, + placement << 24): n chunks
     if (key == 17) { ctx->cmb.sync.spin_us = (uint32_t)std::min<uint64_t>(value, 1000000); return BSG_OK; }
     return fail(BSG_E_INVALID, "unknown lab key %u", key);

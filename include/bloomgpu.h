@@ -94,8 +94,9 @@ typedef struct bsg_timing {
     double   ms_terms_kernel;    /* sum of their durations (the HBM stream)                                 */
     double   ms_eval_kernel;     /* sum of the timestamped k_eval_programs durations (n_eval of them)       */
     uint64_t stream_bytes;       /* bitset bytes those dispatches move: every referenced bitset once where the launch streams
-                                    (k_probe_terms); where it gathers (k_probe_gather), the 128-byte lines its terms x k bit tests
-                                    are expected to touch, lines x (1 - exp(-tests / lines)) per filter — what the counters show */
+                                    (k_probe_terms); where it gathers (k_probe_gather), the 128-byte lines the bit tests it EXECUTED
+                                    (counted on the device: a term absent from a block stops early) are expected to touch,
+                                    lines x (1 - exp(-tests / lines)) per filter — what the counters show */
     uint64_t n_probe_arenas;     /* arenas those dispatches covered (one dispatch probes a group of arenas) */
     uint64_t n_eval;
     uint64_t n_fused;            /* timestamped k_probe_fused dispatches (probe of group i + eval of i-1)   */

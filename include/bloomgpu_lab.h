@@ -29,7 +29,11 @@ extern "C" {
  * k_gather_fused per further chunk (gather chunk i + program evaluation of chunk i-1 in one dispatch), then k_eval_programs on the last
  * chunk: 0 = bsh::pipeline_chunks decides (default), 1 = never, n >= 2 (low 16 bits) = n chunks as equal as possible, at most one
  * per arena, whatever the thresholds say; bits 16-23 = percent of an equal share the last chunk gets (0 = equal); bits 24-25 = k_gather_fused's evaluation workgroups
- * 1 = at the front of its grid, 2 = spread among the gather workgroups (0 = the default))) */
+ * 1 = at the front of its grid, 2 = spread among the gather workgroups (0 = the default));
+ * key 28: workgroups of the gather kernels (k_probe_gather, k_probe_gather_ext, k_gather_fused) per CU, kept there by dynamic LDS the
+ * kernels never touch (bsh::gather_lds_pad: floor(160 KiB / n)): 0 = the planner's rule (default: no pad), 1-4 = that many (8 waves
+ * each: 2 / 4 / 6 / 8 waves per SIMD), above 4 = no pad; k_gather_fused is launched with the larger of the pad and an evaluation
+ * workgroup's LDS, so the cap holds for both of its roles) */
 BSG_API int32_t bsg_set_lab(bsg_ctx *ctx, uint32_t key, uint64_t value);
 /* Synchronous probes poll their stream for up to this long before they block (default 0: block at once).  A single
  * query's kernels finish in ~10 us; being woken from a blocking wait costs more than that. */

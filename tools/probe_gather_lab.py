@@ -4,11 +4,17 @@ arena (1 000 blocks x 10 000 rows, fpr 0.001) and batch, 20 arenas per dispatch 
 
     python tools/probe_gather_lab.py c2 [launches [routes]] kernel time per launch from the dispatch timestamps, the three routes interleaved
     python tools/probe_gather_lab.py sweep [launches]     distinct terms per kind {3 .. 128}: gather vs stream, product and big_filters geometry
-    python tools/probe_gather_lab.py pmc ROUTE [launches] launches of ONE route and nothing else (under rocprofv3 --pmc FETCH_SIZE)
+    python tools/probe_gather_lab.py pmc ROUTE [launches [arenas [cap]]]
+                                                          launches of ONE route and nothing else (under rocprofv3 --pmc FETCH_SIZE / TCC_EA0_RDREQ_sum)
+    python tools/probe_gather_lab.py lines                no GPU: the EXACT number of distinct 128-byte lines the executed bit tests of the bench's batch touch
+                                                          per block of the bench's arena, and the tests executed, under every phase schedule of the gather kernel
+    python tools/probe_gather_lab.py caps [rounds [arenas,.. [caps,..]]]
+                                                          the gather route under bsg_set_lab key 28 = workgroups per CU (5 = no cap), the caps taking turns call by
+                                                          call: kernel time (the dispatches' timestamps, summed) and call wall time, survivors left on the device
 
 ROUTE: stream (bsg_set_gather_cost(1 << 20)), block (cost 0, bsg_set_lab key 26 = 0: k_probe_terms' per-block gathered path), gather (cost 0).
 BSG_LAB_LIB=path loads another build of the library (the -DBSG_GATHER_* variants of csrc/kernels.hip.h).
-The numbers on record and the stop rule they are read by: profiles/probe_gather_lab.txt.
+The numbers on record and the stop rule they are read by: profiles/probe_gather_lab.txt, profiles/probe_gather_lines_lab.txt.
 """
 import os
 import sys
@@ -97,6 +103,40 @@ def time_routes(ctx, arenas, bid, per_call, routes, launches, warm=3):
     return out
 
 
+SCHEDULES = ((4, 4, 2), (2, 8), (2, 2, 6), (4, 6), (1, 3, 6), (10,))
+
+
+def touched_lines(words, desc, h, kinds, schedules):
+    """The gather kernel's loads, restated: words / desc of one arena, h [T][4] base hashes, kinds [T] -> {schedule: (tests executed per block,
+    distinct 128-byte lines per block)}.  A lane runs a phase iff every bit of its earlier phases was set; the last length repeats beyond the list."""
+    B, T = len(desc) // 3, len(h)
+    d = desc.reshape(B, 3)
+    m = d["m"][:, kinds].astype(np.uint64)                                # [B][T]
+    k = d["k"][:, kinds].astype(np.int64)
+    base = d["word_off"][:, kinds].astype(np.uint64)
+    kmax = int(k.max())
+    i = np.arange(kmax)
+    with np.errstate(over="ignore"):
+        x = h[:, i % 2] + i.astype(np.uint64)[None, :] * h[:, 2 + ((i + i % 2) % 4) // 2]       # bloom/v3 location(h, i), wrapping u64: [T][k]
+    live = (m > 0)[:, :, None] & (i[None, None, :] < k[:, :, None])
+    loc = x[None, :, :] % np.maximum(m, 1)[:, :, None]                    # [B][T][k]
+    bit = ((words[(base[:, :, None] + (loc >> np.uint64(6))).astype(np.int64)] >> (loc & np.uint64(63))) & np.uint64(1)).astype(bool) | ~live
+    line = (base[:, :, None] * np.uint64(8) + (loc >> np.uint64(3))) >> np.uint64(7)
+    passed = np.concatenate([np.ones((B, T, 1), dtype=bool), np.logical_and.accumulate(bit, axis=2)], axis=2)      # passed[.., j]: bits 0 .. j - 1 all set
+    out = {}
+    for sch in schedules:
+        start, at = np.zeros(kmax, dtype=np.int64), 0
+        for p in range(kmax):
+            ln = sch[min(p, len(sch) - 1)]
+            start[at: at + ln] = at
+            at += ln
+            if at >= kmax:
+                break
+        ran = passed[:, :, start] & live
+        out[sch] = (ran.sum() / B, len(np.unique(line[ran])) / B)
+    return out, x, passed[:, :, kmax] | (m == 0)
+
+
 def fmt(v):
     return "median %7.1f us  (min %7.1f, max %7.1f, spread %5.1f, n = %d)" % (float(np.median(v)), min(v), max(v), max(v) - min(v), len(v))
 
@@ -113,8 +153,28 @@ def same_results(ctx, arenas, bid, nq, n_blocks, routes):
 
 def main():
     mode = sys.argv[1] if len(sys.argv) > 1 else "c2"
-    print("library %s" % _lib.LIB_PATH, flush=True)
     bench.start_pool(16)         # the synthetic generator's workers: forked before the HIP runtime exists here
+    if mode == "lines":          # the CPU oracle alone: its filters, its hashes, its location arithmetic
+        from oracle import oracle as O
+        B, rows = 1000, 10000
+        plan = plan_blocks(bench.generate_blocks(np.arange(B, dtype=np.int64), rows, 0xB100F5EA4C4, 16), 0.001)
+        bench.stop_pool()
+        words = O.build_many(plan.blob, plan.off, plan.fstart, plan.desc.view(O.DESC_DTYPE), plan.n_words)
+        cb = Q.compile_queries(synth.make_queries(4096, "c2", seed=1234))
+        kinds = np.asarray(cb.arrays()[2], dtype=np.int64)
+        h = np.asarray([O.base_hashes(s if isinstance(s, bytes) else s.encode()) for s in cb.term_strings], dtype=np.uint64)
+        res, x, verdict = touched_lines(words, plan.desc, h, kinds, SCHEDULES)
+        for t in range(len(h)):
+            for i in range(x.shape[1]):
+                assert int(x[t, i]) == O.location(tuple(int(v) for v in h[t]), i)
+        d2 = plan.desc.reshape(B, 3)
+        n_present = int((verdict.mean(axis=0) > 0.5).sum())
+        print("bench arena (%d blocks x %d rows, fpr 0.001) and batch (%d distinct terms, %d of them pass in most blocks, kinds %s); field::token filters of %.1f lines, k = %d"
+              % (B, rows, len(h), n_present, sorted(set(kinds.tolist())), float(np.mean((d2["m"][:, 2] + 1023) // 1024)), int(d2["k"][:, 2].max())))
+        for sch, (tests, lines) in res.items():
+            print("  schedule %-10s tests executed per block %6.1f   distinct lines touched per block %6.1f" % (",".join(map(str, sch)), tests, lines))
+        return
+    print("library %s" % _lib.LIB_PATH, flush=True)
     ctx = Context((0,))
     ctx.set_lab(3, 0)            # no one-dispatch path: every launch goes through k_probe_terms / k_probe_gather
     ctx.set_timed_stride(1)
@@ -129,13 +189,54 @@ def main():
             print("  %-7s %s" % (r, fmt(v)), flush=True)
     elif mode == "pmc":
         route, launches = sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 8
+        per_call = int(sys.argv[4]) if len(sys.argv) > 4 else PER_CALL
         arenas, B = c2_arenas(ctx)
         bid, nq, nt = batch_of(ctx, synth.make_queries(4096, "c2", seed=1234))
         set_route(ctx, route)
+        if len(sys.argv) > 5:
+            ctx.set_lab(28, int(sys.argv[5]))
         for i in range(launches):
-            ctx.probe_many(np.ascontiguousarray([arenas[(i * PER_CALL + j) % R] for j in range(PER_CALL)], dtype=np.uint64), bid, _lib.PROBE_ASYNC | _lib.PROBE_NOFUSE)
+            ctx.probe_many(np.ascontiguousarray([arenas[(i * per_call + j) % R] for j in range(per_call)], dtype=np.uint64), bid, _lib.PROBE_ASYNC | _lib.PROBE_NOFUSE)
             ctx.sync()
-        print("pmc: %d launches of %d arenas on route %s" % (launches, PER_CALL, route))
+        print("pmc: %d launches of %d arenas (%d blocks each) on route %s, key 28 = %s" % (launches, per_call, B, route, sys.argv[5] if len(sys.argv) > 5 else "default"))
+    elif mode == "caps":
+        import time
+        rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+        counts = [int(v) for v in sys.argv[3].split(",")] if len(sys.argv) > 3 else [20, 200]
+        caps = [int(v) for v in sys.argv[4].split(",")] if len(sys.argv) > 4 else [5, 3, 2, 1]
+        arenas, B = c2_arenas(ctx)
+        bid, nq, nt = batch_of(ctx, synth.make_queries(4096, "c2", seed=1234))
+        set_route(ctx, "gather")
+        try:
+            ctx.set_lab(28, 0)
+            has_key = True
+        except Exception:                 # a build from before key 28: its one configuration
+            has_key, caps = False, [5]
+        step = 0
+        for n in counts:
+            kern, wall = {c: [] for c in caps}, {c: [] for c in caps}
+            for i in range(2 + rounds):
+                for c in caps:
+                    if has_key:
+                        ctx.set_lab(28, c)
+                    for timed in (True, False):
+                        ids = np.ascontiguousarray([arenas[(step + j) % R] for j in range(n)], dtype=np.uint64)
+                        step += n
+                        ctx.sync()
+                        t0 = time.perf_counter()
+                        ctx.probe_many(ids, bid, _lib.PROBE_ASYNC | (_lib.PROBE_TIMED if timed else 0))
+                        ctx.sync()
+                        w = (time.perf_counter() - t0) * 1e6
+                        if timed:
+                            tm = ctx.timing_read(reset=True)
+                            assert ctx.last_probe_route() in (_lib.ROUTE_GATHER, _lib.ROUTE_GATHER_CHUNKED)
+                            if i >= 2:
+                                kern[c].append((tm.ms_terms_kernel + tm.ms_fused_kernel) * 1e3)
+                        elif i >= 2:
+                            wall[c].append(w)
+            print("%d arenas per call, route %d (us; probe and fused dispatches' own time, and the call's wall time with no timestamps):" % (n, ctx.last_probe_route()))
+            for c in caps:
+                print("  key 28 = %d   gather dispatches %s   wall %s" % (c, fmt(kern[c]), fmt(wall[c])), flush=True)
     elif mode == "sweep":
         launches = int(sys.argv[2]) if len(sys.argv) > 2 else 12
         for name, (arenas, B), per_call, field in (("product geometry: 1 000-block arenas, 20 per launch", c2_arenas(ctx), PER_CALL, "nested.region"),

@@ -1452,7 +1452,8 @@ static int32_t survivor_rows_list_impl(bsg_ctx *ctx, const uint64_t *arena_ids, 
         if (packed) {
             // byte headers (tag << 6 | a LIST row's count); the run of 256 queries this one belongs to: payloads back to back from the
             // run's first slot, in query order
-            if (G > bsg::kRowsStageG) return fail(BSG_E_INVALID, "packed rows hold arenas of at most %u blocks per device", bsg::kRowsStageG * 64);
+            // (the same answer as bsg_probe_many_rows gave for these arenas: no packed rows of them were ever written)
+            if (G > bsg::kRowsStageG) return fail(BSG_E_UNSUPPORTED, "packed rows hold arenas of at most %u blocks per device", bsg::kRowsStageG * 64);
             const uint32_t q0 = query & ~255u;
             const uint8_t *hr = reinterpret_cast<const uint8_t *>(hdr) + ((size_t)d * n_arenas + arena_index) * Q + q0;
             uint64_t off = 0;

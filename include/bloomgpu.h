@@ -300,7 +300,7 @@ BSG_API int32_t bsg_set_probe_group(bsg_ctx *ctx, uint32_t max_arenas_per_launch
  * (i * n_queries + q) of out_hdr (device d's slice: from byte d * n_arenas * n_queries), tag << 6 | count of a LIST row (at most
  * 32); an ALL row counts the arena's blocks, a DENSE row the bits of its words.  Buffer sizes as without the flag (the packed form
  * uses the front of both); arenas of at most 1 024 blocks per device (BSG_E_UNSUPPORTED beyond, before anything is launched).
- * bsg_survivor_rows_list_packed reads such rows. */
+ * bsg_survivor_rows_list_packed reads such rows (and answers BSG_E_UNSUPPORTED for the same arenas: nothing packed was written for them). */
 #define BSG_ROW_NONE  0u
 #define BSG_ROW_ALL   1u
 #define BSG_ROW_LIST  2u

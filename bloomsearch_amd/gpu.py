@@ -166,18 +166,24 @@ class Context:
     def hash_strings(self, entries) -> np.ndarray:
         return self.hash_entries(*pack_entries(entries))
 
-    def build(self, blob, off, filter_entry_start, desc, n_words: int) -> np.ndarray:
+    def build(self, blob, off, filter_entry_start, desc, n_words: int, out: np.ndarray = None) -> np.ndarray:
+        """out: where the words go (u64, >= n_words); the callee zero-fills what no filter owns."""
         assert desc.dtype == DESC_DTYPE
-        out = np.empty(n_words, dtype=np.uint64)
+        if out is None:
+            out = np.empty(n_words, dtype=np.uint64)
+        assert out.dtype == np.uint64 and len(out) >= n_words and out.flags.c_contiguous
         fs = np.ascontiguousarray(filter_entry_start, dtype=np.uint32)
         self._check(self.L.bsg_build(self.h, _lib._ptr(blob), _lib._ptr(off), len(off) - 1, _lib._ptr(fs),
                                      _lib._ptr(desc), len(desc), _lib._ptr(out), n_words))
         return out
 
-    def build_hashed(self, h, filter_entry_start, desc, n_words: int) -> np.ndarray:
+    def build_hashed(self, h, filter_entry_start, desc, n_words: int, out: np.ndarray = None) -> np.ndarray:
+        """out: as build's."""
         assert desc.dtype == DESC_DTYPE
         h = np.ascontiguousarray(h, dtype=np.uint64)
-        out = np.empty(n_words, dtype=np.uint64)
+        if out is None:
+            out = np.empty(n_words, dtype=np.uint64)
+        assert out.dtype == np.uint64 and len(out) >= n_words and out.flags.c_contiguous
         fs = np.ascontiguousarray(filter_entry_start, dtype=np.uint32)
         self._check(self.L.bsg_build_hashed(self.h, _lib._ptr(h), len(h), _lib._ptr(fs), _lib._ptr(desc), len(desc),
                                             _lib._ptr(out), n_words))

@@ -4,7 +4,10 @@ megabits: LDS-staged filters, filters just beyond LDS (global atomics by default
 window counts of 1, 2, many, a last window of a few words; every eighth seed one bitset of 2^31 or 2^33 bits
 (64-bit modulo, sliced global atomics); several filters per call; from entry bytes and from
 precomputed hashes; with the binning threshold at its default and at zero.  Bitsets must equal the oracle's.
-Exits non-zero on the first difference."""
+Exits non-zero on the first difference.
+The suite's fixed counterpart of this sweep: tests/build_shapes.py (cases crafted onto every route, window, tile and slice edge, with
+chosen bit positions) run by tests/test_build_edges_gpu.py, and tests/test_or_reduce_edges_gpu.py for the OR at merge time; what is
+swept here are the sizes in between."""
 import os
 import sys
 

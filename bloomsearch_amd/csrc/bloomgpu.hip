@@ -23,6 +23,7 @@
 #include "host/wide_plan.hpp"  // bsg_match_rows_wide: pair words, condition masks, part cuts and evaluation items
 #include "host/lookup_plan.hpp"  // bsg_match_rows_lookup: string ids, role records, slot placement, flag words
 #include "host/text.hpp"   // the host walker's Unicode tables: the device defers to the same data
+#include "host/substring_pack.hpp"  // substring conditions: a needle's limits and folding, the packed shift-and tables
 #include <hip/hip_ext.h>
 
 #include <algorithm>

@@ -28,6 +28,7 @@
 #include "expression.hpp"
 #include "regex_groups.hpp"
 #include "section_codec.hpp"
+#include "substring.hpp"
 #include "wide_plan.hpp"
 #include "lookup_plan.hpp"
 
@@ -309,13 +310,21 @@ public:
     // regex: the field-scoped regex tree of the query; files and blocks are pruned by
     // pruneBloomQuery = AndBloomQueries(bloom, RegexFieldGuardBloomQuery(regex)) (query_exec.go:220), rows are matched by the
     // bloom tree AND the regex tree (row_matcher.go:353-368).
-    int32_t query(const BloomExpression *row_expr, QueryResult &out, const RegexExpression *regex = nullptr)
+    // sub: the substring tree of the query (substring.hpp).  Its guard over the pruning terms is a third side of the pruning
+    // expression, And(bloom, regex field guard, substring guard); the row test is bloom AND regex AND substring.  Under DeviceMatch a
+    // query without a regex tree is decided by ONE bsg_match_rows_substr call over the program And(bloom root, substring root) (the
+    // rows it hands back: the host matchers); with a regex tree, or without DeviceMatch, SubstringRowMatcher decides on the host.
+    int32_t query(const BloomExpression *row_expr, QueryResult &out, const RegexExpression *regex = nullptr, const SubstringExpression *sub = nullptr)
     {
         out = QueryResult{};
         const auto t_begin = std::chrono::steady_clock::now();
-        BloomExpression guard, prune_storage;
+        SubstringRowMatcher sub_matcher(sub, cfg_.tokenizer);
+        if (!sub_matcher.valid()) return fail(kErrInvalidQuery, "substring needle: non-empty valid UTF-8 of at most 64 bytes after folding");
+        BloomExpression guard, sub_guard, two_storage, prune_storage;
         const bool has_guard = regex_field_guard(regex, guard);
-        const BloomExpression *expr = and_bloom_queries(row_expr, has_guard ? &guard : nullptr, prune_storage) ? &prune_storage : nullptr;
+        const bool has_two = and_bloom_queries(row_expr, has_guard ? &guard : nullptr, two_storage);
+        const bool has_sub_guard = substring_guard(sub, cfg_.tokenizer, sub_guard);
+        const BloomExpression *expr = and_bloom_queries(has_two ? &two_storage : nullptr, has_sub_guard ? &sub_guard : nullptr, prune_storage) ? &prune_storage : nullptr;
         std::vector<Survivors> sv;
         if (int32_t rc = probe_stage({expr}, sv)) return rc;
         const std::vector<uint8_t> &file_ok = sv[0].file_ok;
@@ -342,6 +351,11 @@ public:
             if (!regex_done && !regex_matcher.valid()) return fail(kErrInvalidQuery, "regex pattern does not compile");
         }
         on_device = regex_done;
+        bool sub_done = false;
+        if (sub && !regex && cfg_.device_match && !scan.empty()) {
+            if (int32_t rc = match_rows_device_substr(row_expr, *sub, scan, matcher, sub_matcher, hit, sub_done)) return rc;
+            on_device = sub_done;
+        }
         if (!on_device && cfg_.device_match && row_expr && !scan.empty()) {
             if (int32_t rc = match_rows_device(row_expr, scan, matcher, hit, on_device)) return rc;
         }
@@ -361,6 +375,9 @@ public:
             for (size_t i = 0; i < scan.size(); ++i)
                 if (hit[i]) hit[i] = cand[i] && regex_matcher.match(*scan[i]);
         }
+        if (sub && !sub_done)
+            for (size_t i = 0; i < scan.size(); ++i)
+                if (hit[i]) hit[i] = sub_matcher.match(*scan[i]);
         for (size_t i = 0; i < scan.size(); ++i)
             if (hit[i]) out.rows.push_back(*scan[i]);
         add_scan_time(t_scan, scanned, out);
@@ -376,8 +393,9 @@ public:
     // subset (the test query() makes): it is probed with query()'s pruning expression And(bloom, field guard) and matched as the
     // program And(bloom root | TRUE, regex root) by bsg_match_rows_many_regex.  Every other regex query is answered by query() and
     // placed at its position, and so is a batched one whose group the device did not decide.
+    // A query with a substring tree (subs[i]) is answered by query() too.
     int32_t query_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
-                       std::vector<QueryResult> &results)
+                       std::vector<QueryResult> &results, const std::vector<const SubstringExpression *> *subs = nullptr)
     {
         results.assign(exprs.size(), QueryResult{});
         std::vector<size_t> live;                   // the batch: queries without a regex tree, and regex queries the device matches
@@ -385,6 +403,7 @@ public:
         std::vector<std::unique_ptr<RegexRowMatcher>> regex_dfas;   // per batched query: the DFA-backed matcher of the rows handed back
         for (size_t i = 0; i < exprs.size(); ++i) {
             const RegexExpression *rx = i < regexes.size() ? regexes[i] : nullptr;
+            if (subs && i < subs->size() && (*subs)[i]) { if (int32_t rc = query(exprs[i], results[i], rx, (*subs)[i])) return rc; continue; }
             std::unique_ptr<RegexRowMatcher> dfa;
             if (rx && cfg_.device_match && cfg_.device_regex) {
                 dfa = std::make_unique<RegexRowMatcher>(rx, true);
@@ -1208,6 +1227,40 @@ private:
         for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
         for (uint32_t i = 0; i < n_fb; ++i) hit[fb[i]] = host_matcher.match(*scan[fb[i]]);   // rows outside the device walker's envelope
         on_device = true;
+        return kEngineOk;
+    }
+
+    // And(bloom root, substring root) over the scan list in one bsg_match_rows_substr call; the rows it hands back are decided by both
+    // host matchers.  done stays false (the host decides) beyond 64 conditions or what the call holds (128 needle bytes, depth, ops).
+    int32_t match_rows_device_substr(const BloomExpression *expr, const SubstringExpression &sub, const std::vector<const std::string *> &scan,
+                                     RowMatcher &host_matcher, SubstringRowMatcher &sub_matcher, std::vector<uint8_t> &hit, bool &done)
+    {
+        MatcherProgram mp(expr);
+        if (mp.prog_ops.empty()) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
+        emit_substring_program(sub, mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
+        mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 2));
+        if (mp.kinds.size() > 64) return kEngineOk;
+        std::vector<uint8_t> cbytes;
+        std::vector<uint32_t> coff{0};
+        for (size_t c = 0; c < mp.kinds.size(); ++c) {
+            cbytes.insert(cbytes.end(), mp.fields[c].begin(), mp.fields[c].end()); coff.push_back((uint32_t)cbytes.size());
+            cbytes.insert(cbytes.end(), mp.tokens[c].begin(), mp.tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
+        }
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> row_off{0};
+        for (const std::string *r : scan) { bytes.insert(bytes.end(), r->begin(), r->end()); row_off.push_back(bytes.size()); }
+        std::vector<uint64_t> bits((scan.size() + 63) / 64);
+        std::vector<uint32_t> fb(scan.size());
+        uint32_t n_fb = 0;
+        const bsg_tokenizer tok = c_tokenizer();
+        const int32_t rc = bsg_match_rows_substr(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(),
+                                                 (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok, bits.data(), fb.data(),
+                                                 (uint32_t)fb.size(), &n_fb);
+        if (rc == BSG_E_UNSUPPORTED) return kEngineOk;
+        if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
+        for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
+        for (uint32_t i = 0; i < n_fb; ++i) hit[fb[i]] = host_matcher.match(*scan[fb[i]]) && sub_matcher.match(*scan[fb[i]]);
+        done = true;
         return kEngineOk;
     }
 

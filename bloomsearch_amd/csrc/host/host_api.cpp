@@ -7,6 +7,7 @@
 
 #include "engine.hpp"
 #include "regex_dfa.hpp"
+#include "substring.hpp"
 
 using namespace bsh;
 
@@ -309,6 +310,71 @@ int32_t bsh_prune_query(const char *bloom_json, uint64_t bloom_len, const char *
     return give(s, out, out_len);
 }
 
+namespace {
+bool parse_substring_json(const char *json, uint64_t len, SubstringExpression &e, bool &nil)
+{
+    nil = true;
+    std::string_view sv(json ? json : "", json ? len : 0);
+    if (sv.empty()) return true;
+    JNode dom;
+    if (!parse_dom(sv, dom)) return false;
+    if (dom.type == JType::Null) return true;
+    if (!substring_expression_from_json(dom, e)) return false;
+    nil = false;
+    return true;
+}
+int32_t needle_status(NeedleStatus s) { return s == NeedleStatus::Ok ? 0 : s == NeedleStatus::TooLong ? BSG_E_UNSUPPORTED : BSH_E_INVALID; }
+}  // namespace
+
+// substring_terms (substring.hpp): the tokens a row that contains the needle must hold, packed as bsh_tokenize_with packs tokens
+int32_t bsh_substring_terms(const uint8_t *needle, uint64_t len, const bsg_tokenizer *tok, uint8_t **out, uint64_t *out_len)
+{
+    Tokenizer t;
+    if (!out || (len && !needle) || !tokenizer_from(tok, t)) return BSH_E_INVALID;
+    const std::string_view nd(reinterpret_cast<const char *>(needle), len);
+    std::string folded, packed;
+    if (int32_t rc = needle_status(fold_needle(nd, t, folded))) return rc;
+    for (const std::string &w : substring_terms(nd, t)) {
+        const uint32_t n = (uint32_t)w.size();
+        for (int i = 0; i < 4; ++i) packed.push_back((char)(n >> (8 * i)));
+        packed.append(w);
+    }
+    return give(packed, reinterpret_cast<char **>(out), out_len);
+}
+
+// bsh_prune_query with the substring tree's guard as a third side: And(bloom, regex field guard, substring guard)
+int32_t bsh_prune_query_sub(const char *bloom_json, uint64_t bloom_len, const char *regex_json, uint64_t regex_len, const char *substring_json,
+                            uint64_t substring_len, const bsg_tokenizer *tok, char **out, uint64_t *out_len)
+{
+    BloomExpression b, guard, sguard, two, pruned;
+    RegexExpression r;
+    SubstringExpression sx;
+    Tokenizer t;
+    bool bnil = true, rnil = true, snil = true;
+    if (!tokenizer_from(tok, t) || !parse_expression_json(bloom_json, bloom_len, b, bnil) || !parse_regex_json(regex_json, regex_len, r, rnil) ||
+        !parse_substring_json(substring_json, substring_len, sx, snil))
+        return BSH_E_INVALID;
+    if (!snil) if (int32_t rc = needle_status(check_needles(sx, t))) return rc;
+    const bool has_guard = regex_field_guard(rnil ? nullptr : &r, guard);
+    const bool has_two = and_bloom_queries(bnil ? nullptr : &b, has_guard ? &guard : nullptr, two);
+    const bool has_sub = substring_guard(snil ? nullptr : &sx, t, sguard);
+    std::string s = "null";
+    if (and_bloom_queries(has_two ? &two : nullptr, has_sub ? &sguard : nullptr, pruned)) { s.clear(); expression_to_json(pruned, s); }
+    return give(s, out, out_len);
+}
+
+// the substring half of the final row test (substring.hpp SubstringRowMatcher): 1 match, 0 no match, < 0 invalid arguments / needle
+int32_t bsh_match_row_substring(const char *substring_json, uint64_t substring_len, const uint8_t *row, uint64_t row_len, const bsg_tokenizer *tok)
+{
+    SubstringExpression sx;
+    Tokenizer t;
+    bool nil = true;
+    if (!tokenizer_from(tok, t) || !parse_substring_json(substring_json, substring_len, sx, nil)) return BSH_E_INVALID;
+    SubstringRowMatcher m(nil ? nullptr : &sx, t);
+    if (int32_t rc = needle_status(m.status())) return rc;
+    return m.match(std::string_view(reinterpret_cast<const char *>(row), row_len)) ? 1 : 0;
+}
+
 // the regex half of matchRowBytes (row_matcher.go:548-573): 1 match, 0 no match, < 0 invalid arguments / pattern
 int32_t bsh_match_row_regex(const char *regex_json, uint64_t regex_len, const uint8_t *row, uint64_t row_len)
 {
@@ -428,7 +494,8 @@ namespace {
 struct ParsedQuery {
     BloomExpression expr;
     RegexExpression regex;
-    bool nil = true, has_regex = false;
+    SubstringExpression sub;
+    bool nil = true, has_regex = false, has_sub = false;
 };
 
 int32_t query_from_dom(const JNode &dom, ParsedQuery &q)
@@ -449,6 +516,13 @@ int32_t query_from_dom(const JNode &dom, ParsedQuery &q)
                 if (!regex_expression_from_json(*ex, q.regex)) return BSE_E_INVALID_QUERY;
                 q.has_regex = true;
             }
+        }
+        // "Substring": the tree itself, or {"Expression": tree} as the two other members are wrapped
+        const JNode *sx = dom.get("Substring");
+        if (sx && sx->type == JType::Object) {
+            const JNode *ex = sx->get("Expression");
+            if (!substring_expression_from_json(ex && ex->type == JType::Object ? *ex : *sx, q.sub)) return BSE_E_INVALID_QUERY;
+            q.has_sub = true;
         }
     } else if (dom.type != JType::Null) {
         return BSE_E_INVALID_QUERY;
@@ -488,7 +562,7 @@ int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, char **ou
         if (int32_t rc = query_from_dom(dom, q)) return rc;
     }
     QueryResult res;
-    if (int32_t rc = e->eng->query(q.nil ? nullptr : &q.expr, res, q.has_regex ? &q.regex : nullptr)) return rc;
+    if (int32_t rc = e->eng->query(q.nil ? nullptr : &q.expr, res, q.has_regex ? &q.regex : nullptr, q.has_sub ? &q.sub : nullptr)) return rc;
     std::string out;
     result_to_json(res, out);
     return give(out, out_json, out_len);
@@ -504,9 +578,12 @@ int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, ch
         if (int32_t rc = query_from_dom(dom.items[i], qs[i])) return rc;
     std::vector<const BloomExpression *> exprs;
     std::vector<const RegexExpression *> regexes;
-    for (const ParsedQuery &q : qs) { exprs.push_back(q.nil ? nullptr : &q.expr); regexes.push_back(q.has_regex ? &q.regex : nullptr); }
+    std::vector<const SubstringExpression *> subs;
+    for (const ParsedQuery &q : qs) {
+        exprs.push_back(q.nil ? nullptr : &q.expr); regexes.push_back(q.has_regex ? &q.regex : nullptr); subs.push_back(q.has_sub ? &q.sub : nullptr);
+    }
     std::vector<QueryResult> res;
-    if (int32_t rc = e->eng->query_many(exprs, regexes, res)) return rc;
+    if (int32_t rc = e->eng->query_many(exprs, regexes, res, &subs)) return rc;
     std::string out = "[";
     for (size_t i = 0; i < res.size(); ++i) { if (i) out.push_back(','); result_to_json(res[i], out); }
     out.push_back(']');

@@ -51,6 +51,18 @@
 // run behind k_eval_row_programs over the words it left on the device: a header per pair (NONE / ALL / LIST / DENSE by the count of
 // its matching rows), an exclusive scan of the payload sizes over any number of pairs, then the LIST indices or the DENSE words
 // written back to back.  Headers and payload travel to the host, the words do not.
+//
+// Substring conditions (kinds 4 and 5, k_match_rows_substr* / k_match_rows_many_substr* = the same body with SUB = true): "some leaf's
+// candidate text contains the needle", decided exactly by a third text consumer beside RxNone and RxLaneT.  SubLane runs shift-and
+// (bitap) over ALL of the call's needles at once: the host folds the needles as the call's tokenizer folds text and packs them
+// first-fit into kSubWords words of 64 bit positions (host/substring_pack.hpp), M[b] has the positions whose needle byte is b, START
+// the first position of every needle.  Per folded text byte a lane reads M[b] once from LDS (16 bytes) and steps
+// D = ((D << 1) | START) & M[b], hit |= D & active — whatever the number of needles.  A leaf request clears D (no carry between
+// leaves) and sets active = ANY, the end positions of the any-field needles (0 for null); the condition loop ORs in the end bit of
+// every FieldSubstring condition whose field equals the leaf's path (FieldToken's hash-and-fingerprint compare).  After the walk a
+// condition whose end bit is in `hit` is satisfied.  The consumer folds what it is fed as the tokenizer would: ASCII A-Z + 32, a
+// rune through the walker's lower table (unknown to the table: a fallback row); without BSG_TOK_LOWER bytes go in as they are.
+// LDS: the 4 096-byte table behind the instance's own bytes (the batched instance's 43 780 rounded up to 16: M[b] is one 16-byte read).
 #pragma once
 #include <type_traits>
 #include "ingest.hip.h"
@@ -194,6 +206,57 @@ struct RxLaneT {
 
 typedef RxLaneT<kRxActive> RxLane;
 
+// ---- substring conditions ----
+constexpr uint32_t kSubWords = 2;                                  // 64 needle bytes each
+constexpr uint32_t kSubTableBytes = 256u * kSubWords * 8u;         // M[256][kSubWords]
+constexpr uint32_t kMatchSubLdsBytes = kMatchLdsBytes + kSubTableBytes;
+constexpr uint32_t kMatchManySubBase = (kMatchManyLdsBytes + 15u) & ~15u;
+constexpr uint32_t kMatchManySubLdsBytes = kMatchManySubBase + kSubTableBytes;
+static_assert(kSubWords == 2u && kMatchLdsBytes % 16u == 0u && kMatchSubLdsBytes == 37376u + 4096u && kMatchManySubLdsBytes == 43780u + 12u + 4096u &&
+                  3u * kMatchSubLdsBytes <= 160u * 1024u && 3u * kMatchManySubLdsBytes <= 160u * 1024u,
+              "k_match_rows_substr and k_match_rows_many_substr keep three workgroups per CU, their tables 16-byte aligned");
+struct SubArgs {
+    const uint64_t *table;                  // M[256][kSubWords]
+    uint64_t start[kSubWords], any[kSubWords];
+};
+// A condition's LDS record e[10] in these kernels: kind | word of its needle << 8 | end bit << 16 (kinds 4 and 5; else the kind alone).
+// One lane's shift-and state over the call's packed needles.
+struct SubLane {
+    const lds_u64i *m;
+    const Walker *wk;                       // its lower table, and whether the current leaf is one that is never emitted
+    uint64_t s0, s1, d0, d1, a0, a1, h0, h1;
+    bool lower, fail;
+    __device__ __forceinline__ void step(uint32_t b)
+    {
+        const lds_u64i *e = m + b * kSubWords;
+        const uint64_t m0 = e[0], m1 = e[1];
+        d0 = ((d0 << 1) | s0) & m0;
+        d1 = ((d1 << 1) | s1) & m1;
+        if (!wk->quiet) { h0 |= d0 & a0; h1 |= d1 & a1; }          // a leaf without a path has no request: it is no candidate text
+    }
+    __device__ __forceinline__ void feed(uint32_t b)
+    {
+        if (lower && b - (uint32_t)'A' < 26u) b += 32u;
+        step(b);
+    }
+    __device__ __forceinline__ void feed_run(uint64_t v, uint32_t n)
+    {
+        for (uint32_t i = 0; i < n; ++i) feed(c_at(v, i));
+    }
+    __device__ __forceinline__ void feed_rune(uint32_t r)          // r >= 0x80
+    {
+        if (lower) {
+            const uint32_t lo = r < 0x20000u ? wk->lower[r] : 0u;
+            if (lo == 0xFFFFFFFFu) { fail = true; return; }
+            if (lo != 0u) r = lo;
+        }
+        if (r < 0x80u) { step(r); return; }                        // U+212A -> 'k': lower case already
+        uint32_t n = 1;
+        const uint32_t bytes = rune_utf8(r, n);
+        for (uint32_t i = 0; i < n; ++i) step((bytes >> (8u * i)) & 0xFFu);
+    }
+};
+
 // the set of row g: the first s whose rows end behind it (set_first_row[n_sets] = the number of rows > g)
 __device__ __forceinline__ uint32_t row_set_of(const uint32_t *set_first_row, uint32_t n_sets, uint32_t g)
 {
@@ -205,11 +268,13 @@ __device__ __forceinline__ uint32_t row_set_of(const uint32_t *set_first_row, ui
     return lo;
 }
 
-template <bool REGEX, class TOK, bool MANY = false, uint32_t SLOTS = kRxActive, bool WIDE = false>
+template <bool REGEX, class TOK, bool MANY = false, uint32_t SLOTS = kRxActive, bool WIDE = false, bool SUB = false>
 __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs &x, const TOK &tk, const MatchManyArgs &m = MatchManyArgs{},
-                                                const MatchWideArgs &wd = MatchWideArgs{})
+                                                const MatchWideArgs &wd = MatchWideArgs{}, const SubArgs &sb = SubArgs{})
 {
     static_assert(!(MANY && WIDE), "the storing walker evaluates no program");
+    static_assert(!(SUB && (REGEX || WIDE)), "substring conditions: the single and the batched call, without regex conditions");
+    constexpr uint32_t kSubBase = MANY ? kMatchManySubBase : kMatchLdsBytes;   // the needle table sits behind the instance's own LDS
     constexpr uint32_t kProgBytes = WIDE ? 0u : MANY ? kMatchManyProgBytes : kMatchMaxOps * 4;
     constexpr uint32_t kRxBase = WIDE ? kMatchWideLdsBytes : MANY ? kMatchManyLdsBytes : kMatchLdsBytes;   // the regex blob sits behind the instance's own LDS
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
@@ -228,6 +293,8 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
         for (uint32_t i = threadIdx.x; i <= m.n_queries; i += kIngestThreads) prog[kMatchManyMaxOps + i] = m.prog_off[i];
     if constexpr (REGEX)
         for (uint32_t i = threadIdx.x; i < x.n_words; i += kIngestThreads) ((lds_u32 *)(lds_raw + kRxBase))[i] = x.blob[i];
+    if constexpr (SUB)
+        for (uint32_t i = threadIdx.x; i < 256u * kSubWords; i += kIngestThreads) ((lds_u64i *)(lds_raw + kSubBase))[i] = sb.table[i];
     __syncthreads();
     const uint32_t r = blockIdx.x * kIngestThreads + threadIdx.x;
     const bool live = r < a.n_rows;
@@ -252,13 +319,21 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
     uint32_t res = walk ? R_CONTINUE : R_DONE;
     uint64_t sat = 0, leaf_mask = 0;
     bool collided = false;       // equal hashes, different fingerprint: only the host's byte compare can decide this row
-    typename std::conditional<REGEX, RxLaneT<SLOTS>, RxNone>::type rx;
+    typename std::conditional<REGEX, RxLaneT<SLOTS>, typename std::conditional<SUB, SubLane, RxNone>::type>::type rx;
     bool rx_over = false;        // more regex conditions on one leaf than a lane holds: the host decides this row
     if constexpr (REGEX) {
         rx.tab = (const lds_u8 *)lds_raw + kRxBase;
         rx.sat = 0;
 #pragma unroll
         for (uint32_t k = 0; k < SLOTS; ++k) rx.hd[k] = ~0u;
+    }
+    if constexpr (SUB) {
+        rx.m = (const lds_u64i *)(lds_raw + kSubBase);
+        rx.wk = &w;
+        rx.s0 = sb.start[0]; rx.s1 = sb.start[1];
+        rx.d0 = rx.d1 = rx.a0 = rx.a1 = rx.h0 = rx.h1 = 0;
+        rx.lower = tk.lower();
+        rx.fail = false;
     }
     while (__ballot(res == R_CONTINUE || w.req != Q_NONE) != 0ull) {
         while (__ballot(res == R_CONTINUE && w.req == Q_NONE) != 0ull)
@@ -305,10 +380,32 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
             }
         }
         const bool is_path = q == Q_FIELD || q == Q_LEAF, is_word = q == Q_WORD;
+        bool sub_text = false;                                           // SUB: this request opens a leaf with a candidate text
+        if constexpr (SUB) {
+            if (q == Q_LEAF) {                                           // a new leaf: no carry from the one before, the any-field needles listen
+                sub_text = !(w.st == S_LIT && w.lit == 2u);              // null is never a candidate text
+                rx.d0 = rx.d1 = 0;
+                rx.a0 = sub_text ? sb.any[0] : 0ull;
+                rx.a1 = sub_text ? sb.any[1] : 0ull;
+            }
+        }
         for (uint32_t c = 0; c < a.n_conds; ++c) {                       // uniform loop: the conditions come from LDS broadcasts
             const lds_u64i *e = conds + c * kMatchCondWords;
-            const uint32_t kind = (uint32_t)e[10];                       // 0 Field, 1 Token, 2 FieldToken
+            const uint32_t kind = SUB ? ((uint32_t)e[10] & 0xFFu) : (uint32_t)e[10];   // 0 Field, 1 Token, 2 FieldToken
             if (REGEX && kind == 3u) continue;                           // FieldRegex: the DFAs above
+            if constexpr (SUB) {
+                if (kind >= 4u) {                                        // Substring: SubLane decides; FieldSubstring: on the leaves of its own path
+                    if (kind == 5u) {
+                        const bool heq = is_path && e[0] == h[0] && e[1] == h[1] && e[2] == h[2] && e[3] == h[3];
+                        const bool eq = heq && e[8] == fp;
+                        collided |= heq && !eq;
+                        const uint32_t rec = (uint32_t)e[10];
+                        const uint64_t end = 1ULL << ((rec >> 16) & 63u);
+                        if (eq && sub_text) { if ((rec >> 8) & 1u) rx.a1 |= end; else rx.a0 |= end; }
+                    }
+                    continue;
+                }
+            }
             const uint64_t bit = 1ULL << c;
             if (kind != 1u) {                                            // conditions with a field: compare paths
                 const bool heq = is_path && e[0] == h[0] && e[1] == h[1] && e[2] == h[2] && e[3] == h[3];
@@ -331,6 +428,13 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
         for (uint32_t j = 0; j < x.n_rx; ++j)
             if ((rx.sat >> j) & 1u) sat |= 1ULL << (hdr[4 * j + 1] >> 16);
         if (rx_over && res == R_DONE) res = R_FAIL;
+    }
+    if constexpr (SUB) {
+        for (uint32_t c = 0; c < a.n_conds; ++c) {                       // uniform loop
+            const uint32_t rec = (uint32_t)conds[c * kMatchCondWords + 10];
+            if ((rec & 0xFFu) >= 4u && ((((rec >> 8) & 1u) ? rx.h1 : rx.h0) >> ((rec >> 16) & 63u)) & 1ULL) sat |= 1ULL << c;
+        }
+        if (rx.fail && res == R_DONE) res = R_FAIL;                      // a rune the lower table cannot decide: the host's ToLower does
     }
     if constexpr (WIDE) {
         // nothing is evaluated here: the flags and what became of the row go to device memory for k_eval_row_programs
@@ -431,6 +535,33 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_tok(co
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_gram(const MatchArgs a, const RxArgs x, const MatchManyArgs m, const TokSpec t)
 {
     match_rows_body<true, TokGramP, true, kRxManyActive>(a, x, TokGramP(t), m);
+}
+
+// Field / Token / FieldToken and Substring / FieldSubstring conditions (bsg_match_rows_substr / bsg_match_rows_many_substr); dynamic
+// LDS kMatchSubLdsBytes / kMatchManySubLdsBytes
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_substr(const MatchArgs a, const SubArgs sb)
+{
+    match_rows_body<false, TokDefault, false, kRxActive, false, true>(a, RxArgs{}, TokDefault{}, MatchManyArgs{}, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_substr_tok(const MatchArgs a, const SubArgs sb, const TokSpec t)
+{
+    match_rows_body<false, TokSpecP, false, kRxActive, false, true>(a, RxArgs{}, TokSpecP{t}, MatchManyArgs{}, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_substr_gram(const MatchArgs a, const SubArgs sb, const TokSpec t)
+{
+    match_rows_body<false, TokGramP, false, kRxActive, false, true>(a, RxArgs{}, TokGramP(t), MatchManyArgs{}, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_substr(const MatchArgs a, const SubArgs sb, const MatchManyArgs m)
+{
+    match_rows_body<false, TokDefault, true, kRxActive, false, true>(a, RxArgs{}, TokDefault{}, m, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_substr_tok(const MatchArgs a, const SubArgs sb, const MatchManyArgs m, const TokSpec t)
+{
+    match_rows_body<false, TokSpecP, true, kRxActive, false, true>(a, RxArgs{}, TokSpecP{t}, m, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_substr_gram(const MatchArgs a, const SubArgs sb, const MatchManyArgs m, const TokSpec t)
+{
+    match_rows_body<false, TokGramP, true, kRxActive, false, true>(a, RxArgs{}, TokGramP(t), m, MatchWideArgs{}, sb);
 }
 
 // the storing walker (bsg_match_rows_wide): plain / regex x default / spec / n-gram tokenizer; dynamic LDS kMatchWideLdsBytes (+ the table

@@ -6,6 +6,9 @@
 // What a family adds to a part is its PartMode (PlanePart: bit planes; WidePart: stored flags, k_eval_row_programs, pair words —
 // or, for bsg_match_rows_wide_rows, the same part with the rows policy: three more passes turn the words into tagged row lists on
 // the device, headers and payload come back instead, and match_fan_out's finish step stitches the parts into the call's result).
+// bsg_match_rows_substr / bsg_match_rows_many_substr are the single and the batched call with Substring / FieldSubstring conditions in the
+// table: build_sub_tables folds and packs the needles (host/substring_pack.hpp) where the regex calls build their blob, the part
+// uploads the 4 KiB table, and PlanePart launches the substring instances of the walker.
 // bsg_match_rows_lookup(_rows) is the wide call with another Family and a LookupPlan beside its WidePlan: WidePart then sizes the
 // flags at W words per row, places the lookup tables (host/lookup_plan.hpp) from the hashes the device made, and launches
 // match_lookup.hip.h's walker and evaluator in place of match.hip.h's.  bsg_match_rows_lookup_regex(_rows) is that call with FieldRegex
@@ -45,6 +48,9 @@ int32_t build_rx_blob(const uint8_t *cond_bytes, const uint32_t *cond_off, const
     }
 }
 
+static_assert(bsh::kSubWords == bsg::kSubWords && sizeof(uint64_t) * 256 * bsh::kSubWords == bsg::kSubTableBytes && bsh::kSubMaxNeedle == 64,
+              "host/substring_pack.hpp states the substring kernels' table");
+
 static_assert(bsh_wide::kWideLdsCap == bsg::kRxWideLdsCap && sizeof(bsh_wide::EvalItem) == sizeof(bsg::RowEvalItem) &&
                   offsetof(bsh_wide::EvalItem, stride) == offsetof(bsg::RowEvalItem, stride),
               "host/wide_plan.hpp states the kernels' limits and item layout");
@@ -77,6 +83,9 @@ struct MatchCall {
     std::vector<uint32_t> prog_off{0};     // [n_queries + 1] into prog
     std::vector<uint32_t> rx_blob;         // build_rx_blob
     uint32_t n_rx = 0;
+    bool substr = false;                   // build_sub_tables: the call holds the substring walkers' tables
+    bsh::NeedlePack sub;                   // ... M, START, ANY
+    std::vector<uint32_t> sub_kinds;       // ... and cond_kinds with word | end bit of a substring condition's needle (match.hip.h SubLane)
     bsg::TokSpec spec{};                   // tok_spec
     bool default_tok = true;
     const bsg::TokSpec *tok() const { return default_tok ? nullptr : &spec; }
@@ -155,6 +164,38 @@ int32_t lower_programs(MatchCall &mc, const Family &f, const uint32_t *prog_ops,
     return BSG_OK;
 }
 
+// The needle tables of a call's Substring / FieldSubstring conditions: each needle (entry 2c + 1, raw) is checked and folded under
+// the call's own tokenizer, then all are packed first-fit.  BSG_E_INVALID for an empty needle or invalid UTF-8, BSG_E_UNSUPPORTED
+// for a needle over 64 folded bytes or needles that do not fit the kSubWords x 64 positions, before anything is launched.
+// mc.cond_kinds then points at the kinds with each needle's place.
+int32_t build_sub_tables(MatchCall &mc)
+{
+    bsh::Tokenizer t;                      // only lower() is read: separators and the width play no part in the exact test
+    if (!mc.default_tok) t.flags = mc.spec.flags;
+    std::vector<std::string> folded;
+    std::vector<uint8_t> any_field;
+    std::vector<uint32_t> cond_of;
+    for (uint32_t c = 0; c < mc.n_conds; ++c) {
+        if (mc.cond_kinds[c] != BSG_KIND_SUBSTRING && mc.cond_kinds[c] != BSG_KIND_FIELD_SUBSTRING) continue;
+        const std::string_view needle((const char *)mc.cond_bytes + mc.cond_off[2 * c + 1], mc.cond_off[2 * c + 2] - mc.cond_off[2 * c + 1]);
+        folded.emplace_back();
+        switch (bsh::fold_needle(needle, t, folded.back())) {
+        case bsh::NeedleStatus::Ok: break;
+        case bsh::NeedleStatus::Invalid: return fail(BSG_E_INVALID, "condition %u: a needle is non-empty valid UTF-8", c);
+        default: return fail(BSG_E_UNSUPPORTED, "condition %u: a needle of %zu bytes after folding (the device matcher holds %u)", c, folded.back().size(), bsh::kSubMaxNeedle);
+        }
+        any_field.push_back(mc.cond_kinds[c] == BSG_KIND_SUBSTRING);
+        cond_of.push_back(c);
+    }
+    if (!bsh::pack_needles(folded, any_field, mc.sub))
+        return fail(BSG_E_UNSUPPORTED, "the needles of %zu substring conditions do not fit %u words of 64 bytes", folded.size(), bsh::kSubWords);
+    mc.sub_kinds.assign(mc.cond_kinds, mc.cond_kinds + mc.n_conds);
+    for (size_t i = 0; i < cond_of.size(); ++i) mc.sub_kinds[cond_of[i]] |= mc.sub.where[i] << 8;   // word << 8 | end bit << 16
+    mc.cond_kinds = mc.sub_kinds.data();
+    mc.substr = true;
+    return BSG_OK;
+}
+
 // ---- the twenty-four walkers: (single / many / wide / lookup) x (regex) x (default tokenizer / spec / spec with an n-gram width) ----
 // E: the mode's own argument struct (none, MatchManyArgs, MatchWideArgs, MatchLookupArgs).  Dynamic LDS: the mode's base (the lookup
 // walkers': what the launch's tables take) plus the regex blob's bytes (a call without regex conditions has no blob).
@@ -176,6 +217,18 @@ constexpr Walkers<bsg::MatchWideArgs> kWideWalkers{bsg::k_match_rows_store, bsg:
 constexpr Walkers<bsg::MatchLookupArgs> kLookupWalkers{bsg::k_match_rows_lookup, bsg::k_match_rows_lookup_tok, bsg::k_match_rows_lookup_regex,
                                                        bsg::k_match_rows_lookup_regex_tok, bsg::k_match_rows_lookup_gram,
                                                        bsg::k_match_rows_lookup_regex_gram};   // regex: bsg_match_rows_lookup_regex(_rows) only
+
+// ... and the six with the substring consumer: (single / many) x (default tokenizer / spec / spec with an n-gram width)
+template <class... E>
+void launch_sub_walker(void (*plain)(bsg::MatchArgs, bsg::SubArgs, E...), void (*tokk)(bsg::MatchArgs, bsg::SubArgs, E..., bsg::TokSpec),
+                       void (*gramk)(bsg::MatchArgs, bsg::SubArgs, E..., bsg::TokSpec), uint32_t lds, hipStream_t stream, hipEvent_t k0, hipEvent_t k1,
+                       const bsg::MatchArgs &a, const bsg::SubArgs &sb, const bsg::TokSpec *tok, const E &...e)
+{
+    const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads), block(bsg::kIngestThreads);
+    if (tok && tok->ngram != 0u) hipExtLaunchKernelGGL(gramk, grid, block, lds, stream, k0, k1, 0, a, sb, e..., *tok);
+    else if (tok) hipExtLaunchKernelGGL(tokk, grid, block, lds, stream, k0, k1, 0, a, sb, e..., *tok);
+    else hipExtLaunchKernelGGL(plain, grid, block, lds, stream, k0, k1, 0, a, sb, e...);
+}
 
 // one chunk's walk: a.n_rows rows, one per lane, between the events k0 and k1
 template <class... E>
@@ -202,6 +255,7 @@ struct PartDev {
     uint32_t r0, n_rows;
     uint32_t *d_prog = nullptr, *d_poff = nullptr;     // the call's lowered programs and (mode.prog_off()) their offsets
     bsg::RxArgs rx{};                                  // the regex blob
+    bsg::SubArgs sub{};                                // the needle tables (mc.substr)
     const uint64_t *d_ch = nullptr;                    // [2 * n_conds][4]: the condition strings' base hashes (k_hash_fp_entries, enqueued)
 };
 
@@ -225,7 +279,11 @@ struct PlanePart {
     uint64_t *d_bits = nullptr, *d_smask = nullptr;
     uint32_t *d_sfirst = nullptr;
 
-    const char *tag() const { return many ? (mc.n_rx ? "bsg_match_rows_many_regex" : "bsg_match_rows_many") : "bsg_match_rows"; }
+    const char *tag() const
+    {
+        if (mc.substr) return many ? "bsg_match_rows_many_substr" : "bsg_match_rows_substr";
+        return many ? (mc.n_rx ? "bsg_match_rows_many_regex" : "bsg_match_rows_many") : "bsg_match_rows";
+    }
     bool prog_off() const { return many != nullptr; }
     int32_t plan(uint32_t r0, uint32_t r1)
     {
@@ -257,6 +315,13 @@ struct PlanePart {
     void launch(PartDev &p, bsg::MatchArgs &a, uint32_t rf, hipEvent_t k0, hipEvent_t k1)
     {
         a.prog = p.d_prog; a.n_ops = (uint32_t)mc.prog.size(); a.out_bits = d_bits + rf / 64;
+        if (mc.substr) {
+            if (many) launch_sub_walker(bsg::k_match_rows_many_substr, bsg::k_match_rows_many_substr_tok, bsg::k_match_rows_many_substr_gram, bsg::kMatchManySubLdsBytes,
+                                        p.d.stream, k0, k1, a, p.sub, mc.tok(), bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
+            else launch_sub_walker(bsg::k_match_rows_substr, bsg::k_match_rows_substr_tok, bsg::k_match_rows_substr_gram, bsg::kMatchSubLdsBytes, p.d.stream, k0, k1, a,
+                                   p.sub, mc.tok());
+            return;
+        }
         if (many) launch_walker(kManyWalkers, bsg::kMatchManyLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok(), bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
         else launch_walker(kSingleWalkers, bsg::kMatchLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok());
     }
@@ -497,6 +562,7 @@ int32_t match_part(bsg_ctx *ctx, Device &d, const MatchCall &mc, uint32_t r0, ui
     uint8_t *d_rows = nullptr, *d_cbytes = nullptr;
     uint64_t *d_off = nullptr, *d_ch = nullptr, *d_cfp = nullptr;
     uint32_t *d_fb = nullptr, *d_nfb = nullptr, *d_coff = nullptr, *d_ckind = nullptr, *d_rx = nullptr;
+    uint64_t *d_sub = nullptr;
     HIP_TRY(scratch.alloc(&d_rows, n_bytes + 64));
     HIP_TRY(scratch.alloc(&d_off, ((size_t)n_rows + 1) * 8));
     HIP_TRY(scratch.alloc(&d_ch, std::max<size_t>(n_conds, 1) * 2 * 32));
@@ -509,6 +575,7 @@ int32_t match_part(bsg_ctx *ctx, Device &d, const MatchCall &mc, uint32_t r0, ui
     HIP_TRY(scratch.alloc(&d_fb, (size_t)n_rows * 4));
     HIP_TRY(scratch.alloc(&d_nfb, 4));
     if (mc.n_rx) HIP_TRY(scratch.alloc(&d_rx, mc.rx_blob.size() * 4));
+    if (mc.substr) HIP_TRY(scratch.alloc(&d_sub, (size_t)bsg::kSubTableBytes));
     if (int32_t rc = mode.alloc(p)) return rc;
     trace.lap("device buffers allocated");
     HIP_TRY(hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream));
@@ -528,6 +595,10 @@ int32_t match_part(bsg_ctx *ctx, Device &d, const MatchCall &mc, uint32_t r0, ui
     HIP_TRY(hipMemsetAsync(d_nfb, 0, 4, d.stream));
     if (mc.n_rx) HIP_TRY(hipMemcpyAsync(d_rx, mc.rx_blob.data(), mc.rx_blob.size() * 4, hipMemcpyHostToDevice, d.stream));
     p.rx = bsg::RxArgs{d_rx, (uint32_t)mc.rx_blob.size(), mc.n_rx};
+    if (mc.substr) {
+        HIP_TRY(hipMemcpyAsync(d_sub, mc.sub.m.data(), (size_t)bsg::kSubTableBytes, hipMemcpyHostToDevice, d.stream));
+        p.sub = bsg::SubArgs{d_sub, {mc.sub.start[0], mc.sub.start[1]}, {mc.sub.any[0], mc.sub.any[1]}};
+    }
     p.d_ch = d_ch;
     if (int32_t rc = mode.upload(p)) return rc;
     // The rows travel in chunks while the chunk before is being matched (RowUpload).  A surviving block is <= 10 MiB and goes in
@@ -606,6 +677,8 @@ int32_t match_fan_out(bsg_ctx *ctx, const MatchCall &mc, const uint32_t *set_fir
     return match_fan_out(ctx, mc, set_first_row, n_sets, part, [] { return (int32_t)BSG_OK; });
 }
 
+constexpr const char *kNoRegexWithSubstr = "condition %u: a FieldRegex condition (regex and substring conditions do not share a call yet)";
+
 // the single and the batched calls' parts: planes over the implicit set {0, n_rows} (cuts at multiples of 64 rows)
 int32_t match_planes_run(bsg_ctx *ctx, const MatchCall &mc, const ManyPlan *many)
 {
@@ -618,14 +691,18 @@ int32_t match_planes_run(bsg_ctx *ctx, const MatchCall &mc, const ManyPlan *many
 
 // bsg_match_rows (max_kind 2), bsg_match_rows_regex (max_kind 3) and bsg_match_rows_tok (max_kind 3, a spec; NULL = default): the
 // one-query case of the shared checks
-int32_t match_rows_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, uint32_t n_ops, uint32_t max_kind, const bsg_tokenizer *tok_in)
+// and bsg_match_rows_substr (substr: kinds 0, 1, 2, 4, 5 under a spec or NULL)
+int32_t match_rows_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, uint32_t n_ops, uint32_t max_kind, const bsg_tokenizer *tok_in, bool substr = false)
 {
     const uint32_t prog_off[2] = {0, n_ops};
     if (int32_t rc = begin_match_call(mc, kSingleFamily, tok_in, prog_ops, prog_off, 1)) return rc;
-    for (uint32_t c = 0; c < mc.n_conds; ++c)
+    for (uint32_t c = 0; c < mc.n_conds; ++c) {
+        if (substr && mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX) return fail(BSG_E_UNSUPPORTED, kNoRegexWithSubstr, c);
         if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
+    }
     if (int32_t rc = lower_programs(mc, kSingleFamily, prog_ops, prog_off, 1)) return rc;
-    if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx)) return rc;
+    if (substr) { if (int32_t rc = build_sub_tables(mc)) return rc; }
+    else if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx)) return rc;
     *mc.out_n_fallback = 0;
     if (mc.n_rows == 0) return BSG_OK;
     return match_planes_run(ctx, mc, nullptr);
@@ -635,11 +712,12 @@ int32_t match_rows_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, u
 // conditions, one upload and one walk of the rows
 int32_t match_rows_many_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
                              const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets, const bsg_tokenizer *tok_in,
-                             uint32_t max_kind)
+                             uint32_t max_kind, bool substr = false)
 {
     if (int32_t rc = begin_match_call(mc, kManyFamily, tok_in, prog_ops, prog_off, n_queries)) return rc;
     const uint32_t n_rows = mc.n_rows;
     for (uint32_t c = 0; c < mc.n_conds; ++c) {
+        if (substr && mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX) return fail(BSG_E_UNSUPPORTED, kNoRegexWithSubstr, c);
         if (mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX && max_kind < BSG_KIND_FIELD_REGEX)
             return fail(BSG_E_UNSUPPORTED, "condition %u: FieldRegex conditions are not matched by the batched call (use bsg_match_rows_regex)", c);
         if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
@@ -657,7 +735,8 @@ int32_t match_rows_many_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
     const ManyPlan plan{set_first_row, query_mask_of_set, n_sets, n_queries, ((size_t)n_rows + 63) / 64};
     if (int32_t rc = lower_programs(mc, kManyFamily, prog_ops, prog_off, n_queries)) return rc;
     // the regex conditions' tables, each with the queries that use it (a table without any: exactly bsg_match_rows_many's kernels)
-    if (max_kind >= BSG_KIND_FIELD_REGEX && n_queries) {
+    if (substr) { if (int32_t rc = build_sub_tables(mc)) return rc; }
+    else if (max_kind >= BSG_KIND_FIELD_REGEX && n_queries) {
         const std::vector<uint64_t> users = bsh_rxg::user_masks(prog_ops, prog_off, n_queries, mc.n_conds);
         if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, bsg::kRxManyLdsCap, users.data())) return rc;
     }
@@ -927,6 +1006,27 @@ int32_t bsg_match_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *ro
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
     return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_REGEX, tok);
+}
+
+int32_t bsg_match_rows_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                              const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                              const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
+                              uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_SUBSTRING, tok, true);
+}
+
+int32_t bsg_match_rows_many_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                   const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                   const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                   const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets, const bsg_tokenizer *tok,
+                                   uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_SUBSTRING, true);
 }
 
 int32_t bsg_match_rows_many(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,

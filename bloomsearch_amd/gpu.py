@@ -657,7 +657,12 @@ class Context:
         """bsg_match_rows_regex: as match_rows, and the matcher (query.CompiledRowQuery) may hold FieldRegex conditions."""
         return self._match_rows(self.L.bsg_match_rows_regex, rows, matcher, tokenizer)
 
-    def _match_rows(self, fn, rows, matcher, tokenizer=None):
+    def match_rows_substr(self, rows, matcher, tokenizer=None):
+        """bsg_match_rows_substr: as match_rows, and the matcher (query.CompiledSubstringQuery) may hold Substring / FieldSubstring
+        conditions (raw needles; the call folds them under `tokenizer`, None = the default)."""
+        return self._match_rows(None, rows, matcher, tokenizer, tok_fn=self.L.bsg_match_rows_substr)
+
+    def _match_rows(self, fn, rows, matcher, tokenizer=None, tok_fn=None):
         if isinstance(rows, tuple):
             blob = np.ascontiguousarray(rows[0], dtype=np.uint8)
             off = np.ascontiguousarray(rows[1], dtype=np.uint64)
@@ -674,8 +679,8 @@ class Context:
         bits = np.zeros((n + 63) // 64, dtype=np.uint64)
         fb = np.zeros(max(n, 1), dtype=np.uint32)
         nfb = C.c_uint32()
-        if tokenizer is not None:
-            self._check(self.L.bsg_match_rows_tok(self.h, _lib._ptr(blob), _lib._ptr(off), n, _lib._ptr(cblob), _lib._ptr(coff), _lib._ptr(kinds),
+        if tokenizer is not None or tok_fn is not None:
+            self._check((tok_fn or self.L.bsg_match_rows_tok)(self.h, _lib._ptr(blob), _lib._ptr(off), n, _lib._ptr(cblob), _lib._ptr(coff), _lib._ptr(kinds),
                                                   len(kinds), _lib._ptr(ops), len(ops), c_spec(tokenizer), _lib._ptr(bits), _lib._ptr(fb), len(fb),
                                                   C.byref(nfb)))
         else:
@@ -693,6 +698,11 @@ class Context:
     def match_rows_many_regex(self, rows, batch, set_first_row=None, masks=None, tokenizer=None):
         """bsg_match_rows_many_regex: as match_rows_many, and the batch (query.CompiledRowQueryBatch) may hold FieldRegex conditions."""
         return self._match_rows_many(self.L.bsg_match_rows_many_regex, rows, batch, set_first_row, masks, tokenizer)
+
+    def match_rows_many_substr(self, rows, batch, set_first_row=None, masks=None, tokenizer=None):
+        """bsg_match_rows_many_substr: as match_rows_many, and the batch (query.CompiledSubstringQueryBatch) may hold Substring /
+        FieldSubstring conditions."""
+        return self._match_rows_many(self.L.bsg_match_rows_many_substr, rows, batch, set_first_row, masks, tokenizer)
 
     def _match_rows_many(self, fn, rows, batch, set_first_row, masks, tokenizer):
         if isinstance(rows, tuple):

@@ -17,6 +17,7 @@ HOST_EXPORTS = [
     "bsh_entry_sets_index_row_with",
     "bsh_entry_sets_union_into", "bsh_entry_sets_counts", "bsh_entry_sets_export_sizes", "bsh_entry_sets_export",
     "bsh_batch_new", "bsh_batch_free", "bsh_batch_add_query", "bsh_batch_sizes", "bsh_batch_export", "bsh_match_row", "bsh_match_row_with", "bsh_prune_query", "bsh_match_row_regex",
+    "bsh_substring_terms", "bsh_prune_query_sub", "bsh_match_row_substring",
     "bsh_regex_match",
     "bsh_section_encode", "bsh_section_parse", "bsh_crc32c",
     "bse_open", "bse_close", "bse_last_error", "bse_stop", "bse_ingest_rows", "bse_flush", "bse_merge", "bse_query", "bse_query_many",
@@ -60,6 +61,9 @@ def lib():
     L.bsh_prune_query.argtypes = [C.c_char_p, u64, C.c_char_p, u64, pp, pu64]
     L.bsh_match_row_regex.argtypes = [C.c_char_p, u64, C.c_char_p, u64]
     L.bsh_regex_match.argtypes = [C.c_char_p, u64, C.c_char_p, u64]
+    L.bsh_substring_terms.argtypes = [C.c_char_p, u64, C.POINTER(_lib.Tokenizer), pp, pu64]
+    L.bsh_prune_query_sub.argtypes = [C.c_char_p, u64, C.c_char_p, u64, C.c_char_p, u64, C.POINTER(_lib.Tokenizer), pp, pu64]
+    L.bsh_match_row_substring.argtypes = [C.c_char_p, u64, C.c_char_p, u64, C.POINTER(_lib.Tokenizer)]
     L.bsh_section_encode.argtypes = [C.POINTER(vp), pu64, pu64, pp, pu64]
     L.bsh_section_parse.argtypes = [C.c_char_p, u64, pu64, pu64, C.POINTER(vp)]
     L.bsh_crc32c.argtypes = [C.c_char_p, u64]; L.bsh_crc32c.restype = u32
@@ -230,6 +234,43 @@ def match_row_regex(regex_expression, row: bytes) -> bool:
     return bool(rc)
 
 
+def substring_terms(needle: bytes | str, tokenizer=None, as_bytes: bool = False) -> list:
+    """bsh_substring_terms: the pruning terms of one needle under `tokenizer` (None = the default)."""
+    L = lib()
+    b = needle.encode("utf-8", "surrogatepass") if isinstance(needle, str) else needle
+    p, n = C.c_void_p(), C.c_uint64()
+    rc = L.bsh_substring_terms(b, len(b), c_spec(tokenizer), C.byref(p), C.byref(n))
+    if rc:
+        raise HostError(rc, "needle: non-empty valid UTF-8 of at most 64 bytes after folding")
+    raw, out, i = _take(L, p, n), [], 0
+    while i < len(raw):
+        ln = int.from_bytes(raw[i: i + 4], "little")
+        out.append(raw[i + 4: i + 4 + ln])
+        i += 4 + ln
+    return out if as_bytes else [t.decode("utf-8", "replace") for t in out]
+
+
+def prune_query_sub(bloom_expression, regex_expression, substring_expression, tokenizer=None):
+    """bsh_prune_query_sub: And(bloom, regex field guard, substring guard) -> expression dict or None."""
+    L = lib()
+    b, r, s = (json.dumps(e).encode() for e in (bloom_expression, regex_expression, substring_expression))
+    p, n = C.c_void_p(), C.c_uint64()
+    rc = L.bsh_prune_query_sub(b, len(b), r, len(r), s, len(s), c_spec(tokenizer), C.byref(p), C.byref(n))
+    if rc:
+        raise HostError(rc)
+    return json.loads(_take(L, p, n))
+
+
+def match_row_substring(substring_expression, row: bytes, tokenizer=None) -> bool:
+    """bsh_match_row_substring: the exact substring test of one row."""
+    L = lib()
+    s = json.dumps(substring_expression).encode()
+    rc = L.bsh_match_row_substring(s, len(s), row, len(row), c_spec(tokenizer))
+    if rc < 0:
+        raise HostError(rc)
+    return bool(rc)
+
+
 def crc32c(data: bytes) -> int:
     return int(lib().bsh_crc32c(data, len(data)))
 
@@ -308,19 +349,23 @@ class Engine:
     def stop(self):
         self._check(self.L.bse_stop(self.h))
 
-    def query(self, bloom_expression=None, regex_expression=None):
-        q = json.dumps({"Bloom": {"Expression": bloom_expression} if bloom_expression is not None else None,
-                        "Regex": {"Expression": regex_expression} if regex_expression is not None else None}).encode()
+    def query(self, bloom_expression=None, regex_expression=None, substring_expression=None):
+        d = {"Bloom": {"Expression": bloom_expression} if bloom_expression is not None else None,
+             "Regex": {"Expression": regex_expression} if regex_expression is not None else None}
+        if substring_expression is not None:
+            d["Substring"] = substring_expression
+        q = json.dumps(d).encode()
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self.L.bse_query(self.h, q, len(q), C.byref(p), C.byref(n)))
         return json.loads(_take(self.L, p, n))
 
-    def query_many(self, bloom_expressions, regex_expressions=None):
+    def query_many(self, bloom_expressions, regex_expressions=None, substring_expressions=None):
         """bse_query_many: one pass for a batch of queries -> list of query()'s results, element i for bloom_expressions[i]
-        (and regex_expressions[i], where given)."""
+        (and regex_expressions[i] / substring_expressions[i], where given)."""
         rx = list(regex_expressions) if regex_expressions is not None else [None] * len(bloom_expressions)
-        q = json.dumps([{"Bloom": {"Expression": b} if b is not None else None,
-                         "Regex": {"Expression": r} if r is not None else None} for b, r in zip(bloom_expressions, rx)]).encode()
+        sx = list(substring_expressions) if substring_expressions is not None else [None] * len(bloom_expressions)
+        q = json.dumps([dict({"Bloom": {"Expression": b} if b is not None else None, "Regex": {"Expression": r} if r is not None else None},
+                             **({"Substring": s} if s is not None else {})) for b, r, s in zip(bloom_expressions, rx, sx)]).encode()
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self.L.bse_query_many(self.h, q, len(q), C.byref(p), C.byref(n)))
         return json.loads(_take(self.L, p, n))

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import KIND_FIELD, KIND_FIELD_REGEX, KIND_FIELD_TOKEN, KIND_TOKEN, OP_AND, OP_FALSE, OP_OR, OP_TERM, OP_TRUE, op
+from ._lib import KIND_FIELD, KIND_FIELD_REGEX, KIND_FIELD_SUBSTRING, KIND_FIELD_TOKEN, KIND_SUBSTRING, KIND_TOKEN, OP_AND, OP_FALSE, OP_OR, OP_TERM, OP_TRUE, op
 
 BLOOM_FIELD, BLOOM_TOKEN, BLOOM_FIELD_TOKEN = "FIELD", "TOKEN", "FIELD_TOKEN"
 EXPR_CONDITION, EXPR_AND, EXPR_OR = "CONDITION", "AND", "OR"
@@ -100,9 +100,64 @@ def regex_field_guard_bloom_query(regex_expression):
     return None
 
 
-def prune_bloom_query(bloom_expression, regex_expression):
-    """pruneBloomQuery (query_exec.go:220)."""
-    return and_bloom_queries(bloom_expression, regex_field_guard_bloom_query(regex_expression))
+# ---- substring query tree and its bloom guard (bloomgpu.h "Substring conditions"; host/substring.hpp is the implementation) ----
+def Substring(needle: str) -> dict:
+    """Some leaf's text contains the needle (folded as the store's tokenizer folds)."""
+    return {"ExpressionType": "CONDITION", "Condition": {"Needle": needle}}
+
+
+def FieldSubstring(field: str, needle: str) -> dict:
+    """... a leaf whose path equals `field`."""
+    return {"ExpressionType": "CONDITION", "Condition": {"Field": field, "Needle": needle}}
+
+
+def SubstringAnd(*expressions) -> dict:
+    return {"ExpressionType": "AND", "Children": _flatten_regex(expressions, "AND")}
+
+
+def SubstringOr(*expressions) -> dict:
+    return {"ExpressionType": "OR", "Children": _flatten_regex(expressions, "OR")}
+
+
+NIL_CONDITION = {"ExpressionType": EXPR_CONDITION, "Condition": None}       # always true (query_exec.go:101-104)
+
+
+def substring_terms(needle, tokenizer=None) -> list:
+    """The tokens a row that contains `needle` must hold under `tokenizer` (None = the default), through the library
+    (bsh_substring_terms): deduplicated, in first-occurrence order."""
+    from . import host
+    return host.substring_terms(needle, tokenizer)
+
+
+def substring_guard_bloom_query(substring_expression, tokenizer=None):
+    """The tree as a bloom expression over its pruning terms: a condition is And(Token(t) ..) / And(FieldToken(field, t) ..); without
+    terms Field(field), or for an any-field condition nil (always true), which an And drops and an Or keeps as NIL_CONDITION.
+    None = nil."""
+    e = substring_expression
+    if e is None:
+        return None
+    t = e.get("ExpressionType")
+    if t == "CONDITION":
+        c = e.get("Condition")
+        if c is None:
+            return None
+        field, terms = c.get("Field"), substring_terms(c.get("Needle", ""), tokenizer)
+        if not terms:
+            return None if field is None else Field(field)
+        return And(*[Token(w) if field is None else FieldToken(field, w) for w in terms])
+    if t in ("AND", "OR"):
+        kids = [substring_guard_bloom_query(c, tokenizer) for c in e.get("Children") or []]
+        if t == "AND":
+            kept = [k for k in kids if k is not None]
+            return None if kids and not kept else {"ExpressionType": EXPR_AND, "Children": kept}
+        return {"ExpressionType": EXPR_OR, "Children": [NIL_CONDITION if k is None else k for k in kids]}
+    return None
+
+
+def prune_bloom_query(bloom_expression, regex_expression, substring_expression=None, tokenizer=None):
+    """pruneBloomQuery (query_exec.go:220), with the substring tree's guard as a third side."""
+    two = and_bloom_queries(bloom_expression, regex_field_guard_bloom_query(regex_expression))
+    return and_bloom_queries(two, substring_guard_bloom_query(substring_expression, tokenizer))
 
 
 def make_field_token_key(field: str, token: str) -> str:
@@ -332,6 +387,57 @@ class CompiledRowQuery(CompiledMatcher):
             self.prog_ops.append(op(OP_AND if et == EXPR_AND else OP_OR, len(kids)))
         else:
             self.prog_ops.append(op(OP_FALSE))
+
+
+class CompiledSubstringQuery(CompiledMatcher):
+    """And(bloom root, substring root) for bsg_match_rows_substr: the bloom side lowered as CompiledMatcher does, the substring
+    side by the regex tree's rules (a nil expression or condition is TRUE, an empty Or FALSE, an empty And TRUE).  A Substring
+    condition keeps an empty field, a FieldSubstring condition its field, both the RAW needle in `tokens` (entry 2i + 1)."""
+
+    def __init__(self, bloom_expression, substring_expression):
+        super().__init__(None)
+        if bloom_expression is None:
+            self.prog_ops.append(op(OP_TRUE))
+        else:
+            self._emit(bloom_expression)
+        self._emit_substring(substring_expression)
+        self.prog_ops.append(op(OP_AND, 2))
+
+    def _emit_substring(self, e) -> None:
+        if e is None:
+            self.prog_ops.append(op(OP_TRUE))
+            return
+        et = e.get("ExpressionType")
+        if et == EXPR_CONDITION:
+            cond = e.get("Condition")
+            if cond is None:
+                self.prog_ops.append(op(OP_TRUE))
+                return
+            field = cond.get("Field")
+            self.prog_ops.append(op(OP_TERM, len(self.kinds)))
+            self.kinds.append(KIND_SUBSTRING if field is None else KIND_FIELD_SUBSTRING)
+            self.fields.append(b"" if field is None else field.encode("utf-8", "surrogatepass"))
+            needle = cond.get("Needle", "")
+            self.tokens.append(needle if isinstance(needle, bytes) else needle.encode("utf-8", "surrogatepass"))
+        elif et in (EXPR_AND, EXPR_OR):
+            kids = e.get("Children") or []
+            if not kids:
+                self.prog_ops.append(op(OP_TRUE if et == EXPR_AND else OP_FALSE))
+                return
+            for c in kids:
+                self._emit_substring(c)
+            self.prog_ops.append(op(OP_AND if et == EXPR_AND else OP_OR, len(kids)))
+        else:
+            self.prog_ops.append(op(OP_FALSE))
+
+
+class CompiledSubstringQueryBatch(CompiledMatcherBatch):
+    """A batch of (bloom expression, substring expression) pairs for one bsg_match_rows_many_substr call: query q's program is
+    CompiledSubstringQuery's with its condition indices remapped into ONE table of distinct conditions."""
+
+    @staticmethod
+    def _compile(pair):
+        return CompiledSubstringQuery(*pair)
 
 
 class CompiledRowQueryBatch(CompiledMatcherBatch):

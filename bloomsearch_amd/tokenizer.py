@@ -7,7 +7,7 @@ mirror the Go binding's bloomgpu.Tokenizer and the engine JSON's "Tokenizer" obj
 
 `ngram` is 0 (the words themselves) or 2, 3, 4: a word of more than that many runes is replaced by its windows of that many
 consecutive runes, a shorter word stays one token; windows never cross a separator (bloomgpu.h BSG_TOK_NGRAM).  Query tokens
-are compared literally: a substring query ANDs the full windows of its needle.
+are compared literally; query.Substring / FieldSubstring derive a needle's windows (query.substring_terms).
 """
 from __future__ import annotations
 

@@ -52,6 +52,8 @@ extern "C" {
 #define BSG_KIND_TOKEN        1u
 #define BSG_KIND_FIELD_TOKEN  2u
 #define BSG_KIND_FIELD_REGEX  3u   /* row matcher only (bsg_match_rows_regex): entry 2i = field, 2i + 1 = pattern */
+#define BSG_KIND_SUBSTRING        4u   /* bsg_match_rows_substr / _many_substr only: entry 2i empty, 2i + 1 = the needle */
+#define BSG_KIND_FIELD_SUBSTRING  5u   /* ... entry 2i = the field, 2i + 1 = the needle */
 
 /* ---- query program opcodes: op = (opcode << 28) | arg, postfix order ----
  * TERM i : push TestString(term i) against the block's filter of term i's kind;
@@ -466,9 +468,23 @@ BSG_API int32_t bsg_host_unregister(bsg_ctx *ctx, void *ptr);
  * the width (bsg_ingest_rows_tok, bsg_ingest_open and its appends, bsg_match_rows_tok, _many, _many_regex, _wide, _wide_rows,
  * _lookup, _lookup_rows, _lookup_regex, _lookup_regex_rows).
  * Condition tokens are still compared LITERALLY with the row's tokens: the matcher does not cut a condition's token into windows.
- * A substring query is built by the caller: AND the full n-rune windows of the needle (lowered as the spec lowers).  A needle
- * word shorter than n must never become a Token term: in a row it is part of a longer word, whose set holds that word's
- * windows and not the needle. */
+ *
+ * Substring conditions.  With fold(x) = strings.ToLower(x) under BSG_TOK_LOWER (the per-rune table the tokenizers use), else x:
+ *   Substring(needle) holds for a row that has a leaf whose candidate text T (leafTokenInput: a string's decoded text, a number's
+ *     raw literal, true / false; never null, never a key) satisfies bytes.Contains(fold(T), fold(needle));
+ *   FieldSubstring(field, needle) is the same over the leaves whose path EQUALS the field (FieldToken's leaf rule, not
+ *     FieldRegex's prefix rule: the bloom side can only prune with field::token keys, which exist for the leaf's own path).
+ * The exact test ignores separators and the n-gram width.  A needle is non-empty valid UTF-8 of at most 64 bytes after folding:
+ * BSG_E_INVALID (empty, invalid UTF-8) or BSG_E_UNSUPPORTED (too long) before anything is launched.
+ * The tokens such a row must hold, which the probe side prunes with (bloomsearch_host.h bsh_substring_terms / bsh_prune_query_sub):
+ * fold the needle, split it at the spec's separators (tested on the folded runes); a word is WHOLE when the needle has a
+ * separator on both of its sides, else PARTIAL (the text may continue it).  A whole word gives itself (n = 0) or grams(word, n);
+ * a partial word gives nothing for n = 0 or fewer than n runes, else all its n-rune windows.  Terms are deduplicated in
+ * first-occurrence order; each condition is And(Token(t) ..) or And(FieldToken(field, t) ..) over its terms, without terms
+ * Field(field) or, for Substring, the always-true nil condition.  A partial word shorter than n never becomes a term: in a row it
+ * is part of a longer word, whose set holds that word's windows and not the needle.
+ * The AND of the terms is a candidate test only (the windows may sit in different words); bsg_match_rows_substr and
+ * bsg_match_rows_many_substr decide exactly. */
 #define BSG_TOK_UNICODE_SPACE 1u   /* runes >= 0x80 with unicode.IsSpace end a word too */
 #define BSG_TOK_LOWER         2u   /* the text is lower-cased first (unicode.ToLower per rune, as strings.ToLower) */
 #define BSG_TOK_NGRAM_SHIFT   8u   /* flags bits 8-10: the n-gram width, 0 (none), 2, 3 or 4 */
@@ -657,6 +673,21 @@ BSG_API int32_t bsg_match_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint
                                    const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
                                    uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                    uint32_t *out_n_fallback);
+/* bsg_match_rows_tok with substring conditions in the table (kinds 0, 1, 2, BSG_KIND_SUBSTRING, BSG_KIND_FIELD_SUBSTRING; the
+ * semantics under "Substring conditions" above).  The caller passes the RAW needle as entry 2i + 1; the call folds it under its own
+ * tokenizer.  The walker's text consumer runs shift-and over all needles at once: one LDS read per text byte whatever their number.
+ * Same arguments, sharding, chunked upload, fallback rows and bsg_last_match_ms as bsg_match_rows_tok; a row with a rune the
+ * lower table cannot decide is a fallback row (bloomsearch_host.h bsh_match_row_substring decides those), as is a row where a
+ * leaf's path has the hashes of a FieldSubstring condition's field but not its fingerprint.
+ * Limits: a needle of at most 64 bytes after folding; the needles are packed first-fit, in condition order, into 2 words of 64
+ * bytes and a needle never straddles a word, so at most 128 needle bytes per call (BSG_E_UNSUPPORTED beyond).
+ * A BSG_KIND_FIELD_REGEX condition is BSG_E_UNSUPPORTED: regex and substring conditions do not share a call yet.  Every other
+ * entry point answers kinds 4 and 5 with BSG_E_INVALID (unknown kind). */
+BSG_API int32_t bsg_match_rows_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                      const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                      const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
+                                      uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                      uint32_t *out_n_fallback);
 /* A batch of queries matched in ONE upload and ONE walk of the rows (k_match_rows_many): n_queries <= 64 expressions over ONE
  * table of distinct Field / Token / FieldToken conditions (packed as for bsg_match_rows), prog_ops / prog_off[n_queries + 1]
  * the public postfix programs over condition indices laid out as for bsg_batch_create (an empty program = nil expression =
@@ -681,6 +712,16 @@ BSG_API int32_t bsg_match_rows_many(bsg_ctx *ctx, const uint8_t *rows, const uin
                                     const bsg_tokenizer *tok,
                                     uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                     uint32_t *out_n_fallback);
+/* bsg_match_rows_many with substring conditions in the table, as bsg_match_rows_substr documents them: the same nineteen arguments,
+ * set / mask semantics, plane layout and limits as bsg_match_rows_many, the needle limits of bsg_match_rows_substr over the table's
+ * DISTINCT conditions; plane q = what bsg_match_rows_substr returns for program q alone, ANDed with the set mask. */
+BSG_API int32_t bsg_match_rows_many_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                           const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                           const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                           const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets,
+                                           const bsg_tokenizer *tok,
+                                           uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                           uint32_t *out_n_fallback);
 /* bsg_match_rows_many with FieldRegex conditions in the table (k_match_rows_many_regex): the same nineteen arguments, set / mask
  * semantics, plane layout, sharding over the context's devices, chunked upload and bsg_last_match_ms.  What differs:
  * - cond_kinds[i] may be BSG_KIND_FIELD_REGEX (entry 2i = the field, 2i + 1 = the pattern) with the meaning bsg_match_rows_regex

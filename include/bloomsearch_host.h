@@ -80,6 +80,24 @@ BSG_API int32_t bsh_prune_query(const char *bloom_json, uint64_t bloom_len, cons
 /* The regex half of the final row test (row_matcher.go:548-573; std::regex ECMAScript stands in for RE2): 1 / 0 / < 0. */
 BSG_API int32_t bsh_match_row_regex(const char *regex_json, uint64_t regex_len, const uint8_t *row, uint64_t row_len);
 
+/* ---- substring conditions (bloomgpu.h "substring conditions"; bloomsearch_amd/csrc/host/substring.hpp) ----
+ * substring_json: {"ExpressionType": "CONDITION"|"AND"|"OR", "Condition": {"Field": string or absent, "Needle": string},
+ * "Children": [...]}; a condition without "Field" looks at every leaf, one with it at the leaves whose path equals the field.
+ * A needle is non-empty valid UTF-8 of at most 64 bytes after folding: BSH_E_INVALID (empty, invalid UTF-8, an invalid spec or
+ * JSON) or BSG_E_UNSUPPORTED (too long) otherwise.  tok: the tokenizer of the store (NULL = the default). */
+/* the pruning terms of one needle, packed as bsh_tokenize_with packs tokens, deduplicated in first-occurrence order */
+BSG_API int32_t bsh_substring_terms(const uint8_t *needle, uint64_t len, const bsg_tokenizer *tok, uint8_t **out, uint64_t *out_len);
+/* bsh_prune_query with the third tree: And(bloom, regex field guard, substring guard) as JSON, "null" when every side is nil.  A
+ * condition's guard is And(Token(t) ..) / And(FieldToken(field, t) ..) over its terms; without terms Field(field), or for an
+ * any-field condition the nil condition ({"ExpressionType":"CONDITION","Condition":null}: always true), which an And drops and an
+ * Or keeps.  A NULL / empty / "null" substring tree gives exactly bsh_prune_query's answer. */
+BSG_API int32_t bsh_prune_query_sub(const char *bloom_json, uint64_t bloom_len, const char *regex_json, uint64_t regex_len,
+                                    const char *substring_json, uint64_t substring_len, const bsg_tokenizer *tok, char **out, uint64_t *out_len);
+/* The substring half of the final row test: 1 when the tree holds for the row, 0 when not, < 0 as above (a row that is not
+ * valid JSON: 0).  The matcher of the rows bsg_match_rows_substr hands back. */
+BSG_API int32_t bsh_match_row_substring(const char *substring_json, uint64_t substring_len, const uint8_t *row, uint64_t row_len,
+                                        const bsg_tokenizer *tok);
+
 /* Go regexp MatchString of `pattern` on `text` for the subset the device row matcher compiles (bsg_match_rows_regex; the
  * subset is listed in bloomsearch_amd/csrc/host/regex_dfa.hpp), run on the same DFA tables.  The text is read as Go reads a
  * string: an invalid byte is U+FFFD.  1 match, 0 no match, BSG_E_UNSUPPORTED for a pattern outside the subset (syntax

@@ -13,6 +13,7 @@
 #include "direct.hip.h"
 #include "match.hip.h"
 #include "match_lookup.hip.h"
+#include "host/arena_cache.hpp" // the policy of the resident file-arena cache (cache_api.inc adapts it to the C ABI)
 #include "host/build_plan.hpp"  // shard layout and stats, the parts of a build call, the route a filter is built by
 #include "host/combiner_sync.hpp"
 #include "host/probe_plan.hpp" // survivor offsets, launch groups, rows layout and the host merge of a probe call

@@ -2,8 +2,11 @@
 //
 // The reference re-reads and re-parses a file's block-filter sections on EVERY query (blockFilterCursor, file_format.go:511-662,
 // consulted per block by evaluateBlockFilters, query_exec.go:546-615).  On the device the decoded filters of a file stay resident
-// between queries; this file is the policy that decides which, for how long, and who frees them — inside the library, so that
-// every host (the Go overlay's gpu_engine.go, host/engine.hpp, a plain C caller) shares one tested implementation:
+// between queries under one policy that decides which, for how long, and who frees them — inside the library, so that every host
+// (the Go overlay's gpu_engine.go, host/engine.hpp, a plain C caller) shares one tested implementation.  The policy itself — the
+// tables, leases, eviction, the counters and the mutex — is host/arena_cache.hpp, which knows arena ids and byte counts only and is
+// run on the CPU under sanitizers (tests/test_arena_cache_policy.py).  This file is its adapter to the C ABI: the argument checks,
+// the arena's device bytes, the policy's statuses as error codes and messages, and the freeing of what the policy lets go:
 //
 //     bsg_file_arena_acquire   file key + the query's candidate blocks (ascending block keys = RowDataOffset):
 //                              covered -> a LEASE on the resident arena + each candidate's row in it; not covered -> lease 0
@@ -23,32 +26,9 @@
 //                              those queries finish — the release that ends the last lease runs the eviction)
 //
 // An arena the cache holds is owned by the cache: the caller must not bsg_arena_free it.  Leases are plain ids (double release
-// and unknown ids are BSG_E_NOTFOUND).  Everything is guarded by one mutex; device memory is freed outside it.
+// and unknown ids are BSG_E_NOTFOUND).  Everything is guarded by the policy's one mutex; device memory is freed outside it.
 
-namespace {
-
-struct FileArena {
-    std::string key;
-    uint64_t arena_id = 0;
-    std::vector<uint64_t> block_keys;             // ascending; row i of the arena is block_keys[i]
-    std::vector<uint64_t> sec_begin, sec_end;     // the blocks' section extents in the file (what a widening load re-reads)
-    uint64_t bytes = 0;                           // device bytes of the arena (words + descriptors, all shards)
-    uint32_t users = 0;
-    uint64_t last_use = 0;
-    bool dead = false;                            // not (or no longer) in the table: freed by its last release
-};
-
-}  // namespace
-
-struct bsg_arena_cache {
-    std::mutex mu;
-    std::unordered_map<std::string, std::shared_ptr<FileArena>> resident;
-    std::unordered_map<uint64_t, std::shared_ptr<FileArena>> leases;
-    std::unordered_set<uint64_t> owned;           // arena ids the cache will free itself (resident, or alive through a lease)
-    uint64_t budget = 32ull << 30;                // (gpu_engine.go's defaultArenaBudget; bsg_set_arena_budget)
-    uint64_t bytes = 0, tick = 0, next_lease = 1;
-    bsg_arena_cache_stats st{};
-};
+struct bsg_arena_cache : bsh_cache::ArenaCache {};
 
 namespace {
 
@@ -57,32 +37,6 @@ uint64_t arena_device_bytes(const Arena &a)
     uint64_t b = 0;
     for (auto &s : a.shards) b += s.n_words * 8 + (uint64_t)s.n_blocks * 3 * sizeof(DevDesc);
     return b;
-}
-
-// (cache mutex held) out of the table; returns the arena id to free now, or 0 when its last user will
-uint64_t cache_drop_locked(bsg_arena_cache &c, const std::shared_ptr<FileArena> &fa)
-{
-    auto it = c.resident.find(fa->key);
-    if (it != c.resident.end() && it->second == fa) c.resident.erase(it);
-    c.bytes -= fa->bytes;
-    fa->dead = true;
-    return fa->users == 0 ? fa->arena_id : 0;
-}
-
-// (cache mutex held) least recently used entries nobody uses go until the cache fits its budget; `keep` never goes.
-// One pass over the table + a sort of the idle entries (a shrinking budget may let thousands go at once).
-void cache_evict_locked(bsg_arena_cache &c, const FileArena *keep, std::vector<uint64_t> &to_free)
-{
-    if (c.bytes <= c.budget) return;
-    std::vector<std::shared_ptr<FileArena>> idle;
-    for (auto &kv : c.resident)
-        if (kv.second.get() != keep && kv.second->users == 0) idle.push_back(kv.second);
-    std::sort(idle.begin(), idle.end(), [](const std::shared_ptr<FileArena> &a, const std::shared_ptr<FileArena> &b) { return a->last_use < b->last_use; });
-    for (auto &victim : idle) {
-        if (c.bytes <= c.budget) return;
-        if (const uint64_t id = cache_drop_locked(c, victim)) to_free.push_back(id);
-        ++c.st.evictions;
-    }
 }
 
 bool strictly_ascending(const uint64_t *v, uint32_t n)
@@ -97,18 +51,11 @@ int32_t arena_free_by_id(bsg_ctx *ctx, uint64_t arena_id);   // bloomgpu.hip
 void cache_free_ids(bsg_ctx *ctx, const std::vector<uint64_t> &ids)
 {
     if (ids.empty()) return;
-    {
-        std::lock_guard<std::mutex> lk(ctx->cache->mu);
-        for (uint64_t id : ids) ctx->cache->owned.erase(id);
-    }
+    ctx->cache->disown(ids);
     for (uint64_t id : ids) (void)arena_free_by_id(ctx, id);
 }
 
-bool cache_owns(bsg_ctx *ctx, uint64_t arena_id)
-{
-    std::lock_guard<std::mutex> lk(ctx->cache->mu);
-    return ctx->cache->owned.count(arena_id) != 0;
-}
+bool cache_owns(bsg_ctx *ctx, uint64_t arena_id) { return ctx->cache->owns(arena_id); }
 
 std::shared_ptr<bsg_arena_cache> arena_cache_create() { return std::make_shared<bsg_arena_cache>(); }
 
@@ -125,11 +72,7 @@ int32_t bsg_set_arena_budget(bsg_ctx *ctx, uint64_t bytes)
 {
     BSG_ENTER(ctx);
     std::vector<uint64_t> to_free;
-    {
-        std::lock_guard<std::mutex> lk(ctx->cache->mu);
-        ctx->cache->budget = bytes;
-        cache_evict_locked(*ctx->cache, nullptr, to_free);
-    }
+    ctx->cache->set_budget(bytes, to_free);
     cache_free_ids(ctx, to_free);
     return BSG_OK;
 }
@@ -141,33 +84,10 @@ int32_t bsg_file_arena_acquire(bsg_ctx *ctx, const uint8_t *key, uint32_t key_le
     if ((!key && key_len) || (!block_keys && n_blocks) || !out_lease || !out_arena_id || (!out_rows && n_blocks))
         return fail(BSG_E_INVALID, "bsg_file_arena_acquire: null argument");
     if (!strictly_ascending(block_keys, n_blocks)) return fail(BSG_E_INVALID, "bsg_file_arena_acquire: block keys are not strictly ascending");
-    *out_lease = 0;
-    *out_arena_id = 0;
-    if (out_arena_blocks) *out_arena_blocks = 0;
-    bsg_arena_cache &c = *ctx->cache;
-    std::lock_guard<std::mutex> lk(c.mu);
-    auto it = c.resident.find(std::string((const char *)key, key_len));
-    if (it != c.resident.end()) {
-        const auto &fa = it->second;
-        bool covered = true;
-        for (uint32_t i = 0; i < n_blocks && covered; ++i) {
-            auto p = std::lower_bound(fa->block_keys.begin(), fa->block_keys.end(), block_keys[i]);
-            if (p == fa->block_keys.end() || *p != block_keys[i]) covered = false;
-            else out_rows[i] = (uint32_t)(p - fa->block_keys.begin());
-        }
-        if (covered) {
-            ++fa->users;
-            fa->last_use = ++c.tick;
-            const uint64_t lease = c.next_lease++;
-            c.leases.emplace(lease, fa);
-            *out_lease = lease;
-            *out_arena_id = fa->arena_id;
-            if (out_arena_blocks) *out_arena_blocks = (uint32_t)fa->block_keys.size();
-            ++c.st.hits;
-            return BSG_OK;
-        }
-    }
-    ++c.st.misses;
+    const bsh_cache::ArenaCache::Hit h = ctx->cache->acquire(std::string((const char *)key, key_len), block_keys, n_blocks, out_rows);
+    *out_lease = h.lease;
+    *out_arena_id = h.arena_id;
+    if (out_arena_blocks) *out_arena_blocks = h.arena_blocks;
     return BSG_OK;
 }
 
@@ -176,18 +96,8 @@ int32_t bsg_file_arena_have(bsg_ctx *ctx, const uint8_t *key, uint32_t key_len, 
 {
     BSG_ENTER(ctx);
     if ((!key && key_len) || !out_n) return fail(BSG_E_INVALID, "bsg_file_arena_have: null argument");
-    bsg_arena_cache &c = *ctx->cache;
-    std::lock_guard<std::mutex> lk(c.mu);
-    auto it = c.resident.find(std::string((const char *)key, key_len));
-    if (it == c.resident.end()) { *out_n = 0; return BSG_OK; }
-    const auto &fa = it->second;
-    *out_n = (uint32_t)fa->block_keys.size();
-    if (cap == 0) return BSG_OK;                                        // size query
-    if (cap < *out_n || !out_block_keys || !out_sec_begin || !out_sec_end)
+    if (ctx->cache->have(std::string((const char *)key, key_len), out_block_keys, out_sec_begin, out_sec_end, cap, out_n) == bsh_cache::kNoRoom)
         return fail(BSG_E_INVALID, "bsg_file_arena_have: room for %u blocks, the resident arena holds %u", cap, *out_n);
-    std::copy(fa->block_keys.begin(), fa->block_keys.end(), out_block_keys);
-    std::copy(fa->sec_begin.begin(), fa->sec_begin.end(), out_sec_begin);
-    std::copy(fa->sec_end.begin(), fa->sec_end.end(), out_sec_end);
     return BSG_OK;
 }
 
@@ -202,43 +112,14 @@ int32_t bsg_file_arena_publish(bsg_ctx *ctx, const uint8_t *key, uint32_t key_le
     std::shared_ptr<Arena> a;
     if (int32_t rc = get_arena(ctx, arena_id, a)) return rc;
     if (a->n_blocks != n_blocks) return fail(BSG_E_INVALID, "bsg_file_arena_publish: the arena holds %u blocks, %u keys given", a->n_blocks, n_blocks);
-    auto fa = std::make_shared<FileArena>();
-    fa->key.assign((const char *)key, key_len);
-    fa->arena_id = arena_id;
-    fa->block_keys.assign(block_keys, block_keys + n_blocks);
-    fa->sec_begin.assign(sec_begin, sec_begin + n_blocks);
-    fa->sec_end.assign(sec_end, sec_end + n_blocks);
-    fa->bytes = arena_device_bytes(*a);
-    fa->users = 1;
     bool clean = true;
     for (uint32_t i = 0; status && i < n_blocks; ++i) clean = clean && status[i] == 0;
-    bsg_arena_cache &c = *ctx->cache;
     std::vector<uint64_t> to_free;
-    int32_t resident = 0;
-    {
-        std::lock_guard<std::mutex> lk(c.mu);
-        if (!c.owned.insert(arena_id).second) return fail(BSG_E_INVALID, "bsg_file_arena_publish: arena %llu is already the cache's", (unsigned long long)arena_id);
-        const uint64_t lease = c.next_lease++;
-        c.leases.emplace(lease, fa);
-        *out_lease = lease;
-        auto it = c.resident.find(fa->key);
-        if (!clean) { fa->dead = true; ++c.st.rejected_dirty; }
-        else if (fa->bytes > c.budget) { fa->dead = true; ++c.st.rejected_over_budget; }
-        else if (it != c.resident.end() && it->second->block_keys.size() > fa->block_keys.size()) { fa->dead = true; ++c.st.rejected_narrower; }
-        else {
-            if (it != c.resident.end()) {
-                ++c.st.widenings;
-                if (const uint64_t id = cache_drop_locked(c, it->second)) to_free.push_back(id);
-            }
-            fa->last_use = ++c.tick;
-            c.resident[fa->key] = fa;
-            c.bytes += fa->bytes;
-            cache_evict_locked(c, fa.get(), to_free);
-            resident = 1;
-            ++c.st.published;
-        }
-    }
-    if (out_resident) *out_resident = resident;
+    const bsh_cache::ArenaCache::Published p = ctx->cache->publish(std::string((const char *)key, key_len), arena_id, arena_device_bytes(*a), block_keys,
+                                                                   sec_begin, sec_end, n_blocks, clean, to_free);
+    if (p.status == bsh_cache::kAlreadyOwned) return fail(BSG_E_INVALID, "bsg_file_arena_publish: arena %llu is already the cache's", (unsigned long long)arena_id);
+    *out_lease = p.lease;
+    if (out_resident) *out_resident = p.resident ? 1 : 0;
     cache_free_ids(ctx, to_free);
     return BSG_OK;
 }
@@ -246,19 +127,8 @@ int32_t bsg_file_arena_publish(bsg_ctx *ctx, const uint8_t *key, uint32_t key_le
 int32_t bsg_file_arena_release(bsg_ctx *ctx, uint64_t lease)
 {
     BSG_ENTER(ctx);
-    bsg_arena_cache &c = *ctx->cache;
     std::vector<uint64_t> to_free;
-    {
-        std::lock_guard<std::mutex> lk(c.mu);
-        auto it = c.leases.find(lease);
-        if (it == c.leases.end()) return fail(BSG_E_NOTFOUND, "unknown file-arena lease %llu", (unsigned long long)lease);
-        auto fa = it->second;
-        c.leases.erase(it);
-        if (--fa->users == 0) {
-            if (fa->dead) to_free.push_back(fa->arena_id);
-            else if (c.bytes > c.budget) cache_evict_locked(c, nullptr, to_free);   // the budget was waiting for leases to end
-        }
-    }
+    if (ctx->cache->release(lease, to_free) == bsh_cache::kUnknownLease) return fail(BSG_E_NOTFOUND, "unknown file-arena lease %llu", (unsigned long long)lease);
     cache_free_ids(ctx, to_free);
     return BSG_OK;
 }
@@ -267,17 +137,9 @@ int32_t bsg_file_arena_forget(bsg_ctx *ctx, const uint8_t *key, uint32_t key_len
 {
     BSG_ENTER(ctx);
     if (!key && key_len) return fail(BSG_E_INVALID, "bsg_file_arena_forget: null key");
-    bsg_arena_cache &c = *ctx->cache;
-    uint64_t free_id = 0;
-    {
-        std::lock_guard<std::mutex> lk(c.mu);
-        auto it = c.resident.find(std::string((const char *)key, key_len));
-        if (it == c.resident.end()) return BSG_OK;
-        auto fa = it->second;
-        free_id = cache_drop_locked(c, fa);
-        ++c.st.forgotten;
-    }
-    if (free_id) cache_free_ids(ctx, {free_id});
+    std::vector<uint64_t> to_free;
+    ctx->cache->forget(std::string((const char *)key, key_len), to_free);
+    cache_free_ids(ctx, to_free);
     return BSG_OK;
 }
 
@@ -285,24 +147,7 @@ int32_t bsg_arena_cache_stats_read(bsg_ctx *ctx, bsg_arena_cache_stats *out, int
 {
     BSG_ENTER(ctx);
     if (!out) return fail(BSG_E_INVALID, "out is null");
-    bsg_arena_cache &c = *ctx->cache;
-    std::lock_guard<std::mutex> lk(c.mu);
-    c.st.budget_bytes = c.budget;
-    c.st.resident_bytes = c.bytes;
-    c.st.resident_files = c.resident.size();
-    c.st.leases = c.leases.size();
-    uint64_t held = 0;            // bytes of arenas alive only through their leases (dead entries) — the device memory the table no longer counts
-    std::unordered_set<const FileArena *> seen;
-    for (auto &kv : c.leases)
-        if (kv.second->dead && seen.insert(kv.second.get()).second) held += kv.second->bytes;
-    c.st.leased_dead_bytes = held;
-    *out = c.st;
-    if (reset) {
-        const bsg_arena_cache_stats keep = c.st;
-        c.st = bsg_arena_cache_stats{};
-        c.st.budget_bytes = keep.budget_bytes; c.st.resident_bytes = keep.resident_bytes; c.st.resident_files = keep.resident_files;
-        c.st.leases = keep.leases; c.st.leased_dead_bytes = keep.leased_dead_bytes;
-    }
+    ctx->cache->stats(out, reset != 0);
     return BSG_OK;
 }
 

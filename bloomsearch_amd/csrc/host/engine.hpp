@@ -18,6 +18,7 @@
 #include <chrono>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <string_view>
 #include <tuple>
@@ -142,6 +143,12 @@ public:
     }
 
     const std::string &last_error() const { return err_; }
+    // how often the engine has called each device row-matcher entry point (bsg_match_rows_*), by name: which route its queries took
+    std::map<std::string, uint64_t> match_calls() const
+    {
+        std::lock_guard<std::mutex> lk(match_calls_mu_);
+        return match_calls_;
+    }
     // DeviceIngestStream at work (bse_describe "IngestStream"): batches and rows handed to a streaming ingest at ingest time, the
     // rows among them the host walker finished at once, and the flushes built from a stream (not from the kept row bytes)
     struct StreamStats { uint64_t batches = 0, rows = 0, host_rows = 0, flushes = 0; };
@@ -313,7 +320,10 @@ public:
     // sub: the substring tree of the query (substring.hpp).  Its guard over the pruning terms is a third side of the pruning
     // expression, And(bloom, regex field guard, substring guard); the row test is bloom AND regex AND substring.  Under DeviceMatch a
     // query without a regex tree is decided by ONE bsg_match_rows_substr call over the program And(bloom root, substring root) (the
-    // rows it hands back: the host matchers); with a regex tree, or without DeviceMatch, SubstringRowMatcher decides on the host.
+    // rows it hands back: the host matchers).  With a regex tree, under DeviceMatch + DeviceRegex and patterns in the device subset, ONE
+    // bsg_match_rows_regex_substr call decides And(bloom root, regex root, substring root); where the library answers
+    // BSG_E_UNSUPPORTED (tables over the cap beside the needle table, needles that do not pack) the regex call decides its two sides
+    // and SubstringRowMatcher the third, as for every other combination of the keys and without DeviceMatch.
     int32_t query(const BloomExpression *row_expr, QueryResult &out, const RegexExpression *regex = nullptr, const SubstringExpression *sub = nullptr)
     {
         out = QueryResult{};
@@ -345,13 +355,17 @@ public:
         for (const ScanBlock &sb : scanned)
             for (const std::string &row : files_[sb.f].blocks[sb.b].rows) scan.push_back(&row);
         std::vector<uint8_t> hit(scan.size(), 0);
-        bool on_device = false, regex_done = false;
-        if (regex_on_device && !scan.empty()) {
+        bool on_device = false, regex_done = false, sub_done = false;
+        if (regex_on_device && sub && !scan.empty()) {      // both trees: one walk decides bloom AND regex AND substring
+            bool both_done = false;
+            if (int32_t rc = match_rows_device_regex_substr(row_expr, *regex, *sub, scan, matcher, regex_dfa, sub_matcher, hit, both_done)) return rc;
+            regex_done = sub_done = both_done;
+        }
+        if (regex_on_device && !regex_done && !scan.empty()) {
             if (int32_t rc = match_rows_device_regex(row_expr, *regex, scan, matcher, regex_dfa, hit, regex_done)) return rc;
             if (!regex_done && !regex_matcher.valid()) return fail(kErrInvalidQuery, "regex pattern does not compile");
         }
         on_device = regex_done;
-        bool sub_done = false;
         if (sub && !regex && cfg_.device_match && !scan.empty()) {
             if (int32_t rc = match_rows_device_substr(row_expr, *sub, scan, matcher, sub_matcher, hit, sub_done)) return rc;
             on_device = sub_done;
@@ -485,6 +499,14 @@ public:
     }
 
 private:
+    void count_match_call(const char *entry_point)
+    {
+        std::lock_guard<std::mutex> lk(match_calls_mu_);
+        ++match_calls_[entry_point];
+    }
+    mutable std::mutex match_calls_mu_;
+    std::map<std::string, uint64_t> match_calls_;
+
     bsg_tokenizer c_tokenizer() const
     {
         bsg_tokenizer t{};
@@ -989,6 +1011,7 @@ private:
         std::vector<uint32_t> fb(scan.size());
         uint32_t n_fb = 0;
         const bsg_tokenizer tok = c_tokenizer();
+        count_match_call("bsg_match_rows_tok");
         const int32_t rc = bsg_match_rows_tok(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
                                               mp.kinds.data(), (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok,
                                               bits.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
@@ -1128,6 +1151,7 @@ private:
                     std::vector<uint32_t> hdr(sq.size() + 1), payload(2 * total + 1), ids;
                     std::vector<uint64_t> pair_off(sq.size() + 1);
                     uint64_t payload_len = 0;
+                    count_match_call(by_lookup_regex ? "bsg_match_rows_lookup_regex_rows" : by_lookup ? "bsg_match_rows_lookup_rows" : "bsg_match_rows_wide_rows");
                     const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex_rows : by_lookup ? bsg_match_rows_lookup_rows : bsg_match_rows_wide_rows)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
                                                                 kinds.data(), (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(),
                                                                 (uint32_t)members.size(), set_first.data(), sq_off.data(), sq.data(), (uint32_t)n_sets, &tok,
@@ -1149,6 +1173,7 @@ private:
                     }
                 } else {
                 std::vector<uint64_t> words(total + 1);
+                count_match_call(by_lookup_regex ? "bsg_match_rows_lookup_regex" : by_lookup ? "bsg_match_rows_lookup" : "bsg_match_rows_wide");
                 const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex : by_lookup ? bsg_match_rows_lookup : bsg_match_rows_wide)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
                                                        (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(),
                                                        sq_off.data(), sq.data(), (uint32_t)n_sets, &tok, words.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
@@ -1178,6 +1203,7 @@ private:
             std::vector<uint64_t> bits(members.size() * n_words);
             std::vector<uint32_t> fb(scan.size());
             uint32_t n_fb = 0;
+            count_match_call(n_rx ? "bsg_match_rows_many_regex" : "bsg_match_rows_many");
             const int32_t rc = (n_rx ? bsg_match_rows_many_regex : bsg_match_rows_many)(
                 ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(), (uint32_t)kinds.size(),
                 prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(), masks.data(), (uint32_t)n_sets, &tok, bits.data(),
@@ -1219,6 +1245,7 @@ private:
         std::vector<uint32_t> fb(scan.size());
         uint32_t n_fb = 0;
         const bsg_tokenizer tok = c_tokenizer();
+        count_match_call("bsg_match_rows_tok");
         const int32_t rc = bsg_match_rows_tok(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(),
                                               (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok, bits.data(), fb.data(),
                                               (uint32_t)fb.size(), &n_fb);
@@ -1253,6 +1280,7 @@ private:
         std::vector<uint32_t> fb(scan.size());
         uint32_t n_fb = 0;
         const bsg_tokenizer tok = c_tokenizer();
+        count_match_call("bsg_match_rows_substr");
         const int32_t rc = bsg_match_rows_substr(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(),
                                                  (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok, bits.data(), fb.data(),
                                                  (uint32_t)fb.size(), &n_fb);
@@ -1260,6 +1288,47 @@ private:
         if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
         for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
         for (uint32_t i = 0; i < n_fb; ++i) hit[fb[i]] = host_matcher.match(*scan[fb[i]]) && sub_matcher.match(*scan[fb[i]]);
+        done = true;
+        return kEngineOk;
+    }
+
+    // And(bloom root | TRUE, regex root, substring root) over the scan list in one bsg_match_rows_regex_substr call; the rows it hands
+    // back are decided by the three host matchers (the regex one DFA-backed, as the device read the patterns).  done stays false
+    // beyond 64 conditions or what the call holds.
+    int32_t match_rows_device_regex_substr(const BloomExpression *expr, const RegexExpression &regex, const SubstringExpression &sub,
+                                           const std::vector<const std::string *> &scan, RowMatcher &host_matcher, RegexRowMatcher &host_regex,
+                                           SubstringRowMatcher &sub_matcher, std::vector<uint8_t> &hit, bool &done)
+    {
+        MatcherProgram mp(expr);
+        if (mp.prog_ops.empty()) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
+        lower_regex(regex, mp);
+        emit_substring_program(sub, mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
+        mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 3));
+        if (mp.kinds.size() > 64) return kEngineOk;
+        std::vector<uint8_t> cbytes;
+        std::vector<uint32_t> coff{0};
+        for (size_t c = 0; c < mp.kinds.size(); ++c) {
+            cbytes.insert(cbytes.end(), mp.fields[c].begin(), mp.fields[c].end()); coff.push_back((uint32_t)cbytes.size());
+            cbytes.insert(cbytes.end(), mp.tokens[c].begin(), mp.tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
+        }
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> row_off{0};
+        for (const std::string *r : scan) { bytes.insert(bytes.end(), r->begin(), r->end()); row_off.push_back(bytes.size()); }
+        std::vector<uint64_t> bits((scan.size() + 63) / 64);
+        std::vector<uint32_t> fb(scan.size());
+        uint32_t n_fb = 0;
+        const bsg_tokenizer tok = c_tokenizer();
+        count_match_call("bsg_match_rows_regex_substr");
+        const int32_t rc = bsg_match_rows_regex_substr(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(),
+                                                       (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok, bits.data(),
+                                                       fb.data(), (uint32_t)fb.size(), &n_fb);
+        if (rc == BSG_E_UNSUPPORTED) return kEngineOk;
+        if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
+        for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
+        for (uint32_t i = 0; i < n_fb; ++i) {
+            const std::string &row = *scan[fb[i]];
+            hit[fb[i]] = host_matcher.match(row) && host_regex.match(row) && sub_matcher.match(row);
+        }
         done = true;
         return kEngineOk;
     }

@@ -590,6 +590,19 @@ int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, ch
     return give(out, out_json, out_len);
 }
 
+// {"<entry point>": calls, ...}: the device row-matcher entry points the engine has called since bse_open
+int32_t bse_match_calls(bse_engine *e, char **out_json, uint64_t *out_len)
+{
+    if (!e || !out_json) return BSH_E_INVALID;
+    std::string out = "{";
+    for (const auto &kv : e->eng->match_calls()) {
+        if (out.size() > 1) out.push_back(',');
+        out += "\"" + kv.first + "\":" + std::to_string(kv.second);
+    }
+    out.push_back('}');
+    return give(out, out_json, out_len);
+}
+
 int32_t bse_describe(bse_engine *e, char **out_json, uint64_t *out_len)
 {
     if (!e || !out_json) return BSH_E_INVALID;

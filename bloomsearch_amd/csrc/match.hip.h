@@ -63,6 +63,11 @@
 // condition whose end bit is in `hit` is satisfied.  The consumer folds what it is fed as the tokenizer would: ASCII A-Z + 32, a
 // rune through the walker's lower table (unknown to the table: a fallback row); without BSG_TOK_LOWER bytes go in as they are.
 // LDS: the 4 096-byte table behind the instance's own bytes (the batched instance's 43 780 rounded up to 16: M[b] is one 16-byte read).
+//
+// Both text consumers in one walk (k_match_rows_regex_substr* / k_match_rows_many_regex_substr* = REGEX and SUB): every candidate text
+// byte goes to the RxLaneT (raw) and to the SubLane (folded), a leaf request runs both parents' handling, and a row is a fallback row
+// by either parent's rule.  LDS: the needle table where the substring instances have it, the regex blob behind the table (at most
+// kRxSubLdsCap = 40 448 / kRxManySubLdsCap = 34 032 bytes: 80 KiB in all, two workgroups per CU as the regex walkers).
 #pragma once
 #include <type_traits>
 #include "ingest.hip.h"
@@ -257,6 +262,30 @@ struct SubLane {
     }
 };
 
+// FieldRegex and substring conditions in one walk (k_match_rows_regex_substr* / k_match_rows_many_regex_substr*): the text consumer is
+// both lanes at once.  The DFAs step over the raw bytes, the needles over the folded ones.  The two lanes stay two objects and this
+// one only refers to them: SubLane::wk points at the Walker, and a lane object that held that pointer BESIDE RxLaneT's hd[] / st[]
+// (indexed by loops that are unrolled late) stays in private memory past the first scalar replacement, the Walker with it; by the
+// next one hs_absorb's `if (t < 8) s.lo |= v; else s.hi |= v;` on the in-memory w.tok has become one access at a computed offset
+// and the Walker can no longer be split: 304 bytes of scratch per lane in the default and the separator instances.
+template <uint32_t SLOTS>
+struct RxSubFeed {
+    RxLaneT<SLOTS> &rx;
+    SubLane &sub;
+    __device__ __forceinline__ void feed(uint32_t b) { rx.feed(b); sub.feed(b); }
+    __device__ __forceinline__ void feed_run(uint64_t v, uint32_t n)
+    {
+        for (uint32_t i = 0; i < n; ++i) feed(c_at(v, i));
+    }
+    __device__ __forceinline__ void feed_rune(uint32_t r) { rx.feed_rune(r); sub.feed_rune(r); }
+};
+// LDS of the two instances: the needle table where the substring instances have it, the regex blob behind the table
+constexpr uint32_t kRxSubLdsCap = 80u * 1024u - kMatchSubLdsBytes;
+constexpr uint32_t kRxManySubLdsCap = 80u * 1024u - kMatchManySubLdsBytes;
+static_assert(kRxSubLdsCap == 40448u && kRxManySubLdsCap == 34032u && kRxSubLdsCap <= 0x10000u && kMatchSubLdsBytes % 4u == 0u && kMatchManySubLdsBytes % 4u == 0u &&
+                  2u * (kMatchSubLdsBytes + kRxSubLdsCap) <= 160u * 1024u && 2u * (kMatchManySubLdsBytes + kRxManySubLdsCap) <= 160u * 1024u,
+              "k_match_rows_regex_substr and k_match_rows_many_regex_substr keep two workgroups per CU, and the blob's 16-bit offsets reach all of it");
+
 // the set of row g: the first s whose rows end behind it (set_first_row[n_sets] = the number of rows > g)
 __device__ __forceinline__ uint32_t row_set_of(const uint32_t *set_first_row, uint32_t n_sets, uint32_t g)
 {
@@ -273,10 +302,10 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
                                                 const MatchWideArgs &wd = MatchWideArgs{}, const SubArgs &sb = SubArgs{})
 {
     static_assert(!(MANY && WIDE), "the storing walker evaluates no program");
-    static_assert(!(SUB && (REGEX || WIDE)), "substring conditions: the single and the batched call, without regex conditions");
+    static_assert(!(SUB && WIDE), "substring conditions: the single and the batched call");
     constexpr uint32_t kSubBase = MANY ? kMatchManySubBase : kMatchLdsBytes;   // the needle table sits behind the instance's own LDS
     constexpr uint32_t kProgBytes = WIDE ? 0u : MANY ? kMatchManyProgBytes : kMatchMaxOps * 4;
-    constexpr uint32_t kRxBase = WIDE ? kMatchWideLdsBytes : MANY ? kMatchManyLdsBytes : kMatchLdsBytes;   // the regex blob sits behind the instance's own LDS
+    constexpr uint32_t kRxBase = SUB ? kSubBase + kSubTableBytes : WIDE ? kMatchWideLdsBytes : MANY ? kMatchManyLdsBytes : kMatchLdsBytes;   // the regex blob sits behind the instance's own LDS (and the needle table)
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     lds_u64i *conds = (lds_u64i *)lds_raw;
     typedef __attribute__((address_space(3))) uint32_t lds_u32i;
@@ -319,7 +348,8 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
     uint32_t res = walk ? R_CONTINUE : R_DONE;
     uint64_t sat = 0, leaf_mask = 0;
     bool collided = false;       // equal hashes, different fingerprint: only the host's byte compare can decide this row
-    typename std::conditional<REGEX, RxLaneT<SLOTS>, typename std::conditional<SUB, SubLane, RxNone>::type>::type rx;
+    typename std::conditional<REGEX, RxLaneT<SLOTS>, RxNone>::type rx;   // the text consumers: the regex lane, the substring lane, or both
+    typename std::conditional<SUB, SubLane, RxNone>::type sl;
     bool rx_over = false;        // more regex conditions on one leaf than a lane holds: the host decides this row
     if constexpr (REGEX) {
         rx.tab = (const lds_u8 *)lds_raw + kRxBase;
@@ -328,16 +358,20 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
         for (uint32_t k = 0; k < SLOTS; ++k) rx.hd[k] = ~0u;
     }
     if constexpr (SUB) {
-        rx.m = (const lds_u64i *)(lds_raw + kSubBase);
-        rx.wk = &w;
-        rx.s0 = sb.start[0]; rx.s1 = sb.start[1];
-        rx.d0 = rx.d1 = rx.a0 = rx.a1 = rx.h0 = rx.h1 = 0;
-        rx.lower = tk.lower();
-        rx.fail = false;
+        sl.m = (const lds_u64i *)(lds_raw + kSubBase);
+        sl.wk = &w;
+        sl.s0 = sb.start[0]; sl.s1 = sb.start[1];
+        sl.d0 = sl.d1 = sl.a0 = sl.a1 = sl.h0 = sl.h1 = 0;
+        sl.lower = tk.lower();
+        sl.fail = false;
     }
     while (__ballot(res == R_CONTINUE || w.req != Q_NONE) != 0ull) {
         while (__ballot(res == R_CONTINUE && w.req == Q_NONE) != 0ull)
-            if (res == R_CONTINUE && w.req == Q_NONE) res = advance<true>(w, cc, rx, tk);
+            if (res == R_CONTINUE && w.req == Q_NONE) {
+                if constexpr (REGEX && SUB) { RxSubFeed<SLOTS> both{rx, sl}; res = advance<true>(w, cc, both, tk); }
+                else if constexpr (SUB) res = advance<true>(w, cc, sl, tk);
+                else res = advance<true>(w, cc, rx, tk);
+            }
         const uint32_t q = w.req;
         w.req = Q_NONE;
         HashStream s;
@@ -384,9 +418,9 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
         if constexpr (SUB) {
             if (q == Q_LEAF) {                                           // a new leaf: no carry from the one before, the any-field needles listen
                 sub_text = !(w.st == S_LIT && w.lit == 2u);              // null is never a candidate text
-                rx.d0 = rx.d1 = 0;
-                rx.a0 = sub_text ? sb.any[0] : 0ull;
-                rx.a1 = sub_text ? sb.any[1] : 0ull;
+                sl.d0 = sl.d1 = 0;
+                sl.a0 = sub_text ? sb.any[0] : 0ull;
+                sl.a1 = sub_text ? sb.any[1] : 0ull;
             }
         }
         for (uint32_t c = 0; c < a.n_conds; ++c) {                       // uniform loop: the conditions come from LDS broadcasts
@@ -401,7 +435,7 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
                         collided |= heq && !eq;
                         const uint32_t rec = (uint32_t)e[10];
                         const uint64_t end = 1ULL << ((rec >> 16) & 63u);
-                        if (eq && sub_text) { if ((rec >> 8) & 1u) rx.a1 |= end; else rx.a0 |= end; }
+                        if (eq && sub_text) { if ((rec >> 8) & 1u) sl.a1 |= end; else sl.a0 |= end; }
                     }
                     continue;
                 }
@@ -432,9 +466,9 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
     if constexpr (SUB) {
         for (uint32_t c = 0; c < a.n_conds; ++c) {                       // uniform loop
             const uint32_t rec = (uint32_t)conds[c * kMatchCondWords + 10];
-            if ((rec & 0xFFu) >= 4u && ((((rec >> 8) & 1u) ? rx.h1 : rx.h0) >> ((rec >> 16) & 63u)) & 1ULL) sat |= 1ULL << c;
+            if ((rec & 0xFFu) >= 4u && ((((rec >> 8) & 1u) ? sl.h1 : sl.h0) >> ((rec >> 16) & 63u)) & 1ULL) sat |= 1ULL << c;
         }
-        if (rx.fail && res == R_DONE) res = R_FAIL;                      // a rune the lower table cannot decide: the host's ToLower does
+        if (sl.fail && res == R_DONE) res = R_FAIL;                      // a rune the lower table cannot decide: the host's ToLower does
     }
     if constexpr (WIDE) {
         // nothing is evaluated here: the flags and what became of the row go to device memory for k_eval_row_programs
@@ -562,6 +596,32 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_substr_tok(c
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_substr_gram(const MatchArgs a, const SubArgs sb, const MatchManyArgs m, const TokSpec t)
 {
     match_rows_body<false, TokGramP, true, kRxActive, false, true>(a, RxArgs{}, TokGramP(t), m, MatchWideArgs{}, sb);
+}
+// ... and with FieldRegex conditions in the same table (bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr); dynamic LDS
+// kMatchSubLdsBytes / kMatchManySubLdsBytes + the table blob (<= kRxSubLdsCap / kRxManySubLdsCap)
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_regex_substr(const MatchArgs a, const RxArgs x, const SubArgs sb)
+{
+    match_rows_body<true, TokDefault, false, kRxActive, false, true>(a, x, TokDefault{}, MatchManyArgs{}, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_regex_substr_tok(const MatchArgs a, const RxArgs x, const SubArgs sb, const TokSpec t)
+{
+    match_rows_body<true, TokSpecP, false, kRxActive, false, true>(a, x, TokSpecP{t}, MatchManyArgs{}, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_regex_substr_gram(const MatchArgs a, const RxArgs x, const SubArgs sb, const TokSpec t)
+{
+    match_rows_body<true, TokGramP, false, kRxActive, false, true>(a, x, TokGramP(t), MatchManyArgs{}, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_substr(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchManyArgs m)
+{
+    match_rows_body<true, TokDefault, true, kRxManyActive, false, true>(a, x, TokDefault{}, m, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_substr_tok(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchManyArgs m, const TokSpec t)
+{
+    match_rows_body<true, TokSpecP, true, kRxManyActive, false, true>(a, x, TokSpecP{t}, m, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_substr_gram(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchManyArgs m, const TokSpec t)
+{
+    match_rows_body<true, TokGramP, true, kRxManyActive, false, true>(a, x, TokGramP(t), m, MatchWideArgs{}, sb);
 }
 
 // the storing walker (bsg_match_rows_wide): plain / regex x default / spec / n-gram tokenizer; dynamic LDS kMatchWideLdsBytes (+ the table

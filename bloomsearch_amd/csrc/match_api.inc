@@ -9,6 +9,10 @@
 // bsg_match_rows_substr / bsg_match_rows_many_substr are the single and the batched call with Substring / FieldSubstring conditions in the
 // table: build_sub_tables folds and packs the needles (host/substring_pack.hpp) where the regex calls build their blob, the part
 // uploads the 4 KiB table, and PlanePart launches the substring instances of the walker.
+// bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr take kinds 0-5 in one table: a table with both FieldRegex and substring
+// conditions gets the blob (under kRxSubLdsCap / kRxManySubLdsCap: what the needle table leaves of the 80 KiB) AND the needle tables
+// and PlanePart launches k_match_rows_regex_substr* / k_match_rows_many_regex_substr*; a table with one of the two sides is the
+// parent call's, its walker and its cap.
 // bsg_match_rows_lookup(_rows) is the wide call with another Family and a LookupPlan beside its WidePlan: WidePart then sizes the
 // flags at W words per row, places the lookup tables (host/lookup_plan.hpp) from the hashes the device made, and launches
 // match_lookup.hip.h's walker and evaluator in place of match.hip.h's.  bsg_match_rows_lookup_regex(_rows) is that call with FieldRegex
@@ -48,6 +52,8 @@ int32_t build_rx_blob(const uint8_t *cond_bytes, const uint32_t *cond_off, const
     }
 }
 
+static_assert(bsh_rxg::kSingleSubLdsCap == bsg::kRxSubLdsCap && bsh_rxg::kManySubLdsCap == bsg::kRxManySubLdsCap,
+              "host/regex_groups.hpp states the caps of the regex tables beside a needle table");
 static_assert(bsh::kSubWords == bsg::kSubWords && sizeof(uint64_t) * 256 * bsh::kSubWords == bsg::kSubTableBytes && bsh::kSubMaxNeedle == 64,
               "host/substring_pack.hpp states the substring kernels' table");
 
@@ -83,6 +89,7 @@ struct MatchCall {
     std::vector<uint32_t> prog_off{0};     // [n_queries + 1] into prog
     std::vector<uint32_t> rx_blob;         // build_rx_blob
     uint32_t n_rx = 0;
+    bool rx_sub = false;                   // the call is bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr (the name in traces)
     bool substr = false;                   // build_sub_tables: the call holds the substring walkers' tables
     bsh::NeedlePack sub;                   // ... M, START, ANY
     std::vector<uint32_t> sub_kinds;       // ... and cond_kinds with word | end bit of a substring condition's needle (match.hip.h SubLane)
@@ -229,6 +236,18 @@ void launch_sub_walker(void (*plain)(bsg::MatchArgs, bsg::SubArgs, E...), void (
     else if (tok) hipExtLaunchKernelGGL(tokk, grid, block, lds, stream, k0, k1, 0, a, sb, e..., *tok);
     else hipExtLaunchKernelGGL(plain, grid, block, lds, stream, k0, k1, 0, a, sb, e...);
 }
+// ... and the six with both consumers; lds_base: the substring instance's bytes, the blob sits behind them
+template <class... E>
+void launch_rx_sub_walker(void (*plain)(bsg::MatchArgs, bsg::RxArgs, bsg::SubArgs, E...), void (*tokk)(bsg::MatchArgs, bsg::RxArgs, bsg::SubArgs, E..., bsg::TokSpec),
+                          void (*gramk)(bsg::MatchArgs, bsg::RxArgs, bsg::SubArgs, E..., bsg::TokSpec), uint32_t lds_base, hipStream_t stream, hipEvent_t k0,
+                          hipEvent_t k1, const bsg::MatchArgs &a, const bsg::RxArgs &x, const bsg::SubArgs &sb, const bsg::TokSpec *tok, const E &...e)
+{
+    const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads), block(bsg::kIngestThreads);
+    const uint32_t lds = lds_base + x.n_words * 4;
+    if (tok && tok->ngram != 0u) hipExtLaunchKernelGGL(gramk, grid, block, lds, stream, k0, k1, 0, a, x, sb, e..., *tok);
+    else if (tok) hipExtLaunchKernelGGL(tokk, grid, block, lds, stream, k0, k1, 0, a, x, sb, e..., *tok);
+    else hipExtLaunchKernelGGL(plain, grid, block, lds, stream, k0, k1, 0, a, x, sb, e...);
+}
 
 // one chunk's walk: a.n_rows rows, one per lane, between the events k0 and k1
 template <class... E>
@@ -281,6 +300,7 @@ struct PlanePart {
 
     const char *tag() const
     {
+        if (mc.rx_sub) return many ? "bsg_match_rows_many_regex_substr" : "bsg_match_rows_regex_substr";
         if (mc.substr) return many ? "bsg_match_rows_many_substr" : "bsg_match_rows_substr";
         return many ? (mc.n_rx ? "bsg_match_rows_many_regex" : "bsg_match_rows_many") : "bsg_match_rows";
     }
@@ -315,6 +335,15 @@ struct PlanePart {
     void launch(PartDev &p, bsg::MatchArgs &a, uint32_t rf, hipEvent_t k0, hipEvent_t k1)
     {
         a.prog = p.d_prog; a.n_ops = (uint32_t)mc.prog.size(); a.out_bits = d_bits + rf / 64;
+        if (mc.substr && mc.n_rx) {                    // both consumers: the blob behind the needle table
+            assert(p.rx.n_words * 4 <= (many ? bsg::kRxManySubLdsCap : bsg::kRxSubLdsCap));
+            if (many) launch_rx_sub_walker(bsg::k_match_rows_many_regex_substr, bsg::k_match_rows_many_regex_substr_tok, bsg::k_match_rows_many_regex_substr_gram,
+                                           bsg::kMatchManySubLdsBytes, p.d.stream, k0, k1, a, p.rx, p.sub, mc.tok(),
+                                           bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
+            else launch_rx_sub_walker(bsg::k_match_rows_regex_substr, bsg::k_match_rows_regex_substr_tok, bsg::k_match_rows_regex_substr_gram,
+                                      bsg::kMatchSubLdsBytes, p.d.stream, k0, k1, a, p.rx, p.sub, mc.tok());
+            return;
+        }
         if (mc.substr) {
             if (many) launch_sub_walker(bsg::k_match_rows_many_substr, bsg::k_match_rows_many_substr_tok, bsg::k_match_rows_many_substr_gram, bsg::kMatchManySubLdsBytes,
                                         p.d.stream, k0, k1, a, p.sub, mc.tok(), bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
@@ -677,7 +706,19 @@ int32_t match_fan_out(bsg_ctx *ctx, const MatchCall &mc, const uint32_t *set_fir
     return match_fan_out(ctx, mc, set_first_row, n_sets, part, [] { return (int32_t)BSG_OK; });
 }
 
-constexpr const char *kNoRegexWithSubstr = "condition %u: a FieldRegex condition (regex and substring conditions do not share a call yet)";
+constexpr const char *kNoRegexWithSubstr = "condition %u: a FieldRegex condition (regex and substring conditions share bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr)";
+
+// which sides a table of bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr holds
+struct TableSides { bool regex = false, sub = false; };
+TableSides table_sides(const MatchCall &mc)
+{
+    TableSides t;
+    for (uint32_t c = 0; c < mc.n_conds; ++c) {
+        t.regex |= mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX;
+        t.sub |= mc.cond_kinds[c] == BSG_KIND_SUBSTRING || mc.cond_kinds[c] == BSG_KIND_FIELD_SUBSTRING;
+    }
+    return t;
+}
 
 // the single and the batched calls' parts: planes over the implicit set {0, n_rows} (cuts at multiples of 64 rows)
 int32_t match_planes_run(bsg_ctx *ctx, const MatchCall &mc, const ManyPlan *many)
@@ -692,6 +733,7 @@ int32_t match_planes_run(bsg_ctx *ctx, const MatchCall &mc, const ManyPlan *many
 // bsg_match_rows (max_kind 2), bsg_match_rows_regex (max_kind 3) and bsg_match_rows_tok (max_kind 3, a spec; NULL = default): the
 // one-query case of the shared checks
 // and bsg_match_rows_substr (substr: kinds 0, 1, 2, 4, 5 under a spec or NULL)
+// and bsg_match_rows_regex_substr (mc.rx_sub: kinds 0-5; the blob and the needle tables are built of what the table holds)
 int32_t match_rows_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, uint32_t n_ops, uint32_t max_kind, const bsg_tokenizer *tok_in, bool substr = false)
 {
     const uint32_t prog_off[2] = {0, n_ops};
@@ -701,7 +743,11 @@ int32_t match_rows_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, u
         if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
     }
     if (int32_t rc = lower_programs(mc, kSingleFamily, prog_ops, prog_off, 1)) return rc;
-    if (substr) { if (int32_t rc = build_sub_tables(mc)) return rc; }
+    if (mc.rx_sub) {
+        const TableSides t = table_sides(mc);
+        if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, t.sub ? bsg::kRxSubLdsCap : bsg::kRxLdsCap)) return rc;
+        if (t.sub) if (int32_t rc = build_sub_tables(mc)) return rc;
+    } else if (substr) { if (int32_t rc = build_sub_tables(mc)) return rc; }
     else if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx)) return rc;
     *mc.out_n_fallback = 0;
     if (mc.n_rows == 0) return BSG_OK;
@@ -735,7 +781,15 @@ int32_t match_rows_many_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
     const ManyPlan plan{set_first_row, query_mask_of_set, n_sets, n_queries, ((size_t)n_rows + 63) / 64};
     if (int32_t rc = lower_programs(mc, kManyFamily, prog_ops, prog_off, n_queries)) return rc;
     // the regex conditions' tables, each with the queries that use it (a table without any: exactly bsg_match_rows_many's kernels)
-    if (substr) { if (int32_t rc = build_sub_tables(mc)) return rc; }
+    if (mc.rx_sub) {
+        const TableSides t = table_sides(mc);
+        if (n_queries) {
+            const std::vector<uint64_t> users = bsh_rxg::user_masks(prog_ops, prog_off, n_queries, mc.n_conds);
+            if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx,
+                                           t.sub ? bsg::kRxManySubLdsCap : bsg::kRxManyLdsCap, users.data())) return rc;
+        }
+        if (t.sub) if (int32_t rc = build_sub_tables(mc)) return rc;
+    } else if (substr) { if (int32_t rc = build_sub_tables(mc)) return rc; }
     else if (max_kind >= BSG_KIND_FIELD_REGEX && n_queries) {
         const std::vector<uint64_t> users = bsh_rxg::user_masks(prog_ops, prog_off, n_queries, mc.n_conds);
         if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, bsg::kRxManyLdsCap, users.data())) return rc;
@@ -1027,6 +1081,29 @@ int32_t bsg_match_rows_many_substr(bsg_ctx *ctx, const uint8_t *rows, const uint
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
     return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_SUBSTRING, true);
+}
+
+int32_t bsg_match_rows_regex_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                    const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                    const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
+                                    uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    mc.rx_sub = true;
+    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_SUBSTRING, tok);
+}
+
+int32_t bsg_match_rows_many_regex_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                         const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                         const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                         const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets, const bsg_tokenizer *tok,
+                                         uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    mc.rx_sub = true;
+    return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_SUBSTRING);
 }
 
 int32_t bsg_match_rows_many(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,

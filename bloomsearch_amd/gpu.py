@@ -662,6 +662,11 @@ class Context:
         conditions (raw needles; the call folds them under `tokenizer`, None = the default)."""
         return self._match_rows(None, rows, matcher, tokenizer, tok_fn=self.L.bsg_match_rows_substr)
 
+    def match_rows_regex_substr(self, rows, matcher, tokenizer=None):
+        """bsg_match_rows_regex_substr: as match_rows_substr, and the matcher (query.CompiledRowSubstringQuery) may hold FieldRegex
+        conditions in the same table: one walk of the rows decides both kinds."""
+        return self._match_rows(None, rows, matcher, tokenizer, tok_fn=self.L.bsg_match_rows_regex_substr)
+
     def _match_rows(self, fn, rows, matcher, tokenizer=None, tok_fn=None):
         if isinstance(rows, tuple):
             blob = np.ascontiguousarray(rows[0], dtype=np.uint8)
@@ -703,6 +708,11 @@ class Context:
         """bsg_match_rows_many_substr: as match_rows_many, and the batch (query.CompiledSubstringQueryBatch) may hold Substring /
         FieldSubstring conditions."""
         return self._match_rows_many(self.L.bsg_match_rows_many_substr, rows, batch, set_first_row, masks, tokenizer)
+
+    def match_rows_many_regex_substr(self, rows, batch, set_first_row=None, masks=None, tokenizer=None):
+        """bsg_match_rows_many_regex_substr: as match_rows_many, and the batch (query.CompiledRowSubstringQueryBatch) may hold FieldRegex,
+        Substring and FieldSubstring conditions in one table."""
+        return self._match_rows_many(self.L.bsg_match_rows_many_regex_substr, rows, batch, set_first_row, masks, tokenizer)
 
     def _match_rows_many(self, fn, rows, batch, set_first_row, masks, tokenizer):
         if isinstance(rows, tuple):

@@ -21,7 +21,7 @@ HOST_EXPORTS = [
     "bsh_regex_match",
     "bsh_section_encode", "bsh_section_parse", "bsh_crc32c",
     "bse_open", "bse_close", "bse_last_error", "bse_stop", "bse_ingest_rows", "bse_flush", "bse_merge", "bse_query", "bse_query_many",
-    "bse_describe", "bse_corrupt_section_byte", "bse_section_bytes",
+    "bse_describe", "bse_match_calls", "bse_corrupt_section_byte", "bse_section_bytes",
 ]
 
 _H = None
@@ -77,6 +77,7 @@ def lib():
     L.bse_query.argtypes = [vp, C.c_char_p, u64, pp, pu64]
     L.bse_query_many.argtypes = [vp, C.c_char_p, u64, pp, pu64]
     L.bse_describe.argtypes = [vp, pp, pu64]
+    L.bse_match_calls.argtypes = [vp, pp, pu64]
     L.bse_corrupt_section_byte.argtypes = [vp, u32, i32, u64]
     L.bse_section_bytes.argtypes = [vp, u32, i32, pp, pu64]
     for n in HOST_EXPORTS:
@@ -373,6 +374,12 @@ class Engine:
     def describe(self):
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self.L.bse_describe(self.h, C.byref(p), C.byref(n)))
+        return json.loads(_take(self.L, p, n))
+
+    def match_calls(self) -> dict:
+        """bse_match_calls: device row-matcher entry point -> how often the engine has called it (the route its queries took)."""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._check(self.L.bse_match_calls(self.h, C.byref(p), C.byref(n)))
         return json.loads(_take(self.L, p, n))
 
     def corrupt_section_byte(self, file_index: int, block_index: int, byte_index: int):

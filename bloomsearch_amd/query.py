@@ -440,6 +440,33 @@ class CompiledSubstringQueryBatch(CompiledMatcherBatch):
         return CompiledSubstringQuery(*pair)
 
 
+class CompiledRowSubstringQuery(CompiledRowQuery, CompiledSubstringQuery):
+    """And(bloom root | TRUE, regex root, substring root) for bsg_match_rows_regex_substr: the bloom side lowered as CompiledMatcher does,
+    the regex side by CompiledRowQuery's rules (an empty field is FALSE), the substring side by CompiledSubstringQuery's; FieldRegex,
+    Substring and FieldSubstring conditions share the one table."""
+
+    def __init__(self, bloom_expression, regex_expression, substring_expression):
+        CompiledMatcher.__init__(self, None)
+        if bloom_expression is None:
+            self.prog_ops.append(op(OP_TRUE))
+        else:
+            self._emit(bloom_expression)
+        self._emit_regex(regex_expression)
+        self._emit_substring(substring_expression)
+        self.prog_ops.append(op(OP_AND, 3))
+
+
+class CompiledRowSubstringQueryBatch(CompiledMatcherBatch):
+    """A batch of (bloom expression, regex expression, substring expression) triples for one bsg_match_rows_many_regex_substr call: query
+    q's program is CompiledRowSubstringQuery's with its condition indices remapped into ONE table of distinct conditions, deduplicated
+    by (kind, field, token / pattern / needle).  Raises ValueError beyond 64 queries, 64 conditions, 2 048 lowered ops or 16 regex
+    conditions."""
+
+    @staticmethod
+    def _compile(triple):
+        return CompiledRowSubstringQuery(*triple)
+
+
 class CompiledRowQueryBatch(CompiledMatcherBatch):
     """A batch of (bloom expression, regex expression) pairs for one bsg_match_rows_many_regex call: query q's program is
     CompiledRowQuery(bloom_q, regex_q)'s with its condition indices remapped into ONE table of distinct conditions,

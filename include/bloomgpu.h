@@ -52,7 +52,7 @@ extern "C" {
 #define BSG_KIND_TOKEN        1u
 #define BSG_KIND_FIELD_TOKEN  2u
 #define BSG_KIND_FIELD_REGEX  3u   /* row matcher only (bsg_match_rows_regex): entry 2i = field, 2i + 1 = pattern */
-#define BSG_KIND_SUBSTRING        4u   /* bsg_match_rows_substr / _many_substr only: entry 2i empty, 2i + 1 = the needle */
+#define BSG_KIND_SUBSTRING        4u   /* bsg_match_rows_substr / _many_substr / _regex_substr / _many_regex_substr only: entry 2i empty, 2i + 1 = the needle */
 #define BSG_KIND_FIELD_SUBSTRING  5u   /* ... entry 2i = the field, 2i + 1 = the needle */
 
 /* ---- query program opcodes: op = (opcode << 28) | arg, postfix order ----
@@ -681,8 +681,8 @@ BSG_API int32_t bsg_match_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint
  * leaf's path has the hashes of a FieldSubstring condition's field but not its fingerprint.
  * Limits: a needle of at most 64 bytes after folding; the needles are packed first-fit, in condition order, into 2 words of 64
  * bytes and a needle never straddles a word, so at most 128 needle bytes per call (BSG_E_UNSUPPORTED beyond).
- * A BSG_KIND_FIELD_REGEX condition is BSG_E_UNSUPPORTED: regex and substring conditions do not share a call yet.  Every other
- * entry point answers kinds 4 and 5 with BSG_E_INVALID (unknown kind). */
+ * A BSG_KIND_FIELD_REGEX condition is BSG_E_UNSUPPORTED here: regex and substring conditions share bsg_match_rows_regex_substr.
+ * Every entry point but these two pairs answers kinds 4 and 5 with BSG_E_INVALID (unknown kind). */
 BSG_API int32_t bsg_match_rows_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
                                       const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
                                       const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
@@ -722,6 +722,33 @@ BSG_API int32_t bsg_match_rows_many_substr(bsg_ctx *ctx, const uint8_t *rows, co
                                            const bsg_tokenizer *tok,
                                            uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                            uint32_t *out_n_fallback);
+/* FieldRegex AND substring conditions in one table, decided in ONE walk of the rows (kinds 0-5; k_match_rows_regex_substr*): the
+ * arguments of bsg_match_rows_substr, a FieldRegex condition as bsg_match_rows_regex documents it, a substring condition as
+ * bsg_match_rows_substr does.  Every candidate text goes to both consumers: the DFAs read the raw bytes, the needles the folded ones.
+ * A table without a FieldRegex condition is bsg_match_rows_substr's, one without a substring condition bsg_match_rows_tok's: the
+ * same kernels, limits and bits.  With both kinds in the table:
+ * Limits (BSG_E_UNSUPPORTED before anything is launched, the condition named): 64 conditions, 16 regex conditions with patterns in
+ * the compiler's subset, regex tables of at most 40 448 bytes (what the needle table leaves of bsg_match_rows_regex's 44 544), the
+ * needle limits of bsg_match_rows_substr, the program limits of bsg_match_rows.
+ * Fallback rows: the union of the two parents' — the walker's envelope, a fingerprint collision, more than 4 regex conditions on
+ * one leaf, a rune the lower table cannot decide.  bsh_match_row_with, bsh_match_row_regex and bsh_match_row_substring decide them. */
+BSG_API int32_t bsg_match_rows_regex_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                            const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                            const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
+                                            uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                            uint32_t *out_n_fallback);
+/* The batched call of the same (k_match_rows_many_regex_substr*): the nineteen arguments, set / mask semantics and plane layout of
+ * bsg_match_rows_many, the regex rules of bsg_match_rows_many_regex (a leaf opens a condition's DFA only on a row whose set mask
+ * selects a query that uses it, so "more than 4 regex conditions on one leaf" counts those alone), the needle limits of
+ * bsg_match_rows_substr, and regex tables (user masks included) of at most 34 032 bytes beside a needle table.  Plane q = what
+ * bsg_match_rows_regex_substr returns for program q alone, ANDed with the set mask. */
+BSG_API int32_t bsg_match_rows_many_regex_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                                 const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                                 const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                                 const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets,
+                                                 const bsg_tokenizer *tok,
+                                                 uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                                 uint32_t *out_n_fallback);
 /* bsg_match_rows_many with FieldRegex conditions in the table (k_match_rows_many_regex): the same nineteen arguments, set / mask
  * semantics, plane layout, sharding over the context's devices, chunked upload and bsg_last_match_ms.  What differs:
  * - cond_kinds[i] may be BSG_KIND_FIELD_REGEX (entry 2i = the field, 2i + 1 = the pattern) with the meaning bsg_match_rows_regex

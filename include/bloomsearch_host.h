@@ -178,6 +178,10 @@ BSG_API int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t
  *  flushes built from a stream.  A batch whose append fails is answered with the error and is not buffered; the rows buffered
  *  before it are flushed through the one-shot path. */
 BSG_API int32_t bse_describe(bse_engine *e, char **out_json, uint64_t *out_len);
+/* {"bsg_match_rows_regex_substr": 3, "bsg_match_rows_tok": 1, ...}: how often the engine has called each device row-matcher entry
+ * point (bloomgpu.h bsg_match_rows_*) since bse_open, a call the library answered BSG_E_UNSUPPORTED included; an entry point never
+ * called is absent.  The route a query took: bsg_device_calls counts parts, and every route makes one match part. */
+BSG_API int32_t bse_match_calls(bse_engine *e, char **out_json, uint64_t *out_len);
 /* fault injection (the reference's tests wrap its stores to corrupt reads): XOR one byte of a stored section */
 BSG_API int32_t bse_corrupt_section_byte(bse_engine *e, uint32_t file_index, int32_t block_index, uint64_t byte_index);
 /* raw filter-section bytes of (file index, block index); block index -1 = the file-level section */

@@ -858,6 +858,9 @@ int32_t bsg_open(const int32_t *device_ids, int32_t n_devices, bsg_ctx **out_ctx
         for (const void *k : {reinterpret_cast<const void *>(bsg::k_match_rows_many_regex_substr), reinterpret_cast<const void *>(bsg::k_match_rows_many_regex_substr_tok),
                               reinterpret_cast<const void *>(bsg::k_match_rows_many_regex_substr_gram)})
             HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bsg::kMatchManySubLdsBytes + bsg::kRxManySubLdsCap));
+        for (const void *k : {reinterpret_cast<const void *>(bsg::k_match_rows_store_regex_substr), reinterpret_cast<const void *>(bsg::k_match_rows_store_regex_substr_tok),
+                              reinterpret_cast<const void *>(bsg::k_match_rows_store_regex_substr_gram)})
+            HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bsg::kMatchWideSubLdsBytes + bsg::kRxWideSubLdsCap));
 
         ctx->devs.push_back(std::move(d));
     }

@@ -30,6 +30,7 @@
 #include "regex_groups.hpp"
 #include "section_codec.hpp"
 #include "substring.hpp"
+#include "substring_groups.hpp"
 #include "wide_plan.hpp"
 #include "lookup_plan.hpp"
 
@@ -70,8 +71,9 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     bool device_regex = false;
     // true (with device_match): query_many packs its queries into groups bounded by the condition table alone (64 distinct
     // conditions, 16 regex conditions, the table bytes, co_active_bound) - not by 64 members - and decides each group by ONE
-    // bsg_match_rows_wide call, every set's query list read straight from the probe's survivors.  Off by default: routing is then
-    // exactly the batched calls'.
+    // bsg_match_rows_wide call, every set's query list read straight from the probe's survivors (a group that holds a substring
+    // condition: ONE bsg_match_rows_wide_substr call, its needles packed and its regex tables under the cap beside them).  Off by
+    // default: routing is then exactly the batched calls'.
     bool device_match_wide = false;
     // true (with device_match): the grouping of device_match_wide, each group decided by ONE bsg_match_rows_wide_rows call: every
     // pair's matching rows come back as a list (or NONE / ALL / its words) and are consumed as such, no bit row is scanned.  Off by
@@ -79,7 +81,8 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     bool device_match_wide_rows = false;
     // true (with device_match): query_many's groups WITHOUT a regex condition hold up to 1 024 distinct conditions and are each decided
     // by ONE bsg_match_rows_lookup call (device_match_lookup_rows: bsg_match_rows_lookup_rows, the lists consumed as under
-    // device_match_wide_rows); a query with a regex condition keeps the 64-condition groups of the wide call.  Off by default.
+    // device_match_wide_rows); a query with a regex condition keeps the 64-condition groups of the wide call, and so does one with a
+    // substring condition (the lookup calls take no needle).  Off by default.
     bool device_match_lookup = false;
     bool device_match_lookup_rows = false;
     // with either of the two (and device_regex): a group that holds regex conditions keeps the 1 024-condition bound and is decided by
@@ -407,26 +410,40 @@ public:
     // subset (the test query() makes): it is probed with query()'s pruning expression And(bloom, field guard) and matched as the
     // program And(bloom root | TRUE, regex root) by bsg_match_rows_many_regex.  Every other regex query is answered by query() and
     // placed at its position, and so is a batched one whose group the device did not decide.
-    // A query with a substring tree (subs[i]) is answered by query() too.
+    // A query with a substring tree (subs[i]) stays in the batch under DeviceMatch when its needles are valid (and, with a regex tree as
+    // well, under the regex rule above): it is probed with query()'s pruning expression And(bloom, regex field guard, substring guard)
+    // and matched as the program And(bloom root | TRUE, regex root, substring root) in its group's call — bsg_match_rows_many_substr /
+    // bsg_match_rows_many_regex_substr, or bsg_match_rows_wide_substr(_rows) under the wide keys (substring_groups.hpp says when a
+    // group closes and which call it makes).  Every other substring query is answered by query(), and so is a batched one whose
+    // group the device did not decide.
     int32_t query_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
                        std::vector<QueryResult> &results, const std::vector<const SubstringExpression *> *subs = nullptr)
     {
         results.assign(exprs.size(), QueryResult{});
         std::vector<size_t> live;                   // the batch: queries without a regex tree, and regex queries the device matches
         std::vector<const RegexExpression *> live_regex;
+        std::vector<const SubstringExpression *> live_sub;
         std::vector<std::unique_ptr<RegexRowMatcher>> regex_dfas;   // per batched query: the DFA-backed matcher of the rows handed back
+        std::vector<std::unique_ptr<SubstringRowMatcher>> sub_matchers;   // ... and the substring matcher of the same
         for (size_t i = 0; i < exprs.size(); ++i) {
             const RegexExpression *rx = i < regexes.size() ? regexes[i] : nullptr;
-            if (subs && i < subs->size() && (*subs)[i]) { if (int32_t rc = query(exprs[i], results[i], rx, (*subs)[i])) return rc; continue; }
+            const SubstringExpression *sx = subs && i < subs->size() ? (*subs)[i] : nullptr;
+            std::unique_ptr<SubstringRowMatcher> sub_matcher;
+            if (sx && cfg_.device_match) {
+                sub_matcher = std::make_unique<SubstringRowMatcher>(sx, cfg_.tokenizer);
+                if (!sub_matcher->valid()) sub_matcher.reset();
+            }
             std::unique_ptr<RegexRowMatcher> dfa;
             if (rx && cfg_.device_match && cfg_.device_regex) {
                 dfa = std::make_unique<RegexRowMatcher>(rx, true);
                 if (!dfa->valid()) dfa.reset();
             }
-            if (rx && !dfa) { if (int32_t rc = query(exprs[i], results[i], rx)) return rc; continue; }
+            if ((sx && !sub_matcher) || (rx && !dfa)) { if (int32_t rc = query(exprs[i], results[i], rx, sx)) return rc; continue; }
             live.push_back(i);
             live_regex.push_back(rx);
+            live_sub.push_back(sx);
             regex_dfas.push_back(std::move(dfa));
+            sub_matchers.push_back(std::move(sub_matcher));
         }
         if (live.empty()) return kEngineOk;
         const auto t_begin = std::chrono::steady_clock::now();
@@ -435,11 +452,14 @@ public:
         for (size_t k = 0; k < live.size(); ++k) {
             batch.push_back(exprs[live[k]]);
             // pruneBloomQuery = AndBloomQueries(bloom, RegexFieldGuardBloomQuery(regex)), as query(); a plain query keeps its pointer
-            if (!live_regex[k]) { prune.push_back(batch[k]); continue; }
-            BloomExpression guard;
+            if (!live_regex[k] && !live_sub[k]) { prune.push_back(batch[k]); continue; }
+            BloomExpression guard, sub_guard, two;
             const bool has_guard = regex_field_guard(live_regex[k], guard);
+            const bool has_two = and_bloom_queries(batch[k], has_guard ? &guard : nullptr, two);
+            // ... and the substring guard as its third side
+            const bool has_sub_guard = substring_guard(live_sub[k], cfg_.tokenizer, sub_guard);
             prune_storage.push_back(std::make_unique<BloomExpression>());
-            prune.push_back(and_bloom_queries(batch[k], has_guard ? &guard : nullptr, *prune_storage.back()) ? prune_storage.back().get() : nullptr);
+            prune.push_back(and_bloom_queries(has_two ? &two : nullptr, has_sub_guard ? &sub_guard : nullptr, *prune_storage.back()) ? prune_storage.back().get() : nullptr);
         }
         std::vector<Survivors> sv;
         if (int32_t rc = probe_stage(prune, sv)) return rc;
@@ -477,13 +497,13 @@ public:
         for (size_t k = 0; k < Q; ++k) matchers.emplace_back(batch[k], cfg_.tokenizer);
         std::vector<uint8_t> on_device(Q, 0);
         if (cfg_.device_match && !scan.empty())
-            if (int32_t rc = match_rows_device_many(batch, live_regex, scan, set_first, set_wants, matchers, regex_dfas, hit, on_device)) return rc;
+            if (int32_t rc = match_rows_device_many(batch, live_regex, live_sub, scan, set_first, set_wants, matchers, regex_dfas, sub_matchers, hit, on_device)) return rc;
         for (size_t k = 0; k < Q; ++k) {
             QueryResult &out = results[live[k]];
             // not decided in a group (alone beyond a limit, or the library refused the group): per query, as before.  query() probes
             // again and rewrites the stats block_stage_stats left here: known, and rare enough not to carry the survivors over
-            if (live_regex[k] && !on_device[k] && !scanned[k].empty()) {
-                if (int32_t rc = query(exprs[live[k]], out, live_regex[k])) return rc;
+            if ((live_regex[k] || live_sub[k]) && !on_device[k] && !scanned[k].empty()) {
+                if (int32_t rc = query(exprs[live[k]], out, live_regex[k], live_sub[k])) return rc;
                 continue;
             }
             for (size_t s = 0; s + 1 < set_first.size(); ++s) {
@@ -1038,11 +1058,17 @@ private:
     // bounded by bsh_lookup::rx_lds_cap_of over the group's table (strings <= 2 x its other conditions, pairs <= its FieldToken ones).
     // Under DeviceMatchWide a group has no member limit (and the storing walker's larger table cap): one bsg_match_rows_wide call per
     // group, each set's CSR query list read from set_wants; its result holds a bit row per (set, listed query) only.
+    // A query with a substring tree (subs[k]) adds And(.., substring root) to its program and its Substring / FieldSubstring conditions
+    // to the table.  A group with a needle also closes where the next query's needles would no longer pack beside its own, and its
+    // regex tables are bounded by the reduced cap beside a needle table (substring_groups.hpp fits); it is decided by
+    // bsg_match_rows_many_substr / bsg_match_rows_many_regex_substr, under the wide keys by bsg_match_rows_wide_substr(_rows), and never by
+    // a lookup call (under the lookup keys it takes the wide route, bounded by 64 conditions).
     int32_t match_rows_device_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
+                                   const std::vector<const SubstringExpression *> &subs,
                                    const std::vector<const std::string *> &scan, const std::vector<uint32_t> &set_first,
                                    const std::vector<const std::vector<uint8_t> *> &set_wants, std::vector<RowMatcher> &host_matchers,
-                                   std::vector<std::unique_ptr<RegexRowMatcher>> &host_regex, std::vector<std::vector<uint8_t>> &hit,
-                                   std::vector<uint8_t> &on_device)
+                                   std::vector<std::unique_ptr<RegexRowMatcher>> &host_regex, std::vector<std::unique_ptr<SubstringRowMatcher>> &host_sub,
+                                   std::vector<std::vector<uint8_t>> &hit, std::vector<uint8_t> &on_device)
     {
         std::vector<uint8_t> bytes;
         std::vector<uint64_t> row_off{0};
@@ -1076,32 +1102,43 @@ private:
             std::vector<size_t> members;
             uint32_t n_rx = 0, rx_table = 0;                                 // the group's regex conditions and their table bytes
             uint32_t n_plain = 0, n_ft = 0;                                  // its other conditions, and the FieldToken ones among them
+            bsh_subg::Group sub_group;                                       // its needles as they pack, and rx_table once more
             for (; k < exprs.size() && members.size() < max_members; ++k) {
                 MatcherProgram mp(exprs[k]);
-                if (regexes[k]) {
-                    if (!exprs[k]) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
-                    lower_regex(*regexes[k], mp);
-                    mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 2));
+                if (regexes[k] || subs[k]) {
+                    if (!exprs[k] || mp.prog_ops.empty()) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
+                    if (regexes[k]) lower_regex(*regexes[k], mp);
+                    if (subs[k]) emit_substring_program(*subs[k], mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
+                    mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 1u + (regexes[k] ? 1u : 0u) + (subs[k] ? 1u : 0u)));
                 }
                 // what the query adds: distinct conditions, regex conditions, table bytes, and the fields that may meet on a leaf
                 std::map<std::tuple<uint32_t, std::string, std::string>, uint32_t> added;
                 uint32_t fresh_rx = 0, fresh_bytes = 0, fresh_plain = 0, fresh_ft = 0;
+                bsh_subg::Fresh fresh_sub;                                   // the folded lengths of its fresh needles, in condition order
                 for (size_t c = 0; c < mp.kinds.size(); ++c) {
                     const auto key = std::make_tuple(mp.kinds[c], mp.fields[c], mp.tokens[c]);
                     if (index.count(key) || !added.emplace(key, 0).second) continue;
                     if (mp.kinds[c] == BSG_KIND_FIELD_REGEX) { ++fresh_rx; fresh_bytes += rx_bytes(mp.fields[c], mp.tokens[c]); }
+                    else if (mp.kinds[c] == BSG_KIND_SUBSTRING || mp.kinds[c] == BSG_KIND_FIELD_SUBSTRING) {
+                        std::string folded;
+                        (void)fold_needle(mp.tokens[c], cfg_.tokenizer, folded);       // valid: the caller kept the query in the batch
+                        fresh_sub.needle_len.push_back((uint32_t)folded.size());
+                    }
                     else { ++fresh_plain; fresh_ft += mp.kinds[c] == BSG_KIND_FIELD_TOKEN ? 1u : 0u; }
                 }
+                fresh_sub.rx_bytes = fresh_bytes;
                 std::vector<std::string_view> rx_fields;
                 for (size_t c = 0; c < kinds.size(); ++c) if (kinds[c] == BSG_KIND_FIELD_REGEX) rx_fields.push_back(fields[c]);
                 for (const auto &kv : added) if (std::get<0>(kv.first) == BSG_KIND_FIELD_REGEX) rx_fields.push_back(std::get<1>(kv.first));
                 const bool rx_group = n_rx + fresh_rx != 0;
-                const size_t cond_cap = lookup && (!rx_group || lookup_regex) ? bsh_lookup::kMaxConds : 64;
+                const bool needle_group = sub_group.n_needles + fresh_sub.needle_len.size() != 0;   // never a lookup call's
+                const size_t cond_cap = lookup && !needle_group && (!rx_group || lookup_regex) ? bsh_lookup::kMaxConds : 64;
                 // the lookup regex call's cap depends on the table: what this group's strings and pairs can take at most
-                const uint32_t group_cap = lookup_regex && rx_group ? bsh_lookup::rx_lds_cap_of(2u * (n_plain + fresh_plain), n_ft + fresh_ft) : table_cap;
+                const uint32_t group_cap = lookup_regex && rx_group && !needle_group ? bsh_lookup::rx_lds_cap_of(2u * (n_plain + fresh_plain), n_ft + fresh_ft) : table_cap;
                 const bool fits = mp.kinds.size() <= cond_cap && index.size() + added.size() <= cond_cap && n_rx + fresh_rx <= bsh_rxg::kMaxRegexConds &&
                                   bsh_rxg::align4(rx_table + fresh_bytes) <= group_cap &&
-                                  bsh_rxg::co_active_bound(rx_fields) <= bsh_rxg::kManySlots;
+                                  bsh_rxg::co_active_bound(rx_fields) <= bsh_rxg::kManySlots &&
+                                  (!needle_group || bsh_subg::fits(sub_group, fresh_sub, wide));   // the needles pack, the tables fit beside them
                 if (!fits) {
                     // alone beyond the call: the caller's (the host matcher; per query for a regex query).  Else it opens the next group
                     if (members.empty()) ++k;
@@ -1122,8 +1159,15 @@ private:
                 rx_table += fresh_bytes;
                 n_plain += fresh_plain;
                 n_ft += fresh_ft;
+                bsh_subg::add(sub_group, fresh_sub);
             }
             if (members.empty()) continue;
+            const bsh_subg::Call call = bsh_subg::group_call(n_rx != 0, sub_group.n_needles != 0, wide, wide_rows);
+            const bool by_sub = sub_group.n_needles != 0;
+            // a row the device handed back: the host matchers of query m together
+            auto host_verdict = [&](size_t m, const std::string &row) {
+                return host_matchers[m].match(row) && (!host_regex[m] || host_regex[m]->match(row)) && (!host_sub[m] || host_sub[m]->match(row));
+            };
             std::vector<uint8_t> cbytes;
             std::vector<uint32_t> coff{0};
             for (size_t c = 0; c < kinds.size(); ++c) {
@@ -1131,7 +1175,7 @@ private:
                 cbytes.insert(cbytes.end(), tokens[c].begin(), tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
             }
             if (wide) {
-                const bool by_lookup = lookup && n_rx == 0, by_lookup_regex = lookup_regex && n_rx != 0;
+                const bool by_lookup = lookup && n_rx == 0 && !by_sub, by_lookup_regex = lookup_regex && n_rx != 0 && !by_sub;
                 // each set's list: the group's members that survived the probe on it, straight from set_wants
                 std::vector<uint32_t> sq_off{0}, sq;
                 for (size_t s = 0; s < n_sets; ++s) {
@@ -1151,8 +1195,8 @@ private:
                     std::vector<uint32_t> hdr(sq.size() + 1), payload(2 * total + 1), ids;
                     std::vector<uint64_t> pair_off(sq.size() + 1);
                     uint64_t payload_len = 0;
-                    count_match_call(by_lookup_regex ? "bsg_match_rows_lookup_regex_rows" : by_lookup ? "bsg_match_rows_lookup_rows" : "bsg_match_rows_wide_rows");
-                    const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex_rows : by_lookup ? bsg_match_rows_lookup_rows : bsg_match_rows_wide_rows)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
+                    count_match_call(by_lookup_regex ? "bsg_match_rows_lookup_regex_rows" : by_lookup ? "bsg_match_rows_lookup_rows" : bsh_subg::call_name(call));
+                    const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex_rows : by_lookup ? bsg_match_rows_lookup_rows : by_sub ? bsg_match_rows_wide_substr_rows : bsg_match_rows_wide_rows)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
                                                                 kinds.data(), (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(),
                                                                 (uint32_t)members.size(), set_first.data(), sq_off.data(), sq.data(), (uint32_t)n_sets, &tok,
                                                                 hdr.data(), pair_off.data(), payload.data(), 2 * total, &payload_len, fb.data(),
@@ -1173,8 +1217,8 @@ private:
                     }
                 } else {
                 std::vector<uint64_t> words(total + 1);
-                count_match_call(by_lookup_regex ? "bsg_match_rows_lookup_regex" : by_lookup ? "bsg_match_rows_lookup" : "bsg_match_rows_wide");
-                const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex : by_lookup ? bsg_match_rows_lookup : bsg_match_rows_wide)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
+                count_match_call(by_lookup_regex ? "bsg_match_rows_lookup_regex" : by_lookup ? "bsg_match_rows_lookup" : bsh_subg::call_name(call));
+                const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex : by_lookup ? bsg_match_rows_lookup : by_sub ? bsg_match_rows_wide_substr : bsg_match_rows_wide)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
                                                        (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(),
                                                        sq_off.data(), sq.data(), (uint32_t)n_sets, &tok, words.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
                 if (rc == BSG_E_UNSUPPORTED) continue;
@@ -1192,7 +1236,7 @@ private:
                     const std::string &row = *scan[fb[i]];
                     for (uint32_t p = sq_off[s]; p < sq_off[s + 1]; ++p) {
                         const size_t m = members[sq[p]];
-                        hit[m][fb[i]] = host_matchers[m].match(row) && (!host_regex[m] || host_regex[m]->match(row));
+                        hit[m][fb[i]] = host_verdict(m, row);
                     }
                 }
                 continue;
@@ -1203,8 +1247,9 @@ private:
             std::vector<uint64_t> bits(members.size() * n_words);
             std::vector<uint32_t> fb(scan.size());
             uint32_t n_fb = 0;
-            count_match_call(n_rx ? "bsg_match_rows_many_regex" : "bsg_match_rows_many");
-            const int32_t rc = (n_rx ? bsg_match_rows_many_regex : bsg_match_rows_many)(
+            count_match_call(bsh_subg::call_name(call));
+            const int32_t rc = (call == bsh_subg::Call::ManyRegexSubstr ? bsg_match_rows_many_regex_substr : call == bsh_subg::Call::ManySubstr ? bsg_match_rows_many_substr :
+                                n_rx ? bsg_match_rows_many_regex : bsg_match_rows_many)(
                 ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(), (uint32_t)kinds.size(),
                 prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(), masks.data(), (uint32_t)n_sets, &tok, bits.data(),
                 fb.data(), (uint32_t)fb.size(), &n_fb);
@@ -1220,7 +1265,7 @@ private:
                 const std::string &row = *scan[fb[i]];
                 for (size_t j = 0; j < members.size(); ++j)
                     if ((masks[s] >> j) & 1)
-                        hit[members[j]][fb[i]] = host_matchers[members[j]].match(row) && (!host_regex[members[j]] || host_regex[members[j]]->match(row));
+                        hit[members[j]][fb[i]] = host_verdict(members[j], row);
             }
         }
         return kEngineOk;

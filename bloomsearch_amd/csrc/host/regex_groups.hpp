@@ -22,6 +22,7 @@ constexpr uint32_t kSingleLdsCap = 44544;      // match.hip.h kRxLdsCap: table b
 constexpr uint32_t kManyLdsCap = 38140;        // match.hip.h kRxManyLdsCap: table bytes of bsg_match_rows_many_regex
 constexpr uint32_t kSingleSubLdsCap = 40448;   // match.hip.h kRxSubLdsCap: table bytes of bsg_match_rows_regex_substr beside a needle table
 constexpr uint32_t kManySubLdsCap = 34032;     // match.hip.h kRxManySubLdsCap: the same of bsg_match_rows_many_regex_substr
+constexpr uint32_t kWideSubLdsCap = 42496;     // match.hip.h kRxWideSubLdsCap: the same of bsg_match_rows_wide_substr
 constexpr uint32_t kSingleSlots = 4;           // match.hip.h kRxActive: regex conditions one leaf may feed at once
 constexpr uint32_t kManySlots = 4;             // match.hip.h kRxManyActive: the same in the batched kernels.  Another shipped count means
                                                // this literal and the "4" of bloomgpu.h, bloomsearch_host.h, INTEGRATION.md, bloomgpu.go and

@@ -68,6 +68,12 @@
 // byte goes to the RxLaneT (raw) and to the SubLane (folded), a leaf request runs both parents' handling, and a row is a fallback row
 // by either parent's rule.  LDS: the needle table where the substring instances have it, the regex blob behind the table (at most
 // kRxSubLdsCap = 40 448 / kRxManySubLdsCap = 34 032 bytes: 80 KiB in all, two workgroups per CU as the regex walkers).
+//
+// Substring conditions in the storing walker (bsg_match_rows_wide_substr, k_match_rows_store_substr* / k_match_rows_store_regex_substr* =
+// WIDE and SUB): the needle table sits at kMatchWideLdsBytes = 35 328 (a multiple of 16), 39 424 bytes in all and three workgroups per CU;
+// with regex tables (at most kRxWideSubLdsCap = 42 496 bytes) 80 KiB, two.  Regex conditions stay gated by the set's condition mask,
+// needles are not: every needle of the table listens on every walked row, and the flag of a condition none of the set's queries
+// references is unspecified (nothing reads it).  A row is a fallback row by the union of the parents' rules.
 #pragma once
 #include <type_traits>
 #include "ingest.hip.h"
@@ -282,6 +288,12 @@ struct RxSubFeed {
 // LDS of the two instances: the needle table where the substring instances have it, the regex blob behind the table
 constexpr uint32_t kRxSubLdsCap = 80u * 1024u - kMatchSubLdsBytes;
 constexpr uint32_t kRxManySubLdsCap = 80u * 1024u - kMatchManySubLdsBytes;
+// ... and of the storing walker's two (k_match_rows_store_substr* / k_match_rows_store_regex_substr*): the table behind the lanes, then the blob
+constexpr uint32_t kMatchWideSubLdsBytes = kMatchWideLdsBytes + kSubTableBytes;
+constexpr uint32_t kRxWideSubLdsCap = 80u * 1024u - kMatchWideSubLdsBytes;
+static_assert(kMatchWideLdsBytes % 16u == 0u && kMatchWideSubLdsBytes == 35328u + 4096u && 3u * kMatchWideSubLdsBytes <= 160u * 1024u &&
+                  kRxWideSubLdsCap == 42496u && kRxWideSubLdsCap <= 0x10000u && 2u * (kMatchWideSubLdsBytes + kRxWideSubLdsCap) <= 160u * 1024u,
+              "k_match_rows_store_substr keeps three workgroups per CU, its table 16-byte aligned; k_match_rows_store_regex_substr two, and the blob's 16-bit offsets reach all of it");
 static_assert(kRxSubLdsCap == 40448u && kRxManySubLdsCap == 34032u && kRxSubLdsCap <= 0x10000u && kMatchSubLdsBytes % 4u == 0u && kMatchManySubLdsBytes % 4u == 0u &&
                   2u * (kMatchSubLdsBytes + kRxSubLdsCap) <= 160u * 1024u && 2u * (kMatchManySubLdsBytes + kRxManySubLdsCap) <= 160u * 1024u,
               "k_match_rows_regex_substr and k_match_rows_many_regex_substr keep two workgroups per CU, and the blob's 16-bit offsets reach all of it");
@@ -302,8 +314,7 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
                                                 const MatchWideArgs &wd = MatchWideArgs{}, const SubArgs &sb = SubArgs{})
 {
     static_assert(!(MANY && WIDE), "the storing walker evaluates no program");
-    static_assert(!(SUB && WIDE), "substring conditions: the single and the batched call");
-    constexpr uint32_t kSubBase = MANY ? kMatchManySubBase : kMatchLdsBytes;   // the needle table sits behind the instance's own LDS
+    constexpr uint32_t kSubBase = WIDE ? kMatchWideLdsBytes : MANY ? kMatchManySubBase : kMatchLdsBytes;   // the needle table sits behind the instance's own LDS
     constexpr uint32_t kProgBytes = WIDE ? 0u : MANY ? kMatchManyProgBytes : kMatchMaxOps * 4;
     constexpr uint32_t kRxBase = SUB ? kSubBase + kSubTableBytes : WIDE ? kMatchWideLdsBytes : MANY ? kMatchManyLdsBytes : kMatchLdsBytes;   // the regex blob sits behind the instance's own LDS (and the needle table)
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
@@ -649,6 +660,34 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_gram(const 
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_gram(const MatchArgs a, const RxArgs x, const MatchWideArgs wd, const TokSpec t)
 {
     match_rows_body<true, TokGramP, false, kRxActive, true>(a, x, TokGramP(t), MatchManyArgs{}, wd);
+}
+
+// ... with the substring consumer (bsg_match_rows_wide_substr): kinds 0, 1, 2, 4, 5; dynamic LDS kMatchWideSubLdsBytes.  Every needle
+// listens on every walked row (needles are not gated by the set's condition mask).
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_substr(const MatchArgs a, const SubArgs sb, const MatchWideArgs wd)
+{
+    match_rows_body<false, TokDefault, false, kRxActive, true, true>(a, RxArgs{}, TokDefault{}, MatchManyArgs{}, wd, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_substr_tok(const MatchArgs a, const SubArgs sb, const MatchWideArgs wd, const TokSpec t)
+{
+    match_rows_body<false, TokSpecP, false, kRxActive, true, true>(a, RxArgs{}, TokSpecP{t}, MatchManyArgs{}, wd, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_substr_gram(const MatchArgs a, const SubArgs sb, const MatchWideArgs wd, const TokSpec t)
+{
+    match_rows_body<false, TokGramP, false, kRxActive, true, true>(a, RxArgs{}, TokGramP(t), MatchManyArgs{}, wd, sb);
+}
+// ... and with both consumers: kinds 0-5; dynamic LDS kMatchWideSubLdsBytes + the table blob (<= kRxWideSubLdsCap)
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_substr(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchWideArgs wd)
+{
+    match_rows_body<true, TokDefault, false, kRxActive, true, true>(a, x, TokDefault{}, MatchManyArgs{}, wd, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_substr_tok(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchWideArgs wd, const TokSpec t)
+{
+    match_rows_body<true, TokSpecP, false, kRxActive, true, true>(a, x, TokSpecP{t}, MatchManyArgs{}, wd, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_substr_gram(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchWideArgs wd, const TokSpec t)
+{
+    match_rows_body<true, TokGramP, false, kRxActive, true, true>(a, x, TokGramP(t), MatchManyArgs{}, wd, sb);
 }
 
 // The programs of the listed (set, query) pairs over the stored flags.  Wave w of the grid owns item w: one 64-row tile of one set

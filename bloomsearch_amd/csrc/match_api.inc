@@ -13,6 +13,9 @@
 // conditions gets the blob (under kRxSubLdsCap / kRxManySubLdsCap: what the needle table leaves of the 80 KiB) AND the needle tables
 // and PlanePart launches k_match_rows_regex_substr* / k_match_rows_many_regex_substr*; a table with one of the two sides is the
 // parent call's, its walker and its cap.
+// bsg_match_rows_wide_substr(_rows) is the wide call with kinds 0-5 in its table: a table with a substring condition gets the needle tables
+// (and its blob under kRxWideSubLdsCap) and WidePart launches k_match_rows_store_substr* / k_match_rows_store_regex_substr*; a table
+// without one is bsg_match_rows_wide(_rows)'s, its walkers and its cap.
 // bsg_match_rows_lookup(_rows) is the wide call with another Family and a LookupPlan beside its WidePlan: WidePart then sizes the
 // flags at W words per row, places the lookup tables (host/lookup_plan.hpp) from the hashes the device made, and launches
 // match_lookup.hip.h's walker and evaluator in place of match.hip.h's.  bsg_match_rows_lookup_regex(_rows) is that call with FieldRegex
@@ -57,6 +60,7 @@ static_assert(bsh_rxg::kSingleSubLdsCap == bsg::kRxSubLdsCap && bsh_rxg::kManySu
 static_assert(bsh::kSubWords == bsg::kSubWords && sizeof(uint64_t) * 256 * bsh::kSubWords == bsg::kSubTableBytes && bsh::kSubMaxNeedle == 64,
               "host/substring_pack.hpp states the substring kernels' table");
 
+static_assert(bsh_rxg::kWideSubLdsCap == bsg::kRxWideSubLdsCap, "host/regex_groups.hpp states the cap of the storing walker's regex tables beside a needle table");
 static_assert(bsh_wide::kWideLdsCap == bsg::kRxWideLdsCap && sizeof(bsh_wide::EvalItem) == sizeof(bsg::RowEvalItem) &&
                   offsetof(bsh_wide::EvalItem, stride) == offsetof(bsg::RowEvalItem, stride),
               "host/wide_plan.hpp states the kernels' limits and item layout");
@@ -90,6 +94,7 @@ struct MatchCall {
     std::vector<uint32_t> rx_blob;         // build_rx_blob
     uint32_t n_rx = 0;
     bool rx_sub = false;                   // the call is bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr (the name in traces)
+    bool wide_sub = false;                 // the call is bsg_match_rows_wide_substr(_rows) (the name in traces)
     bool substr = false;                   // build_sub_tables: the call holds the substring walkers' tables
     bsh::NeedlePack sub;                   // ... M, START, ANY
     std::vector<uint32_t> sub_kinds;       // ... and cond_kinds with word | end bit of a substring condition's needle (match.hip.h SubLane)
@@ -225,7 +230,7 @@ constexpr Walkers<bsg::MatchLookupArgs> kLookupWalkers{bsg::k_match_rows_lookup,
                                                        bsg::k_match_rows_lookup_regex_tok, bsg::k_match_rows_lookup_gram,
                                                        bsg::k_match_rows_lookup_regex_gram};   // regex: bsg_match_rows_lookup_regex(_rows) only
 
-// ... and the six with the substring consumer: (single / many) x (default tokenizer / spec / spec with an n-gram width)
+// ... and the nine with the substring consumer: (single / many / wide) x (default tokenizer / spec / spec with an n-gram width)
 template <class... E>
 void launch_sub_walker(void (*plain)(bsg::MatchArgs, bsg::SubArgs, E...), void (*tokk)(bsg::MatchArgs, bsg::SubArgs, E..., bsg::TokSpec),
                        void (*gramk)(bsg::MatchArgs, bsg::SubArgs, E..., bsg::TokSpec), uint32_t lds, hipStream_t stream, hipEvent_t k0, hipEvent_t k1,
@@ -236,7 +241,7 @@ void launch_sub_walker(void (*plain)(bsg::MatchArgs, bsg::SubArgs, E...), void (
     else if (tok) hipExtLaunchKernelGGL(tokk, grid, block, lds, stream, k0, k1, 0, a, sb, e..., *tok);
     else hipExtLaunchKernelGGL(plain, grid, block, lds, stream, k0, k1, 0, a, sb, e...);
 }
-// ... and the six with both consumers; lds_base: the substring instance's bytes, the blob sits behind them
+// ... and the nine with both consumers; lds_base: the substring instance's bytes, the blob sits behind them
 template <class... E>
 void launch_rx_sub_walker(void (*plain)(bsg::MatchArgs, bsg::RxArgs, bsg::SubArgs, E...), void (*tokk)(bsg::MatchArgs, bsg::RxArgs, bsg::SubArgs, E..., bsg::TokSpec),
                           void (*gramk)(bsg::MatchArgs, bsg::RxArgs, bsg::SubArgs, E..., bsg::TokSpec), uint32_t lds_base, hipStream_t stream, hipEvent_t k0,
@@ -421,6 +426,7 @@ struct WidePart {
     {
         if (wp.lookup_regex) return wp.rows ? "bsg_match_rows_lookup_regex_rows" : "bsg_match_rows_lookup_regex";
         if (wp.lookup) return wp.rows ? "bsg_match_rows_lookup_rows" : "bsg_match_rows_lookup";
+        if (mc.wide_sub) return wp.rows ? "bsg_match_rows_wide_substr_rows" : "bsg_match_rows_wide_substr";
         return wp.rows ? "bsg_match_rows_wide_rows" : "bsg_match_rows_wide";
     }
     bool prog_off() const { return true; }
@@ -505,7 +511,19 @@ struct WidePart {
             launch_walker(kLookupWalkers, bsg::lookup_lds_bytes(lk.n_str_slots, lk.n_pair_slots), p.d.stream, k0, k1, a, p.rx, mc.tok(), lk);
             return;
         }
-        launch_walker(kWideWalkers, bsg::kMatchWideLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok(), bsg::MatchWideArgs{d_sfirst, d_smask, d_spair, d_sat + rf, d_state + rf, n_sets});
+        const bsg::MatchWideArgs wd{d_sfirst, d_smask, d_spair, d_sat + rf, d_state + rf, n_sets};
+        if (mc.substr && mc.n_rx) {                    // both consumers: the blob behind the needle table
+            assert(p.rx.n_words * 4 <= bsg::kRxWideSubLdsCap);
+            launch_rx_sub_walker(bsg::k_match_rows_store_regex_substr, bsg::k_match_rows_store_regex_substr_tok, bsg::k_match_rows_store_regex_substr_gram,
+                                 bsg::kMatchWideSubLdsBytes, p.d.stream, k0, k1, a, p.rx, p.sub, mc.tok(), wd);
+            return;
+        }
+        if (mc.substr) {
+            launch_sub_walker(bsg::k_match_rows_store_substr, bsg::k_match_rows_store_substr_tok, bsg::k_match_rows_store_substr_gram, bsg::kMatchWideSubLdsBytes,
+                              p.d.stream, k0, k1, a, p.sub, mc.tok(), wd);
+            return;
+        }
+        launch_walker(kWideWalkers, bsg::kMatchWideLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok(), wd);
     }
     int32_t results(PartDev &p, EventList &kev)        // the evaluation between two more events, then the part's words
     {
@@ -821,8 +839,9 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
     if (rows && (!rows->len || (rows->cap && !rows->payload))) return fail(BSG_E_INVALID, "null argument");
     if (int32_t rc = begin_match_call(mc, fam, tok_in, prog_ops, prog_off, n_queries)) return rc;
     const uint32_t n_rows = mc.n_rows;
+    const uint32_t max_kind = mc.wide_sub ? BSG_KIND_FIELD_SUBSTRING : BSG_KIND_FIELD_REGEX;   // kinds 4 and 5: bsg_match_rows_wide_substr(_rows) only
     for (uint32_t c = 0; c < mc.n_conds; ++c) {
-        if (mc.cond_kinds[c] > BSG_KIND_FIELD_REGEX) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
+        if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
     }
     // the lookup call: the table's distinct role strings, their role records and the FieldToken pairs
     bsh_lookup::Plan lookup_plan;
@@ -861,7 +880,10 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
     }
     if (int32_t rc = lower_programs(mc, fam, prog_ops, prog_off, n_queries, lookup ? &lookup_plan.canon : nullptr)) return rc;
     if (!lookup) {
-        if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, bsg::kRxWideLdsCap)) return rc;
+        // a table with needles: the blob under what the needle table leaves, then the needle tables; one without: the wide call's own
+        const bool sub = mc.wide_sub && table_sides(mc).sub;
+        if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, sub ? bsg::kRxWideSubLdsCap : bsg::kRxWideLdsCap)) return rc;
+        if (sub) if (int32_t rc = build_sub_tables(mc)) return rc;
     } else if (lookup_regex) {
         // the DISTINCT regex conditions, under what this table's strings, pairs and lanes leave of a workgroup's 80 KiB
         const uint32_t cap = bsh_lookup::rx_lds_cap_of(lookup_plan.n_strings(), (uint32_t)lookup_plan.pairs.size());
@@ -956,6 +978,35 @@ int32_t bsg_match_rows_wide_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64
     // pairs are counted; nothing is written through out_bits)
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
                  fallback_cap, out_n_fallback};
+    const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
+}
+
+int32_t bsg_match_rows_wide_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                   const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                   const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                   const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
+                                   const bsg_tokenizer *tok,
+                                   uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    mc.wide_sub = true;
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
+}
+
+int32_t bsg_match_rows_wide_substr_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                        const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                        const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                        const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
+                                        const bsg_tokenizer *tok,
+                                        uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap, uint64_t *out_payload_len,
+                                        uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
+                 fallback_cap, out_n_fallback};
+    mc.wide_sub = true;
     const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
     return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
 }

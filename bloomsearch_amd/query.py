@@ -494,6 +494,14 @@ class CompiledWideBatch(CompiledRowQueryBatch):
         return CompiledRowQuery(*item) if isinstance(item, tuple) else CompiledMatcher(item)
 
 
+class CompiledWideSubstringBatch(CompiledRowSubstringQueryBatch):
+    """Any number of (bloom expression, regex expression, substring expression) triples for one bsg_match_rows_wide_substr call: the
+    table and the programs exactly as CompiledRowSubstringQueryBatch builds them, without the 64-query and 2 048-op limits of the
+    batched calls.  Raises ValueError beyond 2^20 queries, 2^22 lowered ops, 64 conditions or 16 regex conditions."""
+
+    MAX_QUERIES, MAX_OPS = MATCH_WIDE_MAX_QUERIES, MATCH_WIDE_MAX_OPS
+
+
 MATCH_LOOKUP_MAX_CONDS = 1024                                                        # bloomgpu.h BSG_MATCH_LOOKUP_MAX_CONDS
 
 

@@ -682,7 +682,7 @@ BSG_API int32_t bsg_match_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint
  * Limits: a needle of at most 64 bytes after folding; the needles are packed first-fit, in condition order, into 2 words of 64
  * bytes and a needle never straddles a word, so at most 128 needle bytes per call (BSG_E_UNSUPPORTED beyond).
  * A BSG_KIND_FIELD_REGEX condition is BSG_E_UNSUPPORTED here: regex and substring conditions share bsg_match_rows_regex_substr.
- * Every entry point but these two pairs answers kinds 4 and 5 with BSG_E_INVALID (unknown kind). */
+ * Every entry point but these two pairs and bsg_match_rows_wide_substr(_rows) answers kinds 4 and 5 with BSG_E_INVALID (unknown kind). */
 BSG_API int32_t bsg_match_rows_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
                                       const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
                                       const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
@@ -840,6 +840,38 @@ BSG_API int32_t bsg_match_rows_wide_rows(bsg_ctx *ctx, const uint8_t *rows, cons
                                          uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap,
                                          uint64_t *out_payload_len, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                          uint32_t *out_n_fallback);
+/* bsg_match_rows_wide / bsg_match_rows_wide_rows with substring conditions allowed in the table (kinds 0-5; the storing walkers
+ * k_match_rows_store_substr* / k_match_rows_store_regex_substr*): the parameter lists, sets, pairs and the implicit set, result layouts,
+ * bsg_match_wide_size, bsg_match_pair_rows_list, sharding, chunked upload and bsg_last_match_ms of the two wide calls; a substring
+ * condition as bsg_match_rows_substr documents it (the RAW needle as entry 2i + 1, folded under the call's tokenizer), a FieldRegex
+ * condition as bsg_match_rows_wide does.  Pair p's bits = what bsg_match_rows_regex_substr returns for the program of set_queries[p]
+ * alone over the set's rows.  A table without a substring condition is bsg_match_rows_wide(_rows)'s: the same kernels, limits and bits.
+ * Regex conditions stay gated by the set's queries; needles are not: every needle of the table listens on every walked row.  Rows of
+ * a set with no pair are never walked.
+ * Limits (BSG_E_UNSUPPORTED before anything is launched, the condition named): 64 distinct conditions; 16 distinct regex conditions
+ * with patterns in the compiler's subset; program depth 64; the query, op, pair and item limits of bsg_match_rows_wide; a needle of at
+ * most 64 bytes after folding, the needles packed first-fit in condition order into 2 words of 64 bytes (128 needle bytes at most); regex
+ * tables of at most 42 496 bytes of LDS when the table holds a needle (81 920 minus the storing walker's 35 328 and the needle table's
+ * 4 096: 39 424 bytes without regex tables), 46 592 when it holds none.  BSG_E_INVALID: what bsg_match_rows_wide refuses, an empty
+ * needle or one that is not valid UTF-8, a kind above 5.
+ * Fallback rows, only among rows of a set with at least one pair (all their pair bits 0, never counted in a list): the union of the
+ * parents' rules — the walker's envelope, a fingerprint collision with ANY table condition (a FieldSubstring condition's field
+ * included), more than 4 regex conditions of the set's queries on one leaf, a rune the lower table cannot decide. */
+BSG_API int32_t bsg_match_rows_wide_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                           const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                           const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                           const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                           uint32_t n_sets, const bsg_tokenizer *tok,
+                                           uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                           uint32_t *out_n_fallback);
+BSG_API int32_t bsg_match_rows_wide_substr_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                                const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                                const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                                const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                                uint32_t n_sets, const bsg_tokenizer *tok,
+                                                uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap,
+                                                uint64_t *out_payload_len, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                                uint32_t *out_n_fallback);
 /* One pair of bsg_match_rows_wide_rows, whatever its tag, as its ascending set-relative row indices (host arithmetic without a
  * context): payload = out_payload + out_pair_off[p] (not read for NONE / ALL), set_rows = the rows of the pair's set.  *out_n is the
  * full count; at most cap indices are written.  BSG_E_INVALID: a header and payload that are no pair of such a set (a count the

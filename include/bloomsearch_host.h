@@ -169,7 +169,15 @@ BSG_API int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, c
  * with the mask of the queries that survived on it.  Under DeviceMatch + DeviceRegex a query with a Regex tree whose patterns
  * all lie in the device's RE2 subset joins the batch (probed with its pruning expression, matched by bsg_match_rows_many_regex in
  * groups of <= 16 regex conditions whose tables fit the batched kernel and of which no more than 4 can meet on one leaf); every
- * other query with a Regex tree is answered as by bse_query.  "[]" gives "[]". */
+ * other query with a Regex tree is answered as by bse_query.  Under DeviceMatch a query with a "Substring" tree whose needles are
+ * valid joins the batch too (with a Regex tree as well: under the rule above): it is probed with And(bloom, regex field guard,
+ * substring guard) and matched as And(bloom | TRUE, regex, substring); a group that holds a needle also closes where the needles of
+ * its distinct substring conditions no longer pack first-fit into 2 x 64 bytes and bounds its regex tables by the cap beside a needle
+ * table (34 032 bytes batched, 42 496 wide), and is decided by ONE bsg_match_rows_many_substr / bsg_match_rows_many_regex_substr call -
+ * under DeviceMatchWide / DeviceMatchWideRows (and the lookup keys, which never take a group with a needle) by ONE
+ * bsg_match_rows_wide_substr / bsg_match_rows_wide_substr_rows call.  A query that breaks a limit alone, and a group the library
+ * answers BSG_E_UNSUPPORTED for, are answered as by bse_query.  Without DeviceMatch a query with a Substring tree is answered as by
+ * bse_query.  "[]" gives "[]". */
 BSG_API int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, char **out_json, uint64_t *out_len);
 /* {"files":[{"FileID","BloomEntryCounts":{..},"section_bytes","blocks":[{"PartitionID","Rows","BloomEntryCounts":{..},
  *  "BloomFalsePositiveRate","BloomFilterSize","filters":[{"m","k"}|null x3]}]}],

@@ -29,6 +29,7 @@
 #include "expression.hpp"
 #include "regex_groups.hpp"
 #include "section_codec.hpp"
+#include "range.hpp"
 #include "substring.hpp"
 #include "substring_groups.hpp"
 #include "wide_plan.hpp"
@@ -327,17 +328,26 @@ public:
     // bsg_match_rows_regex_substr call decides And(bloom root, regex root, substring root); where the library answers
     // BSG_E_UNSUPPORTED (tables over the cap beside the needle table, needles that do not pack) the regex call decides its two sides
     // and SubstringRowMatcher the third, as for every other combination of the keys and without DeviceMatch.
-    int32_t query(const BloomExpression *row_expr, QueryResult &out, const RegexExpression *regex = nullptr, const SubstringExpression *sub = nullptr)
+    // range: the range tree of the query (range.hpp).  Its guard — every condition as Field(field) — is a fourth side of the pruning
+    // expression; the row test is bloom AND regex AND substring AND range.  Under DeviceMatch a query with neither a regex nor a
+    // substring tree is decided by ONE bsg_match_rows_range call over the program And(bloom root, range root) (the rows it hands back,
+    // those with an exponent literal on a range field among them: the host matchers).  Every other combination takes the route it
+    // took without the range tree, and RangeRowMatcher filters its hits.
+    int32_t query(const BloomExpression *row_expr, QueryResult &out, const RegexExpression *regex = nullptr, const SubstringExpression *sub = nullptr,
+                  const RangeExpression *range = nullptr)
     {
         out = QueryResult{};
         const auto t_begin = std::chrono::steady_clock::now();
         SubstringRowMatcher sub_matcher(sub, cfg_.tokenizer);
         if (!sub_matcher.valid()) return fail(kErrInvalidQuery, "substring needle: non-empty valid UTF-8 of at most 64 bytes after folding");
-        BloomExpression guard, sub_guard, two_storage, prune_storage;
+        RangeRowMatcher range_matcher(range);
+        BloomExpression guard, sub_guard, range_guard_storage, two_storage, three_storage, prune_storage;
         const bool has_guard = regex_field_guard(regex, guard);
         const bool has_two = and_bloom_queries(row_expr, has_guard ? &guard : nullptr, two_storage);
         const bool has_sub_guard = substring_guard(sub, cfg_.tokenizer, sub_guard);
-        const BloomExpression *expr = and_bloom_queries(has_two ? &two_storage : nullptr, has_sub_guard ? &sub_guard : nullptr, prune_storage) ? &prune_storage : nullptr;
+        const bool has_three = and_bloom_queries(has_two ? &two_storage : nullptr, has_sub_guard ? &sub_guard : nullptr, three_storage);
+        const bool has_range_guard = range_guard(range, range_guard_storage);
+        const BloomExpression *expr = and_bloom_queries(has_three ? &three_storage : nullptr, has_range_guard ? &range_guard_storage : nullptr, prune_storage) ? &prune_storage : nullptr;
         std::vector<Survivors> sv;
         if (int32_t rc = probe_stage({expr}, sv)) return rc;
         const std::vector<uint8_t> &file_ok = sv[0].file_ok;
@@ -358,7 +368,11 @@ public:
         for (const ScanBlock &sb : scanned)
             for (const std::string &row : files_[sb.f].blocks[sb.b].rows) scan.push_back(&row);
         std::vector<uint8_t> hit(scan.size(), 0);
-        bool on_device = false, regex_done = false, sub_done = false;
+        bool on_device = false, regex_done = false, sub_done = false, range_done = false;
+        if (range && !regex && !sub && cfg_.device_match && !scan.empty()) {   // one walk decides bloom AND range
+            if (int32_t rc = match_rows_device_range(row_expr, *range, scan, matcher, range_matcher, hit, range_done)) return rc;
+            on_device = range_done;
+        }
         if (regex_on_device && sub && !scan.empty()) {      // both trees: one walk decides bloom AND regex AND substring
             bool both_done = false;
             if (int32_t rc = match_rows_device_regex_substr(row_expr, *regex, *sub, scan, matcher, regex_dfa, sub_matcher, hit, both_done)) return rc;
@@ -368,7 +382,7 @@ public:
             if (int32_t rc = match_rows_device_regex(row_expr, *regex, scan, matcher, regex_dfa, hit, regex_done)) return rc;
             if (!regex_done && !regex_matcher.valid()) return fail(kErrInvalidQuery, "regex pattern does not compile");
         }
-        on_device = regex_done;
+        on_device = on_device || regex_done;
         if (sub && !regex && cfg_.device_match && !scan.empty()) {
             if (int32_t rc = match_rows_device_substr(row_expr, *sub, scan, matcher, sub_matcher, hit, sub_done)) return rc;
             on_device = sub_done;
@@ -395,6 +409,9 @@ public:
         if (sub && !sub_done)
             for (size_t i = 0; i < scan.size(); ++i)
                 if (hit[i]) hit[i] = sub_matcher.match(*scan[i]);
+        if (range && !range_done)
+            for (size_t i = 0; i < scan.size(); ++i)
+                if (hit[i]) hit[i] = range_matcher.match(*scan[i]);
         for (size_t i = 0; i < scan.size(); ++i)
             if (hit[i]) out.rows.push_back(*scan[i]);
         add_scan_time(t_scan, scanned, out);
@@ -417,7 +434,8 @@ public:
     // group closes and which call it makes).  Every other substring query is answered by query(), and so is a batched one whose
     // group the device did not decide.
     int32_t query_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
-                       std::vector<QueryResult> &results, const std::vector<const SubstringExpression *> *subs = nullptr)
+                       std::vector<QueryResult> &results, const std::vector<const SubstringExpression *> *subs = nullptr,
+                       const std::vector<const RangeExpression *> *ranges = nullptr)
     {
         results.assign(exprs.size(), QueryResult{});
         std::vector<size_t> live;                   // the batch: queries without a regex tree, and regex queries the device matches
@@ -428,6 +446,11 @@ public:
         for (size_t i = 0; i < exprs.size(); ++i) {
             const RegexExpression *rx = i < regexes.size() ? regexes[i] : nullptr;
             const SubstringExpression *sx = subs && i < subs->size() ? (*subs)[i] : nullptr;
+            // a query with a range tree (ranges[i]) is answered by query(): keeping such queries in the groups is a follow-up
+            if (const RangeExpression *rg = ranges && i < ranges->size() ? (*ranges)[i] : nullptr) {
+                if (int32_t rc = query(exprs[i], results[i], rx, sx, rg)) return rc;
+                continue;
+            }
             std::unique_ptr<SubstringRowMatcher> sub_matcher;
             if (sx && cfg_.device_match) {
                 sub_matcher = std::make_unique<SubstringRowMatcher>(sx, cfg_.tokenizer);
@@ -1333,6 +1356,42 @@ private:
         if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
         for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
         for (uint32_t i = 0; i < n_fb; ++i) hit[fb[i]] = host_matcher.match(*scan[fb[i]]) && sub_matcher.match(*scan[fb[i]]);
+        done = true;
+        return kEngineOk;
+    }
+
+    // And(bloom root | TRUE, range root) over the scan list in one bsg_match_rows_range call; the rows it hands back (the walker's envelope,
+    // a fingerprint collision, an exponent literal on a range field) are decided by both host matchers.  done stays false (the host
+    // decides) beyond 64 conditions or what the call holds (depth, ops).
+    int32_t match_rows_device_range(const BloomExpression *expr, const RangeExpression &range, const std::vector<const std::string *> &scan,
+                                    RowMatcher &host_matcher, RangeRowMatcher &range_matcher, std::vector<uint8_t> &hit, bool &done)
+    {
+        MatcherProgram mp(expr);
+        if (mp.prog_ops.empty()) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
+        emit_range_program(range, mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
+        mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 2));
+        if (mp.kinds.size() > 64) return kEngineOk;
+        std::vector<uint8_t> cbytes;
+        std::vector<uint32_t> coff{0};
+        for (size_t c = 0; c < mp.kinds.size(); ++c) {
+            cbytes.insert(cbytes.end(), mp.fields[c].begin(), mp.fields[c].end()); coff.push_back((uint32_t)cbytes.size());
+            cbytes.insert(cbytes.end(), mp.tokens[c].begin(), mp.tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
+        }
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> row_off{0};
+        for (const std::string *r : scan) { bytes.insert(bytes.end(), r->begin(), r->end()); row_off.push_back(bytes.size()); }
+        std::vector<uint64_t> bits((scan.size() + 63) / 64);
+        std::vector<uint32_t> fb(scan.size());
+        uint32_t n_fb = 0;
+        const bsg_tokenizer tok = c_tokenizer();
+        count_match_call("bsg_match_rows_range");
+        const int32_t rc = bsg_match_rows_range(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(),
+                                                (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok, bits.data(), fb.data(),
+                                                (uint32_t)fb.size(), &n_fb);
+        if (rc == BSG_E_UNSUPPORTED) return kEngineOk;
+        if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
+        for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
+        for (uint32_t i = 0; i < n_fb; ++i) hit[fb[i]] = host_matcher.match(*scan[fb[i]]) && range_matcher.match(*scan[fb[i]]);
         done = true;
         return kEngineOk;
     }

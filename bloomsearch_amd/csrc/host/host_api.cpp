@@ -7,6 +7,7 @@
 
 #include "engine.hpp"
 #include "regex_dfa.hpp"
+#include "range.hpp"
 #include "substring.hpp"
 
 using namespace bsh;
@@ -375,6 +376,55 @@ int32_t bsh_match_row_substring(const char *substring_json, uint64_t substring_l
     return m.match(std::string_view(reinterpret_cast<const char *>(row), row_len)) ? 1 : 0;
 }
 
+namespace {
+bool parse_range_json(const char *json, uint64_t len, RangeExpression &e, bool &nil)
+{
+    nil = true;
+    std::string_view sv(json ? json : "", json ? len : 0);
+    if (sv.empty()) return true;
+    JNode dom;
+    if (!parse_dom(sv, dom)) return false;
+    if (dom.type == JType::Null) return true;
+    if (!range_expression_from_json(dom, e)) return false;
+    nil = false;
+    return true;
+}
+}  // namespace
+
+// bsh_prune_query_sub with the range tree's guard as a fourth side
+int32_t bsh_prune_query_range(const char *bloom_json, uint64_t bloom_len, const char *regex_json, uint64_t regex_len, const char *substring_json,
+                              uint64_t substring_len, const char *range_json, uint64_t range_len, const bsg_tokenizer *tok, char **out, uint64_t *out_len)
+{
+    BloomExpression b, guard, sguard, rguard, two, three, pruned;
+    RegexExpression r;
+    SubstringExpression sx;
+    RangeExpression rg;
+    Tokenizer t;
+    bool bnil = true, rnil = true, snil = true, gnil = true;
+    if (!tokenizer_from(tok, t) || !parse_expression_json(bloom_json, bloom_len, b, bnil) || !parse_regex_json(regex_json, regex_len, r, rnil) ||
+        !parse_substring_json(substring_json, substring_len, sx, snil) || !parse_range_json(range_json, range_len, rg, gnil))
+        return BSH_E_INVALID;
+    if (!snil) if (int32_t rc = needle_status(check_needles(sx, t))) return rc;
+    const bool has_guard = regex_field_guard(rnil ? nullptr : &r, guard);
+    const bool has_two = and_bloom_queries(bnil ? nullptr : &b, has_guard ? &guard : nullptr, two);
+    const bool has_sub = substring_guard(snil ? nullptr : &sx, t, sguard);
+    const bool has_three = and_bloom_queries(has_two ? &two : nullptr, has_sub ? &sguard : nullptr, three);
+    const bool has_range = range_guard(gnil ? nullptr : &rg, rguard);
+    std::string s = "null";
+    if (and_bloom_queries(has_three ? &three : nullptr, has_range ? &rguard : nullptr, pruned)) { s.clear(); expression_to_json(pruned, s); }
+    return give(s, out, out_len);
+}
+
+// the range half of the final row test (range.hpp RangeRowMatcher): 1 match, 0 no match, < 0 invalid arguments
+int32_t bsh_match_row_range(const char *range_json, uint64_t range_len, const uint8_t *row, uint64_t row_len)
+{
+    RangeExpression rg;
+    bool nil = true;
+    if ((row_len && !row) || !parse_range_json(range_json, range_len, rg, nil)) return BSH_E_INVALID;
+    RangeRowMatcher m(nil ? nullptr : &rg);
+    return m.match(std::string_view(reinterpret_cast<const char *>(row), row_len)) ? 1 : 0;
+}
+
 // the regex half of matchRowBytes (row_matcher.go:548-573): 1 match, 0 no match, < 0 invalid arguments / pattern
 int32_t bsh_match_row_regex(const char *regex_json, uint64_t regex_len, const uint8_t *row, uint64_t row_len)
 {
@@ -495,7 +545,8 @@ struct ParsedQuery {
     BloomExpression expr;
     RegexExpression regex;
     SubstringExpression sub;
-    bool nil = true, has_regex = false, has_sub = false;
+    RangeExpression range;
+    bool nil = true, has_regex = false, has_sub = false, has_range = false;
 };
 
 int32_t query_from_dom(const JNode &dom, ParsedQuery &q)
@@ -523,6 +574,13 @@ int32_t query_from_dom(const JNode &dom, ParsedQuery &q)
             const JNode *ex = sx->get("Expression");
             if (!substring_expression_from_json(ex && ex->type == JType::Object ? *ex : *sx, q.sub)) return BSE_E_INVALID_QUERY;
             q.has_sub = true;
+        }
+        // "Range": the same two forms
+        const JNode *rg = dom.get("Range");
+        if (rg && rg->type == JType::Object) {
+            const JNode *ex = rg->get("Expression");
+            if (!range_expression_from_json(ex && ex->type == JType::Object ? *ex : *rg, q.range)) return BSE_E_INVALID_QUERY;
+            q.has_range = true;
         }
     } else if (dom.type != JType::Null) {
         return BSE_E_INVALID_QUERY;
@@ -562,7 +620,7 @@ int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, char **ou
         if (int32_t rc = query_from_dom(dom, q)) return rc;
     }
     QueryResult res;
-    if (int32_t rc = e->eng->query(q.nil ? nullptr : &q.expr, res, q.has_regex ? &q.regex : nullptr, q.has_sub ? &q.sub : nullptr)) return rc;
+    if (int32_t rc = e->eng->query(q.nil ? nullptr : &q.expr, res, q.has_regex ? &q.regex : nullptr, q.has_sub ? &q.sub : nullptr, q.has_range ? &q.range : nullptr)) return rc;
     std::string out;
     result_to_json(res, out);
     return give(out, out_json, out_len);
@@ -579,11 +637,13 @@ int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, ch
     std::vector<const BloomExpression *> exprs;
     std::vector<const RegexExpression *> regexes;
     std::vector<const SubstringExpression *> subs;
+    std::vector<const RangeExpression *> ranges;
     for (const ParsedQuery &q : qs) {
         exprs.push_back(q.nil ? nullptr : &q.expr); regexes.push_back(q.has_regex ? &q.regex : nullptr); subs.push_back(q.has_sub ? &q.sub : nullptr);
+        ranges.push_back(q.has_range ? &q.range : nullptr);
     }
     std::vector<QueryResult> res;
-    if (int32_t rc = e->eng->query_many(exprs, regexes, res, &subs)) return rc;
+    if (int32_t rc = e->eng->query_many(exprs, regexes, res, &subs, &ranges)) return rc;
     std::string out = "[";
     for (size_t i = 0; i < res.size(); ++i) { if (i) out.push_back(','); result_to_json(res[i], out); }
     out.push_back(']');

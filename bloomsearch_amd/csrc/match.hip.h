@@ -74,6 +74,16 @@
 // with regex tables (at most kRxWideSubLdsCap = 42 496 bytes) 80 KiB, two.  Regex conditions stay gated by the set's condition mask,
 // needles are not: every needle of the table listens on every walked row, and the flag of a condition none of the set's queries
 // references is unspecified (nothing reads it).  A row is a fallback row by the union of the parents' rules.
+//
+// Numeric range conditions (kind 6, k_match_rows_range* / k_match_rows_many_range* = the same body with RANGE = true): "some number leaf
+// whose path EQUALS the field has a value inside [lo, hi]" (int64 bounds, each closed, open or absent), decided exactly by a fourth text
+// consumer.  NumLane parses the raw literal the walker feeds byte by byte into sign, a u64 magnitude of the integer digits with a sticky
+// overflow bit, and "the fraction has a non-zero digit": one parse per leaf, a few registers, nothing in LDS.  A leaf request decides the
+// number still pending against every range condition listening on ITS leaf (leaf_mask, FieldToken's hash-and-fingerprint compare of the
+// path), then the condition loop marks the conditions listening on the new leaf; the last number is decided after the walk.  The
+// compare is integer arithmetic on (sign, magnitude, overflow, fraction): there is no float64 round trip.  A literal with an exponent on
+// a leaf ANY range condition of the table listens on makes the row a fallback row (the host compares digit strings).  The bounds sit in
+// the condition's record where a token's hash words would (e[4] = lo, e[5] = hi), the flags in bits 8-11 of e[10]: no byte of LDS is added.
 #pragma once
 #include <type_traits>
 #include "ingest.hip.h"
@@ -298,6 +308,74 @@ static_assert(kRxSubLdsCap == 40448u && kRxManySubLdsCap == 34032u && kRxSubLdsC
                   2u * (kMatchSubLdsBytes + kRxSubLdsCap) <= 160u * 1024u && 2u * (kMatchManySubLdsBytes + kRxManySubLdsCap) <= 160u * 1024u,
               "k_match_rows_regex_substr and k_match_rows_many_regex_substr keep two workgroups per CU, and the blob's 16-bit offsets reach all of it");
 
+// ---- numeric range conditions ----
+// A condition's LDS record e[10] in these kernels: kind | flags << 8 (kind 6; else the kind alone); e[4] = lo, e[5] = hi as two's complement.
+constexpr uint32_t kRangeNoLo = 1u, kRangeNoHi = 2u, kRangeLoOpen = 4u, kRangeHiOpen = 8u;   // bloomgpu.h BSG_RANGE_*
+// The range walkers add no LDS: each keeps its RANGE-less sibling's bytes, and so its three workgroups per CU.
+static_assert(3u * kMatchLdsBytes <= 160u * 1024u && 3u * kMatchManyLdsBytes <= 160u * 1024u,
+              "k_match_rows_range and k_match_rows_many_range keep three workgroups per CU as k_match_rows and k_match_rows_many");
+// One lane's number parser: the raw literal of the current number leaf as -?digits[.digits][(e|E)...], fed byte by byte.
+struct NumLane {
+    const Walker *wk;                       // whether the current leaf is one that is never emitted
+    uint64_t mag;                           // the integer digits' value mod 2^64 ...
+    bool on;                                // the current leaf is a number some range condition listens on
+    bool neg, ovf, point, frac, expo;        // '-' seen; ... and whether it passed 2^64 - 1; '.' seen; a non-zero fraction digit; an exponent part
+    __device__ __forceinline__ void open(bool listen)
+    {
+        on = listen; mag = 0; neg = ovf = point = frac = expo = false;
+    }
+    __device__ __forceinline__ void feed(uint32_t b)
+    {
+        if (!on || wk->quiet || expo) return;                       // a leaf without a path has no request: its bytes belong to no number of ours
+        const uint32_t d = b - (uint32_t)'0';
+        if (d <= 9u) {
+            if (point) frac |= d != 0u;
+            else {
+                ovf |= mag > 1844674407370955161ULL || (mag == 1844674407370955161ULL && d > 5u);   // mag * 10 + d > 2^64 - 1
+                mag = mag * 10u + d;
+            }
+        }
+        else if (b == '-') neg = true;
+        else if (b == '.') point = true;
+        else expo = true;                                           // 'e' / 'E': the host decides this literal
+    }
+    __device__ __forceinline__ void feed_run(uint64_t, uint32_t) {}   // only strings reach these two
+    __device__ __forceinline__ void feed_rune(uint32_t) {}
+    // |value| = mag + f, 0 <= f < 1, f != 0 iff frac; against a magnitude k
+    __device__ __forceinline__ bool mag_ge(uint64_t k) const { return ovf || mag >= k; }
+    __device__ __forceinline__ bool mag_gt(uint64_t k) const { return ovf || mag > k || (mag == k && frac); }
+    // the parsed value inside the interval (lo, hi as two's complement, flags kRange*)
+    __device__ __forceinline__ bool inside(uint64_t lo, uint64_t hi, uint32_t flags) const
+    {
+        const bool below = neg && (mag != 0ull || frac || ovf);    // -0 and -0.0 are 0
+        const bool lo_neg = (int64_t)lo < 0, hi_neg = (int64_t)hi < 0;
+        const uint64_t alo = lo_neg ? 0ull - lo : lo, ahi = hi_neg ? 0ull - hi : hi;   // |INT64_MIN| = 2^63 fits
+        bool lo_ok, hi_ok;
+        if (!below) {                                              // value >= 0
+            lo_ok = lo_neg || ((flags & kRangeLoOpen) ? mag_gt(alo) : mag_ge(alo));
+            hi_ok = !hi_neg && ((flags & kRangeHiOpen) ? !mag_ge(ahi) : !mag_gt(ahi));
+        } else {                                                   // value = -(mag + f) < 0: a fraction puts it BELOW its truncated integer part
+            lo_ok = lo_neg && ((flags & kRangeLoOpen) ? !mag_ge(alo) : !mag_gt(alo));
+            hi_ok = !hi_neg || ((flags & kRangeHiOpen) ? mag_gt(ahi) : mag_ge(ahi));
+        }
+        return ((flags & kRangeNoLo) || lo_ok) && ((flags & kRangeNoHi) || hi_ok);
+    }
+};
+
+// The number parsed on the leaf that just ended (pending: this lane has one), against every range condition that listened on it.
+__device__ __forceinline__ void decide_number(const NumLane &nl, bool pending, const lds_u64i *conds, uint32_t n_conds, uint64_t leaf_mask, uint64_t &sat,
+                                              bool &num_fail)
+{
+    if (__ballot(pending) == 0ull) return;
+    if (pending && nl.expo) num_fail = true;
+    for (uint32_t c = 0; c < n_conds; ++c) {                             // uniform loop: bounds and flags are LDS broadcasts
+        const lds_u64i *e = conds + c * kMatchCondWords;
+        const uint32_t rec = (uint32_t)e[10];
+        if ((rec & 0xFFu) != 6u) continue;
+        if (pending && !nl.expo && ((leaf_mask >> c) & 1ULL) && nl.inside(e[4], e[5], rec >> 8)) sat |= 1ULL << c;
+    }
+}
+
 // the set of row g: the first s whose rows end behind it (set_first_row[n_sets] = the number of rows > g)
 __device__ __forceinline__ uint32_t row_set_of(const uint32_t *set_first_row, uint32_t n_sets, uint32_t g)
 {
@@ -309,11 +387,12 @@ __device__ __forceinline__ uint32_t row_set_of(const uint32_t *set_first_row, ui
     return lo;
 }
 
-template <bool REGEX, class TOK, bool MANY = false, uint32_t SLOTS = kRxActive, bool WIDE = false, bool SUB = false>
+template <bool REGEX, class TOK, bool MANY = false, uint32_t SLOTS = kRxActive, bool WIDE = false, bool SUB = false, bool RANGE = false>
 __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs &x, const TOK &tk, const MatchManyArgs &m = MatchManyArgs{},
                                                 const MatchWideArgs &wd = MatchWideArgs{}, const SubArgs &sb = SubArgs{})
 {
     static_assert(!(MANY && WIDE), "the storing walker evaluates no program");
+    static_assert(!(RANGE && (REGEX || SUB || WIDE)), "range conditions: the plain single and batched walkers only");
     constexpr uint32_t kSubBase = WIDE ? kMatchWideLdsBytes : MANY ? kMatchManySubBase : kMatchLdsBytes;   // the needle table sits behind the instance's own LDS
     constexpr uint32_t kProgBytes = WIDE ? 0u : MANY ? kMatchManyProgBytes : kMatchMaxOps * 4;
     constexpr uint32_t kRxBase = SUB ? kSubBase + kSubTableBytes : WIDE ? kMatchWideLdsBytes : MANY ? kMatchManyLdsBytes : kMatchLdsBytes;   // the regex blob sits behind the instance's own LDS (and the needle table)
@@ -361,6 +440,8 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
     bool collided = false;       // equal hashes, different fingerprint: only the host's byte compare can decide this row
     typename std::conditional<REGEX, RxLaneT<SLOTS>, RxNone>::type rx;   // the text consumers: the regex lane, the substring lane, or both
     typename std::conditional<SUB, SubLane, RxNone>::type sl;
+    typename std::conditional<RANGE, NumLane, RxNone>::type nl;
+    bool num_fail = false;       // RANGE: an exponent literal on a leaf a range condition listens on: the host decides this row
     bool rx_over = false;        // more regex conditions on one leaf than a lane holds: the host decides this row
     if constexpr (REGEX) {
         rx.tab = (const lds_u8 *)lds_raw + kRxBase;
@@ -376,11 +457,16 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
         sl.lower = tk.lower();
         sl.fail = false;
     }
+    if constexpr (RANGE) {
+        nl.wk = &w;
+        nl.open(false);
+    }
     while (__ballot(res == R_CONTINUE || w.req != Q_NONE) != 0ull) {
         while (__ballot(res == R_CONTINUE && w.req == Q_NONE) != 0ull)
             if (res == R_CONTINUE && w.req == Q_NONE) {
                 if constexpr (REGEX && SUB) { RxSubFeed<SLOTS> both{rx, sl}; res = advance<true>(w, cc, both, tk); }
                 else if constexpr (SUB) res = advance<true>(w, cc, sl, tk);
+                else if constexpr (RANGE) res = advance<true>(w, cc, nl, tk);
                 else res = advance<true>(w, cc, rx, tk);
             }
         const uint32_t q = w.req;
@@ -393,7 +479,9 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
         if (q == Q_WORD) { word_request<TOK>(w); s = w.tok; }
         uint64_t h[4] = {0, 0, 0, 0}, fp = 0;
         if (q != Q_NONE) fp = hs_finish(s, h, w.key);
+        if constexpr (RANGE) decide_number(nl, q == Q_LEAF && nl.on, conds, a.n_conds, leaf_mask, sat, num_fail);   // before leaf_mask forgets who listened
         if (q == Q_LEAF) leaf_mask = 0;
+        bool num_listen = false;                                         // RANGE: a range condition listens on this request's leaf
         if constexpr (REGEX) {
             if (q == Q_LEAF) rx.close();                                 // the previous leaf's text ended before this request
             const bool text = q == Q_LEAF && !(w.st == S_LIT && w.lit == 2u);   // null is never a candidate text
@@ -436,8 +524,17 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
         }
         for (uint32_t c = 0; c < a.n_conds; ++c) {                       // uniform loop: the conditions come from LDS broadcasts
             const lds_u64i *e = conds + c * kMatchCondWords;
-            const uint32_t kind = SUB ? ((uint32_t)e[10] & 0xFFu) : (uint32_t)e[10];   // 0 Field, 1 Token, 2 FieldToken
+            const uint32_t kind = (SUB || RANGE) ? ((uint32_t)e[10] & 0xFFu) : (uint32_t)e[10];   // 0 Field, 1 Token, 2 FieldToken
             if (REGEX && kind == 3u) continue;                           // FieldRegex: the DFAs above
+            if constexpr (RANGE) {
+                if (kind == 6u) {                                        // FieldRange: marked like FieldToken, decided by NumLane; e[4], e[5] hold bounds, no token
+                    const bool heq = q == Q_LEAF && e[0] == h[0] && e[1] == h[1] && e[2] == h[2] && e[3] == h[3];
+                    const bool eq = heq && e[8] == fp;
+                    collided |= heq && !eq;
+                    if (eq) { leaf_mask |= 1ULL << c; num_listen = true; }
+                    continue;
+                }
+            }
             if constexpr (SUB) {
                 if (kind >= 4u) {                                        // Substring: SubLane decides; FieldSubstring: on the leaves of its own path
                     if (kind == 5u) {
@@ -466,6 +563,13 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
                 if (eq && (kind == 1u || (leaf_mask & bit))) sat |= bit; // Token anywhere; FieldToken only under its own path
             }
         }
+        if constexpr (RANGE) {
+            if (q == Q_LEAF) nl.open(w.st == S_NUM && num_listen);       // the literal's first byte is fed after this request
+        }
+    }
+    if constexpr (RANGE) {
+        decide_number(nl, nl.on, conds, a.n_conds, leaf_mask, sat, num_fail);             // the row's last number
+        if (num_fail && res == R_DONE) res = R_FAIL;
     }
     if constexpr (REGEX) {
         rx.close();
@@ -633,6 +737,33 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_substr
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_substr_gram(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchManyArgs m, const TokSpec t)
 {
     match_rows_body<true, TokGramP, true, kRxManyActive, false, true>(a, x, TokGramP(t), m, MatchWideArgs{}, sb);
+}
+
+// Field / Token / FieldToken and FieldRange conditions (bsg_match_rows_range / bsg_match_rows_many_range); dynamic LDS kMatchLdsBytes /
+// kMatchManyLdsBytes, as the plain walkers
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_range(const MatchArgs a)
+{
+    match_rows_body<false, TokDefault, false, kRxActive, false, false, true>(a, RxArgs{}, TokDefault{});
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_range_tok(const MatchArgs a, const TokSpec t)
+{
+    match_rows_body<false, TokSpecP, false, kRxActive, false, false, true>(a, RxArgs{}, TokSpecP{t});
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_range_gram(const MatchArgs a, const TokSpec t)
+{
+    match_rows_body<false, TokGramP, false, kRxActive, false, false, true>(a, RxArgs{}, TokGramP(t));
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_range(const MatchArgs a, const MatchManyArgs m)
+{
+    match_rows_body<false, TokDefault, true, kRxActive, false, false, true>(a, RxArgs{}, TokDefault{}, m);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_range_tok(const MatchArgs a, const MatchManyArgs m, const TokSpec t)
+{
+    match_rows_body<false, TokSpecP, true, kRxActive, false, false, true>(a, RxArgs{}, TokSpecP{t}, m);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_range_gram(const MatchArgs a, const MatchManyArgs m, const TokSpec t)
+{
+    match_rows_body<false, TokGramP, true, kRxActive, false, false, true>(a, RxArgs{}, TokGramP(t), m);
 }
 
 // the storing walker (bsg_match_rows_wide): plain / regex x default / spec / n-gram tokenizer; dynamic LDS kMatchWideLdsBytes (+ the table

@@ -16,6 +16,10 @@
 // bsg_match_rows_wide_substr(_rows) is the wide call with kinds 0-5 in its table: a table with a substring condition gets the needle tables
 // (and its blob under kRxWideSubLdsCap) and WidePart launches k_match_rows_store_substr* / k_match_rows_store_regex_substr*; a table
 // without one is bsg_match_rows_wide(_rows)'s, its walkers and its cap.
+// bsg_match_rows_range / bsg_match_rows_many_range are the single and the batched call with FieldRange conditions (kind 6) in the table:
+// build_range_table checks each condition's 17 bytes and moves its flags into the kind word, the part writes the bounds over the token
+// slots of the condition's hashes once the device has hashed the table, and PlanePart launches the range instances of the walker.  A
+// table without a range condition is bsg_match_rows_tok's / bsg_match_rows_many's: its walkers and its bits.
 // bsg_match_rows_lookup(_rows) is the wide call with another Family and a LookupPlan beside its WidePlan: WidePart then sizes the
 // flags at W words per row, places the lookup tables (host/lookup_plan.hpp) from the hashes the device made, and launches
 // match_lookup.hip.h's walker and evaluator in place of match.hip.h's.  bsg_match_rows_lookup_regex(_rows) is that call with FieldRegex
@@ -98,6 +102,11 @@ struct MatchCall {
     bool substr = false;                   // build_sub_tables: the call holds the substring walkers' tables
     bsh::NeedlePack sub;                   // ... M, START, ANY
     std::vector<uint32_t> sub_kinds;       // ... and cond_kinds with word | end bit of a substring condition's needle (match.hip.h SubLane)
+    bool range_call = false;               // the call is bsg_match_rows_range / bsg_match_rows_many_range (the name in traces)
+    bool range = false;                    // build_range_table: the table holds a FieldRange condition, the range walkers run
+    std::vector<uint32_t> range_conds;     // ... the conditions of kind 6,
+    std::vector<uint64_t> range_bounds;    // ... lo and hi of each (two's complement), in that order
+    std::vector<uint32_t> range_kinds;     // ... and cond_kinds with a range condition's flags << 8 (match.hip.h NumLane)
     bsg::TokSpec spec{};                   // tok_spec
     bool default_tok = true;
     const bsg::TokSpec *tok() const { return default_tok ? nullptr : &spec; }
@@ -208,6 +217,33 @@ int32_t build_sub_tables(MatchCall &mc)
     return BSG_OK;
 }
 
+// The bounds of a call's FieldRange conditions: entry 2c + 1 is lo (int64, little-endian), hi (the same) and one flag byte
+// (BSG_RANGE_*).  BSG_E_INVALID, naming the condition, for another length or a flag bit above 3.  A table without a kind-6 condition
+// leaves the call as it is; else mc.cond_kinds then points at the kinds with each condition's flags.
+int32_t build_range_table(MatchCall &mc)
+{
+    for (uint32_t c = 0; c < mc.n_conds; ++c) {
+        if (mc.cond_kinds[c] != BSG_KIND_FIELD_RANGE) continue;
+        const uint32_t at = mc.cond_off[2 * c + 1], len = mc.cond_off[2 * c + 2] - at;
+        if (len != BSG_RANGE_ENTRY_BYTES) return fail(BSG_E_INVALID, "condition %u: a range entry is %u bytes (lo, hi, flags), not %u", c, BSG_RANGE_ENTRY_BYTES, len);
+        const uint8_t *b = mc.cond_bytes + at;
+        if (b[16] > 15u) return fail(BSG_E_INVALID, "condition %u: range flags 0x%02x (bits 0-3 are defined)", c, b[16]);
+        uint64_t lo = 0, hi = 0;
+        for (uint32_t i = 0; i < 8; ++i) { lo |= (uint64_t)b[i] << (8 * i); hi |= (uint64_t)b[8 + i] << (8 * i); }
+        if (!mc.range) mc.range_kinds.assign(mc.cond_kinds, mc.cond_kinds + mc.n_conds);
+        mc.range = true;
+        mc.range_kinds[c] |= (uint32_t)b[16] << 8;
+        mc.range_conds.push_back(c);
+        mc.range_bounds.push_back(lo);
+        mc.range_bounds.push_back(hi);
+    }
+    if (mc.range) mc.cond_kinds = mc.range_kinds.data();
+    return BSG_OK;
+}
+static_assert(BSG_RANGE_NO_LO == bsg::kRangeNoLo && BSG_RANGE_NO_HI == bsg::kRangeNoHi && BSG_RANGE_LO_OPEN == bsg::kRangeLoOpen &&
+                  BSG_RANGE_HI_OPEN == bsg::kRangeHiOpen && BSG_KIND_FIELD_RANGE == 6u,
+              "bloomgpu.h states the range walkers' kind and flags");
+
 // ---- the twenty-four walkers: (single / many / wide / lookup) x (regex) x (default tokenizer / spec / spec with an n-gram width) ----
 // E: the mode's own argument struct (none, MatchManyArgs, MatchWideArgs, MatchLookupArgs).  Dynamic LDS: the mode's base (the lookup
 // walkers': what the launch's tables take) plus the regex blob's bytes (a call without regex conditions has no blob).
@@ -229,6 +265,11 @@ constexpr Walkers<bsg::MatchWideArgs> kWideWalkers{bsg::k_match_rows_store, bsg:
 constexpr Walkers<bsg::MatchLookupArgs> kLookupWalkers{bsg::k_match_rows_lookup, bsg::k_match_rows_lookup_tok, bsg::k_match_rows_lookup_regex,
                                                        bsg::k_match_rows_lookup_regex_tok, bsg::k_match_rows_lookup_gram,
                                                        bsg::k_match_rows_lookup_regex_gram};   // regex: bsg_match_rows_lookup_regex(_rows) only
+
+// ... the six with the number consumer (bsg_match_rows_range / bsg_match_rows_many_range: no FieldRegex condition reaches them)
+constexpr Walkers<> kSingleRangeWalkers{bsg::k_match_rows_range, bsg::k_match_rows_range_tok, nullptr, nullptr, bsg::k_match_rows_range_gram, nullptr};
+constexpr Walkers<bsg::MatchManyArgs> kManyRangeWalkers{bsg::k_match_rows_many_range, bsg::k_match_rows_many_range_tok, nullptr, nullptr,
+                                                        bsg::k_match_rows_many_range_gram, nullptr};
 
 // ... and the nine with the substring consumer: (single / many / wide) x (default tokenizer / spec / spec with an n-gram width)
 template <class... E>
@@ -305,6 +346,7 @@ struct PlanePart {
 
     const char *tag() const
     {
+        if (mc.range_call) return many ? "bsg_match_rows_many_range" : "bsg_match_rows_range";
         if (mc.rx_sub) return many ? "bsg_match_rows_many_regex_substr" : "bsg_match_rows_regex_substr";
         if (mc.substr) return many ? "bsg_match_rows_many_substr" : "bsg_match_rows_substr";
         return many ? (mc.n_rx ? "bsg_match_rows_many_regex" : "bsg_match_rows_many") : "bsg_match_rows";
@@ -354,6 +396,12 @@ struct PlanePart {
                                         p.d.stream, k0, k1, a, p.sub, mc.tok(), bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
             else launch_sub_walker(bsg::k_match_rows_substr, bsg::k_match_rows_substr_tok, bsg::k_match_rows_substr_gram, bsg::kMatchSubLdsBytes, p.d.stream, k0, k1, a,
                                    p.sub, mc.tok());
+            return;
+        }
+        if (mc.range) {                                // the same LDS as the plain walkers: the bounds sit in the conditions' records
+            assert(!mc.n_rx);
+            if (many) launch_walker(kManyRangeWalkers, bsg::kMatchManyLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok(), bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
+            else launch_walker(kSingleRangeWalkers, bsg::kMatchLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok());
             return;
         }
         if (many) launch_walker(kManyWalkers, bsg::kMatchManyLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok(), bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
@@ -636,6 +684,9 @@ int32_t match_part(bsg_ctx *ctx, Device &d, const MatchCall &mc, uint32_t r0, ui
         hipLaunchKernelGGL(bsg::k_hash_fp_entries, dim3((2 * n_conds + 255) / 256), dim3(256), 0, d.stream, (const uint8_t *)d_cbytes,
                            (const uint32_t *)d_coff, 2 * n_conds, d_ch, d_cfp, ctx->fp_key);
         HIP_TRY(hipGetLastError());
+        // a FieldRange condition has no token: lo and hi go where the hashes of its 17 bytes were written (the walkers' e[4], e[5])
+        for (size_t i = 0; i < mc.range_conds.size(); ++i)
+            HIP_TRY(hipMemcpyAsync(d_ch + ((size_t)2 * mc.range_conds[i] + 1) * 4, mc.range_bounds.data() + 2 * i, 16, hipMemcpyHostToDevice, d.stream));
     }
     if (!mc.prog.empty()) HIP_TRY(hipMemcpyAsync(p.d_prog, mc.prog.data(), mc.prog.size() * 4, hipMemcpyHostToDevice, d.stream));
     if (p.d_poff) HIP_TRY(hipMemcpyAsync(p.d_poff, mc.prog_off.data(), mc.prog_off.size() * 4, hipMemcpyHostToDevice, d.stream));
@@ -724,6 +775,9 @@ int32_t match_fan_out(bsg_ctx *ctx, const MatchCall &mc, const uint32_t *set_fir
     return match_fan_out(ctx, mc, set_first_row, n_sets, part, [] { return (int32_t)BSG_OK; });
 }
 
+// bsg_match_rows_range / bsg_match_rows_many_range: kinds 0, 1, 2 and 6
+constexpr const char *kNoTextWithRange = "condition %u: kind %u (the range calls hold Field, Token, FieldToken and FieldRange conditions)";
+inline bool range_refuses(uint32_t kind) { return kind >= BSG_KIND_FIELD_REGEX && kind <= BSG_KIND_FIELD_SUBSTRING; }
 constexpr const char *kNoRegexWithSubstr = "condition %u: a FieldRegex condition (regex and substring conditions share bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr)";
 
 // which sides a table of bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr holds
@@ -758,10 +812,12 @@ int32_t match_rows_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, u
     if (int32_t rc = begin_match_call(mc, kSingleFamily, tok_in, prog_ops, prog_off, 1)) return rc;
     for (uint32_t c = 0; c < mc.n_conds; ++c) {
         if (substr && mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX) return fail(BSG_E_UNSUPPORTED, kNoRegexWithSubstr, c);
+        if (mc.range_call && range_refuses(mc.cond_kinds[c])) return fail(BSG_E_UNSUPPORTED, kNoTextWithRange, c, mc.cond_kinds[c]);
         if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
     }
     if (int32_t rc = lower_programs(mc, kSingleFamily, prog_ops, prog_off, 1)) return rc;
-    if (mc.rx_sub) {
+    if (mc.range_call) { if (int32_t rc = build_range_table(mc)) return rc; }
+    else if (mc.rx_sub) {
         const TableSides t = table_sides(mc);
         if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, t.sub ? bsg::kRxSubLdsCap : bsg::kRxLdsCap)) return rc;
         if (t.sub) if (int32_t rc = build_sub_tables(mc)) return rc;
@@ -782,6 +838,7 @@ int32_t match_rows_many_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
     const uint32_t n_rows = mc.n_rows;
     for (uint32_t c = 0; c < mc.n_conds; ++c) {
         if (substr && mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX) return fail(BSG_E_UNSUPPORTED, kNoRegexWithSubstr, c);
+        if (mc.range_call && range_refuses(mc.cond_kinds[c])) return fail(BSG_E_UNSUPPORTED, kNoTextWithRange, c, mc.cond_kinds[c]);
         if (mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX && max_kind < BSG_KIND_FIELD_REGEX)
             return fail(BSG_E_UNSUPPORTED, "condition %u: FieldRegex conditions are not matched by the batched call (use bsg_match_rows_regex)", c);
         if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
@@ -799,7 +856,8 @@ int32_t match_rows_many_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
     const ManyPlan plan{set_first_row, query_mask_of_set, n_sets, n_queries, ((size_t)n_rows + 63) / 64};
     if (int32_t rc = lower_programs(mc, kManyFamily, prog_ops, prog_off, n_queries)) return rc;
     // the regex conditions' tables, each with the queries that use it (a table without any: exactly bsg_match_rows_many's kernels)
-    if (mc.rx_sub) {
+    if (mc.range_call) { if (int32_t rc = build_range_table(mc)) return rc; }
+    else if (mc.rx_sub) {
         const TableSides t = table_sides(mc);
         if (n_queries) {
             const std::vector<uint64_t> users = bsh_rxg::user_masks(prog_ops, prog_off, n_queries, mc.n_conds);
@@ -1121,6 +1179,29 @@ int32_t bsg_match_rows_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t 
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
     return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_SUBSTRING, tok, true);
+}
+
+int32_t bsg_match_rows_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                             const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                             const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
+                             uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    mc.range_call = true;
+    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_RANGE, tok);
+}
+
+int32_t bsg_match_rows_many_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                  const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                  const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                  const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets, const bsg_tokenizer *tok,
+                                  uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    mc.range_call = true;
+    return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_RANGE);
 }
 
 int32_t bsg_match_rows_many_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,

@@ -662,6 +662,11 @@ class Context:
         conditions (raw needles; the call folds them under `tokenizer`, None = the default)."""
         return self._match_rows(None, rows, matcher, tokenizer, tok_fn=self.L.bsg_match_rows_substr)
 
+    def match_rows_range(self, rows, matcher, tokenizer=None):
+        """bsg_match_rows_range: as match_rows, and the matcher (query.CompiledRangeQuery) may hold FieldRange conditions.  Rows with an
+        exponent literal on a range field come back as fallback rows (host.match_row_range decides them)."""
+        return self._match_rows(None, rows, matcher, tokenizer, tok_fn=self.L.bsg_match_rows_range)
+
     def match_rows_regex_substr(self, rows, matcher, tokenizer=None):
         """bsg_match_rows_regex_substr: as match_rows_substr, and the matcher (query.CompiledRowSubstringQuery) may hold FieldRegex
         conditions in the same table: one walk of the rows decides both kinds."""
@@ -708,6 +713,10 @@ class Context:
         """bsg_match_rows_many_substr: as match_rows_many, and the batch (query.CompiledSubstringQueryBatch) may hold Substring /
         FieldSubstring conditions."""
         return self._match_rows_many(self.L.bsg_match_rows_many_substr, rows, batch, set_first_row, masks, tokenizer)
+
+    def match_rows_many_range(self, rows, batch, set_first_row=None, masks=None, tokenizer=None):
+        """bsg_match_rows_many_range: as match_rows_many, and the batch (query.CompiledRangeQueryBatch) may hold FieldRange conditions."""
+        return self._match_rows_many(self.L.bsg_match_rows_many_range, rows, batch, set_first_row, masks, tokenizer)
 
     def match_rows_many_regex_substr(self, rows, batch, set_first_row=None, masks=None, tokenizer=None):
         """bsg_match_rows_many_regex_substr: as match_rows_many, and the batch (query.CompiledRowSubstringQueryBatch) may hold FieldRegex,

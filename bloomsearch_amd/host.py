@@ -18,6 +18,7 @@ HOST_EXPORTS = [
     "bsh_entry_sets_union_into", "bsh_entry_sets_counts", "bsh_entry_sets_export_sizes", "bsh_entry_sets_export",
     "bsh_batch_new", "bsh_batch_free", "bsh_batch_add_query", "bsh_batch_sizes", "bsh_batch_export", "bsh_match_row", "bsh_match_row_with", "bsh_prune_query", "bsh_match_row_regex",
     "bsh_substring_terms", "bsh_prune_query_sub", "bsh_match_row_substring",
+    "bsh_match_row_range", "bsh_prune_query_range",
     "bsh_regex_match",
     "bsh_section_encode", "bsh_section_parse", "bsh_crc32c",
     "bse_open", "bse_close", "bse_last_error", "bse_stop", "bse_ingest_rows", "bse_flush", "bse_merge", "bse_query", "bse_query_many",
@@ -64,6 +65,8 @@ def lib():
     L.bsh_substring_terms.argtypes = [C.c_char_p, u64, C.POINTER(_lib.Tokenizer), pp, pu64]
     L.bsh_prune_query_sub.argtypes = [C.c_char_p, u64, C.c_char_p, u64, C.c_char_p, u64, C.POINTER(_lib.Tokenizer), pp, pu64]
     L.bsh_match_row_substring.argtypes = [C.c_char_p, u64, C.c_char_p, u64, C.POINTER(_lib.Tokenizer)]
+    L.bsh_match_row_range.argtypes = [C.c_char_p, u64, C.c_char_p, u64]
+    L.bsh_prune_query_range.argtypes = [C.c_char_p, u64, C.c_char_p, u64, C.c_char_p, u64, C.c_char_p, u64, C.POINTER(_lib.Tokenizer), pp, pu64]
     L.bsh_section_encode.argtypes = [C.POINTER(vp), pu64, pu64, pp, pu64]
     L.bsh_section_parse.argtypes = [C.c_char_p, u64, pu64, pu64, C.POINTER(vp)]
     L.bsh_crc32c.argtypes = [C.c_char_p, u64]; L.bsh_crc32c.restype = u32
@@ -272,6 +275,27 @@ def match_row_substring(substring_expression, row: bytes, tokenizer=None) -> boo
     return bool(rc)
 
 
+def match_row_range(range_expression, row: bytes) -> bool:
+    """bsh_match_row_range: the exact range test of one row (every JSON number literal, exponents included)."""
+    L = lib()
+    s = json.dumps(range_expression).encode()
+    rc = L.bsh_match_row_range(s, len(s), row, len(row))
+    if rc < 0:
+        raise HostError(rc)
+    return bool(rc)
+
+
+def prune_query_range(bloom_expression, regex_expression, substring_expression, range_expression, tokenizer=None):
+    """bsh_prune_query_range: And(bloom, regex field guard, substring guard, range guard) -> expression dict or None."""
+    L = lib()
+    b, r, s, g = (json.dumps(e).encode() for e in (bloom_expression, regex_expression, substring_expression, range_expression))
+    p, n = C.c_void_p(), C.c_uint64()
+    rc = L.bsh_prune_query_range(b, len(b), r, len(r), s, len(s), g, len(g), c_spec(tokenizer), C.byref(p), C.byref(n))
+    if rc:
+        raise HostError(rc)
+    return json.loads(_take(L, p, n))
+
+
 def crc32c(data: bytes) -> int:
     return int(lib().bsh_crc32c(data, len(data)))
 
@@ -350,23 +374,27 @@ class Engine:
     def stop(self):
         self._check(self.L.bse_stop(self.h))
 
-    def query(self, bloom_expression=None, regex_expression=None, substring_expression=None):
+    def query(self, bloom_expression=None, regex_expression=None, substring_expression=None, range_expression=None):
         d = {"Bloom": {"Expression": bloom_expression} if bloom_expression is not None else None,
              "Regex": {"Expression": regex_expression} if regex_expression is not None else None}
         if substring_expression is not None:
             d["Substring"] = substring_expression
+        if range_expression is not None:
+            d["Range"] = range_expression
         q = json.dumps(d).encode()
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self.L.bse_query(self.h, q, len(q), C.byref(p), C.byref(n)))
         return json.loads(_take(self.L, p, n))
 
-    def query_many(self, bloom_expressions, regex_expressions=None, substring_expressions=None):
+    def query_many(self, bloom_expressions, regex_expressions=None, substring_expressions=None, range_expressions=None):
         """bse_query_many: one pass for a batch of queries -> list of query()'s results, element i for bloom_expressions[i]
-        (and regex_expressions[i] / substring_expressions[i], where given)."""
+        (and regex_expressions[i] / substring_expressions[i] / range_expressions[i], where given)."""
         rx = list(regex_expressions) if regex_expressions is not None else [None] * len(bloom_expressions)
         sx = list(substring_expressions) if substring_expressions is not None else [None] * len(bloom_expressions)
+        gx = list(range_expressions) if range_expressions is not None else [None] * len(bloom_expressions)
         q = json.dumps([dict({"Bloom": {"Expression": b} if b is not None else None, "Regex": {"Expression": r} if r is not None else None},
-                             **({"Substring": s} if s is not None else {})) for b, r, s in zip(bloom_expressions, rx, sx)]).encode()
+                             **({"Substring": s} if s is not None else {}), **({"Range": g} if g is not None else {}))
+                        for b, r, s, g in zip(bloom_expressions, rx, sx, gx)]).encode()
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self.L.bse_query_many(self.h, q, len(q), C.byref(p), C.byref(n)))
         return json.loads(_take(self.L, p, n))

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import KIND_FIELD, KIND_FIELD_REGEX, KIND_FIELD_SUBSTRING, KIND_FIELD_TOKEN, KIND_SUBSTRING, KIND_TOKEN, OP_AND, OP_FALSE, OP_OR, OP_TERM, OP_TRUE, op
+from ._lib import RANGE_HI_OPEN, RANGE_LO_OPEN, RANGE_NO_HI, RANGE_NO_LO, KIND_FIELD, KIND_FIELD_RANGE, KIND_FIELD_REGEX, KIND_FIELD_SUBSTRING, KIND_FIELD_TOKEN, KIND_SUBSTRING, KIND_TOKEN, OP_AND, OP_FALSE, OP_OR, OP_TERM, OP_TRUE, op
 
 BLOOM_FIELD, BLOOM_TOKEN, BLOOM_FIELD_TOKEN = "FIELD", "TOKEN", "FIELD_TOKEN"
 EXPR_CONDITION, EXPR_AND, EXPR_OR = "CONDITION", "AND", "OR"
@@ -158,6 +158,95 @@ def prune_bloom_query(bloom_expression, regex_expression, substring_expression=N
     """pruneBloomQuery (query_exec.go:220), with the substring tree's guard as a third side."""
     two = and_bloom_queries(bloom_expression, regex_field_guard_bloom_query(regex_expression))
     return and_bloom_queries(two, substring_guard_bloom_query(substring_expression, tokenizer))
+
+
+# ---- range query tree and its bloom guard (bloomgpu.h "Range conditions"; host/range.hpp is the implementation) ----
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def FieldRange(field: str, lo=None, hi=None, lo_open: bool = False, hi_open: bool = False) -> dict:
+    """Some NUMBER leaf whose path equals `field` has a value inside the interval: int64 bounds, None = unbounded, each closed
+    unless lo_open / hi_open.  The value is the literal's exact decimal value."""
+    for b in (lo, hi):
+        if b is not None and not (isinstance(b, int) and not isinstance(b, bool) and INT64_MIN <= b <= INT64_MAX):
+            raise ValueError(f"range bound {b!r}: an int64 or None")
+    c = {"Field": field}
+    if lo is not None:
+        c["Lo"] = lo
+    if hi is not None:
+        c["Hi"] = hi
+    if lo_open:
+        c["LoOpen"] = True
+    if hi_open:
+        c["HiOpen"] = True
+    return {"ExpressionType": "CONDITION", "Condition": c}
+
+
+def RangeAnd(*expressions) -> dict:
+    return {"ExpressionType": "AND", "Children": _flatten_regex(expressions, "AND")}
+
+
+def RangeOr(*expressions) -> dict:
+    return {"ExpressionType": "OR", "Children": _flatten_regex(expressions, "OR")}
+
+
+def numeric_condition_range(field: str, condition: dict) -> dict:
+    """The reference's NumericCondition ({"Operator", "Value" | "Values" | "Min", "Max"}, query.go:37-44) as a range tree over the
+    number leaves of `field`: EQ, GT, GTE, LT, LTE and BETWEEN are one interval; NE and NOT_BETWEEN the Or of the two outside
+    intervals; IN an Or of points; NOT_IN the Or of the gaps between the sorted points (open at both points, so 5.5 lies in the gap
+    between 5 and 6).  The tree holds when SOME leaf's value satisfies the operator."""
+    o = condition.get("Operator")
+    v, lo, hi = condition.get("Value", 0), condition.get("Min", 0), condition.get("Max", 0)
+    if o == "EQ":
+        return FieldRange(field, v, v)
+    if o == "GT":
+        return FieldRange(field, v, None, lo_open=True)
+    if o == "GTE":
+        return FieldRange(field, v, None)
+    if o == "LT":
+        return FieldRange(field, None, v, hi_open=True)
+    if o == "LTE":
+        return FieldRange(field, None, v)
+    if o == "BETWEEN":
+        return FieldRange(field, lo, hi)
+    if o == "NE":
+        return RangeOr(FieldRange(field, None, v, hi_open=True), FieldRange(field, v, None, lo_open=True))
+    if o == "NOT_BETWEEN":
+        return RangeOr(FieldRange(field, None, lo, hi_open=True), FieldRange(field, hi, None, lo_open=True))
+    if o == "IN":
+        return RangeOr(*[FieldRange(field, p, p) for p in condition.get("Values") or []])
+    if o == "NOT_IN":
+        pts = sorted(set(condition.get("Values") or []))
+        edges = [None] + pts + [None]
+        return RangeOr(*[FieldRange(field, a, b, lo_open=a is not None, hi_open=b is not None) for a, b in zip(edges, edges[1:])])
+    raise ValueError(f"numeric operator {o!r}")
+
+
+def range_entry(condition: dict) -> bytes:
+    """Entry 2i + 1 of a KIND_FIELD_RANGE condition: lo, hi (int64, little-endian) and the flag byte."""
+    lo, hi = condition.get("Lo"), condition.get("Hi")
+    flags = (RANGE_NO_LO if lo is None else 0) | (RANGE_NO_HI if hi is None else 0) | \
+            (RANGE_LO_OPEN if condition.get("LoOpen") else 0) | (RANGE_HI_OPEN if condition.get("HiOpen") else 0)
+    return (lo or 0).to_bytes(8, "little", signed=True) + (hi or 0).to_bytes(8, "little", signed=True) + bytes([flags])
+
+
+def range_guard_bloom_query(range_expression):
+    """The tree with every condition as Field(field); the nil condition is dropped from an And and kept in an Or (NIL_CONDITION), as
+    in the substring guard.  None = nil."""
+    e = range_expression
+    if e is None:
+        return None
+    t = e.get("ExpressionType")
+    if t == "CONDITION":
+        c = e.get("Condition")
+        return None if c is None else Field(c.get("Field", ""))
+    if t in ("AND", "OR"):
+        kids = [range_guard_bloom_query(c) for c in e.get("Children") or []]
+        if t == "AND":
+            kept = [k for k in kids if k is not None]
+            return None if kids and not kept else {"ExpressionType": EXPR_AND, "Children": kept}
+        return {"ExpressionType": EXPR_OR, "Children": [NIL_CONDITION if k is None else k for k in kids]}
+    return None
 
 
 def make_field_token_key(field: str, token: str) -> str:
@@ -429,6 +518,58 @@ class CompiledSubstringQuery(CompiledMatcher):
             self.prog_ops.append(op(OP_AND if et == EXPR_AND else OP_OR, len(kids)))
         else:
             self.prog_ops.append(op(OP_FALSE))
+
+
+class CompiledRangeQuery(CompiledMatcher):
+    """And(bloom root | TRUE, range root) for bsg_match_rows_range: the bloom side lowered as CompiledMatcher does, the range side by
+    the regex tree's rules (a nil expression or condition is TRUE, an empty field FALSE, an empty Or FALSE, an empty And TRUE).  A
+    FieldRange condition keeps its field in `fields` and range_entry's 17 bytes in `tokens` (entry 2i + 1)."""
+
+    def __init__(self, bloom_expression, range_expression):
+        super().__init__(None)
+        if bloom_expression is None:
+            self.prog_ops.append(op(OP_TRUE))
+        else:
+            self._emit(bloom_expression)
+        self._emit_range(range_expression)
+        self.prog_ops.append(op(OP_AND, 2))
+
+    def _emit_range(self, e) -> None:
+        if e is None:
+            self.prog_ops.append(op(OP_TRUE))
+            return
+        et = e.get("ExpressionType")
+        if et == EXPR_CONDITION:
+            cond = e.get("Condition")
+            if cond is None:
+                self.prog_ops.append(op(OP_TRUE))
+            elif cond.get("Field", "") == "":
+                self.prog_ops.append(op(OP_FALSE))
+            else:
+                self.prog_ops.append(op(OP_TERM, len(self.kinds)))
+                self.kinds.append(KIND_FIELD_RANGE)
+                self.fields.append(cond["Field"].encode("utf-8", "surrogatepass"))
+                self.tokens.append(range_entry(cond))
+        elif et in (EXPR_AND, EXPR_OR):
+            kids = e.get("Children") or []
+            if not kids:
+                self.prog_ops.append(op(OP_TRUE if et == EXPR_AND else OP_FALSE))
+                return
+            for c in kids:
+                self._emit_range(c)
+            self.prog_ops.append(op(OP_AND if et == EXPR_AND else OP_OR, len(kids)))
+        else:
+            self.prog_ops.append(op(OP_FALSE))
+
+
+class CompiledRangeQueryBatch(CompiledMatcherBatch):
+    """A batch of (bloom expression, range expression) pairs for one bsg_match_rows_many_range call: query q's program is
+    CompiledRangeQuery's with its condition indices remapped into ONE table of distinct conditions (a range condition is distinct by
+    its field, bounds and flags)."""
+
+    @staticmethod
+    def _compile(pair):
+        return CompiledRangeQuery(*pair)
 
 
 class CompiledSubstringQueryBatch(CompiledMatcherBatch):

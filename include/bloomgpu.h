@@ -54,6 +54,12 @@ extern "C" {
 #define BSG_KIND_FIELD_REGEX  3u   /* row matcher only (bsg_match_rows_regex): entry 2i = field, 2i + 1 = pattern */
 #define BSG_KIND_SUBSTRING        4u   /* bsg_match_rows_substr / _many_substr / _regex_substr / _many_regex_substr only: entry 2i empty, 2i + 1 = the needle */
 #define BSG_KIND_FIELD_SUBSTRING  5u   /* ... entry 2i = the field, 2i + 1 = the needle */
+#define BSG_KIND_FIELD_RANGE      6u   /* bsg_match_rows_range / _many_range only: entry 2i = the field, 2i + 1 = lo, hi, flags ("Range conditions") */
+#define BSG_RANGE_ENTRY_BYTES 17u      /* lo (int64, little-endian), hi (the same), one byte of BSG_RANGE_* */
+#define BSG_RANGE_NO_LO   1u           /* no lower bound (lo is ignored) */
+#define BSG_RANGE_NO_HI   2u           /* no upper bound (hi is ignored) */
+#define BSG_RANGE_LO_OPEN 4u           /* value > lo instead of value >= lo */
+#define BSG_RANGE_HI_OPEN 8u           /* value < hi instead of value <= hi */
 
 /* ---- query program opcodes: op = (opcode << 28) | arg, postfix order ----
  * TERM i : push TestString(term i) against the block's filter of term i's kind;
@@ -484,7 +490,22 @@ BSG_API int32_t bsg_host_unregister(bsg_ctx *ctx, void *ptr);
  * Field(field) or, for Substring, the always-true nil condition.  A partial word shorter than n never becomes a term: in a row it
  * is part of a longer word, whose set holds that word's windows and not the needle.
  * The AND of the terms is a candidate test only (the windows may sit in different words); bsg_match_rows_substr and
- * bsg_match_rows_many_substr decide exactly. */
+ * bsg_match_rows_many_substr decide exactly.
+ *
+ * Range conditions.  FieldRange(field, lo, hi, flags) (BSG_KIND_FIELD_RANGE; entry 2i + 1 is exactly BSG_RANGE_ENTRY_BYTES bytes: any
+ * other length, or a flag bit above 3, is BSG_E_INVALID naming the condition) holds for a row that has a NUMBER leaf whose path
+ * EQUALS the field (FieldToken's leaf rule, not FieldRegex's "at or beneath"; an array's elements lie under the array's path and each
+ * is a leaf of its own) and whose value lies inside the interval.  A bound is closed, open (BSG_RANGE_LO_OPEN / _HI_OPEN) or absent
+ * (BSG_RANGE_NO_LO / _NO_HI); nothing else tells intervals apart, and lo > hi is valid and never holds.
+ * The value is the exact decimal value of the raw JSON literal: there is no float64 round trip (9007199254740993 is itself, 5.000
+ * equals 5, 5.0001 is greater than 5), and a literal of any length is compared exactly with the int64 bounds.  Strings never hold
+ * ("5" included), nor do true, false and null; an empty field never holds; a leaf without a path (a scalar at the root, a top-level
+ * key "") is no candidate.
+ * A literal with an exponent part (1e3, 1E+21, 2.5e-7) is not decided on the device: on a leaf whose path equals the field of ANY
+ * range condition of the table it makes the row a fallback row (bloomsearch_host.h bsh_match_row_range decides every literal
+ * exactly); on any other leaf it changes nothing.
+ * The probe side prunes a range condition with Field(field) — a leaf's own path is a field-existence entry of the filters — under
+ * the rules of the substring guard (bsh_prune_query_range): a nil condition is dropped from an And and kept in an Or. */
 #define BSG_TOK_UNICODE_SPACE 1u   /* runes >= 0x80 with unicode.IsSpace end a word too */
 #define BSG_TOK_LOWER         2u   /* the text is lower-cased first (unicode.ToLower per rune, as strings.ToLower) */
 #define BSG_TOK_NGRAM_SHIFT   8u   /* flags bits 8-10: the n-gram width, 0 (none), 2, 3 or 4 */
@@ -688,6 +709,21 @@ BSG_API int32_t bsg_match_rows_substr(bsg_ctx *ctx, const uint8_t *rows, const u
                                       const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
                                       uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                       uint32_t *out_n_fallback);
+/* bsg_match_rows_tok with range conditions in the table (kinds 0, 1, 2 and BSG_KIND_FIELD_RANGE; the semantics under "Range
+ * conditions" above).  The walker's fourth text consumer parses each number leaf a range condition listens on once, whatever the
+ * number of conditions on it, and compares in integer arithmetic; the bounds travel in the conditions' own records (no LDS is added:
+ * k_match_rows_range* keep k_match_rows*'s bytes and workgroups per CU).  A table without a range condition runs bsg_match_rows_tok's
+ * kernels and returns its bits.  Same arguments, limits, sharding, chunked upload, fallback rows and bsg_last_match_ms as
+ * bsg_match_rows_tok; a row with an exponent literal on a range condition's leaf is a fallback row too, as is one where a leaf's
+ * path has the hashes of a range condition's field but not its fingerprint.
+ * A condition of kind 3, 4 or 5 is BSG_E_UNSUPPORTED here (the condition named): range conditions do not share a table with the
+ * regex and substring consumers yet.  Every entry point but this one and bsg_match_rows_many_range answers kind 6 with BSG_E_INVALID
+ * (unknown kind). */
+BSG_API int32_t bsg_match_rows_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                     const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                     const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
+                                     uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                     uint32_t *out_n_fallback);
 /* A batch of queries matched in ONE upload and ONE walk of the rows (k_match_rows_many): n_queries <= 64 expressions over ONE
  * table of distinct Field / Token / FieldToken conditions (packed as for bsg_match_rows), prog_ops / prog_off[n_queries + 1]
  * the public postfix programs over condition indices laid out as for bsg_batch_create (an empty program = nil expression =
@@ -722,6 +758,17 @@ BSG_API int32_t bsg_match_rows_many_substr(bsg_ctx *ctx, const uint8_t *rows, co
                                            const bsg_tokenizer *tok,
                                            uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                            uint32_t *out_n_fallback);
+/* bsg_match_rows_many with range conditions in the table, as bsg_match_rows_range documents them: the same nineteen arguments, set /
+ * mask semantics, plane layout and limits as bsg_match_rows_many; plane q = what bsg_match_rows_range returns for program q alone,
+ * ANDed with the set mask.  An exponent literal on the leaf of ANY range condition of the table makes a walked row a fallback row,
+ * whatever the mask bits of the queries that use the condition; a row with mask 0 is never walked and never a fallback row. */
+BSG_API int32_t bsg_match_rows_many_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                          const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                          const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                          const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets,
+                                          const bsg_tokenizer *tok,
+                                          uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                          uint32_t *out_n_fallback);
 /* FieldRegex AND substring conditions in one table, decided in ONE walk of the rows (kinds 0-5; k_match_rows_regex_substr*): the
  * arguments of bsg_match_rows_substr, a FieldRegex condition as bsg_match_rows_regex documents it, a substring condition as
  * bsg_match_rows_substr does.  Every candidate text goes to both consumers: the DFAs read the raw bytes, the needles the folded ones.

@@ -97,6 +97,18 @@ BSG_API int32_t bsh_prune_query_sub(const char *bloom_json, uint64_t bloom_len, 
  * valid JSON: 0).  The matcher of the rows bsg_match_rows_substr hands back. */
 BSG_API int32_t bsh_match_row_substring(const char *substring_json, uint64_t substring_len, const uint8_t *row, uint64_t row_len,
                                         const bsg_tokenizer *tok);
+/* Range conditions (bloomgpu.h "Range conditions").  range_json: {"ExpressionType":"CONDITION"|"AND"|"OR","Condition":{"Field",
+ * "Lo"?,"Hi"?,"LoOpen"?,"HiOpen"?},"Children":[..]} with int64 "Lo" / "Hi" (absent or null: unbounded; anything else: < 0).
+ * The range half of the final row test: 1 when the tree holds for the row, 0 when not, < 0 for invalid arguments (a row that is not
+ * valid JSON: 0).  Exact for every JSON number literal, exponents included: the literal's digits are compared with the bound's, no
+ * floating point.  The matcher of the rows bsg_match_rows_range hands back. */
+BSG_API int32_t bsh_match_row_range(const char *range_json, uint64_t range_len, const uint8_t *row, uint64_t row_len);
+/* bsh_prune_query_sub with the fourth tree: And(bloom, regex field guard, substring guard, range guard).  A range condition's guard
+ * is Field(field); the nil condition is dropped from an And and kept in an Or, as in the substring guard.  A NULL / empty / "null"
+ * range tree gives exactly bsh_prune_query_sub's answer. */
+BSG_API int32_t bsh_prune_query_range(const char *bloom_json, uint64_t bloom_len, const char *regex_json, uint64_t regex_len,
+                                      const char *substring_json, uint64_t substring_len, const char *range_json, uint64_t range_len,
+                                      const bsg_tokenizer *tok, char **out, uint64_t *out_len);
 
 /* Go regexp MatchString of `pattern` on `text` for the subset the device row matcher compiles (bsg_match_rows_regex; the
  * subset is listed in bloomsearch_amd/csrc/host/regex_dfa.hpp), run on the same DFA tables.  The text is read as Go reads a
@@ -157,7 +169,9 @@ BSG_API int32_t bse_stop(bse_engine *e);
 BSG_API int32_t bse_ingest_rows(bse_engine *e, const uint8_t *ndjson, uint64_t len);
 BSG_API int32_t bse_flush(bse_engine *e);
 BSG_API int32_t bse_merge(bse_engine *e);
-/* query_json: {"Bloom":{"Expression":{...}}} (or {"Bloom":null}); result JSON:
+/* query_json: {"Bloom":{"Expression":{...}}} (or {"Bloom":null}), with optional "Regex", "Substring" and "Range" trees (the last:
+ * bsh_match_row_range's tree, or {"Expression": tree}; under DeviceMatch a query with a Range tree and neither of the other two is
+ * decided by ONE bsg_match_rows_range call over And(bloom, range)); result JSON:
  * {"rows":[...],"stats":{"BlockStats":[{"FileID","BlockOffset","RowsProcessed","BytesProcessed","TotalRows",
  *  "TotalBytes","BloomFilterSkipped"}],"Errors":[..],"FilesConsidered","FilesBloomSkipped"}} */
 BSG_API int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, char **out_json, uint64_t *out_len);
@@ -177,7 +191,8 @@ BSG_API int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, c
  * under DeviceMatchWide / DeviceMatchWideRows (and the lookup keys, which never take a group with a needle) by ONE
  * bsg_match_rows_wide_substr / bsg_match_rows_wide_substr_rows call.  A query that breaks a limit alone, and a group the library
  * answers BSG_E_UNSUPPORTED for, are answered as by bse_query.  Without DeviceMatch a query with a Substring tree is answered as by
- * bse_query.  "[]" gives "[]". */
+ * bse_query.  A query with a "Range" tree is answered as by bse_query (keeping such queries in the groups is a follow-up).
+ * "[]" gives "[]". */
 BSG_API int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, char **out_json, uint64_t *out_len);
 /* {"files":[{"FileID","BloomEntryCounts":{..},"section_bytes","blocks":[{"PartitionID","Rows","BloomEntryCounts":{..},
  *  "BloomFalsePositiveRate","BloomFilterSize","filters":[{"m","k"}|null x3]}]}],

@@ -30,6 +30,7 @@
 #include "regex_groups.hpp"
 #include "section_codec.hpp"
 #include "range.hpp"
+#include "range_groups.hpp"
 #include "substring.hpp"
 #include "substring_groups.hpp"
 #include "wide_plan.hpp"
@@ -73,8 +74,8 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // true (with device_match): query_many packs its queries into groups bounded by the condition table alone (64 distinct
     // conditions, 16 regex conditions, the table bytes, co_active_bound) - not by 64 members - and decides each group by ONE
     // bsg_match_rows_wide call, every set's query list read straight from the probe's survivors (a group that holds a substring
-    // condition: ONE bsg_match_rows_wide_substr call, its needles packed and its regex tables under the cap beside them).  Off by
-    // default: routing is then exactly the batched calls'.
+    // condition: ONE bsg_match_rows_wide_substr call, its needles packed and its regex tables under the cap beside them; a group that
+    // holds a range condition: ONE bsg_match_rows_wide_range call).  Off by default: routing is then exactly the batched calls'.
     bool device_match_wide = false;
     // true (with device_match): the grouping of device_match_wide, each group decided by ONE bsg_match_rows_wide_rows call: every
     // pair's matching rows come back as a list (or NONE / ALL / its words) and are consumed as such, no bit row is scanned.  Off by
@@ -83,7 +84,7 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // true (with device_match): query_many's groups WITHOUT a regex condition hold up to 1 024 distinct conditions and are each decided
     // by ONE bsg_match_rows_lookup call (device_match_lookup_rows: bsg_match_rows_lookup_rows, the lists consumed as under
     // device_match_wide_rows); a query with a regex condition keeps the 64-condition groups of the wide call, and so does one with a
-    // substring condition (the lookup calls take no needle).  Off by default.
+    // substring or a range condition (the lookup calls take neither).  Off by default.
     bool device_match_lookup = false;
     bool device_match_lookup_rows = false;
     // with either of the two (and device_regex): a group that holds regex conditions keeps the 1 024-condition bound and is decided by
@@ -433,6 +434,11 @@ public:
     // bsg_match_rows_many_regex_substr, or bsg_match_rows_wide_substr(_rows) under the wide keys (substring_groups.hpp says when a
     // group closes and which call it makes).  Every other substring query is answered by query(), and so is a batched one whose
     // group the device did not decide.
+    // A query with a range tree (ranges[i]) and neither a regex nor a substring tree stays in the batch under DeviceMatch: it is probed
+    // with query()'s pruning expression And(bloom, range guard) and matched as the program And(bloom root | TRUE, range root) in its
+    // group's call — bsg_match_rows_many_range, or bsg_match_rows_wide_range(_rows) under the wide and the lookup keys
+    // (range_groups.hpp: a group never holds a range condition beside a regex or substring one).  A range query with one of the other two
+    // trees, every range query without DeviceMatch, and a batched one whose group the device did not decide are answered by query().
     int32_t query_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
                        std::vector<QueryResult> &results, const std::vector<const SubstringExpression *> *subs = nullptr,
                        const std::vector<const RangeExpression *> *ranges = nullptr)
@@ -441,13 +447,16 @@ public:
         std::vector<size_t> live;                   // the batch: queries without a regex tree, and regex queries the device matches
         std::vector<const RegexExpression *> live_regex;
         std::vector<const SubstringExpression *> live_sub;
+        std::vector<const RangeExpression *> live_range;
         std::vector<std::unique_ptr<RegexRowMatcher>> regex_dfas;   // per batched query: the DFA-backed matcher of the rows handed back
         std::vector<std::unique_ptr<SubstringRowMatcher>> sub_matchers;   // ... and the substring matcher of the same
+        std::vector<std::unique_ptr<RangeRowMatcher>> range_matchers;     // ... and the range matcher
         for (size_t i = 0; i < exprs.size(); ++i) {
             const RegexExpression *rx = i < regexes.size() ? regexes[i] : nullptr;
             const SubstringExpression *sx = subs && i < subs->size() ? (*subs)[i] : nullptr;
-            // a query with a range tree (ranges[i]) is answered by query(): keeping such queries in the groups is a follow-up
-            if (const RangeExpression *rg = ranges && i < ranges->size() ? (*ranges)[i] : nullptr) {
+            const RangeExpression *rg = ranges && i < ranges->size() ? (*ranges)[i] : nullptr;
+            // a range tree beside a regex or substring tree (no walker takes both), or without DeviceMatch: query()
+            if (rg && (rx || sx || !cfg_.device_match)) {
                 if (int32_t rc = query(exprs[i], results[i], rx, sx, rg)) return rc;
                 continue;
             }
@@ -465,8 +474,10 @@ public:
             live.push_back(i);
             live_regex.push_back(rx);
             live_sub.push_back(sx);
+            live_range.push_back(rg);
             regex_dfas.push_back(std::move(dfa));
             sub_matchers.push_back(std::move(sub_matcher));
+            range_matchers.push_back(rg ? std::make_unique<RangeRowMatcher>(rg) : nullptr);
         }
         if (live.empty()) return kEngineOk;
         const auto t_begin = std::chrono::steady_clock::now();
@@ -475,6 +486,13 @@ public:
         for (size_t k = 0; k < live.size(); ++k) {
             batch.push_back(exprs[live[k]]);
             // pruneBloomQuery = AndBloomQueries(bloom, RegexFieldGuardBloomQuery(regex)), as query(); a plain query keeps its pointer
+            if (live_range[k]) {                    // And(bloom, range guard): a range query has neither of the other two trees
+                BloomExpression range_guard_storage;
+                const bool has_range_guard = range_guard(live_range[k], range_guard_storage);
+                prune_storage.push_back(std::make_unique<BloomExpression>());
+                prune.push_back(and_bloom_queries(batch[k], has_range_guard ? &range_guard_storage : nullptr, *prune_storage.back()) ? prune_storage.back().get() : nullptr);
+                continue;
+            }
             if (!live_regex[k] && !live_sub[k]) { prune.push_back(batch[k]); continue; }
             BloomExpression guard, sub_guard, two;
             const bool has_guard = regex_field_guard(live_regex[k], guard);
@@ -520,13 +538,13 @@ public:
         for (size_t k = 0; k < Q; ++k) matchers.emplace_back(batch[k], cfg_.tokenizer);
         std::vector<uint8_t> on_device(Q, 0);
         if (cfg_.device_match && !scan.empty())
-            if (int32_t rc = match_rows_device_many(batch, live_regex, live_sub, scan, set_first, set_wants, matchers, regex_dfas, sub_matchers, hit, on_device)) return rc;
+            if (int32_t rc = match_rows_device_many(batch, live_regex, live_sub, live_range, scan, set_first, set_wants, matchers, regex_dfas, sub_matchers, range_matchers, hit, on_device)) return rc;
         for (size_t k = 0; k < Q; ++k) {
             QueryResult &out = results[live[k]];
             // not decided in a group (alone beyond a limit, or the library refused the group): per query, as before.  query() probes
             // again and rewrites the stats block_stage_stats left here: known, and rare enough not to carry the survivors over
-            if ((live_regex[k] || live_sub[k]) && !on_device[k] && !scanned[k].empty()) {
-                if (int32_t rc = query(exprs[live[k]], out, live_regex[k], live_sub[k])) return rc;
+            if ((live_regex[k] || live_sub[k] || live_range[k]) && !on_device[k] && !scanned[k].empty()) {
+                if (int32_t rc = query(exprs[live[k]], out, live_regex[k], live_sub[k], live_range[k])) return rc;
                 continue;
             }
             for (size_t s = 0; s + 1 < set_first.size(); ++s) {
@@ -1086,11 +1104,16 @@ private:
     // regex tables are bounded by the reduced cap beside a needle table (substring_groups.hpp fits); it is decided by
     // bsg_match_rows_many_substr / bsg_match_rows_many_regex_substr, under the wide keys by bsg_match_rows_wide_substr(_rows), and never by
     // a lookup call (under the lookup keys it takes the wide route, bounded by 64 conditions).
+    // A query with a range tree (ranges[k]; it has neither of the other two) is And(bloom root | TRUE, range root) with its FieldRange
+    // conditions in the table.  A group closes where the next query would put a range condition beside a regex or substring one, in either
+    // order (range_groups.hpp joins); plain queries go with both.  A group with a range condition is decided by bsg_match_rows_many_range,
+    // under the wide keys by bsg_match_rows_wide_range(_rows), and never by a lookup call (the wide route, bounded by 64 conditions).
     int32_t match_rows_device_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
-                                   const std::vector<const SubstringExpression *> &subs,
+                                   const std::vector<const SubstringExpression *> &subs, const std::vector<const RangeExpression *> &ranges,
                                    const std::vector<const std::string *> &scan, const std::vector<uint32_t> &set_first,
                                    const std::vector<const std::vector<uint8_t> *> &set_wants, std::vector<RowMatcher> &host_matchers,
                                    std::vector<std::unique_ptr<RegexRowMatcher>> &host_regex, std::vector<std::unique_ptr<SubstringRowMatcher>> &host_sub,
+                                   std::vector<std::unique_ptr<RangeRowMatcher>> &host_range,
                                    std::vector<std::vector<uint8_t>> &hit, std::vector<uint8_t> &on_device)
     {
         std::vector<uint8_t> bytes;
@@ -1126,9 +1149,14 @@ private:
             uint32_t n_rx = 0, rx_table = 0;                                 // the group's regex conditions and their table bytes
             uint32_t n_plain = 0, n_ft = 0;                                  // its other conditions, and the FieldToken ones among them
             bsh_subg::Group sub_group;                                       // its needles as they pack, and rx_table once more
+            bsh_rngg::Mix mix;                                               // whether its table holds a range / a regex or substring condition
             for (; k < exprs.size() && members.size() < max_members; ++k) {
                 MatcherProgram mp(exprs[k]);
-                if (regexes[k] || subs[k]) {
+                if (ranges[k]) {
+                    if (!exprs[k] || mp.prog_ops.empty()) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
+                    emit_range_program(*ranges[k], mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
+                    mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 2));
+                } else if (regexes[k] || subs[k]) {
                     if (!exprs[k] || mp.prog_ops.empty()) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
                     if (regexes[k]) lower_regex(*regexes[k], mp);
                     if (subs[k]) emit_substring_program(*subs[k], mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
@@ -1138,6 +1166,8 @@ private:
                 std::map<std::tuple<uint32_t, std::string, std::string>, uint32_t> added;
                 uint32_t fresh_rx = 0, fresh_bytes = 0, fresh_plain = 0, fresh_ft = 0;
                 bsh_subg::Fresh fresh_sub;                                   // the folded lengths of its fresh needles, in condition order
+                bsh_rngg::Mix query_mix;
+                for (size_t c = 0; c < mp.kinds.size(); ++c) query_mix.see(mp.kinds[c]);
                 for (size_t c = 0; c < mp.kinds.size(); ++c) {
                     const auto key = std::make_tuple(mp.kinds[c], mp.fields[c], mp.tokens[c]);
                     if (index.count(key) || !added.emplace(key, 0).second) continue;
@@ -1155,10 +1185,11 @@ private:
                 for (const auto &kv : added) if (std::get<0>(kv.first) == BSG_KIND_FIELD_REGEX) rx_fields.push_back(std::get<1>(kv.first));
                 const bool rx_group = n_rx + fresh_rx != 0;
                 const bool needle_group = sub_group.n_needles + fresh_sub.needle_len.size() != 0;   // never a lookup call's
-                const size_t cond_cap = lookup && !needle_group && (!rx_group || lookup_regex) ? bsh_lookup::kMaxConds : 64;
+                const bool range_group = mix.range || query_mix.range;                              // nor is this one
+                const size_t cond_cap = bsh_rngg::lookup_group(lookup, lookup_regex, range_group, rx_group, needle_group) ? bsh_lookup::kMaxConds : 64;
                 // the lookup regex call's cap depends on the table: what this group's strings and pairs can take at most
                 const uint32_t group_cap = lookup_regex && rx_group && !needle_group ? bsh_lookup::rx_lds_cap_of(2u * (n_plain + fresh_plain), n_ft + fresh_ft) : table_cap;
-                const bool fits = mp.kinds.size() <= cond_cap && index.size() + added.size() <= cond_cap && n_rx + fresh_rx <= bsh_rxg::kMaxRegexConds &&
+                const bool fits = bsh_rngg::joins(mix, query_mix) && mp.kinds.size() <= cond_cap && index.size() + added.size() <= cond_cap && n_rx + fresh_rx <= bsh_rxg::kMaxRegexConds &&
                                   bsh_rxg::align4(rx_table + fresh_bytes) <= group_cap &&
                                   bsh_rxg::co_active_bound(rx_fields) <= bsh_rxg::kManySlots &&
                                   (!needle_group || bsh_subg::fits(sub_group, fresh_sub, wide));   // the needles pack, the tables fit beside them
@@ -1183,13 +1214,16 @@ private:
                 n_plain += fresh_plain;
                 n_ft += fresh_ft;
                 bsh_subg::add(sub_group, fresh_sub);
+                bsh_rngg::add(mix, query_mix);
             }
             if (members.empty()) continue;
             const bsh_subg::Call call = bsh_subg::group_call(n_rx != 0, sub_group.n_needles != 0, wide, wide_rows);
-            const bool by_sub = sub_group.n_needles != 0;
+            const bool by_sub = sub_group.n_needles != 0, by_range = mix.range;
+            const char *call_name = bsh_rngg::group_call_name(by_range, n_rx != 0, by_sub, wide, wide_rows);   // (of a group no lookup call decides)
             // a row the device handed back: the host matchers of query m together
             auto host_verdict = [&](size_t m, const std::string &row) {
-                return host_matchers[m].match(row) && (!host_regex[m] || host_regex[m]->match(row)) && (!host_sub[m] || host_sub[m]->match(row));
+                return host_matchers[m].match(row) && (!host_regex[m] || host_regex[m]->match(row)) && (!host_sub[m] || host_sub[m]->match(row)) &&
+                       (!host_range[m] || host_range[m]->match(row));
             };
             std::vector<uint8_t> cbytes;
             std::vector<uint32_t> coff{0};
@@ -1198,7 +1232,7 @@ private:
                 cbytes.insert(cbytes.end(), tokens[c].begin(), tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
             }
             if (wide) {
-                const bool by_lookup = lookup && n_rx == 0 && !by_sub, by_lookup_regex = lookup_regex && n_rx != 0 && !by_sub;
+                const bool by_lookup = lookup && n_rx == 0 && !by_sub && !by_range, by_lookup_regex = lookup_regex && n_rx != 0 && !by_sub;
                 // each set's list: the group's members that survived the probe on it, straight from set_wants
                 std::vector<uint32_t> sq_off{0}, sq;
                 for (size_t s = 0; s < n_sets; ++s) {
@@ -1218,8 +1252,8 @@ private:
                     std::vector<uint32_t> hdr(sq.size() + 1), payload(2 * total + 1), ids;
                     std::vector<uint64_t> pair_off(sq.size() + 1);
                     uint64_t payload_len = 0;
-                    count_match_call(by_lookup_regex ? "bsg_match_rows_lookup_regex_rows" : by_lookup ? "bsg_match_rows_lookup_rows" : bsh_subg::call_name(call));
-                    const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex_rows : by_lookup ? bsg_match_rows_lookup_rows : by_sub ? bsg_match_rows_wide_substr_rows : bsg_match_rows_wide_rows)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
+                    count_match_call(by_lookup_regex ? "bsg_match_rows_lookup_regex_rows" : by_lookup ? "bsg_match_rows_lookup_rows" : call_name);
+                    const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex_rows : by_lookup ? bsg_match_rows_lookup_rows : by_sub ? bsg_match_rows_wide_substr_rows : by_range ? bsg_match_rows_wide_range_rows : bsg_match_rows_wide_rows)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
                                                                 kinds.data(), (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(),
                                                                 (uint32_t)members.size(), set_first.data(), sq_off.data(), sq.data(), (uint32_t)n_sets, &tok,
                                                                 hdr.data(), pair_off.data(), payload.data(), 2 * total, &payload_len, fb.data(),
@@ -1240,8 +1274,8 @@ private:
                     }
                 } else {
                 std::vector<uint64_t> words(total + 1);
-                count_match_call(by_lookup_regex ? "bsg_match_rows_lookup_regex" : by_lookup ? "bsg_match_rows_lookup" : bsh_subg::call_name(call));
-                const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex : by_lookup ? bsg_match_rows_lookup : by_sub ? bsg_match_rows_wide_substr : bsg_match_rows_wide)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
+                count_match_call(by_lookup_regex ? "bsg_match_rows_lookup_regex" : by_lookup ? "bsg_match_rows_lookup" : call_name);
+                const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex : by_lookup ? bsg_match_rows_lookup : by_sub ? bsg_match_rows_wide_substr : by_range ? bsg_match_rows_wide_range : bsg_match_rows_wide)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
                                                        (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(),
                                                        sq_off.data(), sq.data(), (uint32_t)n_sets, &tok, words.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
                 if (rc == BSG_E_UNSUPPORTED) continue;
@@ -1270,8 +1304,8 @@ private:
             std::vector<uint64_t> bits(members.size() * n_words);
             std::vector<uint32_t> fb(scan.size());
             uint32_t n_fb = 0;
-            count_match_call(bsh_subg::call_name(call));
-            const int32_t rc = (call == bsh_subg::Call::ManyRegexSubstr ? bsg_match_rows_many_regex_substr : call == bsh_subg::Call::ManySubstr ? bsg_match_rows_many_substr :
+            count_match_call(call_name);
+            const int32_t rc = (by_range ? bsg_match_rows_many_range : call == bsh_subg::Call::ManyRegexSubstr ? bsg_match_rows_many_regex_substr : call == bsh_subg::Call::ManySubstr ? bsg_match_rows_many_substr :
                                 n_rx ? bsg_match_rows_many_regex : bsg_match_rows_many)(
                 ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(), (uint32_t)kinds.size(),
                 prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(), masks.data(), (uint32_t)n_sets, &tok, bits.data(),

@@ -84,6 +84,12 @@
 // compare is integer arithmetic on (sign, magnitude, overflow, fraction): there is no float64 round trip.  A literal with an exponent on
 // a leaf ANY range condition of the table listens on makes the row a fallback row (the host compares digit strings).  The bounds sit in
 // the condition's record where a token's hash words would (e[4] = lo, e[5] = hi), the flags in bits 8-11 of e[10]: no byte of LDS is added.
+//
+// Range conditions in the storing walker (bsg_match_rows_wide_range, k_match_rows_store_range* = WIDE and RANGE): kMatchWideLdsBytes and three
+// workgroups per CU as k_match_rows_store.  A range condition listens on a leaf only where the row's set lists a query that uses it
+// (the set's condition mask, the gate of the regex header loop), so an exponent literal hands a row back only if such a condition sits
+// on its leaf; the batched walker asks ANY condition of the table.  The flag of a range condition none of the set's queries references
+// is unspecified (nothing reads it).
 #pragma once
 #include <type_traits>
 #include "ingest.hip.h"
@@ -314,6 +320,7 @@ constexpr uint32_t kRangeNoLo = 1u, kRangeNoHi = 2u, kRangeLoOpen = 4u, kRangeHi
 // The range walkers add no LDS: each keeps its RANGE-less sibling's bytes, and so its three workgroups per CU.
 static_assert(3u * kMatchLdsBytes <= 160u * 1024u && 3u * kMatchManyLdsBytes <= 160u * 1024u,
               "k_match_rows_range and k_match_rows_many_range keep three workgroups per CU as k_match_rows and k_match_rows_many");
+static_assert(3u * kMatchWideLdsBytes <= 160u * 1024u, "k_match_rows_store_range keeps three workgroups per CU as k_match_rows_store");
 // One lane's number parser: the raw literal of the current number leaf as -?digits[.digits][(e|E)...], fed byte by byte.
 struct NumLane {
     const Walker *wk;                       // whether the current leaf is one that is never emitted
@@ -392,7 +399,7 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
                                                 const MatchWideArgs &wd = MatchWideArgs{}, const SubArgs &sb = SubArgs{})
 {
     static_assert(!(MANY && WIDE), "the storing walker evaluates no program");
-    static_assert(!(RANGE && (REGEX || SUB || WIDE)), "range conditions: the plain single and batched walkers only");
+    static_assert(!(RANGE && (REGEX || SUB)), "range conditions: the plain single, batched and storing walkers only");
     constexpr uint32_t kSubBase = WIDE ? kMatchWideLdsBytes : MANY ? kMatchManySubBase : kMatchLdsBytes;   // the needle table sits behind the instance's own LDS
     constexpr uint32_t kProgBytes = WIDE ? 0u : MANY ? kMatchManyProgBytes : kMatchMaxOps * 4;
     constexpr uint32_t kRxBase = SUB ? kSubBase + kSubTableBytes : WIDE ? kMatchWideLdsBytes : MANY ? kMatchManyLdsBytes : kMatchLdsBytes;   // the regex blob sits behind the instance's own LDS (and the needle table)
@@ -531,7 +538,9 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
                     const bool heq = q == Q_LEAF && e[0] == h[0] && e[1] == h[1] && e[2] == h[2] && e[3] == h[3];
                     const bool eq = heq && e[8] == fp;
                     collided |= heq && !eq;
-                    if (eq) { leaf_mask |= 1ULL << c; num_listen = true; }
+                    bool hears = eq;
+                    if constexpr (WIDE) hears = eq && ((cmask >> c) & 1ull) != 0ull;   // ... only where the row's set lists a query that uses it
+                    if (hears) { leaf_mask |= 1ULL << c; num_listen = true; }
                     continue;
                 }
             }
@@ -791,6 +800,21 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_gram(const 
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_gram(const MatchArgs a, const RxArgs x, const MatchWideArgs wd, const TokSpec t)
 {
     match_rows_body<true, TokGramP, false, kRxActive, true>(a, x, TokGramP(t), MatchManyArgs{}, wd);
+}
+
+// ... with the number consumer (bsg_match_rows_wide_range): kinds 0, 1, 2, 6; dynamic LDS kMatchWideLdsBytes, as k_match_rows_store.  A range
+// condition listens on a leaf only where the row's set lists a query that uses it (the set's condition mask, as the regex conditions).
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_range(const MatchArgs a, const MatchWideArgs wd)
+{
+    match_rows_body<false, TokDefault, false, kRxActive, true, false, true>(a, RxArgs{}, TokDefault{}, MatchManyArgs{}, wd);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_range_tok(const MatchArgs a, const MatchWideArgs wd, const TokSpec t)
+{
+    match_rows_body<false, TokSpecP, false, kRxActive, true, false, true>(a, RxArgs{}, TokSpecP{t}, MatchManyArgs{}, wd);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_range_gram(const MatchArgs a, const MatchWideArgs wd, const TokSpec t)
+{
+    match_rows_body<false, TokGramP, false, kRxActive, true, false, true>(a, RxArgs{}, TokGramP(t), MatchManyArgs{}, wd);
 }
 
 // ... with the substring consumer (bsg_match_rows_wide_substr): kinds 0, 1, 2, 4, 5; dynamic LDS kMatchWideSubLdsBytes.  Every needle

@@ -20,6 +20,8 @@
 // build_range_table checks each condition's 17 bytes and moves its flags into the kind word, the part writes the bounds over the token
 // slots of the condition's hashes once the device has hashed the table, and PlanePart launches the range instances of the walker.  A
 // table without a range condition is bsg_match_rows_tok's / bsg_match_rows_many's: its walkers and its bits.
+// bsg_match_rows_wide_range(_rows) is the wide call with kinds 0, 1, 2 and 6 in its table: build_range_table and the bounds copy as above,
+// and WidePart launches k_match_rows_store_range*; a table without a range condition is bsg_match_rows_wide(_rows)'s walkers and bits.
 // bsg_match_rows_lookup(_rows) is the wide call with another Family and a LookupPlan beside its WidePlan: WidePart then sizes the
 // flags at W words per row, places the lookup tables (host/lookup_plan.hpp) from the hashes the device made, and launches
 // match_lookup.hip.h's walker and evaluator in place of match.hip.h's.  bsg_match_rows_lookup_regex(_rows) is that call with FieldRegex
@@ -103,6 +105,7 @@ struct MatchCall {
     bsh::NeedlePack sub;                   // ... M, START, ANY
     std::vector<uint32_t> sub_kinds;       // ... and cond_kinds with word | end bit of a substring condition's needle (match.hip.h SubLane)
     bool range_call = false;               // the call is bsg_match_rows_range / bsg_match_rows_many_range (the name in traces)
+    bool wide_range = false;               // the call is bsg_match_rows_wide_range(_rows) (the name in traces)
     bool range = false;                    // build_range_table: the table holds a FieldRange condition, the range walkers run
     std::vector<uint32_t> range_conds;     // ... the conditions of kind 6,
     std::vector<uint64_t> range_bounds;    // ... lo and hi of each (two's complement), in that order
@@ -270,6 +273,10 @@ constexpr Walkers<bsg::MatchLookupArgs> kLookupWalkers{bsg::k_match_rows_lookup,
 constexpr Walkers<> kSingleRangeWalkers{bsg::k_match_rows_range, bsg::k_match_rows_range_tok, nullptr, nullptr, bsg::k_match_rows_range_gram, nullptr};
 constexpr Walkers<bsg::MatchManyArgs> kManyRangeWalkers{bsg::k_match_rows_many_range, bsg::k_match_rows_many_range_tok, nullptr, nullptr,
                                                         bsg::k_match_rows_many_range_gram, nullptr};
+
+// ... and the storing walker's three (bsg_match_rows_wide_range(_rows))
+constexpr Walkers<bsg::MatchWideArgs> kWideRangeWalkers{bsg::k_match_rows_store_range, bsg::k_match_rows_store_range_tok, nullptr, nullptr,
+                                                        bsg::k_match_rows_store_range_gram, nullptr};
 
 // ... and the nine with the substring consumer: (single / many / wide) x (default tokenizer / spec / spec with an n-gram width)
 template <class... E>
@@ -475,6 +482,7 @@ struct WidePart {
         if (wp.lookup_regex) return wp.rows ? "bsg_match_rows_lookup_regex_rows" : "bsg_match_rows_lookup_regex";
         if (wp.lookup) return wp.rows ? "bsg_match_rows_lookup_rows" : "bsg_match_rows_lookup";
         if (mc.wide_sub) return wp.rows ? "bsg_match_rows_wide_substr_rows" : "bsg_match_rows_wide_substr";
+        if (mc.wide_range) return wp.rows ? "bsg_match_rows_wide_range_rows" : "bsg_match_rows_wide_range";
         return wp.rows ? "bsg_match_rows_wide_rows" : "bsg_match_rows_wide";
     }
     bool prog_off() const { return true; }
@@ -569,6 +577,11 @@ struct WidePart {
         if (mc.substr) {
             launch_sub_walker(bsg::k_match_rows_store_substr, bsg::k_match_rows_store_substr_tok, bsg::k_match_rows_store_substr_gram, bsg::kMatchWideSubLdsBytes,
                               p.d.stream, k0, k1, a, p.sub, mc.tok(), wd);
+            return;
+        }
+        if (mc.range) {                                // the same LDS as the plain storing walkers: the bounds sit in the conditions' records
+            assert(!mc.n_rx);
+            launch_walker(kWideRangeWalkers, bsg::kMatchWideLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok(), wd);
             return;
         }
         launch_walker(kWideWalkers, bsg::kMatchWideLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok(), wd);
@@ -899,6 +912,11 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
     const uint32_t n_rows = mc.n_rows;
     const uint32_t max_kind = mc.wide_sub ? BSG_KIND_FIELD_SUBSTRING : BSG_KIND_FIELD_REGEX;   // kinds 4 and 5: bsg_match_rows_wide_substr(_rows) only
     for (uint32_t c = 0; c < mc.n_conds; ++c) {
+        if (mc.wide_range) {                   // bsg_match_rows_wide_range(_rows): kinds 0, 1, 2 and 6, no text consumer beside the number one
+            if (range_refuses(mc.cond_kinds[c])) return fail(BSG_E_UNSUPPORTED, kNoTextWithRange, c, mc.cond_kinds[c]);
+            if (mc.cond_kinds[c] > BSG_KIND_FIELD_RANGE) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
+            continue;
+        }
         if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
     }
     // the lookup call: the table's distinct role strings, their role records and the FieldToken pairs
@@ -937,7 +955,9 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
             }
     }
     if (int32_t rc = lower_programs(mc, fam, prog_ops, prog_off, n_queries, lookup ? &lookup_plan.canon : nullptr)) return rc;
-    if (!lookup) {
+    if (mc.wide_range) {                       // no regex condition reaches this call: the bounds and flags of the kind-6 ones, if any
+        if (int32_t rc = build_range_table(mc)) return rc;
+    } else if (!lookup) {
         // a table with needles: the blob under what the needle table leaves, then the needle tables; one without: the wide call's own
         const bool sub = mc.wide_sub && table_sides(mc).sub;
         if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, sub ? bsg::kRxWideSubLdsCap : bsg::kRxWideLdsCap)) return rc;
@@ -1065,6 +1085,35 @@ int32_t bsg_match_rows_wide_substr_rows(bsg_ctx *ctx, const uint8_t *rows, const
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
                  fallback_cap, out_n_fallback};
     mc.wide_sub = true;
+    const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
+}
+
+int32_t bsg_match_rows_wide_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                  const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                  const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                  const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
+                                  const bsg_tokenizer *tok,
+                                  uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    mc.wide_range = true;
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
+}
+
+int32_t bsg_match_rows_wide_range_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                       const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                       const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                       const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
+                                       const bsg_tokenizer *tok,
+                                       uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap, uint64_t *out_payload_len,
+                                       uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
+                 fallback_cap, out_n_fallback};
+    mc.wide_range = true;
     const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
     return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
 }

@@ -799,7 +799,7 @@ class Context:
         return self._wide_bits(self.L.bsg_match_rows_wide, rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
 
     def _wide_bits(self, call, rows, batch, set_first_row, set_query_off, set_queries, tokenizer):
-        """bsg_match_rows_wide, bsg_match_rows_wide_substr, bsg_match_rows_lookup or bsg_match_rows_lookup_regex (one argument list, one result)"""
+        """bsg_match_rows_wide, bsg_match_rows_wide_substr, bsg_match_rows_wide_range, bsg_match_rows_lookup or bsg_match_rows_lookup_regex (one argument list, one result)"""
         args, _keep, n, pair_word_off, total = self._wide_args(rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
         words = np.zeros(total, dtype=np.uint64)
         fb = np.zeros(max(n, 1), dtype=np.uint32)
@@ -814,7 +814,7 @@ class Context:
         return self._wide_rows(self.L.bsg_match_rows_wide_rows, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap)
 
     def _wide_rows(self, call, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap):
-        """bsg_match_rows_wide_rows, bsg_match_rows_wide_substr_rows, bsg_match_rows_lookup_rows or bsg_match_rows_lookup_regex_rows (one argument list, one result)"""
+        """bsg_match_rows_wide_rows, bsg_match_rows_wide_substr_rows, bsg_match_rows_wide_range_rows, bsg_match_rows_lookup_rows or bsg_match_rows_lookup_regex_rows (one argument list, one result)"""
         args, _keep, n, pair_word_off, total = self._wide_args(rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
         n_pairs = len(pair_word_off) - 1
         cap = 2 * total if payload_cap is None else int(payload_cap)
@@ -835,6 +835,16 @@ class Context:
     def match_rows_wide_substr_rows(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None, payload_cap=None):
         """bsg_match_rows_wide_substr_rows: match_rows_wide_rows' arguments and result over such a table."""
         return self._wide_rows(self.L.bsg_match_rows_wide_substr_rows, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap)
+
+    def match_rows_wide_range(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None):
+        """bsg_match_rows_wide_range: match_rows_wide's arguments and result, and the batch (query.CompiledWideRangeBatch, any number of
+        queries) may hold FieldRange conditions.  A row with an exponent literal on the leaf of a range condition that a listed query
+        of the row's set uses comes back as a fallback row."""
+        return self._wide_bits(self.L.bsg_match_rows_wide_range, rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
+
+    def match_rows_wide_range_rows(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None, payload_cap=None):
+        """bsg_match_rows_wide_range_rows: match_rows_wide_rows' arguments and result over such a table."""
+        return self._wide_rows(self.L.bsg_match_rows_wide_range_rows, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap)
 
     def match_rows_lookup(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None):
         """bsg_match_rows_lookup: match_rows_wide's arguments and result over a table of up to 1 024 Field / Token / FieldToken

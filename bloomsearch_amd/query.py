@@ -643,7 +643,15 @@ class CompiledWideSubstringBatch(CompiledRowSubstringQueryBatch):
     MAX_QUERIES, MAX_OPS = MATCH_WIDE_MAX_QUERIES, MATCH_WIDE_MAX_OPS
 
 
-MATCH_LOOKUP_MAX_CONDS = 1024                                                        # bloomgpu.h BSG_MATCH_LOOKUP_MAX_CONDS
+class CompiledWideRangeBatch(CompiledRangeQueryBatch):
+    """Any number of (bloom expression, range expression) pairs for one bsg_match_rows_wide_range call: the table and the programs
+    exactly as CompiledRangeQueryBatch builds them, without the 64-query and 2 048-op limits of the batched call.  Raises ValueError
+    beyond 2^20 queries, 2^22 lowered ops or 64 distinct conditions."""
+
+    MAX_QUERIES, MAX_OPS = MATCH_WIDE_MAX_QUERIES, MATCH_WIDE_MAX_OPS
+
+
+MATCH_LOOKUP_MAX_CONDS = 1024                                                     # bloomgpu.h BSG_MATCH_LOOKUP_MAX_CONDS
 
 
 class CompiledLookupBatch(CompiledWideBatch):

@@ -54,7 +54,7 @@ extern "C" {
 #define BSG_KIND_FIELD_REGEX  3u   /* row matcher only (bsg_match_rows_regex): entry 2i = field, 2i + 1 = pattern */
 #define BSG_KIND_SUBSTRING        4u   /* bsg_match_rows_substr / _many_substr / _regex_substr / _many_regex_substr only: entry 2i empty, 2i + 1 = the needle */
 #define BSG_KIND_FIELD_SUBSTRING  5u   /* ... entry 2i = the field, 2i + 1 = the needle */
-#define BSG_KIND_FIELD_RANGE      6u   /* bsg_match_rows_range / _many_range only: entry 2i = the field, 2i + 1 = lo, hi, flags ("Range conditions") */
+#define BSG_KIND_FIELD_RANGE      6u   /* bsg_match_rows_range / _many_range / _wide_range(_rows) only: entry 2i = the field, 2i + 1 = lo, hi, flags ("Range conditions") */
 #define BSG_RANGE_ENTRY_BYTES 17u      /* lo (int64, little-endian), hi (the same), one byte of BSG_RANGE_* */
 #define BSG_RANGE_NO_LO   1u           /* no lower bound (lo is ignored) */
 #define BSG_RANGE_NO_HI   2u           /* no upper bound (hi is ignored) */
@@ -717,8 +717,8 @@ BSG_API int32_t bsg_match_rows_substr(bsg_ctx *ctx, const uint8_t *rows, const u
  * bsg_match_rows_tok; a row with an exponent literal on a range condition's leaf is a fallback row too, as is one where a leaf's
  * path has the hashes of a range condition's field but not its fingerprint.
  * A condition of kind 3, 4 or 5 is BSG_E_UNSUPPORTED here (the condition named): range conditions do not share a table with the
- * regex and substring consumers yet.  Every entry point but this one and bsg_match_rows_many_range answers kind 6 with BSG_E_INVALID
- * (unknown kind). */
+ * regex and substring consumers yet.  Every entry point but this one, bsg_match_rows_many_range and bsg_match_rows_wide_range(_rows)
+ * answers kind 6 with BSG_E_INVALID (unknown kind). */
 BSG_API int32_t bsg_match_rows_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
                                      const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
                                      const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
@@ -919,6 +919,36 @@ BSG_API int32_t bsg_match_rows_wide_substr_rows(bsg_ctx *ctx, const uint8_t *row
                                                 uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap,
                                                 uint64_t *out_payload_len, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                                 uint32_t *out_n_fallback);
+/* bsg_match_rows_wide / bsg_match_rows_wide_rows with range conditions allowed in the table (kinds 0, 1, 2 and BSG_KIND_FIELD_RANGE; the
+ * storing walkers k_match_rows_store_range*): the parameter lists, sets, pairs and the implicit set, result layouts,
+ * bsg_match_wide_size, bsg_match_pair_rows_list, sharding, chunked upload and bsg_last_match_ms of the two wide calls; a range
+ * condition as "Range conditions" and bsg_match_rows_range document it.  Pair p's bits = what bsg_match_rows_range returns for the
+ * program of set_queries[p] alone over the set's rows.  A table without a range condition is bsg_match_rows_wide(_rows)'s: the same
+ * kernels, limits and bits.  No LDS is added: the walkers keep k_match_rows_store*'s bytes and workgroups per CU, and one parse of a
+ * number leaf serves every range condition on it.
+ * A range condition listens on a leaf only for rows of a set that lists a query which uses it (the gate of the regex conditions).  So
+ * an exponent literal makes a row a fallback row only if such a condition sits on its leaf - unlike bsg_match_rows_many_range, where
+ * ANY range condition of the table does.  Rows of a set with no pair are never walked and never fallback rows.
+ * BSG_E_UNSUPPORTED before anything is launched: a condition of kind 3, 4 or 5 (the condition named); more than 64 distinct
+ * conditions; program depth 64; the query, op, pair and item limits of bsg_match_rows_wide.  BSG_E_INVALID: what bsg_match_rows_wide
+ * refuses, a range entry of another length than BSG_RANGE_ENTRY_BYTES or a flag bit above 3 (the condition named), a kind above 6.
+ * Fallback rows, only among rows of a set with at least one pair (all their pair bits 0, never counted in a list): the walker's
+ * envelope, a fingerprint collision with ANY table condition (a range condition's field included), an exponent literal as above. */
+BSG_API int32_t bsg_match_rows_wide_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                          const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                          const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                          const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                          uint32_t n_sets, const bsg_tokenizer *tok,
+                                          uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                          uint32_t *out_n_fallback);
+BSG_API int32_t bsg_match_rows_wide_range_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                               const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                               const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                               const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                               uint32_t n_sets, const bsg_tokenizer *tok,
+                                               uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap,
+                                               uint64_t *out_payload_len, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                               uint32_t *out_n_fallback);
 /* One pair of bsg_match_rows_wide_rows, whatever its tag, as its ascending set-relative row indices (host arithmetic without a
  * context): payload = out_payload + out_pair_off[p] (not read for NONE / ALL), set_rows = the rows of the pair's set.  *out_n is the
  * full count; at most cap indices are written.  BSG_E_INVALID: a header and payload that are no pair of such a set (a count the

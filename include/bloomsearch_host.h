@@ -191,7 +191,12 @@ BSG_API int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, c
  * under DeviceMatchWide / DeviceMatchWideRows (and the lookup keys, which never take a group with a needle) by ONE
  * bsg_match_rows_wide_substr / bsg_match_rows_wide_substr_rows call.  A query that breaks a limit alone, and a group the library
  * answers BSG_E_UNSUPPORTED for, are answered as by bse_query.  Without DeviceMatch a query with a Substring tree is answered as by
- * bse_query.  A query with a "Range" tree is answered as by bse_query (keeping such queries in the groups is a follow-up).
+ * bse_query.  Under DeviceMatch a query with a "Range" tree and neither a Regex nor a Substring tree joins the batch as well: it is
+ * probed with And(bloom, range guard) and matched as And(bloom | TRUE, range); a group never holds a range condition beside a regex or
+ * substring condition (it closes where the next query would create that mix, in either order; plain queries go with both), and a group
+ * with a range condition is decided by ONE bsg_match_rows_many_range call - under DeviceMatchWide / DeviceMatchWideRows (and the lookup
+ * keys, which never take such a group) by ONE bsg_match_rows_wide_range / bsg_match_rows_wide_range_rows call.  A query with a Range
+ * tree beside a Regex or Substring tree, and every query with a Range tree without DeviceMatch, is answered as by bse_query.
  * "[]" gives "[]". */
 BSG_API int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, char **out_json, uint64_t *out_len);
 /* {"files":[{"FileID","BloomEntryCounts":{..},"section_bytes","blocks":[{"PartitionID","Rows","BloomEntryCounts":{..},

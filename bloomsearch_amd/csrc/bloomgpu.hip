@@ -13,6 +13,7 @@
 #include "direct.hip.h"
 #include "match.hip.h"
 #include "match_lookup.hip.h"
+#include "minmax.hip.h"
 #include "host/arena_cache.hpp" // the policy of the resident file-arena cache (cache_api.inc adapts it to the C ABI)
 #include "host/build_plan.hpp"  // shard layout and stats, the parts of a build call, the route a filter is built by
 #include "host/combiner_sync.hpp"
@@ -488,7 +489,7 @@ struct bsg_ctx {
     uint32_t union_coarsen = 0;                // lab: the partitioned union starts with 2^this x too few partitions (bsg_set_lab key 10)
     uint32_t union_mode = 0;                   // file-level union: 0 = partitions in LDS (k_union_partitions), 1 = global hash tables (bsg_set_lab key 9)
     // device time of the most recent call of each family: the slowest device that took part (bsg_last_*_ms)
-    float last_build_ms = 0.f, last_hash_ms = 0.f, last_decode_ms = 0.f, last_or_ms = 0.f, last_encode_ms = 0.f, last_match_ms = 0.f;
+    float last_build_ms = 0.f, last_hash_ms = 0.f, last_decode_ms = 0.f, last_or_ms = 0.f, last_encode_ms = 0.f, last_match_ms = 0.f, last_minmax_ms = 0.f;
 };
 
 namespace {

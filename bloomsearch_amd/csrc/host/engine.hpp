@@ -31,6 +31,7 @@
 #include "section_codec.hpp"
 #include "range.hpp"
 #include "range_groups.hpp"
+#include "minmax.hpp"
 #include "substring.hpp"
 #include "substring_groups.hpp"
 #include "wide_plan.hpp"
@@ -95,9 +96,15 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // strings.FieldsFunc(lower ? strings.ToLower(v) : v, isSep) (text.hpp Tokenizer): indexRow, the host matcher and the
     // device calls (bsg_ingest_rows_tok / bsg_match_rows_tok) all use it.  Default: BasicWhitespaceLowerTokenizer.
     Tokenizer tokenizer;
+    // MinMaxIndexes (engine.go: BloomSearchEngineConfig.MinMaxIndexes): top-level keys whose per-block [min, max] every flush records
+    // (minmax.hpp; bloomgpu.h "per-set MinMax indexes" for the limits: 1 to 8 distinct names of 1 to 64 bytes, or none).  Without
+    // DeviceIngest every row is folded on the host at ingest time; with it the flush's device call computes the indexes
+    // (bsg_ingest_rows_minmax / bsg_ingest_open_minmax) and only the rows it hands back are folded on the host.
+    std::vector<std::string> minmax_indexes;
 };
 
 struct DataBlock {
+    std::map<std::string, bsg_minmax> minmax;    // DataBlockMetadata.MinMaxIndexes: the fields some row of the block contributed to
     std::string partition_id;
     std::vector<std::string> rows;
     uint64_t row_bytes = 0;              // uncompressed row bytes incl. the 4-byte length prefixes
@@ -144,6 +151,7 @@ public:
         if (c.max_row_group_rows == 0 || c.max_row_group_bytes == 0) { err = "MaxRowGroupRows / MaxRowGroupBytes must be positive"; return kErrInvalidConfig; }
         if (!(c.bloom_false_positive_rate > 0.0 && c.bloom_false_positive_rate < 1.0)) { err = "BloomFalsePositiveRate must be in (0, 1)"; return kErrInvalidConfig; }
         if (c.device_ingest_stream && !c.device_ingest) { err = "DeviceIngestStream needs DeviceIngest"; return kErrInvalidConfig; }
+        if (!c.minmax_indexes.empty() && !MinMaxFieldNames::check(c.minmax_indexes, err)) { err = "MinMaxIndexes: " + err; return kErrInvalidConfig; }
         return kEngineOk;
     }
 
@@ -202,6 +210,10 @@ public:
             PartitionBuffer &pb = buffers_[pids[i]];
             pb.entries.tok = cfg_.tokenizer;
             if (!cfg_.device_ingest) pb.entries.index_row(rows[i]);   // HOT: walk + tokenize + dedup (ingest.go:450)
+            if (!cfg_.device_ingest && !cfg_.minmax_indexes.empty()) {   // ingest.go:455-470; under DeviceIngest the flush's device call does it
+                pb.minmax.resize(cfg_.minmax_indexes.size(), bsg_minmax{});
+                minmax_row(rows[i], cfg_.minmax_indexes, pb.minmax.data());
+            }
             pb.rows.emplace_back(rows[i]);
             pb.bytes += rows[i].size() + 4;
             buffered_rows_ += 1;
@@ -229,21 +241,24 @@ public:
             if (!cfg_.device_ingest) {
                 blk.counts = kv.second.entries.counts();
                 kv.second.entries.union_into(file_entries);   // flush.go:221
+                set_block_minmax(blk, kv.second.minmax.data(), kv.second.minmax.size());
             }
             file.blocks.push_back(std::move(blk));
         }
         std::vector<std::vector<uint8_t>> sections;
+        bool minmax_done = !cfg_.device_ingest || cfg_.minmax_indexes.empty();
         if (cfg_.device_ingest_stream && stream_ && !stream_broken_) {
-            if (int32_t rc = build_sections_stream(file, sections)) return rc;
+            if (int32_t rc = build_sections_stream(file, sections, minmax_done)) return rc;
             stream_stats_.flushes += 1;
         } else if (cfg_.device_ingest) {
-            if (int32_t rc = build_sections_device(file, sections)) return rc;
+            if (int32_t rc = build_sections_device(file, sections, &minmax_done)) return rc;
         } else {
             for (auto &kv : buffers_) sets.push_back(&kv.second.entries);
             sets.push_back(&file_entries);                    // file-level filters sized for the union (flush.go:253)
             if (int32_t rc = build_sections(sets, sections)) return rc;
             file.counts = file_entries.counts();
         }
+        if (!minmax_done) host_minmax_blocks(file);          // a flush that fell back to the host walker for its sets
         uint64_t off = 0;
         for (size_t b = 0; b < file.blocks.size(); ++b) {
             file.blocks[b].filter_section = std::move(sections[b]);
@@ -284,8 +299,11 @@ public:
             };
             start_block();
             for (DataBlock *src : kv.second) {
+                // merge.go:208-260: two blocks of a partition merge only when their MinMax KEY SETS are equal; the merged index is the
+                // union of the sources' (exact under every ingest route: the fold is associative, so nothing is recomputed)
                 if (!cur.rows.empty() && (cur.rows.size() + src->rows.size() > cfg_.max_row_group_rows ||
-                                          cur.row_bytes + src->row_bytes > cfg_.max_row_group_bytes)) { finish_block(); start_block(); }
+                                          cur.row_bytes + src->row_bytes > cfg_.max_row_group_bytes || !same_minmax_keys(cur, *src))) { finish_block(); start_block(); }
+                for (auto &kv2 : src->minmax) minmax_fold(cur.minmax[kv2.first], kv2.second.min, kv2.second.max);
                 for (auto &r : src->rows) {
                     if (!cfg_.device_ingest) block_sets.back()->index_row(r);      // merge.go:746
                     cur.row_bytes += r.size() + 4;
@@ -334,8 +352,9 @@ public:
     // substring tree is decided by ONE bsg_match_rows_range call over the program And(bloom root, range root) (the rows it hands back,
     // those with an exponent literal on a range field among them: the host matchers).  Every other combination takes the route it
     // took without the range tree, and RangeRowMatcher filters its hits.
+    // prefilter: the tree over the blocks' partition ids and MinMax indexes (minmax.hpp); nullptr takes exactly the path without one.
     int32_t query(const BloomExpression *row_expr, QueryResult &out, const RegexExpression *regex = nullptr, const SubstringExpression *sub = nullptr,
-                  const RangeExpression *range = nullptr)
+                  const RangeExpression *range = nullptr, const PrefilterExpression *prefilter = nullptr)
     {
         out = QueryResult{};
         const auto t_begin = std::chrono::steady_clock::now();
@@ -351,6 +370,7 @@ public:
         const BloomExpression *expr = and_bloom_queries(has_three ? &three_storage : nullptr, has_range_guard ? &range_guard_storage : nullptr, prune_storage) ? &prune_storage : nullptr;
         std::vector<Survivors> sv;
         if (int32_t rc = probe_stage({expr}, sv)) return rc;
+        apply_prefilter(prefilter, sv[0]);
         const std::vector<uint8_t> &file_ok = sv[0].file_ok;
         const int64_t probe_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_begin).count();
         size_t candidate_blocks = 0;
@@ -441,8 +461,10 @@ public:
     // trees, every range query without DeviceMatch, and a batched one whose group the device did not decide are answered by query().
     int32_t query_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
                        std::vector<QueryResult> &results, const std::vector<const SubstringExpression *> *subs = nullptr,
-                       const std::vector<const RangeExpression *> *ranges = nullptr)
+                       const std::vector<const RangeExpression *> *ranges = nullptr, const std::vector<const PrefilterExpression *> *prefilters = nullptr)
     {
+        // every query has its own prefilter mask on its survivors: a block no query of the batch keeps is never walked
+        auto prefilter_of = [&](size_t i) { return prefilters && i < prefilters->size() ? (*prefilters)[i] : nullptr; };
         results.assign(exprs.size(), QueryResult{});
         std::vector<size_t> live;                   // the batch: queries without a regex tree, and regex queries the device matches
         std::vector<const RegexExpression *> live_regex;
@@ -457,7 +479,7 @@ public:
             const RangeExpression *rg = ranges && i < ranges->size() ? (*ranges)[i] : nullptr;
             // a range tree beside a regex or substring tree (no walker takes both), or without DeviceMatch: query()
             if (rg && (rx || sx || !cfg_.device_match)) {
-                if (int32_t rc = query(exprs[i], results[i], rx, sx, rg)) return rc;
+                if (int32_t rc = query(exprs[i], results[i], rx, sx, rg, prefilter_of(i))) return rc;
                 continue;
             }
             std::unique_ptr<SubstringRowMatcher> sub_matcher;
@@ -470,7 +492,7 @@ public:
                 dfa = std::make_unique<RegexRowMatcher>(rx, true);
                 if (!dfa->valid()) dfa.reset();
             }
-            if ((sx && !sub_matcher) || (rx && !dfa)) { if (int32_t rc = query(exprs[i], results[i], rx, sx)) return rc; continue; }
+            if ((sx && !sub_matcher) || (rx && !dfa)) { if (int32_t rc = query(exprs[i], results[i], rx, sx, nullptr, prefilter_of(i))) return rc; continue; }
             live.push_back(i);
             live_regex.push_back(rx);
             live_sub.push_back(sx);
@@ -504,6 +526,7 @@ public:
         }
         std::vector<Survivors> sv;
         if (int32_t rc = probe_stage(prune, sv)) return rc;
+        for (size_t k = 0; k < live.size(); ++k) apply_prefilter(prefilter_of(live[k]), sv[k]);
         const int64_t probe_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_begin).count();
         const auto t_scan = std::chrono::steady_clock::now();
         const size_t Q = live.size();
@@ -544,7 +567,7 @@ public:
             // not decided in a group (alone beyond a limit, or the library refused the group): per query, as before.  query() probes
             // again and rewrites the stats block_stage_stats left here: known, and rare enough not to carry the survivors over
             if ((live_regex[k] || live_sub[k] || live_range[k]) && !on_device[k] && !scanned[k].empty()) {
-                if (int32_t rc = query(exprs[live[k]], out, live_regex[k], live_sub[k], live_range[k])) return rc;
+                if (int32_t rc = query(exprs[live[k]], out, live_regex[k], live_sub[k], live_range[k], prefilter_of(live[k]))) return rc;
                 continue;
             }
             for (size_t s = 0; s + 1 < set_first.size(); ++s) {
@@ -581,7 +604,57 @@ private:
         BloomEntrySets entries;
         std::vector<std::string> rows;
         uint64_t bytes = 0;
+        std::vector<bsg_minmax> minmax;      // (host ingest route) one index per configured field, folded row by row
     };
+
+    // ---- MinMax indexes ----
+    // index[f] of the configured field f -> the block's map (absent indexes are left out, as the reference's map has no entry)
+    void set_block_minmax(DataBlock &blk, const bsg_minmax *index, size_t n) const
+    {
+        blk.minmax.clear();
+        for (size_t f = 0; f < n && f < cfg_.minmax_indexes.size(); ++f)
+            if (index[f].present) blk.minmax[cfg_.minmax_indexes[f]] = bsg_minmax{index[f].min, index[f].max, 1, 0};
+    }
+    static bool same_minmax_keys(const DataBlock &a, const DataBlock &b)
+    {
+        if (a.minmax.size() != b.minmax.size()) return false;
+        for (auto ia = a.minmax.begin(), ib = b.minmax.begin(); ia != a.minmax.end(); ++ia, ++ib)
+            if (ia->first != ib->first) return false;
+        return true;
+    }
+    // every row of every block on the host (a flush whose device route gave up on its tables)
+    void host_minmax_blocks(DataFile &file) const
+    {
+        for (DataBlock &blk : file.blocks) {
+            std::vector<bsg_minmax> index(cfg_.minmax_indexes.size(), bsg_minmax{});
+            for (const std::string &r : blk.rows) minmax_row(r, cfg_.minmax_indexes, index.data());
+            set_block_minmax(blk, index.data(), index.size());
+        }
+    }
+    // the configured names packed like bsg_hash_entries' input
+    void pack_minmax_fields(std::vector<uint8_t> &bytes, std::vector<uint32_t> &off) const
+    {
+        bytes.clear();
+        off.assign(1, 0);
+        for (const std::string &f : cfg_.minmax_indexes) { bytes.insert(bytes.end(), f.begin(), f.end()); off.push_back((uint32_t)bytes.size()); }
+    }
+    // A prefilter as a mask on what the probe stages left: a block failing the tree is neither scanned nor given a BlockStats entry
+    // (block_ok 3), a file left without blocks counts in neither FilesConsidered nor FilesBloomSkipped (file_ok 2: the reference drops
+    // it before the file stage, query_exec.go:390-396).
+    template <class SurvivorsT>
+    void apply_prefilter(const PrefilterExpression *pf, SurvivorsT &sv) const
+    {
+        if (!pf) return;
+        for (size_t f = 0; f < files_.size(); ++f) {
+            size_t kept = 0;
+            for (size_t b = 0; b < files_[f].blocks.size(); ++b) {
+                const DataBlock &blk = files_[f].blocks[b];
+                if (prefilter_eval(*pf, PrefilterBlock{blk.partition_id, &blk.minmax})) ++kept;
+                else sv.block_ok[f][b] = 3;
+            }
+            if (!kept) sv.file_ok[f] = 2;
+        }
+    }
 
     EngineConfig cfg_;
     bsg_ctx *ctx_;
@@ -590,6 +663,7 @@ private:
     // every partition buffer got in it, numbered by first arrival (the blocks of a file are ordered by partition id)
     uint64_t stream_ = 0;
     std::map<std::string, uint32_t> stream_set_;
+    std::map<uint32_t, std::vector<bsg_minmax>> stream_minmax_host_;   // per set: the MinMax contributions of the rows the appends handed back
     bool stream_broken_ = false;         // an append failed (and ingest_rows said so): this flush builds from the kept rows
     StreamStats stream_stats_;
     uint64_t buffered_rows_ = 0, buffered_bytes_ = 0;
@@ -679,9 +753,11 @@ private:
     void block_stage_stats(const Survivors &sv, int64_t probe_share, QueryResult &out, std::vector<ScanBlock> &scanned)
     {
         for (size_t f = 0; f < files_.size(); ++f) {
+            if (sv.file_ok[f] == 2) continue;                               // the prefilter left it no block: not considered at all
             out.files_considered++;
             if (!sv.file_ok[f]) { out.files_bloom_skipped++; continue; }   // file stage prune: no BlockStats for its blocks
             for (size_t b = 0; b < files_[f].blocks.size(); ++b) {
+                if (sv.block_ok[f][b] == 3) continue;                       // failed the prefilter: neither scanned nor listed
                 const DataBlock &blk = files_[f].blocks[b];
                 BlockStats st;
                 st.file_id = files_[f].file_id; st.block_offset = blk.block_offset;
@@ -845,6 +921,7 @@ private:
         if (stream_) bsg_ingest_free(ctx_, stream_);
         stream_ = 0;
         stream_set_.clear();
+        stream_minmax_host_.clear();
     }
 
     // DeviceIngestStream, ingest time (ingest.go:444-450 with indexRow on the device): one validated batch -> the open stream.
@@ -853,6 +930,14 @@ private:
     int32_t stream_append(const std::vector<std::string_view> &rows, const std::vector<std::string> &pids)
     {
         const bsg_tokenizer tok = c_tokenizer();
+        const size_t nf = cfg_.minmax_indexes.size();
+        if (!stream_ && nf) {                       // the appends fold the sets' MinMax indexes too
+            std::vector<uint8_t> fb_bytes;
+            std::vector<uint32_t> f_off;
+            pack_minmax_fields(fb_bytes, f_off);
+            if (bsg_ingest_open_minmax(ctx_, 0, nullptr, 1, nullptr, BSG_INGEST_TRUSTED_JSON, &tok, &stream_, fb_bytes.data(), f_off.data(), (uint32_t)nf))
+                return fail(kErrGpu, bsg_last_error(ctx_));
+        }
         if (!stream_ && bsg_ingest_open(ctx_, 0, nullptr, 1, nullptr, BSG_INGEST_TRUSTED_JSON /* ingest_rows validated every row */, &tok, &stream_))
             return fail(kErrGpu, bsg_last_error(ctx_));
         std::vector<uint32_t> set_of_row(rows.size());
@@ -877,7 +962,14 @@ private:
             return fail(kErrGpu, bsg_last_error(ctx_));
         if (n_fb) {
             std::map<uint32_t, BloomEntrySets> per_set;
-            for (uint32_t i = 0; i < n_fb; ++i) per_set.try_emplace(set_of_row[fb[i]], cfg_.tokenizer).first->second.index_row(rows[fb[i]]);
+            for (uint32_t i = 0; i < n_fb; ++i) {
+                per_set.try_emplace(set_of_row[fb[i]], cfg_.tokenizer).first->second.index_row(rows[fb[i]]);
+                if (nf) {                           // ... and folded on the host: the device decided nothing of such a row, or the same values
+                    std::vector<bsg_minmax> &idx = stream_minmax_host_[set_of_row[fb[i]]];
+                    idx.resize(nf, bsg_minmax{});
+                    minmax_row(rows[fb[i]], cfg_.minmax_indexes, idx.data());
+                }
+            }
             if (int32_t rc = add_host_entries(stream_, per_set)) return rc;
         }
         stream_stats_.batches += 1;
@@ -890,7 +982,7 @@ private:
     // bsg_ingest_build_sections.  The stream numbers its sets by first arrival, the file orders its blocks by partition id: the
     // sections and counts are permuted into block order, and no resident arena is asked for (its block i would be set i); the
     // file's arena is decoded from the stored sections by the first query, as without DeviceIngest.
-    int32_t build_sections_stream(DataFile &file, std::vector<std::vector<uint8_t>> &sections)
+    int32_t build_sections_stream(DataFile &file, std::vector<std::vector<uint8_t>> &sections, bool &minmax_done)
     {
         const size_t nb = file.blocks.size();
         std::vector<uint32_t> set_of_block(nb);
@@ -899,6 +991,18 @@ private:
             if (it == stream_set_.end() || stream_set_.size() != nb)    // every buffered row was appended: anything else is a bug here
                 return fail(kErrGpu, "the streaming ingest does not hold the partitions of this flush");
             set_of_block[b] = it->second;
+        }
+        if (const size_t nf = cfg_.minmax_indexes.size()) {    // what the appends folded on the device, and the handed-back rows' share
+            std::vector<bsg_minmax> index(nb * nf);
+            if (bsg_ingest_minmax(ctx_, stream_, index.data(), index.size())) return fail(kErrGpu, bsg_last_error(ctx_));
+            for (size_t b = 0; b < nb; ++b) {
+                bsg_minmax *idx = index.data() + (size_t)set_of_block[b] * nf;
+                const auto host = stream_minmax_host_.find(set_of_block[b]);
+                for (size_t f = 0; f < nf && host != stream_minmax_host_.end(); ++f)
+                    if (host->second[f].present) minmax_fold(idx[f], host->second[f].min, host->second[f].max);
+                set_block_minmax(file.blocks[b], idx, nf);
+            }
+            minmax_done = true;
         }
         std::vector<uint64_t> counts((nb + 1) * 3);
         std::vector<uint32_t> status(nb + 1);
@@ -934,7 +1038,9 @@ private:
     // bsg_ingest_rows, the rows it hands back -> host walker -> bsg_ingest_add_entries, exact counts ->
     // EstimateParameters on the host -> bsg_ingest_build -> encodeFilterSection.  Fills the blocks' and the
     // file's BloomEntryCounts.  sections = one per block, then the file-level one.
-    int32_t build_sections_device(DataFile &file, std::vector<std::vector<uint8_t>> &sections)
+    // minmax_done (flush only; merge unions its sources' indexes): the call computes the blocks' MinMax indexes too
+    // (bsg_ingest_rows_minmax), the rows it hands back folded on the host in the loop that walks them; set to true once they are in.
+    int32_t build_sections_device(DataFile &file, std::vector<std::vector<uint8_t>> &sections, bool *minmax_done = nullptr)
     {
         const size_t nb = file.blocks.size();
         std::vector<uint8_t> bytes;
@@ -950,10 +1056,20 @@ private:
         }
         uint64_t ing = 0;
         const bsg_tokenizer tok = c_tokenizer();
-        if (bsg_ingest_rows_tok(ctx_, bytes.data(), row_off.data(), (uint32_t)set_of_row.size(), first.data(), (uint32_t)nb,
-                                parent.data(), 1, nullptr, BSG_INGEST_TRUSTED_JSON /* ingest_rows validated every row */, &tok, &ing))
+        const size_t nf = minmax_done && !*minmax_done ? cfg_.minmax_indexes.size() : 0;
+        if (nf) {
+            std::vector<uint8_t> f_bytes;
+            std::vector<uint32_t> f_off;
+            pack_minmax_fields(f_bytes, f_off);
+            if (bsg_ingest_rows_minmax(ctx_, bytes.data(), row_off.data(), (uint32_t)set_of_row.size(), first.data(), (uint32_t)nb, parent.data(), 1, nullptr,
+                                       BSG_INGEST_TRUSTED_JSON, &tok, &ing, f_bytes.data(), f_off.data(), (uint32_t)nf))
+                return fail(kErrGpu, bsg_last_error(ctx_));
+        } else if (bsg_ingest_rows_tok(ctx_, bytes.data(), row_off.data(), (uint32_t)set_of_row.size(), first.data(), (uint32_t)nb,
+                                       parent.data(), 1, nullptr, BSG_INGEST_TRUSTED_JSON /* ingest_rows validated every row */, &tok, &ing))
             return fail(kErrGpu, bsg_last_error(ctx_));
         struct Free { bsg_ctx *c; uint64_t id; ~Free() { bsg_ingest_free(c, id); } } guard{ctx_, ing};
+        std::vector<bsg_minmax> index(nb * nf);
+        if (nf && bsg_ingest_minmax(ctx_, ing, index.data(), index.size())) return fail(kErrGpu, bsg_last_error(ctx_));
         uint32_t n_fb = 0;
         if (bsg_ingest_fallback_rows(ctx_, ing, nullptr, 0, &n_fb)) return fail(kErrGpu, bsg_last_error(ctx_));
         if (n_fb) {
@@ -963,8 +1079,13 @@ private:
             for (uint32_t r : fb) {
                 const uint32_t b = set_of_row[r];
                 per_set.try_emplace(b, cfg_.tokenizer).first->second.index_row(file.blocks[b].rows[r - first[b]]);
+                if (nf) minmax_row(file.blocks[b].rows[r - first[b]], cfg_.minmax_indexes, index.data() + (size_t)b * nf);
             }
             if (int32_t rc = add_host_entries(ing, per_set)) return rc;
+        }
+        if (nf) {
+            for (size_t b = 0; b < nb; ++b) set_block_minmax(file.blocks[b], index.data() + b * nf, nf);
+            *minmax_done = true;
         }
         std::vector<uint64_t> counts((nb + 1) * 3);
         std::vector<uint32_t> status(nb + 1);

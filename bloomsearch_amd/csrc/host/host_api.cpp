@@ -7,6 +7,7 @@
 
 #include "engine.hpp"
 #include "regex_dfa.hpp"
+#include "minmax.hpp"
 #include "range.hpp"
 #include "substring.hpp"
 
@@ -425,6 +426,43 @@ int32_t bsh_match_row_range(const char *range_json, uint64_t range_len, const ui
     return m.match(std::string_view(reinterpret_cast<const char *>(row), row_len)) ? 1 : 0;
 }
 
+// one row's MinMax contributions folded into inout[n_fields] (minmax.hpp minmax_row): 0, or < 0 for invalid fields / a row that is no JSON object
+int32_t bsh_minmax_row(const uint8_t *row, uint64_t len, const uint8_t *field_bytes, const uint32_t *field_off, uint32_t n_fields, bsg_minmax *inout)
+{
+    MinMaxFieldNames f;
+    std::string why;
+    if ((len && !row) || !inout || !f.unpack(field_bytes, field_off, n_fields, why)) return BSH_E_INVALID;
+    return minmax_row(std::string_view(reinterpret_cast<const char *>(row), len), f.names, inout) ? 0 : BSH_E_INVALID;
+}
+
+// EvaluateMinMaxCondition: 1 the block may hold a matching value, 0 it cannot, < 0 invalid arguments (an absent index included)
+int32_t bsh_minmax_eval(const bsg_minmax *index, uint32_t op, int64_t value, const int64_t *values, uint32_t n_values, int64_t min, int64_t max)
+{
+    if (!index || !index->present || op >= MM_OP_COUNT || (n_values && !values)) return BSH_E_INVALID;
+    return minmax_eval(index->min, index->max, op, value, values, n_values, min, max) ? 1 : 0;
+}
+
+// evaluatePrefilterExpression on one block: its partition id and the indexes it carries, named by the packed fields
+int32_t bsh_prefilter_eval(const char *prefilter_json, uint64_t len, const uint8_t *partition_id, uint64_t partition_len, const uint8_t *field_bytes,
+                           const uint32_t *field_off, uint32_t n_fields, const bsg_minmax *indexes)
+{
+    if ((len && !prefilter_json) || (partition_len && !partition_id) || (n_fields && (!field_bytes || !field_off || !indexes))) return BSH_E_INVALID;
+    const std::string_view text(prefilter_json ? prefilter_json : "", len);
+    std::map<std::string, bsg_minmax> have;
+    for (uint32_t f = 0; f < n_fields; ++f) {
+        if (field_off[f + 1] < field_off[f]) return BSH_E_INVALID;
+        if (indexes[f].present) have[std::string((const char *)field_bytes + field_off[f], field_off[f + 1] - field_off[f])] = indexes[f];
+    }
+    if (text.empty() || text == "null") return 1;                  // a nil expression: every block passes
+    JNode n;
+    PrefilterExpression e;
+    if (!parse_dom(text, n)) return BSH_E_INVALID;
+    if (n.type == JType::Null) return 1;
+    if (!prefilter_from_json(n, e)) return BSH_E_INVALID;
+    const PrefilterBlock b{std::string_view((const char *)partition_id, partition_len), &have};
+    return prefilter_eval(e, b) ? 1 : 0;
+}
+
 // the regex half of matchRowBytes (row_matcher.go:548-573): 1 match, 0 no match, < 0 invalid arguments / pattern
 int32_t bsh_match_row_regex(const char *regex_json, uint64_t regex_len, const uint8_t *row, uint64_t row_len)
 {
@@ -503,6 +541,13 @@ int32_t bse_open(const char *config_json, uint64_t len, bsg_ctx *ctx, bse_engine
         if (const JNode *n = dom.get("DeviceMatchLookup")) cfg.device_match_lookup = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchLookupRows")) cfg.device_match_lookup_rows = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchLookupRegex")) cfg.device_match_lookup_regex = n->type == JType::True;
+        if (const JNode *n = dom.get("MinMaxIndexes")) {       // ["timestamp", ...]; null or [] = none
+            if (n->type != JType::Null && n->type != JType::Array) return BSE_E_INVALID_CONFIG;
+            for (const JNode &f : n->items) {
+                if (f.type != JType::String) return BSE_E_INVALID_CONFIG;
+                cfg.minmax_indexes.push_back(f.text);
+            }
+        }
         if (const JNode *n = dom.get("Tokenizer")) {
             if (n->type != JType::Null && !tokenizer_from_json(*n, cfg.tokenizer)) return BSE_E_INVALID_CONFIG;
         }
@@ -546,7 +591,8 @@ struct ParsedQuery {
     RegexExpression regex;
     SubstringExpression sub;
     RangeExpression range;
-    bool nil = true, has_regex = false, has_sub = false, has_range = false;
+    PrefilterExpression prefilter;
+    bool nil = true, has_regex = false, has_sub = false, has_range = false, has_prefilter = false;
 };
 
 int32_t query_from_dom(const JNode &dom, ParsedQuery &q)
@@ -581,6 +627,17 @@ int32_t query_from_dom(const JNode &dom, ParsedQuery &q)
             const JNode *ex = rg->get("Expression");
             if (!range_expression_from_json(ex && ex->type == JType::Object ? *ex : *rg, q.range)) return BSE_E_INVALID_QUERY;
             q.has_range = true;
+        }
+        // "Prefilter": {"Expression": tree} in the reference's shape (QueryPrefilter); a nil Expression prunes nothing
+        const JNode *pf = dom.get("Prefilter");
+        if (pf && pf->type == JType::Object) {
+            const JNode *ex = pf->get("Expression");
+            if (ex && ex->type == JType::Object) {
+                if (!prefilter_from_json(*ex, q.prefilter)) return BSE_E_INVALID_QUERY;
+                q.has_prefilter = true;
+            }
+        } else if (pf && pf->type != JType::Null) {
+            return BSE_E_INVALID_QUERY;
         }
     } else if (dom.type != JType::Null) {
         return BSE_E_INVALID_QUERY;
@@ -620,7 +677,8 @@ int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, char **ou
         if (int32_t rc = query_from_dom(dom, q)) return rc;
     }
     QueryResult res;
-    if (int32_t rc = e->eng->query(q.nil ? nullptr : &q.expr, res, q.has_regex ? &q.regex : nullptr, q.has_sub ? &q.sub : nullptr, q.has_range ? &q.range : nullptr)) return rc;
+    if (int32_t rc = e->eng->query(q.nil ? nullptr : &q.expr, res, q.has_regex ? &q.regex : nullptr, q.has_sub ? &q.sub : nullptr, q.has_range ? &q.range : nullptr,
+                                    q.has_prefilter ? &q.prefilter : nullptr)) return rc;
     std::string out;
     result_to_json(res, out);
     return give(out, out_json, out_len);
@@ -638,12 +696,14 @@ int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, ch
     std::vector<const RegexExpression *> regexes;
     std::vector<const SubstringExpression *> subs;
     std::vector<const RangeExpression *> ranges;
+    std::vector<const PrefilterExpression *> prefilters;
     for (const ParsedQuery &q : qs) {
+        prefilters.push_back(q.has_prefilter ? &q.prefilter : nullptr);
         exprs.push_back(q.nil ? nullptr : &q.expr); regexes.push_back(q.has_regex ? &q.regex : nullptr); subs.push_back(q.has_sub ? &q.sub : nullptr);
         ranges.push_back(q.has_range ? &q.range : nullptr);
     }
     std::vector<QueryResult> res;
-    if (int32_t rc = e->eng->query_many(exprs, regexes, res, &subs, &ranges)) return rc;
+    if (int32_t rc = e->eng->query_many(exprs, regexes, res, &subs, &ranges, &prefilters)) return rc;
     std::string out = "[";
     for (size_t i = 0; i < res.size(); ++i) { if (i) out.push_back(','); result_to_json(res[i], out); }
     out.push_back(']');
@@ -693,7 +753,19 @@ int32_t bse_describe(bse_engine *e, char **out_json, uint64_t *out_len)
             json_escape(out, blk.partition_id);
             out += ",\"Rows\":" + std::to_string(blk.rows.size()) + ",\"BlockOffset\":" + std::to_string(blk.block_offset) +
                    ",\"BloomEntryCounts\":" + counts(blk.counts) + ",\"BloomFalsePositiveRate\":" + std::to_string(blk.fpr) +
-                   ",\"BloomFilterSize\":" + std::to_string(blk.filter_section.size()) + ",\"filters\":" + filters(blk.filter_section) + "}";
+                   ",\"BloomFilterSize\":" + std::to_string(blk.filter_section.size()) + ",\"filters\":" + filters(blk.filter_section);
+            if (!blk.minmax.empty()) {             // DataBlockMetadata.MinMaxIndexes (omitempty)
+                out += ",\"MinMaxIndexes\":{";
+                bool first_i = true;
+                for (const auto &kv : blk.minmax) {
+                    if (!first_i) out.push_back(',');
+                    first_i = false;
+                    json_escape(out, kv.first);
+                    out += ":{\"Min\":" + std::to_string(kv.second.min) + ",\"Max\":" + std::to_string(kv.second.max) + "}";
+                }
+                out.push_back('}');
+            }
+            out.push_back('}');
         }
         out += "]}";
     }

@@ -31,6 +31,10 @@ struct IngestPart {
     std::vector<uint32_t> counts, status;     // last read back
     bool finished = false;
     bsg_ingest_stats stats{};
+    const bsg::MinMaxFields *mm = nullptr;    // the ingest was opened with MinMax fields (Ingest::mm_fields): k_minmax_rows runs once per upload chunk
+    bsg::MinMaxRec *d_mm = nullptr;           // [mm_cap * mm->n]: per (set, field), folded over every walk so far
+    uint32_t mm_cap = 0;                      // sets d_mm has room for
+    float ms_minmax = 0.f;                    // k_minmax_rows dispatch time of the last call
     uint32_t n_tables() const { return (n_sets + n_parents) * 3; }
 };
 
@@ -47,6 +51,8 @@ struct Ingest {
     uint32_t flags = 0;                       // (streaming) BSG_INGEST_* of bsg_ingest_open, applied to every append
     bsg::TokSpec spec{};                      // (streaming) the kernels' form of tok; tok_default: the default tokenizer's kernels serve
     bool tok_default = true;
+    bool has_mm = false;                      // made by bsg_ingest_rows_minmax / bsg_ingest_open_minmax
+    bsg::MinMaxFields mm_fields{};
     bool finished = false;
     float ms_merge = 0.f, ms_build = 0.f, ms_encode = 0.f;
     uint32_t n_tables() const { return (n_sets + n_parents) * 3; }
@@ -59,6 +65,7 @@ void free_part(IngestPart &g)                 // caller holds the device lock
     g.mem.clear();
     g.d_tables = nullptr; g.d_counts = g.d_status = nullptr;
     g.d_set_first = g.d_nfb = nullptr;
+    g.d_mm = nullptr; g.mm_cap = 0;
 }
 
 void free_ingest(Ingest &g)
@@ -252,10 +259,12 @@ int32_t get_ingest(bsg_ctx *ctx, uint64_t id, std::shared_ptr<Ingest> &out)
 // the compute stream walks chunk c, and a chunk is walked again after a table it overflowed has grown.  a: the launch arguments
 // but for the tables and the row range; tables [0, n_set_tables) are inserted into.  stage(c), right before chunk c's bytes are
 // enqueued, sends along what must have landed with them (on up.cs: the chunk's landed event covers it); launch(b, grid, e0, e1)
-// enqueues the walker over b on d.stream.  Caller holds the device lock; G.d_nfb has been zeroed on d.stream.
-template <class Stage, class Launch>
+// enqueues the walker over b on d.stream; once(c, rf, re) runs ONCE per chunk, right after the chunk's bytes are known to land before
+// it and before the chunk's first walk, never again when the walk is re-run (the MinMax scanner: its fold is not rewound).
+// Caller holds the device lock; G.d_nfb has been zeroed on d.stream.
+template <class Stage, class Launch, class Once>
 int32_t walk_chunks(Device &d, IngestPart &G, RowUpload &up, const bsg::IngestArgs &a, uint32_t n_set_tables, const LabTrace &trace,
-                    Stage &&stage, Launch &&launch)
+                    Stage &&stage, Launch &&launch, Once &&once)
 {
     const uint32_t n_chunks = up.n_chunks();
     HIP_TRY(up.start(true));
@@ -269,7 +278,10 @@ int32_t walk_chunks(Device &d, IngestPart &G, RowUpload &up, const bsg::IngestAr
         if (c) HIP_TRY(hipMemcpy(&nfb_before, G.d_nfb, 4, hipMemcpyDeviceToHost));   // K(c-1) has been synchronised
         int32_t rc = run_until_fits(G, 0, n_set_tables, &G.stats.ms_walk, [&](hipEvent_t e0, hipEvent_t e1) -> int32_t {
             if (!first_attempt) HIP_TRY(hipMemcpyAsync(G.d_nfb, &nfb_before, 4, hipMemcpyHostToDevice, d.stream));   // a re-run lists its rows again
-            else HIP_TRY(up.wait_landed(c));
+            else {
+                HIP_TRY(up.wait_landed(c));
+                if (int32_t rc2 = once(c, rf, re)) return rc2;
+            }
             bsg::IngestArgs b = a;
             b.tables = G.d_tables;
             b.row_first = rf; b.row_end = re;
@@ -292,6 +304,110 @@ int32_t walk_chunks(Device &d, IngestPart &G, RowUpload &up, const bsg::IngestAr
     }
     return BSG_OK;
 }
+
+// ---- MinMax indexes (minmax.hip.h): the fields of bsg_ingest_rows_minmax / bsg_ingest_open_minmax ----
+
+// 1 to 8 distinct names of 1 to 64 bytes, packed like bsg_hash_entries' input.  Answered before anything is launched.
+int32_t minmax_fields(const uint8_t *field_bytes, const uint32_t *field_off, uint32_t n_fields, bsg::MinMaxFields &out)
+{
+    if (n_fields == 0 || n_fields > BSG_MINMAX_MAX_FIELDS)
+        return fail(BSG_E_INVALID, "minmax: n_fields = %u (1 to %u)", n_fields, BSG_MINMAX_MAX_FIELDS);
+    if (!field_bytes || !field_off) return fail(BSG_E_INVALID, "minmax: field_bytes / field_off is null");
+    out = bsg::MinMaxFields{};
+    out.n = n_fields;
+    for (uint32_t f = 0; f < n_fields; ++f) {
+        if (field_off[f + 1] < field_off[f]) return fail(BSG_E_INVALID, "minmax: field_off not monotone at field %u", f);
+        const uint32_t len = field_off[f + 1] - field_off[f];
+        if (len == 0) return fail(BSG_E_INVALID, "minmax: field %u has an empty name", f);
+        if (len > BSG_MINMAX_MAX_NAME) return fail(BSG_E_INVALID, "minmax: the name of field %u has %u bytes (at most %u)", f, len, BSG_MINMAX_MAX_NAME);
+        memcpy(out.name + (size_t)f * bsg::kMinMaxMaxName, field_bytes + field_off[f], len);
+        out.len[f] = (uint8_t)len;
+        for (uint32_t g = 0; g < f; ++g)
+            if (out.len[g] == len && !memcmp(out.name + (size_t)g * bsg::kMinMaxMaxName, out.name + (size_t)f * bsg::kMinMaxMaxName, len))
+                return fail(BSG_E_INVALID, "minmax: fields %u and %u have the same name", g, f);
+    }
+    return BSG_OK;
+}
+
+// Room for n_sets sets in G.d_mm; what the sets before have folded travels along.  Everything behind them starts absent.
+int32_t minmax_reserve(IngestPart &G, uint32_t n_sets, bool roomy)
+{
+    if (!G.mm || (G.d_mm && n_sets <= G.mm_cap)) return BSG_OK;
+    const uint32_t nf = G.mm->n;
+    const uint64_t room = roomy ? std::max<uint64_t>(32, (uint64_t)n_sets * 2) : std::max<uint64_t>(n_sets, 1);
+    if (room * nf > 0x7FFFFFFFull) return fail(BSG_E_INVALID, "minmax: too many sets");
+    bsg::MinMaxRec *fresh = nullptr;
+    HIP_TRY(G.mem.alloc(&fresh, (size_t)room * nf * sizeof(bsg::MinMaxRec)));
+    const uint32_t n_rec = (uint32_t)(room * nf);
+    hipLaunchKernelGGL(bsg::k_minmax_init, dim3((n_rec + 255u) / 256u), dim3(256), 0, G.dev->stream, fresh, 0u, n_rec);
+    HIP_TRY(hipGetLastError());
+    if (G.d_mm && G.mm_cap)
+        HIP_TRY(hipMemcpyAsync(fresh, G.d_mm, (size_t)G.mm_cap * nf * sizeof(bsg::MinMaxRec), hipMemcpyDeviceToDevice, G.dev->stream));
+    G.d_mm = fresh;                           // (the block before stays with G.mem until the ingest is freed)
+    G.mm_cap = (uint32_t)room;
+    return BSG_OK;
+}
+
+// The scanner's side of one row walk: its own hand-back list (the walker's is rewound when a chunk is walked again; this one never
+// is), one pair of events per chunk, and the launch walk_chunks runs once per chunk.
+struct MinMaxWalk {
+    IngestPart &G;
+    bsg::MinMaxArgs a{};
+    const bsg::RowsBySet *by_set = nullptr;   // NULL: RowsGrouped
+    EventList ev;
+    uint32_t *d_nfb = nullptr;
+    explicit MinMaxWalk(IngestPart &g) : G(g) {}
+    bool on() const { return G.mm != nullptr; }
+    int32_t prepare(Scratch &scratch, const bsg::IngestArgs &w, uint32_t n_rows, const bsg::RowsBySet *rows_by_set)
+    {
+        if (!on()) return BSG_OK;
+        by_set = rows_by_set;
+        a.rows = w.rows; a.row_off = w.row_off; a.set_first_row = w.set_first_row;
+        a.result = G.d_mm; a.n_sets = w.n_sets;
+        HIP_TRY(scratch.alloc(&a.fallback_rows, std::max<size_t>(n_rows, 1) * 4));
+        HIP_TRY(scratch.alloc(&d_nfb, 64));
+        a.n_fallback = d_nfb;
+        HIP_TRY(hipMemsetAsync(d_nfb, 0, 64, G.dev->stream));
+        G.ms_minmax = 0.f;
+        return BSG_OK;
+    }
+    int32_t launch(uint32_t rf, uint32_t re)
+    {
+        if (!on() || re <= rf) return BSG_OK;
+        Device &d = *G.dev;
+        HIP_TRY(ev.add(2));
+        bsg::MinMaxArgs b = a;
+        b.row_first = rf; b.row_end = re;
+        const uint64_t n = re - rf, max_waves = (uint64_t)d.n_cus * 4 * 8;      // a contiguous run of rows per wave, as the walkers
+        const uint64_t waves = std::min<uint64_t>((n + 63) / 64, max_waves);
+        b.rows_per_wave = (uint32_t)(((n + waves - 1) / waves + 63) / 64 * 64);
+        const uint64_t used = (n + b.rows_per_wave - 1) / b.rows_per_wave, wpw = bsg::kMinMaxThreads / 64;
+        const uint32_t grid = (uint32_t)((used + wpw - 1) / wpw), lds = bsg::minmax_lds_bytes(G.mm->n);
+        hipEvent_t e0 = ev.v[ev.v.size() - 2], e1 = ev.v.back();
+        if (by_set) hipExtLaunchKernelGGL(bsg::k_minmax_rows_sets, dim3(grid), dim3(bsg::kMinMaxThreads), lds, d.stream, e0, e1, 0, b, *G.mm, *by_set);
+        else hipExtLaunchKernelGGL(bsg::k_minmax_rows, dim3(grid), dim3(bsg::kMinMaxThreads), lds, d.stream, e0, e1, 0, b, *G.mm);
+        HIP_TRY(hipGetLastError());
+        return BSG_OK;
+    }
+    // after the walk (d.stream synchronised): the rows the scanner did not decide join fb; ascending, each once
+    int32_t merge_fallback(std::vector<uint32_t> &fb)
+    {
+        if (!on()) return BSG_OK;
+        uint32_t n = 0;
+        HIP_TRY(hipMemcpy(&n, d_nfb, 4, hipMemcpyDeviceToHost));
+        const size_t before = fb.size();
+        fb.resize(before + n);
+        if (n) HIP_TRY(hipMemcpy(fb.data() + before, a.fallback_rows, (size_t)n * 4, hipMemcpyDeviceToHost));
+        std::sort(fb.begin(), fb.end());
+        fb.erase(std::unique(fb.begin(), fb.end()), fb.end());
+        for (size_t i = 0; i + 1 < ev.v.size(); i += 2) {
+            float t = 0.f;
+            HIP_TRY(hipEventElapsedTime(&t, ev.v[i], ev.v[i + 1]));
+            G.ms_minmax += t;
+        }
+        return BSG_OK;
+    }
+};
 
 // One part: rows [0, n_rows) of `rows` (row_off relative to `rows`), n_sets sets, on device d.
 int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -370,6 +486,9 @@ int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *
         if (int32_t rc = ensure_lower_table(d)) return rc;
         a.lower = d.d_lower;
         HIP_TRY(hipMemsetAsync(G.d_nfb, 0, 128, d.stream));
+        if (int32_t rc = minmax_reserve(G, n_sets, false)) return rc;
+        MinMaxWalk mmw(G);
+        if (int32_t rc = mmw.prepare(scratch, a, n_rows, nullptr)) return rc;
         // The rows travel in chunks on the copy stream while the compute stream walks the chunk before (RowUpload)
         RowUpload up(d, rows, d_rows, row_off, n_rows, ctx->ingest_chunk_bytes);
         if (int32_t rc = walk_chunks(d, G, up, a, n_sets * 3, trace, [](uint32_t) { return hipSuccess; },
@@ -380,7 +499,8 @@ int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *
                         hipExtLaunchKernelGGL(bsg::k_ingest_rows_tok, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, *tok);
                     else
                         hipExtLaunchKernelGGL(bsg::k_ingest_rows, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b);
-                })) return rc;
+                },
+                [&](uint32_t, uint32_t rf, uint32_t re) { return mmw.launch(rf, re); })) return rc;
         HIP_TRY(hipStreamSynchronize(d.copy_stream));
         trace.lap("all chunks walked");
         uint32_t nfb = 0;
@@ -399,7 +519,9 @@ int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *
         g->fallback.resize(nfb);
         if (nfb) HIP_TRY(hipMemcpy(g->fallback.data(), d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
         std::sort(g->fallback.begin(), g->fallback.end());
+        if (int32_t rc = mmw.merge_fallback(g->fallback)) return rc;
     } else {
+        if (int32_t rc = minmax_reserve(G, n_sets, false)) return rc;
         if (int32_t rc = read_state(*g)) return rc;
     }
     g->stats.n_fallback_rows = (uint32_t)g->fallback.size();
@@ -687,7 +809,8 @@ int32_t merge_parents(bsg_ctx *ctx, Ingest &I)
 // bsg_ingest_rows (tok_in NULL) and bsg_ingest_rows_tok
 int32_t ingest_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
                          const uint32_t *set_first_row, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents,
-                         const uint32_t *slots_hint, uint32_t flags, const bsg_tokenizer *tok_in, uint64_t *out_ingest_id)
+                         const uint32_t *slots_hint, uint32_t flags, const bsg_tokenizer *tok_in, uint64_t *out_ingest_id,
+                         const bsg::MinMaxFields *mm = nullptr)
 {
     if (!ctx) return fail(BSG_E_INVALID, "ctx is null");
     bsg_tokenizer rec{};
@@ -710,6 +833,7 @@ int32_t ingest_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_
     auto I = std::make_shared<Ingest>();
     I->n_rows = n_rows; I->n_sets = n_sets; I->n_parents = n_parents;
     I->tok = rec;
+    if (mm) { I->has_mm = true; I->mm_fields = *mm; }
     I->parent_of_set.assign(n_sets, 0xFFFFFFFFu);
     if (parent_of_set) I->parent_of_set.assign(parent_of_set, parent_of_set + n_sets);
     // parts: contiguous runs of sets, about equal in row bytes, one per device
@@ -729,6 +853,7 @@ int32_t ingest_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_
         IngestPart &G = *I->parts[i];
         const uint32_t s0 = I->set_cut[i], s1 = I->set_cut[i + 1], r0 = set_first_row[s0], r1 = set_first_row[s1];
         G.set0 = s0; G.row0 = r0;
+        G.mm = I->has_mm ? &I->mm_fields : nullptr;
         Device &d = *G.dev;
         if (np == 1)
             return ingest_rows_part(ctx, d, G, rows, row_off, n_rows, set_first_row, n_sets, parent_of_set, n_parents, slots_hint, flags, tok);
@@ -742,10 +867,14 @@ int32_t ingest_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_
                                 n_parents, slots_hint ? slots_hint + (size_t)s0 * 3 : nullptr, flags, tok);
     });
     if (rc) { free_ingest(*I); return rc; }
-    for (auto &p : I->parts)
+    float ms_minmax = 0.f;
+    for (auto &p : I->parts) {
         for (uint32_t r : p->fallback) I->fallback.push_back(r + p->row0);
+        ms_minmax = std::max(ms_minmax, p->ms_minmax);
+    }
     std::sort(I->fallback.begin(), I->fallback.end());
     std::lock_guard<std::shared_mutex> lk2(ctx->mu);
+    if (mm) ctx->last_minmax_ms = ms_minmax;
     const uint64_t id = ctx->next_id++;
     ctx->ingests[id] = I;
     *out_ingest_id = id;
@@ -807,6 +936,7 @@ int32_t stream_add_sets(IngestPart &G, uint32_t n_more, const uint32_t *parent_o
     G.n_sets = new_sets;
     for (uint32_t i = 0; i < n_more; ++i) G.parent_of_set.push_back(parent_of_new_set ? parent_of_new_set[i] : 0xFFFFFFFFu);
     if (nt) if (int32_t rc = push_tables(G)) return rc;
+    if (int32_t rc = minmax_reserve(G, new_sets, true)) return rc;
     HIP_TRY(hipStreamSynchronize(d.stream));
     return BSG_OK;
 }
@@ -820,9 +950,10 @@ int32_t check_parents(const uint32_t *parent_of_set, uint32_t n_sets, uint32_t n
 }
 
 int32_t ingest_open_call(bsg_ctx *ctx, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents, const uint32_t *slots_hint,
-                         uint32_t flags, const bsg_tokenizer *tok_in, uint64_t *out_ingest_id)
+                         uint32_t flags, const bsg_tokenizer *tok_in, uint64_t *out_ingest_id, const bsg::MinMaxFields *mm = nullptr)
 {
     auto I = std::make_shared<Ingest>();
+    if (mm) { I->has_mm = true; I->mm_fields = *mm; }
     if (int32_t rc = tok_spec(tok_in, I->tok, I->spec, I->tok_default)) return rc;
     if (!out_ingest_id) return fail(BSG_E_INVALID, "null argument");
     if (flags & ~BSG_INGEST_TRUSTED_JSON) return fail(BSG_E_INVALID, "unknown flags 0x%x", flags);
@@ -836,6 +967,7 @@ int32_t ingest_open_call(bsg_ctx *ctx, uint32_t n_sets, const uint32_t *parent_o
     I->parts.push_back(P);
     IngestPart &G = *P;
     G.n_parents = n_parents;
+    G.mm = I->has_mm ? &I->mm_fields : nullptr;
     int32_t rc = BSG_OK;
     {
         std::lock_guard<std::mutex> lk(d.mu);
@@ -906,6 +1038,8 @@ int32_t append_rows_stream(bsg_ctx *ctx, Ingest &I, const uint8_t *rows, const u
     if (int32_t rc = ensure_lower_table(d)) return rc;
     a.lower = d.d_lower;
     const bsg::RowsBySet by_set{d_order, d_set_of_order};
+    MinMaxWalk mmw(G);
+    if (int32_t rc = mmw.prepare(scratch, a, n_rows, &by_set)) return rc;
     std::vector<uint32_t> order(n_rows), set_of_order(n_rows), group_scratch;
     RowUpload up(d, rows, d_rows, row_off, n_rows, ctx->ingest_chunk_bytes);
     if (int32_t rc = walk_chunks(d, G, up, a, G.n_sets * 3, trace,
@@ -923,15 +1057,19 @@ int32_t append_rows_stream(bsg_ctx *ctx, Ingest &I, const uint8_t *rows, const u
                     hipExtLaunchKernelGGL(bsg::k_ingest_rows_sets_tok, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, by_set, I.spec);
                 else
                     hipExtLaunchKernelGGL(bsg::k_ingest_rows_sets, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, by_set);
-            })) return rc;
+            },
+            [&](uint32_t, uint32_t rf, uint32_t re) { return mmw.launch(rf, re); })) return rc;
     HIP_TRY(hipStreamSynchronize(d.copy_stream));
     trace.lap("all chunks walked");
     uint32_t nfb = 0;
     HIP_TRY(hipMemcpy(&nfb, G.d_nfb, 4, hipMemcpyDeviceToHost));
     std::vector<uint32_t> fb(nfb);
     if (nfb) HIP_TRY(hipMemcpy(fb.data(), d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
-    scratch.done();                        // both streams have been synchronised: the row bytes leave the device here
     std::sort(fb.begin(), fb.end());
+    if (int32_t rc = mmw.merge_fallback(fb)) return rc;
+    nfb = (uint32_t)fb.size();
+    { std::lock_guard<std::shared_mutex> lk2(ctx->mu); ctx->last_minmax_ms = G.ms_minmax; }
+    scratch.done();                        // both streams have been synchronised: the row bytes leave the device here
     *n_fallback = nfb;
     // a call that could not deliver its list is appended again (or walked on the host): its rows are counted by the call that does
     const bool count_only = !out_fallback_rows && fallback_cap == 0;
@@ -979,6 +1117,66 @@ int32_t bsg_ingest_open(bsg_ctx *ctx, uint32_t n_sets, const uint32_t *parent_of
 {
     BSG_ENTER(ctx);
     return ingest_open_call(ctx, n_sets, parent_of_set, n_parents, slots_hint, flags, tok, out_ingest_id);
+}
+
+int32_t bsg_ingest_rows_minmax(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                               const uint32_t *set_first_row, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents,
+                               const uint32_t *slots_hint, uint32_t flags, const bsg_tokenizer *tok, uint64_t *out_ingest_id,
+                               const uint8_t *field_bytes, const uint32_t *field_off, uint32_t n_fields)
+{
+    BSG_ENTER(ctx);
+    bsg::MinMaxFields mm;
+    if (int32_t rc = minmax_fields(field_bytes, field_off, n_fields, mm)) return rc;
+    return ingest_rows_call(ctx, rows, row_off, n_rows, set_first_row, n_sets, parent_of_set, n_parents, slots_hint, flags, tok, out_ingest_id, &mm);
+}
+
+int32_t bsg_ingest_open_minmax(bsg_ctx *ctx, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents, const uint32_t *slots_hint,
+                               uint32_t flags, const bsg_tokenizer *tok, uint64_t *out_ingest_id,
+                               const uint8_t *field_bytes, const uint32_t *field_off, uint32_t n_fields)
+{
+    BSG_ENTER(ctx);
+    bsg::MinMaxFields mm;
+    if (int32_t rc = minmax_fields(field_bytes, field_off, n_fields, mm)) return rc;
+    return ingest_open_call(ctx, n_sets, parent_of_set, n_parents, slots_hint, flags, tok, out_ingest_id, &mm);
+}
+
+int32_t bsg_ingest_minmax(bsg_ctx *ctx, uint64_t ingest_id, bsg_minmax *out, uint64_t cap)
+{
+    BSG_ENTER(ctx);
+    std::shared_ptr<Ingest> g;
+    if (int32_t rc = get_ingest(ctx, ingest_id, g)) return rc;
+    Ingest &I = *g;
+    if (!I.has_mm) return fail(BSG_E_INVALID, "bsg_ingest_minmax: ingest %llu was made without MinMax fields", (unsigned long long)ingest_id);
+    const uint32_t nf = I.mm_fields.n;
+    const uint64_t need = (uint64_t)I.n_sets * nf;
+    if (need && !out) return fail(BSG_E_INVALID, "null argument");
+    if (need > cap) return fail(BSG_E_INVALID, "bsg_ingest_minmax: %llu records, out has room for %llu", (unsigned long long)need, (unsigned long long)cap);
+    // every part owns its sets' records: the devices' partial results are folded by placing them
+    for (auto &p : I.parts) {
+        IngestPart &G = *p;
+        if (!G.n_sets) continue;
+        std::lock_guard<std::mutex> lk(G.dev->mu);
+        if (int32_t rc = use_device(*G.dev)) return rc;
+        if (!G.d_mm || G.n_sets > G.mm_cap || (uint64_t)G.set0 + G.n_sets > I.n_sets) return fail(BSG_E_INVALID, "bsg_ingest_minmax: the ingest holds no result");
+        static_assert(sizeof(bsg_minmax) == sizeof(bsg::MinMaxRec), "bsg_minmax is the device record");
+        HIP_TRY(hipStreamSynchronize(G.dev->stream));
+        HIP_TRY(hipMemcpy(out + (size_t)G.set0 * nf, G.d_mm, (size_t)G.n_sets * nf * sizeof(bsg_minmax), hipMemcpyDeviceToHost));
+    }
+    for (uint64_t i = 0; i < need; ++i) {
+        out[i].reserved = 0;
+        if (!out[i].present) out[i].min = out[i].max = 0;       // an absent index: the fold's neutral elements stay inside
+        else out[i].present = 1;
+    }
+    return BSG_OK;
+}
+
+int32_t bsg_last_minmax_ms(bsg_ctx *ctx, float *minmax_ms)
+{
+    BSG_ENTER(ctx);
+    if (!minmax_ms) return fail(BSG_E_INVALID, "null argument");
+    std::shared_lock<std::shared_mutex> lk(ctx->mu);
+    *minmax_ms = ctx->last_minmax_ms;
+    return BSG_OK;
 }
 
 int32_t bsg_ingest_add_sets(bsg_ctx *ctx, uint64_t ingest_id, uint32_t n_more, const uint32_t *parent_of_new_set,

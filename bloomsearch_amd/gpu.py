@@ -129,6 +129,7 @@ class Context:
         self.h = h
         self.n_devices = len(device_ids)
         self._dependents = weakref.WeakSet()     # objects that hold this handle (host.Engine): closed before the context is
+        self._minmax_fields = {}                 # ingest id -> number of MinMax fields (the shape ingest_minmax returns)
 
     def _check(self, rc):
         if rc:
@@ -383,6 +384,7 @@ class Context:
         sc = Context.__new__(Context)
         sc.L, sc.h, sc.n_devices = self.L, h, self.n_devices
         sc._dependents = weakref.WeakSet()
+        sc._minmax_fields = self._minmax_fields
         return sc
 
     def probe(self, arena_id: int, n_blocks: int, terms: np.ndarray, prog_ops, prog_off) -> np.ndarray:
@@ -497,9 +499,11 @@ class Context:
 
     # ---- device ingest (rows -> distinct entries -> counts -> bitsets) ----
     def ingest_rows(self, rows, set_first_row, parent_of_set=None, n_parents: int = 0, slots_hint=None, flags: int = 0,
-                    tokenizer=None) -> int:
+                    tokenizer=None, minmax_fields=None) -> int:
         """rows: list[bytes] (or (u8 blob, u64 offsets[n+1])); returns the ingest id.  tokenizer: None = bsg_ingest_rows
-        (the default tokenizer); a tokenizer.Tokenizer = bsg_ingest_rows_tok under that spec."""
+        (the default tokenizer); a tokenizer.Tokenizer = bsg_ingest_rows_tok under that spec.  minmax_fields: None, or the names
+        (str / bytes) of the top-level keys whose per-set MinMax indexes the call computes too (bsg_ingest_rows_minmax; read them
+        with ingest_minmax)."""
         if isinstance(rows, tuple):
             blob, off = rows
             blob = np.ascontiguousarray(blob, dtype=np.uint8)
@@ -513,6 +517,14 @@ class Context:
         pos = None if parent_of_set is None else np.ascontiguousarray(parent_of_set, dtype=np.uint32)
         hint = None if slots_hint is None else np.ascontiguousarray(slots_hint, dtype=np.uint32)
         out = C.c_uint64()
+        if minmax_fields is not None:
+            fblob, foff = pack_entries([f.encode() if isinstance(f, str) else bytes(f) for f in minmax_fields])
+            self._check(self.L.bsg_ingest_rows_minmax(self.h, _lib._ptr(blob), _lib._ptr(off), len(off) - 1, _lib._ptr(sfr), len(sfr) - 1,
+                                                      _lib._ptr(pos), n_parents, _lib._ptr(hint), flags,
+                                                      None if tokenizer is None else c_spec(tokenizer), C.byref(out),
+                                                      fblob.ctypes.data, foff.ctypes.data, len(foff) - 1))
+            self._minmax_fields[int(out.value)] = len(foff) - 1
+            return int(out.value)
         if tokenizer is not None:
             self._check(self.L.bsg_ingest_rows_tok(self.h, _lib._ptr(blob), _lib._ptr(off), len(off) - 1, _lib._ptr(sfr), len(sfr) - 1,
                                                    _lib._ptr(pos), n_parents, _lib._ptr(hint), flags, c_spec(tokenizer), C.byref(out)))
@@ -522,10 +534,18 @@ class Context:
         return int(out.value)
 
     # streaming ingest: open without rows, append batches whose rows belong to arbitrary sets, then finish / build as above
-    def ingest_open(self, n_sets: int, parent_of_set=None, n_parents: int = 0, slots_hint=None, flags: int = 0, tokenizer=None) -> int:
+    def ingest_open(self, n_sets: int, parent_of_set=None, n_parents: int = 0, slots_hint=None, flags: int = 0, tokenizer=None,
+                    minmax_fields=None) -> int:
         pos = None if parent_of_set is None else np.ascontiguousarray(parent_of_set, dtype=np.uint32)
         hint = None if slots_hint is None else np.ascontiguousarray(slots_hint, dtype=np.uint32)
         out = C.c_uint64()
+        if minmax_fields is not None:         # bsg_ingest_open_minmax: every append folds its batch into the sets' MinMax indexes
+            fblob, foff = pack_entries([f.encode() if isinstance(f, str) else bytes(f) for f in minmax_fields])
+            self._check(self.L.bsg_ingest_open_minmax(self.h, n_sets, _lib._ptr(pos), n_parents, _lib._ptr(hint), flags,
+                                                      None if tokenizer is None else c_spec(tokenizer), C.byref(out),
+                                                      fblob.ctypes.data, foff.ctypes.data, len(foff) - 1))
+            self._minmax_fields[int(out.value)] = len(foff) - 1
+            return int(out.value)
         self._check(self.L.bsg_ingest_open(self.h, n_sets, _lib._ptr(pos), n_parents, _lib._ptr(hint), flags,
                                            None if tokenizer is None else c_spec(tokenizer), C.byref(out)))
         return int(out.value)
@@ -558,6 +578,21 @@ class Context:
         self._check(self.L.bsg_ingest_append_rows(self.h, ingest_id, _lib._ptr(blob), _lib._ptr(off), n_rows, _lib._ptr(sor),
                                                   _lib._ptr(fb), n_rows, C.byref(n)))
         return fb[: n.value].copy()
+
+    def ingest_minmax(self, ingest_id: int, n_sets: int):
+        """The MinMax indexes of an ingest made with minmax_fields, as the device folded them (the rows it handed back are NOT in:
+        fold them in with host.minmax_row): (min i64, max i64, present bool), each of shape (n_sets, n_fields); min = max = 0
+        where present is False."""
+        nf = self._minmax_fields.get(int(ingest_id), 1)
+        rec = np.zeros(max(n_sets * nf, 1), dtype=_lib.MINMAX_DTYPE)
+        self._check(self.L.bsg_ingest_minmax(self.h, ingest_id, rec.ctypes.data, len(rec)))
+        rec = rec[: n_sets * nf].reshape(n_sets, nf)
+        return rec["min"].copy(), rec["max"].copy(), rec["present"] != 0
+
+    def last_minmax_ms(self) -> float:
+        v = C.c_float()
+        self._check(self.L.bsg_last_minmax_ms(self.h, C.byref(v)))
+        return float(v.value)
 
     def ingest_fallback_rows(self, ingest_id: int) -> np.ndarray:
         n = C.c_uint32()
@@ -886,4 +921,5 @@ class Context:
         return st
 
     def ingest_free(self, ingest_id: int):
+        self._minmax_fields.pop(int(ingest_id), None)
         self._check(self.L.bsg_ingest_free(self.h, ingest_id))

@@ -19,6 +19,7 @@ HOST_EXPORTS = [
     "bsh_batch_new", "bsh_batch_free", "bsh_batch_add_query", "bsh_batch_sizes", "bsh_batch_export", "bsh_match_row", "bsh_match_row_with", "bsh_prune_query", "bsh_match_row_regex",
     "bsh_substring_terms", "bsh_prune_query_sub", "bsh_match_row_substring",
     "bsh_match_row_range", "bsh_prune_query_range",
+    "bsh_minmax_row", "bsh_minmax_eval", "bsh_prefilter_eval",
     "bsh_regex_match",
     "bsh_section_encode", "bsh_section_parse", "bsh_crc32c",
     "bse_open", "bse_close", "bse_last_error", "bse_stop", "bse_ingest_rows", "bse_flush", "bse_merge", "bse_query", "bse_query_many",
@@ -67,6 +68,9 @@ def lib():
     L.bsh_match_row_substring.argtypes = [C.c_char_p, u64, C.c_char_p, u64, C.POINTER(_lib.Tokenizer)]
     L.bsh_match_row_range.argtypes = [C.c_char_p, u64, C.c_char_p, u64]
     L.bsh_prune_query_range.argtypes = [C.c_char_p, u64, C.c_char_p, u64, C.c_char_p, u64, C.c_char_p, u64, C.POINTER(_lib.Tokenizer), pp, pu64]
+    L.bsh_minmax_row.argtypes = [C.c_char_p, u64, vp, vp, u32, vp]
+    L.bsh_minmax_eval.argtypes = [vp, u32, C.c_int64, vp, u32, C.c_int64, C.c_int64]
+    L.bsh_prefilter_eval.argtypes = [C.c_char_p, u64, C.c_char_p, u64, vp, vp, u32, vp]
     L.bsh_section_encode.argtypes = [C.POINTER(vp), pu64, pu64, pp, pu64]
     L.bsh_section_parse.argtypes = [C.c_char_p, u64, pu64, pu64, C.POINTER(vp)]
     L.bsh_crc32c.argtypes = [C.c_char_p, u64]; L.bsh_crc32c.restype = u32
@@ -296,6 +300,62 @@ def prune_query_range(bloom_expression, regex_expression, substring_expression, 
     return json.loads(_take(L, p, n))
 
 
+MM_EQ, MM_NE, MM_GT, MM_GE, MM_LT, MM_LE, MM_IN, MM_NOT_IN, MM_BETWEEN, MM_NOT_BETWEEN = range(10)       # bloomsearch_host.h BSH_MM_*
+MM_OPS = {"EQ": MM_EQ, "NE": MM_NE, "GT": MM_GT, "GTE": MM_GE, "LT": MM_LT, "LTE": MM_LE, "IN": MM_IN, "NOT_IN": MM_NOT_IN,
+          "BETWEEN": MM_BETWEEN, "NOT_BETWEEN": MM_NOT_BETWEEN}
+
+
+def _pack_names(names):
+    names = [f.encode() if isinstance(f, str) else bytes(f) for f in names]
+    off = np.zeros(len(names) + 1, dtype=np.uint32)
+    if names:
+        off[1:] = np.cumsum([len(f) for f in names])
+    blob = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8).copy()
+    return blob, off
+
+
+def minmax_row(row: bytes, fields, index=None) -> np.ndarray:
+    """bsh_minmax_row: one row's contributions folded into `index` (an array of _lib.MINMAX_DTYPE, one record per field; None =
+    all absent), in place; returns it.  Exact for every number literal.  HostError for a row that is not one valid JSON object."""
+    L = lib()
+    blob, off = _pack_names(fields)
+    if index is None:
+        index = np.zeros(len(off) - 1, dtype=_lib.MINMAX_DTYPE)
+    assert index.dtype == _lib.MINMAX_DTYPE and len(index) == len(off) - 1 and index.flags.c_contiguous
+    rc = L.bsh_minmax_row(row, len(row), blob.ctypes.data, off.ctypes.data, len(off) - 1, index.ctypes.data)
+    if rc:
+        raise HostError(rc)
+    return index
+
+
+def minmax_eval(imin: int, imax: int, op, value: int = 0, values=(), lo: int = 0, hi: int = 0) -> bool:
+    """bsh_minmax_eval: EvaluateMinMaxCondition on the index (imin, imax).  op: MM_* or the reference's operator name."""
+    L = lib()
+    rec = np.zeros(1, dtype=_lib.MINMAX_DTYPE)
+    rec[0] = (imin, imax, 1, 0)
+    vs = np.ascontiguousarray(list(values), dtype=np.int64)
+    rc = L.bsh_minmax_eval(rec.ctypes.data, MM_OPS.get(op, op), value, vs.ctypes.data if len(vs) else None, len(vs), lo, hi)
+    if rc < 0:
+        raise HostError(rc)
+    return bool(rc)
+
+
+def prefilter_eval(expression, partition_id: bytes | str = b"", indexes=None) -> bool:
+    """bsh_prefilter_eval: evaluatePrefilterExpression for one block.  indexes: {field name: (min, max)} the block carries."""
+    L = lib()
+    s = json.dumps(expression).encode()
+    pid = partition_id.encode() if isinstance(partition_id, str) else bytes(partition_id)
+    names = list(indexes or {})
+    blob, off = _pack_names(names)
+    rec = np.zeros(max(len(names), 1), dtype=_lib.MINMAX_DTYPE)
+    for i, f in enumerate(names):
+        rec[i] = (indexes[f][0], indexes[f][1], 1, 0)
+    rc = L.bsh_prefilter_eval(s, len(s), pid, len(pid), blob.ctypes.data, off.ctypes.data, len(names), rec.ctypes.data)
+    if rc < 0:
+        raise HostError(rc)
+    return bool(rc)
+
+
 def crc32c(data: bytes) -> int:
     return int(lib().bsh_crc32c(data, len(data)))
 
@@ -374,9 +434,13 @@ class Engine:
     def stop(self):
         self._check(self.L.bse_stop(self.h))
 
-    def query(self, bloom_expression=None, regex_expression=None, substring_expression=None, range_expression=None):
+    def query(self, bloom_expression=None, regex_expression=None, substring_expression=None, range_expression=None, prefilter=None):
+        """prefilter: a tree of query.Partition / MinMax / PrefilterAnd / PrefilterOr over the blocks' partition ids and MinMax indexes
+        (config MinMaxIndexes=[...]); None takes exactly the path without one."""
         d = {"Bloom": {"Expression": bloom_expression} if bloom_expression is not None else None,
              "Regex": {"Expression": regex_expression} if regex_expression is not None else None}
+        if prefilter is not None:
+            d["Prefilter"] = {"Expression": prefilter}
         if substring_expression is not None:
             d["Substring"] = substring_expression
         if range_expression is not None:
@@ -386,15 +450,17 @@ class Engine:
         self._check(self.L.bse_query(self.h, q, len(q), C.byref(p), C.byref(n)))
         return json.loads(_take(self.L, p, n))
 
-    def query_many(self, bloom_expressions, regex_expressions=None, substring_expressions=None, range_expressions=None):
+    def query_many(self, bloom_expressions, regex_expressions=None, substring_expressions=None, range_expressions=None, prefilters=None):
         """bse_query_many: one pass for a batch of queries -> list of query()'s results, element i for bloom_expressions[i]
         (and regex_expressions[i] / substring_expressions[i] / range_expressions[i], where given)."""
         rx = list(regex_expressions) if regex_expressions is not None else [None] * len(bloom_expressions)
         sx = list(substring_expressions) if substring_expressions is not None else [None] * len(bloom_expressions)
         gx = list(range_expressions) if range_expressions is not None else [None] * len(bloom_expressions)
+        px = list(prefilters) if prefilters is not None else [None] * len(bloom_expressions)
         q = json.dumps([dict({"Bloom": {"Expression": b} if b is not None else None, "Regex": {"Expression": r} if r is not None else None},
-                             **({"Substring": s} if s is not None else {}), **({"Range": g} if g is not None else {}))
-                        for b, r, s, g in zip(bloom_expressions, rx, sx, gx)]).encode()
+                             **({"Substring": s} if s is not None else {}), **({"Range": g} if g is not None else {}),
+                             **({"Prefilter": {"Expression": p}} if p is not None else {}))
+                        for b, r, s, g, p in zip(bloom_expressions, rx, sx, gx, px)]).encode()
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self.L.bse_query_many(self.h, q, len(q), C.byref(p), C.byref(n)))
         return json.loads(_take(self.L, p, n))

@@ -10,13 +10,21 @@ from __future__ import annotations
 import numpy as np
 
 from . import host
-from ._lib import DESC_DTYPE
+from ._lib import DESC_DTYPE, MINMAX_DTYPE
 from .gpu import Context, estimate_parameters
 
 
 class IngestResult:
-    def __init__(self, counts, status, desc, words, stats, fallback_rows):
+    def __init__(self, counts, status, desc, words, stats, fallback_rows, minmax=None):
         self.counts, self.status, self.desc, self.words, self.stats, self.fallback_rows = counts, status, desc, words, stats, fallback_rows
+        self._minmax = minmax
+
+    def minmax(self):
+        """(min, max, present), each (n_sets, n_fields): the sets' MinMax indexes (device_ingest(..., minmax_fields=...)), the rows
+        the device handed back folded in through host.minmax_row."""
+        if self._minmax is None:
+            raise ValueError("the ingest was made without minmax_fields")
+        return self._minmax
 
     def filter_words(self, set_index: int, kind: int) -> np.ndarray:
         d = self.desc[set_index * 3 + kind]
@@ -64,18 +72,37 @@ def host_walk_entries(rows, row_ids, set_of_row, tokenizer=None):
     return entries, sets, kinds
 
 
+def fold_minmax(index, rows, row_ids, set_of_row, fields):
+    """The rows the device handed back, folded into (min, max, present) of ctx.ingest_minmax on the host (bsh_minmax_row).  A row
+    the device had decided changes nothing: the values are exact and the fold is idempotent."""
+    mn, mx, present = index
+    for r in row_ids:
+        s = int(set_of_row[int(r)])
+        rec = np.zeros(len(fields), dtype=MINMAX_DTYPE)
+        rec["min"], rec["max"], rec["present"] = mn[s], mx[s], present[s]
+        try:
+            host.minmax_row(rows[int(r)], fields, rec)
+        except host.HostError:
+            continue                          # not a JSON object: it contributes nothing
+        mn[s], mx[s], present[s] = rec["min"], rec["max"], rec["present"] != 0
+    return mn, mx, present
+
+
 def device_ingest(ctx: Context, row_sets, fpr: float, parent_of_set=None, n_parents: int = 0, slots_hint=None,
-                  keep: bool = False, flags: int = 0, tokenizer=None) -> IngestResult:
+                  keep: bool = False, flags: int = 0, tokenizer=None, minmax_fields=None) -> IngestResult:
     """row_sets: list (one per set) of lists of row bytes.  tokenizer: None = the default tokenizer (bsg_ingest_rows); a
     tokenizer.Tokenizer of the separator family = bsg_ingest_rows_tok, its fallback rows walked by the host with the same spec."""
     rows = [r for rs in row_sets for r in rs]
     first = np.zeros(len(row_sets) + 1, dtype=np.uint32)
     first[1:] = np.cumsum([len(rs) for rs in row_sets])
-    ing = ctx.ingest_rows(rows, first, parent_of_set, n_parents, slots_hint, flags, tokenizer=tokenizer)
+    ing = ctx.ingest_rows(rows, first, parent_of_set, n_parents, slots_hint, flags, tokenizer=tokenizer, minmax_fields=minmax_fields)
     try:
         fb = ctx.ingest_fallback_rows(ing)
+        set_of_row = np.repeat(np.arange(len(row_sets)), np.diff(first.astype(np.int64)))
+        minmax = None
+        if minmax_fields is not None:
+            minmax = fold_minmax(ctx.ingest_minmax(ing, len(row_sets)), rows, fb, set_of_row, list(minmax_fields))
         if len(fb):
-            set_of_row = np.repeat(np.arange(len(row_sets)), np.diff(first.astype(np.int64)))
             entries, sets, kinds = host_walk_entries(rows, fb, set_of_row, tokenizer)
             if entries:
                 ctx.ingest_add_entries(ing, entries, sets, kinds)
@@ -84,7 +111,7 @@ def device_ingest(ctx: Context, row_sets, fpr: float, parent_of_set=None, n_pare
         desc, n_words = plan_desc(counts, fpr)
         words = ctx.ingest_build(ing, desc, n_words)
         stats = ctx.ingest_stats(ing)
-        return IngestResult(counts, status, desc, words, stats, fb)
+        return IngestResult(counts, status, desc, words, stats, fb, minmax)
     finally:
         if not keep:
             ctx.ingest_free(ing)
@@ -95,13 +122,16 @@ class IngestStream:
     to arbitrary sets are handed to the device as they arrive; finish / build see what bsg_ingest_rows would have left.  Lives
     on one device of the context.  Use as a context manager or call close()."""
 
-    def __init__(self, ctx: Context, ingest_id: int, n_sets: int, n_parents: int, tokenizer=None):
+    def __init__(self, ctx: Context, ingest_id: int, n_sets: int, n_parents: int, tokenizer=None, minmax_fields=None):
         self.ctx, self.id, self.n_sets, self.n_parents, self.tokenizer = ctx, ingest_id, n_sets, n_parents, tokenizer
+        self.minmax_fields = None if minmax_fields is None else list(minmax_fields)
+        self._handed_back = []                # (row, set) of the rows finish_fallback folded: their MinMax contributions, kept for minmax()
 
     @classmethod
     def open(cls, ctx: Context, n_sets: int = 0, parent_of_set=None, n_parents: int = 0, slots_hint=None, flags: int = 0,
-             tokenizer=None) -> "IngestStream":
-        return cls(ctx, ctx.ingest_open(n_sets, parent_of_set, n_parents, slots_hint, flags, tokenizer), n_sets, n_parents, tokenizer)
+             tokenizer=None, minmax_fields=None) -> "IngestStream":
+        return cls(ctx, ctx.ingest_open(n_sets, parent_of_set, n_parents, slots_hint, flags, tokenizer, minmax_fields=minmax_fields), n_sets, n_parents,
+                   tokenizer, minmax_fields)
 
     def add_sets(self, parent_of_new_set, slots_hint=None) -> int:
         first = self.ctx.ingest_add_sets(self.id, parent_of_new_set, slots_hint)
@@ -119,7 +149,18 @@ class IngestStream:
             entries, sets, kinds = host_walk_entries(rows, fb, set_of_row, self.tokenizer)
             if entries:
                 self.ctx.ingest_add_entries(self.id, entries, sets, kinds)
+            if self.minmax_fields is not None:
+                self._handed_back += [(rows[int(r)], int(set_of_row[int(r)])) for r in fb]
         return fb
+
+    def minmax(self):
+        """(min, max, present), each (n_sets, n_fields), over every append so far; the rows append(finish_fallback=True) got back
+        are folded in through host.minmax_row (those of finish_fallback=False appends are the caller's to fold: fold_minmax)."""
+        if self.minmax_fields is None:
+            raise ValueError("the stream was opened without minmax_fields")
+        index = self.ctx.ingest_minmax(self.id, self.n_sets)
+        rows = [r for r, _ in self._handed_back]
+        return fold_minmax(index, rows, range(len(rows)), [s for _, s in self._handed_back], self.minmax_fields)
 
     def finish(self):
         """-> (counts u64 [n_sets + n_parents, 3], status u32 [n_sets + n_parents]): sets, then parents"""

@@ -222,6 +222,56 @@ def numeric_condition_range(field: str, condition: dict) -> dict:
     raise ValueError(f"numeric operator {o!r}")
 
 
+# ---- prefilter tree over block metadata (query.go PrefilterExpression): partition ids and MinMax indexes ----
+PREFILTER_OPS = ("EQ", "NE", "GT", "GTE", "LT", "LTE", "IN", "NOT_IN", "BETWEEN", "NOT_BETWEEN")
+
+
+def _prefilter_condition(op: str, operands, check) -> dict:
+    """{"Operator", "Value" | "Values" | "Min", "Max"} as the reference's StringCondition / NumericCondition"""
+    if op not in PREFILTER_OPS:
+        raise ValueError(f"prefilter operator {op!r}")
+    for v in operands:
+        check(v)
+    if op in ("IN", "NOT_IN"):
+        return {"Operator": op, "Values": list(operands)}
+    if op in ("BETWEEN", "NOT_BETWEEN"):
+        lo, hi = operands
+        return {"Operator": op, "Min": lo, "Max": hi}
+    (v,) = operands
+    return {"Operator": op, "Value": v}
+
+
+def _check_int64(v):
+    if not (isinstance(v, int) and not isinstance(v, bool) and INT64_MIN <= v <= INT64_MAX):
+        raise ValueError(f"MinMax operand {v!r}: an int64")
+
+
+def _check_str(v):
+    if not isinstance(v, str):
+        raise ValueError(f"partition operand {v!r}: a string")
+
+
+def Partition(op: str, *operands) -> dict:
+    """The block's partition id satisfies the operator: Partition("EQ", "p1"), Partition("IN", "a", "b"), Partition("BETWEEN", lo, hi).
+    A block without a partition id fails every partition condition."""
+    return {"ExpressionType": "CONDITION", "Condition": {"ConditionType": "PARTITION", "PartitionCondition": _prefilter_condition(op, operands, _check_str)}}
+
+
+def MinMax(field: str, op: str, *operands) -> dict:
+    """The block's MinMax index of `field` (engine config "MinMaxIndexes") may hold a value that satisfies the operator:
+    MinMax("ts", "GTE", 100), MinMax("ts", "BETWEEN", 0, 99), MinMax("ts", "IN", 1, 2, 3).  A block without the index fails."""
+    return {"ExpressionType": "CONDITION", "Condition": {"ConditionType": "MINMAX", "MinMaxFieldName": field,
+                                                           "MinMaxCondition": _prefilter_condition(op, operands, _check_int64)}}
+
+
+def PrefilterAnd(*expressions) -> dict:
+    return {"ExpressionType": "AND", "Children": _flatten_regex(expressions, "AND")}
+
+
+def PrefilterOr(*expressions) -> dict:
+    return {"ExpressionType": "OR", "Children": _flatten_regex(expressions, "OR")}
+
+
 def range_entry(condition: dict) -> bytes:
     """Entry 2i + 1 of a KIND_FIELD_RANGE condition: lo, hi (int64, little-endian) and the flag byte."""
     lo, hi = condition.get("Lo"), condition.get("Hi")

@@ -554,7 +554,8 @@ typedef struct bsg_ingest_stats {
 /* flags for bsg_ingest_rows.  BSG_INGEST_TRUSTED_JSON: every row is known to be valid JSON (it came out of
  * json.Marshal, or the caller validated it): the device skips its validation pass.  Without the flag a row the
  * device walker hands back has inserted nothing; with it, such a row may already have inserted some of its
- * entries — all of which the host walker inserts again for a valid row, so the result is the same. */
+ * entries — all of which the host walker inserts again for a valid row, so the result is the same.  (An ingest opened with
+ * MinMax fields also hands back rows that HAVE inserted their entries, with or without the flag: "per-set MinMax indexes" below.) */
 #define BSG_INGEST_TRUSTED_JSON 1u
 
 /* rows: marshaled JSON, row r = rows[row_off[r] .. row_off[r+1]) without a trailing newline.
@@ -647,6 +648,52 @@ BSG_API int32_t bsg_ingest_build_sections(bsg_ctx *ctx, uint64_t ingest_id, cons
                                           uint64_t *out_parents_arena_id);
 BSG_API int32_t bsg_ingest_stats_read(bsg_ctx *ctx, uint64_t ingest_id, bsg_ingest_stats *out);
 BSG_API int32_t bsg_ingest_free(bsg_ctx *ctx, uint64_t ingest_id);
+
+/* ---- per-set MinMax indexes computed by the device ingest (partitionBuffer.minMaxIndexes, ingest.go:444-471) ----
+ * Fields: 1 to BSG_MINMAX_MAX_FIELDS distinct names of 1 to BSG_MINMAX_MAX_NAME bytes, packed like bsg_hash_entries' input
+ * (field_off[n_fields + 1]).  A name is a TOP-LEVEL key of the row object compared byte for byte with the decoded key — not a
+ * dotted path: {"a":{"b":1}} does not feed field "a.b", {"a.b":1} does (the reference's row[index], ingest.go:455-456).
+ * One row's contribution to one field: the member's value must itself be a JSON number (a string, "5" too, true, false, null,
+ * an object or an array contributes nothing); of several top-level members with the key only the LAST counts (what a Go map holds
+ * after decoding); the value v is the exact decimal value of the literal (no float64 round trip) and contributes
+ * min = clamp(floor(v)), max = clamp(ceil(v)), clamped to [INT64_MIN, INT64_MAX] — ConvertToMinMaxInt64 (min_max.go) for every
+ * literal json.Marshal writes.  A set's index for a field is the fold of its rows' contributions (UpdateMinMaxIndex) and is
+ * present only if at least one row contributed; parents get none.
+ * Rows the device does not decide: the device commits a row's contributions only after it has scanned the whole row, and hands
+ * the row back — contributing NOTHING — when a top-level member named by a field holds a literal with an exponent, or when any
+ * top-level key contains a backslash (it could decode to a field name).  Such rows are reported through the ingest's existing
+ * fallback list (bsg_ingest_fallback_rows; out_fallback_rows of bsg_ingest_append_rows), merged with the walker's own hand-backs:
+ * ascending, each row once, n_fallback_rows counts the union.  The caller folds every handed-back row in on the host
+ * (bsh_minmax_row, bloomsearch_host.h); folding a row the device had decided again changes nothing.
+ * Amendment to BSG_INGEST_TRUSTED_JSON's note, for ingests opened with fields only: a row handed back for a MinMax reason HAS
+ * inserted its bloom entries, even without the flag; it passed validation, so the host walker inserts the same entries again.
+ * Rows that are not valid JSON objects: the result of their set is unspecified; no other set's result is touched.
+ * With fields, the filters, counts and statuses of an ingest are bit-identical to the same call without them. */
+#define BSG_MINMAX_MAX_FIELDS 8u
+#define BSG_MINMAX_MAX_NAME 64u
+typedef struct bsg_minmax {
+    int64_t min, max;          /* 0, 0 when absent */
+    uint32_t present;          /* 1: at least one row contributed */
+    uint32_t reserved;
+} bsg_minmax;
+/* bsg_ingest_rows_tok plus the fields, which are recorded on the ingest.  Before anything is launched, BSG_E_INVALID with the
+ * field named in bsg_last_error: n_fields 0 or above 8, an empty name, a name over 64 bytes, two equal names, null arrays. */
+BSG_API int32_t bsg_ingest_rows_minmax(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                       const uint32_t *set_first_row, uint32_t n_sets, const uint32_t *parent_of_set,
+                                       uint32_t n_parents, const uint32_t *slots_hint, uint32_t flags, const bsg_tokenizer *tok,
+                                       uint64_t *out_ingest_id, const uint8_t *field_bytes, const uint32_t *field_off,
+                                       uint32_t n_fields);
+/* bsg_ingest_open plus the fields: every bsg_ingest_append_rows folds its batch in; bsg_ingest_add_sets grows the result. */
+BSG_API int32_t bsg_ingest_open_minmax(bsg_ctx *ctx, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents,
+                                       const uint32_t *slots_hint, uint32_t flags, const bsg_tokenizer *tok, uint64_t *out_ingest_id,
+                                       const uint8_t *field_bytes, const uint32_t *field_off, uint32_t n_fields);
+/* out[n_sets * n_fields], record (set, field) at set * n_fields + field; cap: the records out has room for.  Valid any time after
+ * the creating call or an append, and after bsg_ingest_finish.  The parts of a call cut over several devices own disjoint sets:
+ * their results are placed side by side.  BSG_E_INVALID on an ingest made without fields. */
+BSG_API int32_t bsg_ingest_minmax(bsg_ctx *ctx, uint64_t ingest_id, bsg_minmax *out, uint64_t cap);
+/* k_minmax_rows' dispatch time in the last bsg_ingest_rows_minmax / bsg_ingest_append_rows of an ingest with fields (summed over
+ * the upload chunks; the slowest device of a call cut over several).  bsg_ingest_stats keeps its layout. */
+BSG_API int32_t bsg_last_minmax_ms(bsg_ctx *ctx, float *minmax_ms);
 
 /* ---- final row test on the device (compileRowMatcher / matchRowBytes, row_matcher.go:257-626) ----
  * One expression over Field / Token / FieldToken conditions, evaluated for every row of the surviving blocks.

@@ -110,6 +110,38 @@ BSG_API int32_t bsh_prune_query_range(const char *bloom_json, uint64_t bloom_len
                                       const char *substring_json, uint64_t substring_len, const char *range_json, uint64_t range_len,
                                       const bsg_tokenizer *tok, char **out, uint64_t *out_len);
 
+/* ---- MinMax indexes (bloomgpu.h "per-set MinMax indexes"; bloomsearch_amd/csrc/host/minmax.hpp) ----
+ * One row's contributions folded into inout[n_fields] (fields packed as for bsg_ingest_rows_minmax; an index with present == 0 is
+ * absent and takes the first contribution as it is).  Exact for EVERY number literal, exponents of any size included
+ * (1e99999999999999999999 gives (INT64_MAX, INT64_MAX)); escaped keys are decoded; the last duplicate wins; no floating point.
+ * The function the rows a device ingest hands back are folded in with.  BSH_E_INVALID: invalid fields, or a row that is not one
+ * valid JSON object (nothing is folded). */
+BSG_API int32_t bsh_minmax_row(const uint8_t *row, uint64_t len, const uint8_t *field_bytes, const uint32_t *field_off, uint32_t n_fields,
+                               bsg_minmax *inout);
+/* EvaluateMinMaxCondition (query.go) on a present index: 1 the block may hold a matching value, 0 it cannot.  A bound at an int64
+ * extreme is saturated (the true value may lie beyond it): NE, GT, LT and NOT_BETWEEN keep such a block.  NOT_IN is always 1.
+ * value: EQ NE GT GE LT LE; values[n_values]: IN; min, max: BETWEEN, NOT_BETWEEN.  BSH_E_INVALID: an absent index, an unknown op. */
+#define BSH_MM_EQ 0u
+#define BSH_MM_NE 1u
+#define BSH_MM_GT 2u
+#define BSH_MM_GE 3u
+#define BSH_MM_LT 4u
+#define BSH_MM_LE 5u
+#define BSH_MM_IN 6u
+#define BSH_MM_NOT_IN 7u
+#define BSH_MM_BETWEEN 8u
+#define BSH_MM_NOT_BETWEEN 9u
+BSG_API int32_t bsh_minmax_eval(const bsg_minmax *index, uint32_t op, int64_t value, const int64_t *values, uint32_t n_values, int64_t min,
+                                int64_t max);
+/* evaluatePrefilterExpression (query.go) for one block.  prefilter_json: {"ExpressionType":"CONDITION"|"AND"|"OR","Condition":
+ * {"ConditionType":"PARTITION"|"MINMAX","PartitionCondition":{"Operator":"EQ"|"NE"|"GT"|"GTE"|"LT"|"LTE"|"IN"|"NOT_IN"|"BETWEEN"|
+ * "NOT_BETWEEN","Value","Values","Min","Max"},"MinMaxFieldName","MinMaxCondition":{the same with int64 operands}},"Children":[..]};
+ * NULL / empty / "null": 1.  The block: its partition id and indexes[n_fields] named by the packed fields (present == 0: the block
+ * does not carry that index).  An empty Or is 0, an empty And 1, a nil condition 1, a block without the named index 0, an empty
+ * partition id fails every partition condition.  1 the block passes, 0 it does not, BSH_E_INVALID for invalid arguments. */
+BSG_API int32_t bsh_prefilter_eval(const char *prefilter_json, uint64_t len, const uint8_t *partition_id, uint64_t partition_len,
+                                   const uint8_t *field_bytes, const uint32_t *field_off, uint32_t n_fields, const bsg_minmax *indexes);
+
 /* Go regexp MatchString of `pattern` on `text` for the subset the device row matcher compiles (bsg_match_rows_regex; the
  * subset is listed in bloomsearch_amd/csrc/host/regex_dfa.hpp), run on the same DFA tables.  The text is read as Go reads a
  * string: an invalid byte is U+FFFD.  1 match, 0 no match, BSG_E_UNSUPPORTED for a pattern outside the subset (syntax
@@ -130,7 +162,8 @@ typedef struct bse_engine bse_engine;
  *               "DeviceMatch":true|false,
  *               "DeviceRegex":true|false,"DeviceMatchWide":true|false,"DeviceMatchWideRows":true|false,
  *               "DeviceMatchLookup":true|false,"DeviceMatchLookupRows":true|false,"DeviceMatchLookupRegex":true|false,
- *               "Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false,"Ngram":0|2|3|4}};
+ *               "Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false,"Ngram":0|2|3|4},
+ *               "MinMaxIndexes":["timestamp",..]};
  *               missing keys take the
  *               reference defaults.  DeviceIngest (default false): rows are walked / tokenized / deduplicated /
  *               counted on the GPU at flush and merge time (bloomgpu.h bsg_ingest_*) instead of by indexRow on the
@@ -159,6 +192,12 @@ typedef struct bse_engine bse_engine;
  *               keep the std::regex path.  Tokenizer (default: BasicWhitespaceLowerTokenizer): the engine's tokenizer
  *               of the separator family (bloomgpu.h bsg_tokenizer), used by indexing, the host matcher and the device calls;
  *               a missing member is Go's zero value ("" / false); BSE_E_INVALID_CONFIG for a NUL or non-ASCII separator.
+ *               MinMaxIndexes (default none): top-level keys whose per-block [min, max] every flush records (bloomgpu.h "per-set
+ *               MinMax indexes": 1 to 8 distinct names of 1 to 64 bytes, BSE_E_INVALID_CONFIG otherwise).  Without DeviceIngest
+ *               every row is folded by bsh_minmax_row at ingest time; with DeviceIngest / DeviceIngestStream the flush's device
+ *               call computes the indexes (bsg_ingest_rows_minmax / bsg_ingest_open_minmax) and only the rows it hands back are
+ *               folded on the host; the indexes are the same on every route.  Merge joins two blocks of a partition only when
+ *               their index KEY SETS are equal (merge.go:208-260) and unions the sources' indexes.
  *               The config is checked before ctx: an invalid one gives BSE_E_INVALID_CONFIG even with a NULL ctx, a valid one
  *               with a NULL ctx BSH_E_INVALID. */
 BSG_API int32_t bse_open(const char *config_json, uint64_t len, bsg_ctx *ctx, bse_engine **out);
@@ -172,6 +211,10 @@ BSG_API int32_t bse_merge(bse_engine *e);
 /* query_json: {"Bloom":{"Expression":{...}}} (or {"Bloom":null}), with optional "Regex", "Substring" and "Range" trees (the last:
  * bsh_match_row_range's tree, or {"Expression": tree}; under DeviceMatch a query with a Range tree and neither of the other two is
  * decided by ONE bsg_match_rows_range call over And(bloom, range)); result JSON:
+ * An optional "Prefilter": {"Expression": tree} (bsh_prefilter_eval's tree) is applied to every block's partition id and MinMax
+ * indexes: a block failing it is neither scanned nor given a BlockStats entry, and a file left without blocks counts in neither
+ * FilesConsidered nor FilesBloomSkipped; in bse_query_many every query has its own prefilter, and a block no query keeps is not
+ * walked.  A query without a Prefilter takes exactly the path it took before.  Result JSON:
  * {"rows":[...],"stats":{"BlockStats":[{"FileID","BlockOffset","RowsProcessed","BytesProcessed","TotalRows",
  *  "TotalBytes","BloomFilterSkipped"}],"Errors":[..],"FilesConsidered","FilesBloomSkipped"}} */
 BSG_API int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, char **out_json, uint64_t *out_len);
@@ -200,7 +243,8 @@ BSG_API int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, c
  * "[]" gives "[]". */
 BSG_API int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, char **out_json, uint64_t *out_len);
 /* {"files":[{"FileID","BloomEntryCounts":{..},"section_bytes","blocks":[{"PartitionID","Rows","BloomEntryCounts":{..},
- *  "BloomFalsePositiveRate","BloomFilterSize","filters":[{"m","k"}|null x3]}]}],
+ *  "BloomFalsePositiveRate","BloomFilterSize","filters":[{"m","k"}|null x3],"MinMaxIndexes":{"f":{"Min":..,"Max":..}}}]}],
+ *  ("MinMaxIndexes" is omitted when the block has none)
  *  "IngestStream":{"Batches","Rows","HostRows","Flushes"}} — the last: DeviceIngestStream at work since bse_open: bse_ingest_rows
  *  batches and rows handed to a streaming ingest when they arrived, the rows among them the host walker finished at once, and the
  *  flushes built from a stream.  A batch whose append fails is answered with the error and is not buffered; the rows buffered

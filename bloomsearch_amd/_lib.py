@@ -25,6 +25,9 @@ OP_TERM, OP_AND, OP_OR, OP_TRUE, OP_FALSE = 0, 1, 2, 3, 4
 PROBE_ASYNC, PROBE_TIMED, PROBE_NOFUSE, PROBE_ROWS_PACKED = 1, 2, 4, 8
 INGEST_TRUSTED_JSON = 1
 MINMAX_MAX_FIELDS, MINMAX_MAX_NAME = 8, 64      # bsg_ingest_rows_minmax / bsg_ingest_open_minmax
+PARTITION_MAX_NAME, PARTITION_MAX_KEY, PARTITION_PENDING_SLOTS, PARTITION_MAX_SETS = 64, 128, 256, 1 << 20      # bsg_ingest_open_keyed
+SET_UNDECIDED = 0xFFFFFFFF                      # out_set_of_row of bsg_ingest_append_rows_keyed: the partitioner handed the row back
+LAB_PARTITION_HASH_MASK = 29                    # bsg_set_lab key: 1 = the partition dictionary's hash keeps its low 2 bits
 MINMAX_DTYPE = np.dtype([("min", "<i8"), ("max", "<i8"), ("present", "<u4"), ("reserved", "<u4")])      # bsg_minmax
 ROUTE_NONE, ROUTE_STREAM, ROUTE_GATHER, ROUTE_GATHER_CHUNKED = 0, 1, 2, 3      # bsg_lab_last_probe_route (bloomgpu_lab.h)
 GATHER_COST_DEFAULT = 108                             # bsg_set_gather_cost's default (bloomgpu_lab.h)
@@ -100,6 +103,7 @@ EXPORTS = [
     "bsg_tokenizer_default", "bsg_ingest_rows", "bsg_ingest_rows_tok", "bsg_ingest_open", "bsg_ingest_add_sets", "bsg_ingest_append_rows", "bsg_ingest_fallback_rows", "bsg_ingest_add_entries", "bsg_ingest_finish", "bsg_ingest_build",
     "bsg_ingest_stats_read", "bsg_ingest_free", "bsg_ingest_build_sections",
     "bsg_ingest_rows_minmax", "bsg_ingest_open_minmax", "bsg_ingest_minmax", "bsg_last_minmax_ms",
+    "bsg_ingest_open_keyed", "bsg_ingest_append_rows_keyed", "bsg_ingest_add_sets_keyed", "bsg_ingest_keys", "bsg_last_partition_ms",
     "bsg_sections_size", "bsg_build_sections", "bsg_last_encode_ms",
     "bsg_match_rows", "bsg_match_rows_regex", "bsg_match_rows_tok", "bsg_match_rows_substr", "bsg_match_rows_range", "bsg_match_rows_many_range", "bsg_match_rows_regex_substr", "bsg_match_rows_many", "bsg_match_rows_many_substr", "bsg_match_rows_many_regex_substr", "bsg_match_rows_many_regex", "bsg_match_rows_wide", "bsg_match_wide_size", "bsg_match_rows_wide_rows", "bsg_match_rows_wide_substr", "bsg_match_rows_wide_substr_rows", "bsg_match_rows_wide_range", "bsg_match_rows_wide_range_rows", "bsg_match_pair_rows_list", "bsg_match_rows_lookup", "bsg_match_rows_lookup_rows", "bsg_match_rows_lookup_regex", "bsg_match_rows_lookup_regex_rows", "bsg_last_match_ms", "bsg_pinned_alloc", "bsg_pinned_free", "bsg_host_register", "bsg_host_unregister",
 ]
@@ -189,6 +193,11 @@ def load():
     L.bsg_ingest_minmax.argtypes = [vp, u64, vp, u64]
     L.bsg_last_minmax_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.bsg_ingest_add_sets.argtypes = [vp, u64, u32, vp, vp, C.POINTER(u32)]
+    L.bsg_ingest_open_keyed.argtypes = [vp, u32, u32, u32, C.POINTER(Tokenizer), C.POINTER(u64), vp, u32, vp, vp, u32]
+    L.bsg_ingest_append_rows_keyed.argtypes = [vp, u64, vp, vp, u32, vp, C.POINTER(u32), vp, u32, C.POINTER(u32)]
+    L.bsg_ingest_add_sets_keyed.argtypes = [vp, u64, vp, vp, u32, vp]
+    L.bsg_ingest_keys.argtypes = [vp, u64, u32, vp, u64, vp, C.POINTER(u32), C.POINTER(u64)]
+    L.bsg_last_partition_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.bsg_ingest_append_rows.argtypes = [vp, u64, vp, vp, u32, vp, vp, u32, C.POINTER(u32)]
     L.bsg_tokenizer_default.argtypes = [C.POINTER(Tokenizer)]
     L.bsg_ingest_fallback_rows.argtypes = [vp, u64, vp, u32, C.POINTER(u32)]

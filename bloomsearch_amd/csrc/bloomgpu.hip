@@ -14,6 +14,9 @@
 #include "match.hip.h"
 #include "match_lookup.hip.h"
 #include "minmax.hip.h"
+#include "partition.hip.h"
+#include <optional>
+#include <tuple>
 #include "host/arena_cache.hpp" // the policy of the resident file-arena cache (cache_api.inc adapts it to the C ABI)
 #include "host/build_plan.hpp"  // shard layout and stats, the parts of a build call, the route a filter is built by
 #include "host/combiner_sync.hpp"
@@ -329,8 +332,12 @@ struct RowUpload {
     EventList landed;                      // per chunk: its bytes are on the device
     hipStream_t cs = nullptr;              // where the bytes travel
     uint64_t copied_to = 0;                // chunks are copied in order: chunk c starts where chunk c - 1 ended
+    const bool resident = false;           // the bytes are on the device already: copy() only records the chunk's event
     RowUpload(Device &dev, const uint8_t *rows, uint8_t *d_rows, const uint64_t *row_off, uint32_t n_rows, uint64_t first_chunk_bytes)
         : d(dev), src(rows), dst(d_rows), off(row_off), n_bytes(row_off[n_rows]), cuts(bsh::plan_row_chunks(row_off, n_rows, first_chunk_bytes)) {}
+    // what an earlier pass of the same call uploaded (bsg_ingest_append_rows_keyed walks after it has partitioned): one chunk of
+    // n_positions walking positions, nothing travels
+    RowUpload(Device &dev, uint32_t n_positions) : d(dev), src(nullptr), dst(nullptr), off(nullptr), n_bytes(0), cuts{0u, n_positions}, resident(true) {}
     uint32_t n_chunks() const { return (uint32_t)cuts.size() - 1; }
     // on the copy stream (made here if need be), behind everything enqueued on d.stream so far — the zeroed tail and the small
     // uploads precede the first row bytes; or in order on d.stream itself
@@ -346,8 +353,8 @@ struct RowUpload {
     }
     hipError_t copy(uint32_t c)            // once per chunk, in order
     {
-        const auto [b0, b1] = bsh::chunk_copy_range(off, cuts, c, n_bytes, copied_to);
-        copied_to = b1;
+        uint64_t b0 = 0, b1 = 0;
+        if (!resident) { std::tie(b0, b1) = bsh::chunk_copy_range(off, cuts, c, n_bytes, copied_to); copied_to = b1; }
         hipError_t e = landed.add(1, hipEventDisableTiming);
         if (e == hipSuccess && b1 > b0) e = hipMemcpyAsync(dst + b0, src + b0, b1 - b0, hipMemcpyHostToDevice, cs);
         if (e == hipSuccess) e = hipEventRecord(landed.v[c], cs);
@@ -486,10 +493,11 @@ struct bsg_ctx {
     std::atomic<uint32_t> next_dev{0};
     uint64_t shard_min_entries = 1ull << 18;   // bsg_hash_entries / bsg_build*: fewer entries stay on one device (bsg_set_lab key 7)
     uint64_t shard_min_row_bytes = 8ull << 20; // bsg_ingest_rows / bsg_match_rows: fewer row bytes stay on one device (bsg_set_lab key 8)
+    uint32_t partition_hash_mask = 0xFFFFFFFFu;   // lab (bsg_set_lab key 29): bits of the hash the partition dictionary's tags keep (3: every lookup is decided by the byte compare)
     uint32_t union_coarsen = 0;                // lab: the partitioned union starts with 2^this x too few partitions (bsg_set_lab key 10)
     uint32_t union_mode = 0;                   // file-level union: 0 = partitions in LDS (k_union_partitions), 1 = global hash tables (bsg_set_lab key 9)
     // device time of the most recent call of each family: the slowest device that took part (bsg_last_*_ms)
-    float last_build_ms = 0.f, last_hash_ms = 0.f, last_decode_ms = 0.f, last_or_ms = 0.f, last_encode_ms = 0.f, last_match_ms = 0.f, last_minmax_ms = 0.f;
+    float last_build_ms = 0.f, last_hash_ms = 0.f, last_decode_ms = 0.f, last_or_ms = 0.f, last_encode_ms = 0.f, last_match_ms = 0.f, last_minmax_ms = 0.f, last_partition_ms = 0.f;
 };
 
 namespace {

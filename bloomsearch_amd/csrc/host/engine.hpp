@@ -65,6 +65,13 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // file as their only parent) and the rows it hands back are finished by the host walker at once; flush only finishes, sizes
     // and builds.  Merge keeps the one-shot path.  Off by default.
     bool device_ingest_stream = false;
+    // true: the caller promises that every row is one valid JSON object (the reference marshals its own rows, ingest.go:379-396):
+    // ingest_rows validates no row for its own sake (a partition id is still found where a PartitionField asks for one).
+    bool trusted_rows = false;
+    // true (needs device_ingest_stream, trusted_rows and a partition_field of 1 to 64 bytes; anything else is an invalid config): the
+    // batches go to a KEYED streaming ingest (bsg_ingest_open_keyed / bsg_ingest_append_rows_keyed): the device finds every row's
+    // partition text, and validate_object_row runs only over the rows it hands back.  Off by default.
+    bool device_partition = false;
     // true: the final row test of the surviving blocks (matchRowBytes, query_exec.go:751) runs on the device too
     // (bsg_match_rows); rows it hands back, and expressions beyond its limits, go through the host matcher.
     bool device_match = false;
@@ -151,6 +158,12 @@ public:
         if (c.max_row_group_rows == 0 || c.max_row_group_bytes == 0) { err = "MaxRowGroupRows / MaxRowGroupBytes must be positive"; return kErrInvalidConfig; }
         if (!(c.bloom_false_positive_rate > 0.0 && c.bloom_false_positive_rate < 1.0)) { err = "BloomFalsePositiveRate must be in (0, 1)"; return kErrInvalidConfig; }
         if (c.device_ingest_stream && !c.device_ingest) { err = "DeviceIngestStream needs DeviceIngest"; return kErrInvalidConfig; }
+        if (c.device_partition && !c.device_ingest_stream) { err = "DevicePartition needs DeviceIngestStream"; return kErrInvalidConfig; }
+        if (c.device_partition && !c.trusted_rows) { err = "DevicePartition needs TrustedRows"; return kErrInvalidConfig; }
+        if (c.device_partition && (c.partition_field.empty() || c.partition_field.size() > BSG_PARTITION_MAX_NAME)) {
+            err = "DevicePartition needs a PartitionField of 1 to 64 bytes";
+            return kErrInvalidConfig;
+        }
         if (!c.minmax_indexes.empty() && !MinMaxFieldNames::check(c.minmax_indexes, err)) { err = "MinMaxIndexes: " + err; return kErrInvalidConfig; }
         return kEngineOk;
     }
@@ -194,7 +207,11 @@ public:
         if (rows.empty()) return kEngineOk;  // ingest.go:356-359
         std::vector<std::string> pids(rows.size());
         std::string scratch;
-        for (size_t i = 0; i < rows.size(); ++i) {
+        // DevicePartition: the device finds the partition ids (stream_append_keyed fills pids); TrustedRows without a PartitionField:
+        // nothing is asked of a row here
+        const bool keyed = cfg_.device_partition && !stream_broken_;
+        const bool skip = keyed || (cfg_.trusted_rows && cfg_.partition_field.empty());
+        for (size_t i = 0; i < rows.size() && !skip; ++i) {
             bool has_pid = false;
             if (!validate_object_row(rows[i], cfg_.partition_field, pids[i], has_pid, scratch))
                 return fail(kErrInvalidRow, "row " + std::to_string(i) + " is not a JSON object");
@@ -203,7 +220,7 @@ public:
         // the batch goes to the device now.  A failure is the caller's to see, like the one-shot path's at flush: the batch is not
         // buffered, the stream is dropped, and the rows buffered so far are built from their kept bytes (build_sections_device).
         if (cfg_.device_ingest_stream && !stream_broken_) {
-            if (int32_t rc = stream_append(rows, pids)) { drop_stream(); stream_broken_ = true; return rc; }
+            if (int32_t rc = keyed ? stream_append_keyed(rows, pids) : stream_append(rows, pids)) { drop_stream(); stream_broken_ = true; return rc; }
         }
         bool should_flush = false;
         for (size_t i = 0; i < rows.size(); ++i) {
@@ -663,6 +680,7 @@ private:
     // every partition buffer got in it, numbered by first arrival (the blocks of a file are ordered by partition id)
     uint64_t stream_ = 0;
     std::map<std::string, uint32_t> stream_set_;
+    std::vector<std::string> stream_keys_;   // DevicePartition: the text of every set of the keyed stream (bsg_ingest_keys), stream_set_ its inverse
     std::map<uint32_t, std::vector<bsg_minmax>> stream_minmax_host_;   // per set: the MinMax contributions of the rows the appends handed back
     bool stream_broken_ = false;         // an append failed (and ingest_rows said so): this flush builds from the kept rows
     StreamStats stream_stats_;
@@ -921,6 +939,7 @@ private:
         if (stream_) bsg_ingest_free(ctx_, stream_);
         stream_ = 0;
         stream_set_.clear();
+        stream_keys_.clear();
         stream_minmax_host_.clear();
     }
 
@@ -965,6 +984,94 @@ private:
             for (uint32_t i = 0; i < n_fb; ++i) {
                 per_set.try_emplace(set_of_row[fb[i]], cfg_.tokenizer).first->second.index_row(rows[fb[i]]);
                 if (nf) {                           // ... and folded on the host: the device decided nothing of such a row, or the same values
+                    std::vector<bsg_minmax> &idx = stream_minmax_host_[set_of_row[fb[i]]];
+                    idx.resize(nf, bsg_minmax{});
+                    minmax_row(rows[fb[i]], cfg_.minmax_indexes, idx.data());
+                }
+            }
+            if (int32_t rc = add_host_entries(stream_, per_set)) return rc;
+        }
+        stream_stats_.batches += 1;
+        stream_stats_.rows += rows.size();
+        stream_stats_.host_rows += n_fb;
+        return kEngineOk;
+    }
+
+    // DevicePartition: the texts of the sets the keyed stream has made since the last look (bsg_ingest_keys) join stream_keys_ / stream_set_
+    int32_t stream_fetch_keys()
+    {
+        uint32_t n = 0;
+        uint64_t n_bytes = 0;
+        const uint32_t first = (uint32_t)stream_keys_.size();
+        if (bsg_ingest_keys(ctx_, stream_, first, nullptr, 0, nullptr, &n, &n_bytes)) return fail(kErrGpu, bsg_last_error(ctx_));
+        if (!n) return kEngineOk;
+        std::vector<uint8_t> kb((size_t)n_bytes + 1);
+        std::vector<uint32_t> ko((size_t)n + 1);
+        if (bsg_ingest_keys(ctx_, stream_, first, kb.data(), n_bytes, ko.data(), &n, &n_bytes)) return fail(kErrGpu, bsg_last_error(ctx_));
+        for (uint32_t i = 0; i < n; ++i) {
+            stream_keys_.emplace_back(reinterpret_cast<const char *>(kb.data()) + ko[i], ko[i + 1] - ko[i]);
+            stream_set_.emplace(stream_keys_.back(), first + i);
+        }
+        return kEngineOk;
+    }
+
+    // DevicePartition, ingest time: stream_append with the partition ids found by the device.  pids[i] is filled from the texts of the
+    // stream's sets; a row the partitioner hands back is parsed here (validate_object_row, the only rows it runs over), its text
+    // registered (bsg_ingest_add_sets_keyed), and the row finished by the host walker with the other fallback rows.
+    int32_t stream_append_keyed(const std::vector<std::string_view> &rows, std::vector<std::string> &pids)
+    {
+        const bsg_tokenizer tok = c_tokenizer();
+        const size_t nf = cfg_.minmax_indexes.size();
+        if (!stream_) {
+            std::vector<uint8_t> fb_bytes;
+            std::vector<uint32_t> f_off;
+            if (nf) pack_minmax_fields(fb_bytes, f_off);
+            if (bsg_ingest_open_keyed(ctx_, 1, 0, BSG_INGEST_TRUSTED_JSON /* TrustedRows */, &tok, &stream_,
+                                      reinterpret_cast<const uint8_t *>(cfg_.partition_field.data()), (uint32_t)cfg_.partition_field.size(),
+                                      nf ? fb_bytes.data() : nullptr, nf ? f_off.data() : nullptr, (uint32_t)nf))
+                return fail(kErrGpu, bsg_last_error(ctx_));
+        }
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> row_off{0};
+        for (std::string_view r : rows) { bytes.insert(bytes.end(), r.begin(), r.end()); row_off.push_back(bytes.size()); }
+        std::vector<uint32_t> set_of_row(rows.size()), fb(rows.size());
+        uint32_t n_fb = 0, n_new = 0;
+        if (bsg_ingest_append_rows_keyed(ctx_, stream_, bytes.data(), row_off.data(), (uint32_t)rows.size(), set_of_row.data(), &n_new, fb.data(),
+                                         (uint32_t)fb.size(), &n_fb))
+            return fail(kErrGpu, bsg_last_error(ctx_));
+        if (n_new) if (int32_t rc = stream_fetch_keys()) return rc;
+        // the rows the partitioner did not decide: their texts from the host parse, new ones registered in row order
+        std::vector<uint32_t> undecided;
+        std::vector<std::string> texts;
+        std::string scratch;
+        for (uint32_t i = 0; i < n_fb; ++i) {
+            if (set_of_row[fb[i]] != BSG_SET_UNDECIDED) continue;
+            std::string text;
+            bool has = false;
+            if (!validate_object_row(rows[fb[i]], cfg_.partition_field, text, has, scratch))
+                return fail(kErrInvalidRow, "row " + std::to_string(fb[i]) + " is not a JSON object");
+            if (!has) text.clear();
+            undecided.push_back(fb[i]);
+            texts.push_back(std::move(text));
+        }
+        if (!undecided.empty()) {
+            std::vector<uint8_t> kb;
+            std::vector<uint32_t> ko{0}, sets(texts.size());
+            for (const std::string &t : texts) { kb.insert(kb.end(), t.begin(), t.end()); ko.push_back((uint32_t)kb.size()); }
+            kb.push_back(0);
+            if (bsg_ingest_add_sets_keyed(ctx_, stream_, kb.data(), ko.data(), (uint32_t)texts.size(), sets.data())) return fail(kErrGpu, bsg_last_error(ctx_));
+            if (int32_t rc = stream_fetch_keys()) return rc;
+            for (size_t i = 0; i < undecided.size(); ++i) set_of_row[undecided[i]] = sets[i];
+        }
+        for (size_t i = 0; i < rows.size(); ++i) {
+            if (set_of_row[i] >= stream_keys_.size()) return fail(kErrGpu, "the keyed ingest named a set without a text");
+            pids[i] = stream_keys_[set_of_row[i]];
+        }
+        if (n_fb) {
+            std::map<uint32_t, BloomEntrySets> per_set;
+            for (uint32_t i = 0; i < n_fb; ++i) {
+                per_set.try_emplace(set_of_row[fb[i]], cfg_.tokenizer).first->second.index_row(rows[fb[i]]);
+                if (nf) {
                     std::vector<bsg_minmax> &idx = stream_minmax_host_[set_of_row[fb[i]]];
                     idx.resize(nf, bsg_minmax{});
                     minmax_row(rows[fb[i]], cfg_.minmax_indexes, idx.data());

@@ -8,6 +8,7 @@
 #include "engine.hpp"
 #include "regex_dfa.hpp"
 #include "minmax.hpp"
+#include "partition.hpp"
 #include "range.hpp"
 #include "substring.hpp"
 
@@ -435,6 +436,19 @@ int32_t bsh_minmax_row(const uint8_t *row, uint64_t len, const uint8_t *field_by
     return minmax_row(std::string_view(reinterpret_cast<const char *>(row), len), f.names, inout) ? 0 : BSH_E_INVALID;
 }
 
+// one row's partition text (partition.hpp partition_key: the first top-level member with the key; escapes decoded): 0, *out_len = its
+// length, the first min(cap, length) bytes in out; < 0 for an empty or over-long name or a row that is not one valid JSON object
+int32_t bsh_partition_key(const uint8_t *row, uint64_t len, const uint8_t *name, uint32_t name_len, uint8_t *out, uint64_t cap, uint64_t *out_len)
+{
+    if ((len && !row) || !name || name_len == 0 || name_len > BSG_PARTITION_MAX_NAME || !out_len || (cap && !out)) return BSH_E_INVALID;
+    std::string text;
+    if (!partition_key(std::string_view(reinterpret_cast<const char *>(row), len), std::string_view(reinterpret_cast<const char *>(name), name_len), text))
+        return BSH_E_INVALID;
+    *out_len = text.size();
+    if (!text.empty() && cap) memcpy(out, text.data(), std::min<uint64_t>(cap, text.size()));
+    return 0;
+}
+
 // EvaluateMinMaxCondition: 1 the block may hold a matching value, 0 it cannot, < 0 invalid arguments (an absent index included)
 int32_t bsh_minmax_eval(const bsg_minmax *index, uint32_t op, int64_t value, const int64_t *values, uint32_t n_values, int64_t min, int64_t max)
 {
@@ -534,6 +548,8 @@ int32_t bse_open(const char *config_json, uint64_t len, bsg_ctx *ctx, bse_engine
         if (const JNode *n = dom.get("PartitionField")) { if (n->type == JType::String) cfg.partition_field = n->text; }
         if (const JNode *n = dom.get("DeviceIngest")) cfg.device_ingest = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceIngestStream")) cfg.device_ingest_stream = n->type == JType::True;
+        if (const JNode *n = dom.get("TrustedRows")) cfg.trusted_rows = n->type == JType::True;
+        if (const JNode *n = dom.get("DevicePartition")) cfg.device_partition = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatch")) cfg.device_match = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceRegex")) cfg.device_regex = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchWide")) cfg.device_match_wide = n->type == JType::True;

@@ -38,7 +38,26 @@ struct IngestPart {
     uint32_t n_tables() const { return (n_sets + n_parents) * 3; }
 };
 
+// A keyed ingest (bsg_ingest_open_keyed; partition.hip.h): every set has a text, set s = keys[s].  The dictionary the kernels read
+// is rebuilt here from the texts and sent whole whenever it changes (a few keys per batch at most).
+struct PartitionKeys {
+    bsg::PkeyName name{};
+    uint32_t parent = 0xFFFFFFFFu;            // of every set the ingest creates
+    std::vector<std::string> keys;
+    std::unordered_map<std::string, uint32_t> set_of_key;
+    std::vector<bsg::PkeyDictEntry> dict;     // host mirror of d_dict
+    std::vector<uint8_t> pool;                // ... and of d_pool: the texts back to back
+    bsg::PkeyDictEntry *d_dict = nullptr;
+    uint8_t *d_pool = nullptr;
+    bsg::PkeyPending *d_pending = nullptr;
+    uint32_t dict_cap = 0;
+    uint64_t pool_cap = 0;
+    uint32_t built_mask = 0;                  // the hash mask the tags on the device were made with
+    bool dirty = true;                        // the device holds no dictionary, or not the one of `keys`
+};
+
 struct Ingest {
+    std::unique_ptr<PartitionKeys> keyed;     // made by bsg_ingest_open_keyed
     uint32_t n_rows = 0, n_sets = 0, n_parents = 0;
     std::vector<uint32_t> parent_of_set;
     std::vector<std::shared_ptr<IngestPart>> parts;
@@ -950,9 +969,11 @@ int32_t check_parents(const uint32_t *parent_of_set, uint32_t n_sets, uint32_t n
 }
 
 int32_t ingest_open_call(bsg_ctx *ctx, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents, const uint32_t *slots_hint,
-                         uint32_t flags, const bsg_tokenizer *tok_in, uint64_t *out_ingest_id, const bsg::MinMaxFields *mm = nullptr)
+                         uint32_t flags, const bsg_tokenizer *tok_in, uint64_t *out_ingest_id, const bsg::MinMaxFields *mm = nullptr,
+                         std::unique_ptr<PartitionKeys> keyed = nullptr)
 {
     auto I = std::make_shared<Ingest>();
+    I->keyed = std::move(keyed);
     if (mm) { I->has_mm = true; I->mm_fields = *mm; }
     if (int32_t rc = tok_spec(tok_in, I->tok, I->spec, I->tok_default)) return rc;
     if (!out_ingest_id) return fail(BSG_E_INVALID, "null argument");
@@ -1006,14 +1027,186 @@ int32_t get_open_stream(bsg_ctx *ctx, uint64_t id, std::shared_ptr<Ingest> &g, c
     return BSG_OK;
 }
 
+// ---- keyed ingest: the dictionary and the partition pass of one batch (partition.hip.h) ----
+
+// The dictionary over keys (set s = its index) and, behind them, `fresh` (texts this call has met and not numbered yet: their
+// entries carry kPkeyProvisional | index), built on the host and sent whole.  Caller holds the device lock; d.stream is idle.
+int32_t keyed_upload(IngestPart &G, PartitionKeys &K, uint32_t hash_mask, const std::vector<std::string> &fresh)
+{
+    Device &d = *G.dev;
+    const size_t nk = K.keys.size(), n = nk + fresh.size();
+    uint32_t cap = std::max<uint32_t>(64, K.dict_cap);
+    while ((uint64_t)cap < (uint64_t)n * 2 + 2) cap <<= 1;      // at most half full: a lookup always meets an empty slot
+    K.dict.assign(cap, bsg::PkeyDictEntry{0, 0, 0, 0});
+    K.pool.clear();
+    for (size_t i = 0; i < n; ++i) {
+        const std::string &t = i < nk ? K.keys[i] : fresh[i - nk];
+        const uint32_t tag = bsg::partition_tag_bytes(reinterpret_cast<const uint8_t *>(t.data()), (uint32_t)t.size(), hash_mask);
+        uint32_t slot = tag & (cap - 1);
+        while (K.dict[slot].tag) slot = (slot + 1) & (cap - 1);
+        K.dict[slot] = bsg::PkeyDictEntry{tag, i < nk ? (uint32_t)i : bsg::kPkeyProvisional | (uint32_t)(i - nk), (uint32_t)K.pool.size(), (uint32_t)t.size()};
+        K.pool.insert(K.pool.end(), t.begin(), t.end());
+    }
+    if (K.pool.size() > 0x7FFFFFFFull) return fail(BSG_E_INVALID, "keyed ingest: the partition texts exceed 2 GiB");
+    if (cap > K.dict_cap || !K.d_dict) {
+        HIP_TRY(G.mem.alloc(&K.d_dict, (size_t)cap * sizeof(bsg::PkeyDictEntry)));      // (the block before stays with G.mem until the ingest is freed)
+        K.dict_cap = cap;
+    }
+    if (K.pool.size() > K.pool_cap || !K.d_pool) {
+        const uint64_t room = std::max<uint64_t>(4096, K.pool.size() * 2);
+        HIP_TRY(G.mem.alloc(&K.d_pool, room));
+        K.pool_cap = room;
+    }
+    HIP_TRY(hipMemcpyAsync(K.d_dict, K.dict.data(), (size_t)cap * sizeof(bsg::PkeyDictEntry), hipMemcpyHostToDevice, d.stream));
+    if (!K.pool.empty()) HIP_TRY(hipMemcpyAsync(K.d_pool, K.pool.data(), K.pool.size(), hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    K.built_mask = hash_mask;
+    K.dirty = false;
+    return BSG_OK;
+}
+
+// the device scanner on the host's copy of one row (laid into aligned words with the look-ahead the scanner may read)
+bool keyed_host_text(const PartitionKeys &K, const uint8_t *row, uint64_t len, std::string &text)
+{
+    std::vector<uint64_t> words((size_t)(len >> 3) + 3, 0);
+    if (len) memcpy(words.data(), row, len);
+    const bsg::PkeyScan sc = bsg::partition_scan_row(words.data(), 0, len, K.name.name, K.name.len);
+    if (sc.undecided) return false;
+    text.assign(reinterpret_cast<const char *>(words.data()) + sc.pos, sc.len);
+    return true;
+}
+
+struct KeyedCall {
+    uint32_t *out_set_of_row;
+    uint32_t *out_n_new_sets;
+    uint32_t hash_mask;
+};
+
+// The partition pass of one keyed batch: uploads the rows chunk by chunk with k_partition_rows behind each chunk, resolves the new
+// texts in rounds (host: pending slots -> dictionary; device: k_partition_assign), numbers them by their lowest row, creates their
+// sets and leaves: sets[r] (final numbers, kPkeyUndecided for the rows handed back), kept = the rows to walk, kept_sets their sets.
+// The row bytes stay resident in d_rows.  Caller holds the device lock.
+int32_t partition_batch(bsg_ctx *ctx, Ingest &I, IngestPart &G, Scratch &scratch, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                        uint8_t *d_rows, uint64_t *d_row_off, const KeyedCall &kc, std::vector<uint32_t> &sets, std::vector<uint32_t> &kept,
+                        std::vector<uint32_t> &kept_sets, float *ms_partition)
+{
+    Device &d = *G.dev;
+    PartitionKeys &K = *I.keyed;
+    if (K.dirty || K.built_mask != kc.hash_mask || !K.d_dict) if (int32_t rc = keyed_upload(G, K, kc.hash_mask, {})) return rc;
+    uint32_t *d_set = nullptr;
+    bsg::PkeyRow *d_key = nullptr;
+    HIP_TRY(scratch.alloc(&d_set, (size_t)n_rows * 4));
+    HIP_TRY(scratch.alloc(&d_key, (size_t)n_rows * sizeof(bsg::PkeyRow)));
+    if (!K.d_pending) HIP_TRY(G.mem.alloc(&K.d_pending, bsg::kPkeyPendingSlots * sizeof(bsg::PkeyPending)));
+    const std::vector<bsg::PkeyPending> unclaimed(bsg::kPkeyPendingSlots, bsg::PkeyPending{0u, 0xFFFFFFFFu});
+    HIP_TRY(hipMemcpyAsync(K.d_pending, unclaimed.data(), unclaimed.size() * sizeof(bsg::PkeyPending), hipMemcpyHostToDevice, d.stream));
+    bsg::PkeyArgs a{};
+    a.rows = d_rows; a.row_off = d_row_off; a.dict = K.d_dict; a.pool = K.d_pool; a.pending = K.d_pending; a.row_key = d_key; a.set_of_row = d_set;
+    a.dict_mask = K.dict_cap - 1; a.hash_mask = kc.hash_mask;
+    EventList ev;
+    auto timed = [&](auto &&launch) -> hipError_t {
+        if (hipError_t e = ev.add(2); e != hipSuccess) return e;
+        launch(ev.v[ev.v.size() - 2], ev.v.back());
+        return hipGetLastError();
+    };
+    // the scan of chunk c runs behind chunk c's bytes while chunk c + 1 travels on the copy stream
+    RowUpload up(d, rows, d_rows, row_off, n_rows, ctx->ingest_chunk_bytes);
+    HIP_TRY(up.start(true));
+    for (uint32_t c = 0; c < up.n_chunks(); ++c) {
+        HIP_TRY(up.copy(c));
+        HIP_TRY(up.wait_landed(c));
+        bsg::PkeyArgs b = a;
+        b.row_first = up.cuts[c]; b.row_end = up.cuts[c + 1];
+        if (b.row_end == b.row_first) continue;
+        const uint32_t grid = (b.row_end - b.row_first + bsg::kPkeyThreads - 1) / bsg::kPkeyThreads;
+        HIP_TRY(timed([&](hipEvent_t e0, hipEvent_t e1) {
+            hipExtLaunchKernelGGL(bsg::k_partition_rows, dim3(grid), dim3(bsg::kPkeyThreads), 0, d.stream, e0, e1, 0, b, K.name);
+        }));
+    }
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    HIP_TRY(hipStreamSynchronize(d.copy_stream));
+    // rounds: the claimed slots' texts join the dictionary (provisionally numbered), the rows still unassigned are resolved again
+    std::vector<std::string> fresh;
+    std::vector<uint32_t> fresh_row;
+    std::vector<bsg::PkeyPending> pend(bsg::kPkeyPendingSlots);
+    for (uint64_t round = 0;; ++round) {
+        HIP_TRY(hipMemcpy(pend.data(), K.d_pending, pend.size() * sizeof(bsg::PkeyPending), hipMemcpyDeviceToHost));
+        const size_t before = fresh.size();
+        for (const bsg::PkeyPending &p : pend) {
+            if (!p.tag) continue;
+            std::string text;
+            if (p.first_row >= n_rows || !keyed_host_text(K, rows + row_off[p.first_row], row_off[p.first_row + 1] - row_off[p.first_row], text))
+                return fail(BSG_E_HIP, "keyed ingest: pending slot names row %u, which holds no decided text", p.first_row);
+            fresh.push_back(std::move(text));
+            fresh_row.push_back(p.first_row);
+        }
+        if (fresh.size() == before) break;
+        if (round > n_rows) return fail(BSG_E_HIP, "keyed ingest: the partition rounds do not end");
+        if ((uint64_t)I.n_sets + fresh.size() > BSG_PARTITION_MAX_SETS)
+            return fail(BSG_E_INVALID, "keyed ingest: %u sets and %zu new keys exceed BSG_PARTITION_MAX_SETS (%u)", I.n_sets, fresh.size(), BSG_PARTITION_MAX_SETS);
+        if (int32_t rc = keyed_upload(G, K, kc.hash_mask, fresh)) return rc;
+        K.dirty = true;                        // until the sets below exist, the device's dictionary is this call's own
+        HIP_TRY(hipMemcpyAsync(K.d_pending, unclaimed.data(), unclaimed.size() * sizeof(bsg::PkeyPending), hipMemcpyHostToDevice, d.stream));
+        bsg::PkeyArgs b = a;
+        b.dict = K.d_dict; b.pool = K.d_pool; b.dict_mask = K.dict_cap - 1;
+        b.row_first = 0; b.row_end = n_rows;
+        const uint32_t grid = (n_rows + bsg::kPkeyThreads - 1) / bsg::kPkeyThreads;
+        HIP_TRY(timed([&](hipEvent_t e0, hipEvent_t e1) {
+            hipExtLaunchKernelGGL(bsg::k_partition_assign, dim3(grid), dim3(bsg::kPkeyThreads), 0, d.stream, e0, e1, 0, b);
+        }));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+    }
+    // the number of new keys is known: their sets, numbered by the lowest row that holds each
+    const uint32_t n_new = (uint32_t)fresh.size(), old_sets = I.n_sets;
+    std::vector<uint32_t> by_row(n_new), rank(n_new);
+    std::iota(by_row.begin(), by_row.end(), 0u);
+    std::sort(by_row.begin(), by_row.end(), [&](uint32_t x, uint32_t y) { return fresh_row[x] < fresh_row[y]; });
+    for (uint32_t i = 0; i < n_new; ++i) rank[by_row[i]] = i;
+    if (n_new) {
+        if ((uint64_t)old_sets + n_new + I.n_parents > 0xFFFFFFFFu / 3) return fail(BSG_E_INVALID, "too many sets and parents");
+        const std::vector<uint32_t> parent(n_new, K.parent);
+        if (int32_t rc = stream_add_sets(G, n_new, parent.data(), nullptr)) return rc;     // (K.dirty: the next call sends the dictionary of K.keys again)
+        I.n_sets = G.n_sets;
+        I.parent_of_set = G.parent_of_set;
+        I.set_cut = {0, I.n_sets};
+        for (uint32_t i = 0; i < n_new; ++i) {
+            K.set_of_key.emplace(fresh[by_row[i]], (uint32_t)K.keys.size());
+            K.keys.push_back(fresh[by_row[i]]);
+        }
+    }
+    if (K.dirty) if (int32_t rc = keyed_upload(G, K, kc.hash_mask, {})) return rc;
+    sets.resize(n_rows);
+    HIP_TRY(hipMemcpy(sets.data(), d_set, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
+    kept.clear(); kept_sets.clear();
+    for (uint32_t r = 0; r < n_rows; ++r) {
+        uint32_t s = sets[r];
+        if (s == bsg::kPkeyNew) s = bsg::kPkeyUndecided;                        // (no round leaves one; handing it back is exact all the same)
+        else if (s != bsg::kPkeyUndecided && (s & bsg::kPkeyProvisional)) s = old_sets + rank[s & ~bsg::kPkeyProvisional];
+        if (s != bsg::kPkeyUndecided && s >= I.n_sets) return fail(BSG_E_HIP, "keyed ingest: row %u was given set %u of %u", r, s, I.n_sets);
+        sets[r] = s;
+        if (s != bsg::kPkeyUndecided) { kept.push_back(r); kept_sets.push_back(s); }
+    }
+    for (size_t i = 0; i + 1 < ev.v.size(); i += 2) {
+        float t = 0.f;
+        HIP_TRY(hipEventElapsedTime(&t, ev.v[i], ev.v[i + 1]));
+        *ms_partition += t;
+    }
+    memcpy(kc.out_set_of_row, sets.data(), (size_t)n_rows * 4);
+    *kc.out_n_new_sets = n_new;
+    return BSG_OK;
+}
+
 // One batch of a streaming ingest: rows in any order of sets, walked chunk by chunk in the order row_groups.hpp gives them.
+// kc (bsg_ingest_append_rows_keyed; set_of_row is NULL): the batch is partitioned on the device first (partition_batch), then the rows
+// it decided are walked from the resident bytes as one chunk; the rows it handed back join the fallback list and are not walked.
 int32_t append_rows_stream(bsg_ctx *ctx, Ingest &I, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows, const uint32_t *set_of_row,
-                           uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *n_fallback)
+                           uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *n_fallback, const KeyedCall *kc = nullptr)
 {
     IngestPart &G = *I.parts[0];
     Device &d = *G.dev;
     const uint64_t n_bytes = row_off[n_rows];
-    const LabTrace trace{"bsg_ingest_append_rows", d.id};
+    const char *call = kc ? "bsg_ingest_append_rows_keyed" : "bsg_ingest_append_rows";
+    const LabTrace trace{call, d.id};
     d.calls.fetch_add(1, std::memory_order_relaxed);
     std::lock_guard<std::mutex> lk(d.mu);
     if (int32_t rc = use_device(d)) return rc;
@@ -1030,6 +1223,15 @@ int32_t append_rows_stream(bsg_ctx *ctx, Ingest &I, const uint8_t *rows, const u
     HIP_TRY(hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream));
     HIP_TRY(hipMemcpyAsync(d_row_off, row_off, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipMemsetAsync(G.d_nfb, 0, 128, d.stream));
+    std::vector<uint32_t> part_sets, kept, kept_sets;      // (keyed) every row's set, the rows to walk and their sets
+    float ms_partition = 0.f;
+    uint32_t n_walk = n_rows;
+    if (kc) {
+        if (int32_t rc = partition_batch(ctx, I, G, scratch, rows, row_off, n_rows, d_rows, d_row_off, *kc, part_sets, kept, kept_sets, &ms_partition)) return rc;
+        trace.lap("rows partitioned");
+        set_of_row = kept_sets.data();
+        n_walk = (uint32_t)kept.size();
+    }
     bsg::IngestArgs a{};
     a.rows = d_rows; a.row_off = d_row_off;
     a.counts = G.d_counts; a.status = G.d_status; a.fallback_rows = d_fb; a.n_fallback = G.d_nfb;
@@ -1040,12 +1242,17 @@ int32_t append_rows_stream(bsg_ctx *ctx, Ingest &I, const uint8_t *rows, const u
     const bsg::RowsBySet by_set{d_order, d_set_of_order};
     MinMaxWalk mmw(G);
     if (int32_t rc = mmw.prepare(scratch, a, n_rows, &by_set)) return rc;
-    std::vector<uint32_t> order(n_rows), set_of_order(n_rows), group_scratch;
-    RowUpload up(d, rows, d_rows, row_off, n_rows, ctx->ingest_chunk_bytes);
+    std::vector<uint32_t> order(n_walk), set_of_order(n_walk), group_scratch;
+    std::optional<RowUpload> up_box;
+    if (kc) up_box.emplace(d, n_walk);     // the bytes are resident: positions [0, n_walk) of the walking order, one chunk
+    else up_box.emplace(d, rows, d_rows, row_off, n_rows, ctx->ingest_chunk_bytes);
+    RowUpload &up = *up_box;
+    if (n_walk)
     if (int32_t rc = walk_chunks(d, G, up, a, G.n_sets * 3, trace,
             [&](uint32_t c) -> hipError_t {   // the chunk's walking order lands with its bytes
                 const uint32_t rf = up.cuts[c], re = up.cuts[c + 1];
                 bsh::group_rows_by_set(set_of_row, rf, re, G.n_sets, order.data(), set_of_order.data(), group_scratch);
+                if (kc) for (uint32_t i = rf; i < re; ++i) order[i] = kept[order[i]];      // positions among the kept rows -> rows of the batch
                 hipError_t e = hipMemcpyAsync(d_order + rf, order.data() + rf, (size_t)(re - rf) * 4, hipMemcpyHostToDevice, up.cs);
                 if (e == hipSuccess) e = hipMemcpyAsync(d_set_of_order + rf, set_of_order.data() + rf, (size_t)(re - rf) * 4, hipMemcpyHostToDevice, up.cs);
                 return e;
@@ -1059,22 +1266,29 @@ int32_t append_rows_stream(bsg_ctx *ctx, Ingest &I, const uint8_t *rows, const u
                     hipExtLaunchKernelGGL(bsg::k_ingest_rows_sets, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, by_set);
             },
             [&](uint32_t, uint32_t rf, uint32_t re) { return mmw.launch(rf, re); })) return rc;
-    HIP_TRY(hipStreamSynchronize(d.copy_stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    if (d.copy_stream) HIP_TRY(hipStreamSynchronize(d.copy_stream));
     trace.lap("all chunks walked");
     uint32_t nfb = 0;
     HIP_TRY(hipMemcpy(&nfb, G.d_nfb, 4, hipMemcpyDeviceToHost));
     std::vector<uint32_t> fb(nfb);
     if (nfb) HIP_TRY(hipMemcpy(fb.data(), d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
+    if (kc) for (uint32_t r = 0; r < n_rows; ++r) if (part_sets[r] == bsg::kPkeyUndecided) fb.push_back(r);     // merge_fallback sorts: ascending, each row once
     std::sort(fb.begin(), fb.end());
     if (int32_t rc = mmw.merge_fallback(fb)) return rc;
+    if (kc) { std::sort(fb.begin(), fb.end()); fb.erase(std::unique(fb.begin(), fb.end()), fb.end()); }        // (an ingest without fields: merge_fallback did nothing)
     nfb = (uint32_t)fb.size();
-    { std::lock_guard<std::shared_mutex> lk2(ctx->mu); ctx->last_minmax_ms = G.ms_minmax; }
+    {
+        std::lock_guard<std::shared_mutex> lk2(ctx->mu);
+        ctx->last_minmax_ms = G.ms_minmax;
+        if (kc) ctx->last_partition_ms = ms_partition;
+    }
     scratch.done();                        // both streams have been synchronised: the row bytes leave the device here
     *n_fallback = nfb;
     // a call that could not deliver its list is appended again (or walked on the host): its rows are counted by the call that does
     const bool count_only = !out_fallback_rows && fallback_cap == 0;
     if (!count_only && nfb > fallback_cap)
-        return fail(BSG_E_INVALID, "bsg_ingest_append_rows: %u rows are handed back, out_fallback_rows has room for %u", nfb, fallback_cap);
+        return fail(BSG_E_INVALID, "%s: %u rows are handed back, out_fallback_rows has room for %u", call, nfb, fallback_cap);
     if (count_only && nfb) return BSG_OK;
     G.n_rows += n_rows;
     I.n_rows += n_rows;
@@ -1187,6 +1401,7 @@ int32_t bsg_ingest_add_sets(bsg_ctx *ctx, uint64_t ingest_id, uint32_t n_more, c
     std::shared_ptr<Ingest> g;
     if (int32_t rc = get_open_stream(ctx, ingest_id, g, "bsg_ingest_add_sets")) return rc;
     Ingest &I = *g;
+    if (I.keyed) return fail(BSG_E_INVALID, "bsg_ingest_add_sets: ingest %llu is keyed, every set of it has a text (bsg_ingest_add_sets_keyed)", (unsigned long long)ingest_id);
     if ((uint64_t)I.n_sets + n_more + I.n_parents > 0xFFFFFFFFu / 3) return fail(BSG_E_INVALID, "too many sets and parents");
     if (int32_t rc = check_parents(parent_of_new_set, n_more, I.n_parents)) return rc;
     *out_first_new_set = I.n_sets;
@@ -1219,6 +1434,132 @@ int32_t bsg_ingest_append_rows(bsg_ctx *ctx, uint64_t ingest_id, const uint8_t *
     if (const uint32_t bad = bsh::first_bad_set(set_of_row, n_rows, g->n_sets); bad < n_rows)
         return fail(BSG_E_INVALID, "set_of_row[%u] = %u, the ingest has %u sets", bad, set_of_row[bad], g->n_sets);
     return append_rows_stream(ctx, *g, rows, row_off, n_rows, set_of_row, out_fallback_rows, fallback_cap, out_n_fallback);
+}
+
+// ---- keyed ingest: rows partitioned on the device by a top-level field (partition.hip.h) ----
+
+int32_t bsg_ingest_open_keyed(bsg_ctx *ctx, uint32_t n_parents, uint32_t parent_of_new_sets, uint32_t flags, const bsg_tokenizer *tok,
+                              uint64_t *out_ingest_id, const uint8_t *name_bytes, uint32_t name_len,
+                              const uint8_t *field_bytes, const uint32_t *field_off, uint32_t n_fields)
+{
+    BSG_ENTER(ctx);
+    if (name_len == 0) return fail(BSG_E_INVALID, "bsg_ingest_open_keyed: the partition field's name is empty");
+    if (name_len > BSG_PARTITION_MAX_NAME) return fail(BSG_E_INVALID, "bsg_ingest_open_keyed: the partition field's name has %u bytes (at most %u)", name_len, BSG_PARTITION_MAX_NAME);
+    if (!name_bytes) return fail(BSG_E_INVALID, "bsg_ingest_open_keyed: name_bytes is null");
+    if (parent_of_new_sets != 0xFFFFFFFFu && parent_of_new_sets >= n_parents)
+        return fail(BSG_E_INVALID, "bsg_ingest_open_keyed: parent_of_new_sets = %u, the ingest has %u parents", parent_of_new_sets, n_parents);
+    bsg::MinMaxFields mm;
+    if (n_fields || field_bytes || field_off) if (int32_t rc = minmax_fields(field_bytes, field_off, n_fields, mm)) return rc;
+    auto K = std::make_unique<PartitionKeys>();
+    memcpy(K->name.name, name_bytes, name_len);
+    K->name.len = name_len;
+    K->parent = parent_of_new_sets;
+    return ingest_open_call(ctx, 0, nullptr, n_parents, nullptr, flags, tok, out_ingest_id, n_fields ? &mm : nullptr, std::move(K));
+}
+
+int32_t bsg_ingest_append_rows_keyed(bsg_ctx *ctx, uint64_t ingest_id, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                     uint32_t *out_set_of_row, uint32_t *out_n_new_sets, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                     uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    if (!out_n_fallback || !out_n_new_sets) return fail(BSG_E_INVALID, "null argument");
+    std::shared_ptr<Ingest> g;
+    if (int32_t rc = get_open_stream(ctx, ingest_id, g, "bsg_ingest_append_rows_keyed")) return rc;
+    if (!g->keyed) return fail(BSG_E_INVALID, "bsg_ingest_append_rows_keyed: ingest %llu was not made by bsg_ingest_open_keyed", (unsigned long long)ingest_id);
+    *out_n_fallback = 0;
+    *out_n_new_sets = 0;
+    if (n_rows == 0) return BSG_OK;
+    if (!row_off || !out_set_of_row || (!out_fallback_rows && fallback_cap)) return fail(BSG_E_INVALID, "null argument");
+    for (uint32_t r = 0; r < n_rows; ++r)
+        if (row_off[r + 1] < row_off[r]) return fail(BSG_E_INVALID, "row_off not monotone at %u", r);
+    if (row_off[n_rows] && !rows) return fail(BSG_E_INVALID, "rows is null");
+    uint32_t mask = 0;
+    { std::shared_lock<std::shared_mutex> lk(ctx->mu); mask = ctx->partition_hash_mask; }
+    const KeyedCall kc{out_set_of_row, out_n_new_sets, mask};
+    return append_rows_stream(ctx, *g, rows, row_off, n_rows, nullptr, out_fallback_rows, fallback_cap, out_n_fallback, &kc);
+}
+
+int32_t bsg_ingest_add_sets_keyed(bsg_ctx *ctx, uint64_t ingest_id, const uint8_t *key_bytes, const uint32_t *key_off, uint32_t n_keys,
+                                  uint32_t *out_set_of_key)
+{
+    BSG_ENTER(ctx);
+    std::shared_ptr<Ingest> g;
+    if (int32_t rc = get_open_stream(ctx, ingest_id, g, "bsg_ingest_add_sets_keyed")) return rc;
+    Ingest &I = *g;
+    if (!I.keyed) return fail(BSG_E_INVALID, "bsg_ingest_add_sets_keyed: ingest %llu was not made by bsg_ingest_open_keyed", (unsigned long long)ingest_id);
+    if (n_keys == 0) return BSG_OK;
+    if (!key_off || !out_set_of_key) return fail(BSG_E_INVALID, "null argument");
+    for (uint32_t i = 0; i < n_keys; ++i)
+        if (key_off[i + 1] < key_off[i]) return fail(BSG_E_INVALID, "key_off not monotone at %u", i);
+    if (key_off[n_keys] && !key_bytes) return fail(BSG_E_INVALID, "key_bytes is null");
+    PartitionKeys &K = *I.keyed;
+    // which texts are new is known before any set is made
+    std::vector<std::string> fresh;
+    std::unordered_map<std::string, uint32_t> fresh_set;
+    for (uint32_t i = 0; i < n_keys; ++i) {
+        std::string t(reinterpret_cast<const char *>(key_bytes) + key_off[i], key_off[i + 1] - key_off[i]);
+        if (auto it = K.set_of_key.find(t); it != K.set_of_key.end()) { out_set_of_key[i] = it->second; continue; }
+        auto [it, fresh_one] = fresh_set.emplace(t, I.n_sets + (uint32_t)fresh.size());
+        if (fresh_one) fresh.push_back(std::move(t));
+        out_set_of_key[i] = it->second;
+    }
+    if (fresh.empty()) return BSG_OK;
+    if ((uint64_t)I.n_sets + fresh.size() > BSG_PARTITION_MAX_SETS)
+        return fail(BSG_E_INVALID, "bsg_ingest_add_sets_keyed: %u sets and %zu new keys exceed BSG_PARTITION_MAX_SETS (%u)", I.n_sets, fresh.size(), BSG_PARTITION_MAX_SETS);
+    if ((uint64_t)I.n_sets + fresh.size() + I.n_parents > 0xFFFFFFFFu / 3) return fail(BSG_E_INVALID, "too many sets and parents");
+    IngestPart &G = *I.parts[0];
+    {
+        std::lock_guard<std::mutex> lk(G.dev->mu);
+        if (int32_t rc = use_device(*G.dev)) return rc;
+        const std::vector<uint32_t> parent(fresh.size(), K.parent);
+        if (int32_t rc = stream_add_sets(G, (uint32_t)fresh.size(), parent.data(), nullptr)) return rc;
+    }
+    I.n_sets = G.n_sets;
+    I.parent_of_set = G.parent_of_set;
+    I.set_cut = {0, I.n_sets};
+    for (std::string &t : fresh) {
+        K.set_of_key.emplace(t, (uint32_t)K.keys.size());
+        K.keys.push_back(std::move(t));
+    }
+    K.dirty = true;                            // the next keyed append sends the dictionary
+    return BSG_OK;
+}
+
+int32_t bsg_ingest_keys(bsg_ctx *ctx, uint64_t ingest_id, uint32_t first, uint8_t *out_bytes, uint64_t bytes_cap, uint32_t *out_off,
+                        uint32_t *out_n_keys, uint64_t *out_n_bytes)
+{
+    BSG_ENTER(ctx);
+    if (!out_n_keys || !out_n_bytes) return fail(BSG_E_INVALID, "null argument");
+    std::shared_ptr<Ingest> g;
+    if (int32_t rc = get_ingest(ctx, ingest_id, g)) return rc;
+    if (!g->keyed) return fail(BSG_E_INVALID, "bsg_ingest_keys: ingest %llu was not made by bsg_ingest_open_keyed", (unsigned long long)ingest_id);
+    const PartitionKeys &K = *g->keyed;
+    if (first > K.keys.size()) return fail(BSG_E_INVALID, "bsg_ingest_keys: first = %u, the ingest has %zu sets", first, K.keys.size());
+    uint64_t total = 0;
+    for (size_t s = first; s < K.keys.size(); ++s) total += K.keys[s].size();
+    *out_n_keys = (uint32_t)(K.keys.size() - first);
+    *out_n_bytes = total;
+    if (!out_bytes && !out_off) return BSG_OK;       // the sizes only
+    if (!out_off || (total && !out_bytes)) return fail(BSG_E_INVALID, "null argument");
+    if (total > bytes_cap) return fail(BSG_E_INVALID, "bsg_ingest_keys: %llu bytes, out_bytes has room for %llu", (unsigned long long)total, (unsigned long long)bytes_cap);
+    if (total > 0xFFFFFFFFull) return fail(BSG_E_INVALID, "bsg_ingest_keys: the texts exceed 32-bit offsets; ask for fewer sets");
+    uint32_t at = 0;
+    for (size_t s = first; s < K.keys.size(); ++s) {
+        out_off[s - first] = at;
+        if (!K.keys[s].empty()) memcpy(out_bytes + at, K.keys[s].data(), K.keys[s].size());
+        at += (uint32_t)K.keys[s].size();
+    }
+    out_off[K.keys.size() - first] = at;
+    return BSG_OK;
+}
+
+int32_t bsg_last_partition_ms(bsg_ctx *ctx, float *partition_ms)
+{
+    BSG_ENTER(ctx);
+    if (!partition_ms) return fail(BSG_E_INVALID, "null argument");
+    std::shared_lock<std::shared_mutex> lk(ctx->mu);
+    *partition_ms = ctx->last_partition_ms;
+    return BSG_OK;
 }
 
 int32_t bsg_ingest_fallback_rows(bsg_ctx *ctx, uint64_t ingest_id, uint32_t *rows_out, uint32_t cap, uint32_t *n_out)

@@ -1317,6 +1317,7 @@ extern "C" int32_t bsg_set_lab(bsg_ctx *ctx, uint32_t key, uint64_t value)
     if (key == 26) { ctx->gather_kernel = value ? 1u : 0u; return BSG_OK; }     // 0: launches never take k_probe_gather (tools/probe_gather_lab.py: the per-block gathered path of k_probe_terms on its own)
     if (key == 28) { ctx->gather_wgs_per_cu = (uint32_t)std::min<uint64_t>(value, 255); return BSG_OK; }     // workgroups of the gather kernels per CU, by an LDS pad (bsh::gather_lds_pad): 0 = the planner's rule, 1-4, above 4 = no cap
     if (key == 27) { ctx->pipeline_key = value & 0xFFFFFFFFull; return BSG_OK; }     // 0: bsh::pipeline_chunks decides, 1: never, n (+ last-chunk percent << 16, + placement << 24): n chunks
+    if (key == 29) { ctx->partition_hash_mask = value ? 3u : 0xFFFFFFFFu; return BSG_OK; }     // 1: the partition dictionary's hash keeps its low 2 bits (partition.hip.h: the byte compare and the collision rounds, on purpose)
     if (key == 17) { ctx->cmb.sync.spin_us = (uint32_t)std::min<uint64_t>(value, 1000000); return BSG_OK; }
     return fail(BSG_E_INVALID, "unknown lab key %u", key);
 }

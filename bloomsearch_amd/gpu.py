@@ -579,6 +579,65 @@ class Context:
                                                   _lib._ptr(fb), n_rows, C.byref(n)))
         return fb[: n.value].copy()
 
+    # keyed streaming ingest: the device finds every row's set from the text of one top-level member (bloomgpu.h)
+    def ingest_open_keyed(self, partition_field, n_parents: int = 0, parent_of_new_sets: int = 0xFFFFFFFF, flags: int = 0, tokenizer=None,
+                          minmax_fields=None) -> int:
+        name = partition_field.encode() if isinstance(partition_field, str) else bytes(partition_field)
+        nbuf = np.frombuffer(name + b"\0", dtype=np.uint8)
+        out = C.c_uint64()
+        fblob = foff = None
+        if minmax_fields is not None:
+            fblob, foff = pack_entries([f.encode() if isinstance(f, str) else bytes(f) for f in minmax_fields])
+        self._check(self.L.bsg_ingest_open_keyed(self.h, n_parents, parent_of_new_sets, flags, None if tokenizer is None else c_spec(tokenizer),
+                                                 C.byref(out), nbuf.ctypes.data, len(name), _lib._ptr(fblob), _lib._ptr(foff),
+                                                 0 if foff is None else len(foff) - 1))
+        if foff is not None:
+            self._minmax_fields[int(out.value)] = len(foff) - 1
+        return int(out.value)
+
+    def ingest_append_rows_keyed(self, ingest_id: int, rows, fallback_cap=None):
+        """rows: list[bytes] (or (u8 blob, u64 offsets[n+1])).  -> (set_of_row u32 [n], _lib.SET_UNDECIDED where the partitioner handed
+        the row back; number of sets the call created; batch-local indices, ascending, of every row handed back)."""
+        if isinstance(rows, tuple):
+            blob, off = rows
+            blob = np.ascontiguousarray(blob, dtype=np.uint8)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+        else:
+            off = np.zeros(len(rows) + 1, dtype=np.uint64)
+            if rows:
+                off[1:] = np.cumsum([len(r) for r in rows], dtype=np.uint64)
+            blob = np.frombuffer(b"".join(rows), dtype=np.uint8)
+        n_rows = len(off) - 1
+        cap = n_rows if fallback_cap is None else fallback_cap
+        sor = np.zeros(max(n_rows, 1), dtype=np.uint32)
+        fb = np.zeros(max(cap, 1), dtype=np.uint32)
+        n, n_new = C.c_uint32(), C.c_uint32()
+        self._check(self.L.bsg_ingest_append_rows_keyed(self.h, ingest_id, _lib._ptr(blob), _lib._ptr(off), n_rows, _lib._ptr(sor), C.byref(n_new),
+                                                        _lib._ptr(fb), cap, C.byref(n)))
+        return sor[:n_rows].copy(), int(n_new.value), fb[: n.value].copy()
+
+    def ingest_add_sets_keyed(self, ingest_id: int, keys) -> np.ndarray:
+        """keys: list[bytes] of partition texts found on the host -> their sets (known texts keep theirs, new ones get the next)."""
+        blob, off = pack_entries([k.encode() if isinstance(k, str) else bytes(k) for k in keys])
+        out = np.zeros(max(len(off) - 1, 1), dtype=np.uint32)
+        self._check(self.L.bsg_ingest_add_sets_keyed(self.h, ingest_id, blob.ctypes.data, off.ctypes.data, len(off) - 1, out.ctypes.data))
+        return out[: len(off) - 1].copy()
+
+    def ingest_keys(self, ingest_id: int, first: int = 0) -> list:
+        """the partition texts of sets [first, n_sets) of a keyed ingest"""
+        n, nb = C.c_uint32(), C.c_uint64()
+        self._check(self.L.bsg_ingest_keys(self.h, ingest_id, first, None, 0, None, C.byref(n), C.byref(nb)))
+        blob = np.zeros(max(int(nb.value), 1), dtype=np.uint8)
+        off = np.zeros(n.value + 1, dtype=np.uint32)
+        self._check(self.L.bsg_ingest_keys(self.h, ingest_id, first, blob.ctypes.data, int(nb.value), off.ctypes.data, C.byref(n), C.byref(nb)))
+        raw = blob.tobytes()
+        return [raw[int(off[i]): int(off[i + 1])] for i in range(n.value)]
+
+    def last_partition_ms(self) -> float:
+        v = C.c_float()
+        self._check(self.L.bsg_last_partition_ms(self.h, C.byref(v)))
+        return float(v.value)
+
     def ingest_minmax(self, ingest_id: int, n_sets: int):
         """The MinMax indexes of an ingest made with minmax_fields, as the device folded them (the rows it handed back are NOT in:
         fold them in with host.minmax_row): (min i64, max i64, present bool), each of shape (n_sets, n_fields); min = max = 0

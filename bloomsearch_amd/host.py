@@ -19,7 +19,7 @@ HOST_EXPORTS = [
     "bsh_batch_new", "bsh_batch_free", "bsh_batch_add_query", "bsh_batch_sizes", "bsh_batch_export", "bsh_match_row", "bsh_match_row_with", "bsh_prune_query", "bsh_match_row_regex",
     "bsh_substring_terms", "bsh_prune_query_sub", "bsh_match_row_substring",
     "bsh_match_row_range", "bsh_prune_query_range",
-    "bsh_minmax_row", "bsh_minmax_eval", "bsh_prefilter_eval",
+    "bsh_minmax_row", "bsh_minmax_eval", "bsh_prefilter_eval", "bsh_partition_key",
     "bsh_regex_match",
     "bsh_section_encode", "bsh_section_parse", "bsh_crc32c",
     "bse_open", "bse_close", "bse_last_error", "bse_stop", "bse_ingest_rows", "bse_flush", "bse_merge", "bse_query", "bse_query_many",
@@ -69,6 +69,7 @@ def lib():
     L.bsh_match_row_range.argtypes = [C.c_char_p, u64, C.c_char_p, u64]
     L.bsh_prune_query_range.argtypes = [C.c_char_p, u64, C.c_char_p, u64, C.c_char_p, u64, C.c_char_p, u64, C.POINTER(_lib.Tokenizer), pp, pu64]
     L.bsh_minmax_row.argtypes = [C.c_char_p, u64, vp, vp, u32, vp]
+    L.bsh_partition_key.argtypes = [C.c_char_p, u64, C.c_char_p, u32, vp, u64, C.POINTER(u64)]
     L.bsh_minmax_eval.argtypes = [vp, u32, C.c_int64, vp, u32, C.c_int64, C.c_int64]
     L.bsh_prefilter_eval.argtypes = [C.c_char_p, u64, C.c_char_p, u64, vp, vp, u32, vp]
     L.bsh_section_encode.argtypes = [C.POINTER(vp), pu64, pu64, pp, pu64]
@@ -326,6 +327,19 @@ def minmax_row(row: bytes, fields, index=None) -> np.ndarray:
     if rc:
         raise HostError(rc)
     return index
+
+
+def partition_key(row: bytes, name) -> bytes:
+    """bsh_partition_key: the row's partition text under the field `name` (the keyed ingest's rule, exact for every row: escapes
+    decoded).  HostError for a row that is not one valid JSON object, or a name of 0 or more than 64 bytes."""
+    L = lib()
+    name = name.encode() if isinstance(name, str) else bytes(name)
+    out = np.zeros(max(len(row), 1), dtype=np.uint8)
+    n = C.c_uint64()
+    rc = L.bsh_partition_key(row, len(row), name, len(name), out.ctypes.data, len(out), C.byref(n))
+    if rc:
+        raise HostError(rc)
+    return out[: n.value].tobytes()
 
 
 def minmax_eval(imin: int, imax: int, op, value: int = 0, values=(), lo: int = 0, hi: int = 0) -> bool:

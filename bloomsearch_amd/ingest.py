@@ -122,14 +122,23 @@ class IngestStream:
     to arbitrary sets are handed to the device as they arrive; finish / build see what bsg_ingest_rows would have left.  Lives
     on one device of the context.  Use as a context manager or call close()."""
 
-    def __init__(self, ctx: Context, ingest_id: int, n_sets: int, n_parents: int, tokenizer=None, minmax_fields=None):
+    def __init__(self, ctx: Context, ingest_id: int, n_sets: int, n_parents: int, tokenizer=None, minmax_fields=None, partition_field=None):
         self.ctx, self.id, self.n_sets, self.n_parents, self.tokenizer = ctx, ingest_id, n_sets, n_parents, tokenizer
+        self.partition_field = partition_field    # a keyed stream (bsg_ingest_open_keyed): append_keyed / add_keys / keys
         self.minmax_fields = None if minmax_fields is None else list(minmax_fields)
         self._handed_back = []                # (row, set) of the rows finish_fallback folded: their MinMax contributions, kept for minmax()
 
     @classmethod
     def open(cls, ctx: Context, n_sets: int = 0, parent_of_set=None, n_parents: int = 0, slots_hint=None, flags: int = 0,
-             tokenizer=None, minmax_fields=None) -> "IngestStream":
+             tokenizer=None, minmax_fields=None, partition_field=None) -> "IngestStream":
+        """partition_field: a KEYED stream — no initial sets; parent_of_set is then the ONE parent index of every set the stream creates
+        (None = no parent) and the rows go in through append_keyed."""
+        if partition_field is not None:
+            if n_sets or slots_hint is not None:
+                raise ValueError("a keyed stream starts without sets")
+            parent = 0xFFFFFFFF if parent_of_set is None else int(parent_of_set)
+            return cls(ctx, ctx.ingest_open_keyed(partition_field, n_parents, parent, flags, tokenizer, minmax_fields), 0, n_parents, tokenizer,
+                       minmax_fields, partition_field)
         return cls(ctx, ctx.ingest_open(n_sets, parent_of_set, n_parents, slots_hint, flags, tokenizer, minmax_fields=minmax_fields), n_sets, n_parents,
                    tokenizer, minmax_fields)
 
@@ -152,6 +161,34 @@ class IngestStream:
             if self.minmax_fields is not None:
                 self._handed_back += [(rows[int(r)], int(set_of_row[int(r)])) for r in fb]
         return fb
+
+    def append_keyed(self, rows, finish_fallback: bool = True):
+        """A keyed stream's batch (rows: list of row bytes): the device finds every row's set.  -> (set_of_row, handed-back rows).
+        With finish_fallback the rows the partitioner did not decide (set _lib.SET_UNDECIDED) have been given their sets on the host
+        (host.partition_key, add_keys) — set_of_row then holds them — and every handed-back row has been walked by the host walker."""
+        from . import _lib, host
+        sets, n_new, fb = self.ctx.ingest_append_rows_keyed(self.id, rows)
+        self.n_sets += n_new
+        if finish_fallback and len(fb):
+            und = [int(r) for r in fb if sets[int(r)] == _lib.SET_UNDECIDED]
+            if und:
+                sets[und] = self.add_keys([host.partition_key(rows[r], self.partition_field) for r in und])
+            entries, esets, kinds = host_walk_entries(rows, fb, sets, self.tokenizer)
+            if entries:
+                self.ctx.ingest_add_entries(self.id, entries, esets, kinds)
+            if self.minmax_fields is not None:
+                self._handed_back += [(rows[int(r)], int(sets[int(r)])) for r in fb]
+        return sets, fb
+
+    def add_keys(self, keys) -> np.ndarray:
+        """partition texts found on the host -> their sets (bsg_ingest_add_sets_keyed)"""
+        out = self.ctx.ingest_add_sets_keyed(self.id, keys)
+        self.n_sets = len(self.ctx.ingest_keys(self.id)) if len(out) else self.n_sets
+        return out
+
+    def keys(self, first: int = 0) -> list:
+        """the partition texts of sets [first, n_sets)"""
+        return self.ctx.ingest_keys(self.id, first)
 
     def minmax(self):
         """(min, max, present), each (n_sets, n_fields), over every append so far; the rows append(finish_fallback=True) got back

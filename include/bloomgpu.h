@@ -695,6 +695,66 @@ BSG_API int32_t bsg_ingest_minmax(bsg_ctx *ctx, uint64_t ingest_id, bsg_minmax *
  * the upload chunks; the slowest device of a call cut over several).  bsg_ingest_stats keeps its layout. */
 BSG_API int32_t bsg_last_minmax_ms(bsg_ctx *ctx, float *minmax_ms);
 
+/* ---- keyed streaming ingest: the rows of a batch partitioned ON THE DEVICE by the text of one top-level member ----
+ * bsg_ingest_append_rows wants set_of_row[] from the caller, who must therefore parse every row first.  A keyed ingest is opened
+ * with one partition field (a name of 1 to BSG_PARTITION_MAX_NAME bytes) and finds every row's set itself.
+ * A row's partition text: the FIRST top-level member whose key equals the name byte for byte counts (later members with that key
+ * are ignored; unlike the MinMax fields, where the last wins).  A string value gives the bytes between its quotes, a number its raw
+ * literal exactly as written (1.0, -0 and 1e5 stay what they are: no arithmetic), true and false their four or five bytes; null, an
+ * object, an array or no such member give the empty text.  Equal text is the same partition whatever the JSON type: "5" and 5
+ * share a set, "" and an absent member share a set.
+ * Rows the device does not decide (handed back): the member's value is a string that holds a backslash; the text is longer than
+ * BSG_PARTITION_MAX_KEY bytes; a top-level key that holds a backslash stands before the member, or anywhere in a row without the
+ * member (it could decode to the name).  Every other row is decided.  bsh_partition_key (bloomsearch_host.h) decides every row.
+ * Rows are promised to be valid JSON objects; for another row the result of that row is unspecified (nothing outside the row's
+ * words is read, and no other row's result is touched).
+ * Sets: every set of a keyed ingest has a text.  Sets are numbered by first appearance — the lowest row index — among the rows the
+ * device decided, across the upload chunks of a call and across calls; a text registered from the host (bsg_ingest_add_sets_keyed)
+ * has its number from that moment.  An ingest holds at most BSG_PARTITION_MAX_SETS sets.  A call may meet any number of new texts:
+ * the device collects them BSG_PARTITION_PENDING_SLOTS at a time, the caller sees no limit.
+ * Call order: as the streaming ingest's, with bsg_ingest_append_rows_keyed / bsg_ingest_add_sets_keyed in place of
+ * bsg_ingest_append_rows / bsg_ingest_add_sets (plain bsg_ingest_add_sets on a keyed ingest is BSG_E_INVALID: a set without a text
+ * would break the dictionary; plain bsg_ingest_append_rows keeps working with explicit sets).  finish, build, build_sections, minmax,
+ * stats_read and free are unchanged, and for the same rows in the same sets the filters, counts, statuses and MinMax records are
+ * bit-identical to an ingest fed through bsg_ingest_append_rows. */
+#define BSG_PARTITION_MAX_NAME 64u
+#define BSG_PARTITION_MAX_KEY 128u
+#define BSG_PARTITION_PENDING_SLOTS 256u
+#define BSG_PARTITION_MAX_SETS (1u << 20)
+#define BSG_SET_UNDECIDED 0xFFFFFFFFu
+/* bsg_ingest_open with no initial sets, plus the partition field (name_bytes[name_len]), the parent every set the ingest creates
+ * will have (< n_parents, or 0xFFFFFFFF for none) and, optionally, the MinMax fields of bsg_ingest_open_minmax (n_fields == 0 with
+ * NULL arrays: none).  Before anything is allocated, BSG_E_INVALID with the cause in bsg_last_error: an empty name, a name over
+ * BSG_PARTITION_MAX_NAME bytes, parent_of_new_sets >= n_parents, and what bsg_ingest_open(_minmax) refuses. */
+BSG_API int32_t bsg_ingest_open_keyed(bsg_ctx *ctx, uint32_t n_parents, uint32_t parent_of_new_sets, uint32_t flags,
+                                      const bsg_tokenizer *tok, uint64_t *out_ingest_id, const uint8_t *name_bytes, uint32_t name_len,
+                                      const uint8_t *field_bytes, const uint32_t *field_off, uint32_t n_fields);
+/* bsg_ingest_append_rows without set_of_row.  out_set_of_row[n_rows]: every row's set, or BSG_SET_UNDECIDED for a row the
+ * partitioner handed back; *out_n_new_sets: the sets this call created (the ingest's last ones).  The fallback list is the ascending
+ * union, each row once, of the partitioner's hand-backs, the walker's and the MinMax scanner's; the caller tells the first kind by
+ * BSG_SET_UNDECIDED.  A row handed back by the partitioner has not been walked and has inserted nothing; for it the caller finds
+ * the text on the host (bsh_partition_key), registers it if new (bsg_ingest_add_sets_keyed), walks the row with the host walker
+ * (bsg_ingest_add_entries) and folds its MinMax values on the host — what it does for every fallback row already.
+ * fallback_cap, count-only calls, the statistics, n_rows == 0 and the serialisation of calls on one ingest: as bsg_ingest_append_rows.
+ * Sets created by a call whose list did not fit stay created, and out_set_of_row has been written: appending the batch again
+ * gives the same sets.  The number of new texts is known before any set is created: a call that cannot give them their sets
+ * (BSG_PARTITION_MAX_SETS, an allocation failure) fails and leaves the ingest as it was. */
+BSG_API int32_t bsg_ingest_append_rows_keyed(bsg_ctx *ctx, uint64_t ingest_id, const uint8_t *rows, const uint64_t *row_off,
+                                             uint32_t n_rows, uint32_t *out_set_of_row, uint32_t *out_n_new_sets,
+                                             uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback);
+/* Texts found on the host (n_keys of them, packed like bsg_hash_entries' input, key_off[n_keys + 1]; any length, any bytes):
+ * out_set_of_key[i] = the set of text i — the one it has, or the next new one (equal texts within the call share it).  Later
+ * batches resolve these texts to the same sets on the device. */
+BSG_API int32_t bsg_ingest_add_sets_keyed(bsg_ctx *ctx, uint64_t ingest_id, const uint8_t *key_bytes, const uint32_t *key_off,
+                                          uint32_t n_keys, uint32_t *out_set_of_key);
+/* The texts of sets [first, n_sets), packed like bsg_hash_entries' input: out_off[*out_n_keys + 1].  *out_n_keys and *out_n_bytes
+ * are always written; out_bytes == NULL with out_off == NULL asks for them alone.  Valid until bsg_ingest_free. */
+BSG_API int32_t bsg_ingest_keys(bsg_ctx *ctx, uint64_t ingest_id, uint32_t first, uint8_t *out_bytes, uint64_t bytes_cap,
+                                uint32_t *out_off, uint32_t *out_n_keys, uint64_t *out_n_bytes);
+/* The partition kernels' (k_partition_rows, k_partition_assign) dispatch time in the last bsg_ingest_append_rows_keyed, summed over
+ * its upload chunks and rounds.  bsg_ingest_stats keeps its layout. */
+BSG_API int32_t bsg_last_partition_ms(bsg_ctx *ctx, float *partition_ms);
+
 /* ---- final row test on the device (compileRowMatcher / matchRowBytes, row_matcher.go:257-626) ----
  * One expression over Field / Token / FieldToken conditions, evaluated for every row of the surviving blocks.
  * Condition i: cond_kinds[i] (BSG_KIND_*) and two strings packed like bsg_hash_entries' input — entry 2i = the FIELD

@@ -33,7 +33,10 @@ extern "C" {
  * key 28: workgroups of the gather kernels (k_probe_gather, k_probe_gather_ext, k_gather_fused) per CU, kept there by dynamic LDS the
  * kernels never touch (bsh::gather_lds_pad: floor(160 KiB / n)): 0 = the planner's rule (default: no pad), 1-4 = that many (8 waves
  * each: 2 / 4 / 6 / 8 waves per SIMD), above 4 = no pad; k_gather_fused is launched with the larger of the pad and an evaluation
- * workgroup's LDS, so the cap holds for both of its roles) */
+ * workgroup's LDS, so the cap holds for both of its roles);
+ * key 29: 1 = the hash of the keyed ingest's partition dictionary (partition.hip.h) keeps its low 2 bits only, so nearly every lookup
+ * meets entries with its tag and is decided by the byte compare, and the texts of a batch share four pending slots and are collected
+ * over many rounds; 0 = the whole hash (default).  Results are identical either way.) */
 BSG_API int32_t bsg_set_lab(bsg_ctx *ctx, uint32_t key, uint64_t value);
 /* Synchronous probes poll their stream for up to this long before they block (default 0: block at once).  A single
  * query's kernels finish in ~10 us; being woken from a blocking wait costs more than that. */

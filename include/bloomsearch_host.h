@@ -118,6 +118,14 @@ BSG_API int32_t bsh_prune_query_range(const char *bloom_json, uint64_t bloom_len
  * valid JSON object (nothing is folded). */
 BSG_API int32_t bsh_minmax_row(const uint8_t *row, uint64_t len, const uint8_t *field_bytes, const uint32_t *field_off, uint32_t n_fields,
                                bsg_minmax *inout);
+/* One row's partition text by the rule of the keyed ingest (bloomgpu.h "keyed streaming ingest"; the engine's PartitionField): the
+ * FIRST top-level member whose decoded key equals name[name_len] (1 to BSG_PARTITION_MAX_NAME bytes) gives a string's decoded
+ * bytes, a number's raw literal, "true" or "false"; null, an object, an array or no such member give the empty text.  Exact for
+ * EVERY row, escapes in keys and values decoded: the function the rows a keyed ingest hands back are decided with.  *out_len = the
+ * text's length; its first min(cap, *out_len) bytes are written to out (a text is never longer than its row).  BSH_E_INVALID: an
+ * empty or over-long name, null pointers, or a row that is not one valid JSON object. */
+BSG_API int32_t bsh_partition_key(const uint8_t *row, uint64_t len, const uint8_t *name, uint32_t name_len, uint8_t *out, uint64_t cap,
+                                  uint64_t *out_len);
 /* EvaluateMinMaxCondition (query.go) on a present index: 1 the block may hold a matching value, 0 it cannot.  A bound at an int64
  * extreme is saturated (the true value may lie beyond it): NE, GT, LT and NOT_BETWEEN keep such a block.  NOT_IN is always 1.
  * value: EQ NE GT GE LT LE; values[n_values]: IN; min, max: BETWEEN, NOT_BETWEEN.  BSH_E_INVALID: an absent index, an unknown op. */
@@ -159,7 +167,7 @@ BSG_API uint32_t bsh_crc32c(const uint8_t *data, uint64_t len);
 typedef struct bse_engine bse_engine;
 /* config_json: {"MaxRowGroupRows":..,"MaxRowGroupBytes":..,"MaxBufferedRows":..,"MaxBufferedBytes":..,
  *               "BloomFalsePositiveRate":..,"PartitionField":"..","DeviceIngest":true|false,"DeviceIngestStream":true|false,
- *               "DeviceMatch":true|false,
+ *               "TrustedRows":true|false,"DevicePartition":true|false,"DeviceMatch":true|false,
  *               "DeviceRegex":true|false,"DeviceMatchWide":true|false,"DeviceMatchWideRows":true|false,
  *               "DeviceMatchLookup":true|false,"DeviceMatchLookupRows":true|false,"DeviceMatchLookupRegex":true|false,
  *               "Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false,"Ngram":0|2|3|4},
@@ -171,6 +179,12 @@ typedef struct bse_engine bse_engine;
  *               needs DeviceIngest: BSE_E_INVALID_CONFIG without it): every bse_ingest_rows batch is handed to an open
  *               streaming ingest when it arrives (bsg_ingest_open / _add_sets / _append_rows) and its fallback rows are
  *               finished at once, so a flush only finishes, sizes and builds; merge keeps the one-shot path; same bytes.
+ *               TrustedRows (default false): the caller promises one valid JSON object per row (the reference marshals its own
+ *               rows, ingest.go:379-396); bse_ingest_rows then validates no row for its own sake.  DevicePartition (default
+ *               false; needs DeviceIngestStream, TrustedRows and a non-empty PartitionField of at most 64 bytes:
+ *               BSE_E_INVALID_CONFIG otherwise): every batch goes to a KEYED streaming ingest (bsg_ingest_open_keyed /
+ *               _append_rows_keyed), the device finds each row's partition, and only the rows it hands back are parsed on the
+ *               host (bsh_partition_key's rule); same files, same bytes.
  *               DeviceMatch (default false): the
  *               final row test of the surviving blocks runs on the GPU (bsg_match_rows) instead of in the host matcher;
  *               the delivered row set is the same.  DeviceMatchWide (default false, needs DeviceMatch): bse_query_many packs

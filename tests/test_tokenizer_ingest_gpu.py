@@ -73,7 +73,9 @@ def test_ingest_rows_tok_matches_the_restatement(ctx, name, flags):
     spec = R.SPECS[name]
     rs = row_sets(3)
     res = I.device_ingest(ctx, rs, FPR, parent_of_set=[0] * len(rs), n_parents=1, flags=flags, tokenizer=spec)
-    assert len(res.fallback_rows) >= len(rs)                         # the handed-back rows were finished by the host walker
+    flat = [r for rows in rs for r in rows]                          # exactly FALLBACK_ROWS are handed back (and finished by the host walker):
+    assert [int(i) for i in res.fallback_rows] == [i for i, r in enumerate(flat) if r in FALLBACK_ROWS]      # no other row leaves the device
+    assert len(res.fallback_rows) == 2 * len(rs)
     check_all(res, rs, spec)
 
 

@@ -19,7 +19,7 @@ BSG_OK, BSG_E_INVALID, BSG_E_HIP, BSG_E_NOMEM, BSG_E_NOTFOUND, BSG_E_UNSUPPORTED
 KIND_FIELD, KIND_TOKEN, KIND_FIELD_TOKEN = 0, 1, 2
 KIND_FIELD_REGEX = 3          # row matcher only (bsg_match_rows_regex)
 KIND_SUBSTRING, KIND_FIELD_SUBSTRING = 4, 5      # bsg_match_rows_substr / _many_substr / _regex_substr / _many_regex_substr / _wide_substr(_rows) only
-KIND_FIELD_RANGE = 6          # bsg_match_rows_range / _many_range / _wide_range(_rows) only: entry 2i + 1 = lo, hi (int64 LE) and one RANGE_* flag byte
+KIND_FIELD_RANGE = 6          # bsg_match_rows_range / _many_range / _wide_range(_rows) / _regex_substr_range / _many_regex_substr_range only: entry 2i + 1 = lo, hi (int64 LE) and one RANGE_* flag byte
 RANGE_NO_LO, RANGE_NO_HI, RANGE_LO_OPEN, RANGE_HI_OPEN = 1, 2, 4, 8
 OP_TERM, OP_AND, OP_OR, OP_TRUE, OP_FALSE = 0, 1, 2, 3, 4
 PROBE_ASYNC, PROBE_TIMED, PROBE_NOFUSE, PROBE_ROWS_PACKED = 1, 2, 4, 8
@@ -105,7 +105,7 @@ EXPORTS = [
     "bsg_ingest_rows_minmax", "bsg_ingest_open_minmax", "bsg_ingest_minmax", "bsg_last_minmax_ms",
     "bsg_ingest_open_keyed", "bsg_ingest_append_rows_keyed", "bsg_ingest_add_sets_keyed", "bsg_ingest_keys", "bsg_last_partition_ms",
     "bsg_sections_size", "bsg_build_sections", "bsg_last_encode_ms",
-    "bsg_match_rows", "bsg_match_rows_regex", "bsg_match_rows_tok", "bsg_match_rows_substr", "bsg_match_rows_range", "bsg_match_rows_many_range", "bsg_match_rows_regex_substr", "bsg_match_rows_many", "bsg_match_rows_many_substr", "bsg_match_rows_many_regex_substr", "bsg_match_rows_many_regex", "bsg_match_rows_wide", "bsg_match_wide_size", "bsg_match_rows_wide_rows", "bsg_match_rows_wide_substr", "bsg_match_rows_wide_substr_rows", "bsg_match_rows_wide_range", "bsg_match_rows_wide_range_rows", "bsg_match_pair_rows_list", "bsg_match_rows_lookup", "bsg_match_rows_lookup_rows", "bsg_match_rows_lookup_regex", "bsg_match_rows_lookup_regex_rows", "bsg_last_match_ms", "bsg_pinned_alloc", "bsg_pinned_free", "bsg_host_register", "bsg_host_unregister",
+    "bsg_match_rows", "bsg_match_rows_regex", "bsg_match_rows_tok", "bsg_match_rows_substr", "bsg_match_rows_range", "bsg_match_rows_many_range", "bsg_match_rows_regex_substr", "bsg_match_rows_regex_substr_range", "bsg_match_rows_many_regex_substr_range", "bsg_match_rows_many", "bsg_match_rows_many_substr", "bsg_match_rows_many_regex_substr", "bsg_match_rows_many_regex", "bsg_match_rows_wide", "bsg_match_wide_size", "bsg_match_rows_wide_rows", "bsg_match_rows_wide_substr", "bsg_match_rows_wide_substr_rows", "bsg_match_rows_wide_range", "bsg_match_rows_wide_range_rows", "bsg_match_pair_rows_list", "bsg_match_rows_lookup", "bsg_match_rows_lookup_rows", "bsg_match_rows_lookup_regex", "bsg_match_rows_lookup_regex_rows", "bsg_last_match_ms", "bsg_pinned_alloc", "bsg_pinned_free", "bsg_host_register", "bsg_host_unregister",
 ]
 
 _lib = None
@@ -221,6 +221,8 @@ def load():
     L.bsg_match_rows_range.argtypes = L.bsg_match_rows_tok.argtypes
     L.bsg_match_rows_many_range.argtypes = L.bsg_match_rows_many.argtypes
     L.bsg_match_rows_many_regex_substr.argtypes = L.bsg_match_rows_many.argtypes
+    L.bsg_match_rows_regex_substr_range.argtypes = L.bsg_match_rows_tok.argtypes
+    L.bsg_match_rows_many_regex_substr_range.argtypes = L.bsg_match_rows_many.argtypes
     L.bsg_match_rows_wide.argtypes = [vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, C.POINTER(Tokenizer), vp, vp, u32, C.POINTER(u32)]
     L.bsg_match_wide_size.argtypes = [vp, vp, u32, u32, u32, vp, C.POINTER(u64)]
     L.bsg_match_rows_wide_rows.argtypes = [vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, C.POINTER(Tokenizer), vp, vp, vp, u64,

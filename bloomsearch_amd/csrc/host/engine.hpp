@@ -30,7 +30,7 @@
 #include "regex_groups.hpp"
 #include "section_codec.hpp"
 #include "range.hpp"
-#include "range_groups.hpp"
+#include "range_text_groups.hpp"
 #include "minmax.hpp"
 #include "substring.hpp"
 #include "substring_groups.hpp"
@@ -79,6 +79,18 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // matched bloom AND regex by ONE bsg_match_rows_regex call, and the rows it hands back by the host matcher with the same
     // DFAs (RE2 semantics on both sides); other regex queries keep the std::regex path below.  Off by default.
     bool device_regex = false;
+    // true (with device_match): query() decides a query that has a Range tree beside a Regex and / or a Substring tree by ONE
+    // bsg_match_rows_regex_substr_range call over And(bloom root | TRUE, regex root, substring root, range root).  A regex tree takes
+    // part only under device_regex with every pattern in the device subset; otherwise it is left out of the call (TRUE in its place),
+    // range and substring are still decided in the one call, and the host regex matcher filters the hits (with no substring tree
+    // either there is nothing to put beside the range: the route without the key).  The rows the call hands back are decided by the
+    // host matchers together; BSG_E_UNSUPPORTED from the library means the route without the key, and only that route's calls are
+    // counted.  With no wide or lookup key set, query_many lets range conditions and text conditions share a group, decided by ONE
+    // bsg_match_rows_many_regex_substr_range call (range_text_groups.hpp: the closing rules, and the reduced 34 032-byte cap of the
+    // regex tables as soon as kind 6 sits beside a text condition); under a wide or lookup key groups never mix (range_groups.hpp
+    // joins) and such a query goes to query().  Off by default: every route and every counted entry point is then exactly what it is
+    // without the key.
+    bool device_match_range_text = false;
     // true (with device_match): query_many packs its queries into groups bounded by the condition table alone (64 distinct
     // conditions, 16 regex conditions, the table bytes, co_active_bound) - not by 64 members - and decides each group by ONE
     // bsg_match_rows_wide call, every set's query list read straight from the probe's survivors (a group that holds a substring
@@ -407,11 +419,18 @@ public:
             for (const std::string &row : files_[sb.f].blocks[sb.b].rows) scan.push_back(&row);
         std::vector<uint8_t> hit(scan.size(), 0);
         bool on_device = false, regex_done = false, sub_done = false, range_done = false;
+        bool three_done = false;
+        const RegexExpression *rx_dev = regex_on_device ? regex : nullptr;     // a regex tree takes part only where the device reads its patterns
+        if (cfg_.device_match && cfg_.device_match_range_text && range && (rx_dev || sub) && !scan.empty()) {
+            // one walk decides bloom AND regex AND substring AND range; a regex tree left out of it is the host's, below
+            if (int32_t rc = match_rows_device_range_text(row_expr, rx_dev, sub, *range, scan, matcher, regex_dfa, sub_matcher, range_matcher, hit, three_done)) return rc;
+            if (three_done) { on_device = range_done = true; regex_done = rx_dev != nullptr; sub_done = sub != nullptr; }
+        }
         if (range && !regex && !sub && cfg_.device_match && !scan.empty()) {   // one walk decides bloom AND range
             if (int32_t rc = match_rows_device_range(row_expr, *range, scan, matcher, range_matcher, hit, range_done)) return rc;
             on_device = range_done;
         }
-        if (regex_on_device && sub && !scan.empty()) {      // both trees: one walk decides bloom AND regex AND substring
+        if (regex_on_device && sub && !three_done && !scan.empty()) {      // both trees: one walk decides bloom AND regex AND substring
             bool both_done = false;
             if (int32_t rc = match_rows_device_regex_substr(row_expr, *regex, *sub, scan, matcher, regex_dfa, sub_matcher, hit, both_done)) return rc;
             regex_done = sub_done = both_done;
@@ -421,7 +440,7 @@ public:
             if (!regex_done && !regex_matcher.valid()) return fail(kErrInvalidQuery, "regex pattern does not compile");
         }
         on_device = on_device || regex_done;
-        if (sub && !regex && cfg_.device_match && !scan.empty()) {
+        if (sub && !regex && !three_done && cfg_.device_match && !scan.empty()) {
             if (int32_t rc = match_rows_device_substr(row_expr, *sub, scan, matcher, sub_matcher, hit, sub_done)) return rc;
             on_device = sub_done;
         }
@@ -476,6 +495,10 @@ public:
     // group's call — bsg_match_rows_many_range, or bsg_match_rows_wide_range(_rows) under the wide and the lookup keys
     // (range_groups.hpp: a group never holds a range condition beside a regex or substring one).  A range query with one of the other two
     // trees, every range query without DeviceMatch, and a batched one whose group the device did not decide are answered by query().
+    // Under DeviceMatchRangeText with no wide or lookup key, a range query WITH a regex and / or substring tree stays in the batch (by
+    // the rules above for those trees): it is probed with And(bloom, regex field guard, substring guard, range guard), its program is
+    // And(bloom root | TRUE, its trees), and a group whose table holds kind 6 beside a kind 3-5 condition makes ONE
+    // bsg_match_rows_many_regex_substr_range call (range_text_groups.hpp).
     int32_t query_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
                        std::vector<QueryResult> &results, const std::vector<const SubstringExpression *> *subs = nullptr,
                        const std::vector<const RangeExpression *> *ranges = nullptr, const std::vector<const PrefilterExpression *> *prefilters = nullptr)
@@ -483,6 +506,7 @@ public:
         // every query has its own prefilter mask on its survivors: a block no query of the batch keeps is never walked
         auto prefilter_of = [&](size_t i) { return prefilters && i < prefilters->size() ? (*prefilters)[i] : nullptr; };
         results.assign(exprs.size(), QueryResult{});
+        const bool mix_ok = bsh_rtg::mixing(cfg_.device_match, cfg_.device_match_range_text, any_wide_key());
         std::vector<size_t> live;                   // the batch: queries without a regex tree, and regex queries the device matches
         std::vector<const RegexExpression *> live_regex;
         std::vector<const SubstringExpression *> live_sub;
@@ -494,8 +518,8 @@ public:
             const RegexExpression *rx = i < regexes.size() ? regexes[i] : nullptr;
             const SubstringExpression *sx = subs && i < subs->size() ? (*subs)[i] : nullptr;
             const RangeExpression *rg = ranges && i < ranges->size() ? (*ranges)[i] : nullptr;
-            // a range tree beside a regex or substring tree (no walker takes both), or without DeviceMatch: query()
-            if (rg && (rx || sx || !cfg_.device_match)) {
+            // a range tree without DeviceMatch, or beside a regex or substring tree where the two families share no group: query()
+            if (rg && (!cfg_.device_match || ((rx || sx) && !mix_ok))) {
                 if (int32_t rc = query(exprs[i], results[i], rx, sx, rg, prefilter_of(i))) return rc;
                 continue;
             }
@@ -509,7 +533,7 @@ public:
                 dfa = std::make_unique<RegexRowMatcher>(rx, true);
                 if (!dfa->valid()) dfa.reset();
             }
-            if ((sx && !sub_matcher) || (rx && !dfa)) { if (int32_t rc = query(exprs[i], results[i], rx, sx, nullptr, prefilter_of(i))) return rc; continue; }
+            if ((sx && !sub_matcher) || (rx && !dfa)) { if (int32_t rc = query(exprs[i], results[i], rx, sx, rg, prefilter_of(i))) return rc; continue; }
             live.push_back(i);
             live_regex.push_back(rx);
             live_sub.push_back(sx);
@@ -525,21 +549,16 @@ public:
         for (size_t k = 0; k < live.size(); ++k) {
             batch.push_back(exprs[live[k]]);
             // pruneBloomQuery = AndBloomQueries(bloom, RegexFieldGuardBloomQuery(regex)), as query(); a plain query keeps its pointer
-            if (live_range[k]) {                    // And(bloom, range guard): a range query has neither of the other two trees
-                BloomExpression range_guard_storage;
-                const bool has_range_guard = range_guard(live_range[k], range_guard_storage);
-                prune_storage.push_back(std::make_unique<BloomExpression>());
-                prune.push_back(and_bloom_queries(batch[k], has_range_guard ? &range_guard_storage : nullptr, *prune_storage.back()) ? prune_storage.back().get() : nullptr);
-                continue;
-            }
-            if (!live_regex[k] && !live_sub[k]) { prune.push_back(batch[k]); continue; }
-            BloomExpression guard, sub_guard, two;
+            if (!live_regex[k] && !live_sub[k] && !live_range[k]) { prune.push_back(batch[k]); continue; }
+            BloomExpression guard, sub_guard, range_guard_storage, two, three;
             const bool has_guard = regex_field_guard(live_regex[k], guard);
             const bool has_two = and_bloom_queries(batch[k], has_guard ? &guard : nullptr, two);
-            // ... and the substring guard as its third side
+            // ... the substring guard as its third side, the range guard as its fourth
             const bool has_sub_guard = substring_guard(live_sub[k], cfg_.tokenizer, sub_guard);
+            const bool has_three = and_bloom_queries(has_two ? &two : nullptr, has_sub_guard ? &sub_guard : nullptr, three);
+            const bool has_range_guard = range_guard(live_range[k], range_guard_storage);
             prune_storage.push_back(std::make_unique<BloomExpression>());
-            prune.push_back(and_bloom_queries(has_two ? &two : nullptr, has_sub_guard ? &sub_guard : nullptr, *prune_storage.back()) ? prune_storage.back().get() : nullptr);
+            prune.push_back(and_bloom_queries(has_three ? &three : nullptr, has_range_guard ? &range_guard_storage : nullptr, *prune_storage.back()) ? prune_storage.back().get() : nullptr);
         }
         std::vector<Survivors> sv;
         if (int32_t rc = probe_stage(prune, sv)) return rc;
@@ -600,6 +619,11 @@ public:
     }
 
 private:
+    // any of the keys under which query_many's groups take the wide or the lookup calls: range and text conditions never share those
+    bool any_wide_key() const
+    {
+        return cfg_.device_match_wide || cfg_.device_match_wide_rows || cfg_.device_match_lookup || cfg_.device_match_lookup_rows;
+    }
     void count_match_call(const char *entry_point)
     {
         std::lock_guard<std::mutex> lk(match_calls_mu_);
@@ -1354,6 +1378,7 @@ private:
         const bool lookup_rows = cfg_.device_match_lookup_rows, lookup = cfg_.device_match_lookup || lookup_rows;
         const bool wide_rows = cfg_.device_match_wide_rows || lookup_rows, wide = cfg_.device_match_wide || wide_rows || lookup;
         const bool lookup_regex = lookup && cfg_.device_match_lookup_regex;
+        const bool mix_ok = bsh_rtg::mixing(cfg_.device_match, cfg_.device_match_range_text, wide);   // range and text conditions may share a group
         const size_t max_members = wide ? bsh_wide::kMaxQueries : 64;
         const uint32_t table_cap = wide ? bsh_wide::kWideLdsCap : bsh_rxg::kManyLdsCap;
         std::map<std::string, std::pair<uint32_t, uint32_t>> dfa_size;      // pattern -> (states, classes); (0, 0): outside the subset
@@ -1380,15 +1405,12 @@ private:
             bsh_rngg::Mix mix;                                               // whether its table holds a range / a regex or substring condition
             for (; k < exprs.size() && members.size() < max_members; ++k) {
                 MatcherProgram mp(exprs[k]);
-                if (ranges[k]) {
-                    if (!exprs[k] || mp.prog_ops.empty()) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
-                    emit_range_program(*ranges[k], mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
-                    mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 2));
-                } else if (regexes[k] || subs[k]) {
+                if (regexes[k] || subs[k] || ranges[k]) {   // And(bloom root | TRUE, the trees the query has); a range tree beside the others only under mix_ok
                     if (!exprs[k] || mp.prog_ops.empty()) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
                     if (regexes[k]) lower_regex(*regexes[k], mp);
                     if (subs[k]) emit_substring_program(*subs[k], mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
-                    mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 1u + (regexes[k] ? 1u : 0u) + (subs[k] ? 1u : 0u)));
+                    if (ranges[k]) emit_range_program(*ranges[k], mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
+                    mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 1u + (regexes[k] ? 1u : 0u) + (subs[k] ? 1u : 0u) + (ranges[k] ? 1u : 0u)));
                 }
                 // what the query adds: distinct conditions, regex conditions, table bytes, and the fields that may meet on a leaf
                 std::map<std::tuple<uint32_t, std::string, std::string>, uint32_t> added;
@@ -1417,8 +1439,10 @@ private:
                 const size_t cond_cap = bsh_rngg::lookup_group(lookup, lookup_regex, range_group, rx_group, needle_group) ? bsh_lookup::kMaxConds : 64;
                 // the lookup regex call's cap depends on the table: what this group's strings and pairs can take at most
                 const uint32_t group_cap = lookup_regex && rx_group && !needle_group ? bsh_lookup::rx_lds_cap_of(2u * (n_plain + fresh_plain), n_ft + fresh_ft) : table_cap;
-                const bool fits = bsh_rngg::joins(mix, query_mix) && mp.kinds.size() <= cond_cap && index.size() + added.size() <= cond_cap && n_rx + fresh_rx <= bsh_rxg::kMaxRegexConds &&
-                                  bsh_rxg::align4(rx_table + fresh_bytes) <= group_cap &&
+                // a table with kind 6 beside a text condition: the reduced cap beside a needle table, needle or not (range_text_groups.hpp)
+                const uint32_t rx_cap = bsh_rtg::regex_table_cap(bsh_rtg::with(mix, query_mix), wide, false, group_cap);
+                const bool fits = bsh_rtg::joins(mix_ok, mix, query_mix) && mp.kinds.size() <= cond_cap && index.size() + added.size() <= cond_cap && n_rx + fresh_rx <= bsh_rxg::kMaxRegexConds &&
+                                  bsh_rxg::align4(rx_table + fresh_bytes) <= rx_cap &&
                                   bsh_rxg::co_active_bound(rx_fields) <= bsh_rxg::kManySlots &&
                                   (!needle_group || bsh_subg::fits(sub_group, fresh_sub, wide));   // the needles pack, the tables fit beside them
                 if (!fits) {
@@ -1447,7 +1471,8 @@ private:
             if (members.empty()) continue;
             const bsh_subg::Call call = bsh_subg::group_call(n_rx != 0, sub_group.n_needles != 0, wide, wide_rows);
             const bool by_sub = sub_group.n_needles != 0, by_range = mix.range;
-            const char *call_name = bsh_rngg::group_call_name(by_range, n_rx != 0, by_sub, wide, wide_rows);   // (of a group no lookup call decides)
+            const bool by_mixed = bsh_rtg::mixed(mix);           // kind 6 beside a text condition: only where mix_ok, so never under a wide key
+            const char *call_name = bsh_rtg::group_call_name(mix, n_rx != 0, by_sub, wide, wide_rows);   // (of a group no lookup call decides)
             // a row the device handed back: the host matchers of query m together
             auto host_verdict = [&](size_t m, const std::string &row) {
                 return host_matchers[m].match(row) && (!host_regex[m] || host_regex[m]->match(row)) && (!host_sub[m] || host_sub[m]->match(row)) &&
@@ -1533,7 +1558,7 @@ private:
             std::vector<uint32_t> fb(scan.size());
             uint32_t n_fb = 0;
             count_match_call(call_name);
-            const int32_t rc = (by_range ? bsg_match_rows_many_range : call == bsh_subg::Call::ManyRegexSubstr ? bsg_match_rows_many_regex_substr : call == bsh_subg::Call::ManySubstr ? bsg_match_rows_many_substr :
+            const int32_t rc = (by_mixed ? bsg_match_rows_many_regex_substr_range : by_range ? bsg_match_rows_many_range : call == bsh_subg::Call::ManyRegexSubstr ? bsg_match_rows_many_regex_substr : call == bsh_subg::Call::ManySubstr ? bsg_match_rows_many_substr :
                                 n_rx ? bsg_match_rows_many_regex : bsg_match_rows_many)(
                 ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(), (uint32_t)kinds.size(),
                 prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(), masks.data(), (uint32_t)n_sets, &tok, bits.data(),
@@ -1694,6 +1719,48 @@ private:
         for (uint32_t i = 0; i < n_fb; ++i) {
             const std::string &row = *scan[fb[i]];
             hit[fb[i]] = host_matcher.match(row) && host_regex.match(row) && sub_matcher.match(row);
+        }
+        done = true;
+        return kEngineOk;
+    }
+
+    // And(bloom root | TRUE, regex root | TRUE, substring root | TRUE, range root) over the scan list in one
+    // bsg_match_rows_regex_substr_range call (device_match_range_text); the rows it hands back are decided by the four host matchers
+    // (the regex one DFA-backed, as the device read the patterns).  done stays false beyond 64 conditions or what the call holds.
+    int32_t match_rows_device_range_text(const BloomExpression *expr, const RegexExpression *regex, const SubstringExpression *sub, const RangeExpression &range,
+                                         const std::vector<const std::string *> &scan, RowMatcher &host_matcher, RegexRowMatcher &host_regex,
+                                         SubstringRowMatcher &sub_matcher, RangeRowMatcher &range_matcher, std::vector<uint8_t> &hit, bool &done)
+    {
+        MatcherProgram mp(expr);
+        if (mp.prog_ops.empty()) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
+        if (regex) lower_regex(*regex, mp); else mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
+        if (sub) emit_substring_program(*sub, mp.kinds, mp.fields, mp.tokens, mp.prog_ops); else mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
+        emit_range_program(range, mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
+        mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 4));
+        if (mp.kinds.size() > 64) return kEngineOk;
+        std::vector<uint8_t> cbytes;
+        std::vector<uint32_t> coff{0};
+        for (size_t c = 0; c < mp.kinds.size(); ++c) {
+            cbytes.insert(cbytes.end(), mp.fields[c].begin(), mp.fields[c].end()); coff.push_back((uint32_t)cbytes.size());
+            cbytes.insert(cbytes.end(), mp.tokens[c].begin(), mp.tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
+        }
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> row_off{0};
+        for (const std::string *r : scan) { bytes.insert(bytes.end(), r->begin(), r->end()); row_off.push_back(bytes.size()); }
+        std::vector<uint64_t> bits((scan.size() + 63) / 64);
+        std::vector<uint32_t> fb(scan.size());
+        uint32_t n_fb = 0;
+        const bsg_tokenizer tok = c_tokenizer();
+        const int32_t rc = bsg_match_rows_regex_substr_range(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(),
+                                                             (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok, bits.data(),
+                                                             fb.data(), (uint32_t)fb.size(), &n_fb);
+        if (rc == BSG_E_UNSUPPORTED) return kEngineOk;      // the route without the key decides, and only its calls are counted
+        count_match_call("bsg_match_rows_regex_substr_range");
+        if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
+        for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
+        for (uint32_t i = 0; i < n_fb; ++i) {
+            const std::string &row = *scan[fb[i]];
+            hit[fb[i]] = host_matcher.match(row) && (!regex || host_regex.match(row)) && (!sub || sub_matcher.match(row)) && range_matcher.match(row);
         }
         done = true;
         return kEngineOk;

@@ -90,6 +90,12 @@
 // (the set's condition mask, the gate of the regex header loop), so an exponent literal hands a row back only if such a condition sits
 // on its leaf; the batched walker asks ANY condition of the table.  The flag of a range condition none of the set's queries references
 // is unspecified (nothing reads it).
+//
+// Range conditions beside the text consumers (kinds 0-6, k_match_rows_regex_substr_range* / k_match_rows_many_regex_substr_range* = REGEX, SUB
+// and RANGE): RxSubNumFeed hands every byte of a number literal to the DFAs, the needles and NumLane, a string's bytes to the first two.
+// Every statement the three flags guard runs as in the parents; a row is a fallback row by the union of their rules.  In the batched
+// instances a DFA opens only for a row whose set mask selects a user of the condition, needles are ungated, and an exponent literal on
+// the field of ANY range condition of the table hands the row back.  No LDS beyond the regex_substr instances', two workgroups per CU.
 #pragma once
 #include <type_traits>
 #include "ingest.hip.h"
@@ -369,6 +375,35 @@ struct NumLane {
     }
 };
 
+// All three consumers in one walk (k_match_rows_regex_substr_range* / k_match_rows_many_regex_substr_range*): as RxSubFeed, this one only
+// refers to the lanes (it neither derives from them nor holds one by value: the 304 bytes of scratch above).  A number literal arrives
+// byte by byte through feed() and is candidate text of the DFAs and the needles AND the digits NumLane parses; runs and runes come from
+// strings only, which no range condition reads.
+template <uint32_t SLOTS>
+struct RxSubNumFeed {
+    RxLaneT<SLOTS> &rx;
+    SubLane &sub;
+    NumLane &num;
+    // A leaf without a path raises no request, so nothing closes the DFAs the leaf before it left open: they must not read its bytes
+    // (SubLane and NumLane look at Walker::quiet themselves).
+    __device__ __forceinline__ void feed(uint32_t b)
+    {
+        if (!num.wk->quiet) rx.feed(b);
+        sub.feed(b);
+        num.feed(b);
+    }
+    __device__ __forceinline__ void feed_run(uint64_t v, uint32_t n)
+    {
+        const bool heard = !num.wk->quiet;
+        for (uint32_t i = 0; i < n; ++i) { const uint32_t b = c_at(v, i); if (heard) rx.feed(b); sub.feed(b); }
+    }
+    __device__ __forceinline__ void feed_rune(uint32_t r)
+    {
+        if (!num.wk->quiet) rx.feed_rune(r);
+        sub.feed_rune(r);
+    }
+};
+
 // The number parsed on the leaf that just ended (pending: this lane has one), against every range condition that listened on it.
 __device__ __forceinline__ void decide_number(const NumLane &nl, bool pending, const lds_u64i *conds, uint32_t n_conds, uint64_t leaf_mask, uint64_t &sat,
                                               bool &num_fail)
@@ -399,7 +434,11 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
                                                 const MatchWideArgs &wd = MatchWideArgs{}, const SubArgs &sb = SubArgs{})
 {
     static_assert(!(MANY && WIDE), "the storing walker evaluates no program");
-    static_assert(!(RANGE && (REGEX || SUB)), "range conditions: the plain single, batched and storing walkers only");
+    if constexpr (REGEX && SUB) {      // both text consumers: the number consumer may join them, in the single and the batched walkers
+        static_assert(!(RANGE && WIDE), "range conditions beside the text consumers: the single and the batched walkers only");
+    } else {                           // ... and never beside exactly one of the two
+        static_assert(!(RANGE && (REGEX || SUB)), "range conditions: beside no text consumer, or beside both");
+    }
     constexpr uint32_t kSubBase = WIDE ? kMatchWideLdsBytes : MANY ? kMatchManySubBase : kMatchLdsBytes;   // the needle table sits behind the instance's own LDS
     constexpr uint32_t kProgBytes = WIDE ? 0u : MANY ? kMatchManyProgBytes : kMatchMaxOps * 4;
     constexpr uint32_t kRxBase = SUB ? kSubBase + kSubTableBytes : WIDE ? kMatchWideLdsBytes : MANY ? kMatchManyLdsBytes : kMatchLdsBytes;   // the regex blob sits behind the instance's own LDS (and the needle table)
@@ -471,7 +510,8 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
     while (__ballot(res == R_CONTINUE || w.req != Q_NONE) != 0ull) {
         while (__ballot(res == R_CONTINUE && w.req == Q_NONE) != 0ull)
             if (res == R_CONTINUE && w.req == Q_NONE) {
-                if constexpr (REGEX && SUB) { RxSubFeed<SLOTS> both{rx, sl}; res = advance<true>(w, cc, both, tk); }
+                if constexpr (REGEX && SUB && RANGE) { RxSubNumFeed<SLOTS> all{rx, sl, nl}; res = advance<true>(w, cc, all, tk); }
+                else if constexpr (REGEX && SUB) { RxSubFeed<SLOTS> both{rx, sl}; res = advance<true>(w, cc, both, tk); }
                 else if constexpr (SUB) res = advance<true>(w, cc, sl, tk);
                 else if constexpr (RANGE) res = advance<true>(w, cc, nl, tk);
                 else res = advance<true>(w, cc, rx, tk);
@@ -590,6 +630,7 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
     if constexpr (SUB) {
         for (uint32_t c = 0; c < a.n_conds; ++c) {                       // uniform loop
             const uint32_t rec = (uint32_t)conds[c * kMatchCondWords + 10];
+            if (RANGE && (rec & 0xFFu) == 6u) continue;                  // a range condition's record holds flags where a needle's place is
             if ((rec & 0xFFu) >= 4u && ((((rec >> 8) & 1u) ? sl.h1 : sl.h0) >> ((rec >> 16) & 63u)) & 1ULL) sat |= 1ULL << c;
         }
         if (sl.fail && res == R_DONE) res = R_FAIL;                      // a rune the lower table cannot decide: the host's ToLower does
@@ -773,6 +814,38 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_range_tok(co
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_range_gram(const MatchArgs a, const MatchManyArgs m, const TokSpec t)
 {
     match_rows_body<false, TokGramP, true, kRxActive, false, false, true>(a, RxArgs{}, TokGramP(t), m);
+}
+
+// Kinds 0-6 in one table (bsg_match_rows_regex_substr_range / bsg_match_rows_many_regex_substr_range): the DFAs, the needles and the number
+// parser fed by one walk.  NumLane adds no LDS, so the bytes and the blob caps are the regex_substr instances': dynamic LDS
+// kMatchSubLdsBytes / kMatchManySubLdsBytes + the table blob (<= kRxSubLdsCap / kRxManySubLdsCap).  One family serves every mix of the
+// three sides beside a range condition: a table without a needle brings an all-zero needle table (start = any = 0), one without a regex
+// condition n_rx = n_words = 0.
+static_assert(2u * (kMatchSubLdsBytes + kRxSubLdsCap) <= 160u * 1024u && 2u * (kMatchManySubLdsBytes + kRxManySubLdsCap) <= 160u * 1024u,
+              "k_match_rows_regex_substr_range and k_match_rows_many_regex_substr_range keep two workgroups per CU as their regex_substr siblings");
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_regex_substr_range(const MatchArgs a, const RxArgs x, const SubArgs sb)
+{
+    match_rows_body<true, TokDefault, false, kRxActive, false, true, true>(a, x, TokDefault{}, MatchManyArgs{}, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_regex_substr_range_tok(const MatchArgs a, const RxArgs x, const SubArgs sb, const TokSpec t)
+{
+    match_rows_body<true, TokSpecP, false, kRxActive, false, true, true>(a, x, TokSpecP{t}, MatchManyArgs{}, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_regex_substr_range_gram(const MatchArgs a, const RxArgs x, const SubArgs sb, const TokSpec t)
+{
+    match_rows_body<true, TokGramP, false, kRxActive, false, true, true>(a, x, TokGramP(t), MatchManyArgs{}, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_substr_range(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchManyArgs m)
+{
+    match_rows_body<true, TokDefault, true, kRxManyActive, false, true, true>(a, x, TokDefault{}, m, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_substr_range_tok(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchManyArgs m, const TokSpec t)
+{
+    match_rows_body<true, TokSpecP, true, kRxManyActive, false, true, true>(a, x, TokSpecP{t}, m, MatchWideArgs{}, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_many_regex_substr_range_gram(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchManyArgs m, const TokSpec t)
+{
+    match_rows_body<true, TokGramP, true, kRxManyActive, false, true, true>(a, x, TokGramP(t), m, MatchWideArgs{}, sb);
 }
 
 // the storing walker (bsg_match_rows_wide): plain / regex x default / spec / n-gram tokenizer; dynamic LDS kMatchWideLdsBytes (+ the table

@@ -22,6 +22,11 @@
 // table without a range condition is bsg_match_rows_tok's / bsg_match_rows_many's: its walkers and its bits.
 // bsg_match_rows_wide_range(_rows) is the wide call with kinds 0, 1, 2 and 6 in its table: build_range_table and the bounds copy as above,
 // and WidePart launches k_match_rows_store_range*; a table without a range condition is bsg_match_rows_wide(_rows)'s walkers and bits.
+// bsg_match_rows_regex_substr_range / bsg_match_rows_many_regex_substr_range take kinds 0-6 in one table.  A table without a range condition is
+// bsg_match_rows_regex_substr's / _many_regex_substr's (walkers, caps and bits), one with range conditions and no kind 3-5 is
+// bsg_match_rows_range's / _many_range's; any other table gets the blob (under kRxSubLdsCap / kRxManySubLdsCap whether or not it holds a
+// needle: the needle table is always there), the needle tables (all zero without a needle) AND the range table, chained in that order
+// (each rewrites cond_kinds from the current pointer), and PlanePart launches k_match_rows_regex_substr_range* / k_match_rows_many_regex_substr_range*.
 // bsg_match_rows_lookup(_rows) is the wide call with another Family and a LookupPlan beside its WidePlan: WidePart then sizes the
 // flags at W words per row, places the lookup tables (host/lookup_plan.hpp) from the hashes the device made, and launches
 // match_lookup.hip.h's walker and evaluator in place of match.hip.h's.  bsg_match_rows_lookup_regex(_rows) is that call with FieldRegex
@@ -106,6 +111,8 @@ struct MatchCall {
     std::vector<uint32_t> sub_kinds;       // ... and cond_kinds with word | end bit of a substring condition's needle (match.hip.h SubLane)
     bool range_call = false;               // the call is bsg_match_rows_range / bsg_match_rows_many_range (the name in traces)
     bool wide_range = false;               // the call is bsg_match_rows_wide_range(_rows) (the name in traces)
+    bool range_text = false;               // the call is bsg_match_rows_regex_substr_range / bsg_match_rows_many_regex_substr_range (the name in traces)
+    bool three = false;                    // ... and its table holds a FieldRange condition beside a regex or substring one: the three-consumer walkers run
     bool range = false;                    // build_range_table: the table holds a FieldRange condition, the range walkers run
     std::vector<uint32_t> range_conds;     // ... the conditions of kind 6,
     std::vector<uint64_t> range_bounds;    // ... lo and hi of each (two's complement), in that order
@@ -353,6 +360,7 @@ struct PlanePart {
 
     const char *tag() const
     {
+        if (mc.range_text) return many ? "bsg_match_rows_many_regex_substr_range" : "bsg_match_rows_regex_substr_range";
         if (mc.range_call) return many ? "bsg_match_rows_many_range" : "bsg_match_rows_range";
         if (mc.rx_sub) return many ? "bsg_match_rows_many_regex_substr" : "bsg_match_rows_regex_substr";
         if (mc.substr) return many ? "bsg_match_rows_many_substr" : "bsg_match_rows_substr";
@@ -389,6 +397,15 @@ struct PlanePart {
     void launch(PartDev &p, bsg::MatchArgs &a, uint32_t rf, hipEvent_t k0, hipEvent_t k1)
     {
         a.prog = p.d_prog; a.n_ops = (uint32_t)mc.prog.size(); a.out_bits = d_bits + rf / 64;
+        if (mc.three) {                                // all three consumers: the regex_substr instances' LDS, whatever sides the table holds
+            assert(mc.substr && mc.range && p.sub.table && p.rx.n_words * 4 <= (many ? bsg::kRxManySubLdsCap : bsg::kRxSubLdsCap));
+            if (many) launch_rx_sub_walker(bsg::k_match_rows_many_regex_substr_range, bsg::k_match_rows_many_regex_substr_range_tok, bsg::k_match_rows_many_regex_substr_range_gram,
+                                           bsg::kMatchManySubLdsBytes, p.d.stream, k0, k1, a, p.rx, p.sub, mc.tok(),
+                                           bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
+            else launch_rx_sub_walker(bsg::k_match_rows_regex_substr_range, bsg::k_match_rows_regex_substr_range_tok, bsg::k_match_rows_regex_substr_range_gram,
+                                      bsg::kMatchSubLdsBytes, p.d.stream, k0, k1, a, p.rx, p.sub, mc.tok());
+            return;
+        }
         if (mc.substr && mc.n_rx) {                    // both consumers: the blob behind the needle table
             assert(p.rx.n_words * 4 <= (many ? bsg::kRxManySubLdsCap : bsg::kRxSubLdsCap));
             if (many) launch_rx_sub_walker(bsg::k_match_rows_many_regex_substr, bsg::k_match_rows_many_regex_substr_tok, bsg::k_match_rows_many_regex_substr_gram,
@@ -711,6 +728,10 @@ int32_t match_part(bsg_ctx *ctx, Device &d, const MatchCall &mc, uint32_t r0, ui
         p.sub = bsg::SubArgs{d_sub, {mc.sub.start[0], mc.sub.start[1]}, {mc.sub.any[0], mc.sub.any[1]}};
     }
     p.d_ch = d_ch;
+    // the three-consumer walkers copy the needle table and n_words of blob whatever the table holds: a table without a needle brings
+    // its all-zero table, one without a regex condition no blob word at all
+    if (mc.three && (!mc.substr || !p.sub.table || (mc.n_rx == 0) != (p.rx.n_words == 0) || (p.rx.n_words != 0 && !p.rx.blob)))
+        return fail(BSG_E_HIP, "%s: the needle table or the regex blob is not on the device", mode.tag());
     if (int32_t rc = mode.upload(p)) return rc;
     // The rows travel in chunks while the chunk before is being matched (RowUpload).  A surviving block is <= 10 MiB and goes in
     // one piece, in order on the one stream; a scan of many blocks in one call goes in pieces on the copy stream.
@@ -793,6 +814,30 @@ constexpr const char *kNoTextWithRange = "condition %u: kind %u (the range calls
 inline bool range_refuses(uint32_t kind) { return kind >= BSG_KIND_FIELD_REGEX && kind <= BSG_KIND_FIELD_SUBSTRING; }
 constexpr const char *kNoRegexWithSubstr = "condition %u: a FieldRegex condition (regex and substring conditions share bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr)";
 
+// bsg_match_rows_regex_substr_range / bsg_match_rows_many_regex_substr_range: kinds 0-6.  The table decides the path: no range condition is
+// the regex_substr call's, range conditions without a kind 3-5 the range call's, anything else the three-consumer walkers'.
+int32_t route_range_text(MatchCall &mc)
+{
+    if (!mc.range_text) return BSG_OK;
+    bool has_range = false, has_text = false;
+    for (uint32_t c = 0; c < mc.n_conds; ++c) {
+        if (mc.cond_kinds[c] > BSG_KIND_FIELD_RANGE) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
+        has_range |= mc.cond_kinds[c] == BSG_KIND_FIELD_RANGE;
+        has_text |= range_refuses(mc.cond_kinds[c]);
+    }
+    if (!has_range) mc.rx_sub = true;
+    else if (!has_text) mc.range_call = true;
+    else mc.three = true;
+    return BSG_OK;
+}
+// ... the three tables of the last: the blob under the cap beside a needle table (there always is one), the needle tables, the bounds
+int32_t build_three_tables(MatchCall &mc, uint32_t cap, const uint64_t *users)
+{
+    if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, cap, users)) return rc;
+    if (int32_t rc = build_sub_tables(mc)) return rc;
+    return build_range_table(mc);
+}
+
 // which sides a table of bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr holds
 struct TableSides { bool regex = false, sub = false; };
 TableSides table_sides(const MatchCall &mc)
@@ -823,13 +868,15 @@ int32_t match_rows_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, u
 {
     const uint32_t prog_off[2] = {0, n_ops};
     if (int32_t rc = begin_match_call(mc, kSingleFamily, tok_in, prog_ops, prog_off, 1)) return rc;
+    if (int32_t rc = route_range_text(mc)) return rc;
     for (uint32_t c = 0; c < mc.n_conds; ++c) {
         if (substr && mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX) return fail(BSG_E_UNSUPPORTED, kNoRegexWithSubstr, c);
         if (mc.range_call && range_refuses(mc.cond_kinds[c])) return fail(BSG_E_UNSUPPORTED, kNoTextWithRange, c, mc.cond_kinds[c]);
         if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
     }
     if (int32_t rc = lower_programs(mc, kSingleFamily, prog_ops, prog_off, 1)) return rc;
-    if (mc.range_call) { if (int32_t rc = build_range_table(mc)) return rc; }
+    if (mc.three) { if (int32_t rc = build_three_tables(mc, bsg::kRxSubLdsCap, nullptr)) return rc; }
+    else if (mc.range_call) { if (int32_t rc = build_range_table(mc)) return rc; }
     else if (mc.rx_sub) {
         const TableSides t = table_sides(mc);
         if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, t.sub ? bsg::kRxSubLdsCap : bsg::kRxLdsCap)) return rc;
@@ -848,6 +895,7 @@ int32_t match_rows_many_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
                              uint32_t max_kind, bool substr = false)
 {
     if (int32_t rc = begin_match_call(mc, kManyFamily, tok_in, prog_ops, prog_off, n_queries)) return rc;
+    if (int32_t rc = route_range_text(mc)) return rc;
     const uint32_t n_rows = mc.n_rows;
     for (uint32_t c = 0; c < mc.n_conds; ++c) {
         if (substr && mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX) return fail(BSG_E_UNSUPPORTED, kNoRegexWithSubstr, c);
@@ -869,7 +917,11 @@ int32_t match_rows_many_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
     const ManyPlan plan{set_first_row, query_mask_of_set, n_sets, n_queries, ((size_t)n_rows + 63) / 64};
     if (int32_t rc = lower_programs(mc, kManyFamily, prog_ops, prog_off, n_queries)) return rc;
     // the regex conditions' tables, each with the queries that use it (a table without any: exactly bsg_match_rows_many's kernels)
-    if (mc.range_call) { if (int32_t rc = build_range_table(mc)) return rc; }
+    if (mc.three) {
+        const std::vector<uint64_t> users = n_queries ? bsh_rxg::user_masks(prog_ops, prog_off, n_queries, mc.n_conds) : std::vector<uint64_t>(mc.n_conds, 0);
+        if (int32_t rc = build_three_tables(mc, bsg::kRxManySubLdsCap, users.data())) return rc;
+    }
+    else if (mc.range_call) { if (int32_t rc = build_range_table(mc)) return rc; }
     else if (mc.rx_sub) {
         const TableSides t = table_sides(mc);
         if (n_queries) {
@@ -1285,6 +1337,29 @@ int32_t bsg_match_rows_many_regex_substr(bsg_ctx *ctx, const uint8_t *rows, cons
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
     mc.rx_sub = true;
     return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_SUBSTRING);
+}
+
+int32_t bsg_match_rows_regex_substr_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                          const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                          const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
+                                          uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    mc.range_text = true;
+    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_RANGE, tok);
+}
+
+int32_t bsg_match_rows_many_regex_substr_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                               const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                               const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                               const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets, const bsg_tokenizer *tok,
+                                               uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    mc.range_text = true;
+    return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_RANGE);
 }
 
 int32_t bsg_match_rows_many(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,

@@ -766,6 +766,11 @@ class Context:
         conditions in the same table: one walk of the rows decides both kinds."""
         return self._match_rows(None, rows, matcher, tokenizer, tok_fn=self.L.bsg_match_rows_regex_substr)
 
+    def match_rows_regex_substr_range(self, rows, matcher, tokenizer=None):
+        """bsg_match_rows_regex_substr_range: as match_rows_regex_substr, and the matcher (query.CompiledRowTextRangeQuery) may hold
+        FieldRange conditions in the same table: one walk of the rows decides range, regex and substring conditions."""
+        return self._match_rows(None, rows, matcher, tokenizer, tok_fn=self.L.bsg_match_rows_regex_substr_range)
+
     def _match_rows(self, fn, rows, matcher, tokenizer=None, tok_fn=None):
         if isinstance(rows, tuple):
             blob = np.ascontiguousarray(rows[0], dtype=np.uint8)
@@ -816,6 +821,11 @@ class Context:
         """bsg_match_rows_many_regex_substr: as match_rows_many, and the batch (query.CompiledRowSubstringQueryBatch) may hold FieldRegex,
         Substring and FieldSubstring conditions in one table."""
         return self._match_rows_many(self.L.bsg_match_rows_many_regex_substr, rows, batch, set_first_row, masks, tokenizer)
+
+    def match_rows_many_regex_substr_range(self, rows, batch, set_first_row=None, masks=None, tokenizer=None):
+        """bsg_match_rows_many_regex_substr_range: as match_rows_many, and the batch (query.CompiledRowTextRangeQueryBatch) may hold
+        FieldRegex, Substring, FieldSubstring and FieldRange conditions in one table."""
+        return self._match_rows_many(self.L.bsg_match_rows_many_regex_substr_range, rows, batch, set_first_row, masks, tokenizer)
 
     def _match_rows_many(self, fn, rows, batch, set_first_row, masks, tokenizer):
         if isinstance(rows, tuple):

@@ -658,6 +658,34 @@ class CompiledRowSubstringQueryBatch(CompiledMatcherBatch):
         return CompiledRowSubstringQuery(*triple)
 
 
+class CompiledRowTextRangeQuery(CompiledRowQuery, CompiledSubstringQuery, CompiledRangeQuery):
+    """And(bloom root | TRUE, regex root, substring root, range root) for bsg_match_rows_regex_substr_range: each side lowered by its own
+    parent's rules (CompiledMatcher, CompiledRowQuery, CompiledSubstringQuery, CompiledRangeQuery); FieldRegex, Substring,
+    FieldSubstring and FieldRange conditions share the one table."""
+
+    def __init__(self, bloom_expression, regex_expression, substring_expression, range_expression):
+        CompiledMatcher.__init__(self, None)
+        if bloom_expression is None:
+            self.prog_ops.append(op(OP_TRUE))
+        else:
+            self._emit(bloom_expression)
+        self._emit_regex(regex_expression)
+        self._emit_substring(substring_expression)
+        self._emit_range(range_expression)
+        self.prog_ops.append(op(OP_AND, 4))
+
+
+class CompiledRowTextRangeQueryBatch(CompiledMatcherBatch):
+    """A batch of (bloom, regex, substring, range) expression quadruples for one bsg_match_rows_many_regex_substr_range call: query q's
+    program is CompiledRowTextRangeQuery's with its condition indices remapped into ONE table of distinct conditions, deduplicated by
+    (kind, field, token / pattern / needle / range entry).  Raises ValueError beyond 64 queries, 64 conditions, 2 048 lowered ops or 16
+    regex conditions."""
+
+    @staticmethod
+    def _compile(quad):
+        return CompiledRowTextRangeQuery(*quad)
+
+
 class CompiledRowQueryBatch(CompiledMatcherBatch):
     """A batch of (bloom expression, regex expression) pairs for one bsg_match_rows_many_regex call: query q's program is
     CompiledRowQuery(bloom_q, regex_q)'s with its condition indices remapped into ONE table of distinct conditions,

@@ -54,7 +54,7 @@ extern "C" {
 #define BSG_KIND_FIELD_REGEX  3u   /* row matcher only (bsg_match_rows_regex): entry 2i = field, 2i + 1 = pattern */
 #define BSG_KIND_SUBSTRING        4u   /* bsg_match_rows_substr / _many_substr / _regex_substr / _many_regex_substr only: entry 2i empty, 2i + 1 = the needle */
 #define BSG_KIND_FIELD_SUBSTRING  5u   /* ... entry 2i = the field, 2i + 1 = the needle */
-#define BSG_KIND_FIELD_RANGE      6u   /* bsg_match_rows_range / _many_range / _wide_range(_rows) only: entry 2i = the field, 2i + 1 = lo, hi, flags ("Range conditions") */
+#define BSG_KIND_FIELD_RANGE      6u   /* bsg_match_rows_range / _many_range / _wide_range(_rows) / _regex_substr_range / _many_regex_substr_range only: entry 2i = the field, 2i + 1 = lo, hi, flags ("Range conditions") */
 #define BSG_RANGE_ENTRY_BYTES 17u      /* lo (int64, little-endian), hi (the same), one byte of BSG_RANGE_* */
 #define BSG_RANGE_NO_LO   1u           /* no lower bound (lo is ignored) */
 #define BSG_RANGE_NO_HI   2u           /* no upper bound (hi is ignored) */
@@ -823,9 +823,9 @@ BSG_API int32_t bsg_match_rows_substr(bsg_ctx *ctx, const uint8_t *rows, const u
  * kernels and returns its bits.  Same arguments, limits, sharding, chunked upload, fallback rows and bsg_last_match_ms as
  * bsg_match_rows_tok; a row with an exponent literal on a range condition's leaf is a fallback row too, as is one where a leaf's
  * path has the hashes of a range condition's field but not its fingerprint.
- * A condition of kind 3, 4 or 5 is BSG_E_UNSUPPORTED here (the condition named): range conditions do not share a table with the
- * regex and substring consumers yet.  Every entry point but this one, bsg_match_rows_many_range and bsg_match_rows_wide_range(_rows)
- * answers kind 6 with BSG_E_INVALID (unknown kind). */
+ * A condition of kind 3, 4 or 5 is BSG_E_UNSUPPORTED here (the condition named): range conditions share a table with the regex and
+ * substring consumers in bsg_match_rows_regex_substr_range / bsg_match_rows_many_regex_substr_range only.  Every entry point but those
+ * two, this one, bsg_match_rows_many_range and bsg_match_rows_wide_range(_rows) answers kind 6 with BSG_E_INVALID (unknown kind). */
 BSG_API int32_t bsg_match_rows_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
                                      const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
                                      const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
@@ -903,6 +903,41 @@ BSG_API int32_t bsg_match_rows_many_regex_substr(bsg_ctx *ctx, const uint8_t *ro
                                                  const bsg_tokenizer *tok,
                                                  uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                                  uint32_t *out_n_fallback);
+/* Range, FieldRegex and substring conditions in one table, decided in ONE walk of the rows (kinds 0-6; k_match_rows_regex_substr_range*):
+ * the fifteen arguments of bsg_match_rows_regex_substr.  Every kind keeps its documented entry format and refusals: the 17-byte range
+ * entry and its flag bits ("Range conditions"), the needle rules of bsg_match_rows_substr, regex conditions as bsg_match_rows_regex
+ * documents them.  A number literal is candidate text of all three consumers on the same bytes: the DFAs read it raw, the needles
+ * folded, the number parser as digits; a string reaches the first two alone (a string never holds for a range condition).
+ * The table decides the path: without a range condition the call is bsg_match_rows_regex_substr (same kernels, caps and bits); with
+ * range conditions and no condition of kind 3, 4 or 5 it is bsg_match_rows_range; any other table runs the three-consumer walkers,
+ * whether its text side is needles only, regex only or both.
+ * Limits of such a table (BSG_E_UNSUPPORTED before anything is launched, the condition named): 64 conditions, 16 regex conditions with
+ * patterns in the compiler's subset, regex tables of at most 40 448 bytes WHETHER OR NOT the table holds a needle (the walkers always
+ * carry the 4 096-byte needle table), the needle limits of bsg_match_rows_substr, the program limits of bsg_match_rows.
+ * BSG_E_INVALID: a kind above 6, a range entry of another length or with flag bits above 3, an empty or invalid needle.
+ * Fallback rows: the union of the parents' — the walker's envelope, a fingerprint collision, more than 4 regex conditions on one
+ * leaf, a rune the lower table cannot decide, an exponent literal on a range condition's leaf.  bsh_match_row_with,
+ * bsh_match_row_regex, bsh_match_row_substring and bsh_match_row_range decide them together.
+ * Sharding, chunked upload, fallback list and bsg_last_match_ms as bsg_match_rows. */
+BSG_API int32_t bsg_match_rows_regex_substr_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                                  const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                                  const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok,
+                                                  uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                                  uint32_t *out_n_fallback);
+/* The batched call of the same (k_match_rows_many_regex_substr_range*): the nineteen arguments, set / mask semantics, plane layout and
+ * limits of bsg_match_rows_many, and the delegation of the single call (no range condition: bsg_match_rows_many_regex_substr; range
+ * conditions and no kind 3-5: bsg_match_rows_many_range).  Each family keeps its batched parent's gating: a leaf opens a regex
+ * condition's DFA only on a row whose set mask selects a query that uses it, needles are not gated, and an exponent literal on the
+ * leaf of ANY range condition of the table makes a walked row a fallback row whatever its mask.  Regex tables (user masks included):
+ * at most 34 032 bytes, whether or not the table holds a needle.  Plane q = what bsg_match_rows_regex_substr_range returns for
+ * program q alone, ANDed with the set mask. */
+BSG_API int32_t bsg_match_rows_many_regex_substr_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                                       const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                                       const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                                       const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets,
+                                                       const bsg_tokenizer *tok,
+                                                       uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                                       uint32_t *out_n_fallback);
 /* bsg_match_rows_many with FieldRegex conditions in the table (k_match_rows_many_regex): the same nineteen arguments, set / mask
  * semantics, plane layout, sharding over the context's devices, chunked upload and bsg_last_match_ms.  What differs:
  * - cond_kinds[i] may be BSG_KIND_FIELD_REGEX (entry 2i = the field, 2i + 1 = the pattern) with the meaning bsg_match_rows_regex

@@ -168,7 +168,7 @@ typedef struct bse_engine bse_engine;
 /* config_json: {"MaxRowGroupRows":..,"MaxRowGroupBytes":..,"MaxBufferedRows":..,"MaxBufferedBytes":..,
  *               "BloomFalsePositiveRate":..,"PartitionField":"..","DeviceIngest":true|false,"DeviceIngestStream":true|false,
  *               "TrustedRows":true|false,"DevicePartition":true|false,"DeviceMatch":true|false,
- *               "DeviceRegex":true|false,"DeviceMatchWide":true|false,"DeviceMatchWideRows":true|false,
+ *               "DeviceRegex":true|false,"DeviceMatchRangeText":true|false,"DeviceMatchWide":true|false,"DeviceMatchWideRows":true|false,
  *               "DeviceMatchLookup":true|false,"DeviceMatchLookupRows":true|false,"DeviceMatchLookupRegex":true|false,
  *               "Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false,"Ngram":0|2|3|4},
  *               "MinMaxIndexes":["timestamp",..]};
@@ -203,7 +203,15 @@ typedef struct bse_engine bse_engine;
  *               (lookup_plan.hpp rx_lds_cap_of); same answers.  DeviceRegex (default false, needs DeviceMatch):
  *               a query whose regex patterns all lie in the device's RE2 subset is matched bloom AND regex by one
  *               bsg_match_rows_regex call, the rows it hands back by the host matcher on the same DFAs; other regex queries
- *               keep the std::regex path.  Tokenizer (default: BasicWhitespaceLowerTokenizer): the engine's tokenizer
+ *               keep the std::regex path.  DeviceMatchRangeText (default false, needs DeviceMatch): bse_query decides a
+ *               query that has a Range tree beside a Regex and / or Substring tree by one bsg_match_rows_regex_substr_range
+ *               call (a Regex tree takes part only under DeviceRegex with every pattern in the device subset; where the
+ *               library answers BSG_E_UNSUPPORTED the query takes the route it takes without the key; a Regex tree outside
+ *               the subset is left to the host matcher and the call decides range and substring); same answers.  With no wide
+ *               or lookup key set, bse_query_many lets such queries share its groups with range-only and text-only ones: a
+ *               group whose table holds a range condition beside a regex or substring one makes one
+ *               bsg_match_rows_many_regex_substr_range call (64 queries, 64 conditions, 16 regex conditions, needles that pack,
+ *               regex tables of at most 34 032 bytes); under a wide or lookup key groups never mix.  Tokenizer (default: BasicWhitespaceLowerTokenizer): the engine's tokenizer
  *               of the separator family (bloomgpu.h bsg_tokenizer), used by indexing, the host matcher and the device calls;
  *               a missing member is Go's zero value ("" / false); BSE_E_INVALID_CONFIG for a NUL or non-ASCII separator.
  *               MinMaxIndexes (default none): top-level keys whose per-block [min, max] every flush records (bloomgpu.h "per-set

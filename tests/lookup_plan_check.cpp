@@ -8,6 +8,7 @@
 //                     -> status, bad; Ok: n_strings, rec[], string_of[2 n_conds], canon[n_conds], n_pairs, (fid, tid, cond)[],
 //                     pair slots, per query find_pair
 //   kind 2  flags     n_conds, part_rows, row_base, r, cond -> flag_words, flag_index, flag_bit, flag_bytes_per_row
+//   kind 3  pairs     n, (fid, tid, cond)[n] -> slots, place_pairs' table[slots] (tests/test_lookup_shapes.py: slot for slot)
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -97,6 +98,12 @@ int main(int argc, char **argv)
             out.push_back(bsh_lookup::flag_index(cond, part_rows, row_base, r));
             out.push_back(bsh_lookup::flag_bit(cond));
             out.push_back(bsh_lookup::flag_bytes_per_row(n_conds));
+        } else if (kind == 3) {
+            std::vector<bsh_lookup::Pair> pairs((size_t)in.take());
+            for (bsh_lookup::Pair &p : pairs) { p.fid = (uint32_t)in.take(); p.tid = (uint32_t)in.take(); p.cond = (uint32_t)in.take(); }
+            const std::vector<uint64_t> tab = bsh_lookup::place_pairs(pairs);
+            out.push_back(tab.size());
+            out.insert(out.end(), tab.begin(), tab.end());
         } else {
             fprintf(stderr, "unknown case kind %llu\n", (unsigned long long)kind);
             return 2;

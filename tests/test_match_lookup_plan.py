@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.lookup_shapes import want_plan                  # build_strings restated: the lookup shapes place their tables with it too
 from tests.test_match_wide_rows_plan import Answers, run_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -102,38 +103,6 @@ def test_smaller_string_tables(driver, tmp_path, n):
     slots = a.take()
     check_string_table(a.take(slots), h0)
     assert a.take(n) == list(range(n)) and a.take(n + 1) == [NO_STRING] * (n + 1) and a.done()
-
-
-def want_plan(conds):
-    """build_strings restated: ids in order of first appearance in a role; -> (recs as tuples, string_of, canon, pairs)"""
-    ids, recs, string_of, canon, pairs, pair_cond = {}, [], [], [], [], {}
-
-    def sid(s, entry):
-        if s not in ids:
-            ids[s] = len(recs)
-            recs.append([entry, NO_COND, NO_COND, 0])
-        return ids[s]
-
-    for c, (kind, f, t) in enumerate(conds):
-        fid = sid(str(f), 2 * c) if kind != TOKEN else NO_STRING
-        tid = sid(str(t), 2 * c + 1) if kind != FIELD else NO_STRING
-        string_of += [fid, tid]
-        if kind == FIELD:
-            if recs[fid][1] == NO_COND:
-                recs[fid][1] = c
-            canon.append(recs[fid][1])
-        elif kind == TOKEN:
-            if recs[tid][2] == NO_COND:
-                recs[tid][2] = c
-            canon.append(recs[tid][2])
-        else:
-            if (fid, tid) not in pair_cond:
-                pair_cond[(fid, tid)] = c
-                pairs.append((fid, tid, c))
-                recs[fid][3] |= 1
-                recs[tid][3] |= 2
-            canon.append(pair_cond[(fid, tid)])
-    return [e | fc << 16 | tc << 32 | fl << 48 for e, fc, tc, fl in recs], string_of, canon, pairs, pair_cond
 
 
 def table_case(conds, queries):

@@ -105,7 +105,7 @@ EXPORTS = [
     "bsg_ingest_rows_minmax", "bsg_ingest_open_minmax", "bsg_ingest_minmax", "bsg_last_minmax_ms",
     "bsg_ingest_open_keyed", "bsg_ingest_append_rows_keyed", "bsg_ingest_add_sets_keyed", "bsg_ingest_keys", "bsg_last_partition_ms",
     "bsg_sections_size", "bsg_build_sections", "bsg_last_encode_ms",
-    "bsg_match_rows", "bsg_match_rows_regex", "bsg_match_rows_tok", "bsg_match_rows_substr", "bsg_match_rows_range", "bsg_match_rows_many_range", "bsg_match_rows_regex_substr", "bsg_match_rows_regex_substr_range", "bsg_match_rows_many_regex_substr_range", "bsg_match_rows_many", "bsg_match_rows_many_substr", "bsg_match_rows_many_regex_substr", "bsg_match_rows_many_regex", "bsg_match_rows_wide", "bsg_match_wide_size", "bsg_match_rows_wide_rows", "bsg_match_rows_wide_substr", "bsg_match_rows_wide_substr_rows", "bsg_match_rows_wide_range", "bsg_match_rows_wide_range_rows", "bsg_match_pair_rows_list", "bsg_match_rows_lookup", "bsg_match_rows_lookup_rows", "bsg_match_rows_lookup_regex", "bsg_match_rows_lookup_regex_rows", "bsg_last_match_ms", "bsg_pinned_alloc", "bsg_pinned_free", "bsg_host_register", "bsg_host_unregister",
+    "bsg_match_rows", "bsg_match_rows_regex", "bsg_match_rows_tok", "bsg_match_rows_substr", "bsg_match_rows_range", "bsg_match_rows_many_range", "bsg_match_rows_regex_substr", "bsg_match_rows_regex_substr_range", "bsg_match_rows_many_regex_substr_range", "bsg_match_rows_many", "bsg_match_rows_many_substr", "bsg_match_rows_many_regex_substr", "bsg_match_rows_many_regex", "bsg_match_rows_wide", "bsg_match_wide_size", "bsg_match_rows_wide_rows", "bsg_match_rows_wide_substr", "bsg_match_rows_wide_substr_rows", "bsg_match_rows_wide_range", "bsg_match_rows_wide_range_rows", "bsg_match_rows_wide_regex_substr_range", "bsg_match_rows_wide_regex_substr_range_rows", "bsg_match_pair_rows_list", "bsg_match_rows_lookup", "bsg_match_rows_lookup_rows", "bsg_match_rows_lookup_regex", "bsg_match_rows_lookup_regex_rows", "bsg_last_match_ms", "bsg_pinned_alloc", "bsg_pinned_free", "bsg_host_register", "bsg_host_unregister",
 ]
 
 _lib = None
@@ -231,6 +231,8 @@ def load():
     L.bsg_match_rows_wide_substr_rows.argtypes = L.bsg_match_rows_wide_rows.argtypes
     L.bsg_match_rows_wide_range.argtypes = L.bsg_match_rows_wide.argtypes
     L.bsg_match_rows_wide_range_rows.argtypes = L.bsg_match_rows_wide_rows.argtypes
+    L.bsg_match_rows_wide_regex_substr_range.argtypes = L.bsg_match_rows_wide.argtypes
+    L.bsg_match_rows_wide_regex_substr_range_rows.argtypes = L.bsg_match_rows_wide_rows.argtypes
     L.bsg_match_rows_lookup.argtypes = L.bsg_match_rows_wide.argtypes
     L.bsg_match_rows_lookup_rows.argtypes = L.bsg_match_rows_wide_rows.argtypes
     L.bsg_match_rows_lookup_regex.argtypes = L.bsg_match_rows_wide.argtypes

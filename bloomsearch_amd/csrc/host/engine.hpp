@@ -88,9 +88,18 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // counted.  With no wide or lookup key set, query_many lets range conditions and text conditions share a group, decided by ONE
     // bsg_match_rows_many_regex_substr_range call (range_text_groups.hpp: the closing rules, and the reduced 34 032-byte cap of the
     // regex tables as soon as kind 6 sits beside a text condition); under a wide or lookup key groups never mix (range_groups.hpp
-    // joins) and such a query goes to query().  Off by default: every route and every counted entry point is then exactly what it is
+    // joins) and such a query goes to query(), unless device_match_range_text_wide is set as well.  Off by default: every route and every counted entry point is then exactly what it is
     // without the key.
     bool device_match_range_text = false;
+    // true (needs device_match, device_match_range_text and at least one of the wide or lookup keys below; anything else is an invalid
+    // config): under those keys query_many lets range and text conditions share a wide group too (range_text_groups.hpp wide_fits: no
+    // member limit, 64 conditions, 16 regex conditions, co_active_bound, needles that pack, regex tables of at most 42 496 bytes needle
+    // or not), decided by ONE bsg_match_rows_wide_regex_substr_range call - under device_match_wide_rows / device_match_lookup_rows by
+    // its _rows twin, the lists consumed as the other wide groups' are.  Under a lookup key such a group is a 64-condition wide group,
+    // never a lookup call.  The rows the call hands back are decided by the four host matchers together; BSG_E_UNSUPPORTED sends the
+    // group's queries to query(), and the refused call is not counted.  query() is unchanged.  Off by default: every route and every
+    // counted entry point is then exactly what it is without the key.
+    bool device_match_range_text_wide = false;
     // true (with device_match): query_many packs its queries into groups bounded by the condition table alone (64 distinct
     // conditions, 16 regex conditions, the table bytes, co_active_bound) - not by 64 members - and decides each group by ONE
     // bsg_match_rows_wide call, every set's query list read straight from the probe's survivors (a group that holds a substring
@@ -174,6 +183,11 @@ public:
         if (c.device_partition && !c.trusted_rows) { err = "DevicePartition needs TrustedRows"; return kErrInvalidConfig; }
         if (c.device_partition && (c.partition_field.empty() || c.partition_field.size() > BSG_PARTITION_MAX_NAME)) {
             err = "DevicePartition needs a PartitionField of 1 to 64 bytes";
+            return kErrInvalidConfig;
+        }
+        if (c.device_match_range_text_wide && !(c.device_match && c.device_match_range_text &&
+                                                (c.device_match_wide || c.device_match_wide_rows || c.device_match_lookup || c.device_match_lookup_rows))) {
+            err = "DeviceMatchRangeTextWide needs DeviceMatch, DeviceMatchRangeText and one of DeviceMatchWide, DeviceMatchWideRows, DeviceMatchLookup, DeviceMatchLookupRows";
             return kErrInvalidConfig;
         }
         if (!c.minmax_indexes.empty() && !MinMaxFieldNames::check(c.minmax_indexes, err)) { err = "MinMaxIndexes: " + err; return kErrInvalidConfig; }
@@ -498,7 +512,8 @@ public:
     // Under DeviceMatchRangeText with no wide or lookup key, a range query WITH a regex and / or substring tree stays in the batch (by
     // the rules above for those trees): it is probed with And(bloom, regex field guard, substring guard, range guard), its program is
     // And(bloom root | TRUE, its trees), and a group whose table holds kind 6 beside a kind 3-5 condition makes ONE
-    // bsg_match_rows_many_regex_substr_range call (range_text_groups.hpp).
+    // bsg_match_rows_many_regex_substr_range call (range_text_groups.hpp).  Under a wide or lookup key the same holds with
+    // DeviceMatchRangeTextWide as well: the mixed group is a wide group and makes ONE bsg_match_rows_wide_regex_substr_range(_rows) call.
     int32_t query_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
                        std::vector<QueryResult> &results, const std::vector<const SubstringExpression *> *subs = nullptr,
                        const std::vector<const RangeExpression *> *ranges = nullptr, const std::vector<const PrefilterExpression *> *prefilters = nullptr)
@@ -506,7 +521,8 @@ public:
         // every query has its own prefilter mask on its survivors: a block no query of the batch keeps is never walked
         auto prefilter_of = [&](size_t i) { return prefilters && i < prefilters->size() ? (*prefilters)[i] : nullptr; };
         results.assign(exprs.size(), QueryResult{});
-        const bool mix_ok = bsh_rtg::mixing(cfg_.device_match, cfg_.device_match_range_text, any_wide_key());
+        const bool mix_ok = bsh_rtg::mixing(cfg_.device_match, cfg_.device_match_range_text, any_wide_key()) ||
+                            bsh_rtg::wide_mixing(cfg_.device_match, cfg_.device_match_range_text, cfg_.device_match_range_text_wide, any_wide_key());
         std::vector<size_t> live;                   // the batch: queries without a regex tree, and regex queries the device matches
         std::vector<const RegexExpression *> live_regex;
         std::vector<const SubstringExpression *> live_sub;
@@ -619,7 +635,8 @@ public:
     }
 
 private:
-    // any of the keys under which query_many's groups take the wide or the lookup calls: range and text conditions never share those
+    // any of the keys under which query_many's groups take the wide or the lookup calls: range and text conditions share those only
+    // under DeviceMatchRangeTextWide
     bool any_wide_key() const
     {
         return cfg_.device_match_wide || cfg_.device_match_wide_rows || cfg_.device_match_lookup || cfg_.device_match_lookup_rows;
@@ -1360,6 +1377,9 @@ private:
     // conditions in the table.  A group closes where the next query would put a range condition beside a regex or substring one, in either
     // order (range_groups.hpp joins); plain queries go with both.  A group with a range condition is decided by bsg_match_rows_many_range,
     // under the wide keys by bsg_match_rows_wide_range(_rows), and never by a lookup call (the wide route, bounded by 64 conditions).
+    // Under DeviceMatchRangeTextWide (with DeviceMatchRangeText and a wide or lookup key) range and text conditions share a wide group: it
+    // closes by range_text_groups.hpp's wide rules (the regex tables under 42 496 bytes needle or not), is decided by ONE
+    // bsg_match_rows_wide_regex_substr_range(_rows) call, and is a 64-condition wide group under the lookup keys, never a lookup call's.
     int32_t match_rows_device_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
                                    const std::vector<const SubstringExpression *> &subs, const std::vector<const RangeExpression *> &ranges,
                                    const std::vector<const std::string *> &scan, const std::vector<uint32_t> &set_first,
@@ -1378,7 +1398,9 @@ private:
         const bool lookup_rows = cfg_.device_match_lookup_rows, lookup = cfg_.device_match_lookup || lookup_rows;
         const bool wide_rows = cfg_.device_match_wide_rows || lookup_rows, wide = cfg_.device_match_wide || wide_rows || lookup;
         const bool lookup_regex = lookup && cfg_.device_match_lookup_regex;
-        const bool mix_ok = bsh_rtg::mixing(cfg_.device_match, cfg_.device_match_range_text, wide);   // range and text conditions may share a group
+        // range and text conditions may share a group: without a wide key by DeviceMatchRangeText, under one by DeviceMatchRangeTextWide as well
+        const bool wide_mix = bsh_rtg::wide_mixing(cfg_.device_match, cfg_.device_match_range_text, cfg_.device_match_range_text_wide, wide);
+        const bool mix_ok = bsh_rtg::mixing(cfg_.device_match, cfg_.device_match_range_text, wide) || wide_mix;
         const size_t max_members = wide ? bsh_wide::kMaxQueries : 64;
         const uint32_t table_cap = wide ? bsh_wide::kWideLdsCap : bsh_rxg::kManyLdsCap;
         std::map<std::string, std::pair<uint32_t, uint32_t>> dfa_size;      // pattern -> (states, classes); (0, 0): outside the subset
@@ -1440,7 +1462,9 @@ private:
                 // the lookup regex call's cap depends on the table: what this group's strings and pairs can take at most
                 const uint32_t group_cap = lookup_regex && rx_group && !needle_group ? bsh_lookup::rx_lds_cap_of(2u * (n_plain + fresh_plain), n_ft + fresh_ft) : table_cap;
                 // a table with kind 6 beside a text condition: the reduced cap beside a needle table, needle or not (range_text_groups.hpp)
-                const uint32_t rx_cap = bsh_rtg::regex_table_cap(bsh_rtg::with(mix, query_mix), wide, false, group_cap);
+                // ... and in a wide group the storing walker's cap beside its needle table, 42 496 bytes, needle or not
+                const uint32_t rx_cap = wide_mix ? bsh_rtg::wide_regex_table_cap(bsh_rtg::with(mix, query_mix), false, group_cap)
+                                                 : bsh_rtg::regex_table_cap(bsh_rtg::with(mix, query_mix), wide, false, group_cap);
                 const bool fits = bsh_rtg::joins(mix_ok, mix, query_mix) && mp.kinds.size() <= cond_cap && index.size() + added.size() <= cond_cap && n_rx + fresh_rx <= bsh_rxg::kMaxRegexConds &&
                                   bsh_rxg::align4(rx_table + fresh_bytes) <= rx_cap &&
                                   bsh_rxg::co_active_bound(rx_fields) <= bsh_rxg::kManySlots &&
@@ -1471,8 +1495,9 @@ private:
             if (members.empty()) continue;
             const bsh_subg::Call call = bsh_subg::group_call(n_rx != 0, sub_group.n_needles != 0, wide, wide_rows);
             const bool by_sub = sub_group.n_needles != 0, by_range = mix.range;
-            const bool by_mixed = bsh_rtg::mixed(mix);           // kind 6 beside a text condition: only where mix_ok, so never under a wide key
-            const char *call_name = bsh_rtg::group_call_name(mix, n_rx != 0, by_sub, wide, wide_rows);   // (of a group no lookup call decides)
+            const bool by_mixed = bsh_rtg::mixed(mix);           // kind 6 beside a text condition: only where mix_ok; under a wide key only with DeviceMatchRangeTextWide
+            const char *call_name = wide && by_mixed ? bsh_rtg::wide_group_call_name(mix, n_rx != 0, by_sub, wide_rows)
+                                                     : bsh_rtg::group_call_name(mix, n_rx != 0, by_sub, wide, wide_rows);   // (of a group no lookup call decides)
             // a row the device handed back: the host matchers of query m together
             auto host_verdict = [&](size_t m, const std::string &row) {
                 return host_matchers[m].match(row) && (!host_regex[m] || host_regex[m]->match(row)) && (!host_sub[m] || host_sub[m]->match(row)) &&
@@ -1485,7 +1510,7 @@ private:
                 cbytes.insert(cbytes.end(), tokens[c].begin(), tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
             }
             if (wide) {
-                const bool by_lookup = lookup && n_rx == 0 && !by_sub && !by_range, by_lookup_regex = lookup_regex && n_rx != 0 && !by_sub;
+                const bool by_lookup = lookup && n_rx == 0 && !by_sub && !by_range, by_lookup_regex = lookup_regex && n_rx != 0 && !by_sub && !by_range;
                 // each set's list: the group's members that survived the probe on it, straight from set_wants
                 std::vector<uint32_t> sq_off{0}, sq;
                 for (size_t s = 0; s < n_sets; ++s) {
@@ -1506,7 +1531,7 @@ private:
                     std::vector<uint64_t> pair_off(sq.size() + 1);
                     uint64_t payload_len = 0;
                     count_match_call(by_lookup_regex ? "bsg_match_rows_lookup_regex_rows" : by_lookup ? "bsg_match_rows_lookup_rows" : call_name);
-                    const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex_rows : by_lookup ? bsg_match_rows_lookup_rows : by_sub ? bsg_match_rows_wide_substr_rows : by_range ? bsg_match_rows_wide_range_rows : bsg_match_rows_wide_rows)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
+                    const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex_rows : by_lookup ? bsg_match_rows_lookup_rows : by_mixed ? bsg_match_rows_wide_regex_substr_range_rows : by_sub ? bsg_match_rows_wide_substr_rows : by_range ? bsg_match_rows_wide_range_rows : bsg_match_rows_wide_rows)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(),
                                                                 kinds.data(), (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(),
                                                                 (uint32_t)members.size(), set_first.data(), sq_off.data(), sq.data(), (uint32_t)n_sets, &tok,
                                                                 hdr.data(), pair_off.data(), payload.data(), 2 * total, &payload_len, fb.data(),
@@ -1528,7 +1553,7 @@ private:
                 } else {
                 std::vector<uint64_t> words(total + 1);
                 count_match_call(by_lookup_regex ? "bsg_match_rows_lookup_regex" : by_lookup ? "bsg_match_rows_lookup" : call_name);
-                const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex : by_lookup ? bsg_match_rows_lookup : by_sub ? bsg_match_rows_wide_substr : by_range ? bsg_match_rows_wide_range : bsg_match_rows_wide)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
+                const int32_t rc = (by_lookup_regex ? bsg_match_rows_lookup_regex : by_lookup ? bsg_match_rows_lookup : by_mixed ? bsg_match_rows_wide_regex_substr_range : by_sub ? bsg_match_rows_wide_substr : by_range ? bsg_match_rows_wide_range : bsg_match_rows_wide)(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
                                                        (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(),
                                                        sq_off.data(), sq.data(), (uint32_t)n_sets, &tok, words.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
                 if (rc == BSG_E_UNSUPPORTED) continue;

@@ -553,6 +553,7 @@ int32_t bse_open(const char *config_json, uint64_t len, bsg_ctx *ctx, bse_engine
         if (const JNode *n = dom.get("DeviceMatch")) cfg.device_match = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceRegex")) cfg.device_regex = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchRangeText")) cfg.device_match_range_text = n->type == JType::True;
+        if (const JNode *n = dom.get("DeviceMatchRangeTextWide")) cfg.device_match_range_text_wide = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchWide")) cfg.device_match_wide = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchWideRows")) cfg.device_match_wide_rows = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchLookup")) cfg.device_match_lookup = n->type == JType::True;

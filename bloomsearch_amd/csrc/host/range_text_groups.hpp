@@ -7,6 +7,8 @@
 // unchanged (range_groups.hpp itself is untouched: tests/test_range_groups.py pins joins).  The engine mirror (engine.hpp
 // match_rows_device_many) closes its groups and picks its entry points by these functions; tests/range_text_groups_check.cpp runs the
 // same code on the CPU (tests/test_range_text_groups.py).
+// Under a wide or lookup key the two families share a group only with the DeviceMatchRangeTextWide key as well: the wide_* functions at
+// the end (bsg_match_rows_wide_regex_substr_range(_rows); tests/range_text_wide_groups_check.cpp, tests/test_range_text_wide_groups.py).
 #pragma once
 #include <cstdint>
 #include <string_view>
@@ -86,6 +88,47 @@ inline const char *group_call_name(const Mix &table, bool regex, bool needles, b
 {
     if (mixed(table)) return wide || wide_rows ? nullptr : kManyCall;
     return bsh_rngg::group_call_name(table.range, regex, needles, wide, wide_rows);
+}
+
+// ---- under a wide or lookup key: the engine's DeviceMatchRangeTextWide key (bsg_match_rows_wide_regex_substr_range(_rows)) ----
+// Every answer above stands as it is; these are asked beside them.
+
+// May range and text conditions share a group under a wide or lookup key (wide = any of them): DeviceMatch, DeviceMatchRangeText and the
+// wide key of the two families.
+inline bool wide_mixing(bool device_match, bool range_text_key, bool range_text_wide_key, bool wide)
+{
+    return device_match && range_text_key && range_text_wide_key && wide;
+}
+
+constexpr uint32_t kWideMixedCap = bsh_rxg::kWideSubLdsCap;     // 42 496: regex tables (no user masks) of a mixed wide group, needle or not
+// The bytes the regex tables of a wide group may take: the cap beside the needle table for a mixed table whether or not it holds a
+// needle (the three-consumer storing walkers always carry the needle table), else what regex_table_cap says of a wide group.
+inline uint32_t wide_regex_table_cap(const Mix &table, bool needles, uint32_t base)
+{
+    if (mixed(table)) return kWideMixedCap;
+    return regex_table_cap(table, true, needles, base);
+}
+
+// Every closing rule of a wide group at once.  No member limit beyond the call's own (bsh_wide::kMaxQueries); 64 conditions, 16 regex
+// conditions, co_active_bound, needles that pack by substring_groups.hpp fits(.., wide = true), and the regex-table estimate against
+// the cap the table with the query in it has (base: the cap of a table without a needle and not mixed, the wide call's own).
+inline bool wide_fits(bool mix_ok, const Group &g, const Fresh &f, uint32_t base = bsh_wide::kWideLdsCap)
+{
+    if (!joins(mix_ok, g.mix, f.mix)) return false;
+    if (g.n_queries + 1 > bsh_wide::kMaxQueries || f.query_conds > kMaxConds || g.n_conds + f.n_conds > kMaxConds) return false;
+    if (g.n_rx + f.n_rx > bsh_rxg::kMaxRegexConds || f.co_active > bsh_rxg::kManySlots) return false;
+    const bool needles = g.sub.n_needles + f.sub.needle_len.size() != 0;
+    if (needles && !bsh_subg::fits(g.sub, f.sub, true)) return false;
+    return bsh_rxg::align4(g.sub.rx_bytes + f.sub.rx_bytes) <= wide_regex_table_cap(with(g.mix, f.mix), needles, base);
+}
+
+constexpr const char *kWideCall = "bsg_match_rows_wide_regex_substr_range", *kWideRowsCall = "bsg_match_rows_wide_regex_substr_range_rows";
+// The entry point of a wide group that no lookup call decides: the new call (its _rows twin under a rows key) for a mixed table, else
+// group_call_name's answer.
+inline const char *wide_group_call_name(const Mix &table, bool regex, bool needles, bool wide_rows)
+{
+    if (mixed(table)) return wide_rows ? kWideRowsCall : kWideCall;
+    return group_call_name(table, regex, needles, true, wide_rows);
 }
 
 }  // namespace bsh_rtg

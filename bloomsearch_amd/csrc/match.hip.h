@@ -96,6 +96,15 @@
 // Every statement the three flags guard runs as in the parents; a row is a fallback row by the union of their rules.  In the batched
 // instances a DFA opens only for a row whose set mask selects a user of the condition, needles are ungated, and an exponent literal on
 // the field of ANY range condition of the table hands the row back.  No LDS beyond the regex_substr instances', two workgroups per CU.
+//
+// All three in the storing walker (bsg_match_rows_wide_regex_substr_range, k_match_rows_store_regex_substr_range* = WIDE, REGEX, SUB and
+// RANGE): the union of the wide parents.  A DFA opens, and a range condition listens, only where the set's condition mask selects the
+// condition; every needle listens on every walked row; the flag of a condition none of the set's queries references is unspecified
+// (nothing reads it).  So an exponent literal hands a row back only if a range condition of the SET's queries sits on its leaf, and five
+// regex conditions on one leaf only if the set's queries put them there - not the batched walker's "any condition of the table".  One
+// family serves every mix beside a range condition: the needle table always sits at kMatchWideLdsBytes (all zero without a needle), the
+// blob behind it (n_rx = n_words = 0 without a regex condition), at most kRxWideSubLdsCap = 42 496 bytes needle or not: 80 KiB and two
+// workgroups per CU with a blob at the cap, 39 424 bytes and three without one.
 #pragma once
 #include <type_traits>
 #include "ingest.hip.h"
@@ -434,9 +443,7 @@ __device__ __forceinline__ void match_rows_body(const MatchArgs &a, const RxArgs
                                                 const MatchWideArgs &wd = MatchWideArgs{}, const SubArgs &sb = SubArgs{})
 {
     static_assert(!(MANY && WIDE), "the storing walker evaluates no program");
-    if constexpr (REGEX && SUB) {      // both text consumers: the number consumer may join them, in the single and the batched walkers
-        static_assert(!(RANGE && WIDE), "range conditions beside the text consumers: the single and the batched walkers only");
-    } else {                           // ... and never beside exactly one of the two
+    if constexpr (!(REGEX && SUB)) {   // both text consumers: the number consumer may join them, in every walker; never beside exactly one of the two
         static_assert(!(RANGE && (REGEX || SUB)), "range conditions: beside no text consumer, or beside both");
     }
     constexpr uint32_t kSubBase = WIDE ? kMatchWideLdsBytes : MANY ? kMatchManySubBase : kMatchLdsBytes;   // the needle table sits behind the instance's own LDS
@@ -916,6 +923,26 @@ __global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_subst
 __global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_substr_gram(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchWideArgs wd, const TokSpec t)
 {
     match_rows_body<true, TokGramP, false, kRxActive, true, true>(a, x, TokGramP(t), MatchManyArgs{}, wd, sb);
+}
+// ... and with all three (bsg_match_rows_wide_regex_substr_range): kinds 0-6.  NumLane adds no LDS, so the bytes and the blob cap are the
+// regex_substr instances': dynamic LDS kMatchWideSubLdsBytes + the table blob (<= kRxWideSubLdsCap).  One family serves every mix of the
+// three sides beside a range condition: the needle table always sits at kMatchWideLdsBytes (all zero without a needle: start = any = 0),
+// the blob behind it (n_rx = n_words = 0 without a regex condition), and the blob's cap is the same with a needle and without one.
+static_assert(2u * (kMatchWideSubLdsBytes + kRxWideSubLdsCap) <= 160u * 1024u && 3u * (kMatchWideSubLdsBytes + kRxWideSubLdsCap) > 160u * 1024u,
+              "k_match_rows_store_regex_substr_range keeps two workgroups per CU with a blob at the cap, as its regex_substr sibling");
+static_assert(3u * kMatchWideSubLdsBytes <= 160u * 1024u,
+              "k_match_rows_store_regex_substr_range keeps three workgroups per CU without a blob, as k_match_rows_store_substr");
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_substr_range(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchWideArgs wd)
+{
+    match_rows_body<true, TokDefault, false, kRxActive, true, true, true>(a, x, TokDefault{}, MatchManyArgs{}, wd, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_substr_range_tok(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchWideArgs wd, const TokSpec t)
+{
+    match_rows_body<true, TokSpecP, false, kRxActive, true, true, true>(a, x, TokSpecP{t}, MatchManyArgs{}, wd, sb);
+}
+__global__ __launch_bounds__(kIngestThreads) void k_match_rows_store_regex_substr_range_gram(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchWideArgs wd, const TokSpec t)
+{
+    match_rows_body<true, TokGramP, false, kRxActive, true, true, true>(a, x, TokGramP(t), MatchManyArgs{}, wd, sb);
 }
 
 // The programs of the listed (set, query) pairs over the stored flags.  Wave w of the grid owns item w: one 64-row tile of one set

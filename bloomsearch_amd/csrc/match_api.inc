@@ -27,6 +27,10 @@
 // bsg_match_rows_range's / _many_range's; any other table gets the blob (under kRxSubLdsCap / kRxManySubLdsCap whether or not it holds a
 // needle: the needle table is always there), the needle tables (all zero without a needle) AND the range table, chained in that order
 // (each rewrites cond_kinds from the current pointer), and PlanePart launches k_match_rows_regex_substr_range* / k_match_rows_many_regex_substr_range*.
+// bsg_match_rows_wide_regex_substr_range(_rows) is the wide call with kinds 0-6 in its table, routed as the plane calls route theirs: a table
+// without a range condition is bsg_match_rows_wide_substr(_rows)'s (walkers, caps, bits and refusals), one with range conditions and no
+// kind 3-5 is bsg_match_rows_wide_range(_rows)'s; any other table gets the three tables (the blob under kRxWideSubLdsCap needle or not, no
+// user masks) and WidePart launches k_match_rows_store_regex_substr_range*.
 // bsg_match_rows_lookup(_rows) is the wide call with another Family and a LookupPlan beside its WidePlan: WidePart then sizes the
 // flags at W words per row, places the lookup tables (host/lookup_plan.hpp) from the hashes the device made, and launches
 // match_lookup.hip.h's walker and evaluator in place of match.hip.h's.  bsg_match_rows_lookup_regex(_rows) is that call with FieldRegex
@@ -111,6 +115,7 @@ struct MatchCall {
     std::vector<uint32_t> sub_kinds;       // ... and cond_kinds with word | end bit of a substring condition's needle (match.hip.h SubLane)
     bool range_call = false;               // the call is bsg_match_rows_range / bsg_match_rows_many_range (the name in traces)
     bool wide_range = false;               // the call is bsg_match_rows_wide_range(_rows) (the name in traces)
+    bool wide_range_text = false;          // the call is bsg_match_rows_wide_regex_substr_range(_rows) (the name in traces)
     bool range_text = false;               // the call is bsg_match_rows_regex_substr_range / bsg_match_rows_many_regex_substr_range (the name in traces)
     bool three = false;                    // ... and its table holds a FieldRange condition beside a regex or substring one: the three-consumer walkers run
     bool range = false;                    // build_range_table: the table holds a FieldRange condition, the range walkers run
@@ -498,6 +503,7 @@ struct WidePart {
     {
         if (wp.lookup_regex) return wp.rows ? "bsg_match_rows_lookup_regex_rows" : "bsg_match_rows_lookup_regex";
         if (wp.lookup) return wp.rows ? "bsg_match_rows_lookup_rows" : "bsg_match_rows_lookup";
+        if (mc.wide_range_text) return wp.rows ? "bsg_match_rows_wide_regex_substr_range_rows" : "bsg_match_rows_wide_regex_substr_range";
         if (mc.wide_sub) return wp.rows ? "bsg_match_rows_wide_substr_rows" : "bsg_match_rows_wide_substr";
         if (mc.wide_range) return wp.rows ? "bsg_match_rows_wide_range_rows" : "bsg_match_rows_wide_range";
         return wp.rows ? "bsg_match_rows_wide_rows" : "bsg_match_rows_wide";
@@ -585,6 +591,12 @@ struct WidePart {
             return;
         }
         const bsg::MatchWideArgs wd{d_sfirst, d_smask, d_spair, d_sat + rf, d_state + rf, n_sets};
+        if (mc.three) {                                // all three consumers: the regex_substr instances' LDS, whatever sides the table holds
+            assert(mc.substr && mc.range && p.sub.table && p.rx.n_words * 4 <= bsg::kRxWideSubLdsCap);
+            launch_rx_sub_walker(bsg::k_match_rows_store_regex_substr_range, bsg::k_match_rows_store_regex_substr_range_tok, bsg::k_match_rows_store_regex_substr_range_gram,
+                                 bsg::kMatchWideSubLdsBytes, p.d.stream, k0, k1, a, p.rx, p.sub, mc.tok(), wd);
+            return;
+        }
         if (mc.substr && mc.n_rx) {                    // both consumers: the blob behind the needle table
             assert(p.rx.n_words * 4 <= bsg::kRxWideSubLdsCap);
             launch_rx_sub_walker(bsg::k_match_rows_store_regex_substr, bsg::k_match_rows_store_regex_substr_tok, bsg::k_match_rows_store_regex_substr_gram,
@@ -838,6 +850,23 @@ int32_t build_three_tables(MatchCall &mc, uint32_t cap, const uint64_t *users)
     return build_range_table(mc);
 }
 
+// bsg_match_rows_wide_regex_substr_range(_rows): the same three ways.  The parents' paths are taken by their own flags, so their kernels,
+// caps, bits and refusals are theirs; only the name in traces and call counts stays this call's.
+int32_t route_wide_range_text(MatchCall &mc)
+{
+    if (!mc.wide_range_text) return BSG_OK;
+    bool has_range = false, has_text = false;
+    for (uint32_t c = 0; c < mc.n_conds; ++c) {
+        if (mc.cond_kinds[c] > BSG_KIND_FIELD_RANGE) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
+        has_range |= mc.cond_kinds[c] == BSG_KIND_FIELD_RANGE;
+        has_text |= range_refuses(mc.cond_kinds[c]);
+    }
+    mc.wide_sub = !has_range;
+    mc.wide_range = has_range && !has_text;
+    mc.three = has_range && has_text;
+    return BSG_OK;
+}
+
 // which sides a table of bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr holds
 struct TableSides { bool regex = false, sub = false; };
 TableSides table_sides(const MatchCall &mc)
@@ -962,8 +991,9 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
     if (rows && (!rows->len || (rows->cap && !rows->payload))) return fail(BSG_E_INVALID, "null argument");
     if (int32_t rc = begin_match_call(mc, fam, tok_in, prog_ops, prog_off, n_queries)) return rc;
     const uint32_t n_rows = mc.n_rows;
+    if (int32_t rc = route_wide_range_text(mc)) return rc;
     const uint32_t max_kind = mc.wide_sub ? BSG_KIND_FIELD_SUBSTRING : BSG_KIND_FIELD_REGEX;   // kinds 4 and 5: bsg_match_rows_wide_substr(_rows) only
-    for (uint32_t c = 0; c < mc.n_conds; ++c) {
+    for (uint32_t c = 0; c < mc.n_conds && !mc.three; ++c) {   // (three: route_wide_range_text has seen kinds 0-6 and nothing else)
         if (mc.wide_range) {                   // bsg_match_rows_wide_range(_rows): kinds 0, 1, 2 and 6, no text consumer beside the number one
             if (range_refuses(mc.cond_kinds[c])) return fail(BSG_E_UNSUPPORTED, kNoTextWithRange, c, mc.cond_kinds[c]);
             if (mc.cond_kinds[c] > BSG_KIND_FIELD_RANGE) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
@@ -1007,7 +1037,9 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
             }
     }
     if (int32_t rc = lower_programs(mc, fam, prog_ops, prog_off, n_queries, lookup ? &lookup_plan.canon : nullptr)) return rc;
-    if (mc.wide_range) {                       // no regex condition reaches this call: the bounds and flags of the kind-6 ones, if any
+    if (mc.three) {                            // kind 6 beside a text condition: the blob under the cap beside a needle table, the needle tables, the bounds
+        if (int32_t rc = build_three_tables(mc, bsg::kRxWideSubLdsCap, nullptr)) return rc;
+    } else if (mc.wide_range) {                // no regex condition reaches this call: the bounds and flags of the kind-6 ones, if any
         if (int32_t rc = build_range_table(mc)) return rc;
     } else if (!lookup) {
         // a table with needles: the blob under what the needle table leaves, then the needle tables; one without: the wide call's own
@@ -1166,6 +1198,35 @@ int32_t bsg_match_rows_wide_range_rows(bsg_ctx *ctx, const uint8_t *rows, const 
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
                  fallback_cap, out_n_fallback};
     mc.wide_range = true;
+    const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
+}
+
+int32_t bsg_match_rows_wide_regex_substr_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                               const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                               const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                               const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
+                                               const bsg_tokenizer *tok,
+                                               uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
+    mc.wide_range_text = true;
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
+}
+
+int32_t bsg_match_rows_wide_regex_substr_range_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                                    const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                                    const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                                    const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
+                                                    const bsg_tokenizer *tok,
+                                                    uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap, uint64_t *out_payload_len,
+                                                    uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
+                 fallback_cap, out_n_fallback};
+    mc.wide_range_text = true;
     const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
     return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
 }

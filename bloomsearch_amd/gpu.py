@@ -950,6 +950,16 @@ class Context:
         """bsg_match_rows_wide_range_rows: match_rows_wide_rows' arguments and result over such a table."""
         return self._wide_rows(self.L.bsg_match_rows_wide_range_rows, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap)
 
+    def match_rows_wide_regex_substr_range(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None):
+        """bsg_match_rows_wide_regex_substr_range: match_rows_wide's arguments and result, and the batch (query.CompiledWideTextRangeBatch,
+        any number of queries) may hold all seven condition kinds in one table.  Regex and range conditions are gated by the set's
+        queries, needles are not; a row is handed back by the union of match_rows_wide_substr's and match_rows_wide_range's rules."""
+        return self._wide_bits(self.L.bsg_match_rows_wide_regex_substr_range, rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
+
+    def match_rows_wide_regex_substr_range_rows(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None, payload_cap=None):
+        """bsg_match_rows_wide_regex_substr_range_rows: match_rows_wide_rows' arguments and result over such a table."""
+        return self._wide_rows(self.L.bsg_match_rows_wide_regex_substr_range_rows, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap)
+
     def match_rows_lookup(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None):
         """bsg_match_rows_lookup: match_rows_wide's arguments and result over a table of up to 1 024 Field / Token / FieldToken
         conditions (batch: query.CompiledLookupBatch, or anything with kinds / fields / tokens / prog_ops / prog_off)."""

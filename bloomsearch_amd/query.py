@@ -729,7 +729,15 @@ class CompiledWideRangeBatch(CompiledRangeQueryBatch):
     MAX_QUERIES, MAX_OPS = MATCH_WIDE_MAX_QUERIES, MATCH_WIDE_MAX_OPS
 
 
-MATCH_LOOKUP_MAX_CONDS = 1024                                                     # bloomgpu.h BSG_MATCH_LOOKUP_MAX_CONDS
+class CompiledWideTextRangeBatch(CompiledRowTextRangeQueryBatch):
+    """Any number of (bloom, regex, substring, range) expression quadruples for one bsg_match_rows_wide_regex_substr_range call: the table
+    and the programs exactly as CompiledRowTextRangeQueryBatch builds them, without the 64-query and 2 048-op limits of the batched
+    call.  Raises ValueError beyond 2^20 queries, 2^22 lowered ops, 64 conditions or 16 regex conditions."""
+
+    MAX_QUERIES, MAX_OPS = MATCH_WIDE_MAX_QUERIES, MATCH_WIDE_MAX_OPS
+
+
+MATCH_LOOKUP_MAX_CONDS = 1024                                                    # bloomgpu.h BSG_MATCH_LOOKUP_MAX_CONDS
 
 
 class CompiledLookupBatch(CompiledWideBatch):

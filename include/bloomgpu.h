@@ -1091,6 +1091,43 @@ BSG_API int32_t bsg_match_rows_wide_range_rows(bsg_ctx *ctx, const uint8_t *rows
                                                uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap,
                                                uint64_t *out_payload_len, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                                uint32_t *out_n_fallback);
+/* bsg_match_rows_wide / bsg_match_rows_wide_rows with every condition kind allowed in ONE table (kinds 0-6; the storing walkers
+ * k_match_rows_store_regex_substr_range*): the parameter lists, sets, pairs and the implicit set, result layouts, bsg_match_wide_size,
+ * bsg_match_pair_rows_list, the list passes, sharding, chunked upload and bsg_last_match_ms of the two wide calls.  Pair p's bits = what
+ * bsg_match_rows_regex_substr_range returns for the program of set_queries[p] alone over the set's rows, on every row neither call
+ * hands back.  The table decides the path, as in bsg_match_rows_regex_substr_range: a table without a range condition is
+ * bsg_match_rows_wide_substr(_rows)'s (the same kernels, caps, bits and refusals), one with range conditions and no condition of kind
+ * 3, 4 or 5 is bsg_match_rows_wide_range(_rows)'s; any other table is fed by one walk to the DFAs (a number literal raw, as any leaf
+ * text), the needles (folded) and the number parser.
+ * Gating is the union of the wide parents': a FieldRegex condition opens its DFA, and a FieldRange condition listens, on a leaf only
+ * for rows of a set that lists a query which uses it; every needle listens on every walked row; the flag of a condition none of the
+ * set's queries references is unspecified; rows of a set with no pair are never walked and never fallback rows.
+ * Limits (BSG_E_UNSUPPORTED before anything is launched, the condition named): 64 distinct conditions; 16 distinct regex conditions
+ * with patterns in the compiler's subset; regex tables of at most 42 496 bytes of LDS, whether or not the table holds a needle (the
+ * needle table is always there: 39 424 bytes and three workgroups per CU without regex tables, 80 KiB and two with them); a needle of
+ * at most 64 bytes after folding, the needles packed first-fit in condition order into 2 words of 64 bytes; program depth 64; the
+ * query, op, pair and item limits of bsg_match_rows_wide.  BSG_E_INVALID: what bsg_match_rows_wide refuses, a kind above 6, a range
+ * entry of another length than BSG_RANGE_ENTRY_BYTES or a flag bit above 3 (the condition named), an empty needle or one that is not
+ * valid UTF-8.
+ * Fallback rows, only among rows of a set with at least one pair (all their pair bits 0, never counted in a list): the union of the
+ * parents' rules — the walker's envelope, a fingerprint collision with ANY table condition, more than 4 regex conditions of the set's
+ * queries on one leaf, a rune the lower table cannot decide, an exponent literal on a leaf where a range condition used by the set's
+ * queries listens (bsg_match_rows_wide_range's rule, not bsg_match_rows_many_regex_substr_range's "any range condition of the table"). */
+BSG_API int32_t bsg_match_rows_wide_regex_substr_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                                       const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                                       const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                                       const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                                       uint32_t n_sets, const bsg_tokenizer *tok,
+                                                       uint64_t *out_bits, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                                       uint32_t *out_n_fallback);
+BSG_API int32_t bsg_match_rows_wide_regex_substr_range_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                                            const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                                            const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                                            const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                                            uint32_t n_sets, const bsg_tokenizer *tok,
+                                                            uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap,
+                                                            uint64_t *out_payload_len, uint32_t *out_fallback_rows, uint32_t fallback_cap,
+                                                            uint32_t *out_n_fallback);
 /* One pair of bsg_match_rows_wide_rows, whatever its tag, as its ascending set-relative row indices (host arithmetic without a
  * context): payload = out_payload + out_pair_off[p] (not read for NONE / ALL), set_rows = the rows of the pair's set.  *out_n is the
  * full count; at most cap indices are written.  BSG_E_INVALID: a header and payload that are no pair of such a set (a count the

@@ -169,6 +169,7 @@ typedef struct bse_engine bse_engine;
  *               "BloomFalsePositiveRate":..,"PartitionField":"..","DeviceIngest":true|false,"DeviceIngestStream":true|false,
  *               "TrustedRows":true|false,"DevicePartition":true|false,"DeviceMatch":true|false,
  *               "DeviceRegex":true|false,"DeviceMatchRangeText":true|false,"DeviceMatchWide":true|false,"DeviceMatchWideRows":true|false,
+ *               "DeviceMatchRangeTextWide":true|false,
  *               "DeviceMatchLookup":true|false,"DeviceMatchLookupRows":true|false,"DeviceMatchLookupRegex":true|false,
  *               "Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false,"Ngram":0|2|3|4},
  *               "MinMaxIndexes":["timestamp",..]};
@@ -211,7 +212,14 @@ typedef struct bse_engine bse_engine;
  *               or lookup key set, bse_query_many lets such queries share its groups with range-only and text-only ones: a
  *               group whose table holds a range condition beside a regex or substring one makes one
  *               bsg_match_rows_many_regex_substr_range call (64 queries, 64 conditions, 16 regex conditions, needles that pack,
- *               regex tables of at most 34 032 bytes); under a wide or lookup key groups never mix.  Tokenizer (default: BasicWhitespaceLowerTokenizer): the engine's tokenizer
+ *               regex tables of at most 34 032 bytes); under a wide or lookup key groups never mix without the next key.
+ *               DeviceMatchRangeTextWide (default false; needs DeviceMatch, DeviceMatchRangeText and at least one of
+ *               DeviceMatchWide, DeviceMatchWideRows, DeviceMatchLookup, DeviceMatchLookupRows: BSE_E_INVALID_CONFIG otherwise):
+ *               under those keys too bse_query_many lets range and text conditions share a group: a wide group (no member limit,
+ *               64 conditions, 16 regex conditions, needles that pack, regex tables of at most 42 496 bytes needle or not) whose
+ *               table holds both makes one bsg_match_rows_wide_regex_substr_range call, under a rows key one
+ *               bsg_match_rows_wide_regex_substr_range_rows call, and never a lookup call; bse_query is unchanged; same answers.
+ *               Tokenizer (default: BasicWhitespaceLowerTokenizer): the engine's tokenizer
  *               of the separator family (bloomgpu.h bsg_tokenizer), used by indexing, the host matcher and the device calls;
  *               a missing member is Go's zero value ("" / false); BSE_E_INVALID_CONFIG for a NUL or non-ASCII separator.
  *               MinMaxIndexes (default none): top-level keys whose per-block [min, max] every flush records (bloomgpu.h "per-set
@@ -261,7 +269,8 @@ BSG_API int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, c
  * substring condition (it closes where the next query would create that mix, in either order; plain queries go with both), and a group
  * with a range condition is decided by ONE bsg_match_rows_many_range call - under DeviceMatchWide / DeviceMatchWideRows (and the lookup
  * keys, which never take such a group) by ONE bsg_match_rows_wide_range / bsg_match_rows_wide_range_rows call.  A query with a Range
- * tree beside a Regex or Substring tree, and every query with a Range tree without DeviceMatch, is answered as by bse_query.
+ * tree beside a Regex or Substring tree, and every query with a Range tree without DeviceMatch, is answered as by bse_query
+ * (DeviceMatchRangeText, and under a wide or lookup key DeviceMatchRangeTextWide, keep such a query in the batch: bse_open).
  * "[]" gives "[]". */
 BSG_API int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, char **out_json, uint64_t *out_len);
 /* {"files":[{"FileID","BloomEntryCounts":{..},"section_bytes","blocks":[{"PartitionID","Rows","BloomEntryCounts":{..},

@@ -961,6 +961,17 @@ __global__ __launch_bounds__(kProbeThreads) void k_probe_terms_many_ext(const Pr
 // of 4, at 2 it gains 1-3 us at 20 arenas and loses 9-14 at 200, at 1 it loses 4-29 %: the kernel needs its 8 waves per SIMD, so the
 // planner's rule is no pad.  Earlier: non-temporal loads +18 % (a line is wanted again by later locations), all k locations in one
 // phase +18 %, the fp64 modulo a draw (the kernel waits on memory: Barrett, as the other few-term kernels).
+// ORDER (BSG_GATHER_ORDER).  A term passes iff all k bits are set, so the order of a lane's k tests is free.  In hash-index order two
+// terms that need the same line ask for it in unrelated phases; sorted by the filter's 128-byte span (loc >> 10, ties by hash index)
+// every lane's phase 1 falls into the filter's first spans, phase 2 into the next ones, phase 3 into the rest: the lines merge inside
+// a phase, where no L2 has to keep them.  The lane reduces all k locations before phase 1 (290 reductions per C2 block instead of
+// ~205) and sorts them in registers; phases, alive rule, early leave and the executed-test count are the same.  k > 16, filters of
+// 2^31 bits and more (the 64-bit modulo) and filters above kGatherOrderMaxM bits keep the index order.  Same shapes, parent build and
+// this build taking turns (profiles/probe_gather_order_lab.txt; the CPU model per order and schedule is its §1):
+//   order        tests executed   lines touched   sum of the phases' lines   requests (FETCH_SIZE)   gather time, 20 / 200 arenas
+//   0 index           204.8           144.5             177.4                    161.0 / 158.1            59.7 / 566 us
+//   1 line (default)  204.8           143.8             159.1                    147.1 / 145.9            55.8 / 538
+// Requests fall by 8-9 %, the time by 5-6 %: the sort and the 85 extra reductions per block are not quite hidden.
 #ifndef BSG_GATHER_SCHEDULE
 #define BSG_GATHER_SCHEDULE 1, 3, 6   // phase lengths (lab: -DBSG_GATHER_SCHEDULE=4,4,4 ...)
 #endif
@@ -969,6 +980,9 @@ __global__ __launch_bounds__(kProbeThreads) void k_probe_terms_many_ext(const Pr
 #endif
 #ifndef BSG_GATHER_FP64
 #define BSG_GATHER_FP64 0         // lab: 1 = the fp64 modulo for 64 <= m <= 2^19
+#endif
+#ifndef BSG_GATHER_ORDER
+#define BSG_GATHER_ORDER 1        // the order in which a lane takes its k locations: 0 = hash index, 1 = ascending line (ties: hash index)
 #endif
 template <uint32_t... L> struct GatherPhases {};
 typedef GatherPhases<BSG_GATHER_SCHEDULE> GatherSchedule;
@@ -1034,18 +1048,112 @@ __device__ __forceinline__ uint32_t gather_phases(GatherPhases<L0, L...>, const 
     return alive;
 }
 
+// ORDER 1: a lane's k locations sorted by (line of the filter, hash index) before the phases take them.  A location travels as one
+// 32-bit key  line << 14 | hash index << 10 | bit within the line  (line = loc >> 10, the 128-byte span of the FILTER: a filter starts
+// on a 16-byte boundary of the arena, so a span lies in one or two of the arena's lines), so the order is an unsigned comparison and
+// a compare-exchange is v_min_u32 + v_max_u32 on registers; the keys of positions beyond k are ~0 and stay last.  The key has 18 bits for the line; filters of up to kGatherOrderMaxM bits use 17, so no key is ~0 and a phase tells a
+// position beyond k by its key.  A lane has up to kGatherOrderMaxK locations (4 bits of index).
+constexpr uint64_t kGatherOrderMaxM = 1ull << 27;
+constexpr uint32_t kGatherOrderMaxK = 16;
+constexpr uint32_t kGatherOrderSmallK = 10;      // up to here the narrower network (fpr 0.001 and above: k <= 10)
+// Batcher's odd-even merge sort of 16 wires (63 exchanges); the exchanges among the first N wires sort N (the wires beyond hold
+// the largest keys and never move): 32 for N = 10
+constexpr uint8_t kGatherSortNet[63][2] = {
+    {0, 1}, {2, 3}, {4, 5}, {6, 7}, {8, 9}, {10, 11}, {12, 13}, {14, 15}, {0, 2}, {1, 3}, {4, 6}, {5, 7}, {8, 10}, {9, 11}, {12, 14}, {13, 15},
+    {1, 2}, {5, 6}, {9, 10}, {13, 14}, {0, 4}, {1, 5}, {2, 6}, {3, 7}, {8, 12}, {9, 13}, {10, 14}, {11, 15}, {2, 4}, {3, 5}, {10, 12}, {11, 13},
+    {1, 2}, {3, 4}, {5, 6}, {9, 10}, {11, 12}, {13, 14}, {0, 8}, {1, 9}, {2, 10}, {3, 11}, {4, 12}, {5, 13}, {6, 14}, {7, 15}, {4, 8}, {5, 9},
+    {6, 10}, {7, 11}, {2, 4}, {3, 5}, {6, 8}, {7, 9}, {10, 12}, {11, 13}, {1, 2}, {3, 4}, {5, 6}, {7, 8}, {9, 10}, {11, 12}, {13, 14}};
+
+// the lane's keys in ascending order (all k locations reduced here, once); a lane that is not `real` computes nothing
+template <int MODE, uint32_t N>
+__device__ __forceinline__ void gather_sorted_keys(const ProbeDesc &d, uint64_t h0, uint64_t h1, uint64_t h2, uint64_t h3, uint32_t k, bool real,
+                                                   uint32_t (&key)[N])
+{
+    // (k passes through an empty asm here: its comparisons with 0 .. N - 1 are otherwise hoisted out of the term-word loop as N
+    // lane masks that stay live in 2 N SGPRs, and the kernel leaves the 8-waves-per-SIMD register budget)
+    asm volatile("" : "+s"(k));
+#pragma unroll
+    for (uint32_t i = 0; i < N; ++i) {
+        key[i] = ~0u;
+        if (i < k && real) {                                             // (i < k: wave-uniform)
+            const uint32_t loc = (uint32_t)locate_c<MODE>(d, location(h0, h1, h2, h3, i));
+            key[i] = ((loc >> 10) << 14) | (i << 10) | (loc & 1023u);
+        }
+    }
+#pragma unroll
+    for (uint32_t e = 0; e < 63; ++e) {
+        const uint32_t lo = kGatherSortNet[e][0], hi = kGatherSortNet[e][1];
+        if (hi < N) {
+            const uint32_t x = key[lo], y = key[hi];
+            key[lo] = min(x, y);
+            key[hi] = max(x, y);
+        }
+    }
+}
+
+// gather_phase over the sorted keys: positions I0 .. I0 + L - 1 are compile-time, so the keys stay in registers
+template <int MODE, uint32_t N, uint32_t I0, uint32_t L>
+__device__ __forceinline__ uint32_t gather_phase_sorted(const uint64_t *src, const uint32_t (&key)[N], bool on)
+{
+    uint32_t wd[L], sh[L];
+#pragma unroll
+    for (uint32_t v = 0; v < L; ++v) {
+        wd[v] = ~0u; sh[v] = 0u;
+        const uint32_t kv = key[I0 + v < N ? I0 + v : N - 1];
+        if (I0 + v < N && kv != ~0u && on) {                              // the phase is clipped at k: the keys from position k on are ~0
+            const uint32_t loc = ((kv >> 14) << 10) | (kv & 1023u);       // always < d.m: the word lies inside the filter
+            sh[v] = loc;
+            wd[v] = gather_load<MODE>(src, loc);
+        }
+    }
+    uint32_t set = 1u;
+#pragma unroll
+    for (uint32_t v = 0; v < L; ++v) set &= __builtin_amdgcn_ubfe(wd[v], sh[v], 1u);
+    return set;
+}
+
+// gather_phases over the sorted keys: the same phase lengths, alive rule, early leave and n_ran
+template <int MODE, uint32_t N, uint32_t I0, uint32_t L0, uint32_t... L>
+__device__ __forceinline__ uint32_t gather_phases_sorted(GatherPhases<L0, L...>, const uint64_t *src, const uint32_t (&key)[N], uint32_t k, bool real,
+                                                         uint32_t alive, uint32_t &n_ran)
+{
+    if constexpr (I0 >= N) return alive;
+    else {
+        if (I0 >= k) return alive;
+        if (I0 != 0 && __ballot(alive != 0u && real) == 0) return alive;
+        if (real && alive != 0u) n_ran += min(L0, k - I0);
+        alive &= gather_phase_sorted<MODE, N, I0, L0>(src, key, real && alive != 0u);
+        if constexpr (sizeof...(L) != 0) return gather_phases_sorted<MODE, N, I0 + L0>(GatherPhases<L...>{}, src, key, k, real, alive, n_ran);
+        else return gather_phases_sorted<MODE, N, I0 + L0>(GatherPhases<L0>{}, src, key, k, real, alive, n_ran);   // beyond the list: the last length again
+    }
+}
+
+template <int MODE, uint32_t N>
+__device__ __forceinline__ uint32_t gather_term_sorted(const ProbeDesc &d, const uint64_t *src, uint64_t h0, uint64_t h1, uint64_t h2, uint64_t h3,
+                                                       uint32_t k, bool real, uint32_t &n_ran)
+{
+    uint32_t key[N];
+    gather_sorted_keys<MODE, N>(d, h0, h1, h2, h3, k, real, key);
+    return gather_phases_sorted<MODE, N, 0u>(GatherSchedule{}, src, key, k, real, 1u, n_ran);
+}
+
 template <int MODE>
 __device__ __forceinline__ void gather_block(const ProbeArgs &a, const ProbeDesc &d, const uint64_t *src, uint32_t t0, uint32_t n_real,
                                              uint32_t n_tw, uint64_t *vout, uint32_t lane, uint64_t *ran)
 {
     const uint32_t k = d.k;
     uint32_t n_ran = 0;
+    // (wave-uniform) the 64-bit mode, k > 16 and filters beyond the key's line field keep the hash-index order
+    const bool sorted = BSG_GATHER_ORDER == 1 && MODE != kModBarrett64 && k <= kGatherOrderMaxK && d.m <= kGatherOrderMaxM;
     for (uint32_t w = 0; w < n_tw; ++w) {
         const uint32_t idx = w * 64 + lane;
         const bool real = idx < n_real;
         const uint64_t *th = a.th + (t0 + idx);                       // (the padded tail of the last word holds hashes too: Tp is a multiple of 64)
         const uint64_t h0 = th[0], h1 = th[a.Tp], h2 = th[2ull * a.Tp], h3 = th[3ull * a.Tp];
-        const uint32_t alive = gather_phases<MODE>(GatherSchedule{}, d, src, h0, h1, h2, h3, 0u, k, real, 1u, n_ran);
+        uint32_t alive;
+        if (!sorted)      alive = gather_phases<MODE>(GatherSchedule{}, d, src, h0, h1, h2, h3, 0u, k, real, 1u, n_ran);
+        else if (k <= kGatherOrderSmallK) alive = gather_term_sorted<MODE, kGatherOrderSmallK>(d, src, h0, h1, h2, h3, k, real, n_ran);
+        else              alive = gather_term_sorted<MODE, kGatherOrderMaxK>(d, src, h0, h1, h2, h3, k, real, n_ran);
         const uint64_t verdict = __ballot(alive != 0u || !real);
         if (lane == 0) vout[(uint64_t)w * 64] = verdict;
     }

@@ -6,15 +6,18 @@ arena (1 000 blocks x 10 000 rows, fpr 0.001) and batch, 20 arenas per dispatch 
     python tools/probe_gather_lab.py sweep [launches]     distinct terms per kind {3 .. 128}: gather vs stream, product and big_filters geometry
     python tools/probe_gather_lab.py pmc ROUTE [launches [arenas [cap]]]
                                                           launches of ONE route and nothing else (under rocprofv3 --pmc FETCH_SIZE / TCC_EA0_RDREQ_sum)
-    python tools/probe_gather_lab.py lines                no GPU: the EXACT number of distinct 128-byte lines the executed bit tests of the bench's batch touch
-                                                          per block of the bench's arena, and the tests executed, under every phase schedule of the gather kernel
+    python tools/probe_gather_lab.py lines [--order A,B,..]
+                                                          no GPU: the EXACT number of distinct 128-byte lines the executed bit tests of the bench's batch touch
+                                                          per block of the bench's arena (in all, and summed phase by phase), and the tests executed, under
+                                                          every phase schedule of the gather kernel and every order of a lane's k locations (ORDERS; default all)
     python tools/probe_gather_lab.py caps [rounds [arenas,.. [caps,..]]]
                                                           the gather route under bsg_set_lab key 28 = workgroups per CU (5 = no cap), the caps taking turns call by
                                                           call: kernel time (the dispatches' timestamps, summed) and call wall time, survivors left on the device
 
 ROUTE: stream (bsg_set_gather_cost(1 << 20)), block (cost 0, bsg_set_lab key 26 = 0: k_probe_terms' per-block gathered path), gather (cost 0).
 BSG_LAB_LIB=path loads another build of the library (the -DBSG_GATHER_* variants of csrc/kernels.hip.h).
-The numbers on record and the stop rule they are read by: profiles/probe_gather_lab.txt, profiles/probe_gather_lines_lab.txt.
+The numbers on record and the stop rules they are read by: profiles/probe_gather_lab.txt, profiles/probe_gather_lines_lab.txt,
+profiles/probe_gather_order_lab.txt.
 """
 import os
 import sys
@@ -104,12 +107,23 @@ def time_routes(ctx, arenas, bid, per_call, routes, launches, warm=3):
 
 
 SCHEDULES = ((4, 4, 2), (2, 8), (2, 2, 6), (4, 6), (1, 3, 6), (10,))
+ORDERS = ("index", "line", "zones", "count_zone", "count_line")
 
 
-def touched_lines(words, desc, h, kinds, schedules):
-    """The gather kernel's loads, restated: words / desc of one arena, h [T][4] base hashes, kinds [T] -> {schedule: (tests executed per block,
-    distinct 128-byte lines per block)}.  A lane runs a phase iff every bit of its earlier phases was set; the last length repeats beyond the list."""
-    B, T = len(desc) // 3, len(h)
+def phase_of_position(sch, kmax):
+    """-> [kmax] the phase that takes the lane's j-th location under the schedule (the last length repeats beyond the list)"""
+    ph, at, p = np.zeros(kmax, dtype=np.int64), 0, 0
+    while at < kmax:
+        ph[at: at + sch[min(p, len(sch) - 1)]] = p
+        at += sch[min(p, len(sch) - 1)]
+        p += 1
+    return ph
+
+
+def gather_locations(words, desc, h, kinds):
+    """words / desc of one arena, h [T][4] base hashes, kinds [T] -> x [T][kmax] the raw locations, and per [B][T][kmax]: live (i < k of a
+    filter that is not nil), loc (x mod m), bit (the filter's bit there; True where not live), line (the 128-byte line of the arena)"""
+    B = len(desc) // 3
     d = desc.reshape(B, 3)
     m = d["m"][:, kinds].astype(np.uint64)                                # [B][T]
     k = d["k"][:, kinds].astype(np.int64)
@@ -121,20 +135,105 @@ def touched_lines(words, desc, h, kinds, schedules):
     live = (m > 0)[:, :, None] & (i[None, None, :] < k[:, :, None])
     loc = x[None, :, :] % np.maximum(m, 1)[:, :, None]                    # [B][T][k]
     bit = ((words[(base[:, :, None] + (loc >> np.uint64(6))).astype(np.int64)] >> (loc & np.uint64(63))) & np.uint64(1)).astype(bool) | ~live
-    line = (base[:, :, None] * np.uint64(8) + (loc >> np.uint64(3))) >> np.uint64(7)
-    passed = np.concatenate([np.ones((B, T, 1), dtype=bool), np.logical_and.accumulate(bit, axis=2)], axis=2)      # passed[.., j]: bits 0 .. j - 1 all set
+    line = ((base[:, :, None] * np.uint64(8) + (loc >> np.uint64(3))) >> np.uint64(7)).astype(np.int64)
+    return x, live, loc, bit, line, m, k
+
+
+def order_of(order, sch, live, loc, line, m, k):
+    """-> perm [B][T][kmax]: the hash index of the location a lane tests at position j.  Every order is a total order (ties by hash
+    index) and puts the positions beyond k last.
+      index       the hash index: the kernel as built with BSG_GATHER_ORDER=0
+      line        ascending 128-byte span of the filter (loc >> 10), ties by hash index: BSG_GATHER_ORDER=1
+      zones       the filter's address range cut in the proportions of the phase lengths (1,3,6: 10 % / 30 % / 60 %); a location wants the
+                  phase of its zone, a full phase spills into the next, an empty slot takes from the next zone: a stable sort by zone
+      count_zone  with the wave's count of locations per line (all lanes, all k): the locations on lines wanted more than once go, in line
+                  order, to the phase of their zone (the next free phase after it, else the latest free one before it); the others fill the latest free slots
+      count_line  the locations on lines wanted more than once first, in line order; the others after them in index order"""
+    B, T, kmax = loc.shape
+    idx = np.broadcast_to(np.arange(kmax), loc.shape)
+    dead = ~live
+    rel = (loc >> np.uint64(10)).astype(np.int64)                         # the 128-byte span of the filter (filters start on 16-byte boundaries: not quite the arena's line)
+    ph = phase_of_position(sch, kmax)
+    if order == "index":
+        return np.lexsort((idx, dead))
+    if order == "line":
+        return np.lexsort((idx, rel, dead))
+    kk = np.maximum(k, 1)[:, :, None]
+    zone = ph[np.minimum(loc.astype(np.int64) * kk // np.maximum(m, 1).astype(np.int64)[:, :, None], kk - 1)]
+    if order == "zones":
+        return np.lexsort((idx, zone, dead))
+    shared = np.zeros(loc.shape, dtype=bool)                              # the wave: the lanes (terms) of one block and kind share the filter
+    for b in range(B):
+        u, inv, cnt = np.unique(line[b][live[b]], return_inverse=True, return_counts=True)
+        shared[b][live[b]] = cnt[inv] > 1
+    if order == "count_line":
+        return np.lexsort((idx, np.where(shared, rel, 0), ~shared, dead))
+    assert order == "count_zone", order
+    perm = np.lexsort((idx, dead))
+    by_line = np.lexsort((idx, rel, dead))
+    n_ph = int(ph.max()) + 1
+    for b in range(B):
+        for t in range(T):
+            n = int(live[b, t].sum())
+            if n == 0:
+                continue
+            free = [[j for j in range(n) if ph[j] == p] for p in range(n_ph)]
+            out = [0] * n
+            for i in by_line[b, t, :n]:
+                if shared[b, t, i]:
+                    z = int(zone[b, t, i])
+                    p = next((q for q in range(z, n_ph) if free[q]), None)
+                    if p is None:
+                        p = next(q for q in range(z - 1, -1, -1) if free[q])
+                    out[free[p].pop(0)] = i
+            for i in range(n):
+                if not shared[b, t, i]:
+                    p = next(q for q in range(n_ph - 1, -1, -1) if free[q])
+                    out[free[p].pop()] = i
+            perm[b, t, :n] = out
+    return perm
+
+
+def phase_walk(sch, perm, live, bit, line):
+    """The kernel's phase walk over the locations in the order perm: a lane runs a phase iff every bit of its earlier phases was set.
+    -> ran [B][T][kmax] (by position), the lines by position, the phase of each position"""
+    kmax = perm.shape[2]
+    ph = phase_of_position(sch, kmax)
+    start = np.asarray([int(np.argmax(ph == ph[j])) for j in range(kmax)])
+    bit_p, live_p, line_p = (np.take_along_axis(a, perm, axis=2) for a in (bit, live, line))
+    passed = np.concatenate([np.ones(bit_p.shape[:2] + (1,), dtype=bool), np.logical_and.accumulate(bit_p, axis=2)], axis=2)   # [.., j]: bits 0 .. j - 1 all set
+    return passed[:, :, start] & live_p, line_p, ph
+
+
+def touched_lines(words, desc, h, kinds, schedules, orders=("index",)):
+    """The gather kernel's loads, restated -> {(order, schedule): (tests executed, distinct 128-byte lines, sum over the phases of the
+    phase's distinct lines), each per block}, the raw locations, the verdicts.  The distinct lines are the requests if every line a
+    later phase wants again is still in the L2, the per-phase sum if none is; duplicates inside a phase merge either way."""
+    x, live, loc, bit, line, m, k = gather_locations(words, desc, h, kinds)
+    B = live.shape[0]
     out = {}
-    for sch in schedules:
-        start, at = np.zeros(kmax, dtype=np.int64), 0
-        for p in range(kmax):
-            ln = sch[min(p, len(sch) - 1)]
-            start[at: at + ln] = at
-            at += ln
-            if at >= kmax:
-                break
-        ran = passed[:, :, start] & live
-        out[sch] = (ran.sum() / B, len(np.unique(line[ran])) / B)
-    return out, x, passed[:, :, kmax] | (m == 0)
+    for order in orders:
+        for sch in schedules:
+            ran, line_p, ph = phase_walk(sch, order_of(order, sch, live, loc, line, m, k), live, bit, line)
+            n_ph = int(ph.max()) + 1
+            out[(order, sch)] = (ran.sum() / B, len(np.unique(line_p[ran])) / B, len(np.unique((line_p * n_ph + ph[None, None, :])[ran])) / B)
+    return out, x, bit.all(axis=2)
+
+
+def lines_arena(B, rows):
+    """the bench's arena built by the CPU oracle -> words, desc.  BSG_LAB_CACHE=dir keeps it between runs, as c2_arenas does."""
+    from oracle import oracle as O
+    cache = os.environ.get("BSG_LAB_CACHE")
+    files = [os.path.join(cache, "lines_%d_%d_%s.npy" % (B, rows, n)) for n in ("words", "desc")] if cache else []
+    if cache and all(os.path.exists(f) for f in files):
+        return np.load(files[0]), np.load(files[1])
+    plan = plan_blocks(bench.generate_blocks(np.arange(B, dtype=np.int64), rows, 0xB100F5EA4C4, 16), 0.001)
+    words = O.build_many(plan.blob, plan.off, plan.fstart, plan.desc.view(O.DESC_DTYPE), plan.n_words)
+    if cache:
+        os.makedirs(cache, exist_ok=True)
+        np.save(files[0], words)
+        np.save(files[1], plan.desc)
+    return words, plan.desc
 
 
 def fmt(v):
@@ -157,22 +256,25 @@ def main():
     if mode == "lines":          # the CPU oracle alone: its filters, its hashes, its location arithmetic
         from oracle import oracle as O
         B, rows = 1000, 10000
-        plan = plan_blocks(bench.generate_blocks(np.arange(B, dtype=np.int64), rows, 0xB100F5EA4C4, 16), 0.001)
+        words, desc = lines_arena(B, rows)
         bench.stop_pool()
-        words = O.build_many(plan.blob, plan.off, plan.fstart, plan.desc.view(O.DESC_DTYPE), plan.n_words)
         cb = Q.compile_queries(synth.make_queries(4096, "c2", seed=1234))
         kinds = np.asarray(cb.arrays()[2], dtype=np.int64)
         h = np.asarray([O.base_hashes(s if isinstance(s, bytes) else s.encode()) for s in cb.term_strings], dtype=np.uint64)
-        res, x, verdict = touched_lines(words, plan.desc, h, kinds, SCHEDULES)
+        orders = ORDERS if "--order" not in sys.argv else tuple(sys.argv[sys.argv.index("--order") + 1].split(","))
+        assert all(o in ORDERS for o in orders), "--order takes a comma-separated list of %s" % (ORDERS,)
+        res, x, verdict = touched_lines(words, desc, h, kinds, SCHEDULES, orders)
         for t in range(len(h)):
             for i in range(x.shape[1]):
                 assert int(x[t, i]) == O.location(tuple(int(v) for v in h[t]), i)
-        d2 = plan.desc.reshape(B, 3)
+        d2 = desc.reshape(B, 3)
         n_present = int((verdict.mean(axis=0) > 0.5).sum())
         print("bench arena (%d blocks x %d rows, fpr 0.001) and batch (%d distinct terms, %d of them pass in most blocks, kinds %s); field::token filters of %.1f lines, k = %d"
               % (B, rows, len(h), n_present, sorted(set(kinds.tolist())), float(np.mean((d2["m"][:, 2] + 1023) // 1024)), int(d2["k"][:, 2].max())))
-        for sch, (tests, lines) in res.items():
-            print("  schedule %-10s tests executed per block %6.1f   distinct lines touched per block %6.1f" % (",".join(map(str, sch)), tests, lines))
+        print("per block: tests executed / distinct lines touched (requests if every cross-phase reuse hits) / sum of the phases' distinct lines (if none hits) / midpoint")
+        for (order, sch), (tests, lines, per_phase) in res.items():
+            print("  order %-10s schedule %-8s tests %6.1f   distinct lines %6.1f   per-phase sum %6.1f   midpoint %6.1f"
+                  % (order, ",".join(map(str, sch)), tests, lines, per_phase, (lines + per_phase) / 2), flush=True)
         return
     print("library %s" % _lib.LIB_PATH, flush=True)
     ctx = Context((0,))

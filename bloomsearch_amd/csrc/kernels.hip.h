@@ -1227,7 +1227,8 @@ struct EvalArgs {
     uint32_t max_cw;             // max words of any chunk (LDS carve + cw stride)
     uint32_t Lmax;               // max program length of any chunk (prog stride)
     uint32_t identity_cw;        // bit 0: every chunk uses words 0..max_cw-1 in order (small batches): no list to load; bit 1 (k_eval_programs
-                                 // only): take eval_role_all — the launch's LDS holds the transposed words of a whole tile
+                                 // only): take eval_role_all — the launch's LDS holds the transposed words of a whole tile; bit 2 (with
+                                 // bit 1): take eval_role_rows — the launch's tile is kEvalRowSpan and its LDS eval_rows_lds_bytes
     uint32_t n_arenas;
     uint32_t max_G;              // most 64-block groups of any arena of the launch
 };
@@ -1246,6 +1247,15 @@ constexpr uint32_t kEvalGroupTile = BSG_EVAL_GROUP_TILE;   // block groups one e
 // rows per lane): 44.5 / 77.5.  Of the 35.7 us the survivor stores are 17 (33 MB as 32-byte pieces of 128-byte rows) and the
 // programs 8; of the 55.9 us of the C4 batch the 15-op programs are 26.  Non-temporal stores for the survivors: 110 / 117 us
 // (four workgroups complete every 128-byte row at different times; only a write-back L2 can merge them).
+
+// Lab builds only (tools/eval_rows_lab.py): what eval_role_all / eval_role_rows cost without their survivor stores
+// (-DBSG_LAB_EVAL_NO_STORES: a store stays in the code behind a value test that never holds, so that nothing in front of it is
+// dropped) and without their verdict loads and transposes (-DBSG_LAB_EVAL_NO_VERDICTS: the programs run on whatever the LDS holds).
+#ifdef BSG_LAB_EVAL_NO_STORES
+#define BSG_LAB_EVAL_KEEP_STORE(x) ((x) == 0x9E3779B97F4A7C15ULL)
+#else
+#define BSG_LAB_EVAL_KEEP_STORE(x) true
+#endif
 
 // Evaluates chunk c (256 queries) against block groups [g0, g0 + gt) with the 256 threads htid = 0..255
 // of one "half" (a whole k_eval_programs workgroup, or half of a fused workgroup).  The program words
@@ -1366,6 +1376,7 @@ __device__ __forceinline__ void eval_role_all(const EvalArgs &a, const ArenaRef 
     // every row this wave transposes, requested before the first transpose starts
     constexpr uint32_t kRows = 4;                                                // rows per wave per trip
     const uint32_t n_rows = gt * ncw;
+#ifndef BSG_LAB_EVAL_NO_VERDICTS
     for (uint32_t r0 = wave; r0 < n_rows; r0 += n_waves * kRows) {
         uint64_t x[kRows];
 #pragma unroll
@@ -1383,6 +1394,7 @@ __device__ __forceinline__ void eval_role_all(const EvalArgs &a, const ArenaRef 
             if (idx < n_rows) VT[(uint64_t)idx * 64 + lane] = wave_transpose64(x[u], (int)lane);
         }
     }
+#endif
     __syncthreads();
     const uint32_t q = c * kEvalThreads + tid;
     // every op is decoded ONCE and applied to the masks of all the tile's groups (the groups past gt hold zeros: harmless)
@@ -1439,7 +1451,163 @@ __device__ __forceinline__ void eval_role_all(const EvalArgs &a, const ArenaRef 
     if (q < a.n_queries) {
         uint64_t *dst = a.out + ar.out_off(a.n_queries) + (uint64_t)q * ar.G() + g0;
 #pragma unroll
-        for (uint32_t tt = 0; tt < TILE; ++tt) if (tt < gt) dst[tt] = res[tt];
+        for (uint32_t tt = 0; tt < TILE; ++tt) if (tt < gt && BSG_LAB_EVAL_KEEP_STORE(res[tt])) dst[tt] = res[tt];
+    }
+}
+
+// The row-span body: the same batches as eval_role_all (identity word list), for launches of many groups.  A workgroup owns chunk c
+// x one arena x a SPAN of up to S consecutive 64-block groups [g0, g0 + gt): the program words are fetched once per span instead
+// of once per kEvalGroupTile groups, all gt x ncw verdict rows are requested before the first transpose and parked behind one
+// barrier, and the programs run over the span in sub-tiles of kEvalGroupTile masks (the LDS stack keeps eval_role_all's size), a
+// lane's gt survivor words staying in registers.  They do not leave from there: a lane holding its query's gt words would store 16
+// bytes at a stride of G() x 8, one line per lane and instruction.  Behind a second barrier (nobody reads the transposed words or the
+// stacks any more) the words go to an LDS stage [256 rows][S + 1 words] laid OVER them (the odd pitch keeps the 64-bit writes of
+// neighbouring lanes off each other's banks), and behind a third the workgroup writes the stage out in 16-byte slots at even word
+// addresses, consecutive lanes taking consecutive slots of a query's gt x 8-byte segment and then the next query's: a wave
+// instruction covers whole segments, and where gt == G() (an arena of at most S groups) one contiguous kilobyte of the chunk's
+// output.  A slot that reaches over an end of its segment (an odd first address: G() or out_off odd) stores the one word that is
+// inside, so nothing beyond a row's gt words, and nothing beyond n_queries x G(), is ever written.  Same bits as eval_role_all:
+// out_off + q * G() + g, the tail mask on the arena's last group, nil program = all ones.
+// LDS: eval_rows_lds_bytes.  (Measured: profiles/eval_rows_lab.txt.)
+#ifndef BSG_EVAL_ROW_SPAN
+#define BSG_EVAL_ROW_SPAN 8
+#endif
+constexpr uint32_t kEvalRowSpan = BSG_EVAL_ROW_SPAN;       // S: 8 (64-byte segments: two workgroups share a 1 000-block arena's lines) or 16 (whole lines)
+static_assert(kEvalRowSpan % kEvalGroupTile == 0 && kEvalRowSpan >= kEvalGroupTile && kEvalRowSpan <= 16, "a span is whole sub-tiles, at most two lines");
+__host__ __device__ inline uint32_t eval_rows_lds_bytes(uint32_t max_cw, uint32_t max_depth)
+{
+    const uint32_t work = kEvalRowSpan * max_cw * 64u + max_depth * kEvalGroupTile * (uint32_t)kEvalThreads;   // transposed words + stacks
+    const uint32_t stage = (uint32_t)kEvalThreads * (kEvalRowSpan + 1u);
+    return (work > stage ? work : stage) * 8u;
+}
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+
+template <uint32_t S>
+__device__ __forceinline__ void eval_role_rows(const EvalArgs &a, const ArenaRef &ar, uint32_t g0, uint32_t gt, uint32_t c, uint32_t tid, uint64_t *lds)
+{
+    constexpr uint32_t TILE = kEvalGroupTile, PITCH = S + 1;
+    const uint64_t *V = a.V + ar.v_off(a.Wt);
+    const uint32_t lane = tid & (kWave - 1);
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+    constexpr uint32_t n_waves = kEvalThreads / kWave;
+    const uint32_t ncw = a.max_cw;
+    uint64_t *VT = lds;                                                // VT[(t * ncw + s) * 64 + bit], t < gt
+    uint64_t *stk = lds + (uint64_t)S * ncw * 64 + tid;                // per-lane stack of TILE-mask entries, stride kEvalThreads
+    constexpr uint32_t kPre = 8;
+    uint32_t pre[kPre];
+    const uint32_t *P = a.prog + (uint64_t)c * a.Lmax * kEvalThreads + tid;
+#pragma unroll
+    for (uint32_t j = 0; j < kPre; ++j) pre[j] = j < a.Lmax ? P[(uint64_t)j * kEvalThreads] : (7u << 28);
+    const uint32_t len = a.chunk_len[c];
+    constexpr uint32_t kRows = 4;                                      // rows per wave per trip (see eval_role_all)
+    const uint32_t n_rows = gt * ncw;
+#ifndef BSG_LAB_EVAL_NO_VERDICTS
+    for (uint32_t r0 = wave; r0 < n_rows; r0 += n_waves * kRows) {
+        uint64_t x[kRows];
+#pragma unroll
+        for (uint32_t u = 0; u < kRows; ++u) {
+            const uint32_t idx = r0 + u * n_waves;
+            x[u] = 0ULL;
+            if (idx < n_rows) {
+                const uint32_t tt = idx / ncw, s = idx - tt * ncw, g = g0 + tt;
+                if (g * 64u + lane < ar.n_blocks) x[u] = V[((uint64_t)g * a.Wt + s) * 64 + lane];
+            }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kRows; ++u) {
+            const uint32_t idx = r0 + u * n_waves;
+            if (idx < n_rows) VT[(uint64_t)idx * 64 + lane] = wave_transpose64(x[u], (int)lane);
+        }
+    }
+#endif
+    __syncthreads();
+    const uint32_t gstride = ncw * 64;
+    uint64_t row[S];                                                   // this lane's query: the span's survivor words
+#pragma unroll
+    for (uint32_t t0 = 0; t0 < S; t0 += TILE) {
+        if (t0 < gt) {   // workgroup-uniform
+            const uint32_t nt = min(TILE, gt - t0);
+            const uint64_t *VTs = VT + (uint64_t)t0 * gstride;
+            uint64_t res[TILE];
+#pragma unroll
+            for (uint32_t tt = 0; tt < TILE; ++tt) res[tt] = ~0ULL;    // empty program == nil query == true
+            uint32_t sp = 0;
+            auto step = [&](uint32_t op) {                            // (eval_role_all's, on the sub-tile's masks)
+                const uint32_t opc = op >> 28;
+                if (opc == 7u) return;
+                if (opc == 1u || opc == 2u) {
+                    --sp;
+                    const uint64_t *u = stk + (uint64_t)(sp - 1) * TILE * kEvalThreads;
+#pragma unroll
+                    for (uint32_t tt = 0; tt < TILE; ++tt) {
+                        const uint64_t under = u[(uint64_t)tt * kEvalThreads];
+                        res[tt] = (opc == 1u) ? (under & res[tt]) : (under | res[tt]);
+                    }
+                } else {
+                    if (sp > 0) {
+                        uint64_t *u = stk + (uint64_t)(sp - 1) * TILE * kEvalThreads;
+#pragma unroll
+                        for (uint32_t tt = 0; tt < TILE; ++tt) u[(uint64_t)tt * kEvalThreads] = res[tt];
+                    }
+                    ++sp;
+                    if (opc == 0u) {
+                        const uint64_t *vt = VTs + (op & 0x0FFFFFFFu);
+#pragma unroll
+                        for (uint32_t tt = 0; tt < TILE; ++tt) res[tt] = tt < nt ? vt[(uint64_t)tt * gstride] : 0ULL;
+                    } else {
+                        const uint64_t v = opc == 3u ? ~0ULL : 0ULL;
+#pragma unroll
+                        for (uint32_t tt = 0; tt < TILE; ++tt) res[tt] = v;
+                    }
+                }
+            };
+#pragma unroll
+            for (uint32_t j = 0; j < kPre; ++j) if (j < len) step(pre[j]);
+            for (uint32_t j0 = kPre; j0 < len; j0 += kPre) {        // (the next kPre op words together: see eval_role)
+                uint32_t more[kPre];
+#pragma unroll
+                for (uint32_t u = 0; u < kPre; ++u) more[u] = j0 + u < len ? P[(uint64_t)(j0 + u) * kEvalThreads] : (7u << 28);
+#pragma unroll
+                for (uint32_t u = 0; u < kPre; ++u) if (j0 + u < len) step(more[u]);
+            }
+#pragma unroll
+            for (uint32_t tt = 0; tt < TILE; ++tt) {
+                uint64_t m = ~0ULL;
+                if (tt < nt) {
+                    const uint32_t nvalid = ar.n_blocks - (g0 + t0 + tt) * 64u;
+                    if (nvalid < 64) m = (1ULL << nvalid) - 1;
+                }
+                row[t0 + tt] = res[tt] & m;
+            }
+        }
+    }
+    __syncthreads();                                                   // the stage lies over the transposed words and the stacks
+    uint64_t *stage = lds;
+#pragma unroll
+    for (uint32_t t = 0; t < S; ++t) if (t < gt) stage[(uint64_t)tid * PITCH + t] = row[t];
+    __syncthreads();
+    const uint32_t G = ar.G();
+    const uint32_t nq = min((uint32_t)kEvalThreads, a.n_queries - c * kEvalThreads);       // rows of this chunk that exist
+    uint64_t *row0 = a.out + ar.out_off(a.n_queries) + (uint64_t)c * kEvalThreads * G + g0;  // row r's segment: [row0 + r * G, + gt)
+    // slots of two words at even word ADDRESSES (16-byte aligned whatever out_off, G and the caller's buffer are): p = 1 where a
+    // segment starts at an odd one.  G even: every row of the span has row 0's p; G odd: p alternates, and a row takes gt / 2 + 1 slots
+    const uint32_t p0 = (uint32_t)(reinterpret_cast<uintptr_t>(row0) >> 3) & 1u;
+    const uint32_t n_slots = (G & 1u) ? gt / 2 + 1 : (p0 + gt + 1) / 2;
+    for (uint32_t i = tid; i < nq * n_slots; i += kEvalThreads) {
+        const uint32_t r = i / n_slots, j = i - r * n_slots;
+        const uint32_t p = (G & 1u) ? (p0 ^ (r & 1u)) : p0;
+        const uint32_t k1 = 2 * j + 1 - p;                             // the slot's SECOND word within the segment (its first: k1 - 1, outside where k1 == 0)
+        const uint64_t *s = stage + (uint64_t)r * PITCH;
+        uint64_t *dst = row0 + (uint64_t)r * G + k1;
+        const bool lo = k1 >= 1 && k1 - 1 < gt, hi = k1 < gt;
+        if (lo && hi) {
+            const u64x2 v = {s[k1 - 1], s[k1]};
+            if (BSG_LAB_EVAL_KEEP_STORE(v.x)) *reinterpret_cast<u64x2 *>(dst - 1) = v;
+        } else if (lo) {
+            if (BSG_LAB_EVAL_KEEP_STORE(s[k1 - 1])) dst[-1] = s[k1 - 1];
+        } else if (hi) {
+            if (BSG_LAB_EVAL_KEEP_STORE(s[k1])) dst[0] = s[k1];
+        }
     }
 }
 
@@ -1449,6 +1617,8 @@ __device__ __forceinline__ void eval_role_all(const EvalArgs &a, const ArenaRef 
 // 32-byte pieces of every 128-byte row left four different L2s as four partial-line writes.  Here the nx workgroups of one
 // (chunk, arena) are 8 apart in the block numbering: same XCD, dispatched within 8 nx blocks of each other, so the row is
 // whole in one L2 before it is written back.  (A speed affinity only: any placement gives the same bits.)
+// Row spans (eval_role_rows, tile = kEvalRowSpan): nx = ceil(max_G / kEvalRowSpan).  With spans of 8 groups two workgroups still
+// share every line of a 16-group arena and the numbering does its work; with spans of 16 a line has one writer and it is idle.
 __host__ __device__ inline uint32_t eval_grid_blocks(uint32_t nx, uint32_t n_chunks, uint32_t n_arenas)
 {
     return (n_chunks * n_arenas + 7u) / 8u * 8u * nx;
@@ -1465,7 +1635,8 @@ __device__ __forceinline__ void eval_block(const EvalArgs &a, const ArenaRef &ar
 {
     const uint32_t g0 = tx * tile;
     if (g0 >= ar.G()) return;
-    if (a.identity_cw & 2u) {
+    if (a.identity_cw & 4u) eval_role_rows<kEvalRowSpan>(a, ar, g0, min(tile, ar.G() - g0), c, threadIdx.x, lds64);   // (tile == kEvalRowSpan)
+    else if (a.identity_cw & 2u) {
         if (tile == 2u) eval_role_all<2>(a, ar, g0, min(tile, ar.G() - g0), c, threadIdx.x, lds64);
         else eval_role_all<kEvalGroupTile>(a, ar, g0, min(tile, ar.G() - g0), c, threadIdx.x, lds64);
     }

@@ -634,11 +634,21 @@ int32_t enqueue_direct(Device &d, const Group &g, const BatchDev &bd, const Batc
 
 // LDS of an evaluation workgroup (eval_block); sets the bit of a.identity_cw that selects eval_role_all:
 // batches with the identity word list transpose a whole tile's words at once (eval_role_all) when that fits 64 KB of LDS
-uint32_t eval_lds_for(const Batch &B, bsg::EvalArgs &a)
+// Launches tiled by kEvalGroupTile (eval_tile_for: many groups) take row spans instead (eval_role_rows) where a span's transposed
+// words and stacks, or its stage, fit lds_cap: `tile` becomes kEvalRowSpan and the bit that selects the body is set.  Deep programs
+// and batches of many words keep eval_role_all.  lds_cap: 64 KB for the evaluation's own kernels; k_gather_fused passes what keeps
+// three of its workgroups on a CU (the gather loses from two: profiles/probe_gather_lines_lab.txt §4).
+uint32_t eval_lds_for(const Batch &B, bsg::EvalArgs &a, uint32_t &tile, uint32_t lds_cap = 64 * 1024)
 {
     static const bool lab_serial = getenv("BSG_LAB_EVAL_SERIAL") != nullptr;   // lab only: the per-group walk for every batch
+    static const char *lab_rows = getenv("BSG_LAB_EVAL_ROWS");                 // lab only: "0" = eval_role_all where the row spans would run
     if (B.identity_cw && !lab_serial && bsg::eval_lds_bytes(B.max_cw * bsg::kEvalGroupTile, B.max_depth * bsg::kEvalGroupTile) <= 64 * 1024) {
         a.identity_cw |= 2u;
+        if (tile == bsg::kEvalGroupTile && !(lab_rows && atoi(lab_rows) == 0) && bsg::eval_rows_lds_bytes(B.max_cw, B.max_depth) <= lds_cap) {
+            a.identity_cw |= 4u;
+            tile = bsg::kEvalRowSpan;
+            return bsg::eval_rows_lds_bytes(B.max_cw, B.max_depth);
+        }
         return bsg::eval_lds_bytes(B.max_cw * bsg::kEvalGroupTile, B.max_depth * bsg::kEvalGroupTile);
     }
     return bsg::eval_lds_bytes(B.max_cw, B.max_depth);
@@ -654,13 +664,13 @@ int32_t enqueue_eval(Device &d, const Group &g, const BatchDev &bd, const Batch 
     if (int32_t rc = make_eval_args(d, g, bd, B, slot, a)) return rc;
     if (out_override) a.out = out_override;
     const hipStream_t stream = on ? on : d.stream;
-    const uint32_t tile = eval_tile_for(g);
+    uint32_t tile = eval_tile_for(g);
     bsg::ArenaTable<bsg::kMaxGroupArenas> t;
     const bsg::ArenaRef *ext = nullptr;
     if (ext_at) ext = ext_at;
     else if (g.shards.size() <= bsg::kMaxGroupArenas) fill_refs(g, t.ar);
     else ext = d.ext_of_slot[slot];         // written (or found in the device's table cache) by this group's probe dispatch (enqueue_terms), same slot, same stream
-    const uint32_t lds = eval_lds_for(B, a);
+    const uint32_t lds = eval_lds_for(B, a, tile);        // (row spans: tile becomes the span)
     const uint32_t nx = (g.max_G + tile - 1) / tile;
     const uint64_t n_wg = (uint64_t)(B.n_chunks * (uint64_t)a.n_arenas + 7) / 8 * 8 * nx;
     if (n_wg > 0x7FFFFFFFull) return fail(BSG_E_UNSUPPORTED, "evaluation launch of %llu workgroups", (unsigned long long)n_wg);
@@ -750,7 +760,8 @@ int32_t enqueue_gather_fused(bsg_ctx *ctx, Device &d, const Group &gc, uint32_t 
     uint32_t lds = 0;
     if (int32_t rc = make_probe_args(ctx, d, gc, bd, B, slot, ev, f.p, lds)) return rc;
     if (int32_t rc = make_eval_args(d, ec, bd, B, slot, f.e)) return rc;
-    lds = std::max(eval_lds_for(B, f.e), gather_pad(ctx));     // (the pad is per workgroup, so it caps the evaluation workgroups of this dispatch too)
+    // (the pad is per workgroup, so it caps the evaluation workgroups of this dispatch too; row spans only where three workgroups keep a CU)
+    lds = std::max(eval_lds_for(B, f.e, tile, bsh::gather_lds_pad(3)), gather_pad(ctx));
     f.a0 = a0; f.e0 = e0;
     f.spread = spread ? 1u : 0u;
     f.n_kinds = B.n_kinds;

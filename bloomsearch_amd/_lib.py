@@ -25,6 +25,14 @@ OP_TERM, OP_AND, OP_OR, OP_TRUE, OP_FALSE = 0, 1, 2, 3, 4
 PROBE_ASYNC, PROBE_TIMED, PROBE_NOFUSE, PROBE_ROWS_PACKED = 1, 2, 4, 8
 INGEST_TRUSTED_JSON = 1
 MINMAX_MAX_FIELDS, MINMAX_MAX_NAME = 8, 64      # bsg_ingest_rows_minmax / bsg_ingest_open_minmax
+HIST_MAX_BUCKETS = 1024                         # bsg_match_rows_wide_hist
+
+
+def HIST_SLOTS(n_buckets: int) -> int:
+    """BSG_HIST_SLOTS: [0, B) the buckets, B below, B + 1 above, B + 2 missing"""
+    return n_buckets + 3
+
+
 PARTITION_MAX_NAME, PARTITION_MAX_KEY, PARTITION_PENDING_SLOTS, PARTITION_MAX_SETS = 64, 128, 256, 1 << 20      # bsg_ingest_open_keyed
 SET_UNDECIDED = 0xFFFFFFFF                      # out_set_of_row of bsg_ingest_append_rows_keyed: the partitioner handed the row back
 LAB_PARTITION_HASH_MASK = 29                    # bsg_set_lab key: 1 = the partition dictionary's hash keeps its low 2 bits
@@ -105,7 +113,7 @@ EXPORTS = [
     "bsg_ingest_rows_minmax", "bsg_ingest_open_minmax", "bsg_ingest_minmax", "bsg_last_minmax_ms",
     "bsg_ingest_open_keyed", "bsg_ingest_append_rows_keyed", "bsg_ingest_add_sets_keyed", "bsg_ingest_keys", "bsg_last_partition_ms",
     "bsg_sections_size", "bsg_build_sections", "bsg_last_encode_ms",
-    "bsg_match_rows", "bsg_match_rows_regex", "bsg_match_rows_tok", "bsg_match_rows_substr", "bsg_match_rows_range", "bsg_match_rows_many_range", "bsg_match_rows_regex_substr", "bsg_match_rows_regex_substr_range", "bsg_match_rows_many_regex_substr_range", "bsg_match_rows_many", "bsg_match_rows_many_substr", "bsg_match_rows_many_regex_substr", "bsg_match_rows_many_regex", "bsg_match_rows_wide", "bsg_match_wide_size", "bsg_match_rows_wide_rows", "bsg_match_rows_wide_substr", "bsg_match_rows_wide_substr_rows", "bsg_match_rows_wide_range", "bsg_match_rows_wide_range_rows", "bsg_match_rows_wide_regex_substr_range", "bsg_match_rows_wide_regex_substr_range_rows", "bsg_match_pair_rows_list", "bsg_match_rows_lookup", "bsg_match_rows_lookup_rows", "bsg_match_rows_lookup_regex", "bsg_match_rows_lookup_regex_rows", "bsg_last_match_ms", "bsg_pinned_alloc", "bsg_pinned_free", "bsg_host_register", "bsg_host_unregister",
+    "bsg_match_rows", "bsg_match_rows_regex", "bsg_match_rows_tok", "bsg_match_rows_substr", "bsg_match_rows_range", "bsg_match_rows_many_range", "bsg_match_rows_regex_substr", "bsg_match_rows_regex_substr_range", "bsg_match_rows_many_regex_substr_range", "bsg_match_rows_many", "bsg_match_rows_many_substr", "bsg_match_rows_many_regex_substr", "bsg_match_rows_many_regex", "bsg_match_rows_wide", "bsg_match_wide_size", "bsg_match_rows_wide_rows", "bsg_match_rows_wide_substr", "bsg_match_rows_wide_substr_rows", "bsg_match_rows_wide_range", "bsg_match_rows_wide_range_rows", "bsg_match_rows_wide_regex_substr_range", "bsg_match_rows_wide_regex_substr_range_rows", "bsg_match_rows_wide_hist", "bsg_last_hist_ms", "bsg_match_pair_rows_list", "bsg_match_rows_lookup", "bsg_match_rows_lookup_rows", "bsg_match_rows_lookup_regex", "bsg_match_rows_lookup_regex_rows", "bsg_last_match_ms", "bsg_pinned_alloc", "bsg_pinned_free", "bsg_host_register", "bsg_host_unregister",
 ]
 
 _lib = None
@@ -233,6 +241,9 @@ def load():
     L.bsg_match_rows_wide_range_rows.argtypes = L.bsg_match_rows_wide_rows.argtypes
     L.bsg_match_rows_wide_regex_substr_range.argtypes = L.bsg_match_rows_wide.argtypes
     L.bsg_match_rows_wide_regex_substr_range_rows.argtypes = L.bsg_match_rows_wide_rows.argtypes
+    # the parent's parameters up to and including tok, then field, field_len, origin, width, n_buckets, out_counts and the fallback list
+    L.bsg_match_rows_wide_hist.argtypes = L.bsg_match_rows_wide.argtypes[:16] + [vp, u32, C.c_int64, u64, u32, vp, vp, u32, C.POINTER(u32)]
+    L.bsg_last_hist_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.bsg_match_rows_lookup.argtypes = L.bsg_match_rows_wide.argtypes
     L.bsg_match_rows_lookup_rows.argtypes = L.bsg_match_rows_wide_rows.argtypes
     L.bsg_match_rows_lookup_regex.argtypes = L.bsg_match_rows_wide.argtypes

@@ -14,6 +14,7 @@
 #include "match.hip.h"
 #include "match_lookup.hip.h"
 #include "minmax.hip.h"
+#include "hist.hip.h"
 #include "partition.hip.h"
 #include <optional>
 #include <tuple>
@@ -497,7 +498,7 @@ struct bsg_ctx {
     uint32_t union_coarsen = 0;                // lab: the partitioned union starts with 2^this x too few partitions (bsg_set_lab key 10)
     uint32_t union_mode = 0;                   // file-level union: 0 = partitions in LDS (k_union_partitions), 1 = global hash tables (bsg_set_lab key 9)
     // device time of the most recent call of each family: the slowest device that took part (bsg_last_*_ms)
-    float last_build_ms = 0.f, last_hash_ms = 0.f, last_decode_ms = 0.f, last_or_ms = 0.f, last_encode_ms = 0.f, last_match_ms = 0.f, last_minmax_ms = 0.f, last_partition_ms = 0.f;
+    float last_build_ms = 0.f, last_hash_ms = 0.f, last_decode_ms = 0.f, last_or_ms = 0.f, last_encode_ms = 0.f, last_match_ms = 0.f, last_minmax_ms = 0.f, last_partition_ms = 0.f, last_hist_ms = 0.f;
 };
 
 namespace {

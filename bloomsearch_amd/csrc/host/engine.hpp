@@ -120,6 +120,12 @@ struct EngineConfig {           // BloomSearchEngineConfig (engine.go:82-147), t
     // ONE bsg_match_rows_lookup_regex(_rows) call; it closes at 16 regex conditions, at more than 4 of them on one leaf, and where
     // their tables pass what the group's strings and pairs (by their upper bounds) leave of the walker's LDS
     bool device_match_lookup_regex = false;
+    // true (with device_match and one of device_match_wide / device_match_wide_rows): in query_many the queries that carry a histogram
+    // spec form wide groups of their own, one family of groups per distinct spec, closed by the wide groups' rules; each group is
+    // decided by ONE bsg_match_rows_wide_hist call, the per-set counts summed per query on the host, the rows it hands back matched and
+    // bucketed on the host.  BSG_E_UNSUPPORTED (and every query outside a group) takes the host route: matched as before, bucketed by
+    // hist_row_slot.  Off by default; query() always takes the host route.
+    bool device_match_histogram = false;
     // Tokenizer (engine.go:83, "for both indexing and verification"), restricted to the separator family
     // strings.FieldsFunc(lower ? strings.ToLower(v) : v, isSep) (text.hpp Tokenizer): indexRow, the host matcher and the
     // device calls (bsg_ingest_rows_tok / bsg_match_rows_tok) all use it.  Default: BasicWhitespaceLowerTokenizer.
@@ -162,7 +168,17 @@ struct BlockStats {                      // query_exec.go:63-72
     bool bloom_filter_skipped = false;
 };
 
+// "Histogram" of a query: the bucket spec of bsg_match_rows_wide_hist (field 1 to 64 bytes, width >= 1, 1 to 1 024 buckets)
+struct HistSpec {
+    std::string field;
+    int64_t origin = 0;
+    uint64_t width = 1;
+    uint32_t buckets = 1;
+    bool operator<(const HistSpec &o) const { return std::tie(field, origin, width, buckets) < std::tie(o.field, o.origin, o.width, o.buckets); }
+};
+
 struct QueryResult {
+    std::vector<uint64_t> hist;          // buckets + 3 counts where the device route decided a histogram query (rows is then empty)
     std::vector<std::string> rows;
     std::vector<BlockStats> block_stats;
     std::vector<std::string> errors;     // per-block failures joined into Results.Err by the reference
@@ -188,6 +204,10 @@ public:
         if (c.device_match_range_text_wide && !(c.device_match && c.device_match_range_text &&
                                                 (c.device_match_wide || c.device_match_wide_rows || c.device_match_lookup || c.device_match_lookup_rows))) {
             err = "DeviceMatchRangeTextWide needs DeviceMatch, DeviceMatchRangeText and one of DeviceMatchWide, DeviceMatchWideRows, DeviceMatchLookup, DeviceMatchLookupRows";
+            return kErrInvalidConfig;
+        }
+        if (c.device_match_histogram && !(c.device_match && (c.device_match_wide || c.device_match_wide_rows))) {
+            err = "DeviceMatchHistogram needs DeviceMatch and one of DeviceMatchWide, DeviceMatchWideRows";
             return kErrInvalidConfig;
         }
         if (!c.minmax_indexes.empty() && !MinMaxFieldNames::check(c.minmax_indexes, err)) { err = "MinMaxIndexes: " + err; return kErrInvalidConfig; }
@@ -516,7 +536,8 @@ public:
     // DeviceMatchRangeTextWide as well: the mixed group is a wide group and makes ONE bsg_match_rows_wide_regex_substr_range(_rows) call.
     int32_t query_many(const std::vector<const BloomExpression *> &exprs, const std::vector<const RegexExpression *> &regexes,
                        std::vector<QueryResult> &results, const std::vector<const SubstringExpression *> *subs = nullptr,
-                       const std::vector<const RangeExpression *> *ranges = nullptr, const std::vector<const PrefilterExpression *> *prefilters = nullptr)
+                       const std::vector<const RangeExpression *> *ranges = nullptr, const std::vector<const PrefilterExpression *> *prefilters = nullptr,
+                       const std::vector<const HistSpec *> *hists = nullptr)
     {
         // every query has its own prefilter mask on its survivors: a block no query of the batch keeps is never walked
         auto prefilter_of = [&](size_t i) { return prefilters && i < prefilters->size() ? (*prefilters)[i] : nullptr; };
@@ -612,10 +633,32 @@ public:
         matchers.reserve(Q);
         for (size_t k = 0; k < Q; ++k) matchers.emplace_back(batch[k], cfg_.tokenizer);
         std::vector<uint8_t> on_device(Q, 0);
-        if (cfg_.device_match && !scan.empty())
-            if (int32_t rc = match_rows_device_many(batch, live_regex, live_sub, live_range, scan, set_first, set_wants, matchers, regex_dfas, sub_matchers, range_matchers, hit, on_device)) return rc;
+        // DeviceMatchHistogram: the queries with a histogram spec leave the batch's groups and form groups of their own per distinct spec
+        std::vector<std::vector<uint64_t>> hist_counts(Q);
+        std::vector<uint8_t> counted(Q, 0);                          // the device route decided query k's histogram
+        if (cfg_.device_match && !scan.empty()) {
+            std::vector<size_t> plain;
+            std::map<HistSpec, std::vector<size_t>> by_spec;
+            for (size_t k = 0; k < Q; ++k) {
+                const HistSpec *hs = cfg_.device_match_histogram && hists && live[k] < hists->size() ? (*hists)[live[k]] : nullptr;
+                if (hs) by_spec[*hs].push_back(k); else plain.push_back(k);
+            }
+            if (!plain.empty())
+                if (int32_t rc = match_rows_device_many(batch, live_regex, live_sub, live_range, scan, set_first, set_wants, matchers, regex_dfas, sub_matchers, range_matchers, hit, on_device, plain)) return rc;
+            for (const auto &kv : by_spec) {
+                for (size_t k : kv.second) hist_counts[k].assign((size_t)kv.first.buckets + 3, 0);
+                if (int32_t rc = match_rows_device_many(batch, live_regex, live_sub, live_range, scan, set_first, set_wants, matchers, regex_dfas, sub_matchers, range_matchers, hit, on_device, kv.second,
+                                                        &kv.first, &hist_counts)) return rc;
+                for (size_t k : kv.second) counted[k] = on_device[k];
+            }
+        }
         for (size_t k = 0; k < Q; ++k) {
             QueryResult &out = results[live[k]];
+            if (counted[k]) {                                        // its rows were never listed: the counts are the answer
+                out.hist = std::move(hist_counts[k]);
+                add_scan_time(t_scan, scanned[k], out);
+                continue;
+            }
             // not decided in a group (alone beyond a limit, or the library refused the group): per query, as before.  query() probes
             // again and rewrites the stats block_stage_stats left here: known, and rare enough not to carry the survivors over
             if ((live_regex[k] || live_sub[k] || live_range[k]) && !on_device[k] && !scanned[k].empty()) {
@@ -1386,8 +1429,11 @@ private:
                                    const std::vector<const std::vector<uint8_t> *> &set_wants, std::vector<RowMatcher> &host_matchers,
                                    std::vector<std::unique_ptr<RegexRowMatcher>> &host_regex, std::vector<std::unique_ptr<SubstringRowMatcher>> &host_sub,
                                    std::vector<std::unique_ptr<RangeRowMatcher>> &host_range,
-                                   std::vector<std::vector<uint8_t>> &hit, std::vector<uint8_t> &on_device)
+                                   std::vector<std::vector<uint8_t>> &hit, std::vector<uint8_t> &on_device, const std::vector<size_t> &order,
+                                   const HistSpec *hist = nullptr, std::vector<std::vector<uint64_t>> *hist_counts = nullptr)
     {
+        // order: the queries this pass groups, ascending.  hist (under a wide key): every group is decided by ONE bsg_match_rows_wide_hist
+        // call with this spec, and (*hist_counts)[k] takes query k's buckets + 3 counts summed over its sets; hit is not written
         std::vector<uint8_t> bytes;
         std::vector<uint64_t> row_off{0};
         for (const std::string *r : scan) { bytes.insert(bytes.end(), r->begin(), r->end()); row_off.push_back(bytes.size()); }
@@ -1395,7 +1441,7 @@ private:
         const size_t n_words = (scan.size() + 63) / 64, n_sets = set_wants.size();
         // DeviceMatchWide: a group is bounded by its table, not by its members; the storing walker's LDS leaves the tables more room
         // DeviceMatchLookup: the wide call's groups; one without a regex condition may hold 1 024 conditions and takes the lookup call
-        const bool lookup_rows = cfg_.device_match_lookup_rows, lookup = cfg_.device_match_lookup || lookup_rows;
+        const bool lookup_rows = !hist && cfg_.device_match_lookup_rows, lookup = !hist && (cfg_.device_match_lookup || lookup_rows);   // (the hist call is a wide call: 64 conditions)
         const bool wide_rows = cfg_.device_match_wide_rows || lookup_rows, wide = cfg_.device_match_wide || wide_rows || lookup;
         const bool lookup_regex = lookup && cfg_.device_match_lookup_regex;
         // range and text conditions may share a group: without a wide key by DeviceMatchRangeText, under one by DeviceMatchRangeTextWide as well
@@ -1414,8 +1460,8 @@ private:
             }
             return bsh_rxg::rx_table_bytes(it->second.first, it->second.second, (uint32_t)field.size(), !wide);   // the wide blob holds no user masks
         };
-        size_t k = 0;
-        while (k < exprs.size()) {
+        size_t pos = 0;
+        while (pos < order.size()) {
             // the group's table and programs
             std::map<std::tuple<uint32_t, std::string, std::string>, uint32_t> index;
             std::vector<uint32_t> kinds, prog_ops, prog_off{0};
@@ -1425,7 +1471,8 @@ private:
             uint32_t n_plain = 0, n_ft = 0;                                  // its other conditions, and the FieldToken ones among them
             bsh_subg::Group sub_group;                                       // its needles as they pack, and rx_table once more
             bsh_rngg::Mix mix;                                               // whether its table holds a range / a regex or substring condition
-            for (; k < exprs.size() && members.size() < max_members; ++k) {
+            for (; pos < order.size() && members.size() < max_members; ++pos) {
+                const size_t k = order[pos];
                 MatcherProgram mp(exprs[k]);
                 if (regexes[k] || subs[k] || ranges[k]) {   // And(bloom root | TRUE, the trees the query has); a range tree beside the others only under mix_ok
                     if (!exprs[k] || mp.prog_ops.empty()) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
@@ -1471,7 +1518,7 @@ private:
                                   (!needle_group || bsh_subg::fits(sub_group, fresh_sub, wide));   // the needles pack, the tables fit beside them
                 if (!fits) {
                     // alone beyond the call: the caller's (the host matcher; per query for a regex query).  Else it opens the next group
-                    if (members.empty()) ++k;
+                    if (members.empty()) ++pos;
                     break;
                 }
                 for (uint32_t op : mp.prog_ops) {
@@ -1525,6 +1572,34 @@ private:
                     return fail(kErrGpu, bsg_last_error(ctx_));
                 std::vector<uint32_t> fb(scan.size());
                 uint32_t n_fb = 0;
+                if (hist) {
+                    // counts instead of rows: buckets + 3 per (set, listed query), summed per query; a handed-back row is matched by the
+                    // host matchers per query listed on its set and bucketed by hist_row_slot (no JSON object: missing)
+                    const size_t slots = (size_t)hist->buckets + 3;
+                    std::vector<uint32_t> counts(sq.size() * slots + 1);
+                    const int32_t rc = bsg_match_rows_wide_hist(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), kinds.data(),
+                                                                (uint32_t)kinds.size(), prog_ops.data(), prog_off.data(), (uint32_t)members.size(), set_first.data(),
+                                                                sq_off.data(), sq.data(), (uint32_t)n_sets, &tok, (const uint8_t *)hist->field.data(),
+                                                                (uint32_t)hist->field.size(), hist->origin, hist->width, hist->buckets, counts.data(), fb.data(),
+                                                                (uint32_t)fb.size(), &n_fb);
+                    if (rc == BSG_E_UNSUPPORTED) continue;
+                    if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
+                    count_match_call("bsg_match_rows_wide_hist");
+                    for (size_t p = 0; p < sq.size(); ++p) {
+                        std::vector<uint64_t> &into = (*hist_counts)[members[sq[p]]];
+                        for (size_t i = 0; i < slots; ++i) into[i] += counts[p * slots + i];
+                    }
+                    for (size_t j = 0; j < members.size(); ++j) on_device[members[j]] = 1;
+                    for (uint32_t i = 0; i < n_fb; ++i) {
+                        const size_t s = (size_t)(std::upper_bound(set_first.begin() + 1, set_first.end(), fb[i]) - (set_first.begin() + 1));
+                        const std::string &row = *scan[fb[i]];
+                        uint32_t slot = hist->buckets + 2u;
+                        if (!hist_row_slot(row, hist->field, hist->origin, hist->width, hist->buckets, slot)) slot = hist->buckets + 2u;
+                        for (uint32_t p = sq_off[s]; p < sq_off[s + 1]; ++p)
+                            if (host_verdict(members[sq[p]], row)) ++(*hist_counts)[members[sq[p]]][slot];
+                    }
+                    continue;
+                }
                 if (wide_rows) {
                     // the lists themselves: 2 u32 per word is the payload's bound, so the call cannot fail on space
                     std::vector<uint32_t> hdr(sq.size() + 1), payload(2 * total + 1), ids;

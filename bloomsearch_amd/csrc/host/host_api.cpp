@@ -1,6 +1,7 @@
 // host_api.cpp — C-ABI shims of include/bloomsearch_host.h over the header-only host mirror.
 #include "bloomsearch_host.h"
 
+#include <cerrno>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -436,6 +437,21 @@ int32_t bsh_minmax_row(const uint8_t *row, uint64_t len, const uint8_t *field_by
     return minmax_row(std::string_view(reinterpret_cast<const char *>(row), len), f.names, inout) ? 0 : BSH_E_INVALID;
 }
 
+// one row's slot of a bucketed hit count (minmax.hpp hist_row_slot): 0, or < 0 for invalid arguments / a row that is no JSON object
+int32_t bsh_hist_row(const uint8_t *row, uint64_t len, const uint8_t *field, uint32_t field_len, int64_t origin, uint64_t width, uint32_t n_buckets,
+                     uint32_t *out_slot)
+{
+    if ((len && !row) || !field || field_len == 0 || field_len > BSG_MINMAX_MAX_NAME || width == 0 || n_buckets == 0 || n_buckets > BSG_HIST_MAX_BUCKETS ||
+        !out_slot)
+        return BSH_E_INVALID;
+    uint32_t slot = 0;
+    if (!hist_row_slot(std::string_view(reinterpret_cast<const char *>(row), len), std::string(reinterpret_cast<const char *>(field), field_len), origin, width,
+                       n_buckets, slot))
+        return BSH_E_INVALID;
+    *out_slot = slot;
+    return 0;
+}
+
 // one row's partition text (partition.hpp partition_key: the first top-level member with the key; escapes decoded): 0, *out_len = its
 // length, the first min(cap, length) bytes in out; < 0 for an empty or over-long name or a row that is not one valid JSON object
 int32_t bsh_partition_key(const uint8_t *row, uint64_t len, const uint8_t *name, uint32_t name_len, uint8_t *out, uint64_t cap, uint64_t *out_len)
@@ -559,6 +575,7 @@ int32_t bse_open(const char *config_json, uint64_t len, bsg_ctx *ctx, bse_engine
         if (const JNode *n = dom.get("DeviceMatchLookup")) cfg.device_match_lookup = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchLookupRows")) cfg.device_match_lookup_rows = n->type == JType::True;
         if (const JNode *n = dom.get("DeviceMatchLookupRegex")) cfg.device_match_lookup_regex = n->type == JType::True;
+        if (const JNode *n = dom.get("DeviceMatchHistogram")) cfg.device_match_histogram = n->type == JType::True;
         if (const JNode *n = dom.get("MinMaxIndexes")) {       // ["timestamp", ...]; null or [] = none
             if (n->type != JType::Null && n->type != JType::Array) return BSE_E_INVALID_CONFIG;
             for (const JNode &f : n->items) {
@@ -611,7 +628,21 @@ struct ParsedQuery {
     RangeExpression range;
     PrefilterExpression prefilter;
     bool nil = true, has_regex = false, has_sub = false, has_range = false, has_prefilter = false;
+    // "Histogram": {"Field", "Origin", "Width", "Buckets"}: the result holds bucketed hit counts instead of rows
+    bool has_hist = false;
+    HistSpec hist;
 };
+
+// a JSON number that is a plain integer literal within [lo, hi] (no fraction, no exponent)
+bool integer_member(const JNode *n, bool is_signed, int64_t &sv, uint64_t &uv)
+{
+    if (!n || n->type != JType::Number || n->text.empty() || n->text.find_first_of(".eE") != std::string::npos) return false;
+    errno = 0;
+    char *end = nullptr;
+    if (is_signed) sv = strtoll(n->text.c_str(), &end, 10);
+    else { if (n->text[0] == '-') return false; uv = strtoull(n->text.c_str(), &end, 10); }
+    return errno == 0 && end && *end == 0;
+}
 
 int32_t query_from_dom(const JNode &dom, ParsedQuery &q)
 {
@@ -646,6 +677,24 @@ int32_t query_from_dom(const JNode &dom, ParsedQuery &q)
             if (!range_expression_from_json(ex && ex->type == JType::Object ? *ex : *rg, q.range)) return BSE_E_INVALID_QUERY;
             q.has_range = true;
         }
+        // "Histogram": the bucket spec of bsg_match_rows_wide_hist, with its limits
+        const JNode *hg = dom.get("Histogram");
+        if (hg && hg->type == JType::Object) {
+            const JNode *f = hg->get("Field");
+            int64_t sv = 0;
+            uint64_t uv = 0;
+            if (!f || f->type != JType::String || f->text.empty() || f->text.size() > BSG_MINMAX_MAX_NAME) return BSE_E_INVALID_QUERY;
+            q.hist.field = f->text;
+            if (!integer_member(hg->get("Origin"), true, sv, uv)) return BSE_E_INVALID_QUERY;
+            q.hist.origin = sv;
+            if (!integer_member(hg->get("Width"), false, sv, uv) || uv == 0) return BSE_E_INVALID_QUERY;
+            q.hist.width = uv;
+            if (!integer_member(hg->get("Buckets"), false, sv, uv) || uv == 0 || uv > BSG_HIST_MAX_BUCKETS) return BSE_E_INVALID_QUERY;
+            q.hist.buckets = (uint32_t)uv;
+            q.has_hist = true;
+        } else if (hg && hg->type != JType::Null) {
+            return BSE_E_INVALID_QUERY;
+        }
         // "Prefilter": {"Expression": tree} in the reference's shape (QueryPrefilter); a nil Expression prunes nothing
         const JNode *pf = dom.get("Prefilter");
         if (pf && pf->type == JType::Object) {
@@ -663,11 +712,34 @@ int32_t query_from_dom(const JNode &dom, ParsedQuery &q)
     return 0;
 }
 
-void result_to_json(const QueryResult &res, std::string &out)
+// A "Histogram" query's counts.  The device route (query_many under DeviceMatchHistogram) has them in res.hist; on the host route the
+// engine has matched as for any query and every matching row is bucketed here by hist_row_slot (what bsh_hist_row answers; a row that is
+// no JSON object counts as missing).  Either way the result carries "rows": [] and the counts.
+void histogram_to_json(const QueryResult &res, const ParsedQuery &q, std::string &out)
 {
+    const uint32_t B = q.hist.buckets;
+    std::vector<uint64_t> counts = res.hist;
+    if (counts.size() != (size_t)B + 3) {
+        counts.assign((size_t)B + 3, 0);
+        for (const std::string &row : res.rows) {
+            uint32_t slot = B + 2u;
+            if (!hist_row_slot(row, q.hist.field, q.hist.origin, q.hist.width, B, slot)) slot = B + 2u;
+            ++counts[slot];
+        }
+    }
+    out += "\"Histogram\":{\"Counts\":[";
+    for (uint32_t b = 0; b < B; ++b) { if (b) out.push_back(','); out += std::to_string(counts[b]); }
+    out += "],\"Below\":" + std::to_string(counts[B]) + ",\"Above\":" + std::to_string(counts[B + 1u]) + ",\"Missing\":" + std::to_string(counts[B + 2u]) + "},";
+}
+
+void result_to_json(const QueryResult &res, std::string &out, const ParsedQuery *q = nullptr)
+{
+    const bool hist = q && q->has_hist;
     out += "{\"rows\":[";
-    for (size_t i = 0; i < res.rows.size(); ++i) { if (i) out.push_back(','); out += res.rows[i]; }
-    out += "],\"stats\":{\"BlockStats\":[";
+    for (size_t i = 0; i < res.rows.size() && !hist; ++i) { if (i) out.push_back(','); out += res.rows[i]; }
+    out += "],";
+    if (hist) histogram_to_json(res, *q, out);
+    out += "\"stats\":{\"BlockStats\":[";
     for (size_t i = 0; i < res.block_stats.size(); ++i) {
         const BlockStats &s = res.block_stats[i];
         if (i) out.push_back(',');
@@ -698,7 +770,7 @@ int32_t bse_query(bse_engine *e, const char *query_json, uint64_t len, char **ou
     if (int32_t rc = e->eng->query(q.nil ? nullptr : &q.expr, res, q.has_regex ? &q.regex : nullptr, q.has_sub ? &q.sub : nullptr, q.has_range ? &q.range : nullptr,
                                     q.has_prefilter ? &q.prefilter : nullptr)) return rc;
     std::string out;
-    result_to_json(res, out);
+    result_to_json(res, out, &q);
     return give(out, out_json, out_len);
 }
 
@@ -715,15 +787,17 @@ int32_t bse_query_many(bse_engine *e, const char *queries_json, uint64_t len, ch
     std::vector<const SubstringExpression *> subs;
     std::vector<const RangeExpression *> ranges;
     std::vector<const PrefilterExpression *> prefilters;
+    std::vector<const HistSpec *> hists;
     for (const ParsedQuery &q : qs) {
+        hists.push_back(q.has_hist ? &q.hist : nullptr);
         prefilters.push_back(q.has_prefilter ? &q.prefilter : nullptr);
         exprs.push_back(q.nil ? nullptr : &q.expr); regexes.push_back(q.has_regex ? &q.regex : nullptr); subs.push_back(q.has_sub ? &q.sub : nullptr);
         ranges.push_back(q.has_range ? &q.range : nullptr);
     }
     std::vector<QueryResult> res;
-    if (int32_t rc = e->eng->query_many(exprs, regexes, res, &subs, &ranges, &prefilters)) return rc;
+    if (int32_t rc = e->eng->query_many(exprs, regexes, res, &subs, &ranges, &prefilters, &hists)) return rc;
     std::string out = "[";
-    for (size_t i = 0; i < res.size(); ++i) { if (i) out.push_back(','); result_to_json(res[i], out); }
+    for (size_t i = 0; i < res.size(); ++i) { if (i) out.push_back(','); result_to_json(res[i], out, &qs[i]); }
     out.push_back(']');
     return give(out, out_json, out_len);
 }

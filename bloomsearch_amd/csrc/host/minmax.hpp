@@ -130,6 +130,22 @@ inline bool minmax_row(std::string_view row, const std::vector<std::string> &fie
     return true;
 }
 
+// One row's slot among the n_buckets + 3 of a bucketed hit count (bloomgpu.h "Bucketed hit counts"): t = the `min` half of the row's
+// contribution to `field`; t < origin is below (slot B), else q = ((uint64)t - (uint64)origin) / width, bucket q or above (B + 1);
+// a row without a number on the field's last member is missing (B + 2).  width >= 1.  false: the row is not one valid JSON object.
+inline bool hist_row_slot(std::string_view row, const std::string &field, int64_t origin, uint64_t width, uint32_t n_buckets, uint32_t &slot)
+{
+    bsg_minmax idx{};
+    if (!minmax_row(row, std::vector<std::string>{field}, &idx)) return false;
+    if (!idx.present) slot = n_buckets + 2u;
+    else if (idx.min < origin) slot = n_buckets;
+    else {
+        const uint64_t q = ((uint64_t)idx.min - (uint64_t)origin) / width;
+        slot = q >= (uint64_t)n_buckets ? n_buckets + 1u : (uint32_t)q;
+    }
+    return true;
+}
+
 // EvaluateMinMaxCondition.  A bound stored at an int64 extreme is saturated: the true value may lie beyond it, so an operator whose
 // strict comparison at that boundary would drop the block keeps it.  NOT_IN is always true; an unknown operator false.
 inline bool minmax_eval(int64_t imin, int64_t imax, uint32_t op, int64_t value, const int64_t *values, size_t n_values, int64_t lo, int64_t hi)

@@ -109,6 +109,7 @@ struct MatchCall {
     std::vector<uint32_t> rx_blob;         // build_rx_blob
     uint32_t n_rx = 0;
     bool rx_sub = false;                   // the call is bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr (the name in traces)
+    bool no_out_bits = false;              // the call's result goes elsewhere (bsg_match_rows_wide_hist: counters): out_bits is NULL and never read
     bool wide_sub = false;                 // the call is bsg_match_rows_wide_substr(_rows) (the name in traces)
     bool substr = false;                   // build_sub_tables: the call holds the substring walkers' tables
     bsh::NeedlePack sub;                   // ... M, START, ANY
@@ -146,9 +147,9 @@ enum class WideKind { Wide, Lookup, LookupRegex };
 // What every row-matcher call checks of its rows and conditions (the kinds themselves are the caller's); cond_len / n_bytes out.
 int32_t check_match_inputs(const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows, const uint8_t *cond_bytes, const uint32_t *cond_off,
                            const uint32_t *cond_kinds, uint32_t n_conds, const uint64_t *out_bits, const uint32_t *out_n_fallback,
-                           uint32_t &cond_len, uint64_t &n_bytes, uint32_t max_conds = bsg::kMatchMaxConds)
+                           uint32_t &cond_len, uint64_t &n_bytes, uint32_t max_conds = bsg::kMatchMaxConds, bool need_bits = true)
 {
-    if (!out_n_fallback || (n_rows && (!row_off || !out_bits))) return fail(BSG_E_INVALID, "null argument");
+    if (!out_n_fallback || (n_rows && (!row_off || (need_bits && !out_bits)))) return fail(BSG_E_INVALID, "null argument");
     if (n_conds && (!cond_off || !cond_kinds)) return fail(BSG_E_INVALID, "conditions are null");
     if (n_conds > max_conds) return fail(BSG_E_UNSUPPORTED, "%u conditions (the device matcher holds %u)", n_conds, max_conds);
     for (uint32_t e = 0; e < 2 * n_conds; ++e)
@@ -173,7 +174,7 @@ int32_t begin_match_call(MatchCall &mc, const Family &f, const bsg_tokenizer *to
         if (prog_off[q + 1] < prog_off[q]) return fail(BSG_E_INVALID, "prog_off not monotone at %u", q);
     if (n_queries && prog_off[n_queries] > prog_off[0] && !prog_ops) return fail(BSG_E_INVALID, "prog_ops is null");
     return check_match_inputs(mc.rows, mc.row_off, mc.n_rows, mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.out_bits, mc.out_n_fallback,
-                              mc.cond_len, mc.n_bytes, f.max_conds);
+                              mc.cond_len, mc.n_bytes, f.max_conds, !mc.no_out_bits);
 }
 
 // Every query's program lowered over the identity term positions (the lookup call: over term_pos, where a repeated condition is its
@@ -445,6 +446,7 @@ struct PlanePart {
         return BSG_OK;
     }
     void landed() {}
+    void more_fallback(std::vector<uint32_t> &) {}
 };
 
 // bsg_match_rows_wide_rows: where the call's tagged row lists go
@@ -453,6 +455,15 @@ struct WideRowsOut {
     uint64_t *off;                             // [n_pairs + 1] or NULL
     uint32_t *payload;
     uint64_t cap, *len;
+};
+// bsg_match_rows_wide_hist: the bucket rule and where the call's counts go
+struct WideHistOut {
+    bsg::HistField field;
+    int64_t origin;
+    uint64_t width;
+    uint32_t n_buckets;
+    uint32_t *counts;                          // [n_pairs * BSG_HIST_SLOTS(n_buckets)]
+    uint32_t slots() const { return BSG_HIST_SLOTS(n_buckets); }
 };
 // bsg_match_rows_wide: what a part needs beyond the call (sets always materialised: the implicit set is one set with every query)
 struct WidePlan {
@@ -464,6 +475,7 @@ struct WidePlan {
     const WideRowsOut *rows = nullptr;         // the rows policy: lists instead of words
     const bsh_lookup::Plan *lookup = nullptr;  // bsg_match_rows_lookup(_rows) / _lookup_regex(_rows): the table's strings, roles and pairs
     bool lookup_regex = false;                 // ... the second of the two (the names in traces)
+    const WideHistOut *hist = nullptr;         // the hist policy: bucketed counts instead of words
 };
 
 // The wide call: the storing walk chunk by chunk, then one evaluation launch over the part's items (r0 a set-relative multiple of 64).
@@ -498,9 +510,20 @@ struct WidePart {
     std::vector<uint32_t> str_tab;
     uint32_t *d_lk_str = nullptr, *d_lk_rxmask = nullptr;
     uint64_t *d_lk_pair = nullptr, *d_lk_rec = nullptr;
+    // the hist policy: k_bucket_rows beside every chunk's walk leaves a u16 code per row, k_pair_hist folds the words and the codes
+    // into n_pairs * slots counters; those come back (direct: into the caller's array; else staged, added by the finish step) with
+    // the scanner's own list of undecided rows
+    uint16_t *d_code = nullptr;
+    uint32_t *d_counts = nullptr, *d_hfb = nullptr, *d_nhfb = nullptr;
+    EventList hev;                                     // the scanner's launches and k_pair_hist: start, stop each
+    std::vector<uint32_t> staged_counts, hist_fb;
+    float hist_ms = 0.f;
+    int hist_dev = 0;                                  // the device the part ran on (bsg_last_hist_ms: per device the sum of its parts)
+    hipError_t hist_err = hipSuccess;                  // what a scanner launch met (launch() returns nothing)
 
     const char *tag() const
     {
+        if (wp.hist) return "bsg_match_rows_wide_hist";
         if (wp.lookup_regex) return wp.rows ? "bsg_match_rows_lookup_regex_rows" : "bsg_match_rows_lookup_regex";
         if (wp.lookup) return wp.rows ? "bsg_match_rows_lookup_rows" : "bsg_match_rows_lookup";
         if (mc.wide_range_text) return wp.rows ? "bsg_match_rows_wide_regex_substr_range_rows" : "bsg_match_rows_wide_regex_substr_range";
@@ -517,7 +540,7 @@ struct WidePart {
         for (uint32_t &v : pair_off_local) v -= pair0;
         if (!bsh_wide::eval_items(ps, items, part_words))
             return fail(BSG_E_UNSUPPORTED, "more than %u (tile, pair range) items on one device", bsh_wide::kMaxItems);
-        if (wp.rows) psets = bsh_wide::pair_sets(ps);
+        if (wp.rows || wp.hist) psets = bsh_wide::pair_sets(ps);
         return BSG_OK;
     }
     int32_t alloc(PartDev &p)
@@ -545,6 +568,13 @@ struct WidePart {
             HIP_TRY(p.scratch.alloc(&d_bsum, (size_t)scan_blocks() * 8));
             HIP_TRY(p.scratch.alloc(&d_payload, std::max<uint64_t>(part_words, 1) * 8));      // the bound: 2 u32 per word
         }
+        if (wp.hist) {
+            HIP_TRY(p.scratch.alloc(&d_code, std::max<size_t>(p.n_rows, 1) * 2));
+            HIP_TRY(p.scratch.alloc(&d_counts, std::max<size_t>((size_t)n_pairs * wp.hist->slots(), 1) * 4));
+            HIP_TRY(p.scratch.alloc(&d_hfb, std::max<size_t>(p.n_rows, 1) * 4));
+            HIP_TRY(p.scratch.alloc(&d_nhfb, 4));
+            if (n_pairs) HIP_TRY(p.scratch.alloc(&d_psets, psets.size() * sizeof(bsg::PairSetDesc)));
+        }
         return BSG_OK;
     }
     uint32_t scan_blocks() const { return (n_pairs + bsg::kPairScanWidth - 1) / bsg::kPairScanWidth; }
@@ -557,8 +587,31 @@ struct WidePart {
         if (n_pairs) HIP_TRY(hipMemcpyAsync(d_pairs, wp.set_queries + pair0, (size_t)n_pairs * 4, hipMemcpyHostToDevice, p.d.stream));
         if (!items.empty()) HIP_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::RowEvalItem), hipMemcpyHostToDevice, p.d.stream));
         if (d_psets) HIP_TRY(hipMemcpyAsync(d_psets, psets.data(), psets.size() * sizeof(bsg::PairSetDesc), hipMemcpyHostToDevice, p.d.stream));
+        if (wp.hist) HIP_TRY(hipMemsetAsync(d_nhfb, 0, 4, p.d.stream));
         if (wp.lookup) return upload_lookup(p);
         return BSG_OK;
+    }
+    // The bucket scanner over one chunk's rows [rf, rf + n), beside the chunk's walk: a contiguous run of rows per wave, as the
+    // MinMax scanner.  One set with a pair (the implicit set, or a part inside one set): no set search.
+    void launch_scanner(PartDev &p, const bsg::MatchArgs &a, uint32_t rf)
+    {
+        if (!a.n_rows || !n_pairs) return;             // (a part without a pair: nothing is walked, nothing is counted)
+        const size_t k = hev.v.size();
+        if (hipError_t e = hev.add(2); e != hipSuccess) { hist_err = e; return; }
+        const WideHistOut &ho = *wp.hist;
+        bsg::BucketArgs b{};
+        b.rows = a.rows; b.row_off = a.row_off - rf;
+        b.set_first_row = d_sfirst; b.set_pair_off = d_spair;
+        b.code = d_code; b.fallback_rows = d_hfb; b.n_fallback = d_nhfb;
+        b.origin = ho.origin; b.width = ho.width; b.n_buckets = ho.n_buckets; b.n_sets = n_sets;
+        b.row_first = rf; b.row_end = rf + a.n_rows;
+        const uint64_t n = a.n_rows, max_waves = (uint64_t)p.d.n_cus * 4 * 8;
+        const uint64_t waves = std::min<uint64_t>((n + 63) / 64, max_waves);
+        b.rows_per_wave = (uint32_t)(((n + waves - 1) / waves + 63) / 64 * 64);
+        const uint64_t used = (n + b.rows_per_wave - 1) / b.rows_per_wave, wpw = bsg::kBucketThreads / 64;
+        const dim3 grid((uint32_t)((used + wpw - 1) / wpw)), block(bsg::kBucketThreads);
+        if (n_sets == 1) hipExtLaunchKernelGGL(bsg::k_bucket_rows, grid, block, 0, p.d.stream, hev.v[k], hev.v[k + 1], 0, b, ho.field);
+        else hipExtLaunchKernelGGL(bsg::k_bucket_rows_sets, grid, block, 0, p.d.stream, hev.v[k], hev.v[k + 1], 0, b, ho.field);
     }
     // The lookup tables: word 0 of every role string's base hash comes back from the device (the strings are hashed there, under the
     // context's key, like every family's), the host places the slots, tables and role records go up; the flags start at zero.
@@ -583,6 +636,7 @@ struct WidePart {
     }
     void launch(PartDev &p, bsg::MatchArgs &a, uint32_t rf, hipEvent_t k0, hipEvent_t k1)
     {
+        if (wp.hist) launch_scanner(p, a, rf);
         if (wp.lookup) {
             const bsg::MatchLookupArgs lk{d_sfirst, d_spair, d_lk_str, d_lk_pair, d_lk_rec, d_sat + rf, d_state + rf, n_sets, (uint32_t)str_tab.size(),
                                           (uint32_t)pair_tab.size(), p.n_rows, bsh_lookup::pair_shift((uint32_t)pair_tab.size()), d_lk_rxmask};
@@ -628,6 +682,7 @@ struct WidePart {
             HIP_TRY(hipGetLastError());
         }
         if (wp.rows) return rows_results(p, kev);
+        if (wp.hist) return hist_results(p);
         if (part_words) {
             uint64_t *dst = mc.out_bits + wp.set_word0[ps.s0];
             if (!direct) { staged.resize(part_words); dst = staged.data(); }
@@ -663,9 +718,57 @@ struct WidePart {
         if (payload_len) HIP_TRY(hipMemcpyAsync(dst, d_payload, payload_len * 4, hipMemcpyDeviceToHost, p.d.stream));
         return BSG_OK;
     }
+    // k_pair_hist between two events of the part's own (bsg_last_hist_ms, not bsg_last_match_ms), then the part's counters and
+    // the scanner's list (the stream is waited for: its length sizes the copy)
+    int32_t hist_results(PartDev &p)
+    {
+        HIP_TRY(hist_err);
+        hist_dev = p.d.id;
+        const WideHistOut &ho = *wp.hist;
+        const uint32_t slots = ho.slots();
+        if (n_pairs) {
+            uint32_t max_tiles = 0;
+            for (uint32_t ls = 0; ls < n_sets; ++ls)
+                if (ps.pair_off[ls + 1] > ps.pair_off[ls]) max_tiles = std::max(max_tiles, bsh_wide::tiles_of(ps.first_row[ls + 1] - ps.first_row[ls]));
+            // up to 64 waves per pair, each at least one step of tiles
+            const uint32_t step = bsg::kPairHistStep;
+            const uint32_t span_tiles = std::max(step, ((max_tiles + 63u) / 64u + step - 1u) / step * step);
+            const uint32_t spans_max = std::max(1u, (max_tiles + span_tiles - 1u) / span_tiles);
+            const uint64_t waves = (uint64_t)n_pairs * spans_max, per_block = bsg::kPairHistThreads / 64u;
+            const uint64_t blocks = (waves + per_block - 1) / per_block;
+            if (blocks > 0x7FFFFFFFull) return fail(BSG_E_UNSUPPORTED, "%llu (pair, span) waves on one device", (unsigned long long)waves);
+            const size_t k = hev.v.size();
+            HIP_TRY(hev.add(2));
+            HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)n_pairs * slots * 4, p.d.stream));
+            const bsg::PairHistArgs h{d_psets, d_sfirst, d_out, d_code, d_counts, n_pairs, n_sets, ho.n_buckets, span_tiles, spans_max};
+            hipExtLaunchKernelGGL(bsg::k_pair_hist, dim3((uint32_t)blocks), dim3(bsg::kPairHistThreads), 0, p.d.stream, hev.v[k], hev.v[k + 1], 0, h);
+            HIP_TRY(hipGetLastError());
+            uint32_t *dst = ho.counts + (uint64_t)pair0 * slots;
+            if (!direct) { staged_counts.resize((size_t)n_pairs * slots); dst = staged_counts.data(); }
+            HIP_TRY(hipMemcpyAsync(dst, d_counts, (size_t)n_pairs * slots * 4, hipMemcpyDeviceToHost, p.d.stream));
+        }
+        uint32_t n = 0;
+        HIP_TRY(hipMemcpyAsync(&n, d_nhfb, 4, hipMemcpyDeviceToHost, p.d.stream));
+        HIP_TRY(hipStreamSynchronize(p.d.stream));
+        if (n > p.n_rows) return fail(BSG_E_HIP, "the bucket scanner lists %u rows of %u", n, p.n_rows);
+        hist_fb.resize(n);
+        if (n) HIP_TRY(hipMemcpy(hist_fb.data(), d_hfb, (size_t)n * 4, hipMemcpyDeviceToHost));
+        for (uint32_t &r : hist_fb) r += p.r0;
+        hist_ms = 0.f;
+        for (size_t k = 0; k + 1 < hev.v.size(); k += 2) { float t = 0.f; (void)hipEventElapsedTime(&t, hev.v[k], hev.v[k + 1]); hist_ms += t; }
+        return BSG_OK;
+    }
+    // the scanner's undecided rows join the walker's (GLOBAL indices): one list, each row once
+    void more_fallback(std::vector<uint32_t> &fb)
+    {
+        if (hist_fb.empty()) return;
+        fb.insert(fb.end(), hist_fb.begin(), hist_fb.end());
+        std::sort(fb.begin(), fb.end());
+        fb.erase(std::unique(fb.begin(), fb.end()), fb.end());
+    }
     void landed()                                      // the part's layout -> the call's: per pair, the part's tiles of the set
     {
-        if (direct || wp.rows) return;
+        if (direct || wp.rows || wp.hist) return;
         uint64_t at = 0;
         for (uint32_t ls = 0; ls < n_sets; ++ls) {
             const uint32_t s = ps.s0 + ls, tiles = bsh_wide::tiles_of(ps.first_row[ls + 1] - ps.first_row[ls]);
@@ -777,6 +880,7 @@ int32_t match_part(bsg_ctx *ctx, Device &d, const MatchCall &mc, uint32_t r0, ui
     fb.resize(nfb);
     if (nfb) HIP_TRY(hipMemcpy(fb.data(), d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
     for (uint32_t &r : fb) r += r0;
+    mode.more_fallback(fb);
     scratch.done();                        // every kernel has finished, and each waited for its chunk's copy
     mode.landed();
     return BSG_OK;
@@ -984,7 +1088,8 @@ int32_t wide_size_status(bsh_wide::SizeStatus st, uint32_t bad_set, const uint32
 
 int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
                              const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
-                             const bsg_tokenizer *tok_in, const WideRowsOut *rows = nullptr, WideKind which = WideKind::Wide)
+                             const bsg_tokenizer *tok_in, const WideRowsOut *rows = nullptr, WideKind which = WideKind::Wide,
+                             const WideHistOut *hist = nullptr)
 {
     const bool lookup = which != WideKind::Wide, lookup_regex = which == WideKind::LookupRegex;
     const Family &fam = lookup_regex ? kLookupRegexFamily : lookup ? kLookupFamily : kWideFamily;
@@ -1013,7 +1118,7 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
         }
     }
     // the sets: the caller's, or one implicit set of all rows with every query
-    WidePlan wp{set_first_row, set_query_off, set_queries, n_sets, n_queries, {}, {}, {}, rows, lookup ? &lookup_plan : nullptr, lookup_regex};
+    WidePlan wp{set_first_row, set_query_off, set_queries, n_sets, n_queries, {}, {}, {}, rows, lookup ? &lookup_plan : nullptr, lookup_regex, hist};
     std::vector<uint32_t> implicit_first, implicit_off, implicit_queries;
     if (n_sets == 0) {
         if (set_first_row || set_query_off || set_queries) return fail(BSG_E_INVALID, "a set table without its number of sets");
@@ -1068,6 +1173,37 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
         wp.set_word0[s + 1] = wp.set_word0[s] + (uint64_t)bsh_wide::tiles_of(wp.set_first_row[s + 1] - wp.set_first_row[s]) *
                                                     (wp.set_query_off[s + 1] - wp.set_query_off[s]);
     *mc.out_n_fallback = 0;
+    if (hist) {
+        // the hist policy: every counter 0 until a part says otherwise (a set without rows lies in no part); the parts outlive their
+        // devices' work, and the finish step adds the staged counters of a set cut between parts — on one thread, in any order
+        const uint32_t slots = hist->slots();
+        memset(hist->counts, 0, (size_t)n_pairs * slots * 4);
+        std::mutex kept_mu;
+        std::vector<std::unique_ptr<WidePart>> kept;
+        return match_fan_out(
+            ctx, mc, wp.set_first_row, wp.n_sets,
+            [&](uint32_t n_parts, Device &d, uint32_t r0, uint32_t r1, std::vector<uint32_t> &fb, float *ms) -> int32_t {
+                WidePart *mode = new WidePart{mc, wp, n_parts == 1};
+                {
+                    std::lock_guard<std::mutex> lk(kept_mu);
+                    kept.emplace_back(mode);
+                }
+                return match_part(ctx, d, mc, r0, r1, *mode, fb, ms);
+            },
+            [&]() -> int32_t {
+                float ms = 0.f;
+                std::map<int, float> per_device;
+                for (const auto &k : kept) {
+                    ms = std::max(ms, per_device[k->hist_dev] += k->hist_ms);
+                    if (k->direct) continue;
+                    uint32_t *dst = hist->counts + (uint64_t)k->pair0 * slots;
+                    for (size_t i = 0; i < k->staged_counts.size(); ++i) dst[i] += k->staged_counts[i];
+                }
+                std::lock_guard<std::shared_mutex> lk(ctx->mu);
+                ctx->last_hist_ms = ms;
+                return BSG_OK;
+            });
+    }
     if (!rows)
         return match_fan_out(ctx, mc, wp.set_first_row, wp.n_sets,
                              [&](uint32_t n_parts, Device &d, uint32_t r0, uint32_t r1, std::vector<uint32_t> &fb, float *ms) -> int32_t {
@@ -1229,6 +1365,40 @@ int32_t bsg_match_rows_wide_regex_substr_range_rows(bsg_ctx *ctx, const uint8_t 
     mc.wide_range_text = true;
     const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
     return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
+}
+
+int32_t bsg_match_rows_wide_hist(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                 const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                 const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                 const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
+                                 const bsg_tokenizer *tok,
+                                 const uint8_t *field, uint32_t field_len, int64_t origin, uint64_t width, uint32_t n_buckets,
+                                 uint32_t *out_counts, uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback)
+{
+    BSG_ENTER(ctx);
+    if (n_buckets == 0 || n_buckets > BSG_HIST_MAX_BUCKETS)
+        return fail(BSG_E_INVALID, "n_buckets is %u (1 to %u)", n_buckets, BSG_HIST_MAX_BUCKETS);
+    if (width == 0) return fail(BSG_E_INVALID, "width is 0");
+    if (!field) return fail(BSG_E_INVALID, "field is null");
+    if (field_len == 0 || field_len > BSG_MINMAX_MAX_NAME)
+        return fail(BSG_E_INVALID, "field_len is %u (a name of 1 to %u bytes)", field_len, BSG_MINMAX_MAX_NAME);
+    if (!out_counts) return fail(BSG_E_INVALID, "out_counts is null");
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, nullptr, out_fallback_rows, fallback_cap, out_n_fallback};
+    mc.no_out_bits = true;                 // the counters are the result (checked above)
+    mc.wide_range_text = true;
+    WideHistOut out{{}, origin, width, n_buckets, out_counts};
+    memcpy(out.field.name, field, field_len);
+    out.field.len = field_len;
+    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, nullptr, WideKind::Wide, &out);
+}
+
+int32_t bsg_last_hist_ms(bsg_ctx *ctx, float *hist_ms)
+{
+    BSG_ENTER(ctx);
+    if (!hist_ms) return fail(BSG_E_INVALID, "null argument");
+    std::lock_guard<std::shared_mutex> lk(ctx->mu);
+    *hist_ms = ctx->last_hist_ms;
+    return BSG_OK;
 }
 
 int32_t bsg_match_rows_lookup(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,

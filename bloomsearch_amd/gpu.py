@@ -960,6 +960,29 @@ class Context:
         """bsg_match_rows_wide_regex_substr_range_rows: match_rows_wide_rows' arguments and result over such a table."""
         return self._wide_rows(self.L.bsg_match_rows_wide_regex_substr_range_rows, rows, batch, set_first_row, set_query_off, set_queries, tokenizer, payload_cap)
 
+    def match_rows_wide_hist(self, rows, batch, field, origin: int, width: int, n_buckets: int, set_first_row=None, set_query_off=None,
+                             set_queries=None, tokenizer=None):
+        """bsg_match_rows_wide_hist: match_rows_wide_regex_substr_range's rows, batch and sets; field (bytes or str): a top-level key
+        whose number value buckets a matching row (bucket (floor(v) - origin) // width of n_buckets).
+        -> (u32 counts [n_pairs, n_buckets + 3]: the buckets, then below, above and missing; sorted u32 array of rows the host must
+        decide, match and bucket both: they are counted in no slot)."""
+        args, _keep, n, pair_word_off, _total = self._wide_args(rows, batch, set_first_row, set_query_off, set_queries, tokenizer)
+        name = field.encode() if isinstance(field, str) else bytes(field)
+        n_pairs = len(pair_word_off) - 1
+        slots = _lib.HIST_SLOTS(int(n_buckets))
+        counts = np.zeros(max(n_pairs * slots, 1), dtype=np.uint32)
+        fb = np.zeros(max(n, 1), dtype=np.uint32)
+        nfb = C.c_uint32()
+        self._check(self.L.bsg_match_rows_wide_hist(*args, name, len(name), int(origin), int(width), int(n_buckets), counts.ctypes.data,
+                                                    _lib._ptr(fb), len(fb), C.byref(nfb)))
+        return counts[: n_pairs * slots].reshape(n_pairs, slots), fb[: nfb.value].copy()
+
+    def last_hist_ms(self) -> float:
+        """bsg_last_hist_ms: the bucket scanner (summed over chunks) plus the counting pass of the last match_rows_wide_hist"""
+        v = C.c_float()
+        self._check(self.L.bsg_last_hist_ms(self.h, C.byref(v)))
+        return float(v.value)
+
     def match_rows_lookup(self, rows, batch, set_first_row=None, set_query_off=None, set_queries=None, tokenizer=None):
         """bsg_match_rows_lookup: match_rows_wide's arguments and result over a table of up to 1 024 Field / Token / FieldToken
         conditions (batch: query.CompiledLookupBatch, or anything with kinds / fields / tokens / prog_ops / prog_off)."""

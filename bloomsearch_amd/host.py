@@ -19,7 +19,7 @@ HOST_EXPORTS = [
     "bsh_batch_new", "bsh_batch_free", "bsh_batch_add_query", "bsh_batch_sizes", "bsh_batch_export", "bsh_match_row", "bsh_match_row_with", "bsh_prune_query", "bsh_match_row_regex",
     "bsh_substring_terms", "bsh_prune_query_sub", "bsh_match_row_substring",
     "bsh_match_row_range", "bsh_prune_query_range",
-    "bsh_minmax_row", "bsh_minmax_eval", "bsh_prefilter_eval", "bsh_partition_key",
+    "bsh_minmax_row", "bsh_minmax_eval", "bsh_prefilter_eval", "bsh_partition_key", "bsh_hist_row",
     "bsh_regex_match",
     "bsh_section_encode", "bsh_section_parse", "bsh_crc32c",
     "bse_open", "bse_close", "bse_last_error", "bse_stop", "bse_ingest_rows", "bse_flush", "bse_merge", "bse_query", "bse_query_many",
@@ -70,6 +70,7 @@ def lib():
     L.bsh_prune_query_range.argtypes = [C.c_char_p, u64, C.c_char_p, u64, C.c_char_p, u64, C.c_char_p, u64, C.POINTER(_lib.Tokenizer), pp, pu64]
     L.bsh_minmax_row.argtypes = [C.c_char_p, u64, vp, vp, u32, vp]
     L.bsh_partition_key.argtypes = [C.c_char_p, u64, C.c_char_p, u32, vp, u64, C.POINTER(u64)]
+    L.bsh_hist_row.argtypes = [C.c_char_p, u64, C.c_char_p, u32, C.c_int64, u64, u32, C.POINTER(u32)]
     L.bsh_minmax_eval.argtypes = [vp, u32, C.c_int64, vp, u32, C.c_int64, C.c_int64]
     L.bsh_prefilter_eval.argtypes = [C.c_char_p, u64, C.c_char_p, u64, vp, vp, u32, vp]
     L.bsh_section_encode.argtypes = [C.POINTER(vp), pu64, pu64, pp, pu64]
@@ -329,6 +330,18 @@ def minmax_row(row: bytes, fields, index=None) -> np.ndarray:
     return index
 
 
+def hist_row(row: bytes, field, origin: int, width: int, n_buckets: int) -> int:
+    """bsh_hist_row: the row's slot among n_buckets + 3 (a bucket, then below, above, missing) by the rule of
+    bsg_match_rows_wide_hist; exact for every literal.  HostError for a row that is not one valid JSON object or invalid arguments."""
+    L = lib()
+    field = field.encode() if isinstance(field, str) else bytes(field)
+    slot = C.c_uint32()
+    rc = L.bsh_hist_row(row, len(row), field, len(field), int(origin), int(width), int(n_buckets), C.byref(slot))
+    if rc:
+        raise HostError(rc)
+    return int(slot.value)
+
+
 def partition_key(row: bytes, name) -> bytes:
     """bsh_partition_key: the row's partition text under the field `name` (the keyed ingest's rule, exact for every row: escapes
     decoded).  HostError for a row that is not one valid JSON object, or a name of 0 or more than 64 bytes."""
@@ -448,9 +461,11 @@ class Engine:
     def stop(self):
         self._check(self.L.bse_stop(self.h))
 
-    def query(self, bloom_expression=None, regex_expression=None, substring_expression=None, range_expression=None, prefilter=None):
+    def query(self, bloom_expression=None, regex_expression=None, substring_expression=None, range_expression=None, prefilter=None, histogram=None):
         """prefilter: a tree of query.Partition / MinMax / PrefilterAnd / PrefilterOr over the blocks' partition ids and MinMax indexes
-        (config MinMaxIndexes=[...]); None takes exactly the path without one."""
+        (config MinMaxIndexes=[...]); None takes exactly the path without one.
+        histogram: {"Field", "Origin", "Width", "Buckets"}: the result then holds "rows": [] and "Histogram": {"Counts", "Below", "Above",
+        "Missing"} over the matching rows (the bucket rule of bsg_match_rows_wide_hist); its stats are the query's without it."""
         d = {"Bloom": {"Expression": bloom_expression} if bloom_expression is not None else None,
              "Regex": {"Expression": regex_expression} if regex_expression is not None else None}
         if prefilter is not None:
@@ -459,22 +474,25 @@ class Engine:
             d["Substring"] = substring_expression
         if range_expression is not None:
             d["Range"] = range_expression
+        if histogram is not None:
+            d["Histogram"] = histogram
         q = json.dumps(d).encode()
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self.L.bse_query(self.h, q, len(q), C.byref(p), C.byref(n)))
         return json.loads(_take(self.L, p, n))
 
-    def query_many(self, bloom_expressions, regex_expressions=None, substring_expressions=None, range_expressions=None, prefilters=None):
+    def query_many(self, bloom_expressions, regex_expressions=None, substring_expressions=None, range_expressions=None, prefilters=None, histograms=None):
         """bse_query_many: one pass for a batch of queries -> list of query()'s results, element i for bloom_expressions[i]
-        (and regex_expressions[i] / substring_expressions[i] / range_expressions[i], where given)."""
+        (and regex_expressions[i] / substring_expressions[i] / range_expressions[i] / histograms[i], where given)."""
         rx = list(regex_expressions) if regex_expressions is not None else [None] * len(bloom_expressions)
         sx = list(substring_expressions) if substring_expressions is not None else [None] * len(bloom_expressions)
         gx = list(range_expressions) if range_expressions is not None else [None] * len(bloom_expressions)
         px = list(prefilters) if prefilters is not None else [None] * len(bloom_expressions)
+        hx = list(histograms) if histograms is not None else [None] * len(bloom_expressions)
         q = json.dumps([dict({"Bloom": {"Expression": b} if b is not None else None, "Regex": {"Expression": r} if r is not None else None},
                              **({"Substring": s} if s is not None else {}), **({"Range": g} if g is not None else {}),
-                             **({"Prefilter": {"Expression": p}} if p is not None else {}))
-                        for b, r, s, g, p in zip(bloom_expressions, rx, sx, gx, px)]).encode()
+                             **({"Prefilter": {"Expression": p}} if p is not None else {}), **({"Histogram": h} if h is not None else {}))
+                        for b, r, s, g, p, h in zip(bloom_expressions, rx, sx, gx, px, hx)]).encode()
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self.L.bse_query_many(self.h, q, len(q), C.byref(p), C.byref(n)))
         return json.loads(_take(self.L, p, n))

@@ -736,8 +736,45 @@ class CompiledWideTextRangeBatch(CompiledRowTextRangeQueryBatch):
 
     MAX_QUERIES, MAX_OPS = MATCH_WIDE_MAX_QUERIES, MATCH_WIDE_MAX_OPS
 
+    def __init__(self, quadruples):
+        quadruples = list(quadruples)
+        super().__init__(quadruples)
+        self.queries = quadruples                  # what histogram() decides the handed-back rows with
 
-MATCH_LOOKUP_MAX_CONDS = 1024                                                    # bloomgpu.h BSG_MATCH_LOOKUP_MAX_CONDS
+    def histogram(self, ctx, rows, field, origin: int, width: int, n_buckets: int, set_first_row=None, set_query_off=None, set_queries=None,
+                  tokenizer=None):
+        """Per (set, query) pair, how many matching rows fall into each bucket of the top-level number field: ctx.match_rows_wide_hist
+        (bsg_match_rows_wide_hist), then every row the device handed back decided on the host — its match by the four host matchers,
+        its slot by bsh_hist_row — and added.  -> u32 counts [n_pairs, n_buckets + 3] (the buckets, then below, above, missing): final."""
+        from . import host
+        counts, handed_back = ctx.match_rows_wide_hist(rows, self, field, origin, width, n_buckets, set_first_row, set_query_off, set_queries, tokenizer)
+        counts = counts.copy()
+        if len(handed_back) == 0:
+            return counts
+        if isinstance(rows, tuple):
+            blob, off = bytes(np.asarray(rows[0], dtype=np.uint8)), np.asarray(rows[1], dtype=np.uint64)
+            row_of = lambda r: blob[int(off[r]): int(off[r + 1])]
+        else:
+            row_of = lambda r: rows[r]
+        if set_first_row is None:
+            first, pair_off, pairs = np.array([0, 1 << 32], dtype=np.uint64), [0, self.n_queries], list(range(self.n_queries))
+        else:
+            first, pair_off, pairs = np.asarray(set_first_row, dtype=np.uint64), [int(x) for x in set_query_off], [int(q) for q in set_queries]
+        for r in handed_back:
+            row = row_of(int(r))
+            s = int(np.searchsorted(first, int(r), side="right")) - 1
+            slot = None
+            for p in range(pair_off[s], pair_off[s + 1]):
+                bloom, regex, sub, rng = self.queries[pairs[p]]
+                if (bloom is None or host.match_row(bloom, row, tokenizer)) and host.match_row_regex(regex, row) and \
+                        host.match_row_substring(sub, row, tokenizer) and host.match_row_range(rng, row):
+                    if slot is None:
+                        slot = host.hist_row(row, field, origin, width, n_buckets)
+                    counts[p, slot] += 1
+        return counts
+
+
+MATCH_LOOKUP_MAX_CONDS = 1024                                                   # bloomgpu.h BSG_MATCH_LOOKUP_MAX_CONDS
 
 
 class CompiledLookupBatch(CompiledWideBatch):

@@ -1192,6 +1192,45 @@ BSG_API int32_t bsg_match_rows_lookup_regex_rows(bsg_ctx *ctx, const uint8_t *ro
                                                  uint32_t *out_pair_hdr, uint64_t *out_pair_off, uint32_t *out_payload, uint64_t payload_cap,
                                                  uint64_t *out_payload_len, uint32_t *out_fallback_rows, uint32_t fallback_cap,
                                                  uint32_t *out_n_fallback);
+/* ---- Bucketed hit counts: per (set, query) pair, how many matching rows fall into each bucket of a number field ----
+ * bsg_match_rows_wide_regex_substr_range with a third result policy next to "words" and "rows": the condition table (kinds 0-6),
+ * programs, sets, pairs and the implicit set, tok, the limits, the refusals and the table-decides-the-walker routing are that call's,
+ * and so are the walk and the evaluation (the same kernels).  Instead of bit rows the call returns, per pair p,
+ * BSG_HIST_SLOTS(n_buckets) u32 at out_counts[p * BSG_HIST_SLOTS(n_buckets)]: slots [0, B) the buckets, B below, B + 1 above,
+ * B + 2 missing.
+ * The field and the row's value: a TOP-LEVEL key of 1 to BSG_MINMAX_MAX_NAME bytes by the rule of the per-set MinMax indexes (compared
+ * byte for byte with the decoded key; the value must itself be a JSON number; the last member with the key counts); t is the `min`
+ * half of that contract, clamp(floor(v)) of the exact decimal value in int64.
+ * The bucket rule, in exact integer arithmetic: t < origin is `below`; else d = (uint64_t)t - (uint64_t)origin, q = d / width;
+ * q >= n_buckets is `above`, else bucket q.  A row with no such member, or whose last such member is no number, is `missing`.
+ * A pair's slots count exactly the rows whose bit bsg_match_rows_wide_regex_substr_range sets for the pair, so they sum to that bit
+ * row's popcount minus the rows this call hands back beyond the parent's.
+ * Rows handed back: ONE list, ascending, each row once, counted in no slot, only rows of a set with at least one pair: the union of
+ * the parent's rules and the bucket scanner's undecided rows (an exponent literal on the field, a backslash in any top-level key).
+ * The host decides both the match and the bucket of such a row (bsh_hist_row, bloomsearch_host.h).  Rows of a set with no pair are
+ * never scanned, never walked and never handed back.
+ * BSG_E_INVALID, before anything is launched and naming the argument: n_buckets 0 or above BSG_HIST_MAX_BUCKETS, width 0, a name
+ * that is empty or longer than BSG_MINMAX_MAX_NAME, a null array, and everything the parent refuses.  BSG_E_UNSUPPORTED: as the
+ * parent.  n_rows == 0 or zero pairs: BSG_OK, nothing written.
+ * Kernels (hist.hip.h): k_bucket_rows / k_bucket_rows_sets beside every chunk's walk, one lane per row, a u16 code per row;
+ * k_pair_hist behind k_eval_row_programs, a wave per (pair, span of tiles) with a histogram of BSG_HIST_SLOTS(1024) u32 in LDS, four
+ * waves per workgroup: 16 432 bytes.  Device memory beyond the parent's: 2 bytes per row (and 4 for the scanner's list) and
+ * 4 * BSG_HIST_SLOTS(n_buckets) per pair of the part; index arithmetic over pairs x slots is in 64 bits.
+ * Sharding and chunked upload as the parent: a set cut between devices has its counts added on the host, so the result is the same
+ * for any number of devices and any chunk size.  bsg_last_match_ms: the walk plus the evaluation, as after the parent.
+ * The lookup family (bsg_match_rows_lookup*) has no such call yet. */
+#define BSG_HIST_MAX_BUCKETS 1024u
+#define BSG_HIST_SLOTS(n_buckets) ((n_buckets) + 3u)   /* [0, B): buckets, B: below, B + 1: above, B + 2: missing */
+BSG_API int32_t bsg_match_rows_wide_hist(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                                         const uint8_t *cond_bytes, const uint32_t *cond_off, const uint32_t *cond_kinds, uint32_t n_conds,
+                                         const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                                         const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries,
+                                         uint32_t n_sets, const bsg_tokenizer *tok,
+                                         const uint8_t *field, uint32_t field_len, int64_t origin, uint64_t width, uint32_t n_buckets,
+                                         uint32_t *out_counts /* [n_pairs * BSG_HIST_SLOTS(n_buckets)] */,
+                                         uint32_t *out_fallback_rows, uint32_t fallback_cap, uint32_t *out_n_fallback);
+/* the bucket scanner (summed over chunks) + the counting pass of the most recent bsg_match_rows_wide_hist, slowest device */
+BSG_API int32_t bsg_last_hist_ms(bsg_ctx *ctx, float *hist_ms);
 /* Device time of the most recent k_match_rows / k_match_rows_regex / k_match_rows_many / k_match_rows_many_regex dispatch (the
  * slowest device's); after bsg_match_rows_wide, its walk plus its evaluation; after bsg_match_rows_wide_rows, its list passes too. */
 BSG_API int32_t bsg_last_match_ms(bsg_ctx *ctx, float *match_ms);

@@ -118,6 +118,13 @@ BSG_API int32_t bsh_prune_query_range(const char *bloom_json, uint64_t bloom_len
  * valid JSON object (nothing is folded). */
 BSG_API int32_t bsh_minmax_row(const uint8_t *row, uint64_t len, const uint8_t *field_bytes, const uint32_t *field_off, uint32_t n_fields,
                                bsg_minmax *inout);
+/* One row's slot among the BSG_HIST_SLOTS(n_buckets) of bsg_match_rows_wide_hist (bloomgpu.h "Bucketed hit counts"): a bucket, or
+ * n_buckets (below), n_buckets + 1 (above), n_buckets + 2 (missing).  The field, the row's value t = clamp(floor(v)) and the bucket
+ * rule are that call's; exact for EVERY number literal, exponents included, and escaped keys are decoded (built on bsh_minmax_row's
+ * scan): the function the rows that call hands back are bucketed with.  BSH_E_INVALID: a name of 0 or more than BSG_MINMAX_MAX_NAME
+ * bytes, width 0, n_buckets 0 or above BSG_HIST_MAX_BUCKETS, null pointers, or a row that is not one valid JSON object. */
+BSG_API int32_t bsh_hist_row(const uint8_t *row, uint64_t len, const uint8_t *field, uint32_t field_len, int64_t origin, uint64_t width,
+                             uint32_t n_buckets, uint32_t *out_slot);
 /* One row's partition text by the rule of the keyed ingest (bloomgpu.h "keyed streaming ingest"; the engine's PartitionField): the
  * FIRST top-level member whose decoded key equals name[name_len] (1 to BSG_PARTITION_MAX_NAME bytes) gives a string's decoded
  * bytes, a number's raw literal, "true" or "false"; null, an object, an array or no such member give the empty text.  Exact for
@@ -169,7 +176,7 @@ typedef struct bse_engine bse_engine;
  *               "BloomFalsePositiveRate":..,"PartitionField":"..","DeviceIngest":true|false,"DeviceIngestStream":true|false,
  *               "TrustedRows":true|false,"DevicePartition":true|false,"DeviceMatch":true|false,
  *               "DeviceRegex":true|false,"DeviceMatchRangeText":true|false,"DeviceMatchWide":true|false,"DeviceMatchWideRows":true|false,
- *               "DeviceMatchRangeTextWide":true|false,
+ *               "DeviceMatchRangeTextWide":true|false,"DeviceMatchHistogram":true|false,
  *               "DeviceMatchLookup":true|false,"DeviceMatchLookupRows":true|false,"DeviceMatchLookupRegex":true|false,
  *               "Tokenizer":{"Separators":"..","UnicodeSpace":true|false,"Lower":true|false,"Ngram":0|2|3|4},
  *               "MinMaxIndexes":["timestamp",..]};
@@ -219,6 +226,13 @@ typedef struct bse_engine bse_engine;
  *               64 conditions, 16 regex conditions, needles that pack, regex tables of at most 42 496 bytes needle or not) whose
  *               table holds both makes one bsg_match_rows_wide_regex_substr_range call, under a rows key one
  *               bsg_match_rows_wide_regex_substr_range_rows call, and never a lookup call; bse_query is unchanged; same answers.
+ *               DeviceMatchHistogram (default false; needs DeviceMatch and one of DeviceMatchWide, DeviceMatchWideRows:
+ *               BSE_E_INVALID_CONFIG otherwise): in bse_query_many the queries that carry a "Histogram" member leave the batch's
+ *               groups; those with an equal spec form wide groups of their own (the wide groups' closing rules, 64 conditions),
+ *               each decided by ONE bsg_match_rows_wide_hist call: per-set counts summed per query on the host, the rows the call
+ *               hands back matched by the host matchers and bucketed by bsh_hist_row's rule; BSG_E_UNSUPPORTED and a query outside
+ *               a group take the host route.  Without the key, and always in bse_query, a "Histogram" query is matched as any
+ *               query and every matching row bucketed on the host.  Same answers on both routes.
  *               Tokenizer (default: BasicWhitespaceLowerTokenizer): the engine's tokenizer
  *               of the separator family (bloomgpu.h bsg_tokenizer), used by indexing, the host matcher and the device calls;
  *               a missing member is Go's zero value ("" / false); BSE_E_INVALID_CONFIG for a NUL or non-ASCII separator.

@@ -1681,10 +1681,16 @@ private:
         return kEngineOk;
     }
 
-    int32_t match_rows_device(const BloomExpression *expr, const std::vector<const std::string *> &scan, RowMatcher &host_matcher,
-                              std::vector<uint8_t> &hit, bool &on_device)
+    // The five single-query device matchers below differ in their program prologue, the entry point and the host matchers that decide
+    // a row the device hands back (the walker's envelope, a fingerprint collision, ...): mp over the scan list in one call of `call`.
+    // done stays false (the host decides) beyond 64 conditions or what the call holds (depth, ops, tables): BSG_E_UNSUPPORTED.
+    // count_first: the call is counted before it is made; else only once it has not answered BSG_E_UNSUPPORTED.
+    using MatchRowsCall = int32_t (*)(bsg_ctx *, const uint8_t *, const uint64_t *, uint32_t, const uint8_t *, const uint32_t *, const uint32_t *, uint32_t,
+                                      const uint32_t *, uint32_t, const bsg_tokenizer *, uint64_t *, uint32_t *, uint32_t, uint32_t *);
+    template <class Fallback>
+    int32_t match_program_on_device(const MatcherProgram &mp, MatchRowsCall call, const char *name, bool count_first,
+                                    const std::vector<const std::string *> &scan, Fallback &&host_decides, std::vector<uint8_t> &hit, bool &done)
     {
-        MatcherProgram mp(expr);
         if (mp.kinds.size() > 64) return kEngineOk;
         // condition strings as the C-ABI takes them: field i, token i, ... (hashed and fingerprinted on the device)
         std::vector<uint8_t> cbytes;
@@ -1700,20 +1706,27 @@ private:
         std::vector<uint32_t> fb(scan.size());
         uint32_t n_fb = 0;
         const bsg_tokenizer tok = c_tokenizer();
-        count_match_call("bsg_match_rows_tok");
-        const int32_t rc = bsg_match_rows_tok(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(),
-                                              (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok, bits.data(), fb.data(),
-                                              (uint32_t)fb.size(), &n_fb);
-        if (rc == BSG_E_UNSUPPORTED) return kEngineOk;      // expression too deep / long: host matcher
+        if (count_first) count_match_call(name);
+        const int32_t rc = call(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(), (uint32_t)mp.kinds.size(),
+                                mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok, bits.data(), fb.data(), (uint32_t)fb.size(), &n_fb);
+        if (rc == BSG_E_UNSUPPORTED) return kEngineOk;
+        if (!count_first) count_match_call(name);
         if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
         for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
-        for (uint32_t i = 0; i < n_fb; ++i) hit[fb[i]] = host_matcher.match(*scan[fb[i]]);   // rows outside the device walker's envelope
-        on_device = true;
+        for (uint32_t i = 0; i < n_fb; ++i) hit[fb[i]] = host_decides(*scan[fb[i]]);
+        done = true;
         return kEngineOk;
     }
 
-    // And(bloom root, substring root) over the scan list in one bsg_match_rows_substr call; the rows it hands back are decided by both
-    // host matchers.  done stays false (the host decides) beyond 64 conditions or what the call holds (128 needle bytes, depth, ops).
+    int32_t match_rows_device(const BloomExpression *expr, const std::vector<const std::string *> &scan, RowMatcher &host_matcher,
+                              std::vector<uint8_t> &hit, bool &on_device)
+    {
+        const MatcherProgram mp(expr);
+        return match_program_on_device(mp, bsg_match_rows_tok, "bsg_match_rows_tok", true, scan,
+                                       [&](const std::string &row) { return host_matcher.match(row); }, hit, on_device);
+    }
+
+    // And(bloom root | TRUE, substring root) in one bsg_match_rows_substr call (128 needle bytes)
     int32_t match_rows_device_substr(const BloomExpression *expr, const SubstringExpression &sub, const std::vector<const std::string *> &scan,
                                      RowMatcher &host_matcher, SubstringRowMatcher &sub_matcher, std::vector<uint8_t> &hit, bool &done)
     {
@@ -1721,35 +1734,11 @@ private:
         if (mp.prog_ops.empty()) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
         emit_substring_program(sub, mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
         mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 2));
-        if (mp.kinds.size() > 64) return kEngineOk;
-        std::vector<uint8_t> cbytes;
-        std::vector<uint32_t> coff{0};
-        for (size_t c = 0; c < mp.kinds.size(); ++c) {
-            cbytes.insert(cbytes.end(), mp.fields[c].begin(), mp.fields[c].end()); coff.push_back((uint32_t)cbytes.size());
-            cbytes.insert(cbytes.end(), mp.tokens[c].begin(), mp.tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
-        }
-        std::vector<uint8_t> bytes;
-        std::vector<uint64_t> row_off{0};
-        for (const std::string *r : scan) { bytes.insert(bytes.end(), r->begin(), r->end()); row_off.push_back(bytes.size()); }
-        std::vector<uint64_t> bits((scan.size() + 63) / 64);
-        std::vector<uint32_t> fb(scan.size());
-        uint32_t n_fb = 0;
-        const bsg_tokenizer tok = c_tokenizer();
-        count_match_call("bsg_match_rows_substr");
-        const int32_t rc = bsg_match_rows_substr(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(),
-                                                 (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok, bits.data(), fb.data(),
-                                                 (uint32_t)fb.size(), &n_fb);
-        if (rc == BSG_E_UNSUPPORTED) return kEngineOk;
-        if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
-        for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
-        for (uint32_t i = 0; i < n_fb; ++i) hit[fb[i]] = host_matcher.match(*scan[fb[i]]) && sub_matcher.match(*scan[fb[i]]);
-        done = true;
-        return kEngineOk;
+        return match_program_on_device(mp, bsg_match_rows_substr, "bsg_match_rows_substr", true, scan,
+                                       [&](const std::string &row) { return host_matcher.match(row) && sub_matcher.match(row); }, hit, done);
     }
 
-    // And(bloom root | TRUE, range root) over the scan list in one bsg_match_rows_range call; the rows it hands back (the walker's envelope,
-    // a fingerprint collision, an exponent literal on a range field) are decided by both host matchers.  done stays false (the host
-    // decides) beyond 64 conditions or what the call holds (depth, ops).
+    // And(bloom root | TRUE, range root) in one bsg_match_rows_range call (handed back as well: an exponent literal on a range field)
     int32_t match_rows_device_range(const BloomExpression *expr, const RangeExpression &range, const std::vector<const std::string *> &scan,
                                     RowMatcher &host_matcher, RangeRowMatcher &range_matcher, std::vector<uint8_t> &hit, bool &done)
     {
@@ -1757,35 +1746,12 @@ private:
         if (mp.prog_ops.empty()) mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
         emit_range_program(range, mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
         mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 2));
-        if (mp.kinds.size() > 64) return kEngineOk;
-        std::vector<uint8_t> cbytes;
-        std::vector<uint32_t> coff{0};
-        for (size_t c = 0; c < mp.kinds.size(); ++c) {
-            cbytes.insert(cbytes.end(), mp.fields[c].begin(), mp.fields[c].end()); coff.push_back((uint32_t)cbytes.size());
-            cbytes.insert(cbytes.end(), mp.tokens[c].begin(), mp.tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
-        }
-        std::vector<uint8_t> bytes;
-        std::vector<uint64_t> row_off{0};
-        for (const std::string *r : scan) { bytes.insert(bytes.end(), r->begin(), r->end()); row_off.push_back(bytes.size()); }
-        std::vector<uint64_t> bits((scan.size() + 63) / 64);
-        std::vector<uint32_t> fb(scan.size());
-        uint32_t n_fb = 0;
-        const bsg_tokenizer tok = c_tokenizer();
-        count_match_call("bsg_match_rows_range");
-        const int32_t rc = bsg_match_rows_range(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(),
-                                                (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok, bits.data(), fb.data(),
-                                                (uint32_t)fb.size(), &n_fb);
-        if (rc == BSG_E_UNSUPPORTED) return kEngineOk;
-        if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
-        for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
-        for (uint32_t i = 0; i < n_fb; ++i) hit[fb[i]] = host_matcher.match(*scan[fb[i]]) && range_matcher.match(*scan[fb[i]]);
-        done = true;
-        return kEngineOk;
+        return match_program_on_device(mp, bsg_match_rows_range, "bsg_match_rows_range", true, scan,
+                                       [&](const std::string &row) { return host_matcher.match(row) && range_matcher.match(row); }, hit, done);
     }
 
-    // And(bloom root | TRUE, regex root, substring root) over the scan list in one bsg_match_rows_regex_substr call; the rows it hands
-    // back are decided by the three host matchers (the regex one DFA-backed, as the device read the patterns).  done stays false
-    // beyond 64 conditions or what the call holds.
+    // And(bloom root | TRUE, regex root, substring root) in one bsg_match_rows_regex_substr call (the host's regex matcher DFA-backed,
+    // as the device read the patterns)
     int32_t match_rows_device_regex_substr(const BloomExpression *expr, const RegexExpression &regex, const SubstringExpression &sub,
                                            const std::vector<const std::string *> &scan, RowMatcher &host_matcher, RegexRowMatcher &host_regex,
                                            SubstringRowMatcher &sub_matcher, std::vector<uint8_t> &hit, bool &done)
@@ -1795,38 +1761,12 @@ private:
         lower_regex(regex, mp);
         emit_substring_program(sub, mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
         mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 3));
-        if (mp.kinds.size() > 64) return kEngineOk;
-        std::vector<uint8_t> cbytes;
-        std::vector<uint32_t> coff{0};
-        for (size_t c = 0; c < mp.kinds.size(); ++c) {
-            cbytes.insert(cbytes.end(), mp.fields[c].begin(), mp.fields[c].end()); coff.push_back((uint32_t)cbytes.size());
-            cbytes.insert(cbytes.end(), mp.tokens[c].begin(), mp.tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
-        }
-        std::vector<uint8_t> bytes;
-        std::vector<uint64_t> row_off{0};
-        for (const std::string *r : scan) { bytes.insert(bytes.end(), r->begin(), r->end()); row_off.push_back(bytes.size()); }
-        std::vector<uint64_t> bits((scan.size() + 63) / 64);
-        std::vector<uint32_t> fb(scan.size());
-        uint32_t n_fb = 0;
-        const bsg_tokenizer tok = c_tokenizer();
-        count_match_call("bsg_match_rows_regex_substr");
-        const int32_t rc = bsg_match_rows_regex_substr(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(),
-                                                       (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok, bits.data(),
-                                                       fb.data(), (uint32_t)fb.size(), &n_fb);
-        if (rc == BSG_E_UNSUPPORTED) return kEngineOk;
-        if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
-        for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
-        for (uint32_t i = 0; i < n_fb; ++i) {
-            const std::string &row = *scan[fb[i]];
-            hit[fb[i]] = host_matcher.match(row) && host_regex.match(row) && sub_matcher.match(row);
-        }
-        done = true;
-        return kEngineOk;
+        return match_program_on_device(mp, bsg_match_rows_regex_substr, "bsg_match_rows_regex_substr", true, scan,
+                                       [&](const std::string &row) { return host_matcher.match(row) && host_regex.match(row) && sub_matcher.match(row); }, hit, done);
     }
 
-    // And(bloom root | TRUE, regex root | TRUE, substring root | TRUE, range root) over the scan list in one
-    // bsg_match_rows_regex_substr_range call (device_match_range_text); the rows it hands back are decided by the four host matchers
-    // (the regex one DFA-backed, as the device read the patterns).  done stays false beyond 64 conditions or what the call holds.
+    // And(bloom root | TRUE, regex root | TRUE, substring root | TRUE, range root) in one bsg_match_rows_regex_substr_range call
+    // (device_match_range_text).  After BSG_E_UNSUPPORTED the route without the key decides, and only its calls are counted.
     int32_t match_rows_device_range_text(const BloomExpression *expr, const RegexExpression *regex, const SubstringExpression *sub, const RangeExpression &range,
                                          const std::vector<const std::string *> &scan, RowMatcher &host_matcher, RegexRowMatcher &host_regex,
                                          SubstringRowMatcher &sub_matcher, RangeRowMatcher &range_matcher, std::vector<uint8_t> &hit, bool &done)
@@ -1837,33 +1777,9 @@ private:
         if (sub) emit_substring_program(*sub, mp.kinds, mp.fields, mp.tokens, mp.prog_ops); else mp.prog_ops.push_back(BSG_OP(BSG_OP_TRUE, 0));
         emit_range_program(range, mp.kinds, mp.fields, mp.tokens, mp.prog_ops);
         mp.prog_ops.push_back(BSG_OP(BSG_OP_AND, 4));
-        if (mp.kinds.size() > 64) return kEngineOk;
-        std::vector<uint8_t> cbytes;
-        std::vector<uint32_t> coff{0};
-        for (size_t c = 0; c < mp.kinds.size(); ++c) {
-            cbytes.insert(cbytes.end(), mp.fields[c].begin(), mp.fields[c].end()); coff.push_back((uint32_t)cbytes.size());
-            cbytes.insert(cbytes.end(), mp.tokens[c].begin(), mp.tokens[c].end()); coff.push_back((uint32_t)cbytes.size());
-        }
-        std::vector<uint8_t> bytes;
-        std::vector<uint64_t> row_off{0};
-        for (const std::string *r : scan) { bytes.insert(bytes.end(), r->begin(), r->end()); row_off.push_back(bytes.size()); }
-        std::vector<uint64_t> bits((scan.size() + 63) / 64);
-        std::vector<uint32_t> fb(scan.size());
-        uint32_t n_fb = 0;
-        const bsg_tokenizer tok = c_tokenizer();
-        const int32_t rc = bsg_match_rows_regex_substr_range(ctx_, bytes.data(), row_off.data(), (uint32_t)scan.size(), cbytes.data(), coff.data(), mp.kinds.data(),
-                                                             (uint32_t)mp.kinds.size(), mp.prog_ops.data(), (uint32_t)mp.prog_ops.size(), &tok, bits.data(),
-                                                             fb.data(), (uint32_t)fb.size(), &n_fb);
-        if (rc == BSG_E_UNSUPPORTED) return kEngineOk;      // the route without the key decides, and only its calls are counted
-        count_match_call("bsg_match_rows_regex_substr_range");
-        if (rc) return fail(kErrGpu, bsg_last_error(ctx_));
-        for (size_t i = 0; i < scan.size(); ++i) hit[i] = (bits[i >> 6] >> (i & 63)) & 1;
-        for (uint32_t i = 0; i < n_fb; ++i) {
-            const std::string &row = *scan[fb[i]];
-            hit[fb[i]] = host_matcher.match(row) && (!regex || host_regex.match(row)) && (!sub || sub_matcher.match(row)) && range_matcher.match(row);
-        }
-        done = true;
-        return kEngineOk;
+        return match_program_on_device(mp, bsg_match_rows_regex_substr_range, "bsg_match_rows_regex_substr_range", false, scan, [&](const std::string &row) {
+            return host_matcher.match(row) && (!regex || host_regex.match(row)) && (!sub || sub_matcher.match(row)) && range_matcher.match(row);
+        }, hit, done);
     }
 
     // Hand the stored section bytes to the device as they are: CRC32C + big-endian decode run in

@@ -42,7 +42,7 @@ inline bool lookup_group(bool lookup, bool lookup_regex, bool range, bool regex,
 // The call that decides a group WITH a range condition, by the engine's wide keys (wide_rows implies wide; the lookup keys imply wide
 // too: such a group takes the wide route, bounded by 64 conditions, as a group with a needle does).
 enum class Call : uint8_t { ManyRange, WideRange, WideRangeRows };
-inline Call range_call(bool wide, bool wide_rows)
+inline Call range_group_call(bool wide, bool wide_rows)
 {
     if (wide || wide_rows) return wide_rows ? Call::WideRangeRows : Call::WideRange;
     return Call::ManyRange;
@@ -60,7 +60,7 @@ inline const char *call_name(Call c)
 // what substring_groups.hpp names.  nullptr: no call decides a table with both families (joins() keeps such a group from forming).
 inline const char *group_call_name(bool range, bool regex, bool needles, bool wide, bool wide_rows)
 {
-    if (range) return regex || needles ? nullptr : call_name(range_call(wide, wide_rows));
+    if (range) return regex || needles ? nullptr : call_name(range_group_call(wide, wide_rows));
     return bsh_subg::call_name(bsh_subg::group_call(regex, needles, wide, wide_rows));
 }
 

@@ -1,43 +1,20 @@
 // match_api.inc — C-ABI of the device row matcher (included by bloomgpu.hip).  Kernels: match.hip.h; host arithmetic: host/wide_plan.hpp.
 // Every family (bsg_match_rows / _regex / _tok, bsg_match_rows_many / _many_regex, bsg_match_rows_wide, bsg_match_rows_lookup / _lookup_regex) takes ONE path:
-//   entry point -> MatchCall (the caller's arguments) -> begin_match_call (tokenizer, program and input checks) -> the family's own
-//   checks (kinds, sets) -> lower_programs -> build_rx_blob -> match_fan_out (device cuts, parts, fallback fold) -> match_part per
+//   entry point -> MatchCall (the caller's arguments) -> begin_match_call (tokenizer, program and input checks) -> route_call (kinds)
+//   and the family's own checks (sets) -> lower_programs -> build_tables -> match_fan_out (device cuts, parts, fallback fold) -> match_part per
 //   device (buffers, condition hashing, chunked upload, one walker launch per chunk through launch_walker, results back).
 // What a family adds to a part is its PartMode (PlanePart: bit planes; WidePart: stored flags, k_eval_row_programs, pair words —
 // or, for bsg_match_rows_wide_rows, the same part with the rows policy: three more passes turn the words into tagged row lists on
 // the device, headers and payload come back instead, and match_fan_out's finish step stitches the parts into the call's result).
-// bsg_match_rows_substr / bsg_match_rows_many_substr are the single and the batched call with Substring / FieldSubstring conditions in the
-// table: build_sub_tables folds and packs the needles (host/substring_pack.hpp) where the regex calls build their blob, the part
-// uploads the 4 KiB table, and PlanePart launches the substring instances of the walker.
-// bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr take kinds 0-5 in one table: a table with both FieldRegex and substring
-// conditions gets the blob (under kRxSubLdsCap / kRxManySubLdsCap: what the needle table leaves of the 80 KiB) AND the needle tables
-// and PlanePart launches k_match_rows_regex_substr* / k_match_rows_many_regex_substr*; a table with one of the two sides is the
-// parent call's, its walker and its cap.
-// bsg_match_rows_wide_substr(_rows) is the wide call with kinds 0-5 in its table: a table with a substring condition gets the needle tables
-// (and its blob under kRxWideSubLdsCap) and WidePart launches k_match_rows_store_substr* / k_match_rows_store_regex_substr*; a table
-// without one is bsg_match_rows_wide(_rows)'s, its walkers and its cap.
-// bsg_match_rows_range / bsg_match_rows_many_range are the single and the batched call with FieldRange conditions (kind 6) in the table:
-// build_range_table checks each condition's 17 bytes and moves its flags into the kind word, the part writes the bounds over the token
-// slots of the condition's hashes once the device has hashed the table, and PlanePart launches the range instances of the walker.  A
-// table without a range condition is bsg_match_rows_tok's / bsg_match_rows_many's: its walkers and its bits.
-// bsg_match_rows_wide_range(_rows) is the wide call with kinds 0, 1, 2 and 6 in its table: build_range_table and the bounds copy as above,
-// and WidePart launches k_match_rows_store_range*; a table without a range condition is bsg_match_rows_wide(_rows)'s walkers and bits.
-// bsg_match_rows_regex_substr_range / bsg_match_rows_many_regex_substr_range take kinds 0-6 in one table.  A table without a range condition is
-// bsg_match_rows_regex_substr's / _many_regex_substr's (walkers, caps and bits), one with range conditions and no kind 3-5 is
-// bsg_match_rows_range's / _many_range's; any other table gets the blob (under kRxSubLdsCap / kRxManySubLdsCap whether or not it holds a
-// needle: the needle table is always there), the needle tables (all zero without a needle) AND the range table, chained in that order
-// (each rewrites cond_kinds from the current pointer), and PlanePart launches k_match_rows_regex_substr_range* / k_match_rows_many_regex_substr_range*.
-// bsg_match_rows_wide_regex_substr_range(_rows) is the wide call with kinds 0-6 in its table, routed as the plane calls route theirs: a table
-// without a range condition is bsg_match_rows_wide_substr(_rows)'s (walkers, caps, bits and refusals), one with range conditions and no
-// kind 3-5 is bsg_match_rows_wide_range(_rows)'s; any other table gets the three tables (the blob under kRxWideSubLdsCap needle or not, no
-// user masks) and WidePart launches k_match_rows_store_regex_substr_range*.
-// bsg_match_rows_lookup(_rows) is the wide call with another Family and a LookupPlan beside its WidePlan: WidePart then sizes the
-// flags at W words per row, places the lookup tables (host/lookup_plan.hpp) from the hashes the device made, and launches
-// match_lookup.hip.h's walker and evaluator in place of match.hip.h's.  bsg_match_rows_lookup_regex(_rows) is that call with FieldRegex
-// conditions allowed in the table: the blob is built over the DISTINCT regex conditions under the cap THIS table's LDS leaves, a u32 of
-// regex slots per set goes where the wide call's condition mask goes, and the regex instances of the lookup walker are launched.
+// Which tables a call builds, which walker serves it and what it refuses is host/match_route.hpp's: a CallSpec per entry point,
+// route() over the table's kinds, slot() and the list of the 60 walkers (DESIGN.md has the route as a table).  Here: build_tables
+// builds what the route says, launch_walker launches the slot's kernel.  The lookup calls are the wide call with another Family and a
+// LookupPlan beside its WidePlan (host/lookup_plan.hpp): W flag words per row, match_lookup.hip.h's walker and evaluator.
 
 #include <cassert>
+#include <type_traits>
+
+#include "host/match_route.hpp"
 
 namespace {
 
@@ -86,6 +63,10 @@ static_assert(sizeof(bsh_wide::PairSet) == sizeof(bsg::PairSetDesc) && offsetof(
                   BSG_ROW_LIST == bsg::kPairList && BSG_ROW_DENSE == bsg::kPairDense,
               "host/wide_plan.hpp and bloomgpu.h state the list passes' set table, scan width and tags");
 
+static_assert(bsh_route::kKindFieldToken == BSG_KIND_FIELD_TOKEN && bsh_route::kKindFieldRegex == BSG_KIND_FIELD_REGEX && bsh_route::kKindSubstring == BSG_KIND_SUBSTRING &&
+                  bsh_route::kKindFieldSubstring == BSG_KIND_FIELD_SUBSTRING && bsh_route::kKindFieldRange == BSG_KIND_FIELD_RANGE,
+              "host/match_route.hpp states bloomgpu.h's condition kinds");
+
 static_assert(bsh_lookup::kMaxConds == BSG_MATCH_LOOKUP_MAX_CONDS && bsg::lookup_lds_bytes(bsh_lookup::kMaxStringSlots, bsh_lookup::kMaxPairSlots) ==
                                                                       bsg::kMatchLookupLdsBytes,
               "host/lookup_plan.hpp and bloomgpu.h state the lookup walker's limits");
@@ -108,24 +89,20 @@ struct MatchCall {
     std::vector<uint32_t> prog_off{0};     // [n_queries + 1] into prog
     std::vector<uint32_t> rx_blob;         // build_rx_blob
     uint32_t n_rx = 0;
-    bool rx_sub = false;                   // the call is bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr (the name in traces)
-    bool no_out_bits = false;              // the call's result goes elsewhere (bsg_match_rows_wide_hist: counters): out_bits is NULL and never read
-    bool wide_sub = false;                 // the call is bsg_match_rows_wide_substr(_rows) (the name in traces)
     bool substr = false;                   // build_sub_tables: the call holds the substring walkers' tables
     bsh::NeedlePack sub;                   // ... M, START, ANY
     std::vector<uint32_t> sub_kinds;       // ... and cond_kinds with word | end bit of a substring condition's needle (match.hip.h SubLane)
-    bool range_call = false;               // the call is bsg_match_rows_range / bsg_match_rows_many_range (the name in traces)
-    bool wide_range = false;               // the call is bsg_match_rows_wide_range(_rows) (the name in traces)
-    bool wide_range_text = false;          // the call is bsg_match_rows_wide_regex_substr_range(_rows) (the name in traces)
-    bool range_text = false;               // the call is bsg_match_rows_regex_substr_range / bsg_match_rows_many_regex_substr_range (the name in traces)
-    bool three = false;                    // ... and its table holds a FieldRange condition beside a regex or substring one: the three-consumer walkers run
-    bool range = false;                    // build_range_table: the table holds a FieldRange condition, the range walkers run
+    bool range = false;                    // build_range_table: the table holds a FieldRange condition
     std::vector<uint32_t> range_conds;     // ... the conditions of kind 6,
     std::vector<uint64_t> range_bounds;    // ... lo and hi of each (two's complement), in that order
     std::vector<uint32_t> range_kinds;     // ... and cond_kinds with a range condition's flags << 8 (match.hip.h NumLane)
     bsg::TokSpec spec{};                   // tok_spec
     bool default_tok = true;
-    const bsg::TokSpec *tok() const { return default_tok ? nullptr : &spec; }
+    const bsh_route::CallSpec *call = nullptr;   // the entry point (route_call)
+    bsh_route::Route route;                // ... and what its table asks for: the tables to build, the walker's consumers, the name in traces
+    uint32_t slot = bsh_route::kNoSlot;    // ... and the walker: bsh_route::slot of the call's mode, those consumers and the tokenizer
+    bool three() const { return route.consumers == bsh_route::Consumers::RegexSubstrRange; }
+    bool need_bits() const { return call->policy != bsh_route::Policy::Hist; }   // (bsg_match_rows_wide_hist's result is its counters: out_bits is NULL and never read)
 };
 
 // What differs between the families in the shared checks: limits and the words their messages name the call by.
@@ -141,8 +118,6 @@ constexpr Family kManyFamily{bsg::kMatchManyMaxQueries, "batched", bsg::kMatchMa
 constexpr Family kWideFamily{bsh_wide::kMaxQueries, "wide", bsh_wide::kMaxOps, "call's"};
 constexpr Family kLookupFamily{bsh_wide::kMaxQueries, "lookup", bsh_wide::kMaxOps, "call's", bsh_lookup::kMaxConds};
 constexpr Family kLookupRegexFamily{bsh_wide::kMaxQueries, "lookup regex", bsh_wide::kMaxOps, "call's", bsh_lookup::kMaxConds};
-// which call match_rows_wide_call serves
-enum class WideKind { Wide, Lookup, LookupRegex };
 
 // What every row-matcher call checks of its rows and conditions (the kinds themselves are the caller's); cond_len / n_bytes out.
 int32_t check_match_inputs(const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows, const uint8_t *cond_bytes, const uint32_t *cond_off,
@@ -164,9 +139,10 @@ int32_t check_match_inputs(const uint8_t *rows, const uint64_t *row_off, uint32_
 }
 
 // The head of every call: the tokenizer spec, the query limit, the program table and check_match_inputs.
-int32_t begin_match_call(MatchCall &mc, const Family &f, const bsg_tokenizer *tok_in, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries)
+int32_t begin_match_call(MatchCall &mc, const bsh_route::CallSpec &call, const Family &f, const bsg_tokenizer *tok_in, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries)
 {
     bsg_tokenizer rec{};
+    mc.call = &call;
     if (int32_t rc = tok_spec(tok_in, rec, mc.spec, mc.default_tok)) return rc;
     if (n_queries > f.max_queries) return fail(BSG_E_UNSUPPORTED, "%u queries (one %s match call holds %u)", n_queries, f.call, f.max_queries);
     if (n_queries && !prog_off) return fail(BSG_E_INVALID, "prog_off is null");
@@ -174,7 +150,7 @@ int32_t begin_match_call(MatchCall &mc, const Family &f, const bsg_tokenizer *to
         if (prog_off[q + 1] < prog_off[q]) return fail(BSG_E_INVALID, "prog_off not monotone at %u", q);
     if (n_queries && prog_off[n_queries] > prog_off[0] && !prog_ops) return fail(BSG_E_INVALID, "prog_ops is null");
     return check_match_inputs(mc.rows, mc.row_off, mc.n_rows, mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.out_bits, mc.out_n_fallback,
-                              mc.cond_len, mc.n_bytes, f.max_conds, !mc.no_out_bits);
+                              mc.cond_len, mc.n_bytes, f.max_conds, mc.need_bits());
 }
 
 // Every query's program lowered over the identity term positions (the lookup call: over term_pos, where a repeated condition is its
@@ -260,76 +236,108 @@ static_assert(BSG_RANGE_NO_LO == bsg::kRangeNoLo && BSG_RANGE_NO_HI == bsg::kRan
                   BSG_RANGE_HI_OPEN == bsg::kRangeHiOpen && BSG_KIND_FIELD_RANGE == 6u,
               "bloomgpu.h states the range walkers' kind and flags");
 
-// ---- the twenty-four walkers: (single / many / wide / lookup) x (regex) x (default tokenizer / spec / spec with an n-gram width) ----
-// E: the mode's own argument struct (none, MatchManyArgs, MatchWideArgs, MatchLookupArgs).  Dynamic LDS: the mode's base (the lookup
-// walkers': what the launch's tables take) plus the regex blob's bytes (a call without regex conditions has no blob).
-template <class... E>
-struct Walkers {
-    void (*plain)(bsg::MatchArgs, E...);
-    void (*tok)(bsg::MatchArgs, E..., bsg::TokSpec);
-    void (*regex)(bsg::MatchArgs, bsg::RxArgs, E...);
-    void (*regex_tok)(bsg::MatchArgs, bsg::RxArgs, E..., bsg::TokSpec);
-    void (*gram)(bsg::MatchArgs, E..., bsg::TokSpec);
-    void (*regex_gram)(bsg::MatchArgs, bsg::RxArgs, E..., bsg::TokSpec);
+// ---- the sixty walkers: (single / many / wide / lookup) x (consumer set) x (default tokenizer / spec / spec with an n-gram width) ----
+// What a launch may hand a walker; each kernel takes the members its own parameter list names, in its own order.
+struct LaunchArgs {
+    hipStream_t stream;
+    hipEvent_t k0, k1;                     // one chunk's walk lies between them
+    bsg::MatchArgs a;                      // a.n_rows rows, one per lane
+    bsg::RxArgs rx;
+    bsg::SubArgs sub;
+    bsg::TokSpec tok;
+    bsg::MatchManyArgs many{};             // the mode's own argument struct (the single call has none)
+    bsg::MatchWideArgs wide{};
+    bsg::MatchLookupArgs lookup{};
+    template <class T>
+    const T &get() const
+    {
+        if constexpr (std::is_same_v<T, bsg::MatchArgs>) return a;
+        else if constexpr (std::is_same_v<T, bsg::RxArgs>) return rx;
+        else if constexpr (std::is_same_v<T, bsg::SubArgs>) return sub;
+        else if constexpr (std::is_same_v<T, bsg::TokSpec>) return tok;
+        else if constexpr (std::is_same_v<T, bsg::MatchManyArgs>) return many;
+        else if constexpr (std::is_same_v<T, bsg::MatchWideArgs>) return wide;
+        else { static_assert(std::is_same_v<T, bsg::MatchLookupArgs>, "a walker parameter LaunchArgs does not hold"); return lookup; }
+    }
 };
-constexpr Walkers<> kSingleWalkers{bsg::k_match_rows, bsg::k_match_rows_tok, bsg::k_match_rows_regex, bsg::k_match_rows_regex_tok,
-                                 bsg::k_match_rows_gram, bsg::k_match_rows_regex_gram};
-constexpr Walkers<bsg::MatchManyArgs> kManyWalkers{bsg::k_match_rows_many, bsg::k_match_rows_many_tok, bsg::k_match_rows_many_regex,
-                                                   bsg::k_match_rows_many_regex_tok, bsg::k_match_rows_many_gram, bsg::k_match_rows_many_regex_gram};
-constexpr Walkers<bsg::MatchWideArgs> kWideWalkers{bsg::k_match_rows_store, bsg::k_match_rows_store_tok, bsg::k_match_rows_store_regex,
-                                                   bsg::k_match_rows_store_regex_tok, bsg::k_match_rows_store_gram, bsg::k_match_rows_store_regex_gram};
-constexpr Walkers<bsg::MatchLookupArgs> kLookupWalkers{bsg::k_match_rows_lookup, bsg::k_match_rows_lookup_tok, bsg::k_match_rows_lookup_regex,
-                                                       bsg::k_match_rows_lookup_regex_tok, bsg::k_match_rows_lookup_gram,
-                                                       bsg::k_match_rows_lookup_regex_gram};   // regex: bsg_match_rows_lookup_regex(_rows) only
-
-// ... the six with the number consumer (bsg_match_rows_range / bsg_match_rows_many_range: no FieldRegex condition reaches them)
-constexpr Walkers<> kSingleRangeWalkers{bsg::k_match_rows_range, bsg::k_match_rows_range_tok, nullptr, nullptr, bsg::k_match_rows_range_gram, nullptr};
-constexpr Walkers<bsg::MatchManyArgs> kManyRangeWalkers{bsg::k_match_rows_many_range, bsg::k_match_rows_many_range_tok, nullptr, nullptr,
-                                                        bsg::k_match_rows_many_range_gram, nullptr};
-
-// ... and the storing walker's three (bsg_match_rows_wide_range(_rows))
-constexpr Walkers<bsg::MatchWideArgs> kWideRangeWalkers{bsg::k_match_rows_store_range, bsg::k_match_rows_store_range_tok, nullptr, nullptr,
-                                                        bsg::k_match_rows_store_range_gram, nullptr};
-
-// ... and the nine with the substring consumer: (single / many / wide) x (default tokenizer / spec / spec with an n-gram width)
-template <class... E>
-void launch_sub_walker(void (*plain)(bsg::MatchArgs, bsg::SubArgs, E...), void (*tokk)(bsg::MatchArgs, bsg::SubArgs, E..., bsg::TokSpec),
-                       void (*gramk)(bsg::MatchArgs, bsg::SubArgs, E..., bsg::TokSpec), uint32_t lds, hipStream_t stream, hipEvent_t k0, hipEvent_t k1,
-                       const bsg::MatchArgs &a, const bsg::SubArgs &sb, const bsg::TokSpec *tok, const E &...e)
+template <class... P>
+void launch_as(void (*k)(P...), uint32_t lds, const LaunchArgs &l)
 {
-    const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads), block(bsg::kIngestThreads);
-    if (tok && tok->ngram != 0u) hipExtLaunchKernelGGL(gramk, grid, block, lds, stream, k0, k1, 0, a, sb, e..., *tok);
-    else if (tok) hipExtLaunchKernelGGL(tokk, grid, block, lds, stream, k0, k1, 0, a, sb, e..., *tok);
-    else hipExtLaunchKernelGGL(plain, grid, block, lds, stream, k0, k1, 0, a, sb, e...);
+    const dim3 grid((l.a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads), block(bsg::kIngestThreads);
+    hipExtLaunchKernelGGL(k, grid, block, lds, l.stream, l.k0, l.k1, 0, l.get<P>()...);
 }
-// ... and the nine with both consumers; lds_base: the substring instance's bytes, the blob sits behind them
-template <class... E>
-void launch_rx_sub_walker(void (*plain)(bsg::MatchArgs, bsg::RxArgs, bsg::SubArgs, E...), void (*tokk)(bsg::MatchArgs, bsg::RxArgs, bsg::SubArgs, E..., bsg::TokSpec),
-                          void (*gramk)(bsg::MatchArgs, bsg::RxArgs, bsg::SubArgs, E..., bsg::TokSpec), uint32_t lds_base, hipStream_t stream, hipEvent_t k0,
-                          hipEvent_t k1, const bsg::MatchArgs &a, const bsg::RxArgs &x, const bsg::SubArgs &sb, const bsg::TokSpec *tok, const E &...e)
+template <auto K>
+void launch_thunk(uint32_t lds, const LaunchArgs &l) { launch_as(K, lds, l); }
+
+// a slot's kernel takes RxArgs iff its consumers hold regex, SubArgs iff they hold substr, the mode's struct and no other mode's,
+// TokSpec iff the tokenizer is a spec
+template <class K> struct WalkerParams;
+template <class... P>
+struct WalkerParams<void (*)(P...)> {
+    template <class T> static constexpr bool takes = (std::is_same_v<T, P> || ...);
+    static constexpr bool fits(bsh_route::Mode m, bsh_route::Consumers c, bsh_route::Tok t)
+    {
+        return takes<bsg::MatchArgs> && takes<bsg::RxArgs> == bsh_route::has_regex(c) && takes<bsg::SubArgs> == bsh_route::has_substr(c) &&
+               takes<bsg::MatchManyArgs> == (m == bsh_route::Mode::Many) && takes<bsg::MatchWideArgs> == (m == bsh_route::Mode::Wide) &&
+               takes<bsg::MatchLookupArgs> == (m == bsh_route::Mode::Lookup) && takes<bsg::TokSpec> == (t != bsh_route::Tok::Default);
+    }
+};
+#define BSG_WALKER_FITS(M, C, T, K) \
+    static_assert(WalkerParams<decltype(&bsg::K)>::fits(bsh_route::Mode::M, bsh_route::Consumers::C, bsh_route::Tok::T), #K " does not take what its slot says");
+BSH_MATCH_WALKERS(BSG_WALKER_FITS)
+#undef BSG_WALKER_FITS
+
+using WalkerLaunch = void (*)(uint32_t lds, const LaunchArgs &);
+struct WalkerTable { WalkerLaunch at[bsh_route::kSlots]; };
+constexpr WalkerTable walker_table()
 {
-    const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads), block(bsg::kIngestThreads);
-    const uint32_t lds = lds_base + x.n_words * 4;
-    if (tok && tok->ngram != 0u) hipExtLaunchKernelGGL(gramk, grid, block, lds, stream, k0, k1, 0, a, x, sb, e..., *tok);
-    else if (tok) hipExtLaunchKernelGGL(tokk, grid, block, lds, stream, k0, k1, 0, a, x, sb, e..., *tok);
-    else hipExtLaunchKernelGGL(plain, grid, block, lds, stream, k0, k1, 0, a, x, sb, e...);
+    WalkerTable t{};
+#define BSG_WALKER_SLOT(M, C, T, K) t.at[bsh_route::slot(bsh_route::Mode::M, bsh_route::Consumers::C, bsh_route::Tok::T)] = &launch_thunk<&bsg::K>;
+    BSH_MATCH_WALKERS(BSG_WALKER_SLOT)
+#undef BSG_WALKER_SLOT
+    return t;
+}
+constexpr WalkerTable kWalkers = walker_table();
+
+// the bytes of a blob cap the route names
+constexpr uint32_t cap_bytes(bsh_route::Cap c)
+{
+    switch (c) {
+    case bsh_route::Cap::Single: return bsh_rxg::kSingleLdsCap;
+    case bsh_route::Cap::SingleSub: return bsh_rxg::kSingleSubLdsCap;
+    case bsh_route::Cap::Many: return bsh_rxg::kManyLdsCap;
+    case bsh_route::Cap::ManySub: return bsh_rxg::kManySubLdsCap;
+    case bsh_route::Cap::Wide: return bsh_wide::kWideLdsCap;
+    case bsh_route::Cap::WideSub: return bsh_rxg::kWideSubLdsCap;
+    default: return 0;                     // None: no blob; Lookup: build_tables asks the call's own plan
+    }
 }
 
-// one chunk's walk: a.n_rows rows, one per lane, between the events k0 and k1
-template <class... E>
-void launch_walker(const Walkers<E...> &w, uint32_t lds_base, hipStream_t stream, hipEvent_t k0, hipEvent_t k1, const bsg::MatchArgs &a, const bsg::RxArgs &x,
-                   const bsg::TokSpec *tok, const E &...e)
+// Dynamic LDS of a slot's launch: this base plus the regex blob's bytes (a call without regex conditions has no blob).  The substring
+// consumer adds its needle table; the lookup walkers' base is what the launch's own tables take.
+constexpr uint32_t walker_lds_base(bsh_route::Mode m, bsh_route::Consumers c)
 {
-    const dim3 grid((a.n_rows + bsg::kIngestThreads - 1) / bsg::kIngestThreads), block(bsg::kIngestThreads);
-    const uint32_t lds = lds_base + x.n_words * 4;
-    assert(!x.n_rx || (w.regex && w.regex_tok));   // every family has its regex walkers; a call that takes none refuses FieldRegex conditions before it gets here
-    const bool gram = tok && tok->ngram != 0u;     // a spec with an n-gram width: its own walkers
-    if (x.n_rx && gram) hipExtLaunchKernelGGL(w.regex_gram, grid, block, lds, stream, k0, k1, 0, a, x, e..., *tok);
-    else if (gram) hipExtLaunchKernelGGL(w.gram, grid, block, lds, stream, k0, k1, 0, a, e..., *tok);
-    else if (x.n_rx && tok) hipExtLaunchKernelGGL(w.regex_tok, grid, block, lds, stream, k0, k1, 0, a, x, e..., *tok);
-    else if (x.n_rx) hipExtLaunchKernelGGL(w.regex, grid, block, lds, stream, k0, k1, 0, a, x, e...);
-    else if (tok) hipExtLaunchKernelGGL(w.tok, grid, block, lds, stream, k0, k1, 0, a, e..., *tok);
-    else hipExtLaunchKernelGGL(w.plain, grid, block, lds, stream, k0, k1, 0, a, e...);
+    const bool sub = bsh_route::has_substr(c);
+    switch (m) {
+    case bsh_route::Mode::Single: return sub ? bsg::kMatchSubLdsBytes : bsg::kMatchLdsBytes;
+    case bsh_route::Mode::Many: return sub ? bsg::kMatchManySubLdsBytes : bsg::kMatchManyLdsBytes;
+    case bsh_route::Mode::Wide: return sub ? bsg::kMatchWideSubLdsBytes : bsg::kMatchWideLdsBytes;
+    default: return 0;
+    }
+}
+
+// one chunk's walk by the call's walker (mc.slot)
+void launch_walker(const MatchCall &mc, const LaunchArgs &l)
+{
+    const bsh_route::Mode m = mc.call->mode;
+    const bsh_route::Consumers c = mc.route.consumers;
+    const uint32_t base = m == bsh_route::Mode::Lookup ? bsg::lookup_lds_bytes(l.lookup.n_str_slots, l.lookup.n_pair_slots) : walker_lds_base(m, c);
+    // a call that takes no regex walker refuses FieldRegex conditions before it gets here; the blob was built under the route's cap
+    // (the lookup call: under what this table's LDS leaves)
+    assert(mc.slot < bsh_route::kSlots && kWalkers.at[mc.slot] && (!l.rx.n_rx || bsh_route::has_regex(c)) && (!bsh_route::has_substr(c) || l.sub.table));
+    assert(m == bsh_route::Mode::Lookup ? base + l.rx.n_words * 4 <= bsh_lookup::kWorkgroupLds : l.rx.n_words * 4 <= cap_bytes(mc.route.cap));
+    assert(!mc.three() || (mc.substr && mc.range));
+    kWalkers.at[mc.slot](base + l.rx.n_words * 4, l);
 }
 
 // ---- one part: rows [r0, r1) of a call on one device ----
@@ -364,14 +372,7 @@ struct PlanePart {
     uint64_t *d_bits = nullptr, *d_smask = nullptr;
     uint32_t *d_sfirst = nullptr;
 
-    const char *tag() const
-    {
-        if (mc.range_text) return many ? "bsg_match_rows_many_regex_substr_range" : "bsg_match_rows_regex_substr_range";
-        if (mc.range_call) return many ? "bsg_match_rows_many_range" : "bsg_match_rows_range";
-        if (mc.rx_sub) return many ? "bsg_match_rows_many_regex_substr" : "bsg_match_rows_regex_substr";
-        if (mc.substr) return many ? "bsg_match_rows_many_substr" : "bsg_match_rows_substr";
-        return many ? (mc.n_rx ? "bsg_match_rows_many_regex" : "bsg_match_rows_many") : "bsg_match_rows";
-    }
+    const char *tag() const { return mc.route.trace; }
     bool prog_off() const { return many != nullptr; }
     int32_t plan(uint32_t r0, uint32_t r1)
     {
@@ -403,39 +404,9 @@ struct PlanePart {
     void launch(PartDev &p, bsg::MatchArgs &a, uint32_t rf, hipEvent_t k0, hipEvent_t k1)
     {
         a.prog = p.d_prog; a.n_ops = (uint32_t)mc.prog.size(); a.out_bits = d_bits + rf / 64;
-        if (mc.three) {                                // all three consumers: the regex_substr instances' LDS, whatever sides the table holds
-            assert(mc.substr && mc.range && p.sub.table && p.rx.n_words * 4 <= (many ? bsg::kRxManySubLdsCap : bsg::kRxSubLdsCap));
-            if (many) launch_rx_sub_walker(bsg::k_match_rows_many_regex_substr_range, bsg::k_match_rows_many_regex_substr_range_tok, bsg::k_match_rows_many_regex_substr_range_gram,
-                                           bsg::kMatchManySubLdsBytes, p.d.stream, k0, k1, a, p.rx, p.sub, mc.tok(),
-                                           bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
-            else launch_rx_sub_walker(bsg::k_match_rows_regex_substr_range, bsg::k_match_rows_regex_substr_range_tok, bsg::k_match_rows_regex_substr_range_gram,
-                                      bsg::kMatchSubLdsBytes, p.d.stream, k0, k1, a, p.rx, p.sub, mc.tok());
-            return;
-        }
-        if (mc.substr && mc.n_rx) {                    // both consumers: the blob behind the needle table
-            assert(p.rx.n_words * 4 <= (many ? bsg::kRxManySubLdsCap : bsg::kRxSubLdsCap));
-            if (many) launch_rx_sub_walker(bsg::k_match_rows_many_regex_substr, bsg::k_match_rows_many_regex_substr_tok, bsg::k_match_rows_many_regex_substr_gram,
-                                           bsg::kMatchManySubLdsBytes, p.d.stream, k0, k1, a, p.rx, p.sub, mc.tok(),
-                                           bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
-            else launch_rx_sub_walker(bsg::k_match_rows_regex_substr, bsg::k_match_rows_regex_substr_tok, bsg::k_match_rows_regex_substr_gram,
-                                      bsg::kMatchSubLdsBytes, p.d.stream, k0, k1, a, p.rx, p.sub, mc.tok());
-            return;
-        }
-        if (mc.substr) {
-            if (many) launch_sub_walker(bsg::k_match_rows_many_substr, bsg::k_match_rows_many_substr_tok, bsg::k_match_rows_many_substr_gram, bsg::kMatchManySubLdsBytes,
-                                        p.d.stream, k0, k1, a, p.sub, mc.tok(), bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
-            else launch_sub_walker(bsg::k_match_rows_substr, bsg::k_match_rows_substr_tok, bsg::k_match_rows_substr_gram, bsg::kMatchSubLdsBytes, p.d.stream, k0, k1, a,
-                                   p.sub, mc.tok());
-            return;
-        }
-        if (mc.range) {                                // the same LDS as the plain walkers: the bounds sit in the conditions' records
-            assert(!mc.n_rx);
-            if (many) launch_walker(kManyRangeWalkers, bsg::kMatchManyLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok(), bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
-            else launch_walker(kSingleRangeWalkers, bsg::kMatchLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok());
-            return;
-        }
-        if (many) launch_walker(kManyWalkers, bsg::kMatchManyLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok(), bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets});
-        else launch_walker(kSingleWalkers, bsg::kMatchLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok());
+        LaunchArgs l{p.d.stream, k0, k1, a, p.rx, p.sub, mc.spec};
+        if (many) l.many = bsg::MatchManyArgs{p.d_poff, d_sfirst, d_smask, n_words, many->n_queries, n_sets};
+        launch_walker(mc, l);
     }
     int32_t results(PartDev &p, EventList &)           // this part's words of every plane
     {
@@ -474,7 +445,6 @@ struct WidePlan {
     std::vector<uint64_t> set_word0;           // [n_sets + 1]: the first result word of the set's first pair
     const WideRowsOut *rows = nullptr;         // the rows policy: lists instead of words
     const bsh_lookup::Plan *lookup = nullptr;  // bsg_match_rows_lookup(_rows) / _lookup_regex(_rows): the table's strings, roles and pairs
-    bool lookup_regex = false;                 // ... the second of the two (the names in traces)
     const WideHistOut *hist = nullptr;         // the hist policy: bucketed counts instead of words
 };
 
@@ -521,16 +491,7 @@ struct WidePart {
     int hist_dev = 0;                                  // the device the part ran on (bsg_last_hist_ms: per device the sum of its parts)
     hipError_t hist_err = hipSuccess;                  // what a scanner launch met (launch() returns nothing)
 
-    const char *tag() const
-    {
-        if (wp.hist) return "bsg_match_rows_wide_hist";
-        if (wp.lookup_regex) return wp.rows ? "bsg_match_rows_lookup_regex_rows" : "bsg_match_rows_lookup_regex";
-        if (wp.lookup) return wp.rows ? "bsg_match_rows_lookup_rows" : "bsg_match_rows_lookup";
-        if (mc.wide_range_text) return wp.rows ? "bsg_match_rows_wide_regex_substr_range_rows" : "bsg_match_rows_wide_regex_substr_range";
-        if (mc.wide_sub) return wp.rows ? "bsg_match_rows_wide_substr_rows" : "bsg_match_rows_wide_substr";
-        if (mc.wide_range) return wp.rows ? "bsg_match_rows_wide_range_rows" : "bsg_match_rows_wide_range";
-        return wp.rows ? "bsg_match_rows_wide_rows" : "bsg_match_rows_wide";
-    }
+    const char *tag() const { return mc.route.trace; }
     bool prog_off() const { return true; }
     int32_t plan(uint32_t r0, uint32_t r1)
     {
@@ -637,37 +598,12 @@ struct WidePart {
     void launch(PartDev &p, bsg::MatchArgs &a, uint32_t rf, hipEvent_t k0, hipEvent_t k1)
     {
         if (wp.hist) launch_scanner(p, a, rf);
-        if (wp.lookup) {
-            const bsg::MatchLookupArgs lk{d_sfirst, d_spair, d_lk_str, d_lk_pair, d_lk_rec, d_sat + rf, d_state + rf, n_sets, (uint32_t)str_tab.size(),
-                                          (uint32_t)pair_tab.size(), p.n_rows, bsh_lookup::pair_shift((uint32_t)pair_tab.size()), d_lk_rxmask};
-            assert(bsg::lookup_lds_bytes(lk.n_str_slots, lk.n_pair_slots) + p.rx.n_words * 4 <= bsh_lookup::kWorkgroupLds);   // the call built the blob under this table's cap
-            launch_walker(kLookupWalkers, bsg::lookup_lds_bytes(lk.n_str_slots, lk.n_pair_slots), p.d.stream, k0, k1, a, p.rx, mc.tok(), lk);
-            return;
-        }
-        const bsg::MatchWideArgs wd{d_sfirst, d_smask, d_spair, d_sat + rf, d_state + rf, n_sets};
-        if (mc.three) {                                // all three consumers: the regex_substr instances' LDS, whatever sides the table holds
-            assert(mc.substr && mc.range && p.sub.table && p.rx.n_words * 4 <= bsg::kRxWideSubLdsCap);
-            launch_rx_sub_walker(bsg::k_match_rows_store_regex_substr_range, bsg::k_match_rows_store_regex_substr_range_tok, bsg::k_match_rows_store_regex_substr_range_gram,
-                                 bsg::kMatchWideSubLdsBytes, p.d.stream, k0, k1, a, p.rx, p.sub, mc.tok(), wd);
-            return;
-        }
-        if (mc.substr && mc.n_rx) {                    // both consumers: the blob behind the needle table
-            assert(p.rx.n_words * 4 <= bsg::kRxWideSubLdsCap);
-            launch_rx_sub_walker(bsg::k_match_rows_store_regex_substr, bsg::k_match_rows_store_regex_substr_tok, bsg::k_match_rows_store_regex_substr_gram,
-                                 bsg::kMatchWideSubLdsBytes, p.d.stream, k0, k1, a, p.rx, p.sub, mc.tok(), wd);
-            return;
-        }
-        if (mc.substr) {
-            launch_sub_walker(bsg::k_match_rows_store_substr, bsg::k_match_rows_store_substr_tok, bsg::k_match_rows_store_substr_gram, bsg::kMatchWideSubLdsBytes,
-                              p.d.stream, k0, k1, a, p.sub, mc.tok(), wd);
-            return;
-        }
-        if (mc.range) {                                // the same LDS as the plain storing walkers: the bounds sit in the conditions' records
-            assert(!mc.n_rx);
-            launch_walker(kWideRangeWalkers, bsg::kMatchWideLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok(), wd);
-            return;
-        }
-        launch_walker(kWideWalkers, bsg::kMatchWideLdsBytes, p.d.stream, k0, k1, a, p.rx, mc.tok(), wd);
+        LaunchArgs l{p.d.stream, k0, k1, a, p.rx, p.sub, mc.spec};
+        if (wp.lookup)
+            l.lookup = bsg::MatchLookupArgs{d_sfirst, d_spair, d_lk_str, d_lk_pair, d_lk_rec, d_sat + rf, d_state + rf, n_sets, (uint32_t)str_tab.size(),
+                                            (uint32_t)pair_tab.size(), p.n_rows, bsh_lookup::pair_shift((uint32_t)pair_tab.size()), d_lk_rxmask};
+        else l.wide = bsg::MatchWideArgs{d_sfirst, d_smask, d_spair, d_sat + rf, d_state + rf, n_sets};
+        launch_walker(mc, l);
     }
     int32_t results(PartDev &p, EventList &kev)        // the evaluation between two more events, then the part's words
     {
@@ -845,7 +781,7 @@ int32_t match_part(bsg_ctx *ctx, Device &d, const MatchCall &mc, uint32_t r0, ui
     p.d_ch = d_ch;
     // the three-consumer walkers copy the needle table and n_words of blob whatever the table holds: a table without a needle brings
     // its all-zero table, one without a regex condition no blob word at all
-    if (mc.three && (!mc.substr || !p.sub.table || (mc.n_rx == 0) != (p.rx.n_words == 0) || (p.rx.n_words != 0 && !p.rx.blob)))
+    if (mc.three() && (!mc.substr || !p.sub.table || (mc.n_rx == 0) != (p.rx.n_words == 0) || (p.rx.n_words != 0 && !p.rx.blob)))
         return fail(BSG_E_HIP, "%s: the needle table or the regex blob is not on the device", mode.tag());
     if (int32_t rc = mode.upload(p)) return rc;
     // The rows travel in chunks while the chunk before is being matched (RowUpload).  A surviving block is <= 10 MiB and goes in
@@ -925,62 +861,44 @@ int32_t match_fan_out(bsg_ctx *ctx, const MatchCall &mc, const uint32_t *set_fir
     return match_fan_out(ctx, mc, set_first_row, n_sets, part, [] { return (int32_t)BSG_OK; });
 }
 
-// bsg_match_rows_range / bsg_match_rows_many_range: kinds 0, 1, 2 and 6
-constexpr const char *kNoTextWithRange = "condition %u: kind %u (the range calls hold Field, Token, FieldToken and FieldRange conditions)";
-inline bool range_refuses(uint32_t kind) { return kind >= BSG_KIND_FIELD_REGEX && kind <= BSG_KIND_FIELD_SUBSTRING; }
-constexpr const char *kNoRegexWithSubstr = "condition %u: a FieldRegex condition (regex and substring conditions share bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr)";
-
-// bsg_match_rows_regex_substr_range / bsg_match_rows_many_regex_substr_range: kinds 0-6.  The table decides the path: no range condition is
-// the regex_substr call's, range conditions without a kind 3-5 the range call's, anything else the three-consumer walkers'.
-int32_t route_range_text(MatchCall &mc)
+// The call's route over its table (host/match_route.hpp), after begin_match_call: a refusal in the entry point's own words, else
+// mc.route and the walker's slot.
+int32_t route_call(MatchCall &mc, uint32_t n_queries)
 {
-    if (!mc.range_text) return BSG_OK;
-    bool has_range = false, has_text = false;
-    for (uint32_t c = 0; c < mc.n_conds; ++c) {
-        if (mc.cond_kinds[c] > BSG_KIND_FIELD_RANGE) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
-        has_range |= mc.cond_kinds[c] == BSG_KIND_FIELD_RANGE;
-        has_text |= range_refuses(mc.cond_kinds[c]);
+    using bsh_route::Refusal;
+    mc.route = bsh_route::route(*mc.call, mc.cond_kinds, mc.n_conds, n_queries);
+    const uint32_t c = mc.route.cond, kind = mc.route.kind;
+    switch (mc.route.refusal) {
+    case Refusal::None: break;
+    case Refusal::UnknownKind: return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, kind);
+    case Refusal::RegexWithSubstr:
+        return fail(BSG_E_UNSUPPORTED, "condition %u: a FieldRegex condition (regex and substring conditions share bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr)", c);
+    case Refusal::TextWithRange:
+        return fail(BSG_E_UNSUPPORTED, "condition %u: kind %u (the range calls hold Field, Token, FieldToken and FieldRange conditions)", c, kind);
+    case Refusal::RegexInBatched:
+        return fail(BSG_E_UNSUPPORTED, "condition %u: FieldRegex conditions are not matched by the batched call (use bsg_match_rows_regex)", c);
     }
-    if (!has_range) mc.rx_sub = true;
-    else if (!has_text) mc.range_call = true;
-    else mc.three = true;
-    return BSG_OK;
-}
-// ... the three tables of the last: the blob under the cap beside a needle table (there always is one), the needle tables, the bounds
-int32_t build_three_tables(MatchCall &mc, uint32_t cap, const uint64_t *users)
-{
-    if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, cap, users)) return rc;
-    if (int32_t rc = build_sub_tables(mc)) return rc;
-    return build_range_table(mc);
-}
-
-// bsg_match_rows_wide_regex_substr_range(_rows): the same three ways.  The parents' paths are taken by their own flags, so their kernels,
-// caps, bits and refusals are theirs; only the name in traces and call counts stays this call's.
-int32_t route_wide_range_text(MatchCall &mc)
-{
-    if (!mc.wide_range_text) return BSG_OK;
-    bool has_range = false, has_text = false;
-    for (uint32_t c = 0; c < mc.n_conds; ++c) {
-        if (mc.cond_kinds[c] > BSG_KIND_FIELD_RANGE) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
-        has_range |= mc.cond_kinds[c] == BSG_KIND_FIELD_RANGE;
-        has_text |= range_refuses(mc.cond_kinds[c]);
-    }
-    mc.wide_sub = !has_range;
-    mc.wide_range = has_range && !has_text;
-    mc.three = has_range && has_text;
+    const bsh_route::Tok t = mc.default_tok ? bsh_route::Tok::Default : mc.spec.ngram != 0u ? bsh_route::Tok::Gram : bsh_route::Tok::Spec;
+    mc.slot = bsh_route::slot(mc.call->mode, mc.route.consumers, t);
     return BSG_OK;
 }
 
-// which sides a table of bsg_match_rows_regex_substr / bsg_match_rows_many_regex_substr holds
-struct TableSides { bool regex = false, sub = false; };
-TableSides table_sides(const MatchCall &mc)
+// The tables mc.route asks for, in the order blob, needle tables, range table (each rewrites cond_kinds from the current pointer).
+// The batched calls' blob holds each regex condition's users (none for a batch without a query); the lookup call's is built over the
+// DISTINCT regex conditions, under what this table's strings, pairs and lanes leave of a workgroup's 80 KiB.
+int32_t build_tables(MatchCall &mc, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries, const bsh_lookup::Plan *lookup = nullptr)
 {
-    TableSides t;
-    for (uint32_t c = 0; c < mc.n_conds; ++c) {
-        t.regex |= mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX;
-        t.sub |= mc.cond_kinds[c] == BSG_KIND_SUBSTRING || mc.cond_kinds[c] == BSG_KIND_FIELD_SUBSTRING;
+    const bsh_route::Route &r = mc.route;
+    if (r.blob) {
+        std::vector<uint64_t> users;
+        if (r.user_masks) users = n_queries ? bsh_rxg::user_masks(prog_ops, prog_off, n_queries, mc.n_conds) : std::vector<uint64_t>(mc.n_conds, 0);
+        const uint32_t cap = r.cap == bsh_route::Cap::Lookup ? bsh_lookup::rx_lds_cap_of(lookup->n_strings(), (uint32_t)lookup->pairs.size()) : cap_bytes(r.cap);
+        if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, cap, r.user_masks ? users.data() : nullptr,
+                                       lookup ? &lookup->rx_conds : nullptr)) return rc;
     }
-    return t;
+    if (r.needles) if (int32_t rc = build_sub_tables(mc)) return rc;
+    if (r.range_table) if (int32_t rc = build_range_table(mc)) return rc;
+    return BSG_OK;
 }
 
 // the single and the batched calls' parts: planes over the implicit set {0, n_rows} (cuts at multiples of 64 rows)
@@ -993,50 +911,26 @@ int32_t match_planes_run(bsg_ctx *ctx, const MatchCall &mc, const ManyPlan *many
     });
 }
 
-// bsg_match_rows (max_kind 2), bsg_match_rows_regex (max_kind 3) and bsg_match_rows_tok (max_kind 3, a spec; NULL = default): the
-// one-query case of the shared checks
-// and bsg_match_rows_substr (substr: kinds 0, 1, 2, 4, 5 under a spec or NULL)
-// and bsg_match_rows_regex_substr (mc.rx_sub: kinds 0-5; the blob and the needle tables are built of what the table holds)
-int32_t match_rows_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, uint32_t n_ops, uint32_t max_kind, const bsg_tokenizer *tok_in, bool substr = false)
+// the single calls: the one-query case of the shared checks
+int32_t match_rows_call(bsg_ctx *ctx, MatchCall &mc, const bsh_route::CallSpec &call, const uint32_t *prog_ops, uint32_t n_ops, const bsg_tokenizer *tok_in)
 {
     const uint32_t prog_off[2] = {0, n_ops};
-    if (int32_t rc = begin_match_call(mc, kSingleFamily, tok_in, prog_ops, prog_off, 1)) return rc;
-    if (int32_t rc = route_range_text(mc)) return rc;
-    for (uint32_t c = 0; c < mc.n_conds; ++c) {
-        if (substr && mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX) return fail(BSG_E_UNSUPPORTED, kNoRegexWithSubstr, c);
-        if (mc.range_call && range_refuses(mc.cond_kinds[c])) return fail(BSG_E_UNSUPPORTED, kNoTextWithRange, c, mc.cond_kinds[c]);
-        if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
-    }
+    if (int32_t rc = begin_match_call(mc, call, kSingleFamily, tok_in, prog_ops, prog_off, 1)) return rc;
+    if (int32_t rc = route_call(mc, 1)) return rc;
     if (int32_t rc = lower_programs(mc, kSingleFamily, prog_ops, prog_off, 1)) return rc;
-    if (mc.three) { if (int32_t rc = build_three_tables(mc, bsg::kRxSubLdsCap, nullptr)) return rc; }
-    else if (mc.range_call) { if (int32_t rc = build_range_table(mc)) return rc; }
-    else if (mc.rx_sub) {
-        const TableSides t = table_sides(mc);
-        if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, t.sub ? bsg::kRxSubLdsCap : bsg::kRxLdsCap)) return rc;
-        if (t.sub) if (int32_t rc = build_sub_tables(mc)) return rc;
-    } else if (substr) { if (int32_t rc = build_sub_tables(mc)) return rc; }
-    else if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx)) return rc;
+    if (int32_t rc = build_tables(mc, prog_ops, prog_off, 1)) return rc;
     *mc.out_n_fallback = 0;
     if (mc.n_rows == 0) return BSG_OK;
     return match_planes_run(ctx, mc, nullptr);
 }
 
-// bsg_match_rows_many (max_kind 2) and bsg_match_rows_many_regex (max_kind 3): n_queries programs over one table of distinct
-// conditions, one upload and one walk of the rows
-int32_t match_rows_many_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
-                             const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets, const bsg_tokenizer *tok_in,
-                             uint32_t max_kind, bool substr = false)
+// the batched calls: n_queries programs over one table of distinct conditions, one upload and one walk of the rows
+int32_t match_rows_many_call(bsg_ctx *ctx, MatchCall &mc, const bsh_route::CallSpec &call, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+                             const uint32_t *set_first_row, const uint64_t *query_mask_of_set, uint32_t n_sets, const bsg_tokenizer *tok_in)
 {
-    if (int32_t rc = begin_match_call(mc, kManyFamily, tok_in, prog_ops, prog_off, n_queries)) return rc;
-    if (int32_t rc = route_range_text(mc)) return rc;
+    if (int32_t rc = begin_match_call(mc, call, kManyFamily, tok_in, prog_ops, prog_off, n_queries)) return rc;
+    if (int32_t rc = route_call(mc, n_queries)) return rc;
     const uint32_t n_rows = mc.n_rows;
-    for (uint32_t c = 0; c < mc.n_conds; ++c) {
-        if (substr && mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX) return fail(BSG_E_UNSUPPORTED, kNoRegexWithSubstr, c);
-        if (mc.range_call && range_refuses(mc.cond_kinds[c])) return fail(BSG_E_UNSUPPORTED, kNoTextWithRange, c, mc.cond_kinds[c]);
-        if (mc.cond_kinds[c] == BSG_KIND_FIELD_REGEX && max_kind < BSG_KIND_FIELD_REGEX)
-            return fail(BSG_E_UNSUPPORTED, "condition %u: FieldRegex conditions are not matched by the batched call (use bsg_match_rows_regex)", c);
-        if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
-    }
     if (n_sets) {
         if (!set_first_row || !query_mask_of_set) return fail(BSG_E_INVALID, "set table is null");
         if (set_first_row[0] != 0 || set_first_row[n_sets] != n_rows)
@@ -1049,25 +943,7 @@ int32_t match_rows_many_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
     }
     const ManyPlan plan{set_first_row, query_mask_of_set, n_sets, n_queries, ((size_t)n_rows + 63) / 64};
     if (int32_t rc = lower_programs(mc, kManyFamily, prog_ops, prog_off, n_queries)) return rc;
-    // the regex conditions' tables, each with the queries that use it (a table without any: exactly bsg_match_rows_many's kernels)
-    if (mc.three) {
-        const std::vector<uint64_t> users = n_queries ? bsh_rxg::user_masks(prog_ops, prog_off, n_queries, mc.n_conds) : std::vector<uint64_t>(mc.n_conds, 0);
-        if (int32_t rc = build_three_tables(mc, bsg::kRxManySubLdsCap, users.data())) return rc;
-    }
-    else if (mc.range_call) { if (int32_t rc = build_range_table(mc)) return rc; }
-    else if (mc.rx_sub) {
-        const TableSides t = table_sides(mc);
-        if (n_queries) {
-            const std::vector<uint64_t> users = bsh_rxg::user_masks(prog_ops, prog_off, n_queries, mc.n_conds);
-            if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx,
-                                           t.sub ? bsg::kRxManySubLdsCap : bsg::kRxManyLdsCap, users.data())) return rc;
-        }
-        if (t.sub) if (int32_t rc = build_sub_tables(mc)) return rc;
-    } else if (substr) { if (int32_t rc = build_sub_tables(mc)) return rc; }
-    else if (max_kind >= BSG_KIND_FIELD_REGEX && n_queries) {
-        const std::vector<uint64_t> users = bsh_rxg::user_masks(prog_ops, prog_off, n_queries, mc.n_conds);
-        if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, bsg::kRxManyLdsCap, users.data())) return rc;
-    }
+    if (int32_t rc = build_tables(mc, prog_ops, prog_off, n_queries)) return rc;
     if (n_queries == 0 || n_rows == 0) return BSG_OK;
     *mc.out_n_fallback = 0;
     return match_planes_run(ctx, mc, &plan);
@@ -1086,26 +962,16 @@ int32_t wide_size_status(bsh_wide::SizeStatus st, uint32_t bad_set, const uint32
     }
 }
 
-int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
+int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const bsh_route::CallSpec &call, const uint32_t *prog_ops, const uint32_t *prog_off, uint32_t n_queries,
                              const uint32_t *set_first_row, const uint32_t *set_query_off, const uint32_t *set_queries, uint32_t n_sets,
-                             const bsg_tokenizer *tok_in, const WideRowsOut *rows = nullptr, WideKind which = WideKind::Wide,
-                             const WideHistOut *hist = nullptr)
+                             const bsg_tokenizer *tok_in, const WideRowsOut *rows = nullptr, const WideHistOut *hist = nullptr)
 {
-    const bool lookup = which != WideKind::Wide, lookup_regex = which == WideKind::LookupRegex;
+    const bool lookup = call.mode == bsh_route::Mode::Lookup, lookup_regex = lookup && call.accepts == bsh_route::Accepts::Regex;
     const Family &fam = lookup_regex ? kLookupRegexFamily : lookup ? kLookupFamily : kWideFamily;
     if (rows && (!rows->len || (rows->cap && !rows->payload))) return fail(BSG_E_INVALID, "null argument");
-    if (int32_t rc = begin_match_call(mc, fam, tok_in, prog_ops, prog_off, n_queries)) return rc;
+    if (int32_t rc = begin_match_call(mc, call, fam, tok_in, prog_ops, prog_off, n_queries)) return rc;
     const uint32_t n_rows = mc.n_rows;
-    if (int32_t rc = route_wide_range_text(mc)) return rc;
-    const uint32_t max_kind = mc.wide_sub ? BSG_KIND_FIELD_SUBSTRING : BSG_KIND_FIELD_REGEX;   // kinds 4 and 5: bsg_match_rows_wide_substr(_rows) only
-    for (uint32_t c = 0; c < mc.n_conds && !mc.three; ++c) {   // (three: route_wide_range_text has seen kinds 0-6 and nothing else)
-        if (mc.wide_range) {                   // bsg_match_rows_wide_range(_rows): kinds 0, 1, 2 and 6, no text consumer beside the number one
-            if (range_refuses(mc.cond_kinds[c])) return fail(BSG_E_UNSUPPORTED, kNoTextWithRange, c, mc.cond_kinds[c]);
-            if (mc.cond_kinds[c] > BSG_KIND_FIELD_RANGE) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
-            continue;
-        }
-        if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, mc.cond_kinds[c]);
-    }
+    if (int32_t rc = route_call(mc, n_queries)) return rc;
     // the lookup call: the table's distinct role strings, their role records and the FieldToken pairs
     bsh_lookup::Plan lookup_plan;
     if (lookup) {
@@ -1118,7 +984,7 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
         }
     }
     // the sets: the caller's, or one implicit set of all rows with every query
-    WidePlan wp{set_first_row, set_query_off, set_queries, n_sets, n_queries, {}, {}, {}, rows, lookup ? &lookup_plan : nullptr, lookup_regex, hist};
+    WidePlan wp{set_first_row, set_query_off, set_queries, n_sets, n_queries, {}, {}, {}, rows, lookup ? &lookup_plan : nullptr, hist};
     std::vector<uint32_t> implicit_first, implicit_off, implicit_queries;
     if (n_sets == 0) {
         if (set_first_row || set_query_off || set_queries) return fail(BSG_E_INVALID, "a set table without its number of sets");
@@ -1142,20 +1008,7 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
             }
     }
     if (int32_t rc = lower_programs(mc, fam, prog_ops, prog_off, n_queries, lookup ? &lookup_plan.canon : nullptr)) return rc;
-    if (mc.three) {                            // kind 6 beside a text condition: the blob under the cap beside a needle table, the needle tables, the bounds
-        if (int32_t rc = build_three_tables(mc, bsg::kRxWideSubLdsCap, nullptr)) return rc;
-    } else if (mc.wide_range) {                // no regex condition reaches this call: the bounds and flags of the kind-6 ones, if any
-        if (int32_t rc = build_range_table(mc)) return rc;
-    } else if (!lookup) {
-        // a table with needles: the blob under what the needle table leaves, then the needle tables; one without: the wide call's own
-        const bool sub = mc.wide_sub && table_sides(mc).sub;
-        if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, sub ? bsg::kRxWideSubLdsCap : bsg::kRxWideLdsCap)) return rc;
-        if (sub) if (int32_t rc = build_sub_tables(mc)) return rc;
-    } else if (lookup_regex) {
-        // the DISTINCT regex conditions, under what this table's strings, pairs and lanes leave of a workgroup's 80 KiB
-        const uint32_t cap = bsh_lookup::rx_lds_cap_of(lookup_plan.n_strings(), (uint32_t)lookup_plan.pairs.size());
-        if (int32_t rc = build_rx_blob(mc.cond_bytes, mc.cond_off, mc.cond_kinds, mc.n_conds, mc.rx_blob, mc.n_rx, cap, nullptr, &lookup_plan.rx_conds)) return rc;
-    }
+    if (int32_t rc = build_tables(mc, prog_ops, prog_off, n_queries, lookup ? &lookup_plan : nullptr)) return rc;
     const uint32_t n_pairs = wp.set_query_off[wp.n_sets];
     if (rows) {                                // every pair NONE until a part says otherwise (a set without rows lies in no part)
         if (n_pairs && !rows->hdr) return fail(BSG_E_INVALID, "null argument");
@@ -1173,78 +1026,65 @@ int32_t match_rows_wide_call(bsg_ctx *ctx, MatchCall &mc, const uint32_t *prog_o
         wp.set_word0[s + 1] = wp.set_word0[s] + (uint64_t)bsh_wide::tiles_of(wp.set_first_row[s + 1] - wp.set_first_row[s]) *
                                                     (wp.set_query_off[s + 1] - wp.set_query_off[s]);
     *mc.out_n_fallback = 0;
-    if (hist) {
-        // the hist policy: every counter 0 until a part says otherwise (a set without rows lies in no part); the parts outlive their
-        // devices' work, and the finish step adds the staged counters of a set cut between parts — on one thread, in any order
-        const uint32_t slots = hist->slots();
-        memset(hist->counts, 0, (size_t)n_pairs * slots * 4);
-        std::mutex kept_mu;
-        std::vector<std::unique_ptr<WidePart>> kept;
-        return match_fan_out(
-            ctx, mc, wp.set_first_row, wp.n_sets,
-            [&](uint32_t n_parts, Device &d, uint32_t r0, uint32_t r1, std::vector<uint32_t> &fb, float *ms) -> int32_t {
-                WidePart *mode = new WidePart{mc, wp, n_parts == 1};
-                {
-                    std::lock_guard<std::mutex> lk(kept_mu);
-                    kept.emplace_back(mode);
-                }
-                return match_part(ctx, d, mc, r0, r1, *mode, fb, ms);
-            },
-            [&]() -> int32_t {
-                float ms = 0.f;
-                std::map<int, float> per_device;
-                for (const auto &k : kept) {
-                    ms = std::max(ms, per_device[k->hist_dev] += k->hist_ms);
-                    if (k->direct) continue;
-                    uint32_t *dst = hist->counts + (uint64_t)k->pair0 * slots;
-                    for (size_t i = 0; i < k->staged_counts.size(); ++i) dst[i] += k->staged_counts[i];
-                }
-                std::lock_guard<std::shared_mutex> lk(ctx->mu);
-                ctx->last_hist_ms = ms;
-                return BSG_OK;
-            });
-    }
-    if (!rows)
+    if (!rows && !hist)
         return match_fan_out(ctx, mc, wp.set_first_row, wp.n_sets,
                              [&](uint32_t n_parts, Device &d, uint32_t r0, uint32_t r1, std::vector<uint32_t> &fb, float *ms) -> int32_t {
                                  WidePart mode{mc, wp, n_parts == 1};
                                  return match_part(ctx, d, mc, r0, r1, mode, fb, ms);
                              });
-    // the rows policy: the parts outlive their devices' work, the finish step makes the call's result of them
+    // the rows and the hist policies: the parts outlive their devices' work, the finish step makes the call's result of them (on one
+    // thread, in any order)
     std::mutex kept_mu;
     std::vector<std::unique_ptr<WidePart>> kept;
-    return match_fan_out(
-        ctx, mc, wp.set_first_row, wp.n_sets,
-        [&](uint32_t n_parts, Device &d, uint32_t r0, uint32_t r1, std::vector<uint32_t> &fb, float *ms) -> int32_t {
-            WidePart *mode = new WidePart{mc, wp, n_parts == 1};
-            {
-                std::lock_guard<std::mutex> lk(kept_mu);
-                kept.emplace_back(mode);
+    auto kept_part = [&](uint32_t n_parts, Device &d, uint32_t r0, uint32_t r1, std::vector<uint32_t> &fb, float *ms) -> int32_t {
+        WidePart *mode = new WidePart{mc, wp, n_parts == 1};
+        {
+            std::lock_guard<std::mutex> lk(kept_mu);
+            kept.emplace_back(mode);
+        }
+        return match_part(ctx, d, mc, r0, r1, *mode, fb, ms);
+    };
+    if (hist) {
+        // every counter 0 until a part says otherwise (a set without rows lies in no part); the finish step adds the staged counters
+        // of a set cut between parts
+        const uint32_t slots = hist->slots();
+        memset(hist->counts, 0, (size_t)n_pairs * slots * 4);
+        return match_fan_out(ctx, mc, wp.set_first_row, wp.n_sets, kept_part, [&]() -> int32_t {
+            float ms = 0.f;
+            std::map<int, float> per_device;
+            for (const auto &k : kept) {
+                ms = std::max(ms, per_device[k->hist_dev] += k->hist_ms);
+                if (k->direct) continue;
+                uint32_t *dst = hist->counts + (uint64_t)k->pair0 * slots;
+                for (size_t i = 0; i < k->staged_counts.size(); ++i) dst[i] += k->staged_counts[i];
             }
-            return match_part(ctx, d, mc, r0, r1, *mode, fb, ms);
-        },
-        [&]() -> int32_t {
-            uint64_t len = 0;
-            std::vector<bsh_wide::PartRows> parts;
-            if (kept.size() == 1) {                    // direct: the headers are the call's already, and the payload if it fits
-                len = kept[0]->payload_len;
-            } else {
-                std::sort(kept.begin(), kept.end(), [](const auto &a, const auto &b) { return a->ps.s0 != b->ps.s0 ? a->ps.s0 < b->ps.s0 : a->ps.tile0[0] < b->ps.tile0[0]; });
-                for (const auto &k : kept) {
-                    if (!k->n_pairs) continue;
-                    parts.push_back(bsh_wide::PartRows{&k->ps, k->staged_hdr.data(), k->staged_payload.data(), std::vector<uint64_t>((size_t)k->n_pairs + 1)});
-                    bsh_wide::pair_payload_offsets(parts.back().hdr, k->ps.first_row.data(), k->ps.pair_off.data(), k->n_sets, parts.back().off.data());
-                }
-                len = bsh_wide::stitch_headers(parts, wp.set_first_row, wp.set_query_off, wp.n_sets, rows->hdr);
-            }
-            *rows->len = len;
-            if (rows->off) bsh_wide::pair_payload_offsets(rows->hdr, wp.set_first_row, wp.set_query_off, wp.n_sets, rows->off);
-            if (len > rows->cap)
-                return fail(BSG_E_INVALID, "the matches take %llu u32 of payload, caller's buffer holds %llu", (unsigned long long)len,
-                            (unsigned long long)rows->cap);
-            if (kept.size() != 1) bsh_wide::stitch_payloads(parts, wp.set_first_row, wp.set_query_off, wp.n_sets, rows->hdr, rows->payload);
+            std::lock_guard<std::shared_mutex> lk(ctx->mu);
+            ctx->last_hist_ms = ms;
             return BSG_OK;
         });
+    }
+    return match_fan_out(ctx, mc, wp.set_first_row, wp.n_sets, kept_part, [&]() -> int32_t {
+        uint64_t len = 0;
+        std::vector<bsh_wide::PartRows> parts;
+        if (kept.size() == 1) {                    // direct: the headers are the call's already, and the payload if it fits
+            len = kept[0]->payload_len;
+        } else {
+            std::sort(kept.begin(), kept.end(), [](const auto &a, const auto &b) { return a->ps.s0 != b->ps.s0 ? a->ps.s0 < b->ps.s0 : a->ps.tile0[0] < b->ps.tile0[0]; });
+            for (const auto &k : kept) {
+                if (!k->n_pairs) continue;
+                parts.push_back(bsh_wide::PartRows{&k->ps, k->staged_hdr.data(), k->staged_payload.data(), std::vector<uint64_t>((size_t)k->n_pairs + 1)});
+                bsh_wide::pair_payload_offsets(parts.back().hdr, k->ps.first_row.data(), k->ps.pair_off.data(), k->n_sets, parts.back().off.data());
+            }
+            len = bsh_wide::stitch_headers(parts, wp.set_first_row, wp.set_query_off, wp.n_sets, rows->hdr);
+        }
+        *rows->len = len;
+        if (rows->off) bsh_wide::pair_payload_offsets(rows->hdr, wp.set_first_row, wp.set_query_off, wp.n_sets, rows->off);
+        if (len > rows->cap)
+            return fail(BSG_E_INVALID, "the matches take %llu u32 of payload, caller's buffer holds %llu", (unsigned long long)len,
+                        (unsigned long long)rows->cap);
+        if (kept.size() != 1) bsh_wide::stitch_payloads(parts, wp.set_first_row, wp.set_query_off, wp.n_sets, rows->hdr, rows->payload);
+        return BSG_OK;
+    });
 }
 
 }  // namespace
@@ -1260,7 +1100,7 @@ int32_t bsg_match_rows_wide(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *r
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
+    return match_rows_wide_call(ctx, mc, bsh_route::kWide, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
 }
 
 int32_t bsg_match_rows_wide_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1277,7 +1117,7 @@ int32_t bsg_match_rows_wide_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
                  fallback_cap, out_n_fallback};
     const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
+    return match_rows_wide_call(ctx, mc, bsh_route::kWideRows, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
 }
 
 int32_t bsg_match_rows_wide_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1289,8 +1129,7 @@ int32_t bsg_match_rows_wide_substr(bsg_ctx *ctx, const uint8_t *rows, const uint
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    mc.wide_sub = true;
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
+    return match_rows_wide_call(ctx, mc, bsh_route::kWideSubstr, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
 }
 
 int32_t bsg_match_rows_wide_substr_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1304,9 +1143,8 @@ int32_t bsg_match_rows_wide_substr_rows(bsg_ctx *ctx, const uint8_t *rows, const
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
                  fallback_cap, out_n_fallback};
-    mc.wide_sub = true;
     const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
+    return match_rows_wide_call(ctx, mc, bsh_route::kWideSubstrRows, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
 }
 
 int32_t bsg_match_rows_wide_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1318,8 +1156,7 @@ int32_t bsg_match_rows_wide_range(bsg_ctx *ctx, const uint8_t *rows, const uint6
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    mc.wide_range = true;
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
+    return match_rows_wide_call(ctx, mc, bsh_route::kWideRange, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
 }
 
 int32_t bsg_match_rows_wide_range_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1333,9 +1170,8 @@ int32_t bsg_match_rows_wide_range_rows(bsg_ctx *ctx, const uint8_t *rows, const 
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
                  fallback_cap, out_n_fallback};
-    mc.wide_range = true;
     const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
+    return match_rows_wide_call(ctx, mc, bsh_route::kWideRangeRows, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
 }
 
 int32_t bsg_match_rows_wide_regex_substr_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1347,8 +1183,7 @@ int32_t bsg_match_rows_wide_regex_substr_range(bsg_ctx *ctx, const uint8_t *rows
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    mc.wide_range_text = true;
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
+    return match_rows_wide_call(ctx, mc, bsh_route::kWideRegexSubstrRange, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
 }
 
 int32_t bsg_match_rows_wide_regex_substr_range_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1362,9 +1197,8 @@ int32_t bsg_match_rows_wide_regex_substr_range_rows(bsg_ctx *ctx, const uint8_t 
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
                  fallback_cap, out_n_fallback};
-    mc.wide_range_text = true;
     const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
+    return match_rows_wide_call(ctx, mc, bsh_route::kWideRegexSubstrRangeRows, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
 }
 
 int32_t bsg_match_rows_wide_hist(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1383,13 +1217,11 @@ int32_t bsg_match_rows_wide_hist(bsg_ctx *ctx, const uint8_t *rows, const uint64
     if (field_len == 0 || field_len > BSG_MINMAX_MAX_NAME)
         return fail(BSG_E_INVALID, "field_len is %u (a name of 1 to %u bytes)", field_len, BSG_MINMAX_MAX_NAME);
     if (!out_counts) return fail(BSG_E_INVALID, "out_counts is null");
-    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, nullptr, out_fallback_rows, fallback_cap, out_n_fallback};
-    mc.no_out_bits = true;                 // the counters are the result (checked above)
-    mc.wide_range_text = true;
+    MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, nullptr, out_fallback_rows, fallback_cap, out_n_fallback};   // the counters are the result (checked above)
     WideHistOut out{{}, origin, width, n_buckets, out_counts};
     memcpy(out.field.name, field, field_len);
     out.field.len = field_len;
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, nullptr, WideKind::Wide, &out);
+    return match_rows_wide_call(ctx, mc, bsh_route::kWideHist, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, nullptr, &out);
 }
 
 int32_t bsg_last_hist_ms(bsg_ctx *ctx, float *hist_ms)
@@ -1410,7 +1242,7 @@ int32_t bsg_match_rows_lookup(bsg_ctx *ctx, const uint8_t *rows, const uint64_t 
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, nullptr, WideKind::Lookup);
+    return match_rows_wide_call(ctx, mc, bsh_route::kLookup, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
 }
 
 int32_t bsg_match_rows_lookup_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1425,7 +1257,7 @@ int32_t bsg_match_rows_lookup_rows(bsg_ctx *ctx, const uint8_t *rows, const uint
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
                  fallback_cap, out_n_fallback};
     const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out, WideKind::Lookup);
+    return match_rows_wide_call(ctx, mc, bsh_route::kLookupRows, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
 }
 
 int32_t bsg_match_rows_lookup_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1437,7 +1269,7 @@ int32_t bsg_match_rows_lookup_regex(bsg_ctx *ctx, const uint8_t *rows, const uin
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, nullptr, WideKind::LookupRegex);
+    return match_rows_wide_call(ctx, mc, bsh_route::kLookupRegex, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok);
 }
 
 int32_t bsg_match_rows_lookup_regex_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1452,7 +1284,7 @@ int32_t bsg_match_rows_lookup_regex_rows(bsg_ctx *ctx, const uint8_t *rows, cons
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, reinterpret_cast<uint64_t *>(out_payload_len), out_fallback_rows,
                  fallback_cap, out_n_fallback};
     const WideRowsOut out{out_pair_hdr, out_pair_off, out_payload, payload_cap, out_payload_len};
-    return match_rows_wide_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out, WideKind::LookupRegex);
+    return match_rows_wide_call(ctx, mc, bsh_route::kLookupRegexRows, prog_ops, prog_off, n_queries, set_first_row, set_query_off, set_queries, n_sets, tok, &out);
 }
 
 int32_t bsg_match_pair_rows_list(uint32_t hdr, const uint32_t *payload, uint32_t set_rows, uint32_t *out_rows, uint32_t cap, uint32_t *out_n)
@@ -1480,7 +1312,7 @@ int32_t bsg_match_rows(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_of
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_TOKEN, nullptr);
+    return match_rows_call(ctx, mc, bsh_route::kRows, prog_ops, n_ops, nullptr);
 }
 
 int32_t bsg_match_rows_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1490,7 +1322,7 @@ int32_t bsg_match_rows_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_REGEX, nullptr);
+    return match_rows_call(ctx, mc, bsh_route::kRowsRegex, prog_ops, n_ops, nullptr);
 }
 
 int32_t bsg_match_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1500,7 +1332,7 @@ int32_t bsg_match_rows_tok(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *ro
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_REGEX, tok);
+    return match_rows_call(ctx, mc, bsh_route::kRowsTok, prog_ops, n_ops, tok);
 }
 
 int32_t bsg_match_rows_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1510,7 +1342,7 @@ int32_t bsg_match_rows_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t 
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_SUBSTRING, tok, true);
+    return match_rows_call(ctx, mc, bsh_route::kRowsSubstr, prog_ops, n_ops, tok);
 }
 
 int32_t bsg_match_rows_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1520,8 +1352,7 @@ int32_t bsg_match_rows_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    mc.range_call = true;
-    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_RANGE, tok);
+    return match_rows_call(ctx, mc, bsh_route::kRowsRange, prog_ops, n_ops, tok);
 }
 
 int32_t bsg_match_rows_many_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1532,8 +1363,7 @@ int32_t bsg_match_rows_many_range(bsg_ctx *ctx, const uint8_t *rows, const uint6
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    mc.range_call = true;
-    return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_RANGE);
+    return match_rows_many_call(ctx, mc, bsh_route::kManyRange, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok);
 }
 
 int32_t bsg_match_rows_many_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1544,7 +1374,7 @@ int32_t bsg_match_rows_many_substr(bsg_ctx *ctx, const uint8_t *rows, const uint
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_SUBSTRING, true);
+    return match_rows_many_call(ctx, mc, bsh_route::kManySubstr, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok);
 }
 
 int32_t bsg_match_rows_regex_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1554,8 +1384,7 @@ int32_t bsg_match_rows_regex_substr(bsg_ctx *ctx, const uint8_t *rows, const uin
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    mc.rx_sub = true;
-    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_SUBSTRING, tok);
+    return match_rows_call(ctx, mc, bsh_route::kRowsRegexSubstr, prog_ops, n_ops, tok);
 }
 
 int32_t bsg_match_rows_many_regex_substr(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1566,8 +1395,7 @@ int32_t bsg_match_rows_many_regex_substr(bsg_ctx *ctx, const uint8_t *rows, cons
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    mc.rx_sub = true;
-    return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_SUBSTRING);
+    return match_rows_many_call(ctx, mc, bsh_route::kManyRegexSubstr, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok);
 }
 
 int32_t bsg_match_rows_regex_substr_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1577,8 +1405,7 @@ int32_t bsg_match_rows_regex_substr_range(bsg_ctx *ctx, const uint8_t *rows, con
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    mc.range_text = true;
-    return match_rows_call(ctx, mc, prog_ops, n_ops, BSG_KIND_FIELD_RANGE, tok);
+    return match_rows_call(ctx, mc, bsh_route::kRowsRegexSubstrRange, prog_ops, n_ops, tok);
 }
 
 int32_t bsg_match_rows_many_regex_substr_range(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1589,8 +1416,7 @@ int32_t bsg_match_rows_many_regex_substr_range(bsg_ctx *ctx, const uint8_t *rows
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    mc.range_text = true;
-    return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_RANGE);
+    return match_rows_many_call(ctx, mc, bsh_route::kManyRegexSubstrRange, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok);
 }
 
 int32_t bsg_match_rows_many(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1601,7 +1427,7 @@ int32_t bsg_match_rows_many(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *r
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_TOKEN);
+    return match_rows_many_call(ctx, mc, bsh_route::kMany, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok);
 }
 
 int32_t bsg_match_rows_many_regex(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -1612,7 +1438,7 @@ int32_t bsg_match_rows_many_regex(bsg_ctx *ctx, const uint8_t *rows, const uint6
 {
     BSG_ENTER(ctx);
     MatchCall mc{rows, row_off, n_rows, cond_bytes, cond_off, cond_kinds, n_conds, out_bits, out_fallback_rows, fallback_cap, out_n_fallback};
-    return match_rows_many_call(ctx, mc, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok, BSG_KIND_FIELD_REGEX);
+    return match_rows_many_call(ctx, mc, bsh_route::kManyRegex, prog_ops, prog_off, n_queries, set_first_row, query_mask_of_set, n_sets, tok);
 }
 
 int32_t bsg_pinned_alloc(bsg_ctx *ctx, uint64_t n_bytes, void **out_ptr)

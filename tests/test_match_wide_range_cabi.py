@@ -67,26 +67,34 @@ def test_the_three_walkers_add_no_lds_and_the_body_takes_range_under_wide():
     assert "static_assert(!(RANGE && (REGEX || SUB))," in text and "RANGE && (REGEX || SUB || WIDE)" not in text
     for name in ("k_match_rows_store_range", "k_match_rows_store_range_tok", "k_match_rows_store_range_gram"):
         assert len(re.findall(r"void %s\(" % name, text)) == 1, name
-    api = open(os.path.join(CSRC, "match_api.inc")).read()
-    launch = api[api.index("if (mc.range) {                                // the same LDS as the plain storing walkers"):]
-    assert "launch_walker(kWideRangeWalkers, bsg::kMatchWideLdsBytes," in launch[: launch.index("return;")]
+    # the wide mode's range slots hold these kernels and launch with the plain storing walkers' bytes (the range consumer is no substring one)
+    api, route = open(os.path.join(CSRC, "match_api.inc")).read(), open(os.path.join(CSRC, "host", "match_route.hpp")).read()
+    for suffix, tok in (("", "Default"), ("_tok", "Spec"), ("_gram", "Gram")):
+        assert re.search(r"X\(Wide, Range, %s, k_match_rows_store_range%s\)" % (tok, suffix), route), suffix
+    assert "case bsh_route::Mode::Wide: return sub ? bsg::kMatchWideSubLdsBytes : bsg::kMatchWideLdsBytes;" in api
+    assert "has_substr(Consumers c) { return c == Consumers::Substr || c == Consumers::RegexSubstr || c == Consumers::RegexSubstrRange; }" in route
 
 
 def test_only_the_two_entry_points_let_kind_6_into_the_wide_call():
-    api = open(os.path.join(CSRC, "match_api.inc")).read()
-    assert api.count("mc.wide_range = true;") == 2
-    for name in ("bsg_match_rows_wide", "bsg_match_rows_wide_rows", "bsg_match_rows_wide_substr", "bsg_match_rows_wide_substr_rows", "bsg_match_rows_lookup",
-                 "bsg_match_rows_lookup_rows", "bsg_match_rows_lookup_regex", "bsg_match_rows_lookup_regex_rows"):
+    api, route = open(os.path.join(CSRC, "match_api.inc")).read(), open(os.path.join(CSRC, "host", "match_route.hpp")).read()
+    accepts = dict(re.findall(r'constexpr CallSpec (k\w+)\{"bsg_match_rows\w*", Mode::\w+, Accepts::(\w+)', route))
+    accepts.update({k: accepts[p] for k, p in re.findall(r"constexpr CallSpec (k\w+) = with_policy\((k\w+),", route)})
+    assert sorted(k for k, a in accepts.items() if k.startswith(("kWide", "kLookup")) and a == "Range") == ["kWideRange", "kWideRangeRows"]
+    for name, spec in (("bsg_match_rows_wide", "kWide"), ("bsg_match_rows_wide_rows", "kWideRows"), ("bsg_match_rows_wide_substr", "kWideSubstr"),
+                       ("bsg_match_rows_wide_substr_rows", "kWideSubstrRows"), ("bsg_match_rows_lookup", "kLookup"), ("bsg_match_rows_lookup_rows", "kLookupRows"),
+                       ("bsg_match_rows_lookup_regex", "kLookupRegex"), ("bsg_match_rows_lookup_regex_rows", "kLookupRegexRows"),
+                       ("bsg_match_rows_wide_range", "kWideRange"), ("bsg_match_rows_wide_range_rows", "kWideRangeRows")):
         entry = api[api.index("int32_t %s(bsg_ctx" % name):]
-        assert "wide_range" not in entry[: entry.index("\n}\n")], name
-    for name in ("bsg_match_rows_wide_range", "bsg_match_rows_wide_range_rows"):
-        entry = api[api.index("int32_t %s(bsg_ctx" % name):]
-        assert "mc.wide_range = true;" in entry[: entry.index("\n}\n")], name
+        assert re.findall(r"bsh_route::(k\w+)", entry[: entry.index("\n}\n")]) == [spec], name
+        assert accepts[spec] in (("Range",) if "range" in name else ("Plain", "Regex", "RegexSubstr")), name      # kind 6 passes only the two
     body = api[api.index("int32_t match_rows_wide_call("): api.index("}  // namespace", api.index("int32_t match_rows_wide_call("))]
     # kinds 3-5 are named and unsupported, a kind above 6 unknown, and the bounds are built by the function the other range calls use
-    assert "if (range_refuses(mc.cond_kinds[c])) return fail(BSG_E_UNSUPPORTED, kNoTextWithRange, c, mc.cond_kinds[c]);" in body
-    assert 'if (mc.cond_kinds[c] > BSG_KIND_FIELD_RANGE) return fail(BSG_E_INVALID, "condition %u: unknown kind %u"' in body
-    assert body.count("build_range_table(mc)") == 1 and api.count("int32_t build_range_table(") == 1
+    assert "if (int32_t rc = route_call(mc, n_queries)) return rc;" in body
+    assert "if (acc == Accepts::Range && k >= kKindFieldRegex && k <= kKindFieldSubstring) return refuse(Refusal::TextWithRange, c, k);" in route
+    assert re.search(r'case Refusal::TextWithRange:\s+return fail\(BSG_E_UNSUPPORTED, "condition %u: kind %u \(the range calls hold', api)
+    assert 'case Refusal::UnknownKind: return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, kind);' in api
+    assert "acc == Accepts::Range ? kKindFieldRange : kKindFieldSubstring;" in route
+    assert api.count("build_range_table(mc)") == 1 and api.count("int32_t build_range_table(") == 1
 
 
 def test_the_wide_batch_holds_any_number_of_range_queries():

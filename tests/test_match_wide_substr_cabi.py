@@ -50,16 +50,22 @@ def test_the_lds_constants_satisfy_the_stated_sums():
 
 
 def test_the_wide_call_still_refuses_the_kinds():
-    api = open(os.path.join(CSRC, "match_api.inc")).read()
+    api, route = open(os.path.join(CSRC, "match_api.inc")).read(), open(os.path.join(CSRC, "host", "match_route.hpp")).read()
     body = api[api.index("int32_t match_rows_wide_call("): api.index("}  // namespace", api.index("int32_t match_rows_wide_call("))]
-    # kinds 4 and 5 pass the kind check only under the flag the two new entry points set
-    assert re.search(r"max_kind = mc\.wide_sub \? BSG_KIND_FIELD_SUBSTRING : BSG_KIND_FIELD_REGEX;", body)
-    assert 'if (mc.cond_kinds[c] > max_kind) return fail(BSG_E_INVALID, "condition %u: unknown kind %u"' in body
-    assert api.count("mc.wide_sub = true;") == 2
-    for name in ("bsg_match_rows_wide", "bsg_match_rows_wide_rows", "bsg_match_rows_lookup", "bsg_match_rows_lookup_rows", "bsg_match_rows_lookup_regex",
-                 "bsg_match_rows_lookup_regex_rows"):
+    # kinds 4 and 5 pass the kind check only under the specs the two new entry points name (and the calls that take every kind)
+    assert "if (int32_t rc = route_call(mc, n_queries)) return rc;" in body
+    assert 'case Refusal::UnknownKind: return fail(BSG_E_INVALID, "condition %u: unknown kind %u", c, kind);' in api
+    assert "if (k > max_kind) return refuse(Refusal::UnknownKind, c, k);" in route
+    accepts = dict(re.findall(r'constexpr CallSpec (k\w+)\{"bsg_match_rows\w*", Mode::\w+, Accepts::(\w+)', route))
+    accepts.update({k: accepts[p] for k, p in re.findall(r"constexpr CallSpec (k\w+) = with_policy\((k\w+),", route)})
+    assert sorted(k for k, a in accepts.items() if k.startswith("kWide") and a == "RegexSubstr") == ["kWideSubstr", "kWideSubstrRows"]
+    assert all(accepts[k] in ("Plain", "Regex") for k in ("kWide", "kWideRows", "kLookup", "kLookupRows", "kLookupRegex", "kLookupRegexRows"))
+    for name, spec in (("bsg_match_rows_wide", "kWide"), ("bsg_match_rows_wide_rows", "kWideRows"), ("bsg_match_rows_lookup", "kLookup"),
+                       ("bsg_match_rows_lookup_rows", "kLookupRows"), ("bsg_match_rows_lookup_regex", "kLookupRegex"),
+                       ("bsg_match_rows_lookup_regex_rows", "kLookupRegexRows"), ("bsg_match_rows_wide_substr", "kWideSubstr"),
+                       ("bsg_match_rows_wide_substr_rows", "kWideSubstrRows")):
         entry = api[api.index("int32_t %s(bsg_ctx" % name):]
-        assert "wide_sub" not in entry[: entry.index("\n}\n")], name
+        assert re.findall(r"bsh_route::(k\w+)", entry[: entry.index("\n}\n")]) == [spec], name
 
 
 def test_the_wide_batch_holds_any_number_of_substring_queries():

@@ -105,8 +105,14 @@ def test_the_three_consumer_instances_add_no_lds():
     for name in ("k_match_rows_regex_substr_range", "k_match_rows_many_regex_substr_range"):
         for suffix in ("", "_tok", "_gram"):
             assert re.search(r"void %s%s\(" % (name, suffix), body), name + suffix
-    api = open(os.path.join(CSRC, "match_api.inc")).read()
-    assert re.search(r"k_match_rows_regex_substr_range_gram,\s+bsg::kMatchSubLdsBytes", api) and re.search(r"k_match_rows_many_regex_substr_range_gram,\s+bsg::kMatchManySubLdsBytes", api)
+    # the three-consumer slots hold these kernels, and every slot with the substring consumer launches with the needle table's bytes
+    api, route = open(os.path.join(CSRC, "match_api.inc")).read(), open(os.path.join(CSRC, "host", "match_route.hpp")).read()
+    for mode, name in (("Single", "k_match_rows_regex_substr_range"), ("Many", "k_match_rows_many_regex_substr_range")):
+        for suffix, tok in (("", "Default"), ("_tok", "Spec"), ("_gram", "Gram")):
+            assert re.search(r"X\(%s, RegexSubstrRange, %s, %s%s\)" % (mode, tok, name, suffix), route), name + suffix
+    assert re.search(r"has_substr\(Consumers c\) \{ return [^}]*c == Consumers::RegexSubstrRange; \}", route)
+    assert "case bsh_route::Mode::Single: return sub ? bsg::kMatchSubLdsBytes : bsg::kMatchLdsBytes;" in api
+    assert "case bsh_route::Mode::Many: return sub ? bsg::kMatchManySubLdsBytes : bsg::kMatchManyLdsBytes;" in api
 
 
 # ---- with a device: what the two calls refuse before a launch, and what the other entry points still answer ----

@@ -69,6 +69,12 @@ def test_the_three_storing_walkers_launch_with_the_regex_substr_instances_lds():
     for suffix in ("", "_tok", "_gram"):
         assert re.search(r"void k_match_rows_store_regex_substr_range%s\(const MatchArgs a, const RxArgs x, const SubArgs sb, const MatchWideArgs wd" % suffix, body), suffix
     assert "range conditions beside the text consumers: the single and the batched walkers only" not in body
-    api = open(os.path.join(CSRC, "match_api.inc")).read()
-    assert re.search(r"k_match_rows_store_regex_substr_range_gram,\s+bsg::kMatchWideSubLdsBytes", api)
-    assert "build_three_tables(mc, bsg::kRxWideSubLdsCap, nullptr)" in api
+    # the wide mode's three-consumer slots hold these kernels, every slot with the substring consumer launches with the needle table's
+    # bytes, and the three-consumer route builds its blob under the cap beside that table
+    api, route = open(os.path.join(CSRC, "match_api.inc")).read(), open(os.path.join(CSRC, "host", "match_route.hpp")).read()
+    for suffix, tok in (("", "Default"), ("_tok", "Spec"), ("_gram", "Gram")):
+        assert re.search(r"X\(Wide, RegexSubstrRange, %s, k_match_rows_store_regex_substr_range%s\)" % (tok, suffix), route), suffix
+    assert "case bsh_route::Mode::Wide: return sub ? bsg::kMatchWideSubLdsBytes : bsg::kMatchWideLdsBytes;" in api
+    assert re.search(r"has_substr\(Consumers c\) \{ return [^}]*c == Consumers::RegexSubstrRange; \}", route)
+    assert "case bsh_route::Cap::WideSub: return bsh_rxg::kWideSubLdsCap;" in api and "case Mode::Wide: return beside_needles ? Cap::WideSub : Cap::Wide;" in route
+    assert re.search(r"case Accepts::All:[^\n]*\n\s+r\.blob = r\.needles = r\.range_table = true; r\.cap = cap_of\(s\.mode, true\);", route)

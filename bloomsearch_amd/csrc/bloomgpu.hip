@@ -24,6 +24,7 @@
 #include "host/probe_plan.hpp" // survivor offsets, launch groups, rows layout and the host merge of a probe call
 #include "host/regex_dfa.hpp"  // FieldRegex patterns -> the DFA tables k_match_rows_regex steps
 #include "host/regex_groups.hpp"  // the regex table blob, user masks and limits shared with the engine mirror
+#include "host/ingest_plan.hpp"  // device ingest: table layout and capacities, rows per wave, union fineness, walker slot, row checks
 #include "host/row_chunks.hpp" // the chunk plan and byte ranges RowUpload copies by
 #include "host/row_groups.hpp" // the order a streaming ingest walks a chunk's rows in: stably grouped by set
 #include "host/wide_plan.hpp"  // bsg_match_rows_wide: pair words, condition masks, part cuts and evaluation items

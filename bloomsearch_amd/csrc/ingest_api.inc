@@ -12,7 +12,7 @@
 namespace {
 
 using bsg::IngestTable;
-constexpr uint64_t kSlotBytes = 40;   // four base hashes + the keyed fingerprint (kept in a parallel array behind the slots)
+using bsh::kSlotBytes;                // four base hashes + the keyed fingerprint; every size and layout rule: host/ingest_plan.hpp
 
 struct IngestPart {
     Device *dev;
@@ -159,23 +159,28 @@ int32_t tok_spec(const bsg_tokenizer *in, bsg_tokenizer &rec, bsg::TokSpec &out,
     return BSG_OK;
 }
 
-uint32_t pow2_at_least(uint64_t n)
+IngestTable as_table(const bsh::TablePlace &p) { return IngestTable{p.slots, p.fps, p.mask, p.shift}; }
+
+// Zeroed slot storage for the tables of `lay`, one block of g.mem (of min_slots at least); their descriptors go to tables[first ...].
+// counted: the block is table storage (the part's table bytes).  Caller holds the device lock and words the failure.
+hipError_t alloc_tables(IngestPart &g, const bsh::TableLayout &lay, std::vector<IngestTable> &tables, size_t first, uint64_t min_slots = 0,
+                        bool counted = true)
 {
-    uint64_t c = 64;
-    while (c < n && c < (1ull << 31)) c <<= 1;
-    return (uint32_t)c;
+    void *chunk = nullptr;
+    const uint64_t bytes = std::max(lay.total_slots, min_slots) * kSlotBytes;
+    if (hipError_t e = g.mem.alloc(&chunk, bytes); e != hipSuccess) return e;
+    if (counted) g.slot_bytes += bytes;
+    for (size_t i = 0; i < lay.cap.size(); ++i) tables[first + i] = as_table(lay.place(chunk, i));
+    return hipMemsetAsync(chunk, 0, lay.bytes(), g.dev->stream);
 }
 
-uint32_t shift_for(uint64_t cap)          // 32 - log2(cap) for a power-of-two capacity (IngestTable::shift)
+// A parent's tables get their storage in the finish step, sized from the children's exact counts; until then every one of them
+// (tables[first ...]) is the same placeholder nothing inserts into: not table storage.
+hipError_t alloc_placeholder(IngestPart &g, std::vector<IngestTable> &tables, size_t first)
 {
-    uint32_t lg = 0;
-    while ((1ull << lg) < cap) ++lg;
-    return 32u - lg;
-}
-
-IngestTable make_table(void *base, uint64_t first_slot, uint64_t total_slots, uint64_t cap)
-{   // one allocation holds every table's 32-byte slots first, then every table's 8-byte fingerprints
-    return IngestTable{(uint64_t *)base + first_slot * 4, (uint64_t *)base + total_slots * 4 + first_slot, (uint32_t)(cap - 1), shift_for(cap)};
+    const hipError_t e = alloc_tables(g, bsh::layout_tables({bsh::kMinTableSlots}), tables, first, 0, false);
+    std::fill(tables.begin() + first + 1, tables.end(), tables[first]);
+    return e;
 }
 
 int32_t push_tables(IngestPart &g)
@@ -204,13 +209,9 @@ int32_t grow_overflowed(IngestPart &g, uint32_t first, uint32_t last, uint32_t *
     std::vector<IngestTable> fresh = g.tables;
     for (uint32_t t = first; t < last; ++t) {
         if (g.status[t] != bsg::kTableOverflow) continue;
-        const uint64_t cap = ((uint64_t)g.tables[t].mask + 1) * 4;
-        if (cap > (1ull << 31)) return fail(BSG_E_NOMEM, "distinct-entry table %u would exceed 2^31 slots", t);
-        void *p = nullptr;
-        HIP_TRY(g.mem.alloc(&p, cap * kSlotBytes));
-        g.slot_bytes += cap * kSlotBytes;
-        HIP_TRY(hipMemsetAsync(p, 0, cap * kSlotBytes, g.dev->stream));
-        fresh[t] = make_table(p, 0, cap, cap);
+        const uint64_t cap = bsh::grown_slots((uint64_t)g.tables[t].mask + 1);
+        if (!cap) return fail(BSG_E_NOMEM, "distinct-entry table %u would exceed 2^31 slots", t);
+        HIP_TRY(alloc_tables(g, bsh::layout_tables({cap}), fresh, t));
         items.push_back({t, t});
     }
     if (items.empty()) return BSG_OK;
@@ -304,12 +305,9 @@ int32_t walk_chunks(Device &d, IngestPart &G, RowUpload &up, const bsg::IngestAr
             bsg::IngestArgs b = a;
             b.tables = G.d_tables;
             b.row_first = rf; b.row_end = re;
-            // as many waves as the device holds at once (BSG_INGEST_WPE per SIMD), each with a contiguous run of rows
-            const uint64_t n = re - rf, max_waves = (uint64_t)d.n_cus * 4 * BSG_INGEST_WPE;
-            const uint64_t waves = std::min<uint64_t>((n + 63) / 64, max_waves);
-            b.rows_per_wave = (uint32_t)(((n + waves - 1) / waves + 63) / 64 * 64);
-            const uint64_t used = (n + b.rows_per_wave - 1) / b.rows_per_wave, wpw = bsg::kIngestThreads / 64;
-            launch(b, (uint32_t)((used + wpw - 1) / wpw), e0, e1);
+            const bsh::WaveRuns runs = bsh::wave_runs(re - rf, d.n_cus, BSG_INGEST_WPE, bsg::kIngestThreads);
+            b.rows_per_wave = runs.rows_per_wave;
+            launch(b, runs.grid, e0, e1);
             if (first_attempt) {
                 first_attempt = false;
                 if (c + 1 < n_chunks) {                          // K(c) is running: now the next chunk's bytes
@@ -353,8 +351,8 @@ int32_t minmax_reserve(IngestPart &G, uint32_t n_sets, bool roomy)
 {
     if (!G.mm || (G.d_mm && n_sets <= G.mm_cap)) return BSG_OK;
     const uint32_t nf = G.mm->n;
-    const uint64_t room = roomy ? std::max<uint64_t>(32, (uint64_t)n_sets * 2) : std::max<uint64_t>(n_sets, 1);
-    if (room * nf > 0x7FFFFFFFull) return fail(BSG_E_INVALID, "minmax: too many sets");
+    const uint64_t room = bsh::minmax_room(n_sets, roomy, nf);
+    if (!room) return fail(BSG_E_INVALID, "minmax: too many sets");
     bsg::MinMaxRec *fresh = nullptr;
     HIP_TRY(G.mem.alloc(&fresh, (size_t)room * nf * sizeof(bsg::MinMaxRec)));
     const uint32_t n_rec = (uint32_t)(room * nf);
@@ -397,11 +395,9 @@ struct MinMaxWalk {
         HIP_TRY(ev.add(2));
         bsg::MinMaxArgs b = a;
         b.row_first = rf; b.row_end = re;
-        const uint64_t n = re - rf, max_waves = (uint64_t)d.n_cus * 4 * 8;      // a contiguous run of rows per wave, as the walkers
-        const uint64_t waves = std::min<uint64_t>((n + 63) / 64, max_waves);
-        b.rows_per_wave = (uint32_t)(((n + waves - 1) / waves + 63) / 64 * 64);
-        const uint64_t used = (n + b.rows_per_wave - 1) / b.rows_per_wave, wpw = bsg::kMinMaxThreads / 64;
-        const uint32_t grid = (uint32_t)((used + wpw - 1) / wpw), lds = bsg::minmax_lds_bytes(G.mm->n);
+        const bsh::WaveRuns runs = bsh::wave_runs(re - rf, d.n_cus, 8, bsg::kMinMaxThreads);   // a contiguous run of rows per wave, as the walkers
+        b.rows_per_wave = runs.rows_per_wave;
+        const uint32_t grid = runs.grid, lds = bsg::minmax_lds_bytes(G.mm->n);
         hipEvent_t e0 = ev.v[ev.v.size() - 2], e1 = ev.v.back();
         if (by_set) hipExtLaunchKernelGGL(bsg::k_minmax_rows_sets, dim3(grid), dim3(bsg::kMinMaxThreads), lds, d.stream, e0, e1, 0, b, *G.mm, *by_set);
         else hipExtLaunchKernelGGL(bsg::k_minmax_rows, dim3(grid), dim3(bsg::kMinMaxThreads), lds, d.stream, e0, e1, 0, b, *G.mm);
@@ -428,106 +424,78 @@ struct MinMaxWalk {
     }
 };
 
-// One part: rows [0, n_rows) of `rows` (row_off relative to `rows`), n_sets sets, on device d.
-int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
-                         const uint32_t *set_first_row, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents,
-                         const uint32_t *slots_hint, uint32_t flags, const bsg::TokSpec *tok)
+// The six walkers by bsh::walker_slot: rows grouped by set (bsg_ingest_rows) or in a staged order (bsg_ingest_append_rows), each under
+// the default tokenizer, a spec, or a spec with an n-gram width.
+struct WalkerCall { uint32_t grid; hipStream_t s; hipEvent_t e0, e1; const bsg::IngestArgs &b; const bsg::RowsBySet *by_set; const bsg::TokSpec *tok; };
+template <class... A> void walker(const WalkerCall &c, void (*kernel)(A...), A... a)
 {
-    const uint64_t n_bytes = row_off[n_rows];
-    const LabTrace trace{"bsg_ingest_rows", d.id};
-    IngestPart *g = &G;
-    g->n_rows = n_rows; g->n_sets = n_sets; g->n_parents = n_parents;
-    g->parent_of_set.assign(n_sets, 0xFFFFFFFFu);
-    if (parent_of_set) g->parent_of_set.assign(parent_of_set, parent_of_set + n_sets);
-    d.calls.fetch_add(1, std::memory_order_relaxed);
-    std::lock_guard<std::mutex> lk(d.mu);
-    if (int32_t rc = use_device(d)) return rc;
-    // What only this call needs on the device (the row bytes) is `scratch`; what the part keeps is g->mem, declared idle at the
-    // successful end only: a failed call's parts are emptied by ingest_rows_call (free_ingest), drained first like any Scratch.
-    Scratch scratch(d);
+    hipExtLaunchKernelGGL(kernel, dim3(c.grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, c.s, c.e0, c.e1, 0, a...);
+}
+void (*const kIngestWalkers[bsh::kWalkerSlots])(const WalkerCall &) = {
+    [](const WalkerCall &c) { walker(c, bsg::k_ingest_rows, c.b); },
+    [](const WalkerCall &c) { walker(c, bsg::k_ingest_rows_tok, c.b, *c.tok); },
+    [](const WalkerCall &c) { walker(c, bsg::k_ingest_rows_gram, c.b, *c.tok); },
+    [](const WalkerCall &c) { walker(c, bsg::k_ingest_rows_sets, c.b, *c.by_set); },
+    [](const WalkerCall &c) { walker(c, bsg::k_ingest_rows_sets_tok, c.b, *c.by_set, *c.tok); },
+    [](const WalkerCall &c) { walker(c, bsg::k_ingest_rows_sets_gram, c.b, *c.by_set, *c.tok); },
+};
+void launch_walker(const WalkerCall &c) { kIngestWalkers[bsh::walker_slot(c.by_set != nullptr, c.tok != nullptr, c.tok && c.tok->ngram)](c); }
 
-    // initial capacities: fields are few; tokens / field::tokens get 4 slots per row unless the caller knows better
-    const uint32_t nt = g->n_tables();
-    g->tables.assign(nt, IngestTable{nullptr, nullptr, 0, 0});
-    uint64_t total_slots = 0;
-    std::vector<uint64_t> first_slot(nt, 0);
-    for (uint32_t s = 0; s < n_sets; ++s) {
-        const uint64_t rows_in = set_first_row[s + 1] - set_first_row[s];
-        for (uint32_t c = 0; c < 3; ++c) {
-            uint64_t want = c == 0 ? 256 : std::max<uint64_t>(1024, rows_in * 4);
-            if (slots_hint && slots_hint[s * 3 + c]) want = slots_hint[s * 3 + c];
-            const uint32_t cap = pow2_at_least(want);
-            g->tables[s * 3 + c].mask = cap - 1;
-            first_slot[s * 3 + c] = total_slots;
-            total_slots += cap;
-        }
+// One row walk — a part of bsg_ingest_rows, a batch of bsg_ingest_append_rows: the rows' device buffers, the launch arguments, the
+// MinMax scanner beside the walkers, the chunk loop, the hand-back list.  The caller brings what the two differ in: the rows form
+// (by_set NULL: grouped by G.d_set_first; else the order that stage(rf, re, copy stream) sends along with each chunk's bytes) and
+// the upload `up` (chunked; or resident, after the partition pass a keyed batch runs between buffers() and walk()).
+// Caller holds the device lock.
+struct RowWalk {
+    bsg_ctx *ctx; IngestPart &G; Device &d;
+    const LabTrace &trace;                 // the caller's, started before it waited for the device
+    const uint64_t *row_off; const uint32_t n_rows;
+    Scratch scratch;                       // this call's only: the row bytes, their offsets, the hand-back list, what the caller adds
+    uint8_t *d_rows = nullptr; uint64_t *d_row_off = nullptr; uint32_t *d_fb = nullptr;
+    std::optional<RowUpload> up;
+    RowWalk(bsg_ctx *c, IngestPart &g, const LabTrace &t, const uint64_t *off, uint32_t n)
+        : ctx(c), G(g), d(*g.dev), trace(t), row_off(off), n_rows(n), scratch(*g.dev) {}
+    // the row bytes end in a zeroed 64-byte tail; G.d_nfb starts at zero
+    int32_t buffers()
+    {
+        const uint64_t n_bytes = row_off[n_rows];
+        HIP_TRY(scratch.alloc(&d_rows, n_bytes + 64));
+        HIP_TRY(scratch.alloc(&d_row_off, ((size_t)n_rows + 1) * 8));
+        HIP_TRY(scratch.alloc(&d_fb, std::max<size_t>(n_rows, 1) * 4));
+        trace.lap("device buffers allocated");
+        HIP_TRY(hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream));
+        HIP_TRY(hipMemcpyAsync(d_row_off, row_off, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemsetAsync(G.d_nfb, 0, 128, d.stream));
+        return BSG_OK;
     }
-    // 32-byte hash slots, then one 8-byte fingerprint per slot (kSlotBytes = 40 in all)
-    void *chunk = nullptr;
-    HIP_TRY(g->mem.alloc(&chunk, std::max<uint64_t>(total_slots, 1) * kSlotBytes));
-    g->slot_bytes += std::max<uint64_t>(total_slots, 1) * kSlotBytes;
-    HIP_TRY(hipMemsetAsync(chunk, 0, total_slots * kSlotBytes, d.stream));
-    for (uint32_t t = 0; t < n_sets * 3; ++t) g->tables[t] = make_table(chunk, first_slot[t], total_slots, (uint64_t)g->tables[t].mask + 1);
-    // parents get their storage in the finish step, sized from the children's exact counts; until then a
-    // parent table is a 64-slot placeholder nothing inserts into
-    if (n_parents) {
-        void *ph = nullptr;
-        HIP_TRY(g->mem.alloc(&ph, 64 * kSlotBytes));
-        HIP_TRY(hipMemsetAsync(ph, 0, 64 * kSlotBytes, d.stream));
-        for (uint32_t t = n_sets * 3; t < nt; ++t) g->tables[t] = make_table(ph, 0, 64, 64);
-    }
-    HIP_TRY(g->mem.alloc(&g->d_tables, std::max<size_t>(nt, 1) * sizeof(IngestTable)));
-    HIP_TRY(g->mem.alloc(&g->d_counts, std::max<size_t>(nt, 1) * 4));
-    HIP_TRY(g->mem.alloc(&g->d_status, std::max<size_t>(nt, 1) * 4));
-    HIP_TRY(hipMemsetAsync(g->d_counts, 0, std::max<size_t>(nt, 1) * 4, d.stream));
-    HIP_TRY(hipMemsetAsync(g->d_status, 0, std::max<size_t>(nt, 1) * 4, d.stream));
-    if (nt) if (int32_t rc = push_tables(*g)) return rc;
-    uint8_t *d_rows = nullptr;
-    uint64_t *d_row_off = nullptr; uint32_t *d_fb = nullptr;
-    HIP_TRY(scratch.alloc(&d_rows, n_bytes + 64));
-    HIP_TRY(scratch.alloc(&d_row_off, ((size_t)n_rows + 1) * 8));
-    HIP_TRY(g->mem.alloc(&g->d_set_first, ((size_t)n_sets + 1) * 4));
-    HIP_TRY(scratch.alloc(&d_fb, std::max<size_t>(n_rows, 1) * 4));
-    HIP_TRY(g->mem.alloc(&g->d_nfb, 128));
-    trace.lap("device buffers allocated");
-    HIP_TRY(hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream));
-    HIP_TRY(hipMemcpyAsync(d_row_off, row_off, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(g->d_set_first, set_first_row, ((size_t)n_sets + 1) * 4, hipMemcpyHostToDevice, d.stream));
-
-    g->stats.n_rows = n_rows;
-    g->stats.row_bytes = n_bytes;
-    if (n_rows) {
+    // Walks `up`'s rows into the sets' tables and returns with both streams synchronised; the rows handed back (the walkers' and the
+    // scanner's) join fb, which leaves ascending (with fields, merge_fallback also drops a row both listed).
+    template <class Stage>
+    int32_t walk(uint32_t flags, const bsg::TokSpec *tok, const bsg::RowsBySet *by_set, Stage &&stage, std::vector<uint32_t> &fb)
+    {
         bsg::IngestArgs a{};
-        a.rows = d_rows; a.row_off = d_row_off; a.set_first_row = g->d_set_first;
-        a.counts = g->d_counts; a.status = g->d_status; a.fallback_rows = d_fb; a.n_fallback = g->d_nfb;
-        a.n_rows = n_rows; a.n_sets = n_sets; a.validate = (flags & BSG_INGEST_TRUSTED_JSON) ? 0u : 1u;
+        a.rows = d_rows; a.row_off = d_row_off; a.set_first_row = by_set ? nullptr : G.d_set_first;
+        a.counts = G.d_counts; a.status = G.d_status; a.fallback_rows = d_fb; a.n_fallback = G.d_nfb;
+        a.n_rows = n_rows; a.n_sets = G.n_sets; a.validate = (flags & BSG_INGEST_TRUSTED_JSON) ? 0u : 1u;
         a.key = ctx->fp_key;
         if (int32_t rc = ensure_lower_table(d)) return rc;
         a.lower = d.d_lower;
-        HIP_TRY(hipMemsetAsync(G.d_nfb, 0, 128, d.stream));
-        if (int32_t rc = minmax_reserve(G, n_sets, false)) return rc;
         MinMaxWalk mmw(G);
-        if (int32_t rc = mmw.prepare(scratch, a, n_rows, nullptr)) return rc;
-        // The rows travel in chunks on the copy stream while the compute stream walks the chunk before (RowUpload)
-        RowUpload up(d, rows, d_rows, row_off, n_rows, ctx->ingest_chunk_bytes);
-        if (int32_t rc = walk_chunks(d, G, up, a, n_sets * 3, trace, [](uint32_t) { return hipSuccess; },
-                [&](const bsg::IngestArgs &b, uint32_t grid, hipEvent_t e0, hipEvent_t e1) {
-                    if (tok && tok->ngram)
-                        hipExtLaunchKernelGGL(bsg::k_ingest_rows_gram, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, *tok);
-                    else if (tok)
-                        hipExtLaunchKernelGGL(bsg::k_ingest_rows_tok, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, *tok);
-                    else
-                        hipExtLaunchKernelGGL(bsg::k_ingest_rows, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b);
-                },
+        if (int32_t rc = mmw.prepare(scratch, a, n_rows, by_set)) return rc;
+        if (up->cuts.back())
+        if (int32_t rc = walk_chunks(d, G, *up, a, G.n_sets * 3, trace,
+                [&](uint32_t c) -> hipError_t { return stage(up->cuts[c], up->cuts[c + 1], up->cs); },
+                [&](const bsg::IngestArgs &b, uint32_t grid, hipEvent_t e0, hipEvent_t e1) { launch_walker({grid, d.stream, e0, e1, b, by_set, tok}); },
                 [&](uint32_t, uint32_t rf, uint32_t re) { return mmw.launch(rf, re); })) return rc;
-        HIP_TRY(hipStreamSynchronize(d.copy_stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        if (d.copy_stream) HIP_TRY(hipStreamSynchronize(d.copy_stream));
         trace.lap("all chunks walked");
         uint32_t nfb = 0;
-        HIP_TRY(hipMemcpy(&nfb, g->d_nfb, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&nfb, G.d_nfb, 4, hipMemcpyDeviceToHost));
 #ifdef BSG_INGEST_PROF
         {
             uint64_t prof[9] = {0};
-            HIP_TRY(hipMemcpy(prof, g->d_nfb, 72, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(prof, G.d_nfb, 72, hipMemcpyDeviceToHost));
             const double waves = (n_rows + 63) / 64;
             fprintf(stderr, "[ingest prof] per 64-row tile: validate %.0f cyc, parse %.0f, hash %.0f, insert %.0f; rounds %.1f, insert rounds %.1f; "
                             "walker trips %.0f (slowest lane per round), %.0f (mean lane)\n",
@@ -535,18 +503,58 @@ int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *
                     prof[8] / waves / 64.0);
         }
 #endif
-        g->fallback.resize(nfb);
-        if (nfb) HIP_TRY(hipMemcpy(g->fallback.data(), d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
-        std::sort(g->fallback.begin(), g->fallback.end());
-        if (int32_t rc = mmw.merge_fallback(g->fallback)) return rc;
-    } else {
-        if (int32_t rc = minmax_reserve(G, n_sets, false)) return rc;
-        if (int32_t rc = read_state(*g)) return rc;
+        const size_t before = fb.size();
+        fb.resize(before + nfb);
+        if (nfb) HIP_TRY(hipMemcpy(fb.data() + before, d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
+        std::sort(fb.begin(), fb.end());
+        return mmw.merge_fallback(fb);
     }
-    g->stats.n_fallback_rows = (uint32_t)g->fallback.size();
-    // both streams have been synchronised: the row bytes leave the device with `scratch`, the part keeps the rest
-    scratch.done();
-    g->mem.done();
+};
+
+// One part: rows [0, n_rows) of `rows` (row_off relative to `rows`), n_sets sets, on device d.
+int32_t ingest_rows_part(bsg_ctx *ctx, Device &d, IngestPart &G, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
+                         const uint32_t *set_first_row, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents,
+                         const uint32_t *slots_hint, uint32_t flags, const bsg::TokSpec *tok)
+{
+    const LabTrace trace{"bsg_ingest_rows", d.id};
+    G.n_rows = n_rows; G.n_sets = n_sets; G.n_parents = n_parents;
+    G.parent_of_set.assign(n_sets, 0xFFFFFFFFu);
+    if (parent_of_set) G.parent_of_set.assign(parent_of_set, parent_of_set + n_sets);
+    d.calls.fetch_add(1, std::memory_order_relaxed);
+    std::lock_guard<std::mutex> lk(d.mu);
+    if (int32_t rc = use_device(d)) return rc;
+    // What only this call needs on the device (the row bytes) is w.scratch; what the part keeps is G.mem, declared idle at the
+    // successful end only: a failed call's parts are emptied by ingest_rows_call (free_ingest), drained first like any Scratch.
+    RowWalk w(ctx, G, trace, row_off, n_rows);
+    const uint32_t nt = G.n_tables();
+    G.tables.assign(nt, IngestTable{nullptr, nullptr, 0, 0});
+    std::vector<uint64_t> want;
+    for (uint32_t s = 0; s < n_sets; ++s)
+        for (uint32_t c = 0; c < 3; ++c)
+            want.push_back(bsh::oneshot_slots(c, set_first_row[s + 1] - set_first_row[s], slots_hint ? slots_hint[s * 3 + c] : 0));
+    HIP_TRY(alloc_tables(G, bsh::layout_tables(want), G.tables, 0, 1));
+    if (n_parents) HIP_TRY(alloc_placeholder(G, G.tables, (size_t)n_sets * 3));
+    HIP_TRY(G.mem.alloc(&G.d_tables, std::max<size_t>(nt, 1) * sizeof(IngestTable)));
+    HIP_TRY(G.mem.alloc(&G.d_counts, std::max<size_t>(nt, 1) * 4));
+    HIP_TRY(G.mem.alloc(&G.d_status, std::max<size_t>(nt, 1) * 4));
+    HIP_TRY(hipMemsetAsync(G.d_counts, 0, std::max<size_t>(nt, 1) * 4, d.stream));
+    HIP_TRY(hipMemsetAsync(G.d_status, 0, std::max<size_t>(nt, 1) * 4, d.stream));
+    if (nt) if (int32_t rc = push_tables(G)) return rc;
+    HIP_TRY(G.mem.alloc(&G.d_set_first, ((size_t)n_sets + 1) * 4));
+    HIP_TRY(G.mem.alloc(&G.d_nfb, 128));
+    if (int32_t rc = w.buffers()) return rc;
+    HIP_TRY(hipMemcpyAsync(G.d_set_first, set_first_row, ((size_t)n_sets + 1) * 4, hipMemcpyHostToDevice, d.stream));
+    G.stats.n_rows = n_rows; G.stats.row_bytes = row_off[n_rows];
+    if (int32_t rc = minmax_reserve(G, n_sets, false)) return rc;
+    if (n_rows) {
+        // The rows travel in chunks on the copy stream while the compute stream walks the chunk before (RowUpload)
+        w.up.emplace(d, rows, w.d_rows, row_off, n_rows, ctx->ingest_chunk_bytes);
+        if (int32_t rc = w.walk(flags, tok, nullptr, [](uint32_t, uint32_t, hipStream_t) { return hipSuccess; }, G.fallback)) return rc;
+    } else if (int32_t rc = read_state(G)) return rc;
+    G.stats.n_fallback_rows = (uint32_t)G.fallback.size();
+    // both streams have been synchronised: the row bytes leave the device with the walk's scratch, the part keeps the rest
+    w.scratch.done();
+    G.mem.done();
     return BSG_OK;
 }
 
@@ -556,20 +564,9 @@ int32_t union_global_tables(IngestPart &G, const std::vector<uint64_t> &sum, con
 {
     Device &d = *G.dev;
     // parent capacity from the exact child counts: 2 x (sum of children) bounds the union, so it cannot overflow
-    uint64_t total = 0;
-    std::vector<uint64_t> first(sum.size());
-    for (size_t i = 0; i < sum.size(); ++i) {
-        const uint32_t cap = pow2_at_least(std::max<uint64_t>(64, sum[i] * 2));
-        G.tables[(size_t)G.n_sets * 3 + i].mask = cap - 1;
-        first[i] = total;
-        total += cap;
-    }
-    void *chunk = nullptr;
-    HIP_TRY(G.mem.alloc(&chunk, total * kSlotBytes));
-    G.slot_bytes += total * kSlotBytes;
-    HIP_TRY(hipMemsetAsync(chunk, 0, total * kSlotBytes, d.stream));
-    for (size_t i = 0; i < sum.size(); ++i)
-        G.tables[(size_t)G.n_sets * 3 + i] = make_table(chunk, first[i], total, (uint64_t)G.tables[(size_t)G.n_sets * 3 + i].mask + 1);
+    std::vector<uint64_t> want;
+    for (uint64_t s : sum) want.push_back(bsh::parent_slots(s));
+    HIP_TRY(alloc_tables(G, bsh::layout_tables(want), G.tables, (size_t)G.n_sets * 3));
     if (int32_t rc = push_tables(G)) return rc;
     if (items.empty()) return BSG_OK;
     Scratch scratch(d);
@@ -598,29 +595,23 @@ int32_t union_partitioned(IngestPart &G, const std::vector<uint64_t> &sum, const
     for (const bsg::UnionItem &it : items) kids[it.dst - G.n_sets * 3].push_back(it.src);
     std::vector<uint32_t> child_list;
     std::vector<bsg::PartParent> parents(P3);
-    uint64_t total = 0;
-    std::vector<uint64_t> first(P3);
-    for (uint32_t t = 0; t < P3; ++t) { first[t] = total; total += sum[t]; }
-    if (total == 0) return push_tables(G);                 // every parent is empty: the placeholders stay
-    if (total > (1ull << 31)) { *fell_back = true; return BSG_OK; }
+    const bsh::TableLayout lay = bsh::layout_tables(sum, true);      // dense: room for every child entry, no memset
+    if (lay.total_slots == 0) return push_tables(G);       // every parent is empty: the placeholders stay
+    if (lay.total_slots > bsh::kMaxTableSlots) { *fell_back = true; return BSG_OK; }
     void *chunk = nullptr;
-    HIP_TRY(G.mem.alloc(&chunk, total * kSlotBytes));
-    G.slot_bytes += total * kSlotBytes;
-    uint32_t max_log2P = 0;
+    HIP_TRY(G.mem.alloc(&chunk, lay.bytes()));
+    G.slot_bytes += lay.bytes();
     for (uint32_t t = 0; t < P3; ++t) {
         bsg::PartParent &pp = parents[t];
-        pp.out_slots = (uint64_t *)chunk + first[t] * 4;
-        pp.out_fps = (uint64_t *)chunk + total * 4 + first[t];
+        const bsh::TablePlace out = lay.place(chunk, t);
+        pp.out_slots = out.slots;
+        pp.out_fps = out.fps;
         pp.cap_out = (uint32_t)sum[t];
         pp.child_begin = (uint32_t)child_list.size();
         child_list.insert(child_list.end(), kids[t].begin(), kids[t].end());
         pp.child_end = (uint32_t)child_list.size();
         pp.table = G.n_sets * 3 + t;
-        pp.log2P = 0;
-        while ((sum[t] >> pp.log2P) > bsg::kPartTarget && pp.log2P < 24) ++pp.log2P;
-        if (coarsen < 32) pp.log2P -= std::min(pp.log2P, coarsen);  // (lab: start too coarse, to exercise the retry and the fallback)
-        else pp.log2P = std::min(pp.log2P + (coarsen - 32), 24u);   // (lab: 32 + v = 2^v x FINER: runs of 2, 1, < 1 home slots per child)
-        max_log2P = std::max(max_log2P, pp.log2P);
+        pp.log2P = bsh::first_log2P(sum[t], bsg::kPartTarget, coarsen);
     }
     uint32_t *d_kids = nullptr;
     bsg::PartParent *d_parents = nullptr;
@@ -638,7 +629,7 @@ int32_t union_partitioned(IngestPart &G, const std::vector<uint64_t> &sum, const
     std::vector<bsg::PartParent> launch;
     for (int attempt = 0; attempt < 4; ++attempt) {
         launch.clear();
-        max_log2P = 0;
+        uint32_t max_log2P = 0;
         for (uint32_t t : todo) { launch.push_back(parents[t]); max_log2P = std::max(max_log2P, parents[t].log2P); }
         HIP_TRY(hipMemcpyAsync(d_parents, launch.data(), launch.size() * sizeof(bsg::PartParent), hipMemcpyHostToDevice, d.stream));
         if (todo.size() == P3) HIP_TRY(hipMemsetAsync(G.d_counts + G.n_sets * 3, 0, (size_t)P3 * 4, d.stream));
@@ -656,13 +647,13 @@ int32_t union_partitioned(IngestPart &G, const std::vector<uint64_t> &sum, const
             if (G.status[G.n_sets * 3 + t] != bsg::kTableOverflow) continue;
             again = true;
             next.push_back(t);
-            parents[t].log2P = std::min(parents[t].log2P + 2, 26u);      // 4 x finer
+            parents[t].log2P = bsh::finer_log2P(parents[t].log2P);
         }
         todo.swap(next);
         if (!again) {
             for (uint32_t t = 0; t < P3; ++t) {
                 const uint32_t n = G.counts[G.n_sets * 3 + t];
-                if (n) G.tables[G.n_sets * 3 + t] = IngestTable{parents[t].out_slots, parents[t].out_fps, n - 1, 0};      // a dense list
+                if (n) G.tables[G.n_sets * 3 + t] = as_table(bsh::place_table(chunk, lay.first_slot[t], lay.total_slots, n, true));      // a dense list
             }
             scratch.done();                // read_state has synchronised; push_tables touches neither list
             return push_tables(G);
@@ -718,9 +709,6 @@ int32_t merge_parents(bsg_ctx *ctx, Ingest &I)
     Device &H = *I.parts[0]->dev;
     struct Dense { void *buf = nullptr; uint32_t n = 0; Device *dev = nullptr; };
     std::vector<Dense> dense((size_t)np * P3);
-    auto drop_dense = [&]() {
-        for (Dense &x : dense) if (x.buf) { std::lock_guard<std::mutex> lk(x.dev->mu); (void)hipSetDevice(x.dev->id); x.dev->pool.free(x.buf); x.buf = nullptr; }
-    };
     int32_t rc = run_parts(np - 1, [&](uint32_t i) -> int32_t {
         IngestPart &G = *I.parts[i + 1];
         Device &d = *G.dev;
@@ -746,84 +734,89 @@ int32_t merge_parents(bsg_ctx *ctx, Ingest &I)
         scratch.done();
         return BSG_OK;
     });
-    if (rc) { drop_dense(); return rc; }
     auto M = std::make_shared<IngestPart>(H);
     M->n_sets = 0; M->n_parents = I.n_parents;
-    {
+    auto merge_try = [](hipError_t e) { return e == hipSuccess ? BSG_OK : fail(e == hipErrorOutOfMemory ? BSG_E_NOMEM : BSG_E_HIP, "parent merge: %s", hipGetErrorString(e)); };
+    if (!rc) {
         std::lock_guard<std::mutex> lk(H.mu);
-        if ((rc = use_device(H))) { drop_dense(); return rc; }
-        Scratch copies(H);                 // the other parts' dense lists on this device, and the union's two argument arrays
-        // capacity: 2 x the sum of the partial counts bounds the union
-        M->tables.assign(P3, IngestTable{nullptr, nullptr, 0, 0});
-        uint64_t total = 0;
-        std::vector<uint64_t> first(P3);
-        for (uint32_t t = 0; t < P3; ++t) {
-            uint64_t sum = 0;
-            for (uint32_t q = 0; q < np; ++q) sum += I.parts[q]->counts[I.parts[q]->n_sets * 3 + t];
-            const uint32_t cap = pow2_at_least(std::max<uint64_t>(64, sum * 2));
-            M->tables[t].mask = cap - 1;
-            first[t] = total;
-            total += cap;
-        }
-        void *chunk = nullptr;
-        hipError_t e = M->mem.alloc(&chunk, total * kSlotBytes);
-        if (e == hipSuccess) { M->slot_bytes += total * kSlotBytes; e = hipMemsetAsync(chunk, 0, total * kSlotBytes, H.stream); }
-        for (uint32_t t = 0; t < P3 && e == hipSuccess; ++t) M->tables[t] = make_table(chunk, first[t], total, (uint64_t)M->tables[t].mask + 1);
-        if (e == hipSuccess) e = M->mem.alloc(&M->d_tables, (size_t)P3 * sizeof(IngestTable));
-        if (e == hipSuccess) e = M->mem.alloc(&M->d_counts, (size_t)P3 * 4);
-        if (e == hipSuccess) e = M->mem.alloc(&M->d_status, (size_t)P3 * 4);
-        if (e == hipSuccess) e = hipMemsetAsync(M->d_counts, 0, (size_t)P3 * 4, H.stream);
-        if (e == hipSuccess) e = hipMemsetAsync(M->d_status, 0, (size_t)P3 * 4, H.stream);
-        // sources: part 0's partial tables in place, every other part's dense copy
-        std::vector<IngestTable> src((size_t)np * P3, IngestTable{nullptr, nullptr, 0, 0});
-        std::vector<bsg::UnionItem> items;
-        for (uint32_t t = 0; t < P3 && e == hipSuccess; ++t) {
-            src[t] = I.parts[0]->tables[I.parts[0]->n_sets * 3 + t];
-            if (I.parts[0]->counts[I.parts[0]->n_sets * 3 + t]) items.push_back({t, t});
-            for (uint32_t q = 1; q < np && e == hipSuccess; ++q) {
-                const Dense &x = dense[(size_t)q * P3 + t];
-                if (!x.n) continue;
-                void *cp = nullptr;
-                e = copies.alloc(&cp, (uint64_t)x.n * kSlotBytes);
-                if (e != hipSuccess) break;
-                e = peer_copy(ctx, dev_index(ctx, &H), cp, dev_index(ctx, x.dev), x.buf, (uint64_t)x.n * kSlotBytes, H.stream);
-                src[(size_t)q * P3 + t] = IngestTable{(uint64_t *)cp, (uint64_t *)cp + (uint64_t)x.n * 4, x.n - 1, 0};
-                items.push_back({q * P3 + t, t});
+        rc = [&]() -> int32_t {
+            if (int32_t rc2 = use_device(H)) return rc2;
+            Scratch copies(H);             // the other parts' dense lists on this device, and the union's two argument arrays
+            // capacity: 2 x the sum of the partial counts bounds the union
+            std::vector<uint64_t> want(P3, 0);
+            for (uint32_t t = 0; t < P3; ++t)
+                for (uint32_t q = 0; q < np; ++q) want[t] += I.parts[q]->counts[I.parts[q]->n_sets * 3 + t];
+            for (uint64_t &w : want) w = bsh::parent_slots(w);
+            M->tables.assign(P3, IngestTable{nullptr, nullptr, 0, 0});
+            if (int32_t rc2 = merge_try(alloc_tables(*M, bsh::layout_tables(want), M->tables, 0))) return rc2;
+            if (int32_t rc2 = merge_try(M->mem.alloc(&M->d_tables, (size_t)P3 * sizeof(IngestTable)))) return rc2;
+            if (int32_t rc2 = merge_try(M->mem.alloc(&M->d_counts, (size_t)P3 * 4))) return rc2;
+            if (int32_t rc2 = merge_try(M->mem.alloc(&M->d_status, (size_t)P3 * 4))) return rc2;
+            if (int32_t rc2 = merge_try(hipMemsetAsync(M->d_counts, 0, (size_t)P3 * 4, H.stream))) return rc2;
+            if (int32_t rc2 = merge_try(hipMemsetAsync(M->d_status, 0, (size_t)P3 * 4, H.stream))) return rc2;
+            // sources: part 0's partial tables in place, every other part's dense copy
+            std::vector<IngestTable> src((size_t)np * P3, IngestTable{nullptr, nullptr, 0, 0});
+            std::vector<bsg::UnionItem> items;
+            for (uint32_t t = 0; t < P3; ++t) {
+                src[t] = I.parts[0]->tables[I.parts[0]->n_sets * 3 + t];
+                if (I.parts[0]->counts[I.parts[0]->n_sets * 3 + t]) items.push_back({t, t});
+                for (uint32_t q = 1; q < np; ++q) {
+                    const Dense &x = dense[(size_t)q * P3 + t];
+                    if (!x.n) continue;
+                    void *cp = nullptr;
+                    if (int32_t rc2 = merge_try(copies.alloc(&cp, (uint64_t)x.n * kSlotBytes))) return rc2;
+                    if (int32_t rc2 = merge_try(peer_copy(ctx, dev_index(ctx, &H), cp, dev_index(ctx, x.dev), x.buf, (uint64_t)x.n * kSlotBytes, H.stream))) return rc2;
+                    src[(size_t)q * P3 + t] = as_table(bsh::place_table(cp, 0, x.n, x.n, true));
+                    items.push_back({q * P3 + t, t});
+                }
             }
-        }
-        IngestTable *d_src = nullptr;
-        bsg::UnionItem *d_items = nullptr;
-        if (e == hipSuccess) e = copies.alloc(&d_src, src.size() * sizeof(IngestTable));
-        if (e == hipSuccess) e = copies.alloc(&d_items, std::max<size_t>(items.size(), 1) * sizeof(bsg::UnionItem));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_src, src.data(), src.size() * sizeof(IngestTable), hipMemcpyHostToDevice, H.stream);
-        if (e == hipSuccess && !items.empty()) e = hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::UnionItem), hipMemcpyHostToDevice, H.stream);
-        if (e != hipSuccess) { rc = fail(e == hipErrorOutOfMemory ? BSG_E_NOMEM : BSG_E_HIP, "parent merge: %s", hipGetErrorString(e)); }
-        if (!rc) rc = push_tables(*M);
-        if (!rc) {
-            if (!items.empty())
-                rc = run_until_fits(*M, 0, P3, &I.ms_merge, [&](hipEvent_t e0, hipEvent_t e1) -> int32_t {
+            IngestTable *d_src = nullptr;
+            bsg::UnionItem *d_items = nullptr;
+            if (int32_t rc2 = merge_try(copies.alloc(&d_src, src.size() * sizeof(IngestTable)))) return rc2;
+            if (int32_t rc2 = merge_try(copies.alloc(&d_items, std::max<size_t>(items.size(), 1) * sizeof(bsg::UnionItem)))) return rc2;
+            if (int32_t rc2 = merge_try(hipMemcpyAsync(d_src, src.data(), src.size() * sizeof(IngestTable), hipMemcpyHostToDevice, H.stream))) return rc2;
+            if (!items.empty()) if (int32_t rc2 = merge_try(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(bsg::UnionItem), hipMemcpyHostToDevice, H.stream))) return rc2;
+            if (int32_t rc2 = push_tables(*M)) return rc2;
+            if (items.empty()) { if (int32_t rc2 = read_state(*M)) return rc2; }
+            else if (int32_t rc2 = run_until_fits(*M, 0, P3, &I.ms_merge, [&](hipEvent_t e0, hipEvent_t e1) -> int32_t {
                     hipExtLaunchKernelGGL(bsg::k_ingest_union, dim3(64, (uint32_t)items.size()), dim3(256), 0, H.stream, e0, e1, 0,
                                           (const IngestTable *)d_src, (const IngestTable *)M->d_tables, (const bsg::UnionItem *)d_items, M->d_counts, M->d_status);
                     return BSG_OK;
-                });
-            else rc = read_state(*M);
-        }
-        if (!rc) {
+                })) return rc2;
             // a partial that was flagged (an unrepresentable entry, a hash-equal pair) flags the merged parent too
             for (uint32_t t = 0; t < P3; ++t)
                 for (uint32_t q = 0; q < np; ++q) M->status[t] = std::max(M->status[t], I.parts[q]->status[I.parts[q]->n_sets * 3 + t]);
             M->finished = true;
             copies.done();                 // run_until_fits / read_state return synchronised
             M->mem.done();
-        } else {
-            free_part(*M);                 // (under H's lock)
-        }
+            return BSG_OK;
+        }();
+        if (rc) free_part(*M);             // (under H's lock)
     }
-    drop_dense();
+    // whatever happened above, the dense lists leave their devices here, each under its own device's lock
+    for (Dense &x : dense) if (x.buf) { std::lock_guard<std::mutex> lk(x.dev->mu); (void)hipSetDevice(x.dev->id); x.dev->pool.free(x.buf); }
     if (rc) return rc;
     I.merged = M;
     return BSG_OK;
 }
+
+// What bsh::check_rows / check_set_first / check_parents found, refused in the words of the entry points
+int32_t refuse(const bsh::RowCheck &c)
+{
+    switch (c.fault) {
+    case bsh::RowFault::None: return BSG_OK;
+    case bsh::RowFault::OffsetsNotMonotone: return fail(BSG_E_INVALID, "row_off not monotone at %u", c.at);
+    case bsh::RowFault::BytesMissing: return fail(BSG_E_INVALID, "rows is null");
+    case bsh::RowFault::SetFirstSpan: return fail(BSG_E_INVALID, "set_first_row must span [0, n_rows]");
+    case bsh::RowFault::SetFirstNotMonotone: return fail(BSG_E_INVALID, "set_first_row not monotone at %u", c.at);
+    case bsh::RowFault::ParentsMissing: return fail(BSG_E_INVALID, "parent_of_set is null");
+    default: return fail(BSG_E_INVALID, "parent_of_set[%u] out of range", c.at);
+    }
+}
+int32_t check_parents(const uint32_t *parent_of_set, uint32_t n_sets, uint32_t n_parents) { return refuse(bsh::check_parents(parent_of_set, n_sets, n_parents)); }
+int32_t check_table_count(uint64_t n) { return bsh::too_many_tables(n) ? fail(BSG_E_INVALID, "too many sets and parents") : BSG_OK; }
+// the ingest's own record of its one part's sets, after sets were added to the part
+void sync_sets(Ingest &I, const IngestPart &G) { I.n_sets = G.n_sets; I.parent_of_set = G.parent_of_set; I.set_cut = {0, I.n_sets}; }
 
 // bsg_ingest_rows (tok_in NULL) and bsg_ingest_rows_tok
 int32_t ingest_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_off, uint32_t n_rows,
@@ -838,16 +831,10 @@ int32_t ingest_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_
     if (int32_t rc = tok_spec(tok_in, rec, spec, is_default)) return rc;
     const bsg::TokSpec *tok = is_default ? nullptr : &spec;
     if (!out_ingest_id || !row_off || !set_first_row || n_sets == 0) return fail(BSG_E_INVALID, "null argument or no sets");
-    if (set_first_row[0] != 0 || set_first_row[n_sets] != n_rows) return fail(BSG_E_INVALID, "set_first_row must span [0, n_rows]");
-    for (uint32_t s = 0; s < n_sets; ++s)
-        if (set_first_row[s + 1] < set_first_row[s]) return fail(BSG_E_INVALID, "set_first_row not monotone at %u", s);
-    for (uint32_t r = 0; r < n_rows; ++r)
-        if (row_off[r + 1] < row_off[r]) return fail(BSG_E_INVALID, "row_off not monotone at %u", r);
+    if (int32_t rc = refuse(bsh::check_set_first(set_first_row, n_sets, n_rows))) return rc;
+    if (int32_t rc = refuse(bsh::check_rows(row_off, n_rows, rows != nullptr))) return rc;
+    if (int32_t rc = check_parents(parent_of_set, n_sets, n_parents)) return rc;
     const uint64_t n_bytes = row_off[n_rows];
-    if (n_bytes && !rows) return fail(BSG_E_INVALID, "rows is null");
-    if (n_parents && !parent_of_set) return fail(BSG_E_INVALID, "parent_of_set is null");
-    for (uint32_t s = 0; s < n_sets && parent_of_set; ++s)
-        if (parent_of_set[s] != 0xFFFFFFFFu && parent_of_set[s] >= n_parents) return fail(BSG_E_INVALID, "parent_of_set[%u] out of range", s);
 
     auto I = std::make_shared<Ingest>();
     I->n_rows = n_rows; I->n_sets = n_sets; I->n_parents = n_parents;
@@ -908,8 +895,6 @@ int32_t ingest_rows_call(bsg_ctx *ctx, const uint8_t *rows, const uint64_t *row_
 // sets' (the caller's numbering "sets, then parents" holds at every moment; a parent's table index is (n_sets + p) * 3 + kind
 // with the n_sets of the time).
 
-constexpr uint32_t kStreamFieldSlots = 256, kStreamTokenSlots = 1024;   // no row count is known when a set is made
-
 // n_more empty sets behind the existing ones.  Caller holds the device lock and has made the device current.
 int32_t stream_add_sets(IngestPart &G, uint32_t n_more, const uint32_t *parent_of_new_set, const uint32_t *slots_hint)
 {
@@ -919,24 +904,13 @@ int32_t stream_add_sets(IngestPart &G, uint32_t n_more, const uint32_t *parent_o
     std::copy(G.tables.begin(), G.tables.begin() + (size_t)old_sets * 3, tables.begin());
     std::copy(G.tables.begin() + (size_t)old_sets * 3, G.tables.end(), tables.begin() + (size_t)new_sets * 3);   // the parents' placeholders
     if (n_more) {
-        uint64_t total_slots = 0;
-        std::vector<uint64_t> first_slot((size_t)n_more * 3), cap((size_t)n_more * 3);
-        for (size_t i = 0; i < cap.size(); ++i) {
-            uint64_t want = i % 3 == 0 ? kStreamFieldSlots : kStreamTokenSlots;
-            if (slots_hint && slots_hint[i]) want = slots_hint[i];
-            cap[i] = pow2_at_least(want);
-            first_slot[i] = total_slots;
-            total_slots += cap[i];
-        }
-        void *chunk = nullptr;
-        HIP_TRY(G.mem.alloc(&chunk, total_slots * kSlotBytes));
-        G.slot_bytes += total_slots * kSlotBytes;
-        HIP_TRY(hipMemsetAsync(chunk, 0, total_slots * kSlotBytes, d.stream));
-        for (size_t i = 0; i < cap.size(); ++i) tables[(size_t)old_sets * 3 + i] = make_table(chunk, first_slot[i], total_slots, cap[i]);
+        std::vector<uint64_t> want((size_t)n_more * 3);
+        for (size_t i = 0; i < want.size(); ++i) want[i] = bsh::stream_slots(i % 3, slots_hint ? slots_hint[i] : 0);
+        HIP_TRY(alloc_tables(G, bsh::layout_tables(want), tables, (size_t)old_sets * 3));
     }
     if (nt > G.table_cap || !G.d_tables) {
         // room for twice as many: partitions keep showing up.  The sets' counters travel; everything behind them is zero.
-        const uint32_t room = std::max<uint32_t>(96, nt > 0x7FFFFFFFu ? nt : nt * 2);
+        const uint32_t room = bsh::descriptor_room(nt);
         IngestTable *nd_tables = nullptr;
         uint32_t *nd_counts = nullptr, *nd_status = nullptr;
         HIP_TRY(G.mem.alloc(&nd_tables, (size_t)room * sizeof(IngestTable)));
@@ -960,14 +934,6 @@ int32_t stream_add_sets(IngestPart &G, uint32_t n_more, const uint32_t *parent_o
     return BSG_OK;
 }
 
-int32_t check_parents(const uint32_t *parent_of_set, uint32_t n_sets, uint32_t n_parents)
-{
-    if (n_sets && n_parents && !parent_of_set) return fail(BSG_E_INVALID, "parent_of_set is null");
-    for (uint32_t s = 0; s < n_sets && parent_of_set; ++s)
-        if (parent_of_set[s] != 0xFFFFFFFFu && parent_of_set[s] >= n_parents) return fail(BSG_E_INVALID, "parent_of_set[%u] out of range", s);
-    return BSG_OK;
-}
-
 int32_t ingest_open_call(bsg_ctx *ctx, uint32_t n_sets, const uint32_t *parent_of_set, uint32_t n_parents, const uint32_t *slots_hint,
                          uint32_t flags, const bsg_tokenizer *tok_in, uint64_t *out_ingest_id, const bsg::MinMaxFields *mm = nullptr,
                          std::unique_ptr<PartitionKeys> keyed = nullptr)
@@ -978,7 +944,7 @@ int32_t ingest_open_call(bsg_ctx *ctx, uint32_t n_sets, const uint32_t *parent_o
     if (int32_t rc = tok_spec(tok_in, I->tok, I->spec, I->tok_default)) return rc;
     if (!out_ingest_id) return fail(BSG_E_INVALID, "null argument");
     if (flags & ~BSG_INGEST_TRUSTED_JSON) return fail(BSG_E_INVALID, "unknown flags 0x%x", flags);
-    if ((uint64_t)n_sets + n_parents > 0xFFFFFFFFu / 3) return fail(BSG_E_INVALID, "too many sets and parents");
+    if (int32_t rc = check_table_count((uint64_t)n_sets + n_parents)) return rc;
     if (int32_t rc = check_parents(parent_of_set, n_sets, n_parents)) return rc;
     I->streaming = true;
     I->flags = flags;
@@ -994,13 +960,8 @@ int32_t ingest_open_call(bsg_ctx *ctx, uint32_t n_sets, const uint32_t *parent_o
         std::lock_guard<std::mutex> lk(d.mu);
         rc = [&]() -> int32_t {
             if (int32_t rc2 = use_device(d)) return rc2;
-            // a parent table is a 64-slot placeholder nothing inserts into until the finish step sizes it from its children
-            if (n_parents) {
-                void *ph = nullptr;
-                HIP_TRY(G.mem.alloc(&ph, 64 * kSlotBytes));
-                HIP_TRY(hipMemsetAsync(ph, 0, 64 * kSlotBytes, d.stream));
-                G.tables.assign((size_t)n_parents * 3, make_table(ph, 0, 64, 64));
-            }
+            G.tables.assign((size_t)n_parents * 3, IngestTable{nullptr, nullptr, 0, 0});
+            if (n_parents) HIP_TRY(alloc_placeholder(G, G.tables, 0));
             HIP_TRY(G.mem.alloc(&G.d_nfb, 128));
             if (int32_t rc2 = stream_add_sets(G, n_sets, parent_of_set, slots_hint)) return rc2;
             G.mem.done();                  // stream_add_sets returns synchronised
@@ -1008,9 +969,7 @@ int32_t ingest_open_call(bsg_ctx *ctx, uint32_t n_sets, const uint32_t *parent_o
         }();
     }
     if (rc) { free_ingest(*I); return rc; }
-    I->n_sets = n_sets;
-    I->parent_of_set = G.parent_of_set;
-    I->set_cut = {0, n_sets};
+    sync_sets(*I, G);
     std::lock_guard<std::shared_mutex> lk2(ctx->mu);
     const uint64_t id = ctx->next_id++;
     ctx->ingests[id] = I;
@@ -1163,12 +1122,10 @@ int32_t partition_batch(bsg_ctx *ctx, Ingest &I, IngestPart &G, Scratch &scratch
     std::sort(by_row.begin(), by_row.end(), [&](uint32_t x, uint32_t y) { return fresh_row[x] < fresh_row[y]; });
     for (uint32_t i = 0; i < n_new; ++i) rank[by_row[i]] = i;
     if (n_new) {
-        if ((uint64_t)old_sets + n_new + I.n_parents > 0xFFFFFFFFu / 3) return fail(BSG_E_INVALID, "too many sets and parents");
+        if (int32_t rc = check_table_count((uint64_t)old_sets + n_new + I.n_parents)) return rc;
         const std::vector<uint32_t> parent(n_new, K.parent);
         if (int32_t rc = stream_add_sets(G, n_new, parent.data(), nullptr)) return rc;     // (K.dirty: the next call sends the dictionary of K.keys again)
-        I.n_sets = G.n_sets;
-        I.parent_of_set = G.parent_of_set;
-        I.set_cut = {0, I.n_sets};
+        sync_sets(I, G);
         for (uint32_t i = 0; i < n_new; ++i) {
             K.set_of_key.emplace(fresh[by_row[i]], (uint32_t)K.keys.size());
             K.keys.push_back(fresh[by_row[i]]);
@@ -1204,86 +1161,45 @@ int32_t append_rows_stream(bsg_ctx *ctx, Ingest &I, const uint8_t *rows, const u
 {
     IngestPart &G = *I.parts[0];
     Device &d = *G.dev;
-    const uint64_t n_bytes = row_off[n_rows];
     const char *call = kc ? "bsg_ingest_append_rows_keyed" : "bsg_ingest_append_rows";
     const LabTrace trace{call, d.id};
     d.calls.fetch_add(1, std::memory_order_relaxed);
     std::lock_guard<std::mutex> lk(d.mu);
     if (int32_t rc = use_device(d)) return rc;
-    Scratch scratch(d);                    // the row bytes, their offsets, the walking order and the fallback list: this call's only
-    uint8_t *d_rows = nullptr;
-    uint64_t *d_row_off = nullptr;
-    uint32_t *d_fb = nullptr, *d_order = nullptr, *d_set_of_order = nullptr;
-    HIP_TRY(scratch.alloc(&d_rows, n_bytes + 64));
-    HIP_TRY(scratch.alloc(&d_row_off, ((size_t)n_rows + 1) * 8));
-    HIP_TRY(scratch.alloc(&d_fb, (size_t)n_rows * 4));
-    HIP_TRY(scratch.alloc(&d_order, (size_t)n_rows * 4));
-    HIP_TRY(scratch.alloc(&d_set_of_order, (size_t)n_rows * 4));
-    trace.lap("device buffers allocated");
-    HIP_TRY(hipMemsetAsync(d_rows + n_bytes, 0, 64, d.stream));
-    HIP_TRY(hipMemcpyAsync(d_row_off, row_off, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemsetAsync(G.d_nfb, 0, 128, d.stream));
-    std::vector<uint32_t> part_sets, kept, kept_sets;      // (keyed) every row's set, the rows to walk and their sets
+    RowWalk w(ctx, G, trace, row_off, n_rows);
+    uint32_t *d_order = nullptr, *d_set_of_order = nullptr;       // the walking order: this call's only, like the row bytes
+    if (int32_t rc = w.buffers()) return rc;
+    HIP_TRY(w.scratch.alloc(&d_order, (size_t)n_rows * 4));
+    HIP_TRY(w.scratch.alloc(&d_set_of_order, (size_t)n_rows * 4));
+    std::vector<uint32_t> part_sets, kept, kept_sets, fb;  // (keyed) every row's set, the rows to walk and their sets; the rows handed back
     float ms_partition = 0.f;
     uint32_t n_walk = n_rows;
     if (kc) {
-        if (int32_t rc = partition_batch(ctx, I, G, scratch, rows, row_off, n_rows, d_rows, d_row_off, *kc, part_sets, kept, kept_sets, &ms_partition)) return rc;
+        if (int32_t rc = partition_batch(ctx, I, G, w.scratch, rows, row_off, n_rows, w.d_rows, w.d_row_off, *kc, part_sets, kept, kept_sets, &ms_partition)) return rc;
         trace.lap("rows partitioned");
         set_of_row = kept_sets.data();
         n_walk = (uint32_t)kept.size();
-    }
-    bsg::IngestArgs a{};
-    a.rows = d_rows; a.row_off = d_row_off;
-    a.counts = G.d_counts; a.status = G.d_status; a.fallback_rows = d_fb; a.n_fallback = G.d_nfb;
-    a.n_rows = n_rows; a.n_sets = G.n_sets; a.validate = (I.flags & BSG_INGEST_TRUSTED_JSON) ? 0u : 1u;
-    a.key = ctx->fp_key;
-    if (int32_t rc = ensure_lower_table(d)) return rc;
-    a.lower = d.d_lower;
+        for (uint32_t r = 0; r < n_rows; ++r) if (part_sets[r] == bsg::kPkeyUndecided) fb.push_back(r);       // not walked: handed back here
+        w.up.emplace(d, n_walk);           // the bytes are resident: positions [0, n_walk) of the walking order, one chunk
+    } else w.up.emplace(d, rows, w.d_rows, row_off, n_rows, ctx->ingest_chunk_bytes);
     const bsg::RowsBySet by_set{d_order, d_set_of_order};
-    MinMaxWalk mmw(G);
-    if (int32_t rc = mmw.prepare(scratch, a, n_rows, &by_set)) return rc;
     std::vector<uint32_t> order(n_walk), set_of_order(n_walk), group_scratch;
-    std::optional<RowUpload> up_box;
-    if (kc) up_box.emplace(d, n_walk);     // the bytes are resident: positions [0, n_walk) of the walking order, one chunk
-    else up_box.emplace(d, rows, d_rows, row_off, n_rows, ctx->ingest_chunk_bytes);
-    RowUpload &up = *up_box;
-    if (n_walk)
-    if (int32_t rc = walk_chunks(d, G, up, a, G.n_sets * 3, trace,
-            [&](uint32_t c) -> hipError_t {   // the chunk's walking order lands with its bytes
-                const uint32_t rf = up.cuts[c], re = up.cuts[c + 1];
+    if (int32_t rc = w.walk(I.flags, I.tok_default ? nullptr : &I.spec, &by_set,
+            [&](uint32_t rf, uint32_t re, hipStream_t cs) -> hipError_t {   // the chunk's walking order lands with its bytes
                 bsh::group_rows_by_set(set_of_row, rf, re, G.n_sets, order.data(), set_of_order.data(), group_scratch);
                 if (kc) for (uint32_t i = rf; i < re; ++i) order[i] = kept[order[i]];      // positions among the kept rows -> rows of the batch
-                hipError_t e = hipMemcpyAsync(d_order + rf, order.data() + rf, (size_t)(re - rf) * 4, hipMemcpyHostToDevice, up.cs);
-                if (e == hipSuccess) e = hipMemcpyAsync(d_set_of_order + rf, set_of_order.data() + rf, (size_t)(re - rf) * 4, hipMemcpyHostToDevice, up.cs);
+                hipError_t e = hipMemcpyAsync(d_order + rf, order.data() + rf, (size_t)(re - rf) * 4, hipMemcpyHostToDevice, cs);
+                if (e == hipSuccess) e = hipMemcpyAsync(d_set_of_order + rf, set_of_order.data() + rf, (size_t)(re - rf) * 4, hipMemcpyHostToDevice, cs);
                 return e;
-            },
-            [&](const bsg::IngestArgs &b, uint32_t grid, hipEvent_t e0, hipEvent_t e1) {
-                if (!I.tok_default && I.spec.ngram)
-                    hipExtLaunchKernelGGL(bsg::k_ingest_rows_sets_gram, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, by_set, I.spec);
-                else if (!I.tok_default)
-                    hipExtLaunchKernelGGL(bsg::k_ingest_rows_sets_tok, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, by_set, I.spec);
-                else
-                    hipExtLaunchKernelGGL(bsg::k_ingest_rows_sets, dim3(grid), dim3(bsg::kIngestThreads), bsg::kIngestLdsBytes, d.stream, e0, e1, 0, b, by_set);
-            },
-            [&](uint32_t, uint32_t rf, uint32_t re) { return mmw.launch(rf, re); })) return rc;
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    if (d.copy_stream) HIP_TRY(hipStreamSynchronize(d.copy_stream));
-    trace.lap("all chunks walked");
-    uint32_t nfb = 0;
-    HIP_TRY(hipMemcpy(&nfb, G.d_nfb, 4, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> fb(nfb);
-    if (nfb) HIP_TRY(hipMemcpy(fb.data(), d_fb, (size_t)nfb * 4, hipMemcpyDeviceToHost));
-    if (kc) for (uint32_t r = 0; r < n_rows; ++r) if (part_sets[r] == bsg::kPkeyUndecided) fb.push_back(r);     // merge_fallback sorts: ascending, each row once
-    std::sort(fb.begin(), fb.end());
-    if (int32_t rc = mmw.merge_fallback(fb)) return rc;
-    if (kc) { std::sort(fb.begin(), fb.end()); fb.erase(std::unique(fb.begin(), fb.end()), fb.end()); }        // (an ingest without fields: merge_fallback did nothing)
-    nfb = (uint32_t)fb.size();
+            }, fb)) return rc;
+    if (kc) fb.erase(std::unique(fb.begin(), fb.end()), fb.end());      // (keyed: ascending, each row once, also without fields)
+    const uint32_t nfb = (uint32_t)fb.size();
     {
         std::lock_guard<std::shared_mutex> lk2(ctx->mu);
         ctx->last_minmax_ms = G.ms_minmax;
         if (kc) ctx->last_partition_ms = ms_partition;
     }
-    scratch.done();                        // both streams have been synchronised: the row bytes leave the device here
+    w.scratch.done();                      // both streams have been synchronised: the row bytes leave the device here
     *n_fallback = nfb;
     // a call that could not deliver its list is appended again (or walked on the host): its rows are counted by the call that does
     const bool count_only = !out_fallback_rows && fallback_cap == 0;
@@ -1293,7 +1209,7 @@ int32_t append_rows_stream(bsg_ctx *ctx, Ingest &I, const uint8_t *rows, const u
     G.n_rows += n_rows;
     I.n_rows += n_rows;
     G.stats.n_rows += n_rows;
-    G.stats.row_bytes += n_bytes;
+    G.stats.row_bytes += row_off[n_rows];
     G.stats.n_fallback_rows += nfb;
     if (nfb) memcpy(out_fallback_rows, fb.data(), (size_t)nfb * 4);
     return BSG_OK;
@@ -1402,7 +1318,7 @@ int32_t bsg_ingest_add_sets(bsg_ctx *ctx, uint64_t ingest_id, uint32_t n_more, c
     if (int32_t rc = get_open_stream(ctx, ingest_id, g, "bsg_ingest_add_sets")) return rc;
     Ingest &I = *g;
     if (I.keyed) return fail(BSG_E_INVALID, "bsg_ingest_add_sets: ingest %llu is keyed, every set of it has a text (bsg_ingest_add_sets_keyed)", (unsigned long long)ingest_id);
-    if ((uint64_t)I.n_sets + n_more + I.n_parents > 0xFFFFFFFFu / 3) return fail(BSG_E_INVALID, "too many sets and parents");
+    if (int32_t rc = check_table_count((uint64_t)I.n_sets + n_more + I.n_parents)) return rc;
     if (int32_t rc = check_parents(parent_of_new_set, n_more, I.n_parents)) return rc;
     *out_first_new_set = I.n_sets;
     if (n_more == 0) return BSG_OK;
@@ -1412,9 +1328,7 @@ int32_t bsg_ingest_add_sets(bsg_ctx *ctx, uint64_t ingest_id, uint32_t n_more, c
         if (int32_t rc = use_device(*G.dev)) return rc;
         if (int32_t rc = stream_add_sets(G, n_more, parent_of_new_set, slots_hint_new)) return rc;
     }
-    I.n_sets = G.n_sets;
-    I.parent_of_set = G.parent_of_set;
-    I.set_cut = {0, I.n_sets};
+    sync_sets(I, G);
     return BSG_OK;
 }
 
@@ -1428,9 +1342,7 @@ int32_t bsg_ingest_append_rows(bsg_ctx *ctx, uint64_t ingest_id, const uint8_t *
     *out_n_fallback = 0;
     if (n_rows == 0) return BSG_OK;
     if (!row_off || !set_of_row || (!out_fallback_rows && fallback_cap)) return fail(BSG_E_INVALID, "null argument");
-    for (uint32_t r = 0; r < n_rows; ++r)
-        if (row_off[r + 1] < row_off[r]) return fail(BSG_E_INVALID, "row_off not monotone at %u", r);
-    if (row_off[n_rows] && !rows) return fail(BSG_E_INVALID, "rows is null");
+    if (int32_t rc = refuse(bsh::check_rows(row_off, n_rows, rows != nullptr))) return rc;
     if (const uint32_t bad = bsh::first_bad_set(set_of_row, n_rows, g->n_sets); bad < n_rows)
         return fail(BSG_E_INVALID, "set_of_row[%u] = %u, the ingest has %u sets", bad, set_of_row[bad], g->n_sets);
     return append_rows_stream(ctx, *g, rows, row_off, n_rows, set_of_row, out_fallback_rows, fallback_cap, out_n_fallback);
@@ -1470,9 +1382,7 @@ int32_t bsg_ingest_append_rows_keyed(bsg_ctx *ctx, uint64_t ingest_id, const uin
     *out_n_new_sets = 0;
     if (n_rows == 0) return BSG_OK;
     if (!row_off || !out_set_of_row || (!out_fallback_rows && fallback_cap)) return fail(BSG_E_INVALID, "null argument");
-    for (uint32_t r = 0; r < n_rows; ++r)
-        if (row_off[r + 1] < row_off[r]) return fail(BSG_E_INVALID, "row_off not monotone at %u", r);
-    if (row_off[n_rows] && !rows) return fail(BSG_E_INVALID, "rows is null");
+    if (int32_t rc = refuse(bsh::check_rows(row_off, n_rows, rows != nullptr))) return rc;
     uint32_t mask = 0;
     { std::shared_lock<std::shared_mutex> lk(ctx->mu); mask = ctx->partition_hash_mask; }
     const KeyedCall kc{out_set_of_row, out_n_new_sets, mask};
@@ -1506,7 +1416,7 @@ int32_t bsg_ingest_add_sets_keyed(bsg_ctx *ctx, uint64_t ingest_id, const uint8_
     if (fresh.empty()) return BSG_OK;
     if ((uint64_t)I.n_sets + fresh.size() > BSG_PARTITION_MAX_SETS)
         return fail(BSG_E_INVALID, "bsg_ingest_add_sets_keyed: %u sets and %zu new keys exceed BSG_PARTITION_MAX_SETS (%u)", I.n_sets, fresh.size(), BSG_PARTITION_MAX_SETS);
-    if ((uint64_t)I.n_sets + fresh.size() + I.n_parents > 0xFFFFFFFFu / 3) return fail(BSG_E_INVALID, "too many sets and parents");
+    if (int32_t rc = check_table_count((uint64_t)I.n_sets + fresh.size() + I.n_parents)) return rc;
     IngestPart &G = *I.parts[0];
     {
         std::lock_guard<std::mutex> lk(G.dev->mu);
@@ -1514,9 +1424,7 @@ int32_t bsg_ingest_add_sets_keyed(bsg_ctx *ctx, uint64_t ingest_id, const uint8_
         const std::vector<uint32_t> parent(fresh.size(), K.parent);
         if (int32_t rc = stream_add_sets(G, (uint32_t)fresh.size(), parent.data(), nullptr)) return rc;
     }
-    I.n_sets = G.n_sets;
-    I.parent_of_set = G.parent_of_set;
-    I.set_cut = {0, I.n_sets};
+    sync_sets(I, G);
     for (std::string &t : fresh) {
         K.set_of_key.emplace(t, (uint32_t)K.keys.size());
         K.keys.push_back(std::move(t));

@@ -566,11 +566,9 @@ struct WidePart {
         b.code = d_code; b.fallback_rows = d_hfb; b.n_fallback = d_nhfb;
         b.origin = ho.origin; b.width = ho.width; b.n_buckets = ho.n_buckets; b.n_sets = n_sets;
         b.row_first = rf; b.row_end = rf + a.n_rows;
-        const uint64_t n = a.n_rows, max_waves = (uint64_t)p.d.n_cus * 4 * 8;
-        const uint64_t waves = std::min<uint64_t>((n + 63) / 64, max_waves);
-        b.rows_per_wave = (uint32_t)(((n + waves - 1) / waves + 63) / 64 * 64);
-        const uint64_t used = (n + b.rows_per_wave - 1) / b.rows_per_wave, wpw = bsg::kBucketThreads / 64;
-        const dim3 grid((uint32_t)((used + wpw - 1) / wpw)), block(bsg::kBucketThreads);
+        const bsh::WaveRuns runs = bsh::wave_runs(a.n_rows, p.d.n_cus, 8, bsg::kBucketThreads);
+        b.rows_per_wave = runs.rows_per_wave;
+        const dim3 grid(runs.grid), block(bsg::kBucketThreads);
         if (n_sets == 1) hipExtLaunchKernelGGL(bsg::k_bucket_rows, grid, block, 0, p.d.stream, hev.v[k], hev.v[k + 1], 0, b, ho.field);
         else hipExtLaunchKernelGGL(bsg::k_bucket_rows_sets, grid, block, 0, p.d.stream, hev.v[k], hev.v[k + 1], 0, b, ho.field);
     }

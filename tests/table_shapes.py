@@ -79,10 +79,10 @@ MAX_PROBE = K["kMaxProbe"]
 PART_SLOTS, PART_FILL, PART_TARGET = K["kPartSlots"], K["kPartFill"], K["kPartTarget"]
 PART_THREADS, PART_PROBES, PART_AHEAD = K["kPartThreads"], K["kPartProbes"], K["kPartAhead"]
 CACHE_SETS = K["BSG_INGEST_CACHE_SETS"]
-MIN_CAP = 64                 # pow2_at_least (ingest_api.inc): a hint is rounded up to a power of two, 64 at least
-GROWTH = 4                   # grow_overflowed (ingest_api.inc): an overflowed table gets four times its slots
-# capacities where the caller gives no hint: ingest_rows_part (fields 256; tokens and field::tokens max(1024, 4 x rows)) and
-# stream_add_sets (kStreamFieldSlots, kStreamTokenSlots)
+MIN_CAP = 64                 # pow2_at_least (host/ingest_plan.hpp): a hint is rounded up to a power of two, 64 at least
+GROWTH = 4                   # grown_slots (host/ingest_plan.hpp; grow_overflowed in ingest_api.inc): an overflowed table gets four times its slots
+# capacities where the caller gives no hint (host/ingest_plan.hpp): oneshot_slots for ingest_rows_part (fields 256; tokens and
+# field::tokens max(1024, 4 x rows)) and stream_slots for stream_add_sets (256 and 1024)
 DEFAULT_FIELD_SLOTS, DEFAULT_TOKEN_SLOTS = 256, 1024
 KIND_FIELD, KIND_TOKEN, KIND_FT = 0, 1, 2
 KEY_SHARD_MIN_ROW_BYTES, KEY_UNION_MODE, KEY_UNION_COARSEN = 8, 9, 10     # bsg_set_lab keys

@@ -105,11 +105,11 @@ def test_bytes_route_equals_the_oracle(ctx, name):
 
 # ---- tables route: bsg_ingest_build with caller-chosen geometries ----
 
-# (rows, slots_hint of the token table): its capacity is pow2_at_least(hint) (ingest_api.inc, ingest_rows_part), and stays that while no table
+# (rows, slots_hint of the token table): its capacity is pow2_at_least(hint) (host/ingest_plan.hpp, layout_tables), and stays that while no table
 # grows — the test asserts table_grows == 0 and the table bytes the three capacities come to
 TABLE_CLASSES = {"below-one-tile": (100, T // 2), "whole-tiles": (500, 2 * T), "beyond-one-slice": (500, 16 * T)}
 TABLE_GEOMETRIES = (B.TABLES_LDS_BITS, B.TABLES_LDS_BITS + 1, 3 * W, 3 * W + 1)
-SLOT_BYTES = 40                                                               # ingest_api.inc kSlotBytes
+SLOT_BYTES = 40                                                               # host/ingest_plan.hpp kSlotBytes
 
 
 @pytest.mark.parametrize("table_class", list(TABLE_CLASSES))

@@ -1,7 +1,7 @@
 """The chunk plan of the row upload on the host (no GPU): tests/row_chunks_check.cpp, built with plain g++ against
 bloomsearch_amd/csrc/host/row_chunks.hpp — the code RowUpload (bloomgpu.hip) cuts and copies the rows of bsg_ingest_rows and
-bsg_match_rows by.  Reference: the two loops that header replaced, restated below from ingest_rows_part (ingest_api.inc) and
-match_rows_on (match_api.inc) as they stood when each path still planned its own chunks.  On top of the comparison, what the
+bsg_match_rows by.  Reference: the two loops that header replaced, restated below from ingest_rows_part (ingest_api.inc; the walk is
+RowWalk's there now) and match_rows_on (match_api.inc) as they stood when each path still planned its own chunks.  On top of the comparison, what the
 kernels rely on is asserted by itself: chunks are whole 256-row workgroups, the byte ranges of successive copies are disjoint (no
 copy rewrites a byte a running kernel may read) and each reaches through the aligned 8-byte word that holds its last row's last
 byte (the walker reads whole words)."""

@@ -10,7 +10,9 @@ bsg_ingest_stats), the total wall of all calls, and table_grows.  Walls are host
 The legs alternate inside one process, one untimed warm-up round first, R timed rounds; every figure is the median of the
 rounds, the spread (min .. max) of the total wall beside it.  Both legs must count the same distinct entries, or the tool fails.
 
-    python tools/ingest_stream_lab.py [n_rows] [rounds]
+--lib PATH runs the same script against a library built from another commit on the same box.
+
+    python tools/ingest_stream_lab.py [n_rows] [rounds] [--lib PATH]
 """
 import os
 import sys
@@ -19,12 +21,18 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bloomsearch_amd import _lib, synth  # noqa: E402
+from bloomsearch_amd import _lib  # noqa: E402
+
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+if "--lib" in sys.argv:
+    _lib.LIB_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
+    args.remove(sys.argv[sys.argv.index("--lib") + 1])
+from bloomsearch_amd import synth  # noqa: E402
 from bloomsearch_amd.gpu import Context  # noqa: E402
 
 N_SETS = 16
-n_rows = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
-rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+n_rows = int(args[0]) if len(args) > 0 else 1_000_000
+rounds = int(args[1]) if len(args) > 1 else 5
 per_set = n_rows // N_SETS
 n_rows = per_set * N_SETS
 
@@ -79,6 +87,7 @@ def leg_stream(ctx, bs):
 
 
 def main():
+    print("# library %s" % _lib.LIB_PATH)
     print("# python tools/ingest_stream_lab.py %d %d — synth log rows, %d sets of %d rows, one parent, BSG_INGEST_TRUSTED_JSON;\n"
           "# %.1f MB of row bytes; legs alternate in one process, 1 warm-up round + %d timed rounds, medians (total wall: min .. max)"
           % (n_rows, rounds, N_SETS, per_set, int(grouped[1][-1]) / 1e6, rounds))
